@@ -7,8 +7,13 @@ log-likelihood of the same candidates ('walk' primitive: L=40, F=156, K=8; BASEL
 configs[1] per GPU).  With N > 1 ranks the candidate batch is sharded 8192 per GPU (configs[3])
 and every step ends with the RCCL all-gather of the scores.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config walk|graph|optimizer]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR] [--config walk|graph|optimizer]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...   (the driver's form)
+
+A plain run does only what the headline needs: set-up, the clock ramp and W warm-up steps, ONE window of exactly K timed
+steps, the outputs of the last of them when --dump-outputs is given, the JSON line.  `--full` adds everything else the line
+has carried: five timed windows (the headline is then the median), the kernel-events pass and its roofline, the placement
+comparisons, host-transfer times, the CPU baselines and the graph / optimizer / frame_constraints configurations.
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment launches the N ranks itself (child
 processes, before anything touches a GPU) and forwards rank 0's JSON line.  One JSON line on rank 0.
@@ -38,6 +43,25 @@ F64_MFMA_PEAK_TFLOPS = 78.6   # AMD's published MI355X float64 matrix figure (th
 PMC_SUMMARIES = [os.path.join(ROOT, "profiles", n) for n in ("r05_summary.json", "r05_frame_constraints_summary.json", "r04a_summary.json")]   # tools/prof_all.sh (r04a: its counter passes ran the tile-major kernel, the one slow-class boxes get)
 METRIC = "motion-primitive samples scored+back-projected/sec; fraction of HBM roofline"
 L, F, D, NB, K = 40, 156, 79, 31, 8
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+DUMP_FRAMES_SAMPLE = 512    # candidates whose frames --dump-outputs keeps: the whole output (404 MB at B = 8192) is too large
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array as <out_dir>/<name>.npy, float32 or float64, DUMP_LIMIT_BYTES at most in all."""
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        if a.dtype not in (np.float32, np.float64):
+            raise SystemExit("--dump-outputs: %s is %s, not float32 or float64" % (name, a.dtype))
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
+def frames_sample_index(B):
+    """The fixed, seeded sample of candidates whose frames --dump-outputs writes (sorted; all of them when B is small)."""
+    return np.sort(np.random.default_rng(0).choice(B, size=min(B, DUMP_FRAMES_SAMPLE), replace=False))
 
 
 def pmc_traffic_bytes(kernel_substr):
@@ -153,6 +177,14 @@ def ensure_built():
 # ---------------------------------------------------------------------------------------------------------
 # the headline workload: frames + log p of 8192 candidates per GPU
 # ---------------------------------------------------------------------------------------------------------
+def walk_latents(data, B, rank):
+    """A rank's synthetic latents: sklearn-style GMM draw on the host (RandomState(rank)), cast to f32 (made resident in HBM)."""
+    from morphablegraphs_amd.gaussian_mixture import sample_like_sklearn
+    rs = np.random.RandomState(rank)
+    return sample_like_sklearn(B, np.array(data["gmm_weights"]), np.array(data["gmm_means"]),
+                               np.array(data["gmm_covars"]), rs)[0].astype(np.float32)
+
+
 def run_walk(args, rank, local_rank, world):
     dry = args.dry_run
     if dry and os.environ.get("MG_BENCH_DRY_RUN_DIES") == str(rank):   # launcher test: a rank that dies before the rendezvous
@@ -192,6 +224,8 @@ def run_walk(args, rank, local_rank, world):
         elapsed = max_over_ranks(time.perf_counter() - t0)
         if world > 1:
             assert gathered.shape == (world * B,) and all(gathered[r * B] == r for r in range(world))
+        if rank == 0 and args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"logp": gathered})
         if rank == 0:
             print(json.dumps({"metric": METRIC, "value": world * B * args.steps / elapsed, "unit": "samples/s", "n_gpus": world,
                               "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps,
@@ -204,7 +238,6 @@ def run_walk(args, rank, local_rank, world):
     ensure_built()
     from morphablegraphs_amd import _capi, synthetic
     from morphablegraphs_amd.distributed import first_min_argmin
-    from morphablegraphs_amd.gaussian_mixture import sample_like_sklearn
     data = synthetic.make_walk_primitive(seed=0)
     dev_index = local_rank   # one rank per GPU of the node
     if os.environ.get("MG_BENCH_OVERSUBSCRIBE"):   # rehearsal on a box with fewer GPUs than ranks: the ranks share that many devices
@@ -253,10 +286,7 @@ def run_walk(args, rank, local_rank, world):
         ctx.set_option(_capi.MG_OPT_FRAMES_KERNEL, args.frames_kernel)
     kernel_name = prim.step_plan(B)["kernel"]   # (refined below, once the output buffer and its placement class are known)
 
-    # synthetic latents: sklearn-style GMM draw on the host (RandomState(rank)), cast to f32, resident in HBM
-    rs = np.random.RandomState(rank)
-    S_host = sample_like_sklearn(B, np.array(data["gmm_weights"]), np.array(data["gmm_means"]),
-                                 np.array(data["gmm_covars"]), rs)[0].astype(np.float32)
+    S_host = walk_latents(data, B, rank)
     S = ctx.upload(S_host)
     nbytes = B * F * D * 4
     # the output comes from the library's allocator for large outputs: where 404 MB land in HBM decides between two
@@ -270,8 +300,8 @@ def run_walk(args, rank, local_rank, world):
         frames = ctx.malloc_placed(nbytes)
     alloc_s = time.perf_counter() - t_alloc
     kernel_name = prim.step_plan(B, frames)["kernel"]   # a slow-class piece of the output arena gets the tile-major kernel
-    probe = ctx.probe_placement(frames)   # pattern and fill time on THIS buffer: the in-run achievable ceiling
-    fill_us = probe["pattern_us"] / probe["ratio"] if probe["ratio"] > 0 else None
+    probe = ctx.probe_placement(frames) if args.full else None   # pattern and fill time on THIS buffer: the in-run achievable ceiling
+    fill_us = probe["pattern_us"] / probe["ratio"] if probe and probe["ratio"] > 0 else None
     logps = [ctx.malloc(B * 4) for _ in range(2)]
     gathereds = [ctx.malloc(world * B * 4) for _ in range(2)] if world > 1 else None
     scalar_dev = ctx.malloc(8)
@@ -316,19 +346,29 @@ def run_walk(args, rank, local_rank, world):
     barrier()
     # THE TIMED REGION: exactly K steps between barrier + synchronise, nothing else in it -- no timing events, no profiling
     # (round 4 bracketed every second launch with dispatch events inside this region: ~4 us each, 11.5 us of step - kernel on the
-    # driver's box).  Five such windows back to back; the headline is the MEDIAN window (one hiccup of a shared box cannot move it),
-    # all five are in the line (`ms_per_step_windows`).  The kernel's own duration comes from a SECOND pass of K steps with a
-    # dispatch-attached event pair on every launch.
+    # driver's box).  A plain run times one such window.  --full times five back to back; the headline is then the MEDIAN window (one
+    # hiccup of a shared box cannot move it), all five are in the line (`ms_per_step_windows`), and the kernel's own duration comes
+    # from a SECOND pass of K steps with a dispatch-attached event pair on every launch.
     windows = []
-    for _ in range(5 if not args.single_window else 1):
+    for _ in range(5 if args.full and not args.single_window else 1):
         t0 = time.perf_counter()
         for _ in range(args.steps):
             step()
         barrier()
         windows.append(max_over_ranks(time.perf_counter() - t0))
     elapsed = float(np.median(windows))
+    if args.dump_outputs and rank == 0:
+        # what the last timed step handed its caller: log p of every candidate (all ranks' after the all-gather) and the frames of a
+        # fixed sample of rank 0's candidates
+        b_last = (step_no[0] - 1) & 1
+        lp_out = ctx.download(gathereds[b_last], (world * B,), np.float32) if world > 1 else ctx.download(logps[b_last], (B,), np.float32)
+        idx = frames_sample_index(B)
+        fr_out = np.empty((len(idx), F, D), dtype=np.float32)
+        for j, i in enumerate(idx):
+            fr_out[j] = ctx.download(frames.ptr.value + int(i) * F * D * 4, (F, D), np.float32)
+        dump_outputs(args.dump_outputs, {"logp": lp_out, "frames_sample": fr_out})
     interval = max(1, args.event_interval) if args.event_interval else 1
-    if not args.no_profile_events:
+    if args.full and not args.no_profile_events:
         ctx.profile_reset()
         ctx.profile_enable(interval)
         for _ in range(args.steps):
@@ -337,7 +377,7 @@ def run_walk(args, rank, local_rank, world):
         ctx.profile_enable(False)
     last = (step_no[0] - 1) & 1
     gather_us = None
-    if world > 1:
+    if world > 1 and args.full:
         # the collective alone: 200 all-gathers of the step's size back to back on the kernels' stream, nothing else running
         for _ in range(20):
             ctx.dist_all_gather(logps[0], gathereds[0], B, np.float32)
@@ -365,12 +405,16 @@ def run_walk(args, rank, local_rank, world):
         placement = {"allocator": "one hipMalloc (MG_OPT_PLAIN_MALLOC)" if args.output_alloc == "plain" else "the library's placed output regions (mg_device_malloc / mg_device_malloc_placed: every buffer of 64 MiB and more, "
                                   "the *_host entry points' scratch included, is a piece of a region that went through the placement probe; scan of 32 candidates, up to 400 when those were all slow -- six tenths of the free memory held while that runs)",
                      "candidates_probed": frames.placement["probed"] if frames.placement else 0, "alloc_seconds": round(alloc_s, 4),
-                     "pattern_over_fill": round(probe["ratio"], 4)}
+                     "pattern_over_fill": round(probe["ratio"], 4) if probe else None}
         # the class is the arena's: decided once from the scan's own measurement and kept (mg_device_placement_info); the probe
-        # above only supplies the in-run fill / pattern times of the roofline's 'achievable' figures
+        # above (--full) only supplies the in-run fill / pattern times of the roofline's 'achievable' figures
         arena = ctx.placement_info(frames)
-        placement["fast_class"] = arena["fast"] if arena["region"] else probe["fast"]
-        placement["pattern_TBps"] = round(arena["pattern_TBps"], 3) if arena["region"] else round(B * F * D * 4 / probe["pattern_us"] * 1e-6, 3)
+        if arena["region"]:
+            placement["fast_class"], placement["pattern_TBps"] = arena["fast"], round(arena["pattern_TBps"], 3)
+        elif probe:
+            placement["fast_class"], placement["pattern_TBps"] = probe["fast"], round(B * F * D * 4 / probe["pattern_us"] * 1e-6, 3)
+        else:
+            placement["fast_class"] = placement["pattern_TBps"] = None
         result = {
             "metric": METRIC, "value": value, "unit": "samples/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
@@ -389,7 +433,7 @@ def run_walk(args, rank, local_rank, world):
                        "clock_ramp_steps": args.ramp_steps,
                        "output_placement": placement},
         }
-        if frames_n > 0:
+        if args.full and frames_n > 0:
             avg_ms = frames_ms / frames_n
             # algorithmic bytes of the dominant kernel.  Fused step kernel: the whole step (latents, frames, log p,
             # E, mean, basis, mixture constants); stand-alone frames kernel: latents + frames (+ E, mean, basis)
@@ -418,7 +462,7 @@ def run_walk(args, rank, local_rank, world):
                 result["roofline"].update({"kernel_ms_p10": float(smp[int(0.10 * (len(smp) - 1))]),
                                            "kernel_ms_p50": float(smp[int(0.50 * (len(smp) - 1))]),
                                            "kernel_ms_p90": float(smp[int(0.90 * (len(smp) - 1))])})
-        if world == 1:
+        if world == 1 and args.full:
             def wall_us(n, out_buf):
                 for _ in range(20):
                     prim.step_frames_and_logp_dev(S, np.float32, B, L, out_buf, logps[0])
@@ -469,7 +513,7 @@ def run_walk(args, rank, local_rank, world):
                 "d2h_winner_frames": med_us(lambda: ctx.lib.mg_memcpy_d2h(ctx.handle, fr_h.ctypes.data_as(C.c_void_p), C.c_void_p(frames.ptr.value + (B // 2) * F * D * 4), fr_h.nbytes)),
                 "d2h_winner_frames_bytes": 4 * F * D, "note": "pageable host memory, synchronous copies through the C-ABI",
             }
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             result["cpu_baseline"] = cpu_baseline_leg(data, S_host)
     for buf in [S, frames, scalar_dev, scalars_dev] + logps + (gathereds or []):
         buf.free()
@@ -478,7 +522,7 @@ def run_walk(args, rank, local_rank, world):
         ctx.dist_finalize()
     ctx.close()
     if rank == 0:
-        if world == 1 and not args.no_extra_configs and B == 8192 and args.dry_run is False:
+        if world == 1 and args.full and not args.no_extra_configs and B == 8192 and args.dry_run is False:
             # BASELINE configs[2] and configs[4] on this GPU, a few hundred steps each, under keys of their own (the headline keys
             # above are configs[1] and unchanged); `python bench.py --config graph | optimizer` prints each as a line of its own
             import copy
@@ -860,16 +904,22 @@ def main():
     ap.add_argument("--config", choices=("walk", "graph", "optimizer", "frame_constraints"), default="walk",
                     help="walk = BASELINE configs[1] / [3] (the headline); graph = configs[2]; optimizer = configs[4] per iteration on one GPU; "
                          "frame_constraints = candidates against constraints that walk every frame (a root trajectory + a hand position)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--single-window", action="store_true", help="time one window of K steps instead of five (the headline is then that window)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: five timed windows, the kernel-events pass and roofline, the placement comparisons, "
+                         "host-transfer times, the CPU baselines and the graph / optimizer / frame_constraints configurations")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy: logp (every candidate) and frames_sample "
+                         "(the frames of %d candidates drawn with numpy's default_rng(0), sorted)" % DUMP_FRAMES_SAMPLE)
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: no CPU baselines")
+    ap.add_argument("--single-window", action="store_true", help="--full: time one window of K steps instead of five (the headline is then that window)")
     ap.add_argument("--host-counts", action="store_true", help="--config graph: component counts from numpy.random.multinomial on the host (one call per option) instead of the device draw")
-    ap.add_argument("--no-placement-compare", action="store_true", help="skip the steps on a second library buffer and on a foreign hipMalloc after the timed region (profiling runs)")
-    ap.add_argument("--no-extra-configs", action="store_true", help="do not attach the graph / optimizer configurations to the default line")
+    ap.add_argument("--no-placement-compare", action="store_true", help="--full: skip the steps on a second library buffer and on a foreign hipMalloc after the timed region (profiling runs)")
+    ap.add_argument("--no-extra-configs", action="store_true", help="--full: do not attach the graph / optimizer configurations to the line")
     ap.add_argument("--two-launch", action="store_true",
                     help="frames kernel and log-likelihood kernel as two launches instead of the fused step kernel")
     ap.add_argument("--frames-kernel", type=int, choices=(0, 1, 2), default=0,
                     help="MG_OPT_FRAMES_KERNEL: 0 = the library's choice, 1 = tile-major, 2 = chunk-stationary (A/B runs)")
-    ap.add_argument("--no-profile-events", action="store_true", help="do not bracket kernels with HIP events")
+    ap.add_argument("--no-profile-events", action="store_true", help="--full: do not bracket kernels with HIP events")
     ap.add_argument("--event-interval", type=int, default=0,
                     help="every n-th launch of the events pass (after the timed windows) carries HIP start/stop events attached to the dispatch (0 = every launch)")
     ap.add_argument("--ramp-steps", type=int, default=1500,
@@ -889,6 +939,8 @@ def main():
     if args.config != "walk":
         if world > 1:
             raise SystemExit("--config %s is a single-GPU workload" % args.config)
+        if args.dump_outputs:
+            raise SystemExit("--dump-outputs writes the outputs of the walk configuration only")
         return {"graph": run_graph, "optimizer": run_optimizer, "frame_constraints": run_frame_constraints}[args.config](args)
     return run_walk(args, rank, local_rank, world)
 

@@ -7,6 +7,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -100,3 +101,40 @@ def test_ranks_that_never_join_the_communicator_end_the_launch(tmp_path):
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=120)
     assert p.returncode != 0 and time.time() - t0 < 60, p.stderr.decode()[-500:]
     assert b"had not joined the communicator" in p.stderr
+
+
+def test_dry_run_dumps_the_gathered_scores(tmp_path):
+    """--dump-outputs through the launcher: rank 0 alone writes what the step hands its caller, float32, named after it."""
+    out = _run([sys.executable, "bench.py", "--gpus", "2", "--steps", "3", "--warmup", "0", "--dry-run", "--batch", "32",
+                "--dump-outputs", str(tmp_path)])
+    assert len(_json_lines(out)) == 1
+    assert sorted(os.listdir(tmp_path)) == ["logp.npy"]
+    lp = np.load(tmp_path / "logp.npy")
+    assert lp.dtype == np.float32 and lp.shape == (64,) and lp[0] == 0 and lp[32] == 1
+
+
+@pytest.mark.gpu
+def test_plain_run_times_k_steps_and_dumps_what_they_computed(tmp_path):
+    """A plain run: one window of exactly --steps timed steps, the headline keys, none of what --full adds; --dump-outputs writes
+    log p of every candidate and the frames of the seeded sample, the bits of the float32 contract model on bench's own latents."""
+    import bench
+    from morphablegraphs_amd import synthetic
+    from oracle import c_oracle
+    out = _run([sys.executable, "bench.py", "--gpus", "1", "--steps", "40", "--warmup", "4", "--dump-outputs", str(tmp_path)], timeout=400)
+    lines = _json_lines(out)
+    assert len(lines) == 1, out
+    r = lines[0]
+    assert r["steps"] == 40 and r["warmup"] == 4 and r["ms_per_step"] > 0 and r["unit"] == "samples/s" and r["dtype"] == "f32"
+    assert r["ms_per_step_windows"]["n"] == 1 and r["ms_per_step_windows"]["steps_each"] == 40
+    assert abs(r["ms_per_step"] * r["value"] / 1e3 - 8192) < 1e-3
+    assert not {"roofline", "cpu_baseline", "graph", "optimizer", "frame_constraints", "transfers_us"} & set(r)
+    assert sorted(os.listdir(tmp_path)) == ["frames_sample.npy", "logp.npy"]
+    assert sum(os.path.getsize(tmp_path / n) for n in os.listdir(tmp_path)) <= 64 * 10 ** 6
+    lp, fr = np.load(tmp_path / "logp.npy"), np.load(tmp_path / "frames_sample.npy")
+    idx = bench.frames_sample_index(8192)
+    assert lp.dtype == np.float32 and lp.shape == (8192,) and fr.dtype == np.float32 and fr.shape == (len(idx), 156, 79)
+    data = synthetic.make_walk_primitive(seed=0)
+    S = bench.walk_latents(data, 8192, 0).astype(np.float64)
+    cp = c_oracle.COraclePrimitive(data)
+    np.testing.assert_array_equal(fr.view(np.uint32), cp.frames_f32model(S[idx]).view(np.uint32))
+    np.testing.assert_allclose(lp, cp.log_prob_f64(S), rtol=3e-7, atol=1e-6)

@@ -6,7 +6,7 @@ for v in lc0 lc1 lc0 lc1; do
   cp build/lib_$v.so $L
   python bench.py --config optimizer --no-cpu-baseline > /tmp/o.json 2>/dev/null
   python bench.py --config graph --no-cpu-baseline > /tmp/g.json 2>/dev/null
-  python bench.py --two-launch --no-cpu-baseline --single-window --no-extra-configs --no-placement-compare > /tmp/t.json 2>/dev/null
+  python bench.py --full --two-launch --no-cpu-baseline --single-window --no-extra-configs --no-placement-compare > /tmp/t.json 2>/dev/null
   python -c "
 import json
 o=json.load(open('/tmp/o.json')); g=json.load(open('/tmp/g.json')); t=json.load(open('/tmp/t.json'))

@@ -17,5 +17,5 @@ for cfg in graph optimizer frame_constraints; do
   cp $R/gpurun_out/prof_${tag}_$cfg/bench.json $O/${tag}_${cfg}_bench_under_rocprof.json
   rm -rf $R/gpurun_out/prof_${tag}_$cfg
 done
-cd $R && python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/${tag}_bench.json 2> $O/bench.err
+cd $R && python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $O/${tag}_bench.json 2> $O/bench.err
 ls -la $O

@@ -3,6 +3,7 @@
 # usage: tools/prof_bench.sh <tag> [extra bench args]
 set -o pipefail
 tag=${1:-r05}; shift
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 out=$GRAFT_REPO_ROOT/gpurun_out/prof_$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
@@ -10,8 +11,8 @@ cd /tmp && export TMPDIR=/tmp
 # python starts, and the runtime reads the variable then: without the export the profiled kernels fetch their arguments from host memory
 # (+1.6 us on the frames kernel) and the trace is not the product's.
 export HIP_FORCE_DEV_KERNARG=1
-# the default bench.py command (steps 2000, warmup 200, HIP-event bracketing on), minus the CPU baseline leg
-B="$GRAFT_REPO_ROOT/bench.py --steps 2000 --warmup 200 --no-cpu-baseline --no-extra-configs --no-placement-compare $@"
+# the bench.py --full command (steps 2000, warmup 200, five timed windows, HIP-event bracketing on), minus the CPU baseline leg
+B="$ROOT/bench.py --full --steps 2000 --warmup 200 --no-cpu-baseline --no-extra-configs --no-placement-compare $@"
 # the counter passes slow the placement probe down, the arena then calls the buffer slow-class and the library would pick the tile-major
 # kernel for it: the counters are wanted for the kernel the trace pass (and the bench) runs, so the PMC passes name it
 T="$B"

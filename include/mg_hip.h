@@ -705,15 +705,18 @@ int mg_argmin_first_dev(mg_context *ctx, const void *values_dev, int dtype, int6
 int mg_step_frames_and_logp(mg_primitive *prim, const void *latents_dev, int latent_dtype,
                             int64_t n_samples, int64_t ld, float *frames_dev, float *logp_dev);
 
-/* What mg_step_frames_and_logp would launch for n_samples candidates, without launching (for profiles and logs):
+/* What mg_step_frames_and_logp would launch for n_samples FLOAT32 latents, without launching (for profiles and logs):
  * plan[0] = frames kernel (0 = the plain VALU kernel, 1 = tile-major LDS-staged, 2 = chunk-stationary LDS-staged),
  * plan[1] = 1 when log p(x) is scored inside the frames kernel (one launch per step), 0 when it is a second launch,
- * plan[2] = workgroups, plan[3] = LDS bytes per workgroup. */
+ * plan[2] = workgroups, plan[3] = LDS bytes per workgroup.  For float64 latents use mg_step_plan_dtype: from 49 latent
+ * components on, float64 latents keep the tile-major kernel where float32 ones get the chunk-stationary kernel. */
 int mg_step_plan(const mg_primitive *prim, int64_t n_samples, int32_t plan[4]);
-/* The same for a given output buffer: where the frames go can change the kernel -- a piece of a placed region whose scan found
- * only slow-class memory (mg_device_malloc) is written by the tile-major kernel, which is the faster one there (frames_dev NULL:
- * mg_step_plan). */
+/* The same (float32 latents) for a given output buffer: where the frames go can change the kernel -- a piece of a placed region
+ * whose scan found only slow-class memory (mg_device_malloc) is written by the tile-major kernel, which is the faster one there
+ * (frames_dev NULL: mg_step_plan). */
 int mg_step_plan_for(const mg_primitive *prim, int64_t n_samples, const void *frames_dev, int32_t plan[4]);
+/* The same for latents of the given dtype (MG_F32: mg_step_plan_for; MG_F64: what a step over float64 latents launches). */
+int mg_step_plan_dtype(const mg_primitive *prim, int64_t n_samples, const void *frames_dev, int latent_dtype, int32_t plan[4]);
 
 /* evaluate_samples_using_constraints (reference motion_primitive_generator.py:230-261) in one call: score all
  * candidates against the set, first-minimum argmin, result on the host (no allocation, one synchronisation). */

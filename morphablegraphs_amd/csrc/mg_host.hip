@@ -1873,10 +1873,15 @@ extern "C" int mg_step_frames_and_logp(mg_primitive *p, const void *lat, int dt,
     return rc;
 }
 
-static int mg_step_plan_impl(const mg_primitive *p, int64_t B, const void *frames_dev, int32_t *plan);
-extern "C" int mg_step_plan(const mg_primitive *p, int64_t B, int32_t *plan) { return mg_step_plan_impl(p, B, nullptr, plan); }
-extern "C" int mg_step_plan_for(const mg_primitive *p, int64_t B, const void *frames_dev, int32_t *plan) { return mg_step_plan_impl(p, B, frames_dev, plan); }
-static int mg_step_plan_impl(const mg_primitive *p, int64_t B, const void *frames_dev, int32_t *plan) {
+static int mg_step_plan_impl(const mg_primitive *p, int64_t B, const void *frames_dev, bool lat_f64, int32_t *plan);
+extern "C" int mg_step_plan(const mg_primitive *p, int64_t B, int32_t *plan) { return mg_step_plan_impl(p, B, nullptr, false, plan); }
+extern "C" int mg_step_plan_for(const mg_primitive *p, int64_t B, const void *frames_dev, int32_t *plan) { return mg_step_plan_impl(p, B, frames_dev, false, plan); }
+extern "C" int mg_step_plan_dtype(const mg_primitive *p, int64_t B, const void *frames_dev, int latent_dtype, int32_t *plan) {
+    MG_REQUIRE(latent_dtype == MG_F32 || latent_dtype == MG_F64, "mg_step_plan_dtype: bad latent dtype %d", latent_dtype);
+    return mg_step_plan_impl(p, B, frames_dev, latent_dtype == MG_F64, plan);
+}
+// lat_f64: float64 latents, which keep the chunk-stationary kernel from the widths where its float64 instance spills (mg_frames_kernel_choice)
+static int mg_step_plan_impl(const mg_primitive *p, int64_t B, const void *frames_dev, bool lat_f64, int32_t *plan) {
     MG_REQUIRE(p && plan && B >= 0, "mg_step_plan: bad arguments");
     const mg_time_grid *g = p->canonical;
     plan[0] = plan[1] = plan[2] = plan[3] = 0;
@@ -1886,7 +1891,7 @@ static int mg_step_plan_impl(const mg_primitive *p, int64_t B, const void *frame
         plan[2] = (int32_t)std::min<int64_t>((B * (int64_t)g->T * p->D + 255) / 256, (int64_t)p->ctx->n_cu * 32);
         return MG_OK;
     }
-    const int which = mg_frames_kernel_choice(p, g, B, fused, frames_dev);
+    const int which = mg_frames_kernel_choice(p, g, B, fused, frames_dev, lat_f64);
     MG_REQUIRE(which > 0, "mg_step_plan: the chunk-stationary kernel does not cover this shape");
     plan[0] = which;
     plan[1] = fused ? 1 : 0;

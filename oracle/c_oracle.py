@@ -61,14 +61,15 @@ class COraclePrimitive(object):
         self.covars = _d(data["gmm_covars"])
         self.K = len(self.weights)
         self.prec_chol = np.empty_like(self.covars)
-        rc = lib().orc_precision_cholesky(_ptr(self.covars, _dp), self.K, self.L, _ptr(self.prec_chol, _dp))
+        # the mixture spans the spatial AND the time latents (n_gmm_dims = Lg >= L)
+        self.Lg = self.means.shape[1] if self.K else self.L
+        rc = lib().orc_precision_cholesky(_ptr(self.covars, _dp), self.K, self.Lg, _ptr(self.prec_chol, _dp))
         if rc != 0:
             raise ValueError("covariance %d not positive definite" % (rc - 1))
         # the root channels' mode of the float32 contract (include/mg_hip.h, mg_primitive_root_mode): the mean/delta split
         # where its error estimate is at most 5e-6, the float64 pipeline otherwise
-        Lg = self.means.shape[1] if self.K else self.L
         self.root_split_estimate = float(lib().orc_root_split_estimate(
-            _ptr(self.E, _dp), _ptr(self.tm, _dp), self.NB, self.D, self.L, self.K, Lg,
+            _ptr(self.E, _dp), _ptr(self.tm, _dp), self.NB, self.D, self.L, self.K, self.Lg,
             _ptr(self.weights, _dp), _ptr(self.means, _dp), _ptr(self.covars, _dp)))
         self.root_split = bool(np.isfinite(self.root_split_estimate) and self.root_split_estimate <= 5e-6)
 
@@ -118,7 +119,7 @@ class COraclePrimitive(object):
         X = _d(np.atleast_2d(X))
         out = np.empty(X.shape[0])
         lib().orc_gmm_log_prob_f64(_ptr(self.weights, _dp), _ptr(self.means, _dp), _ptr(self.prec_chol, _dp),
-                                   self.K, self.L, _ptr(X, _dp), C.c_int64(X.shape[0]), C.c_int64(X.shape[1]),
+                                   self.K, self.Lg, _ptr(X, _dp), C.c_int64(X.shape[0]), C.c_int64(X.shape[1]),
                                    _ptr(out, _dp))
         return out
 

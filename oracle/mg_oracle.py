@@ -1467,3 +1467,48 @@ def device_multinomial_counts(n, weights, seed):
     u = (np.stack(words, axis=1).reshape(-1)[:n].astype(np.float64) + 0.5) * (1.0 / 4294967296.0)
     below = [int(np.count_nonzero(u < cum[c])) for c in range(K - 1)] + [int(n)]
     return np.diff([0] + below).astype(np.int64)
+
+
+def device_normals(rows, seed, n_groups):
+    """mg_normal4 (csrc/mg_gmm_device.h) restated for groups of four 0 .. n_groups - 1 of the given rows: z (n_rows, 4 n_groups).
+    Philox4x32-10 with counter (row lo, row hi, group q, 0) and key = seed; u0, u2 = (word + 1) / 2^32, u1, u3 = word / 2^32;
+    the float32 Box-Muller as the device writes it -- m = sqrt(-2 ln 2 * log2(float(u))), angle float(u) in REVOLUTIONS --
+    evaluated here in float64 from the same float32 arguments (the device's transcendentals are float32 approximations of
+    these exact values)."""
+    rows = np.asarray(rows, dtype=np.uint64)
+    k0, k1 = int(seed) & 0xFFFFFFFF, (int(seed) >> 32) & 0xFFFFFFFF
+    z = np.empty((len(rows), 4 * n_groups), dtype=np.float64)
+    inv = 1.0 / 4294967296.0
+    for q in range(n_groups):
+        w = philox4x32_10(rows & np.uint64(0xFFFFFFFF), rows >> np.uint64(32), q, 0, k0, k1)
+        u0, u1 = (w[0].astype(np.float64) + 1.0) * inv, w[1].astype(np.float64) * inv
+        u2, u3 = (w[2].astype(np.float64) + 1.0) * inv, w[3].astype(np.float64) * inv
+        c = float(np.float32(1.3862943611198906))
+        m0 = np.sqrt(-c * np.log2(u0.astype(np.float32).astype(np.float64)))
+        m1 = np.sqrt(-c * np.log2(u2.astype(np.float32).astype(np.float64)))
+        a0 = 2.0 * np.pi * u1.astype(np.float32).astype(np.float64)
+        a1 = 2.0 * np.pi * u3.astype(np.float32).astype(np.float64)
+        z[:, 4 * q:4 * q + 4] = np.stack([m0 * np.cos(a0), m0 * np.sin(a0), m1 * np.cos(a1), m1 * np.sin(a1)], axis=1)
+    return z
+
+
+def device_gmm_sample(counts, seed, means, covars):
+    """The device sampler's draw (mg_gmm_sample, csrc/mg_gmm.hip) restated: rows grouped by component in order of `counts`,
+    row b of component k = mu_k + chol_k z_b with chol_k the lower Cholesky factor of covars[k] and z_b the first n_dims
+    normals of device_normals(b).  Returns (x (n, n_dims) float64, component (n,), scale (n, n_dims)): scale[b, i] =
+    sum_j |chol_k[i, j]| (1 + |z_b[j]|), what a float32 error in the normals can move x[b, i] by, per unit of relative error."""
+    counts = np.asarray(counts, dtype=np.int64)
+    means, covars = np.asarray(means, dtype=np.float64), np.asarray(covars, dtype=np.float64)
+    L = means.shape[1]
+    n = int(counts.sum())
+    comp = np.repeat(np.arange(len(counts)), counts).astype(np.int32)
+    z = device_normals(np.arange(n), seed, (L + 3) // 4)[:, :L]
+    x, scale = np.empty((n, L)), np.empty((n, L))
+    for k in range(len(counts)):
+        sel = comp == k
+        if not sel.any():
+            continue
+        chol = np.linalg.cholesky(covars[k])
+        x[sel] = means[k] + z[sel] @ chol.T
+        scale[sel] = (1.0 + np.abs(z[sel])) @ np.abs(chol).T
+    return x, comp, scale

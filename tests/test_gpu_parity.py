@@ -715,7 +715,7 @@ def test_chunk_stationary_kernel_is_bit_identical(ctx, B):
 
 @pytest.mark.parametrize("shape", [dict(n_components=40, n_frames=156, n_dim=79, n_gmm=16), dict(n_components=40, n_frames=156, n_dim=79, n_gmm=1),
                                    dict(n_components=24, n_frames=60, n_dim=79, n_gmm=3), dict(n_components=13, n_frames=47, n_dim=15, n_gmm=5),
-                                   dict(n_components=33, n_frames=97, n_dim=79, n_gmm=11)])
+                                   dict(n_components=33, n_frames=97, n_dim=79, n_gmm=11), dict(n_components=29, n_frames=48, n_basis=5, n_dim=79, n_gmm=16)])
 def test_fused_tail_with_staged_mixture_constants(ctx, shape):
     """The chunk-stationary kernel's mixture tail for float32 latents (round 5): the workgroup's two latent tiles, the components'
     C-in rows and constants staged in LDS at start-up by the four sweep waves that produce nothing, both components of a producer

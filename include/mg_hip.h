@@ -328,7 +328,8 @@ int mg_memset(mg_context *ctx, void *dst_dev, int value, int64_t bytes);
  * microseconds of stream time, so a timed region samples with n ~ 8); totals are resolved on query.
  * slot: 0 = back_project_frames, 1 = gmm_log_prob, 2 = score_constraints, 3 = argmin,
  *       4 = gmm_sample, 5 = spline_evaluate, 6 = fused step, 7 = a planner step in one launch (mg_options_step),
- *       8 = mg_joint_tracks, 9 = mg_score_frame_constraints, 10 = mg_score_trajectory[_points]. */
+ *       8 = mg_joint_tracks, 9 = mg_score_frame_constraints, 10 = mg_score_trajectory[_points],
+ *       11 = mg_cluster_tree_search. */
 int mg_profile_enable(mg_context *ctx, int enabled);
 int mg_profile_reset(mg_context *ctx);
 int mg_profile_get(mg_context *ctx, int slot, double *total_ms, int64_t *launches);
@@ -766,6 +767,41 @@ int mg_options_step_rows(int32_t n_options, mg_primitive *const *prims, const mg
                          void *const *x_dev, int x_dtype, const int64_t *ld, double *const *errors_dev, void *results_dev,
                          int64_t result_stride, void *results_host);
 
+/* ---- cluster-tree search (reference space_partitioning/feature_cluster_tree.py:129-187) --------
+ * A FeatureClusterTree flattened on the host: node 0 is the root; means (n_nodes, dim) float64, row i the mean of node
+ * i (its first n_components entries are what the objective scores); the children of node i are
+ * children[child_begin[i] .. child_begin[i + 1]) in the reference's order (CSR, child_begin has n_nodes + 1 entries,
+ * child_begin[n_nodes] = n_nodes - 1); first_index[i] = indices[0] of node i, the row of the tree's data a leaf
+ * stands for (-1: the node has no indices -- allowed for the root and inner nodes only).  Validated: every node
+ * but the root has exactly one parent and is reachable from it (no cycles), depth <= MG_TREE_MAX_DEPTH, at most
+ * MG_TREE_MAX_CHILDREN children per node, leaf rows in [0, n_rows), dim >= n_components.  Uploaded once. */
+typedef struct mg_cluster_tree mg_cluster_tree;
+#define MG_TREE_MAX_DEPTH 64
+#define MG_TREE_MAX_CHILDREN 256
+#define MG_TREE_MAX_CANDIDATES 64
+/* flags of a search record */
+#define MG_TREE_TIE 1          /* two equal values met in a heap comparison: the reference raises TypeError there */
+#define MG_TREE_NO_RESULT 2    /* no leaf reached (the reference's "failed to find a result"): value +inf, the root's row */
+#define MG_TREE_OVERFLOW 4     /* a heap outgrew its bound (cannot happen for a validated tree; the record is not to be used) */
+typedef struct mg_tree_search_record {
+    int64_t row;               /* first_index of the winning leaf: the data row the search returns (-1: none) */
+    int32_t leaf;              /* the winning leaf node */
+    int32_t flags;             /* MG_TREE_* */
+    int64_t evaluations;       /* objective evaluations: the children scored over the whole descent */
+    double value;              /* the winning leaf's value: the objective of its mean (+inf for a root that is a leaf) */
+} mg_tree_search_record;
+int mg_cluster_tree_create(mg_primitive *prim, int32_t n_nodes, int32_t dim, const double *means, const int32_t *child_begin,
+                           const int32_t *children, const int64_t *first_index, int64_t n_rows, mg_cluster_tree **tree);
+void mg_cluster_tree_destroy(mg_cluster_tree *tree);
+/* find_best_example_excluding_search_candidates(obj, args, n_candidates) for n_searches (prim, tree, constraint set)
+ * triples in ONE launch, a workgroup per search: per level every frontier node's children are scored against the set
+ * (bit for bit what mg_score_constraints gives for the child's mean), pushed onto a heap per node whose list's first
+ * n_candidates entries go onto the level's heap, whose list's first n_candidates entries are the next frontier; leaves
+ * go onto the results heap, whose root is the answer.  All primitives and trees in one context; 1 <= n_candidates <=
+ * MG_TREE_MAX_CANDIDATES.  records_dev: n_searches records (device memory). */
+int mg_cluster_tree_search(int32_t n_searches, mg_primitive *const *prims, mg_cluster_tree *const *trees,
+                           const mg_constraint_set *const *csets, int32_t n_candidates, mg_tree_search_record *records_dev);
+
 /* ---- host-pointer convenience variants (H2D, launch, D2H, synchronise) ---------------- */
 int mg_back_project_frames_host(mg_primitive *prim, const mg_time_grid *grid, const void *latents,
                                 int latent_dtype, int64_t n_samples, int64_t ld, float *frames, int path);
@@ -787,6 +823,8 @@ int mg_score_constraint_residuals_host(mg_primitive *prim, const mg_constraint_s
                                        int latent_dtype, int64_t n_samples, int64_t ld, double *residuals);
 int mg_gmm_log_prob_jac_host(mg_primitive *prim, const void *x, int x_dtype, int64_t n_samples, int64_t ld,
                              double *jac);
+int mg_cluster_tree_search_host(int32_t n_searches, mg_primitive *const *prims, mg_cluster_tree *const *trees,
+                                const mg_constraint_set *const *csets, int32_t n_candidates, mg_tree_search_record *records);
 
 #ifdef __cplusplus
 }

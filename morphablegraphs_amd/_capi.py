@@ -36,7 +36,12 @@ MG_CONSTRAINT_POSITION, MG_CONSTRAINT_DIRECTION_2D, MG_CONSTRAINT_JOINT_POSITION
 MG_CONSTRAINT_JOINT_MIDPOINT, MG_CONSTRAINT_JOINT_ORIENTATION, MG_CONSTRAINT_LOOK_AT, MG_CONSTRAINT_POSE = 3, 4, 5, 6
 MG_CONSTRAINT_VALUE_POSITION, MG_CONSTRAINT_VALUE_HEADING = 7, 8   # values of the aligned motion, not errors (chained graph-walk steps)
 PROFILE_SLOTS = {"frames": 0, "gmm_log_prob": 1, "score_constraints": 2, "argmin": 3,
-                 "gmm_sample": 4, "spline_evaluate": 5, "step": 6, "options_step": 7, "joint_tracks": 8, "frame_constraints": 9, "trajectory": 10}
+                 "gmm_sample": 4, "spline_evaluate": 5, "step": 6, "options_step": 7, "joint_tracks": 8, "frame_constraints": 9, "trajectory": 10,
+                 "cluster_tree_search": 11}
+MG_TREE_MAX_DEPTH, MG_TREE_MAX_CHILDREN, MG_TREE_MAX_CANDIDATES = 64, 256, 64    # include/mg_hip.h
+MG_TREE_TIE, MG_TREE_NO_RESULT, MG_TREE_OVERFLOW = 1, 2, 4
+# struct mg_tree_search_record
+TREE_SEARCH_RECORD = np.dtype([("row", "<i8"), ("leaf", "<i4"), ("flags", "<i4"), ("evaluations", "<i8"), ("value", "<f8")])
 
 # every symbol include/mg_hip.h declares (tests check the built library exports them all)
 EXPORTED_SYMBOLS = [
@@ -59,6 +64,7 @@ EXPORTED_SYMBOLS = [
     "mg_gmm_log_prob_jac_host", "mg_constraint_set_create_fk", "mg_constraint_set_create_aligned", "mg_constraint_set_create_full", "mg_constraint_set_update", "mg_best_candidate", "mg_best_candidate_host",
     "mg_align_frames", "mg_frame_constraint_width", "mg_score_frame_constraint", "mg_score_frame_constraints", "mg_options_frame_lists", "mg_track_plan_create", "mg_track_plan_destroy", "mg_joint_tracks",
     "mg_score_constraint_residuals_chained", "mg_option_step", "mg_options_step", "mg_options_step_device_counts", "mg_option_step_rows", "mg_options_step_rows", "mg_gmm_sample_rows", "mg_dist_broadcast",
+    "mg_cluster_tree_create", "mg_cluster_tree_destroy", "mg_cluster_tree_search", "mg_cluster_tree_search_host",
 ]
 
 
@@ -215,7 +221,8 @@ def load_library(path=None):
     lib.mg_primitive_canonical_grid.restype = C.c_void_p
     lib.mg_primitive_canonical_grid.argtypes = [C.c_void_p]
     lib.mg_time_grid_size.argtypes = [C.c_void_p]
-    for name in ("mg_context_destroy", "mg_primitive_destroy", "mg_time_grid_destroy", "mg_constraint_set_destroy", "mg_trajectory_destroy", "mg_track_plan_destroy"):
+    for name in ("mg_context_destroy", "mg_primitive_destroy", "mg_time_grid_destroy", "mg_constraint_set_destroy", "mg_trajectory_destroy", "mg_track_plan_destroy",
+                 "mg_cluster_tree_destroy"):
         getattr(lib, name).restype = None
         getattr(lib, name).argtypes = [C.c_void_p]
     vp, i32, i64, u64, dbl = C.c_void_p, C.c_int, C.c_int64, C.c_uint64, C.c_double
@@ -314,6 +321,9 @@ def load_library(path=None):
         "mg_gmm_log_prob_jac": [vp, vp, i32, i64, i64, vp],
         "mg_score_constraint_residuals_host": [vp, vp, vp, i32, i64, i64, vp],
         "mg_gmm_log_prob_jac_host": [vp, vp, i32, i64, i64, vp],
+        "mg_cluster_tree_create": [vp, i32, i32, vp, vp, vp, vp, i64, C.POINTER(vp)],
+        "mg_cluster_tree_search": [i32, vp, vp, vp, i32, vp],
+        "mg_cluster_tree_search_host": [i32, vp, vp, vp, i32, vp],
     }
     for name, argtypes in sigs.items():
         fn = getattr(lib, name)
@@ -775,6 +785,59 @@ class Trajectory(object):
             self.close()
         except Exception:
             pass
+
+
+class ClusterTree(object):
+    """A flattened FeatureClusterTree on the device (mg_cluster_tree_create): node 0 the root, means (n_nodes, dim), the
+    children in CSR form (child_begin (n_nodes + 1), children), first_index = indices[0] per node (-1: none), n_rows rows of
+    data.  It lives in the primitive's context and serves every primitive of that context whose n_components <= dim."""
+
+    def __init__(self, prim, means, child_begin, children, first_index, n_rows):
+        self.ctx = prim.ctx
+        self.lib = prim.lib
+        means = np.ascontiguousarray(np.asarray(means, dtype=np.float64))
+        cb = np.ascontiguousarray(np.asarray(child_begin, dtype=np.int32))
+        ch = np.ascontiguousarray(np.asarray(children, dtype=np.int32))
+        fi = np.ascontiguousarray(np.asarray(first_index, dtype=np.int64))
+        if means.ndim != 2 or cb.shape != (means.shape[0] + 1,) or fi.shape != (means.shape[0],):
+            raise ValueError("means (n_nodes, dim), child_begin (n_nodes + 1), first_index (n_nodes)")
+        h = C.c_void_p()
+        _check(self.lib.mg_cluster_tree_create(prim.handle, means.shape[0], means.shape[1], means.ctypes.data_as(C.c_void_p),
+                                               cb.ctypes.data_as(C.c_void_p), ch.ctypes.data_as(C.c_void_p) if ch.size else None,
+                                               fi.ctypes.data_as(C.c_void_p), int(n_rows), C.byref(h)))
+        self.handle = h
+        self.n_nodes, self.dim = means.shape
+
+    def close(self):
+        if getattr(self, "handle", None) and self.ctx.handle:
+            self.lib.mg_cluster_tree_destroy(self.handle)
+        self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def search_cluster_trees(prims, trees, csets, n_candidates, records_dev=None):
+    """mg_cluster_tree_search for len(prims) (Primitive, ClusterTree, ConstraintSet) triples of one context: ONE launch.
+    Returns the records (TREE_SEARCH_RECORD array), read back in one copy; with records_dev (a DeviceBuffer of
+    len(prims) * 32 bytes) the records stay there and nothing is returned."""
+    m = len(prims)
+    if not (len(trees) == m and len(csets) == m):
+        raise ValueError("prims, trees and csets must have one entry per search")
+    vp = C.c_void_p
+    hp = (vp * max(m, 1))(*[p.handle.value for p in prims])
+    ht = (vp * max(m, 1))(*[t.handle.value if t.handle else None for t in trees])
+    hc = (vp * max(m, 1))(*[c.handle.value if c.handle else None for c in csets])
+    lib = prims[0].lib if m else load_library()
+    if records_dev is not None:
+        _check(lib.mg_cluster_tree_search(m, hp, ht, hc, int(n_candidates), _dev_ptr(records_dev)))
+        return None
+    out = np.zeros(m, dtype=TREE_SEARCH_RECORD)
+    _check(lib.mg_cluster_tree_search_host(m, hp, ht, hc, int(n_candidates), out.ctypes.data_as(vp)))
+    return out
 
 
 class TrackPlan(object):

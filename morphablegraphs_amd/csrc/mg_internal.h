@@ -13,7 +13,7 @@
 #define MG_ROWTILE 16       // coefficient rows per MFMA tile (M)
 #define MG_MAX_KK 16        // k-steps of 4 -> n_components <= 64 on the MFMA path
 #define MG_BLOCK 256        // threads per workgroup of the frames kernels
-#define MG_PROFILE_SLOTS 11
+#define MG_PROFILE_SLOTS 12
 
 void mg_set_error(const char *fmt, ...);
 int mg_hip_fail(hipError_t e, const char *what);
@@ -99,6 +99,9 @@ struct mg_context {
     size_t lists_bytes = 0, lists_counters_off = 0;
     void *rccl_comm = nullptr;      // ncclComm_t after mg_dist_init
     int dist_rank = 0, dist_ranks = 1;
+    void *tree_tab_dev = nullptr;   // mg_cluster_tree_search: the per-search descriptors on the device and their host copy
+    size_t tree_tab_cap = 0;        // (rewritten only when a call's table differs from the last one's)
+    std::vector<unsigned char> tree_tab_host;
 };
 void mg_dev_free(mg_context *ctx, void *p);   // hipFree unless p lives in the context's arena
 

@@ -216,6 +216,9 @@ class HipMotionPrimitiveGenerator(object):
         self.use_transition_model = algorithm_config.get("use_transition_model", False)
         self.constrained_sampling_mode = algorithm_config.get("constrained_sampling_mode", SAMPLING_MODE_GPU_BATCH)
         self.n_cluster_search_candidates = int(algorithm_config.get("n_cluster_search_candidates", 2))
+        # "exhaustive" (default): every stored sample of the tree scored in one launch; "descend": the reference's own descent
+        # (feature_cluster_tree.py:129-187) with n_cluster_search_candidates kept per level
+        self.cluster_tree_search_method = algorithm_config.get("cluster_tree_search_method", "exhaustive")
         self.use_local_coordinates = algorithm_config.get("use_local_coordinates", True)
         # gpu_batch only: draw the candidates with the device sampler and keep them on the GPU (not sklearn's stream)
         # a distributed.MgCommunicator (or FileCommunicator) when the candidate loop is sharded over the GPUs of a node: this
@@ -312,7 +315,21 @@ class HipMotionPrimitiveGenerator(object):
     def _get_best_fit_sample_using_cluster_tree(self, graph_node, constraints, prev_frames, n_candidates=-1):
         """The reference descends the k-means / KD tree with `n_candidates` kept per level, calling the objective
         once per visited mean or sample.  At GPU batch sizes the whole tree is cheaper to score than to descend:
-        every stored sample in one launch, first minimum -- the result of find_best_example_exhaustive."""
+        every stored sample in one launch, first minimum -- the result of find_best_example_exhaustive.
+        With algorithm_config["cluster_tree_search_method"] = "descend" the reference's descent instead (its sample and
+        min_error): one launch when the constraints make a device set, else the host-driven descent that scores each level's
+        children in one batched call."""
+        if self.cluster_tree_search_method == "descend":
+            n = self.n_cluster_search_candidates if n_candidates < 1 else n_candidates
+            skeleton = getattr(constraints, "hip_skeleton", None)
+            if graph_node._tree_search_set(constraints, prev_frames, skeleton) is not None:
+                distance, s = graph_node.search_best_sample_on_device(constraints, n, prev_frames, skeleton)
+            else:
+                distance, s = graph_node.search_best_sample_batched(constraints, n, prev_frames, skeleton)
+            constraints.min_error = distance
+            return np.array(s)
+        if self.cluster_tree_search_method != "exhaustive":
+            raise ValueError("cluster_tree_search_method %r: 'exhaustive' or 'descend'" % (self.cluster_tree_search_method,))
         stored = np.asarray(graph_node.cluster_tree.data)[:, :graph_node.get_n_spatial_components()]
         best, distance = evaluate_samples_using_constraints(stored, graph_node, constraints, prev_frames, communicator=self.communicator)
         constraints.min_error = distance

@@ -10,6 +10,7 @@ from . import candidate_scoring as _cs
 
 from . import _capi
 from .candidate_scoring import constraints_to_device_form, evaluate_samples_using_constraints
+from .cluster_tree import HipFeatureClusterTree, search_on_device
 from .frame_constraints import is_frame_constraint
 from .motion_primitive import HipMotionPrimitive, get_context
 from .motion_primitive_wrapper import HipMotionPrimitiveModelWrapper
@@ -109,6 +110,52 @@ class HipMotionStateGraphNode(HipMotionPrimitiveModelWrapper):
             return self.cluster_tree.find_best_example_excluding_search_candidates(obj, data, n_candidates)
         return np.inf, None
 
+    def _tree_search_set(self, constraints, prev_frames=None, skeleton=None):
+        """The device constraint set a one-launch tree search scores against, or None when the constraints hold anything
+        mg_score_constraints does not take (trajectories, per-frame constraints)."""
+        from .candidate_scoring import alignment_from_prev_frames, cached_constraint_set
+        from .frame_constraints import is_frame_constraint
+        clist = constraints.constraints if hasattr(constraints, "constraints") else constraints
+        skeleton = skeleton if skeleton is not None else getattr(constraints, "hip_skeleton", None)
+        form = constraints_to_device_form(clist)
+        if any(is_frame_constraint(c) or c.get("type") == "trajectory" for c in form):
+            return None
+        return cached_constraint_set(self.motion_primitive._prim, form, skeleton, alignment_from_prev_frames(prev_frames, constraints, skeleton))
+
+    def _search_tree(self):
+        if not isinstance(self.cluster_tree, HipFeatureClusterTree):
+            raise NotImplementedError("node %r has no cluster tree to descend (only stored samples)" % (self.name,))
+        return self.cluster_tree
+
+    def search_best_sample_on_device(self, constraints, n_candidates, prev_frames=None, skeleton=None):
+        """search_best_sample with the reference's objective (the constraints' summed weighted errors, aligned to prev_frames
+        outside local mode) as ONE launch (mg_cluster_tree_search): (error, sample).  Adds the objectives scored to
+        constraints.evaluations."""
+        tree = self._search_tree()
+        cset = self._tree_search_set(constraints, prev_frames, skeleton)
+        if cset is None:
+            raise NotImplementedError("the one-launch tree search scores keyframe constraints only")
+        rec = search_on_device([(tree, self.motion_primitive._prim, cset)], n_candidates)[0]
+        if hasattr(constraints, "evaluations"):
+            constraints.evaluations += int(rec["evaluations"])
+        return tree.result_of_record(rec)
+
+    def search_best_sample_batched(self, constraints, n_candidates, prev_frames=None, skeleton=None):
+        """The same descent driven from the host: every level's children scored by one call of the general scoring path
+        (keyframe, trajectory and per-frame constraints alike).  (error, sample); adds to constraints.evaluations."""
+        from .candidate_scoring import alignment_from_prev_frames, errors_of_samples
+        tree = self._search_tree()
+        clist = constraints.constraints if hasattr(constraints, "constraints") else constraints
+        skeleton = skeleton if skeleton is not None else getattr(constraints, "hip_skeleton", None)
+        form = constraints_to_device_form(clist)
+        alignment = alignment_from_prev_frames(prev_frames, constraints, skeleton)
+        L = self.get_n_spatial_components()
+        value, row, _, n_eval = tree.descend(lambda ids: errors_of_samples(self.motion_primitive._prim, form, skeleton, alignment, tree.means[ids, :L]),
+                                             n_candidates)
+        if hasattr(constraints, "evaluations"):
+            constraints.evaluations += n_eval
+        return value, row
+
     def search_best_sample_gpu(self, constraints, n_samples):
         """Brute-force replacement of the cluster-tree search at GPU batch sizes: draw n_samples latents, score
         them in one launch, return (error, parameters) like search_best_sample."""
@@ -190,7 +237,11 @@ class HipMotionStateGraph(object):
                 node = HipMotionStateGraphNode(group, context=self.ctx)
                 node.init_from_dict(action_data["name"], desc)
                 if "space_partition_json" in desc:
-                    node.cluster_tree = _StoredSamples(desc["space_partition_json"]["data"])
+                    tree_data = desc["space_partition_json"]
+                    if isinstance(tree_data.get("root"), dict) and len(tree_data["root"]) > 0:
+                        node.cluster_tree = HipFeatureClusterTree.from_json(tree_data, node.get_n_spatial_components())
+                    else:   # a stub without nodes: the stored samples for the exhaustive search
+                        node.cluster_tree = _StoredSamples(tree_data["data"])
                 self.nodes[(action_data["name"], mp_name)] = node
                 group["nodes"].append(mp_name)
             self._set_node_types(group)
@@ -236,8 +287,45 @@ class HipMotionStateGraph(object):
                     self.nodes[from_node_key].outgoing_edges[to_node_key] = HipMotionStateTransition(
                         from_node_key, to_node_key, self._get_transition_type(from_node_key, to_node_key), None)
 
+    def evaluate_options(self, options, constraints_per_option, n_samples, rng_seed=None, use_cluster_trees=False, prev_frames=None,
+                         skeleton=None):
+        """GraphWalkPlanner._evaluate_options over this graph's nodes (reference graph_walk_planner.py:184-226): options are node
+        keys.  With use_cluster_trees every option whose node has a cluster tree is searched with n_candidates = 1, as
+        _evaluate_option does (:205-207), ALL of them in one launch; the other options draw n_samples candidates, score them and
+        keep the first minimum.  Returns (best_option, {option: (best_sample, min_error)})."""
+        results, searches, general = {}, [], []
+        for key in options:
+            node = self.nodes[key]
+            cons = constraints_per_option[key]
+            if use_cluster_trees and isinstance(node.cluster_tree, HipFeatureClusterTree):
+                cset = node._tree_search_set(cons, prev_frames, skeleton)
+                if cset is not None:
+                    searches.append((key, (node.cluster_tree, node.motion_primitive._prim, cset)))
+                    continue
+                results[key] = node.search_best_sample_batched(cons, 1, prev_frames, skeleton)[::-1]
+                continue
+            general.append(key)
+        if searches:
+            records = search_on_device([s for _, s in searches], 1)
+            for (key, (tree, _, _)), rec in zip(searches, records):
+                cons = constraints_per_option[key]
+                if hasattr(cons, "evaluations"):
+                    cons.evaluations += int(rec["evaluations"])
+                err, row = tree.result_of_record(rec)
+                results[key] = (row, err)
+        for key in general:
+            node = self.nodes[key]
+            if rng_seed is not None:
+                np.random.seed(rng_seed)
+            samples = node.sample_low_dimensional_vectors(n_samples)
+            results[key] = evaluate_samples_using_constraints(samples, node, constraints_per_option[key], prev_frames, skeleton)
+        errors = [results[k][1] for k in options]
+        return options[int(np.argmin(errors))], results
+
     def close(self):
         for node in self.nodes.values():
+            if isinstance(node.cluster_tree, HipFeatureClusterTree):
+                node.cluster_tree.close()
             prim = getattr(node.motion_primitive, "_prim", None)
             if prim is not None:
                 prim.close()

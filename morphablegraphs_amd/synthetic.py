@@ -171,8 +171,55 @@ def write_graph_zip(path, actions, transitions=None, start_node=None, format_ver
                     where = base if node_stats_prefixed else "elementary_action_%s/" % action
                     z.writestr(where + "%s_%s.stats" % (action, name), json.dumps(node_stats[(action, name)]))
                 if cluster_trees and (action, name) in cluster_trees:
-                    tree = {"data": np.asarray(cluster_trees[(action, name)]).tolist(), "features": [], "options": {}, "root": {}}
+                    tree = cluster_trees[(action, name)]
+                    if not isinstance(tree, dict):   # samples alone: a stub tree without nodes
+                        tree = {"data": np.asarray(tree).tolist(), "features": [], "options": {}, "root": {}}
                     z.writestr(base + "%s_%s_quaternion_cluster_tree.json" % (action, name), json.dumps(tree))
+
+
+def _kmeans(x, k, rng, iterations=8):
+    """Lloyd's k-means on the rows of x from k distinct rows drawn by rng: a label per row (clusters may come out empty)."""
+    centres = x[rng.choice(len(x), size=k, replace=False)]
+    labels = np.zeros(len(x), dtype=np.int64)
+    for _ in range(iterations):
+        labels = np.argmin(((x[:, None, :] - centres[None, :, :]) ** 2).sum(axis=2), axis=1)
+        for j in range(k):
+            members = x[labels == j]
+            if len(members):
+                centres[j] = members.mean(axis=0)
+    return labels
+
+
+def make_feature_cluster_tree(samples, n_subdivisions=4, seed=0):
+    """A FeatureClusterTree in the reference's JSON layout (space_partitioning/feature_cluster_tree.py:293-333) over `samples`
+    (n, dim), built the way its constructor builds one (:57-93), deterministically: features = the samples, a node's clusters
+    from k-means with k = n_subdivisions on its members' features, every cluster of one member a leaf; a node of at most
+    n_subdivisions members, of identical features, or whose clustering keeps all members together gets one leaf per member.
+    Means are the averages of the DATA rows (use_feature_mean False, as construction/cluster_tree_builder.py:252-254
+    writes it); the root's indices are null, as the reference writes them.  Iterative, so deep trees are no problem."""
+    data = np.asarray(samples, dtype=np.float64)
+    rng = np.random.default_rng(seed)
+    k = int(n_subdivisions)
+    root = {"mean": data.mean(axis=0).tolist(), "indices": None, "children": []}
+    stack = [(root, np.arange(len(data)))]
+    while stack:
+        node, idx = stack.pop()
+        if len(idx) <= 1:
+            continue
+        x = data[idx]
+        if len(idx) <= k or np.all(x == x[0]):
+            clusters = [idx[i:i + 1] for i in range(len(idx))]
+        else:
+            labels = _kmeans(x, k, rng)
+            clusters = [idx[labels == j] for j in range(k) if np.any(labels == j)]
+            if len(clusters) == 1:
+                clusters = [idx[i:i + 1] for i in range(len(idx))]
+        for c in clusters:
+            child = {"mean": data[c].mean(axis=0).tolist(), "indices": [int(v) for v in c], "children": []}
+            node["children"].append(child)
+            stack.append((child, c))
+    return {"data": data.tolist(), "features": data.tolist(),
+            "options": {"n_subdivisions": k, "use_feature_mean": False}, "root": root}
 
 
 def make_skeleton(n_animated=19):

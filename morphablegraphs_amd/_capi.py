@@ -7,6 +7,7 @@ only owns handles and converts NumPy arrays; the reference-shaped classes live i
 motion_primitive.py / motion_spline.py / gaussian_mixture.py.
 """
 import ctypes as C
+import functools
 import itertools
 import os
 
@@ -17,6 +18,7 @@ LIB_PATH = os.path.join(HERE, "csrc", "libmg_hip.so")   # the product library; t
 
 MG_OK = 0
 MG_ERR_INVALID_ARGUMENT = -1     # enum mg_status (include/mg_hip.h)
+MG_ERR_UNSUPPORTED = -4         # enum mg_status (include/mg_hip.h): a shape the kernels do not take
 MG_F32, MG_F64 = 0, 1
 MG_PATH_AUTO, MG_PATH_MFMA, MG_PATH_DIRECT = 0, 1, 2
 MG_ALIGN_START_POSE = -1   # mg_alignment_desc.joint: the start-pose branch of the reference's alignment
@@ -42,6 +44,20 @@ MG_TREE_MAX_DEPTH, MG_TREE_MAX_CHILDREN, MG_TREE_MAX_CANDIDATES = 64, 256, 64   
 MG_TREE_TIE, MG_TREE_NO_RESULT, MG_TREE_OVERFLOW = 1, 2, 4
 # struct mg_tree_search_record
 TREE_SEARCH_RECORD = np.dtype([("row", "<i8"), ("leaf", "<i4"), ("flags", "<i4"), ("evaluations", "<i8"), ("value", "<f8")])
+MG_FUSED_MAX_OPTIONS = 24        # options of one mg_options_step_device_counts launch (csrc/mg_options.hip)
+
+
+@functools.lru_cache(maxsize=None)
+def _option_record(stride):
+    return np.dtype([("index", "<i8"), ("error", "<f8"), ("latent", "<f8", ((stride - 16) // 8,))])
+
+
+def option_records(raw, m, stride):
+    """The result records of the planner steps (mg_options_step & co., include/mg_hip.h): m records {int64 index, float64 error,
+    float64 latent[(stride - 16) / 8]} side by side every `stride` bytes from the start of the uint8 array `raw`, copied out as a
+    structured array with the fields index, error and latent (an option's winner: the first n_gmm_dims of its latent)."""
+    return raw[:m * stride].copy().view(_option_record(stride))
+
 
 # every symbol include/mg_hip.h declares (tests check the built library exports them all)
 EXPORTED_SYMBOLS = [

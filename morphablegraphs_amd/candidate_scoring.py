@@ -355,7 +355,7 @@ def _values_key(clist, alignment):
 
 
 # bumped whenever a shared set is created, rewritten or closed: "nothing happened to any set since" is one integer comparison
-# (the planner step's whole-step shortcut, motion_state_graph.HipPrimitiveSet.evaluate_options_on_device)
+# (the planner step's whole-step shortcut, motion_state_graph.HipPrimitiveSet._constraint_sets)
 CSET_GENERATION = [0]
 
 

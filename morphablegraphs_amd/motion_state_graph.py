@@ -4,6 +4,9 @@ one GPU, and the batched form of GraphWalkPlanner's option evaluation
 n candidates, score them against the path-following constraints, keep the first minimum per option, pick
 the option with the smallest error (np.argmin over options, graph_walk_planner.py:191-192).
 Graph loading / transitions / control flow stay in the reference; only the scoring is replaced."""
+import ctypes as C
+from collections import namedtuple
+
 import numpy as np
 
 from . import candidate_scoring as _cs
@@ -409,9 +412,8 @@ def constraint_fingerprint(clist):
         return None
 
 
-def _options_frame_lists(plan, steps, fast, extras, n, dtype):
-    """mg_options_frame_lists for the options in `fast` [(k, TrackScorer | None)]: [(index, error, winning latent as float64)]."""
-    import ctypes as C
+def _options_frame_lists(plan, fast, extras):
+    """mg_options_frame_lists for the options in `fast` [(k, TrackScorer | None)]: their result records (_capi.option_records)."""
     vp, m = C.c_void_p, len(fast)
     R, Q = _capi.MG_TRACK_MAX_REQUESTS, _capi.MG_FRAME_LIST_MAX
     prims, plans, lats, errs = (vp * m)(), (vp * m)(), (vp * m)(), (vp * m)()
@@ -419,16 +421,16 @@ def _options_frame_lists(plan, steps, fast, extras, n, dtype):
     grids, tracks, cons = (vp * (m * R))(), (vp * (m * R))(), (vp * (m * Q))()
     req_of = (C.c_int32 * (m * Q))()
     als, al_ptrs = [], (vp * m)()
-    ctx = steps[fast[0][0]][3]
+    ctx = plan.options[fast[0][0]].ctx
     for j, (k, scorer) in enumerate(fast):
-        name, node, prim, _, d_x, d_e, d_r, L, pvals = steps[k]
-        prims[j], lats[j], errs[j], lds[j] = prim.handle, _capi._dev_ptr(d_x), _capi._dev_ptr(d_e), L
-        alignment, sk = extras[k][2], extras[k][3]
+        opt = plan.options[k]
+        prims[j], lats[j], errs[j], lds[j] = opt.prim.handle, _capi._dev_ptr(opt.x), _capi._dev_ptr(opt.errors), opt.width
+        alignment = extras[k].alignment
         if scorer is not None:
             if not scorer.valid():
                 raise _capi.MGError("a track scorer's plan or trajectories were closed under it")
             plans[j], ncons[j] = scorer.plan.handle, scorer.m
-            bufs = scorer._track_buffers(n)
+            bufs = scorer._track_buffers(plan.n)
             for q, (g, b) in enumerate(zip(scorer.grids, bufs)):
                 grids[j * R + q] = g.handle if g is not None else None
                 tracks[j * R + q] = _capi._dev_ptr(b)
@@ -439,23 +441,121 @@ def _options_frame_lists(plan, steps, fast, extras, n, dtype):
                 al = _capi.ConstraintSet._marshal_alignment(alignment, scorer.plan.skeleton)
                 als.append(al)
                 al_ptrs[j] = C.addressof(al)
-    L_max = max(steps[k][7] for k, _ in fast)
-    stride = 16 + 8 * L_max
-    key = ("frame_lists_results", m, stride)
-    bufs = plan.get(key)
+    stride = 16 + 8 * max(plan.options[k].width for k, _ in fast)
+    bufs = plan.frame_lists.get((m, stride))
     if bufs is None:
-        bufs = plan[key] = (ctx.malloc(m * stride), np.empty(m * stride, dtype=np.uint8))
+        bufs = plan.frame_lists[(m, stride)] = (ctx.malloc(m * stride), np.empty(m * stride, dtype=np.uint8))
     d_res, host = bufs
-    code = _capi.MG_F64 if np.dtype(dtype) == np.float64 else _capi.MG_F32
-    _capi._check(ctx.lib.mg_options_frame_lists(m, prims, plans, lats, code, n, lds, al_ptrs, grids, tracks, ncons, cons, req_of, errs, d_res.ptr, stride,
-                                                 host.ctypes.data_as(vp)))
-    rec = host.reshape(m, stride)
-    out = []
-    for j in range(m):
-        idx = int(rec[j, 0:8].view(np.int64)[0])
-        err = float(rec[j, 8:16].view(np.float64)[0])
-        out.append((idx, err, rec[j, 16:].view(np.float64).copy()))
-    return out
+    _capi._check(ctx.lib.mg_options_frame_lists(m, prims, plans, lats, plan.code, plan.n, lds, al_ptrs, grids, tracks, ncons, cons, req_of, errs,
+                                                 d_res.ptr, stride, host.ctypes.data_as(vp)))
+    return _capi.option_records(host, m, stride)
+
+
+# one option of a planner step: the device buffers of its candidates (n x width), their errors and its result record; its full
+# latent width and the normalised mixture weights its component counts are drawn with
+_Option = namedtuple("_Option", "name node prim ctx x errors record width weights")
+# the whole step's shortcut: a flat copy of the constraint mapping, CSET_GENERATION, the sets and general routes made from it
+_Whole = namedtuple("_Whole", "mapping generation csets general")
+# an option's memo: a flat copy of its constraints at the last step, the set made from them and that set's cached_values then
+_Memo = namedtuple("_Memo", "constraints cset values")
+# what _mixed_step adds to an option's keyframe errors
+_Extras = namedtuple("_Extras", "trajectories frames alignment skeleton")
+
+
+class _StepPlan(object):
+    """Everything about a planner step that does not change from step to step, built once per (options, n, dtype): the options'
+    device buffers (no allocation inside a step), the argument arrays of the C calls (no ctypes object is made inside a step),
+    the host block the result records land in, the counts.  Only its methods write the argument arrays."""
+
+    def __init__(self, options, n, dtype):
+        self.options, self.n, self.dtype = options, n, dtype
+        self.code = _capi.MG_F64 if dtype == np.float64 else _capi.MG_F32
+        m = len(options)
+        # all primitives in one context: the whole step is one C call (mg_options_step & co.), else mg_option_step per option
+        self.fused = m > 0 and all(opt.ctx is options[0].ctx for opt in options)
+        self.counts = np.zeros((max(m, 1), max([len(opt.weights) for opt in options] + [1])), dtype=np.int64)
+        self.memo = [None] * m          # per option: _Memo, or None
+        self.whole = None               # _Whole, or None
+        self.track_scorers = {}         # _mixed_step's TrackScorers
+        self.frame_lists = {}           # _options_frame_lists' result blocks
+        self._bound = None
+        vp, mm = C.c_void_p, max(m, 1)
+        self.prims = (vp * mm)(*[opt.prim.handle for opt in options])
+        self.csets, self.seeds = (vp * mm)(), (C.c_uint64 * mm)()
+        self.cnts = (vp * mm)(*[self.counts[k].ctypes.data for k in range(m)])
+        self.xs = (vp * mm)(*[_capi._dev_ptr(opt.x).value for opt in options])
+        self.errs = (vp * mm)(*[_capi._dev_ptr(opt.errors).value for opt in options])
+        self.lds = (C.c_int64 * mm)(*[opt.width for opt in options])
+        self._karange, self._seeds_np = np.arange(m, dtype=np.uint64), np.ctypeslib.as_array(self.seeds)[:m]
+        if self.fused:
+            self.lib = options[0].prim.lib
+            self.stride = 16 + 8 * max(opt.width for opt in options)
+            self.shared = options[0].ctx.malloc(m * self.stride)
+            self.host = np.empty(m * self.stride, dtype=np.uint8)
+            self.device_counts = np.zeros((m, 16), dtype=np.int64)
+            self.shared_ptr, self.host_ptr = self.shared.ptr, self.host.ctypes.data_as(vp)
+            self.device_counts_ptr = self.device_counts.ctypes.data_as(vp)
+
+    def option(self, name):
+        return next(opt for opt in self.options if opt.name == name)
+
+    def bind(self, csets):
+        """Make `csets` (a ConstraintSet per option) the sets the next launch scores against.  The only writer of the sets' argument
+        array: binding other sets than the whole-step shortcut's drops the shortcut, which would otherwise score against them."""
+        if csets is self._bound:
+            return
+        if self.whole is not None and csets is not self.whole.csets:
+            self.whole = None
+        for k, cs in enumerate(csets):
+            self.csets[k] = cs.handle.value
+        self._bound = csets
+
+    def seed(self, seed):
+        """Option k's candidates are drawn with the key seed + k (modulo 2^64)."""
+        np.add(self._karange, np.uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), out=self._seeds_np)
+
+    def draw_counts(self):
+        """Every option's component counts, in option order, from NumPy's global stream."""
+        counts, multinomial, n = self.counts, np.random.multinomial, self.n
+        for k, opt in enumerate(self.options):
+            counts[k, :len(opt.weights)] = multinomial(n, opt.weights)
+
+    def launch(self, device_counts=False, rows=None):
+        """mg_options_step, or mg_options_step_device_counts (counts left in self.device_counts), or for rows = (n of the whole draw,
+        first row) mg_options_step_rows; without one context mg_option_step per option.  Returns MG_OK or MG_ERR_UNSUPPORTED (the
+        one-launch kernel does not take the step, nothing has run); any other status raises."""
+        m, n = len(self.options), self.n
+        if not self.fused:
+            for k, opt in enumerate(self.options):
+                _capi._check(opt.prim.lib.mg_option_step(opt.prim.handle, self.csets[k], n, self.counts[k].ctypes.data, self.seeds[k], opt.x.ptr,
+                                                         self.code, opt.width, opt.errors.ptr, opt.record.ptr))
+            return _capi.MG_OK
+        if rows is not None:
+            rc = self.lib.mg_options_step_rows(m, self.prims, self.csets, rows[0], self.cnts, self.seeds, rows[1], n, self.xs, self.code, self.lds,
+                                               self.errs, self.shared_ptr, self.stride, self.host_ptr)
+        elif device_counts:
+            rc = self.lib.mg_options_step_device_counts(m, self.prims, self.csets, n, self.seeds, self.xs, self.code, self.lds, self.errs,
+                                                        self.shared_ptr, self.stride, self.host_ptr, self.device_counts_ptr)
+        else:
+            rc = self.lib.mg_options_step(m, self.prims, self.csets, n, self.cnts, self.seeds, self.xs, self.code, self.lds, self.errs,
+                                          self.shared_ptr, self.stride, self.host_ptr)
+        if rc != _capi.MG_OK and rc != _capi.MG_ERR_UNSUPPORTED:
+            _capi._check(rc)
+        return rc
+
+    def results(self):
+        """({option: (winning latent as float64, error)}, the index of the first minimum over the options, np.argmin's) of the last launch."""
+        if self.fused:
+            rec = _capi.option_records(self.host, len(self.options), self.stride)     # a copy: the next step reuses the host block
+            lat, errors = rec["latent"], rec["error"]      # lat: (m, widest L), the winners already rounded to the caller's type
+            errs = errors.tolist()
+            return {opt.name: (lat[k, :opt.width], errs[k]) for k, opt in enumerate(self.options)}, int(errors.argmin())
+        results = {}
+        for opt in self.options:
+            size = 16 + 8 * opt.width
+            rec = _capi.option_records(opt.ctx.download(opt.record, (size,), np.uint8), 1, size)     # synchronises this option's stream
+            results[opt.name] = (rec["latent"][0].astype(self.dtype).astype(np.float64), float(rec["error"][0]))
+        return results, int(np.argmin([results[opt.name][1] for opt in self.options]))
 
 
 class HipPrimitiveSet(object):
@@ -465,7 +565,9 @@ class HipPrimitiveSet(object):
     def __init__(self, primitives_json, context=None, device=0, separate_streams=False):
         self.ctx = context or get_context(device)
         self.nodes = {}
-        self._buffers = {}
+        self._plans = {}
+        self._buffers = {}          # (option, n, dtype.str) -> (candidates, errors, result record), shared by the plans holding it
+        self._last_counts = None
         for data in primitives_json:
             ctx = _capi.Context(device) if separate_streams else self.ctx
             p = HipMotionPrimitive(None, context=ctx)
@@ -475,38 +577,32 @@ class HipPrimitiveSet(object):
     @property
     def last_counts(self):
         """{option: component counts} the device drew in the last step with device_counts=True."""
-        raw = getattr(self, "_last_counts", None)
-        if raw is None:
+        plan = self._last_counts
+        if plan is None:
             return None
-        cnt, steps = raw
-        return {st[0]: cnt[k, :len(st[8])].copy() for k, st in enumerate(steps)}
+        return {opt.name: plan.device_counts[k, :len(opt.weights)].copy() for k, opt in enumerate(plan.options)}
 
-    def _repeat_step(self, plan, options, n, seed, dt, device_counts):
-        """evaluate_options_on_device for a step whose constraint sets are the last step's (the caller has checked): the C call and
-        the unpacking of the result records, nothing else.  None: the device cannot draw this step's counts (host route)."""
-        steps = plan["steps"]
-        m, stride, host = len(steps), plan["stride"], plan["host"]
-        code = _capi.MG_F64 if dt == np.float64 else _capi.MG_F32
-        np.add(plan["karange"], np.uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), out=plan["seeds_np"])
-        if device_counts and m <= 24:
-            rc = plan["lib"].mg_options_step_device_counts(m, plan["prims"], plan["csets"], n, plan["seeds"], plan["xs"], code, plan["lds"],
-                                                           plan["errs"], plan["shared_ptr"], stride, plan["host_ptr"], plan["device_counts_ptr"])
-            if rc == -4:
-                return None
-            self._last_counts = (plan["device_counts"], steps)
-        else:
-            counts, multinomial = plan["counts"], np.random.multinomial
-            for k, st in enumerate(steps):   # the component counts, in option order, from NumPy's global stream
-                counts[k, :len(st[8])] = multinomial(n, st[8])
-            rc = plan["lib"].mg_options_step(m, plan["prims"], plan["csets"], n, plan["cnts"], plan["seeds"], plan["xs"], code, plan["lds"],
-                                             plan["errs"], plan["shared_ptr"], stride, plan["host_ptr"])
-        if rc != 0:
-            _capi._check(rc)
-        rec = host[:m * stride].copy().reshape(m, stride)          # one copy: the host block is reused by the next step
-        errs = rec[:, 8:16].copy().view(np.float64)[:, 0].tolist()
-        lat = rec[:, 16:].copy().view(np.float64)                    # (m, widest L): the winners, already rounded to the caller's type
-        results = {st[0]: (lat[k, :st[7]], errs[k]) for k, st in enumerate(steps)}
-        return options[min(range(m), key=errs.__getitem__)], results      # first minimum (the kernel never reports NaN)
+    def step_plan(self, options, n, dtype):
+        """The _StepPlan of a step over `options` with n candidates each, made on first use: per option (.options, .option(name))
+        the device buffers the step leaves its candidates, errors and result record in."""
+        dtype = _DTYPES.get(dtype) or np.dtype(dtype)
+        key = (options if type(options) is tuple else tuple(options), int(n), dtype.str)
+        plan = self._plans.get(key)
+        if plan is None:
+            n, opts = key[1], []
+            for name in key[0]:
+                node = self.nodes[name]
+                prim = node._prim
+                L = prim.n_gmm_dims          # the winner comes back at full width (spatial + time latents)
+                bkey = (name, n, dtype.str)
+                bufs = self._buffers.get(bkey)
+                if bufs is None:
+                    bufs = self._buffers[bkey] = (prim.ctx.malloc(max(n, 1) * L * dtype.itemsize), prim.ctx.malloc(max(n, 1) * 8),
+                                                  prim.ctx.malloc(16 + 8 * L))
+                weights = np.asarray(node.gaussian_mixture_model.weights_, dtype=np.float64)
+                opts.append(_Option(name, node, prim, prim.ctx, bufs[0], bufs[1], bufs[2], L, weights / weights.sum()))
+            plan = self._plans[key] = _StepPlan(opts, n, dtype)
+        return plan
 
     def evaluate_options_on_device(self, options, constraints_per_option, n_samples, seed=0, dtype=np.float32,
                                    prev_frames=None, skeleton=None, communicator=None, device_counts=False):
@@ -528,171 +624,125 @@ class HipPrimitiveSet(object):
         anyway) instead of 16 x np.random.multinomial on the host, which is most of a step's host time; steps the one-launch
         kernel does not cover fall back to the host draw.  self.last_counts holds the counts of the last such step.
         Returns (best_option, {name: (best_sample, min_error)})."""
-        n = int(n_samples)
-        # The step a planner repeats: same options, same batch, same plain constraint values as last time, nothing in between
-        # (see "The whole step's shortcut" below) -- everything the C call needs is in the plan, made once.
-        dt = _DTYPES.get(dtype) or np.dtype(dtype)
-        if communicator is None and prev_frames is None and skeleton is None and type(constraints_per_option) is dict:
-            plan = self._buffers.get(("plan", options if type(options) is tuple else tuple(options), n, dt.str))
-            whole = plan.get("whole") if plan is not None else None
-            if whole is not None and whole[1] == _cs.CSET_GENERATION[0] and len(constraints_per_option) == len(whole[0]) and \
-                    plan["one_context"] and _same_mapping(constraints_per_option, whole[0]):
-                out = self._repeat_step(plan, options, n, seed, dt, device_counts)
-                if out is not None:
-                    return out
-        cached_constraint_set, alignment_from_prev_frames, CSET_GENERATION = _cs.cached_constraint_set, _cs.alignment_from_prev_frames, _cs.CSET_GENERATION
-        import ctypes as C
         if communicator is not None and communicator.world > 1:
-            from . import distributed
-            cmd = {"op": "options_step", "options": list(options), "n_samples": n, "seed": int(seed), "dtype": np.dtype(dtype).name,
-                   "skeleton": skeleton is not None, "counts": {}, "constraints": {}, "alignments": {}, "widths": {}}
-            for name in options:
-                node = self.nodes[name]
-                cons = constraints_per_option[name]
-                clist = cons.constraints if hasattr(cons, "constraints") else cons
-                sk = skeleton if skeleton is not None else getattr(cons, "hip_skeleton", None)
-                w = np.asarray(node.gaussian_mixture_model.weights_, dtype=np.float64)
-                cmd["counts"][name] = np.random.multinomial(n, w / w.sum()).astype(np.int64)
-                cmd["constraints"][name] = constraints_to_device_form(clist)
-                cmd["alignments"][name] = alignment_from_prev_frames(prev_frames, cons, sk)
-                cmd["widths"][name] = node._prim.n_gmm_dims
-            local = {"__primitive_set__": self, "__skeleton__": skeleton}
-            if any(is_frame_constraint(c) or c.get("type") == "trajectory" for name in options for c in cmd["constraints"][name]):
-                # an option with a trajectory or per-frame constraint: the step as one sample-and-evaluate command per option (every
-                # rank holds the primitives under their names), the same draws
-                local.update(self.nodes)
-                out = {}
-                for k, name in enumerate(options):
-                    _, err, lat = distributed.run_command(communicator, local, {
-                        "op": "sample_and_evaluate", "node": name, "constraints": cmd["constraints"][name], "alignment": cmd["alignments"][name],
-                        "skeleton": cmd["skeleton"], "counts": cmd["counts"][name], "seed": int(seed) + k, "dtype": cmd["dtype"],
-                        "width": cmd["widths"][name]})
-                    out[name] = (np.asarray(lat, dtype=np.float64), err)
-            else:
-                out = distributed.run_command(communicator, local, cmd)
-            results = {name: (out[name][0].astype(dtype).astype(np.float64), out[name][1]) for name in options}
-            errors = [results[nm][1] for nm in options]
-            return options[int(np.argmin(errors))], results
-        code = _capi.MG_F64 if np.dtype(dtype) == np.float64 else _capi.MG_F32
-        plan = self._step_plan(tuple(options), n, np.dtype(dtype))
-        steps = plan["steps"]
-        csets, general = [], []
-        memo = plan.setdefault("memo", [None] * len(steps))
-        multinomial = np.random.multinomial
+            return self._distributed_step(options, constraints_per_option, int(n_samples), seed, dtype, prev_frames, skeleton, communicator)
+        plan = self.step_plan(options, n_samples, dtype)
+        csets, general = self._constraint_sets(plan, constraints_per_option, prev_frames, skeleton)
+        if None in csets:      # an option with trajectory or per-frame constraints: the mixed step, else option by option
+            plan.draw_counts()
+            results = self._mixed_step(plan, csets, general, seed) if plan.fused else None
+            if results is None:
+                results = self._option_chains(plan, constraints_per_option, general, seed)
+            return options[int(np.argmin([results[nm][1] for nm in options]))], results
+        plan.bind(csets)
+        plan.seed(seed)
+        # device_counts: the whole step on the device -- counts (mg_options_counts_kernel), candidates, scores, first minima; records
+        # and counts arrive in pinned host memory, one synchronisation.  MG_ERR_UNSUPPORTED (an option the one-launch kernel does
+        # not cover, nothing has run): the host draw.
+        if device_counts and plan.fused and len(plan.options) <= _capi.MG_FUSED_MAX_OPTIONS and plan.launch(device_counts=True) == _capi.MG_OK:
+            self._last_counts = plan
+        else:
+            plan.draw_counts()
+            _capi._check(plan.launch())
+        results, best = plan.results()
+        return options[best], results
+
+    def _constraint_sets(self, plan, constraints_per_option, prev_frames, skeleton):
+        """The step's keyframe constraint sets, one per option (None for an option with trajectory or per-frame constraints), and per
+        option what the general chain scores with, (device form, alignment, skeleton) or None where the memo gave the set."""
+        local = prev_frames is None and skeleton is None
         # The whole step's shortcut.  A planner that asks the same questions as at the last step -- every option's constraints plain
         # device-form dicts with the values they had (ONE comparison by value of the whole mapping against a copy that shares nothing
         # mutable with the caller's: a target rewritten in place is seen), no shared set created, rewritten or closed since (one
         # integer) -- scores against the sets the last step used: no per-option host work at all.
-        whole = plan.get("whole")
-        if whole is not None and prev_frames is None and skeleton is None and whole[1] == CSET_GENERATION[0] and \
-                type(constraints_per_option) is dict and len(constraints_per_option) == len(whole[0]) and _same_mapping(constraints_per_option, whole[0]):
-            csets, general = whole[2], whole[3]
-            steps_loop = ()
-        else:
-            steps_loop = steps
-            plan["whole"] = None
-        for k, (name, node, prim, ctx, d_x, d_e, d_r, L, pvals) in enumerate(steps_loop):
-            cons = constraints_per_option[name]
+        whole = plan.whole
+        if whole is not None and local and whole.generation == _cs.CSET_GENERATION[0] and type(constraints_per_option) is dict and \
+                len(constraints_per_option) == len(whole.mapping) and _same_mapping(constraints_per_option, whole.mapping):
+            return whole.csets, whole.general
+        plan.whole = None
+        memo, csets, general = plan.memo, [], []
+        for k, opt in enumerate(plan.options):
+            cons = constraints_per_option[opt.name]
             clist = cons.constraints if hasattr(cons, "constraints") else cons
             # A planner asks the same questions step after step: when an option's constraints are plain device-form dicts whose
             # every value is what it was at the last step (compared value by value: callers rewrite targets in place), the set of
             # the last step is the set of this one.  Anything else -- reference objects, a previous motion to align to -- takes the
             # general route (device form, structure and values keys, the shared cache).
             last = memo[k]
-            if last is not None and prev_frames is None and skeleton is None and _same_constraints(clist, last[0]) and last[1].handle and \
-                    last[1].cached_values is last[2] and getattr(cons, "hip_skeleton", None) is None and getattr(cons, "is_local", True):
-                csets.append(last[1])      # (cached_values: nobody else rewrote the shared set)
+            if last is not None and local and _same_constraints(clist, last.constraints) and last.cset.handle and \
+                    last.cset.cached_values is last.values and getattr(cons, "hip_skeleton", None) is None and getattr(cons, "is_local", True):
+                csets.append(last.cset)      # (cached_values: nobody else rewrote the shared set)
                 general.append(None)
-            else:
-                fp = flat_constraint_copy(clist) if prev_frames is None and skeleton is None else None
-                sk = skeleton if skeleton is not None else getattr(cons, "hip_skeleton", None)
-                form = constraints_to_device_form(clist)
-                alignment = alignment_from_prev_frames(prev_frames, cons, sk)
-                if any(is_frame_constraint(c) or c.get("type") == "trajectory" for c in form):
-                    # trajectory and per-frame constraints are not keyframe channels: this option is scored by the general chain
-                    # (device sampler, fused scorers, the per-frame kernels adding to the same errors, first minimum)
-                    csets.append(None)
-                    general.append((form, alignment, sk))
-                    memo[k] = None
-                    continue
-                cs = cached_constraint_set(prim, form, sk, alignment)
-                csets.append(cs)
-                general.append((form, alignment, sk))
-                memo[k] = (fp, cs, cs.cached_values) if fp is not None else None
-        if steps_loop and prev_frames is None and skeleton is None and type(constraints_per_option) is dict and len(constraints_per_option) == len(steps) and \
-                all(m is not None for m in memo) and all(cs is not None for cs in csets) and \
-                all(getattr(constraints_per_option[st[0]], "hip_skeleton", None) is None for st in steps):
-            plan["whole"] = ({st[0]: memo[k][0] for k, st in enumerate(steps)}, CSET_GENERATION[0], csets, general)
-        on_device = bool(device_counts) and plan["one_context"] and steps and len(steps) <= 24 and all(cs is not None for cs in csets)
-        if on_device:
-            # the whole step on the device: counts (mg_options_counts_kernel), candidates, scores, first minima; records and
-            # counts arrive in pinned host memory, one synchronisation
-            m, stride, host = len(steps), plan["stride"], plan["host"]
-            if steps_loop:
-                for k, cs in enumerate(csets):
-                    plan["csets"][k] = cs.handle.value
-            np.add(plan["karange"], np.uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), out=plan["seeds_np"])
-            rc = plan["lib"].mg_options_step_device_counts(m, plan["prims"], plan["csets"], n, plan["seeds"], plan["xs"], code, plan["lds"],
-                                                           plan["errs"], plan["shared_ptr"], stride, plan["host_ptr"], plan["device_counts_ptr"])
-            if rc == -4:           # MG_ERR_UNSUPPORTED: an option the one-launch kernel does not cover -- host draw below
-                on_device = False
-            else:
-                if rc != 0:
-                    _capi._check(rc)
-                self._last_counts = (plan["device_counts"], steps)
-                rec = host[:m * stride].copy().reshape(m, stride)
-                errs = rec[:, 8:16].copy().view(np.float64)[:, 0].tolist()
-                lat = rec[:, 16:].copy().view(np.float64)
-                results = {st[0]: (lat[k, :st[7]], errs[k]) for k, st in enumerate(steps)}
-                return options[int(np.argmin(errs))], results
-        for k, st in enumerate(steps):   # the component counts, in option order, from NumPy's global stream
-            plan["counts"][k, :len(st[8])] = multinomial(n, st[8])
-        if any(cs is None for cs in csets) and plan["one_context"] and steps:
-            mixed = self._mixed_step(plan, steps, csets, general, n, seed, dtype, code)
-            if mixed is not None:
-                return options[int(np.argmin([mixed[nm][1] for nm in options]))], mixed
-        if any(cs is None for cs in csets):
-            # at least one option needs the general chain and the mixed step does not cover it: the whole step goes option by option
-            # (same draws: the sampler is keyed by seed + option index and the counts above)
-            from .candidate_scoring import sample_rows_and_first_minimum
-            results = {}
-            for k, (name, node, prim, ctx, d_x, d_e, d_r, L, pvals) in enumerate(steps):
-                form, alignment, sk = general[k] if general[k] is not None else (constraints_to_device_form(
-                    constraints_per_option[name].constraints if hasattr(constraints_per_option[name], "constraints") else constraints_per_option[name]), None, None)
-                idx, err, lat = sample_rows_and_first_minimum(node, form, alignment, plan["counts"][k, :len(pvals)].copy(), int(seed) + k, 0, n,
-                                                              skeleton=sk, dtype=dtype)
-                results[name] = (np.asarray(lat, dtype=np.float64), err)
-            errors = [results[nm][1] for nm in options]
-            return options[int(np.argmin(errors))], results
+                continue
+            fp = flat_constraint_copy(clist) if local else None
+            sk = skeleton if skeleton is not None else getattr(cons, "hip_skeleton", None)
+            form = constraints_to_device_form(clist)
+            alignment = _cs.alignment_from_prev_frames(prev_frames, cons, sk)
+            general.append((form, alignment, sk))
+            if any(is_frame_constraint(c) or c.get("type") == "trajectory" for c in form):
+                # trajectory and per-frame constraints are not keyframe channels: this option is scored by the mixed step or the
+                # general chain (device sampler, fused scorers, the per-frame kernels adding to the same errors, first minimum)
+                csets.append(None)
+                memo[k] = None
+                continue
+            cs = _cs.cached_constraint_set(opt.prim, form, sk, alignment)
+            csets.append(cs)
+            memo[k] = _Memo(fp, cs, cs.cached_values) if fp is not None else None
+        if local and type(constraints_per_option) is dict and len(constraints_per_option) == len(plan.options) and None not in memo and \
+                None not in csets and all(getattr(constraints_per_option[opt.name], "hip_skeleton", None) is None for opt in plan.options):
+            plan.whole = _Whole({opt.name: last.constraints for opt, last in zip(plan.options, memo)}, _cs.CSET_GENERATION[0], csets, general)
+        return csets, general
+
+    def _option_chains(self, plan, constraints_per_option, general, seed):
+        """The step option by option through the general chain (sample_rows_and_first_minimum): the same draws -- the sampler is keyed
+        by seed + option index, the counts are the plan's."""
+        from .candidate_scoring import sample_rows_and_first_minimum
         results = {}
-        if plan["one_context"] and steps:
-            # one C call, ONE launch and ONE read-back for the whole step (mg_options_step): the result records side by side
-            m, stride, host = len(steps), plan["stride"], plan["host"]
-            if steps_loop:
-                for k, cs in enumerate(csets):
-                    plan["csets"][k] = cs.handle.value
-            np.add(plan["karange"], np.uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), out=plan["seeds_np"])
-            rc = plan["lib"].mg_options_step(m, plan["prims"], plan["csets"], n, plan["cnts"], plan["seeds"], plan["xs"], code, plan["lds"],
-                                             plan["errs"], plan["shared_ptr"], stride, plan["host_ptr"])
-            if rc != 0:
-                _capi._check(rc)
-            rec = host[:m * stride].copy().reshape(m, stride)          # one copy: the host block is reused by the next step
-            errs = rec[:, 8:16].copy().view(np.float64)[:, 0].tolist()
-            lat = rec[:, 16:].copy().view(np.float64)                    # (m, widest L): the winners, already rounded to the caller's type
-            results = {st[0]: (lat[k, :st[7]], errs[k]) for k, st in enumerate(steps)}
-            return options[int(np.argmin(errs))], results
+        for k, opt in enumerate(plan.options):
+            if general[k] is not None:
+                form, alignment, sk = general[k]
+            else:
+                cons = constraints_per_option[opt.name]
+                form, alignment, sk = constraints_to_device_form(cons.constraints if hasattr(cons, "constraints") else cons), None, None
+            idx, err, lat = sample_rows_and_first_minimum(opt.node, form, alignment, plan.counts[k, :len(opt.weights)].copy(), int(seed) + k, 0,
+                                                          plan.n, skeleton=sk, dtype=plan.dtype)
+            results[opt.name] = (np.asarray(lat, dtype=np.float64), err)
+        return results
+
+    def _distributed_step(self, options, constraints_per_option, n, seed, dtype, prev_frames, skeleton, communicator):
+        """evaluate_options_on_device over communicator.world > 1 ranks."""
+        from . import distributed
+        cmd = {"op": "options_step", "options": list(options), "n_samples": n, "seed": int(seed), "dtype": np.dtype(dtype).name,
+               "skeleton": skeleton is not None, "counts": {}, "constraints": {}, "alignments": {}, "widths": {}}
+        for name in options:
+            node = self.nodes[name]
+            cons = constraints_per_option[name]
+            clist = cons.constraints if hasattr(cons, "constraints") else cons
+            sk = skeleton if skeleton is not None else getattr(cons, "hip_skeleton", None)
+            w = np.asarray(node.gaussian_mixture_model.weights_, dtype=np.float64)
+            cmd["counts"][name] = np.random.multinomial(n, w / w.sum()).astype(np.int64)
+            cmd["constraints"][name] = constraints_to_device_form(clist)
+            cmd["alignments"][name] = _cs.alignment_from_prev_frames(prev_frames, cons, sk)
+            cmd["widths"][name] = node._prim.n_gmm_dims
+        local = {"__primitive_set__": self, "__skeleton__": skeleton}
+        if any(is_frame_constraint(c) or c.get("type") == "trajectory" for name in options for c in cmd["constraints"][name]):
+            # an option with a trajectory or per-frame constraint: the step as one sample-and-evaluate command per option (every
+            # rank holds the primitives under their names), the same draws
+            local.update(self.nodes)
+            out = {}
+            for k, name in enumerate(options):
+                _, err, lat = distributed.run_command(communicator, local, {
+                    "op": "sample_and_evaluate", "node": name, "constraints": cmd["constraints"][name], "alignment": cmd["alignments"][name],
+                    "skeleton": cmd["skeleton"], "counts": cmd["counts"][name], "seed": int(seed) + k, "dtype": cmd["dtype"],
+                    "width": cmd["widths"][name]})
+                out[name] = (np.asarray(lat, dtype=np.float64), err)
         else:
-            for k, (name, node, prim, ctx, d_x, d_e, d_r, L, pvals) in enumerate(steps):
-                _capi._check(prim.lib.mg_option_step(prim.handle, csets[k].handle, n, plan["counts"][k].ctypes.data, int(seed) + k, d_x.ptr, code, L,
-                                                     d_e.ptr, d_r.ptr))
-            for name, node, prim, ctx, d_x, d_e, d_r, L, pvals in steps:
-                raw = ctx.download(d_r, (16 + 8 * L,), np.uint8)       # synchronises this option's stream
-                err = float(raw[8:16].view(np.float64)[0])
-                results[name] = (raw[16:].view(np.float64).astype(dtype).astype(np.float64), err)
-        errors = [results[n][1] for n in options]
+            out = distributed.run_command(communicator, local, cmd)
+        results = {name: (out[name][0].astype(dtype).astype(np.float64), out[name][1]) for name in options}
+        errors = [results[nm][1] for nm in options]
         return options[int(np.argmin(errors))], results
 
-    def _mixed_step(self, plan, steps, csets, general, n, seed, dtype, code):
+    def _mixed_step(self, plan, csets, general, seed):
         """A planner step in which some options carry trajectory or per-frame constraints (csets[k] is None for them): ONE launch
         still draws every option's candidates and scores their KEYFRAME constraints (mg_options_step, component counts already in
         the plan); the options with more then add the rest to their errors where the launch left them -- one launch per root
@@ -702,9 +752,9 @@ class HipPrimitiveSet(object):
         option without keyframe constraints, a trajectory aligned by another node than the root) -- the caller goes option by option."""
         from .candidate_scoring import cached_constraint_set, cached_trajectory, release_trajectory, split_trajectories
         from .frame_constraints import TrackScorer, split_frame_constraints, add_frame_constraints_dev
-        plan["whole"] = None          # this step rewrites plan["csets"]: the whole-step shortcut must not score against them
+        opts, n, dtype = plan.options, plan.n, plan.dtype
         extras, sets = {}, list(csets)
-        for k, st in enumerate(steps):
+        for k, opt in enumerate(opts):
             if sets[k] is not None:
                 continue
             form, alignment, sk = general[k]
@@ -714,35 +764,25 @@ class HipPrimitiveSet(object):
                 return None
             if alignment is not None and trajectories and alignment.get("joint", 0) not in (0, _capi.MG_ALIGN_START_POSE):
                 return None
-            sets[k] = cached_constraint_set(st[2], keyframes, sk, alignment)
-            extras[k] = (trajectories, frames, alignment, sk)
-        m, stride, host = len(steps), plan["stride"], plan["host"]
-        for k, cs in enumerate(sets):
-            plan["csets"][k] = cs.handle.value
-        np.add(plan["karange"], np.uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), out=plan["seeds_np"])
-        rc = plan["lib"].mg_options_step(m, plan["prims"], plan["csets"], n, plan["cnts"], plan["seeds"], plan["xs"], code, plan["lds"],
-                                         plan["errs"], plan["shared_ptr"], stride, plan["host_ptr"])
-        if rc == -4:      # MG_ERR_UNSUPPORTED: an option the one-launch kernel does not take
+            sets[k] = cached_constraint_set(opt.prim, keyframes, sk, alignment)
+            extras[k] = _Extras(trajectories, frames, alignment, sk)
+        plan.bind(sets)
+        plan.seed(seed)
+        if plan.launch() == _capi.MG_ERR_UNSUPPORTED:      # an option the one-launch kernel does not take
             return None
-        if rc != 0:
-            _capi._check(rc)
-        rec = host[:m * stride].copy().reshape(m, stride)
-        errs = rec[:, 8:16].copy().view(np.float64)[:, 0].tolist()
-        lat = rec[:, 16:].copy().view(np.float64)
-        results = {st[0]: (lat[k, :st[7]], errs[k]) for k, st in enumerate(steps) if k not in extras}
-        scorers = plan.setdefault("track_scorers", {})
+        results = plan.results()[0]       # (the options in `extras` are replaced below)
+        scorers = plan.track_scorers
         # the options' trajectory constraints round by round (the j-th of every option that has one): ONE launch per round
         # (mg_score_trajectories) -- an option's own additions stay in its list's order
-        for j in range(max(len(e[0]) for e in extras.values())):
-            ks = [k for k, e in extras.items() if len(e[0]) > j]
-            cj = [extras[k][0][j] for k in ks]
+        for j in range(max(len(e.trajectories) for e in extras.values())):
+            ks = [k for k, e in extras.items() if len(e.trajectories) > j]
+            cj = [extras[k].trajectories[j] for k in ks]
             # (pinned while the list is built and enqueued: more distinct trajectories than the cache holds must not close the first)
-            trs = [cached_trajectory(steps[k][2], c, pin=True) for k, c in zip(ks, cj)]
+            trs = [cached_trajectory(opts[k].prim, c, pin=True) for k, c in zip(ks, cj)]
             try:
-                _capi.Primitive.score_trajectories_dev([steps[k][2] for k in ks], trs,
-                                                       [steps[k][4] for k in ks], dtype, n, [steps[k][7] for k in ks], [steps[k][5] for k in ks],
-                                                       [c.get("min_u", 0.0) for c in cj], [c.get("weight", 1.0) for c in cj],
-                                                       [extras[k][2] for k in ks], accumulate=True)
+                _capi.Primitive.score_trajectories_dev([opts[k].prim for k in ks], trs, [opts[k].x for k in ks], dtype, n, [opts[k].width for k in ks],
+                                                       [opts[k].errors for k in ks], [c.get("min_u", 0.0) for c in cj], [c.get("weight", 1.0) for c in cj],
+                                                       [extras[k].alignment for k in ks], accumulate=True)
             finally:
                 for t in trs:
                     release_trajectory(t)
@@ -766,99 +806,45 @@ class HipPrimitiveSet(object):
                                 old.close()
                         scorers.clear()
                     try:
-                        scorer = TrackScorer(steps[k][2], frames, sk, alignment)
+                        scorer = TrackScorer(opts[k].prim, frames, sk, alignment)
                     except NotImplementedError:
                         scorer = False        # (a joint-rotation constraint, more than four requests: the frames chain)
                     scorers[key] = scorer
-            if (not frames or (scorer and scorer.m <= _capi.MG_FRAME_LIST_MAX)) and plan["one_context"]:
+            if not frames or (scorer and scorer.m <= _capi.MG_FRAME_LIST_MAX):
                 fast.append((k, scorer if frames else None))
             else:
                 slow.append((k, scorer))
         if fast:
-            out = _options_frame_lists(plan, steps, fast, extras, n, dtype)
-            for (k, _), (idx, err, row) in zip(fast, out):
-                results[steps[k][0]] = (row[:steps[k][7]].copy(), err)
+            rec = _options_frame_lists(plan, fast, extras)
+            for j, (k, _) in enumerate(fast):
+                results[opts[k].name] = (rec["latent"][j, :opts[k].width].copy(), float(rec["error"][j]))
         for k, scorer in slow:
             trajectories, frames, alignment, sk = extras[k]
-            name, node, prim, ctx, d_x, d_e, d_r, L, pvals = steps[k]
+            opt = opts[k]
             if scorer:
-                scorer.score_dev(d_x, dtype, n, L, d_e, accumulate=True)
+                scorer.score_dev(opt.x, dtype, n, opt.width, opt.errors, accumulate=True)
             else:
-                add_frame_constraints_dev(prim, ctx.download(d_x, (n, L), dtype), frames, sk, alignment, d_e, accumulate=True)
-            idx, err = ctx.argmin_first(d_e, n, np.float64)
-            row = ctx.download(d_x.ptr.value + idx * L * np.dtype(dtype).itemsize, (L,), dtype)
-            results[name] = (row.astype(np.float64), err)
+                add_frame_constraints_dev(opt.prim, opt.ctx.download(opt.x, (n, opt.width), dtype), frames, sk, alignment, opt.errors, accumulate=True)
+            idx, err = opt.ctx.argmin_first(opt.errors, n, np.float64)
+            row = opt.ctx.download(opt.x.ptr.value + idx * opt.width * dtype.itemsize, (opt.width,), dtype)
+            results[opt.name] = (row.astype(np.float64), err)
         return results
 
     def options_step_rows(self, cmd, row_begin, row_end, skeleton=None):
         """One rank's share of a sharded planner step (distributed._cmd_options_step): the global rows [row_begin, row_end) of
         every option's draw, through mg_options_step_rows.  Returns {option: (global index, error, winning latent)}."""
         from .candidate_scoring import cached_constraint_set
-        import ctypes as C
-        options, n = tuple(cmd["options"]), int(cmd["n_samples"])
-        dtype = np.dtype(cmd.get("dtype", "float32"))
-        code = _capi.MG_F64 if dtype == np.float64 else _capi.MG_F32
-        m_rows = int(row_end) - int(row_begin)
-        plan = self._step_plan(options, m_rows, dtype)       # buffers sized for the block
-        steps = plan["steps"]
-        if not plan["one_context"]:
+        plan = self.step_plan(tuple(cmd["options"]), int(row_end) - int(row_begin), cmd.get("dtype", "float32"))   # buffers sized for the block
+        if not plan.fused:
             raise NotImplementedError("sharded planner steps need all primitives in one context")
-        m, stride, host = len(steps), plan["stride"], plan["host"]
-        plan["whole"] = None          # plan["csets"] and the seeds are rewritten below (ADVICE r4)
-        for k, st in enumerate(steps):
-            name = st[0]
-            cs = cached_constraint_set(st[2], cmd["constraints"][name], skeleton, cmd["alignments"][name])
-            plan["csets"][k] = cs.handle.value
-            plan["seeds"][k] = int(cmd["seed"]) + k
-            c = np.asarray(cmd["counts"][name], dtype=np.int64)
-            plan["counts"][k, :len(c)] = c
-        _capi._check(steps[0][2].lib.mg_options_step_rows(m, plan["prims"], plan["csets"], n, plan["cnts"], plan["seeds"], int(row_begin), m_rows,
-                                                          plan["xs"], code, plan["lds"], plan["errs"], plan["shared"].ptr, stride,
-                                                          host.ctypes.data_as(C.c_void_p)))
-        out = {}
-        for k, st in enumerate(steps):
-            raw = host[k * stride:k * stride + 16 + 8 * st[7]]
-            out[st[0]] = (int(raw[0:8].view(np.int64)[0]), float(raw[8:16].view(np.float64)[0]), raw[16:].view(np.float64).copy())
-        return out
-
-    def _step_plan(self, options, n, dtype):
-        """Everything about a planner step that does not change from step to step, built once per (options, n, dtype): the
-        per-option device buffers (no allocation inside a step), the argument arrays of mg_options_step, the normalised
-        mixture weights the component counts are drawn with, the host block the result records land in."""
-        import ctypes as C
-        key = ("plan", options, n, dtype.str)
-        plan = self._buffers.get(key)
-        if plan is not None:
-            return plan
-        item = dtype.itemsize
-        steps = []
-        for name in options:
-            node = self.nodes[name]
-            prim, ctx = node._prim, node._prim.ctx
-            L = prim.n_gmm_dims          # the winner comes back at full width (spatial + time latents)
-            bkey = (name, n, dtype.str)
-            bufs = self._buffers.get(bkey)
-            if bufs is None:
-                bufs = self._buffers[bkey] = (ctx.malloc(max(n, 1) * L * item), ctx.malloc(max(n, 1) * 8), ctx.malloc(16 + 8 * L))
-            weights = np.asarray(node.gaussian_mixture_model.weights_, dtype=np.float64)
-            steps.append((name, node, prim, ctx, bufs[0], bufs[1], bufs[2], L, weights / weights.sum()))
-        m = len(steps)
-        plan = {"steps": steps, "one_context": all(st[3] is steps[0][3] for st in steps),
-                "counts": np.zeros((max(m, 1), max([len(st[8]) for st in steps] + [1])), dtype=np.int64)}
-        if plan["one_context"] and steps:
-            vp = C.c_void_p
-            stride = 16 + 8 * max(st[7] for st in steps)
-            plan.update(stride=stride, shared=steps[0][3].malloc(m * stride), host=np.empty(m * stride, dtype=np.uint8),
-                        prims=(vp * m)(*[st[2].handle for st in steps]), csets=(vp * m)(),
-                        cnts=(vp * m)(*[plan["counts"][k].ctypes.data for k in range(m)]), seeds=(C.c_uint64 * m)(),
-                        xs=(vp * m)(*[_capi._dev_ptr(st[4]).value for st in steps]), lds=(C.c_int64 * m)(*[st[7] for st in steps]),
-                        errs=(vp * m)(*[_capi._dev_ptr(st[5]).value for st in steps]), lib=steps[0][2].lib,
-                        device_counts=np.zeros((m, 16), dtype=np.int64), karange=np.arange(m, dtype=np.uint64))
-            # (everything a step hands to the C call, made once: no ctypes object is created inside a step)
-            plan.update(seeds_np=np.ctypeslib.as_array(plan["seeds"]), shared_ptr=plan["shared"].ptr, host_ptr=plan["host"].ctypes.data_as(vp),
-                        device_counts_ptr=plan["device_counts"].ctypes.data_as(vp))
-        self._buffers[key] = plan
-        return plan
+        plan.bind([cached_constraint_set(opt.prim, cmd["constraints"][opt.name], skeleton, cmd["alignments"][opt.name]) for opt in plan.options])
+        plan.seed(cmd["seed"])
+        for k, opt in enumerate(plan.options):
+            c = np.asarray(cmd["counts"][opt.name], dtype=np.int64)
+            plan.counts[k, :len(c)] = c
+        _capi._check(plan.launch(rows=(int(cmd["n_samples"]), int(row_begin))))
+        rec = _capi.option_records(plan.host, len(plan.options), plan.stride)
+        return {opt.name: (int(rec["index"][k]), float(rec["error"][k]), rec["latent"][k, :opt.width].copy()) for k, opt in enumerate(plan.options)}
 
     def evaluate_options(self, options, constraints_per_option, n_samples, rng_seed=None):
         """options: node names; constraints_per_option: name -> constraint list.  Returns

@@ -589,9 +589,9 @@ def _options_step_raw(pset, names, cons, n, seed, dtype, skeleton=None, prev_fra
     out = {}
     for name in names:
         prim = pset.nodes[name]._prim
-        d_x, d_e, d_r = pset._buffers[(name, n, np.dtype(dtype).str)]
+        buf = pset.step_plan(names, n, dtype).option(name)
         L = prim.n_gmm_dims
-        out[name] = (results[name][0].copy(), results[name][1], prim.ctx.download(d_e, (n,), np.float64), prim.ctx.download(d_x, (n, L), dtype))
+        out[name] = (results[name][0].copy(), results[name][1], prim.ctx.download(buf.errors, (n,), np.float64), prim.ctx.download(buf.x, (n, L), dtype))
     return best, out
 
 
@@ -646,9 +646,9 @@ def test_planner_step_at_the_size_of_configs2_returns_what_its_buffers_hold():
         errs = []
         for nm in names:
             prim = pset.nodes[nm]._prim
-            d_x, d_e, d_r = pset._buffers[(nm, n, np.dtype(np.float32).str)]
-            e = prim.ctx.download(d_e, (n,), np.float64)
-            x = prim.ctx.download(d_x, (n, prim.n_gmm_dims), np.float32)
+            buf = pset.step_plan(names, n, np.float32).option(nm)
+            e = prim.ctx.download(buf.errors, (n,), np.float64)
+            x = prim.ctx.download(buf.x, (n, prim.n_gmm_dims), np.float32)
             w = int(np.argmin(e))
             assert res[nm][1] == e[w], (step, nm)
             np.testing.assert_array_equal(np.asarray(res[nm][0], dtype=np.float64), x[w].astype(np.float64))
@@ -685,11 +685,11 @@ def test_planner_steps_publish_complete_records_fenced_or_not():
             errs = []
             for nm in opts:
                 prim = pset.nodes[nm]._prim
-                d_x, d_e, d_r = pset._buffers[(nm, n, np.dtype(np.float32).str)]
-                e = prim.ctx.download(d_e, (n,), np.float64)
+                buf = pset.step_plan(opts, n, np.float32).option(nm)
+                e = prim.ctx.download(buf.errors, (n,), np.float64)
                 w = int(np.argmin(e))
                 assert res[nm][1] == e[w], (step, nm, res[nm][1], e[w])
-                x = prim.ctx.download(d_x.ptr.value + w * prim.n_gmm_dims * 4, (prim.n_gmm_dims,), np.float32)
+                x = prim.ctx.download(buf.x.ptr.value + w * prim.n_gmm_dims * 4, (prim.n_gmm_dims,), np.float32)
                 np.testing.assert_array_equal(np.asarray(res[nm][0], dtype=np.float64), x.astype(np.float64), err_msg="step %d %s" % (step, nm))
                 errs.append(e[w])
             assert best == opts[int(np.argmin(errs))]

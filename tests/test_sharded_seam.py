@@ -200,16 +200,16 @@ def test_a_planner_step_in_blocks_is_the_unsharded_step():
     for mode in (0, 1):
         pset.ctx.set_option(_capi.MG_OPT_OPTIONS_STEP, mode)
         whole = pset.options_step_rows(cmd, 0, n)
-        plan = pset._step_plan(tuple(names), n, np.dtype(np.float32))
-        X = {st[0]: st[3].download(st[4], (n, st[7]), np.float32) for st in plan["steps"]}
-        E = {st[0]: st[3].download(st[5], (n,), np.float64) for st in plan["steps"]}
+        plan = pset.step_plan(names, n, np.float32)
+        X = {o.name: o.ctx.download(o.x, (n, o.width), np.float32) for o in plan.options}
+        E = {o.name: o.ctx.download(o.errors, (n,), np.float64) for o in plan.options}
         parts = []
         for b, e in ((0, n // 3), (n // 3, n)):
             parts.append(pset.options_step_rows(cmd, b, e))
-            plan_b = pset._step_plan(tuple(names), e - b, np.dtype(np.float32))
-            for st in plan_b["steps"]:
-                np.testing.assert_array_equal(st[3].download(st[4], (e - b, st[7]), np.float32).view(np.uint32), X[st[0]][b:e].view(np.uint32))
-                np.testing.assert_array_equal(st[3].download(st[5], (e - b,), np.float64).view(np.uint64), E[st[0]][b:e].view(np.uint64))
+            plan_b = pset.step_plan(names, e - b, np.float32)
+            for o in plan_b.options:
+                np.testing.assert_array_equal(o.ctx.download(o.x, (e - b, o.width), np.float32).view(np.uint32), X[o.name][b:e].view(np.uint32))
+                np.testing.assert_array_equal(o.ctx.download(o.errors, (e - b,), np.float64).view(np.uint64), E[o.name][b:e].view(np.uint64))
         for nm in names:
             rows = np.stack([np.concatenate([[parts[r][nm][1], parts[r][nm][0]], parts[r][nm][2]]) for r in range(2)])
             gi, err, lat = distributed.combine_first_minimum(rows)

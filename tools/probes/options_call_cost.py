@@ -12,13 +12,11 @@ pset = HipPrimitiveSet(prims)
 n = 4096
 for i in range(50):
     pset.evaluate_options_on_device(names, cons, n, seed=i)
-plan = pset._step_plan(tuple(names), n, np.dtype(np.float32))
-steps = plan["steps"]
-lib = steps[0][2].lib
-m, stride, host = len(steps), plan["stride"], plan["host"]
+plan = pset.step_plan(names, n, np.float32)
+lib, m, stride, host = plan.lib, len(plan.options), plan.stride, plan.host
 def call():
-    _capi._check(lib.mg_options_step(m, plan["prims"], plan["csets"], n, plan["cnts"], plan["seeds"], plan["xs"], _capi.MG_F32, plan["lds"],
-                                     plan["errs"], plan["shared"].ptr, stride, host.ctypes.data_as(C.c_void_p)))
+    _capi._check(lib.mg_options_step(m, plan.prims, plan.csets, n, plan.cnts, plan.seeds, plan.xs, _capi.MG_F32, plan.lds,
+                                     plan.errs, plan.shared.ptr, stride, host.ctypes.data_as(C.c_void_p)))
 for _ in range(100): call()
 t0 = time.perf_counter()
 for _ in range(1000): call()

@@ -25,20 +25,20 @@ for dc in (False, True):
     for i in range(1000):
         pset.evaluate_options_on_device(names, cons, n, seed=i, device_counts=dc)
     print("python method, device_counts=%s: %.1f us per step" % (dc, (time.perf_counter() - t) / 1000 * 1e6))
-plan = pset._step_plan(tuple(names), n, np.dtype(np.float32))
-lib, m, stride = plan["lib"], len(names), plan["stride"]
+plan = pset.step_plan(names, n, np.float32)
+lib, m, stride = plan.lib, len(names), plan.stride
 code = _capi.MG_F32
 ctx = pset.ctx
 
 
 def c_host(readback=True):
-    return lib.mg_options_step(m, plan["prims"], plan["csets"], n, plan["cnts"], plan["seeds"], plan["xs"], code, plan["lds"], plan["errs"],
-                               plan["shared_ptr"], stride, plan["host_ptr"] if readback else None)
+    return lib.mg_options_step(m, plan.prims, plan.csets, n, plan.cnts, plan.seeds, plan.xs, code, plan.lds, plan.errs,
+                               plan.shared_ptr, stride, plan.host_ptr if readback else None)
 
 
 def c_dev(readback=True):
-    return lib.mg_options_step_device_counts(m, plan["prims"], plan["csets"], n, plan["seeds"], plan["xs"], code, plan["lds"], plan["errs"],
-                                             plan["shared_ptr"], stride, plan["host_ptr"] if readback else None, None)
+    return lib.mg_options_step_device_counts(m, plan.prims, plan.csets, n, plan.seeds, plan.xs, code, plan.lds, plan.errs,
+                                             plan.shared_ptr, stride, plan.host_ptr if readback else None, None)
 
 
 for name, fn in (("mg_options_step (counts given)", c_host), ("mg_options_step_device_counts", c_dev)):
@@ -53,8 +53,7 @@ for name, fn in (("mg_options_step (counts given)", c_host), ("mg_options_step_d
         print("%s, read-back %s: %.1f us per call" % (name, rb, (time.perf_counter() - t) / 1000 * 1e6))
 t = time.perf_counter()
 for i in range(1000):
-    for k, st in enumerate(plan["steps"]):
-        plan["counts"][k, :len(st[8])] = np.random.multinomial(n, st[8])
+    plan.draw_counts()
 print("16 x np.random.multinomial: %.1f us" % ((time.perf_counter() - t) / 1000 * 1e6))
 t = time.perf_counter()
 for i in range(1000):

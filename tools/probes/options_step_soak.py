@@ -24,9 +24,9 @@ for i in range(steps):
     if i % 10 == 0 or i < 20:       # the check reads 16 x (4096 errors + candidates) back: every tenth step
         for nm in names:
             prim = pset.nodes[nm]._prim
-            d_x, d_e, d_r = pset._buffers[(nm, n, np.dtype(np.float32).str)]
-            e = prim.ctx.download(d_e, (n,), np.float64)
-            x = prim.ctx.download(d_x, (n, prim.n_gmm_dims), np.float32)
+            buf = pset.step_plan(names, n, np.float32).option(nm)
+            e = prim.ctx.download(buf.errors, (n,), np.float64)
+            x = prim.ctx.download(buf.x, (n, prim.n_gmm_dims), np.float32)
             w = int(np.argmin(e))
             lat, err = results[nm][0], results[nm][1]
             if err != e[w] or not np.array_equal(np.asarray(lat, dtype=np.float64), x[w].astype(np.float64)):

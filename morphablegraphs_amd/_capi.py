@@ -345,7 +345,7 @@ def load_library(path=None):
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = C.c_int
-    if path is None or _lib is None:   # an explicit path given before first use (a tool's diagnostic build) becomes the library
+    if path is None or _lib is None:   # an explicit path given before first use (a tool's A/B build) becomes the library
         _lib = lib
     return lib
 

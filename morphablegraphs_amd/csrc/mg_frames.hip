@@ -16,14 +16,7 @@
 //
 // This translation unit: which kernel a launch uses (mg_frames_kernel_choice), its grid and LDS, the dispatch.  The kernels:
 // mg_frames_cs.hip (chunk-stationary), mg_frames_ws.hip (tile-major), mg_frames_direct.hip (one thread per element).
-// The diagnostic build (-DMG_DEBUG_BUILD: ablation switches, phase timers in device globals) compiles them all as ONE
-// translation unit -- this file includes the others -- so that they share the timers' device arrays.
 #include "mg_frames_common.h"
-#ifdef MG_DEBUG_BUILD
-#include "mg_frames_ws.hip"
-#include "mg_frames_cs.hip"
-#include "mg_frames_direct.hip"
-#endif
 
 int mg_setup_kernel_attributes(mg_context *) {
     int rc = mg_frames_ws_attributes();
@@ -100,10 +93,6 @@ int mg_launch_frames_mfma(mg_primitive *p, const mg_time_grid *g, const void *la
     a.rt_total = p->RT;
     a.B = B; a.ld = ld; a.T = g->T; a.D = p->D; a.Dp = p->Dp; a.cshift = p->cshift; a.L = p->L; a.nroot = p->nroot;
     a.n_chunks = g->n_chunks; a.stride = g->stride; a.max_wi = g->max_wi; a.max_nt = g->max_nt; a.nbuf = g->nbuf;
-    a.debug = 0;
-#ifdef MG_DEBUG_BUILD
-    if (const char *dbg_env = getenv("MG_DEBUG_FLAGS")) a.debug = atoi(dbg_env);   // read per launch: A/B tools switch it inside one process
-#endif
     const int64_t n_tiles = (B + MG_NCAND - 1) / MG_NCAND;
     const int64_t units = n_tiles * g->n_chunks;
     if (n_tiles >= ((int64_t)1 << 27) || units >= ((int64_t)1 << 31)) {

@@ -1,10 +1,7 @@
-// Shared pieces of the LDS-staged frames kernels (gfx950): launch arguments, the diagnostic build's switches and timers,
-// the LDS progress-counter hand-off, unit cursors, the quad-row sweep's tap and store helpers, the fused mixture scoring.
+// Shared pieces of the LDS-staged frames kernels (gfx950): launch arguments, the LDS progress-counter hand-off, unit cursors,
+// the quad-row sweep's tap and store helpers, the fused mixture scoring.
 // Included by mg_frames_ws.hip (tile-major), mg_frames_cs.hip (chunk-stationary) and mg_frames.hip (planning and dispatch).
 #pragma once
-#include <cstdio>
-#include <cstdlib>
-
 #include "mg_internal.h"
 #include <hip/hip_ext.h>
 #include <type_traits>
@@ -20,13 +17,10 @@ typedef float f32x2u __attribute__((ext_vector_type(2), aligned(4)));
 struct mg_frames_args {
     int64_t B, ld;
     int32_t T, D, Dp, cshift, L, nroot, n_chunks, n_tiles, stride, max_wi, max_nt;
-    int32_t debug;   // MG_DEBUG_FLAGS (ablations and timers, never set in production): 1 = producers idle, 2 = sweep idle,
-                     // 4 = sweep stores only, 16 = per-wave phase timers, 32 = wave-0 sub-phases (serialising), 64 = row producers without MFMAs,
-                     // 128 = no chunk rotation, 256 = no tile-round rotation, 512 = row producers without E' loads, 1024 = wave 0 idle
     int32_t nbuf;    // LDS ring depth (2 or 3)
     int32_t max_tiles;   // row tiles of the widest chunk window (chunk-stationary kernel: sizes its mean' window in LDS)
     int32_t rt_total;    // row tiles of the primitive's whole eigenvector image (the chunk-stationary kernel's quad copy lies behind the pair image: + rt_total * KK * 64 floats)
-    int32_t gmm_staged;  // chunk-stationary kernel, fused mixture: its latent tiles, C-in rows and constants have room in LDS (staged at start-up, MG_CS_GMM_LDSX)
+    int32_t gmm_staged;  // chunk-stationary kernel, fused mixture: its latent tiles, C-in rows and constants have room in LDS (staged at start-up)
     int32_t cs_magic, cs_per, cs_rem;   // chunk-stationary kernel: workgroup w -> (chunk, block) without a division: q = (w * cs_magic) >> 20;
                                         // cs_per tiles per workgroup of a chunk, the first cs_rem one more
     mg_chunk ck[MG_ARG_CHUNKS];   // the first chunks' descriptors: read with the other arguments instead of a dependent trip to global memory
@@ -37,129 +31,6 @@ __device__ __forceinline__ double mg_load_lat(const void *lat, int64_t idx) {
     if (F64) return ((const double *)lat)[idx];
     return (double)((const float *)lat)[idx];
 }
-
-// Ablation switches and phase timers exist only in the diagnostic build (make libmg_hip_dbg.so, -DMG_DEBUG_BUILD):
-// the product kernel carries none of their branches and never reads the environment.
-#ifdef MG_DEBUG_BUILD
-#define MG_DBG(bits) (a.debug & (bits))
-// diagnostic phase timers (MG_DEBUG_FLAGS & 16): per-wave s_memtime deltas accumulated in
-// registers over all units and written once at kernel end (a store inside the loop would put
-// the producers' loads behind it in vmcnt order and distort what is being measured).
-__device__ unsigned long long mg_dbg_wg[1024][2];      // [workgroup][begin, end] in 100 MHz ticks (first sweep wave)
-__device__ unsigned long long mg_dbg_stamps[16][10];   // [wave][phase] of workgroup 0; [8] = shader cycles, [9] = 100 MHz ticks of the wave
-__device__ unsigned long long mg_dbg_units[16][32][2];  // chunk-stationary kernel, workgroup 0: [wave][unit][work begins, work ends] in 100 MHz ticks
-#define MG_UNIT_STAMP(u_, k_)                                                                                          \
-    do {                                                                                                               \
-        if ((a.debug & 16) && blockIdx.x == 0 && lane == 0 && (u_) < 32) mg_dbg_units[wave][u_][k_] = __builtin_amdgcn_s_memrealtime(); \
-    } while (0)
-#define MG_SUB_STAMP(row_, u_, k_)                                                                                     \
-    do {                                                                                                               \
-        if ((a.debug & 16) && blockIdx.x == 0 && lane == 0 && (u_) < 32) mg_dbg_units[row_][u_][k_] = __builtin_amdgcn_s_memrealtime(); \
-    } while (0)
-#define MG_STAMP_DECL unsigned long long st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}; unsigned long long st_prev = __builtin_amdgcn_s_memtime(); \
-    const unsigned long long st_c0 = st_prev, st_r0 = __builtin_amdgcn_s_memrealtime();
-#define MG_STAMP(ph)                                                     \
-    do {                                                                 \
-        if (a.debug & 16) {                                              \
-            const unsigned long long now_ = __builtin_amdgcn_s_memtime(); \
-            st_acc[ph] += now_ - st_prev;                                \
-            st_prev = now_;                                              \
-        }                                                                \
-    } while (0)
-#define MG_STAMP_DUMP                                                    \
-    do {                                                                 \
-        if ((a.debug & 16) && blockIdx.x == 0 && lane == 0) {            \
-            for (int ph_ = 0; ph_ < 8; ph_++) mg_dbg_stamps[wave][ph_] = st_acc[ph_]; \
-            mg_dbg_stamps[wave][8] = __builtin_amdgcn_s_memtime() - st_c0; \
-            mg_dbg_stamps[wave][9] = __builtin_amdgcn_s_memrealtime() - st_r0; \
-        }                                                                \
-        if ((a.debug & 16) && wave == 4 && lane == 0 && blockIdx.x < 1024) { \
-            mg_dbg_wg[blockIdx.x][0] = st_r0;                            \
-            mg_dbg_wg[blockIdx.x][1] = __builtin_amdgcn_s_memrealtime(); \
-        }                                                                \
-    } while (0)
-
-// Light stamps (MG_DEBUG_FLAGS & 32768, without 16): a handful of 100 MHz clock reads per wave kept in scalar registers and written ONCE when the wave
-// ends -- no store inside the kernel's life, so the timeline is the product kernel's (the per-unit stamps above put global stores into the producers).
-__device__ unsigned long long mg_dbg_lite[2][16][8];   // [workgroup 0 / workgroup 131][wave][stamp]
-#define MG_LITE_DECL unsigned long long lite_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#define MG_LITE(i_) do { if (a.debug & 32768) lite_[i_] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#define MG_LITE_DUMP                                                                                              \
-    do {                                                                                                          \
-        if ((a.debug & 32768) && (blockIdx.x == 0 || blockIdx.x == 131) && lane == 0)                             \
-            for (int i_ = 0; i_ < 8; i_++) mg_dbg_lite[blockIdx.x ? 1 : 0][wave][i_] = lite_[i_];                 \
-    } while (0)
-extern "C" int mg_debug_dump_lite(void) {
-    static unsigned long long h[2][16][8], zero[2][16][8];
-    if (hipMemcpyFromSymbol(h, HIP_SYMBOL(mg_dbg_lite), sizeof(h)) != hipSuccess) return -1;
-    for (int w2 = 0; w2 < 2; w2++) {
-        unsigned long long t0 = ~0ull;
-        for (int w = 0; w < 12; w++) if (h[w2][w][0] && h[w2][w][0] < t0) t0 = h[w2][w][0];
-        printf("light stamps, workgroup %d, us after its first wave's entry: [0] entry; producers (waves 0-3): [1] tail begins [3] terms done [4] log-sum-exp done;\n"
-               "  [5] barrier passed [6] first unit begins (wave 0: its latent tile is published) [7] first unit published; sweep waves: [1] first sweep begins [2] last sweep begins [4] last sweep ends\n", w2 ? 131 : 0);
-        for (int w = 0; w < 12; w++) {
-            printf("  wave %2d:", w);
-            for (int i = 0; i < 8; i++) printf(" %7.2f", h[w2][w][i] ? (h[w2][w][i] - t0) / 100.0 : -1.0);
-            printf("\n");
-        }
-    }
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(mg_dbg_lite), zero, sizeof(zero));
-    return 0;
-}
-
-extern "C" int mg_debug_dump_stamps(void) {
-    unsigned long long h[16][10];
-    if (hipMemcpyFromSymbol(h, HIP_SYMBOL(mg_dbg_stamps), sizeof(h)) != hipSuccess) return -1;
-    printf("per-wave cycles summed over the units of workgroup 0; phase p = time from stamp p-1 to stamp p\n");
-    printf("  (0: loop top, 1: sweep: wait for producers, 2: row producers: tiles, 3: row producers: carried tiles / wave 0: root stage,\n"
-           "   4: sweep / publish, 5: producers: wait for a free slot; sweep: publish)\n");
-    for (int w = 0; w < 12; w++) {
-        printf("wave %2d:", w);
-        for (int ph = 0; ph < 8; ph++) printf(" %9llu", h[w][ph]);
-        printf("  | %9llu cycles in %.2f us = %.3f GHz\n", h[w][8], h[w][9] / 100.0, h[w][9] ? h[w][8] / (h[w][9] * 10.0) : 0.0);
-    }
-    static unsigned long long wg[1024][2];
-    if (hipMemcpyFromSymbol(wg, HIP_SYMBOL(mg_dbg_wg), sizeof(wg)) != hipSuccess) return -1;
-    unsigned long long t0 = ~0ull;
-    for (int i = 0; i < 1024; i++) if (wg[i][1] && wg[i][0] < t0) t0 = wg[i][0];
-    printf("sweep wave 4 of every workgroup, us after the first one began: begin / end\n");
-    for (int i = 0; i < 1024; i++) {
-        if (!wg[i][1]) continue;
-        if (i % 8 == 0) printf("\n  wg %3d:", i);
-        printf(" %5.1f/%5.1f", (wg[i][0] - t0) / 100.0, (wg[i][1] - t0) / 100.0);
-    }
-    printf("\n");
-    static unsigned long long un[16][32][2];
-    if (hipMemcpyFromSymbol(un, HIP_SYMBOL(mg_dbg_units), sizeof(un)) != hipSuccess) return -1;
-    unsigned long long u0 = ~0ull;
-    for (int w = 0; w < 16; w++) if (un[w][0][0] && un[w][0][0] < u0) u0 = un[w][0][0];   // row 14: kernel entry / barrier passed (wave 0)
-    if (u0 != ~0ull) {
-        printf("chunk-stationary kernel, workgroup 0: per unit, us after the first stamp: work begins / ends\n");
-        for (int w = 0; w < 16; w++) {   // rows 12..15: sub-phases of wave 0 (latents staged / root chains done, root image written / taps done)
-            printf("wave %2d:", w);
-            for (int u = 0; u < (w >= 14 ? 4 : 32); u++) if (w >= 14 || un[w][u][1] != 0) printf(" %5.1f/%5.1f", (un[w][u][0] - u0) / 100.0, (un[w][u][1] - u0) / 100.0);
-            printf("\n");
-        }
-    }
-    static unsigned long long zero[16][32][2];
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(mg_dbg_units), zero, sizeof(zero));
-    return 0;
-}
-#else
-#ifdef MG_DBG_CONST   // tools/build_variant.sh NAME -DMG_DBG_CONST=bits: an ablation compiled in, without the diagnostic build's stamps
-#define MG_DBG(bits) ((MG_DBG_CONST) & (bits))
-#else
-#define MG_DBG(bits) 0
-#endif
-#define MG_LITE_DECL
-#define MG_LITE(i_) do { } while (0)
-#define MG_LITE_DUMP do { } while (0)
-#define MG_STAMP_DECL
-#define MG_STAMP(ph) do { } while (0)
-#define MG_STAMP_DUMP do { } while (0)
-#define MG_UNIT_STAMP(u_, k_) do { } while (0)
-#define MG_SUB_STAMP(row_, u_, k_) do { } while (0)
-#endif
 
 // -----------------------------------------------------------------------------------------
 // The hot-path kernel: persistent, wave-specialised.
@@ -193,15 +64,6 @@ extern "C" int mg_debug_dump_stamps(void) {
 // [max_nt] float4 + image tap byte offsets [max_nt] int (max_nt = the grid's longest chunk, padded to 16); rs = float64 root image; prog = 32 counters
 // (producer/consumer progress, mixture hand-off); FUSE_GMM: mixture terms and exponentials [2][K*16] f64 each.
 // -----------------------------------------------------------------------------------------
-#ifndef MG_SWEEP_LANEMAP
-#define MG_SWEEP_LANEMAP 1   // the sweep's third sample in lanes 44 .. 63 (see the kernels)
-#endif
-#ifndef MG_SWEEP_FAST
-#define MG_SWEEP_FAST 1      // the lean loop over a chunk's full trips (see the chunk-stationary kernel)
-#endif
-#ifndef MG_GMM_PAIR_LOADS
-#define MG_GMM_PAIR_LOADS 0   // the fused mixture's component fragments two components per round of loads (A/B: tools/build_variant.sh)
-#endif
 #define MG_FUSE_MAX_KK 10   // fused mixture scoring: k-steps (4 latent components each) that fit the register budget
 #define MG_WS_NPW 4      // producer waves
 #define MG_WS_NCW 8      // consumer waves, two candidates each
@@ -391,20 +253,12 @@ __device__ __forceinline__ void mg_store_n(float *op, const f32x4 &v, int n) {
 template <int KK>
 __device__ __forceinline__ void mg_produce_f32(const float2 *__restrict__ ep, const float *__restrict__ mean32,
                                                const mg_chunk &ck, float *lds_c, int stride, int t_first, int pw, int npw,
-                                               const float (&sfrag)[KK], int lane, int cl, int g, int rot = 0, int dbg = 0) {
+                                               const float (&sfrag)[KK], int lane, int cl, int g, int rot = 0) {
     float2 fa[2][KK / 2], na[2][KK / 2];
     f32x4 fm[2], nm[2];
     auto load_tile = [&](int t, float2(&fr)[KK / 2], f32x4 &cin) {
         const int tc = t < ck.ntiles ? t : ck.ntiles - 1;   // clamp: redundant but in bounds
         const float2 *p = ep + ((size_t)(ck.rt0 + tc) * (KK / 2)) * 64 + lane;
-#ifdef MG_DEBUG_BUILD
-        if (dbg & 512) {   // ablation: no E' loads (with 32768 in the caller: on every other unit)
-#pragma unroll
-            for (int q = 0; q < KK / 2; q++) fr[q] = make_float2(0.5f, 0.25f);
-            cin = f32x4{0.f, 0.f, 0.f, 0.f};
-            return;
-        }
-#endif
 #pragma unroll
         for (int q = 0; q < KK / 2; q++) fr[q] = p[q * 64];
         cin = *(const f32x4 *)(mean32 + (size_t)(ck.rt0 + tc) * 16 + 4 * g);
@@ -425,12 +279,6 @@ __device__ __forceinline__ void mg_produce_f32(const float2 *__restrict__ ep, co
         load_tile(tn, na[0], nm[0]);
         load_tile(tn + npw, na[1], nm[1]);
         f32x4 acc0 = fm[0], acc1 = fm[1];
-#ifdef MG_DEBUG_BUILD
-        if (dbg & 64) {   // ablation: no MFMAs (the loaded fragments stay live)
-#pragma unroll
-            for (int q = 0; q < KK / 2; q++) { asm volatile("" :: "v"(fa[0][q].x), "v"(fa[0][q].y), "v"(fa[1][q].x), "v"(fa[1][q].y)); }
-        } else
-#endif
 #pragma unroll
         for (int q = 0; q < KK / 2; q++) {
             acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[0][q].x, sfrag[2 * q], acc0, 0, 0, 0);
@@ -487,30 +335,12 @@ __device__ __forceinline__ void mg_fused_gmm_terms(mg_lds_int *prog, const doubl
             mg_gmm_load_x<KK, LAT_F64>(xa, lat, ba, na, ld, L, cl, g);
             mg_gmm_load_x<KK, LAT_F64>(xb, lat, bb, nb, ld, L, cl, g);
         }
-#if MG_GMM_PAIR_LOADS
-        // two components' fragments requested together: in the tail every load waits behind the store stream's queue, so a round of
-        // loads is a round trip of microseconds -- one round for a wave's two components (K = 8) instead of two
-        for (int k = pw; k < gK; k += 2 * MG_WS_NPW) {
-            const int k2 = k + MG_WS_NPW;
-            mg_gmm_frag<KK> f, f2;
-            mg_gmm_load_component<KK>(f, gPpack, gmP, gcst, k, gJT, lane, cl, gK);
-            if (k2 < gK) mg_gmm_load_component<KK>(f2, gPpack, gmP, gcst, k2, gJT, lane, cl, gK);
-            typedef typename mg_gmm_xt<LAT_F64>::type XT;
-            mg_gmm_apply_component<KK, XT, true>(f, k, gJT, xa, gterms, cl, g);
-            if (has_b) mg_gmm_apply_component<KK, XT, true>(f, k, gJT, xb, gterms + gK * 16, cl, g);
-            if (k2 < gK) {
-                mg_gmm_apply_component<KK, XT, true>(f2, k2, gJT, xa, gterms, cl, g);
-                if (has_b) mg_gmm_apply_component<KK, XT, true>(f2, k2, gJT, xb, gterms + gK * 16, cl, g);
-            }
-        }
-#else
         for (int k = pw; k < gK; k += MG_WS_NPW) {
             mg_gmm_frag<KK> f;
             mg_gmm_load_component<KK>(f, gPpack, gmP, gcst, k, gJT, lane, cl, gK);
             mg_gmm_apply_component(f, k, gJT, xa, gterms, cl, g);
             if (has_b) mg_gmm_apply_component(f, k, gJT, xb, gterms + gK * 16, cl, g);
         }
-#endif
     }
     mg_publish(prog + 16, pw, lane, group + 1);   // gdone[pw]
 }
@@ -548,7 +378,7 @@ __device__ __forceinline__ void mg_fused_gmm_terms_ldsx(mg_lds_int *prog, const 
     mg_publish(prog + 16, pw, lane, 1);   // gdone[pw]
 }
 
-// Start-up half of the staged form (MG_CS_GMM_EARLY_HALF): sweep wave 4 + MG_CS_NSP + i, idle until the first unit is in LDS, scores component 4 + i on the
+// Start-up half of the staged form: sweep wave 4 + MG_CS_NSP + i, idle until the first unit is in LDS, scores component 4 + i on the
 // workgroup's two latent tiles -- its fragments requested before the start-up barrier, the matrix pipes still idle (the row producers wait for their
 // eigenvector fragments) -- and leaves the terms where the tail's log-sum-exp finds them.  Same device code per (tile, component): the same bits.
 template <int KK>

@@ -8,7 +8,7 @@
 // The tile-major kernel above ended with its row producers 88 % busy and the sweep waiting for them; 9-13 us of its
 // 84-93 went on the E' fragment loads of the unit loop -- 189 MB of L2 hits per launch that travel through the same L2
 // and the same per-CU memory pipe as 400 MB of stores (streaming just five more tiles per unit into THIS kernel's row
-// producers costs 18 us: MG_DEBUG_FLAGS & 2048).  So E' must not travel at all inside the loop:
+// producers costs 18 us).  So E' must not travel at all inside the loop:
 //   * a workgroup works on ONE time chunk for its whole life (workgroup w: chunk w mod n_chunks) and walks a block of
 //     consecutive candidate tiles; the chunk's whole window of E' fragments is loaded ONCE into registers: 768-thread
 //     workgroups, 3 waves per SIMD, 168 VGPRs -- three row producers x TPWP (12) row tiles x KK floats, the four oldest
@@ -34,27 +34,7 @@
 // -----------------------------------------------------------------------------------------
 #define MG_CS_NPW 4      // producer waves (0: root + latents, 1-3: rows)
 #define MG_CS_NCW 8      // sweep waves, two candidates each; they also produce a few row tiles per unit
-#ifndef MG_CS_NSP
 #define MG_CS_NSP 4      // how many of the sweep waves (the first ones, which sweep fastest) produce row tiles as well
-#endif
-#ifndef MG_CS_GMM_EARLY
-#define MG_CS_GMM_EARLY 0   // 1: the fused mixture's first group of tiles is scored while the pipeline fills (below), not in the tail -- A/B only: SLOWER
-#endif
-#ifndef MG_CS_STORE_THROTTLE
-#define MG_CS_STORE_THROTTLE -1   // >= 0 (A/B only): the sweep waits after each trip of its lean loop until at most so many of the wave's stores are in flight
-#endif
-#ifndef MG_CS_THROTTLE_LAST_ONLY
-#define MG_CS_THROTTLE_LAST_ONLY 1   // ... in the workgroup's last unit only (while the mixture's loads share the CU's memory pipe with it)
-#endif
-#ifndef MG_CS_QUAD_FRAGMENTS
-#define MG_CS_QUAD_FRAGMENTS 1   // the one-time eigenvector fragment loads from the quad copy of the image: 16-byte loads
-#endif
-#ifndef MG_CS_GMM_EARLY_HALF
-#define MG_CS_GMM_EARLY_HALF 1   // with the staged tail: components 4 .. 7 are scored at start-up by the four sweep waves that produce nothing
-#endif
-#ifndef MG_CS_GMM_LDSX
-#define MG_CS_GMM_LDSX 1   // float32 latents: the mixture's two latent tiles staged in LDS at start-up, both components of a producer wave requested at once
-#endif
 #define MG_CS_BLOCK (64 * (MG_CS_NPW + MG_CS_NCW))
 template <int KK> struct mg_cs_cfg {
     static constexpr int TPWP = 120 / KK < 17 ? 120 / KK : 17;   // row tiles a row producer keeps in registers (TPWP * KK VGPRs)
@@ -81,7 +61,7 @@ int mg_cs_max_tiles(int KK) {
 // the staged latent tiles of the fused mixture: behind its term and exp buffers ([4][K*16] float64 after the 64 counters)
 __device__ __forceinline__ mg_lds_f32 *mg_cs_gmm_x(mg_lds_int *prog, int gK) { return (mg_lds_f32 *)((mg_lds_f64 *)(prog + MG_CS_PROG_INTS) + 4 * gK * 16); }
 __device__ __forceinline__ mg_lds_f64 *mg_cs_gmm_mp(mg_lds_int *prog, int gK, int KK) { return (mg_lds_f64 *)(mg_cs_gmm_x(prog, gK) + 2 * KK * 64); }   // [K][JT*16], then [K]
-// MG_CS_GMM_EARLY_HALF: are components 4 .. 7 scored at start-up?  Where the workgroup has BOTH tiles of a mixture group (uniform over the workgroup; the
+// The staged tail's start-up half: are components 4 .. 7 scored at start-up?  Where the workgroup has BOTH tiles of a mixture group (uniform over the workgroup; the
 // start-up waves and the tail ask the same question).  Measured, one process and one buffer each: B = 8192 -0.3 us (four boxes: +0.3, -0.7, -0.5, -0.3),
 // 12 000 -0.9, 16 384 -1.0 -- and with ONE tile per workgroup +0.6 (B = 2048) / +0.9 us (4096): the start-up pays the same and the tail has half to gain.
 __device__ __forceinline__ bool mg_cs_gmm_early(const mg_frames_args &a) {
@@ -163,8 +143,7 @@ __device__ __forceinline__ void mg_cs_produce(const float (&ef)[NT][KK], const f
     }
 }
 template <int KK, int NT>
-__device__ __forceinline__ void mg_cs_load_fragments(float (&ef)[NT][KK], const float2 *ep, const mg_chunk &ck, int first, int step, int lane, [[maybe_unused]] int rt_total) {
-#if MG_CS_QUAD_FRAGMENTS
+__device__ __forceinline__ void mg_cs_load_fragments(float (&ef)[NT][KK], const float2 *ep, const mg_chunk &ck, int first, int step, int lane, int rt_total) {
     // from the quad copy behind the pair image (mg_host.hip): per tile [KK / 4][64][4] floats, then [64][2] for the last pair: 16-byte loads
     const float *eq = (const float *)ep + (size_t)rt_total * KK * 64;
 #pragma unroll
@@ -184,20 +163,6 @@ __device__ __forceinline__ void mg_cs_load_fragments(float (&ef)[NT][KK], const 
             ef[i][KK - 1] = v.y;
         }
     }
-#else
-#pragma unroll
-    for (int i = 0; i < NT; i++) {
-        const int t = first + step * i;
-        const int tc = t < ck.ntiles ? t : ck.ntiles - 1;   // clamp: redundant but in bounds
-        const float2 *p = ep + ((size_t)(ck.rt0 + tc) * (KK / 2)) * 64 + lane;
-#pragma unroll
-        for (int q2 = 0; q2 < KK / 2; q2++) {
-            const float2 v = p[q2 * 64];
-            ef[i][2 * q2] = v.x;
-            ef[i][2 * q2 + 1] = v.y;
-        }
-    }
-#endif
 }
 
 template <int KK, bool LAT_F64, bool FUSE_GMM, bool SPLIT>
@@ -222,11 +187,10 @@ __global__ __launch_bounds__(MG_CS_BLOCK) void mg_frames_cs_kernel(
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    MG_LITE_DECL
-    MG_LITE(0);
-    constexpr bool GMM_LDSX = FUSE_GMM && !LAT_F64 && MG_CS_GMM_LDSX && !MG_CS_GMM_EARLY && MG_CS_NCW - MG_CS_NSP == 4;   // (four staging waves)
-    constexpr bool GMM_HALF = GMM_LDSX && MG_CS_GMM_EARLY_HALF && MG_WS_NPW == 4;
-    if (wave == 0) MG_SUB_STAMP(14, 0, 0);
+    // float32 latents: the mixture's two latent tiles staged in LDS at start-up, both components of a producer wave requested at once
+    constexpr bool GMM_LDSX = FUSE_GMM && !LAT_F64 && MG_CS_NCW - MG_CS_NSP == 4;   // (four staging waves)
+    // with the staged tail: components 4 .. 7 are scored at start-up by the four sweep waves that produce nothing
+    constexpr bool GMM_HALF = GMM_LDSX && MG_WS_NPW == 4;
     // Kernel arguments: left alone, the compiler fetches each where a role first uses it -- a dependent trip to memory per
     // 64-byte line of the argument block (wave 0 alone made eight in a row before it had issued its loads, 4.8 us after entry).
     // Asking for all of them here makes that one trip; the later uses hit the scalar cache.
@@ -279,7 +243,7 @@ __global__ __launch_bounds__(MG_CS_BLOCK) void mg_frames_cs_kernel(
         constexpr int MEAN_NTH = 64 * (MG_CS_NCW - MG_CS_NSP);
         const int n_mean = ck.ntiles * 16, e0 = tid - 64 * (MG_CS_NPW + MG_CS_NSP);
         float mv[6];
-        // ... and two of them stage the latent tiles of the workgroup's mixture scoring (MG_CS_GMM_LDSX, float32 latents): requested with mean'
+        // ... and two of them stage the latent tiles of the workgroup's mixture scoring (GMM_LDSX, float32 latents): requested with mean'
         [[maybe_unused]] float gxv[KK];
         [[maybe_unused]] const int gx_tile = cj - MG_CS_NSP;   // 0, 1: the group's first / second tile
         [[maybe_unused]] bool gx_on = false;
@@ -322,7 +286,6 @@ __global__ __launch_bounds__(MG_CS_BLOCK) void mg_frames_cs_kernel(
                 if (e0 + i * MEAN_NTH < n_mean) lds_mean[e0 + i * MEAN_NTH] = mv[i];
             for (int e = e0 + 6 * MEAN_NTH; e < n_mean; e += MEAN_NTH) lds_mean[e] = mean32[(size_t)ck.rt0 * 16 + e];   // (windows beyond 6 * MEAN_NTH rows)
             mg_publish(prog + MG_CS_PROG_MEAN, cj - MG_CS_NSP, lane, 1);   // (the first unit waits for this: nothing of the mixture's in front of it)
-            MG_LITE(5);
             if constexpr (GMM_LDSX) {   // the mixture's tables, with a flag of their own (prog + MG_CS_PROG_GMM + 20 + i) that the tail waits for
                 if (gx_on) {
                     mg_lds_f32 *gx = mg_cs_gmm_x(prog, gK) + gx_tile * KK * 64;
@@ -353,25 +316,6 @@ __global__ __launch_bounds__(MG_CS_BLOCK) void mg_frames_cs_kernel(
                 }
             }
         }
-        if constexpr (FUSE_GMM && MG_CS_GMM_EARLY) {
-            // Round 5's structural attempt, kept for A/B (tools/build_variant.sh x -DMG_CS_GMM_EARLY=1): the mixture while the pipeline
-            // fills.  In the tail (the default) the mixture costs what a launch of its own costs -- the frames alone 69.3 us, the mixture
-            // kernel alone 11.2 us, fused 78.5-82 us: four waves' chains of float64 MFMAs behind 90 KB of fragment loads that wait in
-            // the CU's memory queue behind the last unit's stores.  The four sweep waves that produce nothing are idle until the first
-            // unit is in LDS (~8 us after entry, the HBM idle): here they score the workgroup's first two tiles then, at the lowest
-            // priority.  MEASURED SLOWER: 83.9 against 78.5 us in one process on one buffer (tools/ab.py) -- the fragment loads delay the
-            // row fragments, the float64 MFMAs the first unit, and every microsecond of the first unit is a microsecond of the kernel.
-            // (Two more attempts at the tail's round trips: both components of a wave requested at once, MG_GMM_PAIR_LOADS: 73 spilled
-            // registers, 89.8 us; a component held in the idle sweep waves' registers from the start: 38 spilled, 87.4 us.)
-            if (!producing) {
-                __builtin_amdgcn_s_setprio(0);
-                mg_lds_int *gprog = prog + MG_CS_PROG_GMM;
-                const int gw = cj - MG_CS_NSP;
-                mg_fused_gmm_terms<KK, LAT_F64>(gprog, gPpack, gmP, gcst, lat, a.B, a.ld, L, a.n_tiles, gK, gJT, gw, lane, 0);
-                if (gw < 2) mg_fused_gmm_finish(gprog, logp, a.B, a.n_tiles, gK, gw, lane, 0);
-                __builtin_amdgcn_s_setprio(3);
-            }
-        }
         const int nql = (D - nroot + 3) >> 2;             // quad lanes per sample
         const int gl = nql + 1;                           // + the root lane
         const int rpi = 64 / gl;                          // samples per wave instruction
@@ -380,7 +324,7 @@ __global__ __launch_bounds__(MG_CS_BLOCK) void mg_frames_cs_kernel(
         // last quads (columns 68 .. 79, lanes 36-38) and the third sample's first ones (columns 4 .. 15, lanes 40-42) are different
         // addresses in the same banks whenever the two samples share their tap rows -- one extra LDS cycle on most tap reads.
         // Shifted, lanes 60-62 read the addresses lanes 36-38 read (a broadcast).
-        const bool shift3 = MG_SWEEP_LANEMAP && gl == 20;
+        const bool shift3 = gl == 20;
         const int lane_s = (shift3 && lane >= 40) ? lane - 4 : lane;
         const int fsub = lane_s / gl, ql = lane_s - fsub * gl;
         const bool lane_on = shift3 ? (lane < 40 || lane >= 44) : lane < rpi * gl;
@@ -401,9 +345,6 @@ __global__ __launch_bounds__(MG_CS_BLOCK) void mg_frames_cs_kernel(
         const float4 *lds_w = (const float4 *)tb_base;
         const int *lds_mo = (const int *)(lds_w + max_nt);
         const int col0 = ck.imin * Dp - ck.rt0 * 16;
-        if (wave == 8) MG_SUB_STAMP(15, 2, 0);
-        if (wave == 4) MG_SUB_STAMP(15, 2, 1);
-        MG_STAMP_DECL
         if (n_units > 0 && producing) {   // this wave's tiles of the first unit
             mg_cs_wait_mean(prog);
             mg_cs_wait_latents(prog, 1);
@@ -411,16 +352,10 @@ __global__ __launch_bounds__(MG_CS_BLOCK) void mg_frames_cs_kernel(
             mg_publish(prog, wave, lane, 1);
         }
         for (int u = 0; u < n_units; u++) {
-            MG_STAMP(0);
             const int64_t b0 = (int64_t)(t_begin + u) * MG_NCAND;
             const int ncand = (int)((a.B - b0) < MG_NCAND ? (a.B - b0) : MG_NCAND);
             mg_cs_wait_produced(prog, u + 1);
-            MG_STAMP(1);
-            MG_UNIT_STAMP(u, 0);
-            if (u == 0) MG_LITE(1);
-            if (u == n_units - 1) MG_LITE(2);
             const int slot = u & 1;
-            [[maybe_unused]] const bool throttle_now = FUSE_GMM && u == n_units - 1;
             const unsigned char *img = smem + (size_t)slot * buf_bytes;
             const float *lds_ro = (const float *)(ro_base + (size_t)slot * RO_BYTES);
             const bool has1 = cj + 8 < ncand;
@@ -434,14 +369,13 @@ __global__ __launch_bounds__(MG_CS_BLOCK) void mg_frames_cs_kernel(
                 constexpr int DP4 = decltype(pitch_tag)::value;
                 constexpr bool ALL4 = decltype(all4_tag)::value;   // the usual shape as a constant: every lane stores four floats
                 const bool all4l = ALL4 ? true : all4;
-                if constexpr (ALL4 && !SPLIT && MG_SWEEP_FAST) {
+                if constexpr (ALL4 && !SPLIT) {
                     // The trips whose six samples all lie inside the chunk, lean: the lanes that hold no sample sit the whole loop
                     // out (one exec mask for the loop, none per store); every lane runs the taps -- the root lane on the first
                     // quad lane's columns, so that channel 3 is already in its first register: no cross-lane read -- and the root
                     // lanes then take the three root outputs from wave 0's table; the stores address memory as a scalar base +
                     // a 32-bit lane offset.  Same operations on the same values as the general loop below: the same bits.
-                    if (MG_DBG(4 | 8192 | 16384)) {   // (the sweep's ablations live in the general loop)
-                    } else if (lane_on) {
+                    if (lane_on) {
                         for (; f_first + 2 * rpi <= f_last; f_first += 2 * rpi) {
                             const int fa_ = f_first + fsub, fb_ = fa_ + rpi;
                             const float4 wa = lds_w[fa_], wb = lds_w[fb_];
@@ -462,9 +396,6 @@ __global__ __launch_bounds__(MG_CS_BLOCK) void mg_frames_cs_kernel(
                                 mg_store4_s(pa1, lane_out_b, v1a);
                                 mg_store4_s(pa1 + (size_t)rpi * D, lane_out_b, v1b);
                             }
-                            if constexpr (MG_CS_STORE_THROTTLE >= 0) {   // A/B only: at most so many stores of this wave in flight (see the macro)
-                                if (!MG_CS_THROTTLE_LAST_ONLY || throttle_now) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(MG_CS_STORE_THROTTLE) : "memory");
-                            }
                         }
                     } else {
                         f_first += (f_last - f_first) / (2 * rpi) * (2 * rpi);
@@ -478,31 +409,18 @@ __global__ __launch_bounds__(MG_CS_BLOCK) void mg_frames_cs_kernel(
                     float *pb0 = pa0 + (size_t)rpi * D, *pb1 = pa1 + (size_t)rpi * D;
                     if (f0 + rpi < ck.nT) {   // the usual trip: both row groups
                         f32x4 v0a, v0b, v1a, v1b;
-                        if (MG_DBG(4)) {   // ablation: stores only
-                            v0a = v0b = v1a = v1b = f32x4{1.f, 2.f, 3.f, 4.f};
-                        } else if (SPLIT || !root_lane) {   // all 16 tap rows are requested before the first FMA
+                        if (SPLIT || !root_lane) {   // all 16 tap rows are requested before the first FMA
                             const float4 wa = lds_w[fa_], wb = lds_w[fb_];
                             const int moa = lds_mo[fa_], mob = lds_mo[fb_];
                             mg_rootm ma, mb;   // SPLIT: every lane asks (a broadcast read), the root lanes use them
                             if constexpr (SPLIT) { ma = mg_rootm_load(lds_m, fa_); mb = mg_rootm_load(lds_m, fb_); }
-                            mg_tap_rows r0a, r0b, r1a, r1b;
-                            if (MG_DBG(16384)) {   // ablation: no tap reads (the FMAs run on what is in registers anyway)
-                                const f32x4 k = {wa.x, wa.y, wb.z, wb.w};
-                                r0a = r0b = r1a = r1b = mg_tap_rows{k, k, k, k};
-                            } else {
-                                r0a = mg_quad_load<DP4>(img0 + moa, dp4); r0b = mg_quad_load<DP4>(img0 + mob, dp4);
-                                r1a = mg_quad_load<DP4>(img1 + moa, dp4); r1b = mg_quad_load<DP4>(img1 + mob, dp4);
-                            }
+                            const mg_tap_rows r0a = mg_quad_load<DP4>(img0 + moa, dp4), r0b = mg_quad_load<DP4>(img0 + mob, dp4);
+                            const mg_tap_rows r1a = mg_quad_load<DP4>(img1 + moa, dp4), r1b = mg_quad_load<DP4>(img1 + mob, dp4);
                             __builtin_amdgcn_sched_barrier(0);
-                            if (MG_DBG(8192)) {   // ablation: the tap reads, no FMAs
-                                v0a = r0a.t0 + r0a.t1 * 0.f; v0b = r0b.t2; v1a = r1a.t3; v1b = r1b.t1;
-                                asm volatile("" ::"v"(r0a.t2), "v"(r0a.t3), "v"(r0b.t0), "v"(r0b.t1), "v"(r0b.t3), "v"(r1a.t0), "v"(r1a.t1), "v"(r1a.t2), "v"(r1b.t0), "v"(r1b.t2), "v"(r1b.t3));
-                            } else {
-                                v0a = mg_quad_fma(r0a, wa);
-                                v0b = mg_quad_fma(r0b, wb);
-                                v1a = mg_quad_fma(r1a, wa);
-                                v1b = mg_quad_fma(r1b, wb);
-                            }
+                            v0a = mg_quad_fma(r0a, wa);
+                            v0b = mg_quad_fma(r0b, wb);
+                            v1a = mg_quad_fma(r1a, wa);
+                            v1b = mg_quad_fma(r1b, wb);
                             if constexpr (SPLIT) {
                                 if (root_lane) {
                                     if constexpr (ALL4) {   // (all4: three root channels in columns 1 .. 3)
@@ -520,12 +438,7 @@ __global__ __launch_bounds__(MG_CS_BLOCK) void mg_frames_cs_kernel(
                             v1a = *(const f32x4 *)&ro1[fa_ * 4];
                             v1b = *(const f32x4 *)&ro1[fb_ * 4];
                         }
-                        if (all4l && MG_DBG(4)) {
-                            if (oa) mg_store4_at(pa0, lane_out_b, v0a);
-                            if (ob) mg_store4_at(pb0, lane_out_b, v0b);
-                            if (oa && has1) mg_store4_at(pa1, lane_out_b, v1a);
-                            if (ob && has1) mg_store4_at(pb1, lane_out_b, v1b);
-                        } else if (all4l) {
+                        if (all4l) {
                             const float b0a = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(q0_lane, __builtin_bit_cast(int, v0a[0])));
                             const float b0b = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(q0_lane, __builtin_bit_cast(int, v0b[0])));
                             const float b1a = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(q0_lane, __builtin_bit_cast(int, v1a[0])));
@@ -573,70 +486,35 @@ __global__ __launch_bounds__(MG_CS_BLOCK) void mg_frames_cs_kernel(
                     }
                 }
             };
-            const bool mine = cj < ncand && !MG_DBG(2);
-            if (mine) {
+            if (cj < ncand) {
                 if (dp4 == 320 && all4) sweep_rows(std::integral_constant<int, 320>{}, std::true_type{}, 0, ck.nT);
                 else sweep_rows(std::integral_constant<int, 0>{}, std::false_type{}, 0, ck.nT);
             }
-            MG_STAMP(4);
-            MG_UNIT_STAMP(u, 1);
-            if (u == n_units - 1) MG_LITE(4);
             mg_publish(prog + MG_CS_PROG_SWEPT, cj, lane, u + 1);
-            MG_STAMP(5);
             if (u + 1 < n_units && producing) {
                 // the producing sweep waves are the four oldest, which finish a unit first: its row tiles of the NEXT unit go
                 // into the slot the unit before this one was swept from (every sweep wave is past it by now, as a rule)
                 mg_cs_wait_swept(prog, u);
                 mg_cs_wait_latents(prog, u + 2);
-                MG_STAMP(3);
                 mg_cs_produce<KK, TPWS>(ef, lds_latb + ((u + 1) & 1) * KK * 64, lds_mean, (float *)(smem + (size_t)((u + 1) & 1) * buf_bytes), stride,
                                         nt_p + cj, MG_CS_NSP, ck.ntiles, lane, cl, g);
                 mg_publish(prog, wave, lane, u + 2);
-                MG_STAMP(2);
             }
         }
-        MG_STAMP_DUMP;
-        MG_LITE_DUMP;
     } else if (wave != 0) {
         // ================= row producers (waves 1..3): TPWP row tiles each, the fragments in registers =================
         const int pw = wave - 1;
         float ef[TPWP][KK];
         mg_lds_barrier();
-        MG_LITE(5);
-        MG_SUB_STAMP(14 + (wave == 1 ? 1 : 0), wave == 1 ? 0 : 1, 0);
         mg_cs_load_fragments<KK, TPWP>(ef, ep, ck, pw, NRP, lane, a.rt_total);   // in tile order: the first unit's MFMAs start as its first fragments land
-        if (MG_DBG(32)) {   // when do the fragments land?
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            MG_SUB_STAMP(14 + (wave == 1 ? 1 : 0), wave == 1 ? 0 : 1, 1);
-        }
         mg_cs_wait_mean(prog);
-        MG_LITE(2);
-        MG_STAMP_DECL
         for (int u = 0; u < n_units; u++) {
-            MG_STAMP(0);
             if (u >= 2) mg_cs_wait_swept(prog, u - 1);   // the slot's previous unit has been swept
             mg_cs_wait_latents(prog, u + 1);
-            MG_STAMP(5);
-            MG_UNIT_STAMP(u, 0);
-            if (u == 0) MG_LITE(6);
-            if (!MG_DBG(1))
-                mg_cs_produce<KK, TPWP>(ef, lds_latb + (u & 1) * KK * 64, lds_mean, (float *)(smem + (size_t)(u & 1) * buf_bytes), stride, pw, NRP, nt_p,
-                                        lane, cl, g);
-            MG_STAMP(2);
-            MG_UNIT_STAMP(u, 1);
+            mg_cs_produce<KK, TPWP>(ef, lds_latb + (u & 1) * KK * 64, lds_mean, (float *)(smem + (size_t)(u & 1) * buf_bytes), stride, pw, NRP, nt_p,
+                                    lane, cl, g);
             mg_publish(prog, wave, lane, u + 1);
-            if (u == 0) MG_LITE(7);
-            MG_STAMP(4);
-            if (MG_DBG(2048)) {   // experiment: what would streaming five more row tiles' fragments per unit from L2 cost?
-                for (int i = 0; i < 5; i++) {
-                    const int tc = min(nt_p + pw * 5 + i, ck.ntiles - 1);
-                    const float2 *pp = ep + ((size_t)(ck.rt0 + tc) * (KK / 2)) * 64 + lane;
-#pragma unroll
-                    for (int q2 = 0; q2 < KK / 2; q2++) { const float2 v = pp[q2 * 64]; asm volatile("" ::"v"(v.x), "v"(v.y)); }
-                }
-            }
         }
-        MG_STAMP_DUMP;
     } else {
         // ================= wave 0: the chunk's tables (once); per unit the latent tile -> LDS, root rows and root taps (f64 MFMA) =================
         // every load first, the ones the first unit's root chains wait for at the head of the queue; the index arithmetic after them
@@ -670,25 +548,17 @@ __global__ __launch_bounds__(MG_CS_BLOCK) void mg_frames_cs_kernel(
                     tm[2 * lane + 1] = ml_v;
                 }
             }
-            MG_STAMP_DECL
             for (int u = 0; u < n_units; u++) {
-                MG_STAMP(0);
 #pragma unroll
                 for (int kk = 0; kk < KK; kk++) s64frag[kk] = s64next[kk];
                 if (u >= 2) mg_cs_wait_swept(prog, u - 1);   // every wave is done with the slot's previous unit, its latent tile included
-                MG_STAMP(5);
-                MG_UNIT_STAMP(u, 0);
                 float *lb = lds_latb + (u & 1) * KK * 64;
 #pragma unroll
                 for (int kk = 0; kk < KK; kk++) lb[kk * 64 + lane] = (float)s64frag[kk];
                 mg_publish(prog, MG_CS_PROG_LAT, lane, u + 1);
                 load_latents(s64next, u + 1);   // a unit ahead
-                MG_STAMP(3);
-                MG_UNIT_STAMP(u, 1);
                 mg_publish(prog, wave, lane, u + 1);   // (the first one: the tables are in LDS)
-                MG_STAMP(4);
             }
-            MG_STAMP_DUMP;
         } else {
         const double *rpp[3];
         double rm_v[3][4];   // mean of the root rows: the C-in of the root chains, parked in LDS
@@ -721,8 +591,6 @@ __global__ __launch_bounds__(MG_CS_BLOCK) void mg_frames_cs_kernel(
         const float4 tw_v = w32[ck.t0 + tl];
         const int ti_v = i0tab[ck.t0 + tl];
         mg_lds_barrier();
-        MG_SUB_STAMP(15, 1, 0);
-        MG_LITE(5);
         // LDS offsets of the root stage, every access unconditional: what must not count reads a zero (lds_rmean[63]), what must
         // not land goes to a spare slot (the padding double of a candidate's root image row; the fourth float of a root output)
         double *rs = (double *)rs_base;
@@ -760,19 +628,13 @@ __global__ __launch_bounds__(MG_CS_BLOCK) void mg_frames_cs_kernel(
             }
         };
         if (lane == 63) lds_rmean[63] = 0.0;
-        MG_SUB_STAMP(15, 1, 1);
-        MG_SUB_STAMP(14, 0, 1);
-        MG_STAMP_DECL
         // one unit of the root stage; the first one is peeled (FIRST) so that what only it uses -- the one-time loads still in
         // registers -- is dead in the loop over the others
         auto root_unit = [&](const int u, auto first_tag) {
             constexpr bool FIRST = decltype(first_tag)::value;
-            MG_STAMP(0);
 #pragma unroll
             for (int kk = 0; kk < KK; kk++) s64frag[kk] = s64next[kk];
             if (u >= 2) mg_cs_wait_swept(prog, u - 1);   // every wave is done with the slot's previous unit: image, root outputs, latent tile
-            MG_STAMP(5);
-            MG_UNIT_STAMP(u, 0);
             {   // the latent tile as float32 MFMA B fragments for all the other waves
                 float *lb = lds_latb + (u & 1) * KK * 64;
 #pragma unroll
@@ -782,13 +644,6 @@ __global__ __launch_bounds__(MG_CS_BLOCK) void mg_frames_cs_kernel(
             // the next unit's latents, a unit ahead -- but not yet in the first unit: the request would queue behind the row
             // fragments still being issued and hold this wave up; there it goes out after the root stage
             if (!FIRST) load_latents(s64next, u + 1);
-            MG_SUB_STAMP(12, u, 0);
-            if (u == 0) MG_LITE(6);
-            if (MG_DBG(1024)) {   // ablation: no root stage
-                if (FIRST) { park_tables(); load_latents(s64next, 1); }
-                MG_STAMP(3); mg_publish(prog, wave, lane, u + 1); MG_STAMP(4);
-                return;
-            }
             // up to 3 root tiles (rows rr = i*nroot + d), chains interleaved; v_mfma_f64_16x16x4_f64 C/D: col = lane & 15, row = (lane >> 4) + 4*reg
             f64x4 racc[3];
 #pragma unroll
@@ -828,14 +683,12 @@ __global__ __launch_bounds__(MG_CS_BLOCK) void mg_frames_cs_kernel(
                             if (h0 + q2 < KK) racc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(rp[t][q2], (double)s64frag[h0 + q2 < KK ? h0 + q2 : KK - 1], racc[t], 0, 0, 0);
                 }
             }
-            MG_SUB_STAMP(12, u, 1);
 #pragma unroll
             for (int t = 0; t < 3; t++)
 #pragma unroll
                 for (int r = 0; r < 4; r++) rs[rs_off[t][r]] = racc[t][r];
             if (FIRST) park_tables();
             // root taps on the float64 matrix pipe against the chunk's banded weight matrix (see the tile-major kernel)
-            MG_SUB_STAMP(13, u, 0);
             float *ro = (float *)(ro_base + (size_t)(u & 1) * RO_BYTES);
             double bv[3][MG_TAP_KS];
 #pragma unroll
@@ -859,43 +712,35 @@ __global__ __launch_bounds__(MG_CS_BLOCK) void mg_frames_cs_kernel(
                         for (int r = 0; r < 4; r++) ro[tap_o_off[ct] + (ft * 16 + g + 4 * r) * 4] = (float)acc[ct][r];
                 }
             }
-            MG_STAMP(3);
-            MG_UNIT_STAMP(u, 1);
-            MG_SUB_STAMP(13, u, 1);
-            if (u == 0) MG_LITE(7);
             mg_publish(prog, wave, lane, u + 1);
             if (FIRST) load_latents(s64next, 1);
-            MG_STAMP(4);
         };
         if (n_units > 0) root_unit(0, std::true_type{});
         for (int u = 1; u < n_units; u++) root_unit(u, std::false_type{});
-        MG_STAMP_DUMP;
         }
     }
     if (FUSE_GMM && wave < MG_WS_NPW) {   // the mixture: the four producer waves, as in the tile-major kernel
+        // In the tail the mixture costs what a launch of its own costs -- the frames alone 69.3 us, the mixture kernel alone 11.2 us,
+        // fused 78.5-82 us: four waves' chains of float64 MFMAs behind 90 KB of fragment loads that wait in the CU's memory queue behind
+        // the last unit's stores.  Round 5 scored the workgroup's first two tiles while the pipeline fills instead, in the four sweep
+        // waves that produce nothing (idle until the first unit is in LDS, ~8 us after entry, the HBM idle) at the lowest priority.
+        // MEASURED SLOWER: 83.9 against 78.5 us in one process on one buffer -- the fragment loads delay the row fragments, the float64
+        // MFMAs the first unit, and every microsecond of the first unit is a microsecond of the kernel.  (Two more attempts at the tail's
+        // round trips: both components of a wave requested at once with the latents in registers: 73 spilled registers, 89.8 us; a
+        // component held in the idle sweep waves' registers from the start: 38 spilled, 87.4 us.)
         mg_lds_int *gprog = prog + MG_CS_PROG_GMM;
-        if constexpr (!MG_CS_GMM_EARLY) {
-            MG_UNIT_STAMP(29, 0);   // (diagnostic build: the tail's timeline in rows "unit" 29 .. 30 of the producer waves)
-            MG_LITE(1);
-            bool staged = false;
-            if constexpr (GMM_LDSX) staged = a.gmm_staged != 0;   // (uniform: where the staged tables did not fit LDS the tail loads everything itself)
-            if (staged) {
-                if constexpr (GMM_LDSX) {
-                    mg_wait_producers(gprog + 20, 1);   // the four staging waves' flags (long since set)
-                    mg_fused_gmm_terms_ldsx<KK>(gprog, gPpack, mg_cs_gmm_x(prog, gK), mg_cs_gmm_mp(prog, gK, KK), mg_cs_gmm_mp(prog, gK, KK) + gK * gJT * 16,
-                                                a.n_tiles, gK, gJT, wave, lane, GMM_HALF && mg_cs_gmm_early(a));
-                    if constexpr (GMM_HALF) mg_wait_producers(gprog + 28, 1);   // the start-up's terms (set long ago)
-                }
-            } else
-                mg_fused_gmm_terms<KK, LAT_F64>(gprog, gPpack, gmP, gcst, lat, a.B, a.ld, L, a.n_tiles, gK, gJT, wave, lane, 0);
-            MG_UNIT_STAMP(29, 1);
-            MG_LITE(3);
-            MG_UNIT_STAMP(30, 0);
-            if (wave < 2) mg_fused_gmm_finish(gprog, logp, a.B, a.n_tiles, gK, wave, lane, 0);
-            MG_UNIT_STAMP(30, 1);
-            MG_LITE(4);
-            MG_LITE_DUMP;
-        }
+        bool staged = false;
+        if constexpr (GMM_LDSX) staged = a.gmm_staged != 0;   // (uniform: where the staged tables did not fit LDS the tail loads everything itself)
+        if (staged) {
+            if constexpr (GMM_LDSX) {
+                mg_wait_producers(gprog + 20, 1);   // the four staging waves' flags (long since set)
+                mg_fused_gmm_terms_ldsx<KK>(gprog, gPpack, mg_cs_gmm_x(prog, gK), mg_cs_gmm_mp(prog, gK, KK), mg_cs_gmm_mp(prog, gK, KK) + gK * gJT * 16,
+                                            a.n_tiles, gK, gJT, wave, lane, GMM_HALF && mg_cs_gmm_early(a));
+                if constexpr (GMM_HALF) mg_wait_producers(gprog + 28, 1);   // the start-up's terms (set long ago)
+            }
+        } else
+            mg_fused_gmm_terms<KK, LAT_F64>(gprog, gPpack, gmP, gcst, lat, a.B, a.ld, L, a.n_tiles, gK, gJT, wave, lane, 0);
+        if (wave < 2) mg_fused_gmm_finish(gprog, logp, a.B, a.n_tiles, gK, wave, lane, 0);
         const int64_t my_tiles = ((int64_t)blockIdx.x + 1) * a.n_tiles / gridDim.x - (int64_t)blockIdx.x * a.n_tiles / gridDim.x;
         if (my_tiles > 2) {
             mg_wait_producers(gprog + 24, 1);   // gfin[0], gfin[1]: both term buffers are free again
@@ -949,18 +794,14 @@ static int mg_launch_cs_kk(mg_primitive *p, const mg_time_grid *g, const void *l
 int mg_launch_frames_cs(mg_primitive *p, const mg_time_grid *g, const void *lat, float *out, float *logp, const mg_frames_args &a, bool lat_f64,
                         bool split, int buf_bytes, int lds, int grid, const mg_launch_events &ev) {
     switch (p->KK) {
-#ifndef MG_ONLY_KK10
         case 2: return mg_launch_cs_kk<2>(p, g, lat, out, logp, a, lat_f64, split, buf_bytes, lds, grid, ev);
         case 4: return mg_launch_cs_kk<4>(p, g, lat, out, logp, a, lat_f64, split, buf_bytes, lds, grid, ev);
         case 6: return mg_launch_cs_kk<6>(p, g, lat, out, logp, a, lat_f64, split, buf_bytes, lds, grid, ev);
         case 8: return mg_launch_cs_kk<8>(p, g, lat, out, logp, a, lat_f64, split, buf_bytes, lds, grid, ev);
-#endif
         case 10: return mg_launch_cs_kk<10>(p, g, lat, out, logp, a, lat_f64, split, buf_bytes, lds, grid, ev);
-#ifndef MG_ONLY_KK10
         case 12: return mg_launch_cs_kk<12>(p, g, lat, out, logp, a, lat_f64, split, buf_bytes, lds, grid, ev);
         case 14: return mg_launch_cs_kk<14>(p, g, lat, out, logp, a, lat_f64, split, buf_bytes, lds, grid, ev);
         case 16: return mg_launch_cs_kk<16>(p, g, lat, out, logp, a, lat_f64, split, buf_bytes, lds, grid, ev);
-#endif
         default: mg_set_error("mg_back_project_frames: MFMA path needs n_components <= 64"); return MG_ERR_UNSUPPORTED;
     }
 }
@@ -981,17 +822,13 @@ static int mg_cs_attr_kk() {
 }
 int mg_frames_cs_attributes() {
     int rc;
-#ifndef MG_ONLY_KK10
     if ((rc = mg_cs_attr_kk<2>()) != MG_OK) return rc;
     if ((rc = mg_cs_attr_kk<4>()) != MG_OK) return rc;
     if ((rc = mg_cs_attr_kk<6>()) != MG_OK) return rc;
     if ((rc = mg_cs_attr_kk<8>()) != MG_OK) return rc;
-#endif
     if ((rc = mg_cs_attr_kk<10>()) != MG_OK) return rc;
-#ifndef MG_ONLY_KK10
     if ((rc = mg_cs_attr_kk<12>()) != MG_OK) return rc;
     if ((rc = mg_cs_attr_kk<14>()) != MG_OK) return rc;
     if ((rc = mg_cs_attr_kk<16>()) != MG_OK) return rc;
-#endif
     return MG_OK;
 }

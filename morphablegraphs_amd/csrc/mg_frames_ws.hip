@@ -46,14 +46,13 @@ __global__ __launch_bounds__(MG_WS_BLOCK) void mg_frames_ws_kernel(
     cur.chunk = (int)(u_begin - (int64_t)cur.tile * a.n_chunks);
     // When this workgroup owns whole tiles it walks each tile's chunks starting at chunk (blockIdx mod n_chunks): the
     // workgroups run nearly in lockstep, and without the rotation all 256 of them request the same E' rows from L2 at
-    // the same time, the cold first unit above all (-2 % kernel time; MG_DEBUG_FLAGS & 128 switches it off).
-    const int rot = (!MG_DBG(128) && cur.chunk == 0 && (n_units % a.n_chunks) == 0) ? (int)(blockIdx.x % a.n_chunks) : 0;
+    // the same time, the cold first unit above all (-2 % kernel time).
+    const int rot = (cur.chunk == 0 && (n_units % a.n_chunks) == 0) ? (int)(blockIdx.x % a.n_chunks) : 0;
     const int cl = lane & 15, g = lane >> 4;
 
     if (wave >= MG_WS_NPW) {
         // ================= consumers =================
         const int cj = wave - MG_WS_NPW;                  // candidates cj and cj + 8
-        MG_STAMP_DECL
         const int nql = (D - nroot + 3) >> 2;             // quad lanes per sample
         const int gl = nql + 1;                           // + the root lane
         const int rpi = 64 / gl;                          // samples per wave instruction
@@ -62,7 +61,7 @@ __global__ __launch_bounds__(MG_WS_BLOCK) void mg_frames_ws_kernel(
         // last quads (columns 68 .. 79, lanes 36-38) and the third sample's first ones (columns 4 .. 15, lanes 40-42) are different
         // addresses in the same banks whenever the two samples share their tap rows -- one extra LDS cycle on most tap reads.
         // Shifted, lanes 60-62 read the addresses lanes 36-38 read (a broadcast).
-        const bool shift3 = MG_SWEEP_LANEMAP && gl == 20;
+        const bool shift3 = gl == 20;
         const int lane_s = (shift3 && lane >= 40) ? lane - 4 : lane;
         const int fsub = lane_s / gl, ql = lane_s - fsub * gl;
         const bool lane_on = shift3 ? (lane < 40 || lane >= 44) : lane < rpi * gl;
@@ -79,17 +78,15 @@ __global__ __launch_bounds__(MG_WS_BLOCK) void mg_frames_ws_kernel(
         // When every quad lane holds four floats and the root lane three (D = 79: 3 + 19 x 4), the root lane borrows the
         // row's channel 3 from quad lane 0 (a cross-lane read) and ALL lanes store four floats with one instruction;
         // the float written twice carries the same value.  Otherwise lanes store 4 / 3 / 2 / 1 floats by class.
-        const bool all4 = nroot == 3 && ((D - nroot) & 3) == 0 && !MG_DBG(8192);
+        const bool all4 = nroot == 3 && ((D - nroot) & 3) == 0;
         const int q0_lane = (lane - nql) << 2;            // byte index of this row's quad lane 0 for ds_bpermute
         const unsigned lane_out_b = (unsigned)lane_out * 4u;
         int slot = 0;
         for (int u = 0; u < n_units; u++) {
-            MG_STAMP(0);
             const mg_unit un_prev = mg_unit_at(chunks, a, cur, rot);
             mg_cursor_next(cur, a.n_chunks);
             mg_wait_producers(prog, u + 1);
-            MG_STAMP(1);
-            if (!MG_DBG(2) && cj < un_prev.ncand) {
+            if (cj < un_prev.ncand) {
                 const mg_chunk &ck = un_prev.ck;
                 const unsigned char *img = smem + (size_t)slot * buf_bytes;
                 const float *lds_ro = (const float *)(ro_base + (size_t)slot * MG_RO_BYTES);
@@ -111,35 +108,33 @@ __global__ __launch_bounds__(MG_WS_BLOCK) void mg_frames_ws_kernel(
                 constexpr bool ALL4 = decltype(all4_tag)::value;   // the usual shape as a constant: every lane stores four floats
                 const bool all4l = ALL4 ? true : all4;
                 int f_first = 0;
-                if constexpr (ALL4 && !SPLIT && MG_SWEEP_FAST) {
+                if constexpr (ALL4 && !SPLIT) {
                     // the trips whose six samples all lie inside the chunk, lean (see the chunk-stationary kernel): same operations on
                     // the same values as the general loop below
-                    if (!MG_DBG(4 | 8192 | 131072 | 2048)) {
-                        if (lane_on) {
-                            for (; f_first + 2 * rpi <= ck.nT; f_first += 2 * rpi) {
-                                const int fa_ = f_first + fsub, fb_ = fa_ + rpi;
-                                const float4 wa = lds_w[fa_], wb = lds_w[fb_];
-                                const int moa = lds_mo[fa_], mob = lds_mo[fb_];
-                                const mg_tap_rows r0a = mg_quad_load<DP4>(img0 + moa, dp4), r0b = mg_quad_load<DP4>(img0 + mob, dp4);
-                                const mg_tap_rows r1a = mg_quad_load<DP4>(img1 + moa, dp4), r1b = mg_quad_load<DP4>(img1 + mob, dp4);
-                                __builtin_amdgcn_sched_barrier(0);
-                                f32x4 v0a = mg_quad_fma(r0a, wa), v0b = mg_quad_fma(r0b, wb);
-                                f32x4 v1a = mg_quad_fma(r1a, wa), v1b = mg_quad_fma(r1b, wb);
-                                if (root_lane) {
-                                    v0a = mg_root_merge(v0a, ro0 + fa_ * 4); v0b = mg_root_merge(v0b, ro0 + fb_ * 4);
-                                    v1a = mg_root_merge(v1a, ro1 + fa_ * 4); v1b = mg_root_merge(v1b, ro1 + fb_ * 4);
-                                }
-                                float *pa0 = or0 + (size_t)f_first * D, *pa1 = or1 + (size_t)f_first * D;          // uniform
-                                mg_store4_s(pa0, lane_out_b, v0a);
-                                mg_store4_s(pa0 + (size_t)rpi * D, lane_out_b, v0b);
-                                if (has1) {
-                                    mg_store4_s(pa1, lane_out_b, v1a);
-                                    mg_store4_s(pa1 + (size_t)rpi * D, lane_out_b, v1b);
-                                }
+                    if (lane_on) {
+                        for (; f_first + 2 * rpi <= ck.nT; f_first += 2 * rpi) {
+                            const int fa_ = f_first + fsub, fb_ = fa_ + rpi;
+                            const float4 wa = lds_w[fa_], wb = lds_w[fb_];
+                            const int moa = lds_mo[fa_], mob = lds_mo[fb_];
+                            const mg_tap_rows r0a = mg_quad_load<DP4>(img0 + moa, dp4), r0b = mg_quad_load<DP4>(img0 + mob, dp4);
+                            const mg_tap_rows r1a = mg_quad_load<DP4>(img1 + moa, dp4), r1b = mg_quad_load<DP4>(img1 + mob, dp4);
+                            __builtin_amdgcn_sched_barrier(0);
+                            f32x4 v0a = mg_quad_fma(r0a, wa), v0b = mg_quad_fma(r0b, wb);
+                            f32x4 v1a = mg_quad_fma(r1a, wa), v1b = mg_quad_fma(r1b, wb);
+                            if (root_lane) {
+                                v0a = mg_root_merge(v0a, ro0 + fa_ * 4); v0b = mg_root_merge(v0b, ro0 + fb_ * 4);
+                                v1a = mg_root_merge(v1a, ro1 + fa_ * 4); v1b = mg_root_merge(v1b, ro1 + fb_ * 4);
                             }
-                        } else {
-                            f_first = ck.nT / (2 * rpi) * (2 * rpi);
+                            float *pa0 = or0 + (size_t)f_first * D, *pa1 = or1 + (size_t)f_first * D;          // uniform
+                            mg_store4_s(pa0, lane_out_b, v0a);
+                            mg_store4_s(pa0 + (size_t)rpi * D, lane_out_b, v0b);
+                            if (has1) {
+                                mg_store4_s(pa1, lane_out_b, v1a);
+                                mg_store4_s(pa1 + (size_t)rpi * D, lane_out_b, v1b);
+                            }
                         }
+                    } else {
+                        f_first = ck.nT / (2 * rpi) * (2 * rpi);
                     }
                 }
                 for (int f0 = f_first; f0 < ck.nT; f0 += 2 * rpi) {
@@ -148,29 +143,21 @@ __global__ __launch_bounds__(MG_WS_BLOCK) void mg_frames_ws_kernel(
                     const int fa_ = fla < ck.nT ? fla : ck.nT - 1, fb_ = flb < ck.nT ? flb : ck.nT - 1;
                     float *pa0 = or0 + (size_t)f0 * D, *pa1 = or1 + (size_t)f0 * D;          // uniform
                     float *pb0 = pa0 + (size_t)rpi * D, *pb1 = pa1 + (size_t)rpi * D;
-                    if (f0 + rpi < ck.nT || MG_DBG(2048)) {   // the usual trip: both row groups (flag 2048: always)
+                    if (f0 + rpi < ck.nT) {   // the usual trip: both row groups
                         f32x4 v0a, v0b, v1a, v1b;
-                        if (MG_DBG(4)) {   // ablation: stores only
-                            v0a = v0b = v1a = v1b = f32x4{1.f, 2.f, 3.f, 4.f};
-                        } else if (SPLIT || !root_lane) {
+                        if (SPLIT || !root_lane) {
                             const float4 wa = lds_w[fa_], wb = lds_w[fb_];
                             const int moa = lds_mo[fa_], mob = lds_mo[fb_];
                             mg_rootm ma, mb;   // SPLIT: every lane asks (a broadcast read), the root lanes use them
                             if constexpr (SPLIT) { ma = mg_rootm_load(lds_m, fa_); mb = mg_rootm_load(lds_m, fb_); }
-                            if (MG_DBG(131072)) {
-                                v0a = mg_quad_taps_t<DP4>(img0 + moa, wa, dp4);
-                                v0b = mg_quad_taps_t<DP4>(img0 + mob, wb, dp4);
-                                v1a = mg_quad_taps_t<DP4>(img1 + moa, wa, dp4);
-                                v1b = mg_quad_taps_t<DP4>(img1 + mob, wb, dp4);
-                            } else {   // all 16 tap rows are requested before the first FMA
-                                const mg_tap_rows r0a = mg_quad_load<DP4>(img0 + moa, dp4), r0b = mg_quad_load<DP4>(img0 + mob, dp4);
-                                const mg_tap_rows r1a = mg_quad_load<DP4>(img1 + moa, dp4), r1b = mg_quad_load<DP4>(img1 + mob, dp4);
-                                __builtin_amdgcn_sched_barrier(0);
-                                v0a = mg_quad_fma(r0a, wa);
-                                v0b = mg_quad_fma(r0b, wb);
-                                v1a = mg_quad_fma(r1a, wa);
-                                v1b = mg_quad_fma(r1b, wb);
-                            }
+                            // all 16 tap rows are requested before the first FMA
+                            const mg_tap_rows r0a = mg_quad_load<DP4>(img0 + moa, dp4), r0b = mg_quad_load<DP4>(img0 + mob, dp4);
+                            const mg_tap_rows r1a = mg_quad_load<DP4>(img1 + moa, dp4), r1b = mg_quad_load<DP4>(img1 + mob, dp4);
+                            __builtin_amdgcn_sched_barrier(0);
+                            v0a = mg_quad_fma(r0a, wa);
+                            v0b = mg_quad_fma(r0b, wb);
+                            v1a = mg_quad_fma(r1a, wa);
+                            v1b = mg_quad_fma(r1b, wb);
                             if constexpr (SPLIT) {
                                 if (root_lane) {
                                     if constexpr (ALL4) {   // (all4: three root channels in columns 1 .. 3)
@@ -188,12 +175,7 @@ __global__ __launch_bounds__(MG_WS_BLOCK) void mg_frames_ws_kernel(
                             v1a = *(const f32x4 *)&ro1[fa_ * 4];
                             v1b = *(const f32x4 *)&ro1[fb_ * 4];
                         }
-                        if (all4l && MG_DBG(4)) {
-                            if (oa) mg_store4_at(pa0, lane_out_b, v0a);
-                            if (ob) mg_store4_at(pb0, lane_out_b, v0b);
-                            if (oa && has1) mg_store4_at(pa1, lane_out_b, v1a);
-                            if (ob && has1) mg_store4_at(pb1, lane_out_b, v1b);
-                        } else if (all4l) {
+                        if (all4l) {
                             const float b0a = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(q0_lane, __builtin_bit_cast(int, v0a[0])));
                             const float b0b = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(q0_lane, __builtin_bit_cast(int, v0b[0])));
                             const float b1a = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(q0_lane, __builtin_bit_cast(int, v1a[0])));
@@ -241,15 +223,12 @@ __global__ __launch_bounds__(MG_WS_BLOCK) void mg_frames_ws_kernel(
                     }
                 }
                 };
-                if (dp4 == 320 && all4 && !MG_DBG(16384)) sweep_rows(std::integral_constant<int, 320>{}, std::true_type{});
+                if (dp4 == 320 && all4) sweep_rows(std::integral_constant<int, 320>{}, std::true_type{});
                 else sweep_rows(std::integral_constant<int, 0>{}, std::false_type{});
             }
-            MG_STAMP(4);
             mg_publish(prog, wave, lane, u + 1);
             if (++slot == nbuf) slot = 0;
-            MG_STAMP(5);
         }
-        MG_STAMP_DUMP;
     } else if (wave != 0) {
         // ================= f32 producers (waves 1..3): E' fragments -> MFMA -> LDS image =================
         float sfrag[KK];
@@ -259,55 +238,44 @@ __global__ __launch_bounds__(MG_WS_BLOCK) void mg_frames_ws_kernel(
         int prev_tile = -1, prev_chunk = -1;
         const float2 *ep = (const float2 *)Epack;
         int slot = 0;
-        MG_STAMP_DECL
         for (int u = 0; u < n_units; u++) {
-            MG_STAMP(0);
             const mg_unit un = mg_unit_at(chunks, a, cur, rot);
             mg_cursor_next(cur, a.n_chunks);
             if (u >= nbuf) mg_wait_consumers(prog, u - nbuf + 1);   // the slot's previous unit has been swept
-            MG_STAMP(5);
-            if (!MG_DBG(1)) {
-                const mg_chunk &ck = un.ck;
-                float *lds_c = (float *)(smem + (size_t)slot * buf_bytes);
-                if (un.tile != cur_tile) {
-                    cur_tile = un.tile;
-                    int g_op = g;   // opaque: keeps the (loop-invariant) clamped indices from being hoisted and spilled
-                    asm volatile("" : "+v"(g_op));
-                    mg_load_sfrag<KK, LAT_F64>(sfrag, lat, un, a.ld, L, cl, g_op);
-                }
-                // Consecutive chunks of a tile share basis functions (for 'walk' windows of 10 advance by 7): the row tiles this
-                // unit has in common with the previous one are copied from the previous slot (LDS -> LDS, the same
-                // bits) instead of being recomputed: 37 % fewer MFMAs and E' fragment loads, which is what slows
-                // the sweep waves down (matrix-pipe time on the shared SIMDs, L2 requests in the store path).
-                int n_ov = 0, src_shift = 0;
-                if (un.tile == prev_tile && un.chunk == prev_chunk + 1) {   // the previous unit was this tile's previous chunk
-                    const mg_chunk pk = chunks[un.chunk - 1];
-                    src_shift = ck.rt0 - pk.rt0;
-                    n_ov = pk.rt0 + pk.ntiles - ck.rt0;   // tiles [ck.rt0, pk.rt0 + pk.ntiles) exist in the previous slot
-                    n_ov = (n_ov < 0 || src_shift < 0) ? 0 : (n_ov > ck.ntiles ? ck.ntiles : n_ov);   // a grid may run backwards
-                }
-                if (MG_DBG(4096)) n_ov = 0;   // ablation: no carried-over tiles (every window computed in full)
-                // this slot held unit u - nbuf and was the copy source of unit u - nbuf + 1: every row producer must
-                // have finished that unit before the slot is overwritten (with two slots: a full meeting per unit)
-                if (u >= nbuf - 1) mg_wait_row_producers(prog, u - nbuf + 2);
-                mg_produce_f32<KK>(ep, mean32, ck, lds_c, stride, n_ov, wave - 1, MG_WS_NPW - 1, sfrag, lane, cl, g, MG_DBG(256) ? 0 : (int)(blockIdx.x / a.n_chunks),
-                                   (MG_DBG(32768) && (u & 1)) ? (a.debug | 512) : a.debug);   // 32768: E' loads on every other unit only
-                MG_STAMP(2);
-                if (n_ov > 0) {
-                    mg_wait_row_producers(prog, u);   // the previous unit's window is complete
-                    const float *lds_p = (const float *)(smem + (size_t)(slot == 0 ? nbuf - 1 : slot - 1) * buf_bytes);
-                    for (int t = wave - 1; t < n_ov; t += MG_WS_NPW - 1)
-                        *(f32x4 *)&lds_c[cl * stride + t * 16 + 4 * g] = *(const f32x4 *)&lds_p[cl * stride + (t + src_shift) * 16 + 4 * g];
-                }
-                MG_STAMP(3);
+            const mg_chunk &ck = un.ck;
+            float *lds_c = (float *)(smem + (size_t)slot * buf_bytes);
+            if (un.tile != cur_tile) {
+                cur_tile = un.tile;
+                int g_op = g;   // opaque: keeps the (loop-invariant) clamped indices from being hoisted and spilled
+                asm volatile("" : "+v"(g_op));
+                mg_load_sfrag<KK, LAT_F64>(sfrag, lat, un, a.ld, L, cl, g_op);
+            }
+            // Consecutive chunks of a tile share basis functions (for 'walk' windows of 10 advance by 7): the row tiles this
+            // unit has in common with the previous one are copied from the previous slot (LDS -> LDS, the same
+            // bits) instead of being recomputed: 37 % fewer MFMAs and E' fragment loads, which is what slows
+            // the sweep waves down (matrix-pipe time on the shared SIMDs, L2 requests in the store path).
+            int n_ov = 0, src_shift = 0;
+            if (un.tile == prev_tile && un.chunk == prev_chunk + 1) {   // the previous unit was this tile's previous chunk
+                const mg_chunk pk = chunks[un.chunk - 1];
+                src_shift = ck.rt0 - pk.rt0;
+                n_ov = pk.rt0 + pk.ntiles - ck.rt0;   // tiles [ck.rt0, pk.rt0 + pk.ntiles) exist in the previous slot
+                n_ov = (n_ov < 0 || src_shift < 0) ? 0 : (n_ov > ck.ntiles ? ck.ntiles : n_ov);   // a grid may run backwards
+            }
+            // this slot held unit u - nbuf and was the copy source of unit u - nbuf + 1: every row producer must
+            // have finished that unit before the slot is overwritten (with two slots: a full meeting per unit)
+            if (u >= nbuf - 1) mg_wait_row_producers(prog, u - nbuf + 2);
+            mg_produce_f32<KK>(ep, mean32, ck, lds_c, stride, n_ov, wave - 1, MG_WS_NPW - 1, sfrag, lane, cl, g, (int)(blockIdx.x / a.n_chunks));
+            if (n_ov > 0) {
+                mg_wait_row_producers(prog, u);   // the previous unit's window is complete
+                const float *lds_p = (const float *)(smem + (size_t)(slot == 0 ? nbuf - 1 : slot - 1) * buf_bytes);
+                for (int t = wave - 1; t < n_ov; t += MG_WS_NPW - 1)
+                    *(f32x4 *)&lds_c[cl * stride + t * 16 + 4 * g] = *(const f32x4 *)&lds_p[cl * stride + (t + src_shift) * 16 + 4 * g];
             }
             prev_tile = un.tile;
             prev_chunk = un.chunk;
             mg_publish(prog, wave, lane, u + 1);
             if (++slot == nbuf) slot = 0;
-            MG_STAMP(4);
         }
-        MG_STAMP_DUMP;
     } else {
         // ================= wave 0: tables, root rows and root taps (f64 MFMA), one unit ahead =================
         // per-lane constants of the tap MFMA: B operand = rows[m = 4 ks + (l >> 4)][col = 16 ct + (l & 15)] with
@@ -327,7 +295,6 @@ __global__ __launch_bounds__(MG_WS_BLOCK) void mg_frames_ws_kernel(
                 tap_b_off[ct][ks] = cc * root_stride + m * nroot + cd;
             }
         }
-        MG_STAMP_DECL
         auto root_stage = [&](const mg_unit &un, int slot) {   // tables -> tb[slot], root rows -> rs, root outputs -> ro[slot]
             const mg_chunk &ck = un.ck;
             float4 *tw = (float4 *)(tb_base + (size_t)slot * MG_TB_BYTES);
@@ -352,7 +319,6 @@ __global__ __launch_bounds__(MG_WS_BLOCK) void mg_frames_ws_kernel(
             for (int e = 0; e < MG_TAP_FT * MG_TAP_KS; e++) r_wt[e] = wtap[((size_t)un.chunk * (MG_TAP_FT * MG_TAP_KS) + e) * 64 + lane];
             typename mg_gmm_xt<LAT_F64>::type s64frag[KK];   // widened to float64 at the MFMA
             mg_gmm_load_x<KK, LAT_F64>(s64frag, lat, un.b0, un.ncand, a.ld, L, cl, g);
-            if (MG_DBG(32)) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); MG_STAMP(1); }
             // up to 3 root tiles (8 basis functions x 3 channels = 24 rows, rr = i*nroot + d), chains
             // interleaved; v_mfma_f64_16x16x4_f64 C/D: col = lane & 15, row = (lane >> 4) + 4*reg
             f64x4 racc[3];
@@ -399,7 +365,6 @@ __global__ __launch_bounds__(MG_WS_BLOCK) void mg_frames_ws_kernel(
                     if (t < ck.nrt && lr >= 0 && lr < ck.wi * nroot) rs[cl * root_stride + lr] = racc[t][r];
                 }
             }
-            if (MG_DBG(32)) { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); MG_STAMP(2); }
             // root taps, again on the float64 matrix pipe: out[f][(c,d)] = sum_m W[f][m] * rows[m][(c,d)] with the
             // banded W[f][m] = w[f][m - m0(f)] (0 outside the 4 taps) pre-packed per chunk as A fragments.  The zero
             // products leave the accumulator untouched and the taps are met in ascending m, so the result is
@@ -431,23 +396,17 @@ __global__ __launch_bounds__(MG_WS_BLOCK) void mg_frames_ws_kernel(
                             if (tap_o_off[ct] >= 0 && fo < ck.nT) ro[tap_o_off[ct] + fo * 4] = (float)acc[ct][r];
                         }
                 }
-                if (MG_DBG(32) && ft == 0) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); MG_STAMP(6); }
             }
         };
         int slot = 0;
         for (int u = 0; u < n_units; u++) {
-            MG_STAMP(0);
             const mg_unit un = mg_unit_at(chunks, a, cur, rot);
             mg_cursor_next(cur, a.n_chunks);
             if (u >= nbuf) mg_wait_consumers(prog, u - nbuf + 1);
-            MG_STAMP(5);
-            if (!MG_DBG(1) && !MG_DBG(1024)) root_stage(un, slot);
-            MG_STAMP(3);
+            root_stage(un, slot);
             mg_publish(prog, wave, lane, u + 1);
             if (++slot == nbuf) slot = 0;
-            MG_STAMP(4);
         }
-        MG_STAMP_DUMP;
     }
     if (FUSE_GMM && wave < MG_WS_NPW) {
         // up to four tiles per workgroup, as two groups of two written out one after the other (a loop would let the
@@ -508,18 +467,14 @@ static int mg_launch_ws_kk(mg_primitive *p, const mg_time_grid *g, const void *l
 int mg_launch_frames_ws(mg_primitive *p, const mg_time_grid *g, const void *lat, float *out, float *logp, const mg_frames_args &a, bool lat_f64,
                         bool split, int buf_bytes, int lds, int grid, const mg_launch_events &ev) {
     switch (p->KK) {
-#ifndef MG_ONLY_KK10
         case 2: return mg_launch_ws_kk<2>(p, g, lat, out, logp, a, lat_f64, split, buf_bytes, lds, grid, ev);
         case 4: return mg_launch_ws_kk<4>(p, g, lat, out, logp, a, lat_f64, split, buf_bytes, lds, grid, ev);
         case 6: return mg_launch_ws_kk<6>(p, g, lat, out, logp, a, lat_f64, split, buf_bytes, lds, grid, ev);
         case 8: return mg_launch_ws_kk<8>(p, g, lat, out, logp, a, lat_f64, split, buf_bytes, lds, grid, ev);
-#endif
         case 10: return mg_launch_ws_kk<10>(p, g, lat, out, logp, a, lat_f64, split, buf_bytes, lds, grid, ev);
-#ifndef MG_ONLY_KK10
         case 12: return mg_launch_ws_kk<12>(p, g, lat, out, logp, a, lat_f64, split, buf_bytes, lds, grid, ev);
         case 14: return mg_launch_ws_kk<14>(p, g, lat, out, logp, a, lat_f64, split, buf_bytes, lds, grid, ev);
         case 16: return mg_launch_ws_kk<16>(p, g, lat, out, logp, a, lat_f64, split, buf_bytes, lds, grid, ev);
-#endif
         default: mg_set_error("mg_back_project_frames: MFMA path needs n_components <= 64"); return MG_ERR_UNSUPPORTED;
     }
 }
@@ -540,17 +495,13 @@ static int mg_ws_attr_kk() {
 }
 int mg_frames_ws_attributes() {
     int rc;
-#ifndef MG_ONLY_KK10
     if ((rc = mg_ws_attr_kk<2>()) != MG_OK) return rc;
     if ((rc = mg_ws_attr_kk<4>()) != MG_OK) return rc;
     if ((rc = mg_ws_attr_kk<6>()) != MG_OK) return rc;
     if ((rc = mg_ws_attr_kk<8>()) != MG_OK) return rc;
-#endif
     if ((rc = mg_ws_attr_kk<10>()) != MG_OK) return rc;
-#ifndef MG_ONLY_KK10
     if ((rc = mg_ws_attr_kk<12>()) != MG_OK) return rc;
     if ((rc = mg_ws_attr_kk<14>()) != MG_OK) return rc;
     if ((rc = mg_ws_attr_kk<16>()) != MG_OK) return rc;
-#endif
     return MG_OK;
 }

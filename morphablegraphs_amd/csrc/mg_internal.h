@@ -123,9 +123,7 @@ int mg_prof_resolve(mg_context *ctx);
 // [candidate][sample][4] float32.  nt = the grid's longest chunk, rounded up to 16 samples.  A candidate's root outputs are
 // MG_RO_PAD floats apart from a multiple of 32: wave 0 writes them one float per lane, (candidate, channel) x sample, and with a
 // stride of 4 nt floats (0 mod 32 banks for nt = 16, 32, 48) the six candidates of a column tile meet in the same banks.
-#ifndef MG_RO_PAD
 #define MG_RO_PAD 8
-#endif
 #define MG_RO_CS(nt) ((nt) * 4 + MG_RO_PAD)              // floats per candidate
 #define MG_TB_BYTES_N(nt) ((nt) * 16 + (nt) * 4)
 #define MG_RO_BYTES_N(nt) (MG_NCAND * MG_RO_CS(nt) * 4)

@@ -1,5 +1,4 @@
-"""The fused step N times on one placed buffer, for counter passes: python3 tools/probes/run_step.py <lib.so> [n] (MG_DEBUG_FLAGS from the environment
-when the library is the diagnostic build)."""
+"""The fused step N times on one placed buffer, for counter passes: python3 tools/probes/run_step.py <lib.so> [n]."""
 import os
 import sys
 

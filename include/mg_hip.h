@@ -329,7 +329,7 @@ int mg_memset(mg_context *ctx, void *dst_dev, int value, int64_t bytes);
  * slot: 0 = back_project_frames, 1 = gmm_log_prob, 2 = score_constraints, 3 = argmin,
  *       4 = gmm_sample, 5 = spline_evaluate, 6 = fused step, 7 = a planner step in one launch (mg_options_step),
  *       8 = mg_joint_tracks, 9 = mg_score_frame_constraints, 10 = mg_score_trajectory[_points],
- *       11 = mg_cluster_tree_search. */
+ *       11 = mg_cluster_tree_search (both tree kinds: mg_tree_search_kernel or mg_kd_tree_search_kernel). */
 int mg_profile_enable(mg_context *ctx, int enabled);
 int mg_profile_reset(mg_context *ctx);
 int mg_profile_get(mg_context *ctx, int slot, double *total_ms, int64_t *launches);
@@ -783,6 +783,8 @@ typedef struct mg_cluster_tree mg_cluster_tree;
 #define MG_TREE_TIE 1          /* two equal values met in a heap comparison: the reference raises TypeError there */
 #define MG_TREE_NO_RESULT 2    /* no leaf reached (the reference's "failed to find a result"): value +inf, the root's row */
 #define MG_TREE_OVERFLOW 4     /* a heap outgrew its bound (cannot happen for a validated tree; the record is not to be used) */
+#define MG_TREE_NO_MEAN 8      /* KD trees: the search expanded a non-leaf node whose children are KD trees; the reference raises
+                                  AttributeError ('KDTreeWrapper' object has no attribute 'mean') there.  Row and leaf are -1. */
 typedef struct mg_tree_search_record {
     int64_t row;               /* first_index of the winning leaf: the data row the search returns (-1: none) */
     int32_t leaf;              /* the winning leaf node */
@@ -801,6 +803,31 @@ void mg_cluster_tree_destroy(mg_cluster_tree *tree);
  * MG_TREE_MAX_CANDIDATES.  records_dev: n_searches records (device memory). */
 int mg_cluster_tree_search(int32_t n_searches, mg_primitive *const *prims, mg_cluster_tree *const *trees,
                            const mg_constraint_set *const *csets, int32_t n_candidates, mg_tree_search_record *records_dev);
+
+/* ---- k-means / KD cluster tree (reference space_partitioning/cluster_tree.py:117-149, cluster_tree_node.py:63-138,
+ * kdtree.py:132-164,233-250) ----
+ * The ClusterTree of a pickled model, flattened on the host.  Cluster nodes breadth first (node 0 the root): their
+ * k-means children in CSR form as for mg_cluster_tree_create (child_begin (n_nodes + 1), children (n_nodes - 1)); leaf[i]
+ * the node's `leaf` flag; its KDTreeWrapper children as the KD roots kd_roots[kd_begin[i] .. kd_begin[i + 1]).  KD node
+ * k: its point is row k of `points`, its children kd_left[k] / kd_right[k] (-1: none), kd_inner[k] its type == "inner".
+ * points: (n_kd + n_nodes, dim) float64, the n_kd KD points followed by every cluster node's mean (row n_kd + i is node
+ * i's mean).  Validated: the checks of mg_cluster_tree_create on the cluster nodes; a node has cluster children or KD
+ * children, not both; a leaf has no cluster children; every KD node has one parent (a KD root is its cluster node's
+ * child) and is reachable; KD depth <= MG_KD_MAX_DEPTH.  A non-leaf node with KD children is allowed: the search flags
+ * MG_TREE_NO_MEAN when it expands one.  Destroyed with mg_cluster_tree_destroy.
+ *
+ * mg_cluster_tree_search takes these trees as well, one kind per call (a mix: MG_ERR_INVALID_ARGUMENT).  Per level the
+ * frontier's inner nodes' children are scored and kept as for the other kind, with the reference's (value, idx, node)
+ * tuples; every frontier leaf runs its KD descents in the same launch (root point, then at each inner node the right and
+ * the left child's points, left only if strictly better), keeps (cost, depth) per descent, (value, point) per leaf and
+ * (value, c_idx, point) over the search, comparing points lexicographically on equal values; a leaf without KD trees
+ * scores its mean.  Every value has the bits mg_score_constraints gives for that points row.  The record: row = the
+ * winning points row (>= n_kd: a leaf's mean), leaf = its cluster node, evaluations = every objective scored;
+ * MG_TREE_NO_RESULT: row = n_kd (the root's mean). */
+#define MG_KD_MAX_DEPTH 64
+int mg_cluster_tree_create_kd(mg_primitive *prim, int32_t n_nodes, int32_t n_kd, int32_t dim, const double *points, const int32_t *child_begin,
+                              const int32_t *children, const int32_t *leaf, const int32_t *kd_begin, const int32_t *kd_roots,
+                              const int32_t *kd_left, const int32_t *kd_right, const int32_t *kd_inner, mg_cluster_tree **tree);
 
 /* ---- host-pointer convenience variants (H2D, launch, D2H, synchronise) ---------------- */
 int mg_back_project_frames_host(mg_primitive *prim, const mg_time_grid *grid, const void *latents,

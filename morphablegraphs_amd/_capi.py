@@ -41,7 +41,8 @@ PROFILE_SLOTS = {"frames": 0, "gmm_log_prob": 1, "score_constraints": 2, "argmin
                  "gmm_sample": 4, "spline_evaluate": 5, "step": 6, "options_step": 7, "joint_tracks": 8, "frame_constraints": 9, "trajectory": 10,
                  "cluster_tree_search": 11}
 MG_TREE_MAX_DEPTH, MG_TREE_MAX_CHILDREN, MG_TREE_MAX_CANDIDATES = 64, 256, 64    # include/mg_hip.h
-MG_TREE_TIE, MG_TREE_NO_RESULT, MG_TREE_OVERFLOW = 1, 2, 4
+MG_TREE_TIE, MG_TREE_NO_RESULT, MG_TREE_OVERFLOW, MG_TREE_NO_MEAN = 1, 2, 4, 8
+MG_KD_MAX_DEPTH = 64
 # struct mg_tree_search_record
 TREE_SEARCH_RECORD = np.dtype([("row", "<i8"), ("leaf", "<i4"), ("flags", "<i4"), ("evaluations", "<i8"), ("value", "<f8")])
 MG_FUSED_MAX_OPTIONS = 24        # options of one mg_options_step_device_counts launch (csrc/mg_options.hip)
@@ -81,6 +82,7 @@ EXPORTED_SYMBOLS = [
     "mg_align_frames", "mg_frame_constraint_width", "mg_score_frame_constraint", "mg_score_frame_constraints", "mg_options_frame_lists", "mg_track_plan_create", "mg_track_plan_destroy", "mg_joint_tracks",
     "mg_score_constraint_residuals_chained", "mg_option_step", "mg_options_step", "mg_options_step_device_counts", "mg_option_step_rows", "mg_options_step_rows", "mg_gmm_sample_rows", "mg_dist_broadcast",
     "mg_cluster_tree_create", "mg_cluster_tree_destroy", "mg_cluster_tree_search", "mg_cluster_tree_search_host",
+    "mg_cluster_tree_create_kd",
 ]
 
 
@@ -338,6 +340,7 @@ def load_library(path=None):
         "mg_score_constraint_residuals_host": [vp, vp, vp, i32, i64, i64, vp],
         "mg_gmm_log_prob_jac_host": [vp, vp, i32, i64, i64, vp],
         "mg_cluster_tree_create": [vp, i32, i32, vp, vp, vp, vp, i64, C.POINTER(vp)],
+        "mg_cluster_tree_create_kd": [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(vp)],
         "mg_cluster_tree_search": [i32, vp, vp, vp, i32, vp],
         "mg_cluster_tree_search_host": [i32, vp, vp, vp, i32, vp],
     }
@@ -834,6 +837,33 @@ class ClusterTree(object):
             self.close()
         except Exception:
             pass
+
+
+class KdClusterTree(ClusterTree):
+    """A flattened k-means / KD ClusterTree on the device (mg_cluster_tree_create_kd): points (n_kd + n_nodes, dim), the KD
+    points then the cluster nodes' means; the cluster nodes' children (child_begin, children), leaf flags and KD roots
+    (kd_begin, kd_roots); the KD nodes' kd_left, kd_right, kd_inner.  Searched by search_cluster_trees like ClusterTree."""
+
+    def __init__(self, prim, points, n_kd, child_begin, children, leaf, kd_begin, kd_roots, kd_left, kd_right, kd_inner):
+        self.ctx = prim.ctx
+        self.lib = prim.lib
+        points = np.ascontiguousarray(np.asarray(points, dtype=np.float64))
+        n_kd = int(n_kd)
+        n_nodes = points.shape[0] - n_kd if points.ndim == 2 else 0
+        ints = [np.ascontiguousarray(np.asarray(a, dtype=np.int32)) for a in (child_begin, children, leaf, kd_begin, kd_roots, kd_left, kd_right, kd_inner)]
+        cb, ch, lf, kb, kr, kl, krt, ki = ints
+        if points.ndim != 2 or n_nodes < 1 or cb.shape != (n_nodes + 1,) or lf.shape != (n_nodes,) or kb.shape != (n_nodes + 1,) or \
+                any(a.shape != (n_kd,) for a in (kl, krt, ki)) or ch.shape != (n_nodes - 1,) or kr.shape != (int(kb[-1]),):
+            raise ValueError("points (n_kd + n_nodes, dim), child_begin / kd_begin (n_nodes + 1), children (n_nodes - 1), leaf (n_nodes), "
+                             "kd_roots (kd_begin[-1]), kd_left / kd_right / kd_inner (n_kd)")
+
+        def ptr(a):
+            return a.ctypes.data_as(C.c_void_p) if a.size else None
+        h = C.c_void_p()
+        _check(self.lib.mg_cluster_tree_create_kd(prim.handle, n_nodes, n_kd, points.shape[1], points.ctypes.data_as(C.c_void_p),
+                                                  *[ptr(a) for a in ints], C.byref(h)))
+        self.handle = h
+        self.n_nodes, self.n_kd, self.dim = n_nodes, n_kd, points.shape[1]
 
 
 def search_cluster_trees(prims, trees, csets, n_candidates, records_dev=None):

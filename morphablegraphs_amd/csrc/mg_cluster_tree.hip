@@ -17,12 +17,18 @@
 
 struct mg_cluster_tree {
     mg_context *ctx = nullptr;
+    int32_t kind = 0;                 // 0: a FeatureClusterTree (mg_cluster_tree_create), 1: a k-means/KD ClusterTree (_create_kd)
     int32_t n_nodes = 0, dim = 0, depth = 0, max_children = 0;
     int64_t n_rows = 0;
     double *d_means = nullptr;        // [n_nodes][dim]
     int32_t *d_child_begin = nullptr; // [n_nodes + 1]
     int32_t *d_children = nullptr;    // [n_nodes - 1] (at least one entry allocated)
     int64_t *d_first = nullptr;       // [n_nodes]
+    // kind 1 (d_means, d_first unused): the points table [n_kd + n_nodes][dim] (the KD nodes' points, then every cluster
+    // node's mean), the leaf flags, the KD roots per cluster node (CSR) and the KD nodes' left / right / inner
+    int32_t n_kd = 0, max_kd_children = 0, kd_depth = 0;
+    double *d_points = nullptr;
+    int32_t *d_leaf = nullptr, *d_kd_begin = nullptr, *d_kd_roots = nullptr, *d_kd_left = nullptr, *d_kd_right = nullptr, *d_kd_inner = nullptr;
 };
 
 // what a workgroup reads of its search (one table per launch, in device memory)
@@ -263,7 +269,8 @@ __global__ __launch_bounds__(MG_TREE_CHUNK *MG_TREE_WAVES) void mg_tree_search_k
 
 static void mg_tree_free(mg_cluster_tree *t) {
     if (!t) return;
-    for (void *q : {(void *)t->d_means, (void *)t->d_child_begin, (void *)t->d_children, (void *)t->d_first})
+    for (void *q : {(void *)t->d_means, (void *)t->d_child_begin, (void *)t->d_children, (void *)t->d_first, (void *)t->d_points, (void *)t->d_leaf,
+                    (void *)t->d_kd_begin, (void *)t->d_kd_roots, (void *)t->d_kd_left, (void *)t->d_kd_right, (void *)t->d_kd_inner})
         if (q) (void)hipFree(q);
     delete t;
 }
@@ -341,6 +348,9 @@ extern "C" void mg_cluster_tree_destroy(mg_cluster_tree *tree) {
     mg_tree_free(tree);
 }
 
+static int mg_kd_tree_search(int32_t n_searches, mg_primitive *const *prims, mg_cluster_tree *const *trees, const mg_constraint_set *const *csets,
+                             int32_t n_candidates, mg_tree_search_record *records_dev);
+
 extern "C" int mg_cluster_tree_search(int32_t n_searches, mg_primitive *const *prims, mg_cluster_tree *const *trees,
                                       const mg_constraint_set *const *csets, int32_t n_candidates, mg_tree_search_record *records_dev) {
     MG_TREE_REQUIRE(n_searches >= 0, "mg_cluster_tree_search: n_searches = %d", n_searches);
@@ -349,6 +359,12 @@ extern "C" int mg_cluster_tree_search(int32_t n_searches, mg_primitive *const *p
     MG_TREE_REQUIRE(n_candidates >= 1 && n_candidates <= MG_TREE_MAX_CANDIDATES, "mg_cluster_tree_search: n_candidates = %d outside [1, %d]",
                     n_candidates, MG_TREE_MAX_CANDIDATES);
     MG_TREE_REQUIRE(prims[0] != nullptr, "mg_cluster_tree_search: primitive 0 is NULL");
+    MG_TREE_REQUIRE(trees[0] != nullptr, "mg_cluster_tree_search: search 0: NULL primitive, tree or constraint set");
+    for (int32_t s = 1; s < n_searches; s++)
+        MG_TREE_REQUIRE(trees[s] == nullptr || trees[s]->kind == trees[0]->kind,
+                        "mg_cluster_tree_search: search %d: a %s tree in a call of %s trees (one kind per call)", s,
+                        trees[s]->kind ? "KD" : "feature", trees[0]->kind ? "KD" : "feature");
+    if (trees[0]->kind == 1) return mg_kd_tree_search(n_searches, prims, trees, csets, n_candidates, records_dev);
     mg_context *ctx = prims[0]->ctx;
     std::vector<mg_tree_search_desc> tab(n_searches);
     int Lmax = 1, ncmax = 1, maxch = 1, maxdepth = 0, wrows = 0;
@@ -418,5 +434,548 @@ extern "C" int mg_cluster_tree_search_host(int32_t n_searches, mg_primitive *con
     if (rc != MG_OK) return rc;
     MG_HIP_CHECK(hipMemcpyAsync(records, d_rec, (size_t)bytes, hipMemcpyDeviceToHost, ctx->stream));
     MG_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    return MG_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// The k-means / KD ClusterTree (reference space_partitioning/cluster_tree.py:117-149, cluster_tree_node.py:63-79,113-138,
+// kdtree.py:132-164,233-250): the same level loop, and after each level's k-means children every frontier leaf's
+// KD descents, in the same launch.  The descents of a level run side by side in groups of MG_KD_GROUP, one lane per
+// descent for its heap and two score slots per descent per step (right child, then left), so a step of the whole group
+// is one chunk of 64 scores.  Every value is scored from the points table with mg_score_kernel's statements.
+//
+// The heaps compare tuples as the reference's do:
+//   a node's children   (value, cluster_index, node)  cluster_index unique within the node: never raises
+//   new_candidates      (value, idx, node)            equal value and idx compare nodes: MG_TREE_TIE (TypeError)
+//   a leaf's KD results (value, point list)           lists compare lexicographically
+//   results             (value, c_idx, point list)
+//   a KD descent        (cost, depth)
+// ---------------------------------------------------------------------------------------------------------------
+#define MG_KD_GROUP 32
+
+struct mg_kd_search_desc {
+    mg_score_args a;
+    const double *points;
+    const int32_t *child_begin, *children, *leaf, *kd_begin, *kd_roots, *kd_left, *kd_right, *kd_inner;
+    int32_t dim, rows, n_kd, pad;
+};
+
+struct mg_hent {   // a heap entry: value, then up to three ints (what each heap compares and carries)
+    double v;
+    int32_t a, b, c, pad;
+};
+struct mg_kent {   // a KD descent's (cost, depth)
+    double v;
+    int32_t d, pad;
+};
+
+// heapq.heappush with the tuple comparison lt
+template <class T, class Lt>
+__device__ __forceinline__ void mg_heappush_t(T *h, int &len, int cap, const T &x, Lt lt, int &flags) {
+    if (len >= cap) { flags |= MG_TREE_OVERFLOW; return; }
+    int pos = len++;
+    while (pos > 0) {
+        const int parent = (pos - 1) >> 1;
+        if (lt(x, h[parent])) {
+            h[pos] = h[parent];
+            pos = parent;
+            continue;
+        }
+        break;
+    }
+    h[pos] = x;
+}
+
+// Python's `list < list` of two rows of the points table: the first position whose items differ decides
+__device__ bool mg_kd_rows_lt(const double *__restrict__ P, int dim, int r, int s) {
+    const double *x = P + (size_t)r * dim, *y = P + (size_t)s * dim;
+    for (int k = 0; k < dim; k++)
+        if (!(x[k] == y[k])) return x[k] < y[k];
+    return false;
+}
+
+// cval[j] = the objective of points row cid[j] for j < cnt (a row < 0 scores zeros, and its value is not used).  Called
+// by every thread of the workgroup; mg_tree_search_kernel's statements.
+__device__ void mg_kd_score(const mg_score_args &a, const double *Wm, const double *Bm, const double *__restrict__ P, int dim, const int32_t *cid,
+                            int cnt, double *xs, double *rs, double *cval, int tid, int lane, int wave) {
+    const int L = a.L, xs_stride = L + 1;
+    for (int e = tid; e < MG_TREE_CHUNK * L; e += MG_TREE_CHUNK * MG_TREE_WAVES) {
+        const int c = e / L, i = e - c * L;
+        xs[c * xs_stride + i] = (c < cnt && cid[c] >= 0) ? P[(size_t)cid[c] * dim + i] : 0.0;
+    }
+    __syncthreads();
+    const double *x = xs + lane * xs_stride;
+    for (int c = wave; c < a.n; c += MG_TREE_WAVES) {
+        auto channel = [&](int row) {
+            const double *wr = Wm + (size_t)row * L;
+            double acc = Bm[row];
+            for (int k = 0; k < L; k++) acc = fma(wr[k], x[k], acc);
+            return acc;
+        };
+        rs[c * MG_TREE_CHUNK + lane] = mg_constraint_residual(a, c, channel, 0);
+    }
+    __syncthreads();
+    if (tid < cnt) {
+        double err = 0.0;
+        for (int c = 0; c < a.n; c++) err += rs[c * MG_TREE_CHUNK + tid];
+        cval[tid] = err;
+    }
+    __syncthreads();
+}
+
+struct mg_kd_lds_plan {
+    int n_cand, cap_local, cap_level, cap_res, cap_leaf, kcap, kd_depth, wrows;
+    size_t off_w, off_rs, off_cval, off_lo, off_lv, off_re, off_lf, off_kh, off_resv, off_kev, off_cid, off_cci, off_clast, off_frn, off_froff,
+        off_dsoff, off_resrow, off_dfr, off_dlast, bytes;
+};
+
+static mg_kd_lds_plan mg_kd_plan(int Lmax, int ncmax, int n_cand, int max_children, int max_depth, int max_kd_children, int kd_depth, int wrows) {
+    mg_kd_lds_plan p;
+    p.wrows = wrows;
+    p.n_cand = n_cand;
+    p.cap_local = std::max(max_children, 1);
+    p.cap_level = n_cand * std::min(n_cand, p.cap_local);
+    p.cap_res = n_cand * (max_depth + 1);
+    p.cap_leaf = std::max(max_kd_children, 1);
+    p.kd_depth = kd_depth;
+    p.kcap = kd_depth + 1;
+    size_t o = (size_t)MG_TREE_CHUNK * (Lmax + 1) * 8;   // xs [64][L+1]
+    p.off_w = o;      o += (size_t)wrows * (Lmax + 1) * 8;
+    p.off_rs = o;     o += (size_t)std::max(ncmax, 1) * MG_TREE_CHUNK * 8;
+    p.off_cval = o;   o += MG_TREE_CHUNK * 8;
+    p.off_lo = o;     o += (size_t)p.cap_local * sizeof(mg_hent);
+    p.off_lv = o;     o += (size_t)p.cap_level * sizeof(mg_hent);
+    p.off_re = o;     o += (size_t)p.cap_res * sizeof(mg_hent);
+    p.off_lf = o;     o += (size_t)p.cap_leaf * sizeof(mg_hent);
+    p.off_kh = o;     o += (size_t)MG_KD_GROUP * p.kcap * sizeof(mg_kent);
+    p.off_resv = o;   o += MG_KD_GROUP * 8;
+    p.off_kev = o;    o += (size_t)MG_KD_GROUP * p.kcap * 4;
+    p.off_cid = o;    o += MG_TREE_CHUNK * 4;
+    p.off_cci = o;    o += MG_TREE_CHUNK * 4;
+    p.off_clast = o;  o += MG_TREE_CHUNK * 4;
+    p.off_frn = o;    o += (size_t)n_cand * 4;
+    p.off_froff = o;  o += (size_t)(n_cand + 1) * 4;
+    p.off_dsoff = o;  o += (size_t)(n_cand + 1) * 4;
+    p.off_resrow = o; o += MG_KD_GROUP * 4;
+    p.off_dfr = o;    o += MG_KD_GROUP * 4;
+    p.off_dlast = o;  o += MG_KD_GROUP * 4;
+    p.bytes = (o + 15) & ~(size_t)15;
+    return p;
+}
+
+__global__ __launch_bounds__(MG_TREE_CHUNK *MG_TREE_WAVES) void mg_kd_tree_search_kernel(const mg_kd_search_desc *__restrict__ tab, mg_kd_lds_plan lp,
+                                                                                         mg_tree_search_record *__restrict__ rec) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    __shared__ int s_fr_len, s_eff, s_total, s_ndesc, s_stop, s_kflags;
+    __shared__ long long s_evals;
+    const mg_kd_search_desc *d = tab + blockIdx.x;
+    const mg_score_args a = d->a;
+    const double *__restrict__ P = d->points;
+    const int32_t *__restrict__ cb = d->child_begin;
+    const int32_t *__restrict__ ch = d->children;
+    const int32_t *__restrict__ isleaf = d->leaf;
+    const int32_t *__restrict__ kb = d->kd_begin;
+    const int32_t *__restrict__ kr = d->kd_roots;
+    const int32_t *__restrict__ kl = d->kd_left;
+    const int32_t *__restrict__ krt = d->kd_right;
+    const int32_t *__restrict__ kin = d->kd_inner;
+    const int dim = d->dim, n_kd = d->n_kd, L = a.L, n_cand = lp.n_cand, kcap = lp.kcap;
+    double *xs = (double *)smem;
+    double *rs = (double *)(smem + lp.off_rs);
+    double *cval = (double *)(smem + lp.off_cval);
+    mg_hent *lo = (mg_hent *)(smem + lp.off_lo);
+    mg_hent *lv = (mg_hent *)(smem + lp.off_lv);
+    mg_hent *re = (mg_hent *)(smem + lp.off_re);
+    mg_hent *lf = (mg_hent *)(smem + lp.off_lf);
+    mg_kent *kh_all = (mg_kent *)(smem + lp.off_kh);
+    double *res_v = (double *)(smem + lp.off_resv);
+    int32_t *kev_all = (int32_t *)(smem + lp.off_kev);
+    int32_t *cid = (int32_t *)(smem + lp.off_cid);
+    int32_t *cci = (int32_t *)(smem + lp.off_cci);
+    int32_t *clast = (int32_t *)(smem + lp.off_clast);
+    int32_t *fr_n = (int32_t *)(smem + lp.off_frn);
+    int32_t *fr_off = (int32_t *)(smem + lp.off_froff);
+    int32_t *ds_off = (int32_t *)(smem + lp.off_dsoff);
+    int32_t *res_row = (int32_t *)(smem + lp.off_resrow);
+    int32_t *dfr = (int32_t *)(smem + lp.off_dfr);
+    int32_t *dlast = (int32_t *)(smem + lp.off_dlast);
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const double *Wm = a.W, *Bm = a.bias;
+    if (lp.wrows > 0 && d->rows > 0) {
+        double *wl = (double *)(smem + lp.off_w), *bl = wl + (size_t)lp.wrows * L;
+        for (int i = tid; i < d->rows * L; i += MG_TREE_CHUNK * MG_TREE_WAVES) wl[i] = a.W[i];
+        for (int i = tid; i < d->rows; i += MG_TREE_CHUNK * MG_TREE_WAVES) bl[i] = a.bias[i];
+        Wm = wl;
+        Bm = bl;
+    }
+    // (value, cluster_index, node): the indices differ within a node
+    auto lt_local = [](const mg_hent &x, const mg_hent &y) { return x.v == y.v ? x.a < y.a : x.v < y.v; };
+    // thread 0's heap state
+    int flags = 0, lv_len = 0, lo_len = 0, re_len = 0, lf_len = 0;
+    auto lt_level = [&flags](const mg_hent &x, const mg_hent &y) {   // (value, idx, node): equal idx compare the nodes
+        if (x.v == y.v) {
+            if (x.a == y.a) { flags |= MG_TREE_TIE; return false; }
+            return x.a < y.a;
+        }
+        return x.v < y.v;
+    };
+    auto lt_leaf = [&](const mg_hent &x, const mg_hent &y) { return x.v == y.v ? mg_kd_rows_lt(P, dim, x.b, y.b) : x.v < y.v; };
+    auto lt_res = [&](const mg_hent &x, const mg_hent &y) {   // (value, c_idx, point list)
+        if (x.v == y.v) return x.a == y.a ? mg_kd_rows_lt(P, dim, x.b, y.b) : x.a < y.a;
+        return x.v < y.v;
+    };
+    auto lt_kd = [](const mg_kent &x, const mg_kent &y) { return x.v == y.v ? x.d < y.d : x.v < y.v; };
+    if (tid == 0) {
+        s_fr_len = 1; fr_n[0] = 0;   // candidates = [(np.inf, 0, self.root)]
+        s_evals = 0; s_stop = 0; s_kflags = 0;
+    }
+    __syncthreads();
+    for (int level = 0; level <= MG_TREE_MAX_DEPTH + 1; level++) {
+        const int fr_len = s_fr_len;
+        if (fr_len == 0) break;
+        if (tid == 0) {
+            int tot = 0, nd = 0, eff = fr_len, stop = 0;
+            for (int f = 0; f < fr_len; f++) {
+                const int node = fr_n[f];
+                const int nk = kb[node + 1] - kb[node];
+                fr_off[f] = tot;
+                ds_off[f] = nd;
+                if (!isleaf[node]) {
+                    if (nk > 0) { stop = 1; eff = f; break; }   // KDTreeWrapper children have no .mean: AttributeError
+                    tot += cb[node + 1] - cb[node];
+                } else {
+                    nd += nk > 0 ? nk : 1;                       // a leaf without children scores its mean
+                }
+            }
+            fr_off[eff] = tot;
+            ds_off[eff] = nd;
+            s_eff = eff;
+            s_total = tot;
+            s_ndesc = stop ? 0 : nd;
+            s_stop = stop;
+            s_evals += tot;
+            lv_len = 0;
+            lo_len = 0;
+        }
+        __syncthreads();
+        const int eff = s_eff, tot = s_total, nd = s_ndesc;
+        // the k-means children of the frontier's inner nodes (find_best_cluster_candidates)
+        for (int c0 = 0; c0 < tot; c0 += MG_TREE_CHUNK) {
+            const int cnt = min(MG_TREE_CHUNK, tot - c0);
+            if (tid < cnt) {
+                const int e = c0 + tid;
+                int f = 0;
+                while (f + 1 < eff && fr_off[f + 1] <= e) f++;
+                const int node = fr_n[f];
+                cci[tid] = e - fr_off[f];
+                cid[tid] = n_kd + ch[cb[node] + (e - fr_off[f])];
+                clast[tid] = (e == fr_off[f + 1] - 1);
+            }
+            __syncthreads();
+            mg_kd_score(a, Wm, Bm, P, dim, cid, cnt, xs, rs, cval, tid, lane, wave);
+            if (tid == 0) {
+                for (int j = 0; j < cnt; j++) {
+                    mg_hent x;
+                    x.v = cval[j]; x.a = cci[j]; x.b = 0; x.c = cid[j] - n_kd; x.pad = 0;
+                    mg_heappush_t(lo, lo_len, lp.cap_local, x, lt_local, flags);
+                    if (clast[j]) {   // result_queue[:n_candidates] onto new_candidates as (value, idx, node)
+                        const int m = min(n_cand, lo_len);
+                        for (int i = 0; i < m; i++) {
+                            mg_hent y;   // (built field by field: a copy of the whole entry went through scratch)
+                            y.v = lo[i].v; y.a = i; y.b = lo[i].b; y.c = lo[i].c; y.pad = 0;
+                            mg_heappush_t(lv, lv_len, lp.cap_level, y, lt_level, flags);
+                        }
+                        lo_len = 0;
+                    }
+                }
+            }
+            __syncthreads();
+        }
+        if (s_stop) break;
+        // the leaves' KD descents (find_best_example), MG_KD_GROUP at a time
+        for (int g0 = 0; g0 < nd; g0 += MG_KD_GROUP) {
+            const int gcnt = min(MG_KD_GROUP, nd - g0);
+            const int slot = tid < MG_KD_GROUP ? tid : 0;   // (only lanes < gcnt touch their heap)
+            mg_kent *kh = kh_all + (size_t)slot * kcap;
+            int32_t *kev = kev_all + (size_t)slot * kcap;
+            int cur = -1, klen = 0, depth = 0, kflags = 0;
+            if (tid < gcnt) {
+                const int e = g0 + tid;
+                int f = 0;
+                while (f + 1 < eff && ds_off[f + 1] <= e) f++;
+                const int node = fr_n[f];
+                const int nk = kb[node + 1] - kb[node];
+                const int start = nk > 0 ? kr[kb[node] + (e - ds_off[f])] : n_kd + node;
+                cur = nk > 0 ? start : -1;
+                cid[tid] = start;
+                dfr[tid] = f;
+                dlast[tid] = (e == ds_off[f + 1] - 1);
+            }
+            __syncthreads();
+            mg_kd_score(a, Wm, Bm, P, dim, cid, gcnt, xs, rs, cval, tid, lane, wave);
+            if (tid < gcnt) {   // the KD root's point (or the leaf's mean) at depth 0
+                mg_kent x;
+                x.v = cval[tid]; x.d = 0; x.pad = 0;
+                mg_heappush_t(kh, klen, kcap, x, lt_kd, kflags);
+                kev[0] = cid[tid];
+            }
+            if (tid == 0) s_evals += gcnt;
+            __syncthreads();
+            for (int step = 0; step <= lp.kd_depth; step++) {
+                const bool active = tid < gcnt && cur >= 0 && kin[cur];
+                if (tid < MG_KD_GROUP) {   // slot 2t: the right child, slot 2t + 1: the left (the order the reference scores them)
+                    cid[2 * tid] = active ? krt[cur] : -1;
+                    cid[2 * tid + 1] = active ? kl[cur] : -1;
+                }
+                if (!__syncthreads_or(active)) break;
+                mg_kd_score(a, Wm, Bm, P, dim, cid, MG_TREE_CHUNK, xs, rs, cval, tid, lane, wave);
+                if (active) {   // _decide_direction_objective: left only if l < r
+                    const int r = cid[2 * tid], l = cid[2 * tid + 1];
+                    double cost = INFINITY;
+                    if (l >= 0 && r >= 0) {
+                        const double ld = cval[2 * tid + 1], rd = cval[2 * tid];
+                        if (ld < rd) { cur = l; cost = ld; } else { cur = r; cost = rd; }
+                    } else if (r >= 0) {
+                        cur = r; cost = cval[2 * tid];
+                    } else if (l >= 0) {
+                        cur = l; cost = cval[2 * tid + 1];
+                    } else {
+                        cur = -1;
+                    }
+                    depth++;
+                    if (cur >= 0 && depth < kcap) {
+                        mg_kent x;
+                        x.v = cost; x.d = depth; x.pad = 0;
+                        mg_heappush_t(kh, klen, kcap, x, lt_kd, kflags);
+                        kev[depth] = cur;
+                    } else if (cur >= 0) {
+                        kflags |= MG_TREE_OVERFLOW;
+                        cur = -1;
+                    }
+                }
+                if (tid == 0) {
+                    int n = 0;
+                    for (int j = 0; j < MG_TREE_CHUNK; j++) n += cid[j] >= 0;
+                    s_evals += n;
+                }
+                __syncthreads();
+            }
+            if (tid < gcnt) {   // result_queue[0] with that depth's point
+                res_v[tid] = kh[0].v;
+                res_row[tid] = kev[kh[0].d];
+                if (kflags) atomicOr(&s_kflags, kflags);
+            }
+            __syncthreads();
+            if (tid == 0) {
+                for (int j = 0; j < gcnt; j++) {
+                    mg_hent x;
+                    x.v = res_v[j]; x.a = 0; x.b = res_row[j]; x.c = 0; x.pad = 0;
+                    mg_heappush_t(lf, lf_len, lp.cap_leaf, x, lt_leaf, flags);
+                    if (dlast[j]) {   // heappop(result_queue) onto results as (v, c_idx, sample)
+                        mg_hent y;
+                        y.v = lf[0].v; y.a = dfr[j]; y.b = lf[0].b; y.c = fr_n[dfr[j]]; y.pad = 0;
+                        mg_heappush_t(re, re_len, lp.cap_res, y, lt_res, flags);
+                        lf_len = 0;
+                    }
+                }
+            }
+            __syncthreads();
+        }
+        if (tid == 0) {   // candidates = new_candidates[:n_candidates]
+            const int m = min(n_cand, lv_len);
+            for (int i = 0; i < m; i++) fr_n[i] = lv[i].c;
+            s_fr_len = m;
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        mg_tree_search_record r;
+        flags |= s_kflags;
+        if (s_stop) {
+            if (!(flags & MG_TREE_TIE)) flags |= MG_TREE_NO_MEAN;   // whichever the reference raised first
+            r.leaf = -1; r.value = INFINITY; r.row = -1;
+        } else {
+            if (s_fr_len != 0) flags |= MG_TREE_OVERFLOW;
+            if (re_len == 0) {
+                flags |= MG_TREE_NO_RESULT;
+                r.leaf = 0; r.value = INFINITY; r.row = n_kd;   // self.root.mean
+            } else {
+                r.leaf = re[0].c; r.value = re[0].v; r.row = re[0].b;
+            }
+        }
+        r.flags = flags;
+        r.evaluations = s_evals;
+        rec[blockIdx.x] = r;
+    }
+}
+
+// one parent per node, reachable from `roots` (BFS by levels), at most max_depth edges deep: MG_OK, or the error set
+static int mg_tree_check_forest(const char *fn, const char *what, int32_t n, const std::vector<int32_t> &roots,
+                                const std::vector<std::vector<int32_t>> &kids, int max_depth, int *depth_out) {
+    std::vector<char> seen(n, 0);
+    std::vector<int32_t> level, next;
+    for (int32_t r : roots) {
+        MG_TREE_REQUIRE(r >= 0 && r < n, "%s: %s root %d out of range [0, %d)", fn, what, r, n);
+        MG_TREE_REQUIRE(!seen[r], "%s: %s node %d has more than one parent", fn, what, r);
+        seen[r] = 1;
+        level.push_back(r);
+    }
+    int64_t reached = (int64_t)level.size();
+    int depth = 0;
+    while (true) {
+        next.clear();
+        for (int32_t v : level)
+            for (int32_t c : kids[v]) {
+                MG_TREE_REQUIRE(c >= 0 && c < n && !seen[c], "%s: %s node %d out of range or with more than one parent", fn, what, c);
+                seen[c] = 1;
+                next.push_back(c);
+            }
+        if (next.empty()) break;
+        depth++;
+        reached += (int64_t)next.size();
+        MG_TREE_REQUIRE(depth <= max_depth, "%s: %s depth beyond %d or a cycle", fn, what, max_depth);
+        level.swap(next);
+    }
+    MG_TREE_REQUIRE(reached == n, "%s: %lld of %d %s nodes reachable (a cycle)", fn, (long long)reached, n, what);
+    *depth_out = depth;
+    return MG_OK;
+}
+
+extern "C" int mg_cluster_tree_create_kd(mg_primitive *prim, int32_t n_nodes, int32_t n_kd, int32_t dim, const double *points, const int32_t *child_begin,
+                                         const int32_t *children, const int32_t *leaf, const int32_t *kd_begin, const int32_t *kd_roots,
+                                         const int32_t *kd_left, const int32_t *kd_right, const int32_t *kd_inner, mg_cluster_tree **tree) {
+    const char *fn = "mg_cluster_tree_create_kd";
+    MG_TREE_REQUIRE(tree != nullptr, "%s: tree is NULL", fn);
+    *tree = nullptr;
+    MG_TREE_REQUIRE(prim && points && child_begin && leaf && kd_begin, "%s: NULL argument", fn);
+    MG_TREE_REQUIRE(n_nodes >= 1 && n_kd >= 0, "%s: n_nodes = %d, n_kd = %d", fn, n_nodes, n_kd);
+    MG_TREE_REQUIRE(dim >= prim->L, "%s: point width %d < the primitive's %d spatial components", fn, dim, prim->L);
+    MG_TREE_REQUIRE(n_kd == 0 || (kd_left && kd_right && kd_inner), "%s: NULL KD table", fn);
+    const int64_t n_edges = (int64_t)n_nodes - 1;
+    MG_TREE_REQUIRE(child_begin[0] == 0 && child_begin[n_nodes] == n_edges,
+                    "%s: child_begin must run from 0 to n_nodes - 1 = %lld (every node but the root has one parent)", fn, (long long)n_edges);
+    MG_TREE_REQUIRE(n_edges == 0 || children != nullptr, "%s: children is NULL", fn);
+    const int32_t n_roots = kd_begin[n_nodes];
+    MG_TREE_REQUIRE(kd_begin[0] == 0 && n_roots >= 0 && n_roots <= n_kd, "%s: kd_begin must run from 0 to at most n_kd", fn);
+    MG_TREE_REQUIRE(n_roots == 0 || kd_roots != nullptr, "%s: kd_roots is NULL", fn);
+    std::vector<std::vector<int32_t>> kids(n_nodes), kkids(n_kd);
+    std::vector<int32_t> kroots;
+    int max_children = 0, max_kd = 0;
+    for (int32_t i = 0; i < n_nodes; i++) {
+        const int32_t b = child_begin[i], e = child_begin[i + 1], kb0 = kd_begin[i], ke = kd_begin[i + 1];
+        MG_TREE_REQUIRE(b <= e && kb0 <= ke, "%s: child_begin or kd_begin decreases at node %d", fn, i);
+        MG_TREE_REQUIRE(e - b <= MG_TREE_MAX_CHILDREN && ke - kb0 <= MG_TREE_MAX_CHILDREN, "%s: node %d has more than %d children", fn, i, MG_TREE_MAX_CHILDREN);
+        MG_TREE_REQUIRE(e == b || ke == kb0, "%s: node %d mixes cluster-node and KD-tree children", fn, i);
+        MG_TREE_REQUIRE(!(leaf[i] && e > b), "%s: leaf %d has cluster-node children", fn, i);
+        max_children = std::max(max_children, e - b);
+        max_kd = std::max(max_kd, ke - kb0);
+        for (int32_t k = b; k < e; k++) {
+            MG_TREE_REQUIRE(children[k] >= 1 && children[k] < n_nodes, "%s: child %d of node %d out of range (the root is nobody's child)", fn, children[k], i);
+            kids[i].push_back(children[k]);
+        }
+        for (int32_t k = kb0; k < ke; k++) kroots.push_back(kd_roots[k]);
+    }
+    int depth = 0, kd_depth = 0;
+    int rc = mg_tree_check_forest(fn, "cluster", n_nodes, std::vector<int32_t>(1, 0), kids, MG_TREE_MAX_DEPTH, &depth);
+    if (rc != MG_OK) return rc;
+    for (int32_t k = 0; k < n_kd; k++) {
+        MG_TREE_REQUIRE(kd_left[k] >= -1 && kd_left[k] < n_kd && kd_right[k] >= -1 && kd_right[k] < n_kd, "%s: KD node %d: a child out of range", fn, k);
+        if (kd_left[k] >= 0) kkids[k].push_back(kd_left[k]);
+        if (kd_right[k] >= 0) kkids[k].push_back(kd_right[k]);
+    }
+    rc = mg_tree_check_forest(fn, "KD", n_kd, kroots, kkids, MG_KD_MAX_DEPTH, &kd_depth);
+    if (rc != MG_OK) return rc;
+    mg_context *ctx = prim->ctx;
+    MG_HIP_CHECK(hipSetDevice(ctx->device));
+    mg_cluster_tree *t = new mg_cluster_tree;
+    t->ctx = ctx; t->kind = 1; t->n_nodes = n_nodes; t->dim = dim; t->depth = depth; t->max_children = max_children; t->n_rows = (int64_t)n_kd + n_nodes;
+    t->n_kd = n_kd; t->max_kd_children = max_kd; t->kd_depth = kd_depth;
+    const size_t pb = (size_t)t->n_rows * dim * 8, nb = (size_t)(n_nodes + 1) * 4, chb = (size_t)std::max<int64_t>(n_edges, 1) * 4;
+    const size_t rb = (size_t)std::max(n_roots, 1) * 4, kb = (size_t)std::max(n_kd, 1) * 4;
+    hipError_t e = hipMalloc(&t->d_points, pb);
+    if (e == hipSuccess) e = hipMalloc(&t->d_child_begin, nb);
+    if (e == hipSuccess) e = hipMalloc(&t->d_children, chb);
+    if (e == hipSuccess) e = hipMalloc(&t->d_leaf, nb);
+    if (e == hipSuccess) e = hipMalloc(&t->d_kd_begin, nb);
+    if (e == hipSuccess) e = hipMalloc(&t->d_kd_roots, rb);
+    if (e == hipSuccess) e = hipMalloc(&t->d_kd_left, kb);
+    if (e == hipSuccess) e = hipMalloc(&t->d_kd_right, kb);
+    if (e == hipSuccess) e = hipMalloc(&t->d_kd_inner, kb);
+    if (e == hipSuccess) e = hipMemcpy(t->d_points, points, pb, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(t->d_child_begin, child_begin, nb, hipMemcpyHostToDevice);
+    if (e == hipSuccess && n_edges > 0) e = hipMemcpy(t->d_children, children, (size_t)n_edges * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(t->d_leaf, leaf, (size_t)n_nodes * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(t->d_kd_begin, kd_begin, nb, hipMemcpyHostToDevice);
+    if (e == hipSuccess && n_roots > 0) e = hipMemcpy(t->d_kd_roots, kd_roots, (size_t)n_roots * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess && n_kd > 0) e = hipMemcpy(t->d_kd_left, kd_left, (size_t)n_kd * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess && n_kd > 0) e = hipMemcpy(t->d_kd_right, kd_right, (size_t)n_kd * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess && n_kd > 0) e = hipMemcpy(t->d_kd_inner, kd_inner, (size_t)n_kd * 4, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        mg_tree_free(t);
+        return mg_hip_fail(e, "mg_cluster_tree_create_kd: upload");
+    }
+    *tree = t;
+    return MG_OK;
+}
+
+static int mg_kd_tree_search(int32_t n_searches, mg_primitive *const *prims, mg_cluster_tree *const *trees, const mg_constraint_set *const *csets,
+                             int32_t n_candidates, mg_tree_search_record *records_dev) {
+    mg_context *ctx = prims[0]->ctx;
+    std::vector<mg_kd_search_desc> tab(n_searches);
+    int Lmax = 1, ncmax = 1, maxch = 1, maxdepth = 0, maxkd = 1, kd_depth = 0, wrows = 0;
+    bool rows_known = true;
+    for (int32_t s = 0; s < n_searches; s++) {
+        mg_primitive *p = prims[s];
+        const mg_cluster_tree *t = trees[s];
+        const mg_constraint_set *cs = csets[s];
+        MG_TREE_REQUIRE(p && t && cs, "mg_cluster_tree_search: search %d: NULL primitive, tree or constraint set", s);
+        MG_TREE_REQUIRE(p->ctx == ctx, "mg_cluster_tree_search: search %d: the primitives live in different contexts", s);
+        MG_TREE_REQUIRE(t->ctx == ctx, "mg_cluster_tree_search: search %d: the tree was uploaded to another context", s);
+        MG_TREE_REQUIRE(cs->prim == p, "mg_cluster_tree_search: search %d: the constraint set belongs to another primitive", s);
+        MG_TREE_REQUIRE(t->dim >= p->L, "mg_cluster_tree_search: search %d: tree points of width %d < %d spatial components", s, t->dim, p->L);
+        mg_kd_search_desc &d = tab[s];
+        memset(&d, 0, sizeof(d));
+        d.a.W = cs->d_W; d.a.bias = cs->d_bias; d.a.par = cs->d_par; d.a.woff = cs->d_woff; d.a.chain = cs->d_chain; d.a.choff = cs->d_choff;
+        d.a.pose = cs->d_pose; d.a.align = cs->d_align; d.a.align_cand = nullptr; d.a.lat = nullptr; d.a.out = nullptr; d.a.res = nullptr;
+        d.a.B = 0; d.a.ld = 0; d.a.n = cs->n; d.a.nch = cs->nch; d.a.L = p->L;
+        d.points = t->d_points; d.child_begin = t->d_child_begin; d.children = t->d_children; d.leaf = t->d_leaf;
+        d.kd_begin = t->d_kd_begin; d.kd_roots = t->d_kd_roots; d.kd_left = t->d_kd_left; d.kd_right = t->d_kd_right; d.kd_inner = t->d_kd_inner;
+        d.dim = t->dim; d.rows = cs->rows; d.n_kd = t->n_kd;
+        rows_known = rows_known && cs->rows > 0;
+        wrows = std::max(wrows, (int)cs->rows);
+        Lmax = std::max(Lmax, (int)p->L);
+        ncmax = std::max(ncmax, (int)cs->n);
+        maxch = std::max(maxch, (int)t->max_children);
+        maxdepth = std::max(maxdepth, (int)t->depth);
+        maxkd = std::max(maxkd, (int)t->max_kd_children);
+        kd_depth = std::max(kd_depth, (int)t->kd_depth);
+    }
+    mg_kd_lds_plan lp = mg_kd_plan(Lmax, ncmax, n_candidates, maxch, maxdepth, maxkd, kd_depth, rows_known ? wrows : 0);
+    if (lp.bytes > 160 * 1024 && lp.wrows > 0) lp = mg_kd_plan(Lmax, ncmax, n_candidates, maxch, maxdepth, maxkd, kd_depth, 0);
+    if (lp.bytes > 160 * 1024) {
+        mg_set_error("mg_cluster_tree_search: %zu bytes of LDS (latents %d, constraints %d, candidates %d, children %d, depth %d, KD depth %d) beyond 160 KiB",
+                     lp.bytes, Lmax, ncmax, n_candidates, maxch, maxdepth, kd_depth);
+        return MG_ERR_UNSUPPORTED;
+    }
+    MG_HIP_CHECK(hipSetDevice(ctx->device));
+    const size_t tab_bytes = tab.size() * sizeof(mg_kd_search_desc);
+    if (!ctx->tree_tab_dev || ctx->tree_tab_host.size() != tab_bytes || memcmp(ctx->tree_tab_host.data(), tab.data(), tab_bytes) != 0) {
+        MG_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        if (ctx->tree_tab_cap < tab_bytes) {
+            if (ctx->tree_tab_dev) { (void)hipFree(ctx->tree_tab_dev); ctx->tree_tab_dev = nullptr; ctx->tree_tab_cap = 0; }
+            MG_HIP_CHECK(hipMalloc(&ctx->tree_tab_dev, tab_bytes));
+            ctx->tree_tab_cap = tab_bytes;
+        }
+        MG_HIP_CHECK(hipMemcpy(ctx->tree_tab_dev, tab.data(), tab_bytes, hipMemcpyHostToDevice));
+        ctx->tree_tab_host.assign((const unsigned char *)tab.data(), (const unsigned char *)tab.data() + tab_bytes);
+    }
+    if (lp.bytes > 64 * 1024)
+        MG_HIP_CHECK(hipFuncSetAttribute((const void *)mg_kd_tree_search_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    mg_prof_begin(ctx, 11);
+    hipLaunchKernelGGL(mg_kd_tree_search_kernel, dim3(n_searches), dim3(MG_TREE_CHUNK * MG_TREE_WAVES), lp.bytes, ctx->stream,
+                       (const mg_kd_search_desc *)ctx->tree_tab_dev, lp, records_dev);
+    mg_prof_end(ctx, 11);
+    MG_HIP_CHECK(hipGetLastError());
     return MG_OK;
 }

@@ -45,13 +45,20 @@ def _primitive_key(motion_primitive_name):
     return key, stem
 
 
-def read_graph_zip(path):
+def read_graph_zip(path, pickle_objects=False):
     """ZipReader.get_graph_data (zip_io.py:65-95): {"subgraphs": {action: {"name", "info"?, "nodes": {primitive:
-    {"name", "mm", "stats"?, "space_partition_json"?}}}}, "transitions"?, "startNode"?, "skeleton"?, ...}."""
+    {"name", "mm", "stats"?, "space_partition_json"?, "space_partition_pickle"?}}}}, "transitions"?, "startNode"?, "skeleton"?, ...}.
+
+    With pickle_objects the pickled cluster trees are read as ZipReader reads them (zip_io.py:204-230): for formatVersion < 4
+    or "usePickle", '<primitive>_cluster_tree.pck' under elementary_action_models/<dir>/ (formatVersion >= 2 or usePickle)
+    or <dir>/ (below 2), through cluster_tree_pickle's allow-listed Unpickler, as "space_partition_pickle" (a HipClusterTree
+    or HipFeatureClusterTree with the means' width unchecked).  ZipReader unpickles by default; here nothing is unpickled
+    unless asked, and without the flag the result is what it always was."""
     with zipfile.ZipFile(path, "r") as z:
         names = z.namelist()
         data = json.loads(z.read(GRAPH_DEFINITION_FILE).decode("utf-8")) if GRAPH_DEFINITION_FILE in names else {}
         version = float(data.get("formatVersion", 1.0))
+        use_pickle = bool(data.get("usePickle", False))
         if SKELETON_JSON_FILE in names:
             data[SKELETON_JSON_KEY] = json.loads(z.read(SKELETON_JSON_FILE).decode("utf-8"))
         subgraphs = {}
@@ -84,7 +91,13 @@ def read_graph_zip(path):
                     node["stats"] = json.loads(z.read(stats).decode("utf-8"))
                     break
             tree = prefix + motion_primitive_name + "_cluster_tree.json"
-            if version >= 4.0 and tree in names:
+            if pickle_objects and (version < 4.0 or use_pickle):
+                from .cluster_tree_pickle import load_cluster_tree_pickle
+                where = ELEMENTARY_ACTION_DIRECTORY + "/" + structure_key + "/" if version >= 2.0 or use_pickle else structure_key + "/"
+                pck = where + motion_primitive_name + "_cluster_tree.pck"
+                if pck in names:
+                    node["space_partition_pickle"] = load_cluster_tree_pickle(z.read(pck))
+            elif version >= 4.0 and tree in names:
                 node["space_partition_json"] = json.loads(z.read(tree).decode("utf-8"))
             group["nodes"][key] = node
         data["subgraphs"] = subgraphs

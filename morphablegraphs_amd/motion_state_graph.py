@@ -14,6 +14,9 @@ from . import candidate_scoring as _cs
 from . import _capi
 from .candidate_scoring import constraints_to_device_form, evaluate_samples_using_constraints
 from .cluster_tree import HipFeatureClusterTree, search_on_device
+from .kd_cluster_tree import HipClusterTree
+
+_SEARCH_TREES = (HipFeatureClusterTree, HipClusterTree)   # the trees a search descends (the others hold samples only)
 from .frame_constraints import is_frame_constraint
 from .motion_primitive import HipMotionPrimitive, get_context
 from .motion_primitive_wrapper import HipMotionPrimitiveModelWrapper
@@ -126,7 +129,7 @@ class HipMotionStateGraphNode(HipMotionPrimitiveModelWrapper):
         return cached_constraint_set(self.motion_primitive._prim, form, skeleton, alignment_from_prev_frames(prev_frames, constraints, skeleton))
 
     def _search_tree(self):
-        if not isinstance(self.cluster_tree, HipFeatureClusterTree):
+        if not isinstance(self.cluster_tree, _SEARCH_TREES):
             raise NotImplementedError("node %r has no cluster tree to descend (only stored samples)" % (self.name,))
         return self.cluster_tree
 
@@ -153,7 +156,8 @@ class HipMotionStateGraphNode(HipMotionPrimitiveModelWrapper):
         form = constraints_to_device_form(clist)
         alignment = alignment_from_prev_frames(prev_frames, constraints, skeleton)
         L = self.get_n_spatial_components()
-        value, row, _, n_eval = tree.descend(lambda ids: errors_of_samples(self.motion_primitive._prim, form, skeleton, alignment, tree.means[ids, :L]),
+        table = tree.points if isinstance(tree, HipClusterTree) else tree.means   # what descend's ids index
+        value, row, _, n_eval = tree.descend(lambda ids: errors_of_samples(self.motion_primitive._prim, form, skeleton, alignment, table[ids, :L]),
                                              n_candidates)
         if hasattr(constraints, "evaluations"):
             constraints.evaluations += n_eval
@@ -201,9 +205,10 @@ class HipMotionStateGraph(object):
         self.start_node = None
         self.action_definitions = {}
 
-    def load_from_zip(self, path, recalculate_stats=False):
+    def load_from_zip(self, path, recalculate_stats=False, pickle_objects=False):
+        """pickle_objects: read the pickled cluster trees of formatVersion < 4 or usePickle zips (model_io.read_graph_zip)."""
         from .model_io import read_graph_zip
-        return self.build_from_graph_data(read_graph_zip(path), recalculate_stats)
+        return self.build_from_graph_data(read_graph_zip(path, pickle_objects), recalculate_stats)
 
     def build_from_graph_data(self, graph_data, recalculate_stats=False):
         # every primitive of the graph lives in one device arena (a few 64 MiB blocks instead of ~20 allocations each)
@@ -239,6 +244,9 @@ class HipMotionStateGraph(object):
                     continue   # static primitives carry no statistical model (motion_primitive_wrapper.py:61-66)
                 node = HipMotionStateGraphNode(group, context=self.ctx)
                 node.init_from_dict(action_data["name"], desc)
+                if "space_partition_pickle" in desc:   # motion_state_graph_node.py:96-97
+                    node.cluster_tree = desc["space_partition_pickle"]
+                    node.cluster_tree.validate(node.get_n_spatial_components())
                 if "space_partition_json" in desc:
                     tree_data = desc["space_partition_json"]
                     if isinstance(tree_data.get("root"), dict) and len(tree_data["root"]) > 0:
@@ -300,7 +308,7 @@ class HipMotionStateGraph(object):
         for key in options:
             node = self.nodes[key]
             cons = constraints_per_option[key]
-            if use_cluster_trees and isinstance(node.cluster_tree, HipFeatureClusterTree):
+            if use_cluster_trees and isinstance(node.cluster_tree, _SEARCH_TREES):
                 cset = node._tree_search_set(cons, prev_frames, skeleton)
                 if cset is not None:
                     searches.append((key, (node.cluster_tree, node.motion_primitive._prim, cset)))
@@ -308,9 +316,12 @@ class HipMotionStateGraph(object):
                 results[key] = node.search_best_sample_batched(cons, 1, prev_frames, skeleton)[::-1]
                 continue
             general.append(key)
-        if searches:
-            records = search_on_device([s for _, s in searches], 1)
-            for (key, (tree, _, _)), rec in zip(searches, records):
+        for kind in _SEARCH_TREES:   # one launch per tree kind
+            group = [s for s in searches if isinstance(s[1][0], kind)]
+            if not group:
+                continue
+            records = search_on_device([s for _, s in group], 1)
+            for (key, (tree, _, _)), rec in zip(group, records):
                 cons = constraints_per_option[key]
                 if hasattr(cons, "evaluations"):
                     cons.evaluations += int(rec["evaluations"])
@@ -327,7 +338,7 @@ class HipMotionStateGraph(object):
 
     def close(self):
         for node in self.nodes.values():
-            if isinstance(node.cluster_tree, HipFeatureClusterTree):
+            if isinstance(node.cluster_tree, _SEARCH_TREES):
                 node.cluster_tree.close()
             prim = getattr(node.motion_primitive, "_prim", None)
             if prim is not None:

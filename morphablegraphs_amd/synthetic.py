@@ -243,3 +243,107 @@ def make_skeleton(n_animated=19):
     if n_animated <= 19:                                                  # the toes are the first to go
         animated = [n for n in animated if not n.endswith("ToeBase")]
     return joints, animated[:n_animated]
+
+
+# ---- the reference's k-means / KD ClusterTree (space_partitioning/cluster_tree_node_builder.py, kdtree.py) ----------
+# Objects of classes named as the reference's, so that write_reference_pickle writes what the reference's own pickles name.
+_SP = "morphablegraphs.space_partitioning."
+
+
+def _reference_class(module, name):
+    return type(name, (object,), {"__module__": _SP + module, "__qualname__": name})
+
+
+RefClusterTree = _reference_class("cluster_tree", "ClusterTree")
+RefClusterTreeNode = _reference_class("cluster_tree_node", "ClusterTreeNode")
+RefKDTreeWrapper = _reference_class("kdtree_wrapper_node", "KDTreeWrapper")
+RefKDTree = _reference_class("kdtree", "KDTree")
+RefNode = _reference_class("kdtree", "Node")
+RefFeatureClusterTree = _reference_class("feature_cluster_tree", "FeatureClusterTree")
+
+
+def _obj(cls, **attrs):
+    o = cls.__new__(cls)
+    o.__dict__.update(attrs)
+    return o
+
+
+def _kd_node(points, dim, depth=0):
+    """kdtree.Node: sort by the axis depth % dim (stable), the median as the point, the halves below it."""
+    if len(points) > 1:
+        axis = depth % dim
+        points.sort(key=lambda p: p[axis])
+        median = len(points) // 2
+        left, right = points[:median], points[median + 1:]
+        return _obj(RefNode, index=depth, type="inner", point=points[median],
+                    left=_kd_node(left, dim, depth + 1) if left else None, right=_kd_node(right, dim, depth + 1) if right else None)
+    return _obj(RefNode, index=depth, type="leaf", point=points[0], left=None, right=None)
+
+
+def _kd_wrapper(data, indices, dim):
+    rows = data[indices].tolist()
+    return _obj(RefKDTreeWrapper, id="kd", dim=dim, type="kdtree", kdtree=_obj(RefKDTree, data=rows, root=_kd_node(rows, dim), global_bb=None))
+
+
+def make_kd_cluster_tree(samples, n_subdivisions=4, max_level=4, use_kd_tree=True, seed=0, dim=None):
+    """A ClusterTree as ClusterTreeNodeBuilder.construct_from_data builds it (cluster_tree_node_builder.py:96-163), with this
+    module's k-means in place of sklearn's.  The root is built from explicit indices: the reference passes None, and for a
+    root that is itself a leaf (n_subdivisions = 1) data[None] would wrap all rows into a single KD point."""
+    data = np.asarray(samples, dtype=np.float64)
+    dim = min(data.shape[1], dim or data.shape[1])
+    rng = np.random.default_rng(seed)
+
+    def node_type(depth):
+        return "leaf" if depth >= max_level - 1 else ("root" if depth == 0 else "inner")
+
+    def build(indices, depth):
+        clusters, n = [], len(indices)
+        if not use_kd_tree and n == 1:
+            mean, is_leaf = data[indices[0]], True
+        elif n > n_subdivisions and n_subdivisions > 1:
+            is_leaf, mean = False, data[indices].mean(axis=0)
+            labels = _kmeans(data[indices, :dim], n_subdivisions, rng)
+            groups = [[indices[i] for i in range(n) if labels[i] == j] for j in range(n_subdivisions)]
+            for g in groups:
+                if g:
+                    clusters.append(build(g, depth + 1) if depth < max_level or not use_kd_tree else _kd_wrapper(data, g, dim))
+        else:
+            is_leaf, mean = use_kd_tree, data[indices].mean(axis=0)
+            clusters = [_kd_wrapper(data, indices, dim)] if use_kd_tree else [build([i], depth + 1) for i in indices]
+        return _obj(RefClusterTreeNode, id="n", clusters=clusters, mean=mean, leaf=is_leaf, type=node_type(depth), depth=depth, indices=None)
+    root = build(list(range(len(data))), 0)
+    return _obj(RefClusterTree, n_subdivisions=max(n_subdivisions, 1), max_level=max(max_level, 1), dim=dim, root=root, data=data,
+                store_indices=False, use_kd_tree=use_kd_tree)
+
+
+def make_pickled_feature_cluster_tree(samples, n_subdivisions=4, seed=0):
+    """make_feature_cluster_tree's tree as FeatureClusterTree objects (the attributes the reference pickles: data, _features,
+    _indices, _children, _options, _mean, _n_subdivisions), and the JSON layout of the same tree."""
+    tree = make_feature_cluster_tree(samples, n_subdivisions, seed)
+    data = np.asarray(tree["data"], dtype=np.float64)
+
+    def node(d):
+        return _obj(RefFeatureClusterTree, data=data, _features=data, _options=tree["options"], _n_subdivisions=n_subdivisions,
+                    _indices=d["indices"], _mean=np.asarray(d["mean"]), _children=[node(c) for c in d["children"]])
+    return node(tree["root"]), tree
+
+
+def write_reference_pickle(obj, protocol=2):
+    """pickle.dumps of objects made above, under the reference's module names (registered in sys.modules while it runs)."""
+    import pickle
+    import sys
+    import types
+    added = []
+    for cls in (RefClusterTree, RefClusterTreeNode, RefKDTreeWrapper, RefKDTree, RefNode, RefFeatureClusterTree):
+        parts = cls.__module__.split(".")
+        for i in range(1, len(parts) + 1):
+            name = ".".join(parts[:i])
+            if name not in sys.modules:
+                sys.modules[name] = types.ModuleType(name)
+                added.append(name)
+        setattr(sys.modules[cls.__module__], cls.__qualname__, cls)
+    try:
+        return pickle.dumps(obj, protocol)
+    finally:
+        for name in added:
+            del sys.modules[name]

@@ -1,0 +1,345 @@
+"""The reference's k-means / KD ClusterTree search (space_partitioning/cluster_tree.py:117-149) in one launch
+(mg_cluster_tree_search on mg_cluster_tree_create_kd trees): bit for bit against the host descent that scores each level and
+each KD step with mg_score_constraints, against the reference's search restated with the oracle's objective, batched, through
+the sampling generator and the planner's option evaluation on a graph whose trees come from pickles, and its misuse."""
+import json
+import os
+import zipfile
+
+import numpy as np
+import pytest
+
+from morphablegraphs_amd import _capi, synthetic
+from morphablegraphs_amd.cluster_tree import HipFeatureClusterTree, search_on_device
+from morphablegraphs_amd.kd_cluster_tree import HipClusterTree
+from morphablegraphs_amd.motion_primitive import get_context
+from morphablegraphs_amd.motion_primitive_generator import HipMotionPrimitiveGenerator
+from morphablegraphs_amd.motion_state_graph import HipMotionStateGraph
+from oracle import mg_oracle as orc
+
+pytestmark = pytest.mark.gpu
+
+
+def _bits(x):
+    return np.asarray(x, dtype=np.float64).view(np.uint64)
+
+
+class _Constraints(object):
+    def __init__(self, cons, name="a"):
+        self.constraints, self.min_error, self.evaluations = list(cons), None, 0
+        self.motion_primitive_name, self.use_local_optimization = name, False
+
+
+def _host(tree, prim, cset, n):
+    L = prim.n_components
+    return tree.descend_rows(lambda rows: prim.score_constraints(cset, np.ascontiguousarray(tree.points[rows, :L])), n)
+
+
+@pytest.fixture(scope="module")
+def walk_trees():
+    data = synthetic.make_walk_primitive(seed=0)
+    samples = np.random.default_rng(11).standard_normal((10000, 40))
+    deep = HipClusterTree.from_reference(synthetic.make_kd_cluster_tree(samples, 4, 16, seed=3), 40)
+    pure = HipClusterTree.from_reference(synthetic.make_kd_cluster_tree(samples, 1, seed=3), 40)
+    return data, {"deep": deep, "pure": pure}
+
+
+def test_one_launch_equals_the_host_descent_bit_for_bit(walk_trees):
+    data, trees = walk_trees
+    assert trees["pure"].n_nodes == 1 and trees["pure"].kd_depth >= 13 and trees["deep"].depth >= 6
+    ctx = get_context(0)
+    prim = _capi.Primitive(ctx, data)
+    joints, animated = synthetic.make_skeleton()
+    sk = _capi.Skeleton(joints, animated)
+    cons = [{"type": "position", "t": 155.0, "weight": 1.0, "target": [60.0, None, -40.0]},
+            {"type": "direction", "t": 155.0, "weight": 0.3, "target": [0.2, 1.0]},
+            {"type": "joint_position", "joint": "LeftHand", "t": 80.0, "weight": 0.5, "target": [30.0, 100.0, -20.0]}]
+    prev = np.zeros(79)
+    prev[:3] = [120.0, 90.0, -340.0]
+    prev[3::4] = 1.0
+    prev[3:7] = [0.3, 0.1, 0.9, -0.2]
+    sets = {"local": _capi.ConstraintSet(prim, cons, sk), "aligned": _capi.ConstraintSet(prim, cons, sk, alignment=sk.alignment_to(prev, 0))}
+    try:
+        for name, tree in trees.items():
+            for mode, cset in sets.items():
+                for n in (1, 2, 5):
+                    rec = search_on_device([(tree, prim, cset)], n)[0]
+                    value, row, leaf, n_eval = _host(tree, prim, cset, n)
+                    assert rec["flags"] == 0, (name, mode, n)
+                    assert rec["row"] == row and rec["leaf"] == leaf, (name, mode, n)
+                    assert _bits(rec["value"]) == _bits(value), (name, mode, n, rec["value"], value)
+                    assert rec["evaluations"] == n_eval
+                    # the winner's value is what mg_score_constraints gives for its point
+                    assert _bits(prim.score_constraints(cset, np.ascontiguousarray(tree.points[row:row + 1, :40]))[0]) == _bits(rec["value"])
+                    assert tree.result_of_record(rec)[1] == tree.points[row].tolist()
+    finally:
+        for c in sets.values():
+            c.close()
+        for t in trees.values():
+            t.close()
+        prim.close()
+
+
+@pytest.mark.parametrize("kind,n", [(k, n) for k in ("small", "pure", "kmeans_only", "aligned") for n in (1, 2, 5)])
+def test_device_search_returns_the_references_answer(kind, n):
+    """The reference's search restated call for call with the oracle's objective: the same point, the same number of calls."""
+    data = synthetic.make_tiny_primitive(seed=1)
+    op = orc.OraclePrimitive(data)
+    width = op.n_components + op.n_time_components
+    rng = np.random.default_rng({"small": 1, "pure": 2, "kmeans_only": 3, "aligned": 4}[kind])
+    samples = rng.standard_normal(({"small": 300, "pure": 2000, "kmeans_only": 200, "aligned": 300}[kind], width))
+    kw = {"small": dict(n_subdivisions=4, max_level=6), "pure": dict(n_subdivisions=1), "kmeans_only": dict(n_subdivisions=4, use_kd_tree=False),
+          "aligned": dict(n_subdivisions=4, max_level=6)}[kind]
+    tree = HipClusterTree.from_reference(synthetic.make_kd_cluster_tree(samples, seed=5, **kw), op.n_components)
+    cons = [{"type": "position", "t": 11.0, "weight": 1.0, "target": [40.0, None, -25.0]},
+            {"type": "position", "t": 5.5, "weight": 0.5, "target": [10.0, 3.0, 20.0]}]
+    ctx = get_context(0)
+    prim = _capi.Primitive(ctx, data)
+    sk = None
+    if kind == "aligned":
+        prev = np.asarray([12.0, 80.0, -5.0, 0.9, 0.1, 0.3, 0.2])
+        joints, animated = synthetic.make_skeleton(n_animated=(op.n_dim - 3) // 4)
+        sk = _capi.Skeleton(joints, animated)
+        cset = _capi.ConstraintSet(prim, cons, sk, alignment=sk.alignment_to(prev, animated[0]))
+        f = lambda S: float(op.aligned_residuals(S, cons, prev, joints, animated, animated[0]).sum())
+    else:
+        cset = _capi.ConstraintSet(prim, cons)
+        f = lambda S: float(op.keyframe_errors(S, cons)[0])
+    calls = []
+
+    def obj(x, args):
+        calls.append(1)
+        return f(np.asarray(x, dtype=np.float64)[None, :])
+    try:
+        value, sample = tree.find_best_example_excluding_search_candidates(obj, None, n)
+        rec = search_on_device([(tree, prim, cset)], n)[0]
+        assert rec["flags"] == 0
+        assert tree.points[int(rec["row"])].tolist() == sample
+        assert rec["evaluations"] == len(calls)
+        np.testing.assert_allclose(rec["value"], value, rtol=1e-9, atol=1e-8)    # the scorer's contract with the oracle
+    finally:
+        cset.close()
+        tree.close()
+        prim.close()
+
+
+def test_sixteen_searches_in_one_launch_equal_sixteen_calls():
+    ctx = get_context(0)
+    prims, trees, searches = [], [], []
+    for p, data in enumerate(synthetic.make_graph_primitives(4, seed=300)):
+        prim = _capi.Primitive(ctx, data)
+        samples = np.random.default_rng(p).standard_normal((1500, prim.n_components + 2))    # wider than L: time latents
+        kw = dict(n_subdivisions=1) if p == 3 else dict(n_subdivisions=4, max_level=12)
+        tree = HipClusterTree.from_reference(synthetic.make_kd_cluster_tree(samples, seed=p, **kw), prim.n_components)
+        prims.append(prim)
+        trees.append(tree)
+        t_end = float(prim.n_canonical_frames - 1)
+        for q in range(4):
+            cons = [{"type": "position", "t": t_end, "weight": 1.0, "target": [20.0 * q - 30.0, None, 15.0 * p]},
+                    {"type": "direction", "t": 0.5 * t_end, "weight": 0.2, "target": [0.1 * q, 1.0]}]
+            searches.append((tree, prim, _capi.ConstraintSet(prim, cons)))
+    ctx.profile_enable(True)
+    try:
+        for n in (1, 3):
+            ctx.profile_reset()
+            together = search_on_device(searches, n)
+            assert ctx.profile_get("cluster_tree_search")[1] == 1
+            singles = np.concatenate([search_on_device([s], n) for s in searches])
+            assert ctx.profile_get(11)[1] == 1 + len(searches)
+            np.testing.assert_array_equal(together.view(np.uint8), singles.view(np.uint8))
+            assert np.all(together["flags"] == 0) and len(set(together["row"].tolist())) > 4
+            for (tree, prim, cset), rec in zip(searches, together):
+                value, row, leaf, n_eval = _host(tree, prim, cset, n)
+                assert (rec["row"], rec["leaf"], rec["evaluations"]) == (row, leaf, n_eval) and _bits(rec["value"]) == _bits(value)
+    finally:
+        ctx.profile_enable(False)
+        for _, _, c in searches:
+            c.close()
+        for t in trees:
+            t.close()
+        for p in prims:
+            p.close()
+
+
+def test_no_mean_flag_where_the_reference_raises_attribute_error():
+    data = synthetic.make_tiny_primitive(seed=1)
+    samples = np.random.default_rng(9).standard_normal((2000, 3))
+    tree = HipClusterTree.from_reference(synthetic.make_kd_cluster_tree(samples, 4, 2, seed=0), 3)   # KD children below depth 2
+    ctx = get_context(0)
+    prim = _capi.Primitive(ctx, data)
+    cset = _capi.ConstraintSet(prim, [{"type": "position", "t": 11.0, "weight": 1.0, "target": [1.0, None, 2.0]}])
+    try:
+        for n in (1, 2, 4):
+            rec = search_on_device([(tree, prim, cset)], n)[0]
+            assert rec["flags"] == _capi.MG_TREE_NO_MEAN and rec["row"] == -1
+            with pytest.raises(AttributeError):
+                tree.result_of_record(rec)
+            with pytest.raises(AttributeError):
+                _host(tree, prim, cset, n)
+    finally:
+        cset.close()
+        tree.close()
+        prim.close()
+
+
+def _pickled_graph_zip(path, version=3.0):
+    prims = synthetic.make_graph_primitives(3, seed=500)
+    lists = [{k: (v.tolist() if hasattr(v, "tolist") else v) for k, v in p.items()} for p in prims]
+    synthetic.write_graph_zip(path, {"walk": {"primitives": {"a": lists[0], "b": lists[1], "c": lists[2]}, "info": {}}}, format_version=version)
+    trees = {}
+    with zipfile.ZipFile(path, "a") as z:
+        for i, name in enumerate(("a", "b")):
+            samples = np.random.default_rng(40 + i).standard_normal((800, len(prims[i]["gmm_means"][0])))
+            obj = synthetic.make_kd_cluster_tree(samples, 4, 12, seed=i) if name == "a" else synthetic.make_pickled_feature_cluster_tree(samples, 4, i)[0]
+            trees[("walk", name)] = samples
+            z.writestr("elementary_action_models/elementary_action_walk/walk_%s_quaternion_cluster_tree.pck" % name,
+                       synthetic.write_reference_pickle(obj, 5 if name == "a" else 2))
+    return trees, prims
+
+
+def test_generator_on_a_graph_with_pickled_trees(tmp_path):
+    path = str(tmp_path / "graph.zip")
+    samples, prims = _pickled_graph_zip(path)
+    graph = HipMotionStateGraph().load_from_zip(path, pickle_objects=True)
+    try:
+        node = graph.nodes[("walk", "a")]
+        assert isinstance(node.cluster_tree, HipClusterTree)
+        assert isinstance(graph.nodes[("walk", "b")].cluster_tree, HipFeatureClusterTree)
+        np.testing.assert_array_equal(node.cluster_tree.data, samples[("walk", "a")])
+        t_end = float(node.get_n_canonical_frames() - 1)
+        cons = [{"type": "position", "t": t_end, "weight": 1.0, "target": [25.0, None, -10.0]}]
+        cfg = {"n_random_samples": 50, "use_constraints": True, "use_transition_model": False, "use_local_coordinates": True,
+               "constrained_sampling_mode": "cluster_tree_search", "n_cluster_search_candidates": 2,
+               "local_optimization_settings": {"start_error_threshold": 0.0, "error_scale_factor": 1.0, "quality_scale_factor": 0.1,
+                                               "method": "leastsq", "max_iterations": 50, "verbose": False}}
+        gen = HipMotionPrimitiveGenerator(graph.nodes, cfg, "walk")
+        # exhaustive (the default): every stored sample scored
+        c = _Constraints(cons)
+        pick = gen.generate_constrained_sample(node, c)
+        L = node.get_n_spatial_components()
+        stored = node.cluster_tree.data[:, :L]
+        best_idx, min_error = orc.first_min_argmin(orc.OraclePrimitive(prims[0]).keyframe_errors(stored, cons))
+        np.testing.assert_array_equal(pick, stored[best_idx])
+        assert c.evaluations == len(stored) and abs(c.min_error - min_error) <= 1e-8
+        # descend: the one-launch search, the same as the host-driven per-step path
+        gen.set_algorithm_config(dict(cfg, cluster_tree_search_method="descend"))
+        c = _Constraints(cons)
+        pick = gen.generate_constrained_sample(node, c)
+        err, s = node.search_best_sample_on_device(_Constraints(cons), 2)
+        np.testing.assert_array_equal(pick, np.array(s))
+        assert _bits(c.min_error) == _bits(err) and c.evaluations > 0
+        c2 = _Constraints(cons)
+        err2, s2 = node.search_best_sample_batched(c2, 2)
+        assert s2 == s and _bits(err2) == _bits(err) and c2.evaluations == c.evaluations
+    finally:
+        graph.close()
+
+
+def test_evaluate_options_with_pickled_trees(tmp_path):
+    path = str(tmp_path / "graph.zip")
+    _pickled_graph_zip(path, version=4.0)
+    with zipfile.ZipFile(path, "r") as z:
+        entries = {n: z.read(n) for n in z.namelist()}
+    entries["graph_definition.json"] = b'{"formatVersion": 4.0, "usePickle": true, "transitions": {}}'
+    with zipfile.ZipFile(path, "w") as z:
+        for n, b in entries.items():
+            z.writestr(n, b)
+    graph = HipMotionStateGraph().load_from_zip(path, pickle_objects=True)
+    try:
+        options = [("walk", "a"), ("walk", "b"), ("walk", "c")]
+        cons = {}
+        for key in options:
+            t_end = float(graph.nodes[key].get_n_canonical_frames() - 1)
+            cons[key] = [{"type": "position", "t": t_end, "weight": 1.0, "target": [25.0, None, -10.0]}]
+        ctx = graph.ctx
+        ctx.profile_enable(True)
+        ctx.profile_reset()
+        try:
+            best, results = graph.evaluate_options(options, cons, 64, rng_seed=3, use_cluster_trees=True)
+            assert ctx.profile_get(11)[1] == 2          # one launch per tree kind
+        finally:
+            ctx.profile_enable(False)
+        for key in options[:2]:
+            err, s = graph.nodes[key].search_best_sample_on_device(cons[key], 1)
+            np.testing.assert_array_equal(np.asarray(results[key][0]), np.asarray(s))
+            assert _bits(results[key][1]) == _bits(err)
+        assert np.isfinite(results[("walk", "c")][1])
+        assert best == options[int(np.argmin([results[k][1] for k in options]))]
+    finally:
+        graph.close()
+
+
+def test_misuse_returns_status_codes():
+    ctx = get_context(0)
+    data = synthetic.make_tiny_primitive(seed=1)
+    prim = _capi.Primitive(ctx, data)
+    samples = np.random.default_rng(0).standard_normal((50, 3))
+    kd = HipClusterTree.from_reference(synthetic.make_kd_cluster_tree(samples, 4, 6, seed=0), 3)
+    feat = HipFeatureClusterTree.from_json(synthetic.make_feature_cluster_tree(samples, 4, seed=0), 3)
+    cset = _capi.ConstraintSet(prim, [{"type": "position", "t": 11.0, "weight": 1.0, "target": [1.0, None, 2.0]}])
+    dk, df = kd.device_tree(prim), feat.device_tree(prim)
+    try:
+        for n in (0, _capi.MG_TREE_MAX_CANDIDATES + 1, -1):
+            with pytest.raises(_capi.MGError) as e:
+                _capi.search_cluster_trees([prim], [dk], [cset], n)
+            assert e.value.status == _capi.MG_ERR_INVALID_ARGUMENT
+        for pair in ((dk, df), (df, dk)):                 # one kind per call
+            with pytest.raises(_capi.MGError) as e:
+                _capi.search_cluster_trees([prim, prim], list(pair), [cset, cset], 1)
+            assert e.value.status == _capi.MG_ERR_INVALID_ARGUMENT
+        # the C side validates the tables: (points rows, n_kd, child_begin, children, leaf, kd_begin, kd_roots, left, right, inner)
+        bad = [(3, 1, [0, 1, 1], [1], [0, 1], [0, 1, 1], [0], [-1], [-1], [0]),          # node 0 mixes cluster and KD children
+               (3, 1, [0, 1, 1], [1], [1, 1], [0, 0, 1], [0], [-1], [-1], [0]),          # a leaf with cluster children
+               (3, 2, [0, 0], [], [1], [0, 1], [0], [1, 0], [-1, -1], [1, 1]),          # a KD cycle
+               (3, 2, [0, 0], [], [1], [0, 1], [0], [-1, -1], [-1, -1], [0, 0]),        # a KD node nobody reaches
+               (3, 2, [0, 0], [], [1], [0, 1], [2], [-1, -1], [-1, -1], [0, 0])]        # a KD root out of range
+        for rows, nk, cb, ch, lf, kb, kr, kl, krt, ki in bad:
+            with pytest.raises(_capi.MGError) as e:
+                _capi.KdClusterTree(prim, np.zeros((rows, 3)), nk, cb, ch, lf, kb, kr, kl, krt, ki)
+            assert e.value.status == _capi.MG_ERR_INVALID_ARGUMENT
+        ok = _capi.KdClusterTree(prim, np.zeros((3, 3)), 2, [0, 0], [], [1], [0, 1], [0], [1, -1], [-1, -1], [1, 0])
+        ok.close()
+    finally:
+        cset.close()
+        kd.close()
+        feat.close()
+        prim.close()
+
+
+GOLDEN = np.load(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "kd_cluster_tree_search.npz"),
+                 allow_pickle=False)
+_TABLES = ("child_begin", "children", "leaf", "kd_begin", "kd_roots", "kd_left", "kd_right", "kd_inner")
+
+
+@pytest.mark.parametrize("k,name", list(enumerate(str(n) for n in GOLDEN["names"])))
+def test_device_search_matches_the_golden_cases(k, name):
+    g, p = GOLDEN, "c%d_" % k
+    spec = json.loads(str(g[p + "primitive"]))
+    data = getattr(synthetic, spec["factory"])(**spec["kwargs"])
+    tree = HipClusterTree(g[p + "data"], g[p + "points"], int(g[p + "n_kd"]), *[g[p + t] for t in _TABLES])
+    cons, prev, n = json.loads(str(g[p + "constraints"])), g[p + "prev_frame"], int(g[p + "n_candidates"])
+    ctx = get_context(0)
+    prim = _capi.Primitive(ctx, data)
+    if prev.size:
+        joints, animated = synthetic.make_skeleton(n_animated=(int(data["n_dim_spatial"]) - 3) // 4)
+        sk = _capi.Skeleton(joints, animated)
+        cset = _capi.ConstraintSet(prim, cons, sk, alignment=sk.alignment_to(prev, animated[0]))
+    else:
+        cset = _capi.ConstraintSet(prim, cons)
+    try:
+        rec = search_on_device([(tree, prim, cset)], n)[0]
+        if str(g[p + "raised"]):
+            assert rec["flags"] == _capi.MG_TREE_NO_MEAN
+            with pytest.raises(AttributeError):
+                tree.result_of_record(rec)
+            return
+        assert rec["flags"] == 0
+        assert tree.result_of_record(rec)[1] == g[p + "sample"].tolist(), name
+        assert rec["evaluations"] == len(g[p + "call_values"])
+        np.testing.assert_allclose(rec["value"], g[p + "value"], rtol=1e-9, atol=1e-8)    # the scorer's contract with the oracle
+        value, row, leaf, n_eval = _host(tree, prim, cset, n)
+        assert (rec["row"], rec["leaf"], rec["evaluations"]) == (row, leaf, n_eval) and _bits(rec["value"]) == _bits(value)
+    finally:
+        cset.close()
+        tree.close()
+        prim.close()

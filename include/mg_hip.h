@@ -829,6 +829,24 @@ int mg_cluster_tree_create_kd(mg_primitive *prim, int32_t n_nodes, int32_t n_kd,
                               const int32_t *children, const int32_t *leaf, const int32_t *kd_begin, const int32_t *kd_roots,
                               const int32_t *kd_left, const int32_t *kd_right, const int32_t *kd_inner, mg_cluster_tree **tree);
 
+/* ---- batched k-means for building cluster trees (reference space_partitioning/cluster_tree_node_builder.py:83-100,
+ * clustering.py:69-129: sklearn's KMeans(n_clusters=k).fit_predict, once per tree node) ----
+ * Every segment s is the rows rows[seg_begin[s] .. seg_begin[s + 1]) of the device table points_dev (n_rows, dim) float64,
+ * and all n_segments segments are clustered in one call, with sklearn's KMeans(algorithm="lloyd") semantics per segment:
+ * greedy k-means++ (2 + int(ln k) candidates per centre; uniforms from Philox keyed by (seed, node_ids[s], run), node_ids
+ * NULL = the segment index) or the caller's initial centres init (n_segments, k, dim; then n_init must be 1); Lloyd
+ * iterations with float64 squared distances, ties to the lowest centre, an empty cluster taking the member farthest from
+ * its centre (several: descending distance, first position on ties); stop on unchanged labels, on a summed squared centre
+ * shift <= tol * mean(var(X, axis=0)) of the segment, or after max_iter iterations, then (not strictly converged) one
+ * assignment-only pass.  Of n_init runs the one of least inertia is kept (the first on ties).  Bit-reproducible: no float
+ * atomics, every sum in a fixed order.  Host arrays: seg_begin (n_segments + 1, seg_begin[0] = 0, every segment >= k rows),
+ * rows (seg_begin[n_segments] entries in [0, n_rows)), outputs labels (one per position of rows), centres (n_segments, k,
+ * dim), inertia and n_iter (n_segments).  Synchronises.  MG_ERR_UNSUPPORTED outside 1 <= dim <= 128, 2 <= k <= 64,
+ * 1 <= n_init <= 16. */
+int mg_kmeans_segments(mg_context *ctx, const double *points_dev, int64_t n_rows, int32_t dim, int32_t n_segments, const int64_t *seg_begin,
+                       const int64_t *rows, int32_t k, int32_t n_init, const double *init, const uint64_t *node_ids, uint64_t seed,
+                       int32_t max_iter, double tol, int32_t *labels, double *centres, double *inertia, int32_t *n_iter);
+
 /* ---- host-pointer convenience variants (H2D, launch, D2H, synchronise) ---------------- */
 int mg_back_project_frames_host(mg_primitive *prim, const mg_time_grid *grid, const void *latents,
                                 int latent_dtype, int64_t n_samples, int64_t ld, float *frames, int path);

@@ -82,7 +82,7 @@ EXPORTED_SYMBOLS = [
     "mg_align_frames", "mg_frame_constraint_width", "mg_score_frame_constraint", "mg_score_frame_constraints", "mg_options_frame_lists", "mg_track_plan_create", "mg_track_plan_destroy", "mg_joint_tracks",
     "mg_score_constraint_residuals_chained", "mg_option_step", "mg_options_step", "mg_options_step_device_counts", "mg_option_step_rows", "mg_options_step_rows", "mg_gmm_sample_rows", "mg_dist_broadcast",
     "mg_cluster_tree_create", "mg_cluster_tree_destroy", "mg_cluster_tree_search", "mg_cluster_tree_search_host",
-    "mg_cluster_tree_create_kd",
+    "mg_cluster_tree_create_kd", "mg_kmeans_segments",
 ]
 
 
@@ -343,6 +343,7 @@ def load_library(path=None):
         "mg_cluster_tree_create_kd": [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(vp)],
         "mg_cluster_tree_search": [i32, vp, vp, vp, i32, vp],
         "mg_cluster_tree_search_host": [i32, vp, vp, vp, i32, vp],
+        "mg_kmeans_segments": [vp, vp, i64, i32, i32, vp, vp, i32, i32, vp, vp, u64, i32, dbl, vp, vp, vp, vp],
     }
     for name, argtypes in sigs.items():
         fn = getattr(lib, name)
@@ -884,6 +885,37 @@ def search_cluster_trees(prims, trees, csets, n_candidates, records_dev=None):
     out = np.zeros(m, dtype=TREE_SEARCH_RECORD)
     _check(lib.mg_cluster_tree_search_host(m, hp, ht, hc, int(n_candidates), out.ctypes.data_as(vp)))
     return out
+
+
+MG_KMEANS_MAX_DIM, MG_KMEANS_MAX_K, MG_KMEANS_MAX_N_INIT = 128, 64, 16   # mg_kmeans_segments (include/mg_hip.h)
+
+
+def kmeans_segments(ctx, points_dev, n_rows, dim, seg_begin, rows, k, n_init=1, init=None, node_ids=None, seed=0, max_iter=300, tol=1e-4):
+    """mg_kmeans_segments: k-means of every segment rows[seg_begin[s]:seg_begin[s + 1]] of the device table points_dev (n_rows, dim)
+    float64.  Returns (labels per position of rows (int32), centres (n_segments, k, dim), inertia (n_segments), n_iter (n_segments))."""
+    sb = np.ascontiguousarray(seg_begin, dtype=np.int64)
+    r = np.ascontiguousarray(rows, dtype=np.int64)
+    S = len(sb) - 1
+    if S < 0 or (S > 0 and len(r) != sb[-1]):
+        raise ValueError("seg_begin (n_segments + 1) must end at len(rows)")
+    labels = np.zeros(max(len(r), 1), dtype=np.int32)
+    centres = np.zeros((max(S, 1), int(k), int(dim)), dtype=np.float64)
+    inertia = np.zeros(max(S, 1), dtype=np.float64)
+    n_iter = np.zeros(max(S, 1), dtype=np.int32)
+    vp = C.c_void_p
+    ini = None if init is None else np.ascontiguousarray(init, dtype=np.float64)
+    if ini is not None and ini.shape != (S, int(k), int(dim)):
+        raise ValueError("init must be (n_segments, k, dim)")
+    ids = None if node_ids is None else np.ascontiguousarray(node_ids, dtype=np.uint64)
+    if ids is not None and ids.shape != (S,):
+        raise ValueError("node_ids must have one entry per segment")
+
+    def ptr(a):
+        return None if a is None else a.ctypes.data_as(vp)
+    _check(ctx.lib.mg_kmeans_segments(ctx.handle, _dev_ptr(points_dev), int(n_rows), int(dim), int(max(S, 0)), ptr(sb), ptr(r), int(k), int(n_init),
+                                      ptr(ini), ptr(ids), int(seed) & 0xFFFFFFFFFFFFFFFF, int(max_iter), float(tol), ptr(labels), ptr(centres),
+                                      ptr(inertia), ptr(n_iter)))
+    return labels[:len(r)], centres[:S], inertia[:S], n_iter[:S]
 
 
 class TrackPlan(object):

@@ -847,6 +847,22 @@ int mg_kmeans_segments(mg_context *ctx, const double *points_dev, int64_t n_rows
                        const int64_t *rows, int32_t k, int32_t n_init, const double *init, const uint64_t *node_ids, uint64_t seed,
                        int32_t max_iter, double tol, int32_t *labels, double *centres, double *inertia, int32_t *n_iter);
 
+/* Batched EM of full-covariance Gaussian mixtures (GMMTrainer's AIC sweep: sklearn GaussianMixture(covariance_type='full',
+ * init_params='kmeans', n_init=1) per fit, float64) over one device points table points_dev (n, dim).  Fit f has
+ * n_comp[f] components and starts from the one-hot responsibilities of its labels labels_in[f * n .. f * n + n); the
+ * M-step computes the covariances in two passes (means first) and adds reg_covar on the diagonal; the loop stops when the
+ * lower bound changes by less than tol or after max_iter iterations; a final E-step gives the score (mean log p) and the
+ * labels.  Every sum runs in an order fixed by (n, dim, K) alone: a fit gives the same bits alone or in any batch.
+ * Outputs (host, components of all fits concatenated): weights (sum K), means (sum K, dim), covariances and
+ * precisions_chol (sum K, dim, dim), lower_bounds (n_fits, max_iter; the first n_iter[f] entries set), n_iter, status
+ * (1 converged, 2 stopped at max_iter, 3 ill-defined covariance: a non-positive or non-finite Cholesky pivot, which ends
+ * that fit only), score (n_fits), labels_out (n_fits, n).  Synchronises.  MG_ERR_UNSUPPORTED outside 1 <= dim <= 64 and
+ * 1 <= n_comp[f] <= 64. */
+int mg_gmm_em_fit(mg_context *ctx, const double *points_dev, int64_t n, int32_t dim, int32_t n_fits, const int32_t *n_comp,
+                  const int32_t *labels_in, double tol, double reg_covar, int32_t max_iter, double *weights, double *means,
+                  double *covariances, double *precisions_chol, double *lower_bounds, int32_t *n_iter, int32_t *status,
+                  double *score, int32_t *labels_out);
+
 /* ---- host-pointer convenience variants (H2D, launch, D2H, synchronise) ---------------- */
 int mg_back_project_frames_host(mg_primitive *prim, const mg_time_grid *grid, const void *latents,
                                 int latent_dtype, int64_t n_samples, int64_t ld, float *frames, int path);

@@ -82,7 +82,7 @@ EXPORTED_SYMBOLS = [
     "mg_align_frames", "mg_frame_constraint_width", "mg_score_frame_constraint", "mg_score_frame_constraints", "mg_options_frame_lists", "mg_track_plan_create", "mg_track_plan_destroy", "mg_joint_tracks",
     "mg_score_constraint_residuals_chained", "mg_option_step", "mg_options_step", "mg_options_step_device_counts", "mg_option_step_rows", "mg_options_step_rows", "mg_gmm_sample_rows", "mg_dist_broadcast",
     "mg_cluster_tree_create", "mg_cluster_tree_destroy", "mg_cluster_tree_search", "mg_cluster_tree_search_host",
-    "mg_cluster_tree_create_kd", "mg_kmeans_segments",
+    "mg_cluster_tree_create_kd", "mg_kmeans_segments", "mg_gmm_em_fit",
 ]
 
 
@@ -344,6 +344,7 @@ def load_library(path=None):
         "mg_cluster_tree_search": [i32, vp, vp, vp, i32, vp],
         "mg_cluster_tree_search_host": [i32, vp, vp, vp, i32, vp],
         "mg_kmeans_segments": [vp, vp, i64, i32, i32, vp, vp, i32, i32, vp, vp, u64, i32, dbl, vp, vp, vp, vp],
+        "mg_gmm_em_fit": [vp, vp, i64, i32, i32, vp, vp, dbl, dbl, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     }
     for name, argtypes in sigs.items():
         fn = getattr(lib, name)
@@ -916,6 +917,42 @@ def kmeans_segments(ctx, points_dev, n_rows, dim, seg_begin, rows, k, n_init=1, 
                                       ptr(ini), ptr(ids), int(seed) & 0xFFFFFFFFFFFFFFFF, int(max_iter), float(tol), ptr(labels), ptr(centres),
                                       ptr(inertia), ptr(n_iter)))
     return labels[:len(r)], centres[:S], inertia[:S], n_iter[:S]
+
+
+MG_GMM_EM_MAX_DIM, MG_GMM_EM_MAX_K = 64, 64        # mg_gmm_em_fit (include/mg_hip.h)
+MG_GMM_EM_CONVERGED, MG_GMM_EM_MAX_ITER, MG_GMM_EM_ILL_DEFINED = 1, 2, 3
+
+
+def gmm_em_fit(ctx, points_dev, n, dim, n_comp, labels, tol=1e-3, reg_covar=1e-6, max_iter=100):
+    """mg_gmm_em_fit: EM of len(n_comp) full-covariance mixtures over the device table points_dev (n, dim) float64, fit f
+    from the labels labels[f] (n,).  Returns one dict per fit: weights, means, covariances, precisions_cholesky,
+    lower_bounds (n_iter entries), n_iter, status, score, labels."""
+    K = np.ascontiguousarray(n_comp, dtype=np.int32).reshape(-1)
+    F, NC, n, dim = len(K), int(K.sum()), int(n), int(dim)
+    lab = np.ascontiguousarray(labels, dtype=np.int32).reshape(F, n) if F else np.zeros((0, n), dtype=np.int32)
+    w = np.zeros(max(NC, 1))
+    mu = np.zeros((max(NC, 1), dim))
+    cov = np.zeros((max(NC, 1), dim, dim))
+    prec = np.zeros((max(NC, 1), dim, dim))
+    lbs = np.zeros((max(F, 1), int(max_iter)))
+    n_iter = np.zeros(max(F, 1), dtype=np.int32)
+    status = np.zeros(max(F, 1), dtype=np.int32)
+    score = np.zeros(max(F, 1))
+    lout = np.zeros((max(F, 1), n), dtype=np.int32)
+
+    def ptr(a):
+        return a.ctypes.data_as(C.c_void_p)
+    _check(ctx.lib.mg_gmm_em_fit(ctx.handle, _dev_ptr(points_dev), n, dim, F, ptr(K) if F else None, ptr(lab) if F else None, float(tol),
+                                 float(reg_covar), int(max_iter), ptr(w), ptr(mu), ptr(cov), ptr(prec), ptr(lbs), ptr(n_iter), ptr(status),
+                                 ptr(score), ptr(lout)))
+    out, c0 = [], 0
+    for f in range(F):
+        k = int(K[f])
+        out.append({"weights": w[c0:c0 + k].copy(), "means": mu[c0:c0 + k].copy(), "covariances": cov[c0:c0 + k].copy(),
+                    "precisions_cholesky": prec[c0:c0 + k].copy(), "lower_bounds": lbs[f, :n_iter[f]].copy(), "n_iter": int(n_iter[f]),
+                    "status": int(status[f]), "score": float(score[f]), "labels": lout[f].copy()})
+        c0 += k
+    return out
 
 
 class TrackPlan(object):

@@ -863,6 +863,31 @@ int mg_gmm_em_fit(mg_context *ctx, const double *points_dev, int64_t n, int32_t 
                   double *covariances, double *precisions_chol, double *lower_bounds, int32_t *n_iter, int32_t *status,
                   double *score, int32_t *labels_out);
 
+/* ---- functional PCA of aligned motions (reference construction/fpca), float64, synchronising, bit-reproducible ---- */
+/* Least-squares cubic B-spline coefficients of a batch of motions: coeffs_dev (n_motions, n_basis, n_dims) =
+ * operator . motions_dev[n] per motion, motions_dev (n_motions, n_frames, n_dims) and operator_dev (n_basis, n_frames) --
+ * the least-squares operator of the (n_frames, n_basis) design matrix, factored once by the host -- on the device.  A
+ * motion gives the same bits alone or in any batch.  MG_ERR_UNSUPPORTED outside n_basis <= 64 and n_frames <= 1024. */
+int mg_spline_fit_batch(mg_context *ctx, const double *motions_dev, int64_t n_motions, int32_t n_frames, int32_t n_dims,
+                        const double *operator_dev, int32_t n_basis, double *coeffs_dev);
+
+/* PCA of the device matrix a_dev (n, p): mean (host, p) = column means (rows added in row order; zeros when centre is 0:
+ * the matrix is taken as it is, as the reference's run_pca takes it), centred_dev (device, n, p) = a - mean, and the singular values (host, min(n, p), descending) and right singular vectors vt (host,
+ * (min(n, p), p), rows) of the centred matrix by one-sided Jacobi on the short side, sweeps of round-robin pairs until a
+ * whole sweep rotates no pair with |w_i . w_j| > eps sqrt(max(n, p)) |w_i| |w_j|.  n_sweeps: sweeps run; status: 1
+ * converged, 2 stopped at the cap of 30 sweeps.  Sign rule: each row's entry of largest magnitude is positive (the first
+ * one on ties).  A row whose singular value is at most eps max(n, p) times the largest has no direction of its own and is
+ * completed orthonormally to the others.  MG_ERR_UNSUPPORTED outside min(n, p) <= 4096 and max(n, p) <= 2^20;
+ * MG_ERR_INVALID_ARGUMENT for a matrix with non-finite values. */
+int mg_pca_fit(mg_context *ctx, const double *a_dev, int64_t n, int64_t p, int32_t centre, double *centred_dev, double *mean,
+               double *singular_values, double *vt, int32_t *n_sweeps, int32_t *status);
+
+/* low_dev (n, l) = x_dev (n, p) . vt_dev (l, p)^T, and high_dev (n, p) = low_dev (n, l) . vt_dev (l, p) + mean_dev (p; may
+ * be NULL); all on the device.  MG_ERR_UNSUPPORTED from n or p of 2^24 on. */
+int mg_pca_project(mg_context *ctx, const double *x_dev, const double *vt_dev, int64_t n, int64_t p, int64_t l, double *low_dev);
+int mg_pca_backproject(mg_context *ctx, const double *low_dev, const double *vt_dev, const double *mean_dev, int64_t n, int64_t p,
+                       int64_t l, double *high_dev);
+
 /* ---- host-pointer convenience variants (H2D, launch, D2H, synchronise) ---------------- */
 int mg_back_project_frames_host(mg_primitive *prim, const mg_time_grid *grid, const void *latents,
                                 int latent_dtype, int64_t n_samples, int64_t ld, float *frames, int path);

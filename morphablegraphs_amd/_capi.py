@@ -83,6 +83,7 @@ EXPORTED_SYMBOLS = [
     "mg_score_constraint_residuals_chained", "mg_option_step", "mg_options_step", "mg_options_step_device_counts", "mg_option_step_rows", "mg_options_step_rows", "mg_gmm_sample_rows", "mg_dist_broadcast",
     "mg_cluster_tree_create", "mg_cluster_tree_destroy", "mg_cluster_tree_search", "mg_cluster_tree_search_host",
     "mg_cluster_tree_create_kd", "mg_kmeans_segments", "mg_gmm_em_fit",
+    "mg_spline_fit_batch", "mg_pca_fit", "mg_pca_project", "mg_pca_backproject",
 ]
 
 
@@ -345,6 +346,10 @@ def load_library(path=None):
         "mg_cluster_tree_search_host": [i32, vp, vp, vp, i32, vp],
         "mg_kmeans_segments": [vp, vp, i64, i32, i32, vp, vp, i32, i32, vp, vp, u64, i32, dbl, vp, vp, vp, vp],
         "mg_gmm_em_fit": [vp, vp, i64, i32, i32, vp, vp, dbl, dbl, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+        "mg_spline_fit_batch": [vp, vp, i64, i32, i32, vp, i32, vp],
+        "mg_pca_fit": [vp, vp, i64, i64, i32, vp, vp, vp, vp, vp, vp],
+        "mg_pca_project": [vp, vp, vp, i64, i64, i64, vp],
+        "mg_pca_backproject": [vp, vp, vp, vp, i64, i64, i64, vp],
     }
     for name, argtypes in sigs.items():
         fn = getattr(lib, name)
@@ -953,6 +958,42 @@ def gmm_em_fit(ctx, points_dev, n, dim, n_comp, labels, tol=1e-3, reg_covar=1e-6
                     "status": int(status[f]), "score": float(score[f]), "labels": lout[f].copy()})
         c0 += k
     return out
+
+
+MG_FPCA_MAX_BASIS, MG_FPCA_MAX_FRAMES, MG_PCA_MAX_SHORT, MG_PCA_MAX_LONG, MG_PCA_MAX_SWEEPS = 64, 1024, 4096, 1 << 20, 30   # mg_fpca.hip (include/mg_hip.h)
+MG_PCA_CONVERGED, MG_PCA_SWEEP_CAP = 1, 2
+MG_PCA_PROJECT_MAX_SIDE = (1 << 24) - 1
+
+
+def spline_fit_batch(ctx, motions_dev, n_motions, n_frames, n_dims, operator_dev, n_basis, coeffs_dev):
+    """mg_spline_fit_batch: coeffs_dev (n_motions, n_basis, n_dims) = operator (n_basis, n_frames) . motion, per motion."""
+    _check(ctx.lib.mg_spline_fit_batch(ctx.handle, _dev_ptr(motions_dev), int(n_motions), int(n_frames), int(n_dims), _dev_ptr(operator_dev),
+                                       int(n_basis), _dev_ptr(coeffs_dev)))
+
+
+def pca_fit(ctx, a_dev, n, p, centred_dev, centre=True):
+    """mg_pca_fit of the device matrix a_dev (n, p) float64; centred_dev receives a - mean (a itself with centre=False).  Returns {"mean" (p,),
+    "singular_values" (min,), "vt" (min, p), "n_sweeps", "status"}."""
+    n, p = int(n), int(p)
+    m = max(min(n, p), 1)
+    mean, sv, vt = np.zeros(max(p, 1)), np.zeros(m), np.zeros((m, max(p, 1)))
+    sweeps, status = C.c_int32(0), C.c_int32(0)
+
+    def ptr(a):
+        return a.ctypes.data_as(C.c_void_p)
+    _check(ctx.lib.mg_pca_fit(ctx.handle, _dev_ptr(a_dev), n, p, 1 if centre else 0, _dev_ptr(centred_dev), ptr(mean), ptr(sv), ptr(vt), C.byref(sweeps), C.byref(status)))
+    return {"mean": mean, "singular_values": sv, "vt": vt, "n_sweeps": int(sweeps.value), "status": int(status.value)}
+
+
+def pca_project(ctx, x_dev, vt_dev, n, p, l, low_dev):
+    """mg_pca_project: low_dev (n, l) = x_dev (n, p) . vt_dev (l, p)^T."""
+    _check(ctx.lib.mg_pca_project(ctx.handle, _dev_ptr(x_dev), _dev_ptr(vt_dev), int(n), int(p), int(l), _dev_ptr(low_dev)))
+
+
+def pca_backproject(ctx, low_dev, vt_dev, mean_dev, n, p, l, high_dev):
+    """mg_pca_backproject: high_dev (n, p) = low_dev (n, l) . vt_dev (l, p) + mean_dev (p) (None: no mean)."""
+    _check(ctx.lib.mg_pca_backproject(ctx.handle, _dev_ptr(low_dev), _dev_ptr(vt_dev), None if mean_dev is None else _dev_ptr(mean_dev),
+                                      int(n), int(p), int(l), _dev_ptr(high_dev)))
 
 
 class TrackPlan(object):

@@ -888,6 +888,35 @@ int mg_pca_project(mg_context *ctx, const double *x_dev, const double *vt_dev, i
 int mg_pca_backproject(mg_context *ctx, const double *low_dev, const double *vt_dev, const double *mean_dev, int64_t n, int64_t p,
                        int64_t l, double *high_dev);
 
+/* ---- temporal alignment: exact dynamic time warping of motions against one reference motion (reference construction/dtw.py),
+ * float64, synchronising, bit-reproducible.  Motions are ragged: motion n has F_n = offsets[n + 1] - offsets[n] frames and its rows
+ * start at row offsets[n] of a table; offsets is a HOST array of n_motions + 1 entries, offsets[0] = 0, rising.
+ * MG_ERR_UNSUPPORTED outside n_ref_frames, F_n <= 1024 and n_joints <= 64; MG_ERR_INVALID_ARGUMENT for offsets that do not start at
+ * 0 or do not rise, and for non-finite clouds or grids (found by a check kernel; the DTW kernels are then not launched).
+ * n_motions = 0 is MG_OK and does nothing. ---- */
+/* The distance grids S[n] (n_ref_frames, F_n), row-major, S[n] at grids_dev + n_ref_frames * offsets[n]: cell (i, j) = the MEAN over
+ * the joints of the distance between the reference motion's cloud ref_cloud_dev[i] (n_joints, 3) and clouds_dev[offsets[n] + j]
+ * after the weighted closed-form 2-D rigid fit (rotation about y, translation in x and z) of the latter onto the former; weights:
+ * HOST array (n_joints), NULL = ones.  Formula and order of every sum: csrc/mg_dtw.hip.  PARITY UNPINNED (the reference's distance
+ * is anim_utils' _transform_invariant_point_cloud_distance); the restatement is oracle/mg_oracle.py align_point_clouds_2d. */
+int mg_dtw_distance_grids(mg_context *ctx, const double *ref_cloud_dev, int32_t n_ref_frames, const double *clouds_dev, const int64_t *offsets,
+                          int64_t n_motions, int32_t n_joints, const double *weights, double *grids_dev);
+
+/* Accumulated cost, optimal path and warping function per grid (get_distgrid's second half, find_path, get_warping_function):
+ * D[0,0] = S[0,0], first column and row the running sums, D[i,j] = min(D[i-1,j-1], D[i-1,j], D[i,j-1]) + S[i,j]; back-steps to the
+ * first minimum of (diagonal, (i-1, j), (i, j-1)).  Device outputs: accumulated_dev (laid out as the grids; NULL: not stored),
+ * totals_dev (n_motions) = D[-1,-1], paths_dev: (i, j) int32 pairs front to back, motion n's at pair offsets[n] + n * (n_ref_frames
+ * - 1) with room for n_ref_frames + F_n - 1, path_lengths_dev (n_motions) int32, warping_dev (n_motions, n_ref_frames) int32 = the
+ * last j the path has in row i.  D, paths and totals are the reference's bit for bit for the same grids. */
+int mg_dtw_paths(mg_context *ctx, const double *grids_dev, int32_t n_ref_frames, const int64_t *offsets, int64_t n_motions,
+                 double *accumulated_dev, double *totals_dev, int32_t *paths_dev, int32_t *path_lengths_dev, int32_t *warping_dev);
+
+/* warp_motion for a batch: warped_dev (n_motions, n_ref_frames, n_dim) row i of motion n = row warping_dev[n][i] of motion n's
+ * frames in frames_dev (offsets[n_motions], n_dim).  MG_ERR_INVALID_ARGUMENT if an index lies outside its motion (nothing is read
+ * for it). */
+int mg_warp_motions(mg_context *ctx, const double *frames_dev, const int64_t *offsets, int64_t n_motions, int32_t n_dim,
+                    const int32_t *warping_dev, int32_t n_ref_frames, double *warped_dev);
+
 /* ---- host-pointer convenience variants (H2D, launch, D2H, synchronise) ---------------- */
 int mg_back_project_frames_host(mg_primitive *prim, const mg_time_grid *grid, const void *latents,
                                 int latent_dtype, int64_t n_samples, int64_t ld, float *frames, int path);

@@ -1,6 +1,7 @@
 """MI355X-native motion-primitive back-projection / GMM scoring behind the morphablegraphs plugin surface.
 Importing the package does not load the HIP library; the first backend object does (and fails loudly
 if libmg_hip.so or a gfx950 device is missing -- there is no CPU fallback)."""
+from .dtw import align_frames_temporally  # noqa: F401
 from .fpca import (HipFPCASpatialData, HipFPCATimeSemantic, HipFunctionalData, HipPCAFunctionalData,  # noqa: F401
                    construct_motion_primitive_model)
 from .gaussian_mixture import HipGaussianMixture, sample_like_sklearn  # noqa: F401
@@ -11,4 +12,4 @@ from .motion_spline import HipMotionSpline  # noqa: F401
 
 __all__ = ["HipFPCASpatialData", "HipFPCATimeSemantic", "HipFunctionalData", "HipGaussianMixture", "HipMotionPrimitive",
            "HipMotionPrimitiveModelWrapper", "HipMotionSpline", "HipPCAFunctionalData", "HipStaticMotionPrimitive",
-           "construct_motion_primitive_model", "get_context", "mgrd_json_to_legacy", "sample_like_sklearn"]
+           "align_frames_temporally", "construct_motion_primitive_model", "get_context", "mgrd_json_to_legacy", "sample_like_sklearn"]

@@ -84,6 +84,7 @@ EXPORTED_SYMBOLS = [
     "mg_cluster_tree_create", "mg_cluster_tree_destroy", "mg_cluster_tree_search", "mg_cluster_tree_search_host",
     "mg_cluster_tree_create_kd", "mg_kmeans_segments", "mg_gmm_em_fit",
     "mg_spline_fit_batch", "mg_pca_fit", "mg_pca_project", "mg_pca_backproject",
+    "mg_dtw_distance_grids", "mg_dtw_paths", "mg_warp_motions",
 ]
 
 
@@ -350,6 +351,9 @@ def load_library(path=None):
         "mg_pca_fit": [vp, vp, i64, i64, i32, vp, vp, vp, vp, vp, vp],
         "mg_pca_project": [vp, vp, vp, i64, i64, i64, vp],
         "mg_pca_backproject": [vp, vp, vp, vp, i64, i64, i64, vp],
+        "mg_dtw_distance_grids": [vp, vp, i32, vp, vp, i64, i32, vp, vp],
+        "mg_dtw_paths": [vp, vp, i32, vp, i64, vp, vp, vp, vp, vp],
+        "mg_warp_motions": [vp, vp, vp, i64, i32, vp, i32, vp],
     }
     for name, argtypes in sigs.items():
         fn = getattr(lib, name)
@@ -994,6 +998,40 @@ def pca_backproject(ctx, low_dev, vt_dev, mean_dev, n, p, l, high_dev):
     """mg_pca_backproject: high_dev (n, p) = low_dev (n, l) . vt_dev (l, p) + mean_dev (p) (None: no mean)."""
     _check(ctx.lib.mg_pca_backproject(ctx.handle, _dev_ptr(low_dev), _dev_ptr(vt_dev), None if mean_dev is None else _dev_ptr(mean_dev),
                                       int(n), int(p), int(l), _dev_ptr(high_dev)))
+
+
+MG_DTW_MAX_FRAMES, MG_DTW_MAX_JOINTS = 1024, 64   # mg_dtw.hip (include/mg_hip.h)
+
+
+def _host_ptr(a):
+    return a.ctypes.data_as(C.c_void_p)
+
+
+def dtw_distance_grids(ctx, ref_cloud_dev, n_ref_frames, clouds_dev, offsets, n_joints, weights, grids_dev):
+    """mg_dtw_distance_grids: grids_dev <- S[n] (n_ref_frames, F_n) of every motion of the ragged cloud table clouds_dev
+    (offsets[-1], n_joints, 3); offsets: (n_motions + 1) host integers; weights: (n_joints) or None (ones)."""
+    off = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+    w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+    if w is not None and len(w) != int(n_joints):
+        raise ValueError("%d weights for %d joints" % (len(w), int(n_joints)))
+    _check(ctx.lib.mg_dtw_distance_grids(ctx.handle, _dev_ptr(ref_cloud_dev), int(n_ref_frames), _dev_ptr(clouds_dev), _host_ptr(off), len(off) - 1,
+                                         int(n_joints), None if w is None else _host_ptr(w), _dev_ptr(grids_dev)))
+
+
+def dtw_paths(ctx, grids_dev, n_ref_frames, offsets, accumulated_dev, totals_dev, paths_dev, path_lengths_dev, warping_dev):
+    """mg_dtw_paths: accumulated cost (accumulated_dev None: not stored), totals, paths, path lengths and warping functions
+    of the grids in grids_dev; every output on the device, laid out as include/mg_hip.h says."""
+    off = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+    _check(ctx.lib.mg_dtw_paths(ctx.handle, _dev_ptr(grids_dev), int(n_ref_frames), _host_ptr(off), len(off) - 1,
+                                None if accumulated_dev is None else _dev_ptr(accumulated_dev), _dev_ptr(totals_dev), _dev_ptr(paths_dev),
+                                _dev_ptr(path_lengths_dev), _dev_ptr(warping_dev)))
+
+
+def warp_motions(ctx, frames_dev, offsets, n_dim, warping_dev, n_ref_frames, warped_dev):
+    """mg_warp_motions: warped_dev (n_motions, n_ref_frames, n_dim) <- rows warping_dev[n][i] of motion n's frames."""
+    off = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+    _check(ctx.lib.mg_warp_motions(ctx.handle, _dev_ptr(frames_dev), _host_ptr(off), len(off) - 1, int(n_dim), _dev_ptr(warping_dev), int(n_ref_frames),
+                                   _dev_ptr(warped_dev)))
 
 
 class TrackPlan(object):

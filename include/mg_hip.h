@@ -917,6 +917,46 @@ int mg_dtw_paths(mg_context *ctx, const double *grids_dev, int32_t n_ref_frames,
 int mg_warp_motions(mg_context *ctx, const double *frames_dev, const int64_t *offsets, int64_t n_motions, int32_t n_dim,
                     const int32_t *warping_dev, int32_t n_ref_frames, double *warped_dev);
 
+/* ---- segmentation: cutting clips out of captures at keyframe poses (reference construction/keyframe_detection.py:79-135 argmin,
+ * argmin_multi, KeyframeDetector.find_instance / find_instances / calculate_distances; construction/segmentation.py:34-81
+ * Segmentation.extract_single_segments / extract_segments), float64, synchronising, bit-reproducible.  Captures are ragged like the
+ * motions above: capture n has F_n = offsets[n + 1] - offsets[n] >= 1 frames, offsets a HOST array of n_motions + 1 entries,
+ * offsets[0] = 0, rising; there is no 1024-frame limit here.  n_motions = 0 is MG_OK and does nothing.  Non-finite inputs are
+ * found by a check kernel and refused with MG_ERR_INVALID_ARGUMENT before the kernel proper is launched (the reference's
+ * `v < min_v` silently skips a NaN: a documented difference). ---- */
+/* dist_dev (n_keyframes, offsets[n_motions]), row-major: dist[k][f] = the cell of mg_dtw_distance_grids with A = frame f of
+ * clouds_dev (offsets[n_motions], n_joints, 3) and B = keyframe k of keyframes_dev (n_keyframes, n_joints, 3): the keyframe is
+ * fitted onto the frame (the reference calls distance_measure(frame, keyframe)).  Bit for bit what mg_dtw_distance_grids gives at
+ * cell (f, 0) for (reference motion = the capture, one motion = the one-frame keyframe); each frame is read once for all
+ * keyframes.  weights: HOST array (n_joints), NULL = ones.  MG_ERR_INVALID_ARGUMENT outside 1 <= n_joints <= 64 and
+ * 1 <= n_keyframes <= 8, for a capture without frames and for weights that are negative, non-finite or all 0.  PARITY UNPINNED, as
+ * for mg_dtw_distance_grids (formula and order of every sum: csrc/mg_dtw.hip). */
+int mg_keyframe_distances(mg_context *ctx, const double *clouds_dev, const int64_t *offsets, int64_t n_motions, int32_t n_joints,
+                          const double *keyframes_dev, int32_t n_keyframes, const double *weights, double *dist_dev);
+
+enum mg_segment_mode {
+    MG_SEGMENT_SINGLE = 0, /* extract_single_segments: one (argmin start distance, argmin end distance) pair per capture */
+    MG_SEGMENT_MULTI = 1   /* extract_segments: every instance of the start keyframe opens a search window */
+};
+
+/* The search over given distances start_dist_dev, end_dist_dev (offsets[n_motions] each, capture n's at offsets[n]).  Every
+ * arg-min is the FIRST index of the least value (argmin's strict `<`).
+ * MG_SEGMENT_SINGLE: start = argmin of the start distances, end = argmin of the end distances; always one pair, which may have
+ * end <= start (the reference's empty slice); threshold and min_segment_size are not used.
+ * MG_SEGMENT_MULTI (segmentation.py:61-80): m = min of the start distances; the instances are the frames with v <= m + threshold
+ * (that one addition, rounded as the host rounds it), in frame order; instance i's window ends at instance i + 1, the last one's
+ * at F_n - 1; a window with end - start < min_segment_size is dropped; otherwise e = start + (first index of the minimum of the
+ * end distances over [start, window end), 0 for a window without frames), and the segment is kept if e - start >
+ * min_segment_size (>= 0).
+ * Outputs, on the device: capture n's kept (start, end) int32 pairs, in order of start, at segments_dev + 2 * segment_offsets[n];
+ * counts_dev[n] their number.  segment_offsets: HOST array of n_motions + 1 entries; capture n needs room for 1 pair
+ * (MG_SEGMENT_SINGLE) or F_n / (min_segment_size + 1) + 1 pairs (the segments are disjoint and longer than min_segment_size),
+ * MG_ERR_INVALID_ARGUMENT with less.  MG_ERR_UNSUPPORTED from F_n or n_motions of 2^31 on.  The results are the reference's for
+ * the same distances, do not depend on the batch, and two calls give identical bytes. */
+int mg_segment_search(mg_context *ctx, const double *start_dist_dev, const double *end_dist_dev, const int64_t *offsets,
+                      int64_t n_motions, int32_t mode, double threshold, int32_t min_segment_size, const int64_t *segment_offsets,
+                      int32_t *segments_dev, int32_t *counts_dev);
+
 /* ---- host-pointer convenience variants (H2D, launch, D2H, synchronise) ---------------- */
 int mg_back_project_frames_host(mg_primitive *prim, const mg_time_grid *grid, const void *latents,
                                 int latent_dtype, int64_t n_samples, int64_t ld, float *frames, int path);

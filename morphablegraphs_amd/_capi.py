@@ -85,6 +85,7 @@ EXPORTED_SYMBOLS = [
     "mg_cluster_tree_create_kd", "mg_kmeans_segments", "mg_gmm_em_fit",
     "mg_spline_fit_batch", "mg_pca_fit", "mg_pca_project", "mg_pca_backproject",
     "mg_dtw_distance_grids", "mg_dtw_paths", "mg_warp_motions",
+    "mg_keyframe_distances", "mg_segment_search",
 ]
 
 
@@ -354,6 +355,8 @@ def load_library(path=None):
         "mg_dtw_distance_grids": [vp, vp, i32, vp, vp, i64, i32, vp, vp],
         "mg_dtw_paths": [vp, vp, i32, vp, i64, vp, vp, vp, vp, vp],
         "mg_warp_motions": [vp, vp, vp, i64, i32, vp, i32, vp],
+        "mg_keyframe_distances": [vp, vp, vp, i64, i32, vp, i32, vp, vp],
+        "mg_segment_search": [vp, vp, vp, vp, i64, i32, dbl, i32, vp, vp, vp],
     }
     for name, argtypes in sigs.items():
         fn = getattr(lib, name)
@@ -1032,6 +1035,33 @@ def warp_motions(ctx, frames_dev, offsets, n_dim, warping_dev, n_ref_frames, war
     off = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
     _check(ctx.lib.mg_warp_motions(ctx.handle, _dev_ptr(frames_dev), _host_ptr(off), len(off) - 1, int(n_dim), _dev_ptr(warping_dev), int(n_ref_frames),
                                    _dev_ptr(warped_dev)))
+
+
+MG_SEGMENT_SINGLE, MG_SEGMENT_MULTI = 0, 1             # enum mg_segment_mode (include/mg_hip.h)
+MG_SEGMENT_MAX_KEYFRAMES, MG_SEGMENT_MAX_JOINTS = 8, 64   # mg_segment.hip (include/mg_hip.h)
+
+
+def keyframe_distances(ctx, clouds_dev, offsets, n_joints, keyframes_dev, n_keyframes, weights, dist_dev):
+    """mg_keyframe_distances: dist_dev (n_keyframes, offsets[-1]) <- the distance of every frame of the ragged cloud table
+    clouds_dev (offsets[-1], n_joints, 3) to every keyframe of keyframes_dev (n_keyframes, n_joints, 3); offsets: (n_motions + 1)
+    host integers; weights: (n_joints) or None (ones)."""
+    off = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+    w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+    if w is not None and len(w) != int(n_joints):
+        raise ValueError("%d weights for %d joints" % (len(w), int(n_joints)))
+    _check(ctx.lib.mg_keyframe_distances(ctx.handle, _dev_ptr(clouds_dev), _host_ptr(off), len(off) - 1, int(n_joints), _dev_ptr(keyframes_dev),
+                                         int(n_keyframes), None if w is None else _host_ptr(w), _dev_ptr(dist_dev)))
+
+
+def segment_search(ctx, start_dist_dev, end_dist_dev, offsets, mode, threshold, min_segment_size, segment_offsets, segments_dev, counts_dev):
+    """mg_segment_search: the kept (start, end) int32 pairs of every motion into segments_dev (motion n's at pair
+    segment_offsets[n]) and their numbers into counts_dev; offsets, segment_offsets: (n_motions + 1) host integers."""
+    off = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+    seg_off = np.ascontiguousarray(segment_offsets, dtype=np.int64).reshape(-1)
+    if len(seg_off) != len(off):
+        raise ValueError("%d segment offsets for %d offsets" % (len(seg_off), len(off)))
+    _check(ctx.lib.mg_segment_search(ctx.handle, _dev_ptr(start_dist_dev), _dev_ptr(end_dist_dev), _host_ptr(off), len(off) - 1, int(mode),
+                                     float(threshold), int(min_segment_size), _host_ptr(seg_off), _dev_ptr(segments_dev), _dev_ptr(counts_dev)))
 
 
 class TrackPlan(object):

@@ -30,30 +30,13 @@
 //
 // Nothing depends on the schedule: no float atomics, no grid barriers, every sum in an order the shapes fix, so a motion gives
 // the same bits alone or in any batch.  Limits are answered before any of these kernels is launched.
-#include "mg_internal.h"
+#include "mg_dtw_device.h"
 
 #include <algorithm>
-#include <cmath>
 
 #define DTW_MAX_FRAMES 1024
-#define DTW_MAX_JOINTS 64
 #define DTW_TILE 16
-#define DTW_BLOCK 256
 #define DTW_CODE_LDS_BYTES (96 * 1024)
-
-#define DTW_REQUIRE(cond, code, ...)   \
-    do {                               \
-        if (!(cond)) {                 \
-            mg_set_error(__VA_ARGS__); \
-            return (code);             \
-        }                              \
-    } while (0)
-
-// ---- flag[0] = 1 if any of x[0 .. n) is not finite (every writer stores the same value) ------------------------------------
-__global__ __launch_bounds__(DTW_BLOCK) void dtw_nonfinite_kernel(const double *__restrict__ x, int64_t n, int32_t *__restrict__ flag) {
-    const int64_t e = (int64_t)blockIdx.x * DTW_BLOCK + threadIdx.x;
-    if (e < n && !isfinite(x[e])) flag[0] = 1;
-}
 
 __global__ __launch_bounds__(DTW_BLOCK) void dtw_distance_grids_kernel(const double *__restrict__ A, int32_t Fr, const double *__restrict__ B,
                                                                        const int64_t *__restrict__ off, int32_t J, const double *__restrict__ w,
@@ -75,45 +58,17 @@ __global__ __launch_bounds__(DTW_BLOCK) void dtw_distance_grids_kernel(const dou
     if (tid < J) sW[tid] = w[tid];
     __syncthreads();
     if (tid < 2 * DTW_TILE) {
-        const double *p = (tid < DTW_TILE ? sA : sB) + (tid & (DTW_TILE - 1)) * stride;
-        double sx = 0.0, sz = 0.0;
-        for (int k = 0; k < J; k++) {
-            sx = sx + sW[k] * p[3 * k];
-            sz = sz + sW[k] * p[3 * k + 2];
-        }
-        sums[2 * tid] = sx, sums[2 * tid + 1] = sz;
+        dtw_cloud_sums((tid < DTW_TILE ? sA : sB) + (tid & (DTW_TILE - 1)) * stride, sW, J, &sums[2 * tid], &sums[2 * tid + 1]);
     } else if (tid == 2 * DTW_TILE) {
-        double s = 0.0;
-        for (int k = 0; k < J; k++) s = s + sW[k];
-        sums[4 * DTW_TILE] = s;
+        sums[4 * DTW_TILE] = dtw_weight_sum(sW, J);
     }
     __syncthreads();
     const int r = tid >> 4, c = tid & 15;
     const int i = ti * DTW_TILE + r, j = tj * DTW_TILE + c;
     const double *a = sA + r * stride, *b = sB + c * stride;
     const double sax = sums[2 * r], saz = sums[2 * r + 1], sbx = sums[2 * (DTW_TILE + c)], sbz = sums[2 * (DTW_TILE + c) + 1], sw = sums[4 * DTW_TILE];
-    double num = 0.0, den = 0.0;
-    for (int k = 0; k < J; k++) {
-        const double ax = a[3 * k], az = a[3 * k + 2], bx = b[3 * k], bz = b[3 * k + 2], wk = sW[k];
-        num = num + wk * (ax * bz - bx * az);
-        den = den + wk * (ax * bx + az * bz);
-    }
-    num = num - (sax * sbz - sbx * saz) / sw;
-    den = den - (sax * sbx + saz * sbz) / sw;
-    const double theta = atan2(num, den);
-    double sn, cs;
-    sincos(theta, &sn, &cs);
-    const double ox = ((sax - sbx * cs) - sbz * sn) / sw;
-    const double oz = ((saz + sbx * sn) - sbz * cs) / sw;
-    double total = 0.0;
-    for (int k = 0; k < J; k++) {
-        const double bx = b[3 * k], bz = b[3 * k + 2];
-        const double dx = a[3 * k] - ((bx * cs + bz * sn) + ox);
-        const double dy = a[3 * k + 1] - b[3 * k + 1];
-        const double dz = a[3 * k + 2] - (((-bx) * sn + bz * cs) + oz);
-        total = total + sqrt((dx * dx + dy * dy) + dz * dz);
-    }
-    if (i < Fr && j < F) S[(int64_t)Fr * b0 + (int64_t)i * F + j] = total / (double)J;
+    const double cell = dtw_cell(a, b, sW, J, sax, saz, sbx, sbz, sw);
+    if (i < Fr && j < F) S[(int64_t)Fr * b0 + (int64_t)i * F + j] = cell;
 }
 
 __global__ __launch_bounds__(DTW_MAX_FRAMES) void dtw_paths_kernel(const double *__restrict__ S, int32_t Fr, const int64_t *__restrict__ off,
@@ -226,43 +181,6 @@ static int dtw_check_offsets(const char *who, const int64_t *offsets, int64_t n_
     }
     *f_max = (int32_t)longest;
     return MG_OK;
-}
-
-// a device block for one call: the offsets, 64 doubles, a 256-byte flag area, then `extra` bytes
-struct dtw_block {
-    char *base = nullptr;
-    int64_t *off = nullptr;
-    double *w = nullptr;
-    int32_t *flag = nullptr;
-    char *extra = nullptr;
-    ~dtw_block() { if (base) (void)hipFree(base); }
-};
-
-static int dtw_block_create(const char *who, mg_context *ctx, dtw_block *b, const int64_t *offsets, int64_t n_motions, const double *weights, int32_t n_w,
-                            size_t extra) {
-    const size_t o_w = (((size_t)n_motions + 1) * 8 + 255) & ~(size_t)255, o_flag = o_w + 512, o_extra = o_flag + 256, total = o_extra + extra;
-    if (hipMalloc(&b->base, total) != hipSuccess) {
-        (void)hipGetLastError();
-        b->base = nullptr;
-        mg_set_error("%s: cannot allocate %zu bytes of device memory", who, total);
-        return MG_ERR_OUT_OF_MEMORY;
-    }
-    b->off = (int64_t *)b->base, b->w = (double *)(b->base + o_w), b->flag = (int32_t *)(b->base + o_flag), b->extra = b->base + o_extra;
-    MG_HIP_CHECK(hipMemcpyAsync(b->off, offsets, ((size_t)n_motions + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-    if (n_w > 0) MG_HIP_CHECK(hipMemcpyAsync(b->w, weights, (size_t)n_w * 8, hipMemcpyHostToDevice, ctx->stream));
-    MG_HIP_CHECK(hipMemsetAsync(b->flag, 0, 256, ctx->stream));
-    return MG_OK;
-}
-
-static int dtw_flag_after(mg_context *ctx, const dtw_block &b, int32_t *flag) {
-    MG_HIP_CHECK(hipGetLastError());
-    MG_HIP_CHECK(hipMemcpyAsync(flag, b.flag, 4, hipMemcpyDeviceToHost, ctx->stream));
-    MG_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    return MG_OK;
-}
-
-static void dtw_launch_nonfinite(mg_context *ctx, const double *x, int64_t n, int32_t *flag) {
-    if (n > 0) hipLaunchKernelGGL(dtw_nonfinite_kernel, dim3((unsigned)((n + DTW_BLOCK - 1) / DTW_BLOCK)), dim3(DTW_BLOCK), 0, ctx->stream, x, n, flag);
 }
 
 extern "C" int mg_dtw_distance_grids(mg_context *ctx, const double *ref_cloud_dev, int32_t n_ref_frames, const double *clouds_dev, const int64_t *offsets,

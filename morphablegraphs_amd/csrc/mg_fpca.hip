@@ -17,6 +17,9 @@
 // rotation that makes the pair orthogonal if |c| > tol sqrt(a b), tol = eps sqrt(L).  The host reads the sweep's rotation
 // count (an integer counter) once per sweep and stops at zero.  Every sum runs in an order fixed by the shapes alone, the
 // schedule does not depend on the device: the same input gives the same bits.  No float atomics, no grid barriers.
+// G takes every rotation of every sweep, so its orthonormality drifts with their number (7e-14 at m = 255 after 13 sweeps);
+// after the last sweep one Newton-Schulz step G <- G - (G G^T G - G) / 2 on the GEMM kernel brings it back to rounding level.
+// The step costs two m x m x m products and two more m x m buffers next to G for the length of the call (3 x 128 MiB at m = 4096).
 #include "mg_internal.h"
 
 #include <algorithm>
@@ -220,6 +223,12 @@ __global__ __launch_bounds__(FP_BLOCK) void fpca_jacobi_round_kernel(double *__r
     if (tid == 0) atomicAdd(counter, 1);
 }
 
+// G <- G - (Y - G) / 2 with Y = (G G^T) G: Y - G is the small correction, subtracted from G in one rounding
+__global__ __launch_bounds__(FP_BLOCK) void fpca_polish_kernel(double *__restrict__ G, const double *__restrict__ Y, int64_t count) {
+    const int64_t e = (int64_t)blockIdx.x * FP_BLOCK + threadIdx.x;
+    if (e < count) G[e] = G[e] - 0.5 * (Y[e] - G[e]);
+}
+
 // sum of squares of a row on the host, in blocks of 64 (an order fixed by the length alone)
 static double fp_row_norm2(const double *w, int64_t L) {
     double total = 0.0;
@@ -241,7 +250,7 @@ extern "C" int mg_pca_fit(mg_context *ctx, const double *a_dev, int64_t n, int64
     FP_REQUIRE(L <= FP_MAX_LONG, MG_ERR_UNSUPPORTED, "mg_pca_fit: max(n, p) = %lld, at most %lld", (long long)L, (long long)FP_MAX_LONG);
     const bool wide = n <= p;           // rotate the rows of the centred matrix itself
     MG_HIP_CHECK(hipSetDevice(ctx->device));
-    const size_t wbytes = (size_t)n * p * 8, gbytes = wide ? 0 : (size_t)m * m * 8;
+    const size_t wbytes = (size_t)n * p * 8, g1 = wide ? 0 : (((size_t)m * m * 8 + 255) & ~(size_t)255), gbytes = 3 * g1;   // G, G G^T, (G G^T) G
     const size_t o_mean = (wbytes + 255) & ~(size_t)255, o_g = o_mean + (((size_t)p * 8 + 255) & ~(size_t)255);
     const size_t o_cnt = o_g + ((gbytes + 255) & ~(size_t)255), total = o_cnt + 256;
     char *base = nullptr;
@@ -286,6 +295,13 @@ extern "C" int mg_pca_fit(mg_context *ctx, const double *a_dev, int64_t n, int64
                 }
             }
             if (rc != MG_OK) break;
+            if (G) {
+                double *T = (double *)((char *)G + g1), *Y = (double *)((char *)G + 2 * g1);
+                if ((rc = fp_gemm(ctx, G, G, nullptr, T, 1, 0, 0, 0, m, m, m, m, 1, m, m)) != MG_OK) break;     // T = G G^T
+                if ((rc = fp_gemm(ctx, T, G, nullptr, Y, 1, 0, 0, 0, m, m, m, m, m, 1, m)) != MG_OK) break;     // Y = T G
+                hipLaunchKernelGGL(fpca_polish_kernel, dim3((unsigned)((m * m + FP_BLOCK - 1) / FP_BLOCK)), dim3(FP_BLOCK), 0, ctx->stream, G, Y, m * m);
+                if (fail(hipGetLastError(), "polish launch")) break;
+            }
         } else {
             st = 1;
         }

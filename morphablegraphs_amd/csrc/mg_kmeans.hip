@@ -530,7 +530,8 @@ extern "C" int mg_kmeans_segments(mg_context *ctx, const double *points_dev, int
         MG_KM_TRY(hipGetLastError());
     }
     MG_KM_TRY(hipMemsetAsync(a.labels, 0xFF, (size_t)n_init * n_pos * 4, st));   // label -1: every label of iteration 0 changes
-    if (lds > 64 * 1024) MG_KM_TRY(hipFuncSetAttribute((const void *)mg_kmeans_lloyd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    // what this call needs, not the whole 160 KiB: __syncthreads_count keeps a static word in the LDS, and static + dynamic past 160 KiB is refused
+    if (lds > 64 * 1024) MG_KM_TRY(hipFuncSetAttribute((const void *)mg_kmeans_lloyd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     active = tiles;
     // every unit needs at most max_iter iterations and one final pass
     while (launches < max_iter + 1 && !active.empty()) {
@@ -567,5 +568,6 @@ done:
 #undef MG_KM_TRY
     (void)hipStreamSynchronize(st);
     (void)hipFree(base);
+    if (rc != MG_OK) (void)hipGetLastError();   // a failed call leaves no error behind for the next one's hipGetLastError
     return rc;
 }

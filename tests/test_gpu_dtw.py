@@ -257,7 +257,7 @@ def test_limits_and_misuse(ctx):
         assert status_of(lambda: _capi.dtw_distance_grids(ctx, big, 4, big, off(4), J, [1.0, -1.0, 1.0], out)) == _capi.MG_ERR_INVALID_ARGUMENT
         with pytest.raises(ValueError):
             _capi.dtw_distance_grids(ctx, big, 4, big, off(4), J, [1.0, 1.0], out)
-        grids(1024, off(1024, 1), 64)       # the limits themselves are supported
+        grids(1024, off(1024, 1), 64)       # the limits themselves are supported (their values: test_gpu_construction_shapes.py)
         # a NaN in the clouds, an infinity in a grid
         bad = np.zeros((9, J, 3))
         bad[7, 1, 2] = np.nan

@@ -204,7 +204,7 @@ def test_limits_and_misuse(ctx):
         with pytest.raises(ValueError):
             kd(off(4), J, 2, [1.0, 1.0])
         kd(off())                 # no motions: MG_OK, nothing to do
-        kd(off(30, 10), 64, 8)    # the limits themselves are supported
+        kd(off(30, 10), 64, 8)    # the limits themselves are supported (their values: test_gpu_construction_shapes.py)
         search = lambda o, so, mode=seg.MULTI, t=1.0, m=1: _capi.segment_search(ctx, big, big, o, mode, t, m, so, ints, cnt)      # noqa: E731
         assert status_of(lambda: search(off(10), off(6), 2)) == invalid
         assert status_of(lambda: search(off(10), off(6), seg.MULTI, np.nan)) == invalid

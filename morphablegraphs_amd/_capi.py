@@ -179,6 +179,10 @@ class Skeleton(object):
     def index(self, joint):
         return int(joint) if isinstance(joint, (int, np.integer)) else self.names.index(joint)
 
+    def indices(self, joints):
+        """The joints (names or indices) as the int32 vector mg_joint_positions reads."""
+        return np.ascontiguousarray([self.index(j) for j in joints], dtype=np.int32)
+
     def chain(self, joint):
         out, j = [], self.index(joint)
         while j >= 0:
@@ -510,6 +514,10 @@ class Context(object):
         _check(self.lib.mg_device_placement_info(self.handle, _dev_ptr(buf), info, C.byref(tbps)))
         return {"region": bool(info[0]), "ratio": float(info[1]), "pattern_us": float(info[2]), "fast": bool(info[3]), "pattern_TBps": float(tbps.value)}
 
+    def buffers(self):
+        """with ctx.buffers() as bufs: the device buffers of one call (DeviceBuffers), freed on the way out."""
+        return DeviceBuffers(self)
+
     def upload(self, arr):
         arr = np.ascontiguousarray(arr)
         buf = DeviceBuffer(self, arr.nbytes)
@@ -548,16 +556,18 @@ class Context(object):
         F = np.ascontiguousarray(frames, dtype=np.float64)
         if F.ndim != 2:
             raise ValueError("frames must be (n_frames, n_dim)")
-        idx = np.ascontiguousarray([skeleton.index(j) for j in joints], dtype=np.int32)
-        out = np.empty((F.shape[0], len(idx), 3), dtype=np.float64)
-        d_f, d_o = self.upload(F), self.malloc(max(out.nbytes, 8))
-        try:
-            d = skeleton.desc()
-            _check(self.lib.mg_joint_positions(self.handle, C.byref(d), idx.ctypes.data_as(C.c_void_p), len(idx), d_f.ptr, F.shape[0], F.shape[1], d_o.ptr))
-            return self.download(d_o, out.shape, np.float64)
-        finally:
-            d_f.free()
-            d_o.free()
+        idx = skeleton.indices(joints)
+        with self.buffers() as bufs:
+            d_f, d_o = bufs.upload(F), bufs.malloc(8 * F.shape[0] * len(idx) * 3)
+            self.joint_positions_dev(skeleton, idx, d_f, F.shape[0], F.shape[1], d_o)
+            return self.download(d_o, (F.shape[0], len(idx), 3), np.float64)
+
+    def joint_positions_dev(self, skeleton, joint_indices, frames_dev, n_frames, n_dim, out_dev):
+        """mg_joint_positions on device tables: out_dev (n_frames, len(joint_indices), 3) float64 <- frames_dev (n_frames, n_dim)
+        float64; joint_indices: skeleton.indices(joints)."""
+        d = skeleton.desc()
+        _check(self.lib.mg_joint_positions(self.handle, C.byref(d), _host_ptr(joint_indices), len(joint_indices), _dev_ptr(frames_dev),
+                                           int(n_frames), int(n_dim), _dev_ptr(out_dev)))
 
     def argmin_first(self, values_dev, n, dtype=np.float32):
         idx, val = C.c_int64(), C.c_double()
@@ -601,10 +611,65 @@ class DeviceBuffer(object):
             pass
 
 
+class DeviceBuffers(object):
+    """The device buffers of one call (Context.buffers()): leaving the `with` block frees every buffer upload and malloc
+    handed out, whether the body returned or raised, except those release() gave to the caller."""
+
+    def __init__(self, ctx):
+        self.ctx, self.bufs = ctx, []
+
+    def upload(self, arr):
+        self.bufs.append(self.ctx.upload(np.ascontiguousarray(arr)))
+        return self.bufs[-1]
+
+    def malloc(self, nbytes):
+        self.bufs.append(self.ctx.malloc(max(int(nbytes), 8)))     # an empty table still has an address
+        return self.bufs[-1]
+
+    def release(self, buf):
+        """buf outlives the block: whoever takes it frees it."""
+        self.bufs.remove(buf)
+        return buf
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        for b in self.bufs:
+            b.free()
+
+
+def default_context(ctx):
+    """ctx, or the process's shared context of device 0 for None."""
+    if ctx is not None:
+        return ctx
+    from .motion_primitive import get_context
+    return get_context(0)
+
+
 def _dev_ptr(x):
     if isinstance(x, DeviceBuffer):
         return x.ptr
     return C.c_void_p(int(x))
+
+
+def _host_ptr(a):
+    return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def _offsets_arg(offsets):
+    """An offsets table as the contiguous int64 vector the library reads."""
+    return np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+
+
+def _weights_arg(weights, n_joints):
+    """Joint weights as a contiguous float64 vector of length n_joints, or None (ones)."""
+    if weights is None:
+        return None
+    w = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+    if len(w) != int(n_joints):
+        raise ValueError("%d weights for %d joints" % (len(w), int(n_joints)))
+    return w
 
 
 class TimeGrid(object):
@@ -915,19 +980,15 @@ def kmeans_segments(ctx, points_dev, n_rows, dim, seg_begin, rows, k, n_init=1, 
     centres = np.zeros((max(S, 1), int(k), int(dim)), dtype=np.float64)
     inertia = np.zeros(max(S, 1), dtype=np.float64)
     n_iter = np.zeros(max(S, 1), dtype=np.int32)
-    vp = C.c_void_p
     ini = None if init is None else np.ascontiguousarray(init, dtype=np.float64)
     if ini is not None and ini.shape != (S, int(k), int(dim)):
         raise ValueError("init must be (n_segments, k, dim)")
     ids = None if node_ids is None else np.ascontiguousarray(node_ids, dtype=np.uint64)
     if ids is not None and ids.shape != (S,):
         raise ValueError("node_ids must have one entry per segment")
-
-    def ptr(a):
-        return None if a is None else a.ctypes.data_as(vp)
-    _check(ctx.lib.mg_kmeans_segments(ctx.handle, _dev_ptr(points_dev), int(n_rows), int(dim), int(max(S, 0)), ptr(sb), ptr(r), int(k), int(n_init),
-                                      ptr(ini), ptr(ids), int(seed) & 0xFFFFFFFFFFFFFFFF, int(max_iter), float(tol), ptr(labels), ptr(centres),
-                                      ptr(inertia), ptr(n_iter)))
+    _check(ctx.lib.mg_kmeans_segments(ctx.handle, _dev_ptr(points_dev), int(n_rows), int(dim), int(max(S, 0)), _host_ptr(sb), _host_ptr(r), int(k),
+                                      int(n_init), _host_ptr(ini), _host_ptr(ids), int(seed) & 0xFFFFFFFFFFFFFFFF, int(max_iter), float(tol),
+                                      _host_ptr(labels), _host_ptr(centres), _host_ptr(inertia), _host_ptr(n_iter)))
     return labels[:len(r)], centres[:S], inertia[:S], n_iter[:S]
 
 
@@ -951,12 +1012,9 @@ def gmm_em_fit(ctx, points_dev, n, dim, n_comp, labels, tol=1e-3, reg_covar=1e-6
     status = np.zeros(max(F, 1), dtype=np.int32)
     score = np.zeros(max(F, 1))
     lout = np.zeros((max(F, 1), n), dtype=np.int32)
-
-    def ptr(a):
-        return a.ctypes.data_as(C.c_void_p)
-    _check(ctx.lib.mg_gmm_em_fit(ctx.handle, _dev_ptr(points_dev), n, dim, F, ptr(K) if F else None, ptr(lab) if F else None, float(tol),
-                                 float(reg_covar), int(max_iter), ptr(w), ptr(mu), ptr(cov), ptr(prec), ptr(lbs), ptr(n_iter), ptr(status),
-                                 ptr(score), ptr(lout)))
+    _check(ctx.lib.mg_gmm_em_fit(ctx.handle, _dev_ptr(points_dev), n, dim, F, _host_ptr(K) if F else None, _host_ptr(lab) if F else None, float(tol),
+                                 float(reg_covar), int(max_iter), _host_ptr(w), _host_ptr(mu), _host_ptr(cov), _host_ptr(prec), _host_ptr(lbs),
+                                 _host_ptr(n_iter), _host_ptr(status), _host_ptr(score), _host_ptr(lout)))
     out, c0 = [], 0
     for f in range(F):
         k = int(K[f])
@@ -985,10 +1043,8 @@ def pca_fit(ctx, a_dev, n, p, centred_dev, centre=True):
     m = max(min(n, p), 1)
     mean, sv, vt = np.zeros(max(p, 1)), np.zeros(m), np.zeros((m, max(p, 1)))
     sweeps, status = C.c_int32(0), C.c_int32(0)
-
-    def ptr(a):
-        return a.ctypes.data_as(C.c_void_p)
-    _check(ctx.lib.mg_pca_fit(ctx.handle, _dev_ptr(a_dev), n, p, 1 if centre else 0, _dev_ptr(centred_dev), ptr(mean), ptr(sv), ptr(vt), C.byref(sweeps), C.byref(status)))
+    _check(ctx.lib.mg_pca_fit(ctx.handle, _dev_ptr(a_dev), n, p, 1 if centre else 0, _dev_ptr(centred_dev), _host_ptr(mean), _host_ptr(sv), _host_ptr(vt),
+                              C.byref(sweeps), C.byref(status)))
     return {"mean": mean, "singular_values": sv, "vt": vt, "n_sweeps": int(sweeps.value), "status": int(status.value)}
 
 
@@ -1006,25 +1062,18 @@ def pca_backproject(ctx, low_dev, vt_dev, mean_dev, n, p, l, high_dev):
 MG_DTW_MAX_FRAMES, MG_DTW_MAX_JOINTS = 1024, 64   # mg_dtw.hip (include/mg_hip.h)
 
 
-def _host_ptr(a):
-    return a.ctypes.data_as(C.c_void_p)
-
-
 def dtw_distance_grids(ctx, ref_cloud_dev, n_ref_frames, clouds_dev, offsets, n_joints, weights, grids_dev):
     """mg_dtw_distance_grids: grids_dev <- S[n] (n_ref_frames, F_n) of every motion of the ragged cloud table clouds_dev
     (offsets[-1], n_joints, 3); offsets: (n_motions + 1) host integers; weights: (n_joints) or None (ones)."""
-    off = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
-    w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
-    if w is not None and len(w) != int(n_joints):
-        raise ValueError("%d weights for %d joints" % (len(w), int(n_joints)))
+    off, w = _offsets_arg(offsets), _weights_arg(weights, n_joints)
     _check(ctx.lib.mg_dtw_distance_grids(ctx.handle, _dev_ptr(ref_cloud_dev), int(n_ref_frames), _dev_ptr(clouds_dev), _host_ptr(off), len(off) - 1,
-                                         int(n_joints), None if w is None else _host_ptr(w), _dev_ptr(grids_dev)))
+                                         int(n_joints), _host_ptr(w), _dev_ptr(grids_dev)))
 
 
 def dtw_paths(ctx, grids_dev, n_ref_frames, offsets, accumulated_dev, totals_dev, paths_dev, path_lengths_dev, warping_dev):
     """mg_dtw_paths: accumulated cost (accumulated_dev None: not stored), totals, paths, path lengths and warping functions
     of the grids in grids_dev; every output on the device, laid out as include/mg_hip.h says."""
-    off = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+    off = _offsets_arg(offsets)
     _check(ctx.lib.mg_dtw_paths(ctx.handle, _dev_ptr(grids_dev), int(n_ref_frames), _host_ptr(off), len(off) - 1,
                                 None if accumulated_dev is None else _dev_ptr(accumulated_dev), _dev_ptr(totals_dev), _dev_ptr(paths_dev),
                                 _dev_ptr(path_lengths_dev), _dev_ptr(warping_dev)))
@@ -1032,7 +1081,7 @@ def dtw_paths(ctx, grids_dev, n_ref_frames, offsets, accumulated_dev, totals_dev
 
 def warp_motions(ctx, frames_dev, offsets, n_dim, warping_dev, n_ref_frames, warped_dev):
     """mg_warp_motions: warped_dev (n_motions, n_ref_frames, n_dim) <- rows warping_dev[n][i] of motion n's frames."""
-    off = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+    off = _offsets_arg(offsets)
     _check(ctx.lib.mg_warp_motions(ctx.handle, _dev_ptr(frames_dev), _host_ptr(off), len(off) - 1, int(n_dim), _dev_ptr(warping_dev), int(n_ref_frames),
                                    _dev_ptr(warped_dev)))
 
@@ -1045,19 +1094,15 @@ def keyframe_distances(ctx, clouds_dev, offsets, n_joints, keyframes_dev, n_keyf
     """mg_keyframe_distances: dist_dev (n_keyframes, offsets[-1]) <- the distance of every frame of the ragged cloud table
     clouds_dev (offsets[-1], n_joints, 3) to every keyframe of keyframes_dev (n_keyframes, n_joints, 3); offsets: (n_motions + 1)
     host integers; weights: (n_joints) or None (ones)."""
-    off = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
-    w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
-    if w is not None and len(w) != int(n_joints):
-        raise ValueError("%d weights for %d joints" % (len(w), int(n_joints)))
+    off, w = _offsets_arg(offsets), _weights_arg(weights, n_joints)
     _check(ctx.lib.mg_keyframe_distances(ctx.handle, _dev_ptr(clouds_dev), _host_ptr(off), len(off) - 1, int(n_joints), _dev_ptr(keyframes_dev),
-                                         int(n_keyframes), None if w is None else _host_ptr(w), _dev_ptr(dist_dev)))
+                                         int(n_keyframes), _host_ptr(w), _dev_ptr(dist_dev)))
 
 
 def segment_search(ctx, start_dist_dev, end_dist_dev, offsets, mode, threshold, min_segment_size, segment_offsets, segments_dev, counts_dev):
     """mg_segment_search: the kept (start, end) int32 pairs of every motion into segments_dev (motion n's at pair
     segment_offsets[n]) and their numbers into counts_dev; offsets, segment_offsets: (n_motions + 1) host integers."""
-    off = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
-    seg_off = np.ascontiguousarray(segment_offsets, dtype=np.int64).reshape(-1)
+    off, seg_off = _offsets_arg(offsets), _offsets_arg(segment_offsets)
     if len(seg_off) != len(off):
         raise ValueError("%d segment offsets for %d offsets" % (len(seg_off), len(off)))
     _check(ctx.lib.mg_segment_search(ctx.handle, _dev_ptr(start_dist_dev), _dev_ptr(end_dist_dev), _host_ptr(off), len(off) - 1, int(mode),

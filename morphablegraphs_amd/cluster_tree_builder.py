@@ -88,13 +88,6 @@ class DeviceKMeans(object):
         self.points_dev = None
 
 
-def _context(ctx):
-    if ctx is not None:
-        return ctx
-    from .motion_primitive import get_context
-    return get_context(0)
-
-
 def _cluster_level(kmeans, k, members, node_ids):
     """One batched k-means over the nodes `members` (arrays of rows): per node the k groups of its rows by label, each in
     the parent's order (a stable partition)."""
@@ -188,7 +181,7 @@ def build_kd_cluster_tree(data, n_subdivisions=4, max_level=4, dim=None, use_kd_
     dim = min(data.shape[1], int(dim) if dim else data.shape[1])
     own = kmeans is None and k > 1 and n > k
     if own:
-        kmeans = DeviceKMeans(_context(ctx), data[:, :dim], k, seed, n_init, max_iter, tol, init)
+        kmeans = DeviceKMeans(_capi.default_context(ctx), data[:, :dim], k, seed, n_init, max_iter, tol, init)
     try:
         means, leaf, kids, wrappers = [], [], [], []
         level = [(np.arange(n, dtype=np.int64), 0, 0)]        # (rows, depth, node id), breadth first
@@ -290,7 +283,7 @@ def build_feature_cluster_tree(features, data=None, n_subdivisions=4, use_featur
     src = features if use_feature_mean else data
     own = kmeans is None and k > 1 and n > k
     if own:
-        kmeans = DeviceKMeans(_context(ctx), features, k, seed, n_init, max_iter, tol, init)
+        kmeans = DeviceKMeans(_capi.default_context(ctx), features, k, seed, n_init, max_iter, tol, init)
     try:
         indices, mean_of, kids = [], [], []
         level = [(None, np.arange(n, dtype=np.int64), 0, 0)]      # (indices or None, rows, depth, node id)
@@ -531,7 +524,7 @@ class HipClusterTreeBuilder(object):
             return self.ctx
         prim = motion_primitive.motion_primitive if hasattr(motion_primitive, "motion_primitive") else motion_primitive
         p = getattr(prim, "_prim", None)
-        return p.ctx if p is not None else _context(None)
+        return p.ctx if p is not None else _capi.default_context(None)
 
     # cluster_tree_builder.py:237-247
     def _build_tree(self, elementary_action_dir, cluster_file_name, data, motion_primitive):

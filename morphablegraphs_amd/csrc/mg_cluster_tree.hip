@@ -259,13 +259,7 @@ __global__ __launch_bounds__(MG_TREE_CHUNK *MG_TREE_WAVES) void mg_tree_search_k
 // ---------------------------------------------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------------------------------------------
-#define MG_TREE_REQUIRE(cond, ...)          \
-    do {                                    \
-        if (!(cond)) {                      \
-            mg_set_error(__VA_ARGS__);      \
-            return MG_ERR_INVALID_ARGUMENT; \
-        }                                   \
-    } while (0)
+#define MG_TREE_REQUIRE(cond, ...) MG_REQUIRE_AS(cond, MG_ERR_INVALID_ARGUMENT, __VA_ARGS__)
 
 static void mg_tree_free(mg_cluster_tree *t) {
     if (!t) return;

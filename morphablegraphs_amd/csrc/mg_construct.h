@@ -1,0 +1,73 @@
+// What the model-construction entry points share (mg_kmeans.hip, mg_gmm_em.hip, mg_fpca.hip, mg_dtw.hip, mg_segment.hip): the
+// workgroup sum of the kernels, the per-call device block and the check of an offsets table.  The rules of a call live here:
+//   * one hipMalloc per call, carved at 256-byte boundaries; one that fails is MG_ERR_OUT_OF_MEMORY with the size in the text;
+//   * the block is freed when the call returns, after the stream has drained: a copy into the caller's (or the call's own)
+//     host memory may still be in flight when an error cuts the call short;
+//   * a call that fails leaves no HIP error behind for the next one's hipGetLastError.
+#pragma once
+#include "mg_internal.h"
+
+// sum over the workgroup (BLOCK threads, red[BLOCK] in LDS) of one value per thread, in a fixed tree order
+template <int BLOCK>
+__device__ __forceinline__ double mg_block_sum(double v, double *red) {
+    red[threadIdx.x] = v;
+    __syncthreads();
+    for (int s = BLOCK / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+        __syncthreads();
+    }
+    const double r = red[0];
+    __syncthreads();
+    return r;
+}
+
+// The device block of one call: carve() every region, alloc(), at<T>(offset); the destructor does the rest.
+struct mg_workspace {
+    mg_context *ctx;
+    const char *who;     // the entry point, for the error text
+    char *base = nullptr;
+    size_t bytes = 0;
+
+    mg_workspace(mg_context *c, const char *w) : ctx(c), who(w) {}
+    mg_workspace(const mg_workspace &) = delete;
+    mg_workspace &operator=(const mg_workspace &) = delete;
+    ~mg_workspace() {
+        if (!base) return;
+        (void)hipStreamSynchronize(ctx->stream);
+        (void)hipFree(base);
+        (void)hipGetLastError();
+    }
+    static size_t align(size_t b) { return (b + 255) & ~(size_t)255; }
+    size_t carve(size_t b) {
+        const size_t o = bytes;
+        bytes += align(b);
+        return o;
+    }
+    int alloc() {
+        MG_HIP_CHECK(hipSetDevice(ctx->device));
+        if (hipMalloc(&base, bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            base = nullptr;
+            mg_set_error("%s: cannot allocate %zu bytes of device memory", who, bytes);
+            return MG_ERR_OUT_OF_MEMORY;
+        }
+        return MG_OK;
+    }
+    template <class T>
+    T *at(size_t offset) const { return (T *)(base + offset); }
+};
+
+// An offsets table of n_motions + 1 entries starts at 0 and rises, no motion longer than max_frames (`limit`: that bound in the
+// caller's words, code_too_long: its status); *longest: the longest motion.
+static inline int mg_check_offsets(const char *who, const int64_t *offsets, int64_t n_motions, int64_t max_frames, const char *limit, int code_too_long,
+                                   int64_t *longest) {
+    MG_REQUIRE_AS(offsets[0] == 0, MG_ERR_INVALID_ARGUMENT, "%s: offsets[0] = %lld, not 0", who, (long long)offsets[0]);
+    *longest = 0;
+    for (int64_t n = 0; n < n_motions; n++) {
+        const int64_t f = offsets[n + 1] - offsets[n];
+        MG_REQUIRE_AS(f >= 1, MG_ERR_INVALID_ARGUMENT, "%s: motion %lld has %lld frames (offsets must rise)", who, (long long)n, (long long)f);
+        MG_REQUIRE_AS(f <= max_frames, code_too_long, "%s: motion %lld has %lld frames (%s)", who, (long long)n, (long long)f, limit);
+        if (f > *longest) *longest = f;
+    }
+    return MG_OK;
+}

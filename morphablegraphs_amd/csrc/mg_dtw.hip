@@ -166,43 +166,34 @@ __global__ __launch_bounds__(DTW_BLOCK) void dtw_warp_kernel(const double *__res
 }
 
 // ---- host --------------------------------------------------------------------------------------------------------------------
+#define DTW_STR2(x) #x
+#define DTW_STR(x) DTW_STR2(x)
+
 static int dtw_check_offsets(const char *who, const int64_t *offsets, int64_t n_motions, int32_t n_ref_frames, int32_t *f_max) {
-    DTW_REQUIRE(n_ref_frames >= 1, MG_ERR_INVALID_ARGUMENT, "%s: %d reference frames", who, n_ref_frames);
-    DTW_REQUIRE(n_ref_frames <= DTW_MAX_FRAMES, MG_ERR_UNSUPPORTED, "%s: %d reference frames (at most %d)", who, n_ref_frames, DTW_MAX_FRAMES);
-    DTW_REQUIRE(n_motions < ((int64_t)1 << 24), MG_ERR_UNSUPPORTED, "%s: %lld motions (fewer than 2^24)", who, (long long)n_motions);
-    DTW_REQUIRE(offsets[0] == 0, MG_ERR_INVALID_ARGUMENT, "%s: offsets[0] = %lld, not 0", who, (long long)offsets[0]);
+    MG_REQUIRE_AS(n_ref_frames >= 1, MG_ERR_INVALID_ARGUMENT, "%s: %d reference frames", who, n_ref_frames);
+    MG_REQUIRE_AS(n_ref_frames <= DTW_MAX_FRAMES, MG_ERR_UNSUPPORTED, "%s: %d reference frames (at most %d)", who, n_ref_frames, DTW_MAX_FRAMES);
+    MG_REQUIRE_AS(n_motions < ((int64_t)1 << 24), MG_ERR_UNSUPPORTED, "%s: %lld motions (fewer than 2^24)", who, (long long)n_motions);
     int64_t longest = 0;
-    for (int64_t n = 0; n < n_motions; n++) {
-        const int64_t f = offsets[n + 1] - offsets[n];
-        DTW_REQUIRE(f >= 1, MG_ERR_INVALID_ARGUMENT, "%s: motion %lld has %lld frames (offsets must rise)", who, (long long)n, (long long)f);
-        DTW_REQUIRE(f <= DTW_MAX_FRAMES, MG_ERR_UNSUPPORTED, "%s: motion %lld has %lld frames (at most %d)", who, (long long)n, (long long)f,
-                    DTW_MAX_FRAMES);
-        longest = std::max(longest, f);
-    }
+    const int rc = mg_check_offsets(who, offsets, n_motions, DTW_MAX_FRAMES, "at most " DTW_STR(DTW_MAX_FRAMES), MG_ERR_UNSUPPORTED, &longest);
     *f_max = (int32_t)longest;
-    return MG_OK;
+    return rc;
 }
 
 extern "C" int mg_dtw_distance_grids(mg_context *ctx, const double *ref_cloud_dev, int32_t n_ref_frames, const double *clouds_dev, const int64_t *offsets,
                                      int64_t n_motions, int32_t n_joints, const double *weights, double *grids_dev) {
-    DTW_REQUIRE(ctx && ref_cloud_dev && offsets, MG_ERR_INVALID_ARGUMENT, "mg_dtw_distance_grids: NULL argument");
-    DTW_REQUIRE(n_motions >= 0 && n_joints >= 1, MG_ERR_INVALID_ARGUMENT, "mg_dtw_distance_grids: n_motions = %lld, n_joints = %d", (long long)n_motions,
-                n_joints);
-    DTW_REQUIRE(n_joints <= DTW_MAX_JOINTS, MG_ERR_UNSUPPORTED, "mg_dtw_distance_grids: %d joints (at most %d)", n_joints, DTW_MAX_JOINTS);
+    MG_REQUIRE_AS(ctx && ref_cloud_dev && offsets, MG_ERR_INVALID_ARGUMENT, "mg_dtw_distance_grids: NULL argument");
+    MG_REQUIRE_AS(n_motions >= 0 && n_joints >= 1, MG_ERR_INVALID_ARGUMENT, "mg_dtw_distance_grids: n_motions = %lld, n_joints = %d", (long long)n_motions,
+                  n_joints);
+    MG_REQUIRE_AS(n_joints <= DTW_MAX_JOINTS, MG_ERR_UNSUPPORTED, "mg_dtw_distance_grids: %d joints (at most %d)", n_joints, DTW_MAX_JOINTS);
     int32_t f_max = 0;
     const int rc = dtw_check_offsets("mg_dtw_distance_grids", offsets, n_motions, n_ref_frames, &f_max);
     if (rc != MG_OK || n_motions == 0) return rc;
-    DTW_REQUIRE(clouds_dev && grids_dev, MG_ERR_INVALID_ARGUMENT, "mg_dtw_distance_grids: NULL argument");
-    double ones[DTW_MAX_JOINTS], wsum = 0.0;
-    for (int k = 0; k < n_joints; k++) {
-        ones[k] = weights ? weights[k] : 1.0;
-        DTW_REQUIRE(std::isfinite(ones[k]) && ones[k] >= 0.0, MG_ERR_INVALID_ARGUMENT, "mg_dtw_distance_grids: weight %d is %g", k, ones[k]);
-        wsum += ones[k];
-    }
-    DTW_REQUIRE(wsum > 0.0, MG_ERR_INVALID_ARGUMENT, "mg_dtw_distance_grids: the weights add up to 0");
-    MG_HIP_CHECK(hipSetDevice(ctx->device));
-    dtw_block blk;
-    const int rb = dtw_block_create("mg_dtw_distance_grids", ctx, &blk, offsets, n_motions, ones, n_joints, 0);
+    MG_REQUIRE_AS(clouds_dev && grids_dev, MG_ERR_INVALID_ARGUMENT, "mg_dtw_distance_grids: NULL argument");
+    double ones[DTW_MAX_JOINTS];
+    const int rw = dtw_weights("mg_dtw_distance_grids", weights, n_joints, ones);
+    if (rw != MG_OK) return rw;
+    dtw_block blk(ctx, "mg_dtw_distance_grids");
+    const int rb = dtw_block_create(&blk, offsets, n_motions, ones, n_joints, 0);
     if (rb != MG_OK) return rb;
     const int64_t row_len = 3 * (int64_t)n_joints;
     dtw_launch_nonfinite(ctx, ref_cloud_dev, n_ref_frames * row_len, blk.flag);
@@ -210,7 +201,7 @@ extern "C" int mg_dtw_distance_grids(mg_context *ctx, const double *ref_cloud_de
     int32_t flag = 0;
     const int rf = dtw_flag_after(ctx, blk, &flag);
     if (rf != MG_OK) return rf;
-    DTW_REQUIRE(!flag, MG_ERR_INVALID_ARGUMENT, "mg_dtw_distance_grids: the point clouds hold non-finite values");
+    MG_REQUIRE_AS(!flag, MG_ERR_INVALID_ARGUMENT, "mg_dtw_distance_grids: the point clouds hold non-finite values");
     const int tiles_i = (n_ref_frames + DTW_TILE - 1) / DTW_TILE, tiles_j = (f_max + DTW_TILE - 1) / DTW_TILE;
     const size_t lds = ((size_t)2 * DTW_TILE * ((3 * n_joints) | 1) + DTW_MAX_JOINTS + 4 * DTW_TILE + 1) * 8;   // at most 50 440 bytes
     for (int64_t n0 = 0; n0 < n_motions; n0 += 65535) {     // grid.y limit
@@ -225,25 +216,24 @@ extern "C" int mg_dtw_distance_grids(mg_context *ctx, const double *ref_cloud_de
 
 extern "C" int mg_dtw_paths(mg_context *ctx, const double *grids_dev, int32_t n_ref_frames, const int64_t *offsets, int64_t n_motions,
                             double *accumulated_dev, double *totals_dev, int32_t *paths_dev, int32_t *path_lengths_dev, int32_t *warping_dev) {
-    DTW_REQUIRE(ctx && offsets, MG_ERR_INVALID_ARGUMENT, "mg_dtw_paths: NULL argument");
-    DTW_REQUIRE(n_motions >= 0, MG_ERR_INVALID_ARGUMENT, "mg_dtw_paths: n_motions = %lld", (long long)n_motions);
+    MG_REQUIRE_AS(ctx && offsets, MG_ERR_INVALID_ARGUMENT, "mg_dtw_paths: NULL argument");
+    MG_REQUIRE_AS(n_motions >= 0, MG_ERR_INVALID_ARGUMENT, "mg_dtw_paths: n_motions = %lld", (long long)n_motions);
     int32_t f_max = 0;
     const int rc = dtw_check_offsets("mg_dtw_paths", offsets, n_motions, n_ref_frames, &f_max);
     if (rc != MG_OK || n_motions == 0) return rc;
-    DTW_REQUIRE(grids_dev && totals_dev && paths_dev && path_lengths_dev && warping_dev, MG_ERR_INVALID_ARGUMENT, "mg_dtw_paths: NULL argument");
-    MG_HIP_CHECK(hipSetDevice(ctx->device));
+    MG_REQUIRE_AS(grids_dev && totals_dev && paths_dev && path_lengths_dev && warping_dev, MG_ERR_INVALID_ARGUMENT, "mg_dtw_paths: NULL argument");
     const int32_t wpr_max = (f_max + 15) / 16;
     const size_t code_bytes = (size_t)n_ref_frames * wpr_max * 4;
     const bool in_lds = code_bytes <= DTW_CODE_LDS_BYTES;
     const int64_t chunk = 65535;
-    dtw_block blk;
-    const int rb = dtw_block_create("mg_dtw_paths", ctx, &blk, offsets, n_motions, nullptr, 0, in_lds ? 0 : code_bytes * (size_t)std::min(chunk, n_motions));
+    dtw_block blk(ctx, "mg_dtw_paths");
+    const int rb = dtw_block_create(&blk, offsets, n_motions, nullptr, 0, in_lds ? 0 : code_bytes * (size_t)std::min(chunk, n_motions));
     if (rb != MG_OK) return rb;
     dtw_launch_nonfinite(ctx, grids_dev, (int64_t)n_ref_frames * offsets[n_motions], blk.flag);
     int32_t flag = 0;
     const int rf = dtw_flag_after(ctx, blk, &flag);
     if (rf != MG_OK) return rf;
-    DTW_REQUIRE(!flag, MG_ERR_INVALID_ARGUMENT, "mg_dtw_paths: the grids hold non-finite values");
+    MG_REQUIRE_AS(!flag, MG_ERR_INVALID_ARGUMENT, "mg_dtw_paths: the grids hold non-finite values");
     if (in_lds && code_bytes + sizeof(double) * 3 * DTW_MAX_FRAMES + 64 > 64 * 1024)
         MG_HIP_CHECK(hipFuncSetAttribute((const void *)dtw_paths_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, DTW_CODE_LDS_BYTES));
     const unsigned block = (unsigned)((n_ref_frames + 63) / 64 * 64);
@@ -260,24 +250,23 @@ extern "C" int mg_dtw_paths(mg_context *ctx, const double *grids_dev, int32_t n_
 
 extern "C" int mg_warp_motions(mg_context *ctx, const double *frames_dev, const int64_t *offsets, int64_t n_motions, int32_t n_dim,
                                const int32_t *warping_dev, int32_t n_ref_frames, double *warped_dev) {
-    DTW_REQUIRE(ctx && offsets, MG_ERR_INVALID_ARGUMENT, "mg_warp_motions: NULL argument");
-    DTW_REQUIRE(n_motions >= 0 && n_dim >= 1, MG_ERR_INVALID_ARGUMENT, "mg_warp_motions: n_motions = %lld, n_dim = %d", (long long)n_motions, n_dim);
-    DTW_REQUIRE(n_dim <= (1 << 20), MG_ERR_UNSUPPORTED, "mg_warp_motions: %d channels (at most 2^20)", n_dim);
+    MG_REQUIRE_AS(ctx && offsets, MG_ERR_INVALID_ARGUMENT, "mg_warp_motions: NULL argument");
+    MG_REQUIRE_AS(n_motions >= 0 && n_dim >= 1, MG_ERR_INVALID_ARGUMENT, "mg_warp_motions: n_motions = %lld, n_dim = %d", (long long)n_motions, n_dim);
+    MG_REQUIRE_AS(n_dim <= (1 << 20), MG_ERR_UNSUPPORTED, "mg_warp_motions: %d channels (at most 2^20)", n_dim);
     int32_t f_max = 0;
     const int rc = dtw_check_offsets("mg_warp_motions", offsets, n_motions, n_ref_frames, &f_max);
     if (rc != MG_OK || n_motions == 0) return rc;
-    DTW_REQUIRE(frames_dev && warping_dev && warped_dev, MG_ERR_INVALID_ARGUMENT, "mg_warp_motions: NULL argument");
-    MG_HIP_CHECK(hipSetDevice(ctx->device));
-    dtw_block blk;
-    const int rb = dtw_block_create("mg_warp_motions", ctx, &blk, offsets, n_motions, nullptr, 0, 0);
+    MG_REQUIRE_AS(frames_dev && warping_dev && warped_dev, MG_ERR_INVALID_ARGUMENT, "mg_warp_motions: NULL argument");
+    dtw_block blk(ctx, "mg_warp_motions");
+    const int rb = dtw_block_create(&blk, offsets, n_motions, nullptr, 0, 0);
     if (rb != MG_OK) return rb;
     const int64_t n_rows = n_motions * n_ref_frames, per_wg = DTW_BLOCK / 64;
-    DTW_REQUIRE(n_rows / per_wg < ((int64_t)1 << 31), MG_ERR_UNSUPPORTED, "mg_warp_motions: %lld output frames", (long long)n_rows);
+    MG_REQUIRE_AS(n_rows / per_wg < ((int64_t)1 << 31), MG_ERR_UNSUPPORTED, "mg_warp_motions: %lld output frames", (long long)n_rows);
     hipLaunchKernelGGL(dtw_warp_kernel, dim3((unsigned)((n_rows + per_wg - 1) / per_wg)), dim3(DTW_BLOCK), 0, ctx->stream, frames_dev,
                        (const int64_t *)blk.off, n_dim, warping_dev, n_ref_frames, warped_dev, n_rows, blk.flag);
     int32_t flag = 0;
     const int rf = dtw_flag_after(ctx, blk, &flag);
     if (rf != MG_OK) return rf;
-    DTW_REQUIRE(!flag, MG_ERR_INVALID_ARGUMENT, "mg_warp_motions: a warping function points outside its motion");
+    MG_REQUIRE_AS(!flag, MG_ERR_INVALID_ARGUMENT, "mg_warp_motions: a warping function points outside its motion");
     return MG_OK;
 }

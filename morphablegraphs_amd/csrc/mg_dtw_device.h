@@ -1,21 +1,13 @@
 // What mg_dtw.hip and mg_segment.hip share: the arithmetic of one cell of a distance grid (the contract is the header comment
 // of mg_dtw.hip; both files compile these very statements, so a cell has the same bits whichever kernel evaluates it), the
-// non-finite check kernel and the per-call device block with its flag.
+// non-finite check kernel, the per-call device block with its flag and the check of the joint weights.
 #pragma once
-#include "mg_internal.h"
+#include "mg_construct.h"
 
 #include <cmath>
 
 #define DTW_MAX_JOINTS 64
 #define DTW_BLOCK 256
-
-#define DTW_REQUIRE(cond, code, ...)   \
-    do {                               \
-        if (!(cond)) {                 \
-            mg_set_error(__VA_ARGS__); \
-            return (code);             \
-        }                              \
-    } while (0)
 
 // ---- one cell ------------------------------------------------------------------------------------------------------------------
 // sx = sum w_k x_k, sz = sum w_k z_k of the cloud p (J rows of x, y, z), in joint order
@@ -69,26 +61,21 @@ static __global__ __launch_bounds__(DTW_BLOCK) void dtw_nonfinite_kernel(const d
 }
 
 // ---- host --------------------------------------------------------------------------------------------------------------------
-// a device block for one call: the offsets, 64 doubles, a 256-byte flag area, then `extra` bytes
-struct dtw_block {
-    char *base = nullptr;
+// the device block of one call: the offsets, 64 doubles, a 256-byte flag area, then `extra` bytes
+struct dtw_block : mg_workspace {
+    using mg_workspace::mg_workspace;
     int64_t *off = nullptr;
     double *w = nullptr;
     int32_t *flag = nullptr;
     char *extra = nullptr;
-    ~dtw_block() { if (base) (void)hipFree(base); }
 };
 
-static inline int dtw_block_create(const char *who, mg_context *ctx, dtw_block *b, const int64_t *offsets, int64_t n_motions, const double *weights,
-                                   int32_t n_w, size_t extra) {
-    const size_t o_w = (((size_t)n_motions + 1) * 8 + 255) & ~(size_t)255, o_flag = o_w + 512, o_extra = o_flag + 256, total = o_extra + extra;
-    if (hipMalloc(&b->base, total) != hipSuccess) {
-        (void)hipGetLastError();
-        b->base = nullptr;
-        mg_set_error("%s: cannot allocate %zu bytes of device memory", who, total);
-        return MG_ERR_OUT_OF_MEMORY;
-    }
-    b->off = (int64_t *)b->base, b->w = (double *)(b->base + o_w), b->flag = (int32_t *)(b->base + o_flag), b->extra = b->base + o_extra;
+static inline int dtw_block_create(dtw_block *b, const int64_t *offsets, int64_t n_motions, const double *weights, int32_t n_w, size_t extra) {
+    const size_t o_off = b->carve(((size_t)n_motions + 1) * 8), o_w = b->carve(512), o_flag = b->carve(256), o_extra = b->carve(extra);
+    const int rc = b->alloc();
+    if (rc != MG_OK) return rc;
+    mg_context *ctx = b->ctx;
+    b->off = b->at<int64_t>(o_off), b->w = b->at<double>(o_w), b->flag = b->at<int32_t>(o_flag), b->extra = b->at<char>(o_extra);
     MG_HIP_CHECK(hipMemcpyAsync(b->off, offsets, ((size_t)n_motions + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
     if (n_w > 0) MG_HIP_CHECK(hipMemcpyAsync(b->w, weights, (size_t)n_w * 8, hipMemcpyHostToDevice, ctx->stream));
     MG_HIP_CHECK(hipMemsetAsync(b->flag, 0, 256, ctx->stream));
@@ -99,6 +86,18 @@ static inline int dtw_flag_after(mg_context *ctx, const dtw_block &b, int32_t *f
     MG_HIP_CHECK(hipGetLastError());
     MG_HIP_CHECK(hipMemcpyAsync(flag, b.flag, 4, hipMemcpyDeviceToHost, ctx->stream));
     MG_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    return MG_OK;
+}
+
+// w[0 .. n_joints) = the caller's weights, or ones: finite, none negative, not all zero
+static inline int dtw_weights(const char *who, const double *weights, int32_t n_joints, double *w) {
+    double wsum = 0.0;
+    for (int k = 0; k < n_joints; k++) {
+        w[k] = weights ? weights[k] : 1.0;
+        MG_REQUIRE_AS(std::isfinite(w[k]) && w[k] >= 0.0, MG_ERR_INVALID_ARGUMENT, "%s: weight %d is %g", who, k, w[k]);
+        wsum += w[k];
+    }
+    MG_REQUIRE_AS(wsum > 0.0, MG_ERR_INVALID_ARGUMENT, "%s: the weights add up to 0", who);
     return MG_OK;
 }
 

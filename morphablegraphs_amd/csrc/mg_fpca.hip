@@ -20,7 +20,7 @@
 // G takes every rotation of every sweep, so its orthonormality drifts with their number (7e-14 at m = 255 after 13 sweeps);
 // after the last sweep one Newton-Schulz step G <- G - (G G^T G - G) / 2 on the GEMM kernel brings it back to rounding level.
 // The step costs two m x m x m products and two more m x m buffers next to G for the length of the call (3 x 128 MiB at m = 4096).
-#include "mg_internal.h"
+#include "mg_construct.h"
 
 #include <algorithm>
 #include <cfloat>
@@ -37,14 +37,6 @@
 #define FP_MAX_SWEEPS 30
 
 typedef double fp_f64x4 __attribute__((ext_vector_type(4)));
-
-#define FP_REQUIRE(cond, code, ...)   \
-    do {                              \
-        if (!(cond)) {                \
-            mg_set_error(__VA_ARGS__); \
-            return (code);            \
-        }                             \
-    } while (0)
 
 // ---- C[b] = A[b] . B[b] (+ bias): A (M, K) rows lda apart; B element (k, j) at k * sbk + j * sbj; C (M, Nc) rows ldc apart ----
 struct fp_gemm_args {
@@ -103,13 +95,13 @@ static int fp_gemm(mg_context *ctx, const double *A, const double *B, const doub
 
 extern "C" int mg_spline_fit_batch(mg_context *ctx, const double *motions_dev, int64_t n_motions, int32_t n_frames, int32_t n_dims,
                                    const double *operator_dev, int32_t n_basis, double *coeffs_dev) {
-    FP_REQUIRE(ctx && motions_dev && operator_dev && coeffs_dev, MG_ERR_INVALID_ARGUMENT, "mg_spline_fit_batch: NULL argument");
-    FP_REQUIRE(n_motions >= 0 && n_dims >= 1 && n_frames >= 1 && n_basis >= 1, MG_ERR_INVALID_ARGUMENT,
-               "mg_spline_fit_batch: n_motions = %lld, n_frames = %d, n_dims = %d, n_basis = %d", (long long)n_motions, n_frames, n_dims, n_basis);
-    FP_REQUIRE(n_basis <= FP_MAX_BASIS && n_frames <= FP_MAX_FRAMES, MG_ERR_UNSUPPORTED,
-               "mg_spline_fit_batch: n_basis = %d (at most %d), n_frames = %d (at most %d)", n_basis, FP_MAX_BASIS, n_frames, FP_MAX_FRAMES);
-    FP_REQUIRE(n_basis <= n_frames, MG_ERR_INVALID_ARGUMENT, "mg_spline_fit_batch: %d basis functions for %d frames", n_basis, n_frames);
-    FP_REQUIRE(n_dims <= (1 << 20) && n_motions < ((int64_t)1 << 31), MG_ERR_UNSUPPORTED, "mg_spline_fit_batch: table too large");
+    MG_REQUIRE_AS(ctx && motions_dev && operator_dev && coeffs_dev, MG_ERR_INVALID_ARGUMENT, "mg_spline_fit_batch: NULL argument");
+    MG_REQUIRE_AS(n_motions >= 0 && n_dims >= 1 && n_frames >= 1 && n_basis >= 1, MG_ERR_INVALID_ARGUMENT,
+                  "mg_spline_fit_batch: n_motions = %lld, n_frames = %d, n_dims = %d, n_basis = %d", (long long)n_motions, n_frames, n_dims, n_basis);
+    MG_REQUIRE_AS(n_basis <= FP_MAX_BASIS && n_frames <= FP_MAX_FRAMES, MG_ERR_UNSUPPORTED,
+                  "mg_spline_fit_batch: n_basis = %d (at most %d), n_frames = %d (at most %d)", n_basis, FP_MAX_BASIS, n_frames, FP_MAX_FRAMES);
+    MG_REQUIRE_AS(n_basis <= n_frames, MG_ERR_INVALID_ARGUMENT, "mg_spline_fit_batch: %d basis functions for %d frames", n_basis, n_frames);
+    MG_REQUIRE_AS(n_dims <= (1 << 20) && n_motions < ((int64_t)1 << 31), MG_ERR_UNSUPPORTED, "mg_spline_fit_batch: table too large");
     if (n_motions == 0) return MG_OK;
     MG_HIP_CHECK(hipSetDevice(ctx->device));
     const int rc = fp_gemm(ctx, operator_dev, motions_dev, nullptr, coeffs_dev, n_motions, 0, (int64_t)n_frames * n_dims, (int64_t)n_basis * n_dims,
@@ -120,11 +112,11 @@ extern "C" int mg_spline_fit_batch(mg_context *ctx, const double *motions_dev, i
 }
 
 static int fp_check_project(const char *who, mg_context *ctx, const void *a, const void *b, const void *c, int64_t n, int64_t p, int64_t l) {
-    FP_REQUIRE(ctx && a && b && c, MG_ERR_INVALID_ARGUMENT, "%s: NULL argument", who);
-    FP_REQUIRE(n >= 0 && p >= 1 && l >= 1, MG_ERR_INVALID_ARGUMENT, "%s: n = %lld, p = %lld, l = %lld", who, (long long)n, (long long)p, (long long)l);
-    FP_REQUIRE(l <= p, MG_ERR_INVALID_ARGUMENT, "%s: %lld components of a %lld-dimensional space", who, (long long)l, (long long)p);
-    FP_REQUIRE(n < ((int64_t)1 << 24) && p < ((int64_t)1 << 24) && ((n + 15) / 16) * ((p + 15) / 16) < ((int64_t)1 << 31), MG_ERR_UNSUPPORTED,
-               "%s: table too large", who);
+    MG_REQUIRE_AS(ctx && a && b && c, MG_ERR_INVALID_ARGUMENT, "%s: NULL argument", who);
+    MG_REQUIRE_AS(n >= 0 && p >= 1 && l >= 1, MG_ERR_INVALID_ARGUMENT, "%s: n = %lld, p = %lld, l = %lld", who, (long long)n, (long long)p, (long long)l);
+    MG_REQUIRE_AS(l <= p, MG_ERR_INVALID_ARGUMENT, "%s: %lld components of a %lld-dimensional space", who, (long long)l, (long long)p);
+    MG_REQUIRE_AS(n < ((int64_t)1 << 24) && p < ((int64_t)1 << 24) && ((n + 15) / 16) * ((p + 15) / 16) < ((int64_t)1 << 31), MG_ERR_UNSUPPORTED,
+                  "%s: table too large", who);
     return MG_OK;
 }
 
@@ -241,93 +233,90 @@ static double fp_row_norm2(const double *w, int64_t L) {
     return total;
 }
 
-extern "C" int mg_pca_fit(mg_context *ctx, const double *a_dev, int64_t n, int64_t p, int32_t centre, double *centred_dev, double *mean,
-                          double *singular_values, double *vt, int32_t *n_sweeps, int32_t *status) {
-    FP_REQUIRE(ctx && a_dev && centred_dev && mean && singular_values && vt && n_sweeps && status, MG_ERR_INVALID_ARGUMENT, "mg_pca_fit: NULL argument");
-    FP_REQUIRE(n >= 1 && p >= 1, MG_ERR_INVALID_ARGUMENT, "mg_pca_fit: matrix %lld x %lld", (long long)n, (long long)p);
+// The device's part of mg_pca_fit: centring, the Jacobi sweeps and the polish in one device block, then the rotated rows (hW),
+// the companion (hG, n > p only) and the mean to the host.  The block is freed on return, before the host's part runs.
+static int fp_jacobi_device(mg_context *ctx, const double *a_dev, int64_t n, int64_t p, int32_t centre, double *centred_dev, double *mean,
+                            std::vector<double> &hW, std::vector<double> &hG, int32_t *n_sweeps, int32_t *status) {
     const int64_t m = std::min(n, p), L = std::max(n, p);
-    FP_REQUIRE(m <= FP_MAX_SHORT, MG_ERR_UNSUPPORTED, "mg_pca_fit: min(n, p) = %lld, at most %d", (long long)m, FP_MAX_SHORT);
-    FP_REQUIRE(L <= FP_MAX_LONG, MG_ERR_UNSUPPORTED, "mg_pca_fit: max(n, p) = %lld, at most %lld", (long long)L, (long long)FP_MAX_LONG);
     const bool wide = n <= p;           // rotate the rows of the centred matrix itself
-    MG_HIP_CHECK(hipSetDevice(ctx->device));
-    const size_t wbytes = (size_t)n * p * 8, g1 = wide ? 0 : (((size_t)m * m * 8 + 255) & ~(size_t)255), gbytes = 3 * g1;   // G, G G^T, (G G^T) G
-    const size_t o_mean = (wbytes + 255) & ~(size_t)255, o_g = o_mean + (((size_t)p * 8 + 255) & ~(size_t)255);
-    const size_t o_cnt = o_g + ((gbytes + 255) & ~(size_t)255), total = o_cnt + 256;
-    char *base = nullptr;
-    {
-        const hipError_t e = hipMalloc(&base, total);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            mg_set_error("mg_pca_fit: cannot allocate %zu bytes of device memory", total);
-            return MG_ERR_OUT_OF_MEMORY;
-        }
-    }
-    double *W = (double *)base, *d_mean = (double *)(base + o_mean), *G = wide ? nullptr : (double *)(base + o_g);
-    int32_t *d_cnt = (int32_t *)(base + o_cnt);
-    std::vector<double> hW, hG;
-    int rc = MG_OK;
-    auto fail = [&](hipError_t e, const char *what) { if (e != hipSuccess && rc == MG_OK) rc = mg_hip_fail(e, what); return e != hipSuccess; };
+    mg_workspace ws(ctx, "mg_pca_fit");
+    const size_t g1 = wide ? 0 : mg_workspace::align((size_t)m * m * 8);   // G, G G^T, (G G^T) G
+    const size_t o_w = ws.carve((size_t)n * p * 8), o_mean = ws.carve((size_t)p * 8), o_g = ws.carve(3 * g1), o_cnt = ws.carve(256);
+    const int ra = ws.alloc();
+    if (ra != MG_OK) return ra;
+    double *W = ws.at<double>(o_w), *d_mean = ws.at<double>(o_mean), *G = wide ? nullptr : ws.at<double>(o_g);
+    int32_t *d_cnt = ws.at<int32_t>(o_cnt);
     const int32_t mp = (int32_t)(m + (m & 1));
     int32_t sweeps = 0, st = 2;
-    do {
-        if (fail(hipMemsetAsync(d_cnt, 0, 256, ctx->stream), "hipMemsetAsync")) break;
-        if (centre)
-            hipLaunchKernelGGL(fpca_mean_kernel, dim3((unsigned)((p + FP_BLOCK - 1) / FP_BLOCK)), dim3(FP_BLOCK), 0, ctx->stream, a_dev, n, p, d_mean);
-        else if (fail(hipMemsetAsync(d_mean, 0, (size_t)p * 8, ctx->stream), "hipMemsetAsync")) break;   // a - 0.0 is a
-        hipLaunchKernelGGL(fpca_centre_kernel, dim3((unsigned)((n * p + FP_BLOCK - 1) / FP_BLOCK)), dim3(FP_BLOCK), 0, ctx->stream, a_dev, d_mean, n, p,
-                           centred_dev, W, wide ? 0 : 1);
-        if (G) hipLaunchKernelGGL(fpca_identity_kernel, dim3((unsigned)((m * m + FP_BLOCK - 1) / FP_BLOCK)), dim3(FP_BLOCK), 0, ctx->stream, G, m);
-        if (fail(hipGetLastError(), "centring launch")) break;
-        const double tol = DBL_EPSILON * std::sqrt((double)L);
-        if (m >= 2) {
-            for (sweeps = 0; sweeps < FP_MAX_SWEEPS;) {
-                for (int32_t r = 0; r < mp - 1; r++)
-                    hipLaunchKernelGGL(fpca_jacobi_round_kernel, dim3((unsigned)(mp / 2)), dim3(FP_BLOCK), 0, ctx->stream, W, G, (int32_t)m, mp, L, r, tol,
-                                       d_cnt + sweeps);
-                if (fail(hipGetLastError(), "jacobi launch")) break;
-                int32_t rotations = 0;
-                if (fail(hipMemcpyAsync(&rotations, d_cnt + sweeps, 4, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpyAsync")) break;
-                if (fail(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize")) break;
-                sweeps++;
-                if (rotations == 0) {
-                    st = 1;
-                    break;
-                }
+    MG_HIP_CHECK(hipMemsetAsync(d_cnt, 0, 256, ctx->stream));
+    if (centre)
+        hipLaunchKernelGGL(fpca_mean_kernel, dim3((unsigned)((p + FP_BLOCK - 1) / FP_BLOCK)), dim3(FP_BLOCK), 0, ctx->stream, a_dev, n, p, d_mean);
+    else
+        MG_HIP_CHECK(hipMemsetAsync(d_mean, 0, (size_t)p * 8, ctx->stream));   // a - 0.0 is a
+    hipLaunchKernelGGL(fpca_centre_kernel, dim3((unsigned)((n * p + FP_BLOCK - 1) / FP_BLOCK)), dim3(FP_BLOCK), 0, ctx->stream, a_dev, d_mean, n, p,
+                       centred_dev, W, wide ? 0 : 1);
+    if (G) hipLaunchKernelGGL(fpca_identity_kernel, dim3((unsigned)((m * m + FP_BLOCK - 1) / FP_BLOCK)), dim3(FP_BLOCK), 0, ctx->stream, G, m);
+    MG_HIP_CHECK(hipGetLastError());
+    const double tol = DBL_EPSILON * std::sqrt((double)L);
+    if (m >= 2) {
+        for (sweeps = 0; sweeps < FP_MAX_SWEEPS;) {
+            for (int32_t r = 0; r < mp - 1; r++)
+                hipLaunchKernelGGL(fpca_jacobi_round_kernel, dim3((unsigned)(mp / 2)), dim3(FP_BLOCK), 0, ctx->stream, W, G, (int32_t)m, mp, L, r, tol,
+                                   d_cnt + sweeps);
+            MG_HIP_CHECK(hipGetLastError());
+            int32_t rotations = 0;
+            MG_HIP_CHECK(hipMemcpyAsync(&rotations, d_cnt + sweeps, 4, hipMemcpyDeviceToHost, ctx->stream));
+            MG_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+            sweeps++;
+            if (rotations == 0) {
+                st = 1;
+                break;
             }
-            if (rc != MG_OK) break;
-            if (G) {
-                double *T = (double *)((char *)G + g1), *Y = (double *)((char *)G + 2 * g1);
-                if ((rc = fp_gemm(ctx, G, G, nullptr, T, 1, 0, 0, 0, m, m, m, m, 1, m, m)) != MG_OK) break;     // T = G G^T
-                if ((rc = fp_gemm(ctx, T, G, nullptr, Y, 1, 0, 0, 0, m, m, m, m, m, 1, m)) != MG_OK) break;     // Y = T G
-                hipLaunchKernelGGL(fpca_polish_kernel, dim3((unsigned)((m * m + FP_BLOCK - 1) / FP_BLOCK)), dim3(FP_BLOCK), 0, ctx->stream, G, Y, m * m);
-                if (fail(hipGetLastError(), "polish launch")) break;
-            }
-        } else {
-            st = 1;
         }
-        try {
-            hW.resize((size_t)m * L);
-            if (G) hG.resize((size_t)m * m);
-        } catch (const std::bad_alloc &) {
-            mg_set_error("mg_pca_fit: cannot allocate the host copy of a %lld x %lld matrix", (long long)m, (long long)L);
-            rc = MG_ERR_OUT_OF_MEMORY;
-            break;
-        }
-        if (fail(hipMemcpyAsync(hW.data(), W, (size_t)m * L * 8, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpyAsync")) break;
         if (G) {
-            hG.resize((size_t)m * m);
-            if (fail(hipMemcpyAsync(hG.data(), G, (size_t)m * m * 8, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpyAsync")) break;
+            double *T = (double *)((char *)G + g1), *Y = (double *)((char *)G + 2 * g1);
+            int rc = fp_gemm(ctx, G, G, nullptr, T, 1, 0, 0, 0, m, m, m, m, 1, m, m);                     // T = G G^T
+            if (rc == MG_OK) rc = fp_gemm(ctx, T, G, nullptr, Y, 1, 0, 0, 0, m, m, m, m, m, 1, m);        // Y = T G
+            if (rc != MG_OK) return rc;
+            hipLaunchKernelGGL(fpca_polish_kernel, dim3((unsigned)((m * m + FP_BLOCK - 1) / FP_BLOCK)), dim3(FP_BLOCK), 0, ctx->stream, G, Y, m * m);
+            MG_HIP_CHECK(hipGetLastError());
         }
-        if (fail(hipMemcpyAsync(mean, d_mean, (size_t)p * 8, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpyAsync")) break;
-        if (fail(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize")) break;
-    } while (0);
-    (void)hipFree(base);
+    } else {
+        st = 1;
+    }
+    try {
+        hW.resize((size_t)m * L);
+        if (G) hG.resize((size_t)m * m);
+    } catch (const std::bad_alloc &) {
+        mg_set_error("mg_pca_fit: cannot allocate the host copy of a %lld x %lld matrix", (long long)m, (long long)L);
+        return MG_ERR_OUT_OF_MEMORY;
+    }
+    MG_HIP_CHECK(hipMemcpyAsync(hW.data(), W, (size_t)m * L * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (G) MG_HIP_CHECK(hipMemcpyAsync(hG.data(), G, (size_t)m * m * 8, hipMemcpyDeviceToHost, ctx->stream));
+    MG_HIP_CHECK(hipMemcpyAsync(mean, d_mean, (size_t)p * 8, hipMemcpyDeviceToHost, ctx->stream));
+    MG_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    *n_sweeps = sweeps;
+    *status = st;
+    return MG_OK;
+}
+
+extern "C" int mg_pca_fit(mg_context *ctx, const double *a_dev, int64_t n, int64_t p, int32_t centre, double *centred_dev, double *mean,
+                          double *singular_values, double *vt, int32_t *n_sweeps, int32_t *status) {
+    MG_REQUIRE_AS(ctx && a_dev && centred_dev && mean && singular_values && vt && n_sweeps && status, MG_ERR_INVALID_ARGUMENT, "mg_pca_fit: NULL argument");
+    MG_REQUIRE_AS(n >= 1 && p >= 1, MG_ERR_INVALID_ARGUMENT, "mg_pca_fit: matrix %lld x %lld", (long long)n, (long long)p);
+    const int64_t m = std::min(n, p), L = std::max(n, p);
+    MG_REQUIRE_AS(m <= FP_MAX_SHORT, MG_ERR_UNSUPPORTED, "mg_pca_fit: min(n, p) = %lld, at most %d", (long long)m, FP_MAX_SHORT);
+    MG_REQUIRE_AS(L <= FP_MAX_LONG, MG_ERR_UNSUPPORTED, "mg_pca_fit: max(n, p) = %lld, at most %lld", (long long)L, (long long)FP_MAX_LONG);
+    const bool wide = n <= p;
+    std::vector<double> hW, hG;
+    int32_t sweeps = 0, st = 2;
+    const int rc = fp_jacobi_device(ctx, a_dev, n, p, centre, centred_dev, mean, hW, hG, &sweeps, &st);
     if (rc != MG_OK) return rc;
     // ---- the host's part: norms, descending order (stable), normalisation, null rows, the sign rule ----
     std::vector<double> sig(m);
     for (int64_t r = 0; r < m; r++) sig[r] = std::sqrt(fp_row_norm2(hW.data() + r * L, L));
     for (int64_t r = 0; r < m; r++)
-        FP_REQUIRE(std::isfinite(sig[r]), MG_ERR_INVALID_ARGUMENT, "mg_pca_fit: the matrix holds non-finite values (or its norms overflow)");
+        MG_REQUIRE_AS(std::isfinite(sig[r]), MG_ERR_INVALID_ARGUMENT, "mg_pca_fit: the matrix holds non-finite values (or its norms overflow)");
     std::vector<int64_t> order(m);
     std::iota(order.begin(), order.end(), 0);
     std::stable_sort(order.begin(), order.end(), [&](int64_t x, int64_t y) { return sig[x] > sig[y]; });

@@ -16,7 +16,7 @@
 // pass (lower bound, weights, convergence).  Every component has EM_NSLOT partial slots whatever n is; rows are split into
 // slots by n alone and every sum runs in a fixed order, so a fit gives the same bits in any batch and on any device size.
 // No float atomics, no grid barriers: each kernel combines what an earlier launch of the stream wrote.
-#include "mg_internal.h"
+#include "mg_construct.h"
 
 #include <algorithm>
 #include <cfloat>
@@ -58,19 +58,6 @@ __global__ __launch_bounds__(EM_BLOCK) void em_onehot_kernel(em_args a, const in
     const int K = a.K[f], c0 = a.co[f];
     const int L = lab_in[(size_t)f * a.n + row];
     for (int k = 0; k < K; k++) a.resp[(size_t)(c0 + k) * a.n + row] = k == L ? 1.0 : 0.0;
-}
-
-// sum over the workgroup in a fixed tree order
-__device__ __forceinline__ double em_block_sum(double v, double *red) {
-    red[threadIdx.x] = v;
-    __syncthreads();
-    for (int s = EM_BLOCK / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
-    const double r = red[0];
-    __syncthreads();
-    return r;
 }
 
 // ---- E-step: weighted log prob of every component, logsumexp, responsibilities; the block's sum of log_prob_norm --------
@@ -137,7 +124,7 @@ __global__ __launch_bounds__(EM_BLOCK) void em_estep_kernel(em_args a, int final
             }
         }
     }
-    const double s = em_block_sum(lpn, red);
+    const double s = mg_block_sum<EM_BLOCK>(lpn, red);
     if (tid == 0) a.blk[(size_t)f * a.nblk + blockIdx.x] = s;
 }
 
@@ -335,47 +322,39 @@ __global__ __launch_bounds__(64) void em_state_kernel(em_args a, int mode) {
     else if (it >= a.max_iter) a.state[f] = EM_MAX_ITER;
 }
 
-#define EM_REQUIRE(cond, code, ...) \
-    do {                            \
-        if (!(cond)) {              \
-            mg_set_error(__VA_ARGS__); \
-            return code;            \
-        }                           \
-    } while (0)
-
-static size_t em_align(size_t b) { return (b + 255) & ~(size_t)255; }
-
 extern "C" int mg_gmm_em_fit(mg_context *ctx, const double *points_dev, int64_t n, int32_t dim, int32_t n_fits, const int32_t *n_comp,
                              const int32_t *labels_in, double tol, double reg_covar, int32_t max_iter, double *weights, double *means,
                              double *covariances, double *precisions_chol, double *lower_bounds, int32_t *n_iter, int32_t *status,
                              double *score, int32_t *labels_out) {
     const int BAD = MG_ERR_INVALID_ARGUMENT, UNS = MG_ERR_UNSUPPORTED;
-    EM_REQUIRE(ctx && points_dev, BAD, "mg_gmm_em_fit: NULL context or points");
-    EM_REQUIRE(dim >= 1 && dim <= EM_MAX_D, UNS, "mg_gmm_em_fit: dim = %d outside [1, %d]", dim, EM_MAX_D);
-    EM_REQUIRE(n_fits >= 0 && max_iter >= 1 && tol >= 0.0 && reg_covar >= 0.0, BAD,
-               "mg_gmm_em_fit: n_fits = %d, max_iter = %d, tol = %g, reg_covar = %g", n_fits, max_iter, tol, reg_covar);
+    MG_REQUIRE_AS(ctx && points_dev, BAD, "mg_gmm_em_fit: NULL context or points");
+    MG_REQUIRE_AS(dim >= 1 && dim <= EM_MAX_D, UNS, "mg_gmm_em_fit: dim = %d outside [1, %d]", dim, EM_MAX_D);
+    MG_REQUIRE_AS(n_fits >= 0 && max_iter >= 1 && tol >= 0.0 && reg_covar >= 0.0, BAD,
+                  "mg_gmm_em_fit: n_fits = %d, max_iter = %d, tol = %g, reg_covar = %g", n_fits, max_iter, tol, reg_covar);
     if (n_fits == 0) return MG_OK;
-    EM_REQUIRE(n_comp && labels_in && weights && means && covariances && precisions_chol && lower_bounds && n_iter && status && score && labels_out,
-               BAD, "mg_gmm_em_fit: NULL argument");
-    EM_REQUIRE(n >= 1 && n < ((int64_t)1 << 40), BAD, "mg_gmm_em_fit: n = %lld", (long long)n);
+    MG_REQUIRE_AS(n_comp && labels_in && weights && means && covariances && precisions_chol && lower_bounds && n_iter && status && score && labels_out,
+                  BAD, "mg_gmm_em_fit: NULL argument");
+    MG_REQUIRE_AS(n >= 1 && n < ((int64_t)1 << 40), BAD, "mg_gmm_em_fit: n = %lld", (long long)n);
     std::vector<int32_t> co(n_fits + 1, 0);
     for (int32_t f = 0; f < n_fits; f++) {
-        EM_REQUIRE(n_comp[f] >= 1 && n_comp[f] <= EM_MAX_K, UNS, "mg_gmm_em_fit: fit %d has %d components, outside [1, %d]", f, n_comp[f], EM_MAX_K);
-        EM_REQUIRE(n_comp[f] <= n, BAD, "mg_gmm_em_fit: fit %d has %d components and %lld samples", f, n_comp[f], (long long)n);
+        MG_REQUIRE_AS(n_comp[f] >= 1 && n_comp[f] <= EM_MAX_K, UNS, "mg_gmm_em_fit: fit %d has %d components, outside [1, %d]", f, n_comp[f], EM_MAX_K);
+        MG_REQUIRE_AS(n_comp[f] <= n, BAD, "mg_gmm_em_fit: fit %d has %d components and %lld samples", f, n_comp[f], (long long)n);
         co[f + 1] = co[f] + n_comp[f];
     }
     for (int32_t f = 0; f < n_fits; f++)
         for (int64_t r = 0; r < n; r++)
-            EM_REQUIRE(labels_in[(size_t)f * n + r] >= 0 && labels_in[(size_t)f * n + r] < n_comp[f], BAD,
-                       "mg_gmm_em_fit: fit %d, row %lld: label %d outside [0, %d)", f, (long long)r, labels_in[(size_t)f * n + r], n_comp[f]);
+            MG_REQUIRE_AS(labels_in[(size_t)f * n + r] >= 0 && labels_in[(size_t)f * n + r] < n_comp[f], BAD,
+                          "mg_gmm_em_fit: fit %d, row %lld: label %d outside [0, %d)", f, (long long)r, labels_in[(size_t)f * n + r], n_comp[f]);
     const int32_t C = co[n_fits], d = dim, dt = d * (d + 1) / 2;
     const int64_t nblk = (n + EM_BLOCK - 1) / EM_BLOCK, chunk = (n + EM_NSLOT - 1) / EM_NSLOT;
-    EM_REQUIRE(nblk < ((int64_t)1 << 31) && chunk < ((int64_t)1 << 31), UNS, "mg_gmm_em_fit: n = %lld too large", (long long)n);
+    MG_REQUIRE_AS(nblk < ((int64_t)1 << 31) && chunk < ((int64_t)1 << 31), UNS, "mg_gmm_em_fit: n = %lld too large", (long long)n);
     std::vector<int32_t> fit_of(C);
     for (int32_t f = 0; f < n_fits; f++)
         for (int32_t k = 0; k < n_comp[f]; k++) fit_of[co[f] + k] = f;
-    size_t off = 0;
-    auto carve = [&](size_t bytes) { const size_t o = off; off += em_align(bytes); return o; };
+    std::vector<int32_t> fits(n_fits), comps(C), state(n_fits, EM_RUN);
+    // one device block for everything the call needs; declared after the host buffers its copies touch: it drains the stream first
+    mg_workspace ws(ctx, "mg_gmm_em_fit");
+    auto carve = [&](size_t bytes) { return ws.carve(bytes); };
     const size_t o_K = carve(n_fits * 4), o_co = carve(n_fits * 4), o_fitof = carve(C * 4), o_fits = carve(n_fits * 4), o_comps = carve(C * 4);
     const size_t o_lin = carve((size_t)n_fits * n * 4), o_lout = carve((size_t)n_fits * n * 4);
     const size_t o_resp = carve((size_t)C * n * 8);
@@ -383,17 +362,10 @@ extern "C" int mg_gmm_em_fit(mg_context *ctx, const double *points_dev, int64_t 
     const size_t o_cov = carve((size_t)C * d * d * 8), o_prec = carve((size_t)C * d * d * 8), o_cvec = carve((size_t)C * d * 8), o_ld = carve(C * 8);
     const size_t o_psum = carve((size_t)C * EM_NSLOT * (d + 1) * 8), o_pcov = carve((size_t)C * EM_NSLOT * dt * 8);
     const size_t o_blk = carve((size_t)n_fits * nblk * 8), o_lb = carve((size_t)n_fits * max_iter * 8), o_score = carve(n_fits * 8);
-    const size_t o_state = carve(n_fits * 4), o_iter = carve(n_fits * 4), o_fail = carve(n_fits * 4), o_end = off;
-    MG_HIP_CHECK(hipSetDevice(ctx->device));
-    char *base = nullptr;
-    {
-        const hipError_t e = hipMalloc(&base, off);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            mg_set_error("mg_gmm_em_fit: cannot allocate %zu bytes of device memory", off);
-            return MG_ERR_OUT_OF_MEMORY;
-        }
-    }
+    const size_t o_state = carve(n_fits * 4), o_iter = carve(n_fits * 4), o_fail = carve(n_fits * 4), o_end = ws.bytes;
+    const int ra = ws.alloc();
+    if (ra != MG_OK) return ra;
+    char *const base = ws.base;
     hipStream_t st = ctx->stream;
     em_args a;
     a.X = points_dev;
@@ -408,47 +380,39 @@ extern "C" int mg_gmm_em_fit(mg_context *ctx, const double *points_dev, int64_t 
     a.blk = (double *)(base + o_blk); a.lb = (double *)(base + o_lb); a.score = (double *)(base + o_score);
     a.state = (int32_t *)(base + o_state); a.n_iter = (int32_t *)(base + o_iter); a.fail = (int32_t *)(base + o_fail);
     a.labels = (int32_t *)(base + o_lout);
-    int rc = MG_OK;
-    std::vector<int32_t> fits(n_fits), comps(C), state(n_fits, EM_RUN);
     for (int32_t f = 0; f < n_fits; f++) fits[f] = f;
     for (int32_t c = 0; c < C; c++) comps[c] = c;
     int32_t nf = n_fits, nc = C;
     void (*estep)(em_args, int) = d <= 8 ? em_estep_kernel<8> : d <= 16 ? em_estep_kernel<16> : d <= 32 ? em_estep_kernel<32> : em_estep_kernel<64>;
     int next_check = 1;
-#define EM_TRY(expr)                                                      \
-    do {                                                                  \
-        hipError_t _e = (expr);                                           \
-        if (_e != hipSuccess) { rc = mg_hip_fail(_e, #expr); goto done; } \
-    } while (0)
-#define EM_MSTEP()                                                                                                       \
-    do {                                                                                                                 \
-        hipLaunchKernelGGL(em_msum_kernel, dim3(EM_NSLOT, nc), dim3(64), 0, st, a);                                    \
-        hipLaunchKernelGGL(em_mcov_kernel, dim3(EM_NSLOT, nc), dim3(EM_BLOCK), 0, st, a);                              \
-        hipLaunchKernelGGL(em_mchol_kernel, dim3(nc), dim3(64), 0, st, a);                                             \
-        EM_TRY(hipGetLastError());                                                                                       \
-    } while (0)
-    EM_TRY(hipMemcpyAsync(base + o_K, n_comp, n_fits * 4, hipMemcpyHostToDevice, st));
-    EM_TRY(hipMemcpyAsync(base + o_co, co.data(), n_fits * 4, hipMemcpyHostToDevice, st));
-    EM_TRY(hipMemcpyAsync(base + o_fitof, fit_of.data(), C * 4, hipMemcpyHostToDevice, st));
-    EM_TRY(hipMemcpyAsync(base + o_fits, fits.data(), n_fits * 4, hipMemcpyHostToDevice, st));
-    EM_TRY(hipMemcpyAsync(base + o_comps, comps.data(), C * 4, hipMemcpyHostToDevice, st));
-    EM_TRY(hipMemcpyAsync(base + o_lin, labels_in, (size_t)n_fits * n * 4, hipMemcpyHostToDevice, st));
-    EM_TRY(hipMemsetAsync(base + o_lb, 0, o_end - o_lb, st));     // lower bounds, scores, states (EM_RUN), n_iter, fail flags
+    auto mstep = [&]() {
+        hipLaunchKernelGGL(em_msum_kernel, dim3(EM_NSLOT, nc), dim3(64), 0, st, a);
+        hipLaunchKernelGGL(em_mcov_kernel, dim3(EM_NSLOT, nc), dim3(EM_BLOCK), 0, st, a);
+        hipLaunchKernelGGL(em_mchol_kernel, dim3(nc), dim3(64), 0, st, a);
+        return hipGetLastError();
+    };
+    MG_HIP_CHECK(hipMemcpyAsync(base + o_K, n_comp, n_fits * 4, hipMemcpyHostToDevice, st));
+    MG_HIP_CHECK(hipMemcpyAsync(base + o_co, co.data(), n_fits * 4, hipMemcpyHostToDevice, st));
+    MG_HIP_CHECK(hipMemcpyAsync(base + o_fitof, fit_of.data(), C * 4, hipMemcpyHostToDevice, st));
+    MG_HIP_CHECK(hipMemcpyAsync(base + o_fits, fits.data(), n_fits * 4, hipMemcpyHostToDevice, st));
+    MG_HIP_CHECK(hipMemcpyAsync(base + o_comps, comps.data(), C * 4, hipMemcpyHostToDevice, st));
+    MG_HIP_CHECK(hipMemcpyAsync(base + o_lin, labels_in, (size_t)n_fits * n * 4, hipMemcpyHostToDevice, st));
+    MG_HIP_CHECK(hipMemsetAsync(base + o_lb, 0, o_end - o_lb, st));     // lower bounds, scores, states (EM_RUN), n_iter, fail flags
     hipLaunchKernelGGL(em_onehot_kernel, dim3((unsigned)nblk, nf), dim3(EM_BLOCK), 0, st, a, (const int32_t *)(base + o_lin));
-    EM_TRY(hipGetLastError());
-    EM_MSTEP();
+    MG_HIP_CHECK(hipGetLastError());
+    MG_HIP_CHECK(mstep());
     hipLaunchKernelGGL(em_state_kernel, dim3(nf), dim3(64), 0, st, a, (int)EM_STATE_INIT);
-    EM_TRY(hipGetLastError());
+    MG_HIP_CHECK(hipGetLastError());
     for (int it = 1; it <= max_iter && nf > 0; it++) {
         hipLaunchKernelGGL(estep, dim3((unsigned)nblk, nf), dim3(EM_BLOCK), 0, st, a, 0);
-        EM_TRY(hipGetLastError());
-        EM_MSTEP();
+        MG_HIP_CHECK(hipGetLastError());
+        MG_HIP_CHECK(mstep());
         hipLaunchKernelGGL(em_state_kernel, dim3(nf), dim3(64), 0, st, a, (int)EM_STATE_ITER);
-        EM_TRY(hipGetLastError());
+        MG_HIP_CHECK(hipGetLastError());
         if (it == next_check && it < max_iter) {    // drop the finished fits from the launches
             next_check = it < 8 ? it * 2 : it + 8;
-            EM_TRY(hipMemcpyAsync(state.data(), a.state, n_fits * 4, hipMemcpyDeviceToHost, st));
-            EM_TRY(hipStreamSynchronize(st));
+            MG_HIP_CHECK(hipMemcpyAsync(state.data(), a.state, n_fits * 4, hipMemcpyDeviceToHost, st));
+            MG_HIP_CHECK(hipStreamSynchronize(st));
             nf = nc = 0;
             for (int32_t f = 0; f < n_fits; f++)
                 if (state[f] == EM_RUN) {
@@ -456,32 +420,27 @@ extern "C" int mg_gmm_em_fit(mg_context *ctx, const double *points_dev, int64_t 
                     for (int32_t k = 0; k < n_comp[f]; k++) comps[nc++] = co[f] + k;
                 }
             if (nf > 0) {
-                EM_TRY(hipMemcpyAsync(base + o_fits, fits.data(), nf * 4, hipMemcpyHostToDevice, st));
-                EM_TRY(hipMemcpyAsync(base + o_comps, comps.data(), nc * 4, hipMemcpyHostToDevice, st));
-                EM_TRY(hipStreamSynchronize(st));    // the host lists are rewritten at the next check
+                MG_HIP_CHECK(hipMemcpyAsync(base + o_fits, fits.data(), nf * 4, hipMemcpyHostToDevice, st));
+                MG_HIP_CHECK(hipMemcpyAsync(base + o_comps, comps.data(), nc * 4, hipMemcpyHostToDevice, st));
+                MG_HIP_CHECK(hipStreamSynchronize(st));    // the host lists are rewritten at the next check
             }
         }
     }
     // the scoring pass over every fit that did not fail
     for (int32_t f = 0; f < n_fits; f++) fits[f] = f;
-    EM_TRY(hipMemcpyAsync(base + o_fits, fits.data(), n_fits * 4, hipMemcpyHostToDevice, st));
+    MG_HIP_CHECK(hipMemcpyAsync(base + o_fits, fits.data(), n_fits * 4, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(estep, dim3((unsigned)nblk, n_fits), dim3(EM_BLOCK), 0, st, a, 1);
     hipLaunchKernelGGL(em_state_kernel, dim3(n_fits), dim3(64), 0, st, a, (int)EM_STATE_SCORE);
-    EM_TRY(hipGetLastError());
-    EM_TRY(hipMemcpyAsync(weights, a.w, C * 8, hipMemcpyDeviceToHost, st));
-    EM_TRY(hipMemcpyAsync(means, a.means, (size_t)C * d * 8, hipMemcpyDeviceToHost, st));
-    EM_TRY(hipMemcpyAsync(covariances, a.cov, (size_t)C * d * d * 8, hipMemcpyDeviceToHost, st));
-    EM_TRY(hipMemcpyAsync(precisions_chol, a.prec, (size_t)C * d * d * 8, hipMemcpyDeviceToHost, st));
-    EM_TRY(hipMemcpyAsync(lower_bounds, a.lb, (size_t)n_fits * max_iter * 8, hipMemcpyDeviceToHost, st));
-    EM_TRY(hipMemcpyAsync(n_iter, a.n_iter, n_fits * 4, hipMemcpyDeviceToHost, st));
-    EM_TRY(hipMemcpyAsync(status, a.state, n_fits * 4, hipMemcpyDeviceToHost, st));
-    EM_TRY(hipMemcpyAsync(score, a.score, n_fits * 8, hipMemcpyDeviceToHost, st));
-    EM_TRY(hipMemcpyAsync(labels_out, a.labels, (size_t)n_fits * n * 4, hipMemcpyDeviceToHost, st));
-    EM_TRY(hipStreamSynchronize(st));
-done:
-#undef EM_TRY
-#undef EM_MSTEP
-    (void)hipStreamSynchronize(st);
-    (void)hipFree(base);
-    return rc;
+    MG_HIP_CHECK(hipGetLastError());
+    MG_HIP_CHECK(hipMemcpyAsync(weights, a.w, C * 8, hipMemcpyDeviceToHost, st));
+    MG_HIP_CHECK(hipMemcpyAsync(means, a.means, (size_t)C * d * 8, hipMemcpyDeviceToHost, st));
+    MG_HIP_CHECK(hipMemcpyAsync(covariances, a.cov, (size_t)C * d * d * 8, hipMemcpyDeviceToHost, st));
+    MG_HIP_CHECK(hipMemcpyAsync(precisions_chol, a.prec, (size_t)C * d * d * 8, hipMemcpyDeviceToHost, st));
+    MG_HIP_CHECK(hipMemcpyAsync(lower_bounds, a.lb, (size_t)n_fits * max_iter * 8, hipMemcpyDeviceToHost, st));
+    MG_HIP_CHECK(hipMemcpyAsync(n_iter, a.n_iter, n_fits * 4, hipMemcpyDeviceToHost, st));
+    MG_HIP_CHECK(hipMemcpyAsync(status, a.state, n_fits * 4, hipMemcpyDeviceToHost, st));
+    MG_HIP_CHECK(hipMemcpyAsync(score, a.score, n_fits * 8, hipMemcpyDeviceToHost, st));
+    MG_HIP_CHECK(hipMemcpyAsync(labels_out, a.labels, (size_t)n_fits * n * 4, hipMemcpyDeviceToHost, st));
+    MG_HIP_CHECK(hipStreamSynchronize(st));
+    return MG_OK;
 }

@@ -47,13 +47,7 @@ extern "C" const char *mg_status_string(int s) {
     }
 }
 
-#define MG_REQUIRE(cond, ...)            \
-    do {                                 \
-        if (!(cond)) {                   \
-            mg_set_error(__VA_ARGS__);   \
-            return MG_ERR_INVALID_ARGUMENT; \
-        }                                \
-    } while (0)
+#define MG_REQUIRE(cond, ...) MG_REQUIRE_AS(cond, MG_ERR_INVALID_ARGUMENT, __VA_ARGS__)
 
 // ---------------------------------------------------------------------------------------
 // RCCL, loaded on first use

@@ -24,6 +24,15 @@ int mg_hip_fail(hipError_t e, const char *what);
         if (_e != hipSuccess) return mg_hip_fail(_e, #expr); \
     } while (0)
 
+// argument checks of the entry points: set the error text and return `code`
+#define MG_REQUIRE_AS(cond, code, ...) \
+    do {                               \
+        if (!(cond)) {                 \
+            mg_set_error(__VA_ARGS__); \
+            return (code);             \
+        }                              \
+    } while (0)
+
 struct mg_event_pair {
     hipEvent_t a, b;
     int slot;

@@ -24,7 +24,7 @@
 // acquire hand-off, no co-residency assumed, no float atomics) combines the slots in slot order, moves the centres and
 // decides the unit's state, which the next launch reads.  The host reads the states every few launches.  Everything is
 // summed in a fixed order, so results are bit-reproducible.
-#include "mg_internal.h"
+#include "mg_construct.h"
 
 #include <algorithm>
 #include <cmath>
@@ -313,19 +313,6 @@ __device__ __forceinline__ double mg_km_uniform(uint64_t seed, uint32_t draw, ui
     return (double)(bits & ((1ull << 53) - 1)) * 0x1.0p-53;
 }
 
-// sum over the workgroup of one value per thread, in a fixed tree order
-__device__ __forceinline__ double mg_km_block_sum(double v, double *red) {
-    red[threadIdx.x] = v;
-    __syncthreads();
-    for (int s = MG_KM_BLOCK / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
-    const double r = red[0];
-    __syncthreads();
-    return r;
-}
-
 __global__ __launch_bounds__(MG_KM_BLOCK) void mg_kmeans_pp_kernel(mg_km_args a, const uint64_t *node_ids, uint64_t seed, int trials) {
     __shared__ double red[MG_KM_BLOCK];
     __shared__ double scan[MG_KM_BLOCK];
@@ -348,7 +335,7 @@ __global__ __launch_bounds__(MG_KM_BLOCK) void mg_kmeans_pp_kernel(mg_km_args a,
         closest[q] = v;
         mine += v;
     }
-    double pot = mg_km_block_sum(mine, red);
+    double pot = mg_block_sum<MG_KM_BLOCK>(mine, red);
     for (int c = 1; c < k; c++) {
         if (tid < trials) {
             target[tid] = mg_km_uniform(seed, draw + tid, run, node) * pot;
@@ -389,7 +376,7 @@ __global__ __launch_bounds__(MG_KM_BLOCK) void mg_kmeans_pp_kernel(mg_km_args a,
             }
         }
         for (int tr = 0; tr < trials; tr++) {
-            const double s = mg_km_block_sum(acc[tr], red);
+            const double s = mg_block_sum<MG_KM_BLOCK>(acc[tr], red);
             if (tid == 0) pot_t[tr] = s;
         }
         __syncthreads();
@@ -427,38 +414,28 @@ __global__ __launch_bounds__(MG_KM_BLOCK) void mg_kmeans_select_kernel(mg_km_arg
     }
 }
 
-#define MG_KM_REQUIRE(cond, code, ...) \
-    do {                               \
-        if (!(cond)) {                 \
-            mg_set_error(__VA_ARGS__); \
-            return code;               \
-        }                              \
-    } while (0)
-
-static size_t mg_km_align(size_t b) { return (b + 255) & ~(size_t)255; }
-
 extern "C" int mg_kmeans_segments(mg_context *ctx, const double *points_dev, int64_t n_rows, int32_t dim, int32_t n_segments,
                                   const int64_t *seg_begin, const int64_t *rows, int32_t k, int32_t n_init, const double *init,
                                   const uint64_t *node_ids, uint64_t seed, int32_t max_iter, double tol, int32_t *labels, double *centres,
                                   double *inertia, int32_t *n_iter) {
     const int BAD = MG_ERR_INVALID_ARGUMENT, UNS = MG_ERR_UNSUPPORTED;
-    MG_KM_REQUIRE(ctx && points_dev, BAD, "mg_kmeans_segments: NULL context or points");
-    MG_KM_REQUIRE(dim >= 1 && dim <= MG_KM_MAX_DIM, UNS, "mg_kmeans_segments: dim = %d outside [1, %d]", dim, MG_KM_MAX_DIM);
-    MG_KM_REQUIRE(k >= 2 && k <= MG_KM_MAX_K, UNS, "mg_kmeans_segments: k = %d outside [2, %d]", k, MG_KM_MAX_K);
-    MG_KM_REQUIRE(n_init >= 1 && n_init <= MG_KM_MAX_NINIT, UNS, "mg_kmeans_segments: n_init = %d outside [1, %d]", n_init, MG_KM_MAX_NINIT);
-    MG_KM_REQUIRE(init == nullptr || n_init == 1, BAD, "mg_kmeans_segments: initial centres given with n_init = %d (1 run per segment)", n_init);
-    MG_KM_REQUIRE(n_segments >= 0 && n_rows >= 1 && max_iter >= 1 && tol >= 0.0, BAD,
+    MG_REQUIRE_AS(ctx && points_dev, BAD, "mg_kmeans_segments: NULL context or points");
+    MG_REQUIRE_AS(dim >= 1 && dim <= MG_KM_MAX_DIM, UNS, "mg_kmeans_segments: dim = %d outside [1, %d]", dim, MG_KM_MAX_DIM);
+    MG_REQUIRE_AS(k >= 2 && k <= MG_KM_MAX_K, UNS, "mg_kmeans_segments: k = %d outside [2, %d]", k, MG_KM_MAX_K);
+    MG_REQUIRE_AS(n_init >= 1 && n_init <= MG_KM_MAX_NINIT, UNS, "mg_kmeans_segments: n_init = %d outside [1, %d]", n_init, MG_KM_MAX_NINIT);
+    MG_REQUIRE_AS(init == nullptr || n_init == 1, BAD, "mg_kmeans_segments: initial centres given with n_init = %d (1 run per segment)", n_init);
+    MG_REQUIRE_AS(n_segments >= 0 && n_rows >= 1 && max_iter >= 1 && tol >= 0.0, BAD,
                   "mg_kmeans_segments: n_segments = %d, n_rows = %lld, max_iter = %d, tol = %g", n_segments, (long long)n_rows, max_iter, tol);
     if (n_segments == 0) return MG_OK;
-    MG_KM_REQUIRE(seg_begin && rows && labels && centres && inertia && n_iter, BAD, "mg_kmeans_segments: NULL argument");
-    MG_KM_REQUIRE(seg_begin[0] == 0, BAD, "mg_kmeans_segments: seg_begin[0] = %lld, not 0", (long long)seg_begin[0]);
+    MG_REQUIRE_AS(seg_begin && rows && labels && centres && inertia && n_iter, BAD, "mg_kmeans_segments: NULL argument");
+    MG_REQUIRE_AS(seg_begin[0] == 0, BAD, "mg_kmeans_segments: seg_begin[0] = %lld, not 0", (long long)seg_begin[0]);
     for (int32_t s = 0; s < n_segments; s++)
-        MG_KM_REQUIRE(seg_begin[s + 1] - seg_begin[s] >= k, BAD, "mg_kmeans_segments: segment %d has %lld rows, fewer than k = %d", s,
+        MG_REQUIRE_AS(seg_begin[s + 1] - seg_begin[s] >= k, BAD, "mg_kmeans_segments: segment %d has %lld rows, fewer than k = %d", s,
                       (long long)(seg_begin[s + 1] - seg_begin[s]), k);
     const int64_t n_pos = seg_begin[n_segments];
-    MG_KM_REQUIRE(n_pos * n_init < ((int64_t)1 << 31), UNS, "mg_kmeans_segments: %lld positions x %d runs beyond 2^31", (long long)n_pos, n_init);
+    MG_REQUIRE_AS(n_pos * n_init < ((int64_t)1 << 31), UNS, "mg_kmeans_segments: %lld positions x %d runs beyond 2^31", (long long)n_pos, n_init);
     for (int64_t p = 0; p < n_pos; p++)
-        MG_KM_REQUIRE(rows[p] >= 0 && rows[p] < n_rows, BAD, "mg_kmeans_segments: rows[%lld] = %lld outside [0, %lld)", (long long)p,
+        MG_REQUIRE_AS(rows[p] >= 0 && rows[p] < n_rows, BAD, "mg_kmeans_segments: rows[%lld] = %lld outside [0, %lld)", (long long)p,
                       (long long)rows[p], (long long)n_rows);
     const int U = n_segments * n_init, kd = k * dim;
     const int pstride = kd + k + 2 + 2 * dim;
@@ -478,17 +455,19 @@ extern "C" int mg_kmeans_segments(mg_context *ctx, const double *points_dev, int
     }
     std::vector<uint64_t> ids(n_segments);
     for (int32_t s = 0; s < n_segments; s++) ids[s] = node_ids ? node_ids[s] : (uint64_t)s;
-    // one device block for everything the call needs
-    size_t off = 0;
-    auto carve = [&](size_t bytes) { const size_t o = off; off += mg_km_align(bytes); return o; };
+    std::vector<int32_t> state(U);
+    std::vector<mg_km_tile> active;
+    // one device block for everything the call needs; declared after the host buffers its copies touch: it drains the stream first
+    mg_workspace ws(ctx, "mg_kmeans_segments");
+    auto carve = [&](size_t bytes) { return ws.carve(bytes); };
     const size_t o_rows = carve(n_pos * 8), o_tiles = carve(tiles.size() * sizeof(mg_km_tile)), o_segt = carve(seg_tiles.size() * sizeof(mg_km_tile));
     const size_t o_units = carve(U * sizeof(mg_km_unit)), o_ids = carve(n_segments * 8), o_cent = carve((size_t)U * kd * 8);
     const size_t o_lab = carve((size_t)n_init * n_pos * 4), o_dist = carve((size_t)n_init * n_pos * 8), o_part = carve((size_t)slots * pstride * 8);
     const size_t o_state = carve(U * 4), o_iter = carve(U * 4), o_cnt = carve(U * 4), o_tol = carve(U * 8), o_inert = carve(U * 8);
     const size_t o_lout = carve(n_pos * 4), o_cout = carve((size_t)n_segments * kd * 8), o_iout = carve(n_segments * 8), o_nout = carve(n_segments * 4);
-    MG_HIP_CHECK(hipSetDevice(ctx->device));
-    char *base = nullptr;
-    MG_HIP_CHECK(hipMalloc(&base, off));
+    const int ra = ws.alloc();
+    if (ra != MG_OK) return ra;
+    char *const base = ws.base;
     hipStream_t st = ctx->stream;
     mg_km_args a;
     a.points = points_dev;
@@ -506,68 +485,51 @@ extern "C" int mg_kmeans_segments(mg_context *ctx, const double *points_dev, int
     a.inertia = (double *)(base + o_inert);
     a.tol = tol;
     a.dim = dim; a.k = k; a.n_init = n_init; a.max_iter = max_iter; a.pstride = pstride; a.n_pos = (int32_t)n_pos;
-    int rc = MG_OK;
-    std::vector<int32_t> state(U);
     const size_t lds = (size_t)(2 * kd + k + 1 + 2 * dim + MG_KM_BLOCK) * 8 + (MG_KM_BLOCK + 4 + MG_KM_MAX_K) * 4;
     const int trials = 2 + (int)std::log((double)k);
     int launches = 0, next_check = 1;
-    std::vector<mg_km_tile> active;
-#define MG_KM_TRY(expr)                                            \
-    do {                                                           \
-        hipError_t _e = (expr);                                    \
-        if (_e != hipSuccess) { rc = mg_hip_fail(_e, #expr); goto done; } \
-    } while (0)
-    MG_KM_TRY(hipMemcpyAsync(base + o_rows, rows, n_pos * 8, hipMemcpyHostToDevice, st));
-    MG_KM_TRY(hipMemcpyAsync(base + o_tiles, tiles.data(), tiles.size() * sizeof(mg_km_tile), hipMemcpyHostToDevice, st));
-    MG_KM_TRY(hipMemcpyAsync(base + o_segt, seg_tiles.data(), seg_tiles.size() * sizeof(mg_km_tile), hipMemcpyHostToDevice, st));
-    MG_KM_TRY(hipMemcpyAsync(base + o_units, units.data(), U * sizeof(mg_km_unit), hipMemcpyHostToDevice, st));
-    MG_KM_TRY(hipMemcpyAsync(base + o_ids, ids.data(), n_segments * 8, hipMemcpyHostToDevice, st));
-    MG_KM_TRY(hipMemsetAsync(base + o_state, 0, o_tol - o_state, st));        // state, n_iter, counters
+    MG_HIP_CHECK(hipMemcpyAsync(base + o_rows, rows, n_pos * 8, hipMemcpyHostToDevice, st));
+    MG_HIP_CHECK(hipMemcpyAsync(base + o_tiles, tiles.data(), tiles.size() * sizeof(mg_km_tile), hipMemcpyHostToDevice, st));
+    MG_HIP_CHECK(hipMemcpyAsync(base + o_segt, seg_tiles.data(), seg_tiles.size() * sizeof(mg_km_tile), hipMemcpyHostToDevice, st));
+    MG_HIP_CHECK(hipMemcpyAsync(base + o_units, units.data(), U * sizeof(mg_km_unit), hipMemcpyHostToDevice, st));
+    MG_HIP_CHECK(hipMemcpyAsync(base + o_ids, ids.data(), n_segments * 8, hipMemcpyHostToDevice, st));
+    MG_HIP_CHECK(hipMemsetAsync(base + o_state, 0, o_tol - o_state, st));        // state, n_iter, counters
     if (init) {
-        MG_KM_TRY(hipMemcpyAsync(a.centres, init, (size_t)U * kd * 8, hipMemcpyHostToDevice, st));
+        MG_HIP_CHECK(hipMemcpyAsync(a.centres, init, (size_t)U * kd * 8, hipMemcpyHostToDevice, st));
     } else {
         hipLaunchKernelGGL(mg_kmeans_pp_kernel, dim3(U), dim3(MG_KM_BLOCK), 0, st, a, (const uint64_t *)(base + o_ids), seed, trials);
-        MG_KM_TRY(hipGetLastError());
+        MG_HIP_CHECK(hipGetLastError());
     }
-    MG_KM_TRY(hipMemsetAsync(a.labels, 0xFF, (size_t)n_init * n_pos * 4, st));   // label -1: every label of iteration 0 changes
+    MG_HIP_CHECK(hipMemsetAsync(a.labels, 0xFF, (size_t)n_init * n_pos * 4, st));   // label -1: every label of iteration 0 changes
     // what this call needs, not the whole 160 KiB: __syncthreads_count keeps a static word in the LDS, and static + dynamic past 160 KiB is refused
-    if (lds > 64 * 1024) MG_KM_TRY(hipFuncSetAttribute((const void *)mg_kmeans_lloyd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if (lds > 64 * 1024) MG_HIP_CHECK(hipFuncSetAttribute((const void *)mg_kmeans_lloyd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     active = tiles;
     // every unit needs at most max_iter iterations and one final pass
     while (launches < max_iter + 1 && !active.empty()) {
         hipLaunchKernelGGL(mg_kmeans_lloyd_kernel, dim3((unsigned)active.size()), dim3(MG_KM_BLOCK), lds, st, a);
-        MG_KM_TRY(hipGetLastError());
+        MG_HIP_CHECK(hipGetLastError());
         launches++;
         if (launches == next_check || launches == max_iter + 1) {
             next_check = launches < 8 ? launches * 2 : launches + 8;
-            MG_KM_TRY(hipMemcpyAsync(state.data(), a.state, U * 4, hipMemcpyDeviceToHost, st));
-            MG_KM_TRY(hipStreamSynchronize(st));
+            MG_HIP_CHECK(hipMemcpyAsync(state.data(), a.state, U * 4, hipMemcpyDeviceToHost, st));
+            MG_HIP_CHECK(hipStreamSynchronize(st));
             std::vector<mg_km_tile> still;
             for (const mg_km_tile &t : tiles)
                 if (state[t.unit] != MG_KM_DONE) still.push_back(t);
             if (still.size() != active.size() && !still.empty())
-                MG_KM_TRY(hipMemcpyAsync(base + o_tiles, still.data(), still.size() * sizeof(mg_km_tile), hipMemcpyHostToDevice, st));
+                MG_HIP_CHECK(hipMemcpyAsync(base + o_tiles, still.data(), still.size() * sizeof(mg_km_tile), hipMemcpyHostToDevice, st));
             active.swap(still);
         }
     }
-    if (!active.empty()) {
-        mg_set_error("mg_kmeans_segments: a unit did not finish in %d launches", launches);
-        rc = MG_ERR_INVALID_ARGUMENT;
-        goto done;
-    }
+    MG_REQUIRE_AS(active.empty(), MG_ERR_INVALID_ARGUMENT, "mg_kmeans_segments: a unit did not finish in %d launches", launches);
     hipLaunchKernelGGL(mg_kmeans_select_kernel, dim3((unsigned)seg_tiles.size()), dim3(MG_KM_BLOCK), 0, st, a,
                        (const mg_km_tile *)(base + o_segt), (int32_t *)(base + o_lout), (double *)(base + o_cout), (double *)(base + o_iout),
                        (int32_t *)(base + o_nout));
-    MG_KM_TRY(hipGetLastError());
-    MG_KM_TRY(hipMemcpyAsync(labels, base + o_lout, n_pos * 4, hipMemcpyDeviceToHost, st));
-    MG_KM_TRY(hipMemcpyAsync(centres, base + o_cout, (size_t)n_segments * kd * 8, hipMemcpyDeviceToHost, st));
-    MG_KM_TRY(hipMemcpyAsync(inertia, base + o_iout, n_segments * 8, hipMemcpyDeviceToHost, st));
-    MG_KM_TRY(hipMemcpyAsync(n_iter, base + o_nout, n_segments * 4, hipMemcpyDeviceToHost, st));
-    MG_KM_TRY(hipStreamSynchronize(st));
-done:
-#undef MG_KM_TRY
-    (void)hipStreamSynchronize(st);
-    (void)hipFree(base);
-    if (rc != MG_OK) (void)hipGetLastError();   // a failed call leaves no error behind for the next one's hipGetLastError
-    return rc;
+    MG_HIP_CHECK(hipGetLastError());
+    MG_HIP_CHECK(hipMemcpyAsync(labels, base + o_lout, n_pos * 4, hipMemcpyDeviceToHost, st));
+    MG_HIP_CHECK(hipMemcpyAsync(centres, base + o_cout, (size_t)n_segments * kd * 8, hipMemcpyDeviceToHost, st));
+    MG_HIP_CHECK(hipMemcpyAsync(inertia, base + o_iout, n_segments * 8, hipMemcpyDeviceToHost, st));
+    MG_HIP_CHECK(hipMemcpyAsync(n_iter, base + o_nout, n_segments * 4, hipMemcpyDeviceToHost, st));
+    MG_HIP_CHECK(hipStreamSynchronize(st));
+    return MG_OK;
 }

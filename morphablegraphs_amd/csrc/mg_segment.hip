@@ -192,38 +192,28 @@ __global__ __launch_bounds__(SEG_BLOCK) void segment_search_kernel(const double 
 
 // ---- host --------------------------------------------------------------------------------------------------------------------
 static int seg_check_offsets(const char *who, const int64_t *offsets, int64_t n_motions, int code_too_long) {
-    DTW_REQUIRE(offsets[0] == 0, MG_ERR_INVALID_ARGUMENT, "%s: offsets[0] = %lld, not 0", who, (long long)offsets[0]);
-    for (int64_t n = 0; n < n_motions; n++) {
-        const int64_t f = offsets[n + 1] - offsets[n];
-        DTW_REQUIRE(f >= 1, MG_ERR_INVALID_ARGUMENT, "%s: motion %lld has %lld frames (offsets must rise)", who, (long long)n, (long long)f);
-        DTW_REQUIRE(f <= INT32_MAX, code_too_long, "%s: motion %lld has %lld frames (fewer than 2^31)", who, (long long)n, (long long)f);
-    }
-    return MG_OK;
+    int64_t longest = 0;
+    return mg_check_offsets(who, offsets, n_motions, INT32_MAX, "fewer than 2^31", code_too_long, &longest);
 }
 
 extern "C" int mg_keyframe_distances(mg_context *ctx, const double *clouds_dev, const int64_t *offsets, int64_t n_motions, int32_t n_joints,
                                      const double *keyframes_dev, int32_t n_keyframes, const double *weights, double *dist_dev) {
-    DTW_REQUIRE(ctx && offsets, MG_ERR_INVALID_ARGUMENT, "mg_keyframe_distances: NULL argument");
-    DTW_REQUIRE(n_motions >= 0, MG_ERR_INVALID_ARGUMENT, "mg_keyframe_distances: n_motions = %lld", (long long)n_motions);
-    DTW_REQUIRE(n_joints >= 1 && n_joints <= DTW_MAX_JOINTS, MG_ERR_INVALID_ARGUMENT, "mg_keyframe_distances: %d joints (1 to %d)", n_joints,
-                DTW_MAX_JOINTS);
-    DTW_REQUIRE(n_keyframes >= 1 && n_keyframes <= SEG_MAX_KEYFRAMES, MG_ERR_INVALID_ARGUMENT, "mg_keyframe_distances: %d keyframes (1 to %d)",
-                n_keyframes, SEG_MAX_KEYFRAMES);
+    MG_REQUIRE_AS(ctx && offsets, MG_ERR_INVALID_ARGUMENT, "mg_keyframe_distances: NULL argument");
+    MG_REQUIRE_AS(n_motions >= 0, MG_ERR_INVALID_ARGUMENT, "mg_keyframe_distances: n_motions = %lld", (long long)n_motions);
+    MG_REQUIRE_AS(n_joints >= 1 && n_joints <= DTW_MAX_JOINTS, MG_ERR_INVALID_ARGUMENT, "mg_keyframe_distances: %d joints (1 to %d)", n_joints,
+                  DTW_MAX_JOINTS);
+    MG_REQUIRE_AS(n_keyframes >= 1 && n_keyframes <= SEG_MAX_KEYFRAMES, MG_ERR_INVALID_ARGUMENT, "mg_keyframe_distances: %d keyframes (1 to %d)",
+                  n_keyframes, SEG_MAX_KEYFRAMES);
     const int rc = seg_check_offsets("mg_keyframe_distances", offsets, n_motions, MG_ERR_INVALID_ARGUMENT);
     if (rc != MG_OK || n_motions == 0) return rc;
-    DTW_REQUIRE(clouds_dev && keyframes_dev && dist_dev, MG_ERR_INVALID_ARGUMENT, "mg_keyframe_distances: NULL argument");
+    MG_REQUIRE_AS(clouds_dev && keyframes_dev && dist_dev, MG_ERR_INVALID_ARGUMENT, "mg_keyframe_distances: NULL argument");
     const int64_t total = offsets[n_motions];
-    DTW_REQUIRE((total + SEG_FRAMES - 1) / SEG_FRAMES <= INT32_MAX, MG_ERR_INVALID_ARGUMENT, "mg_keyframe_distances: %lld frames", (long long)total);
-    double ones[DTW_MAX_JOINTS], wsum = 0.0;
-    for (int k = 0; k < n_joints; k++) {
-        ones[k] = weights ? weights[k] : 1.0;
-        DTW_REQUIRE(std::isfinite(ones[k]) && ones[k] >= 0.0, MG_ERR_INVALID_ARGUMENT, "mg_keyframe_distances: weight %d is %g", k, ones[k]);
-        wsum += ones[k];
-    }
-    DTW_REQUIRE(wsum > 0.0, MG_ERR_INVALID_ARGUMENT, "mg_keyframe_distances: the weights add up to 0");
-    MG_HIP_CHECK(hipSetDevice(ctx->device));
-    dtw_block blk;
-    const int rb = dtw_block_create("mg_keyframe_distances", ctx, &blk, offsets, 0, ones, n_joints, 0);   // the kernel needs no offsets
+    MG_REQUIRE_AS((total + SEG_FRAMES - 1) / SEG_FRAMES <= INT32_MAX, MG_ERR_INVALID_ARGUMENT, "mg_keyframe_distances: %lld frames", (long long)total);
+    double ones[DTW_MAX_JOINTS];
+    const int rw = dtw_weights("mg_keyframe_distances", weights, n_joints, ones);
+    if (rw != MG_OK) return rw;
+    dtw_block blk(ctx, "mg_keyframe_distances");
+    const int rb = dtw_block_create(&blk, offsets, 0, ones, n_joints, 0);   // the kernel needs no offsets
     if (rb != MG_OK) return rb;
     const int64_t row_len = 3 * (int64_t)n_joints;
     dtw_launch_nonfinite(ctx, clouds_dev, total * row_len, blk.flag);
@@ -231,7 +221,7 @@ extern "C" int mg_keyframe_distances(mg_context *ctx, const double *clouds_dev, 
     int32_t flag = 0;
     const int rf = dtw_flag_after(ctx, blk, &flag);
     if (rf != MG_OK) return rf;
-    DTW_REQUIRE(!flag, MG_ERR_INVALID_ARGUMENT, "mg_keyframe_distances: the point clouds or the keyframes hold non-finite values");
+    MG_REQUIRE_AS(!flag, MG_ERR_INVALID_ARGUMENT, "mg_keyframe_distances: the point clouds or the keyframes hold non-finite values");
     const size_t lds = ((size_t)(SEG_FRAMES + n_keyframes) * ((3 * n_joints) | 1) + DTW_MAX_JOINTS + 2 * SEG_MAX_KEYFRAMES + 1) * 8;   // at most 111 816 bytes
     if (lds > 64 * 1024)
         MG_HIP_CHECK(hipFuncSetAttribute((const void *)keyframe_distances_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -245,31 +235,29 @@ extern "C" int mg_keyframe_distances(mg_context *ctx, const double *clouds_dev, 
 extern "C" int mg_segment_search(mg_context *ctx, const double *start_dist_dev, const double *end_dist_dev, const int64_t *offsets, int64_t n_motions,
                                  int32_t mode, double threshold, int32_t min_segment_size, const int64_t *segment_offsets, int32_t *segments_dev,
                                  int32_t *counts_dev) {
-    DTW_REQUIRE(ctx && offsets && segment_offsets, MG_ERR_INVALID_ARGUMENT, "mg_segment_search: NULL argument");
-    DTW_REQUIRE(n_motions >= 0, MG_ERR_INVALID_ARGUMENT, "mg_segment_search: n_motions = %lld", (long long)n_motions);
-    DTW_REQUIRE(n_motions < ((int64_t)1 << 31), MG_ERR_UNSUPPORTED, "mg_segment_search: %lld motions (fewer than 2^31)", (long long)n_motions);
-    DTW_REQUIRE(mode == MG_SEGMENT_SINGLE || mode == MG_SEGMENT_MULTI, MG_ERR_INVALID_ARGUMENT, "mg_segment_search: mode %d", mode);
+    MG_REQUIRE_AS(ctx && offsets && segment_offsets, MG_ERR_INVALID_ARGUMENT, "mg_segment_search: NULL argument");
+    MG_REQUIRE_AS(n_motions >= 0, MG_ERR_INVALID_ARGUMENT, "mg_segment_search: n_motions = %lld", (long long)n_motions);
+    MG_REQUIRE_AS(n_motions < ((int64_t)1 << 31), MG_ERR_UNSUPPORTED, "mg_segment_search: %lld motions (fewer than 2^31)", (long long)n_motions);
+    MG_REQUIRE_AS(mode == MG_SEGMENT_SINGLE || mode == MG_SEGMENT_MULTI, MG_ERR_INVALID_ARGUMENT, "mg_segment_search: mode %d", mode);
     if (mode == MG_SEGMENT_MULTI) {
-        DTW_REQUIRE(!std::isnan(threshold), MG_ERR_INVALID_ARGUMENT, "mg_segment_search: the threshold is not a number");
-        DTW_REQUIRE(min_segment_size >= 0, MG_ERR_INVALID_ARGUMENT, "mg_segment_search: min_segment_size = %d", min_segment_size);
+        MG_REQUIRE_AS(!std::isnan(threshold), MG_ERR_INVALID_ARGUMENT, "mg_segment_search: the threshold is not a number");
+        MG_REQUIRE_AS(min_segment_size >= 0, MG_ERR_INVALID_ARGUMENT, "mg_segment_search: min_segment_size = %d", min_segment_size);
     }
     const int rc = seg_check_offsets("mg_segment_search", offsets, n_motions, MG_ERR_UNSUPPORTED);
     if (rc != MG_OK) return rc;
-    DTW_REQUIRE(segment_offsets[0] >= 0, MG_ERR_INVALID_ARGUMENT, "mg_segment_search: segment_offsets[0] = %lld", (long long)segment_offsets[0]);
+    MG_REQUIRE_AS(segment_offsets[0] >= 0, MG_ERR_INVALID_ARGUMENT, "mg_segment_search: segment_offsets[0] = %lld", (long long)segment_offsets[0]);
     for (int64_t n = 0; n < n_motions; n++) {
         const int64_t f = offsets[n + 1] - offsets[n], room = segment_offsets[n + 1] - segment_offsets[n];
         const int64_t need = mode == MG_SEGMENT_SINGLE ? 1 : f / ((int64_t)min_segment_size + 1) + 1;
-        DTW_REQUIRE(room >= need, MG_ERR_INVALID_ARGUMENT, "mg_segment_search: motion %lld of %lld frames has room for %lld pairs (%lld needed)", (long long)n,
-                    (long long)f, (long long)room, (long long)need);
+        MG_REQUIRE_AS(room >= need, MG_ERR_INVALID_ARGUMENT, "mg_segment_search: motion %lld of %lld frames has room for %lld pairs (%lld needed)", (long long)n,
+                      (long long)f, (long long)room, (long long)need);
     }
     if (n_motions == 0) return MG_OK;
-    DTW_REQUIRE(start_dist_dev && end_dist_dev && segments_dev && counts_dev, MG_ERR_INVALID_ARGUMENT, "mg_segment_search: NULL argument");
-    MG_HIP_CHECK(hipSetDevice(ctx->device));
+    MG_REQUIRE_AS(start_dist_dev && end_dist_dev && segments_dev && counts_dev, MG_ERR_INVALID_ARGUMENT, "mg_segment_search: NULL argument");
     const int64_t total = offsets[n_motions];
-    const size_t seg_off_bytes = (((size_t)n_motions + 1) * 8 + 255) & ~(size_t)255;
-    dtw_block blk;
-    const int rb = dtw_block_create("mg_segment_search", ctx, &blk, offsets, n_motions, nullptr, 0,
-                                    seg_off_bytes + (mode == MG_SEGMENT_MULTI ? (size_t)total * 8 : 0));
+    const size_t seg_off_bytes = mg_workspace::align(((size_t)n_motions + 1) * 8);
+    dtw_block blk(ctx, "mg_segment_search");
+    const int rb = dtw_block_create(&blk, offsets, n_motions, nullptr, 0, seg_off_bytes + (mode == MG_SEGMENT_MULTI ? (size_t)total * 8 : 0));
     if (rb != MG_OK) return rb;
     MG_HIP_CHECK(hipMemcpyAsync(blk.extra, segment_offsets, ((size_t)n_motions + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
     dtw_launch_nonfinite(ctx, start_dist_dev, total, blk.flag);
@@ -277,7 +265,7 @@ extern "C" int mg_segment_search(mg_context *ctx, const double *start_dist_dev, 
     int32_t flag = 0;
     const int rf = dtw_flag_after(ctx, blk, &flag);
     if (rf != MG_OK) return rf;
-    DTW_REQUIRE(!flag, MG_ERR_INVALID_ARGUMENT, "mg_segment_search: the distances hold non-finite values");
+    MG_REQUIRE_AS(!flag, MG_ERR_INVALID_ARGUMENT, "mg_segment_search: the distances hold non-finite values");
     hipLaunchKernelGGL(segment_search_kernel, dim3((unsigned)n_motions), dim3(SEG_BLOCK), 0, ctx->stream, start_dist_dev, end_dist_dev,
                        (const int64_t *)blk.off, (const int64_t *)blk.extra, mode, threshold, min_segment_size, (int32_t *)(blk.extra + seg_off_bytes), total,
                        segments_dev, counts_dev);

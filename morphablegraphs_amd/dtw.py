@@ -126,13 +126,6 @@ def get_average_time_line(motions):
 
 
 # ---- the device ------------------------------------------------------------------------------------------------------------
-def _context(ctx):
-    if ctx is not None:
-        return ctx
-    from .motion_primitive import get_context
-    return get_context(0)
-
-
 def _offsets(lengths):
     return np.concatenate([[0], np.cumsum(np.asarray(lengths, dtype=np.int64))]).astype(np.int64)
 
@@ -143,26 +136,6 @@ def _check_limits(n_ref_frames, lengths, n_joints=1):
         raise ValueError("DTW: %d frames (at most %d), %d joints (at most %d)" % (longest, MAX_FRAMES, n_joints, MAX_JOINTS))
     if n_ref_frames < 1 or any(f < 1 for f in lengths):
         raise ValueError("DTW: a motion without frames")
-
-
-class _Buffers(object):
-    def __init__(self, ctx):
-        self.ctx, self.bufs = ctx, []
-
-    def upload(self, arr):
-        self.bufs.append(self.ctx.upload(np.ascontiguousarray(arr)))
-        return self.bufs[-1]
-
-    def malloc(self, nbytes):
-        self.bufs.append(self.ctx.malloc(max(int(nbytes), 8)))
-        return self.bufs[-1]
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        for b in self.bufs:
-            b.free()
 
 
 def _paths_on_device(ctx, bufs, grids_dev, n_ref_frames, offsets, accumulated):
@@ -189,14 +162,14 @@ def _paths_on_device(ctx, bufs, grids_dev, n_ref_frames, offsets, accumulated):
 def distance_grids(ref_cloud, clouds, weights=None, ctx=None):
     """mg_dtw_distance_grids: the grids S[n] (Fr, F_n) of the clouds `clouds` (a list of (F_n, J, 3) arrays) against
     ref_cloud (Fr, J, 3)."""
-    ctx = _context(ctx)
+    ctx = _capi.default_context(ctx)
     ref = np.ascontiguousarray(ref_cloud, dtype=np.float64)
     clouds = [np.asarray(c, dtype=np.float64).reshape(-1, ref.shape[1], 3) for c in clouds]
     if not clouds:
         return []
     _check_limits(len(ref), [len(c) for c in clouds], ref.shape[1])
     off = _offsets([len(c) for c in clouds])
-    with _Buffers(ctx) as bufs:
+    with ctx.buffers() as bufs:
         a_dev, b_dev, s_dev = bufs.upload(ref), bufs.upload(np.concatenate(clouds)), bufs.malloc(8 * len(ref) * int(off[-1]))
         _capi.dtw_distance_grids(ctx, a_dev, len(ref), b_dev, off, ref.shape[1], weights, s_dev)
         S = ctx.download(s_dev, (len(ref) * int(off[-1]),), np.float64)
@@ -206,7 +179,7 @@ def distance_grids(ref_cloud, clouds, weights=None, ctx=None):
 def paths_from_grids(grids, accumulated=True, ctx=None):
     """mg_dtw_paths on given grids (a list of (Fr, F_n) arrays with one Fr): per grid {"D" (None without accumulated),
     "total", "path" (L, 2) int32, "warping_function" (Fr,) int32}."""
-    ctx = _context(ctx)
+    ctx = _capi.default_context(ctx)
     grids = [np.ascontiguousarray(g, dtype=np.float64) for g in grids]
     if not grids:
         return []
@@ -215,7 +188,7 @@ def paths_from_grids(grids, accumulated=True, ctx=None):
         raise ValueError("the grids of one call have the reference motion's frames as their rows")
     _check_limits(fr, [g.shape[1] for g in grids])
     off = _offsets([g.shape[1] for g in grids])
-    with _Buffers(ctx) as bufs:
+    with ctx.buffers() as bufs:
         s_dev = bufs.upload(np.concatenate([g.reshape(-1) for g in grids]))
         return _paths_on_device(ctx, bufs, s_dev, fr, off, accumulated)[0]
 
@@ -223,14 +196,14 @@ def paths_from_grids(grids, accumulated=True, ctx=None):
 def dtw_batch(ref_cloud, clouds, weights=None, accumulated=False, ctx=None):
     """Grids and paths of N clouds against ref_cloud without leaving the device in between; per motion the dict of
     paths_from_grids."""
-    ctx = _context(ctx)
+    ctx = _capi.default_context(ctx)
     ref = np.ascontiguousarray(ref_cloud, dtype=np.float64)
     clouds = [np.asarray(c, dtype=np.float64).reshape(-1, ref.shape[1], 3) for c in clouds]
     if not clouds:
         return []
     _check_limits(len(ref), [len(c) for c in clouds], ref.shape[1])
     off = _offsets([len(c) for c in clouds])
-    with _Buffers(ctx) as bufs:
+    with ctx.buffers() as bufs:
         a_dev, b_dev, s_dev = bufs.upload(ref), bufs.upload(np.concatenate(clouds)), bufs.malloc(8 * len(ref) * int(off[-1]))
         _capi.dtw_distance_grids(ctx, a_dev, len(ref), b_dev, off, ref.shape[1], weights, s_dev)
         return _paths_on_device(ctx, bufs, s_dev, len(ref), off, accumulated)[0]
@@ -262,15 +235,14 @@ def _align_section(ctx, skeleton, joints, motions, mean_key):
     n_dim = frames[0].shape[1]
     if any(f.ndim != 2 or f.shape[1] != n_dim for f in frames):
         raise ValueError("the motions of one call have the same channels")
-    idx = np.ascontiguousarray([skeleton.index(j) for j in joints], dtype=np.int32)
+    idx = skeleton.indices(joints)
     fr = len(motions[mean_key])
     _check_limits(fr, [len(f) for f in frames], len(idx))
     off = _offsets([len(f) for f in frames])
     total, n, nj = int(off[-1]), len(keys), len(idx)
-    with _Buffers(ctx) as bufs:
+    with ctx.buffers() as bufs:
         f_dev, c_dev = bufs.upload(np.concatenate(frames)), bufs.malloc(8 * total * nj * 3)
-        d = skeleton.desc()
-        _capi._check(ctx.lib.mg_joint_positions(ctx.handle, _capi.C.byref(d), idx.ctypes.data_as(_capi.C.c_void_p), nj, f_dev.ptr, total, n_dim, c_dev.ptr))
+        ctx.joint_positions_dev(skeleton, idx, f_dev, total, n_dim, c_dev)
         ref_dev = c_dev.address + 8 * int(off[keys.index(mean_key)]) * nj * 3      # the reference motion's clouds, where they lie
         s_dev = bufs.malloc(8 * fr * total)
         _capi.dtw_distance_grids(ctx, ref_dev, fr, c_dev, off, nj, None, s_dev)
@@ -290,7 +262,7 @@ def align_frames_temporally(skeleton, joints, motions, mean_key=None, sections=N
     positions make a frame's point cloud (mg_joint_positions).  mean_key: the reference motion (None:
     get_average_time_line).  sections: {key: [{"start_idx", "end_idx"}, ...]}: every motion is cut into its sections on the
     host, the sections are aligned one batched call each, and the results are concatenated."""
-    ctx = _context(ctx)
+    ctx = _capi.default_context(ctx)
     if mean_key is None:
         mean_key = get_average_time_line(motions)
     if mean_key not in motions:

@@ -207,13 +207,6 @@ def gen_gaussian_eigen(covars):
 
 
 # ---- the device ------------------------------------------------------------------------------------------------------------
-def _context(ctx):
-    if ctx is not None:
-        return ctx
-    from .motion_primitive import get_context
-    return get_context(0)
-
-
 class _DevicePCA(object):
     """mg_pca_fit of a device matrix and the projections on its leading rows; owns the centred matrix on the device."""
 
@@ -223,12 +216,10 @@ class _DevicePCA(object):
         if min(self.n, self.p) > MAX_SHORT_SIDE or max(self.n, self.p) > MAX_LONG_SIDE:
             raise ValueError("PCA of a %d x %d matrix: the short side may have at most %d, the long side %d" % (self.n, self.p, MAX_SHORT_SIDE,
                                                                                                             MAX_LONG_SIDE))
-        self.centred_dev = ctx.malloc(8 * self.n * self.p)
-        try:
-            self.fit = _capi.pca_fit(ctx, a_dev, n, p, self.centred_dev, centre)
-        except Exception:
-            self.free_centred()
-            raise
+        with ctx.buffers() as bufs:
+            centred_dev = bufs.malloc(8 * self.n * self.p)
+            self.fit = _capi.pca_fit(ctx, a_dev, n, p, centred_dev, centre)
+            self.centred_dev = bufs.release(centred_dev)
 
     def centred(self):
         return self.ctx.download(self.centred_dev, (self.n, self.p), np.float64)
@@ -240,34 +231,26 @@ class _DevicePCA(object):
         self.mean_dev = self.ctx.upload(self.fit["mean"])
 
     def project(self, x_dev, n):
-        low_dev = self.ctx.malloc(8 * int(n) * self.l)
-        try:
+        with self.ctx.buffers() as bufs:
+            low_dev = bufs.malloc(8 * int(n) * self.l)
             _capi.pca_project(self.ctx, x_dev, self.vt_dev, n, self.p, self.l, low_dev)
             return self.ctx.download(low_dev, (int(n), self.l), np.float64)
-        finally:
-            low_dev.free()
 
     def project_host(self, data):
         data = np.ascontiguousarray(data, dtype=np.float64).reshape(-1, self.p)
         if self.l == 0 or len(data) == 0:
             return np.zeros((len(data), self.l))
-        x_dev = self.ctx.upload(data)
-        try:
-            return self.project(x_dev, len(data))
-        finally:
-            x_dev.free()
+        with self.ctx.buffers() as bufs:
+            return self.project(bufs.upload(data), len(data))
 
     def backproject_host(self, low_vecs):
         low = np.ascontiguousarray(low_vecs, dtype=np.float64).reshape(-1, self.l)
         if self.l == 0 or len(low) == 0:
             return np.tile(self.fit["mean"], (len(low), 1))
-        low_dev, high_dev = self.ctx.upload(low), self.ctx.malloc(8 * len(low) * self.p)
-        try:
+        with self.ctx.buffers() as bufs:
+            low_dev, high_dev = bufs.upload(low), bufs.malloc(8 * len(low) * self.p)
             _capi.pca_backproject(self.ctx, low_dev, self.vt_dev, self.mean_dev, len(low), self.p, self.l, high_dev)
             return self.ctx.download(high_dev, (len(low), self.p), np.float64)
-        finally:
-            low_dev.free()
-            high_dev.free()
 
     def free_basis(self):
         for buf in (self.vt_dev, self.mean_dev):
@@ -289,30 +272,25 @@ def run_pca(A, fraction=0.90, ctx=None):
     """fpca/utils.py run_pca on the device: (Vt, npc), Vt the k = max(1, min(A.shape) - 1) leading right singular vectors of A
     as it is (not centred again), npc from the cumulated variance over those k values."""
     A = np.ascontiguousarray(A, dtype=np.float64)
-    ctx = _context(ctx)
-    a_dev = ctx.upload(A)
-    try:
-        pca = _DevicePCA(ctx, a_dev, A.shape[0], A.shape[1], centre=False)
+    ctx = _capi.default_context(ctx)
+    with ctx.buffers() as bufs:
+        pca = _DevicePCA(ctx, bufs.upload(A), A.shape[0], A.shape[1], centre=False)
         pca.close()
-    finally:
-        a_dev.free()
     k, npc = npc_from_singular_values(pca.fit["singular_values"], A.shape, fraction)
     return pca.fit["vt"][:k], npc
 
 
-def _spline_fit_device(ctx, motions_dev, n, n_frames, n_dims, n_basis):
-    """coefficients (n, n_basis, n_dims) on the device, and the knots."""
+def _spline_fit_device(ctx, bufs, motions, n_basis):
+    """The spline coefficients (n, n_basis, n_dims) of the host motions (n, n_frames, n_dims), a device buffer of the scope
+    `bufs`, and the knots.  The uploaded motions and the operator are gone when this returns: what the caller allocates next
+    (the PCA's work matrices) does not sit on top of them."""
+    n, n_frames, n_dims = motions.shape
     if n_basis > MAX_BASIS or n_frames > MAX_FRAMES:
         raise ValueError("spline fit: n_basis = %d (at most %d), n_frames = %d (at most %d)" % (n_basis, MAX_BASIS, n_frames, MAX_FRAMES))
     P, knots = spline_fit_operator(n_basis, n_frames)
-    op_dev, coeffs_dev = ctx.upload(P), ctx.malloc(8 * n * n_basis * n_dims)
-    try:
-        _capi.spline_fit_batch(ctx, motions_dev, n, n_frames, n_dims, op_dev, n_basis, coeffs_dev)
-    except Exception:
-        coeffs_dev.free()
-        raise
-    finally:
-        op_dev.free()
+    with ctx.buffers() as inputs:
+        m_dev, op_dev, coeffs_dev = inputs.upload(motions), inputs.upload(P), bufs.malloc(8 * n * n_basis * n_dims)
+        _capi.spline_fit_batch(ctx, m_dev, n, n_frames, n_dims, op_dev, n_basis, coeffs_dev)
     return coeffs_dev, knots
 
 
@@ -330,16 +308,10 @@ class HipFunctionalData(object):
         assert degree == BSPLINE_DEGREE
         motion_mat = np.ascontiguousarray(motion_mat, dtype=np.float64)
         n, n_frames, n_dims = motion_mat.shape
-        ctx = _context(self.ctx)
-        m_dev = ctx.upload(motion_mat)
-        try:
-            c_dev, self.knots = _spline_fit_device(ctx, m_dev, n, n_frames, n_dims, n_basis)
-        finally:
-            m_dev.free()
-        try:
+        ctx = _capi.default_context(self.ctx)
+        with ctx.buffers() as bufs:
+            c_dev, self.knots = _spline_fit_device(ctx, bufs, motion_mat, n_basis)
             return ctx.download(c_dev, (n, n_basis, n_dims), np.float64)
-        finally:
-            c_dev.free()
 
     def convert_motion_to_functional_data(self, motion_data, n_basis=7, degree=3):
         return self.convert_motions_to_functional_data(np.asarray(motion_data)[None], n_basis, degree)[0]
@@ -355,20 +327,14 @@ class HipPCAFunctionalData(object):
         self.input_data = np.ascontiguousarray(input_data, dtype=np.float64)
         assert len(self.input_data.shape) == 3, ('input data should be a 3d array')
         self.n_basis = n_basis
-        self.ctx = _context(ctx)
+        self.ctx = _capi.default_context(ctx)
         n, n_frames, n_dims = self.input_data.shape
         p = n_basis * n_dims
-        m_dev = self.ctx.upload(self.input_data)
-        try:
-            c_dev, self.knots = _spline_fit_device(self.ctx, m_dev, n, n_frames, n_dims, n_basis)
-        finally:
-            m_dev.free()
-        try:
+        with self.ctx.buffers() as bufs:
+            c_dev, self.knots = _spline_fit_device(self.ctx, bufs, self.input_data, n_basis)
             self.functional_data = self.ctx.download(c_dev, (n, n_basis, n_dims), np.float64)
             self.origin_shape = (n, n_basis, n_dims)
             self._pca = _DevicePCA(self.ctx, c_dev, n, p)      # the flat index coeff * D + d is the table's own
-        finally:
-            c_dev.free()
         fit = self._pca.fit
         self.reshaped_fd, self.mean = self._pca.centred(), fit["mean"]
         self.singular_values_, self.n_sweeps_, self.pca_status_ = fit["singular_values"], fit["n_sweeps"], fit["status"]
@@ -447,27 +413,18 @@ class HipFPCATimeSemantic(object):
         w = np.ascontiguousarray(self.temporal_semantic_data, dtype=np.float64)
         assert w.ndim == 2, "warping functions (N, F) expected (semantic annotation channels are not supported)"
         n, n_frames = w.shape
-        ctx = _context(self.ctx)
-        w_dev = ctx.upload(w)
-        try:
-            c_dev, _ = _spline_fit_device(ctx, w_dev, n, n_frames, 1, self.n_basis)
-        finally:
-            w_dev.free()
-        try:
+        ctx = _capi.default_context(self.ctx)
+        with ctx.buffers() as bufs:
+            c_dev, _ = _spline_fit_device(ctx, bufs, w[:, :, None], self.n_basis)
             coeffs = ctx.download(c_dev, (n, self.n_basis), np.float64)
-        finally:
-            c_dev.free()
         self.fpca_data = temporal_functional_data_host(coeffs, w)
 
     def functional_pca(self):
         self.functional_data_representation()
-        ctx = _context(self.ctx)
+        ctx = _capi.default_context(self.ctx)
         n, p = self.fpca_data.shape
-        a_dev = ctx.upload(self.fpca_data)
-        try:
-            pca = _DevicePCA(ctx, a_dev, n, p)
-        finally:
-            a_dev.free()
+        with ctx.buffers() as bufs:
+            pca = _DevicePCA(ctx, bufs.upload(self.fpca_data), n, p)
         self.fpca_data, self.mean_vec = pca.centred(), pca.fit["mean"]
         self.singular_values_, self.n_sweeps_, self.pca_status_ = pca.fit["singular_values"], pca.fit["n_sweeps"], pca.fit["status"]
         k, npc = npc_from_singular_values(self.singular_values_, (n, p), self.precision_temporal)

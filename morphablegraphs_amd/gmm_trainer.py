@@ -154,13 +154,6 @@ class FittedGaussianMixture(object):
         return -2 * self.train_score_ * n_samples + self._n_parameters() * np.log(n_samples)
 
 
-def _context(ctx):
-    if ctx is not None:
-        return ctx
-    from .motion_primitive import get_context
-    return get_context(0)
-
-
 def fit_gaussian_mixtures(X, n_components, init=None, seed=0, tol=1e-3, reg_covar=1e-6, max_iter=100, ctx=None, points_dev=None):
     """Fit GaussianMixture(n_components=K, covariance_type='full') for every K of `n_components` (an int or a list) in ONE
     device call.  init: None (device k-means++ keyed by `seed` and K), a callable (X, K) -> (K, d) initial k-means centres,
@@ -178,11 +171,10 @@ def fit_gaussian_mixtures(X, n_components, init=None, seed=0, tol=1e-3, reg_cova
             raise ValueError("fit_gaussian_mixtures: n_components = %d; the device EM supports 1 .. %d" % (K, MAX_COMPONENTS))
         if n < K:
             raise ValueError("Expected n_samples >= n_components but got n_components = %d, n_samples = %d" % (K, n))
-    ctx = _context(ctx)
-    own = points_dev is None
-    if own:
-        points_dev = ctx.upload(X)
-    try:
+    ctx = _capi.default_context(ctx)
+    with ctx.buffers() as bufs:
+        if points_dev is None:
+            points_dev = bufs.upload(X)
         labels = []
         if init is not None and not callable(init):
             labels = [np.asarray(lab, dtype=np.int32).reshape(n) for lab in init]
@@ -199,9 +191,6 @@ def fit_gaussian_mixtures(X, n_components, init=None, seed=0, tol=1e-3, reg_cova
                                                      np.array([K], dtype=np.uint64), seed, 300, 1e-4)
                 labels.append(np.asarray(lab, dtype=np.int32))
         fits = _capi.gmm_em_fit(ctx, points_dev, n, d, Ks, np.stack(labels), tol, reg_covar, max_iter)
-    finally:
-        if own:
-            points_dev.free()
     bad = [K for K, f in zip(Ks, fits) if f["status"] == STATUS_ILL_DEFINED]
     if bad:
         raise ValueError(ILL_DEFINED_MESSAGE + " (n_components = %s)" % ", ".join(str(K) for K in bad))

@@ -23,7 +23,7 @@ plain Python; they are the yardstick of the CPU tests.  The device functions hav
 import numpy as np
 
 from . import _capi
-from .dtw import _Buffers, _context, _offsets, distance_grid_host
+from .dtw import _offsets, distance_grid_host
 
 SINGLE, MULTI = _capi.MG_SEGMENT_SINGLE, _capi.MG_SEGMENT_MULTI
 MAX_KEYFRAMES, MAX_JOINTS = _capi.MG_SEGMENT_MAX_KEYFRAMES, _capi.MG_SEGMENT_MAX_JOINTS
@@ -133,7 +133,7 @@ def _search_on_device(ctx, bufs, start_dev, end_dev, off, mode, threshold, min_s
 def keyframe_distances(clouds, keyframes, weights=None, ctx=None):
     """mg_keyframe_distances: per motion the (K, F_n) distances of the clouds (a list of (F_n, J, 3) arrays) to the keyframes
     (K, J, 3)."""
-    ctx = _context(ctx)
+    ctx = _capi.default_context(ctx)
     keyframes = np.ascontiguousarray(keyframes, dtype=np.float64)
     clouds = _as_clouds(clouds, keyframes.shape[1] if keyframes.ndim == 3 else None)
     if not clouds:
@@ -141,7 +141,7 @@ def keyframe_distances(clouds, keyframes, weights=None, ctx=None):
     _check_limits(clouds, keyframes)
     off = _offsets([len(c) for c in clouds])
     k, total = len(keyframes), int(off[-1])
-    with _Buffers(ctx) as bufs:
+    with ctx.buffers() as bufs:
         c_dev, k_dev, d_dev = bufs.upload(np.concatenate(clouds)), bufs.upload(keyframes), bufs.malloc(8 * k * total)
         _capi.keyframe_distances(ctx, c_dev, off, keyframes.shape[1], k_dev, k, weights, d_dev)
         dist = ctx.download(d_dev, (k, total), np.float64)
@@ -151,7 +151,7 @@ def keyframe_distances(clouds, keyframes, weights=None, ctx=None):
 def segment_search(start_dists, end_dists, mode, threshold=1.0, min_segment_size=10, ctx=None):
     """mg_segment_search on given distances (two lists of (F_n,) arrays): per motion the (count, 2) int32 array of kept
     (start, end) pairs."""
-    ctx = _context(ctx)
+    ctx = _capi.default_context(ctx)
     if len(start_dists) != len(end_dists):
         raise ValueError("segment search: %d and %d motions" % (len(start_dists), len(end_dists)))
     if not len(start_dists):
@@ -161,7 +161,7 @@ def segment_search(start_dists, end_dists, mode, threshold=1.0, min_segment_size
     if any(len(a) != len(b) or len(a) < 1 for a, b in zip(s, e)):
         raise ValueError("segment search: one start and one end distance per frame, at least one frame per motion")
     off = _offsets([len(a) for a in s])
-    with _Buffers(ctx) as bufs:
+    with ctx.buffers() as bufs:
         return _search_on_device(ctx, bufs, bufs.upload(np.concatenate(s)), bufs.upload(np.concatenate(e)), off, mode, threshold, min_segment_size)
 
 
@@ -197,15 +197,13 @@ class KeyframeDetector(object):
             n_dim = len(keyframes[0])
             if any(m.shape[1] != n_dim for m in motions) or any(len(k) != n_dim for k in keyframes):
                 raise ValueError("the motions and keyframes of one call have the same channels")
-            idx = np.ascontiguousarray([self._skeleton.index(j) for j in self._joints], dtype=np.int32)
+            idx = self._skeleton.indices(self._joints)
             nj = len(idx)
             if not 1 <= nj <= MAX_JOINTS:
                 raise ValueError("keyframe distances: %d joints (1 to %d)" % (nj, MAX_JOINTS))
             rows = total + len(keyframes)
             f_dev, c_dev = bufs.upload(np.concatenate(motions + [np.stack(keyframes)])), bufs.malloc(8 * rows * nj * 3)
-            d = self._skeleton.desc()
-            _capi._check(ctx.lib.mg_joint_positions(ctx.handle, _capi.C.byref(d), idx.ctypes.data_as(_capi.C.c_void_p), nj, f_dev.ptr, rows, n_dim,
-                                                    c_dev.ptr))
+            ctx.joint_positions_dev(self._skeleton, idx, f_dev, rows, n_dim, c_dev)
         else:
             raise ValueError("one call takes quaternion frames with keyframe poses, or point clouds (F, J, 3) with keyframe clouds (J, 3)")
         return c_dev, c_dev.address + 8 * total * nj * 3, off, nj
@@ -220,16 +218,16 @@ class KeyframeDetector(object):
         """Per motion the (F_n,) distances of its frames to the keyframe, all motions in one call."""
         if not len(point_clouds):
             return []
-        ctx = _context(self._ctx)
-        with _Buffers(ctx) as bufs:
+        ctx = _capi.default_context(self._ctx)
+        with ctx.buffers() as bufs:
             d_dev, off = self._distances_on_device(ctx, bufs, point_clouds, [keyframe])
             dist = ctx.download(d_dev, (int(off[-1]),), np.float64)
         return [dist[int(off[m]):int(off[m + 1])].copy() for m in range(len(off) - 1)]
 
     def find_instance(self, point_cloud, keyframe):
         """The first frame closest to the keyframe."""
-        ctx = _context(self._ctx)
-        with _Buffers(ctx) as bufs:
+        ctx = _capi.default_context(self._ctx)
+        with ctx.buffers() as bufs:
             d_dev, off = self._distances_on_device(ctx, bufs, [point_cloud], [keyframe])
             return int(_search_on_device(ctx, bufs, d_dev, d_dev, off, SINGLE, 0.0, 0)[0][0, 0])
 
@@ -253,8 +251,8 @@ class Segmentation(object):
         if not len(motions):
             return []
         det = self._keyframe_detector
-        ctx = _context(det._ctx)
-        with _Buffers(ctx) as bufs:
+        ctx = _capi.default_context(det._ctx)
+        with ctx.buffers() as bufs:
             d_dev, off = det._distances_on_device(ctx, bufs, motions, [start_keyframe, end_keyframe])
             pairs = _search_on_device(ctx, bufs, d_dev, d_dev.address + 8 * int(off[-1]), off, SINGLE if single else MULTI, threshold,
                                       self.min_segment_size)

@@ -30,6 +30,77 @@ def test_library_loads_and_exports_every_declared_symbol():
     assert lib.mg_status_string(-5) == b"covariance not positive definite"
 
 
+class _StubBuffer(object):
+    def __init__(self, log, nbytes):
+        self.log, self.nbytes, self.freed = log, nbytes, 0
+
+    def free(self):
+        self.freed += 1
+        self.log.append(("free", self))
+
+
+class _StubContext(object):
+    """The part of Context that DeviceBuffers uses, recording what it is asked for."""
+
+    def __init__(self):
+        self.log = []
+
+    def _new(self, kind, nbytes):
+        buf = _StubBuffer(self.log, nbytes)
+        self.log.append((kind, buf))
+        return buf
+
+    def malloc(self, nbytes):
+        return self._new("malloc", nbytes)
+
+    def upload(self, arr):
+        assert arr.flags["C_CONTIGUOUS"]
+        return self._new("upload", arr.nbytes)
+
+    buffers = _capi.Context.buffers
+
+
+def test_device_buffer_scope_frees_what_it_handed_out():
+    """Context.buffers(): every buffer is freed once when the block ends, whether it returns or raises; a released buffer is
+    the caller's; malloc never asks for fewer than 8 bytes; an upload is made contiguous."""
+    ctx = _StubContext()
+    with ctx.buffers() as bufs:
+        a, b, c = bufs.malloc(0), bufs.upload(np.arange(12.0).reshape(3, 4)[:, ::2]), bufs.malloc(24)
+        assert [x.nbytes for x in (a, b, c)] == [8, 48, 24]
+        assert bufs.malloc(3).nbytes == 8 and bufs.malloc(8.0).nbytes == 8 and bufs.malloc(9).nbytes == 9
+        assert not any(kind == "free" for kind, _ in ctx.log)            # nothing goes before the block ends
+    made = [buf for kind, buf in ctx.log if kind != "free"]
+    assert len(made) == 6 and all(buf.freed == 1 for buf in made)
+    assert [buf for kind, buf in ctx.log if kind == "free"] == made       # in the order they were made
+
+    ctx = _StubContext()
+    with pytest.raises(KeyError):
+        with ctx.buffers() as bufs:
+            a, b = bufs.upload(np.zeros(5)), bufs.malloc(16)
+            raise KeyError("the body fails")
+    assert a.freed == 1 and b.freed == 1
+
+    ctx = _StubContext()
+    with ctx.buffers() as bufs:
+        a, b, c = bufs.malloc(16), bufs.malloc(16), bufs.upload(np.zeros(2))
+        assert bufs.release(b) is b
+    assert (a.freed, b.freed, c.freed) == (1, 0, 1)
+    with pytest.raises(KeyError):
+        with ctx.buffers() as bufs:
+            kept = bufs.release(bufs.malloc(32))
+            gone = bufs.malloc(32)
+            raise KeyError("after the release")
+    assert (kept.freed, gone.freed) == (0, 1)
+    with pytest.raises(ValueError):
+        with ctx.buffers() as bufs:
+            bufs.release(a)                                               # not this block's
+
+
+def test_default_context_passes_a_given_context_through():
+    ctx = object()
+    assert _capi.default_context(ctx) is ctx
+
+
 def test_no_gpu_means_loud_failure_not_fallback():
     import torch
     if torch.cuda.is_available():

@@ -917,6 +917,20 @@ int mg_dtw_paths(mg_context *ctx, const double *grids_dev, int32_t n_ref_frames,
 int mg_warp_motions(mg_context *ctx, const double *frames_dev, const int64_t *offsets, int64_t n_motions, int32_t n_dim,
                     const int32_t *warping_dev, int32_t n_ref_frames, double *warped_dev);
 
+/* All-pairs costs (what the reference's find_optimal_dtw averages per candidate reference motion, construction/dtw.py:125-146):
+ * costs_dev (n_refs, n_motions), row-major: costs[r][n] = D[-1,-1] of the DTW of reference motion ref_indices[r] and motion n, both
+ * from the one ragged table clouds_dev (offsets[n_motions], n_joints, 3): bit for bit the totals value mg_dtw_paths returns for the
+ * grid mg_dtw_distance_grids computes for that pair.  No grid, accumulated cost or path is stored; the call's device block holds the
+ * offsets, the weights and the reference indices only.  ref_indices: HOST array (n_refs) of motion indices; NULL = all motions in
+ * order, and then n_refs must equal n_motions.  The matrix is not symmetric (the fit of B onto A is not bitwise that of A onto B).
+ * weights: HOST array (n_joints), NULL = ones.  MG_ERR_UNSUPPORTED for n_joints > 64 or a motion of more than 1024 frames;
+ * MG_ERR_INVALID_ARGUMENT for a NULL argument, offsets that do not start at 0 or do not rise, a reference index outside
+ * [0, n_motions), n_refs < 0, and non-finite clouds: those are found by the check kernel that runs in front of the pairs and are
+ * answered when the call's one synchronisation returns; costs_dev is then without meaning.  Everything else is answered before any
+ * launch.  n_motions = 0 or n_refs = 0 is MG_OK and writes nothing.  A pair gives the same bits alone or in any batch. */
+int mg_dtw_pair_costs(mg_context *ctx, const double *clouds_dev, const int64_t *offsets, int64_t n_motions, int32_t n_joints,
+                      const double *weights, const int64_t *ref_indices, int64_t n_refs, double *costs_dev);
+
 /* ---- segmentation: cutting clips out of captures at keyframe poses (reference construction/keyframe_detection.py:79-135 argmin,
  * argmin_multi, KeyframeDetector.find_instance / find_instances / calculate_distances; construction/segmentation.py:34-81
  * Segmentation.extract_single_segments / extract_segments), float64, synchronising, bit-reproducible.  Captures are ragged like the

@@ -1,7 +1,7 @@
 """MI355X-native motion-primitive back-projection / GMM scoring behind the morphablegraphs plugin surface.
 Importing the package does not load the HIP library; the first backend object does (and fails loudly
 if libmg_hip.so or a gfx950 device is missing -- there is no CPU fallback)."""
-from .dtw import align_frames_temporally  # noqa: F401
+from .dtw import align_frames_temporally, all_pairs_costs, reference_from_costs, select_reference_motion  # noqa: F401
 from .fpca import (HipFPCASpatialData, HipFPCATimeSemantic, HipFunctionalData, HipPCAFunctionalData,  # noqa: F401
                    construct_motion_primitive_model)
 from .gaussian_mixture import HipGaussianMixture, sample_like_sklearn  # noqa: F401

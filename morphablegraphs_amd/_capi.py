@@ -84,7 +84,7 @@ EXPORTED_SYMBOLS = [
     "mg_cluster_tree_create", "mg_cluster_tree_destroy", "mg_cluster_tree_search", "mg_cluster_tree_search_host",
     "mg_cluster_tree_create_kd", "mg_kmeans_segments", "mg_gmm_em_fit",
     "mg_spline_fit_batch", "mg_pca_fit", "mg_pca_project", "mg_pca_backproject",
-    "mg_dtw_distance_grids", "mg_dtw_paths", "mg_warp_motions",
+    "mg_dtw_distance_grids", "mg_dtw_paths", "mg_warp_motions", "mg_dtw_pair_costs",
     "mg_keyframe_distances", "mg_segment_search",
 ]
 
@@ -359,6 +359,7 @@ def load_library(path=None):
         "mg_dtw_distance_grids": [vp, vp, i32, vp, vp, i64, i32, vp, vp],
         "mg_dtw_paths": [vp, vp, i32, vp, i64, vp, vp, vp, vp, vp],
         "mg_warp_motions": [vp, vp, vp, i64, i32, vp, i32, vp],
+        "mg_dtw_pair_costs": [vp, vp, vp, i64, i32, vp, vp, i64, vp],
         "mg_keyframe_distances": [vp, vp, vp, i64, i32, vp, i32, vp, vp],
         "mg_segment_search": [vp, vp, vp, vp, i64, i32, dbl, i32, vp, vp, vp],
     }
@@ -1084,6 +1085,18 @@ def warp_motions(ctx, frames_dev, offsets, n_dim, warping_dev, n_ref_frames, war
     off = _offsets_arg(offsets)
     _check(ctx.lib.mg_warp_motions(ctx.handle, _dev_ptr(frames_dev), _host_ptr(off), len(off) - 1, int(n_dim), _dev_ptr(warping_dev), int(n_ref_frames),
                                    _dev_ptr(warped_dev)))
+
+
+def dtw_pair_costs(ctx, clouds_dev, offsets, n_joints, weights, ref_indices, costs_dev):
+    """mg_dtw_pair_costs: costs_dev (n_refs, n_motions) <- the total DTW cost of every motion of the ragged cloud table clouds_dev
+    (offsets[-1], n_joints, 3) against the reference motions ref_indices (host integers; None: all motions in order); offsets:
+    (n_motions + 1) host integers; weights: (n_joints) or None (ones).  Returns n_refs."""
+    off, w = _offsets_arg(offsets), _weights_arg(weights, n_joints)
+    refs = None if ref_indices is None else np.ascontiguousarray(ref_indices, dtype=np.int64).reshape(-1)
+    n_refs = len(off) - 1 if refs is None else len(refs)
+    _check(ctx.lib.mg_dtw_pair_costs(ctx.handle, _dev_ptr(clouds_dev), _host_ptr(off), len(off) - 1, int(n_joints), _host_ptr(w), _host_ptr(refs), n_refs,
+                                     _dev_ptr(costs_dev)))
+    return n_refs
 
 
 MG_SEGMENT_SINGLE, MG_SEGMENT_MULTI = 0, 1             # enum mg_segment_mode (include/mg_hip.h)

@@ -11,10 +11,17 @@ accumulated cost D, the paths and the warping functions are the reference's bit 
 point distance after the weighted 2-D rigid fit (csrc/mg_dtw.hip states the formula and the order of its sums); the
 reference's own, anim_utils' _transform_invariant_point_cloud_distance, is not available: PARITY UNPINNED for the grids.
 
+The all-pairs search of the reference's find_optimal_dtw (dtw.py:125-146, and find_optimal_dtw_async without a mean_key)
+averages, per candidate reference motion, the path costs of all motions against it and means to keep the least average; its
+selection never updates best_d, so it returns the LAST key's paths whatever the costs.  The rule it means is here as
+all_pairs_costs (mg_dtw_pair_costs: the (R, N) matrix of total costs, no grid or path in memory), reference_from_costs (the
+means added in column order, the FIRST least mean) and select_reference_motion;
+align_frames_temporally(reference_selection="least_mean_cost") uses it.  The matrix is, bit for bit, the `total` of dtw_batch
+pair by pair.
+
 Not reproduced:
-  * the all-pairs search of the reference's find_optimal_dtw (dtw.py:125-146, and find_optimal_dtw_async without a
-    mean_key): its selection never updates best_d, so it returns the LAST key's paths whatever the costs.  find_optimal_dtw
-    here takes the reference motion's key and raises KeyError without one;
+  * the reference's behaviour of find_optimal_dtw without a key (the last key wins): find_optimal_dtw here takes the
+    reference motion's key and raises KeyError without one; select_reference_motion finds the key the search means;
   * fastdtw's approximation (radius 1), which run_dtw_process calls in place of run_dtw: the paths here are the optimum it
     approximates.
 
@@ -209,6 +216,101 @@ def dtw_batch(ref_cloud, clouds, weights=None, accumulated=False, ctx=None):
         return _paths_on_device(ctx, bufs, s_dev, len(ref), off, accumulated)[0]
 
 
+def _reference_indices(references, n):
+    if references is None:
+        return None
+    refs = [int(r) for r in references]
+    if any(r < 0 or r >= n for r in refs):
+        raise ValueError("a reference index outside the %d motions: %r" % (n, refs))
+    return np.asarray(refs, dtype=np.int64)
+
+
+def all_pairs_costs(clouds, weights=None, references=None, ctx=None):
+    """mg_dtw_pair_costs: the (R, N) float64 matrix of total DTW costs, entry (r, n) = dtw_batch(clouds[references[r]],
+    clouds)[n]["total"] bit for bit; clouds: a list of (F_n, J, 3) arrays; references: a list of indices into it (None: all,
+    R = N).  No grid, accumulated cost or path is formed in memory."""
+    ctx = _capi.default_context(ctx)
+    clouds = [np.asarray(c, dtype=np.float64) for c in clouds]
+    if not clouds:
+        return np.zeros((0, 0))
+    n_joints = clouds[0].shape[1]
+    clouds = [c.reshape(-1, n_joints, 3) for c in clouds]
+    refs = _reference_indices(references, len(clouds))
+    n_refs = len(clouds) if refs is None else len(refs)
+    if n_refs == 0:
+        return np.zeros((0, len(clouds)))
+    _check_limits(1, [len(c) for c in clouds], n_joints)
+    off = _offsets([len(c) for c in clouds])
+    with ctx.buffers() as bufs:
+        c_dev, o_dev = bufs.upload(np.concatenate(clouds)), bufs.malloc(8 * n_refs * len(clouds))
+        _capi.dtw_pair_costs(ctx, c_dev, off, n_joints, weights, refs, o_dev)
+        return ctx.download(o_dev, (n_refs, len(clouds)), np.float64)
+
+
+def all_pairs_costs_host(clouds, weights=None, references=None):
+    """all_pairs_costs from distance_grid_host and dtw_paths_host."""
+    clouds = [np.asarray(c, dtype=np.float64) for c in clouds]
+    refs = _reference_indices(references, len(clouds))
+    refs = range(len(clouds)) if refs is None else refs
+    out = np.zeros((len(refs), len(clouds)))
+    for r, m in enumerate(refs):
+        for n, c in enumerate(clouds):
+            out[r, n] = dtw_paths_host(distance_grid_host(clouds[int(m)], c, weights))[0][-1, -1]
+    return out
+
+
+def reference_from_costs(costs, keys):
+    """The selection the reference's find_optimal_dtw means (dtw.py:133-146): row r of `costs` (R, N) holds the path costs of the
+    N motions against candidate keys[r]; its mean is the entries added in column order, then divided by N
+    (avg_distances[i] += path_cost; avg_distances[i] /= n); the FIRST least mean wins (strict <).  Returns (key, the R means)."""
+    costs = np.asarray(costs, dtype=np.float64)
+    keys = list(keys)
+    if costs.ndim != 2 or costs.shape[0] != len(keys) or len(keys) == 0 or costs.shape[1] == 0:
+        raise ValueError("costs %r for %d candidate keys" % (costs.shape, len(keys)))
+    if not np.all(np.isfinite(costs)):
+        raise ValueError("the costs hold non-finite values")
+    n = costs.shape[1]
+    means = np.zeros(len(keys))
+    best_key, best_d = None, np.inf
+    for r, row in enumerate(costs.tolist()):
+        total = 0.0
+        for v in row:
+            total += v
+        means[r] = total / n
+        if means[r] < best_d:
+            best_key, best_d = keys[r], means[r]
+    return best_key, means
+
+
+def select_reference_motion(skeleton, joints, motions, candidates=None, ctx=None):
+    """The motion the others are best warped against: (key, OrderedDict candidate key -> mean cost), the key with the FIRST
+    least mean DTW cost of all motions against it.  One forward-kinematics call for all motions (the clouds stay on the
+    device), one mg_dtw_pair_costs call; candidates: the keys to choose among (None: all, in the motions' order)."""
+    ctx = _capi.default_context(ctx)
+    keys = list(motions.keys())
+    candidates = keys if candidates is None else list(candidates)
+    missing = [k for k in candidates if k not in motions]
+    if missing or not candidates:
+        raise KeyError("the candidates %r are not among the motions" % (missing,))
+    frames = [np.asarray(motions[k], dtype=np.float64) for k in keys]
+    n_dim = frames[0].shape[1]
+    if any(f.ndim != 2 or f.shape[1] != n_dim for f in frames):
+        raise ValueError("the motions of one call have the same channels")
+    idx = skeleton.indices(joints)
+    _check_limits(1, [len(f) for f in frames], len(idx))
+    off = _offsets([len(f) for f in frames])
+    total, nj = int(off[-1]), len(idx)
+    refs = None if candidates == keys else np.asarray([keys.index(k) for k in candidates], dtype=np.int64)
+    with ctx.buffers() as bufs:
+        f_dev, c_dev = bufs.upload(np.concatenate(frames)), bufs.malloc(8 * total * nj * 3)
+        ctx.joint_positions_dev(skeleton, idx, f_dev, total, n_dim, c_dev)
+        o_dev = bufs.malloc(8 * len(candidates) * len(keys))
+        _capi.dtw_pair_costs(ctx, c_dev, off, nj, None, refs, o_dev)
+        costs = ctx.download(o_dev, (len(candidates), len(keys)), np.float64)
+    key, means = reference_from_costs(costs, candidates)
+    return key, collections.OrderedDict((k, float(v)) for k, v in zip(candidates, means))
+
+
 def _as_path(pairs):
     return [(int(i), int(j)) for i, j in pairs]
 
@@ -255,16 +357,24 @@ def _align_section(ctx, skeleton, joints, motions, mean_key):
             collections.OrderedDict((k, [int(v) for v in warps[m]]) for m, k in enumerate(keys)))
 
 
-def align_frames_temporally(skeleton, joints, motions, mean_key=None, sections=None, ctx=None):
+REFERENCE_SELECTIONS = ("average_time_line", "least_mean_cost")
+
+
+def align_frames_temporally(skeleton, joints, motions, mean_key=None, sections=None, ctx=None, reference_selection="average_time_line"):
     """MotionModelConstructor._align_frames_temporally / _align_frames_temporally_split on the device: `motions` {key: (F_k, D)
     quaternion frames} -> (warped_frames {key: (Fr, D) array}, warping_functions {key: list of Fr frame indices}), two
     OrderedDicts in the input's key order.  skeleton: a _capi.Skeleton; joints: the joints (names or indices) whose global
-    positions make a frame's point cloud (mg_joint_positions).  mean_key: the reference motion (None:
-    get_average_time_line).  sections: {key: [{"start_idx", "end_idx"}, ...]}: every motion is cut into its sections on the
+    positions make a frame's point cloud (mg_joint_positions).  mean_key: the reference motion; None: reference_selection
+    decides, "average_time_line" (get_average_time_line, the length closest to the mean length) or "least_mean_cost"
+    (select_reference_motion over the WHOLE motions, once, also with sections: the reference passes one mean_key to every
+    section).  sections: {key: [{"start_idx", "end_idx"}, ...]}: every motion is cut into its sections on the
     host, the sections are aligned one batched call each, and the results are concatenated."""
     ctx = _capi.default_context(ctx)
+    if reference_selection not in REFERENCE_SELECTIONS:
+        raise ValueError("reference_selection %r (one of %r)" % (reference_selection, REFERENCE_SELECTIONS))
     if mean_key is None:
-        mean_key = get_average_time_line(motions)
+        mean_key = get_average_time_line(motions) if reference_selection == "average_time_line" else select_reference_motion(
+            skeleton, joints, motions, ctx=ctx)[0]
     if mean_key not in motions:
         raise KeyError("the reference motion %r is not among the motions" % (mean_key,))
     if sections is None:

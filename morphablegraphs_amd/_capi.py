@@ -886,26 +886,35 @@ class Trajectory(object):
             pass
 
 
+def _i32(a):
+    return np.ascontiguousarray(np.asarray(a, dtype=np.int32))
+
+
 class ClusterTree(object):
     """A flattened FeatureClusterTree on the device (mg_cluster_tree_create): node 0 the root, means (n_nodes, dim), the
     children in CSR form (child_begin (n_nodes + 1), children), first_index = indices[0] per node (-1: none), n_rows rows of
     data.  It lives in the primitive's context and serves every primitive of that context whose n_components <= dim."""
 
     def __init__(self, prim, means, child_begin, children, first_index, n_rows):
-        self.ctx = prim.ctx
-        self.lib = prim.lib
-        means = np.ascontiguousarray(np.asarray(means, dtype=np.float64))
-        cb = np.ascontiguousarray(np.asarray(child_begin, dtype=np.int32))
-        ch = np.ascontiguousarray(np.asarray(children, dtype=np.int32))
         fi = np.ascontiguousarray(np.asarray(first_index, dtype=np.int64))
-        if means.ndim != 2 or cb.shape != (means.shape[0] + 1,) or fi.shape != (means.shape[0],):
+        means, n_nodes, cb, ch = self._nodes(prim, means, 0, child_begin, children)
+        if n_nodes < 1 or cb.shape != (n_nodes + 1,) or fi.shape != (n_nodes,):
             raise ValueError("means (n_nodes, dim), child_begin (n_nodes + 1), first_index (n_nodes)")
+        self._create("mg_cluster_tree_create", prim, n_nodes, means.shape[1], means, cb, ch, fi, int(n_rows))
+
+    def _nodes(self, prim, rows, n_kd, child_begin, children):
+        """The arrays both kinds have: the float64 table (its last rows the cluster nodes') and the children's CSR pair."""
+        self.ctx, self.lib = prim.ctx, prim.lib
+        rows = np.ascontiguousarray(np.asarray(rows, dtype=np.float64))
+        self.dim = rows.shape[1] if rows.ndim == 2 else 0
+        return rows, (rows.shape[0] - n_kd if rows.ndim == 2 else 0), _i32(child_begin), _i32(children)
+
+    def _create(self, entry, prim, n_nodes, *args):
+        """entry(prim, n_nodes, args..., &handle): arrays go as pointers (an empty one as NULL)."""
         h = C.c_void_p()
-        _check(self.lib.mg_cluster_tree_create(prim.handle, means.shape[0], means.shape[1], means.ctypes.data_as(C.c_void_p),
-                                               cb.ctypes.data_as(C.c_void_p), ch.ctypes.data_as(C.c_void_p) if ch.size else None,
-                                               fi.ctypes.data_as(C.c_void_p), int(n_rows), C.byref(h)))
-        self.handle = h
-        self.n_nodes, self.dim = means.shape
+        args = [(a.ctypes.data_as(C.c_void_p) if a.size else None) if isinstance(a, np.ndarray) else a for a in args]
+        _check(getattr(self.lib, entry)(prim.handle, n_nodes, *(args + [C.byref(h)])))
+        self.handle, self.n_nodes = h, n_nodes
 
     def close(self):
         if getattr(self, "handle", None) and self.ctx.handle:
@@ -925,25 +934,15 @@ class KdClusterTree(ClusterTree):
     (kd_begin, kd_roots); the KD nodes' kd_left, kd_right, kd_inner.  Searched by search_cluster_trees like ClusterTree."""
 
     def __init__(self, prim, points, n_kd, child_begin, children, leaf, kd_begin, kd_roots, kd_left, kd_right, kd_inner):
-        self.ctx = prim.ctx
-        self.lib = prim.lib
-        points = np.ascontiguousarray(np.asarray(points, dtype=np.float64))
         n_kd = int(n_kd)
-        n_nodes = points.shape[0] - n_kd if points.ndim == 2 else 0
-        ints = [np.ascontiguousarray(np.asarray(a, dtype=np.int32)) for a in (child_begin, children, leaf, kd_begin, kd_roots, kd_left, kd_right, kd_inner)]
-        cb, ch, lf, kb, kr, kl, krt, ki = ints
-        if points.ndim != 2 or n_nodes < 1 or cb.shape != (n_nodes + 1,) or lf.shape != (n_nodes,) or kb.shape != (n_nodes + 1,) or \
+        points, n_nodes, cb, ch = self._nodes(prim, points, n_kd, child_begin, children)
+        lf, kb, kr, kl, krt, ki = [_i32(a) for a in (leaf, kd_begin, kd_roots, kd_left, kd_right, kd_inner)]
+        if n_nodes < 1 or cb.shape != (n_nodes + 1,) or lf.shape != (n_nodes,) or kb.shape != (n_nodes + 1,) or \
                 any(a.shape != (n_kd,) for a in (kl, krt, ki)) or ch.shape != (n_nodes - 1,) or kr.shape != (int(kb[-1]),):
             raise ValueError("points (n_kd + n_nodes, dim), child_begin / kd_begin (n_nodes + 1), children (n_nodes - 1), leaf (n_nodes), "
                              "kd_roots (kd_begin[-1]), kd_left / kd_right / kd_inner (n_kd)")
-
-        def ptr(a):
-            return a.ctypes.data_as(C.c_void_p) if a.size else None
-        h = C.c_void_p()
-        _check(self.lib.mg_cluster_tree_create_kd(prim.handle, n_nodes, n_kd, points.shape[1], points.ctypes.data_as(C.c_void_p),
-                                                  *[ptr(a) for a in ints], C.byref(h)))
-        self.handle = h
-        self.n_nodes, self.n_kd, self.dim = n_nodes, n_kd, points.shape[1]
+        self._create("mg_cluster_tree_create_kd", prim, n_nodes, n_kd, points.shape[1], points, cb, ch, lf, kb, kr, kl, krt, ki)
+        self.n_kd = n_kd
 
 
 def search_cluster_trees(prims, trees, csets, n_candidates, records_dev=None):

@@ -29,18 +29,81 @@ MG_TREE_MAX_DEPTH, MG_TREE_MAX_CHILDREN, MG_TREE_MAX_CANDIDATES = _capi.MG_TREE_
 
 
 class _TreeNode(object):
-    """A node in the heaps: like the reference's FeatureClusterTree it defines no ordering, so tuples of equal values
-    raise TypeError when heapq compares them."""
+    """A node in the heaps: like the reference's FeatureClusterTree and ClusterTreeNode it defines no ordering, so tuples
+    that reach it raise TypeError when heapq compares them."""
     __slots__ = ("index",)
 
     def __init__(self, index):
         self.index = index
 
 
-class HipFeatureClusterTree(object):
+def _forest(n, roots, kids, max_depth, what, depth_of=None):
+    """Depth of the forest below `roots` (kids(v): v's children); ValueError unless every node has one parent and is reached.
+    depth_of: an array that receives every node's depth."""
+    seen = np.zeros(n, dtype=bool)
+    level = [int(r) for r in roots]
+    for r in level:
+        if r < 0 or r >= n or seen[r]:
+            raise ValueError("cluster tree: every %s node needs exactly one parent" % what)
+        seen[r] = True
+    depth = 0
+    while level:
+        nxt = [int(c) for v in level for c in kids(v)]
+        if not nxt:
+            break
+        depth += 1
+        if depth > max_depth:
+            raise ValueError("cluster tree: %s levels deeper than %d, or a cycle" % (what, max_depth))
+        for c in nxt:
+            if c < 0 or c >= n or seen[c]:
+                raise ValueError("cluster tree: every %s node needs exactly one parent" % what)
+            seen[c] = True
+        if depth_of is not None:
+            depth_of[nxt] = depth
+        level = nxt
+    if not seen.all():
+        raise ValueError("cluster tree: %s nodes not reachable from the root (a cycle)" % what)
+    return depth
+
+
+class _SearchTree(object):
+    """What the two kinds of tree share beside their tables: the device copy per context and the flags of a search record
+    that mean the same for both."""
+    _TIE = None     # the reference's TypeError text
+
+    def _upload(self, prim):
+        raise NotImplementedError
+
+    def device_tree(self, prim):
+        """The tree on the device of prim's context (a _capi.ClusterTree), uploaded once per context."""
+        key = id(prim.ctx)
+        t = self._device.get(key)
+        if t is not None and t[0] is prim.ctx and t[1].handle and prim.ctx.handle:
+            return t[1]
+        tree = self._upload(prim)
+        self._device[key] = (prim.ctx, tree)
+        return tree
+
+    def close(self):
+        for _, tree in self._device.values():
+            tree.close()
+        self._device = {}
+
+    def _flags_of_record(self, rec):
+        """A record's flags, or the exception for a search that overflowed or met a tie."""
+        flags = int(rec["flags"])
+        if flags & _capi.MG_TREE_OVERFLOW:
+            raise RuntimeError("cluster-tree search: a heap outgrew its bound")
+        if flags & _capi.MG_TREE_TIE:
+            raise TypeError(self._TIE)
+        return flags
+
+
+class HipFeatureClusterTree(_SearchTree):
     """A FeatureClusterTree loaded from the reference's JSON layout: {"data", "features", "options", "root": {"mean",
     "indices", "children"}} (feature_cluster_tree.py:293-333).  `.data` is the float64 array of the stored samples
     (what the exhaustive search scores)."""
+    _TIE = "'<' not supported between instances of 'FeatureClusterTree' and 'FeatureClusterTree' (two candidates of equal value)"
 
     def __init__(self, data, means, child_begin, children, first_index, options=None, features=None, n_spatial=None):
         self.data = np.asarray(data, dtype=np.float64)
@@ -112,17 +175,8 @@ class HipFeatureClusterTree(object):
             raise ValueError("cluster tree: a node with more than %d children" % MG_TREE_MAX_CHILDREN)
         if len(ch) and (ch.min() < 1 or ch.max() >= n or len(np.unique(ch)) != len(ch)):
             raise ValueError("cluster tree: every node but the root needs exactly one parent")
-        depth = np.full(n, -1, dtype=np.int32)     # levels from the root: all nodes reached <=> no cycle
-        depth[0], level, d = 0, [0], 0
-        while level:
-            level = [int(c) for v in level for c in ch[cb[v]:cb[v + 1]]]
-            d += 1
-            if level and (d > MG_TREE_MAX_DEPTH or np.any(depth[level] >= 0)):
-                raise ValueError("cluster tree: deeper than %d levels, or a cycle" % MG_TREE_MAX_DEPTH)
-            depth[level] = d
-        if np.any(depth < 0):
-            raise ValueError("cluster tree: nodes not reachable from the root (a cycle)")
-        self.depth = depth
+        self.depth = np.zeros(n, dtype=np.int32)     # every node's level below the root
+        _forest(n, [0], lambda v: ch[cb[v]:cb[v + 1]], MG_TREE_MAX_DEPTH, "cluster", self.depth)
         fi = self.first_index
         if np.any(fi < -1) or np.any(fi >= self.data.shape[0]):
             raise ValueError("cluster tree: an index outside [0, %d)" % self.data.shape[0])
@@ -178,29 +232,12 @@ class HipFeatureClusterTree(object):
         return value, row
 
     # ---- the device copy --------------------------------------------------------------------------------------
-    def device_tree(self, prim):
-        """The tree on the device of prim's context (_capi.ClusterTree), uploaded once per context."""
-        key = id(prim.ctx)
-        t = self._device.get(key)
-        if t is not None and t[0] is prim.ctx and t[1].handle and prim.ctx.handle:
-            return t[1]
-        tree = _capi.ClusterTree(prim, self.means, self.child_begin, self.children, self.first_index, self.data.shape[0])
-        self._device[key] = (prim.ctx, tree)
-        return tree
-
-    def close(self):
-        for _, tree in self._device.values():
-            tree.close()
-        self._device = {}
+    def _upload(self, prim):
+        return _capi.ClusterTree(prim, self.means, self.child_begin, self.children, self.first_index, self.data.shape[0])
 
     def result_of_record(self, rec):
         """(value, row) of a search record, or the reference's exception."""
-        flags = int(rec["flags"])
-        if flags & _capi.MG_TREE_OVERFLOW:
-            raise RuntimeError("cluster-tree search: a heap outgrew its bound")
-        if flags & _capi.MG_TREE_TIE:
-            raise TypeError("'<' not supported between instances of 'FeatureClusterTree' and 'FeatureClusterTree' "
-                            "(two candidates of equal value)")
+        flags = self._flags_of_record(rec)
         if flags & _capi.MG_TREE_NO_RESULT:
             return np.inf, self._root_row()
         row = int(rec["row"])

@@ -6,6 +6,9 @@
 // bits mg_score_constraints gives for its mean).  Lane 0 keeps the three heaps in LDS and restates heapq's _siftdown /
 // _siftup literally; a comparison of two equal values (where the reference's tuples fall through to comparing tree nodes
 // and raise TypeError) sets MG_TREE_TIE.
+//
+// The k-means / KD ClusterTree's search (below) runs the same level loop.  The two kernels share the chunk scorer, the staging of
+// the set's W in LDS, the mapping of a chunk's lanes to frontier nodes, heapq's push and pop, and the LDS regions all of these use.
 #include "mg_internal.h"
 
 #include <algorithm>
@@ -20,148 +23,229 @@ struct mg_cluster_tree {
     int32_t kind = 0;                 // 0: a FeatureClusterTree (mg_cluster_tree_create), 1: a k-means/KD ClusterTree (_create_kd)
     int32_t n_nodes = 0, dim = 0, depth = 0, max_children = 0;
     int64_t n_rows = 0;
-    double *d_means = nullptr;        // [n_nodes][dim]
+    // the rows the search scores, [.][dim].  kind 0: every node's mean.  kind 1: the KD nodes' points, then every cluster node's mean
+    double *d_points = nullptr;
     int32_t *d_child_begin = nullptr; // [n_nodes + 1]
     int32_t *d_children = nullptr;    // [n_nodes - 1] (at least one entry allocated)
-    int64_t *d_first = nullptr;       // [n_nodes]
-    // kind 1 (d_means, d_first unused): the points table [n_kd + n_nodes][dim] (the KD nodes' points, then every cluster
-    // node's mean), the leaf flags, the KD roots per cluster node (CSR) and the KD nodes' left / right / inner
+    int64_t *d_first = nullptr;       // kind 0: [n_nodes]
+    // kind 1: the leaf flags, the KD roots per cluster node (CSR) and the KD nodes' left / right / inner
     int32_t n_kd = 0, max_kd_children = 0, kd_depth = 0;
-    double *d_points = nullptr;
     int32_t *d_leaf = nullptr, *d_kd_begin = nullptr, *d_kd_roots = nullptr, *d_kd_left = nullptr, *d_kd_right = nullptr, *d_kd_inner = nullptr;
 };
 
-// what a workgroup reads of its search (one table per launch, in device memory)
+// what a workgroup reads of its search (one table per launch, in device memory); a feature tree leaves the KD fields NULL
 struct mg_tree_search_desc {
     mg_score_args a;
-    const double *means;
+    const double *points;
     const int32_t *child_begin, *children;
     const int64_t *first;
-    int32_t dim, rows;   // rows: the set's rows of W (0: not known, W is read from global memory)
+    const int32_t *leaf, *kd_begin, *kd_roots, *kd_left, *kd_right, *kd_inner;
+    int32_t dim, rows, n_kd, pad;   // rows: the set's rows of W (0: not known, W is read from global memory)
 };
 
 #define MG_TREE_CHUNK 64
 #define MG_TREE_WAVES 4
+#define MG_TREE_THREADS (MG_TREE_CHUNK * MG_TREE_WAVES)
+#define MG_TREE_LDS_MAX (160 * 1024)
 
-// heapq's comparison of (value, node) tuples whose values differ: value < value.  Equal values would compare the nodes.
-__device__ __forceinline__ bool mg_tree_lt(double a, double b, int &flags) {
-    if (a == b) flags |= MG_TREE_TIE;
-    return a < b;
+// ---- heapq on LDS, for any entry type and tuple comparison ----
+// A heap is an array of entries, or (value, node) entries kept as two arrays (12 bytes an entry).
+template <class T>
+__device__ __forceinline__ T mg_heap_get(const T *h, int i) { return h[i]; }
+template <class T>
+__device__ __forceinline__ void mg_heap_set(T *h, int i, const T &x) { h[i] = x; }
+struct mg_vn {
+    double v;
+    int32_t n;
+};
+struct mg_heap_vn {
+    double *v;
+    int32_t *n;
+};
+__device__ __forceinline__ mg_vn mg_heap_get(const mg_heap_vn &h, int i) { return mg_vn{h.v[i], h.n[i]}; }
+__device__ __forceinline__ void mg_heap_set(const mg_heap_vn &h, int i, const mg_vn &x) { h.v[i] = x.v; h.n[i] = x.n; }
+
+// heapq._siftdown(heap, 0, pos) with x the entry to place
+template <class H, class T, class Lt>
+__device__ __forceinline__ void mg_heap_siftdown(H h, int pos, const T &x, Lt lt) {
+    while (pos > 0) {
+        const int parent = (pos - 1) >> 1;
+        if (!lt(x, mg_heap_get(h, parent))) break;
+        mg_heap_set(h, pos, mg_heap_get(h, parent));
+        pos = parent;
+    }
+    mg_heap_set(h, pos, x);
 }
 
 // heapq.heappush: append, then _siftdown(heap, 0, len - 1)
-__device__ void mg_tree_heappush(double *hv, int32_t *hn, int &len, int cap, double v, int32_t node, int &flags) {
+template <class H, class T, class Lt>
+__device__ __forceinline__ void mg_heappush(H h, int &len, int cap, const T &x, Lt lt, int &flags) {
     if (len >= cap) { flags |= MG_TREE_OVERFLOW; return; }
-    int pos = len++;
-    while (pos > 0) {
-        const int parent = (pos - 1) >> 1;
-        if (mg_tree_lt(v, hv[parent], flags)) {
-            hv[pos] = hv[parent]; hn[pos] = hn[parent];
-            pos = parent;
-            continue;
-        }
-        break;
-    }
-    hv[pos] = v; hn[pos] = node;
+    mg_heap_siftdown(h, len++, x, lt);
 }
 
-// The comparisons of heapq.heappop (the last entry to the root, _siftup, _siftdown) for their tie flag alone: the
+// The comparisons of heapq.heappop (the last entry to the root, _siftup, _siftdown) for what lt records of them (a tie): the
 // answer is the root read before.
-__device__ void mg_tree_heappop_compares(double *hv, int32_t *hn, int len, int &flags) {
+template <class H, class Lt>
+__device__ __forceinline__ void mg_heappop_compares(H h, int len, Lt lt) {
     if (len <= 1) return;
     const int end = len - 1;
-    const double v = hv[end];
-    const int32_t nd = hn[end];
+    const auto x = mg_heap_get(h, end);
     int pos = 0, child = 1;
     while (child < end) {
         const int right = child + 1;
-        if (right < end && !mg_tree_lt(hv[child], hv[right], flags)) child = right;
-        hv[pos] = hv[child]; hn[pos] = hn[child];
+        if (right < end && !lt(mg_heap_get(h, child), mg_heap_get(h, right))) child = right;
+        mg_heap_set(h, pos, mg_heap_get(h, child));
         pos = child;
         child = 2 * pos + 1;
     }
-    while (pos > 0) {
-        const int parent = (pos - 1) >> 1;
-        if (mg_tree_lt(v, hv[parent], flags)) {
-            hv[pos] = hv[parent]; hn[pos] = hn[parent];
-            pos = parent;
-            continue;
-        }
-        break;
-    }
-    hv[pos] = v; hn[pos] = nd;
+    mg_heap_siftdown(h, pos, x, lt);
 }
 
+// ---- the LDS regions, and the routines on them, that both kernels have ----
+struct mg_tree_lds_shared {
+    int n_cand, cap_local, cap_level, cap_res, wrows;
+    size_t off_w, off_rs, off_cval, off_cid, off_clast, off_frn, off_froff;
+};
+
+// the heaps' bounds and the 8-byte regions a plan begins with: xs [64][L + 1] at 0, the set's W [rows][L] and bias [rows], rs, cval.
+// Returns the offset behind them.
+static size_t mg_tree_carve_head(mg_tree_lds_shared &p, int Lmax, int ncmax, int n_cand, int max_children, int max_depth, int wrows) {
+    p.wrows = wrows;
+    p.n_cand = n_cand;
+    p.cap_local = std::max(max_children, 1);
+    p.cap_level = n_cand * std::min(n_cand, p.cap_local);
+    p.cap_res = n_cand * (max_depth + 1);
+    size_t o = (size_t)MG_TREE_CHUNK * (Lmax + 1) * 8;
+    p.off_w = o;    o += (size_t)wrows * (Lmax + 1) * 8;
+    p.off_rs = o;   o += (size_t)std::max(ncmax, 1) * MG_TREE_CHUNK * 8;
+    p.off_cval = o; o += MG_TREE_CHUNK * 8;
+    return o;
+}
+
+// the shared 4-byte regions (behind every 8-byte one): cid, clast, fr_n, fr_off
+static size_t mg_tree_carve_ints(mg_tree_lds_shared &p, size_t o) {
+    p.off_cid = o;   o += MG_TREE_CHUNK * 4;
+    p.off_clast = o; o += MG_TREE_CHUNK * 4;
+    p.off_frn = o;   o += (size_t)p.n_cand * 4;
+    p.off_froff = o; o += (size_t)(p.n_cand + 1) * 4;
+    return o;
+}
+
+struct mg_tree_lds {
+    double *xs, *rs, *cval;   // the scorer's: the chunk's rows, the residuals [constraint][lane], the values
+    int32_t *cid;             // the chunk's rows of the points table
+    const double *Wm, *Bm;   // the set's W and bias as the scorer reads them
+};
+
+// The shared regions of a workgroup, with the set's keyframe matrices staged in LDS where the plan has room for them: a level
+// scores a handful of children, one wave per constraint, and every step of the scorer's fma chains would otherwise wait for a
+// load from memory.  Same values, same order: the same bits.  (The caller's first __syncthreads publishes them.)
+__device__ __forceinline__ mg_tree_lds mg_tree_lds_of(unsigned char *smem, const mg_tree_lds_shared &p, const mg_score_args &a, int rows, int tid) {
+    mg_tree_lds s;
+    s.xs = (double *)smem;
+    s.rs = (double *)(smem + p.off_rs);
+    s.cval = (double *)(smem + p.off_cval);
+    s.cid = (int32_t *)(smem + p.off_cid);
+    s.Wm = a.W;
+    s.Bm = a.bias;
+    if (p.wrows > 0 && rows > 0) {
+        double *wl = (double *)(smem + p.off_w), *bl = wl + (size_t)p.wrows * a.L;
+        for (int i = tid; i < rows * a.L; i += MG_TREE_THREADS) wl[i] = a.W[i];
+        for (int i = tid; i < rows; i += MG_TREE_THREADS) bl[i] = a.bias[i];
+        s.Wm = wl;
+        s.Bm = bl;
+    }
+    return s;
+}
+
+// Entry e of a list that frontier node f's entries fill from off[f] to off[f + 1] (n nodes): its f, and whether e is f's last
+__device__ __forceinline__ int mg_tree_owner(const int32_t *off, int n, int e, int32_t &last) {
+    int f = 0;
+    while (f + 1 < n && off[f + 1] <= e) f++;
+    last = (e == off[f + 1] - 1);
+    return f;
+}
+
+// cval[j] = the objective of row cid[j] of P for j < cnt (a row < 0 scores zeros, and its value is not used): a lane per row,
+// the constraints dealt over the four waves, summed in constraint order by the row's lane.  The statements of mg_score_kernel, so
+// a value has the bits mg_score_constraints gives for that row.  Called by every thread of the workgroup, cid published.
+__device__ void mg_tree_score_chunk(const mg_score_args &a, const mg_tree_lds &s, const double *__restrict__ P, int dim, int cnt, int tid, int lane,
+                                    int wave) {
+    const int L = a.L, xs_stride = L + 1;
+    for (int e = tid; e < MG_TREE_CHUNK * L; e += MG_TREE_THREADS) {
+        const int c = e / L, i = e - c * L;
+        s.xs[c * xs_stride + i] = (c < cnt && s.cid[c] >= 0) ? P[(size_t)s.cid[c] * dim + i] : 0.0;
+    }
+    __syncthreads();
+    const double *x = s.xs + lane * xs_stride;
+    for (int c = wave; c < a.n; c += MG_TREE_WAVES) {
+        auto channel = [&](int row) {   // mg_score_kernel's fma chain over k from the bias
+            const double *wr = s.Wm + (size_t)row * L;
+            double acc = s.Bm[row];
+            for (int k = 0; k < L; k++) acc = fma(wr[k], x[k], acc);
+            return acc;
+        };
+        s.rs[c * MG_TREE_CHUNK + lane] = mg_constraint_residual(a, c, channel, 0);
+    }
+    __syncthreads();
+    if (tid < cnt) {
+        double err = 0.0;
+        for (int c = 0; c < a.n; c++) err += s.rs[c * MG_TREE_CHUNK + tid];
+        s.cval[tid] = err;
+    }
+    __syncthreads();
+}
+
+// ---- the FeatureClusterTree's search ----
 struct mg_tree_lds_plan {
-    int Lmax, ncmax, n_cand, cap_local, cap_level, cap_res, wrows;
-    size_t off_w, off_rs, off_cval, off_frv, off_lvv, off_lov, off_rev, off_frn, off_froff, off_lvn, off_lon, off_ren, off_cid, off_clast, bytes;
+    mg_tree_lds_shared s;
+    size_t off_frv, off_lvv, off_lov, off_rev, off_lvn, off_lon, off_ren, bytes;
 };
 
 static mg_tree_lds_plan mg_tree_plan(int Lmax, int ncmax, int n_cand, int max_children, int max_depth, int wrows) {
     mg_tree_lds_plan p;
-    p.wrows = wrows;
-    p.Lmax = Lmax; p.ncmax = std::max(ncmax, 1); p.n_cand = n_cand;
-    p.cap_local = std::max(max_children, 1);
-    p.cap_level = n_cand * std::min(n_cand, p.cap_local);
-    p.cap_res = n_cand * (max_depth + 1);
-    size_t o = (size_t)MG_TREE_CHUNK * (Lmax + 1) * 8;   // xs [64][L+1]
-    p.off_w = o;     o += (size_t)wrows * (Lmax + 1) * 8;  // the set's W [rows][L] and bias [rows]
-    p.off_rs = o;    o += (size_t)p.ncmax * MG_TREE_CHUNK * 8;
-    p.off_cval = o;  o += MG_TREE_CHUNK * 8;
-    p.off_frv = o;   o += (size_t)n_cand * 8;
-    p.off_lvv = o;   o += (size_t)p.cap_level * 8;
-    p.off_lov = o;   o += (size_t)p.cap_local * 8;
-    p.off_rev = o;   o += (size_t)p.cap_res * 8;
-    p.off_frn = o;   o += (size_t)n_cand * 4;
-    p.off_froff = o; o += (size_t)(n_cand + 1) * 4;
-    p.off_lvn = o;   o += (size_t)p.cap_level * 4;
-    p.off_lon = o;   o += (size_t)p.cap_local * 4;
-    p.off_ren = o;   o += (size_t)p.cap_res * 4;
-    p.off_cid = o;   o += MG_TREE_CHUNK * 4;
-    p.off_clast = o; o += MG_TREE_CHUNK * 4;
+    size_t o = mg_tree_carve_head(p.s, Lmax, ncmax, n_cand, max_children, max_depth, wrows);
+    p.off_frv = o; o += (size_t)n_cand * 8;
+    p.off_lvv = o; o += (size_t)p.s.cap_level * 8;
+    p.off_lov = o; o += (size_t)p.s.cap_local * 8;
+    p.off_rev = o; o += (size_t)p.s.cap_res * 8;
+    o = mg_tree_carve_ints(p.s, o);
+    p.off_lvn = o; o += (size_t)p.s.cap_level * 4;
+    p.off_lon = o; o += (size_t)p.s.cap_local * 4;
+    p.off_ren = o; o += (size_t)p.s.cap_res * 4;
     p.bytes = (o + 15) & ~(size_t)15;
     return p;
 }
 
-__global__ __launch_bounds__(MG_TREE_CHUNK *MG_TREE_WAVES) void mg_tree_search_kernel(const mg_tree_search_desc *__restrict__ tab, mg_tree_lds_plan lp,
-                                                                                      mg_tree_search_record *__restrict__ rec) {
+__global__ __launch_bounds__(MG_TREE_THREADS) void mg_tree_search_kernel(const mg_tree_search_desc *__restrict__ tab, mg_tree_lds_plan lp,
+                                                                         mg_tree_search_record *__restrict__ rec) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     __shared__ int s_fr_len, s_total;
     __shared__ long long s_evals;
     const mg_tree_search_desc *d = tab + blockIdx.x;
     const mg_score_args a = d->a;
-    const double *__restrict__ means = d->means;
+    const double *__restrict__ means = d->points;
     const int32_t *__restrict__ cb = d->child_begin;
     const int32_t *__restrict__ ch = d->children;
-    const int dim = d->dim, L = a.L, xs_stride = L + 1, n_cand = lp.n_cand;
-    double *xs = (double *)smem;
-    double *rs = (double *)(smem + lp.off_rs);
-    double *cval = (double *)(smem + lp.off_cval);
-    double *fr_v = (double *)(smem + lp.off_frv);
-    double *lv_v = (double *)(smem + lp.off_lvv);
-    double *lo_v = (double *)(smem + lp.off_lov);
-    double *re_v = (double *)(smem + lp.off_rev);
-    int32_t *fr_n = (int32_t *)(smem + lp.off_frn);
-    int32_t *fr_off = (int32_t *)(smem + lp.off_froff);
-    int32_t *lv_n = (int32_t *)(smem + lp.off_lvn);
-    int32_t *lo_n = (int32_t *)(smem + lp.off_lon);
-    int32_t *re_n = (int32_t *)(smem + lp.off_ren);
-    int32_t *cid = (int32_t *)(smem + lp.off_cid);
-    int32_t *clast = (int32_t *)(smem + lp.off_clast);
+    const int dim = d->dim, n_cand = lp.s.n_cand;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    // The set's keyframe matrices in LDS: a level scores a handful of children, one wave per constraint, and every step of
-    // the fma chains below would otherwise wait for a load from memory.  Same values, same order: the same bits.
-    const double *Wm = a.W, *Bm = a.bias;
-    if (lp.wrows > 0 && d->rows > 0) {
-        double *wl = (double *)(smem + lp.off_w), *bl = wl + (size_t)lp.wrows * L;
-        for (int i = tid; i < d->rows * L; i += MG_TREE_CHUNK * MG_TREE_WAVES) wl[i] = a.W[i];
-        for (int i = tid; i < d->rows; i += MG_TREE_CHUNK * MG_TREE_WAVES) bl[i] = a.bias[i];
-        Wm = wl;
-        Bm = bl;
-    }
+    const mg_tree_lds s = mg_tree_lds_of(smem, lp.s, a, d->rows, tid);
+    // (cid from the plan, not s.cid: read back out of the struct it costs the KD kernel two VGPRs)
+    int32_t *cid = (int32_t *)(smem + lp.s.off_cid), *clast = (int32_t *)(smem + lp.s.off_clast);
+    int32_t *fr_n = (int32_t *)(smem + lp.s.off_frn), *fr_off = (int32_t *)(smem + lp.s.off_froff);
+    double *fr_v = (double *)(smem + lp.off_frv);
+    const mg_heap_vn lv = {(double *)(smem + lp.off_lvv), (int32_t *)(smem + lp.off_lvn)};   // the level's new_candidates
+    const mg_heap_vn lo = {(double *)(smem + lp.off_lov), (int32_t *)(smem + lp.off_lon)};   // a node's result_queue
+    const mg_heap_vn re = {(double *)(smem + lp.off_rev), (int32_t *)(smem + lp.off_ren)};   // results
     // lane 0's heap state (only thread 0 touches the heaps)
     int flags = 0, lv_len = 0, lo_len = 0, res_len = 0;
+    // heapq's comparison of (value, node) tuples whose values differ: value < value.  Equal values would compare the nodes.
+    auto lt = [&flags](const mg_vn &x, const mg_vn &y) {
+        if (x.v == y.v) flags |= MG_TREE_TIE;
+        return x.v < y.v;
+    };
     if (tid == 0) {
         s_fr_len = 1; fr_v[0] = INFINITY; fr_n[0] = 0;   // candidates = [(np.inf, self)]
         s_evals = 0;
@@ -177,7 +261,7 @@ __global__ __launch_bounds__(MG_TREE_CHUNK *MG_TREE_WAVES) void mg_tree_search_k
                 const int node = fr_n[f];
                 const int nc = cb[node + 1] - cb[node];
                 fr_off[f] = tot;
-                if (nc == 0) mg_tree_heappush(re_v, re_n, res_len, lp.cap_res, fr_v[f], node, flags);   // a leaf: onto results
+                if (nc == 0) mg_heappush(re, res_len, lp.s.cap_res, mg_vn{fr_v[f], node}, lt, flags);   // a leaf: onto results
                 tot += nc;
             }
             fr_off[fr_len] = tot;
@@ -192,41 +276,17 @@ __global__ __launch_bounds__(MG_TREE_CHUNK *MG_TREE_WAVES) void mg_tree_search_k
             const int cnt = min(MG_TREE_CHUNK, tot - c0);
             if (tid < cnt) {   // entry e of the level's list: child k of frontier node f
                 const int e = c0 + tid;
-                int f = 0;
-                while (f + 1 < fr_len && fr_off[f + 1] <= e) f++;
-                const int node = fr_n[f];
-                cid[tid] = ch[cb[node] + (e - fr_off[f])];
-                clast[tid] = (e == fr_off[f + 1] - 1);
+                const int f = mg_tree_owner(fr_off, fr_len, e, clast[tid]);
+                cid[tid] = ch[cb[fr_n[f]] + (e - fr_off[f])];
             }
             __syncthreads();
-            for (int e = tid; e < MG_TREE_CHUNK * L; e += MG_TREE_CHUNK * MG_TREE_WAVES) {
-                const int c = e / L, i = e - c * L;
-                xs[c * xs_stride + i] = c < cnt ? means[(size_t)cid[c] * dim + i] : 0.0;
-            }
-            __syncthreads();
-            const double *x = xs + lane * xs_stride;
-            for (int c = wave; c < a.n; c += MG_TREE_WAVES) {
-                auto channel = [&](int row) {   // mg_score_kernel's fma chain over k from the bias
-                    const double *wr = Wm + (size_t)row * L;
-                    double acc = Bm[row];
-                    for (int k = 0; k < L; k++) acc = fma(wr[k], x[k], acc);
-                    return acc;
-                };
-                rs[c * MG_TREE_CHUNK + lane] = mg_constraint_residual(a, c, channel, 0);
-            }
-            __syncthreads();
-            if (tid < cnt) {
-                double err = 0.0;
-                for (int c = 0; c < a.n; c++) err += rs[c * MG_TREE_CHUNK + tid];
-                cval[tid] = err;
-            }
-            __syncthreads();
+            mg_tree_score_chunk(a, s, means, dim, cnt, tid, lane, wave);
             if (tid == 0) {
                 for (int j = 0; j < cnt; j++) {
-                    mg_tree_heappush(lo_v, lo_n, lo_len, lp.cap_local, cval[j], cid[j], flags);   // _find_best_cluster_candidates
+                    mg_heappush(lo, lo_len, lp.s.cap_local, mg_vn{s.cval[j], cid[j]}, lt, flags);   // _find_best_cluster_candidates
                     if (clast[j]) {   // the node's children are all in: result_queue[:n_candidates] onto the level's heap
                         const int m = min(n_cand, lo_len);
-                        for (int i = 0; i < m; i++) mg_tree_heappush(lv_v, lv_n, lv_len, lp.cap_level, lo_v[i], lo_n[i], flags);
+                        for (int i = 0; i < m; i++) mg_heappush(lv, lv_len, lp.s.cap_level, mg_heap_get(lo, i), lt, flags);
                         lo_len = 0;
                     }
                 }
@@ -235,7 +295,7 @@ __global__ __launch_bounds__(MG_TREE_CHUNK *MG_TREE_WAVES) void mg_tree_search_k
         }
         if (tid == 0) {   // candidates = new_candidates[:n_candidates]
             const int m = min(n_cand, lv_len);
-            for (int i = 0; i < m; i++) { fr_v[i] = lv_v[i]; fr_n[i] = lv_n[i]; }
+            for (int i = 0; i < m; i++) { fr_v[i] = lv.v[i]; fr_n[i] = lv.n[i]; }
             s_fr_len = m;
         }
         __syncthreads();
@@ -247,188 +307,13 @@ __global__ __launch_bounds__(MG_TREE_CHUNK *MG_TREE_WAVES) void mg_tree_search_k
             flags |= MG_TREE_NO_RESULT;
             r.leaf = 0; r.value = INFINITY; r.row = d->first[0];
         } else {
-            r.leaf = re_n[0]; r.value = re_v[0]; r.row = d->first[re_n[0]];
-            mg_tree_heappop_compares(re_v, re_n, res_len, flags);
+            r.leaf = re.n[0]; r.value = re.v[0]; r.row = d->first[re.n[0]];
+            mg_heappop_compares(re, res_len, lt);
         }
         r.flags = flags;
         r.evaluations = s_evals;
         rec[blockIdx.x] = r;
     }
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// C ABI
-// ---------------------------------------------------------------------------------------------------------------
-#define MG_TREE_REQUIRE(cond, ...) MG_REQUIRE_AS(cond, MG_ERR_INVALID_ARGUMENT, __VA_ARGS__)
-
-static void mg_tree_free(mg_cluster_tree *t) {
-    if (!t) return;
-    for (void *q : {(void *)t->d_means, (void *)t->d_child_begin, (void *)t->d_children, (void *)t->d_first, (void *)t->d_points, (void *)t->d_leaf,
-                    (void *)t->d_kd_begin, (void *)t->d_kd_roots, (void *)t->d_kd_left, (void *)t->d_kd_right, (void *)t->d_kd_inner})
-        if (q) (void)hipFree(q);
-    delete t;
-}
-
-extern "C" int mg_cluster_tree_create(mg_primitive *prim, int32_t n_nodes, int32_t dim, const double *means, const int32_t *child_begin,
-                                      const int32_t *children, const int64_t *first_index, int64_t n_rows, mg_cluster_tree **tree) {
-    MG_TREE_REQUIRE(tree != nullptr, "mg_cluster_tree_create: tree is NULL");
-    *tree = nullptr;
-    MG_TREE_REQUIRE(prim && means && child_begin && first_index, "mg_cluster_tree_create: NULL argument");
-    MG_TREE_REQUIRE(n_nodes >= 1, "mg_cluster_tree_create: n_nodes = %d", n_nodes);
-    MG_TREE_REQUIRE(n_rows >= 1, "mg_cluster_tree_create: n_rows = %lld", (long long)n_rows);
-    MG_TREE_REQUIRE(dim >= prim->L, "mg_cluster_tree_create: mean width %d < the primitive's %d spatial components", dim, prim->L);
-    const int64_t n_edges = (int64_t)n_nodes - 1;
-    MG_TREE_REQUIRE(child_begin[0] == 0 && child_begin[n_nodes] == n_edges,
-                    "mg_cluster_tree_create: child_begin must run from 0 to n_nodes - 1 = %lld (every node but the root has one parent)",
-                    (long long)n_edges);
-    MG_TREE_REQUIRE(n_edges == 0 || children != nullptr, "mg_cluster_tree_create: children is NULL");
-    std::vector<int32_t> parents(n_nodes, -1);
-    int max_children = 0;
-    for (int32_t i = 0; i < n_nodes; i++) {
-        const int32_t b = child_begin[i], e = child_begin[i + 1];
-        MG_TREE_REQUIRE(b <= e, "mg_cluster_tree_create: child_begin decreases at node %d", i);
-        MG_TREE_REQUIRE(e - b <= MG_TREE_MAX_CHILDREN, "mg_cluster_tree_create: node %d has %d children (at most %d)", i, e - b, MG_TREE_MAX_CHILDREN);
-        max_children = std::max(max_children, e - b);
-        for (int32_t k = b; k < e; k++) {
-            const int32_t c = children[k];
-            MG_TREE_REQUIRE(c >= 1 && c < n_nodes, "mg_cluster_tree_create: child %d of node %d out of range (the root is nobody's child)", c, i);
-            MG_TREE_REQUIRE(parents[c] < 0, "mg_cluster_tree_create: node %d has more than one parent", c);
-            parents[c] = i;
-        }
-        const int64_t fi = first_index[i];
-        MG_TREE_REQUIRE(fi >= -1 && fi < n_rows, "mg_cluster_tree_create: node %d: index %lld out of range [0, %lld)", i, (long long)fi, (long long)n_rows);
-        MG_TREE_REQUIRE(!(e == b && i != 0 && fi < 0), "mg_cluster_tree_create: leaf %d has no index", i);
-    }
-    // reachability from the root by levels: n - 1 edges, one parent each, all reached <=> a tree (no cycle)
-    std::vector<int32_t> level(1, 0), next;
-    int64_t reached = 1;
-    int depth = 0;
-    while (true) {
-        next.clear();
-        for (int32_t v : level)
-            for (int32_t k = child_begin[v]; k < child_begin[v + 1]; k++) next.push_back(children[k]);
-        if (next.empty()) break;
-        depth++;
-        reached += (int64_t)next.size();
-        MG_TREE_REQUIRE(depth <= MG_TREE_MAX_DEPTH && reached <= n_nodes, "mg_cluster_tree_create: depth beyond %d or a cycle", MG_TREE_MAX_DEPTH);
-        level.swap(next);
-    }
-    MG_TREE_REQUIRE(reached == n_nodes, "mg_cluster_tree_create: %lld of %d nodes reachable from the root (a cycle)", (long long)reached, n_nodes);
-    mg_context *ctx = prim->ctx;
-    MG_HIP_CHECK(hipSetDevice(ctx->device));
-    mg_cluster_tree *t = new mg_cluster_tree;
-    t->ctx = ctx; t->n_nodes = n_nodes; t->dim = dim; t->depth = depth; t->max_children = max_children; t->n_rows = n_rows;
-    const size_t mb = (size_t)n_nodes * dim * 8, cbb = (size_t)(n_nodes + 1) * 4, chb = (size_t)std::max<int64_t>(n_edges, 1) * 4, fb = (size_t)n_nodes * 8;
-    hipError_t e = hipMalloc(&t->d_means, mb);
-    if (e == hipSuccess) e = hipMalloc(&t->d_child_begin, cbb);
-    if (e == hipSuccess) e = hipMalloc(&t->d_children, chb);
-    if (e == hipSuccess) e = hipMalloc(&t->d_first, fb);
-    if (e == hipSuccess) e = hipMemcpy(t->d_means, means, mb, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(t->d_child_begin, child_begin, cbb, hipMemcpyHostToDevice);
-    if (e == hipSuccess && n_edges > 0) e = hipMemcpy(t->d_children, children, (size_t)n_edges * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(t->d_first, first_index, fb, hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        mg_tree_free(t);
-        return mg_hip_fail(e, "mg_cluster_tree_create: upload");
-    }
-    *tree = t;
-    return MG_OK;
-}
-
-extern "C" void mg_cluster_tree_destroy(mg_cluster_tree *tree) {
-    if (!tree) return;
-    (void)hipSetDevice(tree->ctx->device);
-    (void)hipStreamSynchronize(tree->ctx->stream);   // no search in flight reads the arrays
-    mg_tree_free(tree);
-}
-
-static int mg_kd_tree_search(int32_t n_searches, mg_primitive *const *prims, mg_cluster_tree *const *trees, const mg_constraint_set *const *csets,
-                             int32_t n_candidates, mg_tree_search_record *records_dev);
-
-extern "C" int mg_cluster_tree_search(int32_t n_searches, mg_primitive *const *prims, mg_cluster_tree *const *trees,
-                                      const mg_constraint_set *const *csets, int32_t n_candidates, mg_tree_search_record *records_dev) {
-    MG_TREE_REQUIRE(n_searches >= 0, "mg_cluster_tree_search: n_searches = %d", n_searches);
-    if (n_searches == 0) return MG_OK;
-    MG_TREE_REQUIRE(prims && trees && csets && records_dev, "mg_cluster_tree_search: NULL argument");
-    MG_TREE_REQUIRE(n_candidates >= 1 && n_candidates <= MG_TREE_MAX_CANDIDATES, "mg_cluster_tree_search: n_candidates = %d outside [1, %d]",
-                    n_candidates, MG_TREE_MAX_CANDIDATES);
-    MG_TREE_REQUIRE(prims[0] != nullptr, "mg_cluster_tree_search: primitive 0 is NULL");
-    MG_TREE_REQUIRE(trees[0] != nullptr, "mg_cluster_tree_search: search 0: NULL primitive, tree or constraint set");
-    for (int32_t s = 1; s < n_searches; s++)
-        MG_TREE_REQUIRE(trees[s] == nullptr || trees[s]->kind == trees[0]->kind,
-                        "mg_cluster_tree_search: search %d: a %s tree in a call of %s trees (one kind per call)", s,
-                        trees[s]->kind ? "KD" : "feature", trees[0]->kind ? "KD" : "feature");
-    if (trees[0]->kind == 1) return mg_kd_tree_search(n_searches, prims, trees, csets, n_candidates, records_dev);
-    mg_context *ctx = prims[0]->ctx;
-    std::vector<mg_tree_search_desc> tab(n_searches);
-    int Lmax = 1, ncmax = 1, maxch = 1, maxdepth = 0, wrows = 0;
-    bool rows_known = true;
-    for (int32_t s = 0; s < n_searches; s++) {
-        mg_primitive *p = prims[s];
-        const mg_cluster_tree *t = trees[s];
-        const mg_constraint_set *cs = csets[s];
-        MG_TREE_REQUIRE(p && t && cs, "mg_cluster_tree_search: search %d: NULL primitive, tree or constraint set", s);
-        MG_TREE_REQUIRE(p->ctx == ctx, "mg_cluster_tree_search: search %d: the primitives live in different contexts", s);
-        MG_TREE_REQUIRE(t->ctx == ctx, "mg_cluster_tree_search: search %d: the tree was uploaded to another context", s);
-        MG_TREE_REQUIRE(cs->prim == p, "mg_cluster_tree_search: search %d: the constraint set belongs to another primitive", s);
-        MG_TREE_REQUIRE(t->dim >= p->L, "mg_cluster_tree_search: search %d: tree means of width %d < %d spatial components", s, t->dim, p->L);
-        mg_tree_search_desc &d = tab[s];
-        memset(&d, 0, sizeof(d));
-        d.a.W = cs->d_W; d.a.bias = cs->d_bias; d.a.par = cs->d_par; d.a.woff = cs->d_woff; d.a.chain = cs->d_chain; d.a.choff = cs->d_choff;
-        d.a.pose = cs->d_pose; d.a.align = cs->d_align; d.a.align_cand = nullptr; d.a.lat = nullptr; d.a.out = nullptr; d.a.res = nullptr;
-        d.a.B = 0; d.a.ld = 0; d.a.n = cs->n; d.a.nch = cs->nch; d.a.L = p->L;
-        d.means = t->d_means; d.child_begin = t->d_child_begin; d.children = t->d_children; d.first = t->d_first; d.dim = t->dim;
-        d.rows = cs->rows;
-        rows_known = rows_known && cs->rows > 0;
-        wrows = std::max(wrows, (int)cs->rows);
-        Lmax = std::max(Lmax, (int)p->L);
-        ncmax = std::max(ncmax, (int)cs->n);
-        maxch = std::max(maxch, (int)t->max_children);
-        maxdepth = std::max(maxdepth, (int)t->depth);
-    }
-    mg_tree_lds_plan lp = mg_tree_plan(Lmax, ncmax, n_candidates, maxch, maxdepth, rows_known ? wrows : 0);
-    if (lp.bytes > 160 * 1024 && lp.wrows > 0) lp = mg_tree_plan(Lmax, ncmax, n_candidates, maxch, maxdepth, 0);   // W from memory
-    if (lp.bytes > 160 * 1024) {
-        mg_set_error("mg_cluster_tree_search: %zu bytes of LDS (latents %d, constraints %d, candidates %d, children %d, depth %d) beyond 160 KiB",
-                     lp.bytes, Lmax, ncmax, n_candidates, maxch, maxdepth);
-        return MG_ERR_UNSUPPORTED;
-    }
-    MG_HIP_CHECK(hipSetDevice(ctx->device));
-    const size_t tab_bytes = tab.size() * sizeof(mg_tree_search_desc);
-    if (!ctx->tree_tab_dev || ctx->tree_tab_host.size() != tab_bytes || memcmp(ctx->tree_tab_host.data(), tab.data(), tab_bytes) != 0) {
-        MG_HIP_CHECK(hipStreamSynchronize(ctx->stream));   // no launch in flight reads the table being replaced
-        if (ctx->tree_tab_cap < tab_bytes) {
-            if (ctx->tree_tab_dev) { (void)hipFree(ctx->tree_tab_dev); ctx->tree_tab_dev = nullptr; ctx->tree_tab_cap = 0; }
-            MG_HIP_CHECK(hipMalloc(&ctx->tree_tab_dev, tab_bytes));
-            ctx->tree_tab_cap = tab_bytes;
-        }
-        MG_HIP_CHECK(hipMemcpy(ctx->tree_tab_dev, tab.data(), tab_bytes, hipMemcpyHostToDevice));
-        ctx->tree_tab_host.assign((const unsigned char *)tab.data(), (const unsigned char *)tab.data() + tab_bytes);
-    }
-    if (lp.bytes > 64 * 1024)
-        MG_HIP_CHECK(hipFuncSetAttribute((const void *)mg_tree_search_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    mg_prof_begin(ctx, 11);
-    hipLaunchKernelGGL(mg_tree_search_kernel, dim3(n_searches), dim3(MG_TREE_CHUNK * MG_TREE_WAVES), lp.bytes, ctx->stream,
-                       (const mg_tree_search_desc *)ctx->tree_tab_dev, lp, records_dev);
-    mg_prof_end(ctx, 11);
-    MG_HIP_CHECK(hipGetLastError());
-    return MG_OK;
-}
-
-extern "C" int mg_cluster_tree_search_host(int32_t n_searches, mg_primitive *const *prims, mg_cluster_tree *const *trees,
-                                           const mg_constraint_set *const *csets, int32_t n_candidates, mg_tree_search_record *records) {
-    MG_TREE_REQUIRE(n_searches >= 0 && (n_searches == 0 || (records && prims && prims[0])), "mg_cluster_tree_search_host: bad arguments");
-    if (n_searches == 0) return MG_OK;
-    mg_context *ctx = prims[0]->ctx;
-    const int64_t bytes = (int64_t)n_searches * (int64_t)sizeof(mg_tree_search_record);
-    void *d_rec = nullptr;
-    int rc = mg_ctx_scratch(ctx, bytes, &d_rec);
-    if (rc != MG_OK) return rc;
-    rc = mg_cluster_tree_search(n_searches, prims, trees, csets, n_candidates, (mg_tree_search_record *)d_rec);
-    if (rc != MG_OK) return rc;
-    MG_HIP_CHECK(hipMemcpyAsync(records, d_rec, (size_t)bytes, hipMemcpyDeviceToHost, ctx->stream));
-    MG_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    return MG_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -447,13 +332,6 @@ extern "C" int mg_cluster_tree_search_host(int32_t n_searches, mg_primitive *con
 // ---------------------------------------------------------------------------------------------------------------
 #define MG_KD_GROUP 32
 
-struct mg_kd_search_desc {
-    mg_score_args a;
-    const double *points;
-    const int32_t *child_begin, *children, *leaf, *kd_begin, *kd_roots, *kd_left, *kd_right, *kd_inner;
-    int32_t dim, rows, n_kd, pad;
-};
-
 struct mg_hent {   // a heap entry: value, then up to three ints (what each heap compares and carries)
     double v;
     int32_t a, b, c, pad;
@@ -463,23 +341,6 @@ struct mg_kent {   // a KD descent's (cost, depth)
     int32_t d, pad;
 };
 
-// heapq.heappush with the tuple comparison lt
-template <class T, class Lt>
-__device__ __forceinline__ void mg_heappush_t(T *h, int &len, int cap, const T &x, Lt lt, int &flags) {
-    if (len >= cap) { flags |= MG_TREE_OVERFLOW; return; }
-    int pos = len++;
-    while (pos > 0) {
-        const int parent = (pos - 1) >> 1;
-        if (lt(x, h[parent])) {
-            h[pos] = h[parent];
-            pos = parent;
-            continue;
-        }
-        break;
-    }
-    h[pos] = x;
-}
-
 // Python's `list < list` of two rows of the points table: the first position whose items differ decides
 __device__ bool mg_kd_rows_lt(const double *__restrict__ P, int dim, int r, int s) {
     const double *x = P + (size_t)r * dim, *y = P + (size_t)s * dim;
@@ -488,67 +349,27 @@ __device__ bool mg_kd_rows_lt(const double *__restrict__ P, int dim, int r, int 
     return false;
 }
 
-// cval[j] = the objective of points row cid[j] for j < cnt (a row < 0 scores zeros, and its value is not used).  Called
-// by every thread of the workgroup; mg_tree_search_kernel's statements.
-__device__ void mg_kd_score(const mg_score_args &a, const double *Wm, const double *Bm, const double *__restrict__ P, int dim, const int32_t *cid,
-                            int cnt, double *xs, double *rs, double *cval, int tid, int lane, int wave) {
-    const int L = a.L, xs_stride = L + 1;
-    for (int e = tid; e < MG_TREE_CHUNK * L; e += MG_TREE_CHUNK * MG_TREE_WAVES) {
-        const int c = e / L, i = e - c * L;
-        xs[c * xs_stride + i] = (c < cnt && cid[c] >= 0) ? P[(size_t)cid[c] * dim + i] : 0.0;
-    }
-    __syncthreads();
-    const double *x = xs + lane * xs_stride;
-    for (int c = wave; c < a.n; c += MG_TREE_WAVES) {
-        auto channel = [&](int row) {
-            const double *wr = Wm + (size_t)row * L;
-            double acc = Bm[row];
-            for (int k = 0; k < L; k++) acc = fma(wr[k], x[k], acc);
-            return acc;
-        };
-        rs[c * MG_TREE_CHUNK + lane] = mg_constraint_residual(a, c, channel, 0);
-    }
-    __syncthreads();
-    if (tid < cnt) {
-        double err = 0.0;
-        for (int c = 0; c < a.n; c++) err += rs[c * MG_TREE_CHUNK + tid];
-        cval[tid] = err;
-    }
-    __syncthreads();
-}
-
 struct mg_kd_lds_plan {
-    int n_cand, cap_local, cap_level, cap_res, cap_leaf, kcap, kd_depth, wrows;
-    size_t off_w, off_rs, off_cval, off_lo, off_lv, off_re, off_lf, off_kh, off_resv, off_kev, off_cid, off_cci, off_clast, off_frn, off_froff,
-        off_dsoff, off_resrow, off_dfr, off_dlast, bytes;
+    mg_tree_lds_shared s;
+    int cap_leaf, kcap, kd_depth;
+    size_t off_lo, off_lv, off_re, off_lf, off_kh, off_resv, off_kev, off_cci, off_dsoff, off_resrow, off_dfr, off_dlast, bytes;
 };
 
 static mg_kd_lds_plan mg_kd_plan(int Lmax, int ncmax, int n_cand, int max_children, int max_depth, int max_kd_children, int kd_depth, int wrows) {
     mg_kd_lds_plan p;
-    p.wrows = wrows;
-    p.n_cand = n_cand;
-    p.cap_local = std::max(max_children, 1);
-    p.cap_level = n_cand * std::min(n_cand, p.cap_local);
-    p.cap_res = n_cand * (max_depth + 1);
     p.cap_leaf = std::max(max_kd_children, 1);
     p.kd_depth = kd_depth;
     p.kcap = kd_depth + 1;
-    size_t o = (size_t)MG_TREE_CHUNK * (Lmax + 1) * 8;   // xs [64][L+1]
-    p.off_w = o;      o += (size_t)wrows * (Lmax + 1) * 8;
-    p.off_rs = o;     o += (size_t)std::max(ncmax, 1) * MG_TREE_CHUNK * 8;
-    p.off_cval = o;   o += MG_TREE_CHUNK * 8;
-    p.off_lo = o;     o += (size_t)p.cap_local * sizeof(mg_hent);
-    p.off_lv = o;     o += (size_t)p.cap_level * sizeof(mg_hent);
-    p.off_re = o;     o += (size_t)p.cap_res * sizeof(mg_hent);
+    size_t o = mg_tree_carve_head(p.s, Lmax, ncmax, n_cand, max_children, max_depth, wrows);
+    p.off_lo = o;     o += (size_t)p.s.cap_local * sizeof(mg_hent);
+    p.off_lv = o;     o += (size_t)p.s.cap_level * sizeof(mg_hent);
+    p.off_re = o;     o += (size_t)p.s.cap_res * sizeof(mg_hent);
     p.off_lf = o;     o += (size_t)p.cap_leaf * sizeof(mg_hent);
     p.off_kh = o;     o += (size_t)MG_KD_GROUP * p.kcap * sizeof(mg_kent);
     p.off_resv = o;   o += MG_KD_GROUP * 8;
     p.off_kev = o;    o += (size_t)MG_KD_GROUP * p.kcap * 4;
-    p.off_cid = o;    o += MG_TREE_CHUNK * 4;
+    o = mg_tree_carve_ints(p.s, o);
     p.off_cci = o;    o += MG_TREE_CHUNK * 4;
-    p.off_clast = o;  o += MG_TREE_CHUNK * 4;
-    p.off_frn = o;    o += (size_t)n_cand * 4;
-    p.off_froff = o;  o += (size_t)(n_cand + 1) * 4;
     p.off_dsoff = o;  o += (size_t)(n_cand + 1) * 4;
     p.off_resrow = o; o += MG_KD_GROUP * 4;
     p.off_dfr = o;    o += MG_KD_GROUP * 4;
@@ -557,12 +378,12 @@ static mg_kd_lds_plan mg_kd_plan(int Lmax, int ncmax, int n_cand, int max_childr
     return p;
 }
 
-__global__ __launch_bounds__(MG_TREE_CHUNK *MG_TREE_WAVES) void mg_kd_tree_search_kernel(const mg_kd_search_desc *__restrict__ tab, mg_kd_lds_plan lp,
-                                                                                         mg_tree_search_record *__restrict__ rec) {
+__global__ __launch_bounds__(MG_TREE_THREADS) void mg_kd_tree_search_kernel(const mg_tree_search_desc *__restrict__ tab, mg_kd_lds_plan lp,
+                                                                            mg_tree_search_record *__restrict__ rec) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     __shared__ int s_fr_len, s_eff, s_total, s_ndesc, s_stop, s_kflags;
     __shared__ long long s_evals;
-    const mg_kd_search_desc *d = tab + blockIdx.x;
+    const mg_tree_search_desc *d = tab + blockIdx.x;
     const mg_score_args a = d->a;
     const double *__restrict__ P = d->points;
     const int32_t *__restrict__ cb = d->child_begin;
@@ -573,10 +394,14 @@ __global__ __launch_bounds__(MG_TREE_CHUNK *MG_TREE_WAVES) void mg_kd_tree_searc
     const int32_t *__restrict__ kl = d->kd_left;
     const int32_t *__restrict__ krt = d->kd_right;
     const int32_t *__restrict__ kin = d->kd_inner;
-    const int dim = d->dim, n_kd = d->n_kd, L = a.L, n_cand = lp.n_cand, kcap = lp.kcap;
-    double *xs = (double *)smem;
-    double *rs = (double *)(smem + lp.off_rs);
-    double *cval = (double *)(smem + lp.off_cval);
+    const int dim = d->dim, n_kd = d->n_kd, n_cand = lp.s.n_cand, kcap = lp.kcap;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const mg_tree_lds s = mg_tree_lds_of(smem, lp.s, a, d->rows, tid);
+    double *cval = s.cval;
+    // (cid from the plan, not s.cid: read back out of the struct it costs the KD kernel two VGPRs)
+    int32_t *cid = (int32_t *)(smem + lp.s.off_cid), *clast = (int32_t *)(smem + lp.s.off_clast);
+    int32_t *fr_n = (int32_t *)(smem + lp.s.off_frn), *fr_off = (int32_t *)(smem + lp.s.off_froff);
     mg_hent *lo = (mg_hent *)(smem + lp.off_lo);
     mg_hent *lv = (mg_hent *)(smem + lp.off_lv);
     mg_hent *re = (mg_hent *)(smem + lp.off_re);
@@ -584,25 +409,11 @@ __global__ __launch_bounds__(MG_TREE_CHUNK *MG_TREE_WAVES) void mg_kd_tree_searc
     mg_kent *kh_all = (mg_kent *)(smem + lp.off_kh);
     double *res_v = (double *)(smem + lp.off_resv);
     int32_t *kev_all = (int32_t *)(smem + lp.off_kev);
-    int32_t *cid = (int32_t *)(smem + lp.off_cid);
     int32_t *cci = (int32_t *)(smem + lp.off_cci);
-    int32_t *clast = (int32_t *)(smem + lp.off_clast);
-    int32_t *fr_n = (int32_t *)(smem + lp.off_frn);
-    int32_t *fr_off = (int32_t *)(smem + lp.off_froff);
     int32_t *ds_off = (int32_t *)(smem + lp.off_dsoff);
     int32_t *res_row = (int32_t *)(smem + lp.off_resrow);
     int32_t *dfr = (int32_t *)(smem + lp.off_dfr);
     int32_t *dlast = (int32_t *)(smem + lp.off_dlast);
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const double *Wm = a.W, *Bm = a.bias;
-    if (lp.wrows > 0 && d->rows > 0) {
-        double *wl = (double *)(smem + lp.off_w), *bl = wl + (size_t)lp.wrows * L;
-        for (int i = tid; i < d->rows * L; i += MG_TREE_CHUNK * MG_TREE_WAVES) wl[i] = a.W[i];
-        for (int i = tid; i < d->rows; i += MG_TREE_CHUNK * MG_TREE_WAVES) bl[i] = a.bias[i];
-        Wm = wl;
-        Bm = bl;
-    }
     // (value, cluster_index, node): the indices differ within a node
     auto lt_local = [](const mg_hent &x, const mg_hent &y) { return x.v == y.v ? x.a < y.a : x.v < y.v; };
     // thread 0's heap state
@@ -659,26 +470,23 @@ __global__ __launch_bounds__(MG_TREE_CHUNK *MG_TREE_WAVES) void mg_kd_tree_searc
             const int cnt = min(MG_TREE_CHUNK, tot - c0);
             if (tid < cnt) {
                 const int e = c0 + tid;
-                int f = 0;
-                while (f + 1 < eff && fr_off[f + 1] <= e) f++;
-                const int node = fr_n[f];
+                const int f = mg_tree_owner(fr_off, eff, e, clast[tid]);
                 cci[tid] = e - fr_off[f];
-                cid[tid] = n_kd + ch[cb[node] + (e - fr_off[f])];
-                clast[tid] = (e == fr_off[f + 1] - 1);
+                cid[tid] = n_kd + ch[cb[fr_n[f]] + (e - fr_off[f])];
             }
             __syncthreads();
-            mg_kd_score(a, Wm, Bm, P, dim, cid, cnt, xs, rs, cval, tid, lane, wave);
+            mg_tree_score_chunk(a, s, P, dim, cnt, tid, lane, wave);
             if (tid == 0) {
                 for (int j = 0; j < cnt; j++) {
                     mg_hent x;
                     x.v = cval[j]; x.a = cci[j]; x.b = 0; x.c = cid[j] - n_kd; x.pad = 0;
-                    mg_heappush_t(lo, lo_len, lp.cap_local, x, lt_local, flags);
+                    mg_heappush(lo, lo_len, lp.s.cap_local, x, lt_local, flags);
                     if (clast[j]) {   // result_queue[:n_candidates] onto new_candidates as (value, idx, node)
                         const int m = min(n_cand, lo_len);
                         for (int i = 0; i < m; i++) {
                             mg_hent y;   // (built field by field: a copy of the whole entry went through scratch)
                             y.v = lo[i].v; y.a = i; y.b = lo[i].b; y.c = lo[i].c; y.pad = 0;
-                            mg_heappush_t(lv, lv_len, lp.cap_level, y, lt_level, flags);
+                            mg_heappush(lv, lv_len, lp.s.cap_level, y, lt_level, flags);
                         }
                         lo_len = 0;
                     }
@@ -696,22 +504,20 @@ __global__ __launch_bounds__(MG_TREE_CHUNK *MG_TREE_WAVES) void mg_kd_tree_searc
             int cur = -1, klen = 0, depth = 0, kflags = 0;
             if (tid < gcnt) {
                 const int e = g0 + tid;
-                int f = 0;
-                while (f + 1 < eff && ds_off[f + 1] <= e) f++;
+                const int f = mg_tree_owner(ds_off, eff, e, dlast[tid]);
                 const int node = fr_n[f];
                 const int nk = kb[node + 1] - kb[node];
                 const int start = nk > 0 ? kr[kb[node] + (e - ds_off[f])] : n_kd + node;
                 cur = nk > 0 ? start : -1;
                 cid[tid] = start;
                 dfr[tid] = f;
-                dlast[tid] = (e == ds_off[f + 1] - 1);
             }
             __syncthreads();
-            mg_kd_score(a, Wm, Bm, P, dim, cid, gcnt, xs, rs, cval, tid, lane, wave);
+            mg_tree_score_chunk(a, s, P, dim, gcnt, tid, lane, wave);
             if (tid < gcnt) {   // the KD root's point (or the leaf's mean) at depth 0
                 mg_kent x;
                 x.v = cval[tid]; x.d = 0; x.pad = 0;
-                mg_heappush_t(kh, klen, kcap, x, lt_kd, kflags);
+                mg_heappush(kh, klen, kcap, x, lt_kd, kflags);
                 kev[0] = cid[tid];
             }
             if (tid == 0) s_evals += gcnt;
@@ -723,7 +529,7 @@ __global__ __launch_bounds__(MG_TREE_CHUNK *MG_TREE_WAVES) void mg_kd_tree_searc
                     cid[2 * tid + 1] = active ? kl[cur] : -1;
                 }
                 if (!__syncthreads_or(active)) break;
-                mg_kd_score(a, Wm, Bm, P, dim, cid, MG_TREE_CHUNK, xs, rs, cval, tid, lane, wave);
+                mg_tree_score_chunk(a, s, P, dim, MG_TREE_CHUNK, tid, lane, wave);
                 if (active) {   // _decide_direction_objective: left only if l < r
                     const int r = cid[2 * tid], l = cid[2 * tid + 1];
                     double cost = INFINITY;
@@ -741,7 +547,7 @@ __global__ __launch_bounds__(MG_TREE_CHUNK *MG_TREE_WAVES) void mg_kd_tree_searc
                     if (cur >= 0 && depth < kcap) {
                         mg_kent x;
                         x.v = cost; x.d = depth; x.pad = 0;
-                        mg_heappush_t(kh, klen, kcap, x, lt_kd, kflags);
+                        mg_heappush(kh, klen, kcap, x, lt_kd, kflags);
                         kev[depth] = cur;
                     } else if (cur >= 0) {
                         kflags |= MG_TREE_OVERFLOW;
@@ -765,11 +571,11 @@ __global__ __launch_bounds__(MG_TREE_CHUNK *MG_TREE_WAVES) void mg_kd_tree_searc
                 for (int j = 0; j < gcnt; j++) {
                     mg_hent x;
                     x.v = res_v[j]; x.a = 0; x.b = res_row[j]; x.c = 0; x.pad = 0;
-                    mg_heappush_t(lf, lf_len, lp.cap_leaf, x, lt_leaf, flags);
+                    mg_heappush(lf, lf_len, lp.cap_leaf, x, lt_leaf, flags);
                     if (dlast[j]) {   // heappop(result_queue) onto results as (v, c_idx, sample)
                         mg_hent y;
                         y.v = lf[0].v; y.a = dfr[j]; y.b = lf[0].b; y.c = fr_n[dfr[j]]; y.pad = 0;
-                        mg_heappush_t(re, re_len, lp.cap_res, y, lt_res, flags);
+                        mg_heappush(re, re_len, lp.s.cap_res, y, lt_res, flags);
                         lf_len = 0;
                     }
                 }
@@ -804,6 +610,68 @@ __global__ __launch_bounds__(MG_TREE_CHUNK *MG_TREE_WAVES) void mg_kd_tree_searc
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// C ABI
+// ---------------------------------------------------------------------------------------------------------------
+#define MG_TREE_REQUIRE(cond, ...) MG_REQUIRE_AS(cond, MG_ERR_INVALID_ARGUMENT, __VA_ARGS__)
+
+static void mg_tree_free(mg_cluster_tree *t) {
+    if (!t) return;
+    for (void *q : {(void *)t->d_points, (void *)t->d_child_begin, (void *)t->d_children, (void *)t->d_first, (void *)t->d_leaf, (void *)t->d_kd_begin,
+                    (void *)t->d_kd_roots, (void *)t->d_kd_left, (void *)t->d_kd_right, (void *)t->d_kd_inner})
+        if (q) (void)hipFree(q);
+    delete t;
+}
+
+// n elements of h on the device: at least one allocated, copied when there is something to copy.  A step of a chain: does
+// nothing once e holds an error.
+template <class T>
+static void mg_tree_upload(hipError_t &e, T **d, const T *h, int64_t n) {
+    if (e == hipSuccess) e = hipMalloc(d, (size_t)std::max<int64_t>(n, 1) * sizeof(T));
+    if (e == hipSuccess && n > 0) e = hipMemcpy(*d, h, (size_t)n * sizeof(T), hipMemcpyHostToDevice);
+}
+
+// the end of both creators: the tree, or nothing partial left behind
+static int mg_tree_uploaded(hipError_t e, const char *what, mg_cluster_tree *t, mg_cluster_tree **tree) {
+    if (e != hipSuccess) {
+        mg_tree_free(t);
+        return mg_hip_fail(e, what);
+    }
+    *tree = t;
+    return MG_OK;
+}
+
+// A CSR list over the cluster nodes (begin[0] = 0, checked by the caller together with its end): rows that do not decrease and
+// hold at most MG_TREE_MAX_CHILDREN entries, so every row lies inside the list.  *widest: the longest row.
+static int mg_tree_check_rows(const char *fn, const char *what, int32_t n_nodes, const int32_t *begin, int *widest) {
+    *widest = 0;
+    for (int32_t i = 0; i < n_nodes; i++) {
+        const int32_t b = begin[i], e = begin[i + 1];
+        MG_TREE_REQUIRE(b <= e, "%s: %s decreases at node %d", fn, what, i);
+        MG_TREE_REQUIRE(e - b <= MG_TREE_MAX_CHILDREN, "%s: node %d has %d children (at most %d)", fn, i, e - b, MG_TREE_MAX_CHILDREN);
+        *widest = std::max(*widest, e - b);
+    }
+    return MG_OK;
+}
+
+// The cluster nodes' children (child_begin, children): n_nodes - 1 edges, every child in [1, n_nodes).  kids[i]: node i's.
+static int mg_tree_check_children(const char *fn, int32_t n_nodes, const int32_t *child_begin, const int32_t *children,
+                                  std::vector<std::vector<int32_t>> &kids, int *max_children) {
+    const int64_t n_edges = (int64_t)n_nodes - 1;
+    MG_TREE_REQUIRE(child_begin[0] == 0 && child_begin[n_nodes] == n_edges,
+                    "%s: child_begin must run from 0 to n_nodes - 1 = %lld (every node but the root has one parent)", fn, (long long)n_edges);
+    MG_TREE_REQUIRE(n_edges == 0 || children != nullptr, "%s: children is NULL", fn);
+    int rc = mg_tree_check_rows(fn, "child_begin", n_nodes, child_begin, max_children);
+    if (rc != MG_OK) return rc;
+    kids.assign(n_nodes, std::vector<int32_t>());
+    for (int32_t i = 0; i < n_nodes; i++)
+        for (int32_t k = child_begin[i]; k < child_begin[i + 1]; k++) {
+            MG_TREE_REQUIRE(children[k] >= 1 && children[k] < n_nodes, "%s: child %d of node %d out of range (the root is nobody's child)", fn, children[k], i);
+            kids[i].push_back(children[k]);
+        }
+    return MG_OK;
+}
+
 // one parent per node, reachable from `roots` (BFS by levels), at most max_depth edges deep: MG_OK, or the error set
 static int mg_tree_check_forest(const char *fn, const char *what, int32_t n, const std::vector<int32_t> &roots,
                                 const std::vector<std::vector<int32_t>> &kids, int max_depth, int *depth_out) {
@@ -836,6 +704,37 @@ static int mg_tree_check_forest(const char *fn, const char *what, int32_t n, con
     return MG_OK;
 }
 
+extern "C" int mg_cluster_tree_create(mg_primitive *prim, int32_t n_nodes, int32_t dim, const double *means, const int32_t *child_begin,
+                                      const int32_t *children, const int64_t *first_index, int64_t n_rows, mg_cluster_tree **tree) {
+    const char *fn = "mg_cluster_tree_create";
+    MG_TREE_REQUIRE(tree != nullptr, "%s: tree is NULL", fn);
+    *tree = nullptr;
+    MG_TREE_REQUIRE(prim && means && child_begin && first_index, "%s: NULL argument", fn);
+    MG_TREE_REQUIRE(n_nodes >= 1, "%s: n_nodes = %d", fn, n_nodes);
+    MG_TREE_REQUIRE(n_rows >= 1, "%s: n_rows = %lld", fn, (long long)n_rows);
+    MG_TREE_REQUIRE(dim >= prim->L, "%s: mean width %d < the primitive's %d spatial components", fn, dim, prim->L);
+    std::vector<std::vector<int32_t>> kids;
+    int max_children = 0, depth = 0;
+    int rc = mg_tree_check_children(fn, n_nodes, child_begin, children, kids, &max_children);
+    if (rc == MG_OK) rc = mg_tree_check_forest(fn, "cluster", n_nodes, std::vector<int32_t>(1, 0), kids, MG_TREE_MAX_DEPTH, &depth);
+    if (rc != MG_OK) return rc;
+    for (int32_t i = 0; i < n_nodes; i++) {
+        const int64_t fi = first_index[i];
+        MG_TREE_REQUIRE(fi >= -1 && fi < n_rows, "%s: node %d: index %lld out of range [0, %lld)", fn, i, (long long)fi, (long long)n_rows);
+        MG_TREE_REQUIRE(!(kids[i].empty() && i != 0 && fi < 0), "%s: leaf %d has no index", fn, i);
+    }
+    mg_context *ctx = prim->ctx;
+    MG_HIP_CHECK(hipSetDevice(ctx->device));
+    mg_cluster_tree *t = new mg_cluster_tree;
+    t->ctx = ctx; t->n_nodes = n_nodes; t->dim = dim; t->depth = depth; t->max_children = max_children; t->n_rows = n_rows;
+    hipError_t e = hipSuccess;
+    mg_tree_upload(e, &t->d_points, means, (int64_t)n_nodes * dim);
+    mg_tree_upload(e, &t->d_child_begin, child_begin, (int64_t)n_nodes + 1);
+    mg_tree_upload(e, &t->d_children, children, (int64_t)n_nodes - 1);
+    mg_tree_upload(e, &t->d_first, first_index, n_nodes);
+    return mg_tree_uploaded(e, "mg_cluster_tree_create: upload", t, tree);
+}
+
 extern "C" int mg_cluster_tree_create_kd(mg_primitive *prim, int32_t n_nodes, int32_t n_kd, int32_t dim, const double *points, const int32_t *child_begin,
                                          const int32_t *children, const int32_t *leaf, const int32_t *kd_begin, const int32_t *kd_roots,
                                          const int32_t *kd_left, const int32_t *kd_right, const int32_t *kd_inner, mg_cluster_tree **tree) {
@@ -846,79 +745,114 @@ extern "C" int mg_cluster_tree_create_kd(mg_primitive *prim, int32_t n_nodes, in
     MG_TREE_REQUIRE(n_nodes >= 1 && n_kd >= 0, "%s: n_nodes = %d, n_kd = %d", fn, n_nodes, n_kd);
     MG_TREE_REQUIRE(dim >= prim->L, "%s: point width %d < the primitive's %d spatial components", fn, dim, prim->L);
     MG_TREE_REQUIRE(n_kd == 0 || (kd_left && kd_right && kd_inner), "%s: NULL KD table", fn);
-    const int64_t n_edges = (int64_t)n_nodes - 1;
-    MG_TREE_REQUIRE(child_begin[0] == 0 && child_begin[n_nodes] == n_edges,
-                    "%s: child_begin must run from 0 to n_nodes - 1 = %lld (every node but the root has one parent)", fn, (long long)n_edges);
-    MG_TREE_REQUIRE(n_edges == 0 || children != nullptr, "%s: children is NULL", fn);
+    std::vector<std::vector<int32_t>> kids, kkids(n_kd);
+    int max_children = 0, max_kd = 0, depth = 0, kd_depth = 0;
+    int rc = mg_tree_check_children(fn, n_nodes, child_begin, children, kids, &max_children);
+    if (rc != MG_OK) return rc;
     const int32_t n_roots = kd_begin[n_nodes];
     MG_TREE_REQUIRE(kd_begin[0] == 0 && n_roots >= 0 && n_roots <= n_kd, "%s: kd_begin must run from 0 to at most n_kd", fn);
     MG_TREE_REQUIRE(n_roots == 0 || kd_roots != nullptr, "%s: kd_roots is NULL", fn);
-    std::vector<std::vector<int32_t>> kids(n_nodes), kkids(n_kd);
-    std::vector<int32_t> kroots;
-    int max_children = 0, max_kd = 0;
+    rc = mg_tree_check_rows(fn, "kd_begin", n_nodes, kd_begin, &max_kd);
+    if (rc != MG_OK) return rc;
     for (int32_t i = 0; i < n_nodes; i++) {
-        const int32_t b = child_begin[i], e = child_begin[i + 1], kb0 = kd_begin[i], ke = kd_begin[i + 1];
-        MG_TREE_REQUIRE(b <= e && kb0 <= ke, "%s: child_begin or kd_begin decreases at node %d", fn, i);
-        MG_TREE_REQUIRE(e - b <= MG_TREE_MAX_CHILDREN && ke - kb0 <= MG_TREE_MAX_CHILDREN, "%s: node %d has more than %d children", fn, i, MG_TREE_MAX_CHILDREN);
-        MG_TREE_REQUIRE(e == b || ke == kb0, "%s: node %d mixes cluster-node and KD-tree children", fn, i);
-        MG_TREE_REQUIRE(!(leaf[i] && e > b), "%s: leaf %d has cluster-node children", fn, i);
-        max_children = std::max(max_children, e - b);
-        max_kd = std::max(max_kd, ke - kb0);
-        for (int32_t k = b; k < e; k++) {
-            MG_TREE_REQUIRE(children[k] >= 1 && children[k] < n_nodes, "%s: child %d of node %d out of range (the root is nobody's child)", fn, children[k], i);
-            kids[i].push_back(children[k]);
-        }
-        for (int32_t k = kb0; k < ke; k++) kroots.push_back(kd_roots[k]);
+        MG_TREE_REQUIRE(kids[i].empty() || kd_begin[i + 1] == kd_begin[i], "%s: node %d mixes cluster-node and KD-tree children", fn, i);
+        MG_TREE_REQUIRE(!(leaf[i] && !kids[i].empty()), "%s: leaf %d has cluster-node children", fn, i);
     }
-    int depth = 0, kd_depth = 0;
-    int rc = mg_tree_check_forest(fn, "cluster", n_nodes, std::vector<int32_t>(1, 0), kids, MG_TREE_MAX_DEPTH, &depth);
+    rc = mg_tree_check_forest(fn, "cluster", n_nodes, std::vector<int32_t>(1, 0), kids, MG_TREE_MAX_DEPTH, &depth);
     if (rc != MG_OK) return rc;
     for (int32_t k = 0; k < n_kd; k++) {
         MG_TREE_REQUIRE(kd_left[k] >= -1 && kd_left[k] < n_kd && kd_right[k] >= -1 && kd_right[k] < n_kd, "%s: KD node %d: a child out of range", fn, k);
         if (kd_left[k] >= 0) kkids[k].push_back(kd_left[k]);
         if (kd_right[k] >= 0) kkids[k].push_back(kd_right[k]);
     }
-    rc = mg_tree_check_forest(fn, "KD", n_kd, kroots, kkids, MG_KD_MAX_DEPTH, &kd_depth);
+    rc = mg_tree_check_forest(fn, "KD", n_kd, std::vector<int32_t>(kd_roots, kd_roots + n_roots), kkids, MG_KD_MAX_DEPTH, &kd_depth);
     if (rc != MG_OK) return rc;
     mg_context *ctx = prim->ctx;
     MG_HIP_CHECK(hipSetDevice(ctx->device));
     mg_cluster_tree *t = new mg_cluster_tree;
     t->ctx = ctx; t->kind = 1; t->n_nodes = n_nodes; t->dim = dim; t->depth = depth; t->max_children = max_children; t->n_rows = (int64_t)n_kd + n_nodes;
     t->n_kd = n_kd; t->max_kd_children = max_kd; t->kd_depth = kd_depth;
-    const size_t pb = (size_t)t->n_rows * dim * 8, nb = (size_t)(n_nodes + 1) * 4, chb = (size_t)std::max<int64_t>(n_edges, 1) * 4;
-    const size_t rb = (size_t)std::max(n_roots, 1) * 4, kb = (size_t)std::max(n_kd, 1) * 4;
-    hipError_t e = hipMalloc(&t->d_points, pb);
-    if (e == hipSuccess) e = hipMalloc(&t->d_child_begin, nb);
-    if (e == hipSuccess) e = hipMalloc(&t->d_children, chb);
-    if (e == hipSuccess) e = hipMalloc(&t->d_leaf, nb);
-    if (e == hipSuccess) e = hipMalloc(&t->d_kd_begin, nb);
-    if (e == hipSuccess) e = hipMalloc(&t->d_kd_roots, rb);
-    if (e == hipSuccess) e = hipMalloc(&t->d_kd_left, kb);
-    if (e == hipSuccess) e = hipMalloc(&t->d_kd_right, kb);
-    if (e == hipSuccess) e = hipMalloc(&t->d_kd_inner, kb);
-    if (e == hipSuccess) e = hipMemcpy(t->d_points, points, pb, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(t->d_child_begin, child_begin, nb, hipMemcpyHostToDevice);
-    if (e == hipSuccess && n_edges > 0) e = hipMemcpy(t->d_children, children, (size_t)n_edges * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(t->d_leaf, leaf, (size_t)n_nodes * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(t->d_kd_begin, kd_begin, nb, hipMemcpyHostToDevice);
-    if (e == hipSuccess && n_roots > 0) e = hipMemcpy(t->d_kd_roots, kd_roots, (size_t)n_roots * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess && n_kd > 0) e = hipMemcpy(t->d_kd_left, kd_left, (size_t)n_kd * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess && n_kd > 0) e = hipMemcpy(t->d_kd_right, kd_right, (size_t)n_kd * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess && n_kd > 0) e = hipMemcpy(t->d_kd_inner, kd_inner, (size_t)n_kd * 4, hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        mg_tree_free(t);
-        return mg_hip_fail(e, "mg_cluster_tree_create_kd: upload");
+    hipError_t e = hipSuccess;
+    mg_tree_upload(e, &t->d_points, points, t->n_rows * dim);
+    mg_tree_upload(e, &t->d_child_begin, child_begin, (int64_t)n_nodes + 1);
+    mg_tree_upload(e, &t->d_children, children, (int64_t)n_nodes - 1);
+    mg_tree_upload(e, &t->d_leaf, leaf, n_nodes);
+    mg_tree_upload(e, &t->d_kd_begin, kd_begin, (int64_t)n_nodes + 1);
+    mg_tree_upload(e, &t->d_kd_roots, kd_roots, n_roots);
+    mg_tree_upload(e, &t->d_kd_left, kd_left, n_kd);
+    mg_tree_upload(e, &t->d_kd_right, kd_right, n_kd);
+    mg_tree_upload(e, &t->d_kd_inner, kd_inner, n_kd);
+    return mg_tree_uploaded(e, "mg_cluster_tree_create_kd: upload", t, tree);
+}
+
+extern "C" void mg_cluster_tree_destroy(mg_cluster_tree *tree) {
+    if (!tree) return;
+    (void)hipSetDevice(tree->ctx->device);
+    (void)hipStreamSynchronize(tree->ctx->stream);   // no search in flight reads the arrays
+    mg_tree_free(tree);
+}
+
+// The descriptor table of a call on the device: rewritten only when it differs from the last call's (ctx->tree_tab_host)
+static int mg_tree_table_upload(mg_context *ctx, size_t bytes, const void *data) {
+    if (ctx->tree_tab_dev && ctx->tree_tab_host.size() == bytes && memcmp(ctx->tree_tab_host.data(), data, bytes) == 0) return MG_OK;
+    MG_HIP_CHECK(hipStreamSynchronize(ctx->stream));   // no launch in flight reads the table being replaced
+    if (ctx->tree_tab_cap < bytes) {
+        if (ctx->tree_tab_dev) { (void)hipFree(ctx->tree_tab_dev); ctx->tree_tab_dev = nullptr; ctx->tree_tab_cap = 0; }
+        MG_HIP_CHECK(hipMalloc(&ctx->tree_tab_dev, bytes));
+        ctx->tree_tab_cap = bytes;
     }
-    *tree = t;
+    MG_HIP_CHECK(hipMemcpy(ctx->tree_tab_dev, data, bytes, hipMemcpyHostToDevice));
+    ctx->tree_tab_host.assign((const unsigned char *)data, (const unsigned char *)data + bytes);
     return MG_OK;
 }
 
-static int mg_kd_tree_search(int32_t n_searches, mg_primitive *const *prims, mg_cluster_tree *const *trees, const mg_constraint_set *const *csets,
-                             int32_t n_candidates, mg_tree_search_record *records_dev) {
-    mg_context *ctx = prims[0]->ctx;
-    std::vector<mg_kd_search_desc> tab(n_searches);
-    int Lmax = 1, ncmax = 1, maxch = 1, maxdepth = 0, maxkd = 1, kd_depth = 0, wrows = 0;
+// what a call's plan is sized by: the largest of each over its searches
+struct mg_tree_maxima {
+    int L = 1, nc = 1, children = 1, depth = 0, kd_children = 1, kd_depth = 0, wrows = 0;
     bool rows_known = true;
+};
+
+// One launch for the table's searches.  plan(wrows): the kernel's LDS plan with that many rows of W staged; a plan beyond the
+// workgroup's LDS is tried again with W read from memory.
+template <class PlanFn, class Kernel>
+static int mg_tree_launch(mg_context *ctx, const std::vector<mg_tree_search_desc> &tab, const mg_tree_maxima &m, int n_candidates, PlanFn plan, Kernel kernel,
+                          mg_tree_search_record *records_dev) {
+    auto lp = plan(m.rows_known ? m.wrows : 0);
+    if (lp.bytes > MG_TREE_LDS_MAX && lp.s.wrows > 0) lp = plan(0);
+    if (lp.bytes > MG_TREE_LDS_MAX) {
+        mg_set_error("mg_cluster_tree_search: %zu bytes of LDS (latents %d, constraints %d, candidates %d, children %d, depth %d, KD depth %d) beyond 160 KiB",
+                     lp.bytes, m.L, m.nc, n_candidates, m.children, m.depth, m.kd_depth);
+        return MG_ERR_UNSUPPORTED;
+    }
+    MG_HIP_CHECK(hipSetDevice(ctx->device));
+    int rc = mg_tree_table_upload(ctx, tab.size() * sizeof(mg_tree_search_desc), tab.data());
+    if (rc != MG_OK) return rc;
+    if (lp.bytes > 64 * 1024) MG_HIP_CHECK(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, MG_TREE_LDS_MAX));
+    mg_prof_begin(ctx, 11);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)tab.size()), dim3(MG_TREE_THREADS), lp.bytes, ctx->stream, (const mg_tree_search_desc *)ctx->tree_tab_dev, lp,
+                       records_dev);
+    mg_prof_end(ctx, 11);
+    MG_HIP_CHECK(hipGetLastError());
+    return MG_OK;
+}
+
+extern "C" int mg_cluster_tree_search(int32_t n_searches, mg_primitive *const *prims, mg_cluster_tree *const *trees,
+                                      const mg_constraint_set *const *csets, int32_t n_candidates, mg_tree_search_record *records_dev) {
+    MG_TREE_REQUIRE(n_searches >= 0, "mg_cluster_tree_search: n_searches = %d", n_searches);
+    if (n_searches == 0) return MG_OK;
+    MG_TREE_REQUIRE(prims && trees && csets && records_dev, "mg_cluster_tree_search: NULL argument");
+    MG_TREE_REQUIRE(n_candidates >= 1 && n_candidates <= MG_TREE_MAX_CANDIDATES, "mg_cluster_tree_search: n_candidates = %d outside [1, %d]",
+                    n_candidates, MG_TREE_MAX_CANDIDATES);
+    MG_TREE_REQUIRE(prims[0] != nullptr, "mg_cluster_tree_search: primitive 0 is NULL");
+    MG_TREE_REQUIRE(trees[0] != nullptr, "mg_cluster_tree_search: search 0: NULL primitive, tree or constraint set");
+    const int kind = trees[0]->kind;
+    for (int32_t s = 1; s < n_searches; s++)
+        MG_TREE_REQUIRE(trees[s] == nullptr || trees[s]->kind == kind,
+                        "mg_cluster_tree_search: search %d: a %s tree in a call of %s trees (one kind per call)", s,
+                        trees[s]->kind ? "KD" : "feature", kind ? "KD" : "feature");
+    mg_context *ctx = prims[0]->ctx;
+    std::vector<mg_tree_search_desc> tab(n_searches);
+    mg_tree_maxima m;
     for (int32_t s = 0; s < n_searches; s++) {
         mg_primitive *p = prims[s];
         const mg_cluster_tree *t = trees[s];
@@ -927,49 +861,43 @@ static int mg_kd_tree_search(int32_t n_searches, mg_primitive *const *prims, mg_
         MG_TREE_REQUIRE(p->ctx == ctx, "mg_cluster_tree_search: search %d: the primitives live in different contexts", s);
         MG_TREE_REQUIRE(t->ctx == ctx, "mg_cluster_tree_search: search %d: the tree was uploaded to another context", s);
         MG_TREE_REQUIRE(cs->prim == p, "mg_cluster_tree_search: search %d: the constraint set belongs to another primitive", s);
-        MG_TREE_REQUIRE(t->dim >= p->L, "mg_cluster_tree_search: search %d: tree points of width %d < %d spatial components", s, t->dim, p->L);
-        mg_kd_search_desc &d = tab[s];
-        memset(&d, 0, sizeof(d));
-        d.a.W = cs->d_W; d.a.bias = cs->d_bias; d.a.par = cs->d_par; d.a.woff = cs->d_woff; d.a.chain = cs->d_chain; d.a.choff = cs->d_choff;
-        d.a.pose = cs->d_pose; d.a.align = cs->d_align; d.a.align_cand = nullptr; d.a.lat = nullptr; d.a.out = nullptr; d.a.res = nullptr;
-        d.a.B = 0; d.a.ld = 0; d.a.n = cs->n; d.a.nch = cs->nch; d.a.L = p->L;
-        d.points = t->d_points; d.child_begin = t->d_child_begin; d.children = t->d_children; d.leaf = t->d_leaf;
+        MG_TREE_REQUIRE(t->dim >= p->L, "mg_cluster_tree_search: search %d: tree %s of width %d < %d spatial components", s, kind ? "points" : "means",
+                        t->dim, p->L);
+        mg_tree_search_desc &d = tab[s];
+        memset(&d, 0, sizeof(d));   // (the padding too: the table is compared with the last call's)
+        d.a = mg_score_args_of(cs, p->L);
+        d.points = t->d_points; d.child_begin = t->d_child_begin; d.children = t->d_children; d.first = t->d_first; d.leaf = t->d_leaf;
         d.kd_begin = t->d_kd_begin; d.kd_roots = t->d_kd_roots; d.kd_left = t->d_kd_left; d.kd_right = t->d_kd_right; d.kd_inner = t->d_kd_inner;
         d.dim = t->dim; d.rows = cs->rows; d.n_kd = t->n_kd;
-        rows_known = rows_known && cs->rows > 0;
-        wrows = std::max(wrows, (int)cs->rows);
-        Lmax = std::max(Lmax, (int)p->L);
-        ncmax = std::max(ncmax, (int)cs->n);
-        maxch = std::max(maxch, (int)t->max_children);
-        maxdepth = std::max(maxdepth, (int)t->depth);
-        maxkd = std::max(maxkd, (int)t->max_kd_children);
-        kd_depth = std::max(kd_depth, (int)t->kd_depth);
+        m.rows_known = m.rows_known && cs->rows > 0;
+        m.wrows = std::max(m.wrows, (int)cs->rows);
+        m.L = std::max(m.L, (int)p->L);
+        m.nc = std::max(m.nc, (int)cs->n);
+        m.children = std::max(m.children, (int)t->max_children);
+        m.depth = std::max(m.depth, (int)t->depth);
+        m.kd_children = std::max(m.kd_children, (int)t->max_kd_children);
+        m.kd_depth = std::max(m.kd_depth, (int)t->kd_depth);
     }
-    mg_kd_lds_plan lp = mg_kd_plan(Lmax, ncmax, n_candidates, maxch, maxdepth, maxkd, kd_depth, rows_known ? wrows : 0);
-    if (lp.bytes > 160 * 1024 && lp.wrows > 0) lp = mg_kd_plan(Lmax, ncmax, n_candidates, maxch, maxdepth, maxkd, kd_depth, 0);
-    if (lp.bytes > 160 * 1024) {
-        mg_set_error("mg_cluster_tree_search: %zu bytes of LDS (latents %d, constraints %d, candidates %d, children %d, depth %d, KD depth %d) beyond 160 KiB",
-                     lp.bytes, Lmax, ncmax, n_candidates, maxch, maxdepth, kd_depth);
-        return MG_ERR_UNSUPPORTED;
-    }
-    MG_HIP_CHECK(hipSetDevice(ctx->device));
-    const size_t tab_bytes = tab.size() * sizeof(mg_kd_search_desc);
-    if (!ctx->tree_tab_dev || ctx->tree_tab_host.size() != tab_bytes || memcmp(ctx->tree_tab_host.data(), tab.data(), tab_bytes) != 0) {
-        MG_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        if (ctx->tree_tab_cap < tab_bytes) {
-            if (ctx->tree_tab_dev) { (void)hipFree(ctx->tree_tab_dev); ctx->tree_tab_dev = nullptr; ctx->tree_tab_cap = 0; }
-            MG_HIP_CHECK(hipMalloc(&ctx->tree_tab_dev, tab_bytes));
-            ctx->tree_tab_cap = tab_bytes;
-        }
-        MG_HIP_CHECK(hipMemcpy(ctx->tree_tab_dev, tab.data(), tab_bytes, hipMemcpyHostToDevice));
-        ctx->tree_tab_host.assign((const unsigned char *)tab.data(), (const unsigned char *)tab.data() + tab_bytes);
-    }
-    if (lp.bytes > 64 * 1024)
-        MG_HIP_CHECK(hipFuncSetAttribute((const void *)mg_kd_tree_search_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    mg_prof_begin(ctx, 11);
-    hipLaunchKernelGGL(mg_kd_tree_search_kernel, dim3(n_searches), dim3(MG_TREE_CHUNK * MG_TREE_WAVES), lp.bytes, ctx->stream,
-                       (const mg_kd_search_desc *)ctx->tree_tab_dev, lp, records_dev);
-    mg_prof_end(ctx, 11);
-    MG_HIP_CHECK(hipGetLastError());
+    if (kind == 1)
+        return mg_tree_launch(ctx, tab, m, n_candidates,
+                              [&](int w) { return mg_kd_plan(m.L, m.nc, n_candidates, m.children, m.depth, m.kd_children, m.kd_depth, w); },
+                              mg_kd_tree_search_kernel, records_dev);
+    return mg_tree_launch(ctx, tab, m, n_candidates, [&](int w) { return mg_tree_plan(m.L, m.nc, n_candidates, m.children, m.depth, w); },
+                          mg_tree_search_kernel, records_dev);
+}
+
+extern "C" int mg_cluster_tree_search_host(int32_t n_searches, mg_primitive *const *prims, mg_cluster_tree *const *trees,
+                                           const mg_constraint_set *const *csets, int32_t n_candidates, mg_tree_search_record *records) {
+    MG_TREE_REQUIRE(n_searches >= 0 && (n_searches == 0 || (records && prims && prims[0])), "mg_cluster_tree_search_host: bad arguments");
+    if (n_searches == 0) return MG_OK;
+    mg_context *ctx = prims[0]->ctx;
+    const int64_t bytes = (int64_t)n_searches * (int64_t)sizeof(mg_tree_search_record);
+    void *d_rec = nullptr;
+    int rc = mg_ctx_scratch(ctx, bytes, &d_rec);
+    if (rc != MG_OK) return rc;
+    rc = mg_cluster_tree_search(n_searches, prims, trees, csets, n_candidates, (mg_tree_search_record *)d_rec);
+    if (rc != MG_OK) return rc;
+    MG_HIP_CHECK(hipMemcpyAsync(records, d_rec, (size_t)bytes, hipMemcpyDeviceToHost, ctx->stream));
+    MG_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     return MG_OK;
 }

@@ -447,9 +447,8 @@ static int mg_launch_gmm_lds_kk(mg_primitive *p, const void *x, int xdt, int64_t
     if (pairs) lds += (size_t)nw * pair_doubles * 8;
     if (cs) {
         mg_score_args &sa = oa.sa;
-        sa.W = cs->d_W; sa.bias = cs->d_bias; sa.par = cs->d_par; sa.woff = cs->d_woff; sa.chain = cs->d_chain; sa.choff = cs->d_choff;
-        sa.align = cs->d_align; sa.align_cand = nullptr; sa.pose = cs->d_pose; sa.lat = x; sa.out = nullptr; sa.res = nullptr; sa.B = B; sa.ld = ld;
-        sa.n = cs->n; sa.nch = cs->nch; sa.L = p->L;
+        sa = mg_score_args_of(cs, p->L);
+        sa.lat = x; sa.B = B; sa.ld = ld;
         oa.Wpack = cs->d_Wpack; oa.bpad = cs->d_bpad; oa.RT = cs->RT; oa.rows = cs->rows; oa.wave_doubles = wave_doubles;
         oa.pair_doubles = pairs ? pair_doubles : 0;
         oa.error_scale = error_scale; oa.quality_scale = quality_scale; oa.err_out = err_out; oa.obj_out = obj_out;

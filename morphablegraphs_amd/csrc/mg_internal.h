@@ -243,6 +243,34 @@ struct mg_constraint_set {
                                 // its rows (first control point: root xyz, then the chain's quaternions) start at woff[n]
 };
 
+// The scoring statements' argument block (mg_score_device.h)
+struct mg_score_args {
+    const double *W;      // [rows][L]     sum_j w_j E'[(i0+j) D + d]; constraint c owns rows woff[c] ..
+    const double *bias;   // [rows]        mean frame at t_c
+    const double *par;    // [n][8]        type, weight, target[3], ref_dir[3]
+    const int32_t *woff;  // [n + 1]
+    const int32_t *chain; // [n]           FK chain length
+    const double *choff;  // [n][2][MG_MAX_CHAIN][3]
+    const double *pose;   // pose constraints' tables (MG_POSE_HDR / MG_POSE_REC layout) or NULL
+    const double *align;  // [8] or NULL: chain length, previous heading (x,z), previous root (x,z), ref_dir; rows at woff[n]
+    const double *align_cand;   // NULL, or (B, 4): the previous heading (x, z) and root position (x, z) of EVERY candidate, in
+                                // place of align[1..4] (the steps of a graph walk: a candidate's step is aligned to ITS OWN previous step)
+    const void *lat;
+    void *out;            // (B) summed error, or NULL
+    double *res;          // (B, n) weighted residual of every constraint, or NULL
+    int64_t B, ld;
+    int32_t n, nch, L;
+};
+
+// A set's tables, n, nch and the primitive's L; everything else zero: the caller sets lat, out, res, align_cand, B, ld
+inline mg_score_args mg_score_args_of(const mg_constraint_set *cs, int32_t L) {
+    mg_score_args a = {};
+    a.W = cs->d_W; a.bias = cs->d_bias; a.par = cs->d_par; a.woff = cs->d_woff; a.chain = cs->d_chain; a.choff = cs->d_choff;
+    a.pose = cs->d_pose; a.align = cs->d_align;
+    a.n = cs->n; a.nch = cs->nch; a.L = L;
+    return a;
+}
+
 // Device table of one pose constraint inside d_pose (doubles): header, then one record per point
 #define MG_POSE_HDR 8                            // [0] n_points, [1] has_velocity, [2..4] velocity, [5] rows of one pose block
 #define MG_POSE_REC (5 + 4 * MG_MAX_CHAIN)       // target xyz, weight, chain length m, then m x (quaternion row or -1, offset xyz)

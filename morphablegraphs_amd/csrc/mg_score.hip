@@ -203,9 +203,8 @@ static int mg_launch_score_mfma_kk(mg_primitive *p, const mg_constraint_set *cs,
 }
 
 int mg_launch_score(mg_primitive *p, const mg_constraint_set *cs, const void *lat, int ldt, int64_t B, int64_t ld, void *out, int odt, double *res, const double *align_cand) {
-    mg_score_args a;
-    a.res = res; a.align_cand = align_cand;
-    a.W = cs->d_W; a.bias = cs->d_bias; a.par = cs->d_par; a.woff = cs->d_woff; a.chain = cs->d_chain; a.choff = cs->d_choff; a.align = cs->d_align; a.pose = cs->d_pose; a.lat = lat; a.out = out; a.B = B; a.ld = ld; a.n = cs->n; a.nch = cs->nch; a.L = p->L;
+    mg_score_args a = mg_score_args_of(cs, p->L);
+    a.res = res; a.align_cand = align_cand; a.lat = lat; a.out = out; a.B = B; a.ld = ld;
     const bool lf0 = ldt == MG_F64, of0 = odt == MG_F64;
     if (cs->d_Wpack && !p->ctx->opt[MG_OPT_FORCE_VALU_SCORE]) {
         int rc = MG_ERR_UNSUPPORTED;

@@ -1,5 +1,5 @@
-// Device-side pieces of the fused constraint scorer (gfx950): the argument block and the weighted residual of one
-// constraint for one candidate, shared by the stand-alone scoring kernels (mg_score.hip) and the one-launch planner
+// Device-side pieces of the fused constraint scorer (gfx950): the weighted residual of one constraint for one candidate
+// (its argument block, mg_score_args, is in mg_internal.h), shared by the stand-alone scoring kernels (mg_score.hip) and the one-launch planner
 // step (mg_options.hip) so that both produce the same bits.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -8,24 +8,6 @@
 #include <cstdint>
 
 #include "mg_internal.h"
-
-struct mg_score_args {
-    const double *W;      // [rows][L]     sum_j w_j E'[(i0+j) D + d]; constraint c owns rows woff[c] ..
-    const double *bias;   // [rows]        mean frame at t_c
-    const double *par;    // [n][8]        type, weight, target[3], ref_dir[3]
-    const int32_t *woff;  // [n + 1]
-    const int32_t *chain; // [n]           FK chain length
-    const double *choff;  // [n][2][MG_MAX_CHAIN][3]
-    const double *pose;   // pose constraints' tables (MG_POSE_HDR / MG_POSE_REC layout) or NULL
-    const double *align;  // [8] or NULL: chain length, previous heading (x,z), previous root (x,z), ref_dir; rows at woff[n]
-    const double *align_cand;   // NULL, or (B, 4): the previous heading (x, z) and root position (x, z) of EVERY candidate, in
-                                // place of align[1..4] (the steps of a graph walk: a candidate's step is aligned to ITS OWN previous step)
-    const void *lat;
-    void *out;            // (B) summed error, or NULL
-    double *res;          // (B, n) weighted residual of every constraint, or NULL
-    int64_t B, ld;
-    int32_t n, nch, L;
-};
 
 // The weighted residual of constraint c for one candidate; `channel(row)` yields the candidate's pose channel of
 // that row of the fused keyframe matrices (rows of constraint c start at woff[c]).  Shared by the VALU kernel (a dot

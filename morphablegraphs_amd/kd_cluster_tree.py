@@ -28,18 +28,11 @@ import heapq
 import numpy as np
 
 from . import _capi
+from .cluster_tree import _forest, _SearchTree, _TreeNode
 
 MG_TREE_MAX_DEPTH, MG_TREE_MAX_CHILDREN, MG_KD_MAX_DEPTH = _capi.MG_TREE_MAX_DEPTH, _capi.MG_TREE_MAX_CHILDREN, _capi.MG_KD_MAX_DEPTH
 
 _NO_MEAN = "'KDTreeWrapper' object has no attribute 'mean'"
-
-
-class _TreeNode(object):
-    """A ClusterTreeNode in the heaps: no ordering, so tuples that reach it raise TypeError as the reference's do."""
-    __slots__ = ("index",)
-
-    def __init__(self, index):
-        self.index = index
 
 
 class _Point(list):
@@ -50,34 +43,9 @@ class _Point(list):
         self.row, self.leaf = row, leaf
 
 
-def _forest(n, roots, kids, max_depth, what):
-    """Depth of the forest below `roots` (kids(v): v's children); ValueError unless every node has one parent and is reached."""
-    seen = np.zeros(n, dtype=bool)
-    level = [int(r) for r in roots]
-    for r in level:
-        if r < 0 or r >= n or seen[r]:
-            raise ValueError("cluster tree: every %s node needs exactly one parent" % what)
-        seen[r] = True
-    depth = 0
-    while level:
-        nxt = [int(c) for v in level for c in kids(v)]
-        if not nxt:
-            break
-        depth += 1
-        if depth > max_depth:
-            raise ValueError("cluster tree: %s levels deeper than %d, or a cycle" % (what, max_depth))
-        for c in nxt:
-            if c < 0 or c >= n or seen[c]:
-                raise ValueError("cluster tree: every %s node needs exactly one parent" % what)
-            seen[c] = True
-        level = nxt
-    if not seen.all():
-        raise ValueError("cluster tree: %s nodes not reachable from the root (a cycle)" % what)
-    return depth
-
-
-class HipClusterTree(object):
+class HipClusterTree(_SearchTree):
     """A k-means / KD ClusterTree flattened and validated (see the module's docstring for the tables)."""
+    _TIE = "'<' not supported between instances of 'ClusterTreeNode' and 'ClusterTreeNode' (two candidates of equal value and index)"
 
     def __init__(self, data, points, n_kd, child_begin, children, leaf, kd_begin, kd_roots, kd_left, kd_right, kd_inner, n_spatial=None,
                  options=None):
@@ -366,30 +334,13 @@ class HipClusterTree(object):
         return value, (self.means[0].copy() if row < 0 else self.points[row].tolist()), leaf, evaluations
 
     # ---- the device copy --------------------------------------------------------------------------------------
-    def device_tree(self, prim):
-        """The tree on the device of prim's context (_capi.KdClusterTree), uploaded once per context."""
-        key = id(prim.ctx)
-        t = self._device.get(key)
-        if t is not None and t[0] is prim.ctx and t[1].handle and prim.ctx.handle:
-            return t[1]
-        tree = _capi.KdClusterTree(prim, self.points, self.n_kd, self.child_begin, self.children, self.leaf, self.kd_begin, self.kd_roots,
+    def _upload(self, prim):
+        return _capi.KdClusterTree(prim, self.points, self.n_kd, self.child_begin, self.children, self.leaf, self.kd_begin, self.kd_roots,
                                    self.kd_left, self.kd_right, self.kd_inner)
-        self._device[key] = (prim.ctx, tree)
-        return tree
-
-    def close(self):
-        for _, tree in self._device.values():
-            tree.close()
-        self._device = {}
 
     def result_of_record(self, rec):
         """(value, sample list) of a search record, or the reference's exception."""
-        flags = int(rec["flags"])
-        if flags & _capi.MG_TREE_OVERFLOW:
-            raise RuntimeError("cluster-tree search: a heap outgrew its bound")
-        if flags & _capi.MG_TREE_TIE:
-            raise TypeError("'<' not supported between instances of 'ClusterTreeNode' and 'ClusterTreeNode' "
-                            "(two candidates of equal value and index)")
+        flags = self._flags_of_record(rec)
         if flags & _capi.MG_TREE_NO_MEAN:
             raise AttributeError(_NO_MEAN)
         if flags & _capi.MG_TREE_NO_RESULT:

@@ -2,6 +2,7 @@
 (mg_cluster_tree_search), against the reference's own answers (tests/golden/cluster_tree_search.npz) and, bit for bit,
 against the host descent scoring each level with mg_score_constraints; its use by the sampling generator
 ("cluster_tree_search_method": "descend") and by the planner's option evaluation."""
+import heapq
 import json
 import os
 
@@ -264,3 +265,131 @@ def test_misuse_returns_status_codes():
     ctx2.close()
     other_prim.close()
     prim.close()
+
+
+# ---- pins of the level loop's boundaries: hand-made trees on the tiny primitive, the device record against `descend` ----
+_PIN_CONS = [{"type": "position", "t": 11.0, "weight": 1.0, "target": [40.0, None, -25.0]},
+             {"type": "position", "t": 5.5, "weight": 0.5, "target": [10.0, 3.0, 20.0]}]
+
+
+def _flat_tree(counts, means):
+    """A feature tree from its nodes' child counts in breadth-first order (node 0 the root, children numbered consecutively);
+    data = the means, and every leaf's row is its own node."""
+    counts = np.asarray(counts, dtype=np.int64)
+    assert counts.sum() == len(counts) - 1 and means.shape[0] == len(counts)
+    first = np.where(counts == 0, np.arange(len(counts)), -1)
+    first[0] = -1 if counts[0] else 0
+    return HipFeatureClusterTree(means, means, np.concatenate([[0], np.cumsum(counts)]), np.arange(1, len(counts)), first, n_spatial=3)
+
+
+def _distinct_means(seed, n, dim=3):
+    means = np.random.default_rng(seed).standard_normal((n, dim))
+    assert len(np.unique(means, axis=0)) == n
+    return means
+
+
+def _by_score(score, means):
+    """The rows of means, lowest objective first (the objectives all different)."""
+    v = np.asarray(score(means))
+    assert len(set(v.tolist())) == len(v)
+    return means[np.argsort(v)]
+
+
+def _spanning_tree(score, seed=7):
+    """A root with three inner children whose 130 leaves the second level scores as chunks 64 | 64 | 2: in the frontier's order
+    the nodes have 50, 14 and 66 children, so a node's last child falls inside a chunk (slot 49), on a chunk's last slot (63)
+    and on the last slot in use of a short chunk, and the second and third chunk begin inside a node."""
+    means = _distinct_means(seed, 134)
+    heap = []
+    for i, v in enumerate(score(means[1:4])):
+        heapq.heappush(heap, (v, i))
+    counts = [3, 0, 0, 0] + [0] * 130
+    for rank, size in enumerate((50, 14, 66)):
+        counts[1 + heap[rank][1]] = size
+    return _flat_tree(counts, means)
+
+
+def _tie_tree(score, at_pop):
+    """at_pop False: a root with two leaves of one mean (heappush compares them).  True: three leaves a, b, b with a the
+    strictly lowest: nothing compares the two b before the final heappop's _siftdown."""
+    a, b = _by_score(score, _distinct_means(3, 2))
+    means = np.stack([np.zeros(3), a, b, b] if at_pop else [np.zeros(3), a, a])
+    return _flat_tree([len(means) - 1] + [0] * (len(means) - 1), means)
+
+
+def _assert_record_is_descent(tree, prim, cset, n):
+    rec = search_on_device([(tree, prim, cset)], n)[0]
+    value, row, leaf, n_eval = tree.descend(lambda ids: prim.score_constraints(cset, np.ascontiguousarray(tree.means[ids, :prim.n_components])), n)
+    assert rec["flags"] == 0
+    assert (rec["leaf"], rec["row"], rec["evaluations"]) == (leaf, tree.first_index[leaf], n_eval)
+    assert _bits(rec["value"]) == _bits(value)
+    np.testing.assert_array_equal(tree.result_of_record(rec)[1], row)
+    return rec
+
+
+@pytest.fixture(scope="module")
+def tiny():
+    prim = _capi.Primitive(get_context(0), synthetic.make_tiny_primitive(seed=1))
+    cset = _capi.ConstraintSet(prim, _PIN_CONS)
+    yield prim, cset, lambda x: prim.score_constraints(cset, np.ascontiguousarray(x))
+    cset.close()
+    prim.close()
+
+
+@pytest.mark.parametrize("n", [1, 3])
+@pytest.mark.parametrize("children", [64, 65])
+def test_a_level_of_one_chunk_and_of_one_more_child(tiny, children, n):
+    prim, cset, _ = tiny
+    tree = _flat_tree([children] + [0] * children, _distinct_means(children, children + 1))
+    try:
+        assert _assert_record_is_descent(tree, prim, cset, n)["evaluations"] == children
+    finally:
+        tree.close()
+
+
+def test_chunks_that_span_frontier_nodes(tiny):
+    prim, cset, score = tiny
+    tree = _spanning_tree(score)
+    try:
+        assert _assert_record_is_descent(tree, prim, cset, 3)["evaluations"] == 133
+    finally:
+        tree.close()
+
+
+@pytest.mark.parametrize("at_pop", [False, True])
+def test_equal_values_flag_a_tie_at_push_and_at_the_final_pop(tiny, monkeypatch, at_pop):
+    prim, cset, score = tiny
+    tree = _tie_tree(score, at_pop)
+    try:
+        rec = search_on_device([(tree, prim, cset)], 3)[0]
+        assert rec["flags"] & _capi.MG_TREE_TIE
+        with pytest.raises(TypeError):
+            tree.result_of_record(rec)
+        with pytest.raises(TypeError):
+            tree.descend(lambda ids: score(tree.means[ids]), 3)
+        if at_pop:      # heappush alone never compares the two equal entries: only the last line of descend, the heappop, raises
+            pushed, real = [], heapq.heappush
+            monkeypatch.setattr(heapq, "heappush", lambda h, x: (real(h, x), pushed.append(x))[0])
+            with pytest.raises(TypeError):
+                tree.descend(lambda ids: score(tree.means[ids]), 3)
+            monkeypatch.undo()
+            assert len(pushed) == 9     # three pushes each on the node's, the level's and the results' heap: all went through
+    finally:
+        tree.close()
+
+
+def test_w_read_from_memory_beyond_64_latents():
+    data = synthetic.make_primitive(seed=5, n_components=68, n_frames=12, n_basis=7, n_dim=7, n_gmm=2, name="wide")
+    prim = _capi.Primitive(get_context(0), data)
+    cset = _capi.ConstraintSet(prim, _PIN_CONS)
+    counts = [3, 2, 2, 2] + [0] * 6
+    means = _distinct_means(68, len(counts), 68)
+    first = np.where(np.asarray(counts) == 0, np.arange(len(counts)), -1)
+    tree = HipFeatureClusterTree(means, means, np.concatenate([[0], np.cumsum(counts)]), np.arange(1, len(counts)), first, n_spatial=68)
+    try:
+        for n in (1, 2):
+            _assert_record_is_descent(tree, prim, cset, n)
+    finally:
+        tree.close()
+        cset.close()
+        prim.close()

@@ -343,3 +343,155 @@ def test_device_search_matches_the_golden_cases(k, name):
         cset.close()
         tree.close()
         prim.close()
+
+
+# ---- pins of the level loop's and the KD groups' boundaries: hand-made trees on the tiny primitive against `descend_rows` ----
+_PIN_CONS = [{"type": "position", "t": 11.0, "weight": 1.0, "target": [40.0, None, -25.0]},
+             {"type": "position", "t": 5.5, "weight": 0.5, "target": [10.0, 3.0, 20.0]}]
+
+
+def _kd_tree(counts, leaf, means, kd_per_leaf=0, kd_levels=0, seed=0, n_spatial=3):
+    """A ClusterTree from its cluster nodes' child counts and leaf flags in breadth-first order (children numbered
+    consecutively); every leaf owns kd_per_leaf KD trees, each a chain of kd_levels inner nodes with two children (the
+    left one goes on), their points random and all different."""
+    counts, leaf = np.asarray(counts, dtype=np.int64), np.asarray(leaf, dtype=np.int32)
+    assert counts.sum() == len(counts) - 1 and means.shape[0] == len(counts) == len(leaf)
+    per_tree = 1 + 2 * kd_levels
+    n_kd = int(leaf.sum()) * kd_per_leaf * per_tree
+    pts = np.random.default_rng(1000 + seed).standard_normal((n_kd, means.shape[1]))
+    assert len(np.unique(pts, axis=0)) == n_kd
+    left, right, inner = np.full(n_kd, -1), np.full(n_kd, -1), np.zeros(n_kd, dtype=np.int64)
+    roots = np.arange(0, n_kd, per_tree)
+    for r in roots:
+        for lvl in range(kd_levels):     # node r + 2 lvl (r itself, then each left child) is inner
+            k = r if lvl == 0 else r + 2 * lvl - 1
+            left[k], right[k], inner[k] = r + 2 * lvl + 1, r + 2 * lvl + 2, 1
+    kd_begin = np.concatenate([[0], np.cumsum(leaf * kd_per_leaf)])
+    points = np.concatenate([pts, means])
+    return HipClusterTree(points[n_kd:], points, n_kd, np.concatenate([[0], np.cumsum(counts)]), np.arange(1, len(counts)), leaf, kd_begin,
+                          roots, left, right, inner, n_spatial=n_spatial)
+
+
+def _distinct_means(seed, n, dim=3):
+    means = np.random.default_rng(seed).standard_normal((n, dim))
+    assert len(np.unique(means, axis=0)) == n
+    return means
+
+
+def _tie_kd_tree(score, same_idx):
+    """A root with two inner nodes A and B of two leaves each; m scores strictly lowest of m, p, q.  same_idx: A = [m, p],
+    B = [m, q], so the level's heap meets (v, 0, .) twice.  Otherwise A = [p, q], B = [m, m]: it compares (v, 1, .) with
+    (v, 0, .), which the indices decide."""
+    cand = _distinct_means(3, 3)
+    v = np.asarray(score(cand))
+    assert len(set(v.tolist())) == 3
+    m, p, q = cand[np.argsort(v)]
+    kids = [m, p, m, q] if same_idx else [p, q, m, m]
+    means = np.stack([np.zeros(3), np.ones(3), -np.ones(3)] + kids)
+    return _kd_tree([2, 2, 2, 0, 0, 0, 0], [0, 0, 0, 1, 1, 1, 1], means)
+
+
+def _assert_record_is_descent(tree, prim, cset, n):
+    rec = search_on_device([(tree, prim, cset)], n)[0]
+    value, row, leaf, n_eval = _host(tree, prim, cset, n)
+    assert rec["flags"] == 0
+    assert (rec["row"], rec["leaf"], rec["evaluations"]) == (row, leaf, n_eval)
+    assert _bits(rec["value"]) == _bits(value)
+    return rec
+
+
+@pytest.fixture(scope="module")
+def tiny():
+    prim = _capi.Primitive(get_context(0), synthetic.make_tiny_primitive(seed=1))
+    cset = _capi.ConstraintSet(prim, _PIN_CONS)
+    yield prim, cset, lambda x: prim.score_constraints(cset, np.ascontiguousarray(x))
+    cset.close()
+    prim.close()
+
+
+@pytest.mark.parametrize("n", [1, 3])
+@pytest.mark.parametrize("children", [64, 65])
+def test_a_level_of_one_chunk_and_of_one_more_child(tiny, children, n):
+    prim, cset, _ = tiny
+    tree = _kd_tree([children] + [0] * children, [0] + [1] * children, _distinct_means(children, children + 1))
+    try:
+        assert _assert_record_is_descent(tree, prim, cset, n)["evaluations"] == children + n    # then the kept leaves' own means
+    finally:
+        tree.close()
+
+
+@pytest.mark.parametrize("trees,levels", [(32, 0), (33, 0), (33, 2)])
+def test_a_leaf_of_one_group_of_descents_and_of_one_more(tiny, trees, levels):
+    prim, cset, _ = tiny
+    tree = _kd_tree([0], [1], np.zeros((1, 3)), kd_per_leaf=trees, kd_levels=levels, seed=trees + levels)
+    try:
+        assert tree.kd_depth == levels
+        n_eval = _assert_record_is_descent(tree, prim, cset, 2)["evaluations"]
+        assert n_eval == trees if levels == 0 else n_eval >= 3 * trees     # every root is inner: each descent, the 33rd too, steps
+    finally:
+        tree.close()
+
+
+@pytest.mark.parametrize("same_idx", [True, False])
+def test_equal_values_tie_only_with_equal_indices(tiny, same_idx):
+    prim, cset, score = tiny
+    tree = _tie_kd_tree(score, same_idx)
+    try:
+        if same_idx:
+            rec = search_on_device([(tree, prim, cset)], 2)[0]
+            assert rec["flags"] & _capi.MG_TREE_TIE
+            with pytest.raises(TypeError):
+                tree.result_of_record(rec)
+            with pytest.raises(TypeError):
+                _host(tree, prim, cset, 2)
+        else:
+            rec = _assert_record_is_descent(tree, prim, cset, 2)
+            assert rec["leaf"] in (5, 6) and rec["evaluations"] == 2 + 4 + 2
+    finally:
+        tree.close()
+
+
+def test_w_read_from_memory_beyond_64_latents():
+    data = synthetic.make_primitive(seed=5, n_components=68, n_frames=12, n_basis=7, n_dim=7, n_gmm=2, name="wide")
+    prim = _capi.Primitive(get_context(0), data)
+    cset = _capi.ConstraintSet(prim, _PIN_CONS)
+    tree = _kd_tree([3, 0, 0, 0], [0, 1, 1, 1], _distinct_means(68, 4, 68), kd_per_leaf=2, kd_levels=1, seed=68, n_spatial=68)
+    try:
+        for n in (1, 2):
+            _assert_record_is_descent(tree, prim, cset, n)
+    finally:
+        tree.close()
+        cset.close()
+        prim.close()
+
+
+def test_one_descriptor_table_serves_both_kinds(tiny):
+    """A feature call, a KD call, the feature call again (the table is rewritten) and once more (the cached table): the records
+    of fresh single calls, and four launches."""
+    prim, cset, _ = tiny
+    ctx = prim.ctx
+    means = _distinct_means(21, 8)
+    feat = HipFeatureClusterTree(means, means, [0, 3, 5, 7, 7, 7, 7, 7, 7], np.arange(1, 8), [-1, -1, -1, 3, 4, 5, 6, 7], n_spatial=3)
+    kd = _kd_tree([2, 0, 0], [0, 1, 1], _distinct_means(22, 3), kd_per_leaf=2, kd_levels=1, seed=22)
+    fresh = []
+    for t in (feat, kd):      # each in a context of its own, whose first search it is
+        other = _capi.Context(0)
+        other_prim = _capi.Primitive(other, synthetic.make_tiny_primitive(seed=1))
+        other_set = _capi.ConstraintSet(other_prim, _PIN_CONS)
+        fresh.append(search_on_device([(t, other_prim, other_set)], 2))
+        t.close()
+        other_set.close()
+        other_prim.close()
+        other.close()
+    ctx.profile_enable(True)
+    ctx.profile_reset()
+    try:
+        got = [search_on_device([(t, prim, cset)], 2) for t in (feat, kd, feat, feat)]
+        assert ctx.profile_get("cluster_tree_search")[1] == 4
+    finally:
+        ctx.profile_enable(False)
+        feat.close()
+        kd.close()
+    for k, rec in zip((0, 1, 0, 0), got):
+        np.testing.assert_array_equal(rec.view(np.uint8), fresh[k].view(np.uint8))
+        assert rec["flags"][0] == 0

@@ -931,6 +931,35 @@ int mg_warp_motions(mg_context *ctx, const double *frames_dev, const int64_t *of
 int mg_dtw_pair_costs(mg_context *ctx, const double *clouds_dev, const int64_t *offsets, int64_t n_motions, int32_t n_joints,
                       const double *weights, const int64_t *ref_indices, int64_t n_refs, double *costs_dev);
 
+/* ---- spatial alignment and the per-frame preparation in front of the fPCA (reference construction/motion_model_constructor.py
+ * _align_frames_spatially, :244-263, and :359-360; construction/utils.py rotate_frames, normalize_root_translation,
+ * align_quaternion_frames), float64, synchronising, bit-reproducible.  A frame is (x, y, z) of the root, then J quaternions
+ * (w, x, y, z), the root's first.  Statement for statement: csrc/mg_spatial_align.hip. ---- */
+/* out_dev (offsets[n_motions], n_dim) = every motion of frames_dev (ragged as above, no 1024-frame limit) turned about y so that the
+ * heading of its frame frame_idx -- x and z of its normalised root quaternion applied to (0, 0, 1), normalised -- is
+ * ref_orientation[2] (HOST, normalised by the call), and moved so that the turned root position of that frame is (0, 0, 0),
+ * height included.  The rotation is (cos, sin) = (h . r, h x r) of the two unit vectors, never an angle: (x, z) -> (cos x - sin z,
+ * sin x + cos z).  Root quaternions come back normalised with w >= 0; every other channel is copied.  transforms_dev: NULL, or
+ * (n_motions, 5) for each motion's (cos, sin, dx, dy, dz), d the turned root position of frame frame_idx.  out_dev must not be
+ * frames_dev.  MG_ERR_UNSUPPORTED unless n_dim = 3 + 4 J with 1 <= J <= 64, answered before anything else;
+ * MG_ERR_INVALID_ARGUMENT for offsets that do not start at 0 or do not rise, a frame_idx outside any motion, a ref_orientation
+ * of length 0, and -- found by check kernels, before the kernel proper is launched, so that nothing is written -- non-finite
+ * frames, a zero root quaternion, and a frame frame_idx whose root turns z onto the y axis (no heading; the text names the first
+ * such motion).  n_motions = 0 is MG_OK and does nothing.  PARITY UNPINNED for the heading and the angle between headings (the
+ * reference's pose_orientation_quat and get_rotation_angle are anim_utils'). */
+int mg_align_motions_spatially(mg_context *ctx, const double *frames_dev, const int64_t *offsets, int64_t n_motions, int32_t n_dim,
+                               int64_t frame_idx, const double *ref_orientation, double *out_dev, double *transforms_dev);
+
+/* out_dev (n_motions, n_frames, n_dim) = frames_dev with the root positions divided by scale_vec[3] (HOST, out) = the largest |x|,
+ * |y|, |z| over all frames -- unless one of the three is 0: then nothing is scaled and scale_vec is ones
+ * (normalize_root_translation) -- and every quaternion of the first n_joints joints whose dot product with the same joint's
+ * quaternion in frame 0 of motion 0 (w, x, y, z added in that order) is < 0 negated (align_quaternion_frames).  Channels from
+ * 3 + 4 n_joints on are copied.  Bit for bit the two reference functions wherever no dot product lies within rounding of 0.
+ * out_dev must not be frames_dev.  MG_ERR_INVALID_ARGUMENT for 3 + 4 n_joints > n_dim, n_frames < 1 and non-finite frames
+ * (check kernel; nothing is written); n_motions = 0 is MG_OK with scale_vec = ones. */
+int mg_prepare_aligned_frames(mg_context *ctx, const double *frames_dev, int64_t n_motions, int32_t n_frames, int32_t n_dim,
+                              int32_t n_joints, double *out_dev, double *scale_vec);
+
 /* ---- segmentation: cutting clips out of captures at keyframe poses (reference construction/keyframe_detection.py:79-135 argmin,
  * argmin_multi, KeyframeDetector.find_instance / find_instances / calculate_distances; construction/segmentation.py:34-81
  * Segmentation.extract_single_segments / extract_segments), float64, synchronising, bit-reproducible.  Captures are ragged like the

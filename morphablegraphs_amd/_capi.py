@@ -86,6 +86,7 @@ EXPORTED_SYMBOLS = [
     "mg_spline_fit_batch", "mg_pca_fit", "mg_pca_project", "mg_pca_backproject",
     "mg_dtw_distance_grids", "mg_dtw_paths", "mg_warp_motions", "mg_dtw_pair_costs",
     "mg_keyframe_distances", "mg_segment_search",
+    "mg_align_motions_spatially", "mg_prepare_aligned_frames",
 ]
 
 
@@ -362,6 +363,8 @@ def load_library(path=None):
         "mg_dtw_pair_costs": [vp, vp, vp, i64, i32, vp, vp, i64, vp],
         "mg_keyframe_distances": [vp, vp, vp, i64, i32, vp, i32, vp, vp],
         "mg_segment_search": [vp, vp, vp, vp, i64, i32, dbl, i32, vp, vp, vp],
+        "mg_align_motions_spatially": [vp, vp, vp, i64, i32, i64, vp, vp, vp],
+        "mg_prepare_aligned_frames": [vp, vp, i64, i32, i32, i32, vp, vp],
     }
     for name, argtypes in sigs.items():
         fn = getattr(lib, name)
@@ -1119,6 +1122,30 @@ def segment_search(ctx, start_dist_dev, end_dist_dev, offsets, mode, threshold, 
         raise ValueError("%d segment offsets for %d offsets" % (len(seg_off), len(off)))
     _check(ctx.lib.mg_segment_search(ctx.handle, _dev_ptr(start_dist_dev), _dev_ptr(end_dist_dev), _host_ptr(off), len(off) - 1, int(mode),
                                      float(threshold), int(min_segment_size), _host_ptr(seg_off), _dev_ptr(segments_dev), _dev_ptr(counts_dev)))
+
+
+MG_SPATIAL_ALIGN_MAX_JOINTS, MG_SPATIAL_ALIGN_FRAMES_PER_WORKGROUP = 64, 32   # mg_spatial_align.hip
+
+
+def align_motions_spatially(ctx, frames_dev, offsets, n_dim, frame_idx, ref_orientation, out_dev, transforms_dev=None):
+    """mg_align_motions_spatially: out_dev (offsets[-1], n_dim) <- every motion of the ragged table frames_dev turned about y and
+    moved so that its frame frame_idx faces ref_orientation (two host numbers) at the origin; transforms_dev: None, or
+    (n_motions, 5) for each motion's (cos, sin, dx, dy, dz)."""
+    off = _offsets_arg(offsets)
+    r = np.ascontiguousarray(ref_orientation, dtype=np.float64).reshape(-1)
+    if len(r) != 2:
+        raise ValueError("ref_orientation has two entries (x, z)")
+    _check(ctx.lib.mg_align_motions_spatially(ctx.handle, _dev_ptr(frames_dev), _host_ptr(off), len(off) - 1, int(n_dim), int(frame_idx), _host_ptr(r),
+                                              _dev_ptr(out_dev), None if transforms_dev is None else _dev_ptr(transforms_dev)))
+
+
+def prepare_aligned_frames(ctx, frames_dev, n_motions, n_frames, n_dim, n_joints, out_dev):
+    """mg_prepare_aligned_frames: out_dev (n_motions, n_frames, n_dim) <- frames_dev with the root positions divided by their largest
+    magnitudes and the first n_joints quaternions flipped into the hemisphere of frame 0 of motion 0.  Returns scale_vec (3,)."""
+    scale = np.ones(3)
+    _check(ctx.lib.mg_prepare_aligned_frames(ctx.handle, _dev_ptr(frames_dev), int(n_motions), int(n_frames), int(n_dim), int(n_joints), _dev_ptr(out_dev),
+                                             _host_ptr(scale)))
+    return scale
 
 
 class TrackPlan(object):

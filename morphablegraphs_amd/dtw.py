@@ -331,6 +331,30 @@ def find_optimal_dtw(point_clouds, mean_key, weights=None, ctx=None):
     return {k: _as_path(r["path"]) for k, r in zip(keys, results)}
 
 
+def _align_section_dev(ctx, bufs, skeleton, idx, f_dev, off, n_dim, ref_index):
+    """The device-input form of _align_section: f_dev the ragged table (off[-1], n_dim) of the motions' frames, ref_index the
+    reference motion's position (None: the FIRST least mean cost of mg_dtw_pair_costs over the same clouds).  Forward
+    kinematics, grids, paths and the warp without leaving the device; returns (the warped frames (n, fr, n_dim), a device
+    buffer of the scope `bufs`, the warping functions (n, fr) int32 on the host, ref_index)."""
+    total, n, nj = int(off[-1]), len(off) - 1, len(idx)
+    with ctx.buffers() as tmp:
+        c_dev = tmp.malloc(8 * total * nj * 3)
+        ctx.joint_positions_dev(skeleton, idx, f_dev, total, n_dim, c_dev)
+        if ref_index is None:
+            p_dev = tmp.malloc(8 * n * n)
+            _capi.dtw_pair_costs(ctx, c_dev, off, nj, None, None, p_dev)
+            ref_index = reference_from_costs(ctx.download(p_dev, (n, n), np.float64), range(n))[0]
+        fr = int(off[ref_index + 1] - off[ref_index])
+        ref_dev = c_dev.address + 8 * int(off[ref_index]) * nj * 3      # the reference motion's clouds, where they lie
+        s_dev = tmp.malloc(8 * fr * total)
+        _capi.dtw_distance_grids(ctx, ref_dev, fr, c_dev, off, nj, None, s_dev)
+        _, w_dev = _paths_on_device(ctx, tmp, s_dev, fr, off, False)
+        o_dev = bufs.malloc(8 * n * fr * n_dim)
+        _capi.warp_motions(ctx, f_dev, off, n_dim, w_dev, fr, o_dev)
+        warps = ctx.download(w_dev, (n, fr), np.int32)
+    return o_dev, warps, ref_index
+
+
 def _align_section(ctx, skeleton, joints, motions, mean_key):
     keys = list(motions.keys())
     frames = [np.asarray(motions[k], dtype=np.float64) for k in keys]
@@ -341,18 +365,9 @@ def _align_section(ctx, skeleton, joints, motions, mean_key):
     fr = len(motions[mean_key])
     _check_limits(fr, [len(f) for f in frames], len(idx))
     off = _offsets([len(f) for f in frames])
-    total, n, nj = int(off[-1]), len(keys), len(idx)
     with ctx.buffers() as bufs:
-        f_dev, c_dev = bufs.upload(np.concatenate(frames)), bufs.malloc(8 * total * nj * 3)
-        ctx.joint_positions_dev(skeleton, idx, f_dev, total, n_dim, c_dev)
-        ref_dev = c_dev.address + 8 * int(off[keys.index(mean_key)]) * nj * 3      # the reference motion's clouds, where they lie
-        s_dev = bufs.malloc(8 * fr * total)
-        _capi.dtw_distance_grids(ctx, ref_dev, fr, c_dev, off, nj, None, s_dev)
-        _, w_dev = _paths_on_device(ctx, bufs, s_dev, fr, off, False)
-        o_dev = bufs.malloc(8 * n * fr * n_dim)
-        _capi.warp_motions(ctx, f_dev, off, n_dim, w_dev, fr, o_dev)
-        warped = ctx.download(o_dev, (n, fr, n_dim), np.float64)
-        warps = ctx.download(w_dev, (n, fr), np.int32)
+        o_dev, warps, _ = _align_section_dev(ctx, bufs, skeleton, idx, bufs.upload(np.concatenate(frames)), off, n_dim, keys.index(mean_key))
+        warped = ctx.download(o_dev, (len(keys), fr, n_dim), np.float64)
     return (collections.OrderedDict((k, warped[m]) for m, k in enumerate(keys)),
             collections.OrderedDict((k, [int(v) for v in warps[m]]) for m, k in enumerate(keys)))
 

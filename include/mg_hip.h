@@ -329,7 +329,8 @@ int mg_memset(mg_context *ctx, void *dst_dev, int value, int64_t bytes);
  * slot: 0 = back_project_frames, 1 = gmm_log_prob, 2 = score_constraints, 3 = argmin,
  *       4 = gmm_sample, 5 = spline_evaluate, 6 = fused step, 7 = a planner step in one launch (mg_options_step),
  *       8 = mg_joint_tracks, 9 = mg_score_frame_constraints, 10 = mg_score_trajectory[_points],
- *       11 = mg_cluster_tree_search (both tree kinds: mg_tree_search_kernel or mg_kd_tree_search_kernel). */
+ *       11 = mg_cluster_tree_search (both tree kinds: mg_tree_search_kernel or mg_kd_tree_search_kernel),
+ *       12 = the frames kernel of mg_walk_frames. */
 int mg_profile_enable(mg_context *ctx, int enabled);
 int mg_profile_reset(mg_context *ctx);
 int mg_profile_get(mg_context *ctx, int slot, double *total_ms, int64_t *launches);
@@ -409,6 +410,10 @@ int mg_time_function_canonical_host(mg_primitive *prim, const void *gamma, int g
  * batch; lengths NULL: every row has t_cap samples.  Device pointers. */
 int mg_time_function_sample(mg_primitive *prim, const void *gamma, int dtype, int64_t n, int64_t ld, double speed, double *times, int32_t *lengths,
                             int32_t t_cap, double *canonical_out);
+/* The same with the rows of `times` row_pitch >= t_cap doubles apart (mg_time_function_sample: row_pitch = t_cap), so that a batch's
+ * rows can land inside a wider table, such as mg_walk_frames' (n_walks, n_steps, t_cap); a row still holds at most t_cap samples. */
+int mg_time_function_sample_rows(mg_primitive *prim, const void *gamma, int dtype, int64_t n, int64_t ld, double speed, double *times, int32_t *lengths,
+                                 int32_t t_cap, int64_t row_pitch, double *canonical_out);
 int mg_back_project_frames_at(mg_primitive *prim, const void *latents, int dtype, int64_t n, int64_t ld, const double *times, const int32_t *lengths,
                               int32_t t_cap, void *out, int out_dtype);
 
@@ -1000,7 +1005,43 @@ int mg_segment_search(mg_context *ctx, const double *start_dist_dev, const doubl
                       int64_t n_motions, int32_t mode, double threshold, int32_t min_segment_size, const int64_t *segment_offsets,
                       int32_t *segments_dev, int32_t *counts_dev);
 
+/* ---- a graph walk's motion -------------------------------------------------------------------------------
+ * GraphWalk.convert_graph_walk_to_quaternion_frames for a population of walks (reference motion_generator/graph_walk.py:154-176: per
+ * step back_project(parameters).get_motion_vector(), then MotionVector.append_frames, which aligns the step to the last frame so far
+ * and appends it; smoothing is off during synthesis, :102): the frames of n_walks walks over the SAME node sequence, written once where
+ * they end up, in two launches (csrc/mg_walk.hip).
+ *   prims[n_steps]           one primitive per step, all of one context and one n_dim (a primitive may repeat)
+ *   latents_dev              (n_walks, ld) float32 / float64; step i reads columns latent_offset[i] .. + its n_components
+ *   times_dev, lengths       NULL, NULL: every step on its primitive's canonical grid linspace(0, F, F); or times_dev (n_walks, n_steps,
+ *                            t_cap) float64 on the device with lengths (n_walks, n_steps): rows as mg_time_function_sample leaves them
+ *   frame_offset             (n_walks, n_steps): the first output row of every step inside its walk (NULL with canonical grids: back to back)
+ *   alignment                of the FIRST step: NULL (it stays as it is), a previous-frame record, or a start-pose record.  Every later
+ *                            step is aligned to the ALIGNED last sample of the step before it (the last entry of its time row) through
+ *                            the record's joint and ref_dir -- the root and (0, 0, 1) without a previous-frame record.  skeleton: needed
+ *                            only when that joint is not the root
+ *   frames_dev               (n_walks, walk_stride, n_dim) float64; rows no step owns are not written
+ *   transforms_dev           NULL or (n_walks, n_steps, 4) float64 = (c, s, tx, tz) of every step; (1, 0, 0, 0) for an unaligned one
+ * latent_offset, lengths and frame_offset are HOST tables: the call checks them before any launch (a length < 1 or > t_cap, steps that
+ * overlap or pass walk_stride, primitives of two contexts or widths, a non-root aligning joint without a skeleton:
+ * MG_ERR_INVALID_ARGUMENT) and carries them to the device itself.
+ * Arithmetic: a step's unaligned frames are mg_back_project_frames_f64's (canonical grid) or mg_back_project_frames_at's (given times), bit
+ * for bit; its transform is the one mg_align_frames applies -- h the heading it is aligned to, b its own in its first control point:
+ * c = h.b, s = h x b, a position becomes (c x + s z + tx, y, -s x + c z + tz), the root quaternion is multiplied from the left by the
+ * rotation about y, a start pose raises the heights of the first step by position[1].  A walk's frames do not depend on the batch.
+ * At most MG_WALK_MAX_STEPS steps per call: a longer walk is assembled in pieces, the last frame of one piece giving the previous-frame
+ * record of the next (graph_walk.py in the Python package does).  Profile slot 12 times mg_walk_frames_kernel. */
+#define MG_WALK_MAX_STEPS 64
+int mg_walk_frames(int32_t n_steps, mg_primitive *const *prims, const int64_t *latent_offset, const void *latents_dev, int latent_dtype,
+                   int64_t n_walks, int64_t ld, const double *times_dev, const int32_t *lengths, int32_t t_cap, const int64_t *frame_offset,
+                   const mg_alignment_desc *alignment, const mg_skeleton_desc *skeleton, double *frames_dev, int64_t walk_stride,
+                   double *transforms_dev);
+
 /* ---- host-pointer convenience variants (H2D, launch, D2H, synchronise) ---------------- */
+/* mg_walk_frames with latents, times, frames and transforms in host memory; `frames` is read first, so rows no step owns keep their values */
+int mg_walk_frames_host(int32_t n_steps, mg_primitive *const *prims, const int64_t *latent_offset, const void *latents, int latent_dtype,
+                        int64_t n_walks, int64_t ld, const double *times, const int32_t *lengths, int32_t t_cap, const int64_t *frame_offset,
+                        const mg_alignment_desc *alignment, const mg_skeleton_desc *skeleton, double *frames, int64_t walk_stride,
+                        double *transforms);
 int mg_back_project_frames_host(mg_primitive *prim, const mg_time_grid *grid, const void *latents,
                                 int latent_dtype, int64_t n_samples, int64_t ld, float *frames, int path);
 int mg_back_project_frames_f64_host(mg_primitive *prim, const mg_time_grid *grid, const void *latents,

@@ -39,12 +39,14 @@ MG_CONSTRAINT_JOINT_MIDPOINT, MG_CONSTRAINT_JOINT_ORIENTATION, MG_CONSTRAINT_LOO
 MG_CONSTRAINT_VALUE_POSITION, MG_CONSTRAINT_VALUE_HEADING = 7, 8   # values of the aligned motion, not errors (chained graph-walk steps)
 PROFILE_SLOTS = {"frames": 0, "gmm_log_prob": 1, "score_constraints": 2, "argmin": 3,
                  "gmm_sample": 4, "spline_evaluate": 5, "step": 6, "options_step": 7, "joint_tracks": 8, "frame_constraints": 9, "trajectory": 10,
-                 "cluster_tree_search": 11}
+                 "cluster_tree_search": 11, "walk_frames": 12}
 MG_TREE_MAX_DEPTH, MG_TREE_MAX_CHILDREN, MG_TREE_MAX_CANDIDATES = 64, 256, 64    # include/mg_hip.h
 MG_TREE_TIE, MG_TREE_NO_RESULT, MG_TREE_OVERFLOW, MG_TREE_NO_MEAN = 1, 2, 4, 8
 MG_KD_MAX_DEPTH = 64
 # struct mg_tree_search_record
 TREE_SEARCH_RECORD = np.dtype([("row", "<i8"), ("leaf", "<i4"), ("flags", "<i4"), ("evaluations", "<i8"), ("value", "<f8")])
+MG_WALK_MAX_STEPS = 64           # steps of one mg_walk_frames call (include/mg_hip.h)
+MG_WALK_TILE = 32                # frames per workgroup of mg_walk_frames_kernel (csrc/mg_walk.hip)
 MG_FUSED_MAX_OPTIONS = 24        # options of one mg_options_step_device_counts launch (csrc/mg_options.hip)
 
 
@@ -68,7 +70,7 @@ EXPORTED_SYMBOLS = [
     "mg_context_device_info", "mg_device_malloc", "mg_device_malloc_chunked", "mg_device_malloc_placed", "mg_device_probe_placement", "mg_device_placement_info", "mg_device_free", "mg_context_trim_outputs", "mg_context_output_bytes", "mg_memcpy_h2d", "mg_memcpy_d2h",
     "mg_memset", "mg_profile_enable", "mg_profile_reset", "mg_profile_get", "mg_profile_get_samples",
     "mg_primitive_create", "mg_primitive_destroy", "mg_primitive_info", "mg_primitive_info2", "mg_primitive_root_mode", "mg_primitive_get_precisions_cholesky",
-    "mg_time_function_canonical", "mg_time_function_canonical_host", "mg_time_function_sample", "mg_back_project_frames_at",
+    "mg_time_function_canonical", "mg_time_function_canonical_host", "mg_time_function_sample", "mg_time_function_sample_rows", "mg_back_project_frames_at",
     "mg_trajectory_create", "mg_trajectory_destroy", "mg_score_trajectory", "mg_score_trajectories", "mg_score_trajectory_points", "mg_trajectory_closest_points", "mg_joint_positions",
     "mg_time_grid_create", "mg_time_grid_destroy", "mg_primitive_canonical_grid", "mg_time_grid_size",
     "mg_time_grid_get_tables",
@@ -87,6 +89,7 @@ EXPORTED_SYMBOLS = [
     "mg_dtw_distance_grids", "mg_dtw_paths", "mg_warp_motions", "mg_dtw_pair_costs",
     "mg_keyframe_distances", "mg_segment_search",
     "mg_align_motions_spatially", "mg_prepare_aligned_frames",
+    "mg_walk_frames", "mg_walk_frames_host",
 ]
 
 
@@ -337,6 +340,7 @@ def load_library(path=None):
         "mg_dist_broadcast": [vp, vp, i64, i32],
         "mg_objective_error_and_naturalness": [vp, vp, vp, i32, i64, i64, dbl, dbl, vp, vp, vp],
         "mg_time_function_sample": [vp, vp, i32, i64, i64, dbl, vp, vp, i32, vp],
+        "mg_time_function_sample_rows": [vp, vp, i32, i64, i64, dbl, vp, vp, i32, i64, vp],
         "mg_back_project_frames_at": [vp, vp, i32, i64, i64, vp, vp, i32, vp, i32],
         "mg_track_plan_create": [vp, vp, i32, vp, vp, i32, C.POINTER(vp)],
         "mg_joint_tracks": [vp, vp, i32, i64, i64, vp, vp, vp],
@@ -365,6 +369,8 @@ def load_library(path=None):
         "mg_segment_search": [vp, vp, vp, vp, i64, i32, dbl, i32, vp, vp, vp],
         "mg_align_motions_spatially": [vp, vp, vp, i64, i32, i64, vp, vp, vp],
         "mg_prepare_aligned_frames": [vp, vp, i64, i32, i32, i32, vp, vp],
+        "mg_walk_frames": [i32, vp, vp, vp, i32, i64, i64, vp, vp, i32, vp, vp, vp, vp, i64, vp],
+        "mg_walk_frames_host": [i32, vp, vp, vp, i32, i64, i64, vp, vp, i32, vp, vp, vp, vp, i64, vp],
     }
     for name, argtypes in sigs.items():
         fn = getattr(lib, name)

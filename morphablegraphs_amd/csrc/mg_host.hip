@@ -161,6 +161,7 @@ extern "C" void mg_context_destroy(mg_context *ctx) {
     if (ctx->traj_paths) (void)hipFree(ctx->traj_paths);
     if (ctx->lists_dev) (void)hipFree(ctx->lists_dev);
     if (ctx->tree_tab_dev) (void)hipFree(ctx->tree_tab_dev);
+    if (ctx->walk_tab_dev) (void)hipFree(ctx->walk_tab_dev);
     for (auto &b : ctx->arena) (void)hipFree(b.base);
     for (auto &v : ctx->vmm) mg_vmm_release(ctx, v);
     (void)hipDeviceSynchronize();   // nothing of this process is in flight when the parked address ranges go back to the runtime
@@ -1317,17 +1318,23 @@ extern "C" int mg_time_function_canonical(mg_primitive *p, const void *gamma, in
 
 // back_project_time_function for a batch (reference motion_primitive.py:268-319): the spline's time function t'(t) of every
 // candidate -- 0, the inverse of its canonical time function at linspace(1, t(F-2), num), F - 1 -- padded to t_cap per row.
-extern "C" int mg_time_function_sample(mg_primitive *p, const void *gamma, int gdt, int64_t B, int64_t ld, double speed, double *times, int32_t *lengths,
-                                       int32_t t_cap, double *canonical_out) {
+extern "C" int mg_time_function_sample_rows(mg_primitive *p, const void *gamma, int gdt, int64_t B, int64_t ld, double speed, double *times, int32_t *lengths,
+                                            int32_t t_cap, int64_t row_pitch, double *canonical_out) {
     MG_REQUIRE(p != nullptr, "mg_time_function_sample: primitive is NULL");
     MG_REQUIRE(p->Lt > 0, "mg_time_function_sample: the primitive has no time model");
     MG_REQUIRE(B >= 0 && B < ((int64_t)1 << 31) && (gdt == MG_F32 || gdt == MG_F64) && ld >= p->Lt, "mg_time_function_sample: bad arguments (ld %lld, n_time_components %d)",
                (long long)ld, p->Lt);
     MG_REQUIRE(speed > 0.0 && std::isfinite(speed) && t_cap >= 2, "mg_time_function_sample: speed must be positive and finite, t_cap >= 2");
+    MG_REQUIRE(row_pitch >= t_cap, "mg_time_function_sample: a row pitch of %lld doubles is shorter than t_cap %d", (long long)row_pitch, t_cap);
     if (B == 0) return MG_OK;
     MG_REQUIRE(gamma && times && lengths, "mg_time_function_sample: NULL pointer");
     { int rc0 = mg_use_device(p->ctx); if (rc0 != MG_OK) return rc0; }
-    return mg_launch_timewarp(p, gamma, gdt, B, ld, speed, times, lengths, t_cap, canonical_out);
+    return mg_launch_timewarp(p, gamma, gdt, B, ld, speed, times, lengths, t_cap, row_pitch, canonical_out);
+}
+
+extern "C" int mg_time_function_sample(mg_primitive *p, const void *gamma, int gdt, int64_t B, int64_t ld, double speed, double *times, int32_t *lengths,
+                                       int32_t t_cap, double *canonical_out) {
+    return mg_time_function_sample_rows(p, gamma, gdt, B, ld, speed, times, lengths, t_cap, t_cap, canonical_out);
 }
 
 // MotionSpline.get_motion_vector of every candidate at ITS OWN time function (reference motion_spline.py:71-86 behind

@@ -13,7 +13,7 @@
 #define MG_ROWTILE 16       // coefficient rows per MFMA tile (M)
 #define MG_MAX_KK 16        // k-steps of 4 -> n_components <= 64 on the MFMA path
 #define MG_BLOCK 256        // threads per workgroup of the frames kernels
-#define MG_PROFILE_SLOTS 12
+#define MG_PROFILE_SLOTS 13
 
 void mg_set_error(const char *fmt, ...);
 int mg_hip_fail(hipError_t e, const char *what);
@@ -84,7 +84,8 @@ struct mg_context {
     // ... two slots of them: the step's kernel also draws the counts the NEXT step will want if its seeds are this step's + 1 (a planner
     // counts its steps), so that step needs no counts kernel in front; what was drawn for whom:
     struct { bool valid = false; int32_t n_options = 0, slot = 0; int64_t n = 0; uint64_t seeds[24] = {0}; const void *prims[24] = {nullptr}; } fused_next;
-    unsigned attr_gmm_lds = 0, attr_traj = 0;   // dynamic-LDS attributes already set for this context's device (bit per instantiation)
+    unsigned attr_gmm_lds = 0, attr_traj = 0;   // dynamic-LDS attributes already set for this context's device (bit per instantiation;
+                                                // attr_traj: 1 trajectory, 2 time warp, 4 joint tracks, 8 frame constraints, 16 graph walk)
     unsigned long long fused_seq = 0;   // sequence number of the planner steps whose records the kernel leaves in pinned memory
     int fused_partials_n = 0;
     // the output arena (mg_placement.hip): buffers that went through the placement probe, sub-allocated in 2 MiB granules
@@ -111,6 +112,9 @@ struct mg_context {
     void *tree_tab_dev = nullptr;   // mg_cluster_tree_search: the per-search descriptors on the device and their host copy
     size_t tree_tab_cap = 0;        // (rewritten only when a call's table differs from the last one's)
     std::vector<unsigned char> tree_tab_host;
+    void *walk_tab_dev = nullptr;   // mg_walk_frames: the call's step table, offsets and lengths (rewritten only when they differ from the last
+    size_t walk_tab_cap = 0;        // call's) and, behind them, the steps' transforms between its two launches
+    std::vector<unsigned char> walk_tab_host;
 };
 void mg_dev_free(mg_context *ctx, void *p);   // hipFree unless p lives in the context's arena
 
@@ -304,7 +308,7 @@ int mg_launch_argmin_gather(mg_context *ctx, const void *v, int dt, int64_t n, v
 int mg_launch_gmm_jac(mg_primitive *p, const void *x, int xdt, int64_t B, int64_t ld, double *out);
 int mg_launch_time_function(mg_primitive *p, const void *gamma, int gdt, int64_t B, int64_t ld, double *out);
 int mg_launch_timewarp(mg_primitive *p, const void *gamma, int gdt, int64_t B, int64_t ld, double speed, double *times, int32_t *lens, int32_t t_cap,
-                       double *canonical_out);   // mg_timewarp.hip
+                       int64_t row_pitch, double *canonical_out);   // mg_timewarp.hip
 int mg_launch_frames_at(mg_primitive *p, const void *lat, int ldt, int64_t B, int64_t ld, const double *times, const int32_t *lens, int32_t t_cap,
                         void *out, int odt);
 int mg_launch_argmin(mg_context *ctx, const void *v, int dt, int64_t n, void *out_dev);

@@ -19,6 +19,7 @@
 //                             by the FITPACK recurrence, the 4 taps -- the frames of a candidate at its own times, what
 //                             mg_back_project_frames_f64 gives with a time grid per candidate, without a grid per candidate.
 #include "mg_internal.h"
+#include "mg_spline_device.h"
 
 #define MG_TW_BLOCK 64
 #define MG_TW_MAX_F 2048   // canonical frames the inversion holds in LDS (5 arrays of doubles)
@@ -26,7 +27,7 @@
 __global__ __launch_bounds__(MG_TW_BLOCK) void mg_timewarp_kernel(const double *__restrict__ tphi, const double *__restrict__ tmean,
                                                                   const void *__restrict__ gamma, int gamma_f64, int64_t ld, int F, int Lt,
                                                                   double inv_speed, double *__restrict__ times, int32_t *__restrict__ lens,
-                                                                  int32_t t_cap, double *__restrict__ canonical_out) {
+                                                                  int32_t t_cap, int64_t row_pitch, double *__restrict__ canonical_out) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     double *x = (double *)smem;      // [F] the canonical time function t(t'): the spline's abscissae; ordinates are 0 .. F-1
     double *M = x + F;               // [F] second derivatives
@@ -103,7 +104,7 @@ __global__ __launch_bounds__(MG_TW_BLOCK) void mg_timewarp_kernel(const double *
     const int T = num + 2;
     if (tid == 0) lens[b] = T <= t_cap ? T : -T;   // (negative: the caller's rows are too short; nothing else is written)
     if (T > t_cap) return;
-    double *tb = times + b * (int64_t)t_cap;
+    double *tb = times + b * row_pitch;   // (a row holds t_cap samples; row_pitch >= t_cap doubles lie between two rows' starts)
     const double step = num > 1 ? (stop - 1.0) / (double)(num - 1) : 0.0;
     for (int j = tid; j < T; j += MG_TW_BLOCK) {
         double v;
@@ -124,27 +125,6 @@ __global__ __launch_bounds__(MG_TW_BLOCK) void mg_timewarp_kernel(const double *
         }
         tb[j] = v;
     }
-}
-
-// FITPACK fpbspl at x on the span l found like splev does (ext = 0): the host's mg_basis_row, statement for statement
-__device__ __forceinline__ void mg_basis_row_dev(const double *t, int n, double x, int *i0, double *h) {
-    const int k = 3;
-    int l = k;
-    while (!(x < t[l + 1] || l == n - k - 2)) l++;
-    double hh[4];
-    h[0] = 1.0; h[1] = h[2] = h[3] = 0.0;
-    for (int j = 1; j <= k; j++) {
-        for (int i = 0; i < j; i++) hh[i] = h[i];
-        h[0] = 0.0;
-        for (int i = 1; i <= j; i++) {
-            const int li = l + i, lj = li - j;
-            if (t[li] == t[lj]) { h[i] = 0.0; continue; }
-            const double f = hh[i - 1] / (t[li] - t[lj]);
-            h[i - 1] = h[i - 1] + f * (t[li] - x);
-            h[i] = f * (x - t[lj]);
-        }
-    }
-    *i0 = l - k;
 }
 
 #define MG_FA_BLOCK 256
@@ -189,7 +169,7 @@ __global__ __launch_bounds__(MG_FA_BLOCK) void mg_frames_at_kernel(const double 
 }
 
 int mg_launch_timewarp(mg_primitive *p, const void *gamma, int gdt, int64_t B, int64_t ld, double speed, double *times, int32_t *lens, int32_t t_cap,
-                       double *canonical_out) {
+                       int64_t row_pitch, double *canonical_out) {
     const size_t lds = (size_t)4 * p->F * 8;
     if (p->F < 4 || p->F > MG_TW_MAX_F) { mg_set_error("mg_time_function_sample: %d canonical frames (4 .. %d supported)", p->F, MG_TW_MAX_F); return MG_ERR_UNSUPPORTED; }
     if (!(p->ctx->attr_traj & 2u)) {
@@ -201,7 +181,7 @@ int mg_launch_timewarp(mg_primitive *p, const void *gamma, int gdt, int64_t B, i
         p->ctx->attr_traj |= 2u;
     }
     hipLaunchKernelGGL(mg_timewarp_kernel, dim3((unsigned)B), dim3(MG_TW_BLOCK), lds, p->ctx->stream, (const double *)p->d_tphi, (const double *)p->d_tmean, gamma,
-                       gdt == MG_F64 ? 1 : 0, ld, (int)p->F, (int)p->Lt, 1.0 / speed, times, lens, t_cap, canonical_out);
+                       gdt == MG_F64 ? 1 : 0, ld, (int)p->F, (int)p->Lt, 1.0 / speed, times, lens, t_cap, row_pitch, canonical_out);
     MG_HIP_CHECK(hipGetLastError());
     return MG_OK;
 }

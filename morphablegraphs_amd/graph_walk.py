@@ -48,6 +48,14 @@ def _basis_rows(knots, times):
     return i0, w
 
 
+def _untimed_grid(n_canonical_frames, speed=1.0):
+    """The time function of a step without a time model (motion_primitive.py:233): linspace(0, F, int(F * (1 / speed)))."""
+    count = int(n_canonical_frames * (1.0 / float(speed)))
+    if count < 1:
+        raise ValueError("a step of %d canonical frames has no sample at speed %g" % (n_canonical_frames, speed))
+    return np.linspace(0, n_canonical_frames, count)
+
+
 class _HostModel(object):
     """The spatial model of a primitive as NumPy arrays, from the reference's JSON dict or a HipMotionPrimitive."""
 
@@ -72,11 +80,11 @@ class _HostModel(object):
         self.eigen, self.mean = eig * scale[:, None], mean * scale       # scaled once, as the library holds them
         self.n_components = self.eigen.shape[1]
 
-    def frames(self, alpha, times=None):
-        """(control points (NB, D), frames (T, D)) of one latent vector at `times` (None: the canonical grid)."""
+    def frames(self, alpha, times=None, speed=1.0):
+        """(control points (NB, D), frames (T, D)) of one latent vector at `times` (None: the canonical grid at `speed`)."""
         cp = (self.mean + self.eigen @ np.asarray(alpha, dtype=np.float64)).reshape(self.n_basis, self.n_dim)
         if times is None:
-            times = np.linspace(0, self.n_canonical_frames, self.n_canonical_frames)
+            times = _untimed_grid(self.n_canonical_frames, speed)
         i0, w = _basis_rows(self.knots, times)
         out = w[:, 0:1] * cp[i0]
         for j in range(1, 4):
@@ -151,10 +159,11 @@ def _latent_offsets(models, latent_offset):
     return [int(v) for v in np.concatenate(([0], np.cumsum([m.n_components for m in models])[:-1]))]
 
 
-def assemble_walk_host(models, S, latent_offset=None, times=None, alignment=None, skeleton=None):
+def assemble_walk_host(models, S, latent_offset=None, times=None, alignment=None, skeleton=None, speed=1.0):
     """The frames of walks over `models` (one per step: JSON dicts or primitives), NumPy only -- the statement of
     mg_walk_frames' arithmetic.  S (n_walks, ld); step i reads columns latent_offset[i] .. (default: back to back);
-    times: None (canonical grids) or times[w][i] = the step's time row; alignment: None, a previous-frame record
+    times: None (canonical grids) or times[w][i] = the step's time row, None for a step without a time model: its canonical
+    grid at `speed`, linspace(0, F, int(F * (1 / speed))), as back_project takes it (motion_primitive.py:233); alignment: None, a previous-frame record
     (Skeleton.alignment_to) or a start-pose record (alignment_from_start_pose), for the FIRST step; every later step is aligned
     to the aligned last sample of the step before it.  Returns (frames (n_walks, T, D) padded with NaN, offsets
     (n_walks, n_steps + 1), transforms (n_walks, n_steps, 4) = (c, s, tx, tz))."""
@@ -167,7 +176,7 @@ def assemble_walk_host(models, S, latent_offset=None, times=None, alignment=None
     for w in range(n):
         target, parts = _first_target(alignment), []
         for i, model in enumerate(models):
-            cp, fr = model.frames(S[w, offs[i]:offs[i] + model.n_components], None if times is None else times[w][i])
+            cp, fr = model.frames(S[w, offs[i]:offs[i] + model.n_components], None if times is None else times[w][i], speed)
             if target is None:
                 transforms[w, i] = (1.0, 0.0, 0.0, 0.0)
             else:
@@ -235,22 +244,22 @@ def _sample_times(ctx, bufs, mps, d_G, G, goffs, speed):
     """The time rows of every (walk, step) on the device: d_times (n_walks, n_steps, t_cap), lengths (n_walks, n_steps) on the host.
     One mg_time_function_sample_rows per step with a time model, its rows n_steps * t_cap doubles apart so that they land in place
     (a row that needs more than t_cap samples is not written and reports how many: the table is laid out again); the lengths of all
-    steps come back in one download; steps without a time model get their canonical grid.  With smooth_time_parameters the rows
-    pass through the host."""
+    steps come back in one download; steps without a time model get their canonical grid at `speed`.  With smooth_time_parameters
+    the rows pass through the host."""
     n, m = G.shape[0], len(mps)
     has_time = [mp.has_time_parameters and mp.get_n_time_components() > 0 for mp in mps]
     timed = [i for i, ht in enumerate(has_time) if ht]
-    t_cap = max([int(4 * mp.n_canonical_frames / min(float(speed), 1.0)) + 8 if ht else mp.n_canonical_frames for mp, ht in zip(mps, has_time)])
+    grids = [None if ht else _untimed_grid(mp.n_canonical_frames, speed) for mp, ht in zip(mps, has_time)]
+    t_cap = max([int(4 * mp.n_canonical_frames / min(float(speed), 1.0)) + 8 if ht else len(g) for mp, ht, g in zip(mps, has_time, grids)])
     smooth = any(ht and mp.smooth_time_parameters for mp, ht in zip(mps, has_time))
     item = G.dtype.itemsize
     while True:
         lengths = np.zeros((n, m), dtype=np.int32)
         if len(timed) < m:
             host = np.zeros((n, m, t_cap))
-            for i, (mp, ht) in enumerate(zip(mps, has_time)):
-                if not ht:
-                    F = mp.n_canonical_frames
-                    host[:, i, :F], lengths[:, i] = np.linspace(0, F, F), F
+            for i, g in enumerate(grids):
+                if g is not None:
+                    host[:, i, :len(g)], lengths[:, i] = g, len(g)
             d_t = bufs.upload(host)
         else:
             d_t = bufs.malloc(8 * n * m * t_cap)
@@ -278,17 +287,25 @@ def _sample_times(ctx, bufs, mps, d_G, G, goffs, speed):
     return d_t, lengths, t_cap
 
 
-def _assemble_piece(ctx, bufs, mps, S, offs, d_frames, row0, walk_stride, alignment, skeleton, G=None, goffs=None, speed=1.0, d_transforms=None):
+def _piece_times(ctx, bufs, mps, n, G=None, goffs=None, speed=1.0):
+    """(d_times, lengths int32, t_cap, rows the longest walk needs) of one piece: what _assemble_piece takes as `timing`, known
+    before the frame rows are sized.  G None: the canonical grids, (None, None, 0, their sum)."""
+    if G is None:
+        return None, None, 0, sum(mp.n_canonical_frames for mp in mps)
+    d_t, ln, t_cap = _sample_times(ctx, bufs, mps, bufs.upload(G), G, goffs, speed)
+    return d_t, ln, t_cap, int(ln.astype(np.int64).sum(axis=1).max()) if n else 0
+
+
+def _assemble_piece(ctx, bufs, mps, S, offs, d_frames, row0, walk_stride, alignment, skeleton, timing, d_transforms=None):
     """One mg_walk_frames call for at most MG_WALK_MAX_STEPS steps: the frames land in d_frames from row `row0` of every walk on.
-    Returns the offsets (n_walks, n_steps + 1) relative to row0."""
+    timing: the piece's _piece_times.  Returns the offsets (n_walks, n_steps + 1) relative to row0."""
     n, m = S.shape[0], len(mps)
     d_S = bufs.upload(S)
     prims = [mp._prim for mp in mps]
-    if G is None:
+    d_t, ln, t_cap, _ = timing
+    if ln is None:
         lengths = np.tile(np.array([mp.n_canonical_frames for mp in mps], dtype=np.int64), (n, 1))
-        d_t, ln, t_cap = None, None, 0
     else:
-        d_t, ln, t_cap = _sample_times(ctx, bufs, mps, bufs.upload(G), G, goffs, speed)
         lengths = ln.astype(np.int64)
     offsets = np.zeros((n, m + 1), dtype=np.int64)
     offsets[:, 1:] = np.cumsum(lengths, axis=1)
@@ -296,12 +313,13 @@ def _assemble_piece(ctx, bufs, mps, S, offs, d_frames, row0, walk_stride, alignm
         raise ValueError("the walk needs %d rows, %d are left" % (int(offsets[:, -1].max()), walk_stride - row0))
     D = prims[0].n_dim
     walk_frames_dev(prims, offs, d_S, S.dtype, n, S.shape[1], _address(d_frames) + 8 * row0 * D, walk_stride, d_t, ln, t_cap,
-                    offsets[:, :-1] if G is not None else None, alignment, skeleton, d_transforms)
+                    offsets[:, :-1] if ln is not None else None, alignment, skeleton, d_transforms)
     return offsets
 
 
 def _walk_rows(mps, time_parameters, speed):
-    """An upper bound of a walk's rows before its lengths are known."""
+    """The rows a walk usually stays within, before its lengths are known (a step without a time model has int(F / speed) <=
+    4 F / min(speed, 1) + 8 of them; a time function may ask for more: the rows then follow the lengths)."""
     if time_parameters is None:
         return sum(mp.n_canonical_frames for mp in mps)
     return sum(int(4 * mp.n_canonical_frames / min(float(speed), 1.0)) + 8 for mp in mps)
@@ -322,12 +340,20 @@ def assemble_walks(graph, node_keys, S, time_parameters=None, alignment=None, sk
         raise ValueError("latent rows are shorter than the walk's steps need")
     ctx = ctx or mps[0]._prim.ctx
     D = mps[0]._prim.n_dim
-    rows = _walk_rows(mps, G, speed)
+    pieces = [(a, min(a + MG_WALK_MAX_STEPS, m)) for a in range(0, m, MG_WALK_MAX_STEPS)]
     with ctx.buffers() as bufs:
+        # the time functions first: the frame rows are sized by the lengths they give (beyond MG_WALK_MAX_STEPS steps the time tables
+        # of all n_walks x pieces stay on the device until the call ends: n_walks x n_steps x t_cap doubles, a fraction of the frames)
+        if m <= MG_WALK_MAX_STEPS:
+            timing = _piece_times(ctx, bufs, mps, n, G, goffs[:-1], speed)
+            rows = max(timing[3], 1)
+        else:
+            timing = [[_piece_times(ctx, bufs, mps[a:b], 1, None if G is None else G[w:w + 1], goffs[a:b], speed) for a, b in pieces] for w in range(n)]
+            rows = max([sum(t[3] for t in tw) for tw in timing] + [1])
         d_f = bufs.malloc(8 * max(n, 1) * rows * D)
         d_x = bufs.malloc(8 * max(n, 1) * m * 4) if with_transforms else None
         if m <= MG_WALK_MAX_STEPS:
-            offsets = _assemble_piece(ctx, bufs, mps, S, offs[:-1], d_f, 0, rows, alignment, skeleton, G, goffs[:-1], speed, d_x)
+            offsets = _assemble_piece(ctx, bufs, mps, S, offs[:-1], d_f, 0, rows, alignment, skeleton, timing, d_x)
         else:
             # a longer walk in pieces: the last frame of one piece gives the previous-frame record of the next, walk by walk
             joint, ref_dir = _record_node(alignment)
@@ -335,17 +361,16 @@ def assemble_walks(graph, node_keys, S, time_parameters=None, alignment=None, sk
             offsets = np.zeros((n, m + 1), dtype=np.int64)
             for w in range(n):
                 al, row0 = alignment, 0
-                for a in range(0, m, MG_WALK_MAX_STEPS):
-                    b = min(a + MG_WALK_MAX_STEPS, m)
+                for (a, b), tm in zip(pieces, timing[w]):
                     d_w = d_f.address + 8 * w * rows * D
                     d_xw = d_x.address + 8 * (w * m + a) * 4 if d_x is not None else None
                     po = _assemble_piece(ctx, bufs, mps[a:b], S[w:w + 1], offs[a:b], d_w, row0, rows, al, skeleton if (al is alignment or joint != 0) else None,
-                                         None if G is None else G[w:w + 1], goffs[a:b], speed, d_xw)
+                                         tm, d_xw)
                     offsets[w, a + 1:b + 1] = row0 + po[0, 1:]
                     row0 = int(offsets[w, b])
                     last = ctx.download(d_f.address + 8 * ((w * rows + row0 - 1) * D), (D,), np.float64)
                     al = sk.alignment_to(last, joint, ref_dir)
-        # only the rows the walks own come back (with time parameters `rows` is a bound several times the lengths); NaN behind a walk's end
+        # only the rows the walks own come back; NaN behind a walk's end
         T = int(offsets[:, -1].max()) if n else 0
         if T == rows:
             frames = ctx.download(d_f, (n, T, D), np.float64)
@@ -525,12 +550,14 @@ class HipGraphWalk(object):
                 if warped:
                     times = [[mp.back_project_time_function(G[0, goffs[a + i]:goffs[a + i + 1]], step_size)
                               if mp.has_time_parameters and mp.get_n_time_components() > 0 else None for i, mp in enumerate(mps[a:b])]]
-                fr, po, _ = assemble_walk_host(mps[a:b], S, offs[a:b], times, al, self._record_skeleton(al))
+                fr, po, _ = assemble_walk_host(mps[a:b], S, offs[a:b], times, al, self._record_skeleton(al), step_size if warped else 1.0)
+                store.reserve(row0 + fr.shape[1], D, row0)       # (a time function may ask for more rows than _walk_rows assumed)
                 store.write(row0, fr[0])
             else:
                 with self._ctx.buffers() as bufs:
-                    po = _assemble_piece(self._ctx, bufs, mps[a:b], S, offs[a:b], store.address(), row0, store.capacity, al, self._record_skeleton(al), G,
-                                         goffs[a:b], step_size)
+                    timing = _piece_times(self._ctx, bufs, mps[a:b], 1, G, goffs[a:b], step_size)
+                    store.reserve(row0 + timing[3], D, row0)     # (a time function may ask for more rows than _walk_rows assumed)
+                    po = _assemble_piece(self._ctx, bufs, mps[a:b], S, offs[a:b], store.address(), row0, store.capacity, al, self._record_skeleton(al), timing)
                     self._ctx.synchronize()
             for st, lo, hi in zip(steps[a:b], po[0, :-1], po[0, 1:]):
                 st.start_frame, st.end_frame = int(row0 + lo), int(row0 + hi - 1)

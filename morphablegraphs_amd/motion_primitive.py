@@ -163,6 +163,8 @@ class HipMotionPrimitive(object):
         inverse = splrep(t_of_tprime, np.arange(F), k=3)
         last = t_of_tprime[-2]
         n_inner = int(np.round(last) * (1.0 / speed))      # the product, as the reference forms it (x * (1 / speed) and x / speed can differ in the last bit)
+        if n_inner <= 0:                                   # np.linspace(1, last, 0) is empty (splev refuses an empty input): the two pinned ends, as the device gives
+            return np.array([0.0, F - 1.0])
         inner = splev(np.linspace(1.0, last, n_inner), inverse)
         # the reference pins both ends: sample time 0 maps to canonical 0, the last one to the last canonical frame
         return np.concatenate(([0.0], inner, [F - 1.0]))

@@ -1036,7 +1036,43 @@ int mg_walk_frames(int32_t n_steps, mg_primitive *const *prims, const int64_t *l
                    const mg_alignment_desc *alignment, const mg_skeleton_desc *skeleton, double *frames_dev, int64_t walk_stride,
                    double *transforms_dev);
 
+/* The objective of a whole graph walk in ONE launch (csrc/mg_walk_score.hip): what n_steps calls of mg_score_constraint_residuals
+ * [_chained] give when each step's four exit values (MG_CONSTRAINT_VALUE_HEADING x, z; MG_CONSTRAINT_VALUE_POSITION x, z at the step's
+ * exit time) are the next step's per-candidate alignment (obj_global_error_sum and its residual-vector forms, reference
+ * optimization/objective_functions.py:290-380), bit for bit: the same residual statements on the same k-ordered chains, the state
+ * handed on as unrounded float64 -- in the wave's LDS instead of through the host.
+ *   steps[n_steps]           HOST table, one record per step (a primitive may repeat, with the same or other sets)
+ *   latents_dev              (n_samples, ld) float32 / float64; step i reads columns latent_offset .. + its primitive's n_components
+ *   residuals_dev            NULL or (n_samples, ld_res) float64; step i's own residuals go to columns column_offset .. + n_own, columns
+ *                            no step owns are not written
+ *   errors_dev               NULL or (n_samples): per step, in step order, the step's own residuals added in constraint order; the
+ *                            step sums added in step order
+ *   exit_state_dev           NULL or (n_samples, 4): the LAST step's exit values
+ * Step 0 uses the alignment its sets were created with (a previous-frame record, a start-pose record, none).  In every later step a
+ * set with an alignment must carry a previous-frame record: it supplies the node, the chain and ref_dir, its values are replaced per
+ * candidate by the exit values of that candidate's previous step; a set without one is scored unaligned (a local step).
+ * Checked before any launch, MG_ERR_INVALID_ARGUMENT: n_steps outside 1 .. MG_WALK_MAX_STEPS, primitives of two contexts, a set of
+ * another primitive, a later step whose exit-carrying set has no previous-frame alignment, n_own inconsistent with the sets, own
+ * column ranges that overlap or pass ld_res, latent_offset + n_components > ld.  MG_ERR_UNSUPPORTED where a step's tables do not fit
+ * LDS (the per-step calls remain).  Apart from the step table (kept on the device, rewritten only when it differs from the last
+ * call's) the call allocates nothing and does not synchronise.  A candidate's values do not depend on the batch. */
+typedef struct {
+    mg_primitive *prim;
+    const mg_constraint_set *scored; /* constraints whose residuals are the step's own columns; NULL = none.  May END with the four
+                                        exit values */
+    const mg_constraint_set *exit;   /* NULL when `scored` ends with the four exit values, else a set of exactly those four (a local
+                                        step: scored unaligned, exits aligned) */
+    int64_t latent_offset;           /* first column of the step's latents in a row */
+    int32_t n_own;                   /* columns of `scored` that are the step's own (its n, minus 4 if it carries the exits) */
+    int64_t column_offset;           /* where they go in a residual row */
+} mg_walk_score_step;
+int mg_score_walk_residuals(int32_t n_steps, const mg_walk_score_step *steps, const void *latents_dev, int latent_dtype, int64_t n_samples,
+                            int64_t ld, double *residuals_dev, int64_t ld_res, double *errors_dev, double *exit_state_dev);
+
 /* ---- host-pointer convenience variants (H2D, launch, D2H, synchronise) ---------------- */
+/* mg_score_walk_residuals with host arrays; `residuals` is read first, so columns no step owns keep their values */
+int mg_score_walk_residuals_host(int32_t n_steps, const mg_walk_score_step *steps, const void *latents, int latent_dtype, int64_t n_samples,
+                                 int64_t ld, double *residuals, int64_t ld_res, double *errors, double *exit_state);
 /* mg_walk_frames with latents, times, frames and transforms in host memory; `frames` is read first, so rows no step owns keep their values */
 int mg_walk_frames_host(int32_t n_steps, mg_primitive *const *prims, const int64_t *latent_offset, const void *latents, int latent_dtype,
                         int64_t n_walks, int64_t ld, const double *times, const int32_t *lengths, int32_t t_cap, const int64_t *frame_offset,

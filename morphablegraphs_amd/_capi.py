@@ -90,6 +90,7 @@ EXPORTED_SYMBOLS = [
     "mg_keyframe_distances", "mg_segment_search",
     "mg_align_motions_spatially", "mg_prepare_aligned_frames",
     "mg_walk_frames", "mg_walk_frames_host",
+    "mg_score_walk_residuals", "mg_score_walk_residuals_host",
 ]
 
 
@@ -371,6 +372,8 @@ def load_library(path=None):
         "mg_prepare_aligned_frames": [vp, vp, i64, i32, i32, i32, vp, vp],
         "mg_walk_frames": [i32, vp, vp, vp, i32, i64, i64, vp, vp, i32, vp, vp, vp, vp, i64, vp],
         "mg_walk_frames_host": [i32, vp, vp, vp, i32, i64, i64, vp, vp, i32, vp, vp, vp, vp, i64, vp],
+        "mg_score_walk_residuals": [i32, vp, vp, i32, i64, i64, vp, i64, vp, vp],
+        "mg_score_walk_residuals_host": [i32, vp, vp, i32, i64, i64, vp, i64, vp, vp],
     }
     for name, argtypes in sigs.items():
         fn = getattr(lib, name)
@@ -893,6 +896,51 @@ class Trajectory(object):
             self.close()
         except Exception:
             pass
+
+
+class WalkScoreStep(C.Structure):   # struct mg_walk_score_step
+    _fields_ = [("prim", C.c_void_p), ("scored", C.c_void_p), ("exit", C.c_void_p), ("latent_offset", C.c_int64), ("n_own", C.c_int32),
+                ("column_offset", C.c_int64)]
+
+
+class WalkScoreTable(object):
+    """The step table of mg_score_walk_residuals: one (primitive, scored set or None, exit set or None, latent offset, own
+    columns, column offset) per step.  Holds the primitives and sets, so none of them is collected while the table is in use."""
+
+    def __init__(self, steps):
+        if not steps:
+            raise ValueError("a walk has at least one step")
+        self.steps = list(steps)
+        self.n_steps = len(self.steps)
+        self.lib, self.ctx = self.steps[0][0].lib, self.steps[0][0].ctx
+        self.array = (WalkScoreStep * self.n_steps)()
+        for rec, (prim, scored, exit_set, latent_offset, n_own, column_offset) in zip(self.array, self.steps):
+            rec.prim = prim.handle.value
+            rec.scored = scored.handle.value if scored is not None else None
+            rec.exit = exit_set.handle.value if exit_set is not None else None
+            rec.latent_offset, rec.n_own, rec.column_offset = int(latent_offset), int(n_own), int(column_offset)
+
+    def sets(self):
+        return [cs for st in self.steps for cs in st[1:3] if cs is not None]
+
+    def score_dev(self, lat_dev, lat_dtype, n, ld, residuals_dev=None, ld_res=0, errors_dev=None, exit_state_dev=None):
+        """mg_score_walk_residuals on device buffers: asynchronous on the context's stream."""
+        code = MG_F64 if np.dtype(lat_dtype) == np.float64 else MG_F32
+        ptr = lambda b: _dev_ptr(b) if b is not None else None
+        _check(self.lib.mg_score_walk_residuals(self.n_steps, C.cast(self.array, C.c_void_p), ptr(lat_dev), code, int(n), int(ld), ptr(residuals_dev),
+                                                int(ld_res), ptr(errors_dev), ptr(exit_state_dev)))
+
+    def score(self, S, ld_res, residuals=True, errors=True, exit_state=True, fill=0.0):
+        """(residuals (n, ld_res) or None, errors (n) or None, exit state (n, 4) or None) for host latents S
+        (mg_score_walk_residuals_host); columns no step owns hold `fill`."""
+        S = _latents(S)
+        n = S.shape[0]
+        res = np.full((n, int(ld_res)), fill, dtype=np.float64) if residuals else None
+        err = np.empty(n, dtype=np.float64) if errors else None
+        ex = np.empty((n, 4), dtype=np.float64) if exit_state else None
+        _check(self.lib.mg_score_walk_residuals_host(self.n_steps, C.cast(self.array, C.c_void_p), S.ctypes.data_as(C.c_void_p), _dtype_code(S), n,
+                                                     S.shape[1], _host_ptr(res), int(ld_res), _host_ptr(err), _host_ptr(ex)))
+        return res, err, ex
 
 
 def _i32(a):

@@ -85,7 +85,7 @@ struct mg_context {
     // counts its steps), so that step needs no counts kernel in front; what was drawn for whom:
     struct { bool valid = false; int32_t n_options = 0, slot = 0; int64_t n = 0; uint64_t seeds[24] = {0}; const void *prims[24] = {nullptr}; } fused_next;
     unsigned attr_gmm_lds = 0, attr_traj = 0;   // dynamic-LDS attributes already set for this context's device (bit per instantiation;
-                                                // attr_traj: 1 trajectory, 2 time warp, 4 joint tracks, 8 frame constraints, 16 graph walk)
+                                                // attr_traj: 1 trajectory, 2 time warp, 4 joint tracks, 8 frame constraints, 16 graph walk, 32 walk objective)
     unsigned long long fused_seq = 0;   // sequence number of the planner steps whose records the kernel leaves in pinned memory
     int fused_partials_n = 0;
     // the output arena (mg_placement.hip): buffers that went through the placement probe, sub-allocated in 2 MiB granules
@@ -115,6 +115,9 @@ struct mg_context {
     void *walk_tab_dev = nullptr;   // mg_walk_frames: the call's step table, offsets and lengths (rewritten only when they differ from the last
     size_t walk_tab_cap = 0;        // call's) and, behind them, the steps' transforms between its two launches
     std::vector<unsigned char> walk_tab_host;
+    void *wscore_tab_dev = nullptr; // mg_score_walk_residuals: the call's step table (rewritten only when it differs from the last call's)
+    size_t wscore_tab_cap = 0;
+    std::vector<unsigned char> wscore_tab_host;
 };
 void mg_dev_free(mg_context *ctx, void *p);   // hipFree unless p lives in the context's arena
 

@@ -312,6 +312,260 @@ def obj_global_residual_vector_and_naturalness(s, data):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# The same objectives with the whole walk in ONE launch (mg_score_walk_residuals, csrc/mg_walk_score.hip): a wave keeps its 16
+# candidates for all steps and hands the four exit values on in its LDS, where _global_blocks makes a launch, three copies and
+# a synchronisation per step.  The residuals are the chain's, bit for bit.
+# ---------------------------------------------------------------------------------------------------------------------
+def _exit_constraints(t_exit, joint, ref_dir):
+    return [{"type": "value_heading", "t": t_exit, "weight": 1.0, "axis": 0, "joint": joint, "ref_dir": ref_dir},
+            {"type": "value_heading", "t": t_exit, "weight": 1.0, "axis": 2, "joint": joint, "ref_dir": ref_dir},
+            {"type": "value_position", "t": t_exit, "weight": 1.0, "axis": 0},
+            {"type": "value_position", "t": t_exit, "weight": 1.0, "axis": 2}]
+
+
+class HipGraphWalkObjective(object):
+    """The chained objective of graph_walk_steps over motion_primitive_graph, its device sets built once.  Per call: one upload
+    of S (n, sum L_i), one launch, one download.  The sets are the ones _global_blocks asks for (the same `keyframes + exits`
+    lists, the same local-step split, the same first-step record), so blocks(S) equals _global_blocks(S, ...)[2].
+
+    Raises NotImplementedError where _global_blocks does, ValueError for more than MG_WALK_MAX_STEPS steps; a call raises
+    _capi.MGError(-4) where a step's tables do not fit LDS (the callers then take the chain)."""
+
+    def __init__(self, motion_primitive_graph, graph_walk_steps, prev_frames=None, exit_from="frames"):
+        self.graph, self.steps, self.prev_frames, self.exit_from = motion_primitive_graph, list(graph_walk_steps), prev_frames, exit_from
+        if not 1 <= len(self.steps) <= _capi.MG_WALK_MAX_STEPS:
+            raise ValueError("%d steps: 1 .. %d per launch" % (len(self.steps), _capi.MG_WALK_MAX_STEPS))
+        self._private, self._shared, self._buf, self._cap = [], [], None, 0
+        self.n_launches = 0
+        self._build()
+
+    def _set(self, prim, clist, sk, alignment, taken):
+        """cached_constraint_set, unless the shared set of this structure already serves another step of this walk with other
+        values (one launch reads all steps' sets at once): then a set of the objective's own."""
+        from .candidate_scoring import _structure_key, _values_key
+        key, values = _structure_key(prim, clist, sk, alignment), _values_key(clist, alignment)
+        if taken.setdefault(key, values) != values:
+            cs = _capi.ConstraintSet(prim, clist, sk, alignment)
+            self._private.append(cs)
+            return cs
+        cs = cached_constraint_set(prim, clist, sk, alignment)
+        self._shared.append((cs, values))
+        return cs
+
+    def _build(self):
+        graph = self.graph
+        hip_sk = getattr(graph, "hip_skeleton", None)
+        node_name, ref_dir = _aligning_node(graph)
+        if node_name is not None and hip_sk is None:
+            raise NotImplementedError("aligning node %r is not the root joint: the graph needs a _capi.Skeleton as .hip_skeleton" % (node_name,))
+        joint = 0 if node_name is None else node_name
+        for cs in self._private:
+            cs.close()
+        self._private, self._shared = [], []
+        taken, records, self._info = {}, [], []
+        offset = column = 0
+        for i, step in enumerate(self.steps):
+            prim = _prim_of(graph.nodes[step.node_key])
+            Li = int(step.n_spatial_components)
+            cons = step.motion_primitive_constraints
+            keyframes, trajectories = split_trajectories(constraints_to_device_form(_constraint_list(cons)))
+            if trajectories:
+                raise NotImplementedError("trajectory constraints inside a chained graph-walk objective")
+            sk = getattr(cons, "hip_skeleton", None) or hip_sk
+            F = float(prim.n_canonical_frames)
+            exits = _exit_constraints(F if self.exit_from == "frames" else F - 1.0, joint, ref_dir)
+            local = bool(getattr(cons, "is_local", False))
+            if i == 0:
+                al_motion = alignment_from_prev_frames(self.prev_frames, type("_NotLocal", (), {
+                    "start_pose": getattr(cons, "start_pose", None), "is_local": False,
+                    "skeleton": getattr(cons, "skeleton", getattr(graph, "skeleton", None))})(), sk)
+            else:
+                al_motion = {"joint": joint, "position": (0.0, 0.0, 0.0), "heading": (0.0, 1.0), "ref_dir": ref_dir}
+            if local and not (i == 0 and al_motion is None):      # (a local first step without a record: one unaligned set, as in _global_blocks)
+                scored = self._set(prim, keyframes, sk, None, taken) if keyframes else None
+                exit_set = self._set(prim, exits, sk, al_motion, taken)
+            else:
+                scored, exit_set = self._set(prim, keyframes + exits, sk, al_motion, taken), None
+            records.append((prim, scored, exit_set, offset, len(keyframes), column))
+            self._info.append((prim, keyframes, Li, offset, column, cons))
+            offset += Li
+            column += len(keyframes)
+        self.n_latents, self.n_columns = offset, column
+        self.table = _capi.WalkScoreTable(records)
+        self.ctx = self.table.ctx
+
+    def _ensure(self):
+        """A shared set may have been rewritten for another caller's values, or closed by the cache, since the table was made."""
+        if any(not cs.handle or cs.cached_values != values for cs, values in self._shared):
+            self._build()
+
+    def close(self):
+        for cs in self._private:
+            cs.close()
+        self._private = []
+        if self._buf is not None:
+            self._buf.free()
+        self._buf, self._cap = None, 0
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _run(self, S, logp=False):
+        """-> (residuals (n, n_columns), errors (n), exit state (n, 4), {step: log p (n)} for the steps whose mixture has no time
+        latents).  One device block: the latents, then everything that comes back."""
+        self._ensure()
+        S = _capi._latents(S)
+        if S.shape[1] < self.n_latents:
+            raise ValueError("latent rows of %d columns, the walk's steps need %d" % (S.shape[1], self.n_latents))
+        n, ld, m = S.shape[0], S.shape[1], len(self._info)
+        on_device = [i for i, (prim, _, Li, _, _, _) in enumerate(self._info)
+                     if logp and len(np.asarray(self.steps[i].parameters)) <= Li and prim.n_gmm_dims == Li]
+        lat_bytes = (S.nbytes + 255) & ~255
+        n_out = n * (self.n_columns + 5 + len(on_device))
+        need = lat_bytes + 8 * max(n_out, 1)
+        if need > self._cap:
+            if self._buf is not None:
+                self._buf.free()
+            self._buf, self._cap = self.ctx.malloc(2 * need), 2 * need
+        base = self._buf.address
+        d_res = base + lat_bytes
+        d_err = d_res + 8 * n * self.n_columns
+        d_exit = d_err + 8 * n
+        d_logp = d_exit + 8 * n * 4
+        if n == 0:
+            return np.zeros((0, self.n_columns)), np.zeros(0), np.zeros((0, 4)), {i: np.zeros(0) for i in on_device}
+        self.ctx.upload_into(base, S)
+        self.table.score_dev(base, S.dtype, n, ld, d_res if self.n_columns else None, self.n_columns, d_err, d_exit)
+        self.n_launches += 1
+        for j, i in enumerate(on_device):      # stream ordered behind the walk's launch, on the latents already there
+            prim, _, Li, offset, _, _ = self._info[i]
+            prim.gmm_log_prob_dev(base + offset * S.dtype.itemsize, S.dtype, n, ld, d_logp + 8 * n * j, np.float64)
+        out = self.ctx.download(d_res, (n_out,), np.float64)
+        res = out[:n * self.n_columns].reshape(n, self.n_columns)
+        err = out[n * self.n_columns:n * (self.n_columns + 1)]
+        ex = out[n * (self.n_columns + 1):n * (self.n_columns + 5)].reshape(n, 4)
+        lp = {i: out[n * (self.n_columns + 5 + j):n * (self.n_columns + 6 + j)] for j, i in enumerate(on_device)}
+        for _, _, _, _, _, cons in self._info:
+            if hasattr(cons, "evaluations"):
+                cons.evaluations += n
+        return res, err, ex, lp
+
+    def _blocks_of(self, res):
+        out = []
+        for _, keyframes, _, _, column, _ in self._info:
+            res_k = res[:, column:column + len(keyframes)]
+            out.append(group_residuals(keyframes, res_k) if keyframes else res_k)
+        return out
+
+    def blocks(self, S):
+        """Per step the (n, n_residuals_i) matrix: _global_blocks(S, ...)[2]."""
+        return self._blocks_of(self._run(S)[0])
+
+    def exit_state(self, S):
+        """(n, 4): the last step's exit values (unit heading x, z; root position x, z)."""
+        return self._run(S)[2]
+
+    def error_sum(self, S):
+        """(n,): per step the residuals added in constraint order, the step sums added in step order (on the device)."""
+        return self._run(S)[1].copy()
+
+    def residual_vector(self, S, init_error_sum):
+        """obj_global_residual_vector's rows for the batch S."""
+        blocks = self._blocks_of(self._run(S)[0])
+        cols = [_pad(b, int(step.n_spatial_components)) for b, step in zip(blocks, self.steps)]
+        return np.hstack(cols) / init_error_sum
+
+    def residual_vector_and_naturalness(self, S, error_scale, quality_scale, init_error_sum):
+        """obj_global_residual_vector_and_naturalness' rows for the batch S: the mixtures of the steps without time latents are
+        scored on the latents the walk's launch has read (mg_gmm_log_prob at the step's column), everything comes back in one
+        download; a step with time latents (its tail is concatenated) goes through the host for its mixture."""
+        S = np.asarray(_batch(S)[0], dtype=np.float64)
+        res, _, _, lp = self._run(S, logp=True)
+        cols = []
+        for i, (b, step) in enumerate(zip(self._blocks_of(res), self.steps)):
+            prim, _, Li, offset, _, _ = self._info[i]
+            width = Li
+            if i in lp:
+                nll = -lp[i] * quality_scale
+            else:
+                tail = np.asarray(step.parameters, dtype=np.float64)[Li:]
+                concat = np.hstack([S[:, offset:offset + Li], np.tile(tail, (len(S), 1))]) if len(tail) else S[:, offset:offset + Li]
+                nll = -prim.gmm_log_prob(np.ascontiguousarray(concat, dtype=np.float64)) * quality_scale
+                width = concat.shape[1]
+            cols.append(_pad(b * error_scale + nll[:, None], width))
+        return np.hstack(cols) / init_error_sum
+
+
+_WALK_OBJECTIVES = []      # [(graph, steps, constraint lists, prev_frames, exit_from, objective)], most recent last
+_WALK_OBJECTIVES_SIZE = 4
+
+
+def _walk_objective(motion_primitive_graph, graph_walk_steps, prev_frames, exit_from):
+    """The HipGraphWalkObjective of these very objects (the step list, every step's constraint list and prev_frames, by identity:
+    an optimiser hands the same `data` tuple over hundreds of times), built on first use.  None for a walk of more than
+    MG_WALK_MAX_STEPS steps."""
+    if len(graph_walk_steps) > _capi.MG_WALK_MAX_STEPS:
+        return None
+    lists = [_constraint_list(step.motion_primitive_constraints) for step in graph_walk_steps]
+    for k, (g, st, ls, pf, ef, obj) in enumerate(_WALK_OBJECTIVES):
+        if g is motion_primitive_graph and st is graph_walk_steps and pf is prev_frames and ef == exit_from and len(ls) == len(lists) and \
+                all(a is b for a, b in zip(ls, lists)):
+            _WALK_OBJECTIVES.append(_WALK_OBJECTIVES.pop(k))
+            return obj
+    obj = HipGraphWalkObjective(motion_primitive_graph, graph_walk_steps, prev_frames, exit_from)
+    _WALK_OBJECTIVES.append((motion_primitive_graph, graph_walk_steps, lists, prev_frames, exit_from, obj))
+    while len(_WALK_OBJECTIVES) > _WALK_OBJECTIVES_SIZE:
+        _WALK_OBJECTIVES.pop(0)[-1].close()
+    return obj
+
+
+def clear_walk_objectives():
+    """Drop the cached walk objectives (call before closing a primitive they belong to)."""
+    while _WALK_OBJECTIVES:
+        _WALK_OBJECTIVES.pop()[-1].close()
+
+
+def _one_launch(s, motion_primitive_graph, graph_walk_steps, prev_frames, exit_from, method, args, chain):
+    """method(S, *args) of the walk's objective; the chain's function where the walk has more than MG_WALK_MAX_STEPS steps or a
+    step's tables do not fit the kernel's LDS (MG_ERR_UNSUPPORTED)."""
+    obj = _walk_objective(motion_primitive_graph, graph_walk_steps, prev_frames, exit_from)
+    if obj is None:
+        return chain()
+    S, single = _batch(s)
+    try:
+        out = getattr(obj, method)(S, *args)
+    except _capi.MGError as e:
+        if e.status != _capi.MG_ERR_UNSUPPORTED:
+            raise
+        return chain()
+    return (float(out[0]) if out.ndim == 1 else out[0]) if single else out
+
+
+def obj_global_error_sum_one_launch(s, data):
+    """obj_global_error_sum with the walk in one launch.  (The steps' sums are added on the device one by one, NumPy's row sums
+    are pairwise: the last bits may differ from the chain's.)"""
+    motion_primitive_graph, graph_walk_steps, error_scale, quality_scale, prev_frames = data
+    return _one_launch(s, motion_primitive_graph, graph_walk_steps, prev_frames, "frames", "error_sum", (), lambda: obj_global_error_sum(s, data))
+
+
+def obj_global_residual_vector_one_launch(s, data):
+    """obj_global_residual_vector with the walk in one launch: the same bits."""
+    motion_primitive_graph, graph_walk_steps, error_scale, quality_scale, prev_frames, init_error_sum = data
+    return _one_launch(s, motion_primitive_graph, graph_walk_steps, prev_frames, "frames", "residual_vector", (init_error_sum,),
+                       lambda: obj_global_residual_vector(s, data))
+
+
+def obj_global_residual_vector_and_naturalness_one_launch(s, data):
+    """obj_global_residual_vector_and_naturalness with the walk in one launch: the same bits."""
+    motion_primitive_graph, graph_walk_steps, error_scale, quality_scale, prev_frames, init_error_sum = data
+    return _one_launch(s, motion_primitive_graph, graph_walk_steps, prev_frames, "coeffs", "residual_vector_and_naturalness",
+                       (error_scale, quality_scale, init_error_sum), lambda: obj_global_residual_vector_and_naturalness(s, data))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # Time constraints (reference constraints/time_constraints.py:25-110, objective optimization/objective_functions.py:270-287)
 # ---------------------------------------------------------------------------------------------------------------------
 class HipTimeConstraints(object):

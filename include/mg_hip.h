@@ -330,7 +330,7 @@ int mg_memset(mg_context *ctx, void *dst_dev, int value, int64_t bytes);
  *       4 = gmm_sample, 5 = spline_evaluate, 6 = fused step, 7 = a planner step in one launch (mg_options_step),
  *       8 = mg_joint_tracks, 9 = mg_score_frame_constraints, 10 = mg_score_trajectory[_points],
  *       11 = mg_cluster_tree_search (both tree kinds: mg_tree_search_kernel or mg_kd_tree_search_kernel),
- *       12 = the frames kernel of mg_walk_frames. */
+ *       12 = the frames kernel of mg_walk_frames, 13 = mg_score_walk_time. */
 int mg_profile_enable(mg_context *ctx, int enabled);
 int mg_profile_reset(mg_context *ctx);
 int mg_profile_get(mg_context *ctx, int slot, double *total_ms, int64_t *launches);
@@ -1069,7 +1069,46 @@ typedef struct {
 int mg_score_walk_residuals(int32_t n_steps, const mg_walk_score_step *steps, const void *latents_dev, int latent_dtype, int64_t n_samples,
                             int64_t ld, double *residuals_dev, int64_t ld_res, double *errors_dev, double *exit_state_dev);
 
+/* The TIME objective of a graph walk in ONE launch (csrc/mg_walk_time.hip): obj_time_error_sum over TimeConstraints (reference
+ * optimization/objective_functions.py:270-287, constraints/time_constraints.py:40-102) for n_samples rows of concatenated time latents,
+ * bit for bit what mg_time_function_canonical and mg_gmm_log_prob (float64) per step and the reference's host arithmetic give:
+ *   error      per constraint (step_index, keyframe_index, desired_time) in list order, starting from 0: n_frames = start_keyframe, then
+ *              += t_k(F_k - 1) for the steps k < step_index in step order, then += (double)(int64)t_k(keyframe_index) + 1 at k == step_index
+ *              (truncation towards zero), the constraint adds (desired_time - n_frames * frame_time)^2; 0 where keyframe_index >= F_k;
+ *              10000 where step_index >= n_steps; -F_k <= keyframe_index < 0 counts from the end; a negative step_index reads step 0;
+ *   loglik     log p of step k's mixture on [spatial latents of the step | the row's time latents of the step], added in step order
+ *              from 0, divided by n_steps;
+ *   objective  error_scale * error + (-loglik) * quality_scale; every product and sum above rounded on its own.
+ * t_k is the canonical time function of step k (t(i) = i for a primitive without time model).  Where a kept value of it -- t_k(F_k - 1) of
+ * any step, t_k at a constrained keyframe -- is not finite, the row's error and objective are NaN (its loglik is not affected).
+ * steps[k].latent_offset: first column of the step's n_time_components time latents in a row; steps[k].spatial_dev: n_components float64
+ * on the device.  error_dev, loglik_dev: (n_samples) float64 or NULL.  Profile slot 13.
+ * MG_ERR_INVALID_ARGUMENT: NULL pointers, latent_offset + n_time_components > ld, keyframe_index < -F_k.  MG_ERR_UNSUPPORTED, never an
+ * approximate answer: MG_F32 latents, more than MG_WALK_MAX_STEPS steps, primitives of two contexts, a mixture that mg_gmm_log_prob does
+ * not score on the matrix pipe at this batch (no packed matrix: more than 64 dimensions, or more than 240 components) or that does not
+ * span exactly n_components + n_time_components columns, a window whose tables do not fit LDS.  n_samples == 0: MG_OK, no launch.
+ * Apart from the table of steps and constraints (kept on the device, rewritten only when it differs from the last call's:
+ * mg_walk_time_table_uploads counts the uploads of a context) the call allocates nothing and does not synchronise. */
+typedef struct {
+    mg_primitive *prim;
+    int64_t latent_offset;
+    const double *spatial_dev;
+} mg_walk_time_step;
+typedef struct {
+    int32_t step_index;              /* counted from the window's first step */
+    int32_t keyframe_index;          /* canonical frame of that step */
+    double desired_time;             /* seconds */
+} mg_walk_time_constraint;
+int mg_score_walk_time(int32_t n_steps, const mg_walk_time_step *steps, const void *latents_dev, int latent_dtype, int64_t n_samples, int64_t ld,
+                       int32_t n_constraints, const mg_walk_time_constraint *constraints, double start_keyframe, double frame_time,
+                       double error_scale, double quality_scale, double *objective_dev, double *error_dev, double *loglik_dev);
+int mg_walk_time_table_uploads(mg_context *ctx, int64_t *uploads);
+
 /* ---- host-pointer convenience variants (H2D, launch, D2H, synchronise) ---------------- */
+/* mg_score_walk_time with host arrays: latents, outputs and every step's spatial latents (`spatial_dev` is a host pointer here) */
+int mg_score_walk_time_host(int32_t n_steps, const mg_walk_time_step *steps, const void *latents, int latent_dtype, int64_t n_samples, int64_t ld,
+                            int32_t n_constraints, const mg_walk_time_constraint *constraints, double start_keyframe, double frame_time,
+                            double error_scale, double quality_scale, double *objective, double *error, double *loglik);
 /* mg_score_walk_residuals with host arrays; `residuals` is read first, so columns no step owns keep their values */
 int mg_score_walk_residuals_host(int32_t n_steps, const mg_walk_score_step *steps, const void *latents, int latent_dtype, int64_t n_samples,
                                  int64_t ld, double *residuals, int64_t ld_res, double *errors, double *exit_state);

@@ -39,7 +39,7 @@ MG_CONSTRAINT_JOINT_MIDPOINT, MG_CONSTRAINT_JOINT_ORIENTATION, MG_CONSTRAINT_LOO
 MG_CONSTRAINT_VALUE_POSITION, MG_CONSTRAINT_VALUE_HEADING = 7, 8   # values of the aligned motion, not errors (chained graph-walk steps)
 PROFILE_SLOTS = {"frames": 0, "gmm_log_prob": 1, "score_constraints": 2, "argmin": 3,
                  "gmm_sample": 4, "spline_evaluate": 5, "step": 6, "options_step": 7, "joint_tracks": 8, "frame_constraints": 9, "trajectory": 10,
-                 "cluster_tree_search": 11, "walk_frames": 12}
+                 "cluster_tree_search": 11, "walk_frames": 12, "walk_time": 13}
 MG_TREE_MAX_DEPTH, MG_TREE_MAX_CHILDREN, MG_TREE_MAX_CANDIDATES = 64, 256, 64    # include/mg_hip.h
 MG_TREE_TIE, MG_TREE_NO_RESULT, MG_TREE_OVERFLOW, MG_TREE_NO_MEAN = 1, 2, 4, 8
 MG_KD_MAX_DEPTH = 64
@@ -91,6 +91,7 @@ EXPORTED_SYMBOLS = [
     "mg_align_motions_spatially", "mg_prepare_aligned_frames",
     "mg_walk_frames", "mg_walk_frames_host",
     "mg_score_walk_residuals", "mg_score_walk_residuals_host",
+    "mg_score_walk_time", "mg_score_walk_time_host", "mg_walk_time_table_uploads",
 ]
 
 
@@ -374,6 +375,9 @@ def load_library(path=None):
         "mg_walk_frames_host": [i32, vp, vp, vp, i32, i64, i64, vp, vp, i32, vp, vp, vp, vp, i64, vp],
         "mg_score_walk_residuals": [i32, vp, vp, i32, i64, i64, vp, i64, vp, vp],
         "mg_score_walk_residuals_host": [i32, vp, vp, i32, i64, i64, vp, i64, vp, vp],
+        "mg_score_walk_time": [i32, vp, vp, i32, i64, i64, i32, vp, dbl, dbl, dbl, dbl, vp, vp, vp],
+        "mg_score_walk_time_host": [i32, vp, vp, i32, i64, i64, i32, vp, dbl, dbl, dbl, dbl, vp, vp, vp],
+        "mg_walk_time_table_uploads": [vp, C.POINTER(i64)],
     }
     for name, argtypes in sigs.items():
         fn = getattr(lib, name)
@@ -941,6 +945,87 @@ class WalkScoreTable(object):
         _check(self.lib.mg_score_walk_residuals_host(self.n_steps, C.cast(self.array, C.c_void_p), S.ctypes.data_as(C.c_void_p), _dtype_code(S), n,
                                                      S.shape[1], _host_ptr(res), int(ld_res), _host_ptr(err), _host_ptr(ex)))
         return res, err, ex
+
+
+class WalkTimeStep(C.Structure):   # struct mg_walk_time_step
+    _fields_ = [("prim", C.c_void_p), ("latent_offset", C.c_int64), ("spatial", C.c_void_p)]
+
+
+class WalkTimeConstraint(C.Structure):   # struct mg_walk_time_constraint
+    _fields_ = [("step_index", C.c_int32), ("keyframe_index", C.c_int32), ("desired_time", C.c_double)]
+
+
+class WalkTimeTable(object):
+    """The tables of mg_score_walk_time: per step (primitive, first column of its time latents, its n_components fixed spatial
+    latents), and the constraints (step counted from the window's first step, canonical keyframe, desired time) in list order.
+    The spatial latents go to the device once, in one buffer of the table's own (close() frees it); the table holds the
+    primitives, so none of them is collected while it is in use."""
+
+    def __init__(self, steps, constraints, start_keyframe, frame_time):
+        if not steps:
+            raise ValueError("a window has at least one step")
+        self.steps = [(prim, int(off), np.ascontiguousarray(sp, dtype=np.float64)) for prim, off, sp in steps]
+        self.n_steps = len(self.steps)
+        self.lib, self.ctx = self.steps[0][0].lib, self.steps[0][0].ctx
+        self.start_keyframe, self.frame_time = float(start_keyframe), float(frame_time)
+        for prim, _, sp in self.steps:
+            if sp.shape != (prim.n_components,):
+                raise ValueError("a step's spatial latents must be (n_components,) = (%d,), got %r" % (prim.n_components, sp.shape))
+        self.n_latents = max(off + prim.n_time_components for prim, off, _ in self.steps)
+        self._spatial = self.ctx.upload(np.concatenate([sp for _, _, sp in self.steps]))
+        self.array = (WalkTimeStep * self.n_steps)()
+        self.host_array = (WalkTimeStep * self.n_steps)()
+        at = 0
+        for rec, hrec, (prim, off, sp) in zip(self.array, self.host_array, self.steps):
+            rec.prim = hrec.prim = prim.handle.value
+            rec.latent_offset = hrec.latent_offset = off
+            rec.spatial = self._spatial.address + 8 * at
+            hrec.spatial = sp.ctypes.data
+            at += len(sp)
+        self.constraints = [(int(s), int(k), float(t)) for s, k, t in constraints]
+        self.n_constraints = len(self.constraints)
+        self.carray = (WalkTimeConstraint * max(self.n_constraints, 1))()
+        for rec, (s, k, t) in zip(self.carray, self.constraints):
+            rec.step_index, rec.keyframe_index, rec.desired_time = s, k, t
+
+    def close(self):
+        if getattr(self, "_spatial", None) is not None:
+            self._spatial.free()
+        self._spatial = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def table_uploads(self):
+        """How often this context's device table of steps and constraints has been (re)written."""
+        n = C.c_int64()
+        _check(self.lib.mg_walk_time_table_uploads(self.ctx.handle, C.byref(n)))
+        return int(n.value)
+
+    def score_dev(self, lat_dev, lat_dtype, n, ld, error_scale, quality_scale, objective_dev, error_dev=None, loglik_dev=None):
+        """mg_score_walk_time on device buffers: asynchronous on the context's stream."""
+        if self._spatial is None:
+            raise ValueError("the table is closed")
+        code = MG_F64 if np.dtype(lat_dtype) == np.float64 else MG_F32
+        ptr = lambda b: _dev_ptr(b) if b is not None else None
+        _check(self.lib.mg_score_walk_time(self.n_steps, C.cast(self.array, C.c_void_p), ptr(lat_dev), code, int(n), int(ld), self.n_constraints,
+                                           C.cast(self.carray, C.c_void_p), self.start_keyframe, self.frame_time, float(error_scale), float(quality_scale),
+                                           ptr(objective_dev), ptr(error_dev), ptr(loglik_dev)))
+
+    def score(self, S, error_scale, quality_scale, parts=True):
+        """objective (n), or (objective, error, average log-likelihood), for host latents S (mg_score_walk_time_host)."""
+        S = _latents(S)
+        n = S.shape[0]
+        obj = np.empty(n, dtype=np.float64)
+        err = np.empty(n, dtype=np.float64) if parts else None
+        ll = np.empty(n, dtype=np.float64) if parts else None
+        _check(self.lib.mg_score_walk_time_host(self.n_steps, C.cast(self.host_array, C.c_void_p), S.ctypes.data_as(C.c_void_p), _dtype_code(S), n, S.shape[1],
+                                                self.n_constraints, C.cast(self.carray, C.c_void_p), self.start_keyframe, self.frame_time, float(error_scale),
+                                                float(quality_scale), _host_ptr(obj), _host_ptr(err), _host_ptr(ll)))
+        return (obj, err, ll) if parts else obj
 
 
 def _i32(a):

@@ -3,7 +3,8 @@
 The global spatial optimisation evaluates its objective over the concatenated latents of all steps with the whole walk in ONE
 launch (objective_functions.obj_global_residual_vector_and_naturalness_one_launch, csrc/mg_walk_score.hip), writes the result
 back with update_spatial_parameters and rebuilds the frames on the device (HipGraphWalk.convert_graph_walk_to_quaternion_frames:
-mg_walk_frames).  The method table, the algorithm_config keys and the constants are the reference's; constraint construction
+mg_walk_frames).  The time optimisation evaluates its objective over a window's time latents in one launch as well
+(objective_functions.obj_time_error_sum_one_launch, csrc/mg_walk_time.hip).  The method table, the algorithm_config keys and the constants are the reference's; constraint construction
 stays in the reference.
 
 The module imports without a device and works on a HipGraphWalk(host=True) as far as no objective is evaluated.
@@ -71,9 +72,10 @@ class HipGraphWalkOptimizer(object):
         self.global_error_minimizer = minimizers.get("global")
         self.collision_avoidance_error_minimizer = minimizers.get("collision_avoidance")
         if None in (self.time_error_minimizer, self.global_error_minimizer, self.collision_avoidance_error_minimizer):
-            from .motion_primitive_generator import HipLeastSquares, HipOptimizerBuilder
-            if self.time_error_minimizer is None:
-                self.time_error_minimizer = HipOptimizerBuilder(algorithm_config).build_time_error_minimizer()
+            from .motion_primitive_generator import HipLeastSquares, HipNumericalMinimizer, HipOptimizerBuilder
+            if self.time_error_minimizer is None:      # build_time_error_minimizer's settings on the one-launch objective
+                self.time_error_minimizer = HipNumericalMinimizer(algorithm_config["global_time_optimization_settings"],
+                                                                  of.obj_time_error_sum_one_launch)
             if self.global_error_minimizer is None:    # build_global_error_minimizer_residual's settings on the one-launch objective
                 self.global_error_minimizer = HipLeastSquares(algorithm_config["global_spatial_optimization_settings"],
                                                               of.obj_global_residual_vector_and_naturalness_one_launch)

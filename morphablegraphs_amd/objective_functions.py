@@ -526,6 +526,8 @@ def clear_walk_objectives():
     """Drop the cached walk objectives (call before closing a primitive they belong to)."""
     while _WALK_OBJECTIVES:
         _WALK_OBJECTIVES.pop()[-1].close()
+    while _WALK_TIME_OBJECTIVES:
+        _WALK_TIME_OBJECTIVES.pop()[-1].close()
 
 
 def _one_launch(s, motion_primitive_graph, graph_walk_steps, prev_frames, exit_from, method, args, chain):
@@ -652,6 +654,194 @@ def obj_time_error_sum(s, data):
     nll = -np.asarray(time_constraints.get_average_loglikelihood(s, motion_primitive_graph, graph_walk))
     out = error_scale * np.asarray(time_error) + nll * quality_scale
     return float(out) if np.ndim(out) == 0 else out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The time objective with the whole window in ONE launch (mg_score_walk_time, csrc/mg_walk_time.hip): a workgroup keeps its 16
+# candidates for all steps -- the time functions, the entries the constraints read and the mixtures' scores meet in its LDS --
+# where obj_time_error_sum makes two launches, two uploads and two downloads per step and loops over candidates, constraints
+# and steps on the host.  The values are the chain's, bit for bit.
+# ---------------------------------------------------------------------------------------------------------------------
+def walk_time_objective_host(time_functions, log_likelihoods, constraint_list, start_keyframe, frame_time, error_scale, quality_scale, parts=False):
+    """The arithmetic of mg_score_walk_time in NumPy, float64, no device.  time_functions: per step of the window the canonical
+    time functions of the candidates (n, F_k); log_likelihoods: per step the mixture's log p of every candidate (n,);
+    constraint_list: (step counted from the window's first step, canonical keyframe, desired time).  -> objective (n,), or with
+    parts (objective, error, average log-likelihood).  time_constraints.py:68-102, objective_functions.py:270-287: constraints in
+    list order, steps in step order, int() towards zero; a candidate with a non-finite entry among those read has error and
+    objective NaN; a keyframe below -F_k raises IndexError."""
+    tfs = [np.atleast_2d(np.asarray(tf, dtype=np.float64)) for tf in time_functions]
+    if not tfs:
+        raise ValueError("a window has at least one step")
+    n, m = tfs[0].shape[0], len(tfs)
+    before, finite = [], np.ones(n, dtype=bool)
+    n_before = np.full(n, float(start_keyframe))
+    for tf in tfs:                                   # frames before step k: start_keyframe + t_0(F - 1) + ... in step order
+        before.append(n_before)
+        finite &= np.isfinite(tf[:, -1])
+        n_before = n_before + tf[:, -1]
+    err = np.zeros(n)
+    for step_index, keyframe_index, desired_time in constraint_list:
+        k = max(int(step_index), 0)                  # (the reference's loop takes the first step it meets for a negative index)
+        if k >= m:
+            e = 10000.0
+        elif keyframe_index >= tfs[k].shape[1]:
+            e = 0.0
+        else:
+            t = tfs[k][:, keyframe_index]            # IndexError below -F, as in the reference
+            finite &= np.isfinite(t)
+            n_frames = before[k] + (np.trunc(np.where(np.isfinite(t), t, 0.0)) + 1.0)
+            d = desired_time - n_frames * frame_time
+            e = d * d
+        err = err + e
+    total = np.zeros(n)
+    for lp in log_likelihoods:
+        total = total + np.asarray(lp, dtype=np.float64)
+    avg = total / m
+    obj = error_scale * err + (-avg) * quality_scale
+    err, obj = np.where(finite, err, np.nan), np.where(finite, obj, np.nan)
+    return (obj, err, avg) if parts else obj
+
+
+class HipWalkTimeObjective(object):
+    """obj_time_error_sum of the steps start_step .. end_step of graph_walk under `time_constraints` (a HipTimeConstraints: its
+    start_step, end_step, constraint_list and start_keyframe are read), its tables built once: the step table and every step's
+    fixed spatial latents go to the device here.  evaluate(): one upload of S, one launch, one download.
+
+    Raises NotImplementedError for a window the launch does not state (no step, a static primitive, a node without HIP primitive,
+    a step whose widths are not its primitive's) and IndexError for a keyframe below -n_canonical_frames; evaluate() raises
+    _capi.MGError(MG_ERR_UNSUPPORTED) where the entry point refuses (the callers then take the chain)."""
+
+    def __init__(self, motion_primitive_graph, graph_walk, time_constraints):
+        from .motion_primitive_wrapper import HipStaticMotionPrimitive
+        self.graph, self.graph_walk, self.time_constraints = motion_primitive_graph, graph_walk, time_constraints
+        self.start_step, self.end_step = time_constraints.start_step, time_constraints.end_step
+        self.steps = list(graph_walk.steps[self.start_step:self.end_step])
+        self.constraint_list = [tuple(c) for c in time_constraints.constraint_list]
+        self.start_keyframe = float(time_constraints.start_keyframe)
+        self.frame_time = float(motion_primitive_graph.skeleton.frame_time)
+        if not self.steps:
+            raise NotImplementedError("an empty window")
+        records, offset = [], 0
+        for step in self.steps:
+            node = motion_primitive_graph.nodes[step.node_key]
+            if isinstance(getattr(node, "motion_primitive", None), HipStaticMotionPrimitive):
+                raise NotImplementedError("step %r is a static primitive" % (step.node_key,))
+            try:
+                prim = _prim_of(node)
+            except TypeError as e:
+                raise NotImplementedError(str(e))
+            ns, nt = int(step.n_spatial_components), int(step.n_time_components)
+            if ns != prim.n_components or nt != prim.n_time_components or len(np.asarray(step.parameters)) < ns:
+                raise NotImplementedError("step %r: %d spatial and %d time latents, its primitive has %d and %d" %
+                                          (step.node_key, ns, nt, prim.n_components, prim.n_time_components))
+            records.append((prim, offset, np.array(np.asarray(step.parameters, dtype=np.float64)[:ns])))
+            offset += nt
+        for step_index, keyframe_index, _ in self.constraint_list:
+            k = max(int(step_index), 0)
+            if k < len(records) and keyframe_index < -records[k][0].n_canonical_frames:
+                raise IndexError("index %d is out of bounds for a time function of %d canonical frames" % (keyframe_index, records[k][0].n_canonical_frames))
+        self.n_latents = offset
+        self.table = _capi.WalkTimeTable(records, self.constraint_list, self.start_keyframe, self.frame_time)
+        self.ctx = self.table.ctx
+        self._buf, self._cap = None, 0
+        self.n_launches = 0
+
+    def matches(self, graph_walk, time_constraints):
+        """Still the objective of this window: the same steps, constraints and start frame, the steps' spatial latents unchanged."""
+        tc = time_constraints
+        steps = graph_walk.steps[tc.start_step:tc.end_step]
+        if self.table is None or tc.start_step != self.start_step or tc.end_step != self.end_step or len(steps) != len(self.steps) or \
+                any(a is not b for a, b in zip(steps, self.steps)) or float(tc.start_keyframe) != self.start_keyframe or \
+                [tuple(c) for c in tc.constraint_list] != self.constraint_list or float(self.graph.skeleton.frame_time) != self.frame_time:
+            return False
+        return all(np.array_equal(np.asarray(step.parameters, dtype=np.float64)[:len(sp)], sp) for step, (_, _, sp) in zip(steps, self.table.steps))
+
+    def table_uploads(self):
+        return self.table.table_uploads()
+
+    def close(self):
+        if getattr(self, "table", None) is not None:
+            self.table.close()
+        self.table = None
+        if getattr(self, "_buf", None) is not None:
+            self._buf.free()
+        self._buf, self._cap = None, 0
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def evaluate(self, S, error_scale, quality_scale, parts=False):
+        """S (n, >= the window's time latents) -> objective (n,), or with parts (objective, error, average log-likelihood)."""
+        if self.table is None:
+            raise ValueError("the objective is closed")
+        S = _capi._latents(S)
+        if S.shape[1] < self.n_latents:
+            raise ValueError("latent rows of %d columns, the window's steps need %d" % (S.shape[1], self.n_latents))
+        n, ld = S.shape
+        if n == 0:
+            return (np.zeros(0), np.zeros(0), np.zeros(0)) if parts else np.zeros(0)
+        lat_bytes = (S.nbytes + 255) & ~255
+        need = lat_bytes + 8 * 3 * n
+        if need > self._cap:
+            if self._buf is not None:
+                self._buf.free()
+            self._buf, self._cap = self.ctx.malloc(2 * need), 2 * need
+        base = self._buf.address
+        d_out = base + lat_bytes
+        if S.nbytes:
+            self.ctx.upload_into(base, S)
+        self.table.score_dev(base, S.dtype, n, ld, error_scale, quality_scale, d_out, d_out + 8 * n if parts else None, d_out + 16 * n if parts else None)
+        self.n_launches += 1
+        out = self.ctx.download(d_out, (3 * n if parts else n,), np.float64)
+        return (out[:n], out[n:2 * n], out[2 * n:]) if parts else out
+
+
+_WALK_TIME_OBJECTIVES = []      # [(graph, graph_walk, time_constraints, objective)], most recent last
+_WALK_TIME_OBJECTIVES_SIZE = 4
+
+
+def _walk_time_objective(motion_primitive_graph, graph_walk, time_constraints):
+    """The HipWalkTimeObjective of these very objects (by identity: an optimiser hands the same `data` tuple over hundreds of
+    times), built on first use and again when the window, the constraints or a step's spatial latents have changed."""
+    for k, (g, w, t, obj) in enumerate(_WALK_TIME_OBJECTIVES):
+        if g is motion_primitive_graph and w is graph_walk and t is time_constraints:
+            _WALK_TIME_OBJECTIVES.pop(k)
+            if obj.matches(graph_walk, time_constraints):
+                _WALK_TIME_OBJECTIVES.append((g, w, t, obj))
+                return obj
+            obj.close()
+            break
+    obj = HipWalkTimeObjective(motion_primitive_graph, graph_walk, time_constraints)
+    _WALK_TIME_OBJECTIVES.append((motion_primitive_graph, graph_walk, time_constraints, obj))
+    while len(_WALK_TIME_OBJECTIVES) > _WALK_TIME_OBJECTIVES_SIZE:
+        _WALK_TIME_OBJECTIVES.pop(0)[-1].close()
+    return obj
+
+
+def obj_time_error_sum_one_launch(s, data):
+    """obj_time_error_sum with the window in one launch: the same bits.  The chain where the launch does not state the window
+    (a static primitive, MG_ERR_UNSUPPORTED).  ValueError names the first candidate whose time function is not finite at an entry
+    the objective reads (the minimisers take it as a failed evaluation, as the reference's does); IndexError for a keyframe
+    below -n_canonical_frames, as indexing the time function would."""
+    motion_primitive_graph, graph_walk, time_constraints, error_scale, quality_scale = data
+    S, single = _batch(s)
+    S = np.asarray(S, dtype=np.float64)
+    try:
+        objective = _walk_time_objective(motion_primitive_graph, graph_walk, time_constraints)
+        out, err, _ = objective.evaluate(S, error_scale, quality_scale, parts=True)
+    except NotImplementedError:
+        return obj_time_error_sum(s, data)
+    except _capi.MGError as e:
+        if e.status != _capi.MG_ERR_UNSUPPORTED:
+            raise
+        return obj_time_error_sum(s, data)
+    bad = np.flatnonzero(np.isnan(err))
+    if len(bad):
+        raise ValueError("candidate %d: the time function is not finite" % int(bad[0]))
+    return float(out[0]) if single else out
 
 
 # ---------------------------------------------------------------------------------------------------------------------

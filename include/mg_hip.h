@@ -330,7 +330,7 @@ int mg_memset(mg_context *ctx, void *dst_dev, int value, int64_t bytes);
  *       4 = gmm_sample, 5 = spline_evaluate, 6 = fused step, 7 = a planner step in one launch (mg_options_step),
  *       8 = mg_joint_tracks, 9 = mg_score_frame_constraints, 10 = mg_score_trajectory[_points],
  *       11 = mg_cluster_tree_search (both tree kinds: mg_tree_search_kernel or mg_kd_tree_search_kernel),
- *       12 = the frames kernel of mg_walk_frames, 13 = mg_score_walk_time. */
+ *       12 = the frames kernel of mg_walk_frames, 13 = mg_score_walk_time, 14 = mg_step_lengths. */
 int mg_profile_enable(mg_context *ctx, int enabled);
 int mg_profile_reset(mg_context *ctx);
 int mg_profile_get(mg_context *ctx, int slot, double *total_ms, int64_t *launches);
@@ -1104,7 +1104,44 @@ int mg_score_walk_time(int32_t n_steps, const mg_walk_time_step *steps, const vo
                        double error_scale, double quality_scale, double *objective_dev, double *error_dev, double *loglik_dev);
 int mg_walk_time_table_uploads(mg_context *ctx, int64_t *uploads);
 
+/* Step lengths without frames in memory, ONE launch for every candidate of every item (csrc/mg_step_length.hip): what
+ * MotionStateGraphNode.get_step_length_for_sample (reference motion_state_graph_node.py:208-230) takes from a back-projected motion,
+ * and what MotionStateGroup._update_motion_state_stats (motion_state_group.py:74-105) asks of every node of a graph.  Items may use
+ * different primitives, a primitive may repeat; all primitives belong to one context.  Per candidate, float64 throughout, every
+ * operation rounded on its own (float32 latents are converted first):
+ *   control points  of channels 0, 1, 2: mean' then fma(E'[k], s[k], .) for k ascending, translation_maxima included: the statement
+ *                   and the bits of mg_back_project_coeffs(MG_F64);
+ *   positions       p_f, f = 0 .. F - 1, on the primitive's canonical grid linspace(0, F, F) with the primitive's own tap rows (the
+ *                   FITPACK ext=0 row of the last sample included), four taps w0 c0, fma(w1, c1, .), ..: the bits of
+ *                   mg_back_project_frames_f64;
+ *   arc_length      d_1 + d_2 + .. + d_{F-1} added in frame order from d_1, d_f = sqrt((x_f - x_{f-1})^2 + (z_f - z_{f-1})^2); 0 for F = 1;
+ *   distance        sqrt((dx^2 + dy^2) + dz^2), d = p_{F-1} - p_0.
+ * A candidate with a latent that is not finite gets NaN for both, and nothing else does; a candidate's values depend on neither the
+ * batch nor the other items nor its position in either.  Nothing per candidate goes to device memory but the two results.
+ * latent_offset: first column of the item's n_components latents in a row of ld elements, so the steps of a walk can be items over one
+ * shared matrix.  arc_length_dev / distance_dev: (n_samples) float64, one of them may be NULL.
+ * Everything is checked before any launch.  MG_ERR_INVALID_ARGUMENT: NULL item table with n_items > 0, a NULL primitive, NULL latents
+ * with n_samples > 0, latent_offset < 0 or latent_offset + n_components > ld, negative counts, both outputs NULL, primitives of two
+ * contexts.  MG_ERR_UNSUPPORTED, never an approximate answer: a primitive with fewer than 3 channels, or whose root tables do not fit
+ * LDS.  n_items == 0 or all items empty: MG_OK, no launch; empty items among others are skipped.  A launch takes
+ * MG_STEP_LENGTH_MAX_ITEMS non-empty items; a call with more goes through them in slices itself, whatever their number.  Apart from
+ * the item table (kept on the device, rewritten only when it differs from the last call's) the call allocates nothing and does not
+ * synchronise.  Profile slot 14. */
+#define MG_STEP_LENGTH_MAX_ITEMS 256
+typedef struct {
+    mg_primitive *prim;
+    const void *latents_dev;    /* (n_samples, ld) float32 / float64 */
+    int64_t latent_offset;      /* first column of this item's n_components latents in a row */
+    int64_t n_samples, ld;
+    double *arc_length_dev;     /* (n_samples) or NULL */
+    double *distance_dev;       /* (n_samples) or NULL */
+} mg_step_length_item;
+int mg_step_lengths(int32_t n_items, const mg_step_length_item *items, int latent_dtype);
+
 /* ---- host-pointer convenience variants (H2D, launch, D2H, synchronise) ---------------- */
+/* mg_step_lengths with every item's latents and outputs in host memory (the `_dev` members are host pointers here); items that name
+ * the same latent matrix (pointer, n_samples and ld) share one copy of it on the device */
+int mg_step_lengths_host(int32_t n_items, const mg_step_length_item *items, int latent_dtype);
 /* mg_score_walk_time with host arrays: latents, outputs and every step's spatial latents (`spatial_dev` is a host pointer here) */
 int mg_score_walk_time_host(int32_t n_steps, const mg_walk_time_step *steps, const void *latents, int latent_dtype, int64_t n_samples, int64_t ld,
                             int32_t n_constraints, const mg_walk_time_constraint *constraints, double start_keyframe, double frame_time,

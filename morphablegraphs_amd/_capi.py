@@ -39,7 +39,7 @@ MG_CONSTRAINT_JOINT_MIDPOINT, MG_CONSTRAINT_JOINT_ORIENTATION, MG_CONSTRAINT_LOO
 MG_CONSTRAINT_VALUE_POSITION, MG_CONSTRAINT_VALUE_HEADING = 7, 8   # values of the aligned motion, not errors (chained graph-walk steps)
 PROFILE_SLOTS = {"frames": 0, "gmm_log_prob": 1, "score_constraints": 2, "argmin": 3,
                  "gmm_sample": 4, "spline_evaluate": 5, "step": 6, "options_step": 7, "joint_tracks": 8, "frame_constraints": 9, "trajectory": 10,
-                 "cluster_tree_search": 11, "walk_frames": 12, "walk_time": 13}
+                 "cluster_tree_search": 11, "walk_frames": 12, "walk_time": 13, "step_lengths": 14}
 MG_TREE_MAX_DEPTH, MG_TREE_MAX_CHILDREN, MG_TREE_MAX_CANDIDATES = 64, 256, 64    # include/mg_hip.h
 MG_TREE_TIE, MG_TREE_NO_RESULT, MG_TREE_OVERFLOW, MG_TREE_NO_MEAN = 1, 2, 4, 8
 MG_KD_MAX_DEPTH = 64
@@ -48,6 +48,7 @@ TREE_SEARCH_RECORD = np.dtype([("row", "<i8"), ("leaf", "<i4"), ("flags", "<i4")
 MG_WALK_MAX_STEPS = 64           # steps of one mg_walk_frames call (include/mg_hip.h)
 MG_WALK_TILE = 32                # frames per workgroup of mg_walk_frames_kernel (csrc/mg_walk.hip)
 MG_FUSED_MAX_OPTIONS = 24        # options of one mg_options_step_device_counts launch (csrc/mg_options.hip)
+MG_STEP_LENGTH_MAX_ITEMS = 256   # non-empty items of one mg_step_lengths launch (include/mg_hip.h); a call with more goes in slices
 
 
 @functools.lru_cache(maxsize=None)
@@ -92,6 +93,7 @@ EXPORTED_SYMBOLS = [
     "mg_walk_frames", "mg_walk_frames_host",
     "mg_score_walk_residuals", "mg_score_walk_residuals_host",
     "mg_score_walk_time", "mg_score_walk_time_host", "mg_walk_time_table_uploads",
+    "mg_step_lengths", "mg_step_lengths_host",
 ]
 
 
@@ -378,6 +380,8 @@ def load_library(path=None):
         "mg_score_walk_time": [i32, vp, vp, i32, i64, i64, i32, vp, dbl, dbl, dbl, dbl, vp, vp, vp],
         "mg_score_walk_time_host": [i32, vp, vp, i32, i64, i64, i32, vp, dbl, dbl, dbl, dbl, vp, vp, vp],
         "mg_walk_time_table_uploads": [vp, C.POINTER(i64)],
+        "mg_step_lengths": [i32, vp, i32],
+        "mg_step_lengths_host": [i32, vp, i32],
     }
     for name, argtypes in sigs.items():
         fn = getattr(lib, name)
@@ -1028,6 +1032,46 @@ class WalkTimeTable(object):
         return (obj, err, ll) if parts else obj
 
 
+class StepLengthItem(C.Structure):   # struct mg_step_length_item
+    _fields_ = [("prim", C.c_void_p), ("latents", C.c_void_p), ("latent_offset", C.c_int64), ("n_samples", C.c_int64), ("ld", C.c_int64),
+                ("arc_length", C.c_void_p), ("distance", C.c_void_p)]
+
+
+def step_lengths_table(lib, n_items, table, latent_dtype, host=True):
+    """mg_step_lengths_host (host pointers in the table; synchronises) or mg_step_lengths (device pointers; asynchronous on the
+    context's stream) on a (StepLengthItem * n) table as it stands; table None passes NULL."""
+    code = MG_F64 if np.dtype(latent_dtype) == np.float64 else MG_F32
+    fn = lib.mg_step_lengths_host if host else lib.mg_step_lengths
+    _check(fn(int(n_items), C.cast(table, C.c_void_p) if table is not None else None, code))
+
+
+def step_lengths(items, method="both"):
+    """Step lengths of every candidate of every item in one mg_step_lengths call.  items: (primitive, S) or (primitive, S,
+    latent_offset) with S (n, ld) float32 or float64 latents, one dtype for the call; an item reads the n_components columns from
+    latent_offset (default 0) on, and items that pass the same array share one copy of it on the device.  Per item (n,) float64:
+    the ground-plane arc length of the root path over the canonical frames ("arc_length"), the distance between its first and
+    last root position ("distance"), or the pair of them ("both")."""
+    if method not in ("arc_length", "distance", "both"):
+        raise NotImplementedError("step length method %r" % (method,))
+    items = [(it[0], _latents(it[1]), int(it[2]) if len(it) > 2 else 0) for it in items]   # (_latents returns a conforming array itself)
+    if not items:
+        return []
+    dtypes = set(S.dtype for _, S, _ in items)
+    if len(dtypes) != 1:
+        raise TypeError("the items of one call share a latent dtype, got %s" % sorted(str(d) for d in dtypes))
+    table = (StepLengthItem * len(items))()
+    out = []
+    for rec, (prim, S, off) in zip(table, items):
+        arc = np.empty(S.shape[0], dtype=np.float64) if method != "distance" else None
+        dist = np.empty(S.shape[0], dtype=np.float64) if method != "arc_length" else None
+        rec.prim, rec.latents, rec.latent_offset, rec.n_samples, rec.ld = prim.handle.value, S.ctypes.data, off, S.shape[0], S.shape[1]
+        rec.arc_length = arc.ctypes.data if arc is not None else None
+        rec.distance = dist.ctypes.data if dist is not None else None
+        out.append((arc, dist) if method == "both" else arc if dist is None else dist)
+    step_lengths_table(items[0][0].lib, len(items), table, dtypes.pop())
+    return out
+
+
 def _i32(a):
     return np.ascontiguousarray(np.asarray(a, dtype=np.int32))
 
@@ -1596,6 +1640,11 @@ class Primitive(object):
                                                         _dtype_code(S), S.shape[0], S.shape[1],
                                                         out.ctypes.data_as(C.c_void_p)))
         return out
+
+    def step_lengths(self, S, method="arc_length"):
+        """(n,) float64 step lengths of the rows of S (n, ld >= n_components; the first n_components columns are read) without
+        frames in memory (mg_step_lengths): "arc_length", "distance", or "both" = (arc_length, distance)."""
+        return step_lengths([(self, S)], method)[0]
 
     def back_project_coeffs(self, S, dtype=np.float64):
         S = _latents(S)

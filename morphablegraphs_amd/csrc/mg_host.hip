@@ -164,6 +164,7 @@ extern "C" void mg_context_destroy(mg_context *ctx) {
     if (ctx->walk_tab_dev) (void)hipFree(ctx->walk_tab_dev);
     if (ctx->wscore_tab_dev) (void)hipFree(ctx->wscore_tab_dev);
     if (ctx->wtime_tab_dev) (void)hipFree(ctx->wtime_tab_dev);
+    if (ctx->slen_tab_dev) (void)hipFree(ctx->slen_tab_dev);
     for (auto &b : ctx->arena) (void)hipFree(b.base);
     for (auto &v : ctx->vmm) mg_vmm_release(ctx, v);
     (void)hipDeviceSynchronize();   // nothing of this process is in flight when the parked address ranges go back to the runtime

@@ -13,7 +13,7 @@
 #define MG_ROWTILE 16       // coefficient rows per MFMA tile (M)
 #define MG_MAX_KK 16        // k-steps of 4 -> n_components <= 64 on the MFMA path
 #define MG_BLOCK 256        // threads per workgroup of the frames kernels
-#define MG_PROFILE_SLOTS 14
+#define MG_PROFILE_SLOTS 15
 
 void mg_set_error(const char *fmt, ...);
 int mg_hip_fail(hipError_t e, const char *what);
@@ -85,7 +85,7 @@ struct mg_context {
     // counts its steps), so that step needs no counts kernel in front; what was drawn for whom:
     struct { bool valid = false; int32_t n_options = 0, slot = 0; int64_t n = 0; uint64_t seeds[24] = {0}; const void *prims[24] = {nullptr}; } fused_next;
     unsigned attr_gmm_lds = 0, attr_traj = 0;   // dynamic-LDS attributes already set for this context's device (bit per instantiation;
-                                                // attr_traj: 1 trajectory, 2 time warp, 4 joint tracks, 8 frame constraints, 16 graph walk, 32 walk objective, 64 walk time objective)
+                                                // attr_traj: 1 trajectory, 2 time warp, 4 joint tracks, 8 frame constraints, 16 graph walk, 32 walk objective, 64 walk time objective, 128 / 256 step lengths of float32 / float64 latents)
     unsigned long long fused_seq = 0;   // sequence number of the planner steps whose records the kernel leaves in pinned memory
     int fused_partials_n = 0;
     // the output arena (mg_placement.hip): buffers that went through the placement probe, sub-allocated in 2 MiB granules
@@ -122,6 +122,9 @@ struct mg_context {
     size_t wtime_tab_cap = 0;       // from the last call's)
     std::vector<unsigned char> wtime_tab_host;
     int64_t wtime_tab_uploads = 0;  // how often that table went to the device (mg_walk_time_table_uploads)
+    void *slen_tab_dev = nullptr;   // mg_step_lengths: the call's items as the kernel reads them (rewritten only when they differ from the
+    size_t slen_tab_cap = 0;        // last call's)
+    std::vector<unsigned char> slen_tab_host;
 };
 void mg_dev_free(mg_context *ctx, void *p);   // hipFree unless p lives in the context's arena
 

@@ -385,6 +385,19 @@ def assemble_walks(graph, node_keys, S, time_parameters=None, alignment=None, sk
         return frames, offsets
 
 
+def walk_step_lengths(mps, S, offsets=None, method="arc_length"):
+    """Step lengths of a population of walks over the primitives `mps` (one per step; a primitive may repeat) in ONE
+    mg_step_lengths call: (n_walks, n_steps) float64.  S (n_walks, ld) float32 or float64; step i reads its spatial latents from
+    column offsets[i] on (default: back to back).  One item per step over the shared matrix; a step's length does not depend on
+    its alignment (a rotation about y and a translation keep ground-plane lengths), so the unaligned control points are scored."""
+    mps = [_primitive_of(mp) for mp in mps]
+    S = _capi._latents(S)
+    if offsets is None:
+        offsets = np.concatenate(([0], np.cumsum([mp.get_n_spatial_components() for mp in mps])[:-1]))
+    out = _capi.step_lengths([(mp._prim, S, int(off)) for mp, off in zip(mps, offsets)], method)
+    return np.stack(out, axis=1) if out else np.zeros((S.shape[0], 0))
+
+
 _ROOT_ONLY = _capi.Skeleton([("root", None, (0.0, 0.0, 0.0))], ["root"])
 
 
@@ -587,6 +600,19 @@ class HipGraphWalk(object):
 
     def get_num_of_frames(self):
         return self._n_frames
+
+    def update_arc_lengths(self):
+        """Sets every step's arc_length to the length travelled up to and including it (GraphWalkEntry.arc_length, which the
+        reference fills from get_step_length_for_sample step by step) from one mg_step_lengths call; returns the per-step lengths."""
+        if not self.steps:
+            return np.zeros(0)
+        mps = [_primitive_of(self.motion_state_graph.nodes[st.node_key]) for st in self.steps]
+        n_s = [st.n_spatial_components for st in self.steps]
+        S = np.concatenate([st.parameters[:k] for st, k in zip(self.steps, n_s)])[None, :]
+        lengths = walk_step_lengths(mps, S, np.concatenate(([0], np.cumsum(n_s)[:-1])))[0]
+        for st, travelled in zip(self.steps, np.cumsum(lengths)):
+            st.arc_length = float(travelled)
+        return lengths
 
     def get_global_spatial_parameter_vector(self, start_step=0):
         out = []

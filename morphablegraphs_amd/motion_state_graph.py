@@ -34,6 +34,19 @@ def arc_length_xz(root_positions):
     return np.sqrt(((p[..., 1:, :] - p[..., :-1, :]) ** 2).sum(axis=-1)).sum(axis=-1)
 
 
+def step_lengths_host(root_positions):
+    """(arc_length, distance) of root paths (..., F, 3) in NumPy: the statement of mg_step_lengths' two reductions
+    (csrc/mg_step_length.hip).  arc_length = d_1 + .. + d_{F-1} added in frame order (np.cumsum: np.sum adds pairwise, which is
+    not the kernel's order) with d_f = sqrt(dx^2 + dz^2) on the ground plane; distance = sqrt((dx^2 + dy^2) + dz^2) between the
+    first and the last position (np.linalg.norm of motion_state_graph_node.py:225-229)."""
+    p = np.asarray(root_positions, dtype=np.float64)
+    d = p[..., 1:, :] - p[..., :-1, :]
+    seg = np.sqrt(d[..., 0] * d[..., 0] + d[..., 2] * d[..., 2])
+    arc = np.cumsum(seg, axis=-1)[..., -1] if seg.shape[-1] else np.zeros(seg.shape[:-1])
+    e = p[..., -1, :] - p[..., 0, :]
+    return arc, np.sqrt((e[..., 0] * e[..., 0] + e[..., 1] * e[..., 1]) + e[..., 2] * e[..., 2])
+
+
 class HipMotionStateGraphNode(HipMotionPrimitiveModelWrapper):
     """The hot-path call sites of MotionStateGraphNode (reference motion_model/motion_state_graph_node.py:45-275)
     on top of the HIP-backed wrapper: step-length statistics, transition-model dispatch, best-sample search.
@@ -94,6 +107,11 @@ class HipMotionStateGraphNode(HipMotionPrimitiveModelWrapper):
         elif method == "distance":
             return np.linalg.norm(frames[:, -1, :3].astype(np.float64) - frames[:, 0, :3], axis=1)
         raise NotImplementedError
+
+    def step_lengths_on_device(self, samples, method="arc_length"):
+        """get_step_lengths_for_samples without frames in memory (mg_step_lengths): (n,) float64, float64 arithmetic on the
+        root's three channels alone; 8 bytes per candidate come back.  samples (n, >= n_spatial_components)."""
+        return self.motion_primitive._prim.step_lengths(samples, method)
 
     # ---- transitions (motion_state_graph_node.py:232-272) -----------------------------------------
     def has_transition_model(self, to_node_key):
@@ -235,6 +253,30 @@ class HipMotionStateGraph(object):
                 start_node[1] = start_node[1][5:]
             self.start_node = tuple(start_node)
         return self
+
+    def update_all_motion_stats(self, n_samples=5, method="median", node_keys=None):
+        """update_motion_stats of the given nodes (default: all, in self.nodes order) with ONE mg_step_lengths call for all of
+        them (MotionStateGroup._update_motion_state_stats, motion_state_group.py:74-105, pays a back-projection per sample).
+        The latents are drawn node after node with node.sample_low_dimensional_vector(), n_samples each: the draws, in the
+        order, of calling update_motion_stats on each node.  Static primitives keep the per-node path."""
+        keys = list(self.nodes) if node_keys is None else list(node_keys)
+        items, scored = [], []
+        for key in keys:
+            node = self.nodes[key]
+            if not isinstance(node.motion_primitive, HipMotionPrimitive):
+                node.update_motion_stats(n_samples, method)
+                continue
+            node.n_standard_transitions = len([e for e in node.outgoing_edges
+                                               if getattr(node.outgoing_edges[e], "transition_type", None) == NODE_TYPE_STANDARD])
+            rows = [np.ravel(node.sample_low_dimensional_vector()) for _ in range(n_samples)]
+            S = np.asarray(rows, dtype=np.float64).reshape(n_samples, -1)
+            items.append((node.motion_primitive._prim, S))
+            scored.append(node)
+        for node, lengths in zip(scored, _capi.step_lengths(items, "arc_length")):
+            if method == "average":
+                node.average_step_length = sum(lengths.tolist()) / n_samples
+            else:
+                node.average_step_length = np.median(lengths)
 
     def _build_nodes(self, graph_data):
         for action_name, action_data in graph_data["subgraphs"].items():

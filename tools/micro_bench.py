@@ -1,6 +1,6 @@
 """Event-timed averages of the secondary kernels at the bench's batch size (8192 'walk' candidates):
 log-likelihood, its Jacobian, fused keyframe scoring (plain / residual matrix / with FK chains), argmin,
-device sampler.  Usage: python3 tools/micro_bench.py [batch]"""
+device sampler, step lengths without frames.  Usage: python3 tools/micro_bench.py [batch]"""
 import os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -26,6 +26,9 @@ fk = [{"type": "joint_position", "joint": "LeftHand", "t": 155.0, "weight": 1.0,
       {"type": "joint_position", "joint": "RightFoot", "t": 77.0, "weight": 1.0, "target": [None, 0.0, None]}]
 cs = _capi.ConstraintSet(prim, cons)
 cs_fk = _capi.ConstraintSet(prim, cons + fk, sk)
+d_arc = ctx.malloc(B * 8)
+sl = (_capi.StepLengthItem * 1)()
+sl[0].prim, sl[0].latents, sl[0].latent_offset, sl[0].n_samples, sl[0].ld, sl[0].arc_length = prim.handle.value, d_S.address, 0, B, 40, d_arc.address
 lib = prim.lib
 C = _capi.C
 counts = np.full(8, B // 8, dtype=np.int64)
@@ -48,3 +51,4 @@ timed("score_constraints (2 root constraints)", lambda: prim.score_constraints_d
 timed("score_constraint_residuals (2 root + 2 FK)", lambda: _capi._check(lib.mg_score_constraint_residuals(prim.handle, cs_fk.handle, d_S.ptr, _capi.MG_F32, B, 40, d_res.ptr)))
 timed("argmin_first_dev", lambda: _capi._check(lib.mg_argmin_first_dev(ctx.handle, d_err.ptr, _capi.MG_F64, B, d_lp.ptr)))
 timed("gmm_sample (device Philox)", lambda: _capi._check(lib.mg_gmm_sample(prim.handle, B, counts.ctypes.data_as(C.c_void_p), C.c_uint64(1), d_x.ptr, _capi.MG_F32, 40, d_comp.ptr)))
+timed("step_lengths (arc length, f32 in)", lambda: _capi.step_lengths_table(lib, 1, sl, np.float32, host=False))

@@ -1102,7 +1102,14 @@ typedef struct {
 int mg_score_walk_time(int32_t n_steps, const mg_walk_time_step *steps, const void *latents_dev, int latent_dtype, int64_t n_samples, int64_t ld,
                        int32_t n_constraints, const mg_walk_time_constraint *constraints, double start_keyframe, double frame_time,
                        double error_scale, double quality_scale, double *objective_dev, double *error_dev, double *loglik_dev);
-int mg_walk_time_table_uploads(mg_context *ctx, int64_t *uploads);
+int mg_walk_time_table_uploads(mg_context *ctx, int64_t *uploads);   /* mg_context_table_uploads(ctx, MG_TABLE_WALK_TIME, uploads) */
+
+/* The per-call descriptor tables a context keeps on the device, each rewritten only when a call's table differs from the last call's:
+ * of mg_options_step's one-launch path, mg_cluster_tree_search, mg_walk_frames, mg_score_walk_residuals, mg_score_walk_time and
+ * mg_step_lengths.  mg_context_table_uploads: how often table `which` of the context went to the device so far. */
+enum { MG_TABLE_FUSED = 0, MG_TABLE_TREE = 1, MG_TABLE_WALK = 2, MG_TABLE_WALK_SCORE = 3, MG_TABLE_WALK_TIME = 4, MG_TABLE_STEP_LENGTH = 5,
+       MG_TABLE_COUNT = 6 };
+int mg_context_table_uploads(mg_context *ctx, int which, int64_t *uploads);
 
 /* Step lengths without frames in memory, ONE launch for every candidate of every item (csrc/mg_step_length.hip): what
  * MotionStateGraphNode.get_step_length_for_sample (reference motion_state_graph_node.py:208-230) takes from a back-projected motion,

@@ -40,6 +40,7 @@ MG_CONSTRAINT_VALUE_POSITION, MG_CONSTRAINT_VALUE_HEADING = 7, 8   # values of t
 PROFILE_SLOTS = {"frames": 0, "gmm_log_prob": 1, "score_constraints": 2, "argmin": 3,
                  "gmm_sample": 4, "spline_evaluate": 5, "step": 6, "options_step": 7, "joint_tracks": 8, "frame_constraints": 9, "trajectory": 10,
                  "cluster_tree_search": 11, "walk_frames": 12, "walk_time": 13, "step_lengths": 14}
+DEVICE_TABLES = {"fused": 0, "tree": 1, "walk": 2, "walk_score": 3, "walk_time": 4, "step_length": 5}    # MG_TABLE_* (include/mg_hip.h)
 MG_TREE_MAX_DEPTH, MG_TREE_MAX_CHILDREN, MG_TREE_MAX_CANDIDATES = 64, 256, 64    # include/mg_hip.h
 MG_TREE_TIE, MG_TREE_NO_RESULT, MG_TREE_OVERFLOW, MG_TREE_NO_MEAN = 1, 2, 4, 8
 MG_KD_MAX_DEPTH = 64
@@ -92,7 +93,7 @@ EXPORTED_SYMBOLS = [
     "mg_align_motions_spatially", "mg_prepare_aligned_frames",
     "mg_walk_frames", "mg_walk_frames_host",
     "mg_score_walk_residuals", "mg_score_walk_residuals_host",
-    "mg_score_walk_time", "mg_score_walk_time_host", "mg_walk_time_table_uploads",
+    "mg_score_walk_time", "mg_score_walk_time_host", "mg_walk_time_table_uploads", "mg_context_table_uploads",
     "mg_step_lengths", "mg_step_lengths_host",
 ]
 
@@ -380,6 +381,7 @@ def load_library(path=None):
         "mg_score_walk_time": [i32, vp, vp, i32, i64, i64, i32, vp, dbl, dbl, dbl, dbl, vp, vp, vp],
         "mg_score_walk_time_host": [i32, vp, vp, i32, i64, i64, i32, vp, dbl, dbl, dbl, dbl, vp, vp, vp],
         "mg_walk_time_table_uploads": [vp, C.POINTER(i64)],
+        "mg_context_table_uploads": [vp, C.c_int, C.POINTER(i64)],
         "mg_step_lengths": [i32, vp, i32],
         "mg_step_lengths_host": [i32, vp, i32],
     }
@@ -460,6 +462,12 @@ class Context(object):
 
     def synchronize(self):
         _check(self.lib.mg_context_synchronize(self.handle))
+
+    def table_uploads(self, name):
+        """How often the per-call device table `name` (a key of DEVICE_TABLES) of this context has been (re)written."""
+        n = C.c_int64()
+        _check(self.lib.mg_context_table_uploads(self.handle, DEVICE_TABLES[name], C.byref(n)))
+        return int(n.value)
 
     # ---- multi-GPU (RCCL loaded on first use; one process per GPU) ----------------------------------
     def dist_unique_id(self):

@@ -792,20 +792,6 @@ extern "C" void mg_cluster_tree_destroy(mg_cluster_tree *tree) {
     mg_tree_free(tree);
 }
 
-// The descriptor table of a call on the device: rewritten only when it differs from the last call's (ctx->tree_tab_host)
-static int mg_tree_table_upload(mg_context *ctx, size_t bytes, const void *data) {
-    if (ctx->tree_tab_dev && ctx->tree_tab_host.size() == bytes && memcmp(ctx->tree_tab_host.data(), data, bytes) == 0) return MG_OK;
-    MG_HIP_CHECK(hipStreamSynchronize(ctx->stream));   // no launch in flight reads the table being replaced
-    if (ctx->tree_tab_cap < bytes) {
-        if (ctx->tree_tab_dev) { (void)hipFree(ctx->tree_tab_dev); ctx->tree_tab_dev = nullptr; ctx->tree_tab_cap = 0; }
-        MG_HIP_CHECK(hipMalloc(&ctx->tree_tab_dev, bytes));
-        ctx->tree_tab_cap = bytes;
-    }
-    MG_HIP_CHECK(hipMemcpy(ctx->tree_tab_dev, data, bytes, hipMemcpyHostToDevice));
-    ctx->tree_tab_host.assign((const unsigned char *)data, (const unsigned char *)data + bytes);
-    return MG_OK;
-}
-
 // what a call's plan is sized by: the largest of each over its searches
 struct mg_tree_maxima {
     int L = 1, nc = 1, children = 1, depth = 0, kd_children = 1, kd_depth = 0, wrows = 0;
@@ -825,13 +811,14 @@ static int mg_tree_launch(mg_context *ctx, const std::vector<mg_tree_search_desc
         return MG_ERR_UNSUPPORTED;
     }
     MG_HIP_CHECK(hipSetDevice(ctx->device));
-    int rc = mg_tree_table_upload(ctx, tab.size() * sizeof(mg_tree_search_desc), tab.data());
+    mg_device_table &dt = ctx->tab[MG_TABLE_TREE];
+    int rc = dt.upload(ctx, "mg_cluster_tree_search", tab.data(), tab.size() * sizeof(mg_tree_search_desc));
     if (rc != MG_OK) return rc;
-    if (lp.bytes > 64 * 1024) MG_HIP_CHECK(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, MG_TREE_LDS_MAX));
-    mg_prof_begin(ctx, 11);
-    hipLaunchKernelGGL(kernel, dim3((unsigned)tab.size()), dim3(MG_TREE_THREADS), lp.bytes, ctx->stream, (const mg_tree_search_desc *)ctx->tree_tab_dev, lp,
+    if (lp.bytes > 64 * 1024) MG_HIP_CHECK(mg_lds_opt_in(MG_TREE_LDS_MAX, kernel));
+    mg_prof_begin(ctx, MG_PROF_CLUSTER_TREE_SEARCH);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)tab.size()), dim3(MG_TREE_THREADS), lp.bytes, ctx->stream, (const mg_tree_search_desc *)dt.base(), lp,
                        records_dev);
-    mg_prof_end(ctx, 11);
+    mg_prof_end(ctx, MG_PROF_CLUSTER_TREE_SEARCH);
     MG_HIP_CHECK(hipGetLastError());
     return MG_OK;
 }

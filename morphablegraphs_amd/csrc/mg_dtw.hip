@@ -235,7 +235,7 @@ extern "C" int mg_dtw_paths(mg_context *ctx, const double *grids_dev, int32_t n_
     if (rf != MG_OK) return rf;
     MG_REQUIRE_AS(!flag, MG_ERR_INVALID_ARGUMENT, "mg_dtw_paths: the grids hold non-finite values");
     if (in_lds && code_bytes + sizeof(double) * 3 * DTW_MAX_FRAMES + 64 > 64 * 1024)
-        MG_HIP_CHECK(hipFuncSetAttribute((const void *)dtw_paths_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, DTW_CODE_LDS_BYTES));
+        MG_HIP_CHECK(mg_lds_opt_in(DTW_CODE_LDS_BYTES, dtw_paths_kernel));
     const unsigned block = (unsigned)((n_ref_frames + 63) / 64 * 64);
     for (int64_t n0 = 0; n0 < n_motions; n0 += chunk) {
         const int64_t nb = std::min(chunk, n_motions - n0);

@@ -158,7 +158,7 @@ extern "C" int mg_dtw_pair_costs(mg_context *ctx, const double *clouds_dev, cons
     while (pairs_lds_doubles(n_joints, pass_rows, (int32_t)longest_ref) * 8 > PAIRS_LDS_BYTES) pass_rows /= 2;   // 32 at J = 64, and from J = 59 on when a reference motion has 1024 frames
     const size_t lds = pairs_lds_doubles(n_joints, pass_rows, (int32_t)longest_ref) * 8;
     if (lds > 64 * 1024)
-        MG_HIP_CHECK(hipFuncSetAttribute((const void *)dtw_pair_costs_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, PAIRS_LDS_BYTES));
+        MG_HIP_CHECK(mg_lds_opt_in(PAIRS_LDS_BYTES, dtw_pair_costs_kernel));
     const int64_t chunk_n = 65535;                                        // workgroups of a launch: at most 2^22, of 2^9 lanes
     for (int64_t n0 = 0; n0 < n_motions; n0 += chunk_n) {
         const int64_t nb = std::min(chunk_n, n_motions - n0), chunk_r = std::min<int64_t>(65535, ((int64_t)1 << 22) / nb);

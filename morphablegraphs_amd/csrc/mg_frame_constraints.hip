@@ -526,11 +526,8 @@ static size_t mg_fc_place_tables(mg_fc_args *c, int n) {
     return doubles * 8;
 }
 static int mg_fc_attributes(mg_context *ctx) {
-    if (ctx->attr_traj & 8u) return MG_OK;
-    MG_HIP_CHECK(hipFuncSetAttribute((const void *)mg_frame_constraint_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    MG_HIP_CHECK(hipFuncSetAttribute((const void *)mg_frame_constraint_list_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    MG_HIP_CHECK(hipFuncSetAttribute((const void *)mg_options_lists_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    ctx->attr_traj |= 8u;
+    MG_HIP_CHECK(mg_lds_opt_in_once(ctx, MG_LDS_FRAME_CONSTRAINTS, 160 * 1024, mg_frame_constraint_kernel<true>, mg_frame_constraint_list_kernel<true>,
+                                    mg_options_lists_kernel<true>));
     return MG_OK;
 }
 
@@ -594,10 +591,10 @@ extern "C" int mg_score_frame_constraints(mg_primitive *p, int32_t n_constraints
         const size_t lds = mg_fc_place_tables(L.c, L.n);
         if (lds) { const int rc = mg_fc_attributes(p->ctx); if (rc != MG_OK) return rc; }
         const dim3 grid((unsigned)((B + MG_FC_BLOCK - 1) / MG_FC_BLOCK));
-        mg_prof_begin(p->ctx, 9);
+        mg_prof_begin(p->ctx, MG_PROF_FRAME_CONSTRAINTS);
         if (lds) hipLaunchKernelGGL(mg_frame_constraint_list_kernel<true>, grid, dim3(MG_FC_BLOCK), lds, p->ctx->stream, L);
         else hipLaunchKernelGGL(mg_frame_constraint_list_kernel<false>, grid, dim3(MG_FC_BLOCK), 0, p->ctx->stream, L);
-        mg_prof_end(p->ctx, 9);
+        mg_prof_end(p->ctx, MG_PROF_FRAME_CONSTRAINTS);
         MG_HIP_CHECK(hipGetLastError());
         any = true;
         k0 += L.n;
@@ -929,10 +926,7 @@ static int mg_track_fill_args(const char *who, mg_track_plan *pl, const void *la
     return MG_OK;
 }
 static int mg_track_attributes(mg_context *ctx) {
-    if (ctx->attr_traj & 4u) return MG_OK;
-    MG_HIP_CHECK(hipFuncSetAttribute((const void *)mg_joint_tracks_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    MG_HIP_CHECK(hipFuncSetAttribute((const void *)mg_joint_tracks_multi_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    ctx->attr_traj |= 4u;
+    MG_HIP_CHECK(mg_lds_opt_in_once(ctx, MG_LDS_JOINT_TRACKS, 160 * 1024, mg_joint_tracks_kernel, mg_joint_tracks_multi_kernel));
     return MG_OK;
 }
 
@@ -945,9 +939,9 @@ extern "C" int mg_joint_tracks(mg_track_plan *pl, const void *lat, int dt, int64
     mg_primitive *p = pl->prim;
     MG_HIP_CHECK(hipSetDevice(p->ctx->device));
     if (lds > 48 * 1024) { const int rc = mg_track_attributes(p->ctx); if (rc != MG_OK) return rc; }
-    mg_prof_begin(p->ctx, 8);
+    mg_prof_begin(p->ctx, MG_PROF_JOINT_TRACKS);
     hipLaunchKernelGGL(mg_joint_tracks_kernel, dim3((unsigned)((B + MG_TRACK_CANDS - 1) / MG_TRACK_CANDS)), dim3(MG_TRACK_BLOCK), lds, p->ctx->stream, a);
-    mg_prof_end(p->ctx, 8);
+    mg_prof_end(p->ctx, MG_PROF_JOINT_TRACKS);
     MG_HIP_CHECK(hipGetLastError());
     return MG_OK;
 }
@@ -1048,20 +1042,20 @@ extern "C" int mg_options_frame_lists(int32_t n_options, mg_primitive *const *pr
     MG_HIP_CHECK(hipMemcpyAsync(base + t_bytes, lists.data(), l_bytes, hipMemcpyHostToDevice, ctx->stream));
     if (tw.n > 0) {
         if (t_lds > 48 * 1024) { const int rc = mg_track_attributes(ctx); if (rc != MG_OK) return rc; }
-        mg_prof_begin(ctx, 8);
+        mg_prof_begin(ctx, MG_PROF_JOINT_TRACKS);
         hipLaunchKernelGGL(mg_joint_tracks_multi_kernel, dim3((unsigned)tw.wg0[tw.n]), dim3(MG_TRACK_BLOCK), t_lds, ctx->stream, (const mg_track_args *)base, tw);
-        mg_prof_end(ctx, 8);
+        mg_prof_end(ctx, MG_PROF_JOINT_TRACKS);
         MG_HIP_CHECK(hipGetLastError());
     }
     if (l_lds && tables_ok) { const int rc = mg_fc_attributes(ctx); if (rc != MG_OK) return rc; }
-    mg_prof_begin(ctx, 9);
+    mg_prof_begin(ctx, MG_PROF_FRAME_CONSTRAINTS);
     if (l_lds && tables_ok)
         hipLaunchKernelGGL(mg_options_lists_kernel<true>, dim3((unsigned)lw.wg0[n_options]), dim3(MG_FC_BLOCK), l_lds, ctx->stream,
                            (const mg_opt_list_entry *)(base + t_bytes), lw, (mg_min_partial *)(base + t_bytes + l_bytes), (int32_t *)(base + c_off));
     else
         hipLaunchKernelGGL(mg_options_lists_kernel<false>, dim3((unsigned)lw.wg0[n_options]), dim3(MG_FC_BLOCK), 0, ctx->stream,
                            (const mg_opt_list_entry *)(base + t_bytes), lw, (mg_min_partial *)(base + t_bytes + l_bytes), (int32_t *)(base + c_off));
-    mg_prof_end(ctx, 9);
+    mg_prof_end(ctx, MG_PROF_FRAME_CONSTRAINTS);
     MG_HIP_CHECK(hipGetLastError());
     if (results_host) {
         MG_HIP_CHECK(hipMemcpyAsync(results_host, results_dev, (size_t)n_options * result_stride, hipMemcpyDeviceToHost, ctx->stream));

@@ -481,15 +481,11 @@ int mg_launch_frames_ws(mg_primitive *p, const mg_time_grid *g, const void *lat,
 
 template <int KK>
 static int mg_ws_attr_kk() {
-    MG_HIP_CHECK(hipFuncSetAttribute((const void *)mg_frames_ws_kernel<KK, true, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    MG_HIP_CHECK(hipFuncSetAttribute((const void *)mg_frames_ws_kernel<KK, false, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    MG_HIP_CHECK(hipFuncSetAttribute((const void *)mg_frames_ws_kernel<KK, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    MG_HIP_CHECK(hipFuncSetAttribute((const void *)mg_frames_ws_kernel<KK, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    MG_HIP_CHECK(mg_lds_opt_in(160 * 1024, mg_frames_ws_kernel<KK, true, false, false>, mg_frames_ws_kernel<KK, false, false, false>,
+                               mg_frames_ws_kernel<KK, true, false, true>, mg_frames_ws_kernel<KK, false, false, true>));
     if constexpr (KK <= MG_FUSE_MAX_KK) {
-        MG_HIP_CHECK(hipFuncSetAttribute((const void *)mg_frames_ws_kernel<KK, true, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        MG_HIP_CHECK(hipFuncSetAttribute((const void *)mg_frames_ws_kernel<KK, false, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        MG_HIP_CHECK(hipFuncSetAttribute((const void *)mg_frames_ws_kernel<KK, true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        MG_HIP_CHECK(hipFuncSetAttribute((const void *)mg_frames_ws_kernel<KK, false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        MG_HIP_CHECK(mg_lds_opt_in(160 * 1024, mg_frames_ws_kernel<KK, true, true, false>, mg_frames_ws_kernel<KK, false, true, false>,
+                                   mg_frames_ws_kernel<KK, true, true, true>, mg_frames_ws_kernel<KK, false, true, true>));
     }
     return MG_OK;
 }

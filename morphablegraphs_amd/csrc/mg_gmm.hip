@@ -460,16 +460,10 @@ static int mg_launch_gmm_lds_kk(mg_primitive *p, const void *x, int xdt, int64_t
     const bool xf = xdt == MG_F64, of = odt == MG_F64;
     // the dynamic-LDS attribute is a property of (kernel, device): once per context (a per-process flag left a second
     // GPU's context without it)
-    const unsigned abit = 1u << (KK / 2);
-    if (!(p->ctx->attr_gmm_lds & abit)) {
-        MG_HIP_CHECK(hipFuncSetAttribute((const void *)mg_gmm_logp_lds_kernel<KK, true, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        MG_HIP_CHECK(hipFuncSetAttribute((const void *)mg_gmm_logp_lds_kernel<KK, true, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        MG_HIP_CHECK(hipFuncSetAttribute((const void *)mg_gmm_logp_lds_kernel<KK, false, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        MG_HIP_CHECK(hipFuncSetAttribute((const void *)mg_gmm_logp_lds_kernel<KK, false, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        MG_HIP_CHECK(hipFuncSetAttribute((const void *)mg_gmm_logp_lds_kernel<KK, true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        MG_HIP_CHECK(hipFuncSetAttribute((const void *)mg_gmm_logp_lds_kernel<KK, false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        p->ctx->attr_gmm_lds |= abit;
-    }
+    MG_HIP_CHECK(mg_lds_opt_in_once(p->ctx->attr_gmm_lds, 1u << (KK / 2), 160 * 1024, mg_gmm_logp_lds_kernel<KK, true, true, false>,
+                                    mg_gmm_logp_lds_kernel<KK, true, false, false>, mg_gmm_logp_lds_kernel<KK, false, true, false>,
+                                    mg_gmm_logp_lds_kernel<KK, false, false, false>, mg_gmm_logp_lds_kernel<KK, true, true, true>,
+                                    mg_gmm_logp_lds_kernel<KK, false, true, true>));
     if (cs) {   // the objective: log p in float64 (or not at all), errors and objective in float64
         if (xf) hipLaunchKernelGGL((mg_gmm_logp_lds_kernel<KK, true, true, true>), dim3(grid), dim3(64 * nw), lds, st, p->d_gPpack, p->d_gmPpad, p->d_gconst, x, out, a, n_tiles, oa);
         else hipLaunchKernelGGL((mg_gmm_logp_lds_kernel<KK, false, true, true>), dim3(grid), dim3(64 * nw), lds, st, p->d_gPpack, p->d_gmPpad, p->d_gconst, x, out, a, n_tiles, oa);
@@ -559,12 +553,8 @@ int mg_launch_gmm_logp(mg_primitive *p, const void *x, int xdt, int64_t B, int64
     dim3 blk(MG_GMM_CANDS * MG_GMM_WAVES);
     hipStream_t st = p->ctx->stream;
     const bool xf = xdt == MG_F64, of = odt == MG_F64;
-    if (lds > 64 * 1024) {
-        MG_HIP_CHECK(hipFuncSetAttribute((const void *)mg_gmm_logp_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        MG_HIP_CHECK(hipFuncSetAttribute((const void *)mg_gmm_logp_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        MG_HIP_CHECK(hipFuncSetAttribute((const void *)mg_gmm_logp_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        MG_HIP_CHECK(hipFuncSetAttribute((const void *)mg_gmm_logp_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    }
+    if (lds > 64 * 1024) MG_HIP_CHECK(mg_lds_opt_in(160 * 1024, mg_gmm_logp_kernel<true, true>, mg_gmm_logp_kernel<true, false>, mg_gmm_logp_kernel<false, true>,
+                                                    mg_gmm_logp_kernel<false, false>));
     if (xf && of) hipLaunchKernelGGL((mg_gmm_logp_kernel<true, true>), dim3((int)grid), blk, lds, st, a);
     else if (xf) hipLaunchKernelGGL((mg_gmm_logp_kernel<true, false>), dim3((int)grid), blk, lds, st, a);
     else if (of) hipLaunchKernelGGL((mg_gmm_logp_kernel<false, true>), dim3((int)grid), blk, lds, st, a);
@@ -629,10 +619,7 @@ int mg_launch_gmm_sample_valu(mg_primitive *p, int64_t n, const int64_t *cum_dev
     if (lds > 150 * 1024) { mg_set_error("mg_gmm_sample: n_components %d too large", p->Lg); return MG_ERR_UNSUPPORTED; }
     int64_t grid = (n + MG_SAMPLE_BLOCK - 1) / MG_SAMPLE_BLOCK;
     if (grid > 0x7fffffff) { mg_set_error("mg_gmm_sample: too many samples"); return MG_ERR_UNSUPPORTED; }
-    if (lds > 64 * 1024) {
-        MG_HIP_CHECK(hipFuncSetAttribute((const void *)mg_gmm_sample_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        MG_HIP_CHECK(hipFuncSetAttribute((const void *)mg_gmm_sample_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    }
+    if (lds > 64 * 1024) MG_HIP_CHECK(mg_lds_opt_in(160 * 1024, mg_gmm_sample_kernel<true>, mg_gmm_sample_kernel<false>));
     if (xdt == MG_F64) hipLaunchKernelGGL((mg_gmm_sample_kernel<true>), dim3((int)grid), dim3(MG_SAMPLE_BLOCK), lds, p->ctx->stream, a);
     else hipLaunchKernelGGL((mg_gmm_sample_kernel<false>), dim3((int)grid), dim3(MG_SAMPLE_BLOCK), lds, p->ctx->stream, a);
     MG_HIP_CHECK(hipGetLastError());
@@ -763,10 +750,7 @@ static int mg_launch_gmm_jac_mfma_kk(mg_primitive *p, const void *x, int xdt, in
     const int64_t grid = (B + 15) / 16;
     const size_t lds = ((size_t)p->K * 16 * (JTM * 16 + 1) + (size_t)p->K * 16 + 16 + (size_t)4 * 16 * JTM * 16) * 8;
     if (lds > 150 * 1024 || grid > 0x7fffffff) return MG_ERR_UNSUPPORTED;
-    if (lds > 64 * 1024) {
-        MG_HIP_CHECK(hipFuncSetAttribute((const void *)mg_gmm_jac_mfma_kernel<KK, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        MG_HIP_CHECK(hipFuncSetAttribute((const void *)mg_gmm_jac_mfma_kernel<KK, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    }
+    if (lds > 64 * 1024) MG_HIP_CHECK(mg_lds_opt_in(160 * 1024, mg_gmm_jac_mfma_kernel<KK, true>, mg_gmm_jac_mfma_kernel<KK, false>));
     hipStream_t st = p->ctx->stream;
     if (xdt == MG_F64) hipLaunchKernelGGL((mg_gmm_jac_mfma_kernel<KK, true>), dim3((int)grid), dim3(256), lds, st, p->d_gPpack, p->d_gPTpack, p->d_gmPpad, p->d_gconst, x, out, a);
     else hipLaunchKernelGGL((mg_gmm_jac_mfma_kernel<KK, false>), dim3((int)grid), dim3(256), lds, st, p->d_gPpack, p->d_gPTpack, p->d_gmPpad, p->d_gconst, x, out, a);
@@ -798,10 +782,7 @@ int mg_launch_gmm_jac(mg_primitive *p, const void *x, int xdt, int64_t B, int64_
         mg_set_error("mg_gmm_log_prob_jac: n_components %d x n_gmm %d too large for the LDS-staged kernel", p->Lg, p->K);
         return MG_ERR_UNSUPPORTED;
     }
-    if (lds > 64 * 1024) {
-        MG_HIP_CHECK(hipFuncSetAttribute((const void *)mg_gmm_jac_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        MG_HIP_CHECK(hipFuncSetAttribute((const void *)mg_gmm_jac_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    }
+    if (lds > 64 * 1024) MG_HIP_CHECK(mg_lds_opt_in(160 * 1024, mg_gmm_jac_kernel<true>, mg_gmm_jac_kernel<false>));
     hipStream_t st = p->ctx->stream;
     if (xdt == MG_F64) hipLaunchKernelGGL((mg_gmm_jac_kernel<true>), dim3((int)grid), dim3(256), lds, st, a);
     else hipLaunchKernelGGL((mg_gmm_jac_kernel<false>), dim3((int)grid), dim3(256), lds, st, a);

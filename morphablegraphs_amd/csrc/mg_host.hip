@@ -155,16 +155,12 @@ extern "C" void mg_context_destroy(mg_context *ctx) {
     if (ctx->scratch) (void)mg_device_free(ctx, ctx->scratch);
     mg_output_release_all(ctx);
     if (ctx->argmin_out) (void)hipFree(ctx->argmin_out);
-    for (void *q : {ctx->fused_tab_dev, ctx->fused_counters, ctx->fused_partials, ctx->fused_dyn_dev}) if (q) (void)hipFree(q);
+    for (void *q : {ctx->fused_counters, ctx->fused_partials, ctx->fused_dyn_dev}) if (q) (void)hipFree(q);
     if (ctx->pinned) (void)hipHostFree(ctx->pinned);
     if (ctx->flag_block) (void)hipHostFree(ctx->flag_block);
     if (ctx->traj_paths) (void)hipFree(ctx->traj_paths);
     if (ctx->lists_dev) (void)hipFree(ctx->lists_dev);
-    if (ctx->tree_tab_dev) (void)hipFree(ctx->tree_tab_dev);
-    if (ctx->walk_tab_dev) (void)hipFree(ctx->walk_tab_dev);
-    if (ctx->wscore_tab_dev) (void)hipFree(ctx->wscore_tab_dev);
-    if (ctx->wtime_tab_dev) (void)hipFree(ctx->wtime_tab_dev);
-    if (ctx->slen_tab_dev) (void)hipFree(ctx->slen_tab_dev);
+    for (auto &t : ctx->tab) if (t.dev) (void)hipFree(t.dev);
     for (auto &b : ctx->arena) (void)hipFree(b.base);
     for (auto &v : ctx->vmm) mg_vmm_release(ctx, v);
     (void)hipDeviceSynchronize();   // nothing of this process is in flight when the parked address ranges go back to the runtime
@@ -173,6 +169,40 @@ extern "C" void mg_context_destroy(mg_context *ctx) {
     if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
 }
+
+// Hit: the same bytes as the last upload and room for `behind`; nothing is done.  Miss: the stream is drained first (a launch in flight
+// may still read the table), the allocation grows if it must, and the host copy is set only once the copy to the device succeeded.
+int mg_device_table::upload(mg_context *ctx, const char *who, const void *data, size_t bytes, size_t reserve, size_t behind) {
+    const size_t need = behind ? ((bytes + 255) & ~(size_t)255) + behind : bytes;
+    if (dev && cap >= need && host.size() == bytes && memcmp(host.data(), data, bytes) == 0) return MG_OK;
+    MG_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    host.clear();
+    if (cap < need) {
+        if (dev) (void)hipFree(dev);
+        dev = nullptr;
+        cap = 0;
+        const size_t want = std::max(need, reserve);
+        if (hipMalloc(&dev, want) != hipSuccess) {
+            (void)hipGetLastError();
+            dev = nullptr;
+            mg_set_error("%s: cannot allocate %zu bytes of device memory", who, want);
+            return MG_ERR_OUT_OF_MEMORY;
+        }
+        cap = want;
+    }
+    MG_HIP_CHECK(hipMemcpy(dev, data, bytes, hipMemcpyHostToDevice));
+    host.assign((const unsigned char *)data, (const unsigned char *)data + bytes);
+    uploads++;
+    return MG_OK;
+}
+
+extern "C" int mg_context_table_uploads(mg_context *ctx, int which, int64_t *uploads) {
+    MG_REQUIRE(ctx && uploads && which >= 0 && which < MG_TABLE_COUNT, "mg_context_table_uploads: bad arguments");
+    *uploads = ctx->tab[which].uploads;
+    return MG_OK;
+}
+
+extern "C" int mg_walk_time_table_uploads(mg_context *ctx, int64_t *uploads) { return mg_context_table_uploads(ctx, MG_TABLE_WALK_TIME, uploads); }
 
 extern "C" int mg_context_set_stream(mg_context *ctx, void *stream) {
     MG_REQUIRE(ctx != nullptr, "mg_context_set_stream: ctx is NULL");
@@ -1248,10 +1278,10 @@ extern "C" int mg_back_project_frames(mg_primitive *p, const mg_time_grid *g, co
     } else {
         use_mfma = g->mfma_ok && B >= 8;
     }
-    if (use_mfma) return mg_launch_frames_mfma(p, g, lat, dt, B, ld, out, nullptr, 0);   // timed by events attached to the launch
-    mg_prof_begin(p->ctx, 0);
+    if (use_mfma) return mg_launch_frames_mfma(p, g, lat, dt, B, ld, out, nullptr, MG_PROF_FRAMES);   // timed by events attached to the launch
+    mg_prof_begin(p->ctx, MG_PROF_FRAMES);
     rc = mg_launch_frames_direct(p, g, lat, dt, B, ld, out, false);
-    mg_prof_end(p->ctx, 0);
+    mg_prof_end(p->ctx, MG_PROF_FRAMES);
     return rc;
 }
 
@@ -1263,9 +1293,9 @@ extern "C" int mg_back_project_frames_f64(mg_primitive *p, const mg_time_grid *g
     MG_REQUIRE(g->prim == p, "mg_back_project_frames_f64: grid belongs to another primitive");
     if (B == 0 || g->T == 0) return MG_OK;
     MG_REQUIRE(out != nullptr, "mg_back_project_frames_f64: frames pointer is NULL");
-    mg_prof_begin(p->ctx, 0);
+    mg_prof_begin(p->ctx, MG_PROF_FRAMES);
     rc = mg_launch_frames_direct(p, g, lat, dt, B, ld, out, true);
-    mg_prof_end(p->ctx, 0);
+    mg_prof_end(p->ctx, MG_PROF_FRAMES);
     return rc;
 }
 
@@ -1289,9 +1319,9 @@ extern "C" int mg_spline_evaluate(mg_primitive *p, const mg_time_grid *g, const 
     if (n == 0 || g->T == 0) return MG_OK;
     MG_REQUIRE(coeffs && out, "mg_spline_evaluate: NULL pointer");
     { int rc = mg_use_device(p->ctx); if (rc != MG_OK) return rc; }
-    mg_prof_begin(p->ctx, 5);
+    mg_prof_begin(p->ctx, MG_PROF_SPLINE_EVALUATE);
     int rc = mg_launch_spline_eval(p, g, coeffs, n, out);
-    mg_prof_end(p->ctx, 5);
+    mg_prof_end(p->ctx, MG_PROF_SPLINE_EVALUATE);
     return rc;
 }
 
@@ -1302,9 +1332,9 @@ extern "C" int mg_gmm_log_prob(mg_primitive *p, const void *x, int xdt, int64_t 
     MG_REQUIRE(odt == MG_F32 || odt == MG_F64, "mg_gmm_log_prob: bad output dtype %d", odt);
     if (B == 0) return MG_OK;
     MG_REQUIRE(out != nullptr, "mg_gmm_log_prob: output pointer is NULL");
-    mg_prof_begin(p->ctx, 1);
+    mg_prof_begin(p->ctx, MG_PROF_GMM_LOG_PROB);
     rc = mg_launch_gmm_logp(p, x, xdt, B, ld, out, odt);
-    mg_prof_end(p->ctx, 1);
+    mg_prof_end(p->ctx, MG_PROF_GMM_LOG_PROB);
     return rc;
 }
 
@@ -1385,9 +1415,9 @@ extern "C" int mg_gmm_sample_rows(mg_primitive *p, int64_t n, const int64_t *cou
     const int64_t tile0 = tile_of(row_begin), tile_end = tile_of(row_begin + row_count - 1) + 1;
     int rc;
     if (mg_gmm_sample_takes_host_prefix(p)) {   // prefix sums travel as a kernel argument: nothing to upload or wait for
-        mg_prof_begin(p->ctx, 4);
+        mg_prof_begin(p->ctx, MG_PROF_GMM_SAMPLE);
         rc = mg_launch_gmm_sample(p, n, nullptr, cum.data(), tile_end, seed, x, xdt, ld, comp, tile0, row_begin, row_begin + row_count);
-        mg_prof_end(p->ctx, 4);
+        mg_prof_end(p->ctx, MG_PROF_GMM_SAMPLE);
         return rc;
     }
     void *scr = nullptr;
@@ -1395,9 +1425,9 @@ extern "C" int mg_gmm_sample_rows(mg_primitive *p, int64_t n, const int64_t *cou
     if (rc != MG_OK) return rc;
     MG_HIP_CHECK(hipMemcpyAsync(scr, cum.data(), cum.size() * 8, hipMemcpyHostToDevice, p->ctx->stream));
     MG_HIP_CHECK(hipStreamSynchronize(p->ctx->stream));  // cum is a stack-lifetime host buffer
-    mg_prof_begin(p->ctx, 4);
+    mg_prof_begin(p->ctx, MG_PROF_GMM_SAMPLE);
     rc = mg_launch_gmm_sample(p, n, (const int64_t *)scr, nullptr, tile_end, seed, x, xdt, ld, comp, tile0, row_begin, row_begin + row_count);
-    mg_prof_end(p->ctx, 4);
+    mg_prof_end(p->ctx, MG_PROF_GMM_SAMPLE);
     return rc;
 }
 extern "C" int mg_gmm_sample(mg_primitive *p, int64_t n, const int64_t *counts, uint64_t seed, void *x, int xdt,
@@ -1767,9 +1797,9 @@ extern "C" int mg_score_constraints(mg_primitive *p, const mg_constraint_set *cs
     MG_REQUIRE(odt == MG_F32 || odt == MG_F64, "mg_score_constraints: bad output dtype %d", odt);
     if (B == 0) return MG_OK;
     MG_REQUIRE(out != nullptr, "mg_score_constraints: output pointer is NULL");
-    mg_prof_begin(p->ctx, 2);
+    mg_prof_begin(p->ctx, MG_PROF_SCORE_CONSTRAINTS);
     rc = mg_launch_score(p, cs, lat, dt, B, ld, out, odt, nullptr);
-    mg_prof_end(p->ctx, 2);
+    mg_prof_end(p->ctx, MG_PROF_SCORE_CONSTRAINTS);
     return rc;
 }
 
@@ -1785,9 +1815,9 @@ extern "C" int mg_objective_error_and_naturalness(mg_primitive *p, const mg_cons
     if (B == 0) return MG_OK;
     MG_REQUIRE(logp_out || err_out || obj_out, "mg_objective_error_and_naturalness: no output pointer");
     if (mg_objective_can_fuse(p, cs)) {
-        mg_prof_begin(p->ctx, 1);
+        mg_prof_begin(p->ctx, MG_PROF_GMM_LOG_PROB);
         rc = mg_launch_objective(p, cs, lat, dt, B, ld, error_scale, quality_scale, logp_out, err_out, obj_out);
-        mg_prof_end(p->ctx, 1);
+        mg_prof_end(p->ctx, MG_PROF_GMM_LOG_PROB);
         return rc;
     }
     mg_set_error("mg_objective_error_and_naturalness: this mixture / constraint set does not run on the one-launch kernel (mixture over time "
@@ -1802,9 +1832,9 @@ extern "C" int mg_score_constraint_residuals(mg_primitive *p, const mg_constrain
     MG_REQUIRE(cs && cs->prim == p, "mg_score_constraint_residuals: constraint set is NULL or belongs to another primitive");
     if (B == 0 || cs->n == 0) return MG_OK;
     MG_REQUIRE(res != nullptr, "mg_score_constraint_residuals: output pointer is NULL");
-    mg_prof_begin(p->ctx, 2);
+    mg_prof_begin(p->ctx, MG_PROF_SCORE_CONSTRAINTS);
     rc = mg_launch_score(p, cs, lat, dt, B, ld, nullptr, MG_F64, res);
-    mg_prof_end(p->ctx, 2);
+    mg_prof_end(p->ctx, MG_PROF_SCORE_CONSTRAINTS);
     return rc;
 }
 
@@ -1818,9 +1848,9 @@ extern "C" int mg_score_constraint_residuals_chained(mg_primitive *p, const mg_c
     MG_REQUIRE(cs->d_align != nullptr && cs->align_joint >= 0, "mg_score_constraint_residuals_chained: the set needs a previous-frame alignment (its node and reference vector; the values are per candidate)");
     if (B == 0 || cs->n == 0) return MG_OK;
     MG_REQUIRE(res != nullptr && align_cand != nullptr, "mg_score_constraint_residuals_chained: NULL pointer");
-    mg_prof_begin(p->ctx, 2);
+    mg_prof_begin(p->ctx, MG_PROF_SCORE_CONSTRAINTS);
     rc = mg_launch_score(p, cs, lat, dt, B, ld, nullptr, MG_F64, res, align_cand);
-    mg_prof_end(p->ctx, 2);
+    mg_prof_end(p->ctx, MG_PROF_SCORE_CONSTRAINTS);
     return rc;
 }
 
@@ -1830,9 +1860,9 @@ extern "C" int mg_gmm_log_prob_jac(mg_primitive *p, const void *x, int xdt, int6
     MG_REQUIRE(p->K > 0, "mg_gmm_log_prob_jac: primitive has no mixture");
     if (B == 0) return MG_OK;
     MG_REQUIRE(jac != nullptr, "mg_gmm_log_prob_jac: output pointer is NULL");
-    mg_prof_begin(p->ctx, 1);
+    mg_prof_begin(p->ctx, MG_PROF_GMM_LOG_PROB);
     rc = mg_launch_gmm_jac(p, x, xdt, B, ld, jac);
-    mg_prof_end(p->ctx, 1);
+    mg_prof_end(p->ctx, MG_PROF_GMM_LOG_PROB);
     return rc;
 }
 
@@ -1840,9 +1870,9 @@ extern "C" int mg_argmin_first_dev(mg_context *ctx, const void *v, int dt, int64
     MG_REQUIRE(ctx && out_dev && n >= 0 && (n == 0 || v), "mg_argmin_first_dev: bad arguments");
     MG_REQUIRE(dt == MG_F32 || dt == MG_F64, "mg_argmin_first_dev: bad dtype %d", dt);
     { int rc0 = mg_use_device(ctx); if (rc0 != MG_OK) return rc0; }
-    mg_prof_begin(ctx, 3);
+    mg_prof_begin(ctx, MG_PROF_ARGMIN);
     int rc = mg_launch_argmin(ctx, v, dt, n, out_dev);
-    mg_prof_end(ctx, 3);
+    mg_prof_end(ctx, MG_PROF_ARGMIN);
     return rc;
 }
 
@@ -1869,12 +1899,12 @@ extern "C" int mg_step_frames_and_logp(mg_primitive *p, const void *lat, int dt,
     const mg_time_grid *g = p->canonical;
     if (B >= 8 && g->T > 0 && frames && logp && mg_frames_can_fuse_gmm(p, g, B)) {
         // one launch: the mixture is scored by the sweep waves while the pipeline of the frames kernel fills
-        return mg_launch_frames_mfma(p, g, lat, dt, B, ld, frames, logp, 0, 6);   // one kernel: slot "frames" and slot "step"
+        return mg_launch_frames_mfma(p, g, lat, dt, B, ld, frames, logp, MG_PROF_FRAMES, MG_PROF_STEP);   // one kernel: slot "frames" and slot "step"
     }
-    mg_prof_begin(ctx, 6);
+    mg_prof_begin(ctx, MG_PROF_STEP);
     rc = mg_back_project_frames(p, nullptr, lat, dt, B, ld, frames, MG_PATH_AUTO);
     if (rc == MG_OK) rc = mg_gmm_log_prob(p, lat, dt, B, ld, logp, MG_F32);
-    mg_prof_end(ctx, 6);
+    mg_prof_end(ctx, MG_PROF_STEP);
     return rc;
 }
 
@@ -2123,9 +2153,9 @@ extern "C" int mg_option_step_rows(mg_primitive *p, const mg_constraint_set *cs,
     int rc = mg_gmm_sample_rows(p, n, counts, seed, row_begin, row_count, x_dev, xdt, ld, nullptr);
     if (rc == MG_OK) rc = mg_score_constraints(p, cs, x_dev, xdt, row_count, ld, errors_dev, MG_F64);
     if (rc == MG_OK) {   // first minimum and the copy of the winner (at its full width) in one launch
-        mg_prof_begin(p->ctx, 3);
+        mg_prof_begin(p->ctx, MG_PROF_ARGMIN);
         rc = mg_launch_argmin_gather(p->ctx, errors_dev, MG_F64, row_count, result_dev, x_dev, xdt, ld, p->Lg, row_begin);
-        mg_prof_end(p->ctx, 3);
+        mg_prof_end(p->ctx, MG_PROF_ARGMIN);
     }
     return rc;
 }

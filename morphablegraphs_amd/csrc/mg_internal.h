@@ -13,7 +13,10 @@
 #define MG_ROWTILE 16       // coefficient rows per MFMA tile (M)
 #define MG_MAX_KK 16        // k-steps of 4 -> n_components <= 64 on the MFMA path
 #define MG_BLOCK 256        // threads per workgroup of the frames kernels
-#define MG_PROFILE_SLOTS 15
+// profile slots: the keys of _capi.PROFILE_SLOTS
+enum { MG_PROF_FRAMES = 0, MG_PROF_GMM_LOG_PROB, MG_PROF_SCORE_CONSTRAINTS, MG_PROF_ARGMIN, MG_PROF_GMM_SAMPLE, MG_PROF_SPLINE_EVALUATE, MG_PROF_STEP,
+       MG_PROF_OPTIONS_STEP, MG_PROF_JOINT_TRACKS, MG_PROF_FRAME_CONSTRAINTS, MG_PROF_TRAJECTORY, MG_PROF_CLUSTER_TREE_SEARCH, MG_PROF_WALK_FRAMES,
+       MG_PROF_WALK_TIME, MG_PROF_STEP_LENGTHS, MG_PROFILE_SLOTS = MG_PROF_STEP_LENGTHS + 1 };
 
 void mg_set_error(const char *fmt, ...);
 int mg_hip_fail(hipError_t e, const char *what);
@@ -39,6 +42,22 @@ struct mg_event_pair {
     bool ended;
     int slot2 = -1;   // the same duration counted into a second slot as well (the fused step: "frames" and "step")
 };
+
+// A per-call descriptor table on the device and its host copy (mg_host.hip): rewritten only when a call's table differs from the last one's
+struct mg_device_table {
+    void *dev = nullptr;
+    size_t cap = 0;
+    std::vector<unsigned char> host;   // what the device holds; empty after a failed upload
+    int64_t uploads = 0;
+    // reserve: allocate at least this much when (re)allocating; behind: scratch bytes kept after the table, 256-aligned
+    int upload(mg_context *ctx, const char *who, const void *data, size_t bytes, size_t reserve = 0, size_t behind = 0);
+    char *base() const { return (char *)dev; }
+    char *scratch() const { return (char *)dev + ((host.size() + 255) & ~(size_t)255); }
+};
+
+// bits of mg_context::attr_traj: kernels whose dynamic-LDS limit is already raised on this context's device
+enum { MG_LDS_TRAJECTORY = 1, MG_LDS_TIMEWARP = 2, MG_LDS_JOINT_TRACKS = 4, MG_LDS_FRAME_CONSTRAINTS = 8, MG_LDS_WALK_FRAMES = 16, MG_LDS_WALK_SCORE = 32,
+       MG_LDS_WALK_TIME = 64, MG_LDS_STEP_LENGTH_F32 = 128, MG_LDS_STEP_LENGTH_F64 = 256 };
 
 struct mg_context {
     int device = 0;
@@ -75,17 +94,14 @@ struct mg_context {
     std::vector<std::pair<void *, size_t>> vmm_parked;
     hipStream_t side[4] = {nullptr, nullptr, nullptr, nullptr};   // mg_options_step: the options of a step are independent chains of small
     hipEvent_t side_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // launches; four of them run side by side ([4]: the fork)
-    // mg_options_step as one launch (mg_options.hip): the per-option constants on the device and their host copy, the
-    // per-option arrival counters and one {value, index} partial per workgroup
-    void *fused_tab_dev = nullptr;
-    std::vector<unsigned char> fused_tab_host;
+    // mg_options_step as one launch (mg_options.hip): the per-option arrival counters and one {value, index} partial per workgroup
+    // (the per-option constants: tab[MG_TABLE_FUSED])
     void *fused_counters = nullptr, *fused_partials = nullptr;
     void *fused_dyn_dev = nullptr;   // a step's per-option values where the device draws the component counts itself
     // ... two slots of them: the step's kernel also draws the counts the NEXT step will want if its seeds are this step's + 1 (a planner
     // counts its steps), so that step needs no counts kernel in front; what was drawn for whom:
     struct { bool valid = false; int32_t n_options = 0, slot = 0; int64_t n = 0; uint64_t seeds[24] = {0}; const void *prims[24] = {nullptr}; } fused_next;
-    unsigned attr_gmm_lds = 0, attr_traj = 0;   // dynamic-LDS attributes already set for this context's device (bit per instantiation;
-                                                // attr_traj: 1 trajectory, 2 time warp, 4 joint tracks, 8 frame constraints, 16 graph walk, 32 walk objective, 64 walk time objective, 128 / 256 step lengths of float32 / float64 latents)
+    unsigned attr_gmm_lds = 0, attr_traj = 0;   // dynamic-LDS limits already raised (attr_gmm_lds: bit per KK instantiation; attr_traj: MG_LDS_*)
     unsigned long long fused_seq = 0;   // sequence number of the planner steps whose records the kernel leaves in pinned memory
     int fused_partials_n = 0;
     // the output arena (mg_placement.hip): buffers that went through the placement probe, sub-allocated in 2 MiB granules
@@ -109,22 +125,8 @@ struct mg_context {
     size_t lists_bytes = 0, lists_counters_off = 0;
     void *rccl_comm = nullptr;      // ncclComm_t after mg_dist_init
     int dist_rank = 0, dist_ranks = 1;
-    void *tree_tab_dev = nullptr;   // mg_cluster_tree_search: the per-search descriptors on the device and their host copy
-    size_t tree_tab_cap = 0;        // (rewritten only when a call's table differs from the last one's)
-    std::vector<unsigned char> tree_tab_host;
-    void *walk_tab_dev = nullptr;   // mg_walk_frames: the call's step table, offsets and lengths (rewritten only when they differ from the last
-    size_t walk_tab_cap = 0;        // call's) and, behind them, the steps' transforms between its two launches
-    std::vector<unsigned char> walk_tab_host;
-    void *wscore_tab_dev = nullptr; // mg_score_walk_residuals: the call's step table (rewritten only when it differs from the last call's)
-    size_t wscore_tab_cap = 0;
-    std::vector<unsigned char> wscore_tab_host;
-    void *wtime_tab_dev = nullptr;  // mg_score_walk_time: the call's steps, constraints and their order by step (rewritten only when they differ
-    size_t wtime_tab_cap = 0;       // from the last call's)
-    std::vector<unsigned char> wtime_tab_host;
-    int64_t wtime_tab_uploads = 0;  // how often that table went to the device (mg_walk_time_table_uploads)
-    void *slen_tab_dev = nullptr;   // mg_step_lengths: the call's items as the kernel reads them (rewritten only when they differ from the
-    size_t slen_tab_cap = 0;        // last call's)
-    std::vector<unsigned char> slen_tab_host;
+    // the entry points' per-call tables (MG_TABLE_*); MG_TABLE_WALK keeps the steps' transforms between mg_walk_frames' two launches behind it
+    mg_device_table tab[MG_TABLE_COUNT];
 };
 void mg_dev_free(mg_context *ctx, void *p);   // hipFree unless p lives in the context's arena
 
@@ -135,6 +137,23 @@ void mg_prof_begin(mg_context *ctx, int slot);
 bool mg_prof_kernel(mg_context *ctx, int slot, int slot2, hipEvent_t *start, hipEvent_t *stop);
 void mg_prof_end(mg_context *ctx, int slot);
 int mg_prof_resolve(mg_context *ctx);
+
+// Raise the dynamic-LDS limit of every kernel given to `bytes`; the first failure, for MG_HIP_CHECK
+template <typename... K> inline hipError_t mg_lds_opt_in(int bytes, K... kernels) {
+    hipError_t e = hipSuccess;
+    (void)(((e = hipFuncSetAttribute((const void *)kernels, hipFuncAttributeMaxDynamicSharedMemorySize, bytes)) == hipSuccess) && ...);
+    return e;
+}
+// ... once per context: `bit` of `done` (ctx->attr_gmm_lds), or of ctx->attr_traj (MG_LDS_*)
+template <typename... K> inline hipError_t mg_lds_opt_in_once(unsigned &done, unsigned bit, int bytes, K... kernels) {
+    if (done & bit) return hipSuccess;
+    const hipError_t e = mg_lds_opt_in(bytes, kernels...);
+    if (e == hipSuccess) done |= bit;
+    return e;
+}
+template <typename... K> inline hipError_t mg_lds_opt_in_once(mg_context *ctx, unsigned bit, int bytes, K... kernels) {
+    return mg_lds_opt_in_once(ctx->attr_traj, bit, bytes, kernels...);
+}
 
 // One chunk of a time grid handled by one workgroup of the MFMA kernel.
 #define MG_MAX_WI 11         // basis functions per chunk window (11 x 3 root rows still span <= 3 row tiles of 16)

@@ -502,7 +502,7 @@ extern "C" int mg_kmeans_segments(mg_context *ctx, const double *points_dev, int
     }
     MG_HIP_CHECK(hipMemsetAsync(a.labels, 0xFF, (size_t)n_init * n_pos * 4, st));   // label -1: every label of iteration 0 changes
     // what this call needs, not the whole 160 KiB: __syncthreads_count keeps a static word in the LDS, and static + dynamic past 160 KiB is refused
-    if (lds > 64 * 1024) MG_HIP_CHECK(hipFuncSetAttribute((const void *)mg_kmeans_lloyd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if (lds > 64 * 1024) MG_HIP_CHECK(mg_lds_opt_in((int)lds, mg_kmeans_lloyd_kernel));
     active = tiles;
     // every unit needs at most max_iter iterations and one final pass
     while (launches < max_iter + 1 && !active.empty()) {

@@ -381,10 +381,8 @@ __global__ __launch_bounds__(256, MG_FUSED_WAVES_PER_SIMD) void mg_options_fused
 }
 
 int mg_options_fused_attributes() {
-    MG_HIP_CHECK(hipFuncSetAttribute((const void *)mg_options_fused_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024));
-    MG_HIP_CHECK(hipFuncSetAttribute((const void *)mg_options_fused_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024));
-    MG_HIP_CHECK(hipFuncSetAttribute((const void *)mg_options_fused_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024));
-    MG_HIP_CHECK(hipFuncSetAttribute((const void *)mg_options_fused_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024));
+    MG_HIP_CHECK(mg_lds_opt_in(160 * 1024 - 1024, mg_options_fused_kernel<true, false>, mg_options_fused_kernel<false, false>, mg_options_fused_kernel<true, true>,
+                               mg_options_fused_kernel<false, true>));
     return MG_OK;
 }
 
@@ -469,13 +467,9 @@ int mg_launch_options_fused(int32_t n_options, mg_primitive *const *prims, const
     dyn.fenced = ctx->opt[MG_OPT_OPTIONS_STEP] == 3 ? 1 : 0;
     const int total_wg = dyn.wg0[n_options];
     // the static table: uploaded when it differs from the one on the device (a planner reuses its buffers and sets, so: rarely)
-    const size_t tab_bytes = tab.size() * sizeof(mg_fused_static);
-    if (!ctx->fused_tab_dev || ctx->fused_tab_host.size() != tab_bytes || memcmp(ctx->fused_tab_host.data(), tab.data(), tab_bytes) != 0) {
-        MG_HIP_CHECK(hipStreamSynchronize(ctx->stream));   // no launch may still be reading the old table
-        if (!ctx->fused_tab_dev) MG_HIP_CHECK(hipMalloc(&ctx->fused_tab_dev, MG_FUSED_MAX_OPTIONS * sizeof(mg_fused_static)));
-        MG_HIP_CHECK(hipMemcpy(ctx->fused_tab_dev, tab.data(), tab_bytes, hipMemcpyHostToDevice));
-        ctx->fused_tab_host.assign((const unsigned char *)tab.data(), (const unsigned char *)tab.data() + tab_bytes);
-    }
+    mg_device_table &dt = ctx->tab[MG_TABLE_FUSED];
+    const int rc = dt.upload(ctx, "mg_options_step", tab.data(), tab.size() * sizeof(mg_fused_static), MG_FUSED_MAX_OPTIONS * sizeof(mg_fused_static));
+    if (rc != MG_OK) return rc;
     if (!ctx->fused_counters) {
         MG_HIP_CHECK(hipMalloc(&ctx->fused_counters, MG_FUSED_MAX_OPTIONS * sizeof(int32_t)));
         MG_HIP_CHECK(hipMemset(ctx->fused_counters, 0, MG_FUSED_MAX_OPTIONS * sizeof(int32_t)));
@@ -490,8 +484,8 @@ int mg_launch_options_fused(int32_t n_options, mg_primitive *const *prims, const
     }
     const size_t lds = (size_t)4 * wave_doubles * 8;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    const bool timed = mg_prof_kernel(ctx, 7, -1, &ev0, &ev1);
-    const mg_fused_static *tabd = (const mg_fused_static *)ctx->fused_tab_dev;
+    const bool timed = mg_prof_kernel(ctx, MG_PROF_OPTIONS_STEP, -1, &ev0, &ev1);
+    const mg_fused_static *tabd = (const mg_fused_static *)dt.base();
     mg_fused_partial *part = (mg_fused_partial *)ctx->fused_partials;
     int32_t *ctr = (int32_t *)ctx->fused_counters;
     if (dev_counts) {

@@ -188,12 +188,8 @@ static int mg_launch_score_mfma_kk(mg_primitive *p, const mg_constraint_set *cs,
     if (lds > 150 * 1024) return MG_ERR_UNSUPPORTED;
     const int64_t grid = (a.B + 63) / 64;
     if (grid > 0x7fffffff) return MG_ERR_UNSUPPORTED;
-    if (lds > 64 * 1024) {
-        MG_HIP_CHECK(hipFuncSetAttribute((const void *)mg_score_mfma_kernel<KK, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        MG_HIP_CHECK(hipFuncSetAttribute((const void *)mg_score_mfma_kernel<KK, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        MG_HIP_CHECK(hipFuncSetAttribute((const void *)mg_score_mfma_kernel<KK, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        MG_HIP_CHECK(hipFuncSetAttribute((const void *)mg_score_mfma_kernel<KK, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    }
+    if (lds > 64 * 1024) MG_HIP_CHECK(mg_lds_opt_in(160 * 1024, mg_score_mfma_kernel<KK, true, true>, mg_score_mfma_kernel<KK, true, false>, mg_score_mfma_kernel<KK, false, true>,
+                                                    mg_score_mfma_kernel<KK, false, false>));
     if (lf && of) hipLaunchKernelGGL((mg_score_mfma_kernel<KK, true, true>), dim3((int)grid), dim3(256), lds, st, a, cs->d_Wpack, cs->d_bpad, cs->RT);
     else if (lf) hipLaunchKernelGGL((mg_score_mfma_kernel<KK, true, false>), dim3((int)grid), dim3(256), lds, st, a, cs->d_Wpack, cs->d_bpad, cs->RT);
     else if (of) hipLaunchKernelGGL((mg_score_mfma_kernel<KK, false, true>), dim3((int)grid), dim3(256), lds, st, a, cs->d_Wpack, cs->d_bpad, cs->RT);
@@ -227,12 +223,7 @@ int mg_launch_score(mg_primitive *p, const mg_constraint_set *cs, const void *la
     if (grid > 0x7fffffff) { mg_set_error("mg_score_constraints: too many samples"); return MG_ERR_UNSUPPORTED; }
     hipStream_t st = p->ctx->stream;
     const bool lf = ldt == MG_F64, of = odt == MG_F64;
-    if (lds > 64 * 1024) {
-        MG_HIP_CHECK(hipFuncSetAttribute((const void *)mg_score_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        MG_HIP_CHECK(hipFuncSetAttribute((const void *)mg_score_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        MG_HIP_CHECK(hipFuncSetAttribute((const void *)mg_score_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        MG_HIP_CHECK(hipFuncSetAttribute((const void *)mg_score_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    }
+    if (lds > 64 * 1024) MG_HIP_CHECK(mg_lds_opt_in(160 * 1024, mg_score_kernel<true, true>, mg_score_kernel<true, false>, mg_score_kernel<false, true>, mg_score_kernel<false, false>));
     if (lf && of) hipLaunchKernelGGL((mg_score_kernel<true, true>), dim3((int)grid), dim3(MG_SC_CANDS * MG_SC_WAVES), lds, st, a);
     else if (lf) hipLaunchKernelGGL((mg_score_kernel<true, false>), dim3((int)grid), dim3(MG_SC_CANDS * MG_SC_WAVES), lds, st, a);
     else if (of) hipLaunchKernelGGL((mg_score_kernel<false, true>), dim3((int)grid), dim3(MG_SC_CANDS * MG_SC_WAVES), lds, st, a);

@@ -224,7 +224,7 @@ extern "C" int mg_keyframe_distances(mg_context *ctx, const double *clouds_dev, 
     MG_REQUIRE_AS(!flag, MG_ERR_INVALID_ARGUMENT, "mg_keyframe_distances: the point clouds or the keyframes hold non-finite values");
     const size_t lds = ((size_t)(SEG_FRAMES + n_keyframes) * ((3 * n_joints) | 1) + DTW_MAX_JOINTS + 2 * SEG_MAX_KEYFRAMES + 1) * 8;   // at most 111 816 bytes
     if (lds > 64 * 1024)
-        MG_HIP_CHECK(hipFuncSetAttribute((const void *)keyframe_distances_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        MG_HIP_CHECK(mg_lds_opt_in((int)lds, keyframe_distances_kernel));
     hipLaunchKernelGGL(keyframe_distances_kernel, dim3((unsigned)((total + SEG_FRAMES - 1) / SEG_FRAMES)), dim3(SEG_FRAMES), lds, ctx->stream, clouds_dev,
                        total, n_joints, keyframes_dev, n_keyframes, (const double *)blk.w, dist_dev);
     MG_HIP_CHECK(hipGetLastError());

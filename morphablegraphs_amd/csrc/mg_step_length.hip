@@ -15,7 +15,7 @@
 //
 // A candidate's values are computed by statements that see nothing but its own row, so they depend on neither the batch nor the other
 // items.  Which workgroup serves which item is a prefix table (first workgroup of every item) searched by bisection; the items of a
-// call travel in a device table of the context (ctx->slen_tab_dev), rewritten only when it differs from the last call's, and a launch
+// call travel in a device table of the context (ctx->tab[MG_TABLE_STEP_LENGTH]), rewritten only when it differs from the last call's, and a launch
 // takes MG_STEP_LENGTH_MAX_ITEMS of them: a call with more goes through the table in slices.
 #include <cmath>
 #include <cstring>
@@ -28,7 +28,6 @@
 
 #define MG_SLEN_TILE 16                  // candidates per workgroup
 #define MG_SLEN_LDS_MAX (150 * 1024)
-#define MG_SLEN_PROFILE_SLOT 14
 
 struct mg_slen_item {                    // one non-empty item as the kernel reads it
     const double *Et, *mean;             // [L][R], (R): E' and mean' (scaled by translation_maxima), row = i * D + d
@@ -159,29 +158,6 @@ __global__ __launch_bounds__(256) void mg_step_length_kernel(const mg_slen_args 
     }
 }
 
-// the call's table on the device: rewritten only when it differs from the last call's
-static int mg_slen_table_upload(mg_context *ctx, const std::vector<unsigned char> &tab) {
-    const bool same = ctx->slen_tab_dev && ctx->slen_tab_host.size() == tab.size() && memcmp(ctx->slen_tab_host.data(), tab.data(), tab.size()) == 0;
-    if (same) return MG_OK;
-    MG_HIP_CHECK(hipStreamSynchronize(ctx->stream));   // no launch in flight reads the table being replaced
-    if (ctx->slen_tab_cap < tab.size()) {
-        if (ctx->slen_tab_dev) { (void)hipFree(ctx->slen_tab_dev); ctx->slen_tab_dev = nullptr; ctx->slen_tab_cap = 0; }
-        ctx->slen_tab_host.clear();
-        const size_t cap = std::max(tab.size() * 2, (size_t)32 * 1024);
-        if (hipMalloc(&ctx->slen_tab_dev, cap) != hipSuccess) {
-            (void)hipGetLastError();
-            ctx->slen_tab_dev = nullptr;
-            mg_set_error("mg_step_lengths: cannot allocate %zu bytes of device memory", cap);
-            return MG_ERR_OUT_OF_MEMORY;
-        }
-        ctx->slen_tab_cap = cap;
-    }
-    ctx->slen_tab_host.clear();
-    MG_HIP_CHECK(hipMemcpy(ctx->slen_tab_dev, tab.data(), tab.size(), hipMemcpyHostToDevice));
-    ctx->slen_tab_host = tab;
-    return MG_OK;
-}
-
 #define MG_SLEN_REQUIRE(cond, ...) MG_REQUIRE_AS(cond, MG_ERR_INVALID_ARGUMENT, __VA_ARGS__)
 #define MG_SLEN_REFUSE(cond, ...) MG_REQUIRE_AS(!(cond), MG_ERR_UNSUPPORTED, __VA_ARGS__)
 
@@ -250,26 +226,22 @@ extern "C" int mg_step_lengths(int32_t n_items, const mg_step_length_item *items
     }
     if (ds.empty()) return MG_OK;
     MG_HIP_CHECK(hipSetDevice(ctx->device));
-    std::vector<unsigned char> tab(ds.size() * sizeof(mg_slen_item));
-    memcpy(tab.data(), ds.data(), tab.size());
-    rc = mg_slen_table_upload(ctx, tab);
+    mg_device_table &dt = ctx->tab[MG_TABLE_STEP_LENGTH];
+    const size_t tab_bytes = ds.size() * sizeof(mg_slen_item);
+    rc = dt.upload(ctx, "mg_step_lengths", ds.data(), tab_bytes, std::max(tab_bytes * 2, (size_t)32 * 1024));
     if (rc != MG_OK) return rc;
-    const unsigned bit = latent_dtype == MG_F64 ? 256u : 128u;
     for (const launch &l : launches) {
         mg_slen_args k;
-        k.items = (const mg_slen_item *)ctx->slen_tab_dev + l.first;
+        k.items = (const mg_slen_item *)dt.base() + l.first;
         k.n_items = l.n_items;
-        if (l.lds > 64 * 1024 && !(ctx->attr_traj & bit)) {
-            if (latent_dtype == MG_F64)
-                MG_HIP_CHECK(hipFuncSetAttribute((const void *)mg_step_length_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            else
-                MG_HIP_CHECK(hipFuncSetAttribute((const void *)mg_step_length_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            ctx->attr_traj |= bit;
+        if (l.lds > 64 * 1024) {
+            if (latent_dtype == MG_F64) MG_HIP_CHECK(mg_lds_opt_in_once(ctx, MG_LDS_STEP_LENGTH_F64, 160 * 1024, mg_step_length_kernel<true>));
+            else MG_HIP_CHECK(mg_lds_opt_in_once(ctx, MG_LDS_STEP_LENGTH_F32, 160 * 1024, mg_step_length_kernel<false>));
         }
-        mg_prof_begin(ctx, MG_SLEN_PROFILE_SLOT);
+        mg_prof_begin(ctx, MG_PROF_STEP_LENGTHS);
         if (latent_dtype == MG_F64) hipLaunchKernelGGL(mg_step_length_kernel<true>, dim3((unsigned)l.grid), dim3(256), l.lds, ctx->stream, k);
         else hipLaunchKernelGGL(mg_step_length_kernel<false>, dim3((unsigned)l.grid), dim3(256), l.lds, ctx->stream, k);
-        mg_prof_end(ctx, MG_SLEN_PROFILE_SLOT);
+        mg_prof_end(ctx, MG_PROF_STEP_LENGTHS);
         MG_HIP_CHECK(hipGetLastError());
     }
     return MG_OK;

@@ -168,18 +168,17 @@ __global__ __launch_bounds__(MG_FA_BLOCK) void mg_frames_at_kernel(const double 
     }
 }
 
+// (a property of kernel AND device: once per context)
+static hipError_t mg_tw_lds_opt_in(mg_context *ctx) {
+    return mg_lds_opt_in_once(ctx, MG_LDS_TIMEWARP, 160 * 1024, mg_timewarp_kernel, mg_frames_at_kernel<true, true>, mg_frames_at_kernel<true, false>,
+                              mg_frames_at_kernel<false, true>, mg_frames_at_kernel<false, false>);
+}
+
 int mg_launch_timewarp(mg_primitive *p, const void *gamma, int gdt, int64_t B, int64_t ld, double speed, double *times, int32_t *lens, int32_t t_cap,
                        int64_t row_pitch, double *canonical_out) {
     const size_t lds = (size_t)4 * p->F * 8;
     if (p->F < 4 || p->F > MG_TW_MAX_F) { mg_set_error("mg_time_function_sample: %d canonical frames (4 .. %d supported)", p->F, MG_TW_MAX_F); return MG_ERR_UNSUPPORTED; }
-    if (!(p->ctx->attr_traj & 2u)) {
-        MG_HIP_CHECK(hipFuncSetAttribute((const void *)mg_timewarp_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        MG_HIP_CHECK(hipFuncSetAttribute((const void *)mg_frames_at_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        MG_HIP_CHECK(hipFuncSetAttribute((const void *)mg_frames_at_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        MG_HIP_CHECK(hipFuncSetAttribute((const void *)mg_frames_at_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        MG_HIP_CHECK(hipFuncSetAttribute((const void *)mg_frames_at_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        p->ctx->attr_traj |= 2u;
-    }
+    MG_HIP_CHECK(mg_tw_lds_opt_in(p->ctx));
     hipLaunchKernelGGL(mg_timewarp_kernel, dim3((unsigned)B), dim3(MG_TW_BLOCK), lds, p->ctx->stream, (const double *)p->d_tphi, (const double *)p->d_tmean, gamma,
                        gdt == MG_F64 ? 1 : 0, ld, (int)p->F, (int)p->Lt, 1.0 / speed, times, lens, t_cap, row_pitch, canonical_out);
     MG_HIP_CHECK(hipGetLastError());
@@ -193,14 +192,7 @@ int mg_launch_frames_at(mg_primitive *p, const void *lat, int ldt, int64_t B, in
         mg_set_error("mg_back_project_frames_at: %d control-point rows + %d time samples per candidate do not fit LDS", p->R, t_cap);
         return MG_ERR_UNSUPPORTED;
     }
-    if (!(p->ctx->attr_traj & 2u)) {
-        MG_HIP_CHECK(hipFuncSetAttribute((const void *)mg_timewarp_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        MG_HIP_CHECK(hipFuncSetAttribute((const void *)mg_frames_at_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        MG_HIP_CHECK(hipFuncSetAttribute((const void *)mg_frames_at_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        MG_HIP_CHECK(hipFuncSetAttribute((const void *)mg_frames_at_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        MG_HIP_CHECK(hipFuncSetAttribute((const void *)mg_frames_at_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        p->ctx->attr_traj |= 2u;
-    }
+    MG_HIP_CHECK(mg_tw_lds_opt_in(p->ctx));
     const bool lf = ldt == MG_F64, of = odt == MG_F64;
     hipStream_t st = p->ctx->stream;
 #define MG_FA_ARGS (const double *)p->d_Et64, (const double *)p->d_mean, (const double *)p->d_knots, lat, ld, (int)p->L, (int)p->R, (int)p->D, (int)p->NB, times, lens, t_cap, out

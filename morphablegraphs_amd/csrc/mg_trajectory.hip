@@ -546,6 +546,11 @@ static int mg_traj_fill_args(const char *who, mg_primitive *p, const mg_trajecto
     return MG_OK;
 }
 
+// (a property of kernel AND device: once per context, not per process -- ADVICE r3)
+static hipError_t mg_traj_lds_opt_in(mg_context *ctx) {
+    return mg_lds_opt_in_once(ctx, MG_LDS_TRAJECTORY, 160 * 1024, mg_trajectory_kernel<false>, mg_trajectory_kernel<true>);
+}
+
 extern "C" int mg_score_trajectory(mg_primitive *p, const mg_trajectory *t, const mg_time_grid *g, const void *lat, int dt, int64_t B,
                                    int64_t ld, double min_u, double weight, const mg_alignment_desc *al, double *errors_dev,
                                    int accumulate, double *residuals_dev) {
@@ -558,12 +563,7 @@ extern "C" int mg_score_trajectory(mg_primitive *p, const mg_trajectory *t, cons
     const size_t poly_bytes = ((size_t)t->n_seg * 12 + 3) * 8;
     const bool poly_lds = lds + poly_bytes <= 158 * 1024;
     if (poly_lds) lds += poly_bytes;
-    // (a property of kernel AND device: once per context, not per process -- ADVICE r3)
-    if (!(p->ctx->attr_traj & 1u)) {
-        MG_HIP_CHECK(hipFuncSetAttribute((const void *)mg_trajectory_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        MG_HIP_CHECK(hipFuncSetAttribute((const void *)mg_trajectory_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        p->ctx->attr_traj |= 1u;
-    }
+    MG_HIP_CHECK(mg_traj_lds_opt_in(p->ctx));
     const int grid = (int)((B + MG_TRAJ_BLOCK - 1) / MG_TRAJ_BLOCK);
     int lanes = mg_traj_lanes(p->ctx, B, B);
     const int coop_cands = MG_TRAJ_COOP_BLOCK / std::max(lanes, 1);
@@ -572,13 +572,13 @@ extern "C" int mg_score_trajectory(mg_primitive *p, const mg_trajectory *t, cons
     const size_t stream_lds = (size_t)p->L * MG_TRAJ_BLOCK * 8 + poly_bytes;
     const dim3 coop_grid((unsigned)((B + coop_cands - 1) / coop_cands));
     if (lanes == 1 && stream_lds <= 60 * 1024 && a.search == 0) { const int rcp = mg_traj_paths(p->ctx, (size_t)B * a.T * 24, &a.paths); if (rcp != MG_OK) return rcp; }
-    mg_prof_begin(p->ctx, 10);
+    mg_prof_begin(p->ctx, MG_PROF_TRAJECTORY);
     if (lanes == 8) hipLaunchKernelGGL(mg_trajectory_coop_kernel<8>, coop_grid, dim3(MG_TRAJ_COOP_BLOCK), coop_lds, p->ctx->stream, a);
     else if (lanes == 4) hipLaunchKernelGGL(mg_trajectory_coop_kernel<4>, coop_grid, dim3(MG_TRAJ_COOP_BLOCK), coop_lds, p->ctx->stream, a);
     else if (stream_lds <= 60 * 1024) hipLaunchKernelGGL(mg_trajectory_stream_kernel, dim3(grid), dim3(MG_TRAJ_BLOCK), stream_lds, p->ctx->stream, a);
     else if (poly_lds) hipLaunchKernelGGL(mg_trajectory_kernel<true>, dim3(grid), dim3(MG_TRAJ_BLOCK), lds, p->ctx->stream, a);
     else hipLaunchKernelGGL(mg_trajectory_kernel<false>, dim3(grid), dim3(MG_TRAJ_BLOCK), lds, p->ctx->stream, a);
-    mg_prof_end(p->ctx, 10);
+    mg_prof_end(p->ctx, MG_PROF_TRAJECTORY);
     MG_HIP_CHECK(hipGetLastError());
     return MG_OK;
 }
@@ -642,11 +642,11 @@ extern "C" int mg_score_trajectories(int32_t n, mg_primitive *const *prims, cons
             off = 0;
             for (int i = 0; i < m.n; i++) { m.a[i].paths = base + off; off += (size_t)B * m.a[i].T * 3; }
         }
-        mg_prof_begin(ctx, 10);
+        mg_prof_begin(ctx, MG_PROF_TRAJECTORY);
         if (lanes == 8) hipLaunchKernelGGL(mg_trajectory_coop_multi_kernel<8>, dim3((unsigned)m.wg0[m.n]), dim3(MG_TRAJ_COOP_BLOCK), lds, ctx->stream, m);
         else if (lanes == 4) hipLaunchKernelGGL(mg_trajectory_coop_multi_kernel<4>, dim3((unsigned)m.wg0[m.n]), dim3(MG_TRAJ_COOP_BLOCK), lds, ctx->stream, m);
         else hipLaunchKernelGGL(mg_trajectory_stream_multi_kernel, dim3((unsigned)m.wg0[m.n]), dim3(MG_TRAJ_BLOCK), lds, ctx->stream, m);
-        mg_prof_end(ctx, 10);
+        mg_prof_end(ctx, MG_PROF_TRAJECTORY);
         MG_HIP_CHECK(hipGetLastError());
     }
     return MG_OK;
@@ -673,18 +673,14 @@ static int mg_traj_points_launch(const char *who, mg_primitive *p, const mg_traj
     for (double &v : a.al) v = 0.0;
     const int grid = (int)((B + MG_TRAJ_BLOCK - 1) / MG_TRAJ_BLOCK);
     const size_t poly_bytes = ((size_t)t->n_seg * 12 + 3) * 8;
-    if (!(p->ctx->attr_traj & 1u)) {
-        MG_HIP_CHECK(hipFuncSetAttribute((const void *)mg_trajectory_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        MG_HIP_CHECK(hipFuncSetAttribute((const void *)mg_trajectory_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        p->ctx->attr_traj |= 1u;
-    }
-    mg_prof_begin(p->ctx, 10);
+    MG_HIP_CHECK(mg_traj_lds_opt_in(p->ctx));
+    mg_prof_begin(p->ctx, MG_PROF_TRAJECTORY);
     const int lanes = poly_bytes <= 60 * 1024 ? mg_traj_lanes(p->ctx, B, B) : 1;
     if (lanes == 8) hipLaunchKernelGGL(mg_trajectory_coop_kernel<8>, dim3((unsigned)((B + 7) / 8)), dim3(MG_TRAJ_COOP_BLOCK), poly_bytes, p->ctx->stream, a);
     else if (lanes == 4) hipLaunchKernelGGL(mg_trajectory_coop_kernel<4>, dim3((unsigned)((B + 15) / 16)), dim3(MG_TRAJ_COOP_BLOCK), poly_bytes, p->ctx->stream, a);
     else if (poly_bytes <= 158 * 1024) hipLaunchKernelGGL(mg_trajectory_kernel<true>, dim3(grid), dim3(MG_TRAJ_BLOCK), poly_bytes, p->ctx->stream, a);
     else hipLaunchKernelGGL(mg_trajectory_kernel<false>, dim3(grid), dim3(MG_TRAJ_BLOCK), 0, p->ctx->stream, a);
-    mg_prof_end(p->ctx, 10);
+    mg_prof_end(p->ctx, MG_PROF_TRAJECTORY);
     MG_HIP_CHECK(hipGetLastError());
     return MG_OK;
 }

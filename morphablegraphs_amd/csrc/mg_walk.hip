@@ -17,7 +17,7 @@
 //                           final place in 16-byte pieces.
 //
 // An unaligned step (the first one without an alignment record) goes through no transform at all: its frames are the bits of
-// mg_back_project_frames_f64 / mg_back_project_frames_at.  What grows with n_steps travels in a device table (ctx->walk_tab_dev).
+// mg_back_project_frames_f64 / mg_back_project_frames_at.  What grows with n_steps travels in a device table (ctx->tab[MG_TABLE_WALK]).
 #include <cmath>
 #include <cstring>
 
@@ -34,7 +34,6 @@
 #define MG_WALK_BLOCK 256
 #define MG_WALK_CHAIN_BLOCK 64
 #define MG_WALK_LDS_MAX (160 * 1024 - 64)
-#define MG_WALK_PROF_SLOT 12
 
 struct mg_walk_step {            // one step's constants on the device (64 bytes)
     const double *Et64, *mean, *knots;
@@ -249,30 +248,6 @@ __global__ __launch_bounds__(MG_WALK_BLOCK) void mg_walk_frames_kernel(const mg_
     }
 }
 
-// the call's table on the device: rewritten only when it differs from the last call's; the transforms' scratch lies behind it
-static int mg_walk_table_upload(mg_context *ctx, const std::vector<unsigned char> &tab, size_t xf_bytes, char **base) {
-    const size_t tab_al = (tab.size() + 255) & ~(size_t)255, need = tab_al + xf_bytes;
-    const bool same = ctx->walk_tab_dev && ctx->walk_tab_host.size() == tab.size() && memcmp(ctx->walk_tab_host.data(), tab.data(), tab.size()) == 0;
-    if (!same || ctx->walk_tab_cap < need) {
-        MG_HIP_CHECK(hipStreamSynchronize(ctx->stream));   // no launch in flight reads the table being replaced
-        if (ctx->walk_tab_cap < need) {
-            if (ctx->walk_tab_dev) { (void)hipFree(ctx->walk_tab_dev); ctx->walk_tab_dev = nullptr; ctx->walk_tab_cap = 0; }
-            ctx->walk_tab_host.clear();
-            if (hipMalloc(&ctx->walk_tab_dev, need) != hipSuccess) {
-                (void)hipGetLastError();
-                ctx->walk_tab_dev = nullptr;
-                mg_set_error("mg_walk_frames: cannot allocate %zu bytes of device memory", need);
-                return MG_ERR_OUT_OF_MEMORY;
-            }
-            ctx->walk_tab_cap = need;
-        }
-        MG_HIP_CHECK(hipMemcpy(ctx->walk_tab_dev, tab.data(), tab.size(), hipMemcpyHostToDevice));
-        ctx->walk_tab_host = tab;
-    }
-    *base = (char *)ctx->walk_tab_dev;
-    return MG_OK;
-}
-
 #define MG_WALK_REQUIRE(cond, ...) MG_REQUIRE_AS(cond, MG_ERR_INVALID_ARGUMENT, __VA_ARGS__)
 
 extern "C" int mg_walk_frames(int32_t n_steps, mg_primitive *const *prims, const int64_t *latent_offset, const void *latents_dev, int dtype,
@@ -381,22 +356,19 @@ extern "C" int mg_walk_frames(int32_t n_steps, mg_primitive *const *prims, const
     memcpy(tab.data() + off_offs, offs.data(), (size_t)nws * 8);
     if (lengths) memcpy(tab.data() + off_lens, lengths, (size_t)nws * 4);
     MG_HIP_CHECK(hipSetDevice(ctx->device));
-    char *base = nullptr;
-    int rc = mg_walk_table_upload(ctx, tab, (size_t)nws * 8 * 8, &base);
+    mg_device_table &dt = ctx->tab[MG_TABLE_WALK];
+    int rc = dt.upload(ctx, "mg_walk_frames", tab.data(), tab.size(), 0, (size_t)nws * 8 * 8);   // behind the table: the steps' transforms
     if (rc != MG_OK) return rc;
+    char *base = dt.base();
     a.steps = (const mg_walk_step *)(base + off_steps);
     a.frame_offset = (const int64_t *)(base + off_offs);
     a.lengths = lengths ? (const int32_t *)(base + off_lens) : nullptr;
     a.times = times_dev; a.lat = latents_dev;
-    a.xf = (double *)(base + ((tab.size() + 255) & ~(size_t)255));
+    a.xf = (double *)dt.scratch();
     a.transforms = transforms_dev; a.frames = frames_dev;
     a.n_walks = n_walks; a.ld = ld; a.walk_stride = walk_stride;
     a.n_steps = n_steps; a.D = D; a.tiles_per_walk = (int32_t)tiles;
-    if (!(ctx->attr_traj & 16u)) {
-        MG_HIP_CHECK(hipFuncSetAttribute((const void *)mg_walk_frames_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        MG_HIP_CHECK(hipFuncSetAttribute((const void *)mg_walk_frames_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        ctx->attr_traj |= 16u;
-    }
+    MG_HIP_CHECK(mg_lds_opt_in_once(ctx, MG_LDS_WALK_FRAMES, 160 * 1024, mg_walk_frames_kernel<true>, mg_walk_frames_kernel<false>));
     hipStream_t st = ctx->stream;
     const bool lf = dtype == MG_F64;
     a.t_cap = t_cap; a.lmax = lmax; a.rmax = rmax;
@@ -404,7 +376,7 @@ extern "C" int mg_walk_frames(int32_t n_steps, mg_primitive *const *prims, const
     else hipLaunchKernelGGL(mg_walk_chain_kernel<false>, dim3((unsigned)n_walks), dim3(MG_WALK_CHAIN_BLOCK), lds_c, st, a);
     MG_HIP_CHECK(hipGetLastError());
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    const bool timed = mg_prof_kernel(ctx, MG_WALK_PROF_SLOT, -1, &ev0, &ev1);
+    const bool timed = mg_prof_kernel(ctx, MG_PROF_WALK_FRAMES, -1, &ev0, &ev1);
     const unsigned grid = (unsigned)(tiles * n_walks);
     if (lf) hipExtLaunchKernelGGL(mg_walk_frames_kernel<true>, dim3(grid), dim3(MG_WALK_BLOCK), lds_f, st, timed ? ev0 : nullptr, timed ? ev1 : nullptr, 0, a);
     else hipExtLaunchKernelGGL(mg_walk_frames_kernel<false>, dim3(grid), dim3(MG_WALK_BLOCK), lds_f, st, timed ? ev0 : nullptr, timed ? ev1 : nullptr, 0, a);

@@ -17,7 +17,7 @@
 //     state      the set's last four residuals become the wave's state ([16][4]).
 //
 // No workgroup-wide barrier, no grid barrier, nothing between the steps goes through global memory.  What grows with n_steps
-// travels in a device table of the context (ctx->wscore_tab_dev), rewritten only when it differs from the last call's.
+// travels in a device table of the context (ctx->tab[MG_TABLE_WALK_SCORE]), rewritten only when it differs from the last call's.
 #include <cstring>
 
 #include <algorithm>
@@ -150,29 +150,6 @@ __global__ __launch_bounds__(256) void mg_walk_score_kernel(const mg_wscore_args
     if (k.exit_state && cl < ncand) k.exit_state[(b0 + cl) * 4 + g] = state[cl * 4 + g];
 }
 
-// the call's table on the device: rewritten only when it differs from the last call's
-static int mg_wscore_table_upload(mg_context *ctx, const std::vector<unsigned char> &tab) {
-    const bool same = ctx->wscore_tab_dev && ctx->wscore_tab_host.size() == tab.size() && memcmp(ctx->wscore_tab_host.data(), tab.data(), tab.size()) == 0;
-    if (same) return MG_OK;
-    MG_HIP_CHECK(hipStreamSynchronize(ctx->stream));   // no launch in flight reads the table being replaced
-    if (ctx->wscore_tab_cap < tab.size()) {
-        if (ctx->wscore_tab_dev) { (void)hipFree(ctx->wscore_tab_dev); ctx->wscore_tab_dev = nullptr; ctx->wscore_tab_cap = 0; }
-        ctx->wscore_tab_host.clear();
-        const size_t cap = (size_t)MG_WALK_MAX_STEPS * sizeof(mg_wscore_step);   // the largest table there is: one allocation per context
-        if (hipMalloc(&ctx->wscore_tab_dev, cap) != hipSuccess) {
-            (void)hipGetLastError();
-            ctx->wscore_tab_dev = nullptr;
-            mg_set_error("mg_score_walk_residuals: cannot allocate %zu bytes of device memory", cap);
-            return MG_ERR_OUT_OF_MEMORY;
-        }
-        ctx->wscore_tab_cap = cap;
-    }
-    ctx->wscore_tab_host.clear();
-    MG_HIP_CHECK(hipMemcpy(ctx->wscore_tab_dev, tab.data(), tab.size(), hipMemcpyHostToDevice));
-    ctx->wscore_tab_host = tab;
-    return MG_OK;
-}
-
 #define MG_WSCORE_REQUIRE(cond, ...) MG_REQUIRE_AS(cond, MG_ERR_INVALID_ARGUMENT, __VA_ARGS__)
 
 // the four exit values a set may end with: heading x, z, then position x, z (par rows: type, weight, component)
@@ -261,22 +238,19 @@ extern "C" int mg_score_walk_residuals(int32_t n_steps, const mg_walk_score_step
     if (n_samples == 0) return MG_OK;
     MG_WSCORE_REQUIRE(latents_dev && (residuals_dev || errors_dev || exit_state_dev), "mg_score_walk_residuals: NULL pointer");
     MG_HIP_CHECK(hipSetDevice(ctx->device));
-    int rc = mg_wscore_table_upload(ctx, tab);
+    mg_device_table &dt = ctx->tab[MG_TABLE_WALK_SCORE];
+    int rc = dt.upload(ctx, "mg_score_walk_residuals", tab.data(), tab.size(), (size_t)MG_WALK_MAX_STEPS * sizeof(mg_wscore_step));   // one allocation per context
     if (rc != MG_OK) return rc;
     mg_wscore_args k = {};
-    k.steps = (const mg_wscore_step *)ctx->wscore_tab_dev;
+    k.steps = (const mg_wscore_step *)dt.base();
     k.lat = latents_dev; k.res = residuals_dev; k.err = errors_dev; k.exit_state = exit_state_dev;
     k.B = n_samples; k.ld = ld; k.ld_res = ld_res;
     k.n_steps = n_steps; k.vs = vs; k.nmax = nmax; k.xs = xs;
-    if (lds > 64 * 1024 && !(ctx->attr_traj & 32u)) {
-        MG_HIP_CHECK(hipFuncSetAttribute((const void *)mg_walk_score_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        MG_HIP_CHECK(hipFuncSetAttribute((const void *)mg_walk_score_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        ctx->attr_traj |= 32u;
-    }
-    mg_prof_begin(ctx, 2);
+    if (lds > 64 * 1024) MG_HIP_CHECK(mg_lds_opt_in_once(ctx, MG_LDS_WALK_SCORE, 160 * 1024, mg_walk_score_kernel<true>, mg_walk_score_kernel<false>));
+    mg_prof_begin(ctx, MG_PROF_SCORE_CONSTRAINTS);
     if (latent_dtype == MG_F64) hipLaunchKernelGGL(mg_walk_score_kernel<true>, dim3((unsigned)grid), dim3(256), lds, ctx->stream, k);
     else hipLaunchKernelGGL(mg_walk_score_kernel<false>, dim3((unsigned)grid), dim3(256), lds, ctx->stream, k);
-    mg_prof_end(ctx, 2);
+    mg_prof_end(ctx, MG_PROF_SCORE_CONSTRAINTS);
     MG_HIP_CHECK(hipGetLastError());
     return MG_OK;
 }

@@ -18,7 +18,7 @@
 //   rounded on its own (no contraction), constraints in list order, steps in step order.
 //
 // No grid barrier, no fences, nothing between the steps goes through global memory.  What grows with n_steps or n_constraints
-// travels in a device table of the context (ctx->wtime_tab_dev), rewritten only when it differs from the last call's.
+// travels in a device table of the context (ctx->tab[MG_TABLE_WALK_TIME]), rewritten only when it differs from the last call's.
 #include <cstring>
 
 #include <algorithm>
@@ -30,7 +30,6 @@
 #define MG_WTIME_LDS_MAX (150 * 1024)
 #define MG_WTIME_CHUNK 64                     // canonical frames of a time function in LDS at a time
 #define MG_WTIME_BS (MG_WTIME_CHUNK + 1)      // doubles per candidate in the chunk buffer (odd: lane-per-candidate reads hit 16 banks)
-#define MG_WTIME_PROFILE_SLOT 13
 
 struct mg_wtime_step {              // one step as the kernel reads it
     const double *tphi, *tmean;     // [F][Lt], [F]; unused when Lt == 0 (t(i) = i)
@@ -225,30 +224,6 @@ __global__ __launch_bounds__(256) void mg_walk_time_kernel(const mg_wtime_args a
     if (tid < ncand) mg_wtime_finish(a, tend, logp, pref, tkey, tid, b0 + tid);
 }
 
-// the call's table on the device: rewritten only when it differs from the last call's
-static int mg_wtime_table_upload(mg_context *ctx, const std::vector<unsigned char> &tab) {
-    const bool same = ctx->wtime_tab_dev && ctx->wtime_tab_host.size() == tab.size() && memcmp(ctx->wtime_tab_host.data(), tab.data(), tab.size()) == 0;
-    if (same) return MG_OK;
-    MG_HIP_CHECK(hipStreamSynchronize(ctx->stream));   // no launch in flight reads the table being replaced
-    if (ctx->wtime_tab_cap < tab.size()) {
-        if (ctx->wtime_tab_dev) { (void)hipFree(ctx->wtime_tab_dev); ctx->wtime_tab_dev = nullptr; ctx->wtime_tab_cap = 0; }
-        ctx->wtime_tab_host.clear();
-        const size_t cap = std::max(tab.size(), (size_t)16 * 1024);
-        if (hipMalloc(&ctx->wtime_tab_dev, cap) != hipSuccess) {
-            (void)hipGetLastError();
-            ctx->wtime_tab_dev = nullptr;
-            mg_set_error("mg_score_walk_time: cannot allocate %zu bytes of device memory", cap);
-            return MG_ERR_OUT_OF_MEMORY;
-        }
-        ctx->wtime_tab_cap = cap;
-    }
-    ctx->wtime_tab_host.clear();
-    MG_HIP_CHECK(hipMemcpy(ctx->wtime_tab_dev, tab.data(), tab.size(), hipMemcpyHostToDevice));
-    ctx->wtime_tab_host = tab;
-    ctx->wtime_tab_uploads++;
-    return MG_OK;
-}
-
 #define MG_WTIME_REQUIRE(cond, ...) MG_REQUIRE_AS(cond, MG_ERR_INVALID_ARGUMENT, __VA_ARGS__)
 #define MG_WTIME_REFUSE(cond, ...) MG_REQUIRE_AS(!(cond), MG_ERR_UNSUPPORTED, __VA_ARGS__)
 
@@ -320,23 +295,21 @@ extern "C" int mg_score_walk_time(int32_t n_steps, const mg_walk_time_step *step
     if (n_samples == 0) return MG_OK;
     MG_WTIME_REQUIRE(latents_dev && objective_dev, "mg_score_walk_time: NULL pointer");
     MG_HIP_CHECK(hipSetDevice(ctx->device));
-    int rc = mg_wtime_table_upload(ctx, tab);
+    mg_device_table &dt = ctx->tab[MG_TABLE_WALK_TIME];
+    int rc = dt.upload(ctx, "mg_score_walk_time", tab.data(), tab.size(), (size_t)16 * 1024);
     if (rc != MG_OK) return rc;
     mg_wtime_args k = {};
-    k.steps = (const mg_wtime_step *)ctx->wtime_tab_dev;
-    k.cons = (const mg_wtime_con *)((const char *)ctx->wtime_tab_dev + o_cons);
-    k.order = (const int32_t *)((const char *)ctx->wtime_tab_dev + o_order);
+    k.steps = (const mg_wtime_step *)dt.base();
+    k.cons = (const mg_wtime_con *)(dt.base() + o_cons);
+    k.order = (const int32_t *)(dt.base() + o_order);
     k.lat = (const double *)latents_dev; k.obj = objective_dev; k.err = error_dev; k.ll = loglik_dev;
     k.B = n_samples; k.ld = ld;
     k.start_keyframe = start_keyframe; k.frame_time = frame_time; k.error_scale = error_scale; k.quality_scale = quality_scale;
     k.n_steps = n_steps; k.n_cons = n_constraints; k.wave_doubles = wave_doubles;
-    if (lds > 64 * 1024 && !(ctx->attr_traj & 64u)) {
-        MG_HIP_CHECK(hipFuncSetAttribute((const void *)mg_walk_time_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        ctx->attr_traj |= 64u;
-    }
-    mg_prof_begin(ctx, MG_WTIME_PROFILE_SLOT);
+    if (lds > 64 * 1024) MG_HIP_CHECK(mg_lds_opt_in_once(ctx, MG_LDS_WALK_TIME, 160 * 1024, mg_walk_time_kernel));
+    mg_prof_begin(ctx, MG_PROF_WALK_TIME);
     hipLaunchKernelGGL(mg_walk_time_kernel, dim3((unsigned)grid), dim3(256), lds, ctx->stream, k);
-    mg_prof_end(ctx, MG_WTIME_PROFILE_SLOT);
+    mg_prof_end(ctx, MG_PROF_WALK_TIME);
     MG_HIP_CHECK(hipGetLastError());
     return MG_OK;
 }
@@ -372,11 +345,5 @@ extern "C" int mg_score_walk_time_host(int32_t n_steps, const mg_walk_time_step 
     if (error) MG_HIP_CHECK(hipMemcpyAsync(error, ws.at<char>(o_err), out_b, hipMemcpyDeviceToHost, ctx->stream));
     if (loglik) MG_HIP_CHECK(hipMemcpyAsync(loglik, ws.at<char>(o_ll), out_b, hipMemcpyDeviceToHost, ctx->stream));
     MG_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    return MG_OK;
-}
-
-extern "C" int mg_walk_time_table_uploads(mg_context *ctx, int64_t *uploads) {
-    MG_WTIME_REQUIRE(ctx && uploads, "mg_walk_time_table_uploads: NULL pointer");
-    *uploads = ctx->wtime_tab_uploads;
     return MG_OK;
 }

@@ -549,6 +549,19 @@ def test_planner_step_notices_constraints_rewritten_in_place():
     for n in names:
         np.testing.assert_array_equal(r3[n][0], r2[n][0])
         assert r3[n][1] == r2[n][1]
+    # the per-option constants' device table (Context.table_uploads("fused")): written when the option set changes, not when it repeats
+    few = names[:3]
+    pset.evaluate_options_on_device(few, cons, n_samples=1024, seed=7)
+    u0 = pset.ctx.table_uploads("fused")
+    b4, r4 = step(pset, cons)
+    b4b, r4b = step(pset, cons)
+    assert pset.ctx.table_uploads("fused") == u0 + 1
+    pset.evaluate_options_on_device(few, cons, n_samples=1024, seed=7)
+    assert pset.ctx.table_uploads("fused") == u0 + 2
+    for n in names:
+        np.testing.assert_array_equal(r4[n][0], r3[n][0])
+        np.testing.assert_array_equal(r4b[n][0], r3[n][0])
+        assert r4[n][1] == r3[n][1] == r4b[n][1]
 
 
 def test_planner_step_notices_array_targets_rewritten_in_place():

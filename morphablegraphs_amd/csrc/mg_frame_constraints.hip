@@ -20,6 +20,7 @@
 
 #include "mg_internal.h"
 #include "mg_score_device.h"
+#include "mg_spline_device.h"
 #include "mg_traj_device.h"
 
 #define MG_FC_BLOCK 64
@@ -45,30 +46,17 @@ __global__ __launch_bounds__(256) void mg_align_frames_kernel(mg_align_args a) {
     if (e >= a.B * a.T) return;
     const int64_t b = e / a.T;
     const double *v = a.vals + b * a.n_vals;
-    const double p0x = v[0], p0z = v[1];
-    double c, s, ty;
-    if (a.start_pose) {
-        c = a.h0; s = a.h1; ty = a.py;
-    } else {
-        const double bx = v[2], bz = v[3];
-        c = a.h0 * bx + a.h1 * bz;
-        s = a.h0 * bz - a.h1 * bx;
-        ty = 0.0;
-    }
-    const double tx = a.px - (c * p0x + s * p0z), tz = a.pz - (c * p0z - s * p0x);
+    const mg_align2d t = a.start_pose ? mg_align2d_onto(a.h0, a.h1, a.px, a.pz, v[0], v[1], a.py)
+                                      : mg_align2d_from(a.h0, a.h1, v[2], v[3], a.px, a.pz, v[0], v[1]);
     double *f = a.frames + e * a.D;
-    const double x = f[0], z = f[2];
-    f[0] = c * x + s * z + tx;
-    f[1] += ty;
-    f[2] = c * z - s * x + tz;
-    if (a.D >= 7) {   // the root's quaternion turns with the candidate: (cos(phi / 2), 0, sin(phi / 2), 0) x q
-        const double phi = atan2(s, c);
-        const double aw = cos(0.5 * phi), ay = sin(0.5 * phi);
-        const double qw = f[3], qx = f[4], qy = f[5], qz = f[6];
-        f[3] = aw * qw - ay * qy;
-        f[4] = aw * qx + ay * qz;
-        f[5] = aw * qy + ay * qw;
-        f[6] = aw * qz - ay * qx;
+    double x = f[0], y = f[1], z = f[2];
+    mg_align_position(t, x, y, z);
+    f[0] = x; f[1] = y; f[2] = z;
+    if (a.D >= 7) {   // the root's quaternion turns with the candidate
+        double aw, ay, qw = f[3], qx = f[4], qy = f[5], qz = f[6];
+        mg_align_half_angle(t.c, t.s, aw, ay);
+        mg_align_root_quat(aw, ay, qw, qx, qy, qz);
+        f[3] = qw; f[4] = qx; f[5] = qy; f[6] = qz;
     }
 }
 
@@ -611,7 +599,7 @@ extern "C" int mg_score_frame_constraints(mg_primitive *p, int32_t n_constraints
 // from ONE launch here: a workgroup per candidate keeps the control points of the channels the wanted joints' chains READ -- root
 // translation and the quaternions along the chains, a third of the pose for a hand -- in LDS (fma chains over the latents from the
 // mean: the float64 frames kernel's arithmetic), derives the candidate's aligning transform from its first control point (the
-// statements of MG_CONSTRAINT_VALUE_POSITION / _HEADING at t = 0 and of mg_align_frames_kernel), and for every (time, joint)
+// helpers mg_candidate_alignment and mg_align_frames_kernel call: mg_score_device.h), and for every (time, joint)
 // evaluates just those channels (four taps each), turns the root, walks the chain (mg_joint_positions_kernel's loop).  The same
 // operations on the same values: the tracks are the chain's, bit for bit; 24 bytes per (candidate, time, joint) leave the chip.
 // A PLAN holds what does not change between calls: the joints' chain records, the channel list, per request its joints.
@@ -659,10 +647,12 @@ __device__ __forceinline__ void mg_joint_tracks_body(const mg_track_args &a, con
     for (int e = tid; e < MG_TRACK_CANDS * L; e += MG_TRACK_BLOCK) {
         const int c = e / L, k = e - c * L;
         const int64_t bb = b0 + c < a.B ? b0 + c : a.B - 1;     // (a short last group repeats the last candidate; nothing of it is written)
-        s_all[e] = a.lat_f64 ? ((const double *)a.lat)[bb * a.ld + k] : (double)((const float *)a.lat)[bb * a.ld + k];
+        s_all[e] = mg_load_lat(a.lat, a.lat_f64 != 0, bb * a.ld + k);
     }
     for (int d = tid; d < D; d += MG_TRACK_BLOCK) slot[d] = a.slot[d];
     __syncthreads();
+    // (mg_control_point's statement for MG_TRACK_CANDS candidates side by side: one read of an eigenvector element feeds all of them,
+    // which the helper's one-chain form cannot express)
     for (int e = tid; e < ncp; e += MG_TRACK_BLOCK) {
         const int i = e / nc, q = e - i * nc;
         const int r = i * D + a.chan[q];
@@ -684,38 +674,23 @@ __device__ __forceinline__ void mg_joint_tracks_body(const mg_track_args &a, con
         double *al = al_all + tid * 8;
         auto ch0 = [&](int ch) { return cp[slot[ch]]; };
         const double p0x = ch0(0), p0z = ch0(2);
-        double c, sn, ty;
+        mg_align2d t;
         if (a.align_mode == 2) {
-            c = a.h0; sn = a.h1; ty = a.py;
+            t = mg_align2d_onto(a.h0, a.h1, a.px, a.pz, p0x, p0z, a.py);
         } else {
-            // MG_CONSTRAINT_VALUE_HEADING at t = 0 (mg_constraint_residual): the aligning node's global orientation applied to ref_dir, xz, unit
-            double q[4], v[3];
+            // the aligning node's heading at t = 0 (what a MG_CONSTRAINT_VALUE_HEADING constraint of weight 1 probes: the weight's
+            // multiplication is exact)
+            double q[4] = {1.0, 0.0, 0.0, 0.0}, bx, bz;
             const double *rec = a.align_rec;
-            double aw = 1.0, ax = 0.0, ay = 0.0, az = 0.0;
             for (int i = 0; i < a.align_m; i++) {
                 const int qc = (int)rec[1 + 4 * i];
-                double qw = ch0(qc), qx = ch0(qc + 1), qy = ch0(qc + 2), qz = ch0(qc + 3);
-                const double inv = 1.0 / sqrt(qw * qw + qx * qx + qy * qy + qz * qz);
-                qw *= inv; qx *= inv; qy *= inv; qz *= inv;
-                const double nw = aw * qw - ax * qx - ay * qy - az * qz, nx = aw * qx + ax * qw + ay * qz - az * qy;
-                const double ny = aw * qy - ax * qz + ay * qw + az * qx, nz = aw * qz + ax * qy - ay * qx + az * qw;
-                aw = nw; ax = nx; ay = ny; az = nz;
+                mg_quat_accumulate(q, ch0(qc), ch0(qc + 1), ch0(qc + 2), ch0(qc + 3));
             }
-            q[0] = aw; q[1] = ax; q[2] = ay; q[3] = az;
-            mg_rotate(q, a.ref[0], a.ref[1], a.ref[2], v);
-            const double hx = v[0], hz = v[2];
-            const double inv = 1.0 / sqrt(hx * hx + hz * hz);
-            const double bx = 1.0 * hx * inv, bz = 1.0 * hz * inv;      // (weight 1 of the probing constraint)
-            c = a.h0 * bx + a.h1 * bz;
-            sn = a.h0 * bz - a.h1 * bx;
-            ty = 0.0;
+            mg_heading_xz(q, a.ref[0], a.ref[1], a.ref[2], bx, bz);
+            t = mg_align2d_from(a.h0, a.h1, bx, bz, a.px, a.pz, p0x, p0z);
         }
-        al[0] = c; al[1] = sn;
-        al[2] = a.px - (c * p0x + sn * p0z);
-        al[3] = a.pz - (c * p0z - sn * p0x);
-        al[4] = ty;
-        const double phi = atan2(sn, c);
-        al[5] = cos(0.5 * phi); al[6] = sin(0.5 * phi);
+        al[0] = t.c; al[1] = t.s; al[2] = t.tx; al[3] = t.tz; al[4] = t.ty;
+        mg_align_half_angle(t.c, t.s, al[5], al[6]);
     }
     __syncthreads();
     const bool aligned = a.align_mode != 0;
@@ -727,54 +702,31 @@ __device__ __forceinline__ void mg_joint_tracks_body(const mg_track_args &a, con
         for (int ce = tid; ce < n_here * T * J; ce += MG_TRACK_BLOCK) {
             const int c = ce / (T * J), e = ce - c * (T * J);
             const double *cp = cp_all + (size_t)c * ncp, *al = al_all + c * 8;
-            const double ac = al[0], as = al[1], tx = al[2], tz = al[3], ty = al[4], qaw = al[5], qay = al[6];
+            const mg_align2d t = {al[0], al[1], al[2], al[3], al[4]};
+            const double qaw = al[5], qay = al[6];
             double *out = a.out[rq] + (b0 + c) * (int64_t)T * J * 3;
             const int f = e / J, j = e - f * J;
             const double *wf = w + 4 * (size_t)f;
             const double *cf = cp + (size_t)i0[f] * nc;
-            auto chan = [&](int ch) {       // the frame's channel: four taps of its control points (mg_back_project_frames_f64's statement)
+            auto chan = [&](int ch) {       // the frame's channel: four taps of its control points
                 const double *cq = cf + slot[ch];
-                double v = wf[0] * cq[0];
-                v = fma(wf[1], cq[nc], v);
-                v = fma(wf[2], cq[2 * nc], v);
-                v = fma(wf[3], cq[3 * nc], v);
-                return v;
+                return mg_taps4(wf, cq, nc);
             };
-            double p0 = chan(0), p1 = chan(1), p2 = chan(2);
-            if (aligned) {                  // mg_align_frames_kernel's statements
-                const double x = p0, z = p2;
-                p0 = ac * x + as * z + tx;
-                p1 += ty;
-                p2 = ac * z - as * x + tz;
-            }
+            double p[3] = {chan(0), chan(1), chan(2)};
+            if (aligned) mg_align_position(t, p[0], p[1], p[2]);
             const double *rec = a.records + (size_t)(j0 + j) * MG_TRACK_REC;
             const int m = (int)rec[0];
-            double aw = 1.0, ax = 0.0, ay = 0.0, az = 0.0;
-            for (int k = 0; k < m; k++) {   // mg_joint_positions_kernel's loop
+            double q[4] = {1.0, 0.0, 0.0, 0.0};
+            for (int k = 0; k < m; k++) {   // mg_joint_positions_kernel's loop, the root's quaternion turned with the candidate first
                 const int ch = (int)rec[1 + 4 * k];
                 if (ch >= 0) {
                     double qw = chan(ch), qx = chan(ch + 1), qy = chan(ch + 2), qz = chan(ch + 3);
-                    if (aligned && ch == 3 && D >= 7) {   // the root's quaternion turns with the candidate: (cos(phi / 2), 0, sin(phi / 2), 0) x q
-                        const double w0 = qw, x0 = qx, y0 = qy, z0 = qz;
-                        qw = qaw * w0 - qay * y0;
-                        qx = qaw * x0 + qay * z0;
-                        qy = qaw * y0 + qay * w0;
-                        qz = qaw * z0 - qay * x0;
-                    }
-                    const double inv = 1.0 / sqrt(qw * qw + qx * qx + qy * qy + qz * qz);
-                    qw *= inv; qx *= inv; qy *= inv; qz *= inv;
-                    const double nw = aw * qw - ax * qx - ay * qy - az * qz, nx = aw * qx + ax * qw + ay * qz - az * qy;
-                    const double ny = aw * qy - ax * qz + ay * qw + az * qx, nz = aw * qz + ax * qy - ay * qx + az * qw;
-                    aw = nw; ax = nx; ay = ny; az = nz;
+                    if (aligned && ch == 3 && D >= 7) mg_align_root_quat(qaw, qay, qw, qx, qy, qz);
+                    mg_quat_accumulate(q, qw, qx, qy, qz);
                 }
-                const double ox = rec[2 + 4 * k], oy = rec[3 + 4 * k], oz = rec[4 + 4 * k];
-                const double cx = ay * oz - az * oy, cy = az * ox - ax * oz, cz = ax * oy - ay * ox;
-                const double dx = ay * cz - az * cy, dy = az * cx - ax * cz, dz = ax * cy - ay * cx;
-                p0 += ox + 2.0 * (aw * cx + dx);
-                p1 += oy + 2.0 * (aw * cy + dy);
-                p2 += oz + 2.0 * (aw * cz + dz);
+                mg_fk_link(q, rec[2 + 4 * k], rec[3 + 4 * k], rec[4 + 4 * k], p);
             }
-            out[(size_t)e * 3] = p0; out[(size_t)e * 3 + 1] = p1; out[(size_t)e * 3 + 2] = p2;
+            out[(size_t)e * 3] = p[0]; out[(size_t)e * 3 + 1] = p[1]; out[(size_t)e * 3 + 2] = p[2];
         }
     }
 }

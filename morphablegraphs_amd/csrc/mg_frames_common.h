@@ -6,6 +6,7 @@
 #include <hip/hip_ext.h>
 #include <type_traits>
 #include "mg_gmm_device.h"
+#include "mg_spline_device.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef double f64x4 __attribute__((ext_vector_type(4)));
@@ -25,12 +26,6 @@ struct mg_frames_args {
                                         // cs_per tiles per workgroup of a chunk, the first cs_rem one more
     mg_chunk ck[MG_ARG_CHUNKS];   // the first chunks' descriptors: read with the other arguments instead of a dependent trip to global memory
 };
-
-template <bool F64>
-__device__ __forceinline__ double mg_load_lat(const void *lat, int64_t idx) {
-    if (F64) return ((const double *)lat)[idx];
-    return (double)((const float *)lat)[idx];
-}
 
 // -----------------------------------------------------------------------------------------
 // The hot-path kernel: persistent, wave-specialised.

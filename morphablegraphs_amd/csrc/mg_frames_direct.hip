@@ -31,49 +31,27 @@ __global__ __launch_bounds__(256) void mg_frames_direct_kernel(mg_direct_args a)
         const int i0v = a.i0[f];
         const double *wq = a.w + 4 * (size_t)f;
         const int r0 = i0v * a.D + d;
+        auto lat64 = [&](int k) { return mg_load_lat<LAT_F64>(a.lat, b * a.ld + k); };
+        auto lat32 = [&](int k) { return (float)lat64(k); };
         if (!OUT_F64 && d < a.nroot && a.split) {
             float c[4];
 #pragma unroll
-            for (int j = 0; j < 4; j++) {
-                const float *e = a.Et32 + (r0 + j * a.D);
-                float acc = 0.0f;
-                for (int k = 0; k < a.L; k++) acc = fmaf(e[(size_t)k * a.R], (float)mg_load_lat<LAT_F64>(a.lat, b * a.ld + k), acc);
-                c[j] = acc;
-            }
-            float v = (float)wq[0] * c[0];
-            v = fmaf((float)wq[1], c[1], v);
-            v = fmaf((float)wq[2], c[2], v);
-            v = fmaf((float)wq[3], c[3], v);
+            for (int j = 0; j < 4; j++) c[j] = mg_control_point(0.0f, a.Et32 + (r0 + j * a.D), (size_t)a.R, a.L, lat32);
+            const float v = mg_taps4(wq, c, 1);
             const float *m = a.rootm + 8 * (size_t)f;
             ((float *)a.out)[idx] = m[d] + (m[3 + d] + v);
         } else if (OUT_F64 || d < a.nroot) {
             double c[4];
 #pragma unroll
-            for (int j = 0; j < 4; j++) {
-                const double *e = a.Et64 + (r0 + j * a.D);
-                double acc = a.mean[r0 + j * a.D];
-                for (int k = 0; k < a.L; k++) acc = fma(e[(size_t)k * a.R], mg_load_lat<LAT_F64>(a.lat, b * a.ld + k), acc);
-                c[j] = acc;
-            }
-            double v = wq[0] * c[0];
-            v = fma(wq[1], c[1], v);
-            v = fma(wq[2], c[2], v);
-            v = fma(wq[3], c[3], v);
+            for (int j = 0; j < 4; j++) c[j] = mg_control_point(a.mean[r0 + j * a.D], a.Et64 + (r0 + j * a.D), (size_t)a.R, a.L, lat64);
+            const double v = mg_taps4(wq, c, 1);
             if (OUT_F64) ((double *)a.out)[idx] = v;
             else ((float *)a.out)[idx] = (float)v;
         } else {
             float c[4];
 #pragma unroll
-            for (int j = 0; j < 4; j++) {
-                const float *e = a.Et32 + (r0 + j * a.D);
-                float acc = (float)a.mean[r0 + j * a.D];
-                for (int k = 0; k < a.L; k++) acc = fmaf(e[(size_t)k * a.R], (float)mg_load_lat<LAT_F64>(a.lat, b * a.ld + k), acc);
-                c[j] = acc;
-            }
-            float v = (float)wq[0] * c[0];
-            v = fmaf((float)wq[1], c[1], v);
-            v = fmaf((float)wq[2], c[2], v);
-            v = fmaf((float)wq[3], c[3], v);
+            for (int j = 0; j < 4; j++) c[j] = mg_control_point((float)a.mean[r0 + j * a.D], a.Et32 + (r0 + j * a.D), (size_t)a.R, a.L, lat32);
+            const float v = mg_taps4(wq, c, 1);
             ((float *)a.out)[idx] = v;
         }
     }
@@ -91,11 +69,7 @@ __global__ __launch_bounds__(256) void mg_spline_eval_kernel(const double *coeff
         const int f = o / D, d = o - f * D;
         const double *c = coeffs + s * R + (size_t)i0[f] * D + d;
         const double *wq = w + 4 * (size_t)f;
-        double v = wq[0] * c[0];
-        v = fma(wq[1], c[D], v);
-        v = fma(wq[2], c[2 * D], v);
-        v = fma(wq[3], c[3 * D], v);
-        out[idx] = v;
+        out[idx] = mg_taps4(wq, c, D);
     }
 }
 

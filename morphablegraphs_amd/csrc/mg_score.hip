@@ -9,6 +9,7 @@
 #include "mg_gmm_device.h"
 
 #include "mg_score_device.h"
+#include "mg_spline_device.h"
 
 // VALU kernel (fallback for > 64 latent components): one workgroup = 64 candidates (a lane each) x 4 waves that deal
 // the constraints round-robin.  The latent tile is staged in LDS ([64][L+1] float64), the fused keyframe matrices are
@@ -29,7 +30,7 @@ __global__ __launch_bounds__(MG_SC_CANDS *MG_SC_WAVES) void mg_score_kernel(mg_s
     for (int e = tid; e < MG_SC_CANDS * L; e += MG_SC_CANDS * MG_SC_WAVES) {
         int c = e / L, i = e - c * L;
         double v = 0.0;
-        if (c < ncand) v = LAT_F64 ? ((const double *)a.lat)[(b0 + c) * a.ld + i] : (double)((const float *)a.lat)[(b0 + c) * a.ld + i];
+        if (c < ncand) v = mg_load_lat<LAT_F64>(a.lat, (b0 + c) * a.ld + i);
         lds_x[c * xs + i] = v;
     }
     __syncthreads();
@@ -362,26 +363,13 @@ __global__ __launch_bounds__(256) void mg_joint_positions_kernel(const double *_
     const double *f = frames + n * D;
     const double *rec = table + (size_t)j * (1 + 4 * MG_MAX_CHAIN);
     const int m = (int)rec[0];
-    double p0 = f[0], p1 = f[1], p2 = f[2];
-    double aw = 1.0, ax = 0.0, ay = 0.0, az = 0.0;
+    double p[3] = {f[0], f[1], f[2]}, q[4] = {1.0, 0.0, 0.0, 0.0};
     for (int k = 0; k < m; k++) {
         const int ch = (int)rec[1 + 4 * k];
-        if (ch >= 0) {
-            double qw = f[ch], qx = f[ch + 1], qy = f[ch + 2], qz = f[ch + 3];
-            const double inv = 1.0 / sqrt(qw * qw + qx * qx + qy * qy + qz * qz);
-            qw *= inv; qx *= inv; qy *= inv; qz *= inv;
-            const double nw = aw * qw - ax * qx - ay * qy - az * qz, nx = aw * qx + ax * qw + ay * qz - az * qy;
-            const double ny = aw * qy - ax * qz + ay * qw + az * qx, nz = aw * qz + ax * qy - ay * qx + az * qw;
-            aw = nw; ax = nx; ay = ny; az = nz;
-        }
-        const double ox = rec[2 + 4 * k], oy = rec[3 + 4 * k], oz = rec[4 + 4 * k];
-        const double cx = ay * oz - az * oy, cy = az * ox - ax * oz, cz = ax * oy - ay * ox;
-        const double dx = ay * cz - az * cy, dy = az * cx - ax * cz, dz = ax * cy - ay * cx;
-        p0 += ox + 2.0 * (aw * cx + dx);
-        p1 += oy + 2.0 * (aw * cy + dy);
-        p2 += oz + 2.0 * (aw * cz + dz);
+        if (ch >= 0) mg_quat_accumulate(q, f[ch], f[ch + 1], f[ch + 2], f[ch + 3]);
+        mg_fk_link(q, rec[2 + 4 * k], rec[3 + 4 * k], rec[4 + 4 * k], p);
     }
-    out[idx * 3] = p0; out[idx * 3 + 1] = p1; out[idx * 3 + 2] = p2;
+    out[idx * 3] = p[0]; out[idx * 3 + 1] = p[1]; out[idx * 3 + 2] = p[2];
 }
 
 int mg_launch_joint_positions(mg_context *ctx, const double *frames, const double *table, int64_t N, int D, int J, double *out) {

@@ -1,6 +1,14 @@
 // Device-side pieces of the fused constraint scorer (gfx950): the weighted residual of one constraint for one candidate
 // (its argument block, mg_score_args, is in mg_internal.h), shared by the stand-alone scoring kernels (mg_score.hip) and the one-launch planner
 // step (mg_options.hip) so that both produce the same bits.
+// And the float64 pose statements, stated once: every kernel that walks a chain, forms a heading or aligns a pose calls these, so
+// that a fused kernel gives the bits of the chain of calls it replaces.  What this header guarantees:
+//   mg_quat_normalise, mg_quat_accumulate   a chain quaternion made unit, and multiplied into the accumulated orientation
+//   mg_rotate, mg_fk_link                   a vector turned by a unit quaternion; one link of forward kinematics
+//   mg_heading_xz                           an orientation applied to ref_dir, the xz part, made unit
+//   mg_align2d_onto, mg_align2d_from        the 2-D aligning transform (c, s, tx, tz, ty)
+//   mg_align_half_angle                     (cos(phi / 2), sin(phi / 2)) of its rotation
+//   mg_align_position, mg_align_direction, mg_align_root_quat   the transform applied to a position, a direction, the root's quaternion
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -9,22 +17,25 @@
 
 #include "mg_internal.h"
 
-// The weighted residual of constraint c for one candidate; `channel(row)` yields the candidate's pose channel of
-// that row of the fused keyframe matrices (rows of constraint c start at woff[c]).  Shared by the VALU kernel (a dot
-// product per channel) and the MFMA kernel (channels already in LDS), so both produce the same value.
-// Product of the chain's m quaternions (rows r_q ..), each normalised like transformations.quaternion_matrix does.
+// q / |q|, like transformations.quaternion_matrix normalises
+__device__ __forceinline__ void mg_quat_normalise(double &qw, double &qx, double &qy, double &qz) {
+    const double inv = 1.0 / sqrt(qw * qw + qx * qx + qy * qy + qz * qz);
+    qw *= inv; qx *= inv; qy *= inv; qz *= inv;
+}
+// a <- a x (q / |q|): one more quaternion of a chain multiplied into the accumulated orientation (Hamilton product)
+__device__ __forceinline__ void mg_quat_accumulate(double (&a)[4], double qw, double qx, double qy, double qz) {
+    mg_quat_normalise(qw, qx, qy, qz);
+    const double nw = a[0] * qw - a[1] * qx - a[2] * qy - a[3] * qz, nx = a[0] * qx + a[1] * qw + a[2] * qz - a[3] * qy;
+    const double ny = a[0] * qy - a[1] * qz + a[2] * qw + a[3] * qx, nz = a[0] * qz + a[1] * qy - a[2] * qx + a[3] * qw;
+    a[0] = nw; a[1] = nx; a[2] = ny; a[3] = nz;
+}
+// Product of the chain's m quaternions (rows r_q ..), each normalised.  Here and below `channel(row)` yields the candidate's pose
+// channel of that row of the fused keyframe matrices (rows of constraint c start at woff[c]): a dot product per channel in the VALU
+// kernel, a read from LDS in the MFMA kernel, so both produce the same value.
 template <typename ChannelFn>
 __device__ __forceinline__ void mg_chain_orientation(ChannelFn channel, int r_q, int m, double (&q)[4]) {
-    double aw = 1.0, ax = 0.0, ay = 0.0, az = 0.0;
-    for (int i = 0; i < m; i++) {
-        double qw = channel(r_q + 4 * i), qx = channel(r_q + 1 + 4 * i), qy = channel(r_q + 2 + 4 * i), qz = channel(r_q + 3 + 4 * i);
-        const double inv = 1.0 / sqrt(qw * qw + qx * qx + qy * qy + qz * qz);
-        qw *= inv; qx *= inv; qy *= inv; qz *= inv;
-        const double nw = aw * qw - ax * qx - ay * qy - az * qz, nx = aw * qx + ax * qw + ay * qz - az * qy;
-        const double ny = aw * qy - ax * qz + ay * qw + az * qx, nz = aw * qz + ax * qy - ay * qx + az * qw;
-        aw = nw; ax = nx; ay = ny; az = nz;
-    }
-    q[0] = aw; q[1] = ax; q[2] = ay; q[3] = az;
+    q[0] = 1.0; q[1] = 0.0; q[2] = 0.0; q[3] = 0.0;
+    for (int i = 0; i < m; i++) mg_quat_accumulate(q, channel(r_q + 4 * i), channel(r_q + 1 + 4 * i), channel(r_q + 2 + 4 * i), channel(r_q + 3 + 4 * i));
 }
 // v' = v + 2 w (u x v) + 2 u x (u x v) for a unit quaternion (w, u)
 __device__ __forceinline__ void mg_rotate(const double (&q)[4], double vx, double vy, double vz, double (&out)[3]) {
@@ -34,100 +45,101 @@ __device__ __forceinline__ void mg_rotate(const double (&q)[4], double vx, doubl
     out[1] = vy + 2.0 * (q[0] * cy + dy);
     out[2] = vz + 2.0 * (q[0] * cz + dz);
 }
+// One link of forward kinematics: p += R(a) offset, a the accumulated orientation of the link's joint
+__device__ __forceinline__ void mg_fk_link(const double (&a)[4], double ox, double oy, double oz, double (&p)[3]) {
+    double v[3];
+    mg_rotate(a, ox, oy, oz, v);
+    p[0] += v[0]; p[1] += v[1]; p[2] += v[2];
+}
 // Forward kinematics: p = root translation (rows r_p ..) + sum_i R(q_0 .. q_i) offset_i over the chain's m links
 // (quaternion rows r_q .., offsets off[m][3]).
 template <typename ChannelFn>
 __device__ __forceinline__ void mg_fk_position(ChannelFn channel, int r_p, int r_q, int m, const double *off, double (&p)[3]) {
-    double p0 = channel(r_p), p1 = channel(r_p + 1), p2 = channel(r_p + 2);
-    double aw = 1.0, ax = 0.0, ay = 0.0, az = 0.0;   // accumulated global rotation of the parent
+    p[0] = channel(r_p); p[1] = channel(r_p + 1); p[2] = channel(r_p + 2);
+    double a[4] = {1.0, 0.0, 0.0, 0.0};   // accumulated global rotation of the parent
     for (int i = 0; i < m; i++) {
-        double qw = channel(r_q + 4 * i), qx = channel(r_q + 1 + 4 * i), qy = channel(r_q + 2 + 4 * i), qz = channel(r_q + 3 + 4 * i);
-        const double inv = 1.0 / sqrt(qw * qw + qx * qx + qy * qy + qz * qz);
-        qw *= inv; qx *= inv; qy *= inv; qz *= inv;
-        const double nw = aw * qw - ax * qx - ay * qy - az * qz, nx = aw * qx + ax * qw + ay * qz - az * qy;
-        const double ny = aw * qy - ax * qz + ay * qw + az * qx, nz = aw * qz + ax * qy - ay * qx + az * qw;
-        aw = nw; ax = nx; ay = ny; az = nz;
-        const double ox = off[3 * i], oy = off[3 * i + 1], oz = off[3 * i + 2];
-        // v' = v + 2 w (u x v) + 2 u x (u x v), u = (ax, ay, az)
-        const double cx = ay * oz - az * oy, cy = az * ox - ax * oz, cz = ax * oy - ay * ox;
-        const double dx = ay * cz - az * cy, dy = az * cx - ax * cz, dz = ax * cy - ay * cx;
-        p0 += ox + 2.0 * (aw * cx + dx);
-        p1 += oy + 2.0 * (aw * cy + dy);
-        p2 += oz + 2.0 * (aw * cz + dz);
+        mg_quat_accumulate(a, channel(r_q + 4 * i), channel(r_q + 1 + 4 * i), channel(r_q + 2 + 4 * i), channel(r_q + 3 + 4 * i));
+        mg_fk_link(a, off[3 * i], off[3 * i + 1], off[3 * i + 2], p);
     }
-    p[0] = p0; p[1] = p1; p[2] = p2;
 }
 
 // Forward kinematics through a pose table record: link k rotates by the quaternion at row r0 + rec[5 + 4k] (identity if
 // negative) and moves by the offset rec[6 + 4k ..]; rows of the pose block start at r0 (root xyz first).
 template <typename ChannelFn>
 __device__ __forceinline__ void mg_fk_position_table(ChannelFn channel, int r0, const double *rec, double (&p)[3]) {
-    double p0 = channel(r0), p1 = channel(r0 + 1), p2 = channel(r0 + 2);
-    double aw = 1.0, ax = 0.0, ay = 0.0, az = 0.0;
+    p[0] = channel(r0); p[1] = channel(r0 + 1); p[2] = channel(r0 + 2);
+    double a[4] = {1.0, 0.0, 0.0, 0.0};
     const int m = (int)rec[4];
     for (int k = 0; k < m; k++) {
         const int qr = (int)rec[5 + 4 * k];
-        if (qr >= 0) {
-            double qw = channel(r0 + qr), qx = channel(r0 + qr + 1), qy = channel(r0 + qr + 2), qz = channel(r0 + qr + 3);
-            const double inv = 1.0 / sqrt(qw * qw + qx * qx + qy * qy + qz * qz);
-            qw *= inv; qx *= inv; qy *= inv; qz *= inv;
-            const double nw = aw * qw - ax * qx - ay * qy - az * qz, nx = aw * qx + ax * qw + ay * qz - az * qy;
-            const double ny = aw * qy - ax * qz + ay * qw + az * qx, nz = aw * qz + ax * qy - ay * qx + az * qw;
-            aw = nw; ax = nx; ay = ny; az = nz;
-        }
-        const double ox = rec[6 + 4 * k], oy = rec[7 + 4 * k], oz = rec[8 + 4 * k];
-        const double cx = ay * oz - az * oy, cy = az * ox - ax * oz, cz = ax * oy - ay * ox;
-        const double dx = ay * cz - az * cy, dy = az * cx - ax * cz, dz = ax * cy - ay * cx;
-        p0 += ox + 2.0 * (aw * cx + dx);
-        p1 += oy + 2.0 * (aw * cy + dy);
-        p2 += oz + 2.0 * (aw * cz + dz);
+        if (qr >= 0) mg_quat_accumulate(a, channel(r0 + qr), channel(r0 + qr + 1), channel(r0 + qr + 2), channel(r0 + qr + 3));
+        mg_fk_link(a, rec[6 + 4 * k], rec[7 + 4 * k], rec[8 + 4 * k], p);
     }
-    p[0] = p0; p[1] = p1; p[2] = p2;
 }
 
-// The candidate's 2-D aligning transform (mg_alignment_desc): rotation about y by the angle between its own heading
-// in the first control point and the previous motion's, as (cos, sin) = (h . b, h x b), and the xz translation that
-// puts its first root position on the previous one.
-struct mg_align2d { double c, s, tx, tz, ty; };   // ty: the start-pose mode raises every position by the start height
+// Heading of a node: its global orientation q applied to ref_dir r, the xz part, made unit
+__device__ __forceinline__ void mg_heading_xz(const double (&q)[4], double rx, double ry, double rz, double &bx, double &bz) {
+    double v[3];
+    mg_rotate(q, rx, ry, rz, v);
+    const double inv = 1.0 / sqrt(v[0] * v[0] + v[2] * v[2]);
+    bx = v[0] * inv; bz = v[2] * inv;
+}
+
+// A candidate's 2-D aligning transform: rotation about y by (cos, sin) = (c, s), then a translation in xz; ty: the start-pose mode
+// raises every position by the start height
+struct mg_align2d { double c, s, tx, tz, ty; };
+// ... the one with the given rotation that puts the candidate's first root position (p0x, p0z) on (px, pz)
+__device__ __forceinline__ mg_align2d mg_align2d_onto(double c, double s, double px, double pz, double p0x, double p0z, double ty) {
+    mg_align2d t;
+    t.c = c; t.s = s;
+    t.tx = px - (c * p0x + s * p0z);
+    t.tz = pz - (c * p0z - s * p0x);
+    t.ty = ty;
+    return t;
+}
+// ... onto a previous motion: the rotation is the angle between the previous heading h and the candidate's own heading b in its
+// first control point, (cos, sin) = (h . b, h x b)
+__device__ __forceinline__ mg_align2d mg_align2d_from(double hx, double hz, double bx, double bz, double px, double pz, double p0x, double p0z) {
+    return mg_align2d_onto(hx * bx + hz * bz, hx * bz - hz * bx, px, pz, p0x, p0z, 0.0);
+}
+// (cos(phi / 2), sin(phi / 2)) of the transform's rotation: the quaternion (qaw, 0, qay, 0) the root's orientation turns by
+__device__ __forceinline__ void mg_align_half_angle(double c, double s, double &qaw, double &qay) {
+    const double phi = atan2(s, c);
+    qaw = cos(0.5 * phi); qay = sin(0.5 * phi);
+}
+__device__ __forceinline__ void mg_align_position(const mg_align2d &t, double &x, double &y, double &z) {
+    const double x0 = x, z0 = z;
+    x = t.c * x0 + t.s * z0 + t.tx;
+    y += t.ty;
+    z = t.c * z0 - t.s * x0 + t.tz;
+}
+__device__ __forceinline__ void mg_align_direction(const mg_align2d &t, double &x, double &z) {
+    const double x0 = x, z0 = z;
+    x = t.c * x0 + t.s * z0;
+    z = t.c * z0 - t.s * x0;
+}
+// (qaw, 0, qay, 0) x q
+__device__ __forceinline__ void mg_align_root_quat(double qaw, double qay, double &qw, double &qx, double &qy, double &qz) {
+    const double w0 = qw, x0 = qx, y0 = qy, z0 = qz;
+    qw = qaw * w0 - qay * y0;
+    qx = qaw * x0 + qay * z0;
+    qy = qaw * y0 + qay * w0;
+    qz = qaw * z0 - qay * x0;
+}
+
+// The candidate's transform in the fused scorer (mg_alignment_desc), from its own first control point (rows woff[n] ..)
 template <typename ChannelFn>
 __device__ __forceinline__ mg_align2d mg_candidate_alignment(const mg_score_args &a, ChannelFn channel, int64_t cand) {
     const double *al = a.align;
     const int r0 = a.woff[a.n], m = (int)al[0];
-    if (m == 0) {
-        // start-pose mode (reference objective_functions.py:38-47): the SAME rotation about y for every candidate,
-        // (cos, sin) = al[1..2], the candidate's first root position moved to (al[3], ., al[4]), heights raised by al[5]
-        mg_align2d t;
-        t.c = al[1]; t.s = al[2];
-        const double p0x = channel(r0), p0z = channel(r0 + 2);
-        t.tx = al[3] - (t.c * p0x + t.s * p0z);
-        t.tz = al[4] - (t.c * p0z - t.s * p0x);
-        t.ty = al[5];
-        return t;
-    }
-    double aw = 1.0, ax = 0.0, ay = 0.0, az = 0.0;   // global orientation of the aligning node
-    for (int i = 0; i < m; i++) {
-        double qw = channel(r0 + 3 + 4 * i), qx = channel(r0 + 4 + 4 * i), qy = channel(r0 + 5 + 4 * i), qz = channel(r0 + 6 + 4 * i);
-        const double inv = 1.0 / sqrt(qw * qw + qx * qx + qy * qy + qz * qz);
-        qw *= inv; qx *= inv; qy *= inv; qz *= inv;
-        const double nw = aw * qw - ax * qx - ay * qy - az * qz, nx = aw * qx + ax * qw + ay * qz - az * qy;
-        const double ny = aw * qy - ax * qz + ay * qw + az * qx, nz = aw * qz + ax * qy - ay * qx + az * qw;
-        aw = nw; ax = nx; ay = ny; az = nz;
-    }
-    const double rx = al[5], ry = al[6], rz = al[7];
-    const double cx = ay * rz - az * ry, cy = az * rx - ax * rz, cz = ax * ry - ay * rx;
-    const double dx = ay * cz - az * cy, dz = ax * cy - ay * cx;
-    double bx = rx + 2.0 * (aw * cx + dx), bz = rz + 2.0 * (aw * cz + dz);
-    const double bn = 1.0 / sqrt(bx * bx + bz * bz);
-    bx *= bn; bz *= bn;
+    // start-pose mode (reference objective_functions.py:38-47): the SAME rotation about y for every candidate,
+    // (cos, sin) = al[1..2], the candidate's first root position moved to (al[3], ., al[4]), heights raised by al[5]
+    if (m == 0) return mg_align2d_onto(al[1], al[2], al[3], al[4], channel(r0), channel(r0 + 2), al[5]);
+    double q[4], bx, bz;   // global orientation of the aligning node, its heading
+    mg_chain_orientation(channel, r0 + 3, m, q);
+    mg_heading_xz(q, al[5], al[6], al[7], bx, bz);
     const double *pc = a.align_cand ? a.align_cand + cand * 4 - 1 : al;   // [1..4]: previous heading (x, z), previous root (x, z)
-    mg_align2d t;
-    t.c = pc[1] * bx + pc[2] * bz;
-    t.s = pc[1] * bz - pc[2] * bx;
-    const double p0x = channel(r0), p0z = channel(r0 + 2);
-    t.tx = pc[3] - (t.c * p0x + t.s * p0z);
-    t.tz = pc[4] - (t.c * p0z - t.s * p0x);
-    t.ty = 0.0;
-    return t;
+    return mg_align2d_from(pc[1], pc[2], bx, bz, pc[3], pc[4], channel(r0), channel(r0 + 2));
 }
 
 // ROOT_ONLY: the set holds root position / 2-D direction constraints only (the caller has checked): the other kinds' code -- and
@@ -143,12 +155,7 @@ __device__ __forceinline__ double mg_constraint_residual(const mg_score_args &a,
     if constexpr (!ROOT_ONLY) {
     if (type == MG_CONSTRAINT_VALUE_POSITION) {   // not an error: the (aligned) root position's component par[2] at the keyframe
         double pj[3] = {channel(r0), channel(r0 + 1), channel(r0 + 2)};
-        if (a.align) {
-            const double x = pj[0], z = pj[2];
-            pj[0] = al.c * x + al.s * z + al.tx;
-            pj[2] = al.c * z - al.s * x + al.tz;
-            pj[1] += al.ty;
-        }
+        if (a.align) mg_align_position(al, pj[0], pj[1], pj[2]);
         return par[1] * pj[(int)par[2]];
     }
     if (type == MG_CONSTRAINT_VALUE_HEADING) {   // the (aligned) unit heading's x (par[2] = 0) or z component: xz of the joint's global orientation applied to ref_dir
@@ -156,7 +163,7 @@ __device__ __forceinline__ double mg_constraint_residual(const mg_score_args &a,
         mg_chain_orientation(channel, r0, a.chain[c], q);
         mg_rotate(q, par[5], par[6], par[7], v);
         double hx = v[0], hz = v[2];
-        if (a.align) { hx = al.c * v[0] + al.s * v[2]; hz = al.c * v[2] - al.s * v[0]; }
+        if (a.align) mg_align_direction(al, hx, hz);
         const double inv = 1.0 / sqrt(hx * hx + hz * hz);
         return par[1] * ((int)par[2] == 0 ? hx : hz) * inv;
     }
@@ -171,12 +178,7 @@ __device__ __forceinline__ double mg_constraint_residual(const mg_score_args &a,
 #pragma unroll
             for (int i = 0; i < 3; i++) pj[i] = pj[i] + 0.5 * (pk[i] - pj[i]);
         }
-        if (a.align) {
-            const double x = pj[0], z = pj[2];
-            pj[0] = al.c * x + al.s * z + al.tx;
-            pj[2] = al.c * z - al.s * x + al.tz;
-            pj[1] += al.ty;
-        }
+        if (a.align) mg_align_position(al, pj[0], pj[1], pj[2]);
         double ds = 0.0;
 #pragma unroll
         for (int i = 0; i < 3; i++) {
@@ -195,7 +197,7 @@ __device__ __forceinline__ double mg_constraint_residual(const mg_score_args &a,
             const double *rec = tb + MG_POSE_HDR + (size_t)i * MG_POSE_REC;
             double b[3];
             mg_fk_position_table(channel, r0, rec, b);
-            if (a.align) { const double x = b[0], z = b[2]; b[0] = al.c * x + al.s * z + al.tx; b[2] = al.c * z - al.s * x + al.tz; b[1] += al.ty; }
+            if (a.align) mg_align_position(al, b[0], b[1], b[2]);
             const double w = rec[3];
             num += w * (rec[0] * b[2] - b[0] * rec[2]);
             den += w * (rec[0] * b[0] + rec[2] * b[2]);
@@ -210,7 +212,7 @@ __device__ __forceinline__ double mg_constraint_residual(const mg_score_args &a,
             const double *rec = tb + MG_POSE_HDR + (size_t)i * MG_POSE_REC;
             double b[3];
             mg_fk_position_table(channel, r0, rec, b);
-            if (a.align) { const double x = b[0], z = b[2]; b[0] = al.c * x + al.s * z + al.tx; b[2] = al.c * z - al.s * x + al.tz; b[1] += al.ty; }
+            if (a.align) mg_align_position(al, b[0], b[1], b[2]);
             if (i == 0) { first[0] = b[0]; first[1] = b[1]; first[2] = b[2]; }
             const double bx = b[0] * ct + b[2] * st + x0, bz = b[2] * ct - b[0] * st + z0;
             const double ex = rec[0] - bx, ey = rec[1] - b[1], ez = rec[2] - bz;
@@ -220,7 +222,7 @@ __device__ __forceinline__ double mg_constraint_residual(const mg_score_args &a,
         if (tb[1] != 0.0) {
             double nx[3];
             mg_fk_position_table(channel, r0 + block, tb + MG_POSE_HDR, nx);   // the first joint one frame later
-            if (a.align) { const double x = nx[0], z = nx[2]; nx[0] = al.c * x + al.s * z + al.tx; nx[2] = al.c * z - al.s * x + al.tz; nx[1] += al.ty; }
+            if (a.align) mg_align_position(al, nx[0], nx[1], nx[2]);
             const double vx = tb[2] - (nx[0] - first[0]), vy = tb[3] - (nx[1] - first[1]), vz = tb[4] - (nx[2] - first[2]);
             err += sqrt(vx * vx + vy * vy + vz * vz);
         }
@@ -234,12 +236,8 @@ __device__ __forceinline__ double mg_constraint_residual(const mg_score_args &a,
         mg_chain_orientation(channel, r0 + 3, m, q);
         mg_rotate(q, par[5], par[6], par[7], v);
         if (a.align) {
-            const double x = pj[0], z = pj[2], vx = v[0], vz = v[2];
-            pj[0] = al.c * x + al.s * z + al.tx;
-            pj[2] = al.c * z - al.s * x + al.tz;
-            pj[1] += al.ty;
-            v[0] = al.c * vx + al.s * vz;
-            v[2] = al.c * vz - al.s * vx;
+            mg_align_position(al, pj[0], pj[1], pj[2]);
+            mg_align_direction(al, v[0], v[2]);
         }
         const double tx = par[2] - pj[0], ty = par[3] - pj[1], tz = par[4] - pj[2];
         const double dot = (v[0] * tx + v[1] * ty + v[2] * tz) / (sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]) * sqrt(tx * tx + ty * ty + tz * tz));
@@ -251,11 +249,7 @@ __device__ __forceinline__ double mg_constraint_residual(const mg_score_args &a,
         mg_chain_orientation(channel, r0, a.chain[c], q);
         double v[3];
         mg_rotate(q, par[5], par[6], par[7], v);
-        if (a.align) {
-            const double x = v[0], z = v[2];
-            v[0] = al.c * x + al.s * z;
-            v[2] = al.c * z - al.s * x;
-        }
+        if (a.align) mg_align_direction(al, v[0], v[2]);
         const double dot = (v[0] * par[2] + v[1] * par[3] + v[2] * par[4]) /
                            (sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]) * sqrt(par[2] * par[2] + par[3] * par[3] + par[4] * par[4]));
         return par[1] * acos(fmin(1.0, fmax(dot, -1.0)));
@@ -265,8 +259,8 @@ __device__ __forceinline__ double mg_constraint_residual(const mg_score_args &a,
         // _point_distance: axes whose target is NaN (the reference's None) are ignored
         double ds = 0.0;
         if (a.align) {
-            const double x = channel(r0), z = channel(r0 + 2);
-            const double pj[3] = {al.c * x + al.s * z + al.tx, channel(r0 + 1) + al.ty, al.c * z - al.s * x + al.tz};
+            double pj[3] = {channel(r0), channel(r0 + 1), channel(r0 + 2)};
+            mg_align_position(al, pj[0], pj[1], pj[2]);
 #pragma unroll
             for (int i = 0; i < 3; i++) {
                 double t = par[2 + i];
@@ -290,7 +284,8 @@ __device__ __forceinline__ double mg_constraint_residual(const mg_score_args &a,
     const double rx = par[5], ry = par[6], rz = par[7];
     const double lx = (1.0 - s2 * (qy * qy + qz * qz)) * rx + s2 * (qx * qy - qz * qw) * ry + s2 * (qx * qz + qy * qw) * rz;
     const double lz = s2 * (qx * qz - qy * qw) * rx + s2 * (qy * qz + qx * qw) * ry + (1.0 - s2 * (qx * qx + qy * qy)) * rz;
-    const double px = a.align ? al.c * lx + al.s * lz : lx, pz = a.align ? al.c * lz - al.s * lx : lz;
+    double px = lx, pz = lz;
+    if (a.align) mg_align_direction(al, px, pz);
     // par[2..4]: the unit target (tx, tz) = target / |target| and sqrt(tx^2 + tz^2), made on the host by these very statements
     // (mg_constraint_par_row): tn = sqrt(t0^2 + t1^2), tx = t0 / tn, tz = t1 / tn
     const double tx = par[2], tz = par[3];

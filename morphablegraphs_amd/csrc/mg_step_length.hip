@@ -6,10 +6,10 @@
 // MG_SLEN_TILE candidates of ONE item and keeps everything between the latents and the two results in LDS:
 //
 //   constants   the item's 3 n_basis root rows of E' as [L][3 n_basis], their means, the canonical grid's tap rows: once per workgroup
-//   phase 1     control points  c[cand][i * 3 + d] = mean', then fma(E'[k][.], s[k], .) for k ascending: mg_back_project_coeffs(MG_F64)'s
-//               statement, one (candidate, row) per thread; consecutive lanes read consecutive doubles of E', the latent is a broadcast
+//   phase 1     control points  c[cand][i * 3 + d] = mean', then fma(E'[k][.], s[k], .) for k ascending (mg_control_point),
+//               one (candidate, row) per thread; consecutive lanes read consecutive doubles of E', the latent is a broadcast
 //   phase 2     segments        one (candidate, frame) per thread: the positions p[f][d] = w0 c0, then fma(w_j, c_j, .) for j = 1, 2, 3
-//               (mg_back_project_frames_f64's statement) of the segment's two ends in registers, d_f = sqrt(dx * dx + dz * dz), every
+//               (mg_taps4) of the segment's two ends in registers, d_f = sqrt(dx * dx + dz * dz), every
 //               operation rounded on its own
 //   phase 3     one lane per candidate adds d_1 .. d_{F-1} in frame order and states the distance; the only stores to global memory
 //
@@ -65,15 +65,10 @@ __host__ __device__ static inline mg_slen_layout mg_slen_layout_of(int L, int NB
     return y;
 }
 
-// channel d of the root at canonical frame f from a candidate's control points: four taps, mg_back_project_frames_f64's statement
+// channel d of the root at canonical frame f from a candidate's control points
 __device__ __forceinline__ double mg_slen_position(const double *cp, const double *sw, const int32_t *si0, int f, int d) {
     const double *c = cp + si0[f] * 3 + d;
-    const double *wq = sw + 4 * f;
-    double v = wq[0] * c[0];
-    v = fma(wq[1], c[3], v);
-    v = fma(wq[2], c[6], v);
-    v = fma(wq[3], c[9], v);
-    return v;
+    return mg_taps4(sw + 4 * f, c, 3);
 }
 
 template <bool LAT_F64>
@@ -120,9 +115,7 @@ __global__ __launch_bounds__(256) void mg_step_length_kernel(const mg_slen_args 
     for (int e = tid; e < ncand * NR; e += 256) {
         const int c = e / NR, j = e - c * NR;
         const double *s = slat + c * L;
-        double acc = smean[j];
-        for (int k = 0; k < L; k++) acc = fma(sE[k * NR + j], s[k], acc);
-        scp[e] = acc;
+        scp[e] = mg_control_point(smean[j], sE + j, (size_t)NR, L, [&](int k) { return s[k]; });
     }
     __syncthreads();
 

@@ -144,13 +144,9 @@ __global__ __launch_bounds__(MG_FA_BLOCK) void mg_frames_at_kernel(const double 
     const int tid = threadIdx.x;
     const int T = lens ? lens[b] : t_cap;
     if (T <= 0 || T > t_cap) return;     // (a length beyond the rows' capacity would overrun w / i0 and the row in `out`: the row is skipped)
-    for (int k = tid; k < L; k += MG_FA_BLOCK) s[k] = LAT_F64 ? ((const double *)lat)[b * ld + k] : (double)((const float *)lat)[b * ld + k];
+    for (int k = tid; k < L; k += MG_FA_BLOCK) s[k] = mg_load_lat<LAT_F64>(lat, b * ld + k);
     __syncthreads();
-    for (int r = tid; r < R; r += MG_FA_BLOCK) {
-        double acc = mean[r];
-        for (int k = 0; k < L; k++) acc = fma(Et64[(size_t)k * R + r], s[k], acc);
-        c[r] = acc;
-    }
+    for (int r = tid; r < R; r += MG_FA_BLOCK) c[r] = mg_control_point(mean[r], Et64 + r, (size_t)R, L, [&](int k) { return s[k]; });
     const double *tb = times + b * (int64_t)t_cap;
     for (int f = tid; f < T; f += MG_FA_BLOCK) mg_basis_row_dev(knots, NB + 4, tb[f], &i0[f], &w[4 * f]);
     __syncthreads();
@@ -159,10 +155,7 @@ __global__ __launch_bounds__(MG_FA_BLOCK) void mg_frames_at_kernel(const double 
         const int f = (int)(e / D), d = (int)(e - (int64_t)f * D);
         const double *cf = c + (size_t)i0[f] * D + d;
         const double *wf = w + 4 * f;
-        double v = wf[0] * cf[0];
-        v = fma(wf[1], cf[D], v);
-        v = fma(wf[2], cf[2 * D], v);
-        v = fma(wf[3], cf[3 * D], v);
+        const double v = mg_taps4(wf, cf, D);
         if (OUT_F64) ((double *)out)[(b * t_cap + f) * D + d] = v;
         else ((float *)out)[(b * t_cap + f) * D + d] = (float)v;
     }

@@ -22,6 +22,8 @@
 #include <vector>
 
 #include "mg_internal.h"
+#include "mg_score_device.h"
+#include "mg_spline_device.h"
 #include "mg_traj_device.h"
 
 struct mg_traj_args {
@@ -45,6 +47,21 @@ struct mg_traj_args {
 
 #define MG_TRAJ_BLOCK 64
 
+// The candidate's aligning transform (mg_candidate_alignment's for the root node): rotation about y and an xz translation, from the
+// first control point's rows -- root(r) yields row r of the candidate's root coefficient rows (NB x 3 positions, then the first control
+// point's quaternion).  The root's chain is its one quaternion: normalised and used as it is (multiplying it into the identity, the
+// general chain's first step, can flip the sign of a zero component).
+template <typename RootFn>
+__device__ __forceinline__ mg_align2d mg_traj_alignment(const mg_traj_args &a, RootFn root) {
+    if (a.align_mode == 0) return {1.0, 0.0, 0.0, 0.0, 0.0};
+    const double p0x = root(0), p0z = root(2);   // (formed once: root() may be a whole fma chain)
+    if (a.align_mode == 2) return mg_align2d_onto(a.al[0], a.al[1], a.al[2], a.al[3], p0x, p0z, a.al[4]);
+    double q[4] = {root(a.NB * 3 + 0), root(a.NB * 3 + 1), root(a.NB * 3 + 2), root(a.NB * 3 + 3)}, bx, bz;
+    mg_quat_normalise(q[0], q[1], q[2], q[3]);
+    mg_heading_xz(q, a.al[4], a.al[5], a.al[6], bx, bz);
+    return mg_align2d_from(a.al[0], a.al[1], bx, bz, a.al[2], a.al[3], p0x, p0z);
+}
+
 // POLY_LDS: the target spline's segment polynomials (12 n_seg + 3 doubles) are copied behind the rows and searched from there -- the walk
 // is a chain of dependent evaluations (about 17 per frame), each one a look-up of its segment: an LDS read instead of a trip to L2
 template <bool POLY_LDS>
@@ -65,37 +82,11 @@ __global__ __launch_bounds__(MG_TRAJ_BLOCK) void mg_trajectory_kernel(mg_traj_ar
     }
     if (!a.points) {
         for (int k = 0; k < a.L; k++)
-            ls[k * MG_TRAJ_BLOCK + tid] = a.lat_f64 ? ((const double *)a.lat)[bb * a.ld + k] : (double)((const float *)a.lat)[bb * a.ld + k];
-        for (int r = 0; r < rows; r++) {
-            double acc = a.mean[r];
-            const double *e = a.E + (size_t)r * a.L;
-            for (int k = 0; k < a.L; k++) acc = fma(e[k], ls[k * MG_TRAJ_BLOCK + tid], acc);
-            lc[r * MG_TRAJ_BLOCK + tid] = acc;
-        }
+            ls[k * MG_TRAJ_BLOCK + tid] = mg_load_lat(a.lat, a.lat_f64 != 0, bb * a.ld + k);
+        for (int r = 0; r < rows; r++)
+            lc[r * MG_TRAJ_BLOCK + tid] = mg_control_point(a.mean[r], a.E + (size_t)r * a.L, 1, a.L, [&](int k) { return ls[k * MG_TRAJ_BLOCK + tid]; });
     }
-    // the candidate's aligning transform (mg_score.hip's closed form): rotation about y and an xz translation
-    double ac = 1.0, as = 0.0, tx = 0.0, ty = 0.0, tz = 0.0;
-    if (a.align_mode != 0) {
-        if (a.align_mode == 2) {
-            ac = a.al[0]; as = a.al[1]; ty = a.al[4];
-        } else {
-            double qw = lc[(a.NB * 3 + 0) * MG_TRAJ_BLOCK + tid], qx = lc[(a.NB * 3 + 1) * MG_TRAJ_BLOCK + tid];
-            double qy = lc[(a.NB * 3 + 2) * MG_TRAJ_BLOCK + tid], qz = lc[(a.NB * 3 + 3) * MG_TRAJ_BLOCK + tid];
-            const double inv = 1.0 / sqrt(qw * qw + qx * qx + qy * qy + qz * qz);
-            qw *= inv; qx *= inv; qy *= inv; qz *= inv;
-            const double rx = a.al[4], ry = a.al[5], rz = a.al[6];
-            const double cx = qy * rz - qz * ry, cy = qz * rx - qx * rz, cz = qx * ry - qy * rx;
-            const double dx = qy * cz - qz * cy, dz = qx * cy - qy * cx;
-            double bx = rx + 2.0 * (qw * cx + dx), bz = rz + 2.0 * (qw * cz + dz);
-            const double bn = 1.0 / sqrt(bx * bx + bz * bz);
-            bx *= bn; bz *= bn;
-            ac = a.al[0] * bx + a.al[1] * bz;
-            as = a.al[0] * bz - a.al[1] * bx;
-        }
-        const double p0x = lc[0 * MG_TRAJ_BLOCK + tid], p0z = lc[2 * MG_TRAJ_BLOCK + tid];
-        tx = a.al[2] - (ac * p0x + as * p0z);
-        tz = a.al[3] - (ac * p0z - as * p0x);
-    }
+    const mg_align2d t = mg_traj_alignment(a, [&](int r) { return lc[r * MG_TRAJ_BLOCK + tid]; });
     const int G = a.G;
     const double invG = 1.0 / (double)G;
     double min_u = a.min_u, sum = 0.0;
@@ -103,19 +94,9 @@ __global__ __launch_bounds__(MG_TRAJ_BLOCK) void mg_trajectory_kernel(mg_traj_ar
         const int i0 = a.i0[f];
         const double *w = a.w + 4 * (size_t)f;
 #pragma unroll
-        for (int d = 0; d < 3; d++) {
-            double v = w[0] * lc[((i0 + 0) * 3 + d) * MG_TRAJ_BLOCK + tid];
-            v = fma(w[1], lc[((i0 + 1) * 3 + d) * MG_TRAJ_BLOCK + tid], v);
-            v = fma(w[2], lc[((i0 + 2) * 3 + d) * MG_TRAJ_BLOCK + tid], v);
-            v = fma(w[3], lc[((i0 + 3) * 3 + d) * MG_TRAJ_BLOCK + tid], v);
-            q[d] = v;
-        }
-        if (a.align_mode != 0) {
-            const double x = q[0], z = q[2];
-            q[0] = ac * x + as * z + tx;
-            q[2] = ac * z - as * x + tz;
-            q[1] += ty;
-        }
+        for (int d = 0; d < 3; d++)
+            q[d] = mg_taps4(w, lc + (i0 * 3 + d) * MG_TRAJ_BLOCK + tid, 3 * MG_TRAJ_BLOCK);
+        if (a.align_mode != 0) mg_align_position(t, q[0], q[1], q[2]);
     };
     if (a.search == 0) {
         // the reference's search: every lane walks ITS frames at its own pace (mg_traj_chain); the positions come from the caller's
@@ -174,37 +155,12 @@ __device__ __forceinline__ void mg_trajectory_coop_body(const mg_traj_args &a, c
     double *lp = lds + (a.points ? 0 : (size_t)MG_TRAJ_COOP_CANDS * (a.L + rows));
     for (int e = tid; e < a.n_seg * 12 + 3; e += MG_TRAJ_COOP_BLOCK) lp[e] = a.poly[e];
     if (!a.points) {
-        for (int k = sub; k < a.L; k += MG_TRAJ_W) ls[k] = a.lat_f64 ? ((const double *)a.lat)[bb * a.ld + k] : (double)((const float *)a.lat)[bb * a.ld + k];
+        for (int k = sub; k < a.L; k += MG_TRAJ_W) ls[k] = mg_load_lat(a.lat, a.lat_f64 != 0, bb * a.ld + k);
         __syncthreads();
-        for (int r = sub; r < rows; r += MG_TRAJ_W) {
-            double acc = a.mean[r];
-            const double *e = a.E + (size_t)r * a.L;
-            for (int k = 0; k < a.L; k++) acc = fma(e[k], ls[k], acc);
-            lc[r] = acc;
-        }
+        for (int r = sub; r < rows; r += MG_TRAJ_W) lc[r] = mg_control_point(a.mean[r], a.E + (size_t)r * a.L, 1, a.L, [&](int k) { return ls[k]; });
     }
     __syncthreads();
-    double ac = 1.0, as = 0.0, tx = 0.0, ty = 0.0, tz = 0.0;
-    if (a.align_mode != 0) {
-        if (a.align_mode == 2) {
-            ac = a.al[0]; as = a.al[1]; ty = a.al[4];
-        } else {
-            double qw = lc[a.NB * 3 + 0], qx = lc[a.NB * 3 + 1], qy = lc[a.NB * 3 + 2], qz = lc[a.NB * 3 + 3];
-            const double inv = 1.0 / sqrt(qw * qw + qx * qx + qy * qy + qz * qz);
-            qw *= inv; qx *= inv; qy *= inv; qz *= inv;
-            const double rx = a.al[4], ry = a.al[5], rz = a.al[6];
-            const double cx = qy * rz - qz * ry, cy = qz * rx - qx * rz, cz = qx * ry - qy * rx;
-            const double dx = qy * cz - qz * cy, dz = qx * cy - qy * cx;
-            double bx = rx + 2.0 * (qw * cx + dx), bz = rz + 2.0 * (qw * cz + dz);
-            const double bn = 1.0 / sqrt(bx * bx + bz * bz);
-            bx *= bn; bz *= bn;
-            ac = a.al[0] * bx + a.al[1] * bz;
-            as = a.al[0] * bz - a.al[1] * bx;
-        }
-        const double p0x = lc[0], p0z = lc[2];
-        tx = a.al[2] - (ac * p0x + as * p0z);
-        tz = a.al[3] - (ac * p0z - as * p0x);
-    }
+    const mg_align2d t = mg_traj_alignment(a, [&](int r) { return lc[r]; });
     const int G = a.G;
     const double invG = 1.0 / (double)G;
     double min_u = a.min_u, sum = 0.0;
@@ -221,20 +177,9 @@ __device__ __forceinline__ void mg_trajectory_coop_body(const mg_traj_args &a, c
             const int i0 = a.i0[f];
             const double *w = a.w + 4 * (size_t)f;
 #pragma unroll
-            for (int d = 0; d < 3; d++) {
-                double v = w[0] * lc[(i0 + 0) * 3 + d];
-                v = fma(w[1], lc[(i0 + 1) * 3 + d], v);
-                v = fma(w[2], lc[(i0 + 2) * 3 + d], v);
-                v = fma(w[3], lc[(i0 + 3) * 3 + d], v);
-                q[d] = v;
-            }
+            for (int d = 0; d < 3; d++) q[d] = mg_taps4(w, lc + i0 * 3 + d, 3);
         }
-        if (a.align_mode != 0) {
-            const double x = q[0], z = q[2];
-            q[0] = ac * x + as * z + tx;
-            q[2] = ac * z - as * x + tz;
-            q[1] += ty;
-        }
+        if (a.align_mode != 0) mg_align_position(t, q[0], q[1], q[2]);
         const double dist = mg_traj_closest_dist_coop<MG_TRAJ_W>(lp, a.n_seg, G, invG, &min_u, q);
         sum += dist;
         if (a.res && valid && sub == 0) a.res[b * a.T + f] = a.weight * dist;
@@ -265,35 +210,10 @@ __device__ __forceinline__ void mg_trajectory_stream_body(const mg_traj_args &a,
     double *ls = lds, *lp = lds + (size_t)a.L * MG_TRAJ_BLOCK;
     for (int e = tid; e < a.n_seg * 12 + 3; e += MG_TRAJ_BLOCK) lp[e] = a.poly[e];
     for (int k = 0; k < a.L; k++)
-        ls[k * MG_TRAJ_BLOCK + tid] = a.lat_f64 ? ((const double *)a.lat)[bb * a.ld + k] : (double)((const float *)a.lat)[bb * a.ld + k];
+        ls[k * MG_TRAJ_BLOCK + tid] = mg_load_lat(a.lat, a.lat_f64 != 0, bb * a.ld + k);
     __syncthreads();
-    auto row = [&](int r) {
-        double acc = a.mean[r];
-        const double *e = a.E + (size_t)r * a.L;
-        for (int k = 0; k < a.L; k++) acc = fma(e[k], ls[k * MG_TRAJ_BLOCK + tid], acc);
-        return acc;
-    };
-    double ac = 1.0, as = 0.0, tx = 0.0, ty = 0.0, tz = 0.0;
-    if (a.align_mode != 0) {
-        if (a.align_mode == 2) {
-            ac = a.al[0]; as = a.al[1]; ty = a.al[4];
-        } else {
-            double qw = row(a.NB * 3 + 0), qx = row(a.NB * 3 + 1), qy = row(a.NB * 3 + 2), qz = row(a.NB * 3 + 3);
-            const double inv = 1.0 / sqrt(qw * qw + qx * qx + qy * qy + qz * qz);
-            qw *= inv; qx *= inv; qy *= inv; qz *= inv;
-            const double rx = a.al[4], ry = a.al[5], rz = a.al[6];
-            const double cx = qy * rz - qz * ry, cy = qz * rx - qx * rz, cz = qx * ry - qy * rx;
-            const double dx = qy * cz - qz * cy, dz = qx * cy - qy * cx;
-            double bx = rx + 2.0 * (qw * cx + dx), bz = rz + 2.0 * (qw * cz + dz);
-            const double bn = 1.0 / sqrt(bx * bx + bz * bz);
-            bx *= bn; bz *= bn;
-            ac = a.al[0] * bx + a.al[1] * bz;
-            as = a.al[0] * bz - a.al[1] * bx;
-        }
-        const double p0x = row(0), p0z = row(2);
-        tx = a.al[2] - (ac * p0x + as * p0z);
-        tz = a.al[3] - (ac * p0z - as * p0x);
-    }
+    auto row = [&](int r) { return mg_control_point(a.mean[r], a.E + (size_t)r * a.L, 1, a.L, [&](int k) { return ls[k * MG_TRAJ_BLOCK + tid]; }); };
+    const mg_align2d t = mg_traj_alignment(a, row);
     const int G = a.G;
     const double invG = 1.0 / (double)G;
     double min_u = a.min_u, sum = 0.0;
@@ -319,19 +239,8 @@ __device__ __forceinline__ void mg_trajectory_stream_body(const mg_traj_args &a,
         }
         const double *w = a.w + 4 * (size_t)f;
 #pragma unroll
-        for (int d = 0; d < 3; d++) {
-            double v = w[0] * cw[0][d];
-            v = fma(w[1], cw[1][d], v);
-            v = fma(w[2], cw[2][d], v);
-            v = fma(w[3], cw[3][d], v);
-            q[d] = v;
-        }
-        if (a.align_mode != 0) {
-            const double x = q[0], z = q[2];
-            q[0] = ac * x + as * z + tx;
-            q[2] = ac * z - as * x + tz;
-            q[1] += ty;
-        }
+        for (int d = 0; d < 3; d++) q[d] = mg_taps4(w, &cw[0][d], 3);
+        if (a.align_mode != 0) mg_align_position(t, q[0], q[1], q[2]);
     };
     if (a.search == 0) {
         // the reference's search: first the whole path, frame by frame with the window in registers (the lanes in step), into the

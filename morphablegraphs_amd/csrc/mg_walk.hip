@@ -10,7 +10,7 @@
 //                           aligning joint's chain reads (root translation + the chain's quaternions) at the FIRST control point
 //                           and at the four taps of the LAST sample, lanes over (control point, channel) pairs (fma chains from the
 //                           mean: the float64 frames kernels' arithmetic); one lane forms the step's heading, the transform
-//                           (mg_align_frames' statements) and the aligned exit pose the next step is aligned to.
+//                           (mg_align2d_from, mg_align_half_angle) and the aligned exit pose the next step is aligned to.
 //   mg_walk_frames_kernel   grid over (walk, step, tile of MG_WALK_TILE frames): the tile's basis rows (the canonical grid's
 //                           tables, or the FITPACK recurrence at the walk's own times), the control points of the tile's window,
 //                           four taps per channel, the step's transform on the seven root channels, every row stored once at its
@@ -62,11 +62,6 @@ struct mg_walk_args {
 };
 
 template <bool LAT_F64>
-__device__ __forceinline__ double mg_walk_lat(const void *lat, int64_t idx) {
-    return LAT_F64 ? ((const double *)lat)[idx] : (double)((const float *)lat)[idx];
-}
-
-template <bool LAT_F64>
 __global__ __launch_bounds__(MG_WALK_CHAIN_BLOCK) void mg_walk_chain_kernel(const mg_walk_args a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int nch = 3 + 4 * a.n_link;
@@ -80,7 +75,7 @@ __global__ __launch_bounds__(MG_WALK_CHAIN_BLOCK) void mg_walk_chain_kernel(cons
     for (int i = 0; i < a.n_steps; i++) {
         const mg_walk_step st = a.steps[i];
         const int64_t ws = wk * a.n_steps + i;
-        for (int k = tid; k < st.L; k += MG_WALK_CHAIN_BLOCK) s[k] = mg_walk_lat<LAT_F64>(a.lat, wk * a.ld + st.lat_off + k);
+        for (int k = tid; k < st.L; k += MG_WALK_CHAIN_BLOCK) s[k] = mg_load_lat<LAT_F64>(a.lat, wk * a.ld + st.lat_off + k);
         if (tid == 0) {
             if (a.times) {
                 const int len = a.lengths[ws];
@@ -96,69 +91,45 @@ __global__ __launch_bounds__(MG_WALK_CHAIN_BLOCK) void mg_walk_chain_kernel(cons
             const int j = e / nch, q = e - j * nch;
             const int ch = q < 3 ? q : a.link[(q - 3) >> 2] + ((q - 3) & 3);
             const int r = (j == 0 ? 0 : il + j - 1) * D + ch;
-            double acc = st.mean[r];
-            for (int k = 0; k < st.L; k++) acc = fma(st.Et64[(size_t)k * st.R + r], s[k], acc);
-            cpv[e] = acc;
+            cpv[e] = mg_control_point(st.mean[r], st.Et64 + r, (size_t)st.R, st.L, [&](int k) { return s[k]; });
         }
         __syncthreads();
         if (tid == 0) {
-            auto last = [&](int q) {       // the last sample's channel: four taps (mg_back_project_frames_f64's statement)
-                double v = wl[0] * cpv[nch + q];
-                v = fma(wl[1], cpv[2 * nch + q], v);
-                v = fma(wl[2], cpv[3 * nch + q], v);
-                v = fma(wl[3], cpv[4 * nch + q], v);
-                return v;
-            };
+            auto last = [&](int q) { return mg_taps4(wl, cpv + nch + q, nch); };   // the last sample's channel
             // heading of the aligning node: its global orientation applied to ref_dir, xz, unit.  turn: the root's quaternion
             // carries the step's rotation already (the aligned exit pose)
             auto heading = [&](bool at_last, bool turn, double qaw, double qay, double &ox, double &oz) {
-                double aw = 1.0, ax = 0.0, ay = 0.0, az = 0.0;
+                double q4[4] = {1.0, 0.0, 0.0, 0.0};
                 for (int l = 0; l < a.n_link; l++) {
                     const int q = 3 + 4 * l;
                     double qw = at_last ? last(q) : cpv[q], qx = at_last ? last(q + 1) : cpv[q + 1];
                     double qy = at_last ? last(q + 2) : cpv[q + 2], qz = at_last ? last(q + 3) : cpv[q + 3];
-                    if (turn && a.link[l] == 3) {   // (cos(phi / 2), 0, sin(phi / 2), 0) x q: mg_align_frames_kernel's statements
-                        const double w0 = qw, x0 = qx, y0 = qy, z0 = qz;
-                        qw = qaw * w0 - qay * y0;
-                        qx = qaw * x0 + qay * z0;
-                        qy = qaw * y0 + qay * w0;
-                        qz = qaw * z0 - qay * x0;
-                    }
-                    const double inv = 1.0 / sqrt(qw * qw + qx * qx + qy * qy + qz * qz);
-                    qw *= inv; qx *= inv; qy *= inv; qz *= inv;
-                    const double nw = aw * qw - ax * qx - ay * qy - az * qz, nx = aw * qx + ax * qw + ay * qz - az * qy;
-                    const double ny = aw * qy - ax * qz + ay * qw + az * qx, nz = aw * qz + ax * qy - ay * qx + az * qw;
-                    aw = nw; ax = nx; ay = ny; az = nz;
+                    if (turn && a.link[l] == 3) mg_align_root_quat(qaw, qay, qw, qx, qy, qz);
+                    mg_quat_accumulate(q4, qw, qx, qy, qz);
                 }
-                double q4[4] = {aw, ax, ay, az}, v[3];
-                mg_rotate(q4, a.ref[0], a.ref[1], a.ref[2], v);
-                const double inv = 1.0 / sqrt(v[0] * v[0] + v[2] * v[2]);
-                ox = v[0] * inv; oz = v[2] * inv;
+                mg_heading_xz(q4, a.ref[0], a.ref[1], a.ref[2], ox, oz);
             };
             const bool aligned = i > 0 || a.align_mode != 0;
-            double c = 1.0, sn = 0.0, tx = 0.0, tz = 0.0, ty = 0.0, qaw = 1.0, qay = 0.0;
+            mg_align2d t = {1.0, 0.0, 0.0, 0.0, 0.0};
+            double qaw = 1.0, qay = 0.0;
             if (aligned) {
                 const double p0x = cpv[0], p0z = cpv[2];   // the first control point: a clamped spline's value at t = 0
                 if (i == 0 && a.align_mode == 2) {
-                    c = a.h0; sn = a.h1; ty = a.py;
+                    t = mg_align2d_onto(a.h0, a.h1, tpx, tpz, p0x, p0z, a.py);
                 } else {
                     double bx, bz;
                     heading(false, false, 1.0, 0.0, bx, bz);
-                    c = hx * bx + hz * bz;
-                    sn = hx * bz - hz * bx;
+                    t = mg_align2d_from(hx, hz, bx, bz, tpx, tpz, p0x, p0z);
                 }
-                tx = tpx - (c * p0x + sn * p0z);
-                tz = tpz - (c * p0z - sn * p0x);
-                const double phi = atan2(sn, c);
-                qaw = cos(0.5 * phi); qay = sin(0.5 * phi);
+                mg_align_half_angle(t.c, t.s, qaw, qay);
             }
             double *xf = a.xf + ws * 8;
-            xf[0] = c; xf[1] = sn; xf[2] = tx; xf[3] = tz; xf[4] = ty; xf[5] = qaw; xf[6] = qay; xf[7] = aligned ? 1.0 : 0.0;
-            if (a.transforms) { double *t = a.transforms + ws * 4; t[0] = c; t[1] = sn; t[2] = tx; t[3] = tz; }
+            xf[0] = t.c; xf[1] = t.s; xf[2] = t.tx; xf[3] = t.tz; xf[4] = t.ty; xf[5] = qaw; xf[6] = qay; xf[7] = aligned ? 1.0 : 0.0;
+            if (a.transforms) { double *tr = a.transforms + ws * 4; tr[0] = t.c; tr[1] = t.s; tr[2] = t.tx; tr[3] = t.tz; }
             if (i + 1 < a.n_steps) {       // the aligned last sample: what the next step is aligned to
-                const double x = last(0), z = last(2);
-                tpx = aligned ? c * x + sn * z + tx : x;
-                tpz = aligned ? c * z - sn * x + tz : z;
+                double y = 0.0;            // (its height is not needed)
+                tpx = last(0); tpz = last(2);
+                if (aligned) mg_align_position(t, tpx, y, tpz);
                 heading(true, aligned, qaw, qay, hx, hz);
             }
         }
@@ -192,16 +163,14 @@ __global__ __launch_bounds__(MG_WALK_BLOCK) void mg_walk_frames_kernel(const mg_
             for (int j = 0; j < 4; j++) wt[4 * tid + j] = st.w[4 * (size_t)(f0 + tid) + j];
         }
     }
-    for (int k = tid; k < st.L; k += MG_WALK_BLOCK) s[k] = mg_walk_lat<LAT_F64>(a.lat, wk * a.ld + st.lat_off + k);
+    for (int k = tid; k < st.L; k += MG_WALK_BLOCK) s[k] = mg_load_lat<LAT_F64>(a.lat, wk * a.ld + st.lat_off + k);
     __syncthreads();
     int imin = i0t[0], imax = i0t[0];
     for (int f = 1; f < nf; f++) { const int v = i0t[f]; imin = v < imin ? v : imin; imax = v > imax ? v : imax; }
     const int rows = (imax + 4 - imin) * D, r0 = imin * D;
     for (int e = tid; e < rows; e += MG_WALK_BLOCK) {   // control points: fma chain over k ascending from the mean
         const int r = r0 + e;
-        double acc = st.mean[r];
-        for (int k = 0; k < st.L; k++) acc = fma(st.Et64[(size_t)k * st.R + r], s[k], acc);
-        cp[e] = acc;
+        cp[e] = mg_control_point(st.mean[r], st.Et64 + r, (size_t)st.R, st.L, [&](int k) { return s[k]; });
     }
     __syncthreads();
     const double *xf = a.xf + ws * 8;
@@ -210,16 +179,12 @@ __global__ __launch_bounds__(MG_WALK_BLOCK) void mg_walk_frames_kernel(const mg_
     auto value = [&](int e) {
         const int f = e / D, d = e - f * D;
         const double *cf = cp + (size_t)(i0t[f] - imin) * D, *wf = wt + 4 * f;
-        auto chan = [&](int ch) {
-            double v = wf[0] * cf[ch];
-            v = fma(wf[1], cf[D + ch], v);
-            v = fma(wf[2], cf[2 * D + ch], v);
-            v = fma(wf[3], cf[3 * D + ch], v);
-            return v;
-        };
+        auto chan = [&](int ch) { return mg_taps4(wf, cf + ch, D); };
         const double v = chan(d);
         if (!aligned || d >= 7) return v;
-        switch (d) {                       // mg_align_frames_kernel's statements, one channel at a time
+        // mg_align_position's and mg_align_root_quat's statements, one channel at a time: a lane owns one channel and forms only
+        // the partner it needs, which the helpers' whole-pose form cannot express
+        switch (d) {
         case 0: return c * v + sn * chan(2) + tx;
         case 1: return v + ty;
         case 2: return c * v - sn * chan(0) + tz;

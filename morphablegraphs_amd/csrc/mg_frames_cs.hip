@@ -339,7 +339,7 @@ __global__ __launch_bounds__(MG_CS_BLOCK) void mg_frames_cs_kernel(
         const int lane_img = (SPLIT && root_lane) ? 0 : ((root_lane ? nroot : d0) + a.cshift) * 4;
         const float *lds_m = (const float *)ro_base;    // SPLIT: {Mhi, Mlo} per sample of the chunk (where the root outputs would be)
         const int lane_out = fsub * D + d0;               // float offset inside a row group
-        const bool all4 = nroot == 3 && ((D - nroot) & 3) == 0;   // every lane stores four floats (see the tile-major kernel)
+        const bool all4 = nql > 0 && nroot == 3 && ((D - nroot) & 3) == 0;   // every lane stores four floats (see the tile-major kernel)
         const int q0_lane = (lane - nql) << 2;            // byte index of this row's quad lane 0 for ds_bpermute
         const unsigned lane_out_b = (unsigned)lane_out * 4u;
         const float4 *lds_w = (const float4 *)tb_base;

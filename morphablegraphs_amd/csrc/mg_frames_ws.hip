@@ -77,8 +77,9 @@ __global__ __launch_bounds__(MG_WS_BLOCK) void mg_frames_ws_kernel(
         const int lane_out = fsub * D + d0;               // float offset inside a row group
         // When every quad lane holds four floats and the root lane three (D = 79: 3 + 19 x 4), the root lane borrows the
         // row's channel 3 from quad lane 0 (a cross-lane read) and ALL lanes store four floats with one instruction;
-        // the float written twice carries the same value.  Otherwise lanes store 4 / 3 / 2 / 1 floats by class.
-        const bool all4 = nroot == 3 && ((D - nroot) & 3) == 0;
+        // the float written twice carries the same value.  Otherwise lanes store 4 / 3 / 2 / 1 floats by class (D = 3 as
+        // well: no quad lane, no channel 3 to borrow -- a fourth float would land on the next sample's first channel).
+        const bool all4 = nql > 0 && nroot == 3 && ((D - nroot) & 3) == 0;
         const int q0_lane = (lane - nql) << 2;            // byte index of this row's quad lane 0 for ds_bpermute
         const unsigned lane_out_b = (unsigned)lane_out * 4u;
         int slot = 0;

@@ -118,6 +118,8 @@ SHAPES = [
     _row(14, 4, Lt=5),                 # Lg = 19: the mixture in KK 6, the frames in KK 4
     _row(38, 5, Lt=6),                 # Lg = 44: the mixture in KK 12, the frames in KK 10
     _row(62, 3, D=15, Lt=4),           # Lg = 66: the mixture on the VALU kernels, the frames on KK 16
+    _row(13, 5, D=22),                 # KK 4 and KK 12 at a channel count that is not 3 (mod 4): the sweep waves' last quad lane
+    _row(45, 4, D=22),                 # stores three floats, the root lane three (no lane stores a borrowed float)
 ]
 SHAPE_IDS = [s["name"] for s in SHAPES]
 
@@ -173,7 +175,7 @@ def test_table_straddles_every_dispatch_boundary():
     # both sides of the spilling instances: chunk-stationary by choice at KK 14 for float32, not for float64
     assert not cs_spills(14, False) and cs_spills(14, True) and cs_spills(16, False) and not cs_spills(12, True)
     assert any(s["grid"] == "walk" for s in SHAPES) and {s["name"] for s in SHAPES} == set(SHAPE_IDS) and len(SHAPE_IDS) == len(SHAPES)
-    assert any(d % 4 for d in (s["model"]["n_dim"] for s in SHAPES))
+    assert any((d - 3) % 4 for d in (s["model"]["n_dim"] for s in SHAPES))     # a channel count whose last quad is partial
 
 
 def test_device_sampler_restatement_draws_standard_normals_and_the_mixture():

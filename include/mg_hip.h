@@ -467,6 +467,30 @@ int mg_score_trajectories(int32_t n, mg_primitive *const *prims, const mg_trajec
                           int latent_dtype, int64_t n_samples, const int64_t *ld, const double *min_u, const double *weight,
                           const mg_alignment_desc *const *alignments, double *const *errors_dev, int accumulate);
 
+/* Which kernel the three entry points above and below launch, stated once (mg_traj_plan in csrc/mg_trajectory.hip) and readable
+ * without a launch: for a primitive of n_components latents and `rows` = 3 n_basis + 4 root coefficient rows, a target spline of
+ * n_seg = n_points - 1 segments, n_samples candidates per scorer and `total` candidates in flight (n x n_samples for the n scorers of
+ * mg_score_trajectories, n_samples otherwise), on the root rows (points = 0) or on given points (points != 0), under the context's
+ * MG_OPT_TRAJECTORY_LANES and MG_OPT_TRAJECTORY_SEARCH.  together: the scorer fits the side-by-side launch of mg_score_trajectories
+ * (which is taken when EVERY scorer's plan says so; lds_bytes is then the largest of theirs); otherwise the plan is the single
+ * launch's.  needs_paths: the kernel writes the candidates' root paths to the context's scratch first (the reference's search in the
+ * streaming kernels).  MG_ERR_UNSUPPORTED where mg_score_trajectory reports it.  Launches nothing. */
+#define MG_TRAJ_KERNEL_STAGED_LDS 0      /* mg_trajectory_kernel<true>: rows (or nothing, on points) and the polynomials in LDS */
+#define MG_TRAJ_KERNEL_STAGED_GLOBAL 1   /* mg_trajectory_kernel<false>: the polynomials stay in global memory */
+#define MG_TRAJ_KERNEL_STREAM 2          /* mg_trajectory_stream_kernel */
+#define MG_TRAJ_KERNEL_COOP8 3           /* mg_trajectory_coop_kernel<8> */
+#define MG_TRAJ_KERNEL_COOP4 4           /* mg_trajectory_coop_kernel<4> */
+#define MG_TRAJ_KERNEL_STREAM_MULTI 5    /* mg_trajectory_stream_multi_kernel */
+#define MG_TRAJ_KERNEL_COOP8_MULTI 6     /* mg_trajectory_coop_multi_kernel<8> */
+#define MG_TRAJ_KERNEL_COOP4_MULTI 7     /* mg_trajectory_coop_multi_kernel<4> */
+#define MG_TRAJ_KERNEL_COUNT 8
+typedef struct mg_trajectory_plan_info {
+    int32_t kernel, lanes, poly_lds, needs_paths, together, candidates_per_workgroup;
+    int64_t lds_bytes;
+} mg_trajectory_plan_info;
+int mg_trajectory_plan(const mg_context *ctx, int32_t n_components, int32_t rows, int32_t n_seg, int64_t n_samples, int64_t total, int32_t points,
+                       mg_trajectory_plan_info *out);
+
 /* The same search for positions the caller supplies: points_dev (n_samples, n_times, 3) float64 -- one joint's track from
  * mg_back_project_frames_f64 + mg_joint_positions, aligned by the caller -- for TrajectoryConstraint on joints other than the
  * root (trajectory_constraint.py:95-121 over skeleton.nodes[joint].get_global_position(frame)). */

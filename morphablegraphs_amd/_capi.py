@@ -73,7 +73,7 @@ EXPORTED_SYMBOLS = [
     "mg_memset", "mg_profile_enable", "mg_profile_reset", "mg_profile_get", "mg_profile_get_samples",
     "mg_primitive_create", "mg_primitive_destroy", "mg_primitive_info", "mg_primitive_info2", "mg_primitive_root_mode", "mg_primitive_get_precisions_cholesky",
     "mg_time_function_canonical", "mg_time_function_canonical_host", "mg_time_function_sample", "mg_time_function_sample_rows", "mg_back_project_frames_at",
-    "mg_trajectory_create", "mg_trajectory_destroy", "mg_score_trajectory", "mg_score_trajectories", "mg_score_trajectory_points", "mg_trajectory_closest_points", "mg_joint_positions",
+    "mg_trajectory_create", "mg_trajectory_destroy", "mg_score_trajectory", "mg_score_trajectories", "mg_score_trajectory_points", "mg_trajectory_closest_points", "mg_trajectory_plan", "mg_joint_positions",
     "mg_time_grid_create", "mg_time_grid_destroy", "mg_primitive_canonical_grid", "mg_time_grid_size",
     "mg_time_grid_get_tables",
     "mg_back_project_frames", "mg_back_project_frames_f64", "mg_back_project_coeffs", "mg_spline_evaluate",
@@ -148,6 +148,14 @@ class FrameConstraintDesc(C.Structure):   # struct mg_frame_constraint_desc
                 ("start_arc", C.c_double), ("trajectories", C.c_void_p * MG_FRAME_MAX_JOINTS), ("arc0", C.c_double * MG_FRAME_MAX_JOINTS),
                 ("range_start", C.c_double * MG_FRAME_MAX_JOINTS), ("range_end", C.c_double * MG_FRAME_MAX_JOINTS),
                 ("has_range", C.c_int32 * MG_FRAME_MAX_JOINTS), ("quaternion", C.c_double * 4)]
+
+
+class TrajectoryPlanInfo(C.Structure):   # struct mg_trajectory_plan_info
+    _fields_ = [("kernel", C.c_int32), ("lanes", C.c_int32), ("poly_lds", C.c_int32), ("needs_paths", C.c_int32), ("together", C.c_int32),
+                ("candidates_per_workgroup", C.c_int32), ("lds_bytes", C.c_int64)]
+
+
+MG_TRAJ_KERNELS = ("staged_lds", "staged_global", "stream", "coop8", "coop4", "stream_multi", "coop8_multi", "coop4_multi")   # MG_TRAJ_KERNEL_*
 
 
 def _quat_mul(a, b):
@@ -302,6 +310,7 @@ def load_library(path=None):
         "mg_score_trajectories": [i32, vp, vp, vp, i32, i64, vp, vp, vp, vp, vp, i32],
         "mg_score_trajectory_points": [vp, vp, vp, i64, i32, dbl, dbl, vp, i32, vp],
         "mg_trajectory_closest_points": [vp, vp, vp, i64, i32, dbl, vp, vp, vp],
+        "mg_trajectory_plan": [vp, i32, i32, i32, i64, i64, i32, vp],
         "mg_align_frames": [vp, vp, i64, i32, vp, i32, C.POINTER(AlignmentDesc)],
         "mg_frame_constraint_width": [C.POINTER(FrameConstraintDesc), i32],
         "mg_score_frame_constraint": [vp, C.POINTER(FrameConstraintDesc), vp, i64, i32, i32, vp, i32, vp],
@@ -459,6 +468,17 @@ class Context(object):
         r, u = C.c_int64(0), C.c_int64(0)
         _check(self.lib.mg_context_arena_bytes(self.handle, C.byref(r), C.byref(u)))
         return int(r.value), int(u.value)
+
+    def trajectory_plan(self, n_components, rows, n_seg, n, total=None, points=False):
+        """mg_trajectory_plan: the kernel the trajectory scorers launch for n candidates per scorer (`total` in flight) of a primitive
+        with n_components latents and rows = 3 n_basis + 4 root rows against a spline of n_seg segments, under this context's options;
+        launches nothing.  MGError (MG_ERR_UNSUPPORTED) where mg_score_trajectory raises it."""
+        info = TrajectoryPlanInfo()
+        _check(self.lib.mg_trajectory_plan(self.handle, int(n_components), int(rows), int(n_seg), int(n), int(n if total is None else total),
+                                           1 if points else 0, C.byref(info)))
+        return {"kernel": MG_TRAJ_KERNELS[info.kernel], "lanes": int(info.lanes), "poly_lds": bool(info.poly_lds),
+                "needs_paths": bool(info.needs_paths), "together": bool(info.together),
+                "candidates_per_workgroup": int(info.candidates_per_workgroup), "lds_bytes": int(info.lds_bytes)}
 
     def synchronize(self):
         _check(self.lib.mg_context_synchronize(self.handle))

@@ -307,6 +307,67 @@ static int mg_traj_lanes(const mg_context *ctx, int64_t B, int64_t total) {
     return total <= MG_TRAJ_W8_MAX_TOTAL ? 8 : (total <= MG_TRAJ_W4_MAX_TOTAL ? 4 : 1);
 }
 
+// THE DISPATCH, stated once: which kernel scores B candidates per scorer (`total` in flight: n x B for the n scorers of
+// mg_score_trajectories, B otherwise) of a primitive with L latents and `rows` root coefficient rows against a spline of n_seg
+// segments, on the root rows or on given points -- and with how many lanes per candidate, how much LDS, whether the kernel needs the
+// context's path scratch and whether the scorer fits the side-by-side launch.  Pure host arithmetic; every entry point calls it
+// and mg_trajectory_plan reports it (tests/test_gpu_trajectory_shapes.py restates it and pins it line by line).
+struct mg_traj_plan_t { int kernel, lanes, cands; bool poly_lds, needs_paths, together; size_t lds_bytes; };
+static int mg_traj_plan(const mg_context *ctx, int L, int rows, int n_seg, int64_t B, int64_t total, bool points, int search, mg_traj_plan_t *out) {
+    mg_traj_plan_t pl = {MG_TRAJ_KERNEL_STAGED_LDS, 1, MG_TRAJ_BLOCK, true, false, false, 0};
+    const size_t poly_bytes = ((size_t)n_seg * 12 + 3) * 8;
+    if (points) {
+        pl.lanes = poly_bytes <= 60 * 1024 ? mg_traj_lanes(ctx, B, B) : 1;
+        pl.poly_lds = pl.lanes > 1 || poly_bytes <= 158 * 1024;
+        pl.lds_bytes = pl.poly_lds ? poly_bytes : 0;
+        pl.kernel = pl.lanes == 8 ? MG_TRAJ_KERNEL_COOP8 : pl.lanes == 4 ? MG_TRAJ_KERNEL_COOP4 : pl.poly_lds ? MG_TRAJ_KERNEL_STAGED_LDS : MG_TRAJ_KERNEL_STAGED_GLOBAL;
+        pl.cands = MG_TRAJ_COOP_BLOCK / pl.lanes;
+        *out = pl;
+        return MG_OK;
+    }
+    if (total > B) {        // one of several scorers: side by side where its rows and polynomials fit the cooperative or the streaming form
+        const int lanes = mg_traj_lanes(ctx, B, total);
+        const bool coop = lanes > 1;
+        const int coop_cands = MG_TRAJ_COOP_BLOCK / lanes;
+        const size_t need = coop ? (size_t)coop_cands * (L + rows) * 8 + poly_bytes
+                                 : (size_t)L * MG_TRAJ_BLOCK * 8 + poly_bytes;
+        if (need <= 60 * 1024) {
+            pl.kernel = lanes == 8 ? MG_TRAJ_KERNEL_COOP8_MULTI : lanes == 4 ? MG_TRAJ_KERNEL_COOP4_MULTI : MG_TRAJ_KERNEL_STREAM_MULTI;
+            pl.lanes = lanes; pl.cands = coop ? coop_cands : MG_TRAJ_BLOCK; pl.lds_bytes = need;
+            pl.needs_paths = !coop && search == 0; pl.together = true;
+            *out = pl;
+            return MG_OK;
+        }
+    }
+    size_t lds = (size_t)(L + rows) * MG_TRAJ_BLOCK * 8;
+    if (lds > 150 * 1024) { mg_set_error("mg_score_trajectory: %d basis functions x %d components do not fit LDS", (rows - 4) / 3, L); return MG_ERR_UNSUPPORTED; }
+    const bool poly_lds = lds + poly_bytes <= 158 * 1024;
+    if (poly_lds) lds += poly_bytes;
+    int lanes = mg_traj_lanes(ctx, B, B);
+    const int coop_cands = MG_TRAJ_COOP_BLOCK / std::max(lanes, 1);
+    const size_t coop_lds = (size_t)coop_cands * (L + rows) * 8 + poly_bytes;
+    if (coop_lds > 60 * 1024) lanes = 1;
+    const size_t stream_lds = (size_t)L * MG_TRAJ_BLOCK * 8 + poly_bytes;
+    pl.lanes = lanes; pl.cands = MG_TRAJ_COOP_BLOCK / lanes;
+    if (lanes > 1) { pl.kernel = lanes == 8 ? MG_TRAJ_KERNEL_COOP8 : MG_TRAJ_KERNEL_COOP4; pl.lds_bytes = coop_lds; }
+    else if (stream_lds <= 60 * 1024) { pl.kernel = MG_TRAJ_KERNEL_STREAM; pl.lds_bytes = stream_lds; pl.needs_paths = search == 0; }
+    else { pl.kernel = poly_lds ? MG_TRAJ_KERNEL_STAGED_LDS : MG_TRAJ_KERNEL_STAGED_GLOBAL; pl.poly_lds = poly_lds; pl.lds_bytes = lds; }
+    *out = pl;
+    return MG_OK;
+}
+extern "C" int mg_trajectory_plan(const mg_context *ctx, int32_t n_components, int32_t rows, int32_t n_seg, int64_t n_samples, int64_t total, int32_t points,
+                                  mg_trajectory_plan_info *out) {
+    if (!ctx || !out || n_components < 1 || rows < 4 || n_seg < 1 || n_samples < 1 || total < 1) {
+        mg_set_error("mg_trajectory_plan: bad arguments");
+        return MG_ERR_INVALID_ARGUMENT;
+    }
+    mg_traj_plan_t pl;
+    const int rc = mg_traj_plan(ctx, n_components, rows, n_seg, n_samples, total, points != 0, ctx->opt[MG_OPT_TRAJECTORY_SEARCH] == 1 ? 1 : 0, &pl);
+    if (rc != MG_OK) return rc;
+    out->kernel = pl.kernel; out->lanes = pl.lanes; out->poly_lds = pl.poly_lds ? 1 : 0; out->needs_paths = pl.needs_paths ? 1 : 0;
+    out->together = pl.together ? 1 : 0; out->candidates_per_workgroup = pl.cands; out->lds_bytes = (int64_t)pl.lds_bytes;
+    return MG_OK;
+}
 // the context's buffer for the candidates' root paths (the reference's search in the streaming kernels): grown on demand, stream ordered
 static int mg_traj_paths(mg_context *ctx, size_t bytes, double **out) {
     if (ctx->traj_paths_bytes < bytes) {
@@ -460,6 +521,18 @@ static hipError_t mg_traj_lds_opt_in(mg_context *ctx) {
     return mg_lds_opt_in_once(ctx, MG_LDS_TRAJECTORY, 160 * 1024, mg_trajectory_kernel<false>, mg_trajectory_kernel<true>);
 }
 
+// the launch of one scorer by its plan (the multi kernels are launched by mg_score_trajectories itself)
+static void mg_traj_launch(mg_context *ctx, const mg_traj_plan_t &pl, const mg_traj_args &a) {
+    const dim3 grid((unsigned)((a.B + pl.cands - 1) / pl.cands)), block(MG_TRAJ_BLOCK);
+    switch (pl.kernel) {
+    case MG_TRAJ_KERNEL_COOP8: hipLaunchKernelGGL(mg_trajectory_coop_kernel<8>, grid, block, pl.lds_bytes, ctx->stream, a); break;
+    case MG_TRAJ_KERNEL_COOP4: hipLaunchKernelGGL(mg_trajectory_coop_kernel<4>, grid, block, pl.lds_bytes, ctx->stream, a); break;
+    case MG_TRAJ_KERNEL_STREAM: hipLaunchKernelGGL(mg_trajectory_stream_kernel, grid, block, pl.lds_bytes, ctx->stream, a); break;
+    case MG_TRAJ_KERNEL_STAGED_LDS: hipLaunchKernelGGL(mg_trajectory_kernel<true>, grid, block, pl.lds_bytes, ctx->stream, a); break;
+    default: hipLaunchKernelGGL(mg_trajectory_kernel<false>, grid, block, pl.lds_bytes, ctx->stream, a); break;
+    }
+}
+
 extern "C" int mg_score_trajectory(mg_primitive *p, const mg_trajectory *t, const mg_time_grid *g, const void *lat, int dt, int64_t B,
                                    int64_t ld, double min_u, double weight, const mg_alignment_desc *al, double *errors_dev,
                                    int accumulate, double *residuals_dev) {
@@ -467,26 +540,12 @@ extern "C" int mg_score_trajectory(mg_primitive *p, const mg_trajectory *t, cons
     { const int rc = mg_traj_fill_args("mg_score_trajectory", p, t, g, lat, dt, B, ld, min_u, weight, al, errors_dev, accumulate, residuals_dev, &a); if (rc != MG_OK) return rc; }
     if (B == 0) return MG_OK;
     MG_HIP_CHECK(hipSetDevice(p->ctx->device));
-    size_t lds = (size_t)(p->L + t->rows) * MG_TRAJ_BLOCK * 8;
-    if (lds > 150 * 1024) { mg_set_error("mg_score_trajectory: %d basis functions x %d components do not fit LDS", p->NB, p->L); return MG_ERR_UNSUPPORTED; }
-    const size_t poly_bytes = ((size_t)t->n_seg * 12 + 3) * 8;
-    const bool poly_lds = lds + poly_bytes <= 158 * 1024;
-    if (poly_lds) lds += poly_bytes;
+    mg_traj_plan_t pl;
+    { const int rc = mg_traj_plan(p->ctx, p->L, t->rows, t->n_seg, B, B, false, a.search, &pl); if (rc != MG_OK) return rc; }
     MG_HIP_CHECK(mg_traj_lds_opt_in(p->ctx));
-    const int grid = (int)((B + MG_TRAJ_BLOCK - 1) / MG_TRAJ_BLOCK);
-    int lanes = mg_traj_lanes(p->ctx, B, B);
-    const int coop_cands = MG_TRAJ_COOP_BLOCK / std::max(lanes, 1);
-    const size_t coop_lds = (size_t)coop_cands * (p->L + t->rows) * 8 + poly_bytes;
-    if (coop_lds > 60 * 1024) lanes = 1;
-    const size_t stream_lds = (size_t)p->L * MG_TRAJ_BLOCK * 8 + poly_bytes;
-    const dim3 coop_grid((unsigned)((B + coop_cands - 1) / coop_cands));
-    if (lanes == 1 && stream_lds <= 60 * 1024 && a.search == 0) { const int rcp = mg_traj_paths(p->ctx, (size_t)B * a.T * 24, &a.paths); if (rcp != MG_OK) return rcp; }
+    if (pl.needs_paths) { const int rcp = mg_traj_paths(p->ctx, (size_t)B * a.T * 24, &a.paths); if (rcp != MG_OK) return rcp; }
     mg_prof_begin(p->ctx, MG_PROF_TRAJECTORY);
-    if (lanes == 8) hipLaunchKernelGGL(mg_trajectory_coop_kernel<8>, coop_grid, dim3(MG_TRAJ_COOP_BLOCK), coop_lds, p->ctx->stream, a);
-    else if (lanes == 4) hipLaunchKernelGGL(mg_trajectory_coop_kernel<4>, coop_grid, dim3(MG_TRAJ_COOP_BLOCK), coop_lds, p->ctx->stream, a);
-    else if (stream_lds <= 60 * 1024) hipLaunchKernelGGL(mg_trajectory_stream_kernel, dim3(grid), dim3(MG_TRAJ_BLOCK), stream_lds, p->ctx->stream, a);
-    else if (poly_lds) hipLaunchKernelGGL(mg_trajectory_kernel<true>, dim3(grid), dim3(MG_TRAJ_BLOCK), lds, p->ctx->stream, a);
-    else hipLaunchKernelGGL(mg_trajectory_kernel<false>, dim3(grid), dim3(MG_TRAJ_BLOCK), lds, p->ctx->stream, a);
+    mg_traj_launch(p->ctx, pl, a);
     mg_prof_end(p->ctx, MG_PROF_TRAJECTORY);
     MG_HIP_CHECK(hipGetLastError());
     return MG_OK;
@@ -508,18 +567,15 @@ extern "C" int mg_score_trajectories(int32_t n, mg_primitive *const *prims, cons
         if (!prims[k] || prims[k]->ctx != prims[0]->ctx) { mg_set_error("mg_score_trajectories: the primitives must share one context"); return MG_ERR_INVALID_ARGUMENT; }
     mg_context *ctx = prims[0]->ctx;
     MG_HIP_CHECK(hipSetDevice(ctx->device));
-    const int lanes = mg_traj_lanes(ctx, B, (int64_t)n * B);
-    const bool coop = lanes > 1;
-    const int coop_cands = MG_TRAJ_COOP_BLOCK / lanes;
+    const int search = ctx->opt[MG_OPT_TRAJECTORY_SEARCH] == 1 ? 1 : 0;
     bool together = B > 0 && n > 1;
     size_t lds = 0;
+    mg_traj_plan_t pl = {};
     for (int k = 0; k < n && together; k++) {
         if (!trajectories[k]) { mg_set_error("mg_score_trajectories: trajectory %d is NULL", k); return MG_ERR_INVALID_ARGUMENT; }
-        const size_t poly_bytes = ((size_t)trajectories[k]->n_seg * 12 + 3) * 8;
-        const size_t need = coop ? (size_t)coop_cands * (prims[k]->L + trajectories[k]->rows) * 8 + poly_bytes
-                                 : (size_t)prims[k]->L * MG_TRAJ_BLOCK * 8 + poly_bytes;
-        if (need > 60 * 1024) together = false;
-        lds = std::max(lds, need);
+        // (a scorer that fits no kernel at all is reported by its own single launch below, after the scorers before it have run)
+        if (mg_traj_plan(ctx, prims[k]->L, trajectories[k]->rows, trajectories[k]->n_seg, B, (int64_t)n * B, false, search, &pl) != MG_OK || !pl.together) together = false;
+        else lds = std::max(lds, pl.lds_bytes);
     }
     if (!together) {
         for (int k = 0; k < n; k++) {
@@ -529,8 +585,7 @@ extern "C" int mg_score_trajectories(int32_t n, mg_primitive *const *prims, cons
         }
         return MG_OK;
     }
-    const int cands_per_wg = coop ? coop_cands : MG_TRAJ_BLOCK;
-    const int per = (int)((B + cands_per_wg - 1) / cands_per_wg);
+    const int per = (int)((B + pl.cands - 1) / pl.cands);      // (the scorers share B, the options and with them lanes and form)
     for (int k0 = 0; k0 < n; k0 += MG_TRAJ_MULTI_MAX) {
         mg_traj_multi m;
         memset(&m, 0, sizeof(m));
@@ -542,7 +597,7 @@ extern "C" int mg_score_trajectories(int32_t n, mg_primitive *const *prims, cons
             if (rc != MG_OK) return rc;
             m.wg0[i + 1] = m.wg0[i] + per;
         }
-        if (!coop && m.a[0].search == 0) {      // the streaming kernels' root paths: one block of the context's buffer per scorer
+        if (pl.needs_paths) {      // the streaming kernels' root paths: one block of the context's buffer per scorer
             size_t off = 0;
             double *base = nullptr;
             for (int i = 0; i < m.n; i++) off += (size_t)B * m.a[i].T * 3;
@@ -552,8 +607,8 @@ extern "C" int mg_score_trajectories(int32_t n, mg_primitive *const *prims, cons
             for (int i = 0; i < m.n; i++) { m.a[i].paths = base + off; off += (size_t)B * m.a[i].T * 3; }
         }
         mg_prof_begin(ctx, MG_PROF_TRAJECTORY);
-        if (lanes == 8) hipLaunchKernelGGL(mg_trajectory_coop_multi_kernel<8>, dim3((unsigned)m.wg0[m.n]), dim3(MG_TRAJ_COOP_BLOCK), lds, ctx->stream, m);
-        else if (lanes == 4) hipLaunchKernelGGL(mg_trajectory_coop_multi_kernel<4>, dim3((unsigned)m.wg0[m.n]), dim3(MG_TRAJ_COOP_BLOCK), lds, ctx->stream, m);
+        if (pl.kernel == MG_TRAJ_KERNEL_COOP8_MULTI) hipLaunchKernelGGL(mg_trajectory_coop_multi_kernel<8>, dim3((unsigned)m.wg0[m.n]), dim3(MG_TRAJ_COOP_BLOCK), lds, ctx->stream, m);
+        else if (pl.kernel == MG_TRAJ_KERNEL_COOP4_MULTI) hipLaunchKernelGGL(mg_trajectory_coop_multi_kernel<4>, dim3((unsigned)m.wg0[m.n]), dim3(MG_TRAJ_COOP_BLOCK), lds, ctx->stream, m);
         else hipLaunchKernelGGL(mg_trajectory_stream_multi_kernel, dim3((unsigned)m.wg0[m.n]), dim3(MG_TRAJ_BLOCK), lds, ctx->stream, m);
         mg_prof_end(ctx, MG_PROF_TRAJECTORY);
         MG_HIP_CHECK(hipGetLastError());
@@ -580,15 +635,11 @@ static int mg_traj_points_launch(const char *who, mg_primitive *p, const mg_traj
     a.search = p->ctx->opt[MG_OPT_TRAJECTORY_SEARCH] == 1 ? 1 : 0;
     a.align_mode = 0;
     for (double &v : a.al) v = 0.0;
-    const int grid = (int)((B + MG_TRAJ_BLOCK - 1) / MG_TRAJ_BLOCK);
-    const size_t poly_bytes = ((size_t)t->n_seg * 12 + 3) * 8;
+    mg_traj_plan_t pl;
+    { const int rc = mg_traj_plan(p->ctx, p->L, t->rows, t->n_seg, B, B, true, a.search, &pl); if (rc != MG_OK) return rc; }
     MG_HIP_CHECK(mg_traj_lds_opt_in(p->ctx));
     mg_prof_begin(p->ctx, MG_PROF_TRAJECTORY);
-    const int lanes = poly_bytes <= 60 * 1024 ? mg_traj_lanes(p->ctx, B, B) : 1;
-    if (lanes == 8) hipLaunchKernelGGL(mg_trajectory_coop_kernel<8>, dim3((unsigned)((B + 7) / 8)), dim3(MG_TRAJ_COOP_BLOCK), poly_bytes, p->ctx->stream, a);
-    else if (lanes == 4) hipLaunchKernelGGL(mg_trajectory_coop_kernel<4>, dim3((unsigned)((B + 15) / 16)), dim3(MG_TRAJ_COOP_BLOCK), poly_bytes, p->ctx->stream, a);
-    else if (poly_bytes <= 158 * 1024) hipLaunchKernelGGL(mg_trajectory_kernel<true>, dim3(grid), dim3(MG_TRAJ_BLOCK), poly_bytes, p->ctx->stream, a);
-    else hipLaunchKernelGGL(mg_trajectory_kernel<false>, dim3(grid), dim3(MG_TRAJ_BLOCK), 0, p->ctx->stream, a);
+    mg_traj_launch(p->ctx, pl, a);
     mg_prof_end(p->ctx, MG_PROF_TRAJECTORY);
     MG_HIP_CHECK(hipGetLastError());
     return MG_OK;

@@ -935,19 +935,20 @@ def closest_point(control_points, point, min_u, granularity=1000, search="refere
     return closest_point_lbfgsb(control_points, point, min_u, formk_rule=True)
 
 
-def closest_point_walk(control_points, point, min_u, granularity=1000):
+def closest_point_walk(control_points, point, min_u, granularity=1000, info=None):
     """The DEVICE's deterministic form of the same search (what mg_score_trajectory computes, restated): on the grid
     u_k = k / granularity walk forward from the first grid point at or after min_u while the distance falls, then refine
     the parameter by the parabola through the squared distances of the three grid points around the minimum, then by up to
     four Newton steps on the squared distance inside the bracket of those three grid points (clamped to [min_u, 1]): the
-    local minimum of the bracket to rounding, so never farther from the point than a converged search of the same basin."""
+    local minimum of the bracket to rounding, so never farther from the point than a converged search of the same basin.
+    info: a dict that receives the walk's first grid index "k0" and the index "k" it stops at (tests of the device's lane maps)."""
     target = np.asarray(point, dtype=np.float64)
     G = int(granularity)
 
     def d2(u):
         v = catmull_rom_point(control_points, u) - target
         return float(v @ v)
-    k = min(G, int(math.ceil(min_u * G - 1e-12)))
+    k = k0 = min(G, int(math.ceil(min_u * G - 1e-12)))
     dk = d2(k / G)
     d_start = d2(min_u)
     while k < G:
@@ -955,6 +956,8 @@ def closest_point_walk(control_points, point, min_u, granularity=1000):
         if dn >= dk:
             break
         k, dk = k + 1, dn
+    if info is not None:
+        info["k0"], info["k"] = k0, k
     u = k / G
     if 0 < k < G:
         a, b, c = d2((k - 1) / G), dk, d2((k + 1) / G)

@@ -455,6 +455,29 @@ int mg_joint_positions(mg_context *ctx, const mg_skeleton_desc *skeleton, const 
 typedef struct mg_trajectory mg_trajectory;
 int mg_trajectory_create(mg_primitive *prim, const double *control_points, int32_t n_points, int32_t granularity, mg_trajectory **out);
 void mg_trajectory_destroy(mg_trajectory *trajectory);
+/* The same object for any of the three curves the reference's ParameterizedSpline builds (parameterized_spline.py:36-63; the numbers
+ * are the reference's).  Every curve is held as cubic pieces on a uniform parameter grid plus the granularity + 1 arc-length table, so
+ * every entry point that takes a mg_trajectory takes all three:
+ *   MG_SPLINE_CATMULL_ROM     forwards to mg_trajectory_create: the same tables, the same bits
+ *   MG_SPLINE_BSPLINE         the clamped cubic B-spline over n_points - 2 uniform knot values (b_spline.py:70-105), n_points - 3
+ *                             pieces; u <= 0 is the first control point, u >= 1 the last
+ *   MG_SPLINE_FITTED_BSPLINE  FITPACK's splrep(linspace(0, 1, n_points), values, k = 3) with s = 0 per dimension
+ *                             (fitted_b_spline.py:44-47): the interpolating cubic with not-a-knot ends, n_points - 1 pieces
+ * Types 1 and 2 need n_points >= 4 (the reference's de Boor indexes out of range below, splrep needs m > k); an unknown type, fewer
+ * points, a non-finite coordinate: MG_ERR_INVALID_ARGUMENT, nothing is allocated or launched.  Host statement:
+ * morphablegraphs_amd/spline_types.py trajectory_polynomials_host; pinned by tests/golden/trajectory_spline_types.npz. */
+#define MG_SPLINE_CATMULL_ROM 0
+#define MG_SPLINE_BSPLINE 1
+#define MG_SPLINE_FITTED_BSPLINE 2
+int mg_trajectory_create_typed(mg_primitive *prim, const double *control_points, int32_t n_points, int32_t granularity, int32_t spline_type,
+                               mg_trajectory **out);
+/* the type a trajectory was created with (MG_SPLINE_*), -1 for NULL */
+int32_t mg_trajectory_spline_type(const mg_trajectory *trajectory);
+/* The two tables as the kernels read them, copied to the host (tests and tools): poly_host (n_seg * 12 + 3 doubles: per piece
+ * [power 3, 2, 1, 0][x, y, z] of the piece's local parameter, then the last control point) and arc_host (granularity + 1 relative arc
+ * lengths) are filled when not NULL; n_seg, granularity and full_arc_length are reported when not NULL. */
+int mg_trajectory_tables(const mg_trajectory *trajectory, double *poly_host, double *arc_host, int32_t *n_seg, int32_t *granularity,
+                         double *full_arc_length);
 int mg_score_trajectory(mg_primitive *prim, const mg_trajectory *trajectory, const mg_time_grid *grid, const void *latents_dev,
                         int latent_dtype, int64_t n_samples, int64_t ld, double min_u, double weight, const mg_alignment_desc *alignment,
                         double *errors_dev, int accumulate, double *residuals_dev);

@@ -73,7 +73,7 @@ EXPORTED_SYMBOLS = [
     "mg_memset", "mg_profile_enable", "mg_profile_reset", "mg_profile_get", "mg_profile_get_samples",
     "mg_primitive_create", "mg_primitive_destroy", "mg_primitive_info", "mg_primitive_info2", "mg_primitive_root_mode", "mg_primitive_get_precisions_cholesky",
     "mg_time_function_canonical", "mg_time_function_canonical_host", "mg_time_function_sample", "mg_time_function_sample_rows", "mg_back_project_frames_at",
-    "mg_trajectory_create", "mg_trajectory_destroy", "mg_score_trajectory", "mg_score_trajectories", "mg_score_trajectory_points", "mg_trajectory_closest_points", "mg_trajectory_plan", "mg_joint_positions",
+    "mg_trajectory_create", "mg_trajectory_create_typed", "mg_trajectory_spline_type", "mg_trajectory_tables", "mg_trajectory_destroy", "mg_score_trajectory", "mg_score_trajectories", "mg_score_trajectory_points", "mg_trajectory_closest_points", "mg_trajectory_plan", "mg_joint_positions",
     "mg_time_grid_create", "mg_time_grid_destroy", "mg_primitive_canonical_grid", "mg_time_grid_size",
     "mg_time_grid_get_tables",
     "mg_back_project_frames", "mg_back_project_frames_f64", "mg_back_project_coeffs", "mg_spline_evaluate",
@@ -148,6 +148,9 @@ class FrameConstraintDesc(C.Structure):   # struct mg_frame_constraint_desc
                 ("start_arc", C.c_double), ("trajectories", C.c_void_p * MG_FRAME_MAX_JOINTS), ("arc0", C.c_double * MG_FRAME_MAX_JOINTS),
                 ("range_start", C.c_double * MG_FRAME_MAX_JOINTS), ("range_end", C.c_double * MG_FRAME_MAX_JOINTS),
                 ("has_range", C.c_int32 * MG_FRAME_MAX_JOINTS), ("quaternion", C.c_double * 4)]
+
+
+MG_SPLINE_CATMULL_ROM, MG_SPLINE_BSPLINE, MG_SPLINE_FITTED_BSPLINE = 0, 1, 2    # mg_trajectory_create_typed: the reference's SPLINE_TYPE_*
 
 
 class TrajectoryPlanInfo(C.Structure):   # struct mg_trajectory_plan_info
@@ -305,6 +308,9 @@ def load_library(path=None):
         "mg_primitive_root_mode": [vp, C.POINTER(C.c_int32), C.POINTER(C.c_double)],
         "mg_time_function_canonical": [vp, vp, i32, i64, i64, vp],
         "mg_trajectory_create": [vp, vp, i32, i32, C.POINTER(vp)],
+        "mg_trajectory_create_typed": [vp, vp, i32, i32, i32, C.POINTER(vp)],
+        "mg_trajectory_spline_type": [vp],
+        "mg_trajectory_tables": [vp, vp, vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(dbl)],
         "mg_joint_positions": [vp, vp, vp, i32, vp, i64, i32, vp],
         "mg_score_trajectory": [vp, vp, vp, vp, i32, i64, i64, dbl, dbl, vp, vp, i32, vp],
         "mg_score_trajectories": [i32, vp, vp, vp, i32, i64, vp, vp, vp, vp, vp, i32],
@@ -910,17 +916,32 @@ class ConstraintSet(object):
 
 
 class Trajectory(object):
-    """A Catmull-Rom trajectory on the device for mg_score_trajectory: control_points (n, 3), the reference's
-    TrajectoryConstraint spline (trajectory_constraint.py:33-38); granularity = the step of the closest-point search."""
+    """A trajectory on the device for mg_score_trajectory: control_points (n, 3), the reference's TrajectoryConstraint spline
+    (trajectory_constraint.py:33-38); granularity = the step of the closest-point search.  spline_type: the reference's
+    SPLINE_TYPE_* (parameterized_spline.py:36-38): 0 Catmull-Rom (mg_trajectory_create, as ever), 1 B-spline, 2 fitted B-spline
+    (mg_trajectory_create_typed)."""
 
-    def __init__(self, prim, control_points, granularity=1000):
+    def __init__(self, prim, control_points, granularity=1000, spline_type=0):
         self.prim = prim
         cp = np.ascontiguousarray(np.asarray(control_points, dtype=np.float64))
         if cp.ndim != 2 or cp.shape[1] != 3:
             raise ValueError("control_points must be (n, 3)")
         h = C.c_void_p()
-        _check(prim.lib.mg_trajectory_create(prim.handle, cp.ctypes.data_as(C.c_void_p), cp.shape[0], int(granularity), C.byref(h)))
+        if int(spline_type) == MG_SPLINE_CATMULL_ROM:
+            _check(prim.lib.mg_trajectory_create(prim.handle, cp.ctypes.data_as(C.c_void_p), cp.shape[0], int(granularity), C.byref(h)))
+        else:
+            _check(prim.lib.mg_trajectory_create_typed(prim.handle, cp.ctypes.data_as(C.c_void_p), cp.shape[0], int(granularity), int(spline_type),
+                                                       C.byref(h)))
         self.handle = h
+        self.spline_type = int(spline_type)
+
+    def tables(self):
+        """mg_trajectory_tables: (poly (n_seg * 12 + 3,), relative arc lengths (granularity + 1,), full arc length) as the kernels read them"""
+        n_seg, G, full = C.c_int32(), C.c_int32(), C.c_double()
+        _check(self.prim.lib.mg_trajectory_tables(self.handle, None, None, C.byref(n_seg), C.byref(G), C.byref(full)))
+        poly, arc = np.empty(n_seg.value * 12 + 3), np.empty(G.value + 1)
+        _check(self.prim.lib.mg_trajectory_tables(self.handle, poly.ctypes.data_as(C.c_void_p), arc.ctypes.data_as(C.c_void_p), None, None, None))
+        return poly, arc, full.value
 
     def close(self):
         if getattr(self, "handle", None) and self.prim.handle and self.prim.ctx.handle:

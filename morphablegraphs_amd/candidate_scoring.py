@@ -134,14 +134,38 @@ def constraints_to_device_form(constraints, root_joint=None):
     return out
 
 
-def _spline_control_points(spline_owner):
-    """{"control_points", "granularity"} of a reference ParameterizedSpline / TrajectoryConstraint (the padding of
-    catmull_rom_spline.py:66-71 undone)"""
-    spline = getattr(spline_owner, "spline", None)
+def _typed_control_points(spline, what):
+    """(control points, spline type) of the curve under a reference ParameterizedSpline (parameterized_spline.py:53-63), recognised by
+    what its class carries: CatmullRomSpline its base matrix and PADDED control points (catmull_rom_spline.py:66-71, undone here),
+    BSpline `points` and `knots` (b_spline.py:46-59), FittedBSpline `points` and `spline_def` (fitted_b_spline.py:29-47)."""
     padded = getattr(spline, "control_points", None)
-    if padded is None or not hasattr(spline, "_catmullrom_basematrix"):
-        raise NotImplementedError("trajectory without a Catmull-Rom spline")
-    return {"control_points": [list(map(float, p)) for p in padded[1:-2]], "granularity": int(getattr(spline_owner, "granularity", 1000))}
+    if padded is not None and hasattr(spline, "_catmullrom_basematrix"):
+        return [list(map(float, p)) for p in padded[1:-2]], _capi.MG_SPLINE_CATMULL_ROM
+    points = getattr(spline, "points", None)
+    if points is not None and hasattr(spline, "knots"):
+        return [list(map(float, p)) for p in points], _capi.MG_SPLINE_BSPLINE
+    if points is not None and hasattr(spline, "spline_def"):
+        return [list(map(float, p)) for p in points], _capi.MG_SPLINE_FITTED_BSPLINE
+    raise NotImplementedError("%s without a Catmull-Rom, B-spline or fitted B-spline curve" % what)
+
+
+def _with_spline_type(d, spline_type):
+    """"spline_type" goes into a device-form dict only where it is not Catmull-Rom: type-0 dicts and cache keys stay what they were"""
+    if spline_type != _capi.MG_SPLINE_CATMULL_ROM:
+        d["spline_type"] = int(spline_type)
+    return d
+
+
+def trajectory_record(t):
+    """What cached_trajectory keys a device trajectory by, from any device-form dict that carries a curve"""
+    return _with_spline_type({"type": "trajectory", "control_points": t["control_points"], "granularity": t.get("granularity", 1000)},
+                             t.get("spline_type", _capi.MG_SPLINE_CATMULL_ROM))
+
+
+def _spline_control_points(spline_owner):
+    """{"control_points", "granularity"[, "spline_type"]} of a reference ParameterizedSpline / TrajectoryConstraint"""
+    cps, spline_type = _typed_control_points(getattr(spline_owner, "spline", None), "trajectory")
+    return _with_spline_type({"control_points": cps, "granularity": int(getattr(spline_owner, "granularity", 1000))}, spline_type)
 
 
 def _rotation_constraint_quaternion(c):
@@ -167,7 +191,8 @@ def _rotation_constraint_quaternion(c):
 
 def trajectory_to_device_form(c, root_joint=None, group=None):
     """A reference TrajectoryConstraint (trajectory_constraint.py:33-52: an AnnotatedSpline over control points with
-    min_arc_length / full_arc_length, a joint and a weight) as the dict the device path takes.  Catmull-Rom splines only.  The root
+    min_arc_length / full_arc_length, a joint and a weight) as the dict the device path takes.  Any of the reference's three curves
+    ("spline_type" is set for a B-spline, 1, or a fitted B-spline, 2; a Catmull-Rom dict is what it always was).  The root
     joint's path is scored inside the fused kernels ("trajectory"); any other joint's -- a collision-avoidance trajectory is one of
     those, the reference's optimiser evaluates it with the same method (graph_walk_optimizer.py:168-176) -- from the joint's
     forward-kinematics track ("frame_joint_trajectory")."""
@@ -178,14 +203,11 @@ def trajectory_to_device_form(c, root_joint=None, group=None):
         full = float(c.full_arc_length)
         return dict(_spline_control_points(c), type="frame_joint_trajectory", joint=joint, min_u=float(c.min_arc_length) / full if full > 0.0 else 0.0,
                     weight=float(getattr(c, "weight_factor", 1.0)), group=group)
-    spline = getattr(c, "spline", None)
-    padded = getattr(spline, "control_points", None)
-    if padded is None or not hasattr(spline, "_catmullrom_basematrix"):
-        raise NotImplementedError("trajectory constraint without a Catmull-Rom spline")
-    cps = [list(map(float, p)) for p in padded[1:-2]]          # the padding of catmull_rom_spline.py:66-71 undone
+    cps, spline_type = _typed_control_points(getattr(c, "spline", None), "trajectory constraint")
     full = float(c.full_arc_length)
-    return {"type": "trajectory", "control_points": cps, "min_u": float(c.min_arc_length) / full if full > 0.0 else 0.0,
-            "weight": float(getattr(c, "weight_factor", 1.0)), "granularity": int(getattr(c, "granularity", 1000)), "group": group}
+    return _with_spline_type({"type": "trajectory", "control_points": cps, "min_u": float(c.min_arc_length) / full if full > 0.0 else 0.0,
+                              "weight": float(getattr(c, "weight_factor", 1.0)), "granularity": int(getattr(c, "granularity", 1000)), "group": group},
+                             spline_type)
 
 
 def split_trajectories(clist):
@@ -202,7 +224,10 @@ def cached_trajectory(prim, c, pin=False):
     call at hand (a TrackScorer's constraint records, a planner step's side-by-side launch list) asks with pin=True and hands it
     back with release_trajectory(): a pinned trajectory is never destroyed under its holder -- when the cache lets go of it, the
     last release closes it (the records of a cached scorer pointed at trajectories the cache had closed)."""
+    spline_type = int(c.get("spline_type", _capi.MG_SPLINE_CATMULL_ROM))
     key = (prim.serial, prim.handle.value, _freeze(c["control_points"]), int(c.get("granularity", 1000)))
+    if spline_type != _capi.MG_SPLINE_CATMULL_ROM:
+        key += (spline_type,)
     t = None
     for i, (k, cand) in enumerate(_TRAJ_CACHE):
         if k == key and cand.handle:
@@ -210,7 +235,7 @@ def cached_trajectory(prim, c, pin=False):
             t = cand
             break
     if t is None:
-        t = _capi.Trajectory(prim, c["control_points"], c.get("granularity", 1000))
+        t = _capi.Trajectory(prim, c["control_points"], c.get("granularity", 1000), spline_type)
         t.pins, t.evicted = 0, False
         _TRAJ_CACHE.append((key, t))
     if pin:

@@ -364,6 +364,7 @@ void mg_basis_row(const double *knots, int n_knots, double x, int32_t *i0, doubl
 struct mg_trajectory {
     mg_primitive *prim = nullptr;
     int32_t n_seg = 0, granularity = 1000, rows = 0;
+    int32_t spline_type = 0;     // MG_SPLINE_*: which of the reference's curves the pieces were made from (the kernels do not ask)
     double *d_poly = nullptr;    // [n_seg][4][3]: point(t) = ((A0 t + A1) t + A2) t + A3 on a segment; then the last control point [3]
     double *d_arc = nullptr;     // [granularity + 1]: relative arc length at u = k / granularity (arc_length_map.py:45-71)
     double full_arc = 0.0;

@@ -400,6 +400,8 @@ extern "C" void mg_trajectory_destroy(mg_trajectory *t) {
     delete t;
 }
 
+static int mg_traj_finish(mg_primitive *p, const std::vector<double> &poly, int32_t n_seg, int32_t granularity, int32_t spline_type, mg_trajectory **out);
+
 extern "C" int mg_trajectory_create(mg_primitive *p, const double *cp, int32_t n_points, int32_t granularity, mg_trajectory **out) {
     if (!p || !cp || !out || n_points < 2 || granularity < 2 || p->D < 3) {
         mg_set_error("mg_trajectory_create: needs a primitive with root channels, >= 2 control points (x, y, z) and a granularity >= 2");
@@ -409,11 +411,7 @@ extern "C" int mg_trajectory_create(mg_primitive *p, const double *cp, int32_t n
     for (int i = 0; i < 3 * n_points; i++)
         if (!std::isfinite(cp[i])) { mg_set_error("mg_trajectory_create: control point %d is not finite", i / 3); return MG_ERR_INVALID_ARGUMENT; }
     MG_HIP_CHECK(hipSetDevice(p->ctx->device));
-    mg_trajectory *t = new (std::nothrow) mg_trajectory();
-    if (!t) return MG_ERR_OUT_OF_MEMORY;
-    t->prim = p;
-    t->n_seg = n_points - 1;
-    t->granularity = granularity;
+    const int n_seg = n_points - 1;
     // catmull_rom_spline.py:66-71: control points padded to [P0] + P + [Pn, Pn]; segment s (1-based) uses padded[s-1 .. s+2]
     std::vector<double> pad((size_t)(n_points + 3) * 3);
     for (int d = 0; d < 3; d++) {
@@ -422,15 +420,27 @@ extern "C" int mg_trajectory_create(mg_primitive *p, const double *cp, int32_t n
         pad[(size_t)(n_points + 1) * 3 + d] = pad[(size_t)(n_points + 2) * 3 + d] = cp[(size_t)(n_points - 1) * 3 + d];
     }
     static const double M[4][4] = {{-1.0, 3.0, -3.0, 1.0}, {2.0, -5.0, 4.0, -1.0}, {-1.0, 0.0, 1.0, 0.0}, {0.0, 2.0, 0.0, 0.0}};
-    std::vector<double> poly((size_t)t->n_seg * 12 + 3);
-    for (int s = 0; s < t->n_seg; s++)           // 0-based segment s = the reference's segment index s + 1
+    std::vector<double> poly((size_t)n_seg * 12 + 3);
+    for (int s = 0; s < n_seg; s++)           // 0-based segment s = the reference's segment index s + 1
         for (int r = 0; r < 4; r++)
             for (int d = 0; d < 3; d++) {
                 double v = 0.0;
                 for (int j = 0; j < 4; j++) v += M[r][j] * pad[(size_t)(s + j) * 3 + d];
                 poly[(size_t)s * 12 + r * 3 + d] = 0.5 * v;
             }
-    for (int d = 0; d < 3; d++) poly[(size_t)t->n_seg * 12 + d] = cp[(size_t)(n_points - 1) * 3 + d];
+    for (int d = 0; d < 3; d++) poly[(size_t)n_seg * 12 + d] = cp[(size_t)(n_points - 1) * 3 + d];
+    return mg_traj_finish(p, poly, n_seg, granularity, MG_SPLINE_CATMULL_ROM, out);
+}
+
+// Everything of a trajectory but its polynomials, the same for every spline type: the primitive's root rows, the arc-length table
+// over the curve's points at k / granularity, the uploads.
+static int mg_traj_finish(mg_primitive *p, const std::vector<double> &poly, int32_t n_seg, int32_t granularity, int32_t spline_type, mg_trajectory **out) {
+    mg_trajectory *t = new (std::nothrow) mg_trajectory();
+    if (!t) return MG_ERR_OUT_OF_MEMORY;
+    t->prim = p;
+    t->n_seg = n_seg;
+    t->granularity = granularity;
+    t->spline_type = spline_type;
     // root coefficient rows of the primitive (already scaled by translation_maxima), then the root quaternion of the first control point
     const int NB = p->NB, D = p->D, L = p->L;
     t->rows = NB * 3 + 4;
@@ -478,6 +488,109 @@ extern "C" int mg_trajectory_create(mg_primitive *p, const double *cp, int32_t n
     if (rc == MG_OK) rc = mg_traj_upload(mean, &t->d_mean);
     if (rc != MG_OK) { mg_trajectory_destroy(t); return rc; }
     *out = t;
+    return MG_OK;
+}
+
+// The reference's BSpline (splines/b_spline.py:70-105, 174-188) as cubic pieces: a clamped cubic over n_points - 2 uniform knot values,
+// so n_seg = n_points - 3 pieces of equal length.  In units of the knot spacing the knot vector is K_j = clamp(j - 3, 0, n_seg) and on
+// piece s the parameter is s + t: de Boor's recurrence d_j <- (1 - alpha) d_(j-1) + alpha d_j with alpha = (s + t - K_j) /
+// (K_(j+4-r) - K_j) = a0 + a1 t is carried out on the polynomials' coefficients (ascending powers of t).  The denominators are 1, 2 or
+// 3: rounding of a few ulp of the control points.  Statement for statement spline_types.py _b_spline.
+static void mg_traj_poly_bspline(const double *cp, int n_seg, std::vector<double> &poly) {
+    auto knot = [&](int j) { return (double)std::min(std::max(j - 3, 0), n_seg); };
+    for (int s = 0; s < n_seg; s++) {
+        const int i = s + 3;                         // the piece's knot span: K_i = s, K_(i+1) = s + 1
+        for (int d = 0; d < 3; d++) {
+            double c[4][4];
+            for (int j = 0; j < 4; j++) { c[j][0] = cp[(size_t)(s + j) * 3 + d]; c[j][1] = c[j][2] = c[j][3] = 0.0; }
+            for (int r = 1; r < 4; r++)
+                for (int jj = 3; jj >= r; jj--) {    // descending: c[jj - 1] is still the level before
+                    const int j = i - 3 + jj;
+                    const double den = knot(j + 4 - r) - knot(j);
+                    const double a0 = ((double)s - knot(j)) / den, a1 = 1.0 / den;
+                    const double *lo = c[jj - 1], *hi = c[jj];
+                    double nw[4];
+                    nw[0] = (1.0 - a0) * lo[0] + a0 * hi[0];
+                    for (int k = 1; k < 4; k++) nw[k] = ((1.0 - a0) * lo[k] + a0 * hi[k]) + a1 * (hi[k - 1] - lo[k - 1]);
+                    for (int k = 0; k < 4; k++) c[jj][k] = nw[k];
+                }
+            for (int r = 0; r < 4; r++) poly[(size_t)s * 12 + r * 3 + d] = c[3][3 - r];
+        }
+    }
+}
+
+// The reference's FittedBSpline (splines/fitted_b_spline.py:44-47): per dimension FITPACK's splrep(linspace(0, 1, n), values, k = 3) with
+// s = 0 -- the interpolating cubic spline whose knots are the data sites without the second and the last but one, i.e. whose third
+// derivative is continuous there (not-a-knot).  On n - 1 uniform pieces, solved for the second derivatives M_i per unit spacing:
+// M_(i-1) + 4 M_i + M_(i+1) = 6 (y_(i-1) - 2 y_i + y_(i+1)); M_0 - 2 M_1 + M_2 = 0 turns the first row into M_1 = y_0 - 2 y_1 + y_2
+// (the last likewise), what is left is tridiagonal with 4 on the diagonal: elimination without pivoting is stable.  The first two
+// pieces are one cubic re-expanded at the second site, the last two likewise.  Statement for statement spline_types.py _fitted_b_spline.
+static void mg_traj_poly_fitted(const double *cp, int m, std::vector<double> &poly) {
+    std::vector<double> y(m), D2(m), M(m), cc(m), dd(m);
+    for (int d = 0; d < 3; d++) {
+        for (int i = 0; i < m; i++) { y[i] = cp[(size_t)i * 3 + d]; D2[i] = M[i] = cc[i] = dd[i] = 0.0; }
+        for (int i = 1; i < m - 1; i++) D2[i] = (y[i + 1] - y[i]) - (y[i] - y[i - 1]);
+        M[1] = D2[1]; M[m - 2] = D2[m - 2];
+        if (m >= 5) {
+            const int lo = 2, hi = m - 3;
+            for (int i = lo; i <= hi; i++) {
+                double rhs = 6.0 * D2[i];
+                if (i == lo) rhs -= M[1];
+                if (i == hi) rhs -= M[m - 2];
+                const double den = i == lo ? 4.0 : 4.0 - cc[i - 1];
+                cc[i] = 1.0 / den;
+                dd[i] = (i == lo ? rhs : rhs - dd[i - 1]) / den;
+            }
+            M[hi] = dd[hi];
+            for (int i = hi - 1; i >= lo; i--) M[i] = dd[i] - cc[i] * M[i + 1];
+        }
+        M[0] = 2.0 * M[1] - M[2];
+        M[m - 1] = 2.0 * M[m - 2] - M[m - 3];
+        for (int s = 0; s < m - 1; s++) {
+            poly[(size_t)s * 12 + 0 + d] = (M[s + 1] - M[s]) / 6.0;
+            poly[(size_t)s * 12 + 3 + d] = 0.5 * M[s];
+            poly[(size_t)s * 12 + 6 + d] = (y[s + 1] - y[s]) - (2.0 * M[s] + M[s + 1]) / 6.0;
+            poly[(size_t)s * 12 + 9 + d] = y[s];
+        }
+    }
+}
+
+extern "C" int mg_trajectory_create_typed(mg_primitive *p, const double *cp, int32_t n_points, int32_t granularity, int32_t spline_type, mg_trajectory **out) {
+    if (spline_type == MG_SPLINE_CATMULL_ROM) return mg_trajectory_create(p, cp, n_points, granularity, out);
+    if (spline_type != MG_SPLINE_BSPLINE && spline_type != MG_SPLINE_FITTED_BSPLINE) {
+        mg_set_error("mg_trajectory_create_typed: unknown spline type %d (0 Catmull-Rom, 1 B-spline, 2 fitted B-spline)", spline_type);
+        return MG_ERR_INVALID_ARGUMENT;
+    }
+    if (!p || !cp || !out || n_points < 4 || granularity < 2 || p->D < 3) {
+        mg_set_error("mg_trajectory_create_typed: needs a primitive with root channels, >= 4 control points (x, y, z) for a %s and a granularity >= 2",
+                     spline_type == MG_SPLINE_BSPLINE ? "B-spline" : "fitted B-spline");
+        return MG_ERR_INVALID_ARGUMENT;
+    }
+    *out = nullptr;
+    for (int i = 0; i < 3 * n_points; i++)
+        if (!std::isfinite(cp[i])) { mg_set_error("mg_trajectory_create_typed: control point %d is not finite", i / 3); return MG_ERR_INVALID_ARGUMENT; }
+    MG_HIP_CHECK(hipSetDevice(p->ctx->device));
+    const int n_seg = spline_type == MG_SPLINE_BSPLINE ? n_points - 3 : n_points - 1;
+    std::vector<double> poly((size_t)n_seg * 12 + 3);
+    if (spline_type == MG_SPLINE_BSPLINE) mg_traj_poly_bspline(cp, n_seg, poly);
+    else mg_traj_poly_fitted(cp, n_points, poly);
+    // (b_spline.py:134-137: u >= 1 is points[-1]; the fitted spline interpolates its last point)
+    for (int d = 0; d < 3; d++) poly[(size_t)n_seg * 12 + d] = cp[(size_t)(n_points - 1) * 3 + d];
+    return mg_traj_finish(p, poly, n_seg, granularity, spline_type, out);
+}
+
+extern "C" int32_t mg_trajectory_spline_type(const mg_trajectory *t) { return t ? t->spline_type : -1; }
+
+// The two tables as the kernels read them, for tests and tools: poly_host (n_seg * 12 + 3) and arc_host (granularity + 1) are filled
+// when not NULL; n_seg, granularity and full_arc_length are reported when not NULL.
+extern "C" int mg_trajectory_tables(const mg_trajectory *t, double *poly_host, double *arc_host, int32_t *n_seg, int32_t *granularity, double *full_arc_length) {
+    if (!t) { mg_set_error("mg_trajectory_tables: NULL trajectory"); return MG_ERR_INVALID_ARGUMENT; }
+    if (n_seg) *n_seg = t->n_seg;
+    if (granularity) *granularity = t->granularity;
+    if (full_arc_length) *full_arc_length = t->full_arc;
+    if (poly_host || arc_host) MG_HIP_CHECK(hipSetDevice(t->prim->ctx->device));
+    if (poly_host) MG_HIP_CHECK(hipMemcpy(poly_host, t->d_poly, ((size_t)t->n_seg * 12 + 3) * sizeof(double), hipMemcpyDeviceToHost));
+    if (arc_host) MG_HIP_CHECK(hipMemcpy(arc_host, t->d_arc, ((size_t)t->granularity + 1) * sizeof(double), hipMemcpyDeviceToHost));
     return MG_OK;
 }
 

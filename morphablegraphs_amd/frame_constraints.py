@@ -27,6 +27,9 @@ Device forms (what candidate_scoring.constraints_to_device_form makes of the ref
         TrajectorySetConstraint -- trajectory_set_constraint.py:82-104
   {"type": "frame_joint_rotation", "joint_index", "quaternion" (w, x, y, z), "frame_idx", "weight"}
         JointRotationConstraint -- keyframe_constraints/joint_rotation_constraint.py:55-72
+Every dict that carries "control_points" may carry "spline_type" beside them (the reference's SPLINE_TYPE_*: 1 B-spline, 2 fitted
+B-spline; absent = 0, Catmull-Rom); it reaches the device trajectory through candidate_scoring.trajectory_record.  A
+DiscreteTrajectoryConstraint holds sampled points, no curve: its spline's type was spent when the reference sampled it.
 
 PARITY UNPINNED where forward kinematics and alignment are (anim_utils); the target splines and their arc-length look-up are
 pinned (tests/golden/trajectory_spline.npz).  There is no CPU fallback: without the library and a GPU every call raises.
@@ -158,12 +161,12 @@ def _score(batch, desc, d_tracks, T, J, d_err, accumulate, want_residuals):
 
 def _add_frame_constraint(batch, c, d_err, accumulate, want_residuals):
     """Add (or write) constraint c's weighted errors of the batch to d_err (n,) on the device; the residual vectors when wanted."""
-    from .candidate_scoring import cached_trajectory
+    from .candidate_scoring import cached_trajectory, trajectory_record
     prim = batch.prim
     kind, w, F = c["type"], float(c.get("weight", 1.0)), prim.n_canonical_frames
 
     def trajectory_of(t):
-        return cached_trajectory(prim, {"type": "trajectory", "control_points": t["control_points"], "granularity": t.get("granularity", 1000)})
+        return cached_trajectory(prim, trajectory_record(t))
     if kind == "frame_joint_trajectory":
         d_tr, T = batch.tracks([c["joint"]])
         d_res = batch._malloc(batch.n * T * 8) if want_residuals else None
@@ -314,12 +317,13 @@ class TrackScorer(object):
         self.tptr = None
 
     def _fill(self, prim, track_list, descs, widths, cached_trajectory, ctx, F, req_of):
+        from .candidate_scoring import trajectory_record
         for i, c in enumerate(track_list):
             d, T = descs[i], self.Ts[req_of[i]]
             kind = c["type"]
             d.weight, d.n_joints = float(c.get("weight", 1.0)), 1
             if kind == "frame_joint_trajectory":
-                t = cached_trajectory(prim, {"type": "trajectory", "control_points": c["control_points"], "granularity": c.get("granularity", 1000)})
+                t = cached_trajectory(prim, trajectory_record(c))
                 d.type, d.start_arc = _capi.MG_FRAME_JOINT_TRAJECTORY, float(c.get("min_u", 0.0))
                 d.trajectories[0] = t.handle.value
             elif kind == "frame_ca_position":
@@ -338,7 +342,7 @@ class TrackScorer(object):
                 for a in range(3):
                     d.axis_on[a] = 0 if a in free else 1
             elif kind == "frame_local_trajectory":
-                t = cached_trajectory(prim, {"type": "trajectory", "control_points": c["control_points"], "granularity": c.get("granularity", 1000)})
+                t = cached_trajectory(prim, trajectory_record(c))
                 d.type, d.n_frames, d.start_arc = _capi.MG_FRAME_LOCAL_TRAJECTORY, int(c.get("n_frames", F)), float(c.get("start_t", 0.0))
                 d.trajectories[0] = t.handle.value
             elif kind == "frame_trajectory_set":
@@ -348,7 +352,7 @@ class TrackScorer(object):
                 d.type, d.n_frames, d.n_joints = _capi.MG_FRAME_TRAJECTORY_SET, int(c.get("n_frames", F)), len(joints)
                 arcs = c.get("arc_lengths", [0.0] * len(joints))
                 for j, t in enumerate(c["trajectories"]):
-                    tr = cached_trajectory(prim, {"type": "trajectory", "control_points": t["control_points"], "granularity": t.get("granularity", 1000)})
+                    tr = cached_trajectory(prim, trajectory_record(t))
                     d.trajectories[j] = tr.handle.value
                     d.arc0[j] = float(arcs[j])
                     rs, re = t.get("range_start"), t.get("range_end")

@@ -11,6 +11,10 @@
 // flops per frame; (B, T, J, 3) float64 tracks in, 8 bytes (and optionally the residual vector) per candidate out.
 // Oracle: oracle/mg_oracle.py per_frame_constraint_residuals.  PARITY UNPINNED where anim_utils' forward kinematics is involved;
 // the arc-length look-up is pinned (tests/golden/trajectory_spline.npz through the oracle's restatement).
+// Tests: tests/test_gpu_frame_constraints.py (the workload's shape, end to end) and tests/test_gpu_frame_constraint_shapes.py, which
+// restates mg_fc_place_tables, the grouping loop of mg_score_frame_constraints and mg_joint_tracks' LDS bytes, pins them to the lines
+// below, and walks the shape edges: tables in LDS / by the large-LDS opt-in / in global memory, n_frames < T, both CA load paths, every
+// B mod MG_TRACK_CANDS, D < 7, more than 64 workgroups per option, a joint trajectory inside a list.
 #include <cmath>
 #include <cstring>
 

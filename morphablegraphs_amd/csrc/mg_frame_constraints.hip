@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "mg_internal.h"
+#include "mg_pack.h"
 #include "mg_score_device.h"
 #include "mg_spline_device.h"
 #include "mg_traj_device.h"
@@ -756,22 +757,19 @@ extern "C" void mg_track_plan_destroy(mg_track_plan *pl) {
 }
 
 static int mg_track_chain_record(const char *who, const mg_skeleton_desc *sk, int joint, int n_dim, double *rec, std::vector<char> &need) {
-    if (joint < 0 || joint >= sk->n_joints) { mg_set_error("%s: joint %d out of range", who, joint); return MG_ERR_INVALID_ARGUMENT; }
     std::vector<int> ch;
-    for (int j = joint; j >= 0; j = sk->parents[j]) {
-        if (sk->parents[j] >= j) { mg_set_error("%s: joint %d: parents must precede their children", who, j); return MG_ERR_INVALID_ARGUMENT; }
-        ch.insert(ch.begin(), j);
-    }
+    int bad;
+    const int st = mg_joint_chain(sk->parents, sk->n_joints, joint, ch, &bad);
+    if (st != MG_CHAIN_OK) { mg_set_error("%s: joint %d%s", who, bad, mg_chain_why(st)); return MG_ERR_INVALID_ARGUMENT; }
     const int m = (int)ch.size() - 1;
     if (m > MG_MAX_CHAIN) { mg_set_error("%s: chain of %d joints exceeds %d", who, m, MG_MAX_CHAIN); return MG_ERR_INVALID_ARGUMENT; }
-    rec[0] = m;
-    for (int k = 0; k < m; k++) {   // link k: rotation of chain joint k, offset of chain joint k + 1
+    for (int k = 0; k < m; k++) {
         const int qc = sk->quat_channel[ch[(size_t)k]];
         if (qc >= 0 && qc + 4 > n_dim) { mg_set_error("%s: quaternion channel %d outside n_dim = %d", who, qc, n_dim); return MG_ERR_INVALID_ARGUMENT; }
-        rec[1 + 4 * k] = qc;
         if (qc >= 0) for (int e = 0; e < 4; e++) need[(size_t)qc + e] = 1;
-        for (int e = 0; e < 3; e++) rec[2 + 4 * k + e] = sk->offsets[(size_t)ch[(size_t)k + 1] * 3 + e];
     }
+    rec[0] = m;
+    mg_chain_links(ch, sk->offsets, [&](int j) { return sk->quat_channel[j]; }, rec + 1);
     return MG_OK;
 }
 
@@ -806,10 +804,11 @@ extern "C" int mg_track_plan_create(mg_primitive *p, const mg_skeleton_desc *sk,
     for (int o = 0; o < total && rc == MG_OK; o++) rc = mg_track_chain_record("mg_track_plan_create", sk, joints[o], p->D, &records[(size_t)o * MG_TRACK_REC], need);
     if (rc == MG_OK && align_joint >= 0) {
         // the aligning node's global orientation: the quaternions of the chain root .. node, the node's own included
-        if (align_joint >= sk->n_joints) { mg_set_error("mg_track_plan_create: aligning joint %d out of range", align_joint); rc = MG_ERR_INVALID_ARGUMENT; }
+        std::vector<int> ch;
+        int bad;
+        const int st = mg_joint_chain(sk->parents, sk->n_joints, align_joint, ch, &bad);
+        if (st != MG_CHAIN_OK) { mg_set_error("mg_track_plan_create: %sjoint %d%s", st == MG_CHAIN_NO_JOINT ? "aligning " : "", bad, mg_chain_why(st)); rc = MG_ERR_INVALID_ARGUMENT; }
         else {
-            std::vector<int> ch;
-            for (int j = align_joint; j >= 0; j = sk->parents[j]) ch.insert(ch.begin(), j);
             int m = 0;
             for (int j : ch) {
                 const int qc = sk->quat_channel[j];

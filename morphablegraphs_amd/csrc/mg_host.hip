@@ -11,6 +11,7 @@
 #include <time.h>
 
 #include "mg_internal.h"
+#include "mg_pack.h"
 #include <dlfcn.h>
 
 // ---------------------------------------------------------------------------------------
@@ -803,19 +804,14 @@ static int mg_grid_build(mg_primitive *p, mg_time_grid *g, const double *times, 
         if ((rc = mg_upload(p->ctx, rootm, &g->d_rootm)) != MG_OK) return rc;
     }
     if ((rc = mg_upload(p->ctx, g->chunks, &g->d_chunks)) != MG_OK) return rc;
-    {   // banded tap weights of every chunk as v_mfma_f64_16x16x4_f64 A fragments: lane l supplies
-        // W[f = 16 ft + (l & 15)][m = 4 ks + (l >> 4)],  W[f][m] = w[f][m - (i0[f] - imin)] inside the band
+    {   // banded tap weights of every chunk (mg_pack.h): W[f][m] = w[f][m - (i0[f] - imin)] inside the band
         std::vector<double> wtap(std::max<size_t>(g->chunks.size(), 1) * MG_TAP_FT * MG_TAP_KS * 64, 0.0);
         for (size_t c = 0; c < g->chunks.size(); c++) {
             const mg_chunk &ck = g->chunks[c];
-            for (int ft = 0; ft < MG_TAP_FT; ft++)
-                for (int ks = 0; ks < MG_TAP_KS; ks++)
-                    for (int lane = 0; lane < 64; lane++) {
-                        int f = ft * 16 + (lane & 15), m = 4 * ks + (lane >> 4);
-                        if (f >= ck.nT) continue;
-                        int j = m - (g->i0[ck.t0 + f] - ck.imin);
-                        if (j >= 0 && j < 4) wtap[((c * MG_TAP_FT + ft) * MG_TAP_KS + ks) * 64 + lane] = g->w[4 * (size_t)(ck.t0 + f) + j];
-                    }
+            mg_pack_fragments(&wtap[c * MG_TAP_FT * MG_TAP_KS * 64], MG_TAP_FT, MG_TAP_KS, [&](int f, int m) {
+                const int j = f < ck.nT ? m - (g->i0[ck.t0 + f] - ck.imin) : -1;
+                return j >= 0 && j < 4 ? g->w[4 * (size_t)(ck.t0 + f) + j] : 0.0;
+            });
         }
         if ((rc = mg_upload(p->ctx, wtap, &g->d_wtap)) != MG_OK) return rc;
     }
@@ -946,51 +942,29 @@ extern "C" int mg_primitive_create(mg_context *ctx, const mg_primitive_desc *d, 
             if (rc == MG_OK) rc = mg_upload(ctx, m32, &p->d_mean32);
         }
         if (rc == MG_OK && p->KK > 0) {
-            // root rows (row = i*nroot + d) as v_mfma_f64_16x16x4_f64 A fragments:
-            // lane l supplies A[row = l & 15][k = 4*kk + (l >> 4)].  Image [tile][kk][lane].
+            // the root rows (row = i*nroot + d) of E' (mg_pack.h)
             const int KK = p->KK, nr = p->nroot, RR = NB * nr;
             p->RRT = (RR + 15) / 16;
-            std::vector<double> rpack((size_t)p->RRT * KK * 64, 0.0), mroot((size_t)p->RRT * 16, 0.0);
+            std::vector<double> rpack((size_t)p->RRT * KK * 64), mroot((size_t)p->RRT * 16, 0.0);
             for (int rr = 0; rr < RR; rr++) mroot[rr] = p->means_[(size_t)(rr / nr) * D + rr % nr];
-            for (int t = 0; t < p->RRT; t++)
-                for (int kk = 0; kk < KK; kk++)
-                    for (int lane = 0; lane < 64; lane++) {
-                        int rr = t * 16 + (lane & 15), k = 4 * kk + (lane >> 4);
-                        if (rr < RR && k < L)
-                            rpack[((size_t)t * KK + kk) * 64 + lane] = p->Es[((size_t)(rr / nr) * D + rr % nr) * L + k];
-                    }
+            mg_pack_fragments(rpack.data(), p->RRT, KK, [&](int rr, int k) { return rr < RR && k < L ? p->Es[((size_t)(rr / nr) * D + rr % nr) * L + k] : 0.0; });
             rc = mg_upload(ctx, rpack, &p->d_Erpack);
             if (rc == MG_OK) rc = mg_upload(ctx, mroot, &p->d_meanroot);
         }
         if (rc == MG_OK && p->KK > 0) {
-            // MFMA A-operand fragments of v_mfma_f32_16x16x4_f32: lane l supplies
-            // A[row = l & 15][k = 4*kk + (l >> 4)].  Rows are the padded coefficient rows
-            // r' = i*Dp + d + cshift (zero rows elsewhere).  Image [rt][kk/2][lane][2].
+            // the padded coefficient rows r' = i*Dp + d + cshift of E' in float32 (zero rows elsewhere), k-steps in pairs per lane (mg_pack.h) ...
             const int KK = p->KK, Dp = p->Dp;
-            std::vector<float> pack((size_t)p->RT * KK * 64, 0.0f);
-            for (int rt = 0; rt < p->RT; rt++)
-                for (int kk = 0; kk < KK; kk++)
-                    for (int lane = 0; lane < 64; lane++) {
-                        int rp = rt * 16 + (lane & 15), k = 4 * kk + (lane >> 4);
-                        int i = rp / Dp, dd = rp - i * Dp - p->cshift;
-                        float v = (i < NB && dd >= 0 && dd < D && k < L) ? (float)p->Es[((size_t)i * D + dd) * L + k] : 0.0f;
-                        pack[(((size_t)rt * (KK / 2) + kk / 2) * 64 + lane) * 2 + (kk & 1)] = v;
-                    }
-            {   // ... followed by a second copy for the chunk-stationary kernel's one-time fragment loads: per tile the k-steps in QUADS per lane ([q][64][4],
-                // q < KK / 4), then the remaining pair ([64][2]) where KK is no multiple of four -- 16-byte loads, 3 instead of 5 instructions per tile at
-                // KK = 10 through a CU's address unit while the whole chip fetches its windows at once (csrc/mg_frames_cs.hip, mg_cs_load_fragments)
-                const size_t n1 = pack.size();
-                pack.resize(2 * n1, 0.0f);
-                for (int rt = 0; rt < p->RT; rt++)
-                    for (int kk = 0; kk < KK; kk++)
-                        for (int lane = 0; lane < 64; lane++) {
-                            const float v = pack[(((size_t)rt * (KK / 2) + kk / 2) * 64 + lane) * 2 + (kk & 1)];
-                            const int q = kk / 4, nq = KK / 4;
-                            const size_t tile = n1 + (size_t)rt * KK * 64;
-                            if (q < nq) pack[tile + ((size_t)q * 64 + lane) * 4 + (kk & 3)] = v;
-                            else pack[tile + (size_t)nq * 256 + (size_t)lane * 2 + (kk & 1)] = v;
-                        }
-            }
+            const size_t n1 = (size_t)p->RT * KK * 64;
+            std::vector<float> plain(n1), pack(2 * n1);
+            mg_pack_fragments(plain.data(), p->RT, KK, [&](int rp, int k) {
+                const int i = rp / Dp, dd = rp - i * Dp - p->cshift;
+                return (i < NB && dd >= 0 && dd < D && k < L) ? (float)p->Es[((size_t)i * D + dd) * L + k] : 0.0f;
+            });
+            mg_pack_regroup(plain.data(), pack.data(), p->RT, KK, 2);
+            // ... followed by a second copy for the chunk-stationary kernel's one-time fragment loads, k-steps in quads per lane: 16-byte loads, 3 instead
+            // of 5 instructions per tile at KK = 10 through a CU's address unit while the whole chip fetches its windows at once (csrc/mg_frames_cs.hip,
+            // mg_cs_load_fragments)
+            mg_pack_regroup(plain.data(), pack.data() + n1, p->RT, KK, 4);
             rc = mg_upload(ctx, pack, &p->d_Epack);
         }
     }
@@ -1041,64 +1015,27 @@ extern "C" int mg_primitive_create(mg_context *ctx, const mg_primitive_desc *d, 
             gconst[k] = std::log(p->gw[k]) + logdet - 0.5 * (double)Lg * log2pi;
         }
         if (p->KKg > 0) {
-            // B fragments of v_mfma_f64_16x16x4_f64: lane l supplies B[k = 4*kk + (l >> 4)][col = l & 15]
+            // images [component][tile][k-step][lane] (mg_pack.h), (i16, k) = (16-wide index, reduction index):
             const int KK = p->KKg, JT = (Lg + 15) / 16, L = Lg;   // inside this block L is the mixture's dimension
-            std::vector<double> ppack((size_t)K * JT * KK * 64, 0.0), mpad((size_t)K * JT * 16, 0.0);
+            const size_t n1 = (size_t)K * JT * KK * 64, tile = (size_t)JT * KK * 64;
+            std::vector<double> ppack(2 * n1), ptpack(n1), cpack(2 * n1), mpad((size_t)K * JT * 16, 0.0), meanpad((size_t)K * JT * 16, 0.0);
             for (int k = 0; k < K; k++) {
+                const double *P = &p->gp[(size_t)k * L * L], *C = &chol[(size_t)k * L * L];
                 for (int j = 0; j < L; j++) mpad[(size_t)k * JT * 16 + j] = gmP[(size_t)k * L + j];
-                for (int jt = 0; jt < JT; jt++)
-                    for (int kk = 0; kk < KK; kk++)
-                        for (int lane = 0; lane < 64; lane++) {
-                            int i = 4 * kk + (lane >> 4), j = 16 * jt + (lane & 15);
-                            if (i < L && j < L && i <= j)
-                                ppack[((((size_t)k * JT + jt) * KK) + kk) * 64 + lane] = p->gp[(size_t)k * Lg * Lg + (size_t)i * L + j];
-                        }
-            }
-            // the transposed factor for z = y P_k^T (log_likelihood_jac): lane l supplies B[k = 4*kk + (l >> 4) (= j)][col = i]
-            std::vector<double> ptpack((size_t)K * JT * KK * 64, 0.0);
-            for (int k = 0; k < K; k++)
-                for (int it = 0; it < JT; it++)
-                    for (int kk = 0; kk < KK; kk++)
-                        for (int lane = 0; lane < 64; lane++) {
-                            int j = 4 * kk + (lane >> 4), i = 16 * it + (lane & 15);
-                            if (i < L && j < L && i <= j)
-                                ptpack[((((size_t)k * JT + it) * KK) + kk) * 64 + lane] = p->gp[(size_t)k * Lg * Lg + (size_t)i * L + j];
-                        }
-            // sampler: x = mu + z L^T, lane l supplies B[k = 4*kk + (l >> 4) (= j)][col = i] = L_k[i][j] (lower triangular)
-            std::vector<double> cpack((size_t)K * JT * KK * 64, 0.0), meanpad((size_t)K * JT * 16, 0.0);
-            for (int k = 0; k < K; k++) {
                 for (int i = 0; i < L; i++) meanpad[(size_t)k * JT * 16 + i] = p->gm[(size_t)k * L + i];
-                for (int it = 0; it < JT; it++)
-                    for (int kk = 0; kk < KK; kk++)
-                        for (int lane = 0; lane < 64; lane++) {
-                            int j = 4 * kk + (lane >> 4), i = 16 * it + (lane & 15);
-                            if (i < L && j < L && j <= i)
-                                cpack[((((size_t)k * JT + it) * KK) + kk) * 64 + lane] = chol[(size_t)k * Lg * Lg + (size_t)i * L + j];
-                        }
+                // the precision factor P_k[i][j], upper triangular, reduced over i ...
+                mg_pack_fragments(&ppack[k * tile], JT, KK, [&](int j, int i) { return i < L && j < L && i <= j ? P[(size_t)i * L + j] : 0.0; });
+                // ... its transpose for z = y P_k^T (log_likelihood_jac), reduced over j ...
+                mg_pack_fragments(&ptpack[k * tile], JT, KK, [&](int i, int j) { return i < L && j < L && i <= j ? P[(size_t)i * L + j] : 0.0; });
+                // ... and the sampler's x = mu + z L^T: L_k[i][j], lower triangular, reduced over j
+                mg_pack_fragments(&cpack[k * tile], JT, KK, [&](int i, int j) { return i < L && j < L && j <= i ? C[(size_t)i * L + j] : 0.0; });
             }
-            {   // ... followed by the same fragments with the k-steps in pairs per lane ([K][JT][KK/2][64][2]): 16-byte loads in the planner step's sampler
-                const size_t n1 = cpack.size();
-                cpack.resize(2 * n1, 0.0);
-                for (int k = 0; k < K; k++)
-                    for (int it = 0; it < JT; it++)
-                        for (int q = 0; q < KK / 2; q++)
-                            for (int lane = 0; lane < 64; lane++)
-                                for (int h = 0; h < 2; h++)
-                                    cpack[n1 + ((((size_t)k * JT + it) * (KK / 2) + q) * 64 + lane) * 2 + h] = cpack[((((size_t)k * JT + it) * KK) + 2 * q + h) * 64 + lane];
-            }
+            // cpack and ppack are each followed by the same fragments with the k-steps in pairs per lane: 16-byte loads in the planner step's sampler
+            mg_pack_regroup(cpack.data(), cpack.data() + n1, K * JT, KK, 2);
             if (rc == MG_OK) rc = mg_upload(ctx, cpack, &p->d_gcholpack);
             if (rc == MG_OK) rc = mg_upload(ctx, meanpad, &p->d_gmeanpad);
-            {   // ... followed by the same fragments with the k-steps in PAIRS per lane, [K][JT][KK/2][64][2]: one 16-byte load per lane fetches two blocks
-                // (the fused step's staged tail and its start-up half: half the load instructions through a CU's address unit, csrc/mg_gmm_device.h)
-                const size_t n1 = ppack.size();
-                ppack.resize(2 * n1, 0.0);
-                for (int k = 0; k < K; k++)
-                    for (int jt = 0; jt < JT; jt++)
-                        for (int q = 0; q < KK / 2; q++)
-                            for (int lane = 0; lane < 64; lane++)
-                                for (int h = 0; h < 2; h++)
-                                    ppack[n1 + ((((size_t)k * JT + jt) * (KK / 2) + q) * 64 + lane) * 2 + h] = ppack[((((size_t)k * JT + jt) * KK) + 2 * q + h) * 64 + lane];
-            }
+            // (the fused step's staged tail and its start-up half: half the load instructions through a CU's address unit, csrc/mg_gmm_device.h)
+            mg_pack_regroup(ppack.data(), ppack.data() + n1, K * JT, KK, 2);
             if (rc == MG_OK) rc = mg_upload(ctx, ppack, &p->d_gPpack);
             if (rc == MG_OK) rc = mg_upload(ctx, ptpack, &p->d_gPTpack);
             if (rc == MG_OK) rc = mg_upload(ctx, mpad, &p->d_gmPpad);
@@ -1479,6 +1416,8 @@ extern "C" int mg_constraint_set_create_full(mg_primitive *p, const mg_skeleton_
     std::vector<std::vector<int>> chains(n), chains2(n);   // chains2: second joint of a midpoint constraint
     std::vector<int32_t> woff(n + 2, 0), chain_len(n, 0);
     std::vector<int> al_chain;   // root .. aligning node, every one of their quaternions turns the heading
+    // (every joint is range-checked before its chain is asked for, and the skeleton's order was checked above: this cannot fail)
+    auto chain_of = [&](int joint, std::vector<int> &ch) { (void)mg_joint_chain(sk ? sk->parents : nullptr, sk ? sk->n_joints : 1, joint, ch); };
     if (al) {
         MG_REQUIRE(D >= 7, "mg_constraint_set_create_aligned: alignment needs the root quaternion, n_dim = %d", D);
         MG_REQUIRE(al->joint == MG_ALIGN_START_POSE || al->joint == 0 || (sk && al->joint > 0 && al->joint < sk->n_joints),
@@ -1486,9 +1425,7 @@ extern "C" int mg_constraint_set_create_full(mg_primitive *p, const mg_skeleton_
         const double hn = std::sqrt(al->heading[0] * al->heading[0] + al->heading[1] * al->heading[1]);
         MG_REQUIRE(std::isfinite(hn) && hn > 0.0 && std::isfinite(al->position[0]) && std::isfinite(al->position[2]),
                    "mg_constraint_set_create_aligned: previous heading / position not finite or zero");
-        if (al->joint == MG_ALIGN_START_POSE) { /* no chain: the rotation is given, not derived from a heading */ }
-        else if (al->joint == 0) al_chain.push_back(0);
-        else for (int j = al->joint; j >= 0; j = sk->parents[j]) al_chain.insert(al_chain.begin(), j);
+        if (al->joint != MG_ALIGN_START_POSE) chain_of(al->joint, al_chain);   // (the start pose's rotation is given, not derived from a heading)
         MG_REQUIRE((int)al_chain.size() <= MG_MAX_CHAIN, "mg_constraint_set_create_aligned: chain of %d joints exceeds %d", (int)al_chain.size(), MG_MAX_CHAIN);
     }
     for (int c = 0; c < n; c++) {
@@ -1504,7 +1441,7 @@ extern "C" int mg_constraint_set_create_full(mg_primitive *p, const mg_skeleton_
         if (type == MG_CONSTRAINT_JOINT_POSITION) {
             MG_REQUIRE(sk != nullptr, "mg_constraint_set_create: constraint %d needs a skeleton (mg_constraint_set_create_fk)", c);
             MG_REQUIRE(cons[c].joint >= 0 && cons[c].joint < sk->n_joints, "mg_constraint_set_create_fk: constraint %d: joint %d out of range", c, cons[c].joint);
-            for (int j = cons[c].joint; j >= 0; j = sk->parents[j]) chains[c].insert(chains[c].begin(), j);
+            chain_of(cons[c].joint, chains[c]);
             int m = (int)chains[c].size() - 1;   // joints below the root on the chain
             // a point given in the joint's own frame hangs below it like one more joint: the joint's own quaternion turns it
             if (cons[c].ref_dir[0] != 0.0 || cons[c].ref_dir[1] != 0.0 || cons[c].ref_dir[2] != 0.0) m++;
@@ -1535,21 +1472,17 @@ extern "C" int mg_constraint_set_create_full(mg_primitive *p, const mg_skeleton_
                 double *rec = tb + MG_POSE_HDR + (size_t)i * MG_POSE_REC;
                 rec[0] = pc.points[3 * i]; rec[1] = pc.points[3 * i + 1]; rec[2] = pc.points[3 * i + 2]; rec[3] = pc.weights[i];
                 std::vector<int> ch;
-                for (int j = pc.joints[i]; j >= 0; j = sk->parents[j]) ch.insert(ch.begin(), j);
+                chain_of(pc.joints[i], ch);
                 const int m = (int)ch.size() - 1;
                 MG_REQUIRE(m <= MG_MAX_CHAIN, "mg_constraint_set_create: pose %d: chain of %d joints exceeds %d", cons[c].joint, m, MG_MAX_CHAIN);
                 rec[4] = m;
-                for (int k = 0; k < m; k++) {   // link k: rotation of chain joint k, offset of chain joint k + 1
-                    rec[5 + 4 * k] = slot[(size_t)ch[(size_t)k]] >= 0 ? 3 + 4 * slot[(size_t)ch[(size_t)k]] : -1.0;
-                    for (int e = 0; e < 3; e++) rec[6 + 4 * k + e] = sk->offsets[(size_t)ch[(size_t)k + 1] * 3 + e];
-                }
+                mg_chain_links(ch, sk->offsets, [&](int j) { return slot[(size_t)j] >= 0 ? 3 + 4 * slot[(size_t)j] : -1; }, rec + 5);   // channels of the pose block
             }
             rows = block * (pc.has_velocity ? 2 : 1);
         } else if (type == MG_CONSTRAINT_LOOK_AT) {
             MG_REQUIRE(cons[c].joint == 0 || (sk && cons[c].joint > 0 && cons[c].joint < sk->n_joints),
                        "mg_constraint_set_create_fk: constraint %d: joint %d needs a skeleton that has it", c, cons[c].joint);
-            if (cons[c].joint == 0) chains[c].push_back(0);
-            else for (int j = cons[c].joint; j >= 0; j = sk->parents[j]) chains[c].insert(chains[c].begin(), j);
+            chain_of(cons[c].joint, chains[c]);
             const int m = (int)chains[c].size();       // quaternions root .. joint; the first m - 1 place the joint
             MG_REQUIRE(m <= MG_MAX_CHAIN, "mg_constraint_set_create_fk: constraint %d: chain of %d joints exceeds %d", c, m, MG_MAX_CHAIN);
             const double rn = std::sqrt(cons[c].ref_dir[0] * cons[c].ref_dir[0] + cons[c].ref_dir[1] * cons[c].ref_dir[1] + cons[c].ref_dir[2] * cons[c].ref_dir[2]);
@@ -1562,8 +1495,8 @@ extern "C" int mg_constraint_set_create_full(mg_primitive *p, const mg_skeleton_
             MG_REQUIRE(sk != nullptr, "mg_constraint_set_create: constraint %d needs a skeleton (mg_constraint_set_create_fk)", c);
             MG_REQUIRE(cons[c].joint >= 0 && cons[c].joint < sk->n_joints && cons[c].joint2 >= 0 && cons[c].joint2 < sk->n_joints,
                        "mg_constraint_set_create_fk: constraint %d: joints %d, %d out of range", c, cons[c].joint, cons[c].joint2);
-            for (int j = cons[c].joint; j >= 0; j = sk->parents[j]) chains[c].insert(chains[c].begin(), j);
-            for (int j = cons[c].joint2; j >= 0; j = sk->parents[j]) chains2[c].insert(chains2[c].begin(), j);
+            chain_of(cons[c].joint, chains[c]);
+            chain_of(cons[c].joint2, chains2[c]);
             const int m = (int)chains[c].size() - 1, m2 = (int)chains2[c].size() - 1;
             MG_REQUIRE(m <= MG_MAX_CHAIN && m2 <= MG_MAX_CHAIN, "mg_constraint_set_create_fk: constraint %d: chain exceeds %d joints", c, MG_MAX_CHAIN);
             chain_len[c] = m | (m2 << 16);
@@ -1571,8 +1504,7 @@ extern "C" int mg_constraint_set_create_full(mg_primitive *p, const mg_skeleton_
         } else if (type == MG_CONSTRAINT_VALUE_HEADING) {
             MG_REQUIRE(cons[c].joint == 0 || (sk && cons[c].joint > 0 && cons[c].joint < sk->n_joints),
                        "mg_constraint_set_create_fk: constraint %d: joint %d needs a skeleton that has it", c, cons[c].joint);
-            if (cons[c].joint == 0) chains[c].push_back(0);
-            else for (int j = cons[c].joint; j >= 0; j = sk->parents[j]) chains[c].insert(chains[c].begin(), j);
+            chain_of(cons[c].joint, chains[c]);
             const int m = (int)chains[c].size();
             MG_REQUIRE(m <= MG_MAX_CHAIN, "mg_constraint_set_create_fk: constraint %d: chain of %d joints exceeds %d", c, m, MG_MAX_CHAIN);
             const double rn = std::sqrt(cons[c].ref_dir[0] * cons[c].ref_dir[0] + cons[c].ref_dir[1] * cons[c].ref_dir[1] + cons[c].ref_dir[2] * cons[c].ref_dir[2]);
@@ -1582,8 +1514,7 @@ extern "C" int mg_constraint_set_create_full(mg_primitive *p, const mg_skeleton_
         } else if (type == MG_CONSTRAINT_JOINT_ORIENTATION) {
             MG_REQUIRE(cons[c].joint == 0 || (sk && cons[c].joint > 0 && cons[c].joint < sk->n_joints),
                        "mg_constraint_set_create_fk: constraint %d: joint %d needs a skeleton that has it", c, cons[c].joint);
-            if (cons[c].joint == 0) chains[c].push_back(0);
-            else for (int j = cons[c].joint; j >= 0; j = sk->parents[j]) chains[c].insert(chains[c].begin(), j);
+            chain_of(cons[c].joint, chains[c]);
             const int m = (int)chains[c].size();       // every quaternion root .. joint turns the vector
             MG_REQUIRE(m <= MG_MAX_CHAIN, "mg_constraint_set_create_fk: constraint %d: chain of %d joints exceeds %d", c, m, MG_MAX_CHAIN);
             const double tn = std::sqrt(cons[c].target[0] * cons[c].target[0] + cons[c].target[1] * cons[c].target[1] + cons[c].target[2] * cons[c].target[2]);
@@ -1699,17 +1630,11 @@ extern "C" int mg_constraint_set_create_full(mg_primitive *p, const mg_skeleton_
     if (rc == MG_OK) { if (chain_len.empty()) chain_len.push_back(0); rc = mg_upload(p->ctx, chain_len, &cs->d_chain); }
     if (rc == MG_OK) rc = mg_upload(p->ctx, choff, &cs->d_choff);
     if (rc == MG_OK && p->KK > 0 && rows_total > 0) {
-        // B fragments of v_mfma_f64_16x16x4_f64 for channels = X . W^T: lane l supplies B[k = 4*kk + (l >> 4)][col = l & 15]
+        // the set's rows W for channels = X . W^T (mg_pack.h)
         const int KK = p->KK, RT = (int)((rows_total + 15) / 16);
-        std::vector<double> wpack((size_t)RT * KK * 64, 0.0), bpad((size_t)RT * 16, 0.0);
+        std::vector<double> wpack((size_t)RT * KK * 64), bpad((size_t)RT * 16, 0.0);
         for (size_t r = 0; r < rows_total; r++) bpad[r] = bias[r];
-        for (int rt = 0; rt < RT; rt++)
-            for (int kk = 0; kk < KK; kk++)
-                for (int lane = 0; lane < 64; lane++) {
-                    const int k = 4 * kk + (lane >> 4);
-                    const size_t row = (size_t)rt * 16 + (lane & 15);
-                    if (k < L && row < rows_total) wpack[((size_t)rt * KK + kk) * 64 + lane] = W[row * L + k];
-                }
+        mg_pack_fragments(wpack.data(), RT, KK, [&](int row, int k) { return k < L && (size_t)row < rows_total ? W[(size_t)row * L + k] : 0.0; });
         cs->RT = RT;
         cs->rows = (int32_t)rows_total;
         rc = mg_upload(p->ctx, wpack, &cs->d_Wpack);
@@ -1944,22 +1869,19 @@ extern "C" int mg_joint_positions(mg_context *ctx, const mg_skeleton_desc *sk, c
     MG_REQUIRE(sk->n_joints > 0 && sk->parents && sk->offsets && sk->quat_channel && sk->parents[0] < 0, "mg_joint_positions: incomplete skeleton");
     std::vector<double> table((size_t)n_out * (1 + 4 * MG_MAX_CHAIN), 0.0);
     for (int o = 0; o < n_out; o++) {
-        MG_REQUIRE(joints[o] >= 0 && joints[o] < sk->n_joints, "mg_joint_positions: joint %d out of range", joints[o]);
         std::vector<int> ch;
-        for (int j = joints[o]; j >= 0; j = sk->parents[j]) {
-            MG_REQUIRE(sk->parents[j] < j, "mg_joint_positions: joint %d: parents must precede their children", j);
-            ch.insert(ch.begin(), j);
-        }
+        int bad;
+        const int st = mg_joint_chain(sk->parents, sk->n_joints, joints[o], ch, &bad);
+        MG_REQUIRE(st == MG_CHAIN_OK, "mg_joint_positions: joint %d%s", bad, mg_chain_why(st));
         const int m = (int)ch.size() - 1;
         MG_REQUIRE(m <= MG_MAX_CHAIN, "mg_joint_positions: chain of %d joints exceeds %d", m, MG_MAX_CHAIN);
-        double *rec = &table[(size_t)o * (1 + 4 * MG_MAX_CHAIN)];
-        rec[0] = m;
-        for (int k = 0; k < m; k++) {   // link k: rotation of chain joint k, offset of chain joint k + 1
+        for (int k = 0; k < m; k++) {
             const int qc = sk->quat_channel[ch[(size_t)k]];
             MG_REQUIRE(qc < 0 || qc + 4 <= n_dim, "mg_joint_positions: quaternion channel %d outside n_dim = %d", qc, n_dim);
-            rec[1 + 4 * k] = qc;
-            for (int e = 0; e < 3; e++) rec[2 + 4 * k + e] = sk->offsets[(size_t)ch[(size_t)k + 1] * 3 + e];
         }
+        double *rec = &table[(size_t)o * (1 + 4 * MG_MAX_CHAIN)];
+        rec[0] = m;
+        mg_chain_links(ch, sk->offsets, [&](int j) { return sk->quat_channel[j]; }, rec + 1);
     }
     if (n_frames == 0) return MG_OK;
     MG_REQUIRE(frames_dev && out_dev, "mg_joint_positions: NULL pointer");

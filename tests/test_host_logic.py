@@ -398,6 +398,17 @@ def test_c_abi_header_is_plain_c(tmp_path):
     subprocess.check_call(["g++", "-std=c++11", "-Wall", "-Werror", "-I", inc, "-fsyntax-only", "-x", "c++", str(src)])
 
 
+def test_operand_images_and_joint_chains_decode():
+    """csrc/mg_pack.h states the MFMA operand layout and the joint chain once; tests/native/pack_check.cpp decodes every
+    element of its images back to (tile, k-step, lane) and walks the chains' edge cases.  A program of its own (built by
+    tests/native/Makefile, under the host sanitizers where the compiler has them): nothing is loaded into this process."""
+    import subprocess
+    native = os.path.join(ROOT, "tests", "native")
+    subprocess.check_call(["make", "-s", "-C", native, "pack_check"])
+    done = subprocess.run([os.path.join(native, "pack_check")], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=60)
+    assert done.returncode == 0, done.stdout.decode(errors="replace")
+
+
 def test_local_optimizer_spends_the_references_evaluation_budget():
     """HipLeastSquares hands MINPACK an analytic-looking Jacobian (the batched finite differences), so scipy runs lmder,
     whose maxfev counts residual calls only; the reference runs leastsq WITHOUT Dfun (least_squares.py:50-53), where the L

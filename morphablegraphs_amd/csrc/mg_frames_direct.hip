@@ -82,12 +82,9 @@ int mg_launch_frames_direct(mg_primitive *p, const mg_time_grid *g, const void *
     int64_t total = B * (int64_t)g->T * p->D;
     int64_t blocks = (total + 255) / 256;
     int grid = (int)std::min<int64_t>(blocks, (int64_t)p->ctx->n_cu * 32);
-    hipStream_t st = p->ctx->stream;
-    const bool lf = (ldt == MG_F64);
-    if (lf && out_f64) hipLaunchKernelGGL((mg_frames_direct_kernel<true, true>), dim3(grid), dim3(256), 0, st, a);
-    else if (lf) hipLaunchKernelGGL((mg_frames_direct_kernel<true, false>), dim3(grid), dim3(256), 0, st, a);
-    else if (out_f64) hipLaunchKernelGGL((mg_frames_direct_kernel<false, true>), dim3(grid), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((mg_frames_direct_kernel<false, false>), dim3(grid), dim3(256), 0, st, a);
+    mg_dispatch_flags(ldt == MG_F64, out_f64, [&](auto LAT_F64, auto OUT_F64) {
+        hipLaunchKernelGGL((mg_frames_direct_kernel<LAT_F64, OUT_F64>), dim3(grid), dim3(256), 0, p->ctx->stream, a);
+    });
     MG_HIP_CHECK(hipGetLastError());
     return MG_OK;
 }

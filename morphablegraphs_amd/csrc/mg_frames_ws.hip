@@ -428,77 +428,49 @@ __global__ __launch_bounds__(MG_WS_BLOCK) void mg_frames_ws_kernel(
 // -----------------------------------------------------------------------------------------
 // launch
 // -----------------------------------------------------------------------------------------
-template <int KK, bool LAT_F64, bool FUSE, bool SPLIT>
-static int mg_launch_ws_inst(mg_primitive *p, const mg_time_grid *g, const void *lat, float *out, float *logp, const mg_frames_args &a,
-                                 int buf_bytes, int lds, int grid, const mg_launch_events &ev) {
-    // hipExtLaunchKernelGGL with NULL events is hipLaunchKernelGGL; with events the dispatch records its own begin and end
-    hipExtLaunchKernelGGL((mg_frames_ws_kernel<KK, LAT_F64, FUSE, SPLIT>), dim3(grid), dim3(MG_WS_BLOCK), lds, p->ctx->stream, ev.start, ev.stop, 0,
-                          (const float *)p->d_Epack, (const float *)p->d_mean32, (const double *)p->d_Erpack, (const double *)p->d_meanroot, lat,
-                          (const int32_t *)g->d_i0, (const float4 *)g->d_w32, (const double *)g->d_wtap, (const float4 *)g->d_rootm,
-                          (const mg_chunk *)g->d_chunks, out,
-                          (const double *)p->d_gPpack, (const double *)p->d_gmPpad, (const double *)p->d_gconst, logp, a, (int)p->K,
-                          (int)((p->L + 15) / 16), buf_bytes);
-    MG_HIP_CHECK(hipGetLastError());
-    return MG_OK;
-}
-
-template <int KK>
-static int mg_launch_ws_kk(mg_primitive *p, const mg_time_grid *g, const void *lat, float *out, float *logp, const mg_frames_args &a,
-                               bool lat_f64, bool split, int buf_bytes, int lds, int grid, const mg_launch_events &ev) {
-    if (logp) {
-        // fused instances exist for <= 40 components: beyond that the mixture fragments no longer fit the
-        // register budget next to the sweep (mg_frames_can_fuse_gmm refuses, so this is never reached)
-        if constexpr (KK <= MG_FUSE_MAX_KK) {
-            if (split)
-                return lat_f64 ? mg_launch_ws_inst<KK, true, true, true>(p, g, lat, out, logp, a, buf_bytes, lds, grid, ev)
-                               : mg_launch_ws_inst<KK, false, true, true>(p, g, lat, out, logp, a, buf_bytes, lds, grid, ev);
-            return lat_f64 ? mg_launch_ws_inst<KK, true, true, false>(p, g, lat, out, logp, a, buf_bytes, lds, grid, ev)
-                           : mg_launch_ws_inst<KK, false, true, false>(p, g, lat, out, logp, a, buf_bytes, lds, grid, ev);
-        }
-        mg_set_error("mg_step_frames_and_logp: no fused kernel for %d components", p->L);
-        return MG_ERR_UNSUPPORTED;
-    }
-    if (split)
-        return lat_f64 ? mg_launch_ws_inst<KK, true, false, true>(p, g, lat, out, nullptr, a, buf_bytes, lds, grid, ev)
-                       : mg_launch_ws_inst<KK, false, false, true>(p, g, lat, out, nullptr, a, buf_bytes, lds, grid, ev);
-    return lat_f64 ? mg_launch_ws_inst<KK, true, false, false>(p, g, lat, out, nullptr, a, buf_bytes, lds, grid, ev)
-                   : mg_launch_ws_inst<KK, false, false, false>(p, g, lat, out, nullptr, a, buf_bytes, lds, grid, ev);
+// f(kernel) for the one instantiation (kk, lat_f64, fused, split) selects: the launch and the large-LDS opt-in both name it here.
+// Fused instances exist for <= 40 components: beyond that the mixture fragments no longer fit the register budget next to the sweep
+// (mg_frames_can_fuse_gmm refuses, so a launch never asks for one)
+template <class F>
+static int mg_ws_with_kernel(int kk, bool lat_f64, bool fused, bool split, int L, F f) {
+    const int rc = mg_dispatch_kk(kk, 1, [&](auto kk_tag) {
+        constexpr int KK = kk_tag;
+        return mg_dispatch_flags(lat_f64, fused, split, [&](auto LAT_F64, auto FUSE, auto SPLIT) -> int {
+            if constexpr (!FUSE || KK <= MG_FUSE_MAX_KK) return f(mg_frames_ws_kernel<KK, LAT_F64, FUSE, SPLIT>);
+            mg_set_error("mg_step_frames_and_logp: no fused kernel for %d components", L);
+            return MG_ERR_UNSUPPORTED;
+        });
+    });
+    if (rc <= 0) return rc;   // a status; 1: no such k-step count
+    mg_set_error("mg_back_project_frames: MFMA path needs n_components <= 64");
+    return MG_ERR_UNSUPPORTED;
 }
 
 int mg_launch_frames_ws(mg_primitive *p, const mg_time_grid *g, const void *lat, float *out, float *logp, const mg_frames_args &a, bool lat_f64,
                         bool split, int buf_bytes, int lds, int grid, const mg_launch_events &ev) {
-    switch (p->KK) {
-        case 2: return mg_launch_ws_kk<2>(p, g, lat, out, logp, a, lat_f64, split, buf_bytes, lds, grid, ev);
-        case 4: return mg_launch_ws_kk<4>(p, g, lat, out, logp, a, lat_f64, split, buf_bytes, lds, grid, ev);
-        case 6: return mg_launch_ws_kk<6>(p, g, lat, out, logp, a, lat_f64, split, buf_bytes, lds, grid, ev);
-        case 8: return mg_launch_ws_kk<8>(p, g, lat, out, logp, a, lat_f64, split, buf_bytes, lds, grid, ev);
-        case 10: return mg_launch_ws_kk<10>(p, g, lat, out, logp, a, lat_f64, split, buf_bytes, lds, grid, ev);
-        case 12: return mg_launch_ws_kk<12>(p, g, lat, out, logp, a, lat_f64, split, buf_bytes, lds, grid, ev);
-        case 14: return mg_launch_ws_kk<14>(p, g, lat, out, logp, a, lat_f64, split, buf_bytes, lds, grid, ev);
-        case 16: return mg_launch_ws_kk<16>(p, g, lat, out, logp, a, lat_f64, split, buf_bytes, lds, grid, ev);
-        default: mg_set_error("mg_back_project_frames: MFMA path needs n_components <= 64"); return MG_ERR_UNSUPPORTED;
-    }
+    return mg_ws_with_kernel(p->KK, lat_f64, logp != nullptr, split, p->L, [&](auto kernel) -> int {
+        // hipExtLaunchKernelGGL with NULL events is hipLaunchKernelGGL; with events the dispatch records its own begin and end
+        hipExtLaunchKernelGGL(kernel, dim3(grid), dim3(MG_WS_BLOCK), lds, p->ctx->stream, ev.start, ev.stop, 0,
+                              (const float *)p->d_Epack, (const float *)p->d_mean32, (const double *)p->d_Erpack, (const double *)p->d_meanroot, lat,
+                              (const int32_t *)g->d_i0, (const float4 *)g->d_w32, (const double *)g->d_wtap, (const float4 *)g->d_rootm,
+                              (const mg_chunk *)g->d_chunks, out,
+                              (const double *)p->d_gPpack, (const double *)p->d_gmPpad, (const double *)p->d_gconst, logp, a, (int)p->K,
+                              (int)((p->L + 15) / 16), buf_bytes);
+        MG_HIP_CHECK(hipGetLastError());
+        return MG_OK;
+    });
 }
 
-template <int KK>
-static int mg_ws_attr_kk() {
-    MG_HIP_CHECK(mg_lds_opt_in(160 * 1024, mg_frames_ws_kernel<KK, true, false, false>, mg_frames_ws_kernel<KK, false, false, false>,
-                               mg_frames_ws_kernel<KK, true, false, true>, mg_frames_ws_kernel<KK, false, false, true>));
-    if constexpr (KK <= MG_FUSE_MAX_KK) {
-        MG_HIP_CHECK(mg_lds_opt_in(160 * 1024, mg_frames_ws_kernel<KK, true, true, false>, mg_frames_ws_kernel<KK, false, true, false>,
-                                   mg_frames_ws_kernel<KK, true, true, true>, mg_frames_ws_kernel<KK, false, true, true>));
-    }
-    return MG_OK;
-}
+// every instantiation a launch can select, through the same expression (flag bits of m: 1 lat_f64, 2 split, 4 fused)
 int mg_frames_ws_attributes() {
-    int rc;
-    if ((rc = mg_ws_attr_kk<2>()) != MG_OK) return rc;
-    if ((rc = mg_ws_attr_kk<4>()) != MG_OK) return rc;
-    if ((rc = mg_ws_attr_kk<6>()) != MG_OK) return rc;
-    if ((rc = mg_ws_attr_kk<8>()) != MG_OK) return rc;
-    if ((rc = mg_ws_attr_kk<10>()) != MG_OK) return rc;
-    if ((rc = mg_ws_attr_kk<12>()) != MG_OK) return rc;
-    if ((rc = mg_ws_attr_kk<14>()) != MG_OK) return rc;
-    if ((rc = mg_ws_attr_kk<16>()) != MG_OK) return rc;
-    return MG_OK;
+    return mg_each_kk([](auto kk_tag) {
+        constexpr int KK = kk_tag;
+        int rc = MG_OK;
+        for (int m = 0; m < (KK <= MG_FUSE_MAX_KK ? 8 : 4) && rc == MG_OK; m++)
+            rc = mg_ws_with_kernel(KK, m & 1, m & 4, m & 2, 0, [](auto kernel) -> int {
+                MG_HIP_CHECK(mg_lds_opt_in(160 * 1024, kernel));
+                return MG_OK;
+            });
+        return rc;
+    });
 }

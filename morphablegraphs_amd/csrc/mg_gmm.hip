@@ -239,12 +239,9 @@ static int mg_launch_gmm_mfma_kk(mg_primitive *p, const void *x, int xdt, int64_
     const int64_t grid = (B + 15) / 16;
     if (grid > 0x7fffffff) { mg_set_error("mg_gmm_log_prob: too many samples"); return MG_ERR_UNSUPPORTED; }
     const size_t lds = (size_t)p->K * 16 * 8 * 2;
-    hipStream_t st = p->ctx->stream;
-    const bool xf = xdt == MG_F64, of = odt == MG_F64;
-    if (xf && of) hipLaunchKernelGGL((mg_gmm_logp_mfma_kernel<KK, true, true>), dim3((int)grid), dim3(256), lds, st, p->d_gPpack, p->d_gmPpad, p->d_gconst, x, out, a);
-    else if (xf) hipLaunchKernelGGL((mg_gmm_logp_mfma_kernel<KK, true, false>), dim3((int)grid), dim3(256), lds, st, p->d_gPpack, p->d_gmPpad, p->d_gconst, x, out, a);
-    else if (of) hipLaunchKernelGGL((mg_gmm_logp_mfma_kernel<KK, false, true>), dim3((int)grid), dim3(256), lds, st, p->d_gPpack, p->d_gmPpad, p->d_gconst, x, out, a);
-    else hipLaunchKernelGGL((mg_gmm_logp_mfma_kernel<KK, false, false>), dim3((int)grid), dim3(256), lds, st, p->d_gPpack, p->d_gmPpad, p->d_gconst, x, out, a);
+    mg_dispatch_flags(xdt == MG_F64, odt == MG_F64, [&](auto X_F64, auto OUT_F64) {
+        hipLaunchKernelGGL((mg_gmm_logp_mfma_kernel<KK, X_F64, OUT_F64>), dim3((int)grid), dim3(256), lds, p->ctx->stream, p->d_gPpack, p->d_gmPpad, p->d_gconst, x, out, a);
+    });
     MG_HIP_CHECK(hipGetLastError());
     return MG_OK;
 }
@@ -456,22 +453,20 @@ static int mg_launch_gmm_lds_kk(mg_primitive *p, const void *x, int xdt, int64_t
     // every CU gets a workgroup as soon as there are that many tiles: the tiles of a workgroup run side by side on its sixteen
     // waves, so few tiles per workgroup mean short chains per SIMD (16 workgroups of 16 busy waves: 36 us at B = 4096)
     const int grid = (int)std::min<int64_t>(std::max(1, p->ctx->n_cu), n_tiles);
-    hipStream_t st = p->ctx->stream;
-    const bool xf = xdt == MG_F64, of = odt == MG_F64;
+    // f(kernel) for (latents float64, log p float64, with the objective); the objective's log p is float64 (or not written at all)
+    // whatever odt says, so there are six kernels, not eight.  The launch and the opt-in both name the kernel here.
+    auto with_kernel = [](bool xf, bool of, bool score, auto f) {
+        return mg_dispatch_flags(xf, of, score, [&](auto X_F64, auto OUT_F64, auto SCORE) { return f(mg_gmm_logp_lds_kernel<KK, X_F64, OUT_F64 || SCORE, SCORE>); });
+    };
     // the dynamic-LDS attribute is a property of (kernel, device): once per context (a per-process flag left a second
-    // GPU's context without it)
-    MG_HIP_CHECK(mg_lds_opt_in_once(p->ctx->attr_gmm_lds, 1u << (KK / 2), 160 * 1024, mg_gmm_logp_lds_kernel<KK, true, true, false>,
-                                    mg_gmm_logp_lds_kernel<KK, true, false, false>, mg_gmm_logp_lds_kernel<KK, false, true, false>,
-                                    mg_gmm_logp_lds_kernel<KK, false, false, false>, mg_gmm_logp_lds_kernel<KK, true, true, true>,
-                                    mg_gmm_logp_lds_kernel<KK, false, true, true>));
-    if (cs) {   // the objective: log p in float64 (or not at all), errors and objective in float64
-        if (xf) hipLaunchKernelGGL((mg_gmm_logp_lds_kernel<KK, true, true, true>), dim3(grid), dim3(64 * nw), lds, st, p->d_gPpack, p->d_gmPpad, p->d_gconst, x, out, a, n_tiles, oa);
-        else hipLaunchKernelGGL((mg_gmm_logp_lds_kernel<KK, false, true, true>), dim3(grid), dim3(64 * nw), lds, st, p->d_gPpack, p->d_gmPpad, p->d_gconst, x, out, a, n_tiles, oa);
+    // GPU's context without it), for every kernel a later launch with this KK can select
+    if (!(p->ctx->attr_gmm_lds & 1u << (KK / 2))) {
+        for (int m = 0; m < 8; m++) MG_HIP_CHECK(with_kernel(m & 1, m & 2, m & 4, [](auto kernel) { return mg_lds_opt_in(160 * 1024, kernel); }));
+        p->ctx->attr_gmm_lds |= 1u << (KK / 2);
     }
-    else if (xf && of) hipLaunchKernelGGL((mg_gmm_logp_lds_kernel<KK, true, true, false>), dim3(grid), dim3(1024), lds, st, p->d_gPpack, p->d_gmPpad, p->d_gconst, x, out, a, n_tiles, oa);
-    else if (xf) hipLaunchKernelGGL((mg_gmm_logp_lds_kernel<KK, true, false, false>), dim3(grid), dim3(1024), lds, st, p->d_gPpack, p->d_gmPpad, p->d_gconst, x, out, a, n_tiles, oa);
-    else if (of) hipLaunchKernelGGL((mg_gmm_logp_lds_kernel<KK, false, true, false>), dim3(grid), dim3(1024), lds, st, p->d_gPpack, p->d_gmPpad, p->d_gconst, x, out, a, n_tiles, oa);
-    else hipLaunchKernelGGL((mg_gmm_logp_lds_kernel<KK, false, false, false>), dim3(grid), dim3(1024), lds, st, p->d_gPpack, p->d_gmPpad, p->d_gconst, x, out, a, n_tiles, oa);
+    with_kernel(xdt == MG_F64, odt == MG_F64, cs != nullptr, [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(64 * nw), lds, p->ctx->stream, p->d_gPpack, p->d_gmPpad, p->d_gconst, x, out, a, n_tiles, oa);
+    });
     MG_HIP_CHECK(hipGetLastError());
     return MG_OK;
 }
@@ -491,17 +486,10 @@ bool mg_objective_can_fuse(const mg_primitive *p, const mg_constraint_set *cs) {
 }
 int mg_launch_objective(mg_primitive *p, const mg_constraint_set *cs, const void *x, int xdt, int64_t B, int64_t ld, double error_scale,
                         double quality_scale, double *logp_out, double *err_out, double *obj_out) {
-    switch (p->KKg) {
-        case 2: return mg_launch_gmm_lds_kk<2>(p, x, xdt, B, ld, logp_out, MG_F64, cs, error_scale, quality_scale, err_out, obj_out);
-        case 4: return mg_launch_gmm_lds_kk<4>(p, x, xdt, B, ld, logp_out, MG_F64, cs, error_scale, quality_scale, err_out, obj_out);
-        case 6: return mg_launch_gmm_lds_kk<6>(p, x, xdt, B, ld, logp_out, MG_F64, cs, error_scale, quality_scale, err_out, obj_out);
-        case 8: return mg_launch_gmm_lds_kk<8>(p, x, xdt, B, ld, logp_out, MG_F64, cs, error_scale, quality_scale, err_out, obj_out);
-        case 10: return mg_launch_gmm_lds_kk<10>(p, x, xdt, B, ld, logp_out, MG_F64, cs, error_scale, quality_scale, err_out, obj_out);
-        case 12: return mg_launch_gmm_lds_kk<12>(p, x, xdt, B, ld, logp_out, MG_F64, cs, error_scale, quality_scale, err_out, obj_out);
-        case 14: return mg_launch_gmm_lds_kk<14>(p, x, xdt, B, ld, logp_out, MG_F64, cs, error_scale, quality_scale, err_out, obj_out);
-        case 16: return mg_launch_gmm_lds_kk<16>(p, x, xdt, B, ld, logp_out, MG_F64, cs, error_scale, quality_scale, err_out, obj_out);
-        default: break;
-    }
+    const int rc = mg_dispatch_kk(p->KKg, 1, [&](auto KK) {
+        return mg_launch_gmm_lds_kk<KK>(p, x, xdt, B, ld, logp_out, MG_F64, cs, error_scale, quality_scale, err_out, obj_out);
+    });
+    if (rc <= 0) return rc;   // a status; 1: no such k-step count
     mg_set_error("mg_objective_error_and_naturalness: no one-launch kernel for this mixture");
     return MG_ERR_UNSUPPORTED;
 }
@@ -516,31 +504,14 @@ static bool mg_gmm_use_lds_kernel(const mg_primitive *p, int64_t B) {
 }
 
 int mg_launch_gmm_logp(mg_primitive *p, const void *x, int xdt, int64_t B, int64_t ld, void *out, int odt) {
+    // (1: no such k-step count -- the next kernel down; anything else is the launcher's status)
     if (mg_gmm_use_lds_kernel(p, B)) {
-        switch (p->KKg) {
-            case 2: return mg_launch_gmm_lds_kk<2>(p, x, xdt, B, ld, out, odt);
-            case 4: return mg_launch_gmm_lds_kk<4>(p, x, xdt, B, ld, out, odt);
-            case 6: return mg_launch_gmm_lds_kk<6>(p, x, xdt, B, ld, out, odt);
-            case 8: return mg_launch_gmm_lds_kk<8>(p, x, xdt, B, ld, out, odt);
-            case 10: return mg_launch_gmm_lds_kk<10>(p, x, xdt, B, ld, out, odt);
-            case 12: return mg_launch_gmm_lds_kk<12>(p, x, xdt, B, ld, out, odt);
-            case 14: return mg_launch_gmm_lds_kk<14>(p, x, xdt, B, ld, out, odt);
-            case 16: return mg_launch_gmm_lds_kk<16>(p, x, xdt, B, ld, out, odt);
-            default: break;
-        }
+        const int rc = mg_dispatch_kk(p->KKg, 1, [&](auto KK) { return mg_launch_gmm_lds_kk<KK>(p, x, xdt, B, ld, out, odt); });
+        if (rc <= 0) return rc;
     }
     if (p->d_gPpack && p->K * 16 * 16 <= 60 * 1024) {
-        switch (p->KKg) {
-            case 2: return mg_launch_gmm_mfma_kk<2>(p, x, xdt, B, ld, out, odt);
-            case 4: return mg_launch_gmm_mfma_kk<4>(p, x, xdt, B, ld, out, odt);
-            case 6: return mg_launch_gmm_mfma_kk<6>(p, x, xdt, B, ld, out, odt);
-            case 8: return mg_launch_gmm_mfma_kk<8>(p, x, xdt, B, ld, out, odt);
-            case 10: return mg_launch_gmm_mfma_kk<10>(p, x, xdt, B, ld, out, odt);
-            case 12: return mg_launch_gmm_mfma_kk<12>(p, x, xdt, B, ld, out, odt);
-            case 14: return mg_launch_gmm_mfma_kk<14>(p, x, xdt, B, ld, out, odt);
-            case 16: return mg_launch_gmm_mfma_kk<16>(p, x, xdt, B, ld, out, odt);
-            default: break;
-        }
+        const int rc = mg_dispatch_kk(p->KKg, 1, [&](auto KK) { return mg_launch_gmm_mfma_kk<KK>(p, x, xdt, B, ld, out, odt); });
+        if (rc <= 0) return rc;
     }
     mg_gmm_args a;
     a.P = p->d_gP; a.mP = p->d_gmP; a.cst = p->d_gconst; a.x = x; a.out = out; a.B = B; a.ld = ld; a.K = p->K; a.L = p->Lg;
@@ -551,16 +522,13 @@ int mg_launch_gmm_logp(mg_primitive *p, const void *x, int xdt, int64_t B, int64
         return MG_ERR_UNSUPPORTED;
     }
     dim3 blk(MG_GMM_CANDS * MG_GMM_WAVES);
-    hipStream_t st = p->ctx->stream;
-    const bool xf = xdt == MG_F64, of = odt == MG_F64;
-    if (lds > 64 * 1024) MG_HIP_CHECK(mg_lds_opt_in(160 * 1024, mg_gmm_logp_kernel<true, true>, mg_gmm_logp_kernel<true, false>, mg_gmm_logp_kernel<false, true>,
-                                                    mg_gmm_logp_kernel<false, false>));
-    if (xf && of) hipLaunchKernelGGL((mg_gmm_logp_kernel<true, true>), dim3((int)grid), blk, lds, st, a);
-    else if (xf) hipLaunchKernelGGL((mg_gmm_logp_kernel<true, false>), dim3((int)grid), blk, lds, st, a);
-    else if (of) hipLaunchKernelGGL((mg_gmm_logp_kernel<false, true>), dim3((int)grid), blk, lds, st, a);
-    else hipLaunchKernelGGL((mg_gmm_logp_kernel<false, false>), dim3((int)grid), blk, lds, st, a);
-    MG_HIP_CHECK(hipGetLastError());
-    return MG_OK;
+    return mg_dispatch_flags(xdt == MG_F64, odt == MG_F64, [&](auto X_F64, auto OUT_F64) -> int {
+        const auto kernel = mg_gmm_logp_kernel<X_F64, OUT_F64>;
+        if (lds > 64 * 1024) MG_HIP_CHECK(mg_lds_opt_in(160 * 1024, kernel));
+        hipLaunchKernelGGL(kernel, dim3((int)grid), blk, lds, p->ctx->stream, a);
+        MG_HIP_CHECK(hipGetLastError());
+        return MG_OK;
+    });
 }
 
 // -----------------------------------------------------------------------------------------
@@ -750,28 +718,18 @@ static int mg_launch_gmm_jac_mfma_kk(mg_primitive *p, const void *x, int xdt, in
     const int64_t grid = (B + 15) / 16;
     const size_t lds = ((size_t)p->K * 16 * (JTM * 16 + 1) + (size_t)p->K * 16 + 16 + (size_t)4 * 16 * JTM * 16) * 8;
     if (lds > 150 * 1024 || grid > 0x7fffffff) return MG_ERR_UNSUPPORTED;
-    if (lds > 64 * 1024) MG_HIP_CHECK(mg_lds_opt_in(160 * 1024, mg_gmm_jac_mfma_kernel<KK, true>, mg_gmm_jac_mfma_kernel<KK, false>));
-    hipStream_t st = p->ctx->stream;
-    if (xdt == MG_F64) hipLaunchKernelGGL((mg_gmm_jac_mfma_kernel<KK, true>), dim3((int)grid), dim3(256), lds, st, p->d_gPpack, p->d_gPTpack, p->d_gmPpad, p->d_gconst, x, out, a);
-    else hipLaunchKernelGGL((mg_gmm_jac_mfma_kernel<KK, false>), dim3((int)grid), dim3(256), lds, st, p->d_gPpack, p->d_gPTpack, p->d_gmPpad, p->d_gconst, x, out, a);
-    MG_HIP_CHECK(hipGetLastError());
-    return MG_OK;
+    return mg_dispatch_flags(xdt == MG_F64, [&](auto X_F64) -> int {
+        const auto kernel = mg_gmm_jac_mfma_kernel<KK, X_F64>;
+        if (lds > 64 * 1024) MG_HIP_CHECK(mg_lds_opt_in(160 * 1024, kernel));
+        hipLaunchKernelGGL(kernel, dim3((int)grid), dim3(256), lds, p->ctx->stream, p->d_gPpack, p->d_gPTpack, p->d_gmPpad, p->d_gconst, x, out, a);
+        MG_HIP_CHECK(hipGetLastError());
+        return MG_OK;
+    });
 }
 
 int mg_launch_gmm_jac(mg_primitive *p, const void *x, int xdt, int64_t B, int64_t ld, double *out) {
     if (p->d_gPTpack) {
-        int rc = MG_ERR_UNSUPPORTED;
-        switch (p->KKg) {
-            case 2: rc = mg_launch_gmm_jac_mfma_kk<2>(p, x, xdt, B, ld, out); break;
-            case 4: rc = mg_launch_gmm_jac_mfma_kk<4>(p, x, xdt, B, ld, out); break;
-            case 6: rc = mg_launch_gmm_jac_mfma_kk<6>(p, x, xdt, B, ld, out); break;
-            case 8: rc = mg_launch_gmm_jac_mfma_kk<8>(p, x, xdt, B, ld, out); break;
-            case 10: rc = mg_launch_gmm_jac_mfma_kk<10>(p, x, xdt, B, ld, out); break;
-            case 12: rc = mg_launch_gmm_jac_mfma_kk<12>(p, x, xdt, B, ld, out); break;
-            case 14: rc = mg_launch_gmm_jac_mfma_kk<14>(p, x, xdt, B, ld, out); break;
-            case 16: rc = mg_launch_gmm_jac_mfma_kk<16>(p, x, xdt, B, ld, out); break;
-            default: break;
-        }
+        const int rc = mg_dispatch_kk(p->KKg, (int)MG_ERR_UNSUPPORTED, [&](auto KK) { return mg_launch_gmm_jac_mfma_kk<KK>(p, x, xdt, B, ld, out); });
         if (rc != MG_ERR_UNSUPPORTED) return rc;   // too many components for LDS: the VALU kernel below
     }
     mg_gmm_args a;
@@ -869,18 +827,14 @@ static int mg_launch_gmm_sample_mfma_kk(mg_primitive *p, const int64_t *cum_dev,
     if (grid <= 0) return MG_OK;
     if (grid > 0x7fffffff) return MG_ERR_UNSUPPORTED;
     const size_t lds = (size_t)4 * 16 * (4 * KK + 1) * 8;
-    hipStream_t st = p->ctx->stream;
     const int JT = (p->Lg + 15) / 16;
     mg_cum_arg ca;
     memset(&ca, 0, sizeof(ca));
-    if (cum_host) {
-        memcpy(ca.v, cum_host, sizeof(int64_t) * 2 * (p->K + 1));
-        if (xdt == MG_F64) hipLaunchKernelGGL((mg_gmm_sample_mfma_kernel<KK, true, true>), dim3((int)grid), dim3(256), lds, st, p->d_gcholpack, p->d_gmeanpad, nullptr, ca, x, comp, n_tiles, ld, seed, p->K, p->Lg, JT, tile0, row_lo, row_hi);
-        else hipLaunchKernelGGL((mg_gmm_sample_mfma_kernel<KK, false, true>), dim3((int)grid), dim3(256), lds, st, p->d_gcholpack, p->d_gmeanpad, nullptr, ca, x, comp, n_tiles, ld, seed, p->K, p->Lg, JT, tile0, row_lo, row_hi);
-    } else {
-        if (xdt == MG_F64) hipLaunchKernelGGL((mg_gmm_sample_mfma_kernel<KK, true, false>), dim3((int)grid), dim3(256), lds, st, p->d_gcholpack, p->d_gmeanpad, cum_dev, ca, x, comp, n_tiles, ld, seed, p->K, p->Lg, JT, tile0, row_lo, row_hi);
-        else hipLaunchKernelGGL((mg_gmm_sample_mfma_kernel<KK, false, false>), dim3((int)grid), dim3(256), lds, st, p->d_gcholpack, p->d_gmeanpad, cum_dev, ca, x, comp, n_tiles, ld, seed, p->K, p->Lg, JT, tile0, row_lo, row_hi);
-    }
+    if (cum_host) memcpy(ca.v, cum_host, sizeof(int64_t) * 2 * (p->K + 1));   // the prefix sums travel in the arguments: no device copy is read
+    mg_dispatch_flags(xdt == MG_F64, cum_host != nullptr, [&](auto X_F64, auto CUM_ARG) {
+        hipLaunchKernelGGL((mg_gmm_sample_mfma_kernel<KK, X_F64, CUM_ARG>), dim3((int)grid), dim3(256), lds, p->ctx->stream, p->d_gcholpack, p->d_gmeanpad,
+                           CUM_ARG ? nullptr : cum_dev, ca, x, comp, n_tiles, ld, seed, p->K, p->Lg, JT, tile0, row_lo, row_hi);
+    });
     MG_HIP_CHECK(hipGetLastError());
     return MG_OK;
 }
@@ -889,17 +843,10 @@ static int mg_launch_gmm_sample_mfma_kk(mg_primitive *p, const int64_t *cum_dev,
 int mg_launch_gmm_sample(mg_primitive *p, int64_t n, const int64_t *cum_dev, const int64_t *cum_host, int64_t n_tiles, uint64_t seed, void *x, int xdt, int64_t ld, int32_t *comp,
                          int64_t tile0, int64_t row_lo, int64_t row_hi) {
     if (p->d_gcholpack && (cum_host || cum_dev) && !p->ctx->opt[MG_OPT_FORCE_VALU_SAMPLE]) {
-        switch (p->KKg) {
-            case 2: return mg_launch_gmm_sample_mfma_kk<2>(p, cum_dev, cum_host, n_tiles, seed, x, xdt, ld, comp, tile0, row_lo, row_hi);
-            case 4: return mg_launch_gmm_sample_mfma_kk<4>(p, cum_dev, cum_host, n_tiles, seed, x, xdt, ld, comp, tile0, row_lo, row_hi);
-            case 6: return mg_launch_gmm_sample_mfma_kk<6>(p, cum_dev, cum_host, n_tiles, seed, x, xdt, ld, comp, tile0, row_lo, row_hi);
-            case 8: return mg_launch_gmm_sample_mfma_kk<8>(p, cum_dev, cum_host, n_tiles, seed, x, xdt, ld, comp, tile0, row_lo, row_hi);
-            case 10: return mg_launch_gmm_sample_mfma_kk<10>(p, cum_dev, cum_host, n_tiles, seed, x, xdt, ld, comp, tile0, row_lo, row_hi);
-            case 12: return mg_launch_gmm_sample_mfma_kk<12>(p, cum_dev, cum_host, n_tiles, seed, x, xdt, ld, comp, tile0, row_lo, row_hi);
-            case 14: return mg_launch_gmm_sample_mfma_kk<14>(p, cum_dev, cum_host, n_tiles, seed, x, xdt, ld, comp, tile0, row_lo, row_hi);
-            case 16: return mg_launch_gmm_sample_mfma_kk<16>(p, cum_dev, cum_host, n_tiles, seed, x, xdt, ld, comp, tile0, row_lo, row_hi);
-            default: break;
-        }
+        const int rc = mg_dispatch_kk(p->KKg, 1, [&](auto KK) {
+            return mg_launch_gmm_sample_mfma_kk<KK>(p, cum_dev, cum_host, n_tiles, seed, x, xdt, ld, comp, tile0, row_lo, row_hi);
+        });
+        if (rc <= 0) return rc;   // a status; 1: no such k-step count -- the VALU kernel
     }
     return mg_launch_gmm_sample_valu(p, n, cum_dev, seed, x, xdt, ld, comp, row_lo, row_hi);
 }

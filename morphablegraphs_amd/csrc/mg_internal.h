@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/mg_hip.h"
+#include "mg_dispatch.h"
 
 #define MG_NCAND 16         // candidates per MFMA tile (N of v_mfma_f32_16x16x4_f32)
 #define MG_ROWTILE 16       // coefficient rows per MFMA tile (M)
@@ -229,7 +230,9 @@ struct mg_primitive {
     // device constants
     int32_t Dp = 0;              // row pitch of the padded coefficient rows (multiple of 4)
     int32_t cshift = 0;          // column of channel d in a padded row is d + cshift
-    float *d_Epack = nullptr;    // [RT][KK/2][64][2] MFMA A fragments, f32, padded rows r' = i*Dp + d
+    float *d_Epack = nullptr;    // [RT][KK/2][64][2] MFMA A fragments, f32, padded rows r' = i*Dp + d, k-steps in pairs per lane; RT*KK*64 floats
+                                 // on, the same fragments with the k-steps in quads per lane, [RT]{[KK/4][64][4], then [64][2] where KK % 4 == 2}
+                                 // (mg_pack_regroup, G = 4: the chunk-stationary kernel's one-time loads)
     float *d_Et32 = nullptr;     // [L][R] f32
     double *d_Et64 = nullptr;    // [L][R] f64
     double *d_Erpack = nullptr;  // [RRT][KK][64] f64 MFMA A fragments of the root rows (row = i*nroot + d)
@@ -240,12 +243,14 @@ struct mg_primitive {
     double *d_knots = nullptr;   // (NB + 4) f64: the spatial knot vector (basis rows computed on the device: mg_frames_at_kernel)
     int32_t RRT = 0;             // 16-row tiles of the root-row space
     // GMM device constants
-    double *d_gPpack = nullptr;  // [K][JT][KK][64]: v_mfma_f64_16x16x4_f64 B fragments of P_k (L <= 64)
+    double *d_gPpack = nullptr;  // [K][JT][KK][64]: v_mfma_f64_16x16x4_f64 B fragments of P_k (L <= 64); K*JT*KK*64 doubles on, the same fragments
+                                 // with the k-steps in pairs per lane, [K][JT][KK/2][64][2] (the fused step's staged tail, the planner step)
     double *d_gmPpad = nullptr;  // [K][JT*16]: mu_k . P_k, zero padded
     double *d_gP = nullptr;      // [K][L(j)][L(i)]: column j of P_k contiguous over i
     double *d_gmP = nullptr;     // [K][L]: mu_k . P_k
     double *d_gPTpack = nullptr; // [K][JT][KK][64]: B fragments of P_k^T (Jacobian)
-    double *d_gcholpack = nullptr; // [K][JT][KK][64]: B fragments of chol_k^T (sampler)
+    double *d_gcholpack = nullptr; // [K][JT][KK][64]: B fragments of chol_k^T (sampler); K*JT*KK*64 doubles on, the same in pairs per lane,
+                                   // [K][JT][KK/2][64][2] (the planner step's sampler)
     double *d_gmeanpad = nullptr;  // [K][JT*16]: means, zero padded
     double *d_gconst = nullptr;  // [K]: log w_k + sum log diag P_k - 0.5 L log 2pi
     double *d_gmean = nullptr;   // [K][L]

@@ -380,9 +380,13 @@ __global__ __launch_bounds__(256, MG_FUSED_WAVES_PER_SIMD) void mg_options_fused
     }
 }
 
+// f(kernel) for (latents float64, counts drawn on the device): the launch and the large-LDS opt-in both name the kernel here
+template <class F>
+static auto mg_options_with_kernel(bool x_f64, bool dev_counts, F f) {
+    return mg_dispatch_flags(x_f64, dev_counts, [&](auto X_F64, auto DYN_DEV) { return f(mg_options_fused_kernel<X_F64, DYN_DEV>); });
+}
 int mg_options_fused_attributes() {
-    MG_HIP_CHECK(mg_lds_opt_in(160 * 1024 - 1024, mg_options_fused_kernel<true, false>, mg_options_fused_kernel<false, false>, mg_options_fused_kernel<true, true>,
-                               mg_options_fused_kernel<false, true>));
+    for (int m = 0; m < 4; m++) MG_HIP_CHECK(mg_options_with_kernel(m & 1, m & 2, [](auto kernel) { return mg_lds_opt_in(160 * 1024 - 1024, kernel); }));
     return MG_OK;
 }
 
@@ -488,6 +492,7 @@ int mg_launch_options_fused(int32_t n_options, mg_primitive *const *prims, const
     const mg_fused_static *tabd = (const mg_fused_static *)dt.base();
     mg_fused_partial *part = (mg_fused_partial *)ctx->fused_partials;
     int32_t *ctr = (int32_t *)ctx->fused_counters;
+    mg_fused_devcounts *dd = nullptr, *dnext = nullptr;   // this step's counts and the next step's, where the device draws them
     if (dev_counts) {
         if (!ctx->fused_dyn_dev) MG_HIP_CHECK(hipMalloc(&ctx->fused_dyn_dev, 2 * sizeof(mg_fused_devcounts)));
         // were this step's counts drawn by the step before?
@@ -495,23 +500,16 @@ int mg_launch_options_fused(int32_t n_options, mg_primitive *const *prims, const
         bool hit = fn.valid && fn.n_options == n_options && fn.n == n && ctx->opt[MG_OPT_OPTIONS_STEP] != 2;
         for (int k = 0; k < n_options && hit; k++) hit = fn.seeds[k] == seeds[k] && fn.prims[k] == (const void *)prims[k];
         const int slot = hit ? fn.slot : 0;
-        mg_fused_devcounts *dd = (mg_fused_devcounts *)ctx->fused_dyn_dev + slot, *dnext = (mg_fused_devcounts *)ctx->fused_dyn_dev + (slot ^ 1);
+        dd = (mg_fused_devcounts *)ctx->fused_dyn_dev + slot;
+        dnext = (mg_fused_devcounts *)ctx->fused_dyn_dev + (slot ^ 1);
         if (!hit) hipLaunchKernelGGL(mg_options_counts_kernel, dim3(n_options), dim3(256), 0, ctx->stream, tabd, ca, dd);
         fn.valid = false; fn.n_options = n_options; fn.n = n; fn.slot = slot ^ 1;   // (valid once the launch below has been accepted)
         for (int k = 0; k < n_options; k++) { fn.seeds[k] = seeds[k] + 1; fn.prims[k] = (const void *)prims[k]; }
-        if (xdt == MG_F64)
-            hipExtLaunchKernelGGL((mg_options_fused_kernel<true, true>), dim3(total_wg), dim3(256), lds, ctx->stream, timed ? ev0 : nullptr, timed ? ev1 : nullptr, 0,
-                                  tabd, dyn, (const mg_fused_devcounts *)dd, dnext, counts_host, (int)n_options, wave_doubles, part, ctr);
-        else
-            hipExtLaunchKernelGGL((mg_options_fused_kernel<false, true>), dim3(total_wg), dim3(256), lds, ctx->stream, timed ? ev0 : nullptr, timed ? ev1 : nullptr, 0,
-                                  tabd, dyn, (const mg_fused_devcounts *)dd, dnext, counts_host, (int)n_options, wave_doubles, part, ctr);
-    } else if (xdt == MG_F64) {
-        hipExtLaunchKernelGGL((mg_options_fused_kernel<true, false>), dim3(total_wg), dim3(256), lds, ctx->stream, timed ? ev0 : nullptr, timed ? ev1 : nullptr, 0,
-                              tabd, dyn, (const mg_fused_devcounts *)nullptr, (mg_fused_devcounts *)nullptr, (int32_t *)nullptr, (int)n_options, wave_doubles, part, ctr);
-    } else {
-        hipExtLaunchKernelGGL((mg_options_fused_kernel<false, false>), dim3(total_wg), dim3(256), lds, ctx->stream, timed ? ev0 : nullptr, timed ? ev1 : nullptr, 0,
-                              tabd, dyn, (const mg_fused_devcounts *)nullptr, (mg_fused_devcounts *)nullptr, (int32_t *)nullptr, (int)n_options, wave_doubles, part, ctr);
     }
+    mg_options_with_kernel(xdt == MG_F64, dev_counts, [&](auto kernel) {
+        hipExtLaunchKernelGGL(kernel, dim3(total_wg), dim3(256), lds, ctx->stream, timed ? ev0 : nullptr, timed ? ev1 : nullptr, 0,
+                              tabd, dyn, (const mg_fused_devcounts *)dd, dnext, dev_counts ? counts_host : (int32_t *)nullptr, (int)n_options, wave_doubles, part, ctr);
+    });
     MG_HIP_CHECK(hipGetLastError());
     if (dev_counts) ctx->fused_next.valid = true;
     return MG_OK;

@@ -177,10 +177,9 @@ static int mg_launch_score_mfma_kk(mg_primitive *p, const mg_constraint_set *cs,
         if (lds <= 64 * 1024) {
             const int64_t grid = (a.B + 255) / 256;
             if (grid > 0x7fffffff) return MG_ERR_UNSUPPORTED;
-            if (lf && of) hipLaunchKernelGGL((mg_score_mfma64_kernel<KK, true, true>), dim3((int)grid), dim3(256), lds, st, a, cs->d_Wpack, cs->d_bpad, cs->RT);
-            else if (lf) hipLaunchKernelGGL((mg_score_mfma64_kernel<KK, true, false>), dim3((int)grid), dim3(256), lds, st, a, cs->d_Wpack, cs->d_bpad, cs->RT);
-            else if (of) hipLaunchKernelGGL((mg_score_mfma64_kernel<KK, false, true>), dim3((int)grid), dim3(256), lds, st, a, cs->d_Wpack, cs->d_bpad, cs->RT);
-            else hipLaunchKernelGGL((mg_score_mfma64_kernel<KK, false, false>), dim3((int)grid), dim3(256), lds, st, a, cs->d_Wpack, cs->d_bpad, cs->RT);
+            mg_dispatch_flags(lf, of, [&](auto LAT_F64, auto OUT_F64) {
+                hipLaunchKernelGGL((mg_score_mfma64_kernel<KK, LAT_F64, OUT_F64>), dim3((int)grid), dim3(256), lds, st, a, cs->d_Wpack, cs->d_bpad, cs->RT);
+            });
             MG_HIP_CHECK(hipGetLastError());
             return MG_OK;
         }
@@ -189,33 +188,21 @@ static int mg_launch_score_mfma_kk(mg_primitive *p, const mg_constraint_set *cs,
     if (lds > 150 * 1024) return MG_ERR_UNSUPPORTED;
     const int64_t grid = (a.B + 63) / 64;
     if (grid > 0x7fffffff) return MG_ERR_UNSUPPORTED;
-    if (lds > 64 * 1024) MG_HIP_CHECK(mg_lds_opt_in(160 * 1024, mg_score_mfma_kernel<KK, true, true>, mg_score_mfma_kernel<KK, true, false>, mg_score_mfma_kernel<KK, false, true>,
-                                                    mg_score_mfma_kernel<KK, false, false>));
-    if (lf && of) hipLaunchKernelGGL((mg_score_mfma_kernel<KK, true, true>), dim3((int)grid), dim3(256), lds, st, a, cs->d_Wpack, cs->d_bpad, cs->RT);
-    else if (lf) hipLaunchKernelGGL((mg_score_mfma_kernel<KK, true, false>), dim3((int)grid), dim3(256), lds, st, a, cs->d_Wpack, cs->d_bpad, cs->RT);
-    else if (of) hipLaunchKernelGGL((mg_score_mfma_kernel<KK, false, true>), dim3((int)grid), dim3(256), lds, st, a, cs->d_Wpack, cs->d_bpad, cs->RT);
-    else hipLaunchKernelGGL((mg_score_mfma_kernel<KK, false, false>), dim3((int)grid), dim3(256), lds, st, a, cs->d_Wpack, cs->d_bpad, cs->RT);
-    MG_HIP_CHECK(hipGetLastError());
-    return MG_OK;
+    return mg_dispatch_flags(lf, of, [&](auto LAT_F64, auto OUT_F64) -> int {
+        const auto kernel = mg_score_mfma_kernel<KK, LAT_F64, OUT_F64>;
+        if (lds > 64 * 1024) MG_HIP_CHECK(mg_lds_opt_in(160 * 1024, kernel));
+        hipLaunchKernelGGL(kernel, dim3((int)grid), dim3(256), lds, st, a, cs->d_Wpack, cs->d_bpad, cs->RT);
+        MG_HIP_CHECK(hipGetLastError());
+        return MG_OK;
+    });
 }
 
 int mg_launch_score(mg_primitive *p, const mg_constraint_set *cs, const void *lat, int ldt, int64_t B, int64_t ld, void *out, int odt, double *res, const double *align_cand) {
     mg_score_args a = mg_score_args_of(cs, p->L);
     a.res = res; a.align_cand = align_cand; a.lat = lat; a.out = out; a.B = B; a.ld = ld;
-    const bool lf0 = ldt == MG_F64, of0 = odt == MG_F64;
+    const bool lf = ldt == MG_F64, of = odt == MG_F64;
     if (cs->d_Wpack && !p->ctx->opt[MG_OPT_FORCE_VALU_SCORE]) {
-        int rc = MG_ERR_UNSUPPORTED;
-        switch (p->KK) {
-            case 2: rc = mg_launch_score_mfma_kk<2>(p, cs, a, lf0, of0); break;
-            case 4: rc = mg_launch_score_mfma_kk<4>(p, cs, a, lf0, of0); break;
-            case 6: rc = mg_launch_score_mfma_kk<6>(p, cs, a, lf0, of0); break;
-            case 8: rc = mg_launch_score_mfma_kk<8>(p, cs, a, lf0, of0); break;
-            case 10: rc = mg_launch_score_mfma_kk<10>(p, cs, a, lf0, of0); break;
-            case 12: rc = mg_launch_score_mfma_kk<12>(p, cs, a, lf0, of0); break;
-            case 14: rc = mg_launch_score_mfma_kk<14>(p, cs, a, lf0, of0); break;
-            case 16: rc = mg_launch_score_mfma_kk<16>(p, cs, a, lf0, of0); break;
-            default: break;
-        }
+        const int rc = mg_dispatch_kk(p->KK, (int)MG_ERR_UNSUPPORTED, [&](auto KK) { return mg_launch_score_mfma_kk<KK>(p, cs, a, lf, of); });
         if (rc != MG_ERR_UNSUPPORTED) return rc;
     }
     size_t lds = ((size_t)MG_SC_CANDS * (p->L + 1) + (size_t)std::max(cs->n, 1) * MG_SC_CANDS) * 8;
@@ -223,14 +210,13 @@ int mg_launch_score(mg_primitive *p, const mg_constraint_set *cs, const void *la
     int64_t grid = (B + MG_SC_CANDS - 1) / MG_SC_CANDS;
     if (grid > 0x7fffffff) { mg_set_error("mg_score_constraints: too many samples"); return MG_ERR_UNSUPPORTED; }
     hipStream_t st = p->ctx->stream;
-    const bool lf = ldt == MG_F64, of = odt == MG_F64;
-    if (lds > 64 * 1024) MG_HIP_CHECK(mg_lds_opt_in(160 * 1024, mg_score_kernel<true, true>, mg_score_kernel<true, false>, mg_score_kernel<false, true>, mg_score_kernel<false, false>));
-    if (lf && of) hipLaunchKernelGGL((mg_score_kernel<true, true>), dim3((int)grid), dim3(MG_SC_CANDS * MG_SC_WAVES), lds, st, a);
-    else if (lf) hipLaunchKernelGGL((mg_score_kernel<true, false>), dim3((int)grid), dim3(MG_SC_CANDS * MG_SC_WAVES), lds, st, a);
-    else if (of) hipLaunchKernelGGL((mg_score_kernel<false, true>), dim3((int)grid), dim3(MG_SC_CANDS * MG_SC_WAVES), lds, st, a);
-    else hipLaunchKernelGGL((mg_score_kernel<false, false>), dim3((int)grid), dim3(MG_SC_CANDS * MG_SC_WAVES), lds, st, a);
-    MG_HIP_CHECK(hipGetLastError());
-    return MG_OK;
+    return mg_dispatch_flags(lf, of, [&](auto LAT_F64, auto OUT_F64) -> int {
+        const auto kernel = mg_score_kernel<LAT_F64, OUT_F64>;
+        if (lds > 64 * 1024) MG_HIP_CHECK(mg_lds_opt_in(160 * 1024, kernel));
+        hipLaunchKernelGGL(kernel, dim3((int)grid), dim3(MG_SC_CANDS * MG_SC_WAVES), lds, st, a);
+        MG_HIP_CHECK(hipGetLastError());
+        return MG_OK;
+    });
 }
 
 // New constraint parameters for an existing set (mg_constraint_set_update): the values travel as kernel arguments,

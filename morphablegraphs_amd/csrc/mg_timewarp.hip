@@ -186,14 +186,10 @@ int mg_launch_frames_at(mg_primitive *p, const void *lat, int ldt, int64_t B, in
         return MG_ERR_UNSUPPORTED;
     }
     MG_HIP_CHECK(mg_tw_lds_opt_in(p->ctx));
-    const bool lf = ldt == MG_F64, of = odt == MG_F64;
-    hipStream_t st = p->ctx->stream;
-#define MG_FA_ARGS (const double *)p->d_Et64, (const double *)p->d_mean, (const double *)p->d_knots, lat, ld, (int)p->L, (int)p->R, (int)p->D, (int)p->NB, times, lens, t_cap, out
-    if (lf && of) hipLaunchKernelGGL((mg_frames_at_kernel<true, true>), dim3((unsigned)B), dim3(MG_FA_BLOCK), lds, st, MG_FA_ARGS);
-    else if (lf) hipLaunchKernelGGL((mg_frames_at_kernel<true, false>), dim3((unsigned)B), dim3(MG_FA_BLOCK), lds, st, MG_FA_ARGS);
-    else if (of) hipLaunchKernelGGL((mg_frames_at_kernel<false, true>), dim3((unsigned)B), dim3(MG_FA_BLOCK), lds, st, MG_FA_ARGS);
-    else hipLaunchKernelGGL((mg_frames_at_kernel<false, false>), dim3((unsigned)B), dim3(MG_FA_BLOCK), lds, st, MG_FA_ARGS);
-#undef MG_FA_ARGS
+    mg_dispatch_flags(ldt == MG_F64, odt == MG_F64, [&](auto LAT_F64, auto OUT_F64) {
+        hipLaunchKernelGGL((mg_frames_at_kernel<LAT_F64, OUT_F64>), dim3((unsigned)B), dim3(MG_FA_BLOCK), lds, p->ctx->stream, (const double *)p->d_Et64, (const double *)p->d_mean,
+                           (const double *)p->d_knots, lat, ld, (int)p->L, (int)p->R, (int)p->D, (int)p->NB, times, lens, t_cap, out);
+    });
     MG_HIP_CHECK(hipGetLastError());
     return MG_OK;
 }

@@ -585,6 +585,88 @@ def test_step_plan_names_the_kernel_float64_latents_run(ctx, L):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("L", [1, 8, 16, 24, 32, 40, 48, 56, 57, 64, 65])
+def test_instantiations_the_sweep_leaves_out(ctx, L):
+    """The (kernel, KK, flags) combinations the host dispatch can select and the table above does not launch, at the widest
+    width of every KK (and the narrowest of the first and the last), 17 candidates -- a full tile of 16 and a tail of one -- and
+    65 for the 64-candidate scorer: the fused step in BOTH frames kernels with both root modes and latent types (KK <= 10),
+    the scorers' float32 output, the Jacobian over float32 latents, the objective in one launch, and the MFMA sampler with
+    its prefix sums in device memory (more than 16 components); at L = 65 the VALU scorer and Jacobian in their place.  Each
+    against what its neighbours in the sweep compare with."""
+    KK = kk_of(L)
+    data = synthetic.make_primitive(seed=2000 + L, n_components=L, n_gmm=3, n_dim=79, name="inst%d" % L, **SHORT)
+    cp = c_oracle.COraclePrimitive(data)
+    rng = np.random.default_rng(L)
+    S = rng.standard_normal((65, L))
+    _reset(ctx)
+    if 0 < KK <= MG_FUSE_MAX_KK:
+        for mode in (1, 2):
+            ctx.set_option(_capi.MG_OPT_ROOT_MODE, mode)
+            prim = _capi.Primitive(ctx, data)
+            try:
+                for dtype in (np.float32, np.float64):
+                    X = S[:17].astype(dtype)
+                    model = cp.frames_f32model(X.astype(np.float64), root_split=mode == 2)
+                    lp_sep = prim.gmm_log_prob(X, dtype=np.float32)
+                    for kern, name in ((1, "mg_frames_ws_kernel"), (2, "mg_frames_cs_kernel")):
+                        ctx.set_option(_capi.MG_OPT_FRAMES_KERNEL, kern)
+                        plan = prim.step_plan(len(X), dtype=dtype)
+                        assert plan["fused"] and plan["kernel"] == name, (L, mode, kern, plan)
+                        frames, logp = _fused_step(ctx, prim, X, prim.n_canonical_frames, prim.n_dim)
+                        tag = "L %d mode %d %s kernel %d" % (L, mode, np.dtype(dtype).name, kern)
+                        np.testing.assert_array_equal(_bits(frames), _bits(model), err_msg=tag)
+                        np.testing.assert_array_equal(_bits(logp), _bits(lp_sep), err_msg=tag)
+                        np.testing.assert_allclose(logp, cp.log_prob_f64(X.astype(np.float64)), rtol=3e-7, atol=1e-6, err_msg=tag)
+                    ctx.set_option(_capi.MG_OPT_FRAMES_KERNEL, 0)
+            finally:
+                prim.close()
+        ctx.set_option(_capi.MG_OPT_ROOT_MODE, 0)
+    prim = _capi.Primitive(ctx, data)
+    tl = prim.n_canonical_frames - 1.0
+    root = [{"type": "position", "t": tl, "weight": 1.0, "target": [30.0, None, -40.0]},
+            {"type": "direction", "t": tl, "weight": 2.0, "target": [0.3, -1.0]}]
+    cset = _capi.ConstraintSet(prim, root)
+    try:
+        assert prim.kk == KK and prim.kk_gmm == KK
+        for dtype in (np.float32, np.float64):
+            # the scorers' float32 output is their float64 sum rounded once: MG_OPT_SCORE_KERNEL 1 (17 candidates), 2 (65), VALU
+            for opt, val, B in ((_capi.MG_OPT_SCORE_KERNEL, 1, 17), (_capi.MG_OPT_SCORE_KERNEL, 2, 65), (_capi.MG_OPT_FORCE_VALU_SCORE, 1, 17)):
+                ctx.set_option(opt, val)
+                X = S[:B].astype(dtype)
+                e64, e32 = prim.score_constraints(cset, X, dtype=np.float64), prim.score_constraints(cset, X, dtype=np.float32)
+                ctx.set_option(opt, 0)
+                assert e32.dtype == np.float32
+                np.testing.assert_array_equal(_bits(e32), _bits(e64.astype(np.float32)), err_msg="L %d option %d = %d" % (L, opt, val))
+            if KK == 0:
+                continue
+            # the objective in one launch: the two separate calls' bits (the sweep's comparison)
+            X = S[:17].astype(dtype)
+            obj, err, lp = prim.objective(cset, X, 0.75, 1.25)
+            err2, lp2 = prim.score_constraints(cset, X), prim.gmm_log_prob(X, dtype=np.float64)
+            np.testing.assert_array_equal(err.view(np.uint64), err2.view(np.uint64))
+            np.testing.assert_array_equal(lp.view(np.uint64), lp2.view(np.uint64))
+            np.testing.assert_array_equal(obj.view(np.uint64), (0.75 * err2 + (-lp2) * 1.25).view(np.uint64))
+        # the Jacobian over float32 latents: the oracle's at the same (rounded) rows
+        X32 = S[:17].astype(np.float32)
+        ref = orc.OraclePrimitive(data).log_likelihood_jac(X32.astype(np.float64))
+        np.testing.assert_allclose(prim.gmm_log_prob_jac(X32), ref, rtol=1e-8, atol=1e-9 * max(1.0, np.abs(ref).max()))
+    finally:
+        cset.close()
+        prim.close()
+    # 17 components: the sampler reads its prefix sums from device memory (MG_SAMPLE_ARG_K = 16)
+    many = synthetic.make_primitive(seed=3000 + L, n_components=L, n_gmm=17, n_dim=15, name="inst%d_K17" % L, **SHORT)
+    prim = _capi.Primitive(ctx, many)
+    ledger = set(LEDGER)
+    try:
+        _sampler_family(ctx, prim, many, dict(name=many["name"]), rng)
+    finally:
+        LEDGER.clear()
+        LEDGER.update(ledger)       # (the ledger is the sweep's: what ran here must not stand in for a shape of the table)
+        prim.close()
+        _reset(ctx)
+
+
+@pytest.mark.gpu
 def test_planner_step_across_widths(ctx):
     """The planner's one-launch step over options of five widths (KK 2, 8, 12, 14, 16) against the per-option chains, bit for
     bit; each option's winner is the first minimum of the oracle's errors on the candidates the step left on the device."""

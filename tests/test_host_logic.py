@@ -409,6 +409,17 @@ def test_operand_images_and_joint_chains_decode():
     assert done.returncode == 0, done.stdout.decode(errors="replace")
 
 
+def test_kernel_dispatch_reaches_every_instantiation_once():
+    """csrc/mg_dispatch.h states the k-step counts once and turns flags into tags; tests/native/dispatch_check.cpp sends every
+    count, the values around them and every flag combination through it.  A program of its own, built and run as pack_check
+    is: nothing is loaded into this process."""
+    import subprocess
+    native = os.path.join(ROOT, "tests", "native")
+    subprocess.check_call(["make", "-s", "-C", native, "dispatch_check"])
+    done = subprocess.run([os.path.join(native, "dispatch_check")], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=60)
+    assert done.returncode == 0, done.stdout.decode(errors="replace")
+
+
 def test_local_optimizer_spends_the_references_evaluation_budget():
     """HipLeastSquares hands MINPACK an analytic-looking Jacobian (the batched finite differences), so scipy runs lmder,
     whose maxfev counts residual calls only; the reference runs leastsq WITHOUT Dfun (least_squares.py:50-53), where the L

@@ -321,6 +321,9 @@ int mg_device_probe_placement(mg_context *ctx, void *buf_dev, int64_t bytes, dou
 int mg_device_placement_info(mg_context *ctx, const void *buf_dev, double *info4, double *tbps);
 int mg_memcpy_h2d(mg_context *ctx, void *dst_dev, const void *src, int64_t bytes);
 int mg_memcpy_d2h(mg_context *ctx, void *dst, const void *src_dev, int64_t bytes);
+/* rows x row_bytes from one device matrix into another, each with its own pitch in bytes (a column block of a row-major matrix);
+ * asynchronous on the context's stream */
+int mg_memcpy_d2d_rows(mg_context *ctx, void *dst_dev, int64_t dst_pitch, const void *src_dev, int64_t src_pitch, int64_t row_bytes, int64_t rows);
 int mg_memset(mg_context *ctx, void *dst_dev, int value, int64_t bytes);
 
 /* Kernel timing with HIP events on the context's stream.  enabled = n > 0 brackets every
@@ -481,6 +484,19 @@ int mg_trajectory_tables(const mg_trajectory *trajectory, double *poly_host, dou
 int mg_score_trajectory(mg_primitive *prim, const mg_trajectory *trajectory, const mg_time_grid *grid, const void *latents_dev,
                         int latent_dtype, int64_t n_samples, int64_t ld, double min_u, double weight, const mg_alignment_desc *alignment,
                         double *errors_dev, int accumulate, double *residuals_dev);
+/* The same scorer with EVERY candidate aligned to its own previous motion -- a step of a graph walk chained on the step before it
+ * (obj_global_error_sum and its residual-vector forms with a TrajectoryConstraint in a step's list): align_cand_dev (n_samples, 4)
+ * float64, the layout and meaning of mg_score_constraint_residuals_chained's -- per candidate the previous unit heading (x, z) and
+ * the previous root position (x, z), used as they are in place of the record's heading and position.  `alignment` is the template:
+ * a previous-frame record with the root as aligning node, of which the node and ref_dir are used.  MG_ERR_INVALID_ARGUMENT for a
+ * NULL or a start-pose record and for a NULL align_cand_dev with n_samples > 0, MG_ERR_UNSUPPORTED for another aligning joint;
+ * nothing is launched then.  n_samples == 0 returns MG_OK.  The plan, the kernel and the launch are those of mg_score_trajectory for
+ * the same shape (mg_trajectory_plan), the arithmetic is the same statement for statement: a batch whose candidates all carry the
+ * record mg_score_trajectory would normalise to itself gives that call's bits. */
+int mg_score_trajectory_chained(mg_primitive *prim, const mg_trajectory *trajectory, const mg_time_grid *grid, const void *latents_dev,
+                                int latent_dtype, int64_t n_samples, int64_t ld, double min_u, double weight,
+                                const mg_alignment_desc *alignment, const double *align_cand_dev, double *errors_dev, int accumulate,
+                                double *residuals_dev);
 /* n such scorers of the same batch size in ONE launch -- a planner step scores every option's candidates against the option's own
  * trajectory (reference graph_walk_planner.py:184-226 with a TrajectoryConstraint in every option's constraint list): 4096
  * candidates fill a quarter of the chip, sixteen launches in a row take sixteen times one, side by side they take four.  The
@@ -1115,6 +1131,13 @@ typedef struct {
 } mg_walk_score_step;
 int mg_score_walk_residuals(int32_t n_steps, const mg_walk_score_step *steps, const void *latents_dev, int latent_dtype, int64_t n_samples,
                             int64_t ld, double *residuals_dev, int64_t ld_res, double *errors_dev, double *exit_state_dev);
+/* The same launch, which also writes the exit values EVERY step hands on: step_exits_dev NULL (mg_score_walk_residuals, the same
+ * bits) or (n_samples, n_steps, 4) float64 -- row [i] is the state step i + 1 is aligned to, row [n_steps - 1] is exit_state_dev's.
+ * What a step's trajectory constraints are aligned to per candidate (mg_score_trajectory_chained on the same stream, behind this
+ * launch; a column block of it is gathered with mg_memcpy_d2d_rows). */
+int mg_score_walk_residuals_steps(int32_t n_steps, const mg_walk_score_step *steps, const void *latents_dev, int latent_dtype, int64_t n_samples,
+                                  int64_t ld, double *residuals_dev, int64_t ld_res, double *errors_dev, double *exit_state_dev,
+                                  double *step_exits_dev);
 
 /* The TIME objective of a graph walk in ONE launch (csrc/mg_walk_time.hip): obj_time_error_sum over TimeConstraints (reference
  * optimization/objective_functions.py:270-287, constraints/time_constraints.py:40-102) for n_samples rows of concatenated time latents,
@@ -1203,6 +1226,9 @@ int mg_score_walk_time_host(int32_t n_steps, const mg_walk_time_step *steps, con
 /* mg_score_walk_residuals with host arrays; `residuals` is read first, so columns no step owns keep their values */
 int mg_score_walk_residuals_host(int32_t n_steps, const mg_walk_score_step *steps, const void *latents, int latent_dtype, int64_t n_samples,
                                  int64_t ld, double *residuals, int64_t ld_res, double *errors, double *exit_state);
+/* mg_score_walk_residuals_steps with host arrays; step_exits NULL or (n_samples, n_steps, 4) */
+int mg_score_walk_residuals_steps_host(int32_t n_steps, const mg_walk_score_step *steps, const void *latents, int latent_dtype, int64_t n_samples,
+                                       int64_t ld, double *residuals, int64_t ld_res, double *errors, double *exit_state, double *step_exits);
 /* mg_walk_frames with latents, times, frames and transforms in host memory; `frames` is read first, so rows no step owns keep their values */
 int mg_walk_frames_host(int32_t n_steps, mg_primitive *const *prims, const int64_t *latent_offset, const void *latents, int latent_dtype,
                         int64_t n_walks, int64_t ld, const double *times, const int32_t *lengths, int32_t t_cap, const int64_t *frame_offset,

@@ -69,11 +69,11 @@ EXPORTED_SYMBOLS = [
     "mg_version", "mg_last_error", "mg_status_string",
     "mg_context_create", "mg_context_destroy", "mg_context_set_stream", "mg_context_set_reserved_cus", "mg_context_set_option", "mg_context_arena_begin", "mg_context_arena_end", "mg_context_arena_bytes", "mg_context_synchronize",
     "mg_dist_unique_id", "mg_dist_init", "mg_dist_all_gather", "mg_dist_finalize", "mg_dist_preflight", "mg_dist_info",
-    "mg_context_device_info", "mg_device_malloc", "mg_device_malloc_chunked", "mg_device_malloc_placed", "mg_device_probe_placement", "mg_device_placement_info", "mg_device_free", "mg_context_trim_outputs", "mg_context_output_bytes", "mg_memcpy_h2d", "mg_memcpy_d2h",
+    "mg_context_device_info", "mg_device_malloc", "mg_device_malloc_chunked", "mg_device_malloc_placed", "mg_device_probe_placement", "mg_device_placement_info", "mg_device_free", "mg_context_trim_outputs", "mg_context_output_bytes", "mg_memcpy_h2d", "mg_memcpy_d2h", "mg_memcpy_d2d_rows",
     "mg_memset", "mg_profile_enable", "mg_profile_reset", "mg_profile_get", "mg_profile_get_samples",
     "mg_primitive_create", "mg_primitive_destroy", "mg_primitive_info", "mg_primitive_info2", "mg_primitive_root_mode", "mg_primitive_get_precisions_cholesky",
     "mg_time_function_canonical", "mg_time_function_canonical_host", "mg_time_function_sample", "mg_time_function_sample_rows", "mg_back_project_frames_at",
-    "mg_trajectory_create", "mg_trajectory_create_typed", "mg_trajectory_spline_type", "mg_trajectory_tables", "mg_trajectory_destroy", "mg_score_trajectory", "mg_score_trajectories", "mg_score_trajectory_points", "mg_trajectory_closest_points", "mg_trajectory_plan", "mg_joint_positions",
+    "mg_trajectory_create", "mg_trajectory_create_typed", "mg_trajectory_spline_type", "mg_trajectory_tables", "mg_trajectory_destroy", "mg_score_trajectory", "mg_score_trajectory_chained", "mg_score_trajectories", "mg_score_trajectory_points", "mg_trajectory_closest_points", "mg_trajectory_plan", "mg_joint_positions",
     "mg_time_grid_create", "mg_time_grid_destroy", "mg_primitive_canonical_grid", "mg_time_grid_size",
     "mg_time_grid_get_tables",
     "mg_back_project_frames", "mg_back_project_frames_f64", "mg_back_project_coeffs", "mg_spline_evaluate",
@@ -92,7 +92,7 @@ EXPORTED_SYMBOLS = [
     "mg_keyframe_distances", "mg_segment_search",
     "mg_align_motions_spatially", "mg_prepare_aligned_frames",
     "mg_walk_frames", "mg_walk_frames_host",
-    "mg_score_walk_residuals", "mg_score_walk_residuals_host",
+    "mg_score_walk_residuals", "mg_score_walk_residuals_host", "mg_score_walk_residuals_steps", "mg_score_walk_residuals_steps_host",
     "mg_score_walk_time", "mg_score_walk_time_host", "mg_walk_time_table_uploads", "mg_context_table_uploads",
     "mg_step_lengths", "mg_step_lengths_host",
 ]
@@ -297,6 +297,7 @@ def load_library(path=None):
         "mg_device_free": [vp, vp],
         "mg_memcpy_h2d": [vp, vp, vp, i64],
         "mg_memcpy_d2h": [vp, vp, vp, i64],
+        "mg_memcpy_d2d_rows": [vp, vp, i64, vp, i64, i64, i64],
         "mg_memset": [vp, vp, i32, i64],
         "mg_profile_enable": [vp, i32],
         "mg_profile_reset": [vp],
@@ -313,6 +314,7 @@ def load_library(path=None):
         "mg_trajectory_tables": [vp, vp, vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(dbl)],
         "mg_joint_positions": [vp, vp, vp, i32, vp, i64, i32, vp],
         "mg_score_trajectory": [vp, vp, vp, vp, i32, i64, i64, dbl, dbl, vp, vp, i32, vp],
+        "mg_score_trajectory_chained": [vp, vp, vp, vp, i32, i64, i64, dbl, dbl, vp, vp, vp, i32, vp],
         "mg_score_trajectories": [i32, vp, vp, vp, i32, i64, vp, vp, vp, vp, vp, i32],
         "mg_score_trajectory_points": [vp, vp, vp, i64, i32, dbl, dbl, vp, i32, vp],
         "mg_trajectory_closest_points": [vp, vp, vp, i64, i32, dbl, vp, vp, vp],
@@ -393,6 +395,8 @@ def load_library(path=None):
         "mg_walk_frames_host": [i32, vp, vp, vp, i32, i64, i64, vp, vp, i32, vp, vp, vp, vp, i64, vp],
         "mg_score_walk_residuals": [i32, vp, vp, i32, i64, i64, vp, i64, vp, vp],
         "mg_score_walk_residuals_host": [i32, vp, vp, i32, i64, i64, vp, i64, vp, vp],
+        "mg_score_walk_residuals_steps": [i32, vp, vp, i32, i64, i64, vp, i64, vp, vp, vp],
+        "mg_score_walk_residuals_steps_host": [i32, vp, vp, i32, i64, i64, vp, i64, vp, vp, vp],
         "mg_score_walk_time": [i32, vp, vp, i32, i64, i64, i32, vp, dbl, dbl, dbl, dbl, vp, vp, vp],
         "mg_score_walk_time_host": [i32, vp, vp, i32, i64, i64, i32, vp, dbl, dbl, dbl, dbl, vp, vp, vp],
         "mg_walk_time_table_uploads": [vp, C.POINTER(i64)],
@@ -517,6 +521,11 @@ class Context(object):
     def upload_into(self, buf, arr):
         arr = np.ascontiguousarray(arr)
         _check(self.lib.mg_memcpy_h2d(self.handle, _dev_ptr(buf), arr.ctypes.data_as(C.c_void_p), arr.nbytes))
+
+    def copy_rows_dev(self, dst_dev, dst_pitch, src_dev, src_pitch, row_bytes, rows):
+        """mg_memcpy_d2d_rows: `rows` rows of row_bytes bytes between device matrices of their own pitches (bytes), asynchronous on
+        the context's stream."""
+        _check(self.lib.mg_memcpy_d2d_rows(self.handle, _dev_ptr(dst_dev), int(dst_pitch), _dev_ptr(src_dev), int(src_pitch), int(row_bytes), int(rows)))
 
     def dist_finalize(self):
         _check(self.lib.mg_dist_finalize(self.handle))
@@ -980,24 +989,35 @@ class WalkScoreTable(object):
     def sets(self):
         return [cs for st in self.steps for cs in st[1:3] if cs is not None]
 
-    def score_dev(self, lat_dev, lat_dtype, n, ld, residuals_dev=None, ld_res=0, errors_dev=None, exit_state_dev=None):
-        """mg_score_walk_residuals on device buffers: asynchronous on the context's stream."""
+    def score_dev(self, lat_dev, lat_dtype, n, ld, residuals_dev=None, ld_res=0, errors_dev=None, exit_state_dev=None, step_exits_dev=None):
+        """mg_score_walk_residuals on device buffers: asynchronous on the context's stream.  step_exits_dev: (n, n_steps, 4) float64
+        for the exit values of every step (mg_score_walk_residuals_steps)."""
         code = MG_F64 if np.dtype(lat_dtype) == np.float64 else MG_F32
         ptr = lambda b: _dev_ptr(b) if b is not None else None
-        _check(self.lib.mg_score_walk_residuals(self.n_steps, C.cast(self.array, C.c_void_p), ptr(lat_dev), code, int(n), int(ld), ptr(residuals_dev),
-                                                int(ld_res), ptr(errors_dev), ptr(exit_state_dev)))
+        if step_exits_dev is None:
+            _check(self.lib.mg_score_walk_residuals(self.n_steps, C.cast(self.array, C.c_void_p), ptr(lat_dev), code, int(n), int(ld), ptr(residuals_dev),
+                                                    int(ld_res), ptr(errors_dev), ptr(exit_state_dev)))
+        else:
+            _check(self.lib.mg_score_walk_residuals_steps(self.n_steps, C.cast(self.array, C.c_void_p), ptr(lat_dev), code, int(n), int(ld),
+                                                          ptr(residuals_dev), int(ld_res), ptr(errors_dev), ptr(exit_state_dev), ptr(step_exits_dev)))
 
-    def score(self, S, ld_res, residuals=True, errors=True, exit_state=True, fill=0.0):
+    def score(self, S, ld_res, residuals=True, errors=True, exit_state=True, fill=0.0, step_exits=False):
         """(residuals (n, ld_res) or None, errors (n) or None, exit state (n, 4) or None) for host latents S
-        (mg_score_walk_residuals_host); columns no step owns hold `fill`."""
+        (mg_score_walk_residuals_host); columns no step owns hold `fill`.  step_exits=True: a fourth member, the exit values of
+        every step (n, n_steps, 4) (mg_score_walk_residuals_steps_host)."""
         S = _latents(S)
         n = S.shape[0]
         res = np.full((n, int(ld_res)), fill, dtype=np.float64) if residuals else None
         err = np.empty(n, dtype=np.float64) if errors else None
         ex = np.empty((n, 4), dtype=np.float64) if exit_state else None
-        _check(self.lib.mg_score_walk_residuals_host(self.n_steps, C.cast(self.array, C.c_void_p), S.ctypes.data_as(C.c_void_p), _dtype_code(S), n,
-                                                     S.shape[1], _host_ptr(res), int(ld_res), _host_ptr(err), _host_ptr(ex)))
-        return res, err, ex
+        if not step_exits:
+            _check(self.lib.mg_score_walk_residuals_host(self.n_steps, C.cast(self.array, C.c_void_p), S.ctypes.data_as(C.c_void_p), _dtype_code(S), n,
+                                                         S.shape[1], _host_ptr(res), int(ld_res), _host_ptr(err), _host_ptr(ex)))
+            return res, err, ex
+        st = np.empty((n, self.n_steps, 4), dtype=np.float64)
+        _check(self.lib.mg_score_walk_residuals_steps_host(self.n_steps, C.cast(self.array, C.c_void_p), S.ctypes.data_as(C.c_void_p), _dtype_code(S), n,
+                                                           S.shape[1], _host_ptr(res), int(ld_res), _host_ptr(err), _host_ptr(ex), _host_ptr(st)))
+        return res, err, ex, st
 
 
 class WalkTimeStep(C.Structure):   # struct mg_walk_time_step
@@ -1516,6 +1536,35 @@ class Primitive(object):
         _check(self.lib.mg_score_trajectory(self.handle, trajectory.handle, self._grid_handle(grid), _dev_ptr(lat_dev), code, int(n), int(ld),
                                             float(min_u), float(weight), C.byref(al) if al is not None else None, _dev_ptr(errors_dev),
                                             1 if accumulate else 0, _dev_ptr(residuals_dev) if residuals_dev is not None else None))
+
+    def score_trajectory_chained_dev(self, trajectory, lat_dev, lat_dtype, n, ld, align_cand_dev, template, errors_dev, min_u=0.0, weight=1.0,
+                                     accumulate=False, residuals_dev=None, grid=None):
+        """mg_score_trajectory_chained on device buffers: align_cand_dev (n, 4) float64, every candidate's previous unit heading (x, z)
+        and root position (x, z); template: the previous-frame record whose node and ref_dir are used."""
+        al = ConstraintSet._marshal_alignment(template, None) if template is not None else None
+        code = MG_F64 if np.dtype(lat_dtype) == np.float64 else MG_F32
+        _check(self.lib.mg_score_trajectory_chained(self.handle, trajectory.handle, self._grid_handle(grid), _dev_ptr(lat_dev), code, int(n), int(ld),
+                                                    float(min_u), float(weight), C.byref(al) if al is not None else None,
+                                                    _dev_ptr(align_cand_dev) if align_cand_dev is not None else None, _dev_ptr(errors_dev),
+                                                    1 if accumulate else 0, _dev_ptr(residuals_dev) if residuals_dev is not None else None))
+
+    def score_trajectory_chained(self, trajectory, S, align_cand, template, min_u=0.0, weight=1.0, residuals=False, grid=None):
+        """score_trajectory with every sample aligned to ITS OWN previous motion: align_cand (n, 4) as in
+        score_constraint_residuals_chained."""
+        S = _latents(S)
+        A = np.ascontiguousarray(align_cand, dtype=np.float64)
+        assert A.shape == (S.shape[0], 4)
+        n, T = S.shape[0], self._grid_size(grid)
+        d_S, d_A, d_e = self.ctx.upload(S), self.ctx.upload(A), self.ctx.malloc(max(n, 1) * 8)
+        d_r = self.ctx.malloc(max(n * T, 1) * 8) if residuals else None
+        try:
+            self.score_trajectory_chained_dev(trajectory, d_S, S.dtype, n, S.shape[1], d_A, template, d_e, min_u, weight, False, d_r, grid)
+            err = self.ctx.download(d_e, (n,), np.float64)
+            return (err, self.ctx.download(d_r, (n, T), np.float64)) if residuals else err
+        finally:
+            for b in (d_S, d_A, d_e, d_r):
+                if b is not None:
+                    b.free()
 
     @staticmethod
     def score_trajectories_dev(prims, trajectories, lat_devs, lat_dtype, n, lds, err_devs, min_us, weights, alignments=None, accumulate=False):

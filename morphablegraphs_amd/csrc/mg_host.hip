@@ -462,6 +462,14 @@ extern "C" int mg_memcpy_d2h(mg_context *ctx, void *dst, const void *src, int64_
     MG_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     return MG_OK;
 }
+// `rows` rows of row_bytes bytes from one device matrix to another, each with its own pitch; asynchronous on the context's stream
+extern "C" int mg_memcpy_d2d_rows(mg_context *ctx, void *dst, int64_t dst_pitch, const void *src, int64_t src_pitch, int64_t row_bytes, int64_t rows) {
+    MG_REQUIRE(ctx && row_bytes >= 0 && rows >= 0 && dst_pitch >= row_bytes && src_pitch >= row_bytes && (row_bytes == 0 || rows == 0 || (dst && src)),
+               "mg_memcpy_d2d_rows: bad arguments");
+    if (row_bytes == 0 || rows == 0) return MG_OK;
+    MG_HIP_CHECK(hipMemcpy2DAsync(dst, (size_t)dst_pitch, src, (size_t)src_pitch, (size_t)row_bytes, (size_t)rows, hipMemcpyDeviceToDevice, ctx->stream));
+    return MG_OK;
+}
 extern "C" int mg_memset(mg_context *ctx, void *dst, int value, int64_t bytes) {
     MG_REQUIRE(ctx && (bytes == 0 || dst) && bytes >= 0, "mg_memset: bad arguments");
     if (bytes == 0) return MG_OK;

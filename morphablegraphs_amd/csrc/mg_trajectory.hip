@@ -36,6 +36,8 @@ struct mg_traj_args {
     int32_t T, L, NB, n_seg, G, lat_f64, accumulate, align_mode;   // align_mode 0: none, 1: previous frame (root node), 2: start pose
     double min_u, weight;
     double al[7];   // heading (x, z) or (cos, sin); landing (x, z); ref_dir (3) or height
+    const double *al_cand;  // NULL, or (B, 4): the previous unit heading (x, z) and root position (x, z) of EVERY candidate, in place of
+                            // al[0..3] (align_mode 1 only; mg_score_trajectory_chained: the layout of mg_score_args::align_cand)
     const double *points;   // NULL, or (B, T, 3): the positions to follow the trajectory with, given instead of derived from the
                             // candidates' root rows (any joint's track from mg_joint_positions; already aligned by the caller)
     double *res_u;          // NULL, or (B, T): the parameter the search settles on in every frame (mg_trajectory_closest_points)
@@ -50,16 +52,23 @@ struct mg_traj_args {
 // The candidate's aligning transform (mg_candidate_alignment's for the root node): rotation about y and an xz translation, from the
 // first control point's rows -- root(r) yields row r of the candidate's root coefficient rows (NB x 3 positions, then the first control
 // point's quaternion).  The root's chain is its one quaternion: normalised and used as it is (multiplying it into the identity, the
-// general chain's first step, can flip the sign of a zero component).
+// general chain's first step, can flip the sign of a zero component).  cand: the candidate's index in the batch, clamped to it by the
+// caller (a lane past the batch reads the last candidate's record and writes nothing) -- where every candidate has its own previous
+// heading and position (al_cand) they are read from its row, used as they are; the reference vector stays the record's.
 template <typename RootFn>
-__device__ __forceinline__ mg_align2d mg_traj_alignment(const mg_traj_args &a, RootFn root) {
+__device__ __forceinline__ mg_align2d mg_traj_alignment(const mg_traj_args &a, const int64_t cand, RootFn root) {
     if (a.align_mode == 0) return {1.0, 0.0, 0.0, 0.0, 0.0};
     const double p0x = root(0), p0z = root(2);   // (formed once: root() may be a whole fma chain)
     if (a.align_mode == 2) return mg_align2d_onto(a.al[0], a.al[1], a.al[2], a.al[3], p0x, p0z, a.al[4]);
     double q[4] = {root(a.NB * 3 + 0), root(a.NB * 3 + 1), root(a.NB * 3 + 2), root(a.NB * 3 + 3)}, bx, bz;
     mg_quat_normalise(q[0], q[1], q[2], q[3]);
     mg_heading_xz(q, a.al[4], a.al[5], a.al[6], bx, bz);
-    return mg_align2d_from(a.al[0], a.al[1], bx, bz, a.al[2], a.al[3], p0x, p0z);
+    double hx = a.al[0], hz = a.al[1], px = a.al[2], pz = a.al[3];
+    if (a.al_cand) {                                   // (uniform: a kernel argument)
+        const double *prev = a.al_cand + 4 * cand;
+        hx = prev[0]; hz = prev[1]; px = prev[2]; pz = prev[3];
+    }
+    return mg_align2d_from(hx, hz, bx, bz, px, pz, p0x, p0z);
 }
 
 // POLY_LDS: the target spline's segment polynomials (12 n_seg + 3 doubles) are copied behind the rows and searched from there -- the walk
@@ -86,7 +95,7 @@ __global__ __launch_bounds__(MG_TRAJ_BLOCK) void mg_trajectory_kernel(mg_traj_ar
         for (int r = 0; r < rows; r++)
             lc[r * MG_TRAJ_BLOCK + tid] = mg_control_point(a.mean[r], a.E + (size_t)r * a.L, 1, a.L, [&](int k) { return ls[k * MG_TRAJ_BLOCK + tid]; });
     }
-    const mg_align2d t = mg_traj_alignment(a, [&](int r) { return lc[r * MG_TRAJ_BLOCK + tid]; });
+    const mg_align2d t = mg_traj_alignment(a, bb, [&](int r) { return lc[r * MG_TRAJ_BLOCK + tid]; });
     const int G = a.G;
     const double invG = 1.0 / (double)G;
     double min_u = a.min_u, sum = 0.0;
@@ -160,7 +169,7 @@ __device__ __forceinline__ void mg_trajectory_coop_body(const mg_traj_args &a, c
         for (int r = sub; r < rows; r += MG_TRAJ_W) lc[r] = mg_control_point(a.mean[r], a.E + (size_t)r * a.L, 1, a.L, [&](int k) { return ls[k]; });
     }
     __syncthreads();
-    const mg_align2d t = mg_traj_alignment(a, [&](int r) { return lc[r]; });
+    const mg_align2d t = mg_traj_alignment(a, bb, [&](int r) { return lc[r]; });   // (bb: the group's candidate, the same in its MG_TRAJ_W lanes)
     const int G = a.G;
     const double invG = 1.0 / (double)G;
     double min_u = a.min_u, sum = 0.0;
@@ -213,7 +222,7 @@ __device__ __forceinline__ void mg_trajectory_stream_body(const mg_traj_args &a,
         ls[k * MG_TRAJ_BLOCK + tid] = mg_load_lat(a.lat, a.lat_f64 != 0, bb * a.ld + k);
     __syncthreads();
     auto row = [&](int r) { return mg_control_point(a.mean[r], a.E + (size_t)r * a.L, 1, a.L, [&](int k) { return ls[k * MG_TRAJ_BLOCK + tid]; }); };
-    const mg_align2d t = mg_traj_alignment(a, row);
+    const mg_align2d t = mg_traj_alignment(a, bb, row);
     const int G = a.G;
     const double invG = 1.0 / (double)G;
     double min_u = a.min_u, sum = 0.0;
@@ -611,7 +620,7 @@ static int mg_traj_fill_args(const char *who, mg_primitive *p, const mg_trajecto
     a.B = B; a.ld = ld; a.T = g->T; a.L = p->L; a.NB = p->NB; a.n_seg = t->n_seg; a.G = t->granularity; a.lat_f64 = dt == MG_F64 ? 1 : 0;
     a.accumulate = accumulate ? 1 : 0; a.min_u = min_u; a.weight = weight; a.points = nullptr; a.res_u = nullptr; a.res_n = nullptr; a.paths = nullptr;
     a.search = p->ctx->opt[MG_OPT_TRAJECTORY_SEARCH] == 1 ? 1 : 0;
-    a.align_mode = 0;
+    a.align_mode = 0; a.al_cand = nullptr;
     for (double &v : a.al) v = 0.0;
     if (al) {
         const double hn = std::sqrt(al->heading[0] * al->heading[0] + al->heading[1] * al->heading[1]);
@@ -646,12 +655,14 @@ static void mg_traj_launch(mg_context *ctx, const mg_traj_plan_t &pl, const mg_t
     }
 }
 
-extern "C" int mg_score_trajectory(mg_primitive *p, const mg_trajectory *t, const mg_time_grid *g, const void *lat, int dt, int64_t B,
-                                   int64_t ld, double min_u, double weight, const mg_alignment_desc *al, double *errors_dev,
-                                   int accumulate, double *residuals_dev) {
+// one scorer's launch, for the two entry points below: al_cand NULL (the record's values for every candidate) or (B, 4)
+static int mg_traj_score_one(const char *who, mg_primitive *p, const mg_trajectory *t, const mg_time_grid *g, const void *lat, int dt, int64_t B, int64_t ld,
+                             double min_u, double weight, const mg_alignment_desc *al, const double *al_cand, double *errors_dev, int accumulate,
+                             double *residuals_dev) {
     mg_traj_args a;
-    { const int rc = mg_traj_fill_args("mg_score_trajectory", p, t, g, lat, dt, B, ld, min_u, weight, al, errors_dev, accumulate, residuals_dev, &a); if (rc != MG_OK) return rc; }
+    { const int rc = mg_traj_fill_args(who, p, t, g, lat, dt, B, ld, min_u, weight, al, errors_dev, accumulate, residuals_dev, &a); if (rc != MG_OK) return rc; }
     if (B == 0) return MG_OK;
+    a.al_cand = al_cand;
     MG_HIP_CHECK(hipSetDevice(p->ctx->device));
     mg_traj_plan_t pl;
     { const int rc = mg_traj_plan(p->ctx, p->L, t->rows, t->n_seg, B, B, false, a.search, &pl); if (rc != MG_OK) return rc; }
@@ -662,6 +673,28 @@ extern "C" int mg_score_trajectory(mg_primitive *p, const mg_trajectory *t, cons
     mg_prof_end(p->ctx, MG_PROF_TRAJECTORY);
     MG_HIP_CHECK(hipGetLastError());
     return MG_OK;
+}
+
+extern "C" int mg_score_trajectory(mg_primitive *p, const mg_trajectory *t, const mg_time_grid *g, const void *lat, int dt, int64_t B,
+                                   int64_t ld, double min_u, double weight, const mg_alignment_desc *al, double *errors_dev,
+                                   int accumulate, double *residuals_dev) {
+    return mg_traj_score_one("mg_score_trajectory", p, t, g, lat, dt, B, ld, min_u, weight, al, nullptr, errors_dev, accumulate, residuals_dev);
+}
+
+// The same scorer with EVERY candidate aligned to its own previous motion (a step of a graph walk chained on the step before it):
+// align_cand_dev (B, 4) = previous unit heading (x, z) and previous root position (x, z) per candidate, used as they are in place of
+// the record's; the record states the aligning node (the root) and the reference vector.  The plan, the kernel and the launch are
+// mg_score_trajectory's for the same shape.
+extern "C" int mg_score_trajectory_chained(mg_primitive *p, const mg_trajectory *t, const mg_time_grid *g, const void *lat, int dt, int64_t B,
+                                           int64_t ld, double min_u, double weight, const mg_alignment_desc *al, const double *align_cand_dev,
+                                           double *errors_dev, int accumulate, double *residuals_dev) {
+    if (!al) { mg_set_error("mg_score_trajectory_chained: NULL alignment record (its node and reference vector; the values are per candidate)"); return MG_ERR_INVALID_ARGUMENT; }
+    if (al->joint == MG_ALIGN_START_POSE) {
+        mg_set_error("mg_score_trajectory_chained: the record must be a previous-frame alignment, not a start pose");
+        return MG_ERR_INVALID_ARGUMENT;
+    }
+    if (B > 0 && !align_cand_dev) { mg_set_error("mg_score_trajectory_chained: NULL pointer"); return MG_ERR_INVALID_ARGUMENT; }
+    return mg_traj_score_one("mg_score_trajectory_chained", p, t, g, lat, dt, B, ld, min_u, weight, al, align_cand_dev, errors_dev, accumulate, residuals_dev);
 }
 
 // n scorers of the same batch size side by side in one launch (canonical grids, no residual vectors): option k's candidates
@@ -746,7 +779,7 @@ static int mg_traj_points_launch(const char *who, mg_primitive *p, const mg_traj
     a.B = B; a.ld = 0; a.T = T; a.L = p->L; a.NB = p->NB; a.n_seg = t->n_seg; a.G = t->granularity; a.lat_f64 = 1;
     a.accumulate = accumulate ? 1 : 0; a.min_u = min_u; a.weight = weight; a.points = points_dev; a.res_u = params_dev; a.res_n = evals_dev; a.paths = nullptr;
     a.search = p->ctx->opt[MG_OPT_TRAJECTORY_SEARCH] == 1 ? 1 : 0;
-    a.align_mode = 0;
+    a.align_mode = 0; a.al_cand = nullptr;
     for (double &v : a.al) v = 0.0;
     mg_traj_plan_t pl;
     { const int rc = mg_traj_plan(p->ctx, p->L, t->rows, t->n_seg, B, B, true, a.search, &pl); if (rc != MG_OK) return rc; }

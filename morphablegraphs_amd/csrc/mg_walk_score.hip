@@ -48,6 +48,7 @@ struct mg_wscore_args {
     const mg_wscore_step *steps;
     const void *lat;
     double *res, *err, *exit_state;
+    double *step_exits;          // NULL, or (B, n_steps, 4): the state every step hands on (mg_score_walk_residuals_steps)
     int64_t B, ld, ld_res;
     int32_t n_steps;
     int32_t vs;                  // doubles per candidate in the channel slab (16 x the most row tiles of a set, + 1)
@@ -145,6 +146,8 @@ __global__ __launch_bounds__(256) void mg_walk_score_kernel(const mg_wscore_args
             if (ws->carries_exit) state[cl * 4 + g] = resid[(a.n - 4 + g) * 16 + cl];   // every residual that read the old state is in `resid`
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         }
+        // the state the wave is about to hand on (a lane reads back the value it wrote itself)
+        if (k.step_exits && cl < ncand) k.step_exits[((b0 + cl) * k.n_steps + i) * 4 + g] = state[cl * 4 + g];
     }
     if (k.err && lane < ncand) k.err[b0 + lane] = err;
     if (k.exit_state && cl < ncand) k.exit_state[(b0 + cl) * 4 + g] = state[cl * 4 + g];
@@ -160,8 +163,9 @@ static bool mg_wscore_ends_with_exits(const mg_constraint_set *cs) {
            c[3].type == MG_CONSTRAINT_VALUE_POSITION;
 }
 
-extern "C" int mg_score_walk_residuals(int32_t n_steps, const mg_walk_score_step *steps, const void *latents_dev, int latent_dtype, int64_t n_samples,
-                                       int64_t ld, double *residuals_dev, int64_t ld_res, double *errors_dev, double *exit_state_dev) {
+extern "C" int mg_score_walk_residuals_steps(int32_t n_steps, const mg_walk_score_step *steps, const void *latents_dev, int latent_dtype, int64_t n_samples,
+                                             int64_t ld, double *residuals_dev, int64_t ld_res, double *errors_dev, double *exit_state_dev,
+                                             double *step_exits_dev) {
     MG_WSCORE_REQUIRE(n_steps >= 1 && n_steps <= MG_WALK_MAX_STEPS, "mg_score_walk_residuals: %d steps (1 .. %d per call)", n_steps, MG_WALK_MAX_STEPS);
     MG_WSCORE_REQUIRE(steps && steps[0].prim, "mg_score_walk_residuals: NULL pointer");
     MG_WSCORE_REQUIRE((latent_dtype == MG_F32 || latent_dtype == MG_F64) && n_samples >= 0 && ld >= 1 && ld_res >= 0, "mg_score_walk_residuals: bad arguments");
@@ -236,14 +240,14 @@ extern "C" int mg_score_walk_residuals(int32_t n_steps, const mg_walk_score_step
     const int64_t grid = (n_samples + 63) / 64;
     MG_REQUIRE_AS(grid <= 0x7fffffff, MG_ERR_UNSUPPORTED, "mg_score_walk_residuals: too many samples");
     if (n_samples == 0) return MG_OK;
-    MG_WSCORE_REQUIRE(latents_dev && (residuals_dev || errors_dev || exit_state_dev), "mg_score_walk_residuals: NULL pointer");
+    MG_WSCORE_REQUIRE(latents_dev && (residuals_dev || errors_dev || exit_state_dev || step_exits_dev), "mg_score_walk_residuals: NULL pointer");
     MG_HIP_CHECK(hipSetDevice(ctx->device));
     mg_device_table &dt = ctx->tab[MG_TABLE_WALK_SCORE];
     int rc = dt.upload(ctx, "mg_score_walk_residuals", tab.data(), tab.size(), (size_t)MG_WALK_MAX_STEPS * sizeof(mg_wscore_step));   // one allocation per context
     if (rc != MG_OK) return rc;
     mg_wscore_args k = {};
     k.steps = (const mg_wscore_step *)dt.base();
-    k.lat = latents_dev; k.res = residuals_dev; k.err = errors_dev; k.exit_state = exit_state_dev;
+    k.lat = latents_dev; k.res = residuals_dev; k.err = errors_dev; k.exit_state = exit_state_dev; k.step_exits = step_exits_dev;
     k.B = n_samples; k.ld = ld; k.ld_res = ld_res;
     k.n_steps = n_steps; k.vs = vs; k.nmax = nmax; k.xs = xs;
     if (lds > 64 * 1024) MG_HIP_CHECK(mg_lds_opt_in_once(ctx, MG_LDS_WALK_SCORE, 160 * 1024, mg_walk_score_kernel<true>, mg_walk_score_kernel<false>));
@@ -255,30 +259,42 @@ extern "C" int mg_score_walk_residuals(int32_t n_steps, const mg_walk_score_step
     return MG_OK;
 }
 
+extern "C" int mg_score_walk_residuals(int32_t n_steps, const mg_walk_score_step *steps, const void *latents_dev, int latent_dtype, int64_t n_samples,
+                                       int64_t ld, double *residuals_dev, int64_t ld_res, double *errors_dev, double *exit_state_dev) {
+    return mg_score_walk_residuals_steps(n_steps, steps, latents_dev, latent_dtype, n_samples, ld, residuals_dev, ld_res, errors_dev, exit_state_dev, nullptr);
+}
+
 // host arrays in, host arrays out: one device block for the call, synchronises.  `residuals` is read first, so columns no step
 // owns keep their values.
-extern "C" int mg_score_walk_residuals_host(int32_t n_steps, const mg_walk_score_step *steps, const void *latents, int latent_dtype, int64_t n_samples, int64_t ld,
-                                            double *residuals, int64_t ld_res, double *errors, double *exit_state) {
+extern "C" int mg_score_walk_residuals_steps_host(int32_t n_steps, const mg_walk_score_step *steps, const void *latents, int latent_dtype, int64_t n_samples,
+                                                  int64_t ld, double *residuals, int64_t ld_res, double *errors, double *exit_state, double *step_exits) {
     MG_WSCORE_REQUIRE(n_steps >= 1 && steps && steps[0].prim && n_samples >= 0 && ld >= 1 && ld_res >= 0 && (latent_dtype == MG_F32 || latent_dtype == MG_F64),
                       "mg_score_walk_residuals_host: bad arguments");
-    MG_WSCORE_REQUIRE(n_samples == 0 || (latents && (residuals || errors || exit_state)), "mg_score_walk_residuals_host: NULL pointer");
+    MG_WSCORE_REQUIRE(n_samples == 0 || (latents && (residuals || errors || exit_state || step_exits)), "mg_score_walk_residuals_host: NULL pointer");
     mg_context *ctx = steps[0].prim->ctx;
     const size_t lat_b = (size_t)(n_samples * ld) * (latent_dtype == MG_F64 ? 8 : 4), res_b = residuals ? (size_t)(n_samples * ld_res) * 8 : 0;
     const size_t err_b = errors ? (size_t)n_samples * 8 : 0, ex_b = exit_state ? (size_t)n_samples * 32 : 0;
+    const size_t st_b = step_exits ? (size_t)n_samples * n_steps * 32 : 0;
     mg_workspace ws(ctx, "mg_score_walk_residuals_host");
-    const size_t o_lat = ws.carve(lat_b), o_res = ws.carve(res_b), o_err = ws.carve(err_b), o_ex = ws.carve(ex_b);
+    const size_t o_lat = ws.carve(lat_b), o_res = ws.carve(res_b), o_err = ws.carve(err_b), o_ex = ws.carve(ex_b), o_st = ws.carve(st_b);
     if (n_samples > 0) {
         int rc = ws.alloc();
         if (rc != MG_OK) return rc;
         MG_HIP_CHECK(hipMemcpyAsync(ws.at<char>(o_lat), latents, lat_b, hipMemcpyHostToDevice, ctx->stream));
         if (res_b) MG_HIP_CHECK(hipMemcpyAsync(ws.at<char>(o_res), residuals, res_b, hipMemcpyHostToDevice, ctx->stream));
     }
-    int rc = mg_score_walk_residuals(n_steps, steps, n_samples ? ws.at<void>(o_lat) : nullptr, latent_dtype, n_samples, ld, res_b ? ws.at<double>(o_res) : nullptr, ld_res,
-                                     err_b ? ws.at<double>(o_err) : nullptr, ex_b ? ws.at<double>(o_ex) : nullptr);
+    int rc = mg_score_walk_residuals_steps(n_steps, steps, n_samples ? ws.at<void>(o_lat) : nullptr, latent_dtype, n_samples, ld, res_b ? ws.at<double>(o_res) : nullptr,
+                                           ld_res, err_b ? ws.at<double>(o_err) : nullptr, ex_b ? ws.at<double>(o_ex) : nullptr, st_b ? ws.at<double>(o_st) : nullptr);
     if (rc != MG_OK || n_samples == 0) return rc;
     if (res_b) MG_HIP_CHECK(hipMemcpyAsync(residuals, ws.at<char>(o_res), res_b, hipMemcpyDeviceToHost, ctx->stream));
     if (err_b) MG_HIP_CHECK(hipMemcpyAsync(errors, ws.at<char>(o_err), err_b, hipMemcpyDeviceToHost, ctx->stream));
     if (ex_b) MG_HIP_CHECK(hipMemcpyAsync(exit_state, ws.at<char>(o_ex), ex_b, hipMemcpyDeviceToHost, ctx->stream));
+    if (st_b) MG_HIP_CHECK(hipMemcpyAsync(step_exits, ws.at<char>(o_st), st_b, hipMemcpyDeviceToHost, ctx->stream));
     MG_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     return MG_OK;
+}
+
+extern "C" int mg_score_walk_residuals_host(int32_t n_steps, const mg_walk_score_step *steps, const void *latents, int latent_dtype, int64_t n_samples, int64_t ld,
+                                            double *residuals, int64_t ld_res, double *errors, double *exit_state) {
+    return mg_score_walk_residuals_steps_host(n_steps, steps, latents, latent_dtype, n_samples, ld, residuals, ld_res, errors, exit_state, nullptr);
 }

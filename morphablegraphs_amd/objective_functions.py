@@ -17,7 +17,7 @@ import numpy as np
 
 from . import _capi
 from .candidate_scoring import (constraints_to_device_form, cached_constraint_set, alignment_from_prev_frames, group_residuals,
-                                split_trajectories, cached_trajectory)
+                                split_trajectories, cached_trajectory, release_trajectory)
 
 
 def _prim_of(motion_primitive):
@@ -210,11 +210,22 @@ def _aligning_node(motion_primitive_graph):
     return node, ref_dir
 
 
-def _global_blocks(s, motion_primitive_graph, graph_walk_steps, prev_frames, exit_from="frames"):
-    """Per step the (n, n_residuals_i) matrix of a batch of concatenated latent vectors, every candidate's steps chained.
+def _trajectory_alignment_check(trajectories, alignment):
+    if trajectories and alignment is not None and alignment.get("joint", 0) not in (0, _capi.MG_ALIGN_START_POSE):
+        raise NotImplementedError("trajectory constraints in global coordinates need the root joint as aligning node")
+
+
+def _global_blocks(s, motion_primitive_graph, graph_walk_steps, prev_frames, exit_from="frames", states=None):
+    """Per step the (n, n_residuals_i) matrix of a batch of concatenated latent vectors, every candidate's steps chained, and per
+    step the (n,) error MotionPrimitiveConstraints.evaluate adds up -> (S, single, blocks, errors).  A step's block is its grouped
+    keyframe columns, then T columns per trajectory constraint in list order (the order of _residuals); its error is the keyframe
+    columns' sum plus every trajectory's weighted AVERAGE distance -- not the sum of its T columns.  A trajectory is scored like
+    the step's keyframe set: against the walk's record on the first step (score_trajectory), unaligned on a local step, and on a
+    later step against every candidate's own previous step (score_trajectory_chained on the state the keyframe route carries).
     exit_from: "frames" -- the next step is aligned to the last FRAME of this step's aligned motion (obj_global_error_sum,
     obj_global_residual_vector: get_motion_vector()[-1], canonical time F); "coeffs" -- to its last CONTROL POINT
-    (obj_global_residual_vector_and_naturalness hands `.coeffs` on, objective_functions.py:373: the spline at its last knot)."""
+    (obj_global_residual_vector_and_naturalness hands `.coeffs` on, objective_functions.py:373: the spline at its last knot).
+    states: a list that receives the (n, 4) exit state every step hands on."""
     S, single = _batch(s)
     S = np.asarray(S, dtype=np.float64)
     n = len(S)
@@ -223,7 +234,7 @@ def _global_blocks(s, motion_primitive_graph, graph_walk_steps, prev_frames, exi
     if node_name is not None and hip_sk is None:
         raise NotImplementedError("aligning node %r is not the root joint: the graph needs a _capi.Skeleton as .hip_skeleton" % (node_name,))
     joint = 0 if node_name is None else node_name
-    state, offset, blocks = None, 0, []
+    state, offset, blocks, errors = None, 0, [], []
     for step in graph_walk_steps:
         node = motion_primitive_graph.nodes[step.node_key]
         prim = _prim_of(node)
@@ -232,8 +243,6 @@ def _global_blocks(s, motion_primitive_graph, graph_walk_steps, prev_frames, exi
         offset += Li
         cons = step.motion_primitive_constraints
         keyframes, trajectories = split_trajectories(constraints_to_device_form(_constraint_list(cons)))
-        if trajectories:
-            raise NotImplementedError("trajectory constraints inside a chained graph-walk objective")
         sk = getattr(cons, "hip_skeleton", None) or hip_sk
         F = float(prim.n_canonical_frames)
         t_exit = F if exit_from == "frames" else F - 1.0
@@ -247,6 +256,9 @@ def _global_blocks(s, motion_primitive_graph, graph_walk_steps, prev_frames, exi
             al_motion = alignment_from_prev_frames(prev_frames, type("_NotLocal", (), {"start_pose": getattr(cons, "start_pose", None), "is_local": False,
                                                                                       "skeleton": getattr(cons, "skeleton", getattr(motion_primitive_graph, "skeleton", None))})(), sk)
             al_cons = None if local else al_motion
+            _trajectory_alignment_check(trajectories, al_cons)
+            traj = [prim.score_trajectory(cached_trajectory(prim, c), alpha, c.get("min_u", 0.0), c.get("weight", 1.0), al_cons, residuals=True)
+                    for c in trajectories]
             if al_cons is al_motion:
                 res = prim.score_constraint_residuals(cached_constraint_set(prim, keyframes + exits, sk, al_motion), alpha)
                 res_k, new_state = res[:, :len(keyframes)], res[:, len(keyframes):]
@@ -255,27 +267,38 @@ def _global_blocks(s, motion_primitive_graph, graph_walk_steps, prev_frames, exi
                 new_state = prim.score_constraint_residuals(cached_constraint_set(prim, exits, sk, al_motion), alpha)
         else:
             template = {"joint": joint, "position": (0.0, 0.0, 0.0), "heading": (0.0, 1.0), "ref_dir": ref_dir}
+            _trajectory_alignment_check(trajectories, None if local else template)
+            traj = [prim.score_trajectory(cached_trajectory(prim, c), alpha, c.get("min_u", 0.0), c.get("weight", 1.0), None, residuals=True) if local else
+                    prim.score_trajectory_chained(cached_trajectory(prim, c), alpha, state, template, c.get("min_u", 0.0), c.get("weight", 1.0), residuals=True)
+                    for c in trajectories]
             if local:
                 res_k = prim.score_constraint_residuals(cached_constraint_set(prim, keyframes, sk, None), alpha) if keyframes else np.zeros((n, 0))
                 new_state = prim.score_constraint_residuals_chained(cached_constraint_set(prim, exits, sk, template), alpha, state)
             else:
                 res = prim.score_constraint_residuals_chained(cached_constraint_set(prim, keyframes + exits, sk, template), alpha, state)
                 res_k, new_state = res[:, :len(keyframes)], res[:, len(keyframes):]
-        blocks.append(group_residuals(keyframes, res_k) if keyframes else res_k)
+        block = group_residuals(keyframes, res_k) if keyframes else res_k
+        err = block.sum(axis=1)
+        for e, _ in traj:
+            err = err + e
+        blocks.append(np.hstack([block] + [r for _, r in traj]) if traj else block)
+        errors.append(err)
         state = np.ascontiguousarray(new_state)
+        if states is not None:
+            states.append(state)
         if hasattr(cons, "evaluations"):
             cons.evaluations += n
-    return S, single, blocks
+    return S, single, blocks, errors
 
 
 def obj_global_error_sum(s, data):
     """objective_functions.py:290-316: the sum over the walk's steps of MotionPrimitiveConstraints.evaluate, each step scored
     against the previous step's aligned frames -> (n,) (float for 1-D s).  (The reference prints the value on every call.)"""
     motion_primitive_graph, graph_walk_steps, error_scale, quality_scale, prev_frames = data
-    S, single, blocks = _global_blocks(s, motion_primitive_graph, graph_walk_steps, prev_frames, "frames")
+    S, single, _, errors = _global_blocks(s, motion_primitive_graph, graph_walk_steps, prev_frames, "frames")
     err = np.zeros(len(S))
-    for b in blocks:
-        err = err + b.sum(axis=1)
+    for e in errors:
+        err = err + e
     return float(err[0]) if single else err
 
 
@@ -285,7 +308,7 @@ def obj_global_residual_vector(s, data):
     function unpacks six (:341 vs :220), so the reference raises ValueError here; this is the evident intent, with the missing
     per-step init_error_sum = 1 as in the _and_naturalness form (:369)."""
     motion_primitive_graph, graph_walk_steps, error_scale, quality_scale, prev_frames, init_error_sum = data
-    S, single, blocks = _global_blocks(s, motion_primitive_graph, graph_walk_steps, prev_frames, "frames")
+    S, single, blocks, _ = _global_blocks(s, motion_primitive_graph, graph_walk_steps, prev_frames, "frames")
     cols = [_pad(b, int(step.n_spatial_components)) for b, step in zip(blocks, graph_walk_steps)]
     out = np.hstack(cols) / init_error_sum
     return out[0] if single else out
@@ -296,7 +319,7 @@ def obj_global_residual_vector_and_naturalness(s, data):
     quality_scale, zero-padded to the step's FULL number of latents, side by side, divided by init_error_sum; the next step is
     aligned to this step's aligned CONTROL POINTS (the reference passes `.coeffs` on as frames, :362,:373)."""
     motion_primitive_graph, graph_walk_steps, error_scale, quality_scale, prev_frames, init_error_sum = data
-    S, single, blocks = _global_blocks(s, motion_primitive_graph, graph_walk_steps, prev_frames, "coeffs")
+    S, single, blocks, _ = _global_blocks(s, motion_primitive_graph, graph_walk_steps, prev_frames, "coeffs")
     cols, offset = [], 0
     for b, step in zip(blocks, graph_walk_steps):
         Li = int(step.n_spatial_components)
@@ -328,6 +351,11 @@ class HipGraphWalkObjective(object):
     of S (n, sum L_i), one launch, one download.  The sets are the ones _global_blocks asks for (the same `keyframes + exits`
     lists, the same local-step split, the same first-step record), so blocks(S) equals _global_blocks(S, ...)[2].
 
+    A step's trajectory constraints are one launch each on the same stream behind the walk's (mg_score_trajectory; on a later
+    step that is not local mg_score_trajectory_chained on the exit values the walk's launch wrote for the step before,
+    mg_score_walk_residuals_steps): still one upload and one download, n_launches grows by 1 + the number of trajectories per
+    call.  The trajectories are pinned for the life of the objective (close() releases them).
+
     Raises NotImplementedError where _global_blocks does, ValueError for more than MG_WALK_MAX_STEPS steps; a call raises
     _capi.MGError(-4) where a step's tables do not fit LDS (the callers then take the chain)."""
 
@@ -336,8 +364,13 @@ class HipGraphWalkObjective(object):
         if not 1 <= len(self.steps) <= _capi.MG_WALK_MAX_STEPS:
             raise ValueError("%d steps: 1 .. %d per launch" % (len(self.steps), _capi.MG_WALK_MAX_STEPS))
         self._private, self._shared, self._buf, self._cap = [], [], None, 0
+        self._trajectories = []      # [(pinned trajectory, min_u, weight, step index, column offset in the step's block, alignment, chained)]
         self.n_launches = 0
-        self._build()
+        try:
+            self._build()
+        except Exception:
+            self.close()      # (nothing stays pinned behind a refused walk)
+            raise
 
     def _set(self, prim, clist, sk, alignment, taken):
         """cached_constraint_set, unless the shared set of this structure already serves another step of this walk with other
@@ -361,6 +394,7 @@ class HipGraphWalkObjective(object):
         joint = 0 if node_name is None else node_name
         for cs in self._private:
             cs.close()
+        self._release_trajectories()
         self._private, self._shared = [], []
         taken, records, self._info = {}, [], []
         offset = column = 0
@@ -369,8 +403,6 @@ class HipGraphWalkObjective(object):
             Li = int(step.n_spatial_components)
             cons = step.motion_primitive_constraints
             keyframes, trajectories = split_trajectories(constraints_to_device_form(_constraint_list(cons)))
-            if trajectories:
-                raise NotImplementedError("trajectory constraints inside a chained graph-walk objective")
             sk = getattr(cons, "hip_skeleton", None) or hip_sk
             F = float(prim.n_canonical_frames)
             exits = _exit_constraints(F if self.exit_from == "frames" else F - 1.0, joint, ref_dir)
@@ -386,6 +418,14 @@ class HipGraphWalkObjective(object):
                 exit_set = self._set(prim, exits, sk, al_motion, taken)
             else:
                 scored, exit_set = self._set(prim, keyframes + exits, sk, al_motion, taken), None
+            # (a trajectory is aligned like the step's scored set: the walk's record, nothing on a local step, the candidate's own state)
+            al_traj = None if local else al_motion
+            _trajectory_alignment_check(trajectories, al_traj)
+            width = len(keyframes) if not keyframes else group_residuals(keyframes, np.zeros((0, len(keyframes)))).shape[1]
+            for c in trajectories:
+                self._trajectories.append((cached_trajectory(prim, c, pin=True), c.get("min_u", 0.0), c.get("weight", 1.0), i, width, al_traj,
+                                           i > 0 and not local))
+                width += prim._grid_size(None)
             records.append((prim, scored, exit_set, offset, len(keyframes), column))
             self._info.append((prim, keyframes, Li, offset, column, cons))
             offset += Li
@@ -399,10 +439,15 @@ class HipGraphWalkObjective(object):
         if any(not cs.handle or cs.cached_values != values for cs, values in self._shared):
             self._build()
 
+    def _release_trajectories(self):
+        while self._trajectories:
+            release_trajectory(self._trajectories.pop()[0])
+
     def close(self):
         for cs in self._private:
             cs.close()
         self._private = []
+        self._release_trajectories()
         if self._buf is not None:
             self._buf.free()
         self._buf, self._cap = None, 0
@@ -415,7 +460,8 @@ class HipGraphWalkObjective(object):
 
     def _run(self, S, logp=False):
         """-> (residuals (n, n_columns), errors (n), exit state (n, 4), {step: log p (n)} for the steps whose mixture has no time
-        latents).  One device block: the latents, then everything that comes back."""
+        latents, [(n, T) residuals per trajectory]).  One device block: the latents, then everything that comes back, then what
+        stays on the device (every step's exit values and the (n, 4) block of them a chained trajectory launch reads)."""
         self._ensure()
         S = _capi._latents(S)
         if S.shape[1] < self.n_latents:
@@ -424,8 +470,10 @@ class HipGraphWalkObjective(object):
         on_device = [i for i, (prim, _, Li, _, _, _) in enumerate(self._info)
                      if logp and len(np.asarray(self.steps[i].parameters)) <= Li and prim.n_gmm_dims == Li]
         lat_bytes = (S.nbytes + 255) & ~255
-        n_out = n * (self.n_columns + 5 + len(on_device))
-        need = lat_bytes + 8 * max(n_out, 1)
+        traj_T = [t[0].prim._grid_size(None) for t in self._trajectories]
+        chained = any(t[6] for t in self._trajectories)      # some step past the first follows a trajectory from its candidates' states
+        n_out = n * (self.n_columns + 5 + len(on_device) + sum(traj_T))
+        need = lat_bytes + 8 * max(n_out, 1) + (8 * n * 4 * (m + 1) if chained else 0)
         if need > self._cap:
             if self._buf is not None:
                 self._buf.free()
@@ -435,11 +483,27 @@ class HipGraphWalkObjective(object):
         d_err = d_res + 8 * n * self.n_columns
         d_exit = d_err + 8 * n
         d_logp = d_exit + 8 * n * 4
+        d_traj = d_logp + 8 * n * len(on_device)
+        d_steps = base + lat_bytes + 8 * max(n_out, 1)      # (n, m, 4), then the (n, 4) rows of one step gathered from it
+        d_state = d_steps + 8 * n * 4 * m
         if n == 0:
-            return np.zeros((0, self.n_columns)), np.zeros(0), np.zeros((0, 4)), {i: np.zeros(0) for i in on_device}
+            return np.zeros((0, self.n_columns)), np.zeros(0), np.zeros((0, 4)), {i: np.zeros(0) for i in on_device}, [np.zeros((0, T)) for T in traj_T]
         self.ctx.upload_into(base, S)
-        self.table.score_dev(base, S.dtype, n, ld, d_res if self.n_columns else None, self.n_columns, d_err, d_exit)
+        self.table.score_dev(base, S.dtype, n, ld, d_res if self.n_columns else None, self.n_columns, d_err, d_exit, d_steps if chained else None)
         self.n_launches += 1
+        gathered, d_r = None, d_traj
+        for (t, min_u, weight, i, _, al, chain), T in zip(self._trajectories, traj_T):     # stream ordered behind the walk's launch
+            prim, _, _, offset, _, _ = self._info[i]
+            lat = base + offset * S.dtype.itemsize
+            if chain:
+                if gathered != i:      # the state step i is aligned to: step i - 1's exit values of every candidate, side by side
+                    self.ctx.copy_rows_dev(d_state, 32, d_steps + 32 * (i - 1), 32 * m, 32, n)
+                    gathered = i
+                prim.score_trajectory_chained_dev(t, lat, S.dtype, n, ld, d_state, al, d_err, min_u, weight, True, d_r)
+            else:
+                prim.score_trajectory_dev(t, lat, S.dtype, n, ld, d_err, min_u, weight, al, True, d_r)
+            self.n_launches += 1
+            d_r += 8 * n * T
         for j, i in enumerate(on_device):      # stream ordered behind the walk's launch, on the latents already there
             prim, _, Li, offset, _, _ = self._info[i]
             prim.gmm_log_prob_dev(base + offset * S.dtype.itemsize, S.dtype, n, ld, d_logp + 8 * n * j, np.float64)
@@ -448,33 +512,42 @@ class HipGraphWalkObjective(object):
         err = out[n * self.n_columns:n * (self.n_columns + 1)]
         ex = out[n * (self.n_columns + 1):n * (self.n_columns + 5)].reshape(n, 4)
         lp = {i: out[n * (self.n_columns + 5 + j):n * (self.n_columns + 6 + j)] for j, i in enumerate(on_device)}
+        tres, at = [], n * (self.n_columns + 5 + len(on_device))
+        for T in traj_T:
+            tres.append(out[at:at + n * T].reshape(n, T))
+            at += n * T
         for _, _, _, _, _, cons in self._info:
             if hasattr(cons, "evaluations"):
                 cons.evaluations += n
-        return res, err, ex, lp
+        return res, err, ex, lp, tres
 
-    def _blocks_of(self, res):
+    def _blocks_of(self, res, tres=()):
         out = []
-        for _, keyframes, _, _, column, _ in self._info:
+        for i, (_, keyframes, _, _, column, _) in enumerate(self._info):
             res_k = res[:, column:column + len(keyframes)]
-            out.append(group_residuals(keyframes, res_k) if keyframes else res_k)
+            block = group_residuals(keyframes, res_k) if keyframes else res_k
+            mine = [r for t, r in zip(self._trajectories, tres) if t[3] == i]     # in list order, at the columns _build recorded
+            out.append(np.hstack([block] + mine) if mine else block)
         return out
 
     def blocks(self, S):
         """Per step the (n, n_residuals_i) matrix: _global_blocks(S, ...)[2]."""
-        return self._blocks_of(self._run(S)[0])
+        run = self._run(S)
+        return self._blocks_of(run[0], run[4])
 
     def exit_state(self, S):
         """(n, 4): the last step's exit values (unit heading x, z; root position x, z)."""
         return self._run(S)[2]
 
     def error_sum(self, S):
-        """(n,): per step the residuals added in constraint order, the step sums added in step order (on the device)."""
+        """(n,): per step the residuals added in constraint order, the step sums added in step order (on the device); then every
+        trajectory's error in step and list order."""
         return self._run(S)[1].copy()
 
     def residual_vector(self, S, init_error_sum):
         """obj_global_residual_vector's rows for the batch S."""
-        blocks = self._blocks_of(self._run(S)[0])
+        run = self._run(S)
+        blocks = self._blocks_of(run[0], run[4])
         cols = [_pad(b, int(step.n_spatial_components)) for b, step in zip(blocks, self.steps)]
         return np.hstack(cols) / init_error_sum
 
@@ -483,9 +556,9 @@ class HipGraphWalkObjective(object):
         scored on the latents the walk's launch has read (mg_gmm_log_prob at the step's column), everything comes back in one
         download; a step with time latents (its tail is concatenated) goes through the host for its mixture."""
         S = np.asarray(_batch(S)[0], dtype=np.float64)
-        res, _, _, lp = self._run(S, logp=True)
+        res, _, _, lp, tres = self._run(S, logp=True)
         cols = []
-        for i, (b, step) in enumerate(zip(self._blocks_of(res), self.steps)):
+        for i, (b, step) in enumerate(zip(self._blocks_of(res, tres), self.steps)):
             prim, _, Li, offset, _, _ = self._info[i]
             width = Li
             if i in lp:

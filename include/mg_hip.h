@@ -333,7 +333,7 @@ int mg_memset(mg_context *ctx, void *dst_dev, int value, int64_t bytes);
  *       4 = gmm_sample, 5 = spline_evaluate, 6 = fused step, 7 = a planner step in one launch (mg_options_step),
  *       8 = mg_joint_tracks, 9 = mg_score_frame_constraints, 10 = mg_score_trajectory[_points],
  *       11 = mg_cluster_tree_search (both tree kinds: mg_tree_search_kernel or mg_kd_tree_search_kernel),
- *       12 = the frames kernel of mg_walk_frames, 13 = mg_score_walk_time, 14 = mg_step_lengths. */
+ *       12 = the frames kernel of mg_walk_frames, 13 = mg_score_walk_time, 14 = mg_step_lengths, 15 = mg_feature_points. */
 int mg_profile_enable(mg_context *ctx, int enabled);
 int mg_profile_reset(mg_context *ctx);
 int mg_profile_get(mg_context *ctx, int slot, double *total_ms, int64_t *launches);
@@ -1176,9 +1176,9 @@ int mg_walk_time_table_uploads(mg_context *ctx, int64_t *uploads);   /* mg_conte
 
 /* The per-call descriptor tables a context keeps on the device, each rewritten only when a call's table differs from the last call's:
  * of mg_options_step's one-launch path, mg_cluster_tree_search, mg_walk_frames, mg_score_walk_residuals, mg_score_walk_time and
- * mg_step_lengths.  mg_context_table_uploads: how often table `which` of the context went to the device so far. */
+ * mg_step_lengths, and of mg_feature_points.  mg_context_table_uploads: how often table `which` of the context went to the device so far. */
 enum { MG_TABLE_FUSED = 0, MG_TABLE_TREE = 1, MG_TABLE_WALK = 2, MG_TABLE_WALK_SCORE = 3, MG_TABLE_WALK_TIME = 4, MG_TABLE_STEP_LENGTH = 5,
-       MG_TABLE_COUNT = 6 };
+       MG_TABLE_FEATURE_POINTS = 6, MG_TABLE_COUNT = 7 };
 int mg_context_table_uploads(mg_context *ctx, int which, int64_t *uploads);
 
 /* Step lengths without frames in memory, ONE launch for every candidate of every item (csrc/mg_step_length.hip): what
@@ -1215,10 +1215,64 @@ typedef struct {
 } mg_step_length_item;
 int mg_step_lengths(int32_t n_items, const mg_step_length_item *items, int latent_dtype);
 
+/* Feature points without frames in memory, ONE launch for every candidate of every item (csrc/mg_feature_points.hip): what the
+ * reference's FeaturePointModel (construction/feature_point_model.py: create_feature_points :58-84, create_root_pos_ori :86-95)
+ * takes from a whole back-projected motion, and what FeaturePointModelBuilder.build asks of every primitive of a model directory.
+ * Items may use different primitives, skeletons, joint lists and frames; a primitive may repeat; all primitives belong to one
+ * context.  Per candidate, float64 throughout, every operation rounded on its own (float32 latents are converted first):
+ *   control points  only the channels and basis rows the frames 0, frame_idx and F - 1 touch: mean' then fma(E'[k], s[k], .) for k
+ *                   ascending, translation_maxima included: the statement and the bits of mg_back_project_coeffs(MG_F64);
+ *   frames          0, frame_idx and F - 1 on the primitive's canonical grid linspace(0, F, F) with the primitive's own tap rows (the
+ *                   FITPACK ext=0 row of the last sample included), four taps w0 c0, fma(w1, c1, .), ..: the bits of
+ *                   mg_back_project_frames_f64;
+ *   start_root      (n, 3): the root position of frame 0;
+ *   points          (n, 3 n_joints): the global position of every listed joint at frame_idx by forward kinematics along its chain --
+ *                   the statement and the bits of mg_joint_positions on that frame -- minus start_root;
+ *   root_end        (n, 2): x and z of the root at frame F - 1;
+ *   heading_end     (n, 2): the root quaternion of frame F - 1, made unit as every chain quaternion is, applied to (0, 0, 1); its x and z
+ *                   divided by their length (the accumulated orientation is not normalised again);
+ *   heading_len     (n): that length before the division, so that a caller sees a degenerate heading.
+ * No transcendental function runs on the device; the reference's angle (convert_ori_to_angle_deg) is formed on the host from heading_end.
+ * A candidate with a latent that is not finite gets NaN in all its outputs, and nothing else does; a candidate's values depend on
+ * neither the batch nor the other items nor its position in either.  Nothing per candidate goes to device memory but the outputs.
+ * skeleton / joints: HOST pointers, read during the call; skeleton may be NULL with n_joints = 0.  n_joints <=
+ * MG_FEATURE_POINTS_MAX_JOINTS = 32: with chains of MG_MAX_CHAIN links the joints' records are 34 KB of a workgroup's LDS, which leaves
+ * 116 KB of the 150 KB a workgroup may take for the listed rows of E' and the tile's control points.
+ * Everything is checked before any launch or copy.  MG_ERR_INVALID_ARGUMENT: NULL item table with n_items > 0, a NULL primitive, NULL
+ * latents with n_samples > 0, latent_offset < 0 or latent_offset + n_components > ld, negative counts, frame_idx outside 0 .. F - 1,
+ * a joint outside the skeleton (or n_joints outside 0 .. the cap, joints without a skeleton), n_joints > 0 without points_dev or
+ * points_dev with n_joints = 0, all outputs NULL, primitives of two contexts.  MG_ERR_UNSUPPORTED, never an approximate answer: a
+ * primitive with fewer than 7 channels, a skeleton with a quaternion channel beyond the primitive's channels, a chain of more than
+ * MG_MAX_CHAIN links, tables that do not fit LDS even with the large-LDS opt-in.  n_items == 0 or all items empty: MG_OK, no launch;
+ * empty items among others are skipped.  A launch takes MG_FEATURE_POINTS_MAX_ITEMS non-empty items; a call with more goes through them
+ * in slices itself.  Apart from the item table (kept on the device, rewritten only when it differs from the last call's) the call
+ * allocates nothing and does not synchronise.  Profile slot 15. */
+#define MG_FEATURE_POINTS_MAX_ITEMS 256
+#define MG_FEATURE_POINTS_MAX_JOINTS 32
+typedef struct {
+    mg_primitive *prim;
+    const void *latents_dev;            /* (n_samples, ld) float32 / float64 */
+    int64_t latent_offset;              /* first column of this item's n_components latents in a row */
+    int64_t n_samples, ld;
+    const mg_skeleton_desc *skeleton;   /* HOST; NULL allowed with n_joints = 0 */
+    const int32_t *joints;              /* HOST (n_joints) indices into the skeleton */
+    int32_t n_joints;
+    int32_t frame_idx;                  /* canonical frame of `points` */
+    double *start_root_dev;             /* (n_samples, 3) or NULL */
+    double *points_dev;                 /* (n_samples, 3 n_joints); NULL exactly when n_joints = 0 */
+    double *root_end_dev;               /* (n_samples, 2) or NULL */
+    double *heading_end_dev;            /* (n_samples, 2) or NULL */
+    double *heading_len_dev;            /* (n_samples) or NULL */
+} mg_feature_point_item;
+int mg_feature_points(int32_t n_items, const mg_feature_point_item *items, int latent_dtype);
+
 /* ---- host-pointer convenience variants (H2D, launch, D2H, synchronise) ---------------- */
 /* mg_step_lengths with every item's latents and outputs in host memory (the `_dev` members are host pointers here); items that name
  * the same latent matrix (pointer, n_samples and ld) share one copy of it on the device */
 int mg_step_lengths_host(int32_t n_items, const mg_step_length_item *items, int latent_dtype);
+/* mg_feature_points with every item's latents and outputs in host memory (the `_dev` members are host pointers here); items that
+ * name the same latent matrix (pointer, n_samples and ld) share one copy of it on the device */
+int mg_feature_points_host(int32_t n_items, const mg_feature_point_item *items, int latent_dtype);
 /* mg_score_walk_time with host arrays: latents, outputs and every step's spatial latents (`spatial_dev` is a host pointer here) */
 int mg_score_walk_time_host(int32_t n_steps, const mg_walk_time_step *steps, const void *latents, int latent_dtype, int64_t n_samples, int64_t ld,
                             int32_t n_constraints, const mg_walk_time_constraint *constraints, double start_keyframe, double frame_time,

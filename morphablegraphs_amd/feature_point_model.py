@@ -1,0 +1,396 @@
+"""Feature-point (reachability) models of motion primitives (reference construction/feature_point_model.py and
+feature_point_model_builder.py).
+
+FeaturePointModel draws n latents, back-projects each to a whole motion and keeps the root's ground position and heading at the
+last frame (create_root_pos_ori), or the position of a few joints at one frame relative to the first root position
+(create_feature_points); it fits a Gaussian mixture to those 3, 4 or 3 J numbers and stores it with a log-likelihood threshold,
+so that check_reachability / score_trajectory_target can say whether the primitive gets to a target at all.  Here the features
+of every candidate -- of every node, for the builder -- come from ONE mg_feature_points call (csrc/mg_feature_points.hip), which
+evaluates the three frames that are asked for and writes no frame to memory; the mixture is trained by HipGMMTrainer.
+
+feature_points_host is the NumPy statement of the kernel's arithmetic; it needs no library.
+
+Not restated: plot_orientation; time-warped features (use_time_parameters=True on a primitive with a time model raises
+NotImplementedError -- the reference's default would time-warp there; on a primitive without a time model the two agree); the
+reference's mixture.GMM class (loading gives FeatureMixture, the same JSON).
+"""
+import json
+import os
+
+import numpy as np
+
+from . import _capi
+from . import graph_walk as gw
+from .gaussian_mixture import sample_like_sklearn
+from .gmm_trainer import HipGMMTrainer, _compute_precision_cholesky, _estimate_weighted_log_prob
+
+REF_DIR = (0.0, 0.0, 1.0)          # pose_orientation_quat turns this axis
+
+
+# ---- the arithmetic on the host ------------------------------------------------------------------------------------
+def _rotate(q, v):
+    """v turned by the unit quaternion q = (w, u): v + 2 (w u x v + u x (u x v))."""
+    u = q[1:]
+    return v + 2.0 * (q[0] * np.cross(u, v) + np.cross(u, np.cross(u, v)))
+
+
+def joint_position_host(skeleton, frame, joint):
+    """Global position of `joint` in one pose vector: mg_joint_positions' loop (every chain quaternion made unit and multiplied
+    into the accumulated orientation, the child's offset turned by it and added)."""
+    chain = skeleton.chain(joint)
+    p = np.array(frame[:3], dtype=np.float64)
+    q = np.array([1.0, 0.0, 0.0, 0.0])
+    for parent, child in zip(chain[:-1], chain[1:]):
+        ch = int(skeleton.quat_channel[parent])
+        if ch >= 0:
+            qj = np.asarray(frame[ch:ch + 4], dtype=np.float64)
+            q = _capi._quat_mul(q, qj / np.linalg.norm(qj))
+        p = p + _rotate(q, np.asarray(skeleton.offsets[child], dtype=np.float64))
+    return p
+
+
+def heading_host(frame):
+    """(unit (x, z), length before the division) of the root quaternion of `frame`, made unit, applied to (0, 0, 1)."""
+    q = np.asarray(frame[3:7], dtype=np.float64)
+    v = _rotate(q / np.linalg.norm(q), np.array(REF_DIR))
+    d = np.array([v[0], v[2]])
+    length = np.linalg.norm(d)
+    return d / length, length
+
+
+def feature_points_host(model, S, skeleton=None, joints=(), frame_idx=0):
+    """The NumPy statement of mg_feature_points for one item.  model: the reference's JSON dict or a primitive; S (n, >= L): a
+    candidate reads its first L columns; skeleton: a _capi.Skeleton (needed with joints); joints: names or indices.  Returns the
+    dict of float64 arrays _capi.feature_points returns: start_root (n, 3), points (n, 3 J; with joints), root_end (n, 2),
+    heading_end (n, 2), heading_len (n,).  A row with a latent that is not finite is NaN throughout."""
+    hm = model if isinstance(model, gw._HostModel) else gw._HostModel(model)
+    S = np.atleast_2d(np.asarray(S, dtype=np.float64))
+    F, L = hm.n_canonical_frames, hm.n_components
+    if not 0 <= int(frame_idx) < F:
+        raise ValueError("frame_idx %d outside 0 .. %d" % (frame_idx, F - 1))
+    joints = [skeleton.index(j) for j in joints]
+    times = np.linspace(0, F, F)[[0, int(frame_idx), F - 1]]
+    n, J = len(S), len(joints)
+    out = {"start_root": np.full((n, 3), np.nan), "root_end": np.full((n, 2), np.nan), "heading_end": np.full((n, 2), np.nan),
+           "heading_len": np.full(n, np.nan)}
+    if J:
+        out["points"] = np.full((n, 3 * J), np.nan)
+    for b in range(n):
+        if not np.isfinite(S[b, :L]).all():
+            continue
+        _, fr = hm.frames(S[b, :L], times)
+        out["start_root"][b] = fr[0, :3]
+        for j, joint in enumerate(joints):
+            out["points"][b, 3 * j:3 * j + 3] = joint_position_host(skeleton, fr[1], joint) - fr[0, :3]
+        out["root_end"][b] = fr[2, 0], fr[2, 2]
+        out["heading_end"][b], out["heading_len"][b] = heading_host(fr[2])
+    return out
+
+
+def rotation_angle(point1, point2):
+    """anim_utils' get_rotation_angle: the angle from point1 to point2 in degrees, brought into [-180, 180] (restated, unpinned)."""
+    theta1 = np.rad2deg(np.arctan2(point1[1], point1[0]))
+    theta2 = np.rad2deg(np.arctan2(point2[1], point2[0]))
+    delta = theta2 - theta1
+    if delta < -180.0:
+        delta += 360.0
+    elif delta > 180.0:
+        delta -= 360.0
+    return delta
+
+
+def orientations_to_angles(orientations, ref_ori=(0, -1)):
+    """convert_ori_to_angle_deg's loop (feature_point_model.py:97-103), deg2rad(-get_rotation_angle(ori, ref_ori)) per row, for
+    all rows at once: rotation_angle's statements on arrays."""
+    ori = np.asarray(orientations, dtype=np.float64).reshape(-1, 2)
+    theta1 = np.rad2deg(np.arctan2(ori[:, 1], ori[:, 0]))
+    theta2 = np.rad2deg(np.arctan2(ref_ori[1], ref_ori[0]))
+    delta = theta2 - theta1
+    delta = np.where(delta < -180.0, delta + 360.0, np.where(delta > 180.0, delta - 360.0, delta))
+    return list(np.deg2rad(-delta))
+
+
+# ---- the stored mixture --------------------------------------------------------------------------------------------
+class FeatureMixture(object):
+    """A full-covariance mixture over 3, 4 or 3 J features with the attribute names the reference's JSON writer reads
+    (weights_, means_, covars_) and the old sklearn GMM's calling shapes the reference relies on: score(X) is the per-row
+    log p, sample(n) the rows alone.  The log-density is gmm_trainer's host restatement of sklearn's."""
+
+    def __init__(self, weights, means, covars):
+        self.weights_ = np.asarray(weights, dtype=np.float64)
+        self.means_ = np.atleast_2d(np.asarray(means, dtype=np.float64))
+        self.covars_ = np.asarray(covars, dtype=np.float64).reshape(len(self.weights_), self.means_.shape[1], self.means_.shape[1])
+        self.covariances_ = self.covars_
+        self.precisions_cholesky_ = _compute_precision_cholesky(self.covars_)
+        self.n_components = len(self.weights_)
+        self.converged_ = True
+
+    def score_samples(self, X):
+        from scipy.special import logsumexp
+        X = np.atleast_2d(np.asarray(X, dtype=np.float64))
+        if X.shape[1] != self.means_.shape[1]:
+            raise ValueError("X has %d features, but the mixture expects %d" % (X.shape[1], self.means_.shape[1]))
+        return logsumexp(_estimate_weighted_log_prob(X, self.weights_, self.means_, self.precisions_cholesky_), axis=1)
+
+    score = score_samples
+
+    def sample(self, n_samples=1):
+        return sample_like_sklearn(n_samples, self.weights_, self.means_, self.covars_)[0]
+
+
+def _mixture_json(dist):
+    return {"gmm_weights": dist.weights_.tolist(), "gmm_means": dist.means_.tolist(), "gmm_covars": dist.covars_.tolist()}
+
+
+# ---- the model -----------------------------------------------------------------------------------------------------
+class HipFeaturePointModel(object):
+    """FeaturePointModel's method table over a HipMotionPrimitive (or a node that carries one as .motion_primitive) and a
+    _capi.Skeleton (None is enough for the root features).
+
+    latents: None draws them like the reference, one GaussianMixture.sample per candidate from NumPy's global stream (a seeded
+    stream gives the reference's latents); device=True draws the whole batch with the device sampler (same distribution, another
+    stream); latents= passes them in.  The features come from one mg_feature_points call.
+
+    Training: the reference writes GMMTrainer(training_samples) and reads .gmm and .averageScore, which does not match
+    GMMTrainer's constructor (it takes no data; fit(data, score='AIC') trains).  What is built is what it means:
+    HipGMMTrainer().fit(samples) with the AIC default; max_components bounds the sweep (GMMTrainer's n_K, 40).  The thresholds
+    are averageScore (root features) and averageScore - 5 (feature points), as written."""
+
+    def __init__(self, primitive, skeleton=None, use_time_parameters=True, device=False, latents=None, max_components=40, seed=None, ctx=None):
+        self.motion_primitive_model = gw._primitive_of(primitive)
+        self.skeleton = skeleton
+        self.use_time_parameters, self.device, self.latents = use_time_parameters, bool(device), latents
+        self.max_components, self.seed, self.ctx = int(max_components), seed, ctx
+        self.low_dimension_vectors = []
+        self.feature_points = []
+        self.orientations = []
+        self.feature_point = None
+        self.feature_point_list = []
+        self.threshold = None
+        self.root_pos = []
+        self.root_low_dimension_vectors = []
+        self.root_orientation = []
+        self.root_rot_angles = []
+        self.heading_lengths = []          # the headings' lengths before the division (a degenerate heading shows here)
+        self.feature_point_dist = None
+        self.root_feature_dist = None
+        self.root_feature_dist_type = None
+        self.root_threshold = None
+
+    # ---- latents and the one call ------------------------------------------------------------------
+    def _draw(self, n):
+        mp = self.motion_primitive_model
+        if self.use_time_parameters and mp.has_time_parameters and mp.t_pca.get("n_components", 0) > 0:
+            raise NotImplementedError("time-warped feature points: pass use_time_parameters=False for a primitive with a time model")
+        if self.latents is not None:
+            S = _capi._latents(self.latents)
+            if len(S) != n:
+                raise ValueError("%d latents passed, %d asked for" % (len(S), n))
+            return S
+        gmm = mp.gaussian_mixture_model
+        if self.device:
+            return np.ascontiguousarray(gmm.sample(n, device=True)[0])
+        if n == 0:
+            return np.zeros((0, gmm.means_.shape[1]))
+        return np.vstack([mp.sample_low_dimensional_vector() for _ in range(n)])
+
+    def _item(self, S, joints=(), frame_idx=0):
+        return {"prim": self.motion_primitive_model._prim, "S": S, "skeleton": self.skeleton, "joints": list(joints), "frame_idx": frame_idx}
+
+    def _take_root(self, out, S):
+        self.root_low_dimension_vectors += np.asarray(S, dtype=np.float64).tolist()      # (the reference does not keep these)
+        self.root_pos += list(out["root_end"])
+        self.root_orientation += list(out["heading_end"])
+        self.heading_lengths += list(out["heading_len"])
+        self.root_feature_dist_type = 'vector'
+
+    # ---- feature_point_model.py:58-103 -------------------------------------------------------------
+    def create_feature_points(self, joint_name_list, n, frame_idx):
+        assert type(joint_name_list) == list, 'joint names should be a list'
+        if self.skeleton is None:
+            raise ValueError("feature points of joints need a skeleton")
+        self.feature_point_list = joint_name_list
+        S = self._draw(n)
+        out = _capi.feature_points([self._item(S, joint_name_list, frame_idx)], ("points", "heading_end", "heading_len"))[0]
+        self.low_dimension_vectors += np.asarray(S, dtype=np.float64).tolist()
+        self.feature_points += list(out["points"])
+        self.orientations += out["heading_end"].tolist()
+        self.heading_lengths += list(out["heading_len"])
+
+    def create_root_pos_ori(self, n):
+        S = self._draw(n)
+        self._take_root(_capi.feature_points([self._item(S)], ("root_end", "heading_end", "heading_len"))[0], S)
+
+    def convert_ori_to_angle_deg(self, ref_ori=[0, -1]):
+        assert len(self.root_orientation) > 0, ("please create root orientation list first!")
+        self.root_rot_angles += orientations_to_angles(self.root_orientation, ref_ori)
+        self.root_feature_dist_type = 'angle'
+
+    # ---- training ----------------------------------------------------------------------------------
+    def _train(self, samples):
+        trainer = HipGMMTrainer(seed=self.seed, ctx=self.ctx)
+        assert len(samples.shape) == 2, ('the data should be a 2d matrix')      # GMMTrainer.fit with score='AIC'
+        trainer._train_gmm(samples, n_K=self.max_components, score='AIC')
+        trainer._create_gmm(samples)
+        return FeatureMixture(trainer.gmm.weights_, trainer.gmm.means_, trainer.gmm.covariances_), float(trainer.averageScore)
+
+    def model_root_dist(self):
+        if self.root_feature_dist_type == 'vector':
+            training_samples = np.concatenate((np.asarray(self.root_pos), np.asarray(self.root_orientation)), axis=1)
+        elif self.root_feature_dist_type == 'angle':
+            training_samples = np.concatenate((np.asarray(self.root_pos), np.reshape(self.root_rot_angles, (len(self.root_rot_angles), 1))), axis=1)
+        else:
+            raise ValueError('The type of root feature points is not specified!')
+        self.root_feature_dist, self.root_threshold = self._train(training_samples)
+
+    def model_feature_points(self):
+        self.feature_point_dist, score = self._train(np.asarray(self.feature_points))
+        self.threshold = score - 5
+
+    # ---- sampling and scoring ----------------------------------------------------------------------
+    def sample_new_root_feature(self):
+        new_sample = np.ravel(self.root_feature_dist.sample())
+        if self.root_feature_dist_type == 'vector':
+            new_sample[2:] = new_sample[2:] / np.linalg.norm(new_sample[2:])
+        return new_sample
+
+    def sample_new_feature(self):
+        return np.ravel(self.feature_point_dist.sample())
+
+    def score_trajectory_targets(self, targets):
+        """Per-row log p of root targets under the root mixture: (n, 4) for 'vector', (n, 3) for 'angle'."""
+        assert self.root_feature_dist is not None, 'Please model or load root feature distribution.'
+        targets = np.atleast_2d(np.asarray(targets, dtype=np.float64))
+        width = 4 if self.root_feature_dist_type == 'vector' else 3
+        assert targets.shape[1] == width, 'The trajectory target should be a vector of length %d.' % width
+        return self.root_feature_dist.score_samples(targets)
+
+    def score_trajectory_target(self, target):
+        return self.score_trajectory_targets([target, ])[0]
+
+    def score_targets(self, targets):
+        """Per-row log p of feature-point targets (n, 3 J) under the stored mixture."""
+        assert self.feature_point_dist is not None, 'Please model or load the feature point distribution.'
+        return self.feature_point_dist.score_samples(targets)
+
+    def check_reachability_batch(self, targets):
+        return ~(self.score_targets(targets) < self.threshold)
+
+    def evaluate_target_point(self, target_point):
+        if len(self.feature_points) > 0:
+            assert len(target_point) == len(self.feature_points[0]), 'the length of feature is not correct'
+        return self.score_targets([target_point, ])[0]
+
+    def check_reachability(self, target_point):
+        score = self.evaluate_target_point(target_point)
+        if score < self.threshold:
+            return False
+        else:
+            return True
+
+    # ---- JSON --------------------------------------------------------------------------------------
+    def root_feature_dist_json(self):
+        data = {'name': self.motion_primitive_model.name, 'feature_point': 'Hips'}
+        data.update(_mixture_json(self.root_feature_dist))
+        data.update({'threshold': self.root_threshold, 'feature_type': self.root_feature_dist_type})
+        return data
+
+    def save_root_feature_dist(self, save_filename):
+        with open(save_filename, 'w') as outfile:
+            json.dump(self.root_feature_dist_json(), outfile)
+
+    def load_root_feature_dist(self, model_file):
+        with open(model_file, 'r') as infile:
+            data = json.load(infile)
+        self.root_feature_dist = FeatureMixture(data['gmm_weights'], data['gmm_means'], data['gmm_covars'])
+        self.root_feature_dist_type = data['feature_type']
+        self.root_threshold = self.root_feature_threshold = data['threshold']      # (the reference's loader names it root_feature_threshold)
+
+    def save_feature_distribution(self, save_filename):
+        data = {'name': self.motion_primitive_model.name, 'feature_point': self.feature_point}
+        data.update(_mixture_json(self.feature_point_dist))
+        data['threshold'] = self.threshold
+        with open(save_filename, 'w') as outfile:
+            json.dump(data, outfile)
+
+    def load_feature_dist(self, dist_file):
+        with open(dist_file, 'r') as infile:
+            data = json.load(infile)
+        self.feature_point_dist = FeatureMixture(data['gmm_weights'], data['gmm_means'], data['gmm_covars'])
+        self.threshold = data['threshold']
+
+    def save_data(self, save_filename):
+        output_data = {'motion_vectors': [list(map(float, v)) for v in self.low_dimension_vectors],
+                       'feature_points': [list(map(float, v)) for v in self.feature_points],
+                       'orientations': [list(map(float, v)) for v in self.orientations]}
+        with open(save_filename, 'w') as outfile:
+            json.dump(output_data, outfile)
+
+    def load_data_from_json(self, data_file):
+        with open(data_file, 'r') as infile:
+            training_data = json.load(infile)
+        self.low_dimension_vectors = training_data['motion_vectors']
+        self.feature_points = training_data["feature_points"]
+        self.orientations = training_data["orientations"]
+
+
+# ---- the builder ---------------------------------------------------------------------------------------------------
+class HipFeaturePointModelBuilder(object):
+    """FeaturePointModelBuilder (feature_point_model_builder.py): the root-feature mixture of every primitive.  build() takes a
+    graph (its .nodes), a dict {node_key: node or primitive} or nothing -- then every *_quaternion_mm.json below
+    morphable_model_directory is loaded, keyed (elementary action, motion primitive) from the file name as the reference splits
+    it.  The features of all nodes come from ONE mg_feature_points call."""
+
+    def __init__(self, context=None, **model_options):
+        self.morphable_model_directory = None
+        self.skeleton_file = None
+        self.n_samples = 10000
+        self.context = context
+        self.model_options = model_options        # passed to every HipFeaturePointModel (device=, max_components=, seed=, ...)
+
+    def set_config(self, config_file_path):
+        with open(config_file_path) as config_file:
+            config = json.load(config_file)
+        self.morphable_model_directory = config["model_data_dir"]
+        self.skeleton_file = config["skeleton_file_dir"]
+        self.n_samples = config["n_samples"]
+
+    def _nodes_of_directory(self):
+        from .motion_primitive import HipMotionPrimitive
+        nodes, where = {}, {}
+        for root, dirs, files in os.walk(self.morphable_model_directory):
+            for file in sorted(files):
+                if "_quaternion_mm.json" in file:
+                    segments = file.split('_')
+                    key = (segments[0], segments[1])
+                    nodes[key] = HipMotionPrimitive(root + os.sep + file, context=self.context)
+                    where[key] = root
+        return nodes, where
+
+    def build(self, graph_or_nodes=None):
+        if graph_or_nodes is None:
+            if self.morphable_model_directory is None:
+                raise ValueError("no nodes and no model directory: call set_config or pass a graph")
+            nodes, where = self._nodes_of_directory()
+        else:
+            nodes = dict(getattr(graph_or_nodes, "nodes", graph_or_nodes))
+            where = {key: self.morphable_model_directory for key in nodes}
+        models = {key: HipFeaturePointModel(node, None, **self.model_options) for key, node in nodes.items()}
+        keys = list(models)
+        latents = [models[key]._draw(self.n_samples) for key in keys]
+        dtypes = set(S.dtype for S in latents)
+        if len(dtypes) > 1:
+            latents = [S.astype(np.float64) for S in latents]
+        outs = _capi.feature_points([models[key]._item(S) for key, S in zip(keys, latents)], ("root_end", "heading_end", "heading_len"))
+        result = {}
+        for key, out, S in zip(keys, outs, latents):
+            model = models[key]
+            model._take_root(out, S)
+            model.convert_ori_to_angle_deg()
+            model.model_root_dist()
+            if where.get(key) is not None:
+                name = key if isinstance(key, str) else '_'.join(str(k) for k in key[:2])
+                model.save_root_feature_dist(where[key] + os.sep + '_'.join([name, "root_dist_angle.json"]))
+            result[key] = model.root_feature_dist_json()
+        self.models = models
+        return result

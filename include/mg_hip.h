@@ -1086,7 +1086,8 @@ int mg_segment_search(mg_context *ctx, const double *start_dist_dev, const doubl
  *   transforms_dev           NULL or (n_walks, n_steps, 4) float64 = (c, s, tx, tz) of every step; (1, 0, 0, 0) for an unaligned one
  * latent_offset, lengths and frame_offset are HOST tables: the call checks them before any launch (a length < 1 or > t_cap, steps that
  * overlap or pass walk_stride, primitives of two contexts or widths, a non-root aligning joint without a skeleton:
- * MG_ERR_INVALID_ARGUMENT) and carries them to the device itself.
+ * MG_ERR_INVALID_ARGUMENT) and carries them to the device itself.  One step without an alignment record aligns nothing: n_dim may then
+ * be 3 .. 6, no aligning chain is formed and a skeleton passed along is not looked at.
  * Arithmetic: a step's unaligned frames are mg_back_project_frames_f64's (canonical grid) or mg_back_project_frames_at's (given times), bit
  * for bit; its transform is the one mg_align_frames applies -- h the heading it is aligned to, b its own in its first control point:
  * c = h.b, s = h x b, a position becomes (c x + s z + tx, y, -s x + c z + tz), the root quaternion is multiplied from the left by the

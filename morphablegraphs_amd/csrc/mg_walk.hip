@@ -257,7 +257,9 @@ extern "C" int mg_walk_frames(int32_t n_steps, mg_primitive *const *prims, const
             MG_WALK_REQUIRE(a.ref[0] * a.ref[0] + a.ref[2] * a.ref[2] > 0.0, "mg_walk_frames: ref_dir has no xz part");
         }
     }
-    if (joint == 0 && !sk) {
+    if (!aligned_any) {
+        a.n_link = 0;            // nothing is aligned: no heading is formed, the chain kernel reads the root translation only (n_dim may be 3)
+    } else if (joint == 0 && !sk) {
         a.n_link = 1; a.link[0] = 3;
     } else {
         MG_WALK_REQUIRE(sk != nullptr, "mg_walk_frames: aligning joint %d is not the root: a skeleton is needed", joint);

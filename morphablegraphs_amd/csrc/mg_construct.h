@@ -21,12 +21,24 @@ __device__ __forceinline__ double mg_block_sum(double v, double *red) {
     return r;
 }
 
-// The device block of one call: carve() every region, alloc(), at<T>(offset); the destructor does the rest.
+// One host array's region of a call's block (mg_workspace).  Made from a NULL pointer or zero bytes it is absent: dev() is NULL and
+// nothing is copied.
+struct mg_staged {
+    char *const *base = nullptr;
+    size_t offset = 0;
+    template <class T>
+    T *dev() const { return base ? (T *)(*base + offset) : nullptr; }   // after upload()
+};
+
+// The device block of one call: carve() every region, alloc(), at<T>(offset); the destructor does the rest.  A call whose regions
+// mirror host arrays states each once -- in(), out(), inout() -- then upload(), its kernels on h.dev<T>(), download().
 struct mg_workspace {
     mg_context *ctx;
     const char *who;     // the entry point, for the error text
     char *base = nullptr;
     size_t bytes = 0;
+    struct copy { size_t offset; void *host; size_t bytes; bool in, out; };
+    std::vector<copy> copies;
 
     mg_workspace(mg_context *c, const char *w) : ctx(c), who(w) {}
     mg_workspace(const mg_workspace &) = delete;
@@ -55,6 +67,33 @@ struct mg_workspace {
     }
     template <class T>
     T *at(size_t offset) const { return (T *)(base + offset); }
+
+    mg_staged stage(const void *host, size_t b, bool in, bool out) {
+        if (!host || !b) return {};
+        copies.push_back({carve(b), (void *)host, b, in, out});
+        return {&base, copies.back().offset};
+    }
+    mg_staged room(size_t b) { return {&base, carve(b)}; }                             // the kernels' own: no host array, always present
+    mg_staged in(const void *host, size_t b) { return stage(host, b, true, false); }    // copied to the device by upload()
+    mg_staged out(void *host, size_t b) { return stage(host, b, false, true); }         // copied back by download()
+    mg_staged inout(void *host, size_t b) { return stage(host, b, true, true); }        // both: what the kernels leave alone stays the caller's
+    // alloc() and the copies in, on the context's stream (a call without regions allocates nothing)
+    int upload() {
+        if (!bytes) return MG_OK;
+        const int rc = alloc();
+        if (rc != MG_OK) return rc;
+        for (const copy &c : copies)
+            if (c.in) MG_HIP_CHECK(hipMemcpyAsync(base + c.offset, c.host, c.bytes, hipMemcpyHostToDevice, ctx->stream));
+        return MG_OK;
+    }
+    // the copies out, then the stream drains: the host arrays are the caller's to read when it returns
+    int download() {
+        if (!base) return MG_OK;
+        for (const copy &c : copies)
+            if (c.out) MG_HIP_CHECK(hipMemcpyAsync(c.host, base + c.offset, c.bytes, hipMemcpyDeviceToHost, ctx->stream));
+        MG_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        return MG_OK;
+    }
 };
 
 // An offsets table of n_motions + 1 entries starts at 0 and rises, no motion longer than max_frames (`limit`: that bound in the

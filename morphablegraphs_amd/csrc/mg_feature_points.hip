@@ -11,27 +11,22 @@
 //   constants   the listed rows of E' as [L][rows], their means, the three tap rows, where (control point, channel) sits among the
 //               rows, the chain records of the listed joints (mg_fk_position_table's layout): once per workgroup.  A row two frames
 //               share (frame_idx 0 or F - 1, overlapping tap windows) is listed once
-//   phase 1     control points  c[cand][row] = mean', then fma(E'[k][.], s[k], .) for k ascending (mg_control_point), one
-//               (candidate, row) per thread; consecutive lanes read consecutive doubles of E', the latent is a broadcast
+//   phase 1     control points  c[cand][row] of the listed rows (mg_item_control_points)
 //   phase 2     one (candidate, joint) per thread walks its chain (mg_fk_position_table) on channels evaluated from LDS (mg_taps4) and
 //               subtracts the root position of frame 0; one more thread per candidate states start_root, root_end and the heading
 //               (mg_chain_orientation, mg_rotate, mg_heading_xz).  The only stores to global memory
 //
-// A candidate's values are computed by statements that see nothing but its own row, so they depend on neither the batch nor the other
-// items.  Which workgroup serves which item is a prefix table (first workgroup of every item) searched by bisection; the items of a
-// call, their row lists and chain records travel in a device table of the context (ctx->tab[MG_TABLE_FEATURE_POINTS]), rewritten only
-// when it differs from the last call's, and a launch takes MG_FEATURE_POINTS_MAX_ITEMS of them: a call with more goes through the table
-// in slices.
+// The launch shape -- which workgroup serves which item, the slices of MG_FEATURE_POINTS_MAX_ITEMS items, the _host twin -- is
+// mg_items.h's; behind the items their row lists and chain records travel in the same device table (ctx->tab[MG_TABLE_FEATURE_POINTS]).
 #include <cmath>
 #include <cstring>
 
 #include <algorithm>
 #include <vector>
 
-#include "mg_construct.h"
+#include "mg_items.h"
 #include "mg_pack.h"
 #include "mg_score_device.h"
-#include "mg_spline_device.h"
 
 #define MG_FP_TILE 16                    // candidates per workgroup
 #define MG_FP_LDS_MAX (150 * 1024)
@@ -83,14 +78,7 @@ __global__ __launch_bounds__(256) void mg_feature_points_kernel(const mg_fp_args
 #pragma clang fp contract(off)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x;
-    // the item of this workgroup: the last one whose first workgroup is not past it
-    int lo = 0, hi = a.n_items - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (a.items[mid].wg0 <= (int)blockIdx.x) lo = mid;
-        else hi = mid - 1;
-    }
-    const mg_fp_item *ip = a.items + lo;
+    const mg_fp_item *ip = a.items + mg_item_of_workgroup(a.items, a.n_items);
     const int L = ip->L, D = ip->D, J = ip->J, NRS = ip->NRS, NCP = ip->NCP, RS = ip->rec_stride;
     const int64_t n = ip->n, ld = ip->ld;
     const size_t R = (size_t)ip->R;
@@ -99,8 +87,8 @@ __global__ __launch_bounds__(256) void mg_feature_points_kernel(const mg_fp_args
     double *sm = (double *)smem;
     double *sE = sm + y.E, *smean = sm + y.mean, *sw = sm + y.w, *slat = sm + y.lat, *scp = sm + y.cp, *srec = sm + y.rec;
     int32_t *smap = (int32_t *)(sm + y.ints), *stap = smap + NCP * D, *sbad = stap + MG_FP_SLOTS;
-    const int64_t b0 = (int64_t)((int)blockIdx.x - ip->wg0) * MG_FP_TILE;
-    const int ncand = (int)((n - b0) < MG_FP_TILE ? (n - b0) : MG_FP_TILE);
+    int ncand;
+    const int64_t b0 = mg_item_tile_of<MG_FP_TILE>(ip->wg0, n, ncand);
 
     // the item's constants and the tile's latents
     {
@@ -119,23 +107,11 @@ __global__ __launch_bounds__(256) void mg_feature_points_kernel(const mg_fp_args
         if (tid < MG_FP_TILE) sbad[tid] = 0;
     }
     __syncthreads();
-    {
-        const void *lat = ip->lat;
-        for (int e = tid; e < ncand * L; e += 256) {
-            const int c = e / L, k = e - c * L;
-            const double s = mg_load_lat<LAT_F64>(lat, (b0 + c) * ld + k);
-            slat[e] = s;
-            if (!isfinite(s)) sbad[c] = 1;          // (every writer stores the same value)
-        }
-    }
+    mg_item_stage_latents<LAT_F64>(ip->lat, ld, b0, ncand, L, slat, sbad);
     __syncthreads();
 
     // phase 1: control points of the listed rows
-    for (int e = tid; e < ncand * NRS; e += 256) {
-        const int c = e / NRS, j = e - c * NRS;
-        const double *s = slat + c * L;
-        scp[c * CS + j] = mg_control_point(smean[j], sE + j, (size_t)NRS, L, [&](int k) { return s[k]; });
-    }
+    mg_item_control_points(smean, sE, slat, ncand, NRS, L, scp, CS);
     __syncthreads();
 
     // phase 2: one (candidate, joint) per thread, and one thread per candidate for the root's outputs
@@ -177,9 +153,6 @@ __global__ __launch_bounds__(256) void mg_feature_points_kernel(const mg_fp_args
     }
 }
 
-#define MG_FP_REQUIRE(cond, ...) MG_REQUIRE_AS(cond, MG_ERR_INVALID_ARGUMENT, __VA_ARGS__)
-#define MG_FP_REFUSE(cond, ...) MG_REQUIRE_AS(!(cond), MG_ERR_UNSUPPORTED, __VA_ARGS__)
-
 // What the host prepares of one item: the listed rows, where a (control point, channel) sits among them, the chain records
 struct mg_fp_plan {
     std::vector<int32_t> src, map;
@@ -191,19 +164,19 @@ struct mg_fp_plan {
 
 // the argument errors of one item's joint list (MG_ERR_INVALID_ARGUMENT)
 static int mg_fp_check_joints(const char *who, int i, const mg_feature_point_item &q) {
-    MG_FP_REQUIRE(q.n_joints >= 0 && q.n_joints <= MG_FEATURE_POINTS_MAX_JOINTS, "%s: item %d: %d joints (0 .. %d)", who, i, q.n_joints,
-                  MG_FEATURE_POINTS_MAX_JOINTS);
-    MG_FP_REQUIRE((q.n_joints > 0) == (q.points_dev != nullptr), "%s: item %d: %d joints and %s points output", who, i, q.n_joints,
-                  q.points_dev ? "a" : "no");
+    MG_ITEM_REQUIRE(q.n_joints >= 0 && q.n_joints <= MG_FEATURE_POINTS_MAX_JOINTS, "%s: item %d: %d joints (0 .. %d)", who, i, q.n_joints,
+                    MG_FEATURE_POINTS_MAX_JOINTS);
+    MG_ITEM_REQUIRE((q.n_joints > 0) == (q.points_dev != nullptr), "%s: item %d: %d joints and %s points output", who, i, q.n_joints,
+                    q.points_dev ? "a" : "no");
     if (q.n_joints == 0) return MG_OK;
     const mg_skeleton_desc *sk = q.skeleton;
-    MG_FP_REQUIRE(sk && q.joints, "%s: item %d: joints without a skeleton or a joint list", who, i);
-    MG_FP_REQUIRE(sk->n_joints > 0 && sk->parents && sk->offsets && sk->quat_channel && sk->parents[0] < 0, "%s: item %d: incomplete skeleton", who, i);
+    MG_ITEM_REQUIRE(sk && q.joints, "%s: item %d: joints without a skeleton or a joint list", who, i);
+    MG_ITEM_REQUIRE(sk->n_joints > 0 && sk->parents && sk->offsets && sk->quat_channel && sk->parents[0] < 0, "%s: item %d: incomplete skeleton", who, i);
     for (int j = 0; j < q.n_joints; j++) {
         std::vector<int> ch;
         int bad;
         const int st = mg_joint_chain(sk->parents, sk->n_joints, q.joints[j], ch, &bad);
-        MG_FP_REQUIRE(st == MG_CHAIN_OK, "%s: item %d: joint %d%s", who, i, bad, mg_chain_why(st));
+        MG_ITEM_REQUIRE(st == MG_CHAIN_OK, "%s: item %d: joint %d%s", who, i, bad, mg_chain_why(st));
     }
     return MG_OK;
 }
@@ -213,19 +186,19 @@ static int mg_fp_plan_of(const char *who, int i, const mg_feature_point_item &q,
     const mg_primitive *p = q.prim;
     const mg_time_grid *g = p->canonical;
     const int D = p->D, F = p->F;
-    MG_FP_REFUSE(D < 7, "%s: item %d: the primitive has %d channels, a root pose needs 7", who, i, D);
-    MG_FP_REFUSE(!g || g->T < 1 || g->T != F || !p->d_Et64 || !p->d_mean || (int)g->i0.size() != F || (int)g->w.size() != 4 * F,
-                 "%s: item %d: the primitive has no canonical grid (%d canonical frames)", who, i, F);
+    MG_ITEM_REFUSE(D < 7, "%s: item %d: the primitive has %d channels, a root pose needs 7", who, i, D);
+    MG_ITEM_REFUSE(!g || g->T < 1 || g->T != F || !p->d_Et64 || !p->d_mean || (int)g->i0.size() != F || (int)g->w.size() != 4 * F,
+                   "%s: item %d: the primitive has no canonical grid (%d canonical frames)", who, i, F);
     const mg_skeleton_desc *sk = q.skeleton;
     if (sk && sk->quat_channel)
         for (int j = 0; j < sk->n_joints; j++)
-            MG_FP_REFUSE(sk->quat_channel[j] >= 0 && sk->quat_channel[j] + 4 > D, "%s: item %d: the skeleton's joint %d has channels %d .. %d, the primitive %d",
-                         who, i, j, sk->quat_channel[j], sk->quat_channel[j] + 3, D);
+            MG_ITEM_REFUSE(sk->quat_channel[j] >= 0 && sk->quat_channel[j] + 4 > D, "%s: item %d: the skeleton's joint %d has channels %d .. %d, the primitive %d",
+                           who, i, j, sk->quat_channel[j], sk->quat_channel[j] + 3, D);
     const int frames[MG_FP_SLOTS] = {0, q.frame_idx, F - 1};
     std::vector<int32_t> cps;
     for (int s = 0; s < MG_FP_SLOTS; s++) {
         const int i0 = g->i0[(size_t)frames[s]];
-        MG_FP_REFUSE(i0 < 0 || i0 + 4 > p->NB, "%s: item %d: frame %d takes control points %d .. %d of %d", who, i, frames[s], i0, i0 + 3, p->NB);
+        MG_ITEM_REFUSE(i0 < 0 || i0 + 4 > p->NB, "%s: item %d: frame %d takes control points %d .. %d of %d", who, i, frames[s], i0, i0 + 3, p->NB);
         for (int j = 0; j < 4; j++) {
             cps.push_back(i0 + j);
             pl.w[4 * s + j] = g->w[4 * (size_t)frames[s] + j];
@@ -249,7 +222,7 @@ static int mg_fp_plan_of(const char *who, int i, const mg_feature_point_item &q,
     for (int j = 0; j < q.n_joints; j++) {
         mg_joint_chain(sk->parents, sk->n_joints, q.joints[j], chains[(size_t)j]);
         const int m = (int)chains[(size_t)j].size() - 1;
-        MG_FP_REFUSE(m > MG_MAX_CHAIN, "%s: item %d: chain of %d joints exceeds %d", who, i, m, MG_MAX_CHAIN);
+        MG_ITEM_REFUSE(m > MG_MAX_CHAIN, "%s: item %d: chain of %d joints exceeds %d", who, i, m, MG_MAX_CHAIN);
         longest = std::max(longest, m);
         for (int k = 0; k < m; k++) {
             const int qc = sk->quat_channel[chains[(size_t)j][(size_t)k]];
@@ -271,47 +244,40 @@ static int mg_fp_plan_of(const char *who, int i, const mg_feature_point_item &q,
         rec[4] = (double)(chains[(size_t)j].size() - 1);
         mg_chain_links(chains[(size_t)j], sk->offsets, [&](int joint) { return sk->quat_channel[joint]; }, rec + MG_FP_REC_HDR);
     }
-    MG_FP_REFUSE((int64_t)p->L * pl.NRS > (1 << 20) || mg_fp_layout_of(p->L, pl.NRS, pl.NCP, D, q.n_joints, pl.rec_stride).total_bytes > MG_FP_LDS_MAX,
-                 "%s: item %d: the tables (%d x %d control-point values, %d joints) do not fit LDS", who, i, p->L, pl.NRS, q.n_joints);
-    MG_FP_REFUSE((q.n_samples + MG_FP_TILE - 1) / MG_FP_TILE > 0x7fffffff, "%s: item %d: too many samples", who, i);
+    MG_ITEM_REFUSE((int64_t)p->L * pl.NRS > (1 << 20) || mg_fp_layout_of(p->L, pl.NRS, pl.NCP, D, q.n_joints, pl.rec_stride).total_bytes > MG_FP_LDS_MAX,
+                   "%s: item %d: the tables (%d x %d control-point values, %d joints) do not fit LDS", who, i, p->L, pl.NRS, q.n_joints);
+    MG_ITEM_REFUSE_GRID(who, i, q.n_samples, MG_FP_TILE);
     return MG_OK;
 }
 
 // the checks both entry points make of an item table (nothing is launched or copied before they pass); plans: one per item
 static int mg_fp_check(const char *who, int32_t n_items, const mg_feature_point_item *items, int latent_dtype, std::vector<mg_fp_plan> &plans) {
-    MG_FP_REQUIRE(n_items >= 0 && (n_items == 0 || items), "%s: %d items, or NULL item table", who, n_items);
-    MG_FP_REQUIRE(latent_dtype == MG_F32 || latent_dtype == MG_F64, "%s: bad latent dtype %d", who, latent_dtype);
-    const mg_context *ctx = nullptr;
-    for (int i = 0; i < n_items; i++) {
-        const mg_feature_point_item &q = items[i];
-        const mg_primitive *p = q.prim;
-        MG_FP_REQUIRE(p != nullptr, "%s: item %d: the primitive is NULL", who, i);
-        if (!ctx) ctx = p->ctx;
-        MG_FP_REQUIRE(p->ctx == ctx, "%s: item %d: the primitive belongs to another context", who, i);
-        MG_FP_REQUIRE(q.n_samples >= 0 && q.ld >= 0, "%s: item %d: %lld samples, ld %lld", who, i, (long long)q.n_samples, (long long)q.ld);
-        MG_FP_REQUIRE(q.latent_offset >= 0 && q.latent_offset + p->L <= q.ld, "%s: item %d reads latent columns %lld .. %lld of %lld", who, i,
-                      (long long)q.latent_offset, (long long)(q.latent_offset + p->L), (long long)q.ld);
-        MG_FP_REQUIRE(q.n_samples == 0 || q.latents_dev, "%s: item %d: the latents are NULL", who, i);
-        MG_FP_REQUIRE(q.frame_idx >= 0 && q.frame_idx < p->F, "%s: item %d: frame %d of %d", who, i, q.frame_idx, p->F);
-        MG_FP_REQUIRE(q.start_root_dev || q.points_dev || q.root_end_dev || q.heading_end_dev || q.heading_len_dev, "%s: item %d: all outputs are NULL", who, i);
-        const int rc = mg_fp_check_joints(who, i, q);
-        if (rc != MG_OK) return rc;
-    }
+    int rc = mg_items_check(
+        who, n_items, items, latent_dtype, [](int, const mg_feature_point_item &) { return (int)MG_OK; },
+        [&](int i, const mg_feature_point_item &q) -> int {
+            MG_ITEM_REQUIRE(q.frame_idx >= 0 && q.frame_idx < q.prim->F, "%s: item %d: frame %d of %d", who, i, q.frame_idx, q.prim->F);
+            MG_ITEM_REQUIRE(q.start_root_dev || q.points_dev || q.root_end_dev || q.heading_end_dev || q.heading_len_dev, "%s: item %d: all outputs are NULL", who, i);
+            return mg_fp_check_joints(who, i, q);
+        });
+    if (rc != MG_OK) return rc;
     plans.resize((size_t)n_items);
-    for (int i = 0; i < n_items; i++) {
-        const int rc = mg_fp_plan_of(who, i, items[i], plans[(size_t)i]);
-        if (rc != MG_OK) return rc;
-    }
+    for (int i = 0; i < n_items; i++)
+        if ((rc = mg_fp_plan_of(who, i, items[i], plans[(size_t)i])) != MG_OK) return rc;
     return MG_OK;
 }
 
 static int mg_fp_run(const char *who, int32_t n_items, const mg_feature_point_item *items, int latent_dtype, const std::vector<mg_fp_plan> &plans) {
     const size_t elem = latent_dtype == MG_F64 ? 8 : 4;
-    // the non-empty items, cut into launches: at most MG_FEATURE_POINTS_MAX_ITEMS items and 2^31 - 1 workgroups each
-    std::vector<mg_fp_item> ds;
+    auto lds_of = [&](int i) {
+        const mg_fp_plan &pl = plans[(size_t)i];
+        return mg_fp_layout_of(items[i].prim->L, pl.NRS, pl.NCP, items[i].prim->D, items[i].n_joints, pl.rec_stride).total_bytes;
+    };
+    std::vector<int32_t> wg0;
+    const std::vector<mg_item_launch> launches =
+        mg_cut_items(n_items, [&](int i) { return items[i].n_samples; }, lds_of, MG_FP_TILE, MG_FEATURE_POINTS_MAX_ITEMS, wg0);
+    if (launches.empty()) return MG_OK;
+    std::vector<mg_fp_item> ds;          // the non-empty items
     std::vector<int> of;                 // the caller's item behind every entry of ds
-    struct launch { size_t first; int32_t n_items; int64_t grid; int lds; };
-    std::vector<launch> launches;
     mg_context *ctx = nullptr;
     for (int i = 0; i < n_items; i++) {
         const mg_feature_point_item &q = items[i];
@@ -319,10 +285,6 @@ static int mg_fp_run(const char *who, int32_t n_items, const mg_feature_point_it
         mg_primitive *p = q.prim;
         const mg_fp_plan &pl = plans[(size_t)i];
         ctx = p->ctx;
-        const int64_t wgs = (q.n_samples + MG_FP_TILE - 1) / MG_FP_TILE;
-        if (launches.empty() || launches.back().n_items == MG_FEATURE_POINTS_MAX_ITEMS || launches.back().grid + wgs > 0x7fffffff)
-            launches.push_back({ds.size(), 0, 0, 0});
-        launch &l = launches.back();
         mg_fp_item d;
         memset(&d, 0, sizeof(d));
         d.Et = p->d_Et64; d.mean = p->d_mean;
@@ -333,14 +295,10 @@ static int mg_fp_run(const char *who, int32_t n_items, const mg_feature_point_it
         memcpy(d.w, pl.w, sizeof(d.w));
         memcpy(d.tap, pl.tap, sizeof(d.tap));
         d.L = p->L; d.D = p->D; d.R = p->R; d.J = q.n_joints; d.NRS = pl.NRS; d.NCP = pl.NCP; d.rec_stride = pl.rec_stride;
-        d.wg0 = (int32_t)l.grid;
+        d.wg0 = wg0[i];
         ds.push_back(d);
         of.push_back(i);
-        l.n_items++;
-        l.grid += wgs;
-        l.lds = std::max(l.lds, mg_fp_layout_of(p->L, pl.NRS, pl.NCP, p->D, q.n_joints, pl.rec_stride).total_bytes);
     }
-    if (ds.empty()) return MG_OK;
     // the table: the items, then every item's row list, map and chain records
     std::vector<unsigned char> blob(ds.size() * sizeof(mg_fp_item));
     auto append = [&](const void *data, size_t bytes) {
@@ -357,28 +315,10 @@ static int mg_fp_run(const char *who, int32_t n_items, const mg_feature_point_it
         ds[e].off_src = (uint32_t)o_src; ds[e].off_map = (uint32_t)o_map; ds[e].off_rec = (uint32_t)o_rec;
     }
     memcpy(blob.data(), ds.data(), ds.size() * sizeof(mg_fp_item));
-    MG_HIP_CHECK(hipSetDevice(ctx->device));
-    mg_device_table &dt = ctx->tab[MG_TABLE_FEATURE_POINTS];
-    int rc = dt.upload(ctx, who, blob.data(), blob.size(), std::max(blob.size() * 2, (size_t)64 * 1024));
-    if (rc != MG_OK) return rc;
-    for (const launch &l : launches) {
-        mg_fp_args k;
-        k.base = dt.base();
-        k.items = (const mg_fp_item *)dt.base() + l.first;
-        k.n_items = l.n_items;
-        rc = mg_dispatch_flags(latent_dtype == MG_F64, [&](auto LAT_F64) {
-            constexpr bool f64 = decltype(LAT_F64)::value;
-            if (l.lds > 64 * 1024)
-                MG_HIP_CHECK(mg_lds_opt_in_once(ctx, f64 ? MG_LDS_FEATURE_POINTS_F64 : MG_LDS_FEATURE_POINTS_F32, 160 * 1024, mg_feature_points_kernel<f64>));
-            mg_prof_begin(ctx, MG_PROF_FEATURE_POINTS);
-            hipLaunchKernelGGL(mg_feature_points_kernel<f64>, dim3((unsigned)l.grid), dim3(256), l.lds, ctx->stream, k);
-            mg_prof_end(ctx, MG_PROF_FEATURE_POINTS);
-            MG_HIP_CHECK(hipGetLastError());
-            return (int)MG_OK;
-        });
-        if (rc != MG_OK) return rc;
-    }
-    return MG_OK;
+    return mg_items_launch(
+        ctx, who, ctx->tab[MG_TABLE_FEATURE_POINTS], blob.data(), blob.size(), std::max(blob.size() * 2, (size_t)64 * 1024), launches, latent_dtype,
+        MG_LDS_FEATURE_POINTS_F32, MG_LDS_FEATURE_POINTS_F64, MG_PROF_FEATURE_POINTS, [](auto LAT_F64) { return mg_feature_points_kernel<decltype(LAT_F64)::value>; },
+        [](const char *base, const mg_item_launch &l) { return mg_fp_args{base, (const mg_fp_item *)base + l.first, l.n_items}; });
 }
 
 extern "C" int mg_feature_points(int32_t n_items, const mg_feature_point_item *items, int latent_dtype) {
@@ -388,54 +328,13 @@ extern "C" int mg_feature_points(int32_t n_items, const mg_feature_point_item *i
     return mg_fp_run("mg_feature_points", n_items, items, latent_dtype, plans);
 }
 
-// host arrays in, host arrays out: one device block for the call, synchronises.  Items that name the same latent matrix (same
-// pointer, rows and ld: the nodes of a graph over one matrix) share one copy of it.
 extern "C" int mg_feature_points_host(int32_t n_items, const mg_feature_point_item *items, int latent_dtype) {
+    typedef mg_feature_point_item item;
     std::vector<mg_fp_plan> plans;
-    int rc = mg_fp_check("mg_feature_points_host", n_items, items, latent_dtype, plans);
+    const int rc = mg_fp_check("mg_feature_points_host", n_items, items, latent_dtype, plans);
     if (rc != MG_OK) return rc;
-    const size_t elem = latent_dtype == MG_F64 ? 8 : 4;
-    mg_context *ctx = nullptr;
-    for (int i = 0; i < n_items; i++)
-        if (items[i].n_samples > 0) ctx = items[i].prim->ctx;
-    if (!ctx) return MG_OK;
-    std::vector<mg_feature_point_item> dev(items, items + n_items);
-    struct out { double *mg_feature_point_item::*member; int width; };   // doubles per candidate; points: per joint
-    const out outs[5] = {{&mg_feature_point_item::start_root_dev, 3}, {&mg_feature_point_item::points_dev, 3}, {&mg_feature_point_item::root_end_dev, 2},
-                         {&mg_feature_point_item::heading_end_dev, 2}, {&mg_feature_point_item::heading_len_dev, 1}};
-    auto bytes_of = [&](const mg_feature_point_item &q, int o) {
-        return (size_t)q.n_samples * outs[o].width * (o == 1 ? (size_t)q.n_joints : 1) * 8;
-    };
-    std::vector<size_t> o_lat((size_t)n_items, 0), o_out((size_t)n_items * 5, 0);
-    std::vector<int> lat_of((size_t)n_items, -1);      // the earlier item whose copy of the latents this one reads
-    mg_workspace ws(ctx, "mg_feature_points_host");
-    for (int i = 0; i < n_items; i++) {
-        const mg_feature_point_item &q = items[i];
-        if (q.n_samples == 0) continue;
-        for (int j = 0; j < i && lat_of[i] < 0; j++)
-            if (items[j].n_samples == q.n_samples && items[j].latents_dev == q.latents_dev && items[j].ld == q.ld) lat_of[i] = lat_of[j] >= 0 ? lat_of[j] : j;
-        if (lat_of[i] < 0) o_lat[i] = ws.carve((size_t)(q.n_samples * q.ld) * elem);
-        for (int o = 0; o < 5; o++)
-            if (q.*(outs[o].member)) o_out[(size_t)i * 5 + o] = ws.carve(bytes_of(q, o));
-    }
-    if ((rc = ws.alloc()) != MG_OK) return rc;
-    for (int i = 0; i < n_items; i++) {
-        const mg_feature_point_item &q = items[i];
-        if (q.n_samples == 0) continue;
-        if (lat_of[i] < 0)
-            MG_HIP_CHECK(hipMemcpyAsync(ws.at<char>(o_lat[i]), q.latents_dev, (size_t)(q.n_samples * q.ld) * elem, hipMemcpyHostToDevice, ctx->stream));
-        dev[i].latents_dev = ws.at<void>(o_lat[lat_of[i] < 0 ? i : lat_of[i]]);
-        for (int o = 0; o < 5; o++)
-            dev[i].*(outs[o].member) = q.*(outs[o].member) ? ws.at<double>(o_out[(size_t)i * 5 + o]) : nullptr;
-    }
-    if ((rc = mg_fp_run("mg_feature_points_host", n_items, dev.data(), latent_dtype, plans)) != MG_OK) return rc;
-    for (int i = 0; i < n_items; i++) {
-        const mg_feature_point_item &q = items[i];
-        if (q.n_samples == 0) continue;
-        for (int o = 0; o < 5; o++)
-            if (q.*(outs[o].member))
-                MG_HIP_CHECK(hipMemcpyAsync(q.*(outs[o].member), ws.at<char>(o_out[(size_t)i * 5 + o]), bytes_of(q, o), hipMemcpyDeviceToHost, ctx->stream));
-    }
-    MG_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    return MG_OK;
+    const mg_item_output<item> outs[5] = {{&item::start_root_dev, 3, nullptr}, {&item::points_dev, 3, &item::n_joints}, {&item::root_end_dev, 2, nullptr},
+                                          {&item::heading_end_dev, 2, nullptr}, {&item::heading_len_dev, 1, nullptr}};
+    return mg_items_host("mg_feature_points_host", n_items, items, latent_dtype, outs,
+                         [&](const item *dev) { return mg_fp_run("mg_feature_points_host", n_items, dev, latent_dtype, plans); });
 }

@@ -361,22 +361,15 @@ extern "C" int mg_walk_frames_host(int32_t n_steps, mg_primitive *const *prims, 
     MG_WALK_REQUIRE(!times || t_cap >= 1, "mg_walk_frames_host: times need t_cap >= 1");
     mg_context *ctx = prims[0]->ctx;
     const int64_t D = prims[0]->D;
-    const size_t lat_b = (size_t)(n_walks * ld) * (dtype == MG_F64 ? 8 : 4), times_b = times ? (size_t)(n_walks * n_steps * t_cap) * 8 : 0;
-    const size_t frames_b = (size_t)(n_walks * walk_stride * D) * 8, xf_b = transforms ? (size_t)(n_walks * n_steps * 4) * 8 : 0;
     mg_workspace ws(ctx, "mg_walk_frames_host");
-    const size_t o_lat = ws.carve(lat_b), o_times = ws.carve(times_b), o_frames = ws.carve(frames_b), o_xf = ws.carve(xf_b);
-    if (n_walks > 0) {
-        int rc = ws.alloc();
-        if (rc != MG_OK) return rc;
-        MG_HIP_CHECK(hipMemcpyAsync(ws.at<char>(o_lat), latents, lat_b, hipMemcpyHostToDevice, ctx->stream));
-        if (times) MG_HIP_CHECK(hipMemcpyAsync(ws.at<char>(o_times), times, times_b, hipMemcpyHostToDevice, ctx->stream));
-        MG_HIP_CHECK(hipMemcpyAsync(ws.at<char>(o_frames), frames, frames_b, hipMemcpyHostToDevice, ctx->stream));   // rows no step owns stay the caller's
-    }
-    int rc = mg_walk_frames(n_steps, prims, latent_offset, n_walks ? ws.at<void>(o_lat) : nullptr, dtype, n_walks, ld, times ? ws.at<double>(o_times) : nullptr, lengths,
-                            t_cap, frame_offset, al, sk, n_walks ? ws.at<double>(o_frames) : nullptr, walk_stride, transforms ? ws.at<double>(o_xf) : nullptr);
-    if (rc != MG_OK || n_walks == 0) return rc;
-    MG_HIP_CHECK(hipMemcpyAsync(frames, ws.at<char>(o_frames), frames_b, hipMemcpyDeviceToHost, ctx->stream));
-    if (transforms) MG_HIP_CHECK(hipMemcpyAsync(transforms, ws.at<char>(o_xf), xf_b, hipMemcpyDeviceToHost, ctx->stream));
-    MG_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    return MG_OK;
+    const mg_staged d_lat = ws.in(latents, (size_t)(n_walks * ld) * (dtype == MG_F64 ? 8 : 4));
+    const mg_staged d_times = ws.in(times, (size_t)(n_walks * n_steps * t_cap) * 8);
+    const mg_staged d_frames = ws.inout(frames, (size_t)(n_walks * walk_stride * D) * 8);   // rows no step owns stay the caller's
+    const mg_staged d_xf = ws.out(transforms, (size_t)(n_walks * n_steps * 4) * 8);
+    int rc = ws.upload();
+    if (rc != MG_OK) return rc;
+    rc = mg_walk_frames(n_steps, prims, latent_offset, d_lat.dev<void>(), dtype, n_walks, ld, d_times.dev<double>(), lengths, t_cap, frame_offset, al, sk,
+                        d_frames.dev<double>(), walk_stride, d_xf.dev<double>());
+    if (rc != MG_OK) return rc;
+    return ws.download();
 }

@@ -272,26 +272,17 @@ extern "C" int mg_score_walk_residuals_steps_host(int32_t n_steps, const mg_walk
                       "mg_score_walk_residuals_host: bad arguments");
     MG_WSCORE_REQUIRE(n_samples == 0 || (latents && (residuals || errors || exit_state || step_exits)), "mg_score_walk_residuals_host: NULL pointer");
     mg_context *ctx = steps[0].prim->ctx;
-    const size_t lat_b = (size_t)(n_samples * ld) * (latent_dtype == MG_F64 ? 8 : 4), res_b = residuals ? (size_t)(n_samples * ld_res) * 8 : 0;
-    const size_t err_b = errors ? (size_t)n_samples * 8 : 0, ex_b = exit_state ? (size_t)n_samples * 32 : 0;
-    const size_t st_b = step_exits ? (size_t)n_samples * n_steps * 32 : 0;
     mg_workspace ws(ctx, "mg_score_walk_residuals_host");
-    const size_t o_lat = ws.carve(lat_b), o_res = ws.carve(res_b), o_err = ws.carve(err_b), o_ex = ws.carve(ex_b), o_st = ws.carve(st_b);
-    if (n_samples > 0) {
-        int rc = ws.alloc();
-        if (rc != MG_OK) return rc;
-        MG_HIP_CHECK(hipMemcpyAsync(ws.at<char>(o_lat), latents, lat_b, hipMemcpyHostToDevice, ctx->stream));
-        if (res_b) MG_HIP_CHECK(hipMemcpyAsync(ws.at<char>(o_res), residuals, res_b, hipMemcpyHostToDevice, ctx->stream));
-    }
-    int rc = mg_score_walk_residuals_steps(n_steps, steps, n_samples ? ws.at<void>(o_lat) : nullptr, latent_dtype, n_samples, ld, res_b ? ws.at<double>(o_res) : nullptr,
-                                           ld_res, err_b ? ws.at<double>(o_err) : nullptr, ex_b ? ws.at<double>(o_ex) : nullptr, st_b ? ws.at<double>(o_st) : nullptr);
-    if (rc != MG_OK || n_samples == 0) return rc;
-    if (res_b) MG_HIP_CHECK(hipMemcpyAsync(residuals, ws.at<char>(o_res), res_b, hipMemcpyDeviceToHost, ctx->stream));
-    if (err_b) MG_HIP_CHECK(hipMemcpyAsync(errors, ws.at<char>(o_err), err_b, hipMemcpyDeviceToHost, ctx->stream));
-    if (ex_b) MG_HIP_CHECK(hipMemcpyAsync(exit_state, ws.at<char>(o_ex), ex_b, hipMemcpyDeviceToHost, ctx->stream));
-    if (st_b) MG_HIP_CHECK(hipMemcpyAsync(step_exits, ws.at<char>(o_st), st_b, hipMemcpyDeviceToHost, ctx->stream));
-    MG_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    return MG_OK;
+    const mg_staged d_lat = ws.in(latents, (size_t)(n_samples * ld) * (latent_dtype == MG_F64 ? 8 : 4));
+    const mg_staged d_res = ws.inout(residuals, (size_t)(n_samples * ld_res) * 8);
+    const mg_staged d_err = ws.out(errors, (size_t)n_samples * 8), d_ex = ws.out(exit_state, (size_t)n_samples * 32);
+    const mg_staged d_st = ws.out(step_exits, (size_t)n_samples * n_steps * 32);
+    int rc = ws.upload();
+    if (rc != MG_OK) return rc;
+    rc = mg_score_walk_residuals_steps(n_steps, steps, d_lat.dev<void>(), latent_dtype, n_samples, ld, d_res.dev<double>(), ld_res, d_err.dev<double>(),
+                                       d_ex.dev<double>(), d_st.dev<double>());
+    if (rc != MG_OK) return rc;
+    return ws.download();
 }
 
 extern "C" int mg_score_walk_residuals_host(int32_t n_steps, const mg_walk_score_step *steps, const void *latents, int latent_dtype, int64_t n_samples, int64_t ld,

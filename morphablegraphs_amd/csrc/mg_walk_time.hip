@@ -327,23 +327,16 @@ extern "C" int mg_score_walk_time_host(int32_t n_steps, const mg_walk_time_step 
     mg_context *ctx = steps[0].prim->ctx;
     const size_t lat_b = (size_t)(n_samples * ld) * 8, out_b = (size_t)n_samples * 8;
     mg_workspace ws(ctx, "mg_score_walk_time_host");
-    const size_t o_lat = ws.carve(std::max(lat_b, (size_t)8)), o_obj = ws.carve(out_b), o_err = ws.carve(error ? out_b : 0), o_ll = ws.carve(loglik ? out_b : 0);
+    const mg_staged d_lat = lat_b ? ws.in(latents, lat_b) : ws.room(8);    // (rows without columns still want a pointer)
+    const mg_staged d_obj = ws.out(objective, out_b), d_err = ws.out(error, out_b), d_ll = ws.out(loglik, out_b);
     std::vector<mg_walk_time_step> dsteps(steps, steps + n_steps);
-    std::vector<size_t> o_sp((size_t)n_steps);
-    for (int i = 0; i < n_steps; i++) o_sp[i] = ws.carve((size_t)steps[i].prim->L * 8);
-    int rc = ws.alloc();
+    std::vector<mg_staged> d_sp((size_t)n_steps);
+    for (int i = 0; i < n_steps; i++) d_sp[i] = ws.in(steps[i].spatial_dev, (size_t)steps[i].prim->L * 8);
+    int rc = ws.upload();
     if (rc != MG_OK) return rc;
-    for (int i = 0; i < n_steps; i++) {
-        MG_HIP_CHECK(hipMemcpyAsync(ws.at<char>(o_sp[i]), steps[i].spatial_dev, (size_t)steps[i].prim->L * 8, hipMemcpyHostToDevice, ctx->stream));
-        dsteps[i].spatial_dev = ws.at<double>(o_sp[i]);
-    }
-    if (n_samples > 0 && lat_b) MG_HIP_CHECK(hipMemcpyAsync(ws.at<char>(o_lat), latents, lat_b, hipMemcpyHostToDevice, ctx->stream));
-    rc = mg_score_walk_time(n_steps, dsteps.data(), ws.at<void>(o_lat), latent_dtype, n_samples, ld, n_constraints, constraints, start_keyframe, frame_time,
-                            error_scale, quality_scale, ws.at<double>(o_obj), error ? ws.at<double>(o_err) : nullptr, loglik ? ws.at<double>(o_ll) : nullptr);
-    if (rc != MG_OK || n_samples == 0) return rc;
-    MG_HIP_CHECK(hipMemcpyAsync(objective, ws.at<char>(o_obj), out_b, hipMemcpyDeviceToHost, ctx->stream));
-    if (error) MG_HIP_CHECK(hipMemcpyAsync(error, ws.at<char>(o_err), out_b, hipMemcpyDeviceToHost, ctx->stream));
-    if (loglik) MG_HIP_CHECK(hipMemcpyAsync(loglik, ws.at<char>(o_ll), out_b, hipMemcpyDeviceToHost, ctx->stream));
-    MG_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    return MG_OK;
+    for (int i = 0; i < n_steps; i++) dsteps[i].spatial_dev = d_sp[i].dev<double>();
+    rc = mg_score_walk_time(n_steps, dsteps.data(), d_lat.dev<void>(), latent_dtype, n_samples, ld, n_constraints, constraints, start_keyframe, frame_time,
+                            error_scale, quality_scale, d_obj.dev<double>(), d_err.dev<double>(), d_ll.dev<double>());
+    if (rc != MG_OK) return rc;
+    return ws.download();
 }

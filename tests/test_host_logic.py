@@ -420,6 +420,18 @@ def test_kernel_dispatch_reaches_every_instantiation_once():
     assert done.returncode == 0, done.stdout.decode(errors="replace")
 
 
+def test_item_tables_cut_into_launches():
+    """csrc/mg_items_cut.h states the item-table entry points' host decisions once: the cut of a call's items into launches (item
+    cap, the 2^31 - 1 workgroup bound, wg0, LDS), the workgroup-to-item bisection and the shared-latents search;
+    tests/native/items_check.cpp holds them to a restatement at every edge.  A program of its own, built and run as pack_check
+    is: nothing is loaded into this process."""
+    import subprocess
+    native = os.path.join(ROOT, "tests", "native")
+    subprocess.check_call(["make", "-s", "-C", native, "items_check"])
+    done = subprocess.run([os.path.join(native, "items_check")], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=60)
+    assert done.returncode == 0, done.stdout.decode(errors="replace")
+
+
 def test_local_optimizer_spends_the_references_evaluation_budget():
     """HipLeastSquares hands MINPACK an analytic-looking Jacobian (the batched finite differences), so scipy runs lmder,
     whose maxfev counts residual calls only; the reference runs leastsq WITHOUT Dfun (least_squares.py:50-53), where the L

@@ -11,6 +11,7 @@
 #include <time.h>
 
 #include "mg_internal.h"
+#include "mg_constraint_image.h"
 #include "mg_pack.h"
 #include <dlfcn.h>
 
@@ -47,8 +48,6 @@ extern "C" const char *mg_status_string(int s) {
         default: return "unknown status";
     }
 }
-
-#define MG_REQUIRE(cond, ...) MG_REQUIRE_AS(cond, MG_ERR_INVALID_ARGUMENT, __VA_ARGS__)
 
 // ---------------------------------------------------------------------------------------
 // RCCL, loaded on first use
@@ -594,28 +593,6 @@ extern "C" int mg_profile_get_samples(mg_context *ctx, int slot, float *out_ms, 
 // ---------------------------------------------------------------------------------------
 // float64 host helpers
 // ---------------------------------------------------------------------------------------
-// FITPACK splev.f interval search + fpbspl.f recurrence (scipy.interpolate.splev, ext=0),
-// the arithmetic behind reference motion_spline.py:86,92.
-void mg_basis_row(const double *t, int n, double x, int32_t *i0, double *h) {
-    const int k = 3;
-    int l = k;
-    while (!(x < t[l + 1] || l == n - k - 2)) l++;
-    double hh[4];
-    h[0] = 1.0; h[1] = h[2] = h[3] = 0.0;
-    for (int j = 1; j <= k; j++) {
-        for (int i = 0; i < j; i++) hh[i] = h[i];
-        h[0] = 0.0;
-        for (int i = 1; i <= j; i++) {
-            int li = l + i, lj = li - j;
-            if (t[li] == t[lj]) { h[i] = 0.0; continue; }
-            double f = hh[i - 1] / (t[li] - t[lj]);
-            h[i - 1] = h[i - 1] + f * (t[li] - x);
-            h[i] = f * (x - t[lj]);
-        }
-    }
-    *i0 = l - k;
-}
-
 // lower Cholesky factor; returns false if not positive definite
 static bool mg_cholesky_lower(const double *S, int L, double *c) {
     std::fill(c, c + (size_t)L * L, 0.0);
@@ -1381,18 +1358,22 @@ extern "C" int mg_gmm_sample(mg_primitive *p, int64_t n, const int64_t *counts, 
 }
 
 // ---- constraint sets ---------------------------------------------------------------------
-// A constraint's row of the scorers' parameter table: {type, weight, target[3], ref_dir[3]}.  For the direction constraint the row
-// carries what its residual derives from the target alone -- the unit target (tx, tz) and sqrt(tx^2 + tz^2) -- computed here once per
-// set instead of by every lane for every candidate: the residual's own statements (mg_score_device.h), correctly rounded IEEE
-// square roots and divisions on both sides, no contraction: the same bits.
-static void mg_constraint_par_row(const mg_keyframe_constraint &c, double *q) {
-    q[0] = (double)c.type; q[1] = c.weight_factor;
-    for (int i = 0; i < 3; i++) { q[2 + i] = c.target[i]; q[5 + i] = c.ref_dir[i]; }
-    if (c.type == MG_CONSTRAINT_DIRECTION_2D) {
-        const double tn = std::sqrt(c.target[0] * c.target[0] + c.target[1] * c.target[1]);
-        const double tx = c.target[0] / tn, tz = c.target[1] / tn;
-        q[2] = tx; q[3] = tz; q[4] = std::sqrt(tx * tx + tz * tz);
-    }
+// The set's device tables and the vectors of the image (mg_constraint_image.h) they are uploaded from, in one list: create uploads
+// along it and destroy frees along it.  each(vector member of the image, pointer member of the set) until one fails.
+template <class Each> static int mg_constraint_set_tables(Each each) {
+    int rc = MG_OK;
+    auto next = [&](auto host, auto dev) { if (rc == MG_OK) rc = each(host, dev); };
+    next(&mg_constraint_image::W, &mg_constraint_set::d_W);
+    next(&mg_constraint_image::align, &mg_constraint_set::d_align);
+    next(&mg_constraint_image::pose_tab, &mg_constraint_set::d_pose);
+    next(&mg_constraint_image::bias, &mg_constraint_set::d_bias);
+    next(&mg_constraint_image::par, &mg_constraint_set::d_par);
+    next(&mg_constraint_image::woff, &mg_constraint_set::d_woff);
+    next(&mg_constraint_image::chain_len, &mg_constraint_set::d_chain);
+    next(&mg_constraint_image::choff, &mg_constraint_set::d_choff);
+    next(&mg_constraint_image::wpack, &mg_constraint_set::d_Wpack);
+    next(&mg_constraint_image::bpad, &mg_constraint_set::d_bpad);
+    return rc;
 }
 
 extern "C" int mg_constraint_set_create_full(mg_primitive *p, const mg_skeleton_desc *sk, const mg_keyframe_constraint *cons,
@@ -1400,257 +1381,16 @@ extern "C" int mg_constraint_set_create_full(mg_primitive *p, const mg_skeleton_
                                              const mg_alignment_desc *al, mg_constraint_set **out) {
     MG_REQUIRE(p && out && n >= 0 && (n == 0 || cons) && n_poses >= 0 && (n_poses == 0 || poses), "mg_constraint_set_create: bad arguments");
     *out = nullptr;
-    // animated joints of the skeleton in skeleton order: a pose block is root xyz + one quaternion per slot
-    std::vector<int> slot;
-    int n_slots = 0;
-    if (sk) {
-        slot.assign((size_t)std::max(sk->n_joints, 0), -1);
-        for (int j = 0; j < sk->n_joints; j++)
-            if (sk->quat_channel && sk->quat_channel[j] >= 0) slot[(size_t)j] = n_slots++;
-    }
-    std::vector<double> pose_tab;
-    std::vector<size_t> pose_off((size_t)std::max(n, 1), 0);
-    const int nch = std::min(7, p->D), L = p->L, D = p->D;
-    if (sk) {
-        MG_REQUIRE(sk->n_joints > 0 && sk->parents && sk->offsets && sk->quat_channel, "mg_constraint_set_create_fk: incomplete skeleton");
-        MG_REQUIRE(sk->parents[0] < 0, "mg_constraint_set_create_fk: joint 0 must be the root");
-        for (int j = 0; j < sk->n_joints; j++) {
-            MG_REQUIRE(sk->parents[j] < j, "mg_constraint_set_create_fk: joint %d: parents must precede their children", j);
-            MG_REQUIRE(sk->quat_channel[j] < 0 || sk->quat_channel[j] + 4 <= D,
-                       "mg_constraint_set_create_fk: joint %d: quaternion channel %d outside n_dim = %d", j, sk->quat_channel[j], D);
-        }
-    }
-    // chains (root first) and row counts
-    std::vector<std::vector<int>> chains(n), chains2(n);   // chains2: second joint of a midpoint constraint
-    std::vector<int32_t> woff(n + 2, 0), chain_len(n, 0);
-    std::vector<int> al_chain;   // root .. aligning node, every one of their quaternions turns the heading
-    // (every joint is range-checked before its chain is asked for, and the skeleton's order was checked above: this cannot fail)
-    auto chain_of = [&](int joint, std::vector<int> &ch) { (void)mg_joint_chain(sk ? sk->parents : nullptr, sk ? sk->n_joints : 1, joint, ch); };
-    if (al) {
-        MG_REQUIRE(D >= 7, "mg_constraint_set_create_aligned: alignment needs the root quaternion, n_dim = %d", D);
-        MG_REQUIRE(al->joint == MG_ALIGN_START_POSE || al->joint == 0 || (sk && al->joint > 0 && al->joint < sk->n_joints),
-                   "mg_constraint_set_create_aligned: aligning joint %d needs a skeleton that has it", al->joint);
-        const double hn = std::sqrt(al->heading[0] * al->heading[0] + al->heading[1] * al->heading[1]);
-        MG_REQUIRE(std::isfinite(hn) && hn > 0.0 && std::isfinite(al->position[0]) && std::isfinite(al->position[2]),
-                   "mg_constraint_set_create_aligned: previous heading / position not finite or zero");
-        if (al->joint != MG_ALIGN_START_POSE) chain_of(al->joint, al_chain);   // (the start pose's rotation is given, not derived from a heading)
-        MG_REQUIRE((int)al_chain.size() <= MG_MAX_CHAIN, "mg_constraint_set_create_aligned: chain of %d joints exceeds %d", (int)al_chain.size(), MG_MAX_CHAIN);
-    }
-    for (int c = 0; c < n; c++) {
-        const int type = cons[c].type;
-        MG_REQUIRE(type >= MG_CONSTRAINT_POSITION && type <= MG_CONSTRAINT_VALUE_HEADING,
-                   "mg_constraint_set_create: constraint %d has unknown type %d", c, type);
-        MG_REQUIRE(std::isfinite(cons[c].canonical_keyframe), "mg_constraint_set_create: constraint %d keyframe not finite", c);
-        MG_REQUIRE((type == MG_CONSTRAINT_VALUE_POSITION || type == MG_CONSTRAINT_VALUE_HEADING) ? (cons[c].target[0] == 0.0 || cons[c].target[0] == 2.0 ||
-                   (type == MG_CONSTRAINT_VALUE_POSITION && cons[c].target[0] == 1.0)) : true, "mg_constraint_set_create: constraint %d: value constraints select a component with target[0] = 0, (1,) 2", c);
-        MG_REQUIRE(type == MG_CONSTRAINT_POSITION ? D >= 3 : D >= 7,
-                   "mg_constraint_set_create: constraint %d needs more pose channels than n_dim = %d", c, D);
-        int rows = nch;
-        if (type == MG_CONSTRAINT_JOINT_POSITION) {
-            MG_REQUIRE(sk != nullptr, "mg_constraint_set_create: constraint %d needs a skeleton (mg_constraint_set_create_fk)", c);
-            MG_REQUIRE(cons[c].joint >= 0 && cons[c].joint < sk->n_joints, "mg_constraint_set_create_fk: constraint %d: joint %d out of range", c, cons[c].joint);
-            chain_of(cons[c].joint, chains[c]);
-            int m = (int)chains[c].size() - 1;   // joints below the root on the chain
-            // a point given in the joint's own frame hangs below it like one more joint: the joint's own quaternion turns it
-            if (cons[c].ref_dir[0] != 0.0 || cons[c].ref_dir[1] != 0.0 || cons[c].ref_dir[2] != 0.0) m++;
-            MG_REQUIRE(m <= MG_MAX_CHAIN, "mg_constraint_set_create_fk: constraint %d: chain of %d joints exceeds %d", c, m, MG_MAX_CHAIN);
-            chain_len[c] = m;
-            rows = 3 + 4 * std::max(m, 1);
-        } else if (type == MG_CONSTRAINT_POSE) {
-            MG_REQUIRE(sk != nullptr, "mg_constraint_set_create: constraint %d (pose) needs a skeleton", c);
-            MG_REQUIRE(cons[c].joint >= 0 && cons[c].joint < n_poses, "mg_constraint_set_create: constraint %d refers to pose %d of %d", c, cons[c].joint, n_poses);
-            const mg_pose_constraint &pc = poses[cons[c].joint];
-            MG_REQUIRE(pc.n_points > 0 && pc.n_points <= MG_MAX_POSE_POINTS && pc.joints && pc.points && pc.weights,
-                       "mg_constraint_set_create: pose %d: 1..%d points with joints, points and weights", cons[c].joint, MG_MAX_POSE_POINTS);
-            double sw = 0.0;
-            for (int i = 0; i < pc.n_points; i++) {
-                MG_REQUIRE(pc.joints[i] >= 0 && pc.joints[i] < sk->n_joints, "mg_constraint_set_create: pose %d: joint %d out of range", cons[c].joint, pc.joints[i]);
-                MG_REQUIRE(std::isfinite(pc.weights[i]) && std::isfinite(pc.points[3 * i]) && std::isfinite(pc.points[3 * i + 1]) && std::isfinite(pc.points[3 * i + 2]),
-                           "mg_constraint_set_create: pose %d: point %d not finite", cons[c].joint, i);
-                sw += pc.weights[i];
-            }
-            MG_REQUIRE(sw != 0.0, "mg_constraint_set_create: pose %d: weights sum to zero", cons[c].joint);
-            const int block = 3 + 4 * n_slots;
-            pose_off[(size_t)c] = pose_tab.size();
-            pose_tab.resize(pose_tab.size() + MG_POSE_HDR + (size_t)pc.n_points * MG_POSE_REC, 0.0);
-            double *tb = &pose_tab[pose_off[(size_t)c]];
-            tb[0] = pc.n_points; tb[1] = pc.has_velocity ? 1.0 : 0.0; tb[2] = pc.velocity[0]; tb[3] = pc.velocity[1]; tb[4] = pc.velocity[2];
-            tb[5] = block;
-            for (int i = 0; i < pc.n_points; i++) {
-                double *rec = tb + MG_POSE_HDR + (size_t)i * MG_POSE_REC;
-                rec[0] = pc.points[3 * i]; rec[1] = pc.points[3 * i + 1]; rec[2] = pc.points[3 * i + 2]; rec[3] = pc.weights[i];
-                std::vector<int> ch;
-                chain_of(pc.joints[i], ch);
-                const int m = (int)ch.size() - 1;
-                MG_REQUIRE(m <= MG_MAX_CHAIN, "mg_constraint_set_create: pose %d: chain of %d joints exceeds %d", cons[c].joint, m, MG_MAX_CHAIN);
-                rec[4] = m;
-                mg_chain_links(ch, sk->offsets, [&](int j) { return slot[(size_t)j] >= 0 ? 3 + 4 * slot[(size_t)j] : -1; }, rec + 5);   // channels of the pose block
-            }
-            rows = block * (pc.has_velocity ? 2 : 1);
-        } else if (type == MG_CONSTRAINT_LOOK_AT) {
-            MG_REQUIRE(cons[c].joint == 0 || (sk && cons[c].joint > 0 && cons[c].joint < sk->n_joints),
-                       "mg_constraint_set_create_fk: constraint %d: joint %d needs a skeleton that has it", c, cons[c].joint);
-            chain_of(cons[c].joint, chains[c]);
-            const int m = (int)chains[c].size();       // quaternions root .. joint; the first m - 1 place the joint
-            MG_REQUIRE(m <= MG_MAX_CHAIN, "mg_constraint_set_create_fk: constraint %d: chain of %d joints exceeds %d", c, m, MG_MAX_CHAIN);
-            const double rn = std::sqrt(cons[c].ref_dir[0] * cons[c].ref_dir[0] + cons[c].ref_dir[1] * cons[c].ref_dir[1] + cons[c].ref_dir[2] * cons[c].ref_dir[2]);
-            MG_REQUIRE(std::isfinite(rn) && rn > 0.0, "mg_constraint_set_create: constraint %d: zero reference vector", c);
-            MG_REQUIRE(std::isfinite(cons[c].target[0]) && std::isfinite(cons[c].target[1]) && std::isfinite(cons[c].target[2]),
-                       "mg_constraint_set_create: constraint %d: look-at target not finite", c);
-            chain_len[c] = m;
-            rows = 3 + 4 * m;
-        } else if (type == MG_CONSTRAINT_JOINT_MIDPOINT) {
-            MG_REQUIRE(sk != nullptr, "mg_constraint_set_create: constraint %d needs a skeleton (mg_constraint_set_create_fk)", c);
-            MG_REQUIRE(cons[c].joint >= 0 && cons[c].joint < sk->n_joints && cons[c].joint2 >= 0 && cons[c].joint2 < sk->n_joints,
-                       "mg_constraint_set_create_fk: constraint %d: joints %d, %d out of range", c, cons[c].joint, cons[c].joint2);
-            chain_of(cons[c].joint, chains[c]);
-            chain_of(cons[c].joint2, chains2[c]);
-            const int m = (int)chains[c].size() - 1, m2 = (int)chains2[c].size() - 1;
-            MG_REQUIRE(m <= MG_MAX_CHAIN && m2 <= MG_MAX_CHAIN, "mg_constraint_set_create_fk: constraint %d: chain exceeds %d joints", c, MG_MAX_CHAIN);
-            chain_len[c] = m | (m2 << 16);
-            rows = 3 + 4 * std::max(m, 1) + 4 * std::max(m2, 1);
-        } else if (type == MG_CONSTRAINT_VALUE_HEADING) {
-            MG_REQUIRE(cons[c].joint == 0 || (sk && cons[c].joint > 0 && cons[c].joint < sk->n_joints),
-                       "mg_constraint_set_create_fk: constraint %d: joint %d needs a skeleton that has it", c, cons[c].joint);
-            chain_of(cons[c].joint, chains[c]);
-            const int m = (int)chains[c].size();
-            MG_REQUIRE(m <= MG_MAX_CHAIN, "mg_constraint_set_create_fk: constraint %d: chain of %d joints exceeds %d", c, m, MG_MAX_CHAIN);
-            const double rn = std::sqrt(cons[c].ref_dir[0] * cons[c].ref_dir[0] + cons[c].ref_dir[1] * cons[c].ref_dir[1] + cons[c].ref_dir[2] * cons[c].ref_dir[2]);
-            MG_REQUIRE(std::isfinite(rn) && rn > 0.0, "mg_constraint_set_create: constraint %d: zero reference vector", c);
-            chain_len[c] = m;
-            rows = 4 * m;
-        } else if (type == MG_CONSTRAINT_JOINT_ORIENTATION) {
-            MG_REQUIRE(cons[c].joint == 0 || (sk && cons[c].joint > 0 && cons[c].joint < sk->n_joints),
-                       "mg_constraint_set_create_fk: constraint %d: joint %d needs a skeleton that has it", c, cons[c].joint);
-            chain_of(cons[c].joint, chains[c]);
-            const int m = (int)chains[c].size();       // every quaternion root .. joint turns the vector
-            MG_REQUIRE(m <= MG_MAX_CHAIN, "mg_constraint_set_create_fk: constraint %d: chain of %d joints exceeds %d", c, m, MG_MAX_CHAIN);
-            const double tn = std::sqrt(cons[c].target[0] * cons[c].target[0] + cons[c].target[1] * cons[c].target[1] + cons[c].target[2] * cons[c].target[2]);
-            const double rn = std::sqrt(cons[c].ref_dir[0] * cons[c].ref_dir[0] + cons[c].ref_dir[1] * cons[c].ref_dir[1] + cons[c].ref_dir[2] * cons[c].ref_dir[2]);
-            MG_REQUIRE(std::isfinite(tn) && tn > 0.0 && std::isfinite(rn) && rn > 0.0, "mg_constraint_set_create: constraint %d: zero target or reference vector", c);
-            chain_len[c] = m;
-            rows = 4 * m;
-        }
-        woff[c + 1] = woff[c] + rows;
-    }
-    woff[n + 1] = woff[n] + (al ? 3 + 4 * (int)al_chain.size() : 0);
+    mg_constraint_image im;
+    int rc = mg_constraint_image_build(p->L, p->D, p->KK, p->knots, p->means_, p->Es, sk, cons, n, poses, n_poses, al, im);
+    if (rc != MG_OK) return rc;
     mg_constraint_set *cs = new (std::nothrow) mg_constraint_set();
     if (!cs) return MG_ERR_OUT_OF_MEMORY;
-    cs->prim = p; cs->n = n; cs->nch = nch;
-    const size_t rows_total = (size_t)woff[n + 1];
-    std::vector<double> W(std::max<size_t>(rows_total, 1) * L, 0.0), bias(std::max<size_t>(rows_total, 1), 0.0), par((size_t)std::max(n, 1) * 8, 0.0);
-    std::vector<double> choff((size_t)std::max(n, 1) * 2 * MG_MAX_CHAIN * 3, 0.0);
-    for (int c = 0; c < n; c++) {
-        int32_t i0; double w[4];
-        mg_basis_row(p->knots.data(), (int)p->knots.size(), cons[c].canonical_keyframe, &i0, w);
-        auto fill_row = [&](size_t row, int d) {   // pose channel d at the keyframe as a (1 x L) matrix + bias
-            double b = 0.0;
-            for (int j = 0; j < 4; j++) b = b + w[j] * p->means_[(size_t)(i0 + j) * D + d];
-            bias[row] = b;
-            for (int k = 0; k < L; k++) {
-                double acc = 0.0;
-                for (int j = 0; j < 4; j++) acc = acc + w[j] * p->Es[((size_t)(i0 + j) * D + d) * L + k];
-                W[row * L + k] = acc;
-            }
-        };
-        const size_t r0 = (size_t)woff[c];
-        auto fill_quats = [&](size_t row, const std::vector<int> &chain, int count) {   // (w,x,y,z) of chain[0 .. count-1]
-            for (int i = 0; i < count; i++) {
-                const int ch = sk ? sk->quat_channel[chain[i]] : 3;
-                for (int e = 0; e < 4; e++) {
-                    if (ch >= 0) fill_row(row + 4 * i + e, ch + e);
-                    else bias[row + 4 * i + e] = (e == 0) ? 1.0 : 0.0;   // not animated: identity, zero matrix row
-                }
-            }
-        };
-        auto fill_offsets = [&](int which, const std::vector<int> &chain, int m) {
-            for (int i = 0; i < m; i++)
-                for (int e = 0; e < 3; e++) choff[(((size_t)c * 2 + which) * MG_MAX_CHAIN + i) * 3 + e] = sk->offsets[(size_t)chain[i + 1] * 3 + e];
-        };
-        if (cons[c].type == MG_CONSTRAINT_POSE) {
-            const int block = 3 + 4 * n_slots;
-            const mg_pose_constraint &pc = poses[cons[c].joint];
-            for (int blk = 0; blk < (pc.has_velocity ? 2 : 1); blk++) {
-                if (blk == 1) mg_basis_row(p->knots.data(), (int)p->knots.size(), cons[c].canonical_keyframe + 1.0, &i0, w);   // frame2 = evaluate(t + 1)
-                const size_t rb = r0 + (size_t)blk * block;
-                for (int d = 0; d < 3; d++) fill_row(rb + d, d);
-                for (int j = 0; j < sk->n_joints; j++)
-                    if (slot[(size_t)j] >= 0)
-                        for (int e = 0; e < 4; e++) fill_row(rb + 3 + 4 * slot[(size_t)j] + e, sk->quat_channel[j] + e);
-            }
-        } else if (cons[c].type == MG_CONSTRAINT_JOINT_POSITION && chain_len[c] == (int)chains[c].size()) {
-            // relative point: every quaternion root .. joint, the skeleton's offsets and the point itself as the last link
-            for (int d = 0; d < 3; d++) fill_row(r0 + d, d);
-            const int m = chain_len[c];
-            fill_quats(r0 + 3, chains[c], m);
-            fill_offsets(0, chains[c], m - 1);
-            for (int e = 0; e < 3; e++) choff[(((size_t)c * 2) * MG_MAX_CHAIN + (m - 1)) * 3 + e] = cons[c].ref_dir[e];
-        } else if (cons[c].type == MG_CONSTRAINT_LOOK_AT) {
-            for (int d = 0; d < 3; d++) fill_row(r0 + d, d);
-            fill_quats(r0 + 3, chains[c], chain_len[c]);
-            fill_offsets(0, chains[c], chain_len[c] - 1);
-        } else if (cons[c].type == MG_CONSTRAINT_JOINT_POSITION || cons[c].type == MG_CONSTRAINT_JOINT_MIDPOINT) {
-            for (int d = 0; d < 3; d++) fill_row(r0 + d, d);
-            const int m = chain_len[c] & 0xffff;
-            fill_quats(r0 + 3, chains[c], std::max(m, 1));   // joints 0 .. m-1 (the end joint's own rotation does not move it)
-            fill_offsets(0, chains[c], m);
-            if (cons[c].type == MG_CONSTRAINT_JOINT_MIDPOINT) {
-                const int m2 = chain_len[c] >> 16;
-                fill_quats(r0 + 3 + 4 * std::max(m, 1), chains2[c], std::max(m2, 1));
-                fill_offsets(1, chains2[c], m2);
-            }
-        } else if (cons[c].type == MG_CONSTRAINT_JOINT_ORIENTATION || cons[c].type == MG_CONSTRAINT_VALUE_HEADING) {
-            fill_quats(r0, chains[c], chain_len[c]);
-        } else {
-            for (int d = 0; d < nch; d++) fill_row(r0 + d, d);
-        }
-        double *q = &par[(size_t)c * 8];
-        mg_constraint_par_row(cons[c], q);
-        if (cons[c].type == MG_CONSTRAINT_POSE) q[2] = (double)pose_off[(size_t)c];
-    }
-    std::vector<double> align;
-    if (al) {
-        // the candidate's first control point (new_frames[0] of align_quaternion_frames_automatically): plain rows of E', mean'
-        const size_t r0 = (size_t)woff[n];
-        auto cp0_row = [&](size_t row, int d) {
-            bias[row] = p->means_[d];
-            for (int k = 0; k < L; k++) W[row * L + k] = p->Es[(size_t)d * L + k];
-        };
-        for (int d = 0; d < 3; d++) cp0_row(r0 + d, d);
-        for (size_t i = 0; i < al_chain.size(); i++) {
-            const int ch = sk ? sk->quat_channel[al_chain[i]] : 3;
-            for (int e = 0; e < 4; e++) {
-                if (ch >= 0) cp0_row(r0 + 3 + 4 * i + e, ch + e);
-                else bias[r0 + 3 + 4 * i + e] = (e == 0) ? 1.0 : 0.0;
-            }
-        }
-        const double hn = std::sqrt(al->heading[0] * al->heading[0] + al->heading[1] * al->heading[1]);
-        align = {(double)al_chain.size(), al->heading[0] / hn, al->heading[1] / hn, al->position[0], al->position[2],
-                 al->ref_dir[0], al->ref_dir[1], al->ref_dir[2]};
-        if (al->joint == MG_ALIGN_START_POSE) { align[5] = al->position[1]; align[6] = align[7] = 0.0; }   // heights += position[1]
-    }
-    int rc = mg_upload(p->ctx, W, &cs->d_W);
-    if (rc == MG_OK && al) rc = mg_upload(p->ctx, align, &cs->d_align);
-    if (rc == MG_OK && !pose_tab.empty()) { rc = mg_upload(p->ctx, pose_tab, &cs->d_pose); cs->has_pose = true; }
-    if (rc == MG_OK) rc = mg_upload(p->ctx, bias, &cs->d_bias);
-    if (rc == MG_OK) rc = mg_upload(p->ctx, par, &cs->d_par);
-    if (rc == MG_OK) rc = mg_upload(p->ctx, woff, &cs->d_woff);
-    if (rc == MG_OK) { if (chain_len.empty()) chain_len.push_back(0); rc = mg_upload(p->ctx, chain_len, &cs->d_chain); }
-    if (rc == MG_OK) rc = mg_upload(p->ctx, choff, &cs->d_choff);
-    if (rc == MG_OK && p->KK > 0 && rows_total > 0) {
-        // the set's rows W for channels = X . W^T (mg_pack.h)
-        const int KK = p->KK, RT = (int)((rows_total + 15) / 16);
-        std::vector<double> wpack((size_t)RT * KK * 64), bpad((size_t)RT * 16, 0.0);
-        for (size_t r = 0; r < rows_total; r++) bpad[r] = bias[r];
-        mg_pack_fragments(wpack.data(), RT, KK, [&](int row, int k) { return k < L && (size_t)row < rows_total ? W[(size_t)row * L + k] : 0.0; });
-        cs->RT = RT;
-        cs->rows = (int32_t)rows_total;
-        rc = mg_upload(p->ctx, wpack, &cs->d_Wpack);
-        if (rc == MG_OK) rc = mg_upload(p->ctx, bpad, &cs->d_bpad);
-    }
+    cs->prim = p; cs->n = n; cs->nch = im.nch; cs->RT = im.RT; cs->rows = im.rows; cs->has_pose = im.has_pose; cs->align_joint = im.align_joint;
+    // a table the set does not have (alignment, poses, the MFMA image) stays NULL
+    rc = mg_constraint_set_tables([&](auto host, auto dev) { return (im.*host).empty() ? MG_OK : mg_upload(p->ctx, im.*host, &(cs->*dev)); });
     if (rc != MG_OK) { mg_constraint_set_destroy(cs); return rc; }
     cs->structure.assign(cons, cons + n);
-    cs->align_joint = al ? al->joint : -1;
     *out = cs;
     return MG_OK;
 }
@@ -1670,24 +1410,18 @@ extern "C" int mg_constraint_set_update(mg_constraint_set *cs, const mg_keyframe
             same = o.ref_dir[0] == v.ref_dir[0] && o.ref_dir[1] == v.ref_dir[1] && o.ref_dir[2] == v.ref_dir[2];
         MG_REQUIRE(same, "mg_constraint_set_update: constraint %d differs in type, joint, keyframe or relative point", c);
         if (v.type == MG_CONSTRAINT_JOINT_ORIENTATION || v.type == MG_CONSTRAINT_LOOK_AT) {
-            const double rn = v.ref_dir[0] * v.ref_dir[0] + v.ref_dir[1] * v.ref_dir[1] + v.ref_dir[2] * v.ref_dir[2];
-            const double tn = v.target[0] * v.target[0] + v.target[1] * v.target[1] + v.target[2] * v.target[2];
-            MG_REQUIRE(std::isfinite(rn) && rn > 0.0 && std::isfinite(tn) && (tn > 0.0 || v.type == MG_CONSTRAINT_LOOK_AT),
+            const double tn = mg_norm3(v.target);
+            MG_REQUIRE(mg_nonzero3(v.ref_dir) && std::isfinite(tn) && (tn > 0.0 || v.type == MG_CONSTRAINT_LOOK_AT),
                        "mg_constraint_set_update: constraint %d: zero or non-finite target / reference vector", c);
         }
     }
     std::vector<double> values((size_t)n * 8 + 7, 0.0);   // par [n][8], then entries 1..7 of the alignment record
-    for (int c = 0; c < n; c++) {
-        mg_constraint_par_row(cons[c], &values[(size_t)c * 8]);
-    }
+    for (int c = 0; c < n; c++) mg_constraint_par_row(cons[c], &values[(size_t)c * 8]);
     if (al) {
-        const double hn = std::sqrt(al->heading[0] * al->heading[0] + al->heading[1] * al->heading[1]);
-        MG_REQUIRE(std::isfinite(hn) && hn > 0.0 && std::isfinite(al->position[0]) && std::isfinite(al->position[2]),
-                   "mg_constraint_set_update: previous heading / position not finite or zero");
-        double *q = &values[(size_t)n * 8];
-        q[0] = al->heading[0] / hn; q[1] = al->heading[1] / hn; q[2] = al->position[0]; q[3] = al->position[2];
-        q[4] = al->ref_dir[0]; q[5] = al->ref_dir[1]; q[6] = al->ref_dir[2];
-        if (al->joint == MG_ALIGN_START_POSE) { q[4] = al->position[1]; q[5] = q[6] = 0.0; }
+        double rec[8];
+        int rc = mg_alignment_record("mg_constraint_set_update", al, 0, rec);
+        if (rc != MG_OK) return rc;
+        std::copy(rec + 1, rec + 8, &values[(size_t)n * 8]);
     }
     { int rc = mg_use_device(cs->prim->ctx); if (rc != MG_OK) return rc; }
     // entry 0 of the alignment record, the chain length, is structure and stays
@@ -1709,16 +1443,7 @@ extern "C" int mg_constraint_set_create(mg_primitive *p, const mg_keyframe_const
 extern "C" void mg_constraint_set_destroy(mg_constraint_set *cs) {
     if (!cs) return;
     if (cs->prim) (void)hipStreamSynchronize(cs->prim->ctx->stream);
-    mg_dev_free(cs->prim->ctx, cs->d_W);
-    mg_dev_free(cs->prim->ctx, cs->d_bias);
-    mg_dev_free(cs->prim->ctx, cs->d_par);
-    mg_dev_free(cs->prim->ctx, cs->d_woff);
-    mg_dev_free(cs->prim->ctx, cs->d_chain);
-    mg_dev_free(cs->prim->ctx, cs->d_choff);
-    mg_dev_free(cs->prim->ctx, cs->d_Wpack);
-    mg_dev_free(cs->prim->ctx, cs->d_bpad);
-    mg_dev_free(cs->prim->ctx, cs->d_align);
-    mg_dev_free(cs->prim->ctx, cs->d_pose);
+    (void)mg_constraint_set_tables([&](auto, auto dev) { mg_dev_free(cs->prim->ctx, cs->*dev); return MG_OK; });
     delete cs;
 }
 

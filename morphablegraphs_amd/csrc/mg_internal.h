@@ -9,6 +9,7 @@
 
 #include "../../include/mg_hip.h"
 #include "mg_dispatch.h"
+#include "mg_hostdefs.h"   // mg_set_error, MG_REQUIRE_AS / MG_REQUIRE, MG_POSE_HDR / MG_POSE_REC, mg_basis_row
 
 #define MG_NCAND 16         // candidates per MFMA tile (N of v_mfma_f32_16x16x4_f32)
 #define MG_ROWTILE 16       // coefficient rows per MFMA tile (M)
@@ -19,22 +20,12 @@ enum { MG_PROF_FRAMES = 0, MG_PROF_GMM_LOG_PROB, MG_PROF_SCORE_CONSTRAINTS, MG_P
        MG_PROF_OPTIONS_STEP, MG_PROF_JOINT_TRACKS, MG_PROF_FRAME_CONSTRAINTS, MG_PROF_TRAJECTORY, MG_PROF_CLUSTER_TREE_SEARCH, MG_PROF_WALK_FRAMES,
        MG_PROF_WALK_TIME, MG_PROF_STEP_LENGTHS, MG_PROF_FEATURE_POINTS, MG_PROFILE_SLOTS = MG_PROF_FEATURE_POINTS + 1 };
 
-void mg_set_error(const char *fmt, ...);
 int mg_hip_fail(hipError_t e, const char *what);
 
 #define MG_HIP_CHECK(expr)                                   \
     do {                                                     \
         hipError_t _e = (expr);                              \
         if (_e != hipSuccess) return mg_hip_fail(_e, #expr); \
-    } while (0)
-
-// argument checks of the entry points: set the error text and return `code`
-#define MG_REQUIRE_AS(cond, code, ...) \
-    do {                               \
-        if (!(cond)) {                 \
-            mg_set_error(__VA_ARGS__); \
-            return (code);             \
-        }                              \
     } while (0)
 
 struct mg_event_pair {
@@ -309,10 +300,6 @@ inline mg_score_args mg_score_args_of(const mg_constraint_set *cs, int32_t L) {
     return a;
 }
 
-// Device table of one pose constraint inside d_pose (doubles): header, then one record per point
-#define MG_POSE_HDR 8                            // [0] n_points, [1] has_velocity, [2..4] velocity, [5] rows of one pose block
-#define MG_POSE_REC (5 + 4 * MG_MAX_CHAIN)       // target xyz, weight, chain length m, then m x (quaternion row or -1, offset xyz)
-
 // launchers (each validates nothing: the C-ABI entry points did)
 int mg_launch_frames_mfma(mg_primitive *p, const mg_time_grid *g, const void *lat, int ldt, int64_t B, int64_t ld, float *out, float *logp,
                           int prof_slot = -1, int prof_slot2 = -1);   // prof_slot >= 0: the launch carries its own timing events
@@ -361,9 +348,6 @@ int mg_output_alloc(mg_context *ctx, int64_t bytes, int32_t max_candidates, void
 bool mg_output_free(mg_context *ctx, void *p);
 void mg_output_release_all(mg_context *ctx);
 int mg_device_free_raw(mg_context *ctx, void *p);   // hipFree / virtual-memory release, no arena lookup
-
-// host-side float64 spline basis (FITPACK splev/fpbspl semantics)
-void mg_basis_row(const double *knots, int n_knots, double x, int32_t *i0, double *w4);
 
 // A trajectory constraint's target spline on the device (mg_trajectory.hip; read by mg_frame_constraints.hip as well)
 struct mg_trajectory {

@@ -432,6 +432,18 @@ def test_item_tables_cut_into_launches():
     assert done.returncode == 0, done.stdout.decode(errors="replace")
 
 
+def test_constraint_set_image_decodes():
+    """csrc/mg_constraint_image.h builds a constraint set's device image as plain host code, the per-type rules in one table;
+    tests/native/constraint_image_check.cpp decodes the image of every type at its edges against a restatement of the layout,
+    holds the chain and pose-point limits and pins every refusal's text, code and precedence.  A program of its own, built and
+    run as pack_check is: nothing is loaded into this process."""
+    import subprocess
+    native = os.path.join(ROOT, "tests", "native")
+    subprocess.check_call(["make", "-s", "-C", native, "constraint_image_check"])
+    done = subprocess.run([os.path.join(native, "constraint_image_check")], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=60)
+    assert done.returncode == 0, done.stdout.decode(errors="replace")
+
+
 def test_local_optimizer_spends_the_references_evaluation_budget():
     """HipLeastSquares hands MINPACK an analytic-looking Jacobian (the batched finite differences), so scipy runs lmder,
     whose maxfev counts residual calls only; the reference runs leastsq WITHOUT Dfun (least_squares.py:50-53), where the L

@@ -231,7 +231,8 @@ int mg_context_set_reserved_cus(mg_context *ctx, int32_t n);
  *                             default; MG_ERR_UNSUPPORTED never: a mixture that does not fit LDS falls back to 1) -- identical results
  *   MG_OPT_SCORE_KERNEL       mg_score_constraints on the matrix pipe: 0 = by batch size, 1 = a wave per 16-candidate tile, (candidate,
  *                             constraint) pairs on the lanes, 2 = a wave per 64 candidates, a lane per candidate (from 49 152
- *                             candidates on by default) -- identical results
+ *                             candidates on by default; sets of at most 16 rows only, every other set keeps 1: mg_score_plan) --
+ *                             identical results
  *   MG_OPT_PLACED_HOLD        n > 0: the placement scan holds at most n candidates at once (default: a quarter of the free memory);
  *                             tests use it to make the scan drop candidates while it runs
  *   MG_OPT_TRAJECTORY_LANES   1 = one lane per candidate in the closest-point walks of mg_score_trajectory[_points / ies] whatever the
@@ -760,6 +761,21 @@ int mg_score_constraint_residuals(mg_primitive *prim, const mg_constraint_set *c
  * forms, reference optimization/objective_functions.py:290-380, for a whole batch of concatenated latent vectors). */
 int mg_score_constraint_residuals_chained(mg_primitive *prim, const mg_constraint_set *cs, const void *latents_dev, int latent_dtype,
                                           int64_t n_samples, int64_t ld, const double *align_cand_dev, double *residuals_dev);
+
+/* Which kernel mg_score_constraints, mg_score_constraint_residuals[_chained] and mg_best_candidate launch for n_samples >= 1 candidates
+ * against this set, stated once (mg_score_route_of in csrc/mg_score_route.h) and readable without a launch, under the context's
+ * MG_OPT_SCORE_KERNEL and MG_OPT_FORCE_VALU_SCORE.  rows / row_tiles: the rows of the set's fused keyframe matrices and their 16-row
+ * tiles (0 / 0 for a set without the matrix-pipe image: no constraints, or more than 64 components).  The wide kernel holds ONE row
+ * tile: only sets of at most 16 rows take it, whatever the option or the batch size; every other set takes the tile kernel.
+ * MG_ERR_UNSUPPORTED, with mg_score_constraints' text, where that call reports it.  Launches nothing. */
+#define MG_SCORE_KERNEL_VALU 0   /* mg_score_kernel: a lane per candidate, the constraints dealt over four waves */
+#define MG_SCORE_KERNEL_TILE 1   /* mg_score_mfma_kernel: a wave per 16 candidates */
+#define MG_SCORE_KERNEL_WIDE 2   /* mg_score_mfma64_kernel: a wave per 64 candidates */
+typedef struct mg_score_plan_info {
+    int32_t kernel, lds_opt_in, rows, row_tiles;
+    int64_t lds_bytes, workgroups;
+} mg_score_plan_info;
+int mg_score_plan(const mg_primitive *prim, const mg_constraint_set *cs, int64_t n_samples, mg_score_plan_info *out);
 
 /* The argmin rule of evaluate_samples_using_constraints
  * (reference motion_primitive_generator.py:251-257): FIRST strict minimum, NaN never

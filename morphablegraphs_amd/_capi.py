@@ -87,7 +87,7 @@ EXPORTED_SYMBOLS = [
     "mg_score_constraint_residuals", "mg_objective_error_and_naturalness", "mg_gmm_log_prob_jac", "mg_score_constraint_residuals_host",
     "mg_gmm_log_prob_jac_host", "mg_constraint_set_create_fk", "mg_constraint_set_create_aligned", "mg_constraint_set_create_full", "mg_constraint_set_update", "mg_best_candidate", "mg_best_candidate_host",
     "mg_align_frames", "mg_frame_constraint_width", "mg_score_frame_constraint", "mg_score_frame_constraints", "mg_options_frame_lists", "mg_track_plan_create", "mg_track_plan_destroy", "mg_joint_tracks",
-    "mg_score_constraint_residuals_chained", "mg_option_step", "mg_options_step", "mg_options_step_device_counts", "mg_option_step_rows", "mg_options_step_rows", "mg_gmm_sample_rows", "mg_dist_broadcast",
+    "mg_score_constraint_residuals_chained", "mg_score_plan", "mg_option_step", "mg_options_step", "mg_options_step_device_counts", "mg_option_step_rows", "mg_options_step_rows", "mg_gmm_sample_rows", "mg_dist_broadcast",
     "mg_cluster_tree_create", "mg_cluster_tree_destroy", "mg_cluster_tree_search", "mg_cluster_tree_search_host",
     "mg_cluster_tree_create_kd", "mg_kmeans_segments", "mg_gmm_em_fit",
     "mg_spline_fit_batch", "mg_pca_fit", "mg_pca_project", "mg_pca_backproject",
@@ -162,6 +162,12 @@ class TrajectoryPlanInfo(C.Structure):   # struct mg_trajectory_plan_info
                 ("candidates_per_workgroup", C.c_int32), ("lds_bytes", C.c_int64)]
 
 
+class ScorePlanInfo(C.Structure):   # struct mg_score_plan_info
+    _fields_ = [("kernel", C.c_int32), ("lds_opt_in", C.c_int32), ("rows", C.c_int32), ("row_tiles", C.c_int32), ("lds_bytes", C.c_int64),
+                ("workgroups", C.c_int64)]
+
+
+MG_SCORE_KERNELS = ("valu", "tile", "wide")   # MG_SCORE_KERNEL_*
 MG_TRAJ_KERNELS = ("staged_lds", "staged_global", "stream", "coop8", "coop4", "stream_multi", "coop8_multi", "coop4_multi")   # MG_TRAJ_KERNEL_*
 
 
@@ -359,6 +365,7 @@ def load_library(path=None):
         "mg_best_candidate": [vp, vp, vp, i32, i64, i64, C.POINTER(i64), C.POINTER(dbl)],
         "mg_best_candidate_host": [vp, vp, vp, i32, i64, i64, C.POINTER(i64), C.POINTER(dbl)],
         "mg_score_constraint_residuals_chained": [vp, vp, vp, i32, i64, i64, vp, vp],
+        "mg_score_plan": [vp, vp, i64, vp],
         "mg_option_step": [vp, vp, i64, vp, u64, vp, i32, i64, vp, vp],
         "mg_option_step_rows": [vp, vp, i64, vp, u64, i64, i64, vp, i32, i64, vp, vp],
         "mg_options_step_rows": [i32, vp, vp, i64, vp, vp, i64, i64, vp, i32, vp, vp, vp, i64, vp],
@@ -1943,6 +1950,25 @@ class Primitive(object):
         finally:
             for b in [d_S] + bufs:
                 b.free()
+
+    def score_plan(self, cset, n):
+        """mg_score_plan: what the keyframe scorers launch for n candidates against cset under the context's options -- dict(kernel
+        "valu" | "tile" | "wide", lds_bytes, lds_opt_in, workgroups, rows, row_tiles); launches nothing.  MGError (MG_ERR_UNSUPPORTED)
+        where mg_score_constraints raises it."""
+        info = ScorePlanInfo()
+        _check(self.lib.mg_score_plan(self.handle, cset.handle, int(n), C.byref(info)))
+        return {"kernel": MG_SCORE_KERNELS[info.kernel], "lds_bytes": int(info.lds_bytes), "lds_opt_in": bool(info.lds_opt_in),
+                "workgroups": int(info.workgroups), "rows": int(info.rows), "row_tiles": int(info.row_tiles)}
+
+    def score_constraint_residuals_dev(self, cset, lat_dev, lat_dtype, n, ld, res_dev, align_cand_dev=None):
+        """mg_score_constraint_residuals on device pointers: res_dev (n, cset.n) float64; align_cand_dev (n, 4) float64: the chained
+        form (mg_score_constraint_residuals_chained)."""
+        lc = MG_F64 if np.dtype(lat_dtype) == np.float64 else MG_F32
+        if align_cand_dev is None:
+            _check(self.lib.mg_score_constraint_residuals(self.handle, cset.handle, _dev_ptr(lat_dev), lc, int(n), int(ld), _dev_ptr(res_dev)))
+        else:
+            _check(self.lib.mg_score_constraint_residuals_chained(self.handle, cset.handle, _dev_ptr(lat_dev), lc, int(n), int(ld),
+                                                                  _dev_ptr(align_cand_dev), _dev_ptr(res_dev)))
 
     def score_constraints_dev(self, cset, lat_dev, lat_dtype, n, ld, out_dev, out_dtype=np.float64):
         lc = MG_F64 if np.dtype(lat_dtype) == np.float64 else MG_F32

@@ -9,6 +9,7 @@
 #include "mg_gmm_device.h"
 
 #include "mg_score_device.h"
+#include "mg_score_route.h"
 #include "mg_spline_device.h"
 
 // VALU kernel (fallback for > 64 latent components): one workgroup = 64 candidates (a lane each) x 4 waves that deal
@@ -17,6 +18,7 @@
 // order (the order MotionPrimitiveConstraints.evaluate adds them in).
 #define MG_SC_CANDS 64
 #define MG_SC_WAVES 4
+static_assert(MG_SC_CANDS == 64, "mg_score_route.h states the VALU kernel's LDS and grid for 64 candidates per workgroup");
 template <bool LAT_F64, bool OUT_F64>
 __global__ __launch_bounds__(MG_SC_CANDS *MG_SC_WAVES) void mg_score_kernel(mg_score_args a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -35,6 +37,8 @@ __global__ __launch_bounds__(MG_SC_CANDS *MG_SC_WAVES) void mg_score_kernel(mg_s
     }
     __syncthreads();
     const double *x = lds_x + lane * xs;
+    // a lane past the batch end works on zeros and its residual is dropped; its align_cand row is the last candidate's (there is none of its own)
+    const int64_t cand = b0 + (lane < ncand ? lane : ncand - 1);
     for (int c = wave; c < a.n; c += MG_SC_WAVES) {
         auto channel = [&](int row) {   // one pose channel of this candidate at the keyframe: fma chain over k from the bias
             const double *wr = a.W + (size_t)row * L;
@@ -42,7 +46,7 @@ __global__ __launch_bounds__(MG_SC_CANDS *MG_SC_WAVES) void mg_score_kernel(mg_s
             for (int k = 0; k < L; k++) acc = fma(wr[k], x[k], acc);
             return acc;
         };
-        lds_r[c * MG_SC_CANDS + lane] = mg_constraint_residual(a, c, channel, b0 + lane);
+        lds_r[c * MG_SC_CANDS + lane] = mg_constraint_residual(a, c, channel, cand);
     }
     __syncthreads();
     if (a.res)   // (n_samples, n) row-major: consecutive threads write consecutive constraints of a candidate
@@ -93,7 +97,8 @@ __global__ __launch_bounds__(256) void mg_score_mfma_kernel(mg_score_args a, con
     for (int e = lane; e < 16 * a.n; e += 64) {
         const int cand = e & 15, c = e >> 4;
         const double *v = vals + cand * vs;
-        resid[c * 16 + cand] = mg_constraint_residual(a, c, [&](int row) { return v[row]; }, b0 + cand);
+        // (a row past the batch end holds the last candidate's channels, mg_gmm_load_x; it takes that candidate's align_cand row too)
+        resid[c * 16 + cand] = mg_constraint_residual(a, c, [&](int row) { return v[row]; }, b0 + (cand < ncand ? cand : ncand - 1));
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     if (a.res)
@@ -165,58 +170,67 @@ __global__ __launch_bounds__(256) void mg_score_mfma64_kernel(mg_score_args a, c
     }
 }
 
-#define MG_SCORE_WIDE_MIN_B 49152   // measured crossover (tools/probes/score_kernel_ab.py): below, the tile kernel's eight waves per SIMD hide more latency than its idle lanes cost
-
+// The kernel, its LDS, the opt-in and the grid are mg_score_route_of's (mg_score_route.h): this only launches what it says.
 template <int KK>
-static int mg_launch_score_mfma_kk(mg_primitive *p, const mg_constraint_set *cs, const mg_score_args &a, bool lf, bool of) {
+static int mg_launch_score_mfma_kk(mg_primitive *p, const mg_constraint_set *cs, const mg_score_args &a, bool lf, bool of, const mg_score_route &r) {
     hipStream_t st = p->ctx->stream;
-    const int kernel_opt = p->ctx->opt[MG_OPT_SCORE_KERNEL];   // 0: by batch size, 1: 16-candidate waves, 2: 64-candidate waves
-    const bool wide = kernel_opt == 2 || (kernel_opt == 0 && a.B >= MG_SCORE_WIDE_MIN_B);
-    if (wide) {
-        const size_t lds = (size_t)4 * 64 * (cs->RT * 16 + 1) * 8;
-        if (lds <= 64 * 1024) {
-            const int64_t grid = (a.B + 255) / 256;
-            if (grid > 0x7fffffff) return MG_ERR_UNSUPPORTED;
-            mg_dispatch_flags(lf, of, [&](auto LAT_F64, auto OUT_F64) {
-                hipLaunchKernelGGL((mg_score_mfma64_kernel<KK, LAT_F64, OUT_F64>), dim3((int)grid), dim3(256), lds, st, a, cs->d_Wpack, cs->d_bpad, cs->RT);
-            });
-            MG_HIP_CHECK(hipGetLastError());
-            return MG_OK;
-        }
+    if (r.kernel == MG_SCORE_KERNEL_WIDE) {
+        mg_dispatch_flags(lf, of, [&](auto LAT_F64, auto OUT_F64) {
+            hipLaunchKernelGGL((mg_score_mfma64_kernel<KK, LAT_F64, OUT_F64>), dim3((int)r.grid), dim3(256), r.lds, st, a, cs->d_Wpack, cs->d_bpad, cs->RT);
+        });
+        MG_HIP_CHECK(hipGetLastError());
+        return MG_OK;
     }
-    const size_t lds = (size_t)4 * (16 * (cs->RT * 16 + 1) + (size_t)std::max(cs->n, 1) * 16) * 8;
-    if (lds > 150 * 1024) return MG_ERR_UNSUPPORTED;
-    const int64_t grid = (a.B + 63) / 64;
-    if (grid > 0x7fffffff) return MG_ERR_UNSUPPORTED;
     return mg_dispatch_flags(lf, of, [&](auto LAT_F64, auto OUT_F64) -> int {
         const auto kernel = mg_score_mfma_kernel<KK, LAT_F64, OUT_F64>;
-        if (lds > 64 * 1024) MG_HIP_CHECK(mg_lds_opt_in(160 * 1024, kernel));
-        hipLaunchKernelGGL(kernel, dim3((int)grid), dim3(256), lds, st, a, cs->d_Wpack, cs->d_bpad, cs->RT);
+        if (r.opt_in) MG_HIP_CHECK(mg_lds_opt_in(160 * 1024, kernel));
+        hipLaunchKernelGGL(kernel, dim3((int)r.grid), dim3(256), r.lds, st, a, cs->d_Wpack, cs->d_bpad, cs->RT);
         MG_HIP_CHECK(hipGetLastError());
         return MG_OK;
     });
+}
+
+static int mg_score_route_for(const mg_primitive *p, const mg_constraint_set *cs, int64_t B, mg_score_route *r) {
+    return mg_score_route_of(p->KK, p->L, cs->RT, cs->n, B, p->ctx->opt[MG_OPT_SCORE_KERNEL], p->ctx->opt[MG_OPT_FORCE_VALU_SCORE], cs->d_Wpack != nullptr, r);
+}
+static int mg_score_refusal(const mg_primitive *p, const mg_constraint_set *cs, int why) {
+    if (why == MG_SCORE_REFUSED_LDS) mg_set_error("mg_score_constraints: n_components %d x %d constraints too large for LDS", p->L, cs->n);
+    else mg_set_error("mg_score_constraints: too many samples");
+    return MG_ERR_UNSUPPORTED;
 }
 
 int mg_launch_score(mg_primitive *p, const mg_constraint_set *cs, const void *lat, int ldt, int64_t B, int64_t ld, void *out, int odt, double *res, const double *align_cand) {
     mg_score_args a = mg_score_args_of(cs, p->L);
     a.res = res; a.align_cand = align_cand; a.lat = lat; a.out = out; a.B = B; a.ld = ld;
     const bool lf = ldt == MG_F64, of = odt == MG_F64;
-    if (cs->d_Wpack && !p->ctx->opt[MG_OPT_FORCE_VALU_SCORE]) {
-        const int rc = mg_dispatch_kk(p->KK, (int)MG_ERR_UNSUPPORTED, [&](auto KK) { return mg_launch_score_mfma_kk<KK>(p, cs, a, lf, of); });
-        if (rc != MG_ERR_UNSUPPORTED) return rc;
-    }
-    size_t lds = ((size_t)MG_SC_CANDS * (p->L + 1) + (size_t)std::max(cs->n, 1) * MG_SC_CANDS) * 8;
-    if (lds > 150 * 1024) { mg_set_error("mg_score_constraints: n_components %d x %d constraints too large for LDS", p->L, cs->n); return MG_ERR_UNSUPPORTED; }
-    int64_t grid = (B + MG_SC_CANDS - 1) / MG_SC_CANDS;
-    if (grid > 0x7fffffff) { mg_set_error("mg_score_constraints: too many samples"); return MG_ERR_UNSUPPORTED; }
+    mg_score_route r;
+    const int why = mg_score_route_for(p, cs, B, &r);
+    if (why != MG_SCORE_ROUTE_OK) return mg_score_refusal(p, cs, why);
+    if (r.kernel != MG_SCORE_KERNEL_VALU)
+        return mg_dispatch_kk(p->KK, (int)MG_ERR_UNSUPPORTED, [&](auto KK) { return mg_launch_score_mfma_kk<KK>(p, cs, a, lf, of, r); });
     hipStream_t st = p->ctx->stream;
     return mg_dispatch_flags(lf, of, [&](auto LAT_F64, auto OUT_F64) -> int {
         const auto kernel = mg_score_kernel<LAT_F64, OUT_F64>;
-        if (lds > 64 * 1024) MG_HIP_CHECK(mg_lds_opt_in(160 * 1024, kernel));
-        hipLaunchKernelGGL(kernel, dim3((int)grid), dim3(MG_SC_CANDS * MG_SC_WAVES), lds, st, a);
+        if (r.opt_in) MG_HIP_CHECK(mg_lds_opt_in(160 * 1024, kernel));
+        hipLaunchKernelGGL(kernel, dim3((int)r.grid), dim3(MG_SC_CANDS * MG_SC_WAVES), r.lds, st, a);
         MG_HIP_CHECK(hipGetLastError());
         return MG_OK;
     });
+}
+
+// What the next mg_score_constraints / mg_score_constraint_residuals[_chained] / mg_best_candidate call of n_samples candidates would
+// take under the context's options, without a launch.
+extern "C" int mg_score_plan(const mg_primitive *p, const mg_constraint_set *cs, int64_t n_samples, mg_score_plan_info *out) {
+    if (!p || !cs || cs->prim != p || !out || n_samples < 1) {
+        mg_set_error("mg_score_plan: bad arguments");
+        return MG_ERR_INVALID_ARGUMENT;
+    }
+    mg_score_route r;
+    const int why = mg_score_route_for(p, cs, n_samples, &r);
+    if (why != MG_SCORE_ROUTE_OK) return mg_score_refusal(p, cs, why);
+    out->kernel = r.kernel; out->lds_opt_in = r.opt_in ? 1 : 0; out->rows = cs->rows; out->row_tiles = cs->RT;
+    out->lds_bytes = (int64_t)r.lds; out->workgroups = r.grid;
+    return MG_OK;
 }
 
 // New constraint parameters for an existing set (mg_constraint_set_update): the values travel as kernel arguments,

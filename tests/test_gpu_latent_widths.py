@@ -449,7 +449,8 @@ SAMPLER_RATIOS = []
 def _score_family(ctx, prim, data, s, S):
     """Root position, 2-D direction and (D = 79) a joint_position constraint, local and aligned to a start pose:
     MG_OPT_SCORE_KERNEL 1 / 2 and the VALU scorer bit-identical, errors against the oracle; the one-launch objective equals the
-    two separate calls where it carries the set."""
+    two separate calls where it carries the set.  Three root constraints own 21 rows, more than the 16 the wide kernel takes: option 2
+    runs the tile kernel here, as the plan asserted per option states (the wide kernel: tests/test_gpu_score_shapes.py)."""
     from morphablegraphs_amd.candidate_scoring import alignment_from_start_pose
     L, F, D = s["L"], prim.n_canonical_frames, prim.n_dim
     op = orc.OraclePrimitive(data)
@@ -478,6 +479,9 @@ def _score_family(ctx, prim, data, s, S):
                 outs = []
                 for opt, val in ((_capi.MG_OPT_SCORE_KERNEL, 1), (_capi.MG_OPT_SCORE_KERNEL, 2), (_capi.MG_OPT_FORCE_VALU_SCORE, 1)):
                     ctx.set_option(opt, val)
+                    plan = prim.score_plan(cset, len(X))
+                    assert plan["kernel"] == ("tile" if prim.mfma_supported and opt == _capi.MG_OPT_SCORE_KERNEL else "valu"), (s["name"], opt, val, plan)
+                    assert not prim.mfma_supported or plan["rows"] >= 21
                     outs.append((prim.score_constraints(cset, X), prim.score_constraint_residuals(cset, X)))
                     ctx.set_option(opt, 0)
                 for e, r in outs[1:]:

@@ -1087,10 +1087,11 @@ def test_start_pose_alignment_branch(ctx):
 
 
 def test_wide_scoring_kernel_is_bit_identical(ctx):
-    """mg_score_constraints' large-batch kernel (a wave per 64 candidates, a lane per candidate walking the constraints in order)
-    against the tile kernel (a wave per 16 candidates, (candidate, constraint) pairs on the lanes) and the VALU kernel: the same
-    errors and residual matrices bit for bit, for ragged batches, both latent types, forward-kinematics constraints and candidates
-    aligned to a start pose."""
+    """MG_OPT_SCORE_KERNEL 1 against 2 and the VALU kernel: the same errors and residual matrices bit for bit, for ragged batches, both
+    latent types, forward-kinematics constraints and candidates aligned to a start pose.  These five constraints own dozens of rows
+    and the wide kernel (a wave per 64 candidates) takes sets of at most 16: option 2 falls through to the tile kernel here, as the
+    plan asserted below states, so this compares the tile kernel under both options with the VALU kernel.  The wide kernel itself is
+    covered by tests/test_gpu_score_shapes.py."""
     from morphablegraphs_amd.candidate_scoring import alignment_from_start_pose
     joints, animated = synthetic.make_skeleton()
     sk = _capi.Skeleton(joints, animated)
@@ -1109,6 +1110,8 @@ def test_wide_scoring_kernel_is_bit_identical(ctx):
                 out = []
                 for mode in (1, 2):
                     ctx.set_option(_capi.MG_OPT_SCORE_KERNEL, mode)
+                    plan = prim.score_plan(cset, B)
+                    assert plan["kernel"] == "tile" and plan["rows"] > 16 and plan["row_tiles"] > 1, (mode, plan)
                     out.append((prim.score_constraints(cset, S.astype(dt), dtype=np.float64), prim.score_constraints(cset, S.astype(dt), dtype=np.float32),
                                 prim.score_constraint_residuals(cset, S.astype(dt))))
                 ctx.set_option(_capi.MG_OPT_SCORE_KERNEL, 0)
@@ -1116,6 +1119,7 @@ def test_wide_scoring_kernel_is_bit_identical(ctx):
                     np.testing.assert_array_equal(a.view(np.uint8), b.view(np.uint8))
                 if B == 4099:
                     ctx.set_option(_capi.MG_OPT_FORCE_VALU_SCORE, 1)
+                    assert prim.score_plan(cset, B)["kernel"] == "valu"
                     np.testing.assert_array_equal(prim.score_constraint_residuals(cset, S.astype(dt)), out[1][2])
                     ctx.set_option(_capi.MG_OPT_FORCE_VALU_SCORE, 0)
         cset.close()

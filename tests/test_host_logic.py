@@ -444,6 +444,18 @@ def test_constraint_set_image_decodes():
     assert done.returncode == 0, done.stdout.decode(errors="replace")
 
 
+def test_keyframe_scorers_route_is_the_restated_one():
+    """csrc/mg_score_route.h states once which kernel the keyframe scorers launch (VALU / tile / wide), its LDS, the opt-in and the
+    grid; tests/native/score_route_check.cpp holds it to a restatement over a dense grid of k-step counts, row tiles, constraint
+    counts, batch sizes and options, up to the workgroup bound.  A program of its own, built and run as pack_check is: nothing is
+    loaded into this process."""
+    import subprocess
+    native = os.path.join(ROOT, "tests", "native")
+    subprocess.check_call(["make", "-s", "-C", native, "score_route_check"])
+    done = subprocess.run([os.path.join(native, "score_route_check")], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=60)
+    assert done.returncode == 0, done.stdout.decode(errors="replace")
+
+
 def test_local_optimizer_spends_the_references_evaluation_budget():
     """HipLeastSquares hands MINPACK an analytic-looking Jacobian (the batched finite differences), so scipy runs lmder,
     whose maxfev counts residual calls only; the reference runs leastsq WITHOUT Dfun (least_squares.py:50-53), where the L

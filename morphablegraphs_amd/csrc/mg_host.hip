@@ -12,7 +12,7 @@
 
 #include "mg_internal.h"
 #include "mg_constraint_image.h"
-#include "mg_pack.h"
+#include "mg_primitive_image.h"
 #include <dlfcn.h>
 
 // ---------------------------------------------------------------------------------------
@@ -591,25 +591,8 @@ extern "C" int mg_profile_get_samples(mg_context *ctx, int slot, float *out_ms, 
 }
 
 // ---------------------------------------------------------------------------------------
-// float64 host helpers
+// device copies of the host-built images (mg_primitive_image.h, mg_constraint_image.h)
 // ---------------------------------------------------------------------------------------
-// lower Cholesky factor; returns false if not positive definite
-static bool mg_cholesky_lower(const double *S, int L, double *c) {
-    std::fill(c, c + (size_t)L * L, 0.0);
-    for (int j = 0; j < L; j++) {
-        double sum = S[j * L + j];
-        for (int p = 0; p < j; p++) sum -= c[j * L + p] * c[j * L + p];
-        if (!(sum > 0.0) || !std::isfinite(sum)) return false;
-        c[j * L + j] = std::sqrt(sum);
-        for (int i = j + 1; i < L; i++) {
-            double s2 = S[i * L + j];
-            for (int p = 0; p < j; p++) s2 -= c[i * L + p] * c[j * L + p];
-            c[i * L + j] = s2 / c[j * L + j];
-        }
-    }
-    return true;
-}
-
 template <typename T>
 static int mg_upload(mg_context *ctx, const std::vector<T> &h, T **d) {
     *d = nullptr;
@@ -627,179 +610,41 @@ static int mg_upload(mg_context *ctx, const std::vector<T> &h, T **d) {
 // ---------------------------------------------------------------------------------------
 // time grids
 // ---------------------------------------------------------------------------------------
-static void mg_free_grid_device(mg_time_grid *g) {
-    mg_context *ctx = g->prim->ctx;
-    mg_dev_free(ctx, g->d_i0);
-    mg_dev_free(ctx, g->d_w);
-    mg_dev_free(ctx, g->d_w32);
-    mg_dev_free(ctx, g->d_rootm);
-    g->d_rootm = nullptr;
-    mg_dev_free(ctx, g->d_wtap);
-    g->d_wtap = nullptr;
-    mg_dev_free(ctx, g->d_chunks);
-    g->d_i0 = nullptr; g->d_w = nullptr; g->d_w32 = nullptr; g->d_chunks = nullptr;
+// A grid's device tables and the vectors of its image (mg_primitive_image.h) they are uploaded from, in one list: create uploads
+// along it and destroy frees along it.  A table that is empty is allocated all the same (mg_upload's 16-byte floor).
+template <class Each> static int mg_grid_tables(Each each) {
+    int rc = MG_OK;
+    auto next = [&](auto host, auto dev) { if (rc == MG_OK) rc = each(host, dev); };
+    next(&mg_grid_image::i0, &mg_time_grid::d_i0);
+    next(&mg_grid_image::w, &mg_time_grid::d_w);
+    next(&mg_grid_image::w32, &mg_time_grid::d_w32);
+    next(&mg_grid_image::rootm, &mg_time_grid::d_rootm);
+    next(&mg_grid_image::chunks, &mg_time_grid::d_chunks);
+    next(&mg_grid_image::wtap, &mg_time_grid::d_wtap);
+    return rc;
 }
 
-static int mg_round_stride(int nlocal) {
-    // floats per candidate in the LDS coefficient image: == 4 (mod 32) makes the
-    // 16-candidate ds_write_b128 of an MFMA accumulator tile conflict-free.
-    int s = nlocal;
-    while (s % 32 != 4) s++;
-    return s;
+static void mg_grid_free(mg_time_grid *g) {
+    (void)mg_grid_tables([&](auto, auto dev) { mg_dev_free(g->prim->ctx, g->*dev); return MG_OK; });
+    delete g;
 }
 
-// LDS of the persistent kernel: two buffers (coefficient image + float32 root outputs),
-// three per-sample table sets, two float64 root images.
-static int mg_lds_bytes(const mg_primitive *p, int stride, int wi, int nbuf = 2, int max_nt = MG_MAX_NT) {
-    int buf = (MG_NCAND * stride * 4 + 255) / 256 * 256;
-    int rout = MG_RO_BYTES_N(max_nt);
-    int tabs = max_nt * 16 + max_nt * 4;
-    int root = MG_NCAND * (wi * p->nroot + 1) * 8;
-    return nbuf * (buf + rout + tabs) + root + 128;
-}
-
-// Split the grid into chunks (runs of consecutive time samples) whose coefficient window
-// fits the LDS budget.
-static void mg_plan_chunks(mg_primitive *p, mg_time_grid *g) {
-    const int Dp = p->Dp;
-    g->chunks.clear();
-    g->mfma_ok = false;
-    if (p->KK == 0 || g->T == 0 || (p->D - p->nroot + 3) / 4 + 1 > 64) return;   // one row group must fit a wave
-    // widest window (<= 8 basis functions) whose double-buffered image fits one CU's 160 KiB of LDS
-    const int budget1 = 160 * 1024;
-    auto fits = [&](int wi, int budget) {
-        int nlocal = ((wi * Dp + 15) / 16 + 1) * 16;
-        return mg_lds_bytes(p, mg_round_stride(nlocal), wi) <= budget;
-    };
-    int max_nt = MG_MAX_NT;
-    if (const int o = p->ctx->opt[MG_OPT_CHUNK_SAMPLES]) max_nt = std::max(1, std::min(MG_MAX_NT, o));
-    auto count_chunks = [&](int w) {   // greedy split under a window of w basis functions
-        int n = 0;
-        for (int a0 = 0; a0 < g->T; n++) {
-            int imin = g->i0[a0], imax = g->i0[a0], b = a0 + 1;
-            while (b < g->T && b - a0 < max_nt) {
-                int lo = std::min(imin, g->i0[b]), hi = std::max(imax, g->i0[b]);
-                if (hi - lo + 4 > w) break;
-                imin = lo; imax = hi;
-                b++;
-            }
-            a0 = b;
-        }
-        return n;
-    };
-    // Fewer, longer chunks win (each unit has fixed costs -- measured: 6 -> 4 chunks of the 'walk' grid -3 %, while a
-    // two-slot ring instead of three costs 0.5 %): the narrowest window that reaches the smallest chunk count among
-    // the windows whose two-slot ring fits LDS.
-    int W = 0, best_n = 0;
-    for (int w = MG_MAX_WI; w >= 4; w--) {
-        if (!fits(w, budget1)) continue;
-        const int n = count_chunks(w);
-        if (W == 0 || n <= best_n) { W = w; best_n = n; }
-    }
-    if (W == 0) return;  // n_dim too large for the LDS-staged kernel
-    if (const int o = p->ctx->opt[MG_OPT_CHUNK_WINDOW]) W = std::max(4, std::min(W, o));
-    // the chunk count of the greedy split, evened out
-    const int n_greedy = count_chunks(W);
-    int a = 0;
-    int max_stride = 0, max_wi = 0, longest = 0;
-    while (a < g->T) {
-        int imin = g->i0[a], imax = g->i0[a];
-        int b = a + 1;
-        const int left = std::max(1, n_greedy - (int)g->chunks.size());
-        const int target = std::min(max_nt, (g->T - a + left - 1) / left);
-        while (b < g->T && b - a < target) {
-            int lo = std::min(imin, g->i0[b]), hi = std::max(imax, g->i0[b]);
-            if (hi - lo + 4 > W) break;
-            imin = lo; imax = hi;
-            b++;
-        }
-        mg_chunk c;
-        memset(&c, 0, sizeof(c));
-        c.t0 = a;
-        c.nT = b - a;
-        c.imin = imin;
-        c.wi = imax - imin + 4;
-        c.rt0 = (imin * Dp) / 16;
-        int rt1 = ((imin + c.wi) * Dp + 15) / 16;
-        c.ntiles = rt1 - c.rt0;
-        c.rrt0 = (imin * p->nroot) / 16;
-        c.nrt = ((imin + c.wi) * p->nroot + 15) / 16 - c.rrt0;
-        g->chunks.push_back(c);
-        max_stride = std::max(max_stride, mg_round_stride(c.ntiles * 16));
-        max_wi = std::max(max_wi, c.wi);
-        longest = std::max(longest, c.nT);
-        a = b;
-    }
-    g->stride = max_stride;
-    g->max_wi = max_wi;
-    g->max_nt = (longest + 15) / 16 * 16;
-    // a third ring slot lets the producers run a full unit ahead of the slowest consumer wave
-    g->nbuf = mg_lds_bytes(p, max_stride, max_wi, 3, g->max_nt) <= budget1 ? 3 : 2;
-    if (p->ctx->opt[MG_OPT_RING_SLOTS] == 2) g->nbuf = 2;
-    g->lds_bytes = mg_lds_bytes(p, max_stride, max_wi, g->nbuf, g->max_nt);
-    g->n_chunks = (int32_t)g->chunks.size();
-    g->mfma_ok = g->lds_bytes <= budget1;
-    // the chunk-stationary kernel: two ring slots, ONE table set, the window's mean' rows; its row producers hold the
-    // window's eigenvector fragments in registers
-    g->max_tiles = 0;
-    for (const mg_chunk &c : g->chunks) g->max_tiles = std::max(g->max_tiles, c.ntiles);
-    {
-        const int buf = (MG_NCAND * max_stride * 4 + 255) / 256 * 256;
-        g->cs_lds_bytes = 2 * (buf + MG_RO_BYTES_N(g->max_nt)) + g->max_nt * 20 + MG_NCAND * (max_wi * p->nroot + 1) * 8 + g->max_tiles * 64 +
-                          MG_TAP_FT * MG_TAP_KS * 64 * 8 + 512 + 2 * p->KK * 64 * 4 + 256;   // + tap weights, root means, two latent tiles, 64 counters
-        g->cs_ok = g->mfma_ok && g->max_tiles <= mg_cs_max_tiles(p->KK) && g->cs_lds_bytes <= budget1 && (int)g->chunks.size() <= MG_ARG_CHUNKS;
-    }
-}
-
-static int mg_grid_build(mg_primitive *p, mg_time_grid *g, const double *times, int32_t T,
-                         const int32_t *i0_override, const double *w_override) {
-    g->prim = p;
-    g->T = T;
-    g->times.assign(times, times + T);
-    g->i0.resize(T);
-    g->w.resize((size_t)T * 4);
-    for (int f = 0; f < T; f++) {
-        if (i0_override) {
-            g->i0[f] = i0_override[f];
-            for (int j = 0; j < 4; j++) g->w[4 * f + j] = w_override[4 * f + j];
-        } else {
-            mg_basis_row(p->knots.data(), (int)p->knots.size(), times[f], &g->i0[f], &g->w[4 * f]);
-        }
-    }
-    mg_plan_chunks(p, g);
-    std::vector<float> w32(g->w.size());
-    for (size_t q = 0; q < g->w.size(); q++) w32[q] = (float)g->w[q];
+// A grid of p's: the image under the context's options, the upload; the plan and the host tables move into the handle
+static int mg_grid_create(mg_primitive *p, const double *times, int32_t T, const int32_t *i0_override, const double *w_override, bool owned,
+                          mg_time_grid **out) {
+    const int32_t *opt = p->ctx->opt;
+    mg_grid_image im;
+    mg_grid_image_build(*p, times, T, i0_override, w_override, opt[MG_OPT_CHUNK_SAMPLES], opt[MG_OPT_CHUNK_WINDOW], opt[MG_OPT_RING_SLOTS],
+                        mg_cs_max_tiles(p->KK), im);
     MG_HIP_CHECK(hipSetDevice(p->ctx->device));
-    int rc;
-    if ((rc = mg_upload(p->ctx, g->i0, &g->d_i0)) != MG_OK) return rc;
-    if ((rc = mg_upload(p->ctx, g->w, &g->d_w)) != MG_OK) return rc;
-    if ((rc = mg_upload(p->ctx, w32, &g->d_w32)) != MG_OK) return rc;
-    {   // the root channels' mean part (mean/delta split, mg_primitive_root_mode): M[f][d] = w0 m0, fma(w1, m1, .), fma(w2, m2, .),
-        // fma(w3, m3, .) in float64 with m_j = mean'[(i0[f] + j) D + d]; Mhi = (float)M, Mlo = (float)(M - Mhi)
-        std::vector<float> rootm((size_t)std::max(T, 1) * 8, 0.0f);
-        for (int f = 0; f < T; f++)
-            for (int d = 0; d < p->nroot; d++) {
-                const double *m = &p->means_[(size_t)g->i0[f] * p->D + d];
-                double M = g->w[4 * (size_t)f] * m[0];
-                for (int j = 1; j < 4; j++) M = std::fma(g->w[4 * (size_t)f + j], m[(size_t)j * p->D], M);
-                const float hi = (float)M;
-                rootm[8 * (size_t)f + d] = hi;                              // {Mhi[0..2], Mlo[0], Mlo[1], Mlo[2], 0, 0}: the sweep reads
-                rootm[8 * (size_t)f + 3 + d] = (float)(M - (double)hi);    // a float4 and a float2 per sample, every element used
-            }
-        if ((rc = mg_upload(p->ctx, rootm, &g->d_rootm)) != MG_OK) return rc;
-    }
-    if ((rc = mg_upload(p->ctx, g->chunks, &g->d_chunks)) != MG_OK) return rc;
-    {   // banded tap weights of every chunk (mg_pack.h): W[f][m] = w[f][m - (i0[f] - imin)] inside the band
-        std::vector<double> wtap(std::max<size_t>(g->chunks.size(), 1) * MG_TAP_FT * MG_TAP_KS * 64, 0.0);
-        for (size_t c = 0; c < g->chunks.size(); c++) {
-            const mg_chunk &ck = g->chunks[c];
-            mg_pack_fragments(&wtap[c * MG_TAP_FT * MG_TAP_KS * 64], MG_TAP_FT, MG_TAP_KS, [&](int f, int m) {
-                const int j = f < ck.nT ? m - (g->i0[ck.t0 + f] - ck.imin) : -1;
-                return j >= 0 && j < 4 ? g->w[4 * (size_t)(ck.t0 + f) + j] : 0.0;
-            });
-        }
-        if ((rc = mg_upload(p->ctx, wtap, &g->d_wtap)) != MG_OK) return rc;
-    }
+    mg_time_grid *g = new (std::nothrow) mg_time_grid();
+    if (!g) return MG_ERR_OUT_OF_MEMORY;
+    g->prim = p;
+    g->owned_by_prim = owned;
+    const int rc = mg_grid_tables([&](auto host, auto dev) { return mg_upload(p->ctx, im.*host, &(g->*dev)); });
+    if (rc != MG_OK) { mg_grid_free(g); return rc; }
+    static_cast<mg_grid_plan &>(*g) = std::move(im);
+    *out = g;
     return MG_OK;
 }
 
@@ -807,18 +652,12 @@ extern "C" int mg_time_grid_create(mg_primitive *prim, const double *times, int3
     MG_REQUIRE(prim && out && n_times >= 0 && (n_times == 0 || times), "mg_time_grid_create: bad arguments");
     *out = nullptr;
     for (int i = 0; i < n_times; i++) MG_REQUIRE(std::isfinite(times[i]), "mg_time_grid_create: times[%d] is not finite", i);
-    mg_time_grid *g = new (std::nothrow) mg_time_grid();
-    if (!g) return MG_ERR_OUT_OF_MEMORY;
-    int rc = mg_grid_build(prim, g, times, n_times, nullptr, nullptr);
-    if (rc != MG_OK) { mg_free_grid_device(g); delete g; return rc; }
-    *out = g;
-    return MG_OK;
+    return mg_grid_create(prim, times, n_times, nullptr, nullptr, false, out);
 }
 extern "C" void mg_time_grid_destroy(mg_time_grid *g) {
     if (!g || g->owned_by_prim) return;
-    if (g->prim) (void)hipStreamSynchronize(g->prim->ctx->stream);
-    mg_free_grid_device(g);
-    delete g;
+    (void)hipStreamSynchronize(g->prim->ctx->stream);
+    mg_grid_free(g);
 }
 extern "C" mg_time_grid *mg_primitive_canonical_grid(mg_primitive *prim) { return prim ? prim->canonical : nullptr; }
 extern "C" int mg_time_grid_size(const mg_time_grid *g) { return g ? g->T : 0; }
@@ -833,16 +672,42 @@ extern "C" int mg_time_grid_get_tables(const mg_time_grid *g, int32_t *i0, doubl
 // ---------------------------------------------------------------------------------------
 // primitive
 // ---------------------------------------------------------------------------------------
+// A primitive's device tables and the vectors of its image (mg_primitive_image.h) they are uploaded from, in one list, as the grids'
+// above.  each(the primitive has the table, vector, pointer): one it does not have (no k-steps, no mixture, no time model) stays NULL.
+template <class Each> static int mg_primitive_tables(const mg_primitive_model &m, Each each) {
+    int rc = MG_OK;
+    auto next = [&](bool has, auto host, auto dev) { if (rc == MG_OK && has) rc = each(host, dev); };
+    const bool packs = m.KK > 0, mixture = m.K > 0, mixture_packs = mixture && m.KKg > 0, time_model = m.Lt > 0;
+    next(true, &mg_primitive_image::Et32, &mg_primitive::d_Et32);
+    next(true, &mg_primitive_image::Et64, &mg_primitive::d_Et64);
+    next(true, &mg_primitive_image::means_, &mg_primitive::d_mean);
+    next(true, &mg_primitive_image::knots, &mg_primitive::d_knots);
+    next(true, &mg_primitive_image::mean32, &mg_primitive::d_mean32);
+    next(packs, &mg_primitive_image::Erpack, &mg_primitive::d_Erpack);
+    next(packs, &mg_primitive_image::meanroot, &mg_primitive::d_meanroot);
+    next(packs, &mg_primitive_image::Epack, &mg_primitive::d_Epack);
+    next(mixture_packs, &mg_primitive_image::gcholpack, &mg_primitive::d_gcholpack);
+    next(mixture_packs, &mg_primitive_image::gmeanpad, &mg_primitive::d_gmeanpad);
+    next(mixture_packs, &mg_primitive_image::gPpack, &mg_primitive::d_gPpack);
+    next(mixture_packs, &mg_primitive_image::gPTpack, &mg_primitive::d_gPTpack);
+    next(mixture_packs, &mg_primitive_image::gmPpad, &mg_primitive::d_gmPpad);
+    next(mixture, &mg_primitive_image::gP, &mg_primitive::d_gP);
+    next(mixture, &mg_primitive_image::gmP, &mg_primitive::d_gmP);
+    next(mixture, &mg_primitive_image::gconst, &mg_primitive::d_gconst);
+    next(mixture, &mg_primitive_image::gm, &mg_primitive::d_gmean);
+    next(mixture, &mg_primitive_image::gchol, &mg_primitive::d_gchol);
+    next(time_model, &mg_primitive_image::tphi, &mg_primitive::d_tphi);
+    next(time_model, &mg_primitive_image::tmean, &mg_primitive::d_tmean);
+    return rc;
+}
+
 static void mg_primitive_free(mg_primitive *p) {
     if (!p) return;
     (void)hipSetDevice(p->ctx->device);
     (void)hipStreamSynchronize(p->ctx->stream);
-    void *ptrs[] = {p->d_Epack, p->d_Et32, p->d_Et64, p->d_Erpack, p->d_meanroot, p->d_mean32, p->d_mean, p->d_knots,
-                    p->d_gP, p->d_gmP, p->d_gconst, p->d_gmean, p->d_gchol, p->d_gPpack, p->d_gmPpad, p->d_gPTpack, p->d_gcholpack, p->d_gmeanpad,
-                    p->d_tphi, p->d_tmean};
-    for (void *q : ptrs) mg_dev_free(p->ctx, q);
+    (void)mg_primitive_tables(*p, [&](auto, auto dev) { mg_dev_free(p->ctx, p->*dev); return MG_OK; });
     for (mg_time_grid *g : {p->canonical, p->coeff_grid})
-        if (g) { mg_free_grid_device(g); delete g; }
+        if (g) mg_grid_free(g);
     delete p;
 }
 
@@ -854,269 +719,18 @@ extern "C" void mg_primitive_destroy(mg_primitive *p) {
 extern "C" int mg_primitive_create(mg_context *ctx, const mg_primitive_desc *d, mg_primitive **out) {
     MG_REQUIRE(ctx && d && out, "mg_primitive_create: NULL argument");
     *out = nullptr;
-    MG_REQUIRE(d->n_basis >= 4, "mg_primitive_create: n_basis = %d, a cubic spline needs >= 4", d->n_basis);
-    MG_REQUIRE(d->n_dim >= 1 && d->n_components >= 1 && d->n_canonical_frames >= 1,
-               "mg_primitive_create: n_dim/n_components/n_canonical_frames must be >= 1");
-    MG_REQUIRE(d->n_gmm >= 0, "mg_primitive_create: n_gmm < 0");
-    MG_REQUIRE(d->eigen_vectors && d->mean_vector && d->knots, "mg_primitive_create: eigen_vectors/mean_vector/knots are required");
-    MG_REQUIRE(d->n_gmm == 0 || (d->gmm_weights && d->gmm_means && d->gmm_covars),
-               "mg_primitive_create: gmm arrays are required when n_gmm > 0");
-    MG_REQUIRE((int64_t)d->n_basis * d->n_dim < (1 << 24), "mg_primitive_create: n_basis*n_dim too large");
-    const int NB = d->n_basis, D = d->n_dim, L = d->n_components, K = d->n_gmm, R = NB * D;
-    const int Lg = d->n_gmm_dims > 0 ? d->n_gmm_dims : L;   // the mixture spans the spatial AND the time latents
-    MG_REQUIRE(Lg >= L, "mg_primitive_create: n_gmm_dims = %d < n_components = %d", Lg, L);
-    const int Lt = d->n_time_components, NBt = d->n_basis_time;
-    MG_REQUIRE(Lt >= 0 && (Lt == 0 || (NBt >= 4 && d->eigen_vectors_time && d->mean_time_vector && d->knots_time)),
-               "mg_primitive_create: a time model needs n_basis_time >= 4, eigen_vectors_time, mean_time_vector and knots_time");
-    for (int i = 0; i + 1 < NB + 4; i++)
-        MG_REQUIRE(d->knots[i] <= d->knots[i + 1] && std::isfinite(d->knots[i + 1]), "mg_primitive_create: knots must be finite and non-decreasing");
-    MG_REQUIRE(d->knots[3] < d->knots[NB], "mg_primitive_create: knot vector has an empty domain");
     MG_HIP_CHECK(hipSetDevice(ctx->device));
-
+    mg_primitive_image im;
+    int rc = mg_primitive_image_build(d, im);   // every refusal of a descriptor, before anything is allocated
+    if (rc != MG_OK) return rc;
     mg_primitive *p = new (std::nothrow) mg_primitive();
     if (!p) return MG_ERR_OUT_OF_MEMORY;
     p->ctx = ctx;
-    p->NB = NB; p->D = D; p->L = L; p->F = d->n_canonical_frames; p->K = K; p->R = R;
-    p->nroot = std::min(3, D);
-    p->KK = (L <= 4 * MG_MAX_KK) ? (((L + 3) / 4 + 1) / 2) * 2 : 0;
-    p->Lg = Lg;
-    p->KKg = (Lg <= 4 * MG_MAX_KK) ? (((Lg + 3) / 4 + 1) / 2) * 2 : 0;
-    p->Lt = Lt; p->NBt = NBt;
-    // padded coefficient rows: column = d + cshift so that the first non-root channel sits on a
-    // 16-byte boundary (quads of channels start at d = nroot), pitch a multiple of 4
-    p->cshift = (4 - p->nroot) & 3;
-    p->Dp = (D + p->cshift + 3) & ~3;
-    p->RT = (NB * p->Dp + 15) / 16;
-    p->knots.assign(d->knots, d->knots + NB + 4);
-    double tm[3] = {1.0, 1.0, 1.0};
-    if (d->translation_maxima)
-        for (int i = 0; i < 3; i++) tm[i] = d->translation_maxima[i];
-
-    // E' = E * scale_d, mean' = mean * scale_d (float64 products): the reference applies
-    // translation_maxima after adding the mean (motion_primitive.py:251-255), which is
-    // the same linear map.
-    p->Es.resize((size_t)R * L);
-    p->means_.resize(R);
-    for (int r = 0; r < R; r++) {
-        double sc = (r % D < 3) ? tm[r % D] : 1.0;
-        for (int k = 0; k < L; k++) {
-            double e = d->eigen_is_transposed ? d->eigen_vectors[(size_t)r * L + k] : d->eigen_vectors[(size_t)k * R + r];
-            p->Es[(size_t)r * L + k] = e * sc;
-        }
-        p->means_[r] = d->mean_vector[r] * sc;
-    }
-
-    int rc = MG_OK;
-    {   // device images of E'
-        std::vector<float> et32((size_t)L * R);
-        std::vector<double> et64((size_t)L * R);
-        for (int r = 0; r < R; r++)
-            for (int k = 0; k < L; k++) {
-                et64[(size_t)k * R + r] = p->Es[(size_t)r * L + k];
-                et32[(size_t)k * R + r] = (float)p->Es[(size_t)r * L + k];
-            }
-        if (rc == MG_OK) rc = mg_upload(ctx, et32, &p->d_Et32);
-        if (rc == MG_OK) rc = mg_upload(ctx, et64, &p->d_Et64);
-        if (rc == MG_OK) rc = mg_upload(ctx, p->means_, &p->d_mean);
-        if (rc == MG_OK) rc = mg_upload(ctx, p->knots, &p->d_knots);
-        {
-            std::vector<float> m32((size_t)p->RT * 16, 0.0f);
-            for (int i = 0; i < NB; i++)
-                for (int dd = p->nroot; dd < D; dd++)   // the root rows' C-in is zero: they hold E'.s alone (the split's delta)
-                    m32[(size_t)i * p->Dp + dd + p->cshift] = (float)p->means_[(size_t)i * D + dd];
-            if (rc == MG_OK) rc = mg_upload(ctx, m32, &p->d_mean32);
-        }
-        if (rc == MG_OK && p->KK > 0) {
-            // the root rows (row = i*nroot + d) of E' (mg_pack.h)
-            const int KK = p->KK, nr = p->nroot, RR = NB * nr;
-            p->RRT = (RR + 15) / 16;
-            std::vector<double> rpack((size_t)p->RRT * KK * 64), mroot((size_t)p->RRT * 16, 0.0);
-            for (int rr = 0; rr < RR; rr++) mroot[rr] = p->means_[(size_t)(rr / nr) * D + rr % nr];
-            mg_pack_fragments(rpack.data(), p->RRT, KK, [&](int rr, int k) { return rr < RR && k < L ? p->Es[((size_t)(rr / nr) * D + rr % nr) * L + k] : 0.0; });
-            rc = mg_upload(ctx, rpack, &p->d_Erpack);
-            if (rc == MG_OK) rc = mg_upload(ctx, mroot, &p->d_meanroot);
-        }
-        if (rc == MG_OK && p->KK > 0) {
-            // the padded coefficient rows r' = i*Dp + d + cshift of E' in float32 (zero rows elsewhere), k-steps in pairs per lane (mg_pack.h) ...
-            const int KK = p->KK, Dp = p->Dp;
-            const size_t n1 = (size_t)p->RT * KK * 64;
-            std::vector<float> plain(n1), pack(2 * n1);
-            mg_pack_fragments(plain.data(), p->RT, KK, [&](int rp, int k) {
-                const int i = rp / Dp, dd = rp - i * Dp - p->cshift;
-                return (i < NB && dd >= 0 && dd < D && k < L) ? (float)p->Es[((size_t)i * D + dd) * L + k] : 0.0f;
-            });
-            mg_pack_regroup(plain.data(), pack.data(), p->RT, KK, 2);
-            // ... followed by a second copy for the chunk-stationary kernel's one-time fragment loads, k-steps in quads per lane: 16-byte loads, 3 instead
-            // of 5 instructions per tile at KK = 10 through a CU's address unit while the whole chip fetches its windows at once (csrc/mg_frames_cs.hip,
-            // mg_cs_load_fragments)
-            mg_pack_regroup(plain.data(), pack.data() + n1, p->RT, KK, 4);
-            rc = mg_upload(ctx, pack, &p->d_Epack);
-        }
-    }
+    rc = mg_primitive_tables(im, [&](auto host, auto dev) { return mg_upload(ctx, im.*host, &(p->*dev)); });
+    static_cast<mg_primitive_model &>(*p) = std::move(im);   // (the grids' times below are the image's own members)
+    if (rc == MG_OK) rc = mg_grid_create(p, im.canonical_times.data(), p->F, nullptr, nullptr, true, &p->canonical);
+    if (rc == MG_OK) rc = mg_grid_create(p, im.identity_times.data(), p->NB, im.identity_i0.data(), im.identity_w.data(), true, &p->coeff_grid);
     if (rc != MG_OK) { mg_primitive_free(p); return rc; }
-
-    if (K > 0) {
-        p->gw.assign(d->gmm_weights, d->gmm_weights + K);
-        p->gm.assign(d->gmm_means, d->gmm_means + (size_t)K * Lg);
-        p->gc.assign(d->gmm_covars, d->gmm_covars + (size_t)K * Lg * Lg);
-        p->gp.assign((size_t)K * Lg * Lg, 0.0);
-        std::vector<double> chol((size_t)K * Lg * Lg), inv((size_t)Lg * Lg);
-        std::vector<double> gP((size_t)K * Lg * Lg, 0.0), gmP((size_t)K * Lg), gconst(K);
-        const double log2pi = std::log(2.0 * M_PI);
-        for (int k = 0; k < K; k++) {
-            double *c = &chol[(size_t)k * Lg * Lg];
-            if (!(p->gw[k] >= 0.0) || !std::isfinite(p->gw[k])) {
-                mg_set_error("mg_primitive_create: gmm_weights[%d] is negative or not finite", k);
-                mg_primitive_free(p);
-                return MG_ERR_INVALID_ARGUMENT;
-            }
-            if (!mg_cholesky_lower(&p->gc[(size_t)k * Lg * Lg], Lg, c)) {
-                mg_set_error("mg_primitive_create: gmm_covars[%d] is not positive definite", k);
-                mg_primitive_free(p);
-                return MG_ERR_NOT_POSITIVE_DEFINITE;
-            }
-            // sklearn _compute_precision_cholesky: P = solve_triangular(chol, I, lower=True).T
-            std::fill(inv.begin(), inv.end(), 0.0);
-            for (int col = 0; col < Lg; col++)
-                for (int r = col; r < Lg; r++) {
-                    double s = (r == col) ? 1.0 : 0.0;
-                    for (int q = col; q < r; q++) s -= c[r * Lg + q] * inv[(size_t)q * Lg + col];
-                    inv[(size_t)r * Lg + col] = s / c[r * Lg + r];
-                }
-            double *P = &p->gp[(size_t)k * Lg * Lg];
-            double logdet = 0.0;
-            for (int i = 0; i < Lg; i++) {
-                for (int j = 0; j < Lg; j++) P[i * Lg + j] = inv[(size_t)j * Lg + i];
-                logdet += std::log(P[i * Lg + i]);
-            }
-            for (int j = 0; j < Lg; j++) {
-                double acc = 0.0;
-                for (int i = 0; i <= j; i++) {
-                    gP[((size_t)k * Lg + j) * Lg + i] = P[i * Lg + j];
-                    acc += p->gm[(size_t)k * Lg + i] * P[i * Lg + j];
-                }
-                gmP[(size_t)k * Lg + j] = acc;
-            }
-            gconst[k] = std::log(p->gw[k]) + logdet - 0.5 * (double)Lg * log2pi;
-        }
-        if (p->KKg > 0) {
-            // images [component][tile][k-step][lane] (mg_pack.h), (i16, k) = (16-wide index, reduction index):
-            const int KK = p->KKg, JT = (Lg + 15) / 16, L = Lg;   // inside this block L is the mixture's dimension
-            const size_t n1 = (size_t)K * JT * KK * 64, tile = (size_t)JT * KK * 64;
-            std::vector<double> ppack(2 * n1), ptpack(n1), cpack(2 * n1), mpad((size_t)K * JT * 16, 0.0), meanpad((size_t)K * JT * 16, 0.0);
-            for (int k = 0; k < K; k++) {
-                const double *P = &p->gp[(size_t)k * L * L], *C = &chol[(size_t)k * L * L];
-                for (int j = 0; j < L; j++) mpad[(size_t)k * JT * 16 + j] = gmP[(size_t)k * L + j];
-                for (int i = 0; i < L; i++) meanpad[(size_t)k * JT * 16 + i] = p->gm[(size_t)k * L + i];
-                // the precision factor P_k[i][j], upper triangular, reduced over i ...
-                mg_pack_fragments(&ppack[k * tile], JT, KK, [&](int j, int i) { return i < L && j < L && i <= j ? P[(size_t)i * L + j] : 0.0; });
-                // ... its transpose for z = y P_k^T (log_likelihood_jac), reduced over j ...
-                mg_pack_fragments(&ptpack[k * tile], JT, KK, [&](int i, int j) { return i < L && j < L && i <= j ? P[(size_t)i * L + j] : 0.0; });
-                // ... and the sampler's x = mu + z L^T: L_k[i][j], lower triangular, reduced over j
-                mg_pack_fragments(&cpack[k * tile], JT, KK, [&](int i, int j) { return i < L && j < L && j <= i ? C[(size_t)i * L + j] : 0.0; });
-            }
-            // cpack and ppack are each followed by the same fragments with the k-steps in pairs per lane: 16-byte loads in the planner step's sampler
-            mg_pack_regroup(cpack.data(), cpack.data() + n1, K * JT, KK, 2);
-            if (rc == MG_OK) rc = mg_upload(ctx, cpack, &p->d_gcholpack);
-            if (rc == MG_OK) rc = mg_upload(ctx, meanpad, &p->d_gmeanpad);
-            // (the fused step's staged tail and its start-up half: half the load instructions through a CU's address unit, csrc/mg_gmm_device.h)
-            mg_pack_regroup(ppack.data(), ppack.data() + n1, K * JT, KK, 2);
-            if (rc == MG_OK) rc = mg_upload(ctx, ppack, &p->d_gPpack);
-            if (rc == MG_OK) rc = mg_upload(ctx, ptpack, &p->d_gPTpack);
-            if (rc == MG_OK) rc = mg_upload(ctx, mpad, &p->d_gmPpad);
-        }
-        if (rc == MG_OK) rc = mg_upload(ctx, gP, &p->d_gP);
-        if (rc == MG_OK) rc = mg_upload(ctx, gmP, &p->d_gmP);
-        if (rc == MG_OK) rc = mg_upload(ctx, gconst, &p->d_gconst);
-        if (rc == MG_OK) rc = mg_upload(ctx, p->gm, &p->d_gmean);
-        if (rc == MG_OK) rc = mg_upload(ctx, chol, &p->d_gchol);
-        if (rc != MG_OK) { mg_primitive_free(p); return rc; }
-    }
-
-    {   // the mean/delta split's accuracy gate (mg_primitive_root_mode)
-        std::vector<double> m2(L, 1.0);
-        double wsum = 0.0;
-        for (int j = 0; j < K; j++) wsum += p->gw[j];
-        if (K > 0)
-            for (int k = 0; k < L; k++) {
-                double acc = 0.0;
-                for (int j = 0; j < K; j++) {
-                    const double mu = p->gm[(size_t)j * Lg + k];
-                    acc += p->gw[j] * (mu * mu + p->gc[(size_t)j * Lg * Lg + (size_t)k * Lg + k]);
-                }
-                m2[k] = acc / wsum;
-            }
-        double worst = 0.0;
-        for (int i = 0; i < NB; i++)
-            for (int dd = 0; dd < p->nroot; dd++) {
-                const double *e = &p->Es[((size_t)i * D + dd) * L];
-                double ss = 0.0;
-                for (int k = 0; k < L; k++) ss += e[k] * e[k] * m2[k];
-                worst = std::max(worst, std::sqrt(ss));
-            }
-        p->root_split_est = (double)(L + 8) * 0x1p-24 * worst;
-        p->root_split = std::isfinite(p->root_split_est) && p->root_split_est <= MG_ROOT_SPLIT_MAX_EST;
-    }
-
-    if (Lt > 0) {
-        // mean time spline and harmonics at the canonical frames 0 .. F-1 (reference motion_primitive.py:258-268,293-296:
-        // si.splev(canonical_time_range, (knots_t, coefficients, 3)); column l of eigen_vectors_time = coefficients of harmonic l)
-        const int F = p->F;
-        for (int i = 0; i + 1 < NBt + 4; i++)
-            if (!(d->knots_time[i] <= d->knots_time[i + 1]) || !std::isfinite(d->knots_time[i + 1])) {
-                mg_set_error("mg_primitive_create: knots_time must be finite and non-decreasing");
-                mg_primitive_free(p);
-                return MG_ERR_INVALID_ARGUMENT;
-            }
-        std::vector<double> tphi((size_t)F * Lt), tmean(F);
-        for (int f = 0; f < F; f++) {
-            int32_t i0;
-            double w[4];
-            mg_basis_row(d->knots_time, NBt + 4, (double)f, &i0, w);
-            double m = w[0] * d->mean_time_vector[i0];
-            for (int j = 1; j < 4; j++) m = std::fma(w[j], d->mean_time_vector[i0 + j], m);
-            tmean[f] = m;
-            for (int l = 0; l < Lt; l++) {
-                double v = w[0] * d->eigen_vectors_time[(size_t)i0 * Lt + l];
-                for (int j = 1; j < 4; j++) v = std::fma(w[j], d->eigen_vectors_time[(size_t)(i0 + j) * Lt + l], v);
-                tphi[(size_t)f * Lt + l] = v;
-            }
-        }
-        rc = mg_upload(ctx, tphi, &p->d_tphi);
-        if (rc == MG_OK) rc = mg_upload(ctx, tmean, &p->d_tmean);
-        if (rc != MG_OK) { mg_primitive_free(p); return rc; }
-    }
-    {   // canonical grid: np.linspace(0, F, int(F * 1.0))  (reference motion_primitive.py:233)
-        const int F = p->F;
-        std::vector<double> t(F);
-        if (F == 1) {
-            t[0] = 0.0;
-        } else {
-            double step = (double)F / (double)(F - 1);
-            for (int f = 0; f < F; f++) t[f] = (double)f * step;
-            t[F - 1] = (double)F;
-        }
-        p->canonical = new (std::nothrow) mg_time_grid();
-        if (!p->canonical) { mg_primitive_free(p); return MG_ERR_OUT_OF_MEMORY; }
-        p->canonical->owned_by_prim = true;
-        rc = mg_grid_build(p, p->canonical, t.data(), F, nullptr, nullptr);
-        if (rc != MG_OK) { mg_primitive_free(p); return rc; }
-    }
-    {   // identity grid: row i selects coefficient i, so "frames" are the coefficients
-        std::vector<double> t(NB, 0.0), w((size_t)NB * 4, 0.0);
-        std::vector<int32_t> i0(NB);
-        for (int i = 0; i < NB; i++) {
-            int base = std::min(i, NB - 4);
-            i0[i] = base;
-            w[4 * i + (i - base)] = 1.0;
-            t[i] = (double)i;
-        }
-        p->coeff_grid = new (std::nothrow) mg_time_grid();
-        if (!p->coeff_grid) { mg_primitive_free(p); return MG_ERR_OUT_OF_MEMORY; }
-        p->coeff_grid->owned_by_prim = true;
-        rc = mg_grid_build(p, p->coeff_grid, t.data(), NB, i0.data(), w.data());
-        if (rc != MG_OK) { mg_primitive_free(p); return rc; }
-    }
     *out = p;
     return MG_OK;
 }

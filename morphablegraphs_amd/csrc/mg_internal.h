@@ -9,11 +9,10 @@
 
 #include "../../include/mg_hip.h"
 #include "mg_dispatch.h"
-#include "mg_hostdefs.h"   // mg_set_error, MG_REQUIRE_AS / MG_REQUIRE, MG_POSE_HDR / MG_POSE_REC, mg_basis_row
+#include "mg_hostdefs.h"   // mg_set_error, MG_REQUIRE_AS / MG_REQUIRE, MG_POSE_HDR / MG_POSE_REC, the chunk planner's constants, mg_chunk, mg_basis_row
+#include "mg_primitive_image.h"   // mg_primitive_model, mg_grid_plan: the host halves of mg_primitive and mg_time_grid
 
-#define MG_NCAND 16         // candidates per MFMA tile (N of v_mfma_f32_16x16x4_f32)
 #define MG_ROWTILE 16       // coefficient rows per MFMA tile (M)
-#define MG_MAX_KK 16        // k-steps of 4 -> n_components <= 64 on the MFMA path
 #define MG_BLOCK 256        // threads per workgroup of the frames kernels
 // profile slots: the keys of _capi.PROFILE_SLOTS
 enum { MG_PROF_FRAMES = 0, MG_PROF_GMM_LOG_PROB, MG_PROF_SCORE_CONSTRAINTS, MG_PROF_ARGMIN, MG_PROF_GMM_SAMPLE, MG_PROF_SPLINE_EVALUATE, MG_PROF_STEP,
@@ -147,39 +146,10 @@ template <typename... K> inline hipError_t mg_lds_opt_in_once(mg_context *ctx, u
     return mg_lds_opt_in_once(ctx->attr_traj, bit, bytes, kernels...);
 }
 
-// One chunk of a time grid handled by one workgroup of the MFMA kernel.
-#define MG_MAX_WI 11         // basis functions per chunk window (11 x 3 root rows still span <= 3 row tiles of 16)
-#define MG_MAX_NT 48         // time samples per chunk
-#define MG_TAP_KS ((MG_MAX_WI + 3) / 4)   // k-steps of the banded root-tap MFMA (4 basis functions each)
-#define MG_TAP_FT (MG_MAX_NT / 16)       // sample tiles of 16 of the root-tap MFMA
-#define MG_ARG_CHUNKS 8   // chunk descriptors that travel in the frames kernels' arguments
-// LDS of the frames kernels per ring slot: per-sample tables (tap weights + tap row offsets) and the root outputs
-// [candidate][sample][4] float32.  nt = the grid's longest chunk, rounded up to 16 samples.  A candidate's root outputs are
-// MG_RO_PAD floats apart from a multiple of 32: wave 0 writes them one float per lane, (candidate, channel) x sample, and with a
-// stride of 4 nt floats (0 mod 32 banks for nt = 16, 32, 48) the six candidates of a column tile meet in the same banks.
-#define MG_RO_PAD 8
-#define MG_RO_CS(nt) ((nt) * 4 + MG_RO_PAD)              // floats per candidate
-#define MG_TB_BYTES_N(nt) ((nt) * 16 + (nt) * 4)
-#define MG_RO_BYTES_N(nt) (MG_NCAND * MG_RO_CS(nt) * 4)
-struct mg_chunk {
-    int32_t t0;        // first time index (chunks are runs of consecutive time indices)
-    int32_t nT;        // number of time samples in the chunk, <= MG_MAX_NT
-    int32_t rt0;       // first global 16-row tile of the (padded-row) coefficient window
-    int32_t ntiles;    // number of 16-row tiles
-    int32_t imin;      // first coefficient index of the window
-    int32_t wi;        // coefficient rows (basis functions) in the window, <= MG_MAX_WI
-    int32_t rrt0;      // first 16-row tile of the root-row window (rows = i*nroot + d)
-    int32_t nrt;       // number of root tiles
-};
-
-struct mg_time_grid {
+// A time grid: its samples' basis rows and chunk plan (mg_grid_plan, mg_primitive_image.h) and the device tables
+struct mg_time_grid : mg_grid_plan {
     mg_primitive *prim = nullptr;
     bool owned_by_prim = false;
-    int32_t T = 0;
-    std::vector<double> times;
-    std::vector<int32_t> i0;
-    std::vector<double> w;  // (T,4)
-    std::vector<mg_chunk> chunks;
     // device tables
     int32_t *d_i0 = nullptr;
     double *d_w = nullptr;      // (T,4) float64 weights
@@ -188,39 +158,13 @@ struct mg_time_grid {
                                 // float32 pairs: {Mhi[0..2], Mlo[0..2], 0, 0} (the mean/delta split of the frames kernels)
     double *d_wtap = nullptr;   // [n_chunks][2][2][64] banded tap weights, f64 MFMA A fragments
     mg_chunk *d_chunks = nullptr;
-    int32_t n_chunks = 0;
-    int32_t stride = 0;      // floats per candidate in the LDS coefficient image
-    int32_t max_wi = 0;
-    int32_t max_nt = 16;        // samples of the longest chunk, rounded up to 16: sizes the per-slot tables in LDS
-    int32_t lds_bytes = 0;   // dynamic LDS of the MFMA kernel for this grid
-    int32_t nbuf = 2;        // LDS ring depth of the MFMA kernel (3 when it fits)
-    bool mfma_ok = false;
-    int32_t max_tiles = 0;   // row tiles of the widest chunk window
-    int32_t cs_lds_bytes = 0;   // dynamic LDS of the chunk-stationary kernel (without the fused mixture's buffers)
-    bool cs_ok = false;      // the chunk-stationary kernel covers this grid (window fits the row producers' registers, LDS fits)
 };
 
-struct mg_primitive {
+// A primitive: its shape, derived scalars and host float64 copies (mg_primitive_model, mg_primitive_image.h) and the device constants
+struct mg_primitive : mg_primitive_model {
     mg_context *ctx = nullptr;
-    int32_t NB = 0, D = 0, L = 0, F = 0, K = 0, R = 0;
-    int32_t nroot = 0;  // min(3, D): root-translation channels (float64 pipeline or mean/delta split)
-    bool root_split = false;      // the accuracy gate allows the mean/delta split (mg_primitive_root_mode)
-    double root_split_est = 0.0;  // its error estimate
-    int32_t KK = 0;     // MFMA k-steps (even), 0 when L > 64
-    int32_t Lg = 0;     // dimension of the mixture (>= L: spatial + time latents)
-    int32_t KKg = 0;    // MFMA k-steps of the mixture kernels (even), 0 when Lg > 64
-    int32_t Lt = 0, NBt = 0;         // time model: components, basis functions
     double *d_tphi = nullptr;        // [F][Lt]: harmonics at the canonical frames
     double *d_tmean = nullptr;       // [F]: mean time spline at the canonical frames
-    int32_t RT = 0;     // 16-row tiles of the padded-row space NB*Dp
-    // host float64 copies (already scaled by translation_maxima)
-    std::vector<double> Es;    // (R, L)
-    std::vector<double> means_;  // mean' (R)
-    std::vector<double> knots;
-    std::vector<double> gw, gm, gc, gp;  // weights (K), means (K,L), covars (K,L,L), prec chol (K,L,L)
-    // device constants
-    int32_t Dp = 0;              // row pitch of the padded coefficient rows (multiple of 4)
-    int32_t cshift = 0;          // column of channel d in a padded row is d + cshift
     float *d_Epack = nullptr;    // [RT][KK/2][64][2] MFMA A fragments, f32, padded rows r' = i*Dp + d, k-steps in pairs per lane; RT*KK*64 floats
                                  // on, the same fragments with the k-steps in quads per lane, [RT]{[KK/4][64][4], then [64][2] where KK % 4 == 2}
                                  // (mg_pack_regroup, G = 4: the chunk-stationary kernel's one-time loads)
@@ -232,7 +176,6 @@ struct mg_primitive {
                                  // therefore hold E'.s alone: the delta of the mean/delta split)
     double *d_mean = nullptr;    // (R) f64
     double *d_knots = nullptr;   // (NB + 4) f64: the spatial knot vector (basis rows computed on the device: mg_frames_at_kernel)
-    int32_t RRT = 0;             // 16-row tiles of the root-row space
     // GMM device constants
     double *d_gPpack = nullptr;  // [K][JT][KK][64]: v_mfma_f64_16x16x4_f64 B fragments of P_k (L <= 64); K*JT*KK*64 doubles on, the same fragments
                                  // with the k-steps in pairs per lane, [K][JT][KK/2][64][2] (the fused step's staged tail, the planner step)
@@ -309,7 +252,6 @@ int mg_output_class(mg_context *ctx, const void *p);   // mg_placement.hip: 1 fa
 int mg_frames_lds_bytes(const mg_primitive *p, const mg_time_grid *g, int which, bool fused);
 int mg_frames_grid(const mg_primitive *p, const mg_time_grid *g, int64_t B, int which);
 bool mg_frames_root_split(const mg_primitive *p);   // the root-channel mode a launch uses (gate + MG_OPT_ROOT_MODE)
-#define MG_ROOT_SPLIT_MAX_EST 5e-6
 int mg_cs_max_tiles(int KK);   // row tiles of a chunk window the chunk-stationary kernel can hold in registers
 int mg_launch_frames_direct(mg_primitive *p, const mg_time_grid *g, const void *lat, int ldt, int64_t B, int64_t ld, void *out, bool out_f64);
 int mg_launch_spline_eval(mg_primitive *p, const mg_time_grid *g, const double *coeffs, int64_t n, double *out);

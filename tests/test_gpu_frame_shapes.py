@@ -7,7 +7,7 @@ below is one table of small synthetic primitives (F = 20, K = 3) that puts every
 the tile-major and the chunk-stationary kernel and of the fused step, with the contracts the rest of the suite uses: float32
 frames bit for bit the oracle's float32 model, log p bit for bit the stand-alone float32 log-likelihood.
 
-The planner (mg_plan_chunks) and the sweep waves' lane map are restated here in Python; the CPU tests pin the restatements to
+The planner (mg_plan_chunks, csrc/mg_primitive_image.h) and the sweep waves' lane map are restated here in Python; the CPU tests pin the restatements to
 the C sources line by line, assert that the table straddles every boundary and that the lane map writes every output float
 and none outside its row; the GPU sweep compares the restated plan with what the library reports.  LEDGER records which
 (kernel, D class, latent dtype, root mode) ran and matched; test_the_ledger_covers_every_class fails when a shape stops
@@ -24,7 +24,7 @@ from test_gpu_parity import _bits, _fused_step, pose_tol
 MG_ERR_UNSUPPORTED = -4
 
 # ---- the planner and the lane map, restated (kept in step with the C sources by test_restatements_match_the_sources) --------
-MG_NCAND = 16                    # mg_internal.h
+MG_NCAND = 16                    # mg_hostdefs.h
 MG_MAX_WI = 11
 MG_MAX_NT = 48
 MG_ARG_CHUNKS = 8
@@ -304,39 +304,49 @@ def _source(name):
 
 def test_restatements_match_the_sources():
     """Every formula restated above, pinned to its line in the C sources."""
-    host, internal, ws, cs, frames = (_source(n) for n in ("mg_host.hip", "mg_internal.h", "mg_frames_ws.hip", "mg_frames_cs.hip",
-                                                            "mg_frames.hip"))
+    host, image, hostdefs, ws, cs, frames = (_source(n) for n in ("mg_host.hip", "mg_primitive_image.h", "mg_hostdefs.h", "mg_frames_ws.hip",
+                                                                  "mg_frames_cs.hip", "mg_frames.hip"))
+    # (mg_lds_bytes' per-slot and root terms are mg_lds_slot_bytes and mg_lds_root_bytes, which the chunk-stationary kernel's LDS
+    # shares; one mg_grow_chunk is the window-growing loop of the greedy count (cap = max_nt) and of the final split (cap = target))
     for line in ("p->nroot = std::min(3, D);", "p->cshift = (4 - p->nroot) & 3;", "p->Dp = (D + p->cshift + 3) & ~3;",
                  "while (s % 32 != 4) s++;", "int buf = (MG_NCAND * stride * 4 + 255) / 256 * 256;",
-                 "int rout = MG_RO_BYTES_N(max_nt);", "int tabs = max_nt * 16 + max_nt * 4;",
-                 "int root = MG_NCAND * (wi * p->nroot + 1) * 8;", "return nbuf * (buf + rout + tabs) + root + 128;",
-                 "if (p->KK == 0 || g->T == 0 || (p->D - p->nroot + 3) / 4 + 1 > 64) return;",
-                 "int nlocal = ((wi * Dp + 15) / 16 + 1) * 16;", "return mg_lds_bytes(p, mg_round_stride(nlocal), wi) <= budget;",
+                 "int rout = MG_RO_BYTES_N(max_nt);", "return buf + rout;", "int tabs = max_nt * 16 + max_nt * 4;",
+                 "inline int mg_lds_root_bytes(int nroot, int wi) { return MG_NCAND * (wi * nroot + 1) * 8; }",
+                 "return nbuf * (mg_lds_slot_bytes(stride, max_nt) + tabs) + mg_lds_root_bytes(nroot, wi) + 128;",
+                 "if (p.KK == 0 || T == 0 || (p.D - p.nroot + 3) / 4 + 1 > 64) return;",
+                 "int nlocal = ((wi * Dp + 15) / 16 + 1) * 16;", "return mg_lds_bytes(p.nroot, mg_round_stride(nlocal), wi) <= budget;",
                  "const int budget1 = 160 * 1024;",
-                 "if (const int o = p->ctx->opt[MG_OPT_CHUNK_SAMPLES]) max_nt = std::max(1, std::min(MG_MAX_NT, o));",
-                 "while (b < g->T && b - a0 < max_nt) {", "if (hi - lo + 4 > w) break;",
+                 "if (const int o = opt_samples) max_nt = std::max(1, std::min(MG_MAX_NT, o));",
+                 "for (int a0 = 0; a0 < T; n++) a0 = mg_grow_chunk(g.i0, a0, max_nt, w, imin, imax);",
+                 "while (b < T && b - a < cap) {", "if (hi - lo + 4 > w) break;",
                  "for (int w = MG_MAX_WI; w >= 4; w--) {", "if (W == 0 || n <= best_n) { W = w; best_n = n; }",
-                 "if (const int o = p->ctx->opt[MG_OPT_CHUNK_WINDOW]) W = std::max(4, std::min(W, o));",
-                 "const int left = std::max(1, n_greedy - (int)g->chunks.size());",
-                 "const int target = std::min(max_nt, (g->T - a + left - 1) / left);",
-                 "while (b < g->T && b - a < target) {", "if (hi - lo + 4 > W) break;",
+                 "if (const int o = opt_window) W = std::max(4, std::min(W, o));",
+                 "const int left = std::max(1, n_greedy - (int)g.chunks.size());",
+                 "const int target = std::min(max_nt, (T - a + left - 1) / left);",
+                 "const int b = mg_grow_chunk(g.i0, a, target, W, imin, imax);",
                  "c.wi = imax - imin + 4;", "c.rt0 = (imin * Dp) / 16;", "int rt1 = ((imin + c.wi) * Dp + 15) / 16;",
-                 "max_stride = std::max(max_stride, mg_round_stride(c.ntiles * 16));", "g->max_nt = (longest + 15) / 16 * 16;",
-                 "g->nbuf = mg_lds_bytes(p, max_stride, max_wi, 3, g->max_nt) <= budget1 ? 3 : 2;",
-                 "if (p->ctx->opt[MG_OPT_RING_SLOTS] == 2) g->nbuf = 2;",
-                 "g->lds_bytes = mg_lds_bytes(p, max_stride, max_wi, g->nbuf, g->max_nt);", "g->mfma_ok = g->lds_bytes <= budget1;",
-                 "g->cs_lds_bytes = 2 * (buf + MG_RO_BYTES_N(g->max_nt)) + g->max_nt * 20 + MG_NCAND * (max_wi * p->nroot + 1) * 8 + "
-                 "g->max_tiles * 64 +",
-                 "MG_TAP_FT * MG_TAP_KS * 64 * 8 + 512 + 2 * p->KK * 64 * 4 + 256;",
-                 "g->cs_ok = g->mfma_ok && g->max_tiles <= mg_cs_max_tiles(p->KK) && g->cs_lds_bytes <= budget1 && "
-                 "(int)g->chunks.size() <= MG_ARG_CHUNKS;",
-                 "use_mfma = g->mfma_ok && B >= 8;"):
+                 "max_stride = std::max(max_stride, mg_round_stride(c.ntiles * 16));", "g.max_nt = (longest + 15) / 16 * 16;",
+                 "g.nbuf = mg_lds_bytes(p.nroot, max_stride, max_wi, 3, g.max_nt) <= budget1 ? 3 : 2;",
+                 "if (opt_ring == 2) g.nbuf = 2;",
+                 "g.lds_bytes = mg_lds_bytes(p.nroot, max_stride, max_wi, g.nbuf, g.max_nt);", "g.mfma_ok = g.lds_bytes <= budget1;",
+                 "g.cs_lds_bytes = 2 * mg_lds_slot_bytes(max_stride, g.max_nt) + g.max_nt * 20 + mg_lds_root_bytes(p.nroot, max_wi) + "
+                 "g.max_tiles * 64 +",
+                 "MG_TAP_FT * MG_TAP_KS * 64 * 8 + 512 + 2 * p.KK * 64 * 4 + 256;",
+                 "g.cs_ok = g.mfma_ok && g.max_tiles <= cs_max_tiles && g.cs_lds_bytes <= budget1 && "
+                 "(int)g.chunks.size() <= MG_ARG_CHUNKS;"):
+        assert line in image, line
+    # the options and the chunk-stationary kernel's register bound reach the planner from the context, in this order
+    for line in ("mg_grid_image_build(*p, times, T, i0_override, w_override, opt[MG_OPT_CHUNK_SAMPLES], opt[MG_OPT_CHUNK_WINDOW], "
+                 "opt[MG_OPT_RING_SLOTS],", "mg_cs_max_tiles(p->KK), im);", "use_mfma = g->mfma_ok && B >= 8;"):
         assert line in host, line
+    assert ("inline void mg_plan_chunks(const mg_primitive_model &p, mg_grid_plan &g, int opt_samples, int opt_window, int opt_ring, "
+            "int cs_max_tiles) {") in image
+    assert "mg_plan_chunks(p, im, opt_samples, opt_window, opt_ring, cs_max_tiles);" in image
     for line in ("#define MG_NCAND %d " % MG_NCAND, "#define MG_MAX_WI %d " % MG_MAX_WI, "#define MG_MAX_NT %d " % MG_MAX_NT,
                  "#define MG_ARG_CHUNKS %d " % MG_ARG_CHUNKS, "#define MG_RO_PAD %d" % MG_RO_PAD,
                  "#define MG_TAP_KS ((MG_MAX_WI + 3) / 4)", "#define MG_TAP_FT (MG_MAX_NT / 16)",
                  "#define MG_RO_CS(nt) ((nt) * 4 + MG_RO_PAD)", "#define MG_RO_BYTES_N(nt) (MG_NCAND * MG_RO_CS(nt) * 4)"):
-        assert line in internal, line
+        assert line in hostdefs, line
     for line in ("static constexpr int TPWP = 120 / KK < 17 ? 120 / KK : 17;", "static constexpr int TPWS_REGS = 160 / MG_CS_NSP;",
                  "static constexpr int TPWS = TPWS_REGS / KK < 5 ? (TPWS_REGS / KK > 0 ? TPWS_REGS / KK : 1) : 5;",
                  "static constexpr int MAX_TILES = (MG_CS_NPW - 1) * TPWP + MG_CS_NSP * TPWS;", "#define MG_CS_NPW 4 ", "#define MG_CS_NSP 4 "):

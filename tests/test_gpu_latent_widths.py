@@ -23,7 +23,7 @@ N_CU = 256                       # MI355X compute units (BIG_B: two chunk-statio
 KKS = (2, 4, 6, 8, 10, 12, 14, 16)
 
 # ---- the dispatch formulas, restated (kept in step with the C sources by test_table_straddles_every_dispatch_boundary) -------------
-MG_MAX_KK = 16                   # mg_internal.h
+MG_MAX_KK = 16                   # mg_hostdefs.h
 MG_FUSE_MAX_KK = 10              # mg_frames_common.h
 MG_GMM_LDS_MIN_B = 20480         # mg_gmm.hip
 LDS_BUDGET = 160 * 1024
@@ -140,10 +140,10 @@ def _source(name):
 
 def test_table_straddles_every_dispatch_boundary():
     """The formulas restated above match the C sources, and the table has shapes on both sides of every boundary."""
-    host, gmm, common, internal, frames = (_source(n) for n in ("mg_host.hip", "mg_gmm.hip", "mg_frames_common.h", "mg_internal.h",
-                                                                  "mg_frames.hip"))
-    assert "p->KK = (L <= 4 * MG_MAX_KK) ? (((L + 3) / 4 + 1) / 2) * 2 : 0;" in host
-    assert "#define MG_MAX_KK %d " % MG_MAX_KK in internal
+    image, gmm, common, hostdefs, frames = (_source(n) for n in ("mg_primitive_image.h", "mg_gmm.hip", "mg_frames_common.h", "mg_hostdefs.h",
+                                                                   "mg_frames.hip"))
+    assert "p->KK = (L <= 4 * MG_MAX_KK) ? (((L + 3) / 4 + 1) / 2) * 2 : 0;" in image
+    assert "#define MG_MAX_KK %d " % MG_MAX_KK in hostdefs
     assert "#define MG_FUSE_MAX_KK %d " % MG_FUSE_MAX_KK in common
     assert "#define MG_GMM_LDS_MIN_B %d" % MG_GMM_LDS_MIN_B in gmm
     assert "(size_t)p->K * mg_gmm_lds_nf(p->KKg, JT) * 64 + (size_t)p->K * JT * 16 + (size_t)16 * 2 * p->K * 16) * 8;" in gmm

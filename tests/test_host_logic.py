@@ -444,6 +444,18 @@ def test_constraint_set_image_decodes():
     assert done.returncode == 0, done.stdout.decode(errors="replace")
 
 
+def test_primitive_and_grid_images_decode():
+    """csrc/mg_primitive_image.h builds a primitive's and a time grid's device images and the chunk plan as plain host code;
+    tests/native/primitive_image_check.cpp decodes every table at the shapes where an index expression can go wrong, holds the
+    planner to a restatement over a dense sweep of channel counts, grids and options, and pins every refusal's text, code and
+    precedence.  A program of its own, built and run as pack_check is: nothing is loaded into this process."""
+    import subprocess
+    native = os.path.join(ROOT, "tests", "native")
+    subprocess.check_call(["make", "-s", "-C", native, "primitive_image_check"])
+    done = subprocess.run([os.path.join(native, "primitive_image_check")], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=120)
+    assert done.returncode == 0, done.stdout.decode(errors="replace")
+
+
 def test_keyframe_scorers_route_is_the_restated_one():
     """csrc/mg_score_route.h states once which kernel the keyframe scorers launch (VALU / tile / wide), its LDS, the opt-in and the
     grid; tests/native/score_route_check.cpp holds it to a restatement over a dense grid of k-step counts, row tiles, constraint

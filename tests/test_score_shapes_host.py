@@ -32,9 +32,9 @@ def _csrc(name):
 
 def test_restatement_matches_the_source():
     route, score, host, image = _csrc("mg_score_route.h"), _csrc("mg_score.hip"), _csrc("mg_host.hip"), _csrc("mg_constraint_image.h")
-    header, internal = _source("include", "mg_hip.h"), _csrc("mg_internal.h")
+    header, hostdefs = _source("include", "mg_hip.h"), _csrc("mg_hostdefs.h")
     for src, name, value in ((route, "MG_SCORE_WIDE_MIN_B", sc.MG_SCORE_WIDE_MIN_B), (score, "MG_SET_PARAMS_MAX", sc.MG_SET_PARAMS_MAX),
-                             (header, "MG_MAX_CHAIN", sc.MG_MAX_CHAIN), (header, "MG_MAX_POSE_POINTS", sc.MG_MAX_POSE_POINTS), (internal, "MG_MAX_KK", sc.MG_MAX_KK),
+                             (header, "MG_MAX_CHAIN", sc.MG_MAX_CHAIN), (header, "MG_MAX_POSE_POINTS", sc.MG_MAX_POSE_POINTS), (hostdefs, "MG_MAX_KK", sc.MG_MAX_KK),
                              (score, "MG_SC_CANDS", 64), (score, "MG_SC_WAVES", 4), (header, "MG_SCORE_KERNEL_VALU", 0), (header, "MG_SCORE_KERNEL_TILE", 1),
                              (header, "MG_SCORE_KERNEL_WIDE", 2)):
         m = re.search(r"#define %s (\d+)\b" % name, src)
@@ -87,7 +87,7 @@ def test_restatement_matches_the_source():
                  "add_rows(n, al ? 3 + 4 * (int)al_chain.size() : 0)", "if (KK > 0 && rows_total > 0) {", "im.RT = (int32_t)((rows_total + 15) / 16);",
                  'MG_REQUIRE(m <= MG_MAX_CHAIN, "mg_constraint_set_create_fk: constraint %d: chain of %d joints exceeds %d", c, m, MG_MAX_CHAIN);'):
         assert line in image, line
-    assert "p->KK = (L <= 4 * MG_MAX_KK) ? (((L + 3) / 4 + 1) / 2) * 2 : 0;" in host
+    assert "p->KK = (L <= 4 * MG_MAX_KK) ? (((L + 3) / 4 + 1) / 2) * 2 : 0;" in _csrc("mg_primitive_image.h")
 
 
 def _kernel(row, label, B=None):

@@ -38,20 +38,21 @@ def _csrc(name):
 
 def test_restatements_match_the_source():
     walk, score, time, host = _csrc("mg_walk.hip"), _csrc("mg_walk_score.hip"), _csrc("mg_walk_time.hip"), _csrc("mg_host.hip")
-    header, internal = _source("include", "mg_hip.h"), _csrc("mg_internal.h")
+    header, hostdefs = _source("include", "mg_hip.h"), _csrc("mg_hostdefs.h")
     for src, name, value in ((walk, "MG_WALK_TILE", wc.MG_WALK_TILE), (walk, "MG_WALK_BLOCK", wc.MG_WALK_BLOCK), (walk, "MG_WALK_CHAIN_BLOCK", wc.MG_WALK_CHAIN_BLOCK),
                              (time, "MG_WTIME_CHUNK", wc.MG_WTIME_CHUNK), (header, "MG_MAX_CHAIN", wc.MG_MAX_CHAIN), (header, "MG_WALK_MAX_STEPS", wc.MG_WALK_MAX_STEPS),
-                             (internal, "MG_MAX_KK", wc.MG_MAX_KK)):
+                             (hostdefs, "MG_MAX_KK", wc.MG_MAX_KK)):
         m = re.search(r"#define %s (\d+)\b" % name, src)
         assert m and int(m.group(1)) == value, name
     assert "#define MG_WALK_LDS_MAX (160 * 1024 - 64)" in walk and wc.MG_WALK_LDS_MAX == 163776
     assert "#define MG_WSCORE_LDS_MAX (150 * 1024)" in score and "#define MG_WTIME_LDS_MAX (150 * 1024)" in time
     assert "#define MG_WTIME_BS (MG_WTIME_CHUNK + 1)" in time
     assert wc.MG_WALK_TILE == wc._capi.MG_WALK_TILE and wc.MG_WALK_MAX_STEPS == wc._capi.MG_WALK_MAX_STEPS
-    # mg_primitive_create: the k-steps and the control-point rows
+    # mg_primitive_image_build (behind mg_primitive_create): the k-steps and the control-point rows
+    image = _csrc("mg_primitive_image.h")
     for line in ("p->KK = (L <= 4 * MG_MAX_KK) ? (((L + 3) / 4 + 1) / 2) * 2 : 0;", "p->KKg = (Lg <= 4 * MG_MAX_KK) ? (((Lg + 3) / 4 + 1) / 2) * 2 : 0;",
                  "const int NB = d->n_basis, D = d->n_dim, L = d->n_components, K = d->n_gmm, R = NB * D;"):
-        assert line in host, line
+        assert line in image, line
     # mg_walk_frames
     body = walk[walk.index('extern "C" int mg_walk_frames('):walk.index('extern "C" int mg_walk_frames_host(')]
     for line in ("MG_WALK_REQUIRE(n_steps >= 1 && n_steps <= MG_WALK_MAX_STEPS,", "lmax = std::max(lmax, (int)p->L);", "rmax = std::max(rmax, (int)p->R);",
@@ -79,7 +80,7 @@ def test_restatements_match_the_source():
                  "MG_REQUIRE_AS(lds <= MG_WSCORE_LDS_MAX, MG_ERR_UNSUPPORTED,",
                  "if (lds > 64 * 1024) MG_HIP_CHECK(mg_lds_opt_in_once(ctx, MG_LDS_WALK_SCORE, 160 * 1024,"):
         assert line in score, line
-    assert "double *d_Wpack = nullptr;  // [RT][KK][64] MFMA B fragments of W (n_components <= 64)" in internal
+    assert "double *d_Wpack = nullptr;  // [RT][KK][64] MFMA B fragments of W (n_components <= 64)" in _csrc("mg_internal.h")
     # mg_score_walk_time
     for line in ("MG_WTIME_REFUSE(p->K <= 0 || !p->d_gPpack || p->KKg < 2 || p->KKg > MG_MAX_KK || (p->KKg & 1) || (size_t)p->K * 16 * 16 > 60 * 1024,",
                  "d.KKg = p->KKg; d.JT = (p->Lg + 15) / 16;", "kmax = std::max(kmax, (int)p->K);", "int kmax = 1;",

@@ -323,7 +323,13 @@ int mg_device_placement_info(mg_context *ctx, const void *buf_dev, double *info4
 int mg_memcpy_h2d(mg_context *ctx, void *dst_dev, const void *src, int64_t bytes);
 int mg_memcpy_d2h(mg_context *ctx, void *dst, const void *src_dev, int64_t bytes);
 /* rows x row_bytes from one device matrix into another, each with its own pitch in bytes (a column block of a row-major matrix);
- * asynchronous on the context's stream */
+ * asynchronous on the context's stream.  It is the runtime's 2-D copy (hipMemcpy2DAsync), and that copy rejects -- "invalid
+ * argument", MG_ERR_HIP, nothing copied -- a source or destination that lies in memory mapped from SEVERAL physical chunks through
+ * the virtual-memory API, whatever the pitch (measured on an MI355X: a 986 MB source of 32 MiB or 2 MiB chunks and a 6 MB
+ * destination of 2 MiB chunks fail, one 1 GiB chunk and plain allocations pass).  Such memory comes from mg_device_malloc_chunked
+ * with a chunk smaller than the buffer and, on devices where the arena's scan settles on that recipe, from any allocation of 64 MiB
+ * and more (mg_device_malloc, mg_device_malloc_placed: csrc/mg_placement.hip); MG_OPT_PLAIN_MALLOC keeps mg_device_malloc's
+ * buffers out of it.  A caller that must gather from such a buffer uses a kernel or an indexed gather of its own. */
 int mg_memcpy_d2d_rows(mg_context *ctx, void *dst_dev, int64_t dst_pitch, const void *src_dev, int64_t src_pitch, int64_t row_bytes, int64_t rows);
 int mg_memset(mg_context *ctx, void *dst_dev, int value, int64_t bytes);
 
@@ -334,7 +340,8 @@ int mg_memset(mg_context *ctx, void *dst_dev, int value, int64_t bytes);
  *       4 = gmm_sample, 5 = spline_evaluate, 6 = fused step, 7 = a planner step in one launch (mg_options_step),
  *       8 = mg_joint_tracks, 9 = mg_score_frame_constraints, 10 = mg_score_trajectory[_points],
  *       11 = mg_cluster_tree_search (both tree kinds: mg_tree_search_kernel or mg_kd_tree_search_kernel),
- *       12 = the frames kernel of mg_walk_frames, 13 = mg_score_walk_time, 14 = mg_step_lengths, 15 = mg_feature_points. */
+ *       12 = the frames kernel of mg_walk_frames, 13 = mg_score_walk_time, 14 = mg_step_lengths, 15 = mg_feature_points,
+ *       16 = mg_feature_points_warped. */
 int mg_profile_enable(mg_context *ctx, int enabled);
 int mg_profile_reset(mg_context *ctx);
 int mg_profile_get(mg_context *ctx, int slot, double *total_ms, int64_t *launches);
@@ -1193,9 +1200,9 @@ int mg_walk_time_table_uploads(mg_context *ctx, int64_t *uploads);   /* mg_conte
 
 /* The per-call descriptor tables a context keeps on the device, each rewritten only when a call's table differs from the last call's:
  * of mg_options_step's one-launch path, mg_cluster_tree_search, mg_walk_frames, mg_score_walk_residuals, mg_score_walk_time and
- * mg_step_lengths, and of mg_feature_points.  mg_context_table_uploads: how often table `which` of the context went to the device so far. */
+ * mg_step_lengths, of mg_feature_points and of mg_feature_points_warped.  mg_context_table_uploads: how often table `which` of the context went to the device so far. */
 enum { MG_TABLE_FUSED = 0, MG_TABLE_TREE = 1, MG_TABLE_WALK = 2, MG_TABLE_WALK_SCORE = 3, MG_TABLE_WALK_TIME = 4, MG_TABLE_STEP_LENGTH = 5,
-       MG_TABLE_FEATURE_POINTS = 6, MG_TABLE_COUNT = 7 };
+       MG_TABLE_FEATURE_POINTS = 6, MG_TABLE_FEATURE_POINTS_WARPED = 7, MG_TABLE_COUNT = 8 };
 int mg_context_table_uploads(mg_context *ctx, int which, int64_t *uploads);
 
 /* Step lengths without frames in memory, ONE launch for every candidate of every item (csrc/mg_step_length.hip): what
@@ -1283,6 +1290,55 @@ typedef struct {
 } mg_feature_point_item;
 int mg_feature_points(int32_t n_items, const mg_feature_point_item *items, int latent_dtype);
 
+/* Feature points of the TIME-WARPED motion, no time function and no frame in memory, ONE launch for every candidate of every item
+ * (csrc/mg_feature_points.hip): what the reference's FeaturePointModel takes from back_project(s, use_time_parameters=True) -- its
+ * default -- on a primitive with a time model.  A latent row holds the item's n_components spatial latents from latent_offset on and
+ * its n_time_components time latents gamma from time_offset on (the reference's layout: time_offset = latent_offset + n_components).
+ * Per candidate, float64 throughout, every operation rounded on its own (float32 latents are converted first):
+ *   time function   x(i) = t(i), i = 0 .. F - 1: the running sum of exp(mean_t(i) + phi(i) . gamma) minus 1: the statement and the
+ *                   bits of mg_time_function_canonical;
+ *   n_frames        num + 2, num = int(round(x(F - 2))): the length of the warped motion (speed 1); 0 for a time function that is not
+ *                   finite or asks for more than 2^24 samples (mg_time_function_sample's test);
+ *   time_mid        the canonical time of frame frame_idx of the warped motion: 0 for frame_idx = 0, F - 1 for frame_idx =
+ *                   n_frames - 1, else the not-a-knot cubic through (x(i), i) at numpy.linspace(1, x(F - 2), num)[frame_idx - 1]: the
+ *                   statements and the bits of mg_time_function_sample's times[frame_idx] (csrc/mg_timewarp_device.h states both);
+ *                   NaN for frame_idx >= n_frames (the reference's indexing raises IndexError there);
+ *   frames          at the times 0, time_mid and F - 1 (NOT F, the canonical grid's last sample): control points mean' then
+ *                   fma(E'[k], s[k], .) for k ascending, the basis row by the FITPACK recurrence, four taps: the statements and the
+ *                   bits of mg_back_project_frames_at at those times;
+ *   start_root, points, root_end, heading_end, heading_len   as in mg_feature_points, on those three frames.
+ * n_frames = 0: NaN in every output of the candidate.  A spatial latent that is not finite: NaN in start_root, points, root_end,
+ * heading_end and heading_len; n_frames and time_mid are stated.  frame_idx >= n_frames: NaN in points and time_mid only.  Nothing
+ * else is NaN for such a row, and a candidate's values depend on neither the batch nor the other items nor its position in either.
+ * Nothing per candidate goes to device memory but the outputs: no time function, no frame.
+ * Everything is checked before any launch or copy.  MG_ERR_INVALID_ARGUMENT: what mg_feature_points refuses so (but frame_idx has no
+ * upper bound here: the warped length is the candidate's), frame_idx < 0, time_offset < 0 or time_offset + n_time_components > ld,
+ * spatial and time columns that overlap, a primitive without a time model, all outputs NULL.  MG_ERR_UNSUPPORTED, never an
+ * approximate answer: what mg_feature_points refuses so, fewer than 4 or more than MG_FEATURE_POINTS_WARPED_MAX_F canonical frames (a
+ * workgroup keeps 3 F doubles of each of its 16 candidates in LDS for the inversion), tables that do not fit LDS.  Empty items,
+ * slices of MG_FEATURE_POINTS_MAX_ITEMS items and the device table (MG_TABLE_FEATURE_POINTS_WARPED) as in mg_feature_points; the
+ * call allocates nothing else and does not synchronise.  Profile slot 16. */
+#define MG_FEATURE_POINTS_WARPED_MAX_F 256
+typedef struct {
+    mg_primitive *prim;
+    const void *latents_dev;            /* (n_samples, ld) float32 / float64 */
+    int64_t latent_offset;              /* first column of this item's n_components spatial latents in a row */
+    int64_t n_samples, ld;
+    const mg_skeleton_desc *skeleton;   /* HOST; NULL allowed with n_joints = 0 */
+    const int32_t *joints;              /* HOST (n_joints) indices into the skeleton */
+    int32_t n_joints;
+    int32_t frame_idx;                  /* frame of `points` in the WARPED motion, >= 0 */
+    double *start_root_dev;             /* (n_samples, 3) or NULL */
+    double *points_dev;                 /* (n_samples, 3 n_joints); NULL exactly when n_joints = 0 */
+    double *root_end_dev;               /* (n_samples, 2) or NULL */
+    double *heading_end_dev;            /* (n_samples, 2) or NULL */
+    double *heading_len_dev;            /* (n_samples) or NULL */
+    int64_t time_offset;                /* first column of this item's n_time_components time latents in a row */
+    double *time_mid_dev;               /* (n_samples) or NULL */
+    int32_t *n_frames_dev;              /* (n_samples) or NULL */
+} mg_warped_feature_point_item;
+int mg_feature_points_warped(int32_t n_items, const mg_warped_feature_point_item *items, int latent_dtype);
+
 /* ---- host-pointer convenience variants (H2D, launch, D2H, synchronise) ---------------- */
 /* mg_step_lengths with every item's latents and outputs in host memory (the `_dev` members are host pointers here); items that name
  * the same latent matrix (pointer, n_samples and ld) share one copy of it on the device */
@@ -1290,6 +1346,8 @@ int mg_step_lengths_host(int32_t n_items, const mg_step_length_item *items, int 
 /* mg_feature_points with every item's latents and outputs in host memory (the `_dev` members are host pointers here); items that
  * name the same latent matrix (pointer, n_samples and ld) share one copy of it on the device */
 int mg_feature_points_host(int32_t n_items, const mg_feature_point_item *items, int latent_dtype);
+/* mg_feature_points_warped in the same way */
+int mg_feature_points_warped_host(int32_t n_items, const mg_warped_feature_point_item *items, int latent_dtype);
 /* mg_score_walk_time with host arrays: latents, outputs and every step's spatial latents (`spatial_dev` is a host pointer here) */
 int mg_score_walk_time_host(int32_t n_steps, const mg_walk_time_step *steps, const void *latents, int latent_dtype, int64_t n_samples, int64_t ld,
                             int32_t n_constraints, const mg_walk_time_constraint *constraints, double start_keyframe, double frame_time,

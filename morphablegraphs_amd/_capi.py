@@ -39,8 +39,10 @@ MG_CONSTRAINT_JOINT_MIDPOINT, MG_CONSTRAINT_JOINT_ORIENTATION, MG_CONSTRAINT_LOO
 MG_CONSTRAINT_VALUE_POSITION, MG_CONSTRAINT_VALUE_HEADING = 7, 8   # values of the aligned motion, not errors (chained graph-walk steps)
 PROFILE_SLOTS = {"frames": 0, "gmm_log_prob": 1, "score_constraints": 2, "argmin": 3,
                  "gmm_sample": 4, "spline_evaluate": 5, "step": 6, "options_step": 7, "joint_tracks": 8, "frame_constraints": 9, "trajectory": 10,
-                 "cluster_tree_search": 11, "walk_frames": 12, "walk_time": 13, "step_lengths": 14, "feature_points": 15}
-DEVICE_TABLES = {"fused": 0, "tree": 1, "walk": 2, "walk_score": 3, "walk_time": 4, "step_length": 5, "feature_points": 6}    # MG_TABLE_* (include/mg_hip.h)
+                 "cluster_tree_search": 11, "walk_frames": 12, "walk_time": 13, "step_lengths": 14, "feature_points": 15,
+                 "feature_points_warped": 16}
+DEVICE_TABLES = {"fused": 0, "tree": 1, "walk": 2, "walk_score": 3, "walk_time": 4, "step_length": 5, "feature_points": 6,
+                 "feature_points_warped": 7}    # MG_TABLE_* (include/mg_hip.h)
 MG_TREE_MAX_DEPTH, MG_TREE_MAX_CHILDREN, MG_TREE_MAX_CANDIDATES = 64, 256, 64    # include/mg_hip.h
 MG_TREE_TIE, MG_TREE_NO_RESULT, MG_TREE_OVERFLOW, MG_TREE_NO_MEAN = 1, 2, 4, 8
 MG_KD_MAX_DEPTH = 64
@@ -53,6 +55,7 @@ MG_STEP_LENGTH_MAX_ITEMS = 256   # non-empty items of one mg_step_lengths launch
 MG_FEATURE_POINTS_MAX_ITEMS = 256   # non-empty items of one mg_feature_points launch (include/mg_hip.h); a call with more goes in slices
 MG_FEATURE_POINTS_MAX_JOINTS = 32   # listed joints of one item
 MG_FEATURE_POINTS_TILE = 16         # candidates per workgroup of mg_feature_points_kernel (csrc/mg_feature_points.hip)
+MG_FEATURE_POINTS_WARPED_MAX_F = 256   # canonical frames mg_feature_points_warped inverts in LDS (include/mg_hip.h)
 
 
 @functools.lru_cache(maxsize=None)
@@ -98,7 +101,7 @@ EXPORTED_SYMBOLS = [
     "mg_score_walk_residuals", "mg_score_walk_residuals_host", "mg_score_walk_residuals_steps", "mg_score_walk_residuals_steps_host",
     "mg_score_walk_time", "mg_score_walk_time_host", "mg_walk_time_table_uploads", "mg_context_table_uploads",
     "mg_step_lengths", "mg_step_lengths_host",
-    "mg_feature_points", "mg_feature_points_host",
+    "mg_feature_points", "mg_feature_points_host", "mg_feature_points_warped", "mg_feature_points_warped_host",
 ]
 
 
@@ -416,6 +419,8 @@ def load_library(path=None):
         "mg_step_lengths_host": [i32, vp, i32],
         "mg_feature_points": [i32, vp, i32],
         "mg_feature_points_host": [i32, vp, i32],
+        "mg_feature_points_warped": [i32, vp, i32],
+        "mg_feature_points_warped_host": [i32, vp, i32],
     }
     for name, argtypes in sigs.items():
         fn = getattr(lib, name)
@@ -1177,38 +1182,82 @@ def feature_point_widths(n_joints):
     return {"start_root": 3, "points": 3 * int(n_joints), "root_end": 2, "heading_end": 2, "heading_len": 1}
 
 
+def _feature_point_table(items, outputs, known, record, fill):
+    """What feature_points and feature_points_warped share: the `record` table over the items' latents and joint lists, one array per
+    wanted output; fill(rec, it, S, n_joints) sets the members only one of them has and returns its own outputs' {name: (shape,
+    dtype)}.  Returns (table, per-item arrays, things to keep alive, latent dtype)."""
+    unknown = [o for o in outputs if o not in known]
+    if unknown:
+        raise ValueError("unknown outputs %r" % (unknown,))
+    if not items:
+        return None, [], [], None
+    prepared = [(it, _latents(it["S"])) for it in items]
+    dtypes = set(S.dtype for _, S in prepared)
+    if len(dtypes) != 1:
+        raise TypeError("the items of one call share a latent dtype, got %s" % sorted(str(d) for d in dtypes))
+    table = (record * len(prepared))()
+    keep, out = [], []
+    for rec, (it, S) in zip(table, prepared):
+        sk, joints = it.get("skeleton"), it.get("joints") or []
+        idx = sk.indices(joints) if joints else np.zeros(0, dtype=np.int32)
+        desc = sk.desc() if sk is not None else None
+        keep.append((idx, desc, sk, S))
+        rec.prim, rec.latents, rec.latent_offset, rec.n_samples, rec.ld = it["prim"].handle.value, S.ctypes.data, int(it.get("latent_offset", 0)), S.shape[0], S.shape[1]
+        rec.skeleton = C.addressof(desc) if desc is not None else None
+        rec.joints, rec.n_joints, rec.frame_idx = (idx.ctypes.data if len(idx) else None), len(idx), int(it.get("frame_idx", 0))
+        shapes = {name: ((S.shape[0], width) if name != "heading_len" else (S.shape[0],), np.float64)
+                  for name, width in feature_point_widths(len(idx)).items() if width > 0}
+        shapes.update(fill(rec, it, S, len(idx)))
+        arrays = {}
+        for name, (shape, dtype) in shapes.items():
+            if name in outputs:
+                arrays[name] = np.empty(shape, dtype=dtype)
+                setattr(rec, name, arrays[name].ctypes.data)
+        out.append(arrays)
+    return table, out, keep, dtypes.pop()
+
+
 def feature_points(items, outputs=FEATURE_POINT_OUTPUTS):
     """The feature points of every candidate of every item in one mg_feature_points call.  items: dicts with prim (a Primitive),
     S (n, ld) float32 or float64 latents (one dtype for the call), and optionally latent_offset (0), skeleton (a Skeleton), joints
     (names or indices, default none) and frame_idx (0).  Items that pass the same array share one copy of it on the device.  Returns
     per item a dict of float64 arrays: start_root (n, 3), points (n, 3 J; only with joints), root_end (n, 2), heading_end (n, 2),
     heading_len (n,), those of `outputs`."""
-    unknown = [o for o in outputs if o not in FEATURE_POINT_OUTPUTS]
-    if unknown:
-        raise ValueError("unknown outputs %r" % (unknown,))
-    if not items:
-        return []
-    prepared = [(it, _latents(it["S"])) for it in items]
-    dtypes = set(S.dtype for _, S in prepared)
-    if len(dtypes) != 1:
-        raise TypeError("the items of one call share a latent dtype, got %s" % sorted(str(d) for d in dtypes))
-    table = (FeaturePointItem * len(prepared))()
-    keep, out = [], []
-    for rec, (it, S) in zip(table, prepared):
-        sk, joints = it.get("skeleton"), it.get("joints") or []
-        idx = sk.indices(joints) if joints else np.zeros(0, dtype=np.int32)
-        desc = sk.desc() if sk is not None else None
-        keep.append((idx, desc, sk))
-        rec.prim, rec.latents, rec.latent_offset, rec.n_samples, rec.ld = it["prim"].handle.value, S.ctypes.data, int(it.get("latent_offset", 0)), S.shape[0], S.shape[1]
-        rec.skeleton = C.addressof(desc) if desc is not None else None
-        rec.joints, rec.n_joints, rec.frame_idx = (idx.ctypes.data if len(idx) else None), len(idx), int(it.get("frame_idx", 0))
-        arrays = {}
-        for name, width in feature_point_widths(len(idx)).items():
-            if name in outputs and width > 0:
-                arrays[name] = np.empty((S.shape[0], width) if name != "heading_len" else (S.shape[0],), dtype=np.float64)
-                setattr(rec, name, arrays[name].ctypes.data)
-        out.append(arrays)
-    feature_points_table(prepared[0][0]["prim"].lib, len(prepared), table, dtypes.pop())
+    table, out, keep, dtype = _feature_point_table(items, outputs, FEATURE_POINT_OUTPUTS, FeaturePointItem, lambda rec, it, S, n_joints: {})
+    if items:
+        feature_points_table(items[0]["prim"].lib, len(items), table, dtype)
+    return out
+
+
+class WarpedFeaturePointItem(C.Structure):   # struct mg_warped_feature_point_item
+    _fields_ = FeaturePointItem._fields_ + [("time_offset", C.c_int64), ("time_mid", C.c_void_p), ("n_frames", C.c_void_p)]
+
+
+WARPED_FEATURE_POINT_OUTPUTS = FEATURE_POINT_OUTPUTS + ("time_mid", "n_frames")
+
+
+def feature_points_warped_table(lib, n_items, table, latent_dtype, host=True):
+    """mg_feature_points_warped_host (host pointers in the table; synchronises) or mg_feature_points_warped (device pointers;
+    asynchronous on the context's stream) on a (WarpedFeaturePointItem * n) table as it stands; table None passes NULL."""
+    code = MG_F64 if np.dtype(latent_dtype) == np.float64 else MG_F32
+    fn = lib.mg_feature_points_warped_host if host else lib.mg_feature_points_warped
+    _check(fn(int(n_items), C.cast(table, C.c_void_p) if table is not None else None, code))
+
+
+def feature_points_warped(items, outputs=WARPED_FEATURE_POINT_OUTPUTS):
+    """The feature points of the TIME-WARPED motion of every candidate of every item in one mg_feature_points_warped call: items as
+    for feature_points, on primitives with a time model; a row of S holds the spatial latents from latent_offset on and the time
+    latents from time_offset on (default: right behind the spatial ones), frame_idx counts the warped motion's frames.  Returns per
+    item what feature_points returns, and time_mid (n,) float64 -- the canonical time of frame frame_idx, NaN where the candidate's
+    motion is shorter -- and n_frames (n,) int32, the warped length (0: no time function)."""
+    def fill(rec, it, S, n_joints):
+        off = it.get("time_offset")
+        rec.time_offset = int(off) if off is not None else int(it.get("latent_offset", 0)) + it["prim"].n_components
+        return {"time_mid": ((S.shape[0],), np.float64), "n_frames": ((S.shape[0],), np.int32)}
+
+    table, out, keep, dtype = _feature_point_table(items, outputs, WARPED_FEATURE_POINT_OUTPUTS, WarpedFeaturePointItem, fill)
+    if items:
+        feature_points_warped_table(items[0]["prim"].lib, len(items), table, dtype)
     return out
 
 

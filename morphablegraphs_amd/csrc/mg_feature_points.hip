@@ -27,6 +27,7 @@
 #include "mg_items.h"
 #include "mg_pack.h"
 #include "mg_score_device.h"
+#include "mg_timewarp_device.h"
 
 #define MG_FP_TILE 16                    // candidates per workgroup
 #define MG_FP_LDS_MAX (150 * 1024)
@@ -163,7 +164,8 @@ struct mg_fp_plan {
 };
 
 // the argument errors of one item's joint list (MG_ERR_INVALID_ARGUMENT)
-static int mg_fp_check_joints(const char *who, int i, const mg_feature_point_item &q) {
+template <class Item>
+static int mg_fp_check_joints(const char *who, int i, const Item &q) {
     MG_ITEM_REQUIRE(q.n_joints >= 0 && q.n_joints <= MG_FEATURE_POINTS_MAX_JOINTS, "%s: item %d: %d joints (0 .. %d)", who, i, q.n_joints,
                     MG_FEATURE_POINTS_MAX_JOINTS);
     MG_ITEM_REQUIRE((q.n_joints > 0) == (q.points_dev != nullptr), "%s: item %d: %d joints and %s points output", who, i, q.n_joints,
@@ -179,6 +181,36 @@ static int mg_fp_check_joints(const char *who, int i, const mg_feature_point_ite
         MG_ITEM_REQUIRE(st == MG_CHAIN_OK, "%s: item %d: joint %d%s", who, i, bad, mg_chain_why(st));
     }
     return MG_OK;
+}
+
+// the chains of an item's listed joints (checked: mg_fp_check_joints); wanted(qc): every quaternion channel along them
+template <class Item, class Wanted>
+static int mg_fp_chains_of(const char *who, int i, const Item &q, std::vector<std::vector<int>> &chains, Wanted wanted) {
+    const mg_skeleton_desc *sk = q.skeleton;
+    chains.assign((size_t)q.n_joints, std::vector<int>());
+    for (int j = 0; j < q.n_joints; j++) {
+        mg_joint_chain(sk->parents, sk->n_joints, q.joints[j], chains[(size_t)j]);
+        const int m = (int)chains[(size_t)j].size() - 1;
+        MG_ITEM_REFUSE(m > MG_MAX_CHAIN, "%s: item %d: chain of %d joints exceeds %d", who, i, m, MG_MAX_CHAIN);
+        for (int k = 0; k < m; k++) {
+            const int qc = sk->quat_channel[chains[(size_t)j][(size_t)k]];
+            if (qc >= 0) wanted(qc);
+        }
+    }
+    return MG_OK;
+}
+
+// ... and their records (mg_fk_position_table's layout), all as long as the longest chain's
+static void mg_fp_records_of(const mg_skeleton_desc *sk, const std::vector<std::vector<int>> &chains, int32_t &rec_stride, std::vector<double> &rec) {
+    size_t longest = 0;
+    for (const std::vector<int> &ch : chains) longest = std::max(longest, ch.size() - 1);
+    rec_stride = MG_FP_REC_HDR + 4 * (int32_t)longest;
+    rec.assign(chains.size() * rec_stride, 0.0);
+    for (size_t j = 0; j < chains.size(); j++) {
+        double *r = &rec[j * rec_stride];
+        r[4] = (double)(chains[j].size() - 1);
+        mg_chain_links(chains[j], sk->offsets, [&](int joint) { return sk->quat_channel[joint]; }, r + MG_FP_REC_HDR);
+    }
 }
 
 // the plan of one item whose arguments passed; what the kernels do not take is MG_ERR_UNSUPPORTED
@@ -217,18 +249,9 @@ static int mg_fp_plan_of(const char *who, int i, const mg_feature_point_item &q,
     want(0, 0, 3);
     want(1, 0, 3);
     want(2, 0, 7);
-    std::vector<std::vector<int>> chains((size_t)q.n_joints);
-    int longest = 0;
-    for (int j = 0; j < q.n_joints; j++) {
-        mg_joint_chain(sk->parents, sk->n_joints, q.joints[j], chains[(size_t)j]);
-        const int m = (int)chains[(size_t)j].size() - 1;
-        MG_ITEM_REFUSE(m > MG_MAX_CHAIN, "%s: item %d: chain of %d joints exceeds %d", who, i, m, MG_MAX_CHAIN);
-        longest = std::max(longest, m);
-        for (int k = 0; k < m; k++) {
-            const int qc = sk->quat_channel[chains[(size_t)j][(size_t)k]];
-            if (qc >= 0) want(1, qc, 4);
-        }
-    }
+    std::vector<std::vector<int>> chains;
+    const int rc = mg_fp_chains_of(who, i, q, chains, [&](int qc) { want(1, qc, 4); });
+    if (rc != MG_OK) return rc;
     pl.map.assign((size_t)pl.NCP * D, -1);
     for (int c = 0; c < pl.NCP; c++)
         for (int d = 0; d < D; d++)
@@ -237,13 +260,7 @@ static int mg_fp_plan_of(const char *who, int i, const mg_feature_point_item &q,
                 pl.src.push_back(cps[(size_t)c] * D + d);
             }
     pl.NRS = (int32_t)pl.src.size();
-    pl.rec_stride = MG_FP_REC_HDR + 4 * longest;
-    pl.rec.assign((size_t)q.n_joints * pl.rec_stride, 0.0);
-    for (int j = 0; j < q.n_joints; j++) {
-        double *rec = &pl.rec[(size_t)j * pl.rec_stride];
-        rec[4] = (double)(chains[(size_t)j].size() - 1);
-        mg_chain_links(chains[(size_t)j], sk->offsets, [&](int joint) { return sk->quat_channel[joint]; }, rec + MG_FP_REC_HDR);
-    }
+    mg_fp_records_of(sk, chains, pl.rec_stride, pl.rec);
     MG_ITEM_REFUSE((int64_t)p->L * pl.NRS > (1 << 20) || mg_fp_layout_of(p->L, pl.NRS, pl.NCP, D, q.n_joints, pl.rec_stride).total_bytes > MG_FP_LDS_MAX,
                    "%s: item %d: the tables (%d x %d control-point values, %d joints) do not fit LDS", who, i, p->L, pl.NRS, q.n_joints);
     MG_ITEM_REFUSE_GRID(who, i, q.n_samples, MG_FP_TILE);
@@ -337,4 +354,401 @@ extern "C" int mg_feature_points_host(int32_t n_items, const mg_feature_point_it
                                           {&item::heading_end_dev, 2, nullptr}, {&item::heading_len_dev, 1, nullptr}};
     return mg_items_host("mg_feature_points_host", n_items, items, latent_dtype, outs,
                          [&](const item *dev) { return mg_fp_run("mg_feature_points_host", n_items, dev, latent_dtype, plans); });
+}
+
+// ---- the time-warped motion ---------------------------------------------------------------------------------------------------------
+// mg_feature_points_warped: the same features of back_project(s, use_time_parameters=True) -- frame 0 at time 0, frame -1 at time
+// F - 1, frame frame_idx at a time of the candidate's own: the frame_idx-th sample of the inverse of its canonical time function
+// (mg_timewarp_device.h).  A workgroup owns MG_FP_TILE candidates of one item, as above:
+//
+//   constants   the rows of E' the two END frames touch (host-planned: their times do not depend on the candidate), their means and
+//               tap rows, the chain records, the channels the mid frame is wanted for
+//   warp 1      increments exp(mean_t(i) + phi(i) . gamma), one (canonical frame, candidate) per thread, into x[i][cand]
+//   warp 2      ONE LANE PER CANDIDATE (the tile's 16 lanes of wave 0): running sum, sample count, the sample point of frame_idx and
+//               its interval, the tridiagonal sweep (x, cp, dp: 3 F doubles per candidate, [i][cand] so the 16 lanes read
+//               consecutive doubles), the back-substitution down to that interval only, the sample -> time_mid, n_frames; the basis
+//               row of time_mid.  Meanwhile waves 1 .. 3 form the end frames' control points (phase 1 above)
+//   mid         the tap window differs per candidate, so no row list: one (candidate, channel) per thread forms its four control
+//               points straight from E' in global memory (L2: consecutive threads read consecutive channels of one row of E') and
+//               takes the four taps -> mid[cand][channel]
+//   phase 2     as above, the mid frame's channels from mid[][]
+// An item without joints and without the time_mid output needs no sample: its lanes stop after the count, and x alone is kept.
+#define MG_FPW_SLOTS 2                   // the host-planned frames: time 0, time F - 1
+
+struct mg_fpw_item {
+    const double *Et, *mean, *knots, *tphi, *tmean;
+    const void *lat, *gam;               // the item's first spatial / first time latent: row b at + b * ld
+    double *start_root, *points, *root_end, *heading_end, *heading_len, *time_mid;
+    int32_t *n_frames;
+    int64_t n, ld;
+    double w[MG_FPW_SLOTS * 4];
+    int32_t tap[MG_FPW_SLOTS];
+    int32_t L, Lt, D, R, F, NB, J, NRS, NCP, NC;   // NC: channels of the mid frame
+    int32_t frame_idx, need_mid, rec_stride;
+    int32_t wg0;
+    uint32_t off_src, off_map, off_rec, off_chan;   // ..., int32 chan[NC] (the mid frame's channels, ascending), pos[D] (where a channel sits among them)
+};
+
+struct mg_fpw_args {
+    const char *base;
+    const mg_fpw_item *items;
+    int32_t n_items;
+};
+
+struct mg_fpw_layout {
+    int x, cpt, dpt, gam, tmid, wm, E, mean, w, lat, cp, mid, rec, ints, total_bytes;
+    int CS, MS;
+};
+__host__ __device__ static inline mg_fpw_layout mg_fpw_layout_of(int F, int Lt, int need_mid, int L, int NRS, int NCP, int NC, int D, int J, int rec_stride) {
+    mg_fpw_layout y;
+    y.CS = NRS | 1;
+    y.MS = NC | 1;
+    y.x = 0;
+    y.cpt = y.x + F * MG_FP_TILE;
+    y.dpt = y.cpt + (need_mid ? F * MG_FP_TILE : 0);
+    y.gam = y.dpt + (need_mid ? F * MG_FP_TILE : 0);
+    y.tmid = y.gam + MG_FP_TILE * Lt;
+    y.wm = y.tmid + MG_FP_TILE;
+    y.E = y.wm + MG_FP_TILE * 4;
+    y.mean = y.E + L * NRS;
+    y.w = y.mean + NRS;
+    y.lat = y.w + MG_FPW_SLOTS * 4;
+    y.cp = y.lat + MG_FP_TILE * L;
+    y.mid = y.cp + MG_FP_TILE * y.CS;
+    y.rec = y.mid + MG_FP_TILE * y.MS;
+    y.ints = y.rec + J * rec_stride;     // then int32: map[NCP * D], chan[NC], pos[D], tap[MG_FPW_SLOTS], bad[TILE], nf[TILE], i0[TILE]
+    y.total_bytes = y.ints * 8 + (NCP * D + NC + D + MG_FPW_SLOTS + 3 * MG_FP_TILE) * 4;
+    return y;
+}
+
+template <bool LAT_F64>
+__global__ __launch_bounds__(256) void mg_feature_points_warped_kernel(const mg_fpw_args a) {
+#pragma clang fp contract(off)
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int tid = threadIdx.x;
+    const mg_fpw_item *ip = a.items + mg_item_of_workgroup(a.items, a.n_items);
+    const int L = ip->L, Lt = ip->Lt, D = ip->D, F = ip->F, J = ip->J, NRS = ip->NRS, NCP = ip->NCP, NC = ip->NC, RS = ip->rec_stride;
+    const int frame_idx = ip->frame_idx, need_mid = ip->need_mid;
+    const int64_t n = ip->n, ld = ip->ld;
+    const size_t R = (size_t)ip->R;
+    const mg_fpw_layout y = mg_fpw_layout_of(F, Lt, need_mid, L, NRS, NCP, NC, D, J, RS);
+    const int CS = y.CS, MS = y.MS;
+    double *sm = (double *)smem;
+    double *sx = sm + y.x, *scpt = sm + y.cpt, *sdpt = sm + y.dpt, *sgam = sm + y.gam, *stmid = sm + y.tmid, *swm = sm + y.wm;
+    double *sE = sm + y.E, *smean = sm + y.mean, *sw = sm + y.w, *slat = sm + y.lat, *scp = sm + y.cp, *smid = sm + y.mid, *srec = sm + y.rec;
+    int32_t *smap = (int32_t *)(sm + y.ints), *schan = smap + NCP * D, *spos = schan + NC, *stap = spos + D, *sbad = stap + MG_FPW_SLOTS;
+    int32_t *snf = sbad + MG_FP_TILE, *si0 = snf + MG_FP_TILE;
+    int ncand;
+    const int64_t b0 = mg_item_tile_of<MG_FP_TILE>(ip->wg0, n, ncand);
+    const double *Et = ip->Et, *mean = ip->mean;
+
+    // the item's constants and the tile's latents
+    {
+        const int32_t *src = (const int32_t *)(a.base + ip->off_src), *map = (const int32_t *)(a.base + ip->off_map);
+        const int32_t *chan = (const int32_t *)(a.base + ip->off_chan);
+        const double *rec = (const double *)(a.base + ip->off_rec);
+        for (int e = tid; e < L * NRS; e += 256) {
+            const int k = e / NRS, j = e - k * NRS;
+            sE[e] = Et[(size_t)k * R + (size_t)src[j]];
+        }
+        for (int j = tid; j < NRS; j += 256) smean[j] = mean[src[j]];
+        for (int e = tid; e < NCP * D; e += 256) smap[e] = map[e];
+        for (int e = tid; e < NC + D; e += 256) schan[e] = chan[e];      // (chan, then pos)
+        for (int e = tid; e < J * RS; e += 256) srec[e] = rec[e];
+        if (tid < MG_FPW_SLOTS * 4) sw[tid] = ip->w[tid];
+        if (tid < MG_FPW_SLOTS) stap[tid] = ip->tap[tid];
+        if (tid < MG_FP_TILE) sbad[tid] = 0;
+    }
+    __syncthreads();
+    mg_item_stage_latents<LAT_F64>(ip->lat, ld, b0, ncand, L, slat, sbad);
+    for (int e = tid; e < ncand * Lt; e += 256) {                        // the time latents carry no flag: one that is not finite shows in the count
+        const int c = e / Lt, k = e - c * Lt;
+        sgam[e] = mg_load_lat<LAT_F64>(ip->gam, (b0 + c) * ld + k);
+    }
+    __syncthreads();
+
+    // warp 1: the increments, x[i][cand]
+    for (int e = tid; e < F * MG_FP_TILE; e += 256) {
+        const int i = e / MG_FP_TILE, c = e - i * MG_FP_TILE;
+        if (c < ncand) {
+            const double *g = sgam + c * Lt;
+            sx[e] = mg_tw_increment(ip->tphi, ip->tmean, i, Lt, [&](int l) { return g[l]; });
+        }
+    }
+    __syncthreads();
+
+    if (tid < 64) {
+        // warp 2: one lane per candidate
+        if (tid < ncand) {
+            const int c = tid;
+            const mg_tw_strided x = {sx + c, MG_FP_TILE};
+            mg_tw_running_sum(x, x, F);
+            const double stop = x[F - 2];
+            int num = 0, T = 0, i0 = 0;
+            double tmid = NAN;
+            if (mg_tw_sample_count(stop, 1.0, num)) {
+                T = num + 2;
+                if (frame_idx == 0) tmid = 0.0;
+                else if (frame_idx == T - 1) tmid = (double)(F - 1);
+                else if (frame_idx < T && need_mid) {
+                    const double t = mg_tw_sample_point(frame_idx - 1, num, stop, mg_tw_sample_step(stop, num));
+                    const int i = mg_tw_interval(x, F, t);
+                    const mg_tw_strided cpt = {scpt + c, MG_FP_TILE}, dpt = {sdpt + c, MG_FP_TILE};
+                    const int top = F - 3 > 1 ? F - 3 : 1;
+                    mg_tw_second_derivatives(x, dpt, cpt, dpt, F, i < 1 ? 1 : (i > top ? top : i));   // (M takes dp's place)
+                    tmid = mg_tw_inverse_at(x, dpt, i, t);
+                }
+            }
+            const bool mid_ok = T > 0 && frame_idx < T;
+            if (mid_ok && NC > 0) mg_basis_row_dev(ip->knots, ip->NB + 4, tmid, &i0, swm + 4 * c);
+            snf[c] = T;
+            si0[c] = i0;
+            stmid[c] = tmid;
+            if (ip->n_frames) ip->n_frames[b0 + c] = T;
+            if (ip->time_mid) ip->time_mid[b0 + c] = mid_ok ? tmid : NAN;
+        }
+    } else {
+        // phase 1 on the other three waves: the end frames' control points (mg_item_control_points' statement)
+        for (int e = tid - 64; e < ncand * NRS; e += 192) {
+            const int c = e / NRS, j = e - c * NRS;
+            const double *s = slat + c * L;
+            scp[c * CS + j] = mg_control_point(smean[j], sE + j, (size_t)NRS, L, [&](int k) { return s[k]; });
+        }
+    }
+    __syncthreads();
+
+    // mid: channel schan[ch] of every candidate's frame at ITS time_mid
+    for (int e = tid; e < ncand * NC; e += 256) {
+        const int c = e / NC, ch = e - c * NC;
+        if (sbad[c] || snf[c] <= 0 || frame_idx >= snf[c]) continue;
+        const double *s = slat + c * L;
+        const size_t r0 = (size_t)si0[c] * D + (size_t)schan[ch];
+        double c4[4];
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const size_t r = r0 + (size_t)j * D;
+            c4[j] = mg_control_point(mean[r], Et + r, R, L, [&](int k) { return s[k]; });
+        }
+        smid[c * MS + ch] = mg_taps4(swm + 4 * c, c4, 1);
+    }
+    __syncthreads();
+
+    // phase 2: one (candidate, joint) per thread, and one thread per candidate for the root's outputs
+    for (int e = tid; e < ncand * (J + 1); e += 256) {
+        const int c = e / (J + 1), u = e - c * (J + 1);
+        const double *cp = scp + c * CS;
+        auto channel = [&](int s, int d) {
+            const int32_t *m = smap + stap[s] * D + d;
+            const double c4[4] = {cp[m[0]], cp[m[D]], cp[m[2 * D]], cp[m[3 * D]]};
+            return mg_taps4(sw + 4 * s, c4, 1);
+        };
+        const int T = snf[c];
+        const bool bad = sbad[c] != 0 || T <= 0;
+        const int64_t b = b0 + c;
+        const double s0[3] = {channel(0, 0), channel(0, 1), channel(0, 2)};
+        if (u < J) {
+            double *o = ip->points + (b * J + u) * 3;
+            if (bad || frame_idx >= T) { o[0] = NAN; o[1] = NAN; o[2] = NAN; continue; }
+            const double *mid = smid + c * MS;
+            double p[3];
+            mg_fk_position_table([&](int r) { return mid[spos[r]]; }, 0, srec + u * RS, p);
+#pragma unroll
+            for (int i = 0; i < 3; i++) o[i] = p[i] - s0[i];
+        } else {
+            auto last = [&](int r) { return channel(1, r); };
+            const double ex = last(0), ez = last(2);
+            double q[4], v[3], hx, hz;
+            mg_chain_orientation(last, 3, 1, q);
+            mg_rotate(q, 0.0, 0.0, 1.0, v);
+            const double len = sqrt(v[0] * v[0] + v[2] * v[2]);
+            mg_heading_xz(q, 0.0, 0.0, 1.0, hx, hz);
+            if (ip->start_root) {
+                double *o = ip->start_root + b * 3;
+#pragma unroll
+                for (int i = 0; i < 3; i++) o[i] = bad ? NAN : s0[i];
+            }
+            if (ip->root_end) { ip->root_end[b * 2] = bad ? NAN : ex; ip->root_end[b * 2 + 1] = bad ? NAN : ez; }
+            if (ip->heading_end) { ip->heading_end[b * 2] = bad ? NAN : hx; ip->heading_end[b * 2 + 1] = bad ? NAN : hz; }
+            if (ip->heading_len) ip->heading_len[b] = bad ? NAN : len;
+        }
+    }
+}
+
+struct mg_fpw_plan {
+    std::vector<int32_t> src, map, chan;   // chan: the mid frame's channels, then pos[D]
+    std::vector<double> rec;
+    int32_t NCP = 0, NRS = 0, NC = 0, need_mid = 0, rec_stride = MG_FP_REC_HDR;
+    int32_t tap[MG_FPW_SLOTS] = {0, 0};
+    double w[MG_FPW_SLOTS * 4] = {0};
+    int lds = 0;
+};
+
+static int mg_fpw_plan_of(const char *who, int i, const mg_warped_feature_point_item &q, mg_fpw_plan &pl) {
+    const mg_primitive *p = q.prim;
+    const int D = p->D, F = p->F, NB = p->NB;
+    MG_ITEM_REFUSE(D < 7, "%s: item %d: the primitive has %d channels, a root pose needs 7", who, i, D);
+    MG_ITEM_REFUSE(F < 4 || F > MG_FEATURE_POINTS_WARPED_MAX_F, "%s: item %d: %d canonical frames (4 .. %d supported)", who, i, F, MG_FEATURE_POINTS_WARPED_MAX_F);
+    MG_ITEM_REFUSE(!p->d_Et64 || !p->d_mean || !p->d_knots || !p->d_tphi || !p->d_tmean || NB < 4 || (int)p->knots.size() != NB + 4,
+                   "%s: item %d: the primitive has no float64 tables (%d basis functions)", who, i, NB);
+    const mg_skeleton_desc *sk = q.skeleton;
+    if (sk && sk->quat_channel)
+        for (int j = 0; j < sk->n_joints; j++)
+            MG_ITEM_REFUSE(sk->quat_channel[j] >= 0 && sk->quat_channel[j] + 4 > D, "%s: item %d: the skeleton's joint %d has channels %d .. %d, the primitive %d",
+                           who, i, j, sk->quat_channel[j], sk->quat_channel[j] + 3, D);
+    // the two end frames: their basis rows (the host's mg_basis_row is mg_basis_row_dev statement for statement) and the rows of E' they touch
+    const double times[MG_FPW_SLOTS] = {0.0, (double)(F - 1)};
+    int32_t first[MG_FPW_SLOTS];
+    std::vector<int32_t> cps;
+    for (int s = 0; s < MG_FPW_SLOTS; s++) {
+        mg_basis_row(p->knots.data(), NB + 4, times[s], &first[s], &pl.w[4 * s]);
+        MG_ITEM_REFUSE(first[s] < 0 || first[s] + 4 > NB, "%s: item %d: time %g takes control points %d .. %d of %d", who, i, times[s], first[s], first[s] + 3, NB);
+        for (int j = 0; j < 4; j++) cps.push_back(first[s] + j);
+    }
+    std::sort(cps.begin(), cps.end());
+    cps.erase(std::unique(cps.begin(), cps.end()), cps.end());
+    pl.NCP = (int32_t)cps.size();
+    std::vector<char> need((size_t)pl.NCP * D, 0);
+    const int count[MG_FPW_SLOTS] = {3, 7};
+    for (int s = 0; s < MG_FPW_SLOTS; s++) {
+        pl.tap[s] = (int32_t)(std::lower_bound(cps.begin(), cps.end(), first[s]) - cps.begin());
+        for (int j = 0; j < 4; j++)
+            for (int d = 0; d < count[s]; d++) need[(size_t)(pl.tap[s] + j) * D + d] = 1;
+    }
+    pl.map.assign((size_t)pl.NCP * D, -1);
+    for (int c = 0; c < pl.NCP; c++)
+        for (int d = 0; d < D; d++)
+            if (need[(size_t)c * D + d]) {
+                pl.map[(size_t)c * D + d] = (int32_t)pl.src.size();
+                pl.src.push_back(cps[(size_t)c] * D + d);
+            }
+    pl.NRS = (int32_t)pl.src.size();
+    // the mid frame's channels: the root position and the quaternions along the listed joints' chains
+    std::vector<char> mid((size_t)D, 0);
+    std::vector<std::vector<int>> chains;
+    const int rc = mg_fp_chains_of(who, i, q, chains, [&](int qc) { for (int e = 0; e < 4; e++) mid[(size_t)(qc + e)] = 1; });
+    if (rc != MG_OK) return rc;
+    if (q.n_joints > 0) mid[0] = mid[1] = mid[2] = 1;
+    std::vector<int32_t> pos((size_t)D, -1);
+    for (int d = 0; d < D; d++)
+        if (mid[(size_t)d]) { pos[(size_t)d] = (int32_t)pl.chan.size(); pl.chan.push_back(d); }
+    pl.NC = (int32_t)pl.chan.size();
+    pl.chan.insert(pl.chan.end(), pos.begin(), pos.end());
+    pl.need_mid = q.n_joints > 0 || q.time_mid_dev != nullptr;
+    mg_fp_records_of(sk, chains, pl.rec_stride, pl.rec);
+    pl.lds = mg_fpw_layout_of(F, p->Lt, pl.need_mid, p->L, pl.NRS, pl.NCP, pl.NC, D, q.n_joints, pl.rec_stride).total_bytes;
+    MG_ITEM_REFUSE(pl.lds > MG_FP_LDS_MAX, "%s: item %d: the tables (%d canonical frames x %d candidates, %d x %d control-point values, %d joints) do not fit LDS", who,
+                   i, F, MG_FP_TILE, p->L, pl.NRS, q.n_joints);
+    MG_ITEM_REFUSE_GRID(who, i, q.n_samples, MG_FP_TILE);
+    return MG_OK;
+}
+
+static int mg_fpw_check(const char *who, int32_t n_items, const mg_warped_feature_point_item *items, int latent_dtype, std::vector<mg_fpw_plan> &plans) {
+    typedef mg_warped_feature_point_item item;
+    int rc = mg_items_check(
+        who, n_items, items, latent_dtype,
+        [&](int i, const item &q) -> int {
+            const mg_primitive *p = q.prim;
+            MG_ITEM_REQUIRE(p->Lt > 0, "%s: item %d: the primitive has no time model", who, i);
+            MG_ITEM_REQUIRE(q.time_offset >= 0 && q.time_offset + p->Lt <= q.ld, "%s: item %d reads time latent columns %lld .. %lld of %lld", who, i,
+                            (long long)q.time_offset, (long long)(q.time_offset + p->Lt), (long long)q.ld);
+            MG_ITEM_REQUIRE(q.time_offset >= q.latent_offset + p->L || q.latent_offset >= q.time_offset + p->Lt,
+                            "%s: item %d: the spatial columns %lld .. %lld and the time columns %lld .. %lld overlap", who, i, (long long)q.latent_offset,
+                            (long long)(q.latent_offset + p->L), (long long)q.time_offset, (long long)(q.time_offset + p->Lt));
+            return MG_OK;
+        },
+        [&](int i, const item &q) -> int {
+            MG_ITEM_REQUIRE(q.frame_idx >= 0, "%s: item %d: frame %d", who, i, q.frame_idx);
+            MG_ITEM_REQUIRE(q.start_root_dev || q.points_dev || q.root_end_dev || q.heading_end_dev || q.heading_len_dev || q.time_mid_dev || q.n_frames_dev,
+                            "%s: item %d: all outputs are NULL", who, i);
+            return mg_fp_check_joints(who, i, q);
+        });
+    if (rc != MG_OK) return rc;
+    plans.resize((size_t)n_items);
+    for (int i = 0; i < n_items; i++)
+        if ((rc = mg_fpw_plan_of(who, i, items[i], plans[(size_t)i])) != MG_OK) return rc;
+    return MG_OK;
+}
+
+static int mg_fpw_run(const char *who, int32_t n_items, const mg_warped_feature_point_item *items, int latent_dtype, const std::vector<mg_fpw_plan> &plans) {
+    const size_t elem = latent_dtype == MG_F64 ? 8 : 4;
+    std::vector<int32_t> wg0;
+    const std::vector<mg_item_launch> launches = mg_cut_items(
+        n_items, [&](int i) { return items[i].n_samples; }, [&](int i) { return plans[(size_t)i].lds; }, MG_FP_TILE, MG_FEATURE_POINTS_MAX_ITEMS, wg0);
+    if (launches.empty()) return MG_OK;
+    std::vector<mg_fpw_item> ds;         // the non-empty items
+    std::vector<int> of;                 // the caller's item behind every entry of ds
+    mg_context *ctx = nullptr;
+    for (int i = 0; i < n_items; i++) {
+        const mg_warped_feature_point_item &q = items[i];
+        if (q.n_samples == 0) continue;
+        mg_primitive *p = q.prim;
+        const mg_fpw_plan &pl = plans[(size_t)i];
+        ctx = p->ctx;
+        mg_fpw_item d;
+        memset(&d, 0, sizeof(d));
+        d.Et = p->d_Et64; d.mean = p->d_mean; d.knots = p->d_knots; d.tphi = p->d_tphi; d.tmean = p->d_tmean;
+        d.lat = (const char *)q.latents_dev + (size_t)q.latent_offset * elem;
+        d.gam = (const char *)q.latents_dev + (size_t)q.time_offset * elem;
+        d.start_root = q.start_root_dev; d.points = q.points_dev; d.root_end = q.root_end_dev; d.heading_end = q.heading_end_dev;
+        d.heading_len = q.heading_len_dev; d.time_mid = q.time_mid_dev; d.n_frames = q.n_frames_dev;
+        d.n = q.n_samples; d.ld = q.ld;
+        memcpy(d.w, pl.w, sizeof(d.w));
+        memcpy(d.tap, pl.tap, sizeof(d.tap));
+        d.L = p->L; d.Lt = p->Lt; d.D = p->D; d.R = p->R; d.F = p->F; d.NB = p->NB; d.J = q.n_joints; d.NRS = pl.NRS; d.NCP = pl.NCP; d.NC = pl.NC;
+        d.frame_idx = q.frame_idx; d.need_mid = pl.need_mid; d.rec_stride = pl.rec_stride;
+        d.wg0 = wg0[i];
+        ds.push_back(d);
+        of.push_back(i);
+    }
+    // the table: the items, then every item's row list, map, channel list and chain records
+    std::vector<unsigned char> blob(ds.size() * sizeof(mg_fpw_item));
+    auto append = [&](const void *data, size_t bytes) {
+        const size_t at = (blob.size() + 7) & ~(size_t)7;
+        blob.resize(at + bytes, 0);
+        if (bytes) memcpy(blob.data() + at, data, bytes);
+        return at;
+    };
+    for (size_t e = 0; e < ds.size(); e++) {
+        const mg_fpw_plan &pl = plans[(size_t)of[e]];
+        const size_t o_src = append(pl.src.data(), pl.src.size() * 4), o_map = append(pl.map.data(), pl.map.size() * 4);
+        const size_t o_chan = append(pl.chan.data(), pl.chan.size() * 4), o_rec = append(pl.rec.data(), pl.rec.size() * 8);
+        MG_REQUIRE_AS(blob.size() < ((size_t)1 << 31), MG_ERR_UNSUPPORTED, "%s: the item table exceeds 2 GiB", who);
+        ds[e].off_src = (uint32_t)o_src; ds[e].off_map = (uint32_t)o_map; ds[e].off_chan = (uint32_t)o_chan; ds[e].off_rec = (uint32_t)o_rec;
+    }
+    memcpy(blob.data(), ds.data(), ds.size() * sizeof(mg_fpw_item));
+    return mg_items_launch(
+        ctx, who, ctx->tab[MG_TABLE_FEATURE_POINTS_WARPED], blob.data(), blob.size(), std::max(blob.size() * 2, (size_t)64 * 1024), launches, latent_dtype,
+        MG_LDS_FEATURE_POINTS_WARPED_F32, MG_LDS_FEATURE_POINTS_WARPED_F64, MG_PROF_FEATURE_POINTS_WARPED,
+        [](auto LAT_F64) { return mg_feature_points_warped_kernel<decltype(LAT_F64)::value>; },
+        [](const char *base, const mg_item_launch &l) { return mg_fpw_args{base, (const mg_fpw_item *)base + l.first, l.n_items}; });
+}
+
+extern "C" int mg_feature_points_warped(int32_t n_items, const mg_warped_feature_point_item *items, int latent_dtype) {
+    std::vector<mg_fpw_plan> plans;
+    const int rc = mg_fpw_check("mg_feature_points_warped", n_items, items, latent_dtype, plans);
+    if (rc != MG_OK) return rc;
+    return mg_fpw_run("mg_feature_points_warped", n_items, items, latent_dtype, plans);
+}
+
+extern "C" int mg_feature_points_warped_host(int32_t n_items, const mg_warped_feature_point_item *items, int latent_dtype) {
+    typedef mg_warped_feature_point_item item;
+    const char *who = "mg_feature_points_warped_host";
+    std::vector<mg_fpw_plan> plans;
+    const int rc = mg_fpw_check(who, n_items, items, latent_dtype, plans);
+    if (rc != MG_OK) return rc;
+    const mg_item_output<item> outs[6] = {{&item::start_root_dev, 3, nullptr}, {&item::points_dev, 3, &item::n_joints}, {&item::root_end_dev, 2, nullptr},
+                                          {&item::heading_end_dev, 2, nullptr}, {&item::heading_len_dev, 1, nullptr}, {&item::time_mid_dev, 1, nullptr}};
+    return mg_items_host(who, n_items, items, latent_dtype, outs, [&](item *dev) {
+        // the lengths are int32: a block of their own beside the float64 outputs'
+        mg_workspace lens(dev[0].prim->ctx, who);
+        std::vector<mg_staged> at((size_t)n_items);
+        for (int i = 0; i < n_items; i++)
+            if (items[i].n_samples > 0 && items[i].n_frames_dev) at[(size_t)i] = lens.out(items[i].n_frames_dev, (size_t)items[i].n_samples * 4);
+        int rc2 = lens.upload();
+        if (rc2 != MG_OK) return rc2;
+        for (int i = 0; i < n_items; i++)
+            if (items[i].n_samples > 0 && items[i].n_frames_dev) dev[i].n_frames_dev = at[(size_t)i].dev<int32_t>();
+        if ((rc2 = mg_fpw_run(who, n_items, dev, latent_dtype, plans)) != MG_OK) return rc2;
+        return lens.download();
+    });
 }

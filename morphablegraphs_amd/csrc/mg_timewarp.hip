@@ -11,7 +11,7 @@
 //   mg_timewarp_kernel        one wave per candidate: increments exp(mean_t + phi . gamma) in parallel, their running sum by one lane
 //                             in canonical-frame order (np's cumulative order: the same bits as mg_time_function_kernel), the
 //                             not-a-knot cubic through (t(t'), t') by its second derivatives (a tridiagonal solve, one lane),
-//                             the samples in parallel.  The not-a-knot cubic is unique, so this is FITPACK's spline up to rounding
+//                             the samples in parallel (the statements: mg_timewarp_device.h).  The not-a-knot cubic is unique, so this is FITPACK's spline up to rounding
 //                             (1e-12 of F on the fixtures); the sample count is int(round(t(F-2)) * (1 / speed)), the value NumPy
 //                             before 1.18 made of the float the reference passes (newer NumPy raises TypeError there: SURVEY 8c).
 //   mg_frames_at_kernel       one workgroup per candidate: its control points (mean' + E' . s, fma chain over k ascending from the
@@ -20,6 +20,7 @@
 //                             mg_back_project_frames_f64 gives with a time grid per candidate, without a grid per candidate.
 #include "mg_internal.h"
 #include "mg_spline_device.h"
+#include "mg_timewarp_device.h"
 
 #define MG_TW_BLOCK 64
 #define MG_TW_MAX_F 2048   // canonical frames the inversion holds in LDS (5 arrays of doubles)
@@ -36,92 +37,35 @@ __global__ __launch_bounds__(MG_TW_BLOCK) void mg_timewarp_kernel(const double *
     const int64_t b = blockIdx.x;
     const int tid = threadIdx.x;
     const void *gb = gamma_f64 ? (const void *)((const double *)gamma + b * ld) : (const void *)((const float *)gamma + b * ld);
-    for (int i = tid; i < F; i += MG_TW_BLOCK) {
-        double e = tmean[i];
-        for (int l = 0; l < Lt; l++) {
-            const double gl = gamma_f64 ? ((const double *)gb)[l] : (double)((const float *)gb)[l];
-            e = fma(tphi[(size_t)i * Lt + l], gl, e);
-        }
-        M[i] = exp(e);               // the increment (parked in M)
-    }
+    for (int i = tid; i < F; i += MG_TW_BLOCK)   // the increments (parked in M)
+        M[i] = mg_tw_increment(tphi, tmean, i, Lt, [&](int l) { return gamma_f64 ? ((const double *)gb)[l] : (double)((const float *)gb)[l]; });
     __syncthreads();
     if (tid == 0) {
-        double acc = 0.0;
-        for (int i = 0; i < F; i++) { acc += M[i]; x[i] = acc - 1.0; }
-        // not-a-knot cubic through (x_i, i): h_{i-1} M_{i-1} + 2 (h_{i-1} + h_i) M_i + h_i M_{i+1} = 6 ((y_{i+1} - y_i) / h_i - (y_i - y_{i-1}) / h_{i-1}),
-        // i = 1 .. F-2, with M_0 and M_{F-1} eliminated by the continuity of the third derivative at x_1 and x_{F-2}
-        const int m = F;
-        auto h = [&](int i) { return x[i + 1] - x[i]; };
-        auto rhs = [&](int i) { return 6.0 * (1.0 / h(i) - 1.0 / h(i - 1)); };   // y_{i+1} - y_i = 1
-        // rows 1 .. m-2: (lo, di, up); the first and the last one carry the end conditions
-        auto row = [&](int i, double &lo, double &di, double &up) {
-            const double h0 = h(i - 1), h1 = h(i);
-            if (i == 1) { lo = 0.0; di = 2.0 * (h0 + h1) + h0 * (1.0 + h0 / h1); up = h1 - h0 * h0 / h1; }
-            else if (i == m - 2) { lo = h0 - h1 * h1 / h0; di = 2.0 * (h0 + h1) + h1 * (1.0 + h1 / h0); up = 0.0; }
-            else { lo = h0; di = 2.0 * (h0 + h1); up = h1; }
-        };
-        if (m == 4) {   // rows 1 and 2, both with an end condition: row 1 keeps its `up`, row 2 its `lo`
-            const double h0 = h(0), h1 = h(1), h2 = h(2);
-            const double d1 = 2.0 * (h0 + h1) + h0 * (1.0 + h0 / h1), u1 = h1 - h0 * h0 / h1;
-            const double l2 = h1 - h2 * h2 / h1, d2 = 2.0 * (h1 + h2) + h2 * (1.0 + h2 / h1);
-            const double r1 = rhs(1), r2 = rhs(2);
-            const double det = d1 * d2 - u1 * l2;
-            M[1] = (r1 * d2 - u1 * r2) / det;
-            M[2] = (d1 * r2 - l2 * r1) / det;
-        } else {
-            double lo, di, up;
-            row(1, lo, di, up);
-            cp[1] = up / di;
-            dp[1] = rhs(1) / di;
-            for (int i = 2; i <= m - 2; i++) {
-                row(i, lo, di, up);
-                const double den = di - lo * cp[i - 1];
-                cp[i] = up / den;
-                dp[i] = (rhs(i) - lo * dp[i - 1]) / den;
-            }
-            M[m - 2] = dp[m - 2];
-            for (int i = m - 3; i >= 1; i--) M[i] = dp[i] - cp[i] * M[i + 1];
-        }
-        {
-            const double h0 = h(0), h1 = h(1), a = h(m - 2) / h(m - 3);
-            M[0] = (1.0 + h0 / h1) * M[1] - (h0 / h1) * M[2];
-            M[m - 1] = (1.0 + a) * M[m - 2] - a * M[m - 3];
-        }
+        mg_tw_running_sum(M, x, F);
+        mg_tw_second_derivatives(x, M, cp, dp, F, 1);
     }
     __syncthreads();
     if (canonical_out)
         for (int i = tid; i < F; i += MG_TW_BLOCK) canonical_out[b * F + i] = x[i];
     // the samples: 0, the inverse spline at linspace(1, x[F-2], num), F - 1
     const double stop = x[F - 2];
-    const double numf = rint(stop) * inv_speed;
-    // a time function that is not finite (exp() overflowed on a wild gamma) or asks for more than 2^24 samples has no row: length 0,
-    // nothing written (the conversion of such a float to int is undefined, and T = num + 2 could wrap -- ADVICE r4)
-    if (!(numf == numf) || !(fabs(stop) <= 1.0e300) || numf > 16777216.0) {
+    int num;
+    if (!mg_tw_sample_count(stop, inv_speed, num)) {   // no row: length 0, nothing written
         if (tid == 0) lens[b] = 0;
         return;
     }
-    const int num = numf > 0.0 ? (int)numf : 0;
     const int T = num + 2;
     if (tid == 0) lens[b] = T <= t_cap ? T : -T;   // (negative: the caller's rows are too short; nothing else is written)
     if (T > t_cap) return;
     double *tb = times + b * row_pitch;   // (a row holds t_cap samples; row_pitch >= t_cap doubles lie between two rows' starts)
-    const double step = num > 1 ? (stop - 1.0) / (double)(num - 1) : 0.0;
+    const double step = mg_tw_sample_step(stop, num);
     for (int j = tid; j < T; j += MG_TW_BLOCK) {
         double v;
         if (j == 0) v = 0.0;
         else if (j == T - 1) v = (double)(F - 1);
         else {
-            const int q = j - 1;
-            const double t = (q == num - 1 && num > 1) ? stop : (double)q * step + 1.0;   // numpy.linspace: arange * step + start, the last one = stop
-            int lo = 0, hi = F - 2;                    // the interval [x_i, x_{i+1}) that holds t, the end intervals for anything outside
-            while (lo < hi) {
-                const int mid = (lo + hi + 1) >> 1;
-                if (x[mid] <= t) lo = mid; else hi = mid - 1;
-            }
-            const int i = lo;
-            const double hi_ = x[i + 1] - x[i], A = x[i + 1] - t, Bq = t - x[i];
-            v = M[i] * A * A * A / (6.0 * hi_) + M[i + 1] * Bq * Bq * Bq / (6.0 * hi_) + ((double)i / hi_ - M[i] * hi_ / 6.0) * A +
-                ((double)(i + 1) / hi_ - M[i + 1] * hi_ / 6.0) * Bq;
+            const double t = mg_tw_sample_point(j - 1, num, stop, step);
+            v = mg_tw_inverse_at(x, M, mg_tw_interval(x, F, t), t);
         }
         tb[j] = v;
     }

@@ -8,11 +8,15 @@ so that check_reachability / score_trajectory_target can say whether the primiti
 of every candidate -- of every node, for the builder -- come from ONE mg_feature_points call (csrc/mg_feature_points.hip), which
 evaluates the three frames that are asked for and writes no frame to memory; the mixture is trained by HipGMMTrainer.
 
-feature_points_host is the NumPy statement of the kernel's arithmetic; it needs no library.
+The reference's own default is the time-warped motion (back_project(s, use_time_parameters=True)): with time_warped=True the
+features of a primitive with a time model come from ONE mg_feature_points_warped call, which takes from every candidate's time
+function the one sample it needs.  Without the keyword that combination raises NotImplementedError, as before.
 
-Not restated: plot_orientation; time-warped features (use_time_parameters=True on a primitive with a time model raises
-NotImplementedError -- the reference's default would time-warp there; on a primitive without a time model the two agree); the
-reference's mixture.GMM class (loading gives FeatureMixture, the same JSON).
+feature_points_host and feature_points_warped_host are the NumPy statements of the kernels' arithmetic; they need no library.
+
+Not restated: plot_orientation; smoothed time functions (smooth_time_parameters=True: the Savitzky-Golay pass needs the whole
+row) and speeds other than 1 in the time-warped features; the reference's mixture.GMM class (loading gives FeatureMixture, the
+same JSON).
 """
 import json
 import os
@@ -87,6 +91,92 @@ def feature_points_host(model, S, skeleton=None, joints=(), frame_idx=0):
     return out
 
 
+def _time_model_host(model):
+    """(knots, mean vector, eigen vectors (n_basis_time, Lt)) of the time model of the reference's JSON dict or a primitive."""
+    if isinstance(model, dict):
+        return (np.asarray(model["b_spline_knots_time"], dtype=np.float64), np.asarray(model["mean_time_vector"], dtype=np.float64),
+                np.asarray(model["eigen_vectors_time"], dtype=np.float64))
+    t_pca = getattr(model, "motion_primitive", model).t_pca
+    return (np.asarray(t_pca["knots"], dtype=np.float64), np.asarray(t_pca["mean_vector"], dtype=np.float64),
+            np.asarray(t_pca["eigen_vectors"], dtype=np.float64))
+
+
+def canonical_time_function_host(time_model, F, gamma):
+    """t(t') at the canonical frames (motion_primitive.py:289-302): the running sum of exp(mean spline + harmonics . gamma) in
+    canonical-frame order, minus 1."""
+    from scipy.interpolate import splev
+    knots, mean, eig = time_model
+    frames = np.arange(F)
+    mean_t = splev(frames, (knots, mean, 3))
+    phi = np.array([splev(frames, (knots, eig[:, l].copy(), 3)) for l in range(eig.shape[1])]).T
+    out = [0]
+    for i in range(F):
+        out.append(out[-1] + np.exp(mean_t[i] + np.dot(phi[i], gamma)))
+    return np.array(out[1:]) - 1.0
+
+
+def sample_time_function_host(canonical):
+    """The spline's time function at speed 1 (motion_primitive.py:304-319) as HipMotionPrimitive._invert_canonical_to_sample_
+    time_function states it: 0, scipy's interpolating cubic through (t(t'), t') at linspace(1, t(F - 2), int(round(t(F - 2)))),
+    F - 1.  None for a time function that is not finite or asks for more than 2^24 samples (the kernels' test)."""
+    from scipy.interpolate import splev, splrep
+    canonical = np.asarray(canonical, dtype=np.float64)
+    F, last = len(canonical), canonical[-2]
+    if not np.isfinite(last) or not abs(last) <= 1.0e300 or np.round(last) > 16777216.0:
+        return None
+    n_inner = int(np.round(last))
+    if n_inner <= 0:
+        return np.array([0.0, F - 1.0])
+    if not np.isfinite(canonical).all():
+        return np.concatenate(([0.0], np.full(n_inner, np.nan), [F - 1.0]))
+    inner = splev(np.linspace(1.0, last, n_inner), splrep(canonical, np.arange(F), k=3))
+    return np.concatenate(([0.0], inner, [F - 1.0]))
+
+
+def feature_points_warped_host(model, S, skeleton=None, joints=(), frame_idx=0, time_mid=None):
+    """The NumPy statement of mg_feature_points_warped for one item.  model: the reference's JSON dict or a primitive, with a
+    time model; S (n, >= L + Lt): a candidate reads L spatial latents and, right behind them, Lt time latents; frame_idx counts
+    the frames of the WARPED motion.  The frames are those of the times 0, time_mid and F - 1; with time_mid (n,) given, the mid
+    frame is evaluated at those times instead of the statement's own (a NaN there: the candidate's motion is shorter).  Returns
+    what feature_points_host returns and time_mid (n,), n_frames (n,) int32.  n_frames = 0 (no time function): NaN in every
+    output of the row; a spatial latent that is not finite: NaN in the feature outputs; frame_idx >= n_frames: NaN in points
+    and time_mid only."""
+    hm = model if isinstance(model, gw._HostModel) else gw._HostModel(model)
+    tm = _time_model_host(model)
+    S = np.atleast_2d(np.asarray(S, dtype=np.float64))
+    F, L, Lt = hm.n_canonical_frames, hm.n_components, tm[2].shape[1]
+    frame_idx = int(frame_idx)
+    if frame_idx < 0:
+        raise ValueError("frame_idx %d below 0" % frame_idx)
+    joints = [skeleton.index(j) for j in joints]
+    n, J = len(S), len(joints)
+    out = {"start_root": np.full((n, 3), np.nan), "root_end": np.full((n, 2), np.nan), "heading_end": np.full((n, 2), np.nan),
+           "heading_len": np.full(n, np.nan), "time_mid": np.full(n, np.nan), "n_frames": np.zeros(n, dtype=np.int32)}
+    if J:
+        out["points"] = np.full((n, 3 * J), np.nan)
+    for b in range(n):
+        with np.errstate(over="ignore", invalid="ignore"):
+            times = sample_time_function_host(canonical_time_function_host(tm, F, S[b, L:L + Lt]))
+        if times is None:
+            continue
+        out["n_frames"][b] = len(times)
+        short = frame_idx >= len(times)
+        if not short:
+            out["time_mid"][b] = times[frame_idx]
+        mid = out["time_mid"][b] if time_mid is None else float(np.asarray(time_mid)[b])
+        short = short or (time_mid is not None and np.isnan(mid))
+        if not np.isfinite(S[b, :L]).all():
+            continue
+        _, fr = hm.frames(S[b, :L], np.array([0.0, 0.0 if short else mid, F - 1.0]))
+        out["start_root"][b] = fr[0, :3]
+        if not short:
+            for j, joint in enumerate(joints):
+                out["points"][b, 3 * j:3 * j + 3] = joint_position_host(skeleton, fr[1], joint) - fr[0, :3]
+        out["root_end"][b] = fr[2, 0], fr[2, 2]
+        out["heading_end"][b], out["heading_len"][b] = heading_host(fr[2])
+    return out
+
+
 def rotation_angle(point1, point2):
     """anim_utils' get_rotation_angle: the angle from point1 to point2 in degrees, brought into [-180, 180] (restated, unpinned)."""
     theta1 = np.rad2deg(np.arctan2(point1[1], point1[0]))
@@ -151,14 +241,24 @@ class HipFeaturePointModel(object):
     stream gives the reference's latents); device=True draws the whole batch with the device sampler (same distribution, another
     stream); latents= passes them in.  The features come from one mg_feature_points call.
 
+    time_warped=True: on a primitive with a time model and use_time_parameters=True the features are those of the time-warped
+    motion -- the reference's default -- from one mg_feature_points_warped call on full latent rows (spatial + time); a candidate
+    whose warped motion has no frame frame_idx raises IndexError, as the reference's indexing does; so does a candidate without a
+    time function (n_frames 0: exp overflowed, or a time latent is not finite) in the root features and in the builder, which name
+    it instead of training on NaN rows.  smooth_time_parameters=True
+    on the primitive raises NotImplementedError (the Savitzky-Golay pass needs the whole time function and stays on the host).
+    Without a time model, or with use_time_parameters=False, the keyword changes nothing.
+
     Training: the reference writes GMMTrainer(training_samples) and reads .gmm and .averageScore, which does not match
     GMMTrainer's constructor (it takes no data; fit(data, score='AIC') trains).  What is built is what it means:
     HipGMMTrainer().fit(samples) with the AIC default; max_components bounds the sweep (GMMTrainer's n_K, 40).  The thresholds
     are averageScore (root features) and averageScore - 5 (feature points), as written."""
 
-    def __init__(self, primitive, skeleton=None, use_time_parameters=True, device=False, latents=None, max_components=40, seed=None, ctx=None):
+    def __init__(self, primitive, skeleton=None, use_time_parameters=True, device=False, latents=None, max_components=40, seed=None, ctx=None,
+                 time_warped=False):
         self.motion_primitive_model = gw._primitive_of(primitive)
         self.skeleton = skeleton
+        self.time_warped = bool(time_warped)
         self.use_time_parameters, self.device, self.latents = use_time_parameters, bool(device), latents
         self.max_components, self.seed, self.ctx = int(max_components), seed, ctx
         self.low_dimension_vectors = []
@@ -178,10 +278,18 @@ class HipFeaturePointModel(object):
         self.root_threshold = None
 
     # ---- latents and the one call ------------------------------------------------------------------
+    def _warps(self):
+        """Whether the features are those of the time-warped motion: use_time_parameters on a primitive with a time model."""
+        mp = self.motion_primitive_model
+        return bool(self.use_time_parameters and mp.has_time_parameters and mp.t_pca.get("n_components", 0) > 0)
+
     def _draw(self, n):
         mp = self.motion_primitive_model
-        if self.use_time_parameters and mp.has_time_parameters and mp.t_pca.get("n_components", 0) > 0:
-            raise NotImplementedError("time-warped feature points: pass use_time_parameters=False for a primitive with a time model")
+        if self._warps():
+            if not self.time_warped:
+                raise NotImplementedError("time-warped feature points: pass time_warped=True, or use_time_parameters=False, for a primitive with a time model")
+            if getattr(mp, "smooth_time_parameters", False):
+                raise NotImplementedError("time-warped feature points of a smoothed time function: the Savitzky-Golay pass needs the whole row")
         if self.latents is not None:
             S = _capi._latents(self.latents)
             if len(S) != n:
@@ -197,6 +305,23 @@ class HipFeaturePointModel(object):
     def _item(self, S, joints=(), frame_idx=0):
         return {"prim": self.motion_primitive_model._prim, "S": S, "skeleton": self.skeleton, "joints": list(joints), "frame_idx": frame_idx}
 
+    def _features(self, items, wanted):
+        """One call for `items` (all of this model's kind): mg_feature_points_warped where the motion is time-warped."""
+        return _capi.feature_points_warped(items, wanted) if self._warps() else _capi.feature_points(items, wanted)
+
+    @staticmethod
+    def _require_frame(out, frame_idx, name=""):
+        """IndexError for the first candidate whose warped motion has no frame frame_idx (out: with "n_frames")."""
+        short = np.flatnonzero(out["n_frames"] <= frame_idx) if "n_frames" in out else ()
+        if len(short):
+            raise IndexError("%scandidate %d: index %d is out of bounds for a warped motion of %d frames" % (name and name + ": ", short[0], frame_idx,
+                                                                                                             out["n_frames"][short[0]]))
+
+    def _root_outputs(self):
+        """What the root features ask of the call; with the warp also n_frames, so that a candidate without a time function (0 frames:
+        exp overflowed, or time latents that are not finite) raises through _require_frame(out, 0) instead of training on NaN."""
+        return ("root_end", "heading_end", "heading_len") + (("n_frames",) if self._warps() else ())
+
     def _take_root(self, out, S):
         self.root_low_dimension_vectors += np.asarray(S, dtype=np.float64).tolist()      # (the reference does not keep these)
         self.root_pos += list(out["root_end"])
@@ -211,7 +336,9 @@ class HipFeaturePointModel(object):
             raise ValueError("feature points of joints need a skeleton")
         self.feature_point_list = joint_name_list
         S = self._draw(n)
-        out = _capi.feature_points([self._item(S, joint_name_list, frame_idx)], ("points", "heading_end", "heading_len"))[0]
+        warps = self._warps()
+        out = self._features([self._item(S, joint_name_list, frame_idx)], ("points", "heading_end", "heading_len") + (("n_frames",) if warps else ()))[0]
+        self._require_frame(out, int(frame_idx))
         self.low_dimension_vectors += np.asarray(S, dtype=np.float64).tolist()
         self.feature_points += list(out["points"])
         self.orientations += out["heading_end"].tolist()
@@ -219,7 +346,9 @@ class HipFeaturePointModel(object):
 
     def create_root_pos_ori(self, n):
         S = self._draw(n)
-        self._take_root(_capi.feature_points([self._item(S)], ("root_end", "heading_end", "heading_len"))[0], S)
+        out = self._features([self._item(S)], self._root_outputs())[0]
+        self._require_frame(out, 0)
+        self._take_root(out, S)
 
     def convert_ori_to_angle_deg(self, ref_ori=[0, -1]):
         assert len(self.root_orientation) > 0, ("please create root orientation list first!")
@@ -339,7 +468,8 @@ class HipFeaturePointModelBuilder(object):
     """FeaturePointModelBuilder (feature_point_model_builder.py): the root-feature mixture of every primitive.  build() takes a
     graph (its .nodes), a dict {node_key: node or primitive} or nothing -- then every *_quaternion_mm.json below
     morphable_model_directory is loaded, keyed (elementary action, motion primitive) from the file name as the reference splits
-    it.  The features of all nodes come from ONE mg_feature_points call."""
+    it.  The features of all nodes come from ONE mg_feature_points call; with time_warped=True among the model options the nodes
+    whose motion is time-warped go in one mg_feature_points_warped call and the others in one mg_feature_points call."""
 
     def __init__(self, context=None, **model_options):
         self.morphable_model_directory = None
@@ -381,7 +511,15 @@ class HipFeaturePointModelBuilder(object):
         dtypes = set(S.dtype for S in latents)
         if len(dtypes) > 1:
             latents = [S.astype(np.float64) for S in latents]
-        outs = _capi.feature_points([models[key]._item(S) for key, S in zip(keys, latents)], ("root_end", "heading_end", "heading_len"))
+        outs = [None] * len(keys)
+        for warped in (True, False):
+            which = [k for k, key in enumerate(keys) if models[key]._warps() == warped]
+            if which:
+                first = models[keys[which[0]]]
+                got = first._features([models[keys[k]]._item(latents[k]) for k in which], first._root_outputs())
+                for k, out in zip(which, got):
+                    first._require_frame(out, 0, str(keys[k]))
+                    outs[k] = out
         result = {}
         for key, out, S in zip(keys, outs, latents):
             model = models[key]

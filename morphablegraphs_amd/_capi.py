@@ -1124,12 +1124,17 @@ class StepLengthItem(C.Structure):   # struct mg_step_length_item
                 ("arc_length", C.c_void_p), ("distance", C.c_void_p)]
 
 
-def step_lengths_table(lib, n_items, table, latent_dtype, host=True):
-    """mg_step_lengths_host (host pointers in the table; synchronises) or mg_step_lengths (device pointers; asynchronous on the
-    context's stream) on a (StepLengthItem * n) table as it stands; table None passes NULL."""
+def _items_call(lib, name, n_items, table, latent_dtype, host):
+    """An item-table entry point on a table of its item structs as it stands: `name`_host (host pointers in the table;
+    synchronises) or `name` (device pointers; asynchronous on the context's stream); table None passes NULL."""
     code = MG_F64 if np.dtype(latent_dtype) == np.float64 else MG_F32
-    fn = lib.mg_step_lengths_host if host else lib.mg_step_lengths
+    fn = getattr(lib, name + "_host" if host else name)
     _check(fn(int(n_items), C.cast(table, C.c_void_p) if table is not None else None, code))
+
+
+def step_lengths_table(lib, n_items, table, latent_dtype, host=True):
+    """mg_step_lengths_host or mg_step_lengths on a (StepLengthItem * n) table (_items_call)."""
+    _items_call(lib, "mg_step_lengths", n_items, table, latent_dtype, host)
 
 
 def step_lengths(items, method="both"):
@@ -1170,11 +1175,8 @@ FEATURE_POINT_OUTPUTS = ("start_root", "points", "root_end", "heading_end", "hea
 
 
 def feature_points_table(lib, n_items, table, latent_dtype, host=True):
-    """mg_feature_points_host (host pointers in the table; synchronises) or mg_feature_points (device pointers; asynchronous on the
-    context's stream) on a (FeaturePointItem * n) table as it stands; table None passes NULL."""
-    code = MG_F64 if np.dtype(latent_dtype) == np.float64 else MG_F32
-    fn = lib.mg_feature_points_host if host else lib.mg_feature_points
-    _check(fn(int(n_items), C.cast(table, C.c_void_p) if table is not None else None, code))
+    """mg_feature_points_host or mg_feature_points on a (FeaturePointItem * n) table (_items_call)."""
+    _items_call(lib, "mg_feature_points", n_items, table, latent_dtype, host)
 
 
 def feature_point_widths(n_joints):
@@ -1237,11 +1239,8 @@ WARPED_FEATURE_POINT_OUTPUTS = FEATURE_POINT_OUTPUTS + ("time_mid", "n_frames")
 
 
 def feature_points_warped_table(lib, n_items, table, latent_dtype, host=True):
-    """mg_feature_points_warped_host (host pointers in the table; synchronises) or mg_feature_points_warped (device pointers;
-    asynchronous on the context's stream) on a (WarpedFeaturePointItem * n) table as it stands; table None passes NULL."""
-    code = MG_F64 if np.dtype(latent_dtype) == np.float64 else MG_F32
-    fn = lib.mg_feature_points_warped_host if host else lib.mg_feature_points_warped
-    _check(fn(int(n_items), C.cast(table, C.c_void_p) if table is not None else None, code))
+    """mg_feature_points_warped_host or mg_feature_points_warped on a (WarpedFeaturePointItem * n) table (_items_call)."""
+    _items_call(lib, "mg_feature_points_warped", n_items, table, latent_dtype, host)
 
 
 def feature_points_warped(items, outputs=WARPED_FEATURE_POINT_OUTPUTS):

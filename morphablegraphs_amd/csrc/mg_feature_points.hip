@@ -17,13 +17,19 @@
 //               (mg_chain_orientation, mg_rotate, mg_heading_xz).  The only stores to global memory
 //
 // The launch shape -- which workgroup serves which item, the slices of MG_FEATURE_POINTS_MAX_ITEMS items, the _host twin -- is
-// mg_items.h's; behind the items their row lists and chain records travel in the same device table (ctx->tab[MG_TABLE_FEATURE_POINTS]).
+// mg_items.h's, the table's layout included; behind the items their row lists and chain records travel in the same device table
+// (ctx->tab[MG_TABLE_FEATURE_POINTS]).  The row list is mg_feature_rows.h's (host-only).  What the time-warped kernel further down
+// shares with this one is stated once, between the layouts and the kernels: the item's leading members (mg_fp_item), the staging of
+// its constants (mg_fp_stage_constants), the four-tap read (mg_fp_channel), the root thread (mg_fp_root_outputs); on the host the
+// shared refusals (mg_fp_refuse), the chains and their records, the members of the device item (mg_fp_fill).
+#include <climits>
 #include <cmath>
 #include <cstring>
 
 #include <algorithm>
 #include <vector>
 
+#include "mg_feature_rows.h"
 #include "mg_items.h"
 #include "mg_pack.h"
 #include "mg_score_device.h"
@@ -34,12 +40,12 @@
 #define MG_FP_SLOTS 3                    // the frames 0, frame_idx, F - 1
 #define MG_FP_REC_HDR 5                  // mg_fk_position_table's record: [4] = chain length m, then m x (quaternion channel or -1, offset xyz)
 
-struct mg_fp_item {                      // one non-empty item as the kernel reads it
+struct mg_fp_item {                      // one non-empty item as the kernel reads it; the time-warped kernel's item starts with it
     const double *Et, *mean;             // [L][R], (R): E' and mean' (scaled by translation_maxima), row = i * D + d
     const void *lat;                     // the item's first latent: row b at lat + b * ld
     double *start_root, *points, *root_end, *heading_end, *heading_len;   // outputs or NULL
     int64_t n, ld;
-    double w[MG_FP_SLOTS * 4];           // the three frames' tap rows
+    double w[MG_FP_SLOTS * 4];           // the host-planned frames' tap rows (three; two of the time-warped motion)
     int32_t tap[MG_FP_SLOTS];            // where each frame's first tap sits in the item's list of control points
     int32_t L, D, R, J;
     int32_t NRS, NCP;                    // listed rows; listed control points (<= 12)
@@ -74,6 +80,58 @@ __host__ __device__ static inline mg_fp_layout mg_fp_layout_of(int L, int NRS, i
     return y;
 }
 
+// ---- the statements both kernels make (inlined into them, under their fp contract(off)) ---------------------------------------------
+// the item's constants into LDS: the listed rows of E' as sE[L][NRS], their means, where (control point, channel) sits among the rows,
+// the chain records, the tap rows and tap positions of the `slots` host-planned frames; the tile's not-finite flags zeroed
+__device__ __forceinline__ void mg_fp_stage_constants(const char *base, const mg_fp_item *ip, int slots, double *sE, double *smean, double *sw, double *srec,
+                                                      int32_t *smap, int32_t *stap, int32_t *sbad) {
+    const int tid = threadIdx.x, L = ip->L, NRS = ip->NRS, n_map = ip->NCP * ip->D, n_rec = ip->J * ip->rec_stride;
+    const size_t R = (size_t)ip->R;
+    const double *Et = ip->Et, *mean = ip->mean;
+    const int32_t *src = (const int32_t *)(base + ip->off_src), *map = (const int32_t *)(base + ip->off_map);
+    const double *rec = (const double *)(base + ip->off_rec);
+    for (int e = tid; e < L * NRS; e += 256) {
+        const int k = e / NRS, j = e - k * NRS;
+        sE[e] = Et[(size_t)k * R + (size_t)src[j]];
+    }
+    for (int j = tid; j < NRS; j += 256) smean[j] = mean[src[j]];
+    for (int e = tid; e < n_map; e += 256) smap[e] = map[e];
+    for (int e = tid; e < n_rec; e += 256) srec[e] = rec[e];
+    if (tid < slots * 4) sw[tid] = ip->w[tid];
+    if (tid < slots) stap[tid] = ip->tap[tid];
+    if (tid < MG_FP_TILE) sbad[tid] = 0;
+}
+
+// channel d of host-planned frame slot s from a candidate's control points cp: the four taps of its knot span
+__device__ __forceinline__ double mg_fp_channel(const double *cp, const double *sw, const int32_t *smap, const int32_t *stap, int D, int s, int d) {
+#pragma clang fp contract(off)
+    const int32_t *m = smap + stap[s] * D + d;
+    const double c4[4] = {cp[m[0]], cp[m[D]], cp[m[2 * D]], cp[m[3 * D]]};
+    return mg_taps4(sw + 4 * s, c4, 1);
+}
+
+// the root thread of phase 2: start_root (s0), root_end and the heading of frame slot `slot` (the last frame) for candidate b of the
+// item; NaN throughout for a bad one.  channel(s, d): mg_fp_channel on the candidate's control points
+template <class Channel>
+__device__ __forceinline__ void mg_fp_root_outputs(const mg_fp_item *ip, int64_t b, bool bad, const double *s0, Channel channel, int slot) {
+#pragma clang fp contract(off)
+    auto last = [&](int r) { return channel(slot, r); };
+    const double ex = last(0), ez = last(2);
+    double q[4], v[3], hx, hz;
+    mg_chain_orientation(last, 3, 1, q);
+    mg_rotate(q, 0.0, 0.0, 1.0, v);
+    const double len = sqrt(v[0] * v[0] + v[2] * v[2]);
+    mg_heading_xz(q, 0.0, 0.0, 1.0, hx, hz);
+    if (ip->start_root) {
+        double *o = ip->start_root + b * 3;
+#pragma unroll
+        for (int i = 0; i < 3; i++) o[i] = bad ? NAN : s0[i];
+    }
+    if (ip->root_end) { ip->root_end[b * 2] = bad ? NAN : ex; ip->root_end[b * 2 + 1] = bad ? NAN : ez; }
+    if (ip->heading_end) { ip->heading_end[b * 2] = bad ? NAN : hx; ip->heading_end[b * 2 + 1] = bad ? NAN : hz; }
+    if (ip->heading_len) ip->heading_len[b] = bad ? NAN : len;
+}
+
 template <bool LAT_F64>
 __global__ __launch_bounds__(256) void mg_feature_points_kernel(const mg_fp_args a) {
 #pragma clang fp contract(off)
@@ -82,7 +140,6 @@ __global__ __launch_bounds__(256) void mg_feature_points_kernel(const mg_fp_args
     const mg_fp_item *ip = a.items + mg_item_of_workgroup(a.items, a.n_items);
     const int L = ip->L, D = ip->D, J = ip->J, NRS = ip->NRS, NCP = ip->NCP, RS = ip->rec_stride;
     const int64_t n = ip->n, ld = ip->ld;
-    const size_t R = (size_t)ip->R;
     const mg_fp_layout y = mg_fp_layout_of(L, NRS, NCP, D, J, RS);
     const int CS = y.CS;
     double *sm = (double *)smem;
@@ -92,21 +149,7 @@ __global__ __launch_bounds__(256) void mg_feature_points_kernel(const mg_fp_args
     const int64_t b0 = mg_item_tile_of<MG_FP_TILE>(ip->wg0, n, ncand);
 
     // the item's constants and the tile's latents
-    {
-        const double *Et = ip->Et, *mean = ip->mean;
-        const int32_t *src = (const int32_t *)(a.base + ip->off_src), *map = (const int32_t *)(a.base + ip->off_map);
-        const double *rec = (const double *)(a.base + ip->off_rec);
-        for (int e = tid; e < L * NRS; e += 256) {
-            const int k = e / NRS, j = e - k * NRS;
-            sE[e] = Et[(size_t)k * R + (size_t)src[j]];
-        }
-        for (int j = tid; j < NRS; j += 256) smean[j] = mean[src[j]];
-        for (int e = tid; e < NCP * D; e += 256) smap[e] = map[e];
-        for (int e = tid; e < J * RS; e += 256) srec[e] = rec[e];
-        if (tid < MG_FP_SLOTS * 4) sw[tid] = ip->w[tid];
-        if (tid < MG_FP_SLOTS) stap[tid] = ip->tap[tid];
-        if (tid < MG_FP_TILE) sbad[tid] = 0;
-    }
+    mg_fp_stage_constants(a.base, ip, MG_FP_SLOTS, sE, smean, sw, srec, smap, stap, sbad);
     __syncthreads();
     mg_item_stage_latents<LAT_F64>(ip->lat, ld, b0, ncand, L, slat, sbad);
     __syncthreads();
@@ -119,12 +162,7 @@ __global__ __launch_bounds__(256) void mg_feature_points_kernel(const mg_fp_args
     for (int e = tid; e < ncand * (J + 1); e += 256) {
         const int c = e / (J + 1), u = e - c * (J + 1);
         const double *cp = scp + c * CS;
-        // channel d of frame slot s: the four taps of its knot span
-        auto channel = [&](int s, int d) {
-            const int32_t *m = smap + stap[s] * D + d;
-            const double c4[4] = {cp[m[0]], cp[m[D]], cp[m[2 * D]], cp[m[3 * D]]};
-            return mg_taps4(sw + 4 * s, c4, 1);
-        };
+        auto channel = [&](int s, int d) { return mg_fp_channel(cp, sw, smap, stap, D, s, d); };
         const bool bad = sbad[c] != 0;
         const int64_t b = b0 + c;
         const double s0[3] = {channel(0, 0), channel(0, 1), channel(0, 2)};
@@ -135,33 +173,34 @@ __global__ __launch_bounds__(256) void mg_feature_points_kernel(const mg_fp_args
 #pragma unroll
             for (int i = 0; i < 3; i++) o[i] = bad ? NAN : p[i] - s0[i];
         } else {
-            auto last = [&](int r) { return channel(2, r); };
-            const double ex = last(0), ez = last(2);
-            double q[4], v[3], hx, hz;
-            mg_chain_orientation(last, 3, 1, q);
-            mg_rotate(q, 0.0, 0.0, 1.0, v);
-            const double len = sqrt(v[0] * v[0] + v[2] * v[2]);
-            mg_heading_xz(q, 0.0, 0.0, 1.0, hx, hz);
-            if (ip->start_root) {
-                double *o = ip->start_root + b * 3;
-#pragma unroll
-                for (int i = 0; i < 3; i++) o[i] = bad ? NAN : s0[i];
-            }
-            if (ip->root_end) { ip->root_end[b * 2] = bad ? NAN : ex; ip->root_end[b * 2 + 1] = bad ? NAN : ez; }
-            if (ip->heading_end) { ip->heading_end[b * 2] = bad ? NAN : hx; ip->heading_end[b * 2 + 1] = bad ? NAN : hz; }
-            if (ip->heading_len) ip->heading_len[b] = bad ? NAN : len;
+            mg_fp_root_outputs(ip, b, bad, s0, channel, 2);
         }
     }
 }
 
-// What the host prepares of one item: the listed rows, where a (control point, channel) sits among them, the chain records
+// What the host prepares of one item: the listed rows and where a (control point, channel) sits among them (mg_feature_rows.h), the
+// chain records, the host-planned frames' tap rows, the LDS bytes of a workgroup; the time-warped item's plan starts with it
 struct mg_fp_plan {
-    std::vector<int32_t> src, map;
+    mg_feature_rows rows;
     std::vector<double> rec;
-    int32_t NCP = 0, NRS = 0, rec_stride = MG_FP_REC_HDR;
-    int32_t tap[MG_FP_SLOTS] = {0, 0, 0};
+    int32_t rec_stride = MG_FP_REC_HDR;
     double w[MG_FP_SLOTS * 4] = {0};
+    int lds = 0;
 };
+
+// What both plans refuse of the channels (MG_ERR_UNSUPPORTED), in the order they always had: a primitive without a root pose, then the
+// plan's own refusals of the primitive (own()), then a skeleton channel beyond the primitive's
+template <class Own>
+static int mg_fp_refuse(const char *who, int i, int D, const mg_skeleton_desc *sk, Own own) {
+    MG_ITEM_REFUSE(D < 7, "%s: item %d: the primitive has %d channels, a root pose needs 7", who, i, D);
+    const int rc = own();
+    if (rc != MG_OK) return rc;
+    if (sk && sk->quat_channel)
+        for (int j = 0; j < sk->n_joints; j++)
+            MG_ITEM_REFUSE(sk->quat_channel[j] >= 0 && sk->quat_channel[j] + 4 > D, "%s: item %d: the skeleton's joint %d has channels %d .. %d, the primitive %d",
+                           who, i, j, sk->quat_channel[j], sk->quat_channel[j] + 3, D);
+    return MG_OK;
+}
 
 // the argument errors of one item's joint list (MG_ERR_INVALID_ARGUMENT)
 template <class Item>
@@ -218,51 +257,29 @@ static int mg_fp_plan_of(const char *who, int i, const mg_feature_point_item &q,
     const mg_primitive *p = q.prim;
     const mg_time_grid *g = p->canonical;
     const int D = p->D, F = p->F;
-    MG_ITEM_REFUSE(D < 7, "%s: item %d: the primitive has %d channels, a root pose needs 7", who, i, D);
-    MG_ITEM_REFUSE(!g || g->T < 1 || g->T != F || !p->d_Et64 || !p->d_mean || (int)g->i0.size() != F || (int)g->w.size() != 4 * F,
-                   "%s: item %d: the primitive has no canonical grid (%d canonical frames)", who, i, F);
-    const mg_skeleton_desc *sk = q.skeleton;
-    if (sk && sk->quat_channel)
-        for (int j = 0; j < sk->n_joints; j++)
-            MG_ITEM_REFUSE(sk->quat_channel[j] >= 0 && sk->quat_channel[j] + 4 > D, "%s: item %d: the skeleton's joint %d has channels %d .. %d, the primitive %d",
-                           who, i, j, sk->quat_channel[j], sk->quat_channel[j] + 3, D);
+    int rc = mg_fp_refuse(who, i, D, q.skeleton, [&]() -> int {
+        MG_ITEM_REFUSE(!g || g->T < 1 || g->T != F || !p->d_Et64 || !p->d_mean || (int)g->i0.size() != F || (int)g->w.size() != 4 * F,
+                       "%s: item %d: the primitive has no canonical grid (%d canonical frames)", who, i, F);
+        return MG_OK;
+    });
+    if (rc != MG_OK) return rc;
+    // the three frames' taps, from the canonical grid
     const int frames[MG_FP_SLOTS] = {0, q.frame_idx, F - 1};
-    std::vector<int32_t> cps;
+    std::vector<int32_t> first;
     for (int s = 0; s < MG_FP_SLOTS; s++) {
         const int i0 = g->i0[(size_t)frames[s]];
         MG_ITEM_REFUSE(i0 < 0 || i0 + 4 > p->NB, "%s: item %d: frame %d takes control points %d .. %d of %d", who, i, frames[s], i0, i0 + 3, p->NB);
-        for (int j = 0; j < 4; j++) {
-            cps.push_back(i0 + j);
-            pl.w[4 * s + j] = g->w[4 * (size_t)frames[s] + j];
-        }
+        first.push_back(i0);
+        for (int j = 0; j < 4; j++) pl.w[4 * s + j] = g->w[4 * (size_t)frames[s] + j];
     }
-    std::sort(cps.begin(), cps.end());
-    cps.erase(std::unique(cps.begin(), cps.end()), cps.end());
-    pl.NCP = (int32_t)cps.size();
-    // the channels every listed control point is wanted for
-    std::vector<char> need((size_t)pl.NCP * D, 0);
-    auto want = [&](int s, int d0, int count) {
-        pl.tap[s] = (int32_t)(std::lower_bound(cps.begin(), cps.end(), g->i0[(size_t)frames[s]]) - cps.begin());
-        for (int j = 0; j < 4; j++)
-            for (int d = d0; d < d0 + count; d++) need[(size_t)(pl.tap[s] + j) * D + d] = 1;
-    };
-    want(0, 0, 3);
-    want(1, 0, 3);
-    want(2, 0, 7);
+    // the root position of frame 0; the root position and the quaternions along the listed joints' chains of frame_idx; the root pose of F - 1
+    std::vector<mg_feature_range> wanted = {{0, 0, 3}, {1, 0, 3}, {2, 0, 7}};
     std::vector<std::vector<int>> chains;
-    const int rc = mg_fp_chains_of(who, i, q, chains, [&](int qc) { want(1, qc, 4); });
-    if (rc != MG_OK) return rc;
-    pl.map.assign((size_t)pl.NCP * D, -1);
-    for (int c = 0; c < pl.NCP; c++)
-        for (int d = 0; d < D; d++)
-            if (need[(size_t)c * D + d]) {
-                pl.map[(size_t)c * D + d] = (int32_t)pl.src.size();
-                pl.src.push_back(cps[(size_t)c] * D + d);
-            }
-    pl.NRS = (int32_t)pl.src.size();
-    mg_fp_records_of(sk, chains, pl.rec_stride, pl.rec);
-    MG_ITEM_REFUSE((int64_t)p->L * pl.NRS > (1 << 20) || mg_fp_layout_of(p->L, pl.NRS, pl.NCP, D, q.n_joints, pl.rec_stride).total_bytes > MG_FP_LDS_MAX,
-                   "%s: item %d: the tables (%d x %d control-point values, %d joints) do not fit LDS", who, i, p->L, pl.NRS, q.n_joints);
+    if ((rc = mg_fp_chains_of(who, i, q, chains, [&](int qc) { wanted.push_back({1, qc, 4}); })) != MG_OK) return rc;
+    pl.rows = mg_feature_rows_of(D, first, wanted);
+    mg_fp_records_of(q.skeleton, chains, pl.rec_stride, pl.rec);
+    pl.lds = (int64_t)p->L * pl.rows.NRS > (1 << 20) ? INT_MAX : mg_fp_layout_of(p->L, pl.rows.NRS, pl.rows.NCP, D, q.n_joints, pl.rec_stride).total_bytes;
+    MG_ITEM_REFUSE(pl.lds > MG_FP_LDS_MAX, "%s: item %d: the tables (%d x %d control-point values, %d joints) do not fit LDS", who, i, p->L, pl.rows.NRS, q.n_joints);
     MG_ITEM_REFUSE_GRID(who, i, q.n_samples, MG_FP_TILE);
     return MG_OK;
 }
@@ -283,57 +300,39 @@ static int mg_fp_check(const char *who, int32_t n_items, const mg_feature_point_
     return MG_OK;
 }
 
+// the members both kernels read of the caller's item q, from it and its plan; append: mg_items_table's
+template <class Item, class Append>
+static void mg_fp_fill(mg_fp_item &d, const Item &q, const mg_fp_plan &pl, size_t elem, int32_t wg0, Append append) {
+    const mg_primitive *p = q.prim;
+    d.Et = p->d_Et64; d.mean = p->d_mean;
+    d.lat = (const char *)q.latents_dev + (size_t)q.latent_offset * elem;
+    d.start_root = q.start_root_dev; d.points = q.points_dev; d.root_end = q.root_end_dev; d.heading_end = q.heading_end_dev;
+    d.heading_len = q.heading_len_dev;
+    d.n = q.n_samples; d.ld = q.ld;
+    memcpy(d.w, pl.w, sizeof(d.w));
+    std::copy(pl.rows.tap.begin(), pl.rows.tap.end(), d.tap);
+    d.L = p->L; d.D = p->D; d.R = p->R; d.J = q.n_joints; d.NRS = pl.rows.NRS; d.NCP = pl.rows.NCP; d.rec_stride = pl.rec_stride;
+    d.wg0 = wg0;
+    d.off_src = append(pl.rows.src); d.off_map = append(pl.rows.map);
+}
+
 static int mg_fp_run(const char *who, int32_t n_items, const mg_feature_point_item *items, int latent_dtype, const std::vector<mg_fp_plan> &plans) {
     const size_t elem = latent_dtype == MG_F64 ? 8 : 4;
-    auto lds_of = [&](int i) {
-        const mg_fp_plan &pl = plans[(size_t)i];
-        return mg_fp_layout_of(items[i].prim->L, pl.NRS, pl.NCP, items[i].prim->D, items[i].n_joints, pl.rec_stride).total_bytes;
-    };
+    auto samples_of = [&](int i) { return items[i].n_samples; };
     std::vector<int32_t> wg0;
     const std::vector<mg_item_launch> launches =
-        mg_cut_items(n_items, [&](int i) { return items[i].n_samples; }, lds_of, MG_FP_TILE, MG_FEATURE_POINTS_MAX_ITEMS, wg0);
+        mg_cut_items(n_items, samples_of, [&](int i) { return plans[(size_t)i].lds; }, MG_FP_TILE, MG_FEATURE_POINTS_MAX_ITEMS, wg0);
     if (launches.empty()) return MG_OK;
-    std::vector<mg_fp_item> ds;          // the non-empty items
-    std::vector<int> of;                 // the caller's item behind every entry of ds
     mg_context *ctx = nullptr;
-    for (int i = 0; i < n_items; i++) {
-        const mg_feature_point_item &q = items[i];
-        if (q.n_samples == 0) continue;
-        mg_primitive *p = q.prim;
-        const mg_fp_plan &pl = plans[(size_t)i];
-        ctx = p->ctx;
-        mg_fp_item d;
-        memset(&d, 0, sizeof(d));
-        d.Et = p->d_Et64; d.mean = p->d_mean;
-        d.lat = (const char *)q.latents_dev + (size_t)q.latent_offset * elem;
-        d.start_root = q.start_root_dev; d.points = q.points_dev; d.root_end = q.root_end_dev; d.heading_end = q.heading_end_dev;
-        d.heading_len = q.heading_len_dev;
-        d.n = q.n_samples; d.ld = q.ld;
-        memcpy(d.w, pl.w, sizeof(d.w));
-        memcpy(d.tap, pl.tap, sizeof(d.tap));
-        d.L = p->L; d.D = p->D; d.R = p->R; d.J = q.n_joints; d.NRS = pl.NRS; d.NCP = pl.NCP; d.rec_stride = pl.rec_stride;
-        d.wg0 = wg0[i];
-        ds.push_back(d);
-        of.push_back(i);
-    }
-    // the table: the items, then every item's row list, map and chain records
-    std::vector<unsigned char> blob(ds.size() * sizeof(mg_fp_item));
-    auto append = [&](const void *data, size_t bytes) {
-        const size_t at = (blob.size() + 7) & ~(size_t)7;
-        blob.resize(at + bytes, 0);
-        if (bytes) memcpy(blob.data() + at, data, bytes);
-        return at;
-    };
-    for (size_t e = 0; e < ds.size(); e++) {
-        const mg_fp_plan &pl = plans[(size_t)of[e]];
-        const size_t o_src = append(pl.src.data(), pl.src.size() * 4), o_map = append(pl.map.data(), pl.map.size() * 4);
-        const size_t o_rec = append(pl.rec.data(), pl.rec.size() * 8);
-        MG_REQUIRE_AS(blob.size() < ((size_t)1 << 31), MG_ERR_UNSUPPORTED, "%s: the item table exceeds 2 GiB", who);
-        ds[e].off_src = (uint32_t)o_src; ds[e].off_map = (uint32_t)o_map; ds[e].off_rec = (uint32_t)o_rec;
-    }
-    memcpy(blob.data(), ds.data(), ds.size() * sizeof(mg_fp_item));
+    std::vector<unsigned char> table;    // the items, then every item's row list, map and chain records
+    const int rc = mg_items_table<mg_fp_item>(who, n_items, samples_of, table, [&](int i, mg_fp_item &d, auto append) {
+        ctx = items[i].prim->ctx;
+        mg_fp_fill(d, items[i], plans[(size_t)i], elem, wg0[(size_t)i], append);
+        d.off_rec = append(plans[(size_t)i].rec);
+    });
+    if (rc != MG_OK) return rc;
     return mg_items_launch(
-        ctx, who, ctx->tab[MG_TABLE_FEATURE_POINTS], blob.data(), blob.size(), std::max(blob.size() * 2, (size_t)64 * 1024), launches, latent_dtype,
+        ctx, who, ctx->tab[MG_TABLE_FEATURE_POINTS], table.data(), table.size(), std::max(table.size() * 2, (size_t)64 * 1024), launches, latent_dtype,
         MG_LDS_FEATURE_POINTS_F32, MG_LDS_FEATURE_POINTS_F64, MG_PROF_FEATURE_POINTS, [](auto LAT_F64) { return mg_feature_points_kernel<decltype(LAT_F64)::value>; },
         [](const char *base, const mg_item_launch &l) { return mg_fp_args{base, (const mg_fp_item *)base + l.first, l.n_items}; });
 }
@@ -375,18 +374,14 @@ extern "C" int mg_feature_points_host(int32_t n_items, const mg_feature_point_it
 // An item without joints and without the time_mid output needs no sample: its lanes stop after the count, and x alone is kept.
 #define MG_FPW_SLOTS 2                   // the host-planned frames: time 0, time F - 1
 
-struct mg_fpw_item {
-    const double *Et, *mean, *knots, *tphi, *tmean;
-    const void *lat, *gam;               // the item's first spatial / first time latent: row b at + b * ld
-    double *start_root, *points, *root_end, *heading_end, *heading_len, *time_mid;
+struct mg_fpw_item : mg_fp_item {       // (w, tap: the two end frames'; the rows: theirs)
+    const double *knots, *tphi, *tmean;
+    const void *gam;                     // the item's first time latent: row b at gam + b * ld
+    double *time_mid;
     int32_t *n_frames;
-    int64_t n, ld;
-    double w[MG_FPW_SLOTS * 4];
-    int32_t tap[MG_FPW_SLOTS];
-    int32_t L, Lt, D, R, F, NB, J, NRS, NCP, NC;   // NC: channels of the mid frame
-    int32_t frame_idx, need_mid, rec_stride;
-    int32_t wg0;
-    uint32_t off_src, off_map, off_rec, off_chan;   // ..., int32 chan[NC] (the mid frame's channels, ascending), pos[D] (where a channel sits among them)
+    int32_t Lt, F, NB, NC;               // NC: channels of the mid frame
+    int32_t frame_idx, need_mid;
+    uint32_t off_chan;                   // int32 chan[NC] (the mid frame's channels, ascending), pos[D] (where a channel sits among them)
 };
 
 struct mg_fpw_args {
@@ -443,21 +438,10 @@ __global__ __launch_bounds__(256) void mg_feature_points_warped_kernel(const mg_
     const double *Et = ip->Et, *mean = ip->mean;
 
     // the item's constants and the tile's latents
+    mg_fp_stage_constants(a.base, ip, MG_FPW_SLOTS, sE, smean, sw, srec, smap, stap, sbad);
     {
-        const int32_t *src = (const int32_t *)(a.base + ip->off_src), *map = (const int32_t *)(a.base + ip->off_map);
         const int32_t *chan = (const int32_t *)(a.base + ip->off_chan);
-        const double *rec = (const double *)(a.base + ip->off_rec);
-        for (int e = tid; e < L * NRS; e += 256) {
-            const int k = e / NRS, j = e - k * NRS;
-            sE[e] = Et[(size_t)k * R + (size_t)src[j]];
-        }
-        for (int j = tid; j < NRS; j += 256) smean[j] = mean[src[j]];
-        for (int e = tid; e < NCP * D; e += 256) smap[e] = map[e];
         for (int e = tid; e < NC + D; e += 256) schan[e] = chan[e];      // (chan, then pos)
-        for (int e = tid; e < J * RS; e += 256) srec[e] = rec[e];
-        if (tid < MG_FPW_SLOTS * 4) sw[tid] = ip->w[tid];
-        if (tid < MG_FPW_SLOTS) stap[tid] = ip->tap[tid];
-        if (tid < MG_FP_TILE) sbad[tid] = 0;
     }
     __syncthreads();
     mg_item_stage_latents<LAT_F64>(ip->lat, ld, b0, ncand, L, slat, sbad);
@@ -508,12 +492,8 @@ __global__ __launch_bounds__(256) void mg_feature_points_warped_kernel(const mg_
             if (ip->time_mid) ip->time_mid[b0 + c] = mid_ok ? tmid : NAN;
         }
     } else {
-        // phase 1 on the other three waves: the end frames' control points (mg_item_control_points' statement)
-        for (int e = tid - 64; e < ncand * NRS; e += 192) {
-            const int c = e / NRS, j = e - c * NRS;
-            const double *s = slat + c * L;
-            scp[c * CS + j] = mg_control_point(smean[j], sE + j, (size_t)NRS, L, [&](int k) { return s[k]; });
-        }
+        // phase 1 on the other three waves: the end frames' control points
+        mg_item_control_points(smean, sE, slat, ncand, NRS, L, scp, CS, tid - 64, 192);
     }
     __syncthreads();
 
@@ -537,11 +517,7 @@ __global__ __launch_bounds__(256) void mg_feature_points_warped_kernel(const mg_
     for (int e = tid; e < ncand * (J + 1); e += 256) {
         const int c = e / (J + 1), u = e - c * (J + 1);
         const double *cp = scp + c * CS;
-        auto channel = [&](int s, int d) {
-            const int32_t *m = smap + stap[s] * D + d;
-            const double c4[4] = {cp[m[0]], cp[m[D]], cp[m[2 * D]], cp[m[3 * D]]};
-            return mg_taps4(sw + 4 * s, c4, 1);
-        };
+        auto channel = [&](int s, int d) { return mg_fp_channel(cp, sw, smap, stap, D, s, d); };
         const int T = snf[c];
         const bool bad = sbad[c] != 0 || T <= 0;
         const int64_t b = b0 + c;
@@ -555,78 +531,40 @@ __global__ __launch_bounds__(256) void mg_feature_points_warped_kernel(const mg_
 #pragma unroll
             for (int i = 0; i < 3; i++) o[i] = p[i] - s0[i];
         } else {
-            auto last = [&](int r) { return channel(1, r); };
-            const double ex = last(0), ez = last(2);
-            double q[4], v[3], hx, hz;
-            mg_chain_orientation(last, 3, 1, q);
-            mg_rotate(q, 0.0, 0.0, 1.0, v);
-            const double len = sqrt(v[0] * v[0] + v[2] * v[2]);
-            mg_heading_xz(q, 0.0, 0.0, 1.0, hx, hz);
-            if (ip->start_root) {
-                double *o = ip->start_root + b * 3;
-#pragma unroll
-                for (int i = 0; i < 3; i++) o[i] = bad ? NAN : s0[i];
-            }
-            if (ip->root_end) { ip->root_end[b * 2] = bad ? NAN : ex; ip->root_end[b * 2 + 1] = bad ? NAN : ez; }
-            if (ip->heading_end) { ip->heading_end[b * 2] = bad ? NAN : hx; ip->heading_end[b * 2 + 1] = bad ? NAN : hz; }
-            if (ip->heading_len) ip->heading_len[b] = bad ? NAN : len;
+            mg_fp_root_outputs(ip, b, bad, s0, channel, 1);
         }
     }
 }
 
-struct mg_fpw_plan {
-    std::vector<int32_t> src, map, chan;   // chan: the mid frame's channels, then pos[D]
-    std::vector<double> rec;
-    int32_t NCP = 0, NRS = 0, NC = 0, need_mid = 0, rec_stride = MG_FP_REC_HDR;
-    int32_t tap[MG_FPW_SLOTS] = {0, 0};
-    double w[MG_FPW_SLOTS * 4] = {0};
-    int lds = 0;
+struct mg_fpw_plan : mg_fp_plan {       // (w: the two end frames')
+    std::vector<int32_t> chan;           // the mid frame's channels, then pos[D]
+    int32_t NC = 0, need_mid = 0;
 };
 
 static int mg_fpw_plan_of(const char *who, int i, const mg_warped_feature_point_item &q, mg_fpw_plan &pl) {
     const mg_primitive *p = q.prim;
     const int D = p->D, F = p->F, NB = p->NB;
-    MG_ITEM_REFUSE(D < 7, "%s: item %d: the primitive has %d channels, a root pose needs 7", who, i, D);
-    MG_ITEM_REFUSE(F < 4 || F > MG_FEATURE_POINTS_WARPED_MAX_F, "%s: item %d: %d canonical frames (4 .. %d supported)", who, i, F, MG_FEATURE_POINTS_WARPED_MAX_F);
-    MG_ITEM_REFUSE(!p->d_Et64 || !p->d_mean || !p->d_knots || !p->d_tphi || !p->d_tmean || NB < 4 || (int)p->knots.size() != NB + 4,
-                   "%s: item %d: the primitive has no float64 tables (%d basis functions)", who, i, NB);
-    const mg_skeleton_desc *sk = q.skeleton;
-    if (sk && sk->quat_channel)
-        for (int j = 0; j < sk->n_joints; j++)
-            MG_ITEM_REFUSE(sk->quat_channel[j] >= 0 && sk->quat_channel[j] + 4 > D, "%s: item %d: the skeleton's joint %d has channels %d .. %d, the primitive %d",
-                           who, i, j, sk->quat_channel[j], sk->quat_channel[j] + 3, D);
-    // the two end frames: their basis rows (the host's mg_basis_row is mg_basis_row_dev statement for statement) and the rows of E' they touch
+    int rc = mg_fp_refuse(who, i, D, q.skeleton, [&]() -> int {
+        MG_ITEM_REFUSE(F < 4 || F > MG_FEATURE_POINTS_WARPED_MAX_F, "%s: item %d: %d canonical frames (4 .. %d supported)", who, i, F, MG_FEATURE_POINTS_WARPED_MAX_F);
+        MG_ITEM_REFUSE(!p->d_Et64 || !p->d_mean || !p->d_knots || !p->d_tphi || !p->d_tmean || NB < 4 || (int)p->knots.size() != NB + 4,
+                       "%s: item %d: the primitive has no float64 tables (%d basis functions)", who, i, NB);
+        return MG_OK;
+    });
+    if (rc != MG_OK) return rc;
+    // the two end frames: their basis rows (the host's mg_basis_row is mg_basis_row_dev statement for statement); of the rows of E' they
+    // touch, the root position at time 0 and the root pose at time F - 1
     const double times[MG_FPW_SLOTS] = {0.0, (double)(F - 1)};
-    int32_t first[MG_FPW_SLOTS];
-    std::vector<int32_t> cps;
+    std::vector<int32_t> first(MG_FPW_SLOTS);
     for (int s = 0; s < MG_FPW_SLOTS; s++) {
-        mg_basis_row(p->knots.data(), NB + 4, times[s], &first[s], &pl.w[4 * s]);
-        MG_ITEM_REFUSE(first[s] < 0 || first[s] + 4 > NB, "%s: item %d: time %g takes control points %d .. %d of %d", who, i, times[s], first[s], first[s] + 3, NB);
-        for (int j = 0; j < 4; j++) cps.push_back(first[s] + j);
+        mg_basis_row(p->knots.data(), NB + 4, times[s], &first[(size_t)s], &pl.w[4 * s]);
+        MG_ITEM_REFUSE(first[(size_t)s] < 0 || first[(size_t)s] + 4 > NB, "%s: item %d: time %g takes control points %d .. %d of %d", who, i, times[s], first[(size_t)s],
+                       first[(size_t)s] + 3, NB);
     }
-    std::sort(cps.begin(), cps.end());
-    cps.erase(std::unique(cps.begin(), cps.end()), cps.end());
-    pl.NCP = (int32_t)cps.size();
-    std::vector<char> need((size_t)pl.NCP * D, 0);
-    const int count[MG_FPW_SLOTS] = {3, 7};
-    for (int s = 0; s < MG_FPW_SLOTS; s++) {
-        pl.tap[s] = (int32_t)(std::lower_bound(cps.begin(), cps.end(), first[s]) - cps.begin());
-        for (int j = 0; j < 4; j++)
-            for (int d = 0; d < count[s]; d++) need[(size_t)(pl.tap[s] + j) * D + d] = 1;
-    }
-    pl.map.assign((size_t)pl.NCP * D, -1);
-    for (int c = 0; c < pl.NCP; c++)
-        for (int d = 0; d < D; d++)
-            if (need[(size_t)c * D + d]) {
-                pl.map[(size_t)c * D + d] = (int32_t)pl.src.size();
-                pl.src.push_back(cps[(size_t)c] * D + d);
-            }
-    pl.NRS = (int32_t)pl.src.size();
+    pl.rows = mg_feature_rows_of(D, first, {{0, 0, 3}, {1, 0, 7}});
     // the mid frame's channels: the root position and the quaternions along the listed joints' chains
     std::vector<char> mid((size_t)D, 0);
     std::vector<std::vector<int>> chains;
-    const int rc = mg_fp_chains_of(who, i, q, chains, [&](int qc) { for (int e = 0; e < 4; e++) mid[(size_t)(qc + e)] = 1; });
-    if (rc != MG_OK) return rc;
+    if ((rc = mg_fp_chains_of(who, i, q, chains, [&](int qc) { for (int e = 0; e < 4; e++) mid[(size_t)(qc + e)] = 1; })) != MG_OK) return rc;
     if (q.n_joints > 0) mid[0] = mid[1] = mid[2] = 1;
     std::vector<int32_t> pos((size_t)D, -1);
     for (int d = 0; d < D; d++)
@@ -634,10 +572,10 @@ static int mg_fpw_plan_of(const char *who, int i, const mg_warped_feature_point_
     pl.NC = (int32_t)pl.chan.size();
     pl.chan.insert(pl.chan.end(), pos.begin(), pos.end());
     pl.need_mid = q.n_joints > 0 || q.time_mid_dev != nullptr;
-    mg_fp_records_of(sk, chains, pl.rec_stride, pl.rec);
-    pl.lds = mg_fpw_layout_of(F, p->Lt, pl.need_mid, p->L, pl.NRS, pl.NCP, pl.NC, D, q.n_joints, pl.rec_stride).total_bytes;
+    mg_fp_records_of(q.skeleton, chains, pl.rec_stride, pl.rec);
+    pl.lds = mg_fpw_layout_of(F, p->Lt, pl.need_mid, p->L, pl.rows.NRS, pl.rows.NCP, pl.NC, D, q.n_joints, pl.rec_stride).total_bytes;
     MG_ITEM_REFUSE(pl.lds > MG_FP_LDS_MAX, "%s: item %d: the tables (%d canonical frames x %d candidates, %d x %d control-point values, %d joints) do not fit LDS", who,
-                   i, F, MG_FP_TILE, p->L, pl.NRS, q.n_joints);
+                   i, F, MG_FP_TILE, p->L, pl.rows.NRS, q.n_joints);
     MG_ITEM_REFUSE_GRID(who, i, q.n_samples, MG_FP_TILE);
     return MG_OK;
 }
@@ -671,53 +609,29 @@ static int mg_fpw_check(const char *who, int32_t n_items, const mg_warped_featur
 
 static int mg_fpw_run(const char *who, int32_t n_items, const mg_warped_feature_point_item *items, int latent_dtype, const std::vector<mg_fpw_plan> &plans) {
     const size_t elem = latent_dtype == MG_F64 ? 8 : 4;
+    auto samples_of = [&](int i) { return items[i].n_samples; };
     std::vector<int32_t> wg0;
-    const std::vector<mg_item_launch> launches = mg_cut_items(
-        n_items, [&](int i) { return items[i].n_samples; }, [&](int i) { return plans[(size_t)i].lds; }, MG_FP_TILE, MG_FEATURE_POINTS_MAX_ITEMS, wg0);
+    const std::vector<mg_item_launch> launches =
+        mg_cut_items(n_items, samples_of, [&](int i) { return plans[(size_t)i].lds; }, MG_FP_TILE, MG_FEATURE_POINTS_MAX_ITEMS, wg0);
     if (launches.empty()) return MG_OK;
-    std::vector<mg_fpw_item> ds;         // the non-empty items
-    std::vector<int> of;                 // the caller's item behind every entry of ds
     mg_context *ctx = nullptr;
-    for (int i = 0; i < n_items; i++) {
+    std::vector<unsigned char> table;    // the items, then every item's row list, map, channel list and chain records
+    const int rc = mg_items_table<mg_fpw_item>(who, n_items, samples_of, table, [&](int i, mg_fpw_item &d, auto append) {
         const mg_warped_feature_point_item &q = items[i];
-        if (q.n_samples == 0) continue;
-        mg_primitive *p = q.prim;
+        const mg_primitive *p = q.prim;
         const mg_fpw_plan &pl = plans[(size_t)i];
         ctx = p->ctx;
-        mg_fpw_item d;
-        memset(&d, 0, sizeof(d));
-        d.Et = p->d_Et64; d.mean = p->d_mean; d.knots = p->d_knots; d.tphi = p->d_tphi; d.tmean = p->d_tmean;
-        d.lat = (const char *)q.latents_dev + (size_t)q.latent_offset * elem;
+        mg_fp_fill(d, q, pl, elem, wg0[(size_t)i], append);
+        d.knots = p->d_knots; d.tphi = p->d_tphi; d.tmean = p->d_tmean;
         d.gam = (const char *)q.latents_dev + (size_t)q.time_offset * elem;
-        d.start_root = q.start_root_dev; d.points = q.points_dev; d.root_end = q.root_end_dev; d.heading_end = q.heading_end_dev;
-        d.heading_len = q.heading_len_dev; d.time_mid = q.time_mid_dev; d.n_frames = q.n_frames_dev;
-        d.n = q.n_samples; d.ld = q.ld;
-        memcpy(d.w, pl.w, sizeof(d.w));
-        memcpy(d.tap, pl.tap, sizeof(d.tap));
-        d.L = p->L; d.Lt = p->Lt; d.D = p->D; d.R = p->R; d.F = p->F; d.NB = p->NB; d.J = q.n_joints; d.NRS = pl.NRS; d.NCP = pl.NCP; d.NC = pl.NC;
-        d.frame_idx = q.frame_idx; d.need_mid = pl.need_mid; d.rec_stride = pl.rec_stride;
-        d.wg0 = wg0[i];
-        ds.push_back(d);
-        of.push_back(i);
-    }
-    // the table: the items, then every item's row list, map, channel list and chain records
-    std::vector<unsigned char> blob(ds.size() * sizeof(mg_fpw_item));
-    auto append = [&](const void *data, size_t bytes) {
-        const size_t at = (blob.size() + 7) & ~(size_t)7;
-        blob.resize(at + bytes, 0);
-        if (bytes) memcpy(blob.data() + at, data, bytes);
-        return at;
-    };
-    for (size_t e = 0; e < ds.size(); e++) {
-        const mg_fpw_plan &pl = plans[(size_t)of[e]];
-        const size_t o_src = append(pl.src.data(), pl.src.size() * 4), o_map = append(pl.map.data(), pl.map.size() * 4);
-        const size_t o_chan = append(pl.chan.data(), pl.chan.size() * 4), o_rec = append(pl.rec.data(), pl.rec.size() * 8);
-        MG_REQUIRE_AS(blob.size() < ((size_t)1 << 31), MG_ERR_UNSUPPORTED, "%s: the item table exceeds 2 GiB", who);
-        ds[e].off_src = (uint32_t)o_src; ds[e].off_map = (uint32_t)o_map; ds[e].off_chan = (uint32_t)o_chan; ds[e].off_rec = (uint32_t)o_rec;
-    }
-    memcpy(blob.data(), ds.data(), ds.size() * sizeof(mg_fpw_item));
+        d.time_mid = q.time_mid_dev; d.n_frames = q.n_frames_dev;
+        d.Lt = p->Lt; d.F = p->F; d.NB = p->NB; d.NC = pl.NC;
+        d.frame_idx = q.frame_idx; d.need_mid = pl.need_mid;
+        d.off_chan = append(pl.chan); d.off_rec = append(pl.rec);
+    });
+    if (rc != MG_OK) return rc;
     return mg_items_launch(
-        ctx, who, ctx->tab[MG_TABLE_FEATURE_POINTS_WARPED], blob.data(), blob.size(), std::max(blob.size() * 2, (size_t)64 * 1024), launches, latent_dtype,
+        ctx, who, ctx->tab[MG_TABLE_FEATURE_POINTS_WARPED], table.data(), table.size(), std::max(table.size() * 2, (size_t)64 * 1024), launches, latent_dtype,
         MG_LDS_FEATURE_POINTS_WARPED_F32, MG_LDS_FEATURE_POINTS_WARPED_F64, MG_PROF_FEATURE_POINTS_WARPED,
         [](auto LAT_F64) { return mg_feature_points_warped_kernel<decltype(LAT_F64)::value>; },
         [](const char *base, const mg_item_launch &l) { return mg_fpw_args{base, (const mg_fpw_item *)base + l.first, l.n_items}; });

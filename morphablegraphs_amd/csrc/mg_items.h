@@ -6,7 +6,8 @@
 // bisection.  A candidate's values are computed by statements that see nothing but its own row, so they depend on neither the batch
 // nor the other items.  The non-empty items of a call travel in a device table of the context (ctx->tab[]), rewritten only when it
 // differs from the last call's; a launch takes a slice of it, a call with more items than a launch holds goes through the table in
-// slices (mg_items_cut.h: the cut, the bisection and the shared-latents search as host-only code).
+// slices (mg_items_cut.h: the cut, the bisection, the table's layout and the shared-latents search as host-only code).  An entry point
+// fills its own kernel-side item and names the arrays that travel behind the items (mg_items_table); the rest is here.
 #pragma once
 #include "mg_construct.h"
 #include "mg_items_cut.h"
@@ -43,9 +44,10 @@ __device__ __forceinline__ void mg_item_stage_latents(const void *lat, int64_t l
 
 // phase 1: control points c[cand * CS + row] = mean', then fma(E'[k][.], s[k], .) for k ascending (mg_control_point) over the item's
 // NR staged rows (sE[L][NR], smean[NR]); one (candidate, row) per thread: consecutive lanes read consecutive doubles of E', the latent
-// is a broadcast
-__device__ __forceinline__ void mg_item_control_points(const double *smean, const double *sE, const double *slat, int ncand, int NR, int L, double *scp, int CS) {
-    for (int e = threadIdx.x; e < ncand * NR; e += 256) {
+// is a broadcast.  A kernel that keeps some waves for other work names the first of the `stride` threads that take part
+__device__ __forceinline__ void mg_item_control_points(const double *smean, const double *sE, const double *slat, int ncand, int NR, int L, double *scp, int CS,
+                                                       int first = threadIdx.x, int stride = 256) {
+    for (int e = first; e < ncand * NR; e += stride) {
         const int c = e / NR, j = e - c * NR;
         const double *s = slat + c * L;
         scp[c * CS + j] = mg_control_point(smean[j], sE + j, (size_t)NR, L, [&](int k) { return s[k]; });
@@ -73,6 +75,23 @@ static int mg_items_check(const char *who, int32_t n_items, const Item *items, i
         MG_ITEM_REQUIRE(q.n_samples == 0 || q.latents_dev, "%s: item %d: the latents are NULL", who, i);
         if ((rc = after_latents(i, q)) != MG_OK) return rc;
     }
+    return MG_OK;
+}
+
+// The table of a call: its non-empty items as the kernel reads them (DItem, zeroed, then item_of(i, d, append): the caller's item i
+// into d), then the arrays item_of names: append(vector) puts one behind the table, 8-byte aligned, and returns its offset from the
+// table's base for d to keep.  A table of 2 GiB or more is MG_ERR_UNSUPPORTED.
+template <class DItem, class SamplesOf, class ItemOf>
+static int mg_items_table(const char *who, int n_items, SamplesOf samples_of, std::vector<unsigned char> &table, ItemOf item_of) {
+    const std::vector<int> of = mg_nonempty_items(n_items, samples_of);
+    std::vector<DItem> ds(of.size());
+    table.assign(ds.size() * sizeof(DItem), 0);
+    if (!ds.empty()) memset((void *)ds.data(), 0, table.size());
+    for (size_t e = 0; e < ds.size(); e++) {
+        item_of(of[e], ds[e], [&](const auto &v) { return (uint32_t)mg_table_append(table, v.data(), v.size() * sizeof(*v.data())); });
+        MG_REQUIRE_AS(table.size() < ((size_t)1 << 31), MG_ERR_UNSUPPORTED, "%s: the item table exceeds 2 GiB", who);
+    }
+    if (!ds.empty()) memcpy(table.data(), ds.data(), ds.size() * sizeof(DItem));
     return MG_OK;
 }
 

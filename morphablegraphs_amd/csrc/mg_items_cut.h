@@ -1,8 +1,10 @@
-// The host decisions of the item-table entry points (mg_items.h), as plain code: standard headers only and no HIP call, so that
-// tests/native/items_check.cpp compiles this file alone.
+// The host decisions of the item-table entry points (mg_items.h) -- the cut into launches, the bisection, which items travel and
+// where an array lands behind them, the shared latents -- as plain code: standard headers only and no HIP call, so that
+// tests/native/items_check.cpp compiles this file without the library.
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#include <cstring>
 
 #include <algorithm>
 #include <vector>
@@ -42,6 +44,23 @@ inline std::vector<mg_item_launch> mg_cut_items(int n_items, SamplesOf samples_o
         taken++;
     }
     return launches;
+}
+
+// the caller's index of every non-empty item, in order: the items of the device table
+template <class SamplesOf>
+inline std::vector<int> mg_nonempty_items(int n_items, SamplesOf samples_of) {
+    std::vector<int> of;
+    for (int i = 0; i < n_items; i++)
+        if (samples_of(i) != 0) of.push_back(i);
+    return of;
+}
+
+// `bytes` of data behind a device table, at the next multiple of 8 (the gap zeroed); returns where, in bytes from the table's base
+inline size_t mg_table_append(std::vector<unsigned char> &table, const void *data, size_t bytes) {
+    const size_t at = (table.size() + 7) & ~(size_t)7;
+    table.resize(at + bytes, 0);
+    if (bytes) std::memcpy(table.data() + at, data, bytes);
+    return at;
 }
 
 // the item of workgroup wg in a launch's slice of the table: the last one whose wg0 is not past it (the kernels' bisection)

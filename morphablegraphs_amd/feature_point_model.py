@@ -62,6 +62,25 @@ def heading_host(frame):
     return d / length, length
 
 
+def _nan_outputs(n, J, **more):
+    """The outputs of n candidates with J joints, NaN until a row is stated; more: an entry point's own arrays."""
+    out = {"start_root": np.full((n, 3), np.nan), "root_end": np.full((n, 2), np.nan), "heading_end": np.full((n, 2), np.nan),
+           "heading_len": np.full(n, np.nan)}
+    out.update(more)
+    if J:
+        out["points"] = np.full((n, 3 * J), np.nan)
+    return out
+
+
+def _state_row(out, b, fr, skeleton, joints):
+    """Row b of the outputs from its frames fr: the first, the one of `joints` (none: points stays NaN), the last."""
+    out["start_root"][b] = fr[0, :3]
+    for j, joint in enumerate(joints):
+        out["points"][b, 3 * j:3 * j + 3] = joint_position_host(skeleton, fr[1], joint) - fr[0, :3]
+    out["root_end"][b] = fr[2, 0], fr[2, 2]
+    out["heading_end"][b], out["heading_len"][b] = heading_host(fr[2])
+
+
 def feature_points_host(model, S, skeleton=None, joints=(), frame_idx=0):
     """The NumPy statement of mg_feature_points for one item.  model: the reference's JSON dict or a primitive; S (n, >= L): a
     candidate reads its first L columns; skeleton: a _capi.Skeleton (needed with joints); joints: names or indices.  Returns the
@@ -74,20 +93,10 @@ def feature_points_host(model, S, skeleton=None, joints=(), frame_idx=0):
         raise ValueError("frame_idx %d outside 0 .. %d" % (frame_idx, F - 1))
     joints = [skeleton.index(j) for j in joints]
     times = np.linspace(0, F, F)[[0, int(frame_idx), F - 1]]
-    n, J = len(S), len(joints)
-    out = {"start_root": np.full((n, 3), np.nan), "root_end": np.full((n, 2), np.nan), "heading_end": np.full((n, 2), np.nan),
-           "heading_len": np.full(n, np.nan)}
-    if J:
-        out["points"] = np.full((n, 3 * J), np.nan)
-    for b in range(n):
-        if not np.isfinite(S[b, :L]).all():
-            continue
-        _, fr = hm.frames(S[b, :L], times)
-        out["start_root"][b] = fr[0, :3]
-        for j, joint in enumerate(joints):
-            out["points"][b, 3 * j:3 * j + 3] = joint_position_host(skeleton, fr[1], joint) - fr[0, :3]
-        out["root_end"][b] = fr[2, 0], fr[2, 2]
-        out["heading_end"][b], out["heading_len"][b] = heading_host(fr[2])
+    out = _nan_outputs(len(S), len(joints))
+    for b in range(len(S)):
+        if np.isfinite(S[b, :L]).all():
+            _state_row(out, b, hm.frames(S[b, :L], times)[1], skeleton, joints)
     return out
 
 
@@ -149,11 +158,8 @@ def feature_points_warped_host(model, S, skeleton=None, joints=(), frame_idx=0, 
     if frame_idx < 0:
         raise ValueError("frame_idx %d below 0" % frame_idx)
     joints = [skeleton.index(j) for j in joints]
-    n, J = len(S), len(joints)
-    out = {"start_root": np.full((n, 3), np.nan), "root_end": np.full((n, 2), np.nan), "heading_end": np.full((n, 2), np.nan),
-           "heading_len": np.full(n, np.nan), "time_mid": np.full(n, np.nan), "n_frames": np.zeros(n, dtype=np.int32)}
-    if J:
-        out["points"] = np.full((n, 3 * J), np.nan)
+    n = len(S)
+    out = _nan_outputs(n, len(joints), time_mid=np.full(n, np.nan), n_frames=np.zeros(n, dtype=np.int32))
     for b in range(n):
         with np.errstate(over="ignore", invalid="ignore"):
             times = sample_time_function_host(canonical_time_function_host(tm, F, S[b, L:L + Lt]))
@@ -168,12 +174,7 @@ def feature_points_warped_host(model, S, skeleton=None, joints=(), frame_idx=0, 
         if not np.isfinite(S[b, :L]).all():
             continue
         _, fr = hm.frames(S[b, :L], np.array([0.0, 0.0 if short else mid, F - 1.0]))
-        out["start_root"][b] = fr[0, :3]
-        if not short:
-            for j, joint in enumerate(joints):
-                out["points"][b, 3 * j:3 * j + 3] = joint_position_host(skeleton, fr[1], joint) - fr[0, :3]
-        out["root_end"][b] = fr[2, 0], fr[2, 2]
-        out["heading_end"][b], out["heading_len"][b] = heading_host(fr[2])
+        _state_row(out, b, fr, skeleton, () if short else joints)
     return out
 
 

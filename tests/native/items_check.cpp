@@ -1,7 +1,10 @@
 // What csrc/mg_items_cut.h promises the item-table entry points (mg_items.h): the cut of a call's items into launches against a
-// direct restatement, the workgroup-to-item bisection on every launch it makes, and which items share one copy of a latent matrix.
+// direct restatement, the workgroup-to-item bisection on every launch it makes, which items share one copy of a latent matrix, and
+// where an array lands behind a table.  What csrc/mg_feature_rows.h promises the feature-point entry points: the row plan of the
+// host-planned frames against a literal statement of it.
 // The workgroup bound of a launch (2^31 - 1) is reached here with sample counts no GPU test can afford.  Plain host code with its
 // own main (test infrastructure, never linked into the library); exit status 0 = every check held.
+#include "../../morphablegraphs_amd/csrc/mg_feature_rows.h"
 #include "../../morphablegraphs_amd/csrc/mg_items_cut.h"
 
 #include <cstdio>
@@ -87,7 +90,109 @@ static void check_shared(const char *name, const std::vector<lat_item> &items, c
         for (size_t i = 0; i < got.size() && i < expect.size(); i++) std::printf("  item %zu: %d, expected %d\n", i, got[i], expect[i]);
 }
 
+// The row plan, literally: sort and unique the slots' tap control points, find every slot's first among them, mark the (control
+// point, channel) pairs some range wants, number the marked pairs in order.  Then what the kernels rely on: every wanted channel of
+// every tap of a slot is found through tap[] and map[] at the row of E' it means, and nothing else is listed.
+static void check_rows(const char *name, int D, const std::vector<int32_t> &first, const std::vector<mg_feature_range> &wanted) {
+    const mg_feature_rows got = mg_feature_rows_of(D, first, wanted);
+    std::vector<int32_t> cps;
+    for (size_t s = 0; s < first.size(); s++)
+        for (int j = 0; j < 4; j++) cps.push_back(first[s] + j);
+    std::sort(cps.begin(), cps.end());
+    cps.erase(std::unique(cps.begin(), cps.end()), cps.end());
+    std::vector<int32_t> tap(first.size(), 0);
+    for (size_t s = 0; s < first.size(); s++)
+        while (cps[(size_t)tap[s]] != first[s]) tap[s]++;
+    std::vector<char> need(cps.size() * D, 0);
+    for (const mg_feature_range &w : wanted)
+        for (int j = 0; j < 4; j++)
+            for (int d = w.d0; d < w.d0 + w.count; d++) need[(size_t)(tap[(size_t)w.slot] + j) * D + d] = 1;
+    std::vector<int32_t> map(cps.size() * D, -1), src;
+    for (size_t c = 0; c < cps.size(); c++)
+        for (int d = 0; d < D; d++)
+            if (need[c * D + d]) {
+                map[c * D + d] = (int32_t)src.size();
+                src.push_back(cps[c] * D + d);
+            }
+    CHECK(got.NCP == (int32_t)cps.size() && got.NRS == (int32_t)src.size(), "%s: %d control points, %d rows; the statement lists %zu and %zu", name, got.NCP, got.NRS,
+          cps.size(), src.size());
+    CHECK(got.tap == tap, "%s: tap differs", name);
+    CHECK(got.map == map, "%s: map differs", name);
+    CHECK(got.src == src, "%s: src differs", name);
+    if ((size_t)got.NCP != cps.size() || got.map.size() != map.size() || got.tap.size() != first.size()) return;
+    size_t listed = 0;
+    for (size_t c = 0; c < cps.size(); c++)
+        for (int d = 0; d < D; d++) {
+            const int32_t row = got.map[c * D + d];
+            if (row < 0) continue;
+            listed++;
+            CHECK(row < got.NRS && (size_t)row < got.src.size() && got.src[(size_t)row] == cps[c] * D + d, "%s: map[%zu][%d] = %d does not name row %d of E'", name, c, d,
+                  row, cps[c] * D + d);
+        }
+    CHECK(listed == got.src.size(), "%s: %zu map entries for %zu rows", name, listed, got.src.size());
+    for (size_t e = 1; e < got.src.size(); e++) CHECK(got.src[e] > got.src[e - 1], "%s: src does not rise at %zu", name, e);
+    for (const mg_feature_range &w : wanted)
+        for (int j = 0; j < 4; j++)
+            for (int d = w.d0; d < w.d0 + w.count; d++) {
+                const size_t at = (size_t)(got.tap[(size_t)w.slot] + j) * D + d;
+                CHECK(at < got.map.size() && got.map[at] >= 0 && got.src[(size_t)got.map[at]] == (first[(size_t)w.slot] + j) * D + d,
+                      "%s: slot %d, tap %d, channel %d is not found at its row", name, w.slot, j, d);
+            }
+}
+
+// the plain kernel's three slots (root xyz; root xyz and the quaternions at `quats`; the root's seven) and the time-warped kernel's two
+static void check_plans(const char *name, int D, const std::vector<int32_t> &first, const std::vector<int> &quats) {
+    std::vector<mg_feature_range> three = {{0, 0, 3}, {1, 0, 3}, {2, 0, 7}};
+    for (const int qc : quats) three.push_back({1, qc, 4});
+    check_rows(name, D, first, three);
+    check_rows(name, D, {first[0], first[2]}, {{0, 0, 3}, {1, 0, 7}});
+}
+
 int main() {
+    for (const int D : {7, 8, 79}) {
+        const std::vector<std::vector<int>> quat_sets = {{}, {3}, {D - 4}, {3, D - 4, 3}};
+        for (const std::vector<int> &quats : quat_sets) {
+            check_plans("one frame", D, {0, 0, 0}, quats);
+            check_plans("one frame, later", D, {5, 5, 5}, quats);
+            check_plans("frame 0 as the mid frame", D, {0, 0, 9}, quats);
+            check_plans("frame F - 1 as the mid frame", D, {0, 9, 9}, quats);
+            for (int shared = 1; shared <= 3; shared++) {
+                check_plans("mid window overlaps the first", D, {0, 4 - shared, 12}, quats);
+                check_plans("mid window overlaps the last", D, {0, 8 + shared, 12}, quats);
+                check_plans("all three overlap", D, {0, 4 - shared, 3}, quats);
+            }
+            check_plans("adjacent windows", D, {0, 4, 8}, quats);
+            check_plans("disjoint windows", D, {2, 11, 40}, quats);
+        }
+    }
+    // seeded random slot sets: one to four slots in any order, ranges anywhere in 0 .. D
+    {
+        uint32_t state = 12345u;
+        auto draw = [&](int n) { state = state * 1664525u + 1013904223u; return (int)((state >> 8) % (uint32_t)n); };
+        for (int round = 0; round < 4000; round++) {
+            const int D = 7 + draw(6), slots = 1 + draw(4);
+            std::vector<int32_t> first;
+            for (int s = 0; s < slots; s++) first.push_back(draw(12));
+            std::vector<mg_feature_range> wanted;
+            for (int r = draw(8); r > 0; r--) {
+                const int d0 = draw(D), count = draw(D - d0 + 1);
+                wanted.push_back({draw(slots), d0, count});
+            }
+            check_rows("random", D, first, wanted);
+        }
+    }
+
+    // an array behind a table: at the next multiple of 8, the gap zeroed, an empty array at its place too
+    {
+        std::vector<unsigned char> table(13, 0xff);
+        const int32_t three[3] = {1, 2, 3};
+        const size_t a = mg_table_append(table, three, sizeof(three)), b = mg_table_append(table, nullptr, 0), c = mg_table_append(table, three, 4);
+        CHECK(a == 16 && b == 32 && c == 32 && table.size() == 36, "appends at %zu, %zu, %zu, %zu bytes in all", a, b, c, table.size());
+        CHECK(table[12] == 0xff && table[13] == 0 && table[15] == 0 && table[16] == 1 && table[28] == 0 && table[32] == 1, "the appended bytes");
+        const std::vector<int> of = mg_nonempty_items(5, [](int i) { return i % 2 ? 0 : 7; });
+        CHECK(of == std::vector<int>({0, 2, 4}), "the non-empty items");
+    }
+
     const int MAX = 8;
     check_cut("no items", {}, 16, MAX, 0);
     check_cut("all empty", {{0, 5}, {0, 7}, {0, 9}}, 16, MAX, 0);

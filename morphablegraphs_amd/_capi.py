@@ -52,6 +52,8 @@ MG_WALK_MAX_STEPS = 64           # steps of one mg_walk_frames call (include/mg_
 MG_WALK_TILE = 32                # frames per workgroup of mg_walk_frames_kernel (csrc/mg_walk.hip)
 MG_FUSED_MAX_OPTIONS = 24        # options of one mg_options_step_device_counts launch (csrc/mg_options.hip)
 MG_STEP_LENGTH_MAX_ITEMS = 256   # non-empty items of one mg_step_lengths launch (include/mg_hip.h); a call with more goes in slices
+MG_SLEN_TILE = 16                # candidates per workgroup of mg_step_length_kernel (csrc/mg_step_length_layout.h)
+MG_SLEN_LDS_MAX = 150 * 1024     # bytes of LDS past which mg_step_lengths refuses an item (csrc/mg_step_length_layout.h)
 MG_FEATURE_POINTS_MAX_ITEMS = 256   # non-empty items of one mg_feature_points launch (include/mg_hip.h); a call with more goes in slices
 MG_FEATURE_POINTS_MAX_JOINTS = 32   # listed joints of one item
 MG_FEATURE_POINTS_TILE = 16         # candidates per workgroup of mg_feature_points_kernel (csrc/mg_feature_points.hip)

@@ -22,9 +22,7 @@
 
 #include "mg_frames_common.h"
 #include "mg_items.h"
-
-#define MG_SLEN_TILE 16                  // candidates per workgroup
-#define MG_SLEN_LDS_MAX (150 * 1024)
+#include "mg_step_length_layout.h"   // MG_SLEN_TILE, MG_SLEN_LDS_MAX, mg_slen_layout_of: the workgroup's LDS, host-only
 
 struct mg_slen_item {                    // one non-empty item as the kernel reads it
     const double *Et, *mean;             // [L][R], (R): E' and mean' (scaled by translation_maxima), row = i * D + d
@@ -41,26 +39,6 @@ struct mg_slen_args {
     const mg_slen_item *items;           // the launch's slice of the table
     int32_t n_items;
 };
-
-// LDS of a workgroup, in doubles, and where its parts start (host and device agree through this)
-struct mg_slen_layout {
-    int E, mean, w, lat, cp, seg, ints, total_bytes;
-    int NR, FS;
-};
-__host__ __device__ static inline mg_slen_layout mg_slen_layout_of(int L, int NB, int F) {
-    mg_slen_layout y;
-    y.NR = 3 * NB;
-    y.FS = F | 1;                        // odd: the lanes of phase 3 (one per candidate) read different banks
-    y.E = 0;
-    y.mean = y.E + L * y.NR;
-    y.w = y.mean + y.NR;
-    y.lat = y.w + 4 * F;
-    y.cp = y.lat + MG_SLEN_TILE * L;
-    y.seg = y.cp + MG_SLEN_TILE * y.NR;
-    y.ints = y.seg + MG_SLEN_TILE * y.FS;   // then int32: i0[F], bad[MG_SLEN_TILE]
-    y.total_bytes = y.ints * 8 + (F + MG_SLEN_TILE) * 4;
-    return y;
-}
 
 // channel d of the root at canonical frame f from a candidate's control points
 __device__ __forceinline__ double mg_slen_position(const double *cp, const double *sw, const int32_t *si0, int f, int d) {
@@ -150,6 +128,9 @@ static int mg_slen_check(const char *who, int32_t n_items, const mg_step_length_
         for (int f = 0; f < g->T; f++)
             MG_ITEM_REFUSE(g->i0[f] < 0 || g->i0[f] + 4 > p->NB, "%s: item %d: frame %d takes control points %d .. %d of %d", who, i, f, g->i0[f],
                            g->i0[f] + 3, p->NB);
+        // (the first two never refuse on their own: 8 L 3 NB bytes past 2^20 entries, or 160 F bytes past 2^16 frames, are megabytes
+        // beyond MG_SLEN_LDS_MAX, and tests/step_length_cases.py's sweep is refused by the LDS limit at L 56, NB 64, F 209.  They stand in
+        // front of mg_slen_layout_of so that its int arithmetic cannot overflow into a size that passes)
         MG_ITEM_REFUSE((int64_t)p->L * 3 * p->NB > (1 << 20) || p->F > (1 << 16) || mg_slen_layout_of(p->L, p->NB, p->F).total_bytes > MG_SLEN_LDS_MAX,
                        "%s: item %d: the root tables (%d x %d control points, %d frames) do not fit LDS", who, i, p->L, 3 * p->NB, p->F);
         MG_ITEM_REFUSE_GRID(who, i, items[i].n_samples, MG_SLEN_TILE);

@@ -1,13 +1,17 @@
 // What csrc/mg_items_cut.h promises the item-table entry points (mg_items.h): the cut of a call's items into launches against a
 // direct restatement, the workgroup-to-item bisection on every launch it makes, which items share one copy of a latent matrix, and
 // where an array lands behind a table.  What csrc/mg_feature_rows.h promises the feature-point entry points: the row plan of the
-// host-planned frames against a literal statement of it.
+// host-planned frames against a literal statement of it.  What csrc/mg_step_length_layout.h gives the step-length kernel: its parts
+// in order without overlap, and, called as `items_check slen L NB F [L NB F ...]`, the tile, the limit and every shape's total_bytes
+// on a line each, for tests/test_step_length_shapes_host.py to compare its restatement with.
 // The workgroup bound of a launch (2^31 - 1) is reached here with sample counts no GPU test can afford.  Plain host code with its
 // own main (test infrastructure, never linked into the library); exit status 0 = every check held.
 #include "../../morphablegraphs_amd/csrc/mg_feature_rows.h"
 #include "../../morphablegraphs_amd/csrc/mg_items_cut.h"
+#include "../../morphablegraphs_amd/csrc/mg_step_length_layout.h"
 
 #include <cstdio>
+#include <cstdlib>
 
 static int failures = 0;
 #define CHECK(cond, ...) do { if (!(cond)) { if (failures++ < 20) { std::printf("FAIL %s:%d: ", __FILE__, __LINE__); std::printf(__VA_ARGS__); std::printf("\n"); } } } while (0)
@@ -148,7 +152,28 @@ static void check_plans(const char *name, int D, const std::vector<int32_t> &fir
     check_rows(name, D, {first[0], first[2]}, {{0, 0, 3}, {1, 0, 7}});
 }
 
-int main() {
+// the step-length workgroup's LDS: every part starts where the one before it ends, the int32 tail behind the doubles
+static void check_slen_layout(int L, int NB, int F) {
+    const mg_slen_layout y = mg_slen_layout_of(L, NB, F);
+    const int T = MG_SLEN_TILE;
+    CHECK(y.NR == 3 * NB && y.FS >= F && y.FS <= F + 1 && (y.FS & 1), "slen %d %d %d: NR %d, FS %d", L, NB, F, y.NR, y.FS);
+    CHECK(y.E == 0 && y.mean - y.E == L * y.NR && y.w - y.mean == y.NR && y.lat - y.w == 4 * F && y.cp - y.lat == T * L && y.seg - y.cp == T * y.NR &&
+              y.ints - y.seg == T * y.FS && y.total_bytes == y.ints * 8 + 4 * (F + T),
+          "slen %d %d %d: the parts are not back to back", L, NB, F);
+}
+
+int main(int argc, char **argv) {
+    if (argc > 1 && std::strcmp(argv[1], "slen") == 0) {
+        std::printf("tile %d\nlds_max %d\n", MG_SLEN_TILE, MG_SLEN_LDS_MAX);
+        for (int a = 2; a + 2 < argc; a += 3) {
+            const int L = std::atoi(argv[a]), NB = std::atoi(argv[a + 1]), F = std::atoi(argv[a + 2]);
+            std::printf("%d %d %d %d\n", L, NB, F, mg_slen_layout_of(L, NB, F).total_bytes);
+        }
+        return 0;
+    }
+    for (const int L : {1, 3, 64, 65})
+        for (const int NB : {4, 7, 64})
+            for (const int F : {2, 3, 127, 128, 257}) check_slen_layout(L, NB, F);
     for (const int D : {7, 8, 79}) {
         const std::vector<std::vector<int>> quat_sets = {{}, {3}, {D - 4}, {3, D - 4, 3}};
         for (const std::vector<int> &quats : quat_sets) {

@@ -341,7 +341,7 @@ int mg_memset(mg_context *ctx, void *dst_dev, int value, int64_t bytes);
  *       8 = mg_joint_tracks, 9 = mg_score_frame_constraints, 10 = mg_score_trajectory[_points],
  *       11 = mg_cluster_tree_search (both tree kinds: mg_tree_search_kernel or mg_kd_tree_search_kernel),
  *       12 = the frames kernel of mg_walk_frames, 13 = mg_score_walk_time, 14 = mg_step_lengths, 15 = mg_feature_points,
- *       16 = mg_feature_points_warped. */
+ *       16 = mg_feature_points_warped, 17 = mg_mixture_scores. */
 int mg_profile_enable(mg_context *ctx, int enabled);
 int mg_profile_reset(mg_context *ctx);
 int mg_profile_get(mg_context *ctx, int slot, double *total_ms, int64_t *launches);
@@ -1200,9 +1200,9 @@ int mg_walk_time_table_uploads(mg_context *ctx, int64_t *uploads);   /* mg_conte
 
 /* The per-call descriptor tables a context keeps on the device, each rewritten only when a call's table differs from the last call's:
  * of mg_options_step's one-launch path, mg_cluster_tree_search, mg_walk_frames, mg_score_walk_residuals, mg_score_walk_time and
- * mg_step_lengths, of mg_feature_points and of mg_feature_points_warped.  mg_context_table_uploads: how often table `which` of the context went to the device so far. */
+ * mg_step_lengths, of mg_feature_points, of mg_feature_points_warped and of mg_mixture_scores.  mg_context_table_uploads: how often table `which` of the context went to the device so far. */
 enum { MG_TABLE_FUSED = 0, MG_TABLE_TREE = 1, MG_TABLE_WALK = 2, MG_TABLE_WALK_SCORE = 3, MG_TABLE_WALK_TIME = 4, MG_TABLE_STEP_LENGTH = 5,
-       MG_TABLE_FEATURE_POINTS = 6, MG_TABLE_FEATURE_POINTS_WARPED = 7, MG_TABLE_COUNT = 8 };
+       MG_TABLE_FEATURE_POINTS = 6, MG_TABLE_FEATURE_POINTS_WARPED = 7, MG_TABLE_MIXTURE_SCORES = 8, MG_TABLE_COUNT = 9 };
 int mg_context_table_uploads(mg_context *ctx, int which, int64_t *uploads);
 
 /* Step lengths without frames in memory, ONE launch for every candidate of every item (csrc/mg_step_length.hip): what
@@ -1338,6 +1338,67 @@ typedef struct {
     int32_t *n_frames_dev;              /* (n_samples) or NULL */
 } mg_warped_feature_point_item;
 int mg_feature_points_warped(int32_t n_items, const mg_warped_feature_point_item *items, int latent_dtype);
+
+/* Targets scored against the reachability mixtures of many nodes, ONE launch for every target of every item
+ * (csrc/mg_mixture_scores.hip): what the reference's FeaturePointModel asks of its stored mixture in check_reachability,
+ * evaluate_target_point and score_trajectory_target (construction/feature_point_model.py) -- sklearn's score_samples of a
+ * full-covariance mixture over 3, 4 or 3 J features -- and what a planner asks of every node of a graph.
+ *
+ * A feature mixture is formed once, on the host, in float64 (csrc/mg_mixture_image.h, plain host code).  Per component k:
+ *   P   the upper-triangular precision Cholesky factor inv(chol_lower(C))^T (sklearn's _compute_precision_cholesky): the Cholesky
+ *       factor row by row and its inverse by forward substitution, every product and difference rounded on its own (no fma), the sums
+ *       in ascending index order; only the triangle is kept;
+ *   m   m_j = mu_0 P[0][j], then fma(mu_i, P[i][j], .) for i = 1 .. j;
+ *   c   (-0.5 dim log(2 pi) + (log P[0][0] + log P[1][1] + ..)) + log w.
+ * weights, means (n_components, dim), covars (n_components, dim, dim): HOST arrays; of a covariance the lower triangle is read.
+ * MG_ERR_INVALID_ARGUMENT: NULL pointers, a weight that is negative or not finite, a mean or a threshold that is NaN, a covariance that
+ * is not positive definite (with sklearn's text for it).  A component of weight 0 is legal: its c is -inf.  MG_ERR_UNSUPPORTED, never an
+ * approximate answer: dim outside 1 .. MG_FEATURE_MIXTURE_MAX_DIM (3 x MG_FEATURE_POINTS_MAX_JOINTS), n_components outside 1 ..
+ * MG_FEATURE_MIXTURE_MAX_COMPONENTS.  ctx NULL makes a mixture without a device copy: mg_mixture_scores_host and the two getters take
+ * it, mg_mixture_scores refuses it.  Otherwise the image goes to the device once (one allocation, freed by _destroy). */
+#define MG_FEATURE_MIXTURE_MAX_DIM 96
+#define MG_FEATURE_MIXTURE_MAX_COMPONENTS 64
+typedef struct mg_feature_mixture mg_feature_mixture;
+int mg_feature_mixture_create(mg_context *ctx, int32_t n_components, int32_t dim, const double *weights, const double *means,
+                              const double *covars, double threshold, mg_feature_mixture **out);
+void mg_feature_mixture_destroy(mg_feature_mixture *m);
+int mg_feature_mixture_info(const mg_feature_mixture *m, int32_t *n_components, int32_t *dim, double *threshold);
+/* The image as formed: prec_chol (n_components, dim, dim) with zeros below the diagonal, m (n_components, dim), c (n_components);
+ * HOST arrays, each may be NULL. */
+int mg_feature_mixture_get_image(const mg_feature_mixture *m, double *prec_chol, double *mean_prec, double *log_const);
+
+/* The scores.  Per target x (the mixture's dim columns of a row from target_offset on) and component k, float64, every operation
+ * rounded on its own:
+ *   y_j   = (x_0 P[0][j], then fma(x_i, P[i][j], .) for i = 1 .. j) - m_j
+ *   q     = y_0 y_0, then fma(y_j, y_j, .) for j = 1 .. dim - 1
+ *   wlp_k = fma(-0.5, q, c_k)                                    (sklearn's _estimate_weighted_log_prob)
+ *   logp  = max + log(exp(wlp_0 - max) + exp(wlp_1 - max) + ..), max the largest wlp_k, the sum in component order; -inf where
+ *           every wlp_k is -inf                                  (score_samples)
+ *   reachable = !(logp < threshold): the reference's `if score < threshold: False else: True`, so a NaN score reads as reachable.
+ * wlp carries no transcendental function of the target: the device's and the host twin's are the same bits; logp differs by the
+ * exp and log of the two maths libraries.  A target with a coordinate that is not finite gets NaN in logp and in its wlp row, and
+ * nothing else does; a target's values depend on neither the batch nor the other items nor its position in either.  Items may share a
+ * target matrix (N nodes against one set of targets), a mixture may repeat.
+ * Everything is checked before any launch or copy.  MG_ERR_INVALID_ARGUMENT: a NULL context, a NULL item table with n_items > 0, a
+ * NULL mixture, a mixture of another context (or without a device copy), negative counts, target_offset < 0 or target_offset + dim >
+ * ld, all outputs NULL, NULL targets with n_targets > 0.  n_items == 0 or all items empty: MG_OK, no launch; empty items among others
+ * are skipped.  A launch takes MG_MIXTURE_SCORES_MAX_ITEMS non-empty items; a call with more goes through them in slices itself.  Apart
+ * from the item table (MG_TABLE_MIXTURE_SCORES: kept on the device, rewritten only when it differs from the last call's) the call
+ * allocates nothing and does not synchronise.  Profile slot 17.
+ * mg_mixture_scores_host: the same checks and the same statements (csrc/mg_mixture_image.h) on the HOST, every pointer of an item a host
+ * pointer; no device is touched, ctx may be NULL and so may the mixtures' contexts. */
+#define MG_MIXTURE_SCORES_MAX_ITEMS 256
+typedef struct {
+    const mg_feature_mixture *mixture;
+    const double *targets_dev;     /* (n_targets, ld) float64 */
+    int64_t target_offset;         /* first of the mixture's `dim` columns in a row */
+    int64_t n_targets, ld;
+    double *logp_dev;              /* (n_targets) or NULL */
+    double *wlp_dev;               /* (n_targets, n_components) weighted log-probabilities, or NULL */
+    int32_t *reachable_dev;        /* (n_targets): !(logp < threshold), or NULL */
+} mg_mixture_score_item;
+int mg_mixture_scores(mg_context *ctx, int32_t n_items, const mg_mixture_score_item *items);
+int mg_mixture_scores_host(mg_context *ctx, int32_t n_items, const mg_mixture_score_item *items);
 
 /* ---- host-pointer convenience variants (H2D, launch, D2H, synchronise) ---------------- */
 /* mg_step_lengths with every item's latents and outputs in host memory (the `_dev` members are host pointers here); items that name

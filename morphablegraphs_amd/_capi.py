@@ -40,9 +40,9 @@ MG_CONSTRAINT_VALUE_POSITION, MG_CONSTRAINT_VALUE_HEADING = 7, 8   # values of t
 PROFILE_SLOTS = {"frames": 0, "gmm_log_prob": 1, "score_constraints": 2, "argmin": 3,
                  "gmm_sample": 4, "spline_evaluate": 5, "step": 6, "options_step": 7, "joint_tracks": 8, "frame_constraints": 9, "trajectory": 10,
                  "cluster_tree_search": 11, "walk_frames": 12, "walk_time": 13, "step_lengths": 14, "feature_points": 15,
-                 "feature_points_warped": 16}
+                 "feature_points_warped": 16, "mixture_scores": 17}
 DEVICE_TABLES = {"fused": 0, "tree": 1, "walk": 2, "walk_score": 3, "walk_time": 4, "step_length": 5, "feature_points": 6,
-                 "feature_points_warped": 7}    # MG_TABLE_* (include/mg_hip.h)
+                 "feature_points_warped": 7, "mixture_scores": 8}    # MG_TABLE_* (include/mg_hip.h)
 MG_TREE_MAX_DEPTH, MG_TREE_MAX_CHILDREN, MG_TREE_MAX_CANDIDATES = 64, 256, 64    # include/mg_hip.h
 MG_TREE_TIE, MG_TREE_NO_RESULT, MG_TREE_OVERFLOW, MG_TREE_NO_MEAN = 1, 2, 4, 8
 MG_KD_MAX_DEPTH = 64
@@ -58,6 +58,18 @@ MG_FEATURE_POINTS_MAX_ITEMS = 256   # non-empty items of one mg_feature_points l
 MG_FEATURE_POINTS_MAX_JOINTS = 32   # listed joints of one item
 MG_FEATURE_POINTS_TILE = 16         # candidates per workgroup of mg_feature_points_kernel (csrc/mg_feature_points.hip)
 MG_FEATURE_POINTS_WARPED_MAX_F = 256   # canonical frames mg_feature_points_warped inverts in LDS (include/mg_hip.h)
+MG_FEATURE_MIXTURE_MAX_DIM, MG_FEATURE_MIXTURE_MAX_COMPONENTS = 96, 64   # caps of mg_feature_mixture_create (include/mg_hip.h)
+MG_MIXTURE_SCORES_MAX_ITEMS = 256   # non-empty items of one mg_mixture_scores launch (include/mg_hip.h); a call with more goes in slices
+MG_MIXTURE_SCORES_TILE = 64         # targets per workgroup of mg_mixture_scores_kernel (csrc/mg_mixture_image.h)
+
+
+def mixture_lds_bytes(n_components, dim):
+    """Dynamic LDS of a workgroup of mg_mixture_scores_kernel (mg_mix_lds_of, csrc/mg_mixture_image.h): up to 8 dimensions the
+    mixture's image, above the tile's targets [dim][65] and its weighted log-probabilities [K][64]; past 64 KB the kernel takes
+    the large-LDS opt-in."""
+    if dim <= 8:
+        return n_components * (dim * (dim + 1) // 2 + dim + 1) * 8
+    return (dim * 65 + n_components * MG_MIXTURE_SCORES_TILE) * 8
 
 
 @functools.lru_cache(maxsize=None)
@@ -104,6 +116,8 @@ EXPORTED_SYMBOLS = [
     "mg_score_walk_time", "mg_score_walk_time_host", "mg_walk_time_table_uploads", "mg_context_table_uploads",
     "mg_step_lengths", "mg_step_lengths_host",
     "mg_feature_points", "mg_feature_points_host", "mg_feature_points_warped", "mg_feature_points_warped_host",
+    "mg_feature_mixture_create", "mg_feature_mixture_destroy", "mg_feature_mixture_info", "mg_feature_mixture_get_image",
+    "mg_mixture_scores", "mg_mixture_scores_host",
 ]
 
 
@@ -282,7 +296,7 @@ def load_library(path=None):
     lib.mg_primitive_canonical_grid.argtypes = [C.c_void_p]
     lib.mg_time_grid_size.argtypes = [C.c_void_p]
     for name in ("mg_context_destroy", "mg_primitive_destroy", "mg_time_grid_destroy", "mg_constraint_set_destroy", "mg_trajectory_destroy", "mg_track_plan_destroy",
-                 "mg_cluster_tree_destroy"):
+                 "mg_cluster_tree_destroy", "mg_feature_mixture_destroy"):
         getattr(lib, name).restype = None
         getattr(lib, name).argtypes = [C.c_void_p]
     vp, i32, i64, u64, dbl = C.c_void_p, C.c_int, C.c_int64, C.c_uint64, C.c_double
@@ -423,6 +437,11 @@ def load_library(path=None):
         "mg_feature_points_host": [i32, vp, i32],
         "mg_feature_points_warped": [i32, vp, i32],
         "mg_feature_points_warped_host": [i32, vp, i32],
+        "mg_feature_mixture_create": [vp, i32, i32, vp, vp, vp, dbl, C.POINTER(vp)],
+        "mg_feature_mixture_info": [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(dbl)],
+        "mg_feature_mixture_get_image": [vp, vp, vp, vp],
+        "mg_mixture_scores": [vp, i32, vp],
+        "mg_mixture_scores_host": [vp, i32, vp],
     }
     for name, argtypes in sigs.items():
         fn = getattr(lib, name)
@@ -1260,6 +1279,129 @@ def feature_points_warped(items, outputs=WARPED_FEATURE_POINT_OUTPUTS):
     if items:
         feature_points_warped_table(items[0]["prim"].lib, len(items), table, dtype)
     return out
+
+
+class FeatureMixture(object):
+    """A reachability mixture as the scoring kernel reads it (mg_feature_mixture): weights (K,), means (K, dim), full covariances
+    (K, dim, dim) and the log-likelihood threshold; the image -- precision Cholesky factors, mu . P, the constants -- is formed once
+    on the host in float64 and, with a context, copied to its device.  ctx None and host=True: no device copy (and no device
+    needed): such a mixture is scored by mixture_scores_host alone.  ctx None and host=False: the process's shared context."""
+
+    def __init__(self, ctx, weights, means, covars, threshold=-np.inf, host=False):
+        self.ctx = None if host else default_context(ctx)
+        self.lib = self.ctx.lib if self.ctx is not None else load_library()
+        w = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+        mu = np.ascontiguousarray(np.atleast_2d(np.asarray(means, dtype=np.float64)))
+        if len(mu) != len(w):
+            raise ValueError("%d weights, %d means" % (len(w), len(mu)))
+        cov = np.ascontiguousarray(np.asarray(covars, dtype=np.float64).reshape(len(w), mu.shape[1], mu.shape[1]))
+        self.handle = None
+        h = C.c_void_p()
+        _check(self.lib.mg_feature_mixture_create(self.ctx.handle if self.ctx is not None else None, len(w), mu.shape[1], _host_ptr(w), _host_ptr(mu),
+                                                  _host_ptr(cov), float(threshold), C.byref(h)))
+        self.handle = h
+        self.n_components, self.dim, self.threshold = len(w), mu.shape[1], float(threshold)
+
+    def image(self):
+        """(prec_chol (K, dim, dim) upper triangular, mu . P (K, dim), c (K,)) as the library formed them."""
+        P, m, c = np.empty((self.n_components, self.dim, self.dim)), np.empty((self.n_components, self.dim)), np.empty(self.n_components)
+        _check(self.lib.mg_feature_mixture_get_image(self.handle, _host_ptr(P), _host_ptr(m), _host_ptr(c)))
+        return P, m, c
+
+    def close(self):
+        if getattr(self, "handle", None) and (self.ctx is None or self.ctx.handle):
+            self.lib.mg_feature_mixture_destroy(self.handle)
+        self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class MixtureScoreItem(C.Structure):   # struct mg_mixture_score_item
+    _fields_ = [("mixture", C.c_void_p), ("targets", C.c_void_p), ("target_offset", C.c_int64), ("n_targets", C.c_int64), ("ld", C.c_int64),
+                ("logp", C.c_void_p), ("wlp", C.c_void_p), ("reachable", C.c_void_p)]
+
+
+MIXTURE_SCORE_OUTPUTS = ("logp", "wlp", "reachable")
+
+
+def mixture_scores_table(ctx, n_items, table, host=False, lib=None):
+    """mg_mixture_scores (device pointers in the table; asynchronous on the context's stream) or mg_mixture_scores_host (host
+    pointers; runs on the host, ctx may be None) on a (MixtureScoreItem * n) table as it stands; table None passes NULL."""
+    lib = lib or (ctx.lib if ctx is not None else load_library())
+    fn = lib.mg_mixture_scores_host if host else lib.mg_mixture_scores
+    _check(fn(ctx.handle if ctx is not None else None, int(n_items), C.cast(table, C.c_void_p) if table is not None else None))
+
+
+def _mixture_items(items, outputs):
+    """[(mixture, X (n, ld) float64 contiguous, offset)] and the per-item output arrays of a mixture_scores call."""
+    unknown = [o for o in outputs if o not in MIXTURE_SCORE_OUTPUTS]
+    if unknown or not outputs:
+        raise ValueError("outputs %r: some of %r" % (tuple(outputs), MIXTURE_SCORE_OUTPUTS))
+    prepared, out = [], []
+    for it in items:
+        mix, X = it[0], np.asarray(it[1], dtype=np.float64)
+        X = X if X.ndim == 2 and X.flags.c_contiguous else np.ascontiguousarray(X.reshape(-1, mix.dim) if X.ndim != 2 else X)
+        prepared.append((mix, X, int(it[2]) if len(it) > 2 else 0))
+        shapes = {"logp": ((len(X),), np.float64), "wlp": ((len(X), mix.n_components), np.float64), "reachable": ((len(X),), np.int32)}
+        out.append({name: np.empty(*shapes[name]) for name in outputs})
+    return prepared, out
+
+
+def _same_array(a, b):
+    return a is b or (a.ctypes.data == b.ctypes.data and a.shape == b.shape and a.strides == b.strides)
+
+
+def mixture_scores(items, outputs=("logp",), ctx=None):
+    """Every target of every item against its mixture in ONE mg_mixture_scores launch.  items: (FeatureMixture, X) or (FeatureMixture,
+    X, target_offset) with X (n, ld) float64 targets; an item reads the mixture's dim columns from target_offset (default 0) on, and
+    items that pass the same array share ONE copy of it on the device.  Returns per item a dict of those of `outputs`: logp (n,)
+    float64, wlp (n, K) float64 weighted log-probabilities, reachable (n,) bool: not (logp < threshold)."""
+    prepared, out = _mixture_items(items, outputs)
+    if not prepared:
+        return out
+    ctx = ctx if ctx is not None else prepared[0][0].ctx
+    table = (MixtureScoreItem * len(prepared))()
+    with ctx.buffers() as bufs:
+        shared, devs = [], []
+        for rec, (mix, X, off), arrays in zip(table, prepared, out):
+            d_x = next((d for Y, d in shared if _same_array(X, Y)), None)
+            if d_x is None and X.size:
+                d_x = bufs.upload(X)
+                shared.append((X, d_x))
+            rec.mixture, rec.targets, rec.target_offset, rec.n_targets, rec.ld = mix.handle.value, (d_x.address if d_x is not None else None), off, X.shape[0], X.shape[1]
+            devs.append({name: bufs.malloc(a.nbytes) for name, a in arrays.items()})
+            for name, d in devs[-1].items():
+                setattr(rec, name, d.address)
+        mixture_scores_table(ctx, len(prepared), table)
+        for arrays, dev in zip(out, devs):
+            for name in arrays:
+                if arrays[name].size:
+                    arrays[name] = ctx.download(dev[name], arrays[name].shape, arrays[name].dtype)
+    return [_mixture_outputs(arrays) for arrays in out]
+
+
+def _mixture_outputs(arrays):
+    if "reachable" in arrays:
+        arrays["reachable"] = arrays["reachable"].astype(bool)
+    return arrays
+
+
+def mixture_scores_host(items, outputs=("logp",)):
+    """mixture_scores by mg_mixture_scores_host: the same statements on the host, no device (the mixtures may be host-only)."""
+    prepared, out = _mixture_items(items, outputs)
+    if not prepared:
+        return out
+    table = (MixtureScoreItem * len(prepared))()
+    for rec, (mix, X, off), arrays in zip(table, prepared, out):
+        rec.mixture, rec.targets, rec.target_offset, rec.n_targets, rec.ld = mix.handle.value, (X.ctypes.data if X.size else None), off, X.shape[0], X.shape[1]
+        for name, a in arrays.items():
+            setattr(rec, name, a.ctypes.data)
+    mixture_scores_table(None, len(prepared), table, host=True, lib=prepared[0][0].lib)
+    return [_mixture_outputs(arrays) for arrays in out]
 
 
 def _i32(a):

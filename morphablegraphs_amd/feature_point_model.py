@@ -14,6 +14,10 @@ function the one sample it needs.  Without the keyword that combination raises N
 
 feature_points_host and feature_points_warped_host are the NumPy statements of the kernels' arithmetic; they need no library.
 
+Scoring targets: score_targets, score_trajectory_targets and check_reachability_batch take device=True, which scores the rows by
+mg_mixture_scores (csrc/mg_mixture_scores.hip) against the model's mixture, uploaded once; HipReachabilityIndex scores a set of
+targets against the mixtures of ALL nodes of a graph in ONE launch.  mixture_scores_host is the NumPy statement of that kernel.
+
 Not restated: plot_orientation; smoothed time functions (smooth_time_parameters=True: the Savitzky-Golay pass needs the whole
 row) and speeds other than 1 in the time-warped features; the reference's mixture.GMM class (loading gives FeatureMixture, the
 same JSON).
@@ -26,7 +30,7 @@ import numpy as np
 from . import _capi
 from . import graph_walk as gw
 from .gaussian_mixture import sample_like_sklearn
-from .gmm_trainer import HipGMMTrainer, _compute_precision_cholesky, _estimate_weighted_log_prob
+from .gmm_trainer import ILL_DEFINED_MESSAGE, HipGMMTrainer, _compute_precision_cholesky, _estimate_weighted_log_prob
 
 REF_DIR = (0.0, 0.0, 1.0)          # pose_orientation_quat turns this axis
 
@@ -176,6 +180,119 @@ def feature_points_warped_host(model, S, skeleton=None, joints=(), frame_idx=0, 
         _, fr = hm.frames(S[b, :L], np.array([0.0, 0.0 if short else mid, F - 1.0]))
         _state_row(out, b, fr, skeleton, () if short else joints)
     return out
+
+
+def _two_sum(a, b):
+    """(s, e) with s = fl(a + b) and a + b = s + e exactly (Knuth)."""
+    s = a + b
+    bb = s - a
+    return s, (a - (s - bb)) + (b - bb)
+
+
+def _fma(a, b, c):
+    """fl(a b + c) with ONE rounding, on float64 arrays, as the C fma gives it: the product exactly as two doubles (Veltkamp's
+    split, Dekker's product), then Boldo and Melquiond's three-term sum -- the small terms added with rounding to odd, so that
+    the last addition rounds the exact value.  Holds while no intermediate overflows and the product's low half is a normal
+    number (|a b| between about 1e-290 and 1e290): the ranges of a mixture's statements, not of every double.  A NaN or an
+    infinity among the operands gives a + b * c, which has their special value."""
+    a, b, c = np.broadcast_arrays(np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64), np.asarray(c, dtype=np.float64))
+    with np.errstate(invalid="ignore", over="ignore"):
+        ph = a * b
+        ta, tb = 134217729.0 * a, 134217729.0 * b                    # 2^27 + 1
+        ah, bh = ta - (ta - a), tb - (tb - b)
+        al, bl = a - ah, b - bh
+        pl = al * bl - (((ph - ah * bh) - al * bh) - ah * bl)
+        th, tl = _two_sum(c, ph)
+        v, e = _two_sum(tl, pl)
+        # rounding to odd: where the sum was inexact and its last bit is even, one step towards the error
+        even = (v.view(np.int64) & 1) == 0
+        v = np.where((e != 0.0) & even, np.nextafter(v, np.where(e > 0.0, np.inf, -np.inf)), v)
+        z = th + v
+        return np.where(np.isfinite(ph) & np.isfinite(c), z, ph + c)
+
+
+LOG_2PI = 1.8378770664093453          # log(2 pi) to the nearest double, as csrc/mg_mixture_image.h writes it
+
+
+def mixture_image_host(weights, means, covars):
+    """The image mg_feature_mixture_create forms, statement for statement (csrc/mg_mixture_image.h): (P (K, dim, dim) upper
+    triangular, m (K, dim), c (K,)).  The Cholesky factor row by row and its inverse by forward substitution, every product and
+    difference rounded on its own, the sums in ascending index order; m_j = mu_0 P[0][j], then fma(mu_i, P[i][j], .); c = (-0.5
+    dim log(2 pi) + (log P[0][0] + log P[1][1] + ..)) + log w, the logarithms by the C library's log (math.log), -inf for a weight
+    of 0.  ValueError with sklearn's text for a covariance that is not positive definite."""
+    import math
+    w = np.asarray(weights, dtype=np.float64).reshape(-1)
+    mu = np.atleast_2d(np.asarray(means, dtype=np.float64))
+    K, d = mu.shape
+    C = np.asarray(covars, dtype=np.float64).reshape(K, d, d)
+    Lo = np.zeros((K, d, d))
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        for i in range(d):
+            s = C[:, i, :i + 1].copy()                       # s[j], j = 0 .. i; the subtractions reach every s[j] in ascending p
+            for p in range(i):
+                Lo[:, i, p] = s[:, p] / Lo[:, p, p]
+                s[:, p + 1:] = s[:, p + 1:] - Lo[:, i, p, None] * Lo[:, p + 1:i + 1, p]
+            if not (np.isfinite(s[:, i]) & (s[:, i] > 0.0)).all():
+                raise ValueError(ILL_DEFINED_MESSAGE)
+            Lo[:, i, i] = np.sqrt(s[:, i])
+        X = np.zeros((K, d, d))                                  # inv(chol): X[r][c] = ((r == c) - sum_{p = c}^{r - 1} chol[r][p] X[p][c]) / chol[r][r]
+        S = np.broadcast_to(np.eye(d), (K, d, d)).copy()
+        for p in range(d):
+            X[:, p, :p + 1] = S[:, p, :p + 1] / Lo[:, p, p, None]
+            S[:, p + 1:, :p + 1] = S[:, p + 1:, :p + 1] - Lo[:, p + 1:, p, None] * X[:, p, None, :p + 1]
+    P = np.transpose(X, (0, 2, 1)).copy()
+    m = np.empty((K, d))
+    for j in range(d):
+        acc = mu[:, 0] * P[:, 0, j]
+        for i in range(1, j + 1):
+            acc = _fma(mu[:, i], P[:, i, j], acc)
+        m[:, j] = acc
+    c = np.empty(K)
+    for k in range(K):
+        if not all(np.isfinite(P[k, j, j]) and P[k, j, j] > 0.0 for j in range(d)):
+            raise ValueError(ILL_DEFINED_MESSAGE)
+        logdet = math.log(P[k, 0, 0])
+        for j in range(1, d):
+            logdet = logdet + math.log(P[k, j, j])
+        c[k] = (-0.5 * d * LOG_2PI + logdet) + (math.log(w[k]) if w[k] > 0.0 else -np.inf)
+    return P, m, c
+
+
+def mixture_scores_host(weights, means, covars, X, image=None):
+    """The NumPy statement of mg_mixture_scores for one item: (logp (n,), wlp (n, K)) of the targets X (n, dim) under the
+    full-covariance mixture, float64, every operation rounded on its own, in the kernel's order (no BLAS dot, whose summation
+    order is the library's own):
+        y_j   = (x_0 P[0][j], then fma(x_i, P[i][j], .) for i = 1 .. j) - m_j
+        q     = y_0 y_0, then fma(y_j, y_j, .)
+        wlp_k = fma(-0.5, q, c_k)
+        logp  = max + log(exp(wlp_0 - max) + exp(wlp_1 - max) + ..); -inf where every wlp_k is -inf.
+    A target with a coordinate that is not finite is NaN in both.  image: (P, m, c) in place of mixture_image_host's."""
+    P, m, c = image if image is not None else mixture_image_host(weights, means, covars)
+    K, d = m.shape
+    X = np.atleast_2d(np.asarray(X, dtype=np.float64))
+    if X.shape[1] != d:
+        raise ValueError("X has %d features, but the mixture expects %d" % (X.shape[1], d))
+    bad = ~np.isfinite(X).all(axis=1)
+    Xs = np.where(bad[:, None], 0.0, X)
+    n = len(X)
+    q = np.zeros((n, K))
+    for j in range(d):
+        acc = Xs[:, 0, None] * P[None, :, 0, j]
+        for i in range(1, j + 1):
+            acc = _fma(Xs[:, i, None], P[None, :, i, j], acc)
+        y = acc - m[None, :, j]
+        q = y * y if j == 0 else _fma(y, y, q)
+    wlp = _fma(-0.5, q, c[None, :])
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        mx = wlp.max(axis=1) if n else np.zeros(0)
+        safe = np.where(np.isfinite(mx), mx, 0.0)
+        s = np.exp(wlp[:, 0] - safe)
+        for k in range(1, K):
+            s = s + np.exp(wlp[:, k] - safe)
+        logp = np.where(mx == -np.inf, -np.inf, mx + np.log(s))
+    wlp[bad] = np.nan
+    logp[bad] = np.nan
+    return logp, wlp
 
 
 def rotation_angle(point1, point2):
@@ -387,23 +504,52 @@ class HipFeaturePointModel(object):
     def sample_new_feature(self):
         return np.ravel(self.feature_point_dist.sample())
 
-    def score_trajectory_targets(self, targets):
-        """Per-row log p of root targets under the root mixture: (n, 4) for 'vector', (n, 3) for 'angle'."""
+    def device_mixture(self, which="points", host=False):
+        """The model's mixture ("points": feature_point_dist and threshold; "root": root_feature_dist and root_threshold) as a
+        _capi.FeatureMixture, made on first use and kept until the model's mixture or threshold is another object or value
+        (retrained, reloaded); host=True: without a device copy, for _capi.mixture_scores_host."""
+        dist, threshold = (self.feature_point_dist, self.threshold) if which == "points" else (self.root_feature_dist, self.root_threshold)
+        assert dist is not None, 'Please model or load the %s distribution.' % ("feature point" if which == "points" else "root feature")
+        cache = self.__dict__.setdefault("_device_mixtures", {})
+        kept = cache.get((which, host))
+        if kept is None or kept[0] is not dist or kept[1] != threshold:
+            if kept is not None:
+                kept[2].close()
+            mix = _capi.FeatureMixture(self.ctx, dist.weights_, dist.means_, dist.covars_, -np.inf if threshold is None else threshold, host=host)
+            kept = cache[(which, host)] = (dist, threshold, mix)
+        return kept[2]
+
+    def _device_scores(self, which, targets, output="logp"):
+        mix = self.device_mixture(which)
+        targets = np.atleast_2d(np.asarray(targets, dtype=np.float64))
+        if targets.shape[1] != mix.dim:
+            raise ValueError("X has %d features, but the mixture expects %d" % (targets.shape[1], mix.dim))
+        return _capi.mixture_scores([(mix, targets)], (output,))[0][output]
+
+    def score_trajectory_targets(self, targets, device=False):
+        """Per-row log p of root targets under the root mixture: (n, 4) for 'vector', (n, 3) for 'angle'.  device=True: by
+        mg_mixture_scores."""
         assert self.root_feature_dist is not None, 'Please model or load root feature distribution.'
         targets = np.atleast_2d(np.asarray(targets, dtype=np.float64))
         width = 4 if self.root_feature_dist_type == 'vector' else 3
         assert targets.shape[1] == width, 'The trajectory target should be a vector of length %d.' % width
+        if device:
+            return self._device_scores("root", targets)
         return self.root_feature_dist.score_samples(targets)
 
     def score_trajectory_target(self, target):
         return self.score_trajectory_targets([target, ])[0]
 
-    def score_targets(self, targets):
-        """Per-row log p of feature-point targets (n, 3 J) under the stored mixture."""
+    def score_targets(self, targets, device=False):
+        """Per-row log p of feature-point targets (n, 3 J) under the stored mixture.  device=True: by mg_mixture_scores."""
         assert self.feature_point_dist is not None, 'Please model or load the feature point distribution.'
+        if device:
+            return self._device_scores("points", targets)
         return self.feature_point_dist.score_samples(targets)
 
-    def check_reachability_batch(self, targets):
+    def check_reachability_batch(self, targets, device=False):
+        if device:
+            return self._device_scores("points", targets, "reachable")
         return ~(self.score_targets(targets) < self.threshold)
 
     def evaluate_target_point(self, target_point):
@@ -533,3 +679,107 @@ class HipFeaturePointModelBuilder(object):
             result[key] = model.root_feature_dist_json()
         self.models = models
         return result
+
+
+# ---- every node's mixture against a set of targets ----------------------------------------------------------------
+class HipReachabilityIndex(object):
+    """The reachability mixtures of many nodes, on the device once, so that a planner's question -- which of a graph's N nodes
+    get to each of M targets -- is ONE mg_mixture_scores launch over one upload of the targets instead of N score_samples calls.
+
+    models: a {key: HipFeaturePointModel} dict, a built HipFeaturePointModelBuilder (its .models), or a directory of the
+    reference's JSON files: *_root_dist_angle.json for which="root", keyed (elementary action, motion primitive) from the file
+    name as the builder writes it; for which="points" every other *.json with gmm_weights, keyed by its "name".  which: "root"
+    (root_feature_dist, root_threshold) or "points" (feature_point_dist, threshold).  The nodes keep the order of `models`
+    (a directory: sorted file names).  host=True scores by mg_mixture_scores_host: the same statements on the host, no device."""
+
+    def __init__(self, models, which="root", ctx=None, host=False):
+        if which not in ("root", "points"):
+            raise ValueError("which is 'root' or 'points', got %r" % (which,))
+        self.which, self.ctx, self.host = which, ctx, bool(host)
+        if isinstance(models, str):
+            entries = self._entries_of_directory(models, which)
+        else:
+            models = getattr(models, "models", models)
+            entries = []
+            for key, model in models.items():
+                dist, threshold = (model.feature_point_dist, model.threshold) if which == "points" else (model.root_feature_dist, model.root_threshold)
+                if dist is None:
+                    raise ValueError("node %r has no %s distribution" % (key, which))
+                entries.append((key, dist.weights_, dist.means_, dist.covars_, threshold))
+        self.keys = [e[0] for e in entries]
+        self.mixtures = [_capi.FeatureMixture(ctx, w, mu, cov, -np.inf if thr is None else thr, host=self.host) for _, w, mu, cov, thr in entries]
+        self._of = {key: k for k, key in enumerate(self.keys)}
+
+    @staticmethod
+    def _entries_of_directory(directory, which):
+        entries = []
+        for root, dirs, files in sorted(os.walk(directory)):
+            for file in sorted(files):
+                is_root = file.endswith("_root_dist_angle.json")
+                if not file.endswith(".json") or is_root != (which == "root"):
+                    continue
+                with open(root + os.sep + file, 'r') as infile:
+                    data = json.load(infile)
+                if not isinstance(data, dict) or "gmm_weights" not in data:
+                    continue
+                segments = file.split('_')
+                key = (segments[0], segments[1]) if is_root and len(segments) >= 5 else data.get("name", file[:-len(".json")])
+                entries.append((key, data["gmm_weights"], data["gmm_means"], data["gmm_covars"], data.get("threshold")))
+        return entries
+
+    def __len__(self):
+        return len(self.keys)
+
+    def close(self):
+        for mix in self.mixtures:
+            mix.close()
+
+    def _run(self, items, outputs):
+        return _capi.mixture_scores_host(items, outputs) if self.host else _capi.mixture_scores(items, outputs, ctx=self.mixtures[0].ctx)
+
+    def _all(self, targets, output):
+        dims = sorted(set(mix.dim for mix in self.mixtures))
+        if len(dims) > 1:
+            raise ValueError("the index holds mixtures of %s dimensions: one set of targets cannot serve them all (scores_each takes a set per node)" % dims)
+        targets = np.atleast_2d(np.asarray(targets, dtype=np.float64))
+        if not self.mixtures:
+            return np.zeros((0, len(targets)), dtype=bool if output == "reachable" else np.float64)
+        if targets.shape[1] != dims[0]:
+            raise ValueError("targets have %d features, but the mixtures expect %d" % (targets.shape[1], dims[0]))
+        targets = np.ascontiguousarray(targets)
+        return np.stack([out[output] for out in self._run([(mix, targets) for mix in self.mixtures], (output,))])
+
+    def scores(self, targets):
+        """(n_nodes, n_targets) log p of every target under every node's mixture: one launch, one upload of the targets."""
+        return self._all(targets, "logp")
+
+    def reachable(self, targets):
+        """(n_nodes, n_targets) bool: not (log p < the node's threshold)."""
+        return self._all(targets, "reachable")
+
+    def reachable_nodes(self, target):
+        """The keys of the nodes that reach the one target, in the index's order."""
+        return [key for key, ok in zip(self.keys, self.reachable([target])[:, 0]) if ok]
+
+    def best_nodes(self, targets):
+        """Per target the key of the node with the highest log p; of equal scores the first in the index's order wins (NaN scores
+        never do, unless a target has no other)."""
+        scores = self.scores(targets)
+        if not len(self.keys):
+            raise ValueError("the index holds no node")
+        with np.errstate(invalid="ignore"):
+            filled = np.where(np.isnan(scores), -np.inf, scores)
+        return [self.keys[k] for k in np.argmax(filled, axis=0)]
+
+    def scores_each(self, targets_of, output="logp"):
+        """{key: log p (n_key,)} of per-node target sets {key: targets (n_key, dim of that node)} in the same single launch; the
+        nodes' mixtures may differ in dimension."""
+        keys = list(targets_of)
+        items = []
+        for key in keys:
+            mix = self.mixtures[self._of[key]]
+            X = np.ascontiguousarray(np.atleast_2d(np.asarray(targets_of[key], dtype=np.float64)).reshape(-1, mix.dim))
+            items.append((mix, X))
+        if not items:
+            return {}
+        return {key: out[output] for key, out in zip(keys, self._run(items, (output,)))}

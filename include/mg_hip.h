@@ -894,6 +894,21 @@ void mg_cluster_tree_destroy(mg_cluster_tree *tree);
  * MG_TREE_MAX_CANDIDATES.  records_dev: n_searches records (device memory). */
 int mg_cluster_tree_search(int32_t n_searches, mg_primitive *const *prims, mg_cluster_tree *const *trees,
                            const mg_constraint_set *const *csets, int32_t n_candidates, mg_tree_search_record *records_dev);
+/* The same launch with root trajectory constraints in the objective (what MotionPrimitiveConstraintsBuilder appends to every
+ * primitive's list for path following): search s scores, behind its keyframe set, the trajectory_counts[s] trajectories
+ * trajectories[off .. off + count) of the flat arrays (off = the counts before s added up) with their min_u and weights, in list
+ * order, aligned by alignments[s]: NULL, a previous-frame record whose joint is the root (0), or a start-pose record -- what
+ * mg_score_trajectory accepts.  A row's value has the bits of mg_score_constraints followed by mg_score_trajectory(...,
+ * accumulate = 1) per trajectory on the canonical grid, with the context's MG_OPT_TRAJECTORY_SEARCH.  trajectory_counts NULL:
+ * no search has any; alignments NULL: none is aligned; a search without trajectories ignores its alignment entry.  Zero
+ * trajectories everywhere is mg_cluster_tree_search, byte for byte.  0 <= count <= MG_TREE_MAX_TRAJECTORIES, every trajectory
+ * made for its search's primitive; otherwise MG_ERR_INVALID_ARGUMENT, as for a mix of tree kinds; another aligning joint:
+ * MG_ERR_UNSUPPORTED.  Nothing is launched on an error.  The launch is timed on profile slot 11. */
+#define MG_TREE_MAX_TRAJECTORIES 4
+int mg_cluster_tree_search_trajectories(int32_t n_searches, mg_primitive *const *prims, mg_cluster_tree *const *trees,
+                                        const mg_constraint_set *const *csets, const int32_t *trajectory_counts,
+                                        const mg_trajectory *const *trajectories, const double *min_u, const double *weights,
+                                        const mg_alignment_desc *const *alignments, int32_t n_candidates, mg_tree_search_record *records_dev);
 
 /* ---- k-means / KD cluster tree (reference space_partitioning/cluster_tree.py:117-149, cluster_tree_node.py:63-138,
  * kdtree.py:132-164,233-250) ----
@@ -1446,6 +1461,10 @@ int mg_gmm_log_prob_jac_host(mg_primitive *prim, const void *x, int x_dtype, int
                              double *jac);
 int mg_cluster_tree_search_host(int32_t n_searches, mg_primitive *const *prims, mg_cluster_tree *const *trees,
                                 const mg_constraint_set *const *csets, int32_t n_candidates, mg_tree_search_record *records);
+int mg_cluster_tree_search_trajectories_host(int32_t n_searches, mg_primitive *const *prims, mg_cluster_tree *const *trees,
+                                             const mg_constraint_set *const *csets, const int32_t *trajectory_counts,
+                                             const mg_trajectory *const *trajectories, const double *min_u, const double *weights,
+                                             const mg_alignment_desc *const *alignments, int32_t n_candidates, mg_tree_search_record *records);
 
 #ifdef __cplusplus
 }

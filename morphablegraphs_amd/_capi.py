@@ -45,6 +45,7 @@ DEVICE_TABLES = {"fused": 0, "tree": 1, "walk": 2, "walk_score": 3, "walk_time":
                  "feature_points_warped": 7, "mixture_scores": 8}    # MG_TABLE_* (include/mg_hip.h)
 MG_TREE_MAX_DEPTH, MG_TREE_MAX_CHILDREN, MG_TREE_MAX_CANDIDATES = 64, 256, 64    # include/mg_hip.h
 MG_TREE_TIE, MG_TREE_NO_RESULT, MG_TREE_OVERFLOW, MG_TREE_NO_MEAN = 1, 2, 4, 8
+MG_TREE_MAX_TRAJECTORIES = 4    # root trajectory constraints of one search (mg_cluster_tree_search_trajectories)
 MG_KD_MAX_DEPTH = 64
 # struct mg_tree_search_record
 TREE_SEARCH_RECORD = np.dtype([("row", "<i8"), ("leaf", "<i4"), ("flags", "<i4"), ("evaluations", "<i8"), ("value", "<f8")])
@@ -106,6 +107,7 @@ EXPORTED_SYMBOLS = [
     "mg_align_frames", "mg_frame_constraint_width", "mg_score_frame_constraint", "mg_score_frame_constraints", "mg_options_frame_lists", "mg_track_plan_create", "mg_track_plan_destroy", "mg_joint_tracks",
     "mg_score_constraint_residuals_chained", "mg_score_plan", "mg_option_step", "mg_options_step", "mg_options_step_device_counts", "mg_option_step_rows", "mg_options_step_rows", "mg_gmm_sample_rows", "mg_dist_broadcast",
     "mg_cluster_tree_create", "mg_cluster_tree_destroy", "mg_cluster_tree_search", "mg_cluster_tree_search_host",
+    "mg_cluster_tree_search_trajectories", "mg_cluster_tree_search_trajectories_host",
     "mg_cluster_tree_create_kd", "mg_kmeans_segments", "mg_gmm_em_fit",
     "mg_spline_fit_batch", "mg_pca_fit", "mg_pca_project", "mg_pca_backproject",
     "mg_dtw_distance_grids", "mg_dtw_paths", "mg_warp_motions", "mg_dtw_pair_costs",
@@ -407,6 +409,8 @@ def load_library(path=None):
         "mg_cluster_tree_create_kd": [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(vp)],
         "mg_cluster_tree_search": [i32, vp, vp, vp, i32, vp],
         "mg_cluster_tree_search_host": [i32, vp, vp, vp, i32, vp],
+        "mg_cluster_tree_search_trajectories": [i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp],
+        "mg_cluster_tree_search_trajectories_host": [i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp],
         "mg_kmeans_segments": [vp, vp, i64, i32, i32, vp, vp, i32, i32, vp, vp, u64, i32, dbl, vp, vp, vp, vp],
         "mg_gmm_em_fit": [vp, vp, i64, i32, i32, vp, vp, dbl, dbl, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp],
         "mg_spline_fit_batch": [vp, vp, i64, i32, i32, vp, i32, vp],
@@ -1463,10 +1467,13 @@ class KdClusterTree(ClusterTree):
         self.n_kd = n_kd
 
 
-def search_cluster_trees(prims, trees, csets, n_candidates, records_dev=None):
+def search_cluster_trees(prims, trees, csets, n_candidates, records_dev=None, trajectories=None, alignments=None):
     """mg_cluster_tree_search for len(prims) (Primitive, ClusterTree, ConstraintSet) triples of one context: ONE launch.
     Returns the records (TREE_SEARCH_RECORD array), read back in one copy; with records_dev (a DeviceBuffer of
-    len(prims) * 32 bytes) the records stay there and nothing is returned."""
+    len(prims) * 32 bytes) the records stay there and nothing is returned.
+    trajectories: per search a list of (Trajectory | None, min_u, weight), the root trajectory constraints scored behind the
+    set in list order (mg_cluster_tree_search_trajectories, the same one launch); alignments: per search the alignment dict
+    the trajectories are scored under (None: local coordinates), as score_trajectory_dev takes it."""
     m = len(prims)
     if not (len(trees) == m and len(csets) == m):
         raise ValueError("prims, trees and csets must have one entry per search")
@@ -1475,6 +1482,23 @@ def search_cluster_trees(prims, trees, csets, n_candidates, records_dev=None):
     ht = (vp * max(m, 1))(*[t.handle.value if t.handle else None for t in trees])
     hc = (vp * max(m, 1))(*[c.handle.value if c.handle else None for c in csets])
     lib = prims[0].lib if m else load_library()
+    if trajectories is not None:
+        if len(trajectories) != m or (alignments is not None and len(alignments) != m):
+            raise ValueError("trajectories and alignments must have one entry per search")
+        flat = [t for per in trajectories for t in per]
+        counts = (C.c_int32 * max(m, 1))(*[len(per) for per in trajectories])
+        n = max(len(flat), 1)
+        th = (vp * n)(*[t[0].handle.value if t[0] is not None and t[0].handle else None for t in flat])
+        mu = (C.c_double * n)(*[float(t[1]) for t in flat])
+        wt = (C.c_double * n)(*[float(t[2]) for t in flat])
+        descs = [ConstraintSet._marshal_alignment(a, None) if a is not None else None for a in (alignments or [None] * m)]
+        al = (vp * max(m, 1))(*[C.addressof(d) if d is not None else None for d in descs])
+        if records_dev is not None:
+            _check(lib.mg_cluster_tree_search_trajectories(m, hp, ht, hc, counts, th, mu, wt, al, int(n_candidates), _dev_ptr(records_dev)))
+            return None
+        out = np.zeros(m, dtype=TREE_SEARCH_RECORD)
+        _check(lib.mg_cluster_tree_search_trajectories_host(m, hp, ht, hc, counts, th, mu, wt, al, int(n_candidates), out.ctypes.data_as(vp)))
+        return out
     if records_dev is not None:
         _check(lib.mg_cluster_tree_search(m, hp, ht, hc, int(n_candidates), _dev_ptr(records_dev)))
         return None

@@ -246,15 +246,35 @@ class HipFeatureClusterTree(_SearchTree):
         return float(rec["value"]), self.data[row]
 
 
+class TreeSearchSet(object):
+    """What a one-launch search scores a row against: the device keyframe set, then the root trajectory constraints
+    [(_capi.Trajectory, min_u, weight)] in list order, both under `alignment` (None: local coordinates).  The trajectories
+    are the cache's (candidate_scoring.cached_trajectory(..., pin=True)): release() hands them back, once."""
+
+    def __init__(self, cset, trajectories=(), alignment=None):
+        self.cset, self.trajectories, self.alignment = cset, list(trajectories), alignment
+
+    def release(self):
+        from .candidate_scoring import release_trajectory
+        held, self.trajectories = self.trajectories, []
+        for t, _, _ in held:
+            release_trajectory(t)
+
+
 def search_on_device(searches, n_candidates):
-    """searches: [(HipFeatureClusterTree, _capi.Primitive, _capi.ConstraintSet)], all in one context.  ONE launch, one
-    read-back.  Returns the records (the caller interprets them with tree.result_of_record)."""
+    """searches: [(HipFeatureClusterTree | HipClusterTree, _capi.Primitive, _capi.ConstraintSet | TreeSearchSet)], all in one
+    context and of one tree kind.  ONE launch, one read-back, with or without trajectories (mg_cluster_tree_search[_trajectories]).
+    Returns the records (the caller interprets them with tree.result_of_record)."""
     if not searches:
         return np.zeros(0, dtype=_capi.TREE_SEARCH_RECORD)
     prims = [p for _, p, _ in searches]
     trees = [t.device_tree(p) for t, p, _ in searches]
-    csets = [c for _, _, c in searches]
-    return _capi.search_cluster_trees(prims, trees, csets, n_candidates)
+    sets = [c if isinstance(c, TreeSearchSet) else TreeSearchSet(c) for _, _, c in searches]
+    csets = [c.cset for c in sets]
+    if not any(c.trajectories for c in sets):
+        return _capi.search_cluster_trees(prims, trees, csets, n_candidates)
+    return _capi.search_cluster_trees(prims, trees, csets, n_candidates, trajectories=[c.trajectories for c in sets],
+                                      alignments=[c.alignment if c.trajectories else None for c in sets])
 
 
 def has_search_tree(node):

@@ -17,6 +17,9 @@
 #include <vector>
 
 #include "mg_score_device.h"
+#include "mg_spline_device.h"
+#include "mg_traj_device.h"
+#include "mg_tree_plan.h"   // the chunk's size, the LDS plans and their ladder, the trajectory lists as a workgroup reads them
 
 struct mg_cluster_tree {
     mg_context *ctx = nullptr;
@@ -41,12 +44,8 @@ struct mg_tree_search_desc {
     const int64_t *first;
     const int32_t *leaf, *kd_begin, *kd_roots, *kd_left, *kd_right, *kd_inner;
     int32_t dim, rows, n_kd, pad;   // rows: the set's rows of W (0: not known, W is read from global memory)
+    mg_tree_traj_desc tr;           // the root trajectory constraints scored behind the set (tr.n = 0: none)
 };
-
-#define MG_TREE_CHUNK 64
-#define MG_TREE_WAVES 4
-#define MG_TREE_THREADS (MG_TREE_CHUNK * MG_TREE_WAVES)
-#define MG_TREE_LDS_MAX (160 * 1024)
 
 // ---- heapq on LDS, for any entry type and tuple comparison ----
 // A heap is an array of entries, or (value, node) entries kept as two arrays (12 bytes an entry).
@@ -102,36 +101,7 @@ __device__ __forceinline__ void mg_heappop_compares(H h, int len, Lt lt) {
     mg_heap_siftdown(h, pos, x, lt);
 }
 
-// ---- the LDS regions, and the routines on them, that both kernels have ----
-struct mg_tree_lds_shared {
-    int n_cand, cap_local, cap_level, cap_res, wrows;
-    size_t off_w, off_rs, off_cval, off_cid, off_clast, off_frn, off_froff;
-};
-
-// the heaps' bounds and the 8-byte regions a plan begins with: xs [64][L + 1] at 0, the set's W [rows][L] and bias [rows], rs, cval.
-// Returns the offset behind them.
-static size_t mg_tree_carve_head(mg_tree_lds_shared &p, int Lmax, int ncmax, int n_cand, int max_children, int max_depth, int wrows) {
-    p.wrows = wrows;
-    p.n_cand = n_cand;
-    p.cap_local = std::max(max_children, 1);
-    p.cap_level = n_cand * std::min(n_cand, p.cap_local);
-    p.cap_res = n_cand * (max_depth + 1);
-    size_t o = (size_t)MG_TREE_CHUNK * (Lmax + 1) * 8;
-    p.off_w = o;    o += (size_t)wrows * (Lmax + 1) * 8;
-    p.off_rs = o;   o += (size_t)std::max(ncmax, 1) * MG_TREE_CHUNK * 8;
-    p.off_cval = o; o += MG_TREE_CHUNK * 8;
-    return o;
-}
-
-// the shared 4-byte regions (behind every 8-byte one): cid, clast, fr_n, fr_off
-static size_t mg_tree_carve_ints(mg_tree_lds_shared &p, size_t o) {
-    p.off_cid = o;   o += MG_TREE_CHUNK * 4;
-    p.off_clast = o; o += MG_TREE_CHUNK * 4;
-    p.off_frn = o;   o += (size_t)p.n_cand * 4;
-    p.off_froff = o; o += (size_t)(p.n_cand + 1) * 4;
-    return o;
-}
-
+// ---- the LDS regions (mg_tree_plan.h), and the routines on them, that both kernels have ----
 struct mg_tree_lds {
     double *xs, *rs, *cval;   // the scorer's: the chunk's rows, the residuals [constraint][lane], the values
     int32_t *cid;             // the chunk's rows of the points table
@@ -197,27 +167,112 @@ __device__ void mg_tree_score_chunk(const mg_score_args &a, const mg_tree_lds &s
     __syncthreads();
 }
 
-// ---- the FeatureClusterTree's search ----
-struct mg_tree_lds_plan {
-    mg_tree_lds_shared s;
-    size_t off_frv, off_lvv, off_lov, off_rev, off_lvn, off_lon, off_ren, bytes;
+// ---- root trajectory constraints behind the set (mg_cluster_tree_search_trajectories) ----
+struct mg_tree_traj_lds {
+    double *cp;           // the chunk's root coefficient rows [3 NB + 4][64], or NULL: formed from the latents at each tap
+    const double *poly;   // the search's polynomial tables staged one behind the other, or NULL: read from memory
+    int poly_stride;
+    double *tv;           // the terms [trajectory][lane]
 };
 
-static mg_tree_lds_plan mg_tree_plan(int Lmax, int ncmax, int n_cand, int max_children, int max_depth, int wrows) {
-    mg_tree_lds_plan p;
-    size_t o = mg_tree_carve_head(p.s, Lmax, ncmax, n_cand, max_children, max_depth, wrows);
-    p.off_frv = o; o += (size_t)n_cand * 8;
-    p.off_lvv = o; o += (size_t)p.s.cap_level * 8;
-    p.off_lov = o; o += (size_t)p.s.cap_local * 8;
-    p.off_rev = o; o += (size_t)p.s.cap_res * 8;
-    o = mg_tree_carve_ints(p.s, o);
-    p.off_lvn = o; o += (size_t)p.s.cap_level * 4;
-    p.off_lon = o; o += (size_t)p.s.cap_local * 4;
-    p.off_ren = o; o += (size_t)p.s.cap_res * 4;
-    p.bytes = (o + 15) & ~(size_t)15;
-    return p;
+// A workgroup's trajectory regions, the polynomial tables staged where the plan has room for them: every evaluation of the
+// closest-point search looks its segment up, a chain of dependent reads.  (The caller's first __syncthreads publishes them.)
+__device__ __forceinline__ mg_tree_traj_lds mg_tree_traj_lds_of(unsigned char *smem, const mg_tree_lds_shared &p, const mg_tree_traj_desc *__restrict__ tr, int tid) {
+    mg_tree_traj_lds t;
+    t.cp = p.cp_rows > 0 ? (double *)(smem + p.off_cp) : nullptr;
+    t.tv = (double *)(smem + p.off_tv);
+    t.poly = nullptr;
+    t.poly_stride = p.poly_doubles;
+    if (p.poly_doubles > 0) {
+        double *pl = (double *)(smem + p.off_poly);
+        for (int i = 0; i < tr->n; i++) {
+            const double *src = tr->t[i].poly;
+            const int m = tr->t[i].n_seg * 12 + 3;
+            for (int e = tid; e < m; e += MG_TREE_THREADS) pl[(size_t)i * p.poly_doubles + e] = src[e];
+        }
+        t.poly = pl;
+    }
+    return t;
 }
 
+// cval[j] += weight x the average distance of row j's root path from each of the search's trajectories, in list order: what
+// mg_score_trajectory(..., accumulate = 1) adds to mg_score_constraints' value, statement for statement (mg_trajectory.hip) --
+// the root's coefficient rows as fma chains over the row's latents from the means, four taps per channel and frame on the
+// canonical grid, the aligning transform from the first control point, the closest-point search of mg_traj_device.h with the
+// bound carried from frame to frame, the sum over the frames in frame order, one division.  A lane per row; the root rows (the
+// same for every trajectory: they are the primitive's) are formed once per chunk by all four waves, then wave i walks trajectory i.
+// Lanes without a row walk zeros in the monotone search (its wave-wide help wants every lane) and nothing in the reference's.
+// Called by every thread of the workgroup behind mg_tree_score_chunk, whose xs it reads.
+__device__ void mg_tree_score_chunk_trajectories(const mg_tree_traj_desc *__restrict__ tr, const mg_tree_lds &s, const mg_tree_traj_lds &t, int L, int cnt,
+                                                 int tid, int lane, int wave) {
+    const int xs_stride = L + 1, NB = tr->NB, T = tr->T, n = tr->n, align_mode = tr->align_mode;
+    const double *__restrict__ E = tr->E;
+    const double *__restrict__ mean = tr->mean;
+    const double *x = s.xs + lane * xs_stride;
+    auto row = [&](int r) { return mg_control_point(mean[r], E + (size_t)r * L, 1, L, [&](int k) { return x[k]; }); };
+    if (t.cp) {
+        const int rows = NB * 3 + 4;
+        for (int r = wave; r < rows; r += MG_TREE_WAVES) t.cp[r * MG_TREE_CHUNK + lane] = row(r);
+        __syncthreads();
+    }
+    for (int i = wave; i < n; i += MG_TREE_WAVES) {   // (uniform over the wave)
+        const double *poly = t.poly ? t.poly + (size_t)i * t.poly_stride : tr->t[i].poly;
+        const int n_seg = tr->t[i].n_seg, G = tr->t[i].G;
+        const double min_u0 = tr->t[i].min_u, weight = tr->t[i].weight;
+        auto root = [&](int r) { return t.cp ? t.cp[r * MG_TREE_CHUNK + lane] : row(r); };
+        const mg_align2d al = mg_traj_alignment_of(align_mode, tr->al, NB, nullptr, root);
+        auto position = [&](int f, double *q) {        // the row's root position in frame f, aligned
+            const int i0 = tr->i0[f];
+            const double *w = tr->w + 4 * (size_t)f;
+            if (t.cp) {
+#pragma unroll
+                for (int d = 0; d < 3; d++) q[d] = mg_taps4(w, t.cp + (i0 * 3 + d) * MG_TREE_CHUNK + lane, 3 * MG_TREE_CHUNK);
+            } else {
+#pragma unroll
+                for (int d = 0; d < 3; d++) {
+                    const double c[4] = {row(i0 * 3 + d), row((i0 + 1) * 3 + d), row((i0 + 2) * 3 + d), row((i0 + 3) * 3 + d)};
+                    q[d] = mg_taps4(w, c, 1);
+                }
+            }
+            if (align_mode != 0) mg_align_position(al, q[0], q[1], q[2]);
+        };
+        const bool valid = lane < cnt && s.cid[lane] >= 0;
+        double sum = 0.0;
+        if (tr->search == 0) {
+            mg_traj_chain(poly, n_seg, valid ? T : 0, min_u0, position, [&](int f, double dist, double u, int trips) { sum += dist; });
+        } else {
+            const double invG = 1.0 / (double)G;
+            double min_u = min_u0;
+            for (int f = 0; f < T; f++) {
+                double q[3];
+                position(f, q);
+                sum += mg_traj_closest_dist<true>(poly, n_seg, G, invG, &min_u, q);   // (every lane of the wave is here: the help is legal)
+            }
+        }
+        t.tv[i * MG_TREE_CHUNK + lane] = weight * (T > 0 ? sum / (double)T : 0.0);
+    }
+    __syncthreads();
+    if (tid < cnt) {
+        double err = s.cval[tid];
+        for (int i = 0; i < n; i++) err = err + t.tv[i * MG_TREE_CHUNK + tid];
+        s.cval[tid] = err;
+    }
+    __syncthreads();
+}
+
+// The chunk scorer of both kernels: the set's value, then (a launch with trajectories, TRAJ) the search's trajectory terms.  Without
+// TRAJ this is mg_tree_score_chunk alone: the kernels a call without trajectories always launched.
+template <bool TRAJ>
+__device__ __forceinline__ void mg_tree_score(const mg_tree_search_desc *__restrict__ d, const mg_score_args &a, const mg_tree_lds &s, const mg_tree_traj_lds &t,
+                                              const double *__restrict__ P, int dim, int cnt, int tid, int lane, int wave) {
+    mg_tree_score_chunk(a, s, P, dim, cnt, tid, lane, wave);
+    if constexpr (TRAJ) {
+        if (d->tr.n > 0) mg_tree_score_chunk_trajectories(&d->tr, s, t, a.L, cnt, tid, lane, wave);   // (uniform over the workgroup)
+    }
+}
+
+// ---- the FeatureClusterTree's search ----
+template <bool TRAJ>
 __global__ __launch_bounds__(MG_TREE_THREADS) void mg_tree_search_kernel(const mg_tree_search_desc *__restrict__ tab, mg_tree_lds_plan lp,
                                                                          mg_tree_search_record *__restrict__ rec) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -232,6 +287,8 @@ __global__ __launch_bounds__(MG_TREE_THREADS) void mg_tree_search_kernel(const m
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const mg_tree_lds s = mg_tree_lds_of(smem, lp.s, a, d->rows, tid);
+    mg_tree_traj_lds tl = {};
+    if constexpr (TRAJ) tl = mg_tree_traj_lds_of(smem, lp.s, &d->tr, tid);
     // (cid from the plan, not s.cid: read back out of the struct it costs the KD kernel two VGPRs)
     int32_t *cid = (int32_t *)(smem + lp.s.off_cid), *clast = (int32_t *)(smem + lp.s.off_clast);
     int32_t *fr_n = (int32_t *)(smem + lp.s.off_frn), *fr_off = (int32_t *)(smem + lp.s.off_froff);
@@ -280,7 +337,7 @@ __global__ __launch_bounds__(MG_TREE_THREADS) void mg_tree_search_kernel(const m
                 cid[tid] = ch[cb[fr_n[f]] + (e - fr_off[f])];
             }
             __syncthreads();
-            mg_tree_score_chunk(a, s, means, dim, cnt, tid, lane, wave);
+            mg_tree_score<TRAJ>(d, a, s, tl, means, dim, cnt, tid, lane, wave);
             if (tid == 0) {
                 for (int j = 0; j < cnt; j++) {
                     mg_heappush(lo, lo_len, lp.s.cap_local, mg_vn{s.cval[j], cid[j]}, lt, flags);   // _find_best_cluster_candidates
@@ -330,8 +387,6 @@ __global__ __launch_bounds__(MG_TREE_THREADS) void mg_tree_search_kernel(const m
 //   results             (value, c_idx, point list)
 //   a KD descent        (cost, depth)
 // ---------------------------------------------------------------------------------------------------------------
-#define MG_KD_GROUP 32
-
 struct mg_hent {   // a heap entry: value, then up to three ints (what each heap compares and carries)
     double v;
     int32_t a, b, c, pad;
@@ -341,6 +396,8 @@ struct mg_kent {   // a KD descent's (cost, depth)
     int32_t d, pad;
 };
 
+static_assert(sizeof(mg_hent) == MG_TREE_HENT_BYTES && sizeof(mg_kent) == MG_TREE_KENT_BYTES, "mg_kd_plan sizes the heaps by these");
+
 // Python's `list < list` of two rows of the points table: the first position whose items differ decides
 __device__ bool mg_kd_rows_lt(const double *__restrict__ P, int dim, int r, int s) {
     const double *x = P + (size_t)r * dim, *y = P + (size_t)s * dim;
@@ -349,35 +406,7 @@ __device__ bool mg_kd_rows_lt(const double *__restrict__ P, int dim, int r, int 
     return false;
 }
 
-struct mg_kd_lds_plan {
-    mg_tree_lds_shared s;
-    int cap_leaf, kcap, kd_depth;
-    size_t off_lo, off_lv, off_re, off_lf, off_kh, off_resv, off_kev, off_cci, off_dsoff, off_resrow, off_dfr, off_dlast, bytes;
-};
-
-static mg_kd_lds_plan mg_kd_plan(int Lmax, int ncmax, int n_cand, int max_children, int max_depth, int max_kd_children, int kd_depth, int wrows) {
-    mg_kd_lds_plan p;
-    p.cap_leaf = std::max(max_kd_children, 1);
-    p.kd_depth = kd_depth;
-    p.kcap = kd_depth + 1;
-    size_t o = mg_tree_carve_head(p.s, Lmax, ncmax, n_cand, max_children, max_depth, wrows);
-    p.off_lo = o;     o += (size_t)p.s.cap_local * sizeof(mg_hent);
-    p.off_lv = o;     o += (size_t)p.s.cap_level * sizeof(mg_hent);
-    p.off_re = o;     o += (size_t)p.s.cap_res * sizeof(mg_hent);
-    p.off_lf = o;     o += (size_t)p.cap_leaf * sizeof(mg_hent);
-    p.off_kh = o;     o += (size_t)MG_KD_GROUP * p.kcap * sizeof(mg_kent);
-    p.off_resv = o;   o += MG_KD_GROUP * 8;
-    p.off_kev = o;    o += (size_t)MG_KD_GROUP * p.kcap * 4;
-    o = mg_tree_carve_ints(p.s, o);
-    p.off_cci = o;    o += MG_TREE_CHUNK * 4;
-    p.off_dsoff = o;  o += (size_t)(n_cand + 1) * 4;
-    p.off_resrow = o; o += MG_KD_GROUP * 4;
-    p.off_dfr = o;    o += MG_KD_GROUP * 4;
-    p.off_dlast = o;  o += MG_KD_GROUP * 4;
-    p.bytes = (o + 15) & ~(size_t)15;
-    return p;
-}
-
+template <bool TRAJ>
 __global__ __launch_bounds__(MG_TREE_THREADS) void mg_kd_tree_search_kernel(const mg_tree_search_desc *__restrict__ tab, mg_kd_lds_plan lp,
                                                                             mg_tree_search_record *__restrict__ rec) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -398,6 +427,8 @@ __global__ __launch_bounds__(MG_TREE_THREADS) void mg_kd_tree_search_kernel(cons
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const mg_tree_lds s = mg_tree_lds_of(smem, lp.s, a, d->rows, tid);
+    mg_tree_traj_lds tl = {};
+    if constexpr (TRAJ) tl = mg_tree_traj_lds_of(smem, lp.s, &d->tr, tid);
     double *cval = s.cval;
     // (cid from the plan, not s.cid: read back out of the struct it costs the KD kernel two VGPRs)
     int32_t *cid = (int32_t *)(smem + lp.s.off_cid), *clast = (int32_t *)(smem + lp.s.off_clast);
@@ -475,7 +506,7 @@ __global__ __launch_bounds__(MG_TREE_THREADS) void mg_kd_tree_search_kernel(cons
                 cid[tid] = n_kd + ch[cb[fr_n[f]] + (e - fr_off[f])];
             }
             __syncthreads();
-            mg_tree_score_chunk(a, s, P, dim, cnt, tid, lane, wave);
+            mg_tree_score<TRAJ>(d, a, s, tl, P, dim, cnt, tid, lane, wave);
             if (tid == 0) {
                 for (int j = 0; j < cnt; j++) {
                     mg_hent x;
@@ -513,7 +544,7 @@ __global__ __launch_bounds__(MG_TREE_THREADS) void mg_kd_tree_search_kernel(cons
                 dfr[tid] = f;
             }
             __syncthreads();
-            mg_tree_score_chunk(a, s, P, dim, gcnt, tid, lane, wave);
+            mg_tree_score<TRAJ>(d, a, s, tl, P, dim, gcnt, tid, lane, wave);
             if (tid < gcnt) {   // the KD root's point (or the leaf's mean) at depth 0
                 mg_kent x;
                 x.v = cval[tid]; x.d = 0; x.pad = 0;
@@ -529,7 +560,7 @@ __global__ __launch_bounds__(MG_TREE_THREADS) void mg_kd_tree_search_kernel(cons
                     cid[2 * tid + 1] = active ? kl[cur] : -1;
                 }
                 if (!__syncthreads_or(active)) break;
-                mg_tree_score_chunk(a, s, P, dim, MG_TREE_CHUNK, tid, lane, wave);
+                mg_tree_score<TRAJ>(d, a, s, tl, P, dim, MG_TREE_CHUNK, tid, lane, wave);
                 if (active) {   // _decide_direction_objective: left only if l < r
                     const int r = cid[2 * tid], l = cid[2 * tid + 1];
                     double cost = INFINITY;
@@ -796,18 +827,18 @@ extern "C" void mg_cluster_tree_destroy(mg_cluster_tree *tree) {
 struct mg_tree_maxima {
     int L = 1, nc = 1, children = 1, depth = 0, kd_children = 1, kd_depth = 0, wrows = 0;
     bool rows_known = true;
+    int traj = 0, cp_rows = 0, poly_doubles = 0;   // the longest trajectory list, the most root rows and the longest polynomial table
 };
 
-// One launch for the table's searches.  plan(wrows): the kernel's LDS plan with that many rows of W staged; a plan beyond the
-// workgroup's LDS is tried again with W read from memory.
+// One launch for the table's searches.  plan(staging): the kernel's LDS plan with those tables staged; a plan beyond the
+// workgroup's LDS is tried again with one more of them read from memory (mg_tree_plan_fit).
 template <class PlanFn, class Kernel>
 static int mg_tree_launch(mg_context *ctx, const std::vector<mg_tree_search_desc> &tab, const mg_tree_maxima &m, int n_candidates, PlanFn plan, Kernel kernel,
                           mg_tree_search_record *records_dev) {
-    auto lp = plan(m.rows_known ? m.wrows : 0);
-    if (lp.bytes > MG_TREE_LDS_MAX && lp.s.wrows > 0) lp = plan(0);
+    const auto lp = mg_tree_plan_fit(mg_tree_staging{m.rows_known ? m.wrows : 0, m.cp_rows, m.poly_doubles}, m.traj, plan);
     if (lp.bytes > MG_TREE_LDS_MAX) {
-        mg_set_error("mg_cluster_tree_search: %zu bytes of LDS (latents %d, constraints %d, candidates %d, children %d, depth %d, KD depth %d) beyond 160 KiB",
-                     lp.bytes, m.L, m.nc, n_candidates, m.children, m.depth, m.kd_depth);
+        mg_set_error("mg_cluster_tree_search: %zu bytes of LDS (latents %d, constraints %d, candidates %d, children %d, depth %d, KD depth %d, trajectories %d) "
+                     "beyond 160 KiB", lp.bytes, m.L, m.nc, n_candidates, m.children, m.depth, m.kd_depth, m.traj);
         return MG_ERR_UNSUPPORTED;
     }
     MG_HIP_CHECK(hipSetDevice(ctx->device));
@@ -823,8 +854,10 @@ static int mg_tree_launch(mg_context *ctx, const std::vector<mg_tree_search_desc
     return MG_OK;
 }
 
-extern "C" int mg_cluster_tree_search(int32_t n_searches, mg_primitive *const *prims, mg_cluster_tree *const *trees,
-                                      const mg_constraint_set *const *csets, int32_t n_candidates, mg_tree_search_record *records_dev) {
+// Both entry points (the messages name the family): trajectory_counts NULL is the call without trajectories.
+static int mg_tree_search(int32_t n_searches, mg_primitive *const *prims, mg_cluster_tree *const *trees, const mg_constraint_set *const *csets,
+                          const int32_t *trajectory_counts, const mg_trajectory *const *trajectories, const double *min_u, const double *weights,
+                          const mg_alignment_desc *const *alignments, int32_t n_candidates, mg_tree_search_record *records_dev) {
     MG_TREE_REQUIRE(n_searches >= 0, "mg_cluster_tree_search: n_searches = %d", n_searches);
     if (n_searches == 0) return MG_OK;
     MG_TREE_REQUIRE(prims && trees && csets && records_dev, "mg_cluster_tree_search: NULL argument");
@@ -838,6 +871,9 @@ extern "C" int mg_cluster_tree_search(int32_t n_searches, mg_primitive *const *p
                         "mg_cluster_tree_search: search %d: a %s tree in a call of %s trees (one kind per call)", s,
                         trees[s]->kind ? "KD" : "feature", kind ? "KD" : "feature");
     mg_context *ctx = prims[0]->ctx;
+    std::vector<int64_t> toff;
+    { const int rc = mg_tree_traj_offsets("mg_cluster_tree_search", n_searches, trajectory_counts, toff); if (rc != MG_OK) return rc; }
+    MG_TREE_REQUIRE(toff[n_searches] == 0 || (trajectories && min_u && weights), "mg_cluster_tree_search: NULL trajectory, min_u or weight array");
     std::vector<mg_tree_search_desc> tab(n_searches);
     mg_tree_maxima m;
     for (int32_t s = 0; s < n_searches; s++) {
@@ -864,17 +900,52 @@ extern "C" int mg_cluster_tree_search(int32_t n_searches, mg_primitive *const *p
         m.depth = std::max(m.depth, (int)t->depth);
         m.kd_children = std::max(m.kd_children, (int)t->max_kd_children);
         m.kd_depth = std::max(m.kd_depth, (int)t->kd_depth);
+        // the search's trajectories: every one made for this primitive (its root rows are the primitive's), scored on the canonical grid
+        const int32_t count = (int32_t)(toff[s + 1] - toff[s]);
+        if (count == 0) continue;
+        mg_tree_traj_in in[MG_TREE_MAX_TRAJECTORIES];
+        for (int32_t i = 0; i < count; i++) {
+            const mg_trajectory *tj = trajectories[toff[s] + i];
+            MG_TREE_REQUIRE(tj != nullptr, "mg_cluster_tree_search: search %d: trajectory %d is NULL", s, i);
+            MG_TREE_REQUIRE(tj->prim == p, "mg_cluster_tree_search: search %d: trajectory %d was made for another primitive or context", s, i);
+            in[i] = mg_tree_traj_in{tj->d_poly, tj->n_seg, tj->granularity};
+            m.poly_doubles = std::max(m.poly_doubles, (int)tj->n_seg * 12 + 3);
+        }
+        const int rc = mg_tree_traj_fill("mg_cluster_tree_search", s, count, in, min_u + toff[s], weights + toff[s], alignments ? alignments[s] : nullptr, &d.tr);
+        if (rc != MG_OK) return rc;
+        const mg_trajectory *t0 = trajectories[toff[s]];
+        const mg_time_grid *g = p->canonical;
+        d.tr.E = t0->d_E; d.tr.mean = t0->d_mean; d.tr.i0 = g->d_i0; d.tr.w = g->d_w;
+        d.tr.T = g->T; d.tr.NB = p->NB; d.tr.search = ctx->opt[MG_OPT_TRAJECTORY_SEARCH] == 1 ? 1 : 0;
+        m.traj = std::max(m.traj, (int)count);
+        m.cp_rows = std::max(m.cp_rows, (int)t0->rows);
     }
-    if (kind == 1)
-        return mg_tree_launch(ctx, tab, m, n_candidates,
-                              [&](int w) { return mg_kd_plan(m.L, m.nc, n_candidates, m.children, m.depth, m.kd_children, m.kd_depth, w); },
-                              mg_kd_tree_search_kernel, records_dev);
-    return mg_tree_launch(ctx, tab, m, n_candidates, [&](int w) { return mg_tree_plan(m.L, m.nc, n_candidates, m.children, m.depth, w); },
-                          mg_tree_search_kernel, records_dev);
+    // (a call without trajectories launches the kernels it always did, with the plan it always had)
+    if (kind == 1) {
+        auto plan = [&](const mg_tree_staging &st) { return mg_kd_plan(m.L, m.nc, n_candidates, m.children, m.depth, m.kd_children, m.kd_depth, m.traj, st); };
+        if (m.traj > 0) return mg_tree_launch(ctx, tab, m, n_candidates, plan, mg_kd_tree_search_kernel<true>, records_dev);
+        return mg_tree_launch(ctx, tab, m, n_candidates, plan, mg_kd_tree_search_kernel<false>, records_dev);
+    }
+    auto plan = [&](const mg_tree_staging &st) { return mg_tree_plan(m.L, m.nc, n_candidates, m.children, m.depth, m.traj, st); };
+    if (m.traj > 0) return mg_tree_launch(ctx, tab, m, n_candidates, plan, mg_tree_search_kernel<true>, records_dev);
+    return mg_tree_launch(ctx, tab, m, n_candidates, plan, mg_tree_search_kernel<false>, records_dev);
 }
 
-extern "C" int mg_cluster_tree_search_host(int32_t n_searches, mg_primitive *const *prims, mg_cluster_tree *const *trees,
-                                           const mg_constraint_set *const *csets, int32_t n_candidates, mg_tree_search_record *records) {
+extern "C" int mg_cluster_tree_search(int32_t n_searches, mg_primitive *const *prims, mg_cluster_tree *const *trees,
+                                      const mg_constraint_set *const *csets, int32_t n_candidates, mg_tree_search_record *records_dev) {
+    return mg_tree_search(n_searches, prims, trees, csets, nullptr, nullptr, nullptr, nullptr, nullptr, n_candidates, records_dev);
+}
+
+extern "C" int mg_cluster_tree_search_trajectories(int32_t n_searches, mg_primitive *const *prims, mg_cluster_tree *const *trees,
+                                                   const mg_constraint_set *const *csets, const int32_t *trajectory_counts,
+                                                   const mg_trajectory *const *trajectories, const double *min_u, const double *weights,
+                                                   const mg_alignment_desc *const *alignments, int32_t n_candidates, mg_tree_search_record *records_dev) {
+    return mg_tree_search(n_searches, prims, trees, csets, trajectory_counts, trajectories, min_u, weights, alignments, n_candidates, records_dev);
+}
+
+// the records read back: the launch, one copy, one wait
+template <class Search>
+static int mg_tree_search_to_host(int32_t n_searches, mg_primitive *const *prims, mg_tree_search_record *records, Search search) {
     MG_TREE_REQUIRE(n_searches >= 0 && (n_searches == 0 || (records && prims && prims[0])), "mg_cluster_tree_search_host: bad arguments");
     if (n_searches == 0) return MG_OK;
     mg_context *ctx = prims[0]->ctx;
@@ -882,9 +953,26 @@ extern "C" int mg_cluster_tree_search_host(int32_t n_searches, mg_primitive *con
     void *d_rec = nullptr;
     int rc = mg_ctx_scratch(ctx, bytes, &d_rec);
     if (rc != MG_OK) return rc;
-    rc = mg_cluster_tree_search(n_searches, prims, trees, csets, n_candidates, (mg_tree_search_record *)d_rec);
+    rc = search((mg_tree_search_record *)d_rec);
     if (rc != MG_OK) return rc;
     MG_HIP_CHECK(hipMemcpyAsync(records, d_rec, (size_t)bytes, hipMemcpyDeviceToHost, ctx->stream));
     MG_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     return MG_OK;
+}
+
+extern "C" int mg_cluster_tree_search_host(int32_t n_searches, mg_primitive *const *prims, mg_cluster_tree *const *trees,
+                                           const mg_constraint_set *const *csets, int32_t n_candidates, mg_tree_search_record *records) {
+    return mg_tree_search_to_host(n_searches, prims, records, [&](mg_tree_search_record *d_rec) {
+        return mg_cluster_tree_search(n_searches, prims, trees, csets, n_candidates, d_rec);
+    });
+}
+
+extern "C" int mg_cluster_tree_search_trajectories_host(int32_t n_searches, mg_primitive *const *prims, mg_cluster_tree *const *trees,
+                                                        const mg_constraint_set *const *csets, const int32_t *trajectory_counts,
+                                                        const mg_trajectory *const *trajectories, const double *min_u, const double *weights,
+                                                        const mg_alignment_desc *const *alignments, int32_t n_candidates, mg_tree_search_record *records) {
+    return mg_tree_search_to_host(n_searches, prims, records, [&](mg_tree_search_record *d_rec) {
+        return mg_cluster_tree_search_trajectories(n_searches, prims, trees, csets, trajectory_counts, trajectories, min_u, weights, alignments, n_candidates,
+                                                   d_rec);
+    });
 }

@@ -142,6 +142,25 @@ __device__ __forceinline__ mg_align2d mg_candidate_alignment(const mg_score_args
     return mg_align2d_from(pc[1], pc[2], bx, bz, pc[3], pc[4], channel(r0), channel(r0 + 2));
 }
 
+// The candidate's transform in the trajectory scorers, the root as aligning node: rotation about y and an xz translation, from the
+// first control point's rows -- root(r) yields row r of the candidate's root coefficient rows (NB x 3 positions, then the first control
+// point's quaternion).  mode 0: none, 1: previous frame, 2: start pose; al: the record as mg_traj_align_record normalises it.  The
+// root's chain is its one quaternion: normalised and used as it is (multiplying it into the identity, the general chain's first step,
+// can flip the sign of a zero component).  prev: NULL, or the candidate's OWN previous unit heading (x, z) and root position (x, z) in
+// place of al[0..3] (mode 1 only; the reference vector stays the record's).
+template <typename RootFn>
+__device__ __forceinline__ mg_align2d mg_traj_alignment_of(int mode, const double *al, int NB, const double *prev, RootFn root) {
+    if (mode == 0) return {1.0, 0.0, 0.0, 0.0, 0.0};
+    const double p0x = root(0), p0z = root(2);   // (formed once: root() may be a whole fma chain)
+    if (mode == 2) return mg_align2d_onto(al[0], al[1], al[2], al[3], p0x, p0z, al[4]);
+    double q[4] = {root(NB * 3 + 0), root(NB * 3 + 1), root(NB * 3 + 2), root(NB * 3 + 3)}, bx, bz;
+    mg_quat_normalise(q[0], q[1], q[2], q[3]);
+    mg_heading_xz(q, al[4], al[5], al[6], bx, bz);
+    double hx = al[0], hz = al[1], px = al[2], pz = al[3];
+    if (prev) { hx = prev[0]; hz = prev[1]; px = prev[2]; pz = prev[3]; }
+    return mg_align2d_from(hx, hz, bx, bz, px, pz, p0x, p0z);
+}
+
 // ROOT_ONLY: the set holds root position / 2-D direction constraints only (the caller has checked): the other kinds' code -- and
 // the registers their forward-kinematics chains want -- stay out of a kernel that has none to spare (the optimiser's objective
 // inside the LDS-resident mixture kernel, four waves per SIMD).  The two kinds compiled in are the same statements: the same bits.

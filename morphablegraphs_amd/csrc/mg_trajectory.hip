@@ -25,6 +25,7 @@
 #include "mg_score_device.h"
 #include "mg_spline_device.h"
 #include "mg_traj_device.h"
+#include "mg_tree_plan.h"
 
 struct mg_traj_args {
     const double *poly, *E, *mean;
@@ -49,26 +50,13 @@ struct mg_traj_args {
 
 #define MG_TRAJ_BLOCK 64
 
-// The candidate's aligning transform (mg_candidate_alignment's for the root node): rotation about y and an xz translation, from the
-// first control point's rows -- root(r) yields row r of the candidate's root coefficient rows (NB x 3 positions, then the first control
-// point's quaternion).  The root's chain is its one quaternion: normalised and used as it is (multiplying it into the identity, the
-// general chain's first step, can flip the sign of a zero component).  cand: the candidate's index in the batch, clamped to it by the
-// caller (a lane past the batch reads the last candidate's record and writes nothing) -- where every candidate has its own previous
-// heading and position (al_cand) they are read from its row, used as they are; the reference vector stays the record's.
+// The candidate's aligning transform (mg_score_device.h: mg_traj_alignment_of, which the one-launch tree search calls as well).
+// cand: the candidate's index in the batch, clamped to it by the caller (a lane past the batch reads the last candidate's record and
+// writes nothing) -- where every candidate has its own previous heading and position (al_cand) they are read from its row, used as
+// they are.
 template <typename RootFn>
 __device__ __forceinline__ mg_align2d mg_traj_alignment(const mg_traj_args &a, const int64_t cand, RootFn root) {
-    if (a.align_mode == 0) return {1.0, 0.0, 0.0, 0.0, 0.0};
-    const double p0x = root(0), p0z = root(2);   // (formed once: root() may be a whole fma chain)
-    if (a.align_mode == 2) return mg_align2d_onto(a.al[0], a.al[1], a.al[2], a.al[3], p0x, p0z, a.al[4]);
-    double q[4] = {root(a.NB * 3 + 0), root(a.NB * 3 + 1), root(a.NB * 3 + 2), root(a.NB * 3 + 3)}, bx, bz;
-    mg_quat_normalise(q[0], q[1], q[2], q[3]);
-    mg_heading_xz(q, a.al[4], a.al[5], a.al[6], bx, bz);
-    double hx = a.al[0], hz = a.al[1], px = a.al[2], pz = a.al[3];
-    if (a.al_cand) {                                   // (uniform: a kernel argument)
-        const double *prev = a.al_cand + 4 * cand;
-        hx = prev[0]; hz = prev[1]; px = prev[2]; pz = prev[3];
-    }
-    return mg_align2d_from(hx, hz, bx, bz, px, pz, p0x, p0z);
+    return mg_traj_alignment_of(a.align_mode, a.al, a.NB, a.al_cand ? a.al_cand + 4 * cand : nullptr, root);   // (al_cand: uniform, a kernel argument)
 }
 
 // POLY_LDS: the target spline's segment polynomials (12 n_seg + 3 doubles) are copied behind the rows and searched from there -- the walk
@@ -620,20 +608,8 @@ static int mg_traj_fill_args(const char *who, mg_primitive *p, const mg_trajecto
     a.B = B; a.ld = ld; a.T = g->T; a.L = p->L; a.NB = p->NB; a.n_seg = t->n_seg; a.G = t->granularity; a.lat_f64 = dt == MG_F64 ? 1 : 0;
     a.accumulate = accumulate ? 1 : 0; a.min_u = min_u; a.weight = weight; a.points = nullptr; a.res_u = nullptr; a.res_n = nullptr; a.paths = nullptr;
     a.search = p->ctx->opt[MG_OPT_TRAJECTORY_SEARCH] == 1 ? 1 : 0;
-    a.align_mode = 0; a.al_cand = nullptr;
-    for (double &v : a.al) v = 0.0;
-    if (al) {
-        const double hn = std::sqrt(al->heading[0] * al->heading[0] + al->heading[1] * al->heading[1]);
-        if (!(hn > 0.0) || !std::isfinite(hn)) { mg_set_error("%s: heading is zero or not finite", who); return MG_ERR_INVALID_ARGUMENT; }
-        if (al->joint != 0 && al->joint != MG_ALIGN_START_POSE) {
-            mg_set_error("%s: only the root joint or a start pose can be the aligning reference here (joint %d)", who, al->joint);
-            return MG_ERR_UNSUPPORTED;
-        }
-        a.align_mode = al->joint == MG_ALIGN_START_POSE ? 2 : 1;
-        a.al[0] = al->heading[0] / hn; a.al[1] = al->heading[1] / hn; a.al[2] = al->position[0]; a.al[3] = al->position[2];
-        if (a.align_mode == 2) a.al[4] = al->position[1];
-        else { a.al[4] = al->ref_dir[0]; a.al[5] = al->ref_dir[1]; a.al[6] = al->ref_dir[2]; }
-    }
+    a.al_cand = nullptr;
+    { const int rc = mg_traj_align_record(who, al, &a.align_mode, a.al); if (rc != MG_OK) return rc; }   // (mg_tree_plan.h)
     *out = a;
     return MG_OK;
 }

@@ -317,13 +317,14 @@ class HipMotionPrimitiveGenerator(object):
         once per visited mean or sample.  At GPU batch sizes the whole tree is cheaper to score than to descend:
         every stored sample in one launch, first minimum -- the result of find_best_example_exhaustive.
         With algorithm_config["cluster_tree_search_method"] = "descend" the reference's descent instead (its sample and
-        min_error): one launch when the constraints make a device set, else the host-driven descent that scores each level's
-        children in one batched call."""
+        min_error): one launch when the constraints make a device search set (keyframe constraints and the action's root
+        trajectory constraints), else the host-driven descent that scores each level's children in one batched call."""
         if self.cluster_tree_search_method == "descend":
             n = self.n_cluster_search_candidates if n_candidates < 1 else n_candidates
             skeleton = getattr(constraints, "hip_skeleton", None)
-            if graph_node._tree_search_set(constraints, prev_frames, skeleton) is not None:
-                distance, s = graph_node.search_best_sample_on_device(constraints, n, prev_frames, skeleton)
+            search_set = graph_node._tree_search_set(constraints, prev_frames, skeleton)
+            if search_set is not None:     # (released by the search)
+                distance, s = graph_node.search_best_sample_on_device(constraints, n, prev_frames, skeleton, search_set=search_set)
             else:
                 distance, s = graph_node.search_best_sample_batched(constraints, n, prev_frames, skeleton)
             constraints.min_error = distance

@@ -13,7 +13,7 @@ from . import candidate_scoring as _cs
 
 from . import _capi
 from .candidate_scoring import constraints_to_device_form, evaluate_samples_using_constraints
-from .cluster_tree import HipFeatureClusterTree, search_on_device
+from .cluster_tree import HipFeatureClusterTree, TreeSearchSet, search_on_device
 from .kd_cluster_tree import HipClusterTree
 
 _SEARCH_TREES = (HipFeatureClusterTree, HipClusterTree)   # the trees a search descends (the others hold samples only)
@@ -135,31 +135,56 @@ class HipMotionStateGraphNode(HipMotionPrimitiveModelWrapper):
         return np.inf, None
 
     def _tree_search_set(self, constraints, prev_frames=None, skeleton=None):
-        """The device constraint set a one-launch tree search scores against, or None when the constraints hold anything
-        mg_score_constraints does not take (trajectories, per-frame constraints)."""
-        from .candidate_scoring import alignment_from_prev_frames, cached_constraint_set
+        """What a one-launch tree search scores against (cluster_tree.TreeSearchSet: the device keyframe set, the root
+        trajectory constraints as pinned device trajectories, the alignment), or None when the launch does not cover the
+        constraints: per-frame constraints, more than MG_TREE_MAX_TRAJECTORIES trajectories, trajectories aligned to another
+        joint than the root.  The caller release()s the set after its call."""
+        from .candidate_scoring import alignment_from_prev_frames, cached_constraint_set, cached_trajectory, split_trajectories
         from .frame_constraints import is_frame_constraint
         clist = constraints.constraints if hasattr(constraints, "constraints") else constraints
         skeleton = skeleton if skeleton is not None else getattr(constraints, "hip_skeleton", None)
         form = constraints_to_device_form(clist)
-        if any(is_frame_constraint(c) or c.get("type") == "trajectory" for c in form):
+        if any(is_frame_constraint(c) for c in form):
             return None
-        return cached_constraint_set(self.motion_primitive._prim, form, skeleton, alignment_from_prev_frames(prev_frames, constraints, skeleton))
+        keyframes, trajectories = split_trajectories(form)
+        if len(trajectories) > _capi.MG_TREE_MAX_TRAJECTORIES:
+            return None
+        alignment = alignment_from_prev_frames(prev_frames, constraints, skeleton)
+        if trajectories and alignment is not None and alignment.get("joint", 0) not in (0, _capi.MG_ALIGN_START_POSE):
+            return None
+        prim = self.motion_primitive._prim
+        cset = cached_constraint_set(prim, keyframes, skeleton, alignment)
+        sset = TreeSearchSet(cset, alignment=alignment)
+        try:
+            for c in trajectories:
+                sset.trajectories.append((cached_trajectory(prim, c, pin=True), c.get("min_u", 0.0), c.get("weight", 1.0)))
+        except Exception:
+            sset.release()
+            raise
+        return sset
 
     def _search_tree(self):
         if not isinstance(self.cluster_tree, _SEARCH_TREES):
             raise NotImplementedError("node %r has no cluster tree to descend (only stored samples)" % (self.name,))
         return self.cluster_tree
 
-    def search_best_sample_on_device(self, constraints, n_candidates, prev_frames=None, skeleton=None):
+    def search_best_sample_on_device(self, constraints, n_candidates, prev_frames=None, skeleton=None, search_set=None):
         """search_best_sample with the reference's objective (the constraints' summed weighted errors, aligned to prev_frames
-        outside local mode) as ONE launch (mg_cluster_tree_search): (error, sample).  Adds the objectives scored to
-        constraints.evaluations."""
-        tree = self._search_tree()
-        cset = self._tree_search_set(constraints, prev_frames, skeleton)
-        if cset is None:
-            raise NotImplementedError("the one-launch tree search scores keyframe constraints only")
-        rec = search_on_device([(tree, self.motion_primitive._prim, cset)], n_candidates)[0]
+        outside local mode) as ONE launch (mg_cluster_tree_search[_trajectories]): (error, sample).  Adds the objectives scored
+        to constraints.evaluations.  search_set: what _tree_search_set returned for these arguments, where the caller has asked
+        already; it is released here either way."""
+        sset = search_set
+        try:
+            tree = self._search_tree()
+            if sset is None:
+                sset = self._tree_search_set(constraints, prev_frames, skeleton)
+            if sset is None:
+                raise NotImplementedError("the one-launch tree search scores keyframe constraints and up to %d root trajectories"
+                                          % _capi.MG_TREE_MAX_TRAJECTORIES)
+            rec = search_on_device([(tree, self.motion_primitive._prim, sset)], n_candidates)[0]
+        finally:
+            if sset is not None:
+                sset.release()
         if hasattr(constraints, "evaluations"):
             constraints.evaluations += int(rec["evaluations"])
         return tree.result_of_record(rec)
@@ -347,28 +372,32 @@ class HipMotionStateGraph(object):
         _evaluate_option does (:205-207), ALL of them in one launch; the other options draw n_samples candidates, score them and
         keep the first minimum.  Returns (best_option, {option: (best_sample, min_error)})."""
         results, searches, general = {}, [], []
-        for key in options:
-            node = self.nodes[key]
-            cons = constraints_per_option[key]
-            if use_cluster_trees and isinstance(node.cluster_tree, _SEARCH_TREES):
-                cset = node._tree_search_set(cons, prev_frames, skeleton)
-                if cset is not None:
-                    searches.append((key, (node.cluster_tree, node.motion_primitive._prim, cset)))
-                    continue
-                results[key] = node.search_best_sample_batched(cons, 1, prev_frames, skeleton)[::-1]
-                continue
-            general.append(key)
-        for kind in _SEARCH_TREES:   # one launch per tree kind
-            group = [s for s in searches if isinstance(s[1][0], kind)]
-            if not group:
-                continue
-            records = search_on_device([s for _, s in group], 1)
-            for (key, (tree, _, _)), rec in zip(group, records):
+        try:
+            for key in options:
+                node = self.nodes[key]
                 cons = constraints_per_option[key]
-                if hasattr(cons, "evaluations"):
-                    cons.evaluations += int(rec["evaluations"])
-                err, row = tree.result_of_record(rec)
-                results[key] = (row, err)
+                if use_cluster_trees and isinstance(node.cluster_tree, _SEARCH_TREES):
+                    sset = node._tree_search_set(cons, prev_frames, skeleton)
+                    if sset is not None:
+                        searches.append((key, (node.cluster_tree, node.motion_primitive._prim, sset)))
+                        continue
+                    results[key] = node.search_best_sample_batched(cons, 1, prev_frames, skeleton)[::-1]
+                    continue
+                general.append(key)
+            for kind in _SEARCH_TREES:   # one launch per tree kind, trajectory constraints included
+                group = [s for s in searches if isinstance(s[1][0], kind)]
+                if not group:
+                    continue
+                records = search_on_device([s for _, s in group], 1)
+                for (key, (tree, _, _)), rec in zip(group, records):
+                    cons = constraints_per_option[key]
+                    if hasattr(cons, "evaluations"):
+                        cons.evaluations += int(rec["evaluations"])
+                    err, row = tree.result_of_record(rec)
+                    results[key] = (row, err)
+        finally:
+            for _, (_, _, sset) in searches:
+                sset.release()
         for key in general:
             node = self.nodes[key]
             if rng_seed is not None:

@@ -910,6 +910,22 @@ int mg_cluster_tree_search_trajectories(int32_t n_searches, mg_primitive *const 
                                         const mg_trajectory *const *trajectories, const double *min_u, const double *weights,
                                         const mg_alignment_desc *const *alignments, int32_t n_candidates, mg_tree_search_record *records_dev);
 
+/* What that launch would stage in LDS, readable without a launch: the same validation and the same maxima over the call's searches
+ * (latents, constraints, rows of W, root rows 3 NB + 4, polynomial doubles 12 n_seg + 3, trajectory slots, the trees' widths and
+ * depths), then the ladder a plan beyond the workgroup's LDS is retried by (W read from memory, then the polynomials, then the
+ * root rows).  lds_bytes: the plan's dynamic LDS; w_rows / root_rows / poly_doubles: what is staged (0: read from memory, or
+ * nothing to stage); trajectory_slots: the longest trajectory list; lds_opt_in: the plan needs more than 64 KiB; refused: no rung
+ * fits and the search returns MG_ERR_UNSUPPORTED (the query itself returns MG_OK and the bare plan's size).  The arguments of
+ * mg_cluster_tree_search_trajectories without the records; errors as there.  Launches nothing, uploads nothing. */
+typedef struct mg_tree_search_plan_info {
+    int64_t lds_bytes;
+    int32_t w_rows, root_rows, poly_doubles, trajectory_slots, lds_opt_in, refused;
+} mg_tree_search_plan_info;
+int mg_cluster_tree_search_plan(int32_t n_searches, mg_primitive *const *prims, mg_cluster_tree *const *trees,
+                                const mg_constraint_set *const *csets, const int32_t *trajectory_counts,
+                                const mg_trajectory *const *trajectories, const double *min_u, const double *weights,
+                                const mg_alignment_desc *const *alignments, int32_t n_candidates, mg_tree_search_plan_info *out);
+
 /* ---- k-means / KD cluster tree (reference space_partitioning/cluster_tree.py:117-149, cluster_tree_node.py:63-138,
  * kdtree.py:132-164,233-250) ----
  * The ClusterTree of a pickled model, flattened on the host.  Cluster nodes breadth first (node 0 the root): their

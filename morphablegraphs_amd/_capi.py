@@ -107,7 +107,7 @@ EXPORTED_SYMBOLS = [
     "mg_align_frames", "mg_frame_constraint_width", "mg_score_frame_constraint", "mg_score_frame_constraints", "mg_options_frame_lists", "mg_track_plan_create", "mg_track_plan_destroy", "mg_joint_tracks",
     "mg_score_constraint_residuals_chained", "mg_score_plan", "mg_option_step", "mg_options_step", "mg_options_step_device_counts", "mg_option_step_rows", "mg_options_step_rows", "mg_gmm_sample_rows", "mg_dist_broadcast",
     "mg_cluster_tree_create", "mg_cluster_tree_destroy", "mg_cluster_tree_search", "mg_cluster_tree_search_host",
-    "mg_cluster_tree_search_trajectories", "mg_cluster_tree_search_trajectories_host",
+    "mg_cluster_tree_search_trajectories", "mg_cluster_tree_search_trajectories_host", "mg_cluster_tree_search_plan",
     "mg_cluster_tree_create_kd", "mg_kmeans_segments", "mg_gmm_em_fit",
     "mg_spline_fit_batch", "mg_pca_fit", "mg_pca_project", "mg_pca_backproject",
     "mg_dtw_distance_grids", "mg_dtw_paths", "mg_warp_motions", "mg_dtw_pair_costs",
@@ -186,6 +186,11 @@ class TrajectoryPlanInfo(C.Structure):   # struct mg_trajectory_plan_info
 class ScorePlanInfo(C.Structure):   # struct mg_score_plan_info
     _fields_ = [("kernel", C.c_int32), ("lds_opt_in", C.c_int32), ("rows", C.c_int32), ("row_tiles", C.c_int32), ("lds_bytes", C.c_int64),
                 ("workgroups", C.c_int64)]
+
+
+class TreeSearchPlanInfo(C.Structure):   # struct mg_tree_search_plan_info
+    _fields_ = [("lds_bytes", C.c_int64), ("w_rows", C.c_int32), ("root_rows", C.c_int32), ("poly_doubles", C.c_int32),
+                ("trajectory_slots", C.c_int32), ("lds_opt_in", C.c_int32), ("refused", C.c_int32)]
 
 
 MG_SCORE_KERNELS = ("valu", "tile", "wide")   # MG_SCORE_KERNEL_*
@@ -411,6 +416,7 @@ def load_library(path=None):
         "mg_cluster_tree_search_host": [i32, vp, vp, vp, i32, vp],
         "mg_cluster_tree_search_trajectories": [i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp],
         "mg_cluster_tree_search_trajectories_host": [i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp],
+        "mg_cluster_tree_search_plan": [i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp],
         "mg_kmeans_segments": [vp, vp, i64, i32, i32, vp, vp, i32, i32, vp, vp, u64, i32, dbl, vp, vp, vp, vp],
         "mg_gmm_em_fit": [vp, vp, i64, i32, i32, vp, vp, dbl, dbl, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp],
         "mg_spline_fit_batch": [vp, vp, i64, i32, i32, vp, i32, vp],
@@ -1467,13 +1473,8 @@ class KdClusterTree(ClusterTree):
         self.n_kd = n_kd
 
 
-def search_cluster_trees(prims, trees, csets, n_candidates, records_dev=None, trajectories=None, alignments=None):
-    """mg_cluster_tree_search for len(prims) (Primitive, ClusterTree, ConstraintSet) triples of one context: ONE launch.
-    Returns the records (TREE_SEARCH_RECORD array), read back in one copy; with records_dev (a DeviceBuffer of
-    len(prims) * 32 bytes) the records stay there and nothing is returned.
-    trajectories: per search a list of (Trajectory | None, min_u, weight), the root trajectory constraints scored behind the
-    set in list order (mg_cluster_tree_search_trajectories, the same one launch); alignments: per search the alignment dict
-    the trajectories are scored under (None: local coordinates), as score_trajectory_dev takes it."""
+def _tree_search_handles(prims, trees, csets):
+    """The handle arrays of len(prims) (Primitive, ClusterTree, ConstraintSet) triples."""
     m = len(prims)
     if not (len(trees) == m and len(csets) == m):
         raise ValueError("prims, trees and csets must have one entry per search")
@@ -1481,18 +1482,38 @@ def search_cluster_trees(prims, trees, csets, n_candidates, records_dev=None, tr
     hp = (vp * max(m, 1))(*[p.handle.value for p in prims])
     ht = (vp * max(m, 1))(*[t.handle.value if t.handle else None for t in trees])
     hc = (vp * max(m, 1))(*[c.handle.value if c.handle else None for c in csets])
+    return m, hp, ht, hc
+
+
+def _tree_search_trajectories(m, trajectories, alignments):
+    """The flat trajectory arrays of mg_cluster_tree_search_trajectories: (counts, handles, min_u, weights, alignment pointers, the
+    alignment records they point to -- keep them until the call has returned)."""
+    vp = C.c_void_p
+    if len(trajectories) != m or (alignments is not None and len(alignments) != m):
+        raise ValueError("trajectories and alignments must have one entry per search")
+    flat = [t for per in trajectories for t in per]
+    counts = (C.c_int32 * max(m, 1))(*[len(per) for per in trajectories])
+    n = max(len(flat), 1)
+    th = (vp * n)(*[t[0].handle.value if t[0] is not None and t[0].handle else None for t in flat])
+    mu = (C.c_double * n)(*[float(t[1]) for t in flat])
+    wt = (C.c_double * n)(*[float(t[2]) for t in flat])
+    descs = [ConstraintSet._marshal_alignment(a, None) if a is not None else None for a in (alignments or [None] * m)]
+    al = (vp * max(m, 1))(*[C.addressof(d) if d is not None else None for d in descs])
+    return counts, th, mu, wt, al, descs
+
+
+def search_cluster_trees(prims, trees, csets, n_candidates, records_dev=None, trajectories=None, alignments=None):
+    """mg_cluster_tree_search for len(prims) (Primitive, ClusterTree, ConstraintSet) triples of one context: ONE launch.
+    Returns the records (TREE_SEARCH_RECORD array), read back in one copy; with records_dev (a DeviceBuffer of
+    len(prims) * 32 bytes) the records stay there and nothing is returned.
+    trajectories: per search a list of (Trajectory | None, min_u, weight), the root trajectory constraints scored behind the
+    set in list order (mg_cluster_tree_search_trajectories, the same one launch); alignments: per search the alignment dict
+    the trajectories are scored under (None: local coordinates), as score_trajectory_dev takes it."""
+    m, hp, ht, hc = _tree_search_handles(prims, trees, csets)
+    vp = C.c_void_p
     lib = prims[0].lib if m else load_library()
     if trajectories is not None:
-        if len(trajectories) != m or (alignments is not None and len(alignments) != m):
-            raise ValueError("trajectories and alignments must have one entry per search")
-        flat = [t for per in trajectories for t in per]
-        counts = (C.c_int32 * max(m, 1))(*[len(per) for per in trajectories])
-        n = max(len(flat), 1)
-        th = (vp * n)(*[t[0].handle.value if t[0] is not None and t[0].handle else None for t in flat])
-        mu = (C.c_double * n)(*[float(t[1]) for t in flat])
-        wt = (C.c_double * n)(*[float(t[2]) for t in flat])
-        descs = [ConstraintSet._marshal_alignment(a, None) if a is not None else None for a in (alignments or [None] * m)]
-        al = (vp * max(m, 1))(*[C.addressof(d) if d is not None else None for d in descs])
+        counts, th, mu, wt, al, descs = _tree_search_trajectories(m, trajectories, alignments)
         if records_dev is not None:
             _check(lib.mg_cluster_tree_search_trajectories(m, hp, ht, hc, counts, th, mu, wt, al, int(n_candidates), _dev_ptr(records_dev)))
             return None
@@ -1505,6 +1526,21 @@ def search_cluster_trees(prims, trees, csets, n_candidates, records_dev=None, tr
     out = np.zeros(m, dtype=TREE_SEARCH_RECORD)
     _check(lib.mg_cluster_tree_search_host(m, hp, ht, hc, int(n_candidates), out.ctypes.data_as(vp)))
     return out
+
+
+def cluster_tree_search_plan(prims, trees, csets, n_candidates, trajectories=None, alignments=None):
+    """mg_cluster_tree_search_plan: what search_cluster_trees with these arguments would stage in its workgroups' LDS -- dict(lds_bytes,
+    w_rows, root_rows, poly_doubles, trajectory_slots, lds_opt_in, refused).  Launches nothing."""
+    m, hp, ht, hc = _tree_search_handles(prims, trees, csets)
+    lib = prims[0].lib if m else load_library()
+    info = TreeSearchPlanInfo()
+    if trajectories is not None:
+        counts, th, mu, wt, al, descs = _tree_search_trajectories(m, trajectories, alignments)
+        _check(lib.mg_cluster_tree_search_plan(m, hp, ht, hc, counts, th, mu, wt, al, int(n_candidates), C.byref(info)))
+    else:
+        _check(lib.mg_cluster_tree_search_plan(m, hp, ht, hc, None, None, None, None, None, int(n_candidates), C.byref(info)))
+    return dict(lds_bytes=int(info.lds_bytes), w_rows=int(info.w_rows), root_rows=int(info.root_rows), poly_doubles=int(info.poly_doubles),
+                trajectory_slots=int(info.trajectory_slots), lds_opt_in=bool(info.lds_opt_in), refused=bool(info.refused))
 
 
 MG_KMEANS_MAX_DIM, MG_KMEANS_MAX_K, MG_KMEANS_MAX_N_INIT = 128, 64, 16   # mg_kmeans_segments (include/mg_hip.h)

@@ -830,12 +830,10 @@ struct mg_tree_maxima {
     int traj = 0, cp_rows = 0, poly_doubles = 0;   // the longest trajectory list, the most root rows and the longest polynomial table
 };
 
-// One launch for the table's searches.  plan(staging): the kernel's LDS plan with those tables staged; a plan beyond the
-// workgroup's LDS is tried again with one more of them read from memory (mg_tree_plan_fit).
-template <class PlanFn, class Kernel>
-static int mg_tree_launch(mg_context *ctx, const std::vector<mg_tree_search_desc> &tab, const mg_tree_maxima &m, int n_candidates, PlanFn plan, Kernel kernel,
+// One launch for the table's searches with the plan the ladder settled on (mg_tree_planned).
+template <class Plan, class Kernel>
+static int mg_tree_launch(mg_context *ctx, const std::vector<mg_tree_search_desc> &tab, const mg_tree_maxima &m, int n_candidates, const Plan &lp, Kernel kernel,
                           mg_tree_search_record *records_dev) {
-    const auto lp = mg_tree_plan_fit(mg_tree_staging{m.rows_known ? m.wrows : 0, m.cp_rows, m.poly_doubles}, m.traj, plan);
     if (lp.bytes > MG_TREE_LDS_MAX) {
         mg_set_error("mg_cluster_tree_search: %zu bytes of LDS (latents %d, constraints %d, candidates %d, children %d, depth %d, KD depth %d, trajectories %d) "
                      "beyond 160 KiB", lp.bytes, m.L, m.nc, n_candidates, m.children, m.depth, m.kd_depth, m.traj);
@@ -854,13 +852,19 @@ static int mg_tree_launch(mg_context *ctx, const std::vector<mg_tree_search_desc
     return MG_OK;
 }
 
-// Both entry points (the messages name the family): trajectory_counts NULL is the call without trajectories.
-static int mg_tree_search(int32_t n_searches, mg_primitive *const *prims, mg_cluster_tree *const *trees, const mg_constraint_set *const *csets,
+// a validated call: its context, its tree kind, the table its workgroups read and the maxima its plan is sized by
+struct mg_tree_call {
+    mg_context *ctx = nullptr;
+    int kind = 0;
+    std::vector<mg_tree_search_desc> tab;
+    mg_tree_maxima m;
+};
+
+// The arguments of both entry points and of the plan query (the messages name the family), validated and gathered into c:
+// trajectory_counts NULL is the call without trajectories.  n_searches >= 1.  Touches no device.
+static int mg_tree_gather(int32_t n_searches, mg_primitive *const *prims, mg_cluster_tree *const *trees, const mg_constraint_set *const *csets,
                           const int32_t *trajectory_counts, const mg_trajectory *const *trajectories, const double *min_u, const double *weights,
-                          const mg_alignment_desc *const *alignments, int32_t n_candidates, mg_tree_search_record *records_dev) {
-    MG_TREE_REQUIRE(n_searches >= 0, "mg_cluster_tree_search: n_searches = %d", n_searches);
-    if (n_searches == 0) return MG_OK;
-    MG_TREE_REQUIRE(prims && trees && csets && records_dev, "mg_cluster_tree_search: NULL argument");
+                          const mg_alignment_desc *const *alignments, int32_t n_candidates, mg_tree_call &c) {
     MG_TREE_REQUIRE(n_candidates >= 1 && n_candidates <= MG_TREE_MAX_CANDIDATES, "mg_cluster_tree_search: n_candidates = %d outside [1, %d]",
                     n_candidates, MG_TREE_MAX_CANDIDATES);
     MG_TREE_REQUIRE(prims[0] != nullptr, "mg_cluster_tree_search: primitive 0 is NULL");
@@ -871,11 +875,14 @@ static int mg_tree_search(int32_t n_searches, mg_primitive *const *prims, mg_clu
                         "mg_cluster_tree_search: search %d: a %s tree in a call of %s trees (one kind per call)", s,
                         trees[s]->kind ? "KD" : "feature", kind ? "KD" : "feature");
     mg_context *ctx = prims[0]->ctx;
+    c.ctx = ctx;
+    c.kind = kind;
     std::vector<int64_t> toff;
     { const int rc = mg_tree_traj_offsets("mg_cluster_tree_search", n_searches, trajectory_counts, toff); if (rc != MG_OK) return rc; }
     MG_TREE_REQUIRE(toff[n_searches] == 0 || (trajectories && min_u && weights), "mg_cluster_tree_search: NULL trajectory, min_u or weight array");
-    std::vector<mg_tree_search_desc> tab(n_searches);
-    mg_tree_maxima m;
+    std::vector<mg_tree_search_desc> &tab = c.tab;
+    tab.resize(n_searches);
+    mg_tree_maxima &m = c.m;
     for (int32_t s = 0; s < n_searches; s++) {
         mg_primitive *p = prims[s];
         const mg_cluster_tree *t = trees[s];
@@ -920,15 +927,57 @@ static int mg_tree_search(int32_t n_searches, mg_primitive *const *prims, mg_clu
         m.traj = std::max(m.traj, (int)count);
         m.cp_rows = std::max(m.cp_rows, (int)t0->rows);
     }
-    // (a call without trajectories launches the kernels it always did, with the plan it always had)
-    if (kind == 1) {
-        auto plan = [&](const mg_tree_staging &st) { return mg_kd_plan(m.L, m.nc, n_candidates, m.children, m.depth, m.kd_children, m.kd_depth, m.traj, st); };
-        if (m.traj > 0) return mg_tree_launch(ctx, tab, m, n_candidates, plan, mg_kd_tree_search_kernel<true>, records_dev);
-        return mg_tree_launch(ctx, tab, m, n_candidates, plan, mg_kd_tree_search_kernel<false>, records_dev);
+    return MG_OK;
+}
+
+// The plan of a gathered call as the ladder settles it, and the kernel that goes with it: f(plan, kernel).  The searches launch
+// through it and the plan query reads it, so the two cannot disagree.  (A call without trajectories has the kernels it always
+// launched, with the plan it always had.)
+template <class F>
+static int mg_tree_planned(const mg_tree_call &c, int n_candidates, F f) {
+    const mg_tree_maxima &m = c.m;
+    const mg_tree_staging want{m.rows_known ? m.wrows : 0, m.cp_rows, m.poly_doubles};
+    if (c.kind == 1) {
+        const auto lp = mg_tree_plan_fit(want, m.traj, [&](const mg_tree_staging &st) {
+            return mg_kd_plan(m.L, m.nc, n_candidates, m.children, m.depth, m.kd_children, m.kd_depth, m.traj, st);
+        });
+        return m.traj > 0 ? f(lp, mg_kd_tree_search_kernel<true>) : f(lp, mg_kd_tree_search_kernel<false>);
     }
-    auto plan = [&](const mg_tree_staging &st) { return mg_tree_plan(m.L, m.nc, n_candidates, m.children, m.depth, m.traj, st); };
-    if (m.traj > 0) return mg_tree_launch(ctx, tab, m, n_candidates, plan, mg_tree_search_kernel<true>, records_dev);
-    return mg_tree_launch(ctx, tab, m, n_candidates, plan, mg_tree_search_kernel<false>, records_dev);
+    const auto lp = mg_tree_plan_fit(want, m.traj, [&](const mg_tree_staging &st) { return mg_tree_plan(m.L, m.nc, n_candidates, m.children, m.depth, m.traj, st); });
+    return m.traj > 0 ? f(lp, mg_tree_search_kernel<true>) : f(lp, mg_tree_search_kernel<false>);
+}
+
+static int mg_tree_search(int32_t n_searches, mg_primitive *const *prims, mg_cluster_tree *const *trees, const mg_constraint_set *const *csets,
+                          const int32_t *trajectory_counts, const mg_trajectory *const *trajectories, const double *min_u, const double *weights,
+                          const mg_alignment_desc *const *alignments, int32_t n_candidates, mg_tree_search_record *records_dev) {
+    MG_TREE_REQUIRE(n_searches >= 0, "mg_cluster_tree_search: n_searches = %d", n_searches);
+    if (n_searches == 0) return MG_OK;
+    MG_TREE_REQUIRE(prims && trees && csets && records_dev, "mg_cluster_tree_search: NULL argument");
+    mg_tree_call c;
+    const int rc = mg_tree_gather(n_searches, prims, trees, csets, trajectory_counts, trajectories, min_u, weights, alignments, n_candidates, c);
+    if (rc != MG_OK) return rc;
+    return mg_tree_planned(c, n_candidates, [&](const auto &lp, auto kernel) { return mg_tree_launch(c.ctx, c.tab, c.m, n_candidates, lp, kernel, records_dev); });
+}
+
+extern "C" int mg_cluster_tree_search_plan(int32_t n_searches, mg_primitive *const *prims, mg_cluster_tree *const *trees,
+                                           const mg_constraint_set *const *csets, const int32_t *trajectory_counts,
+                                           const mg_trajectory *const *trajectories, const double *min_u, const double *weights,
+                                           const mg_alignment_desc *const *alignments, int32_t n_candidates, mg_tree_search_plan_info *out) {
+    MG_TREE_REQUIRE(out != nullptr, "mg_cluster_tree_search_plan: out is NULL");
+    memset(out, 0, sizeof(*out));
+    MG_TREE_REQUIRE(n_searches >= 0, "mg_cluster_tree_search: n_searches = %d", n_searches);
+    if (n_searches == 0) return MG_OK;
+    MG_TREE_REQUIRE(prims && trees && csets, "mg_cluster_tree_search: NULL argument");
+    mg_tree_call c;
+    const int rc = mg_tree_gather(n_searches, prims, trees, csets, trajectory_counts, trajectories, min_u, weights, alignments, n_candidates, c);
+    if (rc != MG_OK) return rc;
+    return mg_tree_planned(c, n_candidates, [&](const auto &lp, auto) {
+        out->lds_bytes = (int64_t)lp.bytes;
+        out->w_rows = lp.s.wrows; out->root_rows = lp.s.cp_rows; out->poly_doubles = lp.s.poly_doubles; out->trajectory_slots = lp.s.traj;
+        out->lds_opt_in = lp.bytes > 64 * 1024;
+        out->refused = lp.bytes > MG_TREE_LDS_MAX;
+        return MG_OK;
+    });
 }
 
 extern "C" int mg_cluster_tree_search(int32_t n_searches, mg_primitive *const *prims, mg_cluster_tree *const *trees,

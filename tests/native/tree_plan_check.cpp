@@ -6,6 +6,7 @@
 
 #include <cstdarg>
 #include <cstdio>
+#include <cstdlib>
 #include <vector>
 
 static int failures = 0;
@@ -55,7 +56,28 @@ static void check_plans(int L, int nc, int n_cand, int children, int depth, int 
     }
 }
 
-int main() {
+// The fitted plan of shapes given on the command line, twelve integers each (kind 0 feature / 1 KD, L, nc, n_cand, children, depth,
+// kd_children, kd_depth, traj, wrows, cp_rows, poly_doubles): one line "bytes wrows cp_rows poly_doubles traj" per shape, as
+// mg_cluster_tree_search_plan reports them.  tests/test_tree_search_shapes_host.py compares them with its restatement.
+static int print_fitted(int argc, char **argv) {
+    if ((argc - 1) % 12 != 0) { std::printf("usage: tree_plan_check [kind L nc n_cand children depth kd_children kd_depth traj wrows cp_rows poly]...\n"); return 2; }
+    for (int a = 1; a + 12 <= argc; a += 12) {
+        int v[12];
+        for (int i = 0; i < 12; i++) v[i] = std::atoi(argv[a + i]);
+        const mg_tree_staging want{v[9], v[10], v[11]};
+        if (v[0] == 1) {
+            const auto p = mg_tree_plan_fit(want, v[8], [&](const mg_tree_staging &st) { return mg_kd_plan(v[1], v[2], v[3], v[4], v[5], v[6], v[7], v[8], st); });
+            std::printf("%zu %d %d %d %d\n", p.bytes, p.s.wrows, p.s.cp_rows, p.s.poly_doubles, p.s.traj);
+        } else {
+            const auto p = mg_tree_plan_fit(want, v[8], [&](const mg_tree_staging &st) { return mg_tree_plan(v[1], v[2], v[3], v[4], v[5], v[8], st); });
+            std::printf("%zu %d %d %d %d\n", p.bytes, p.s.wrows, p.s.cp_rows, p.s.poly_doubles, p.s.traj);
+        }
+    }
+    return 0;
+}
+
+int main(int argc, char **argv) {
+    if (argc > 1) return print_fitted(argc, argv);
     // the plans over a grid of shapes, with and without trajectories and each staging
     for (int L : {1, 3, 40, 64, 68})
         for (int nc : {0, 1, 5, 33})

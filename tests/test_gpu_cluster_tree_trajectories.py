@@ -290,6 +290,18 @@ def test_misuse_returns_status_codes(ctx, nodes):
         ctx.profile_enable(False)
         rec = _capi.search_cluster_trees([prim], [dev], [cset], 1, trajectories=[one * _capi.MG_TREE_MAX_TRAJECTORIES], alignments=[root_record])
         assert rec["flags"][0] == 0 and np.isfinite(rec["value"][0])
+        # a full list, one wave per trajectory: the host-driven descent's record
+        # (the set aligned like the trajectories, as the descent's scorers build it)
+        tree, form = node.cluster_tree, [{"type": "position", "t": 11.0, "weight": 1.0, "target": [1.0, None, 2.0]}] + [_trajectory(path, 8)] * 4
+        aligned = _capi.ConstraintSet(prim, form[:1], None, root_record)
+        try:
+            rec = _capi.search_cluster_trees([prim], [dev], [aligned], 1, trajectories=[one * _capi.MG_TREE_MAX_TRAJECTORIES], alignments=[root_record])
+        finally:
+            aligned.close()
+        assert rec["flags"][0] == 0
+        value, _, leaf, n_eval = tree.descend(lambda ids: candidate_scoring.errors_of_samples(prim, form, None, root_record, tree.means[ids, :prim.n_components]), 1)
+        assert (rec["leaf"][0], rec["row"][0], rec["evaluations"][0]) == (leaf, tree.first_index[leaf], n_eval)
+        assert _bits(rec["value"][0]) == _bits(value), (rec["value"][0], value)
     finally:
         ctx.profile_enable(False)
         for obj in (traj, kd_traj, cset, kd_cset):

@@ -926,6 +926,57 @@ int mg_cluster_tree_search_plan(int32_t n_searches, mg_primitive *const *prims, 
                                 const mg_trajectory *const *trajectories, const double *min_u, const double *weights,
                                 const mg_alignment_desc *const *alignments, int32_t n_candidates, mg_tree_search_plan_info *out);
 
+/* The same launch with PER-FRAME constraints in the objective (the lists of the pick / carry actions and of the collision-avoidance
+ * pass: a collision-avoidance position, a discrete trajectory, a local trajectory or trajectory set looked up by walked arc length, a
+ * joint rotation, a joint's trajectory constraint): search s scores, behind its keyframe set and its root trajectories, the
+ * n_constraints[s] <= MG_FRAME_LIST_MAX descriptors constraints[s][.] in list order -- the additions of
+ * candidate_scoring.errors_of_samples (mg_score_constraints, mg_score_trajectory per trajectory, then mg_joint_tracks +
+ * mg_score_frame_constraints, a joint rotation at its place in the list), with the same statements (csrc/mg_frame_device.h).
+ * Everything mg_cluster_tree_search_trajectories takes, both tree kinds, several searches per launch, and per search:
+ *   plans[s]           the track plan of the search's primitive (mg_track_plan_create: the requests' joints, the aligning joint); NULL
+ *                      with n_constraints[s] = 0: the search has no list (it is scored as mg_cluster_tree_search_trajectories scores it)
+ *   grids[s][q]        request q's time grid (NULL: the canonical grid), q < MG_TRACK_MAX_REQUESTS
+ *   constraints[s][i]  the descriptors, as mg_score_frame_constraints / mg_options_frame_lists take them; request_of[s][i]: the plan's
+ *                      request whose tracks constraint i reads (ignored for MG_FRAME_JOINT_ROTATION)
+ *   rotation_grids[s][i]  MG_FRAME_JOINT_ROTATION only: a one-sample grid of the primitive at the constraint's frame index
+ * alignments[s] aligns the search's trajectories AND its tracks (a previous-frame record's joint is the plan's aligning joint; with
+ * trajectories that is the root).  Per chunk of 64 children the workgroup forms the children's joint tracks -- the control points of
+ * the channels the joints' chains read, MG_TREE_TRACK_GROUP children at a time in LDS, four taps per channel and frame, the candidate's
+ * aligning transform, the chain -- into the search's slab of scratch_dev, and behind a barrier a lane per child runs the chain scorers.
+ * scratch_dev: device memory of at least mg_cluster_tree_search_frames_plan's scratch_bytes, 16-byte aligned, owned by the caller and
+ * free again when the launch has finished.  The lists' trajectory tables stand in LDS where they fit on the rung the plan took
+ * (further rungs of the ladder: after W, the polynomials and the root rows, the lists' tables are read from memory, then the track
+ * group is halved down to one child).  No rung fits, or the slabs exceed 256 MiB: MG_ERR_UNSUPPORTED, nothing launched.  No search with
+ * a list: mg_cluster_tree_search_trajectories, byte for byte.  The launch is timed on profile slot 11. */
+typedef struct mg_tree_frame_lists {
+    mg_track_plan *const *plans;                          /* [n_searches] */
+    const mg_time_grid *const *grids;                     /* [n_searches][MG_TRACK_MAX_REQUESTS] */
+    const int32_t *n_constraints;                         /* [n_searches] */
+    const mg_frame_constraint_desc *const *constraints;   /* [n_searches][MG_FRAME_LIST_MAX] */
+    const int32_t *request_of;                            /* [n_searches][MG_FRAME_LIST_MAX] */
+    const mg_time_grid *const *rotation_grids;            /* [n_searches][MG_FRAME_LIST_MAX], NULL where there are no joint rotations */
+} mg_tree_frame_lists;
+int mg_cluster_tree_search_frames(int32_t n_searches, mg_primitive *const *prims, mg_cluster_tree *const *trees,
+                                  const mg_constraint_set *const *csets, const int32_t *trajectory_counts,
+                                  const mg_trajectory *const *trajectories, const double *min_u, const double *weights,
+                                  const mg_alignment_desc *const *alignments, const mg_tree_frame_lists *lists, int32_t n_candidates,
+                                  void *scratch_dev, int64_t scratch_bytes, mg_tree_search_record *records_dev);
+/* What that launch would stage, readable without a launch: mg_tree_search_plan_info's fields (lds_bytes: the whole dynamic LDS, the
+ * lists' regions included), then track_group (children whose control points stand in LDS side by side; 0: no search has a list),
+ * control_points (NB x kept channels of the widest list), tables_lds / table_bytes (the lists' tables staged, and their bytes) and
+ * scratch_bytes (what scratch_dev must hold).  Launches nothing, uploads nothing. */
+typedef struct mg_tree_frames_plan_info {
+    int64_t lds_bytes;
+    int32_t w_rows, root_rows, poly_doubles, trajectory_slots, lds_opt_in, refused;
+    int32_t track_group, control_points, tables_lds, pad;
+    int64_t table_bytes, scratch_bytes;
+} mg_tree_frames_plan_info;
+int mg_cluster_tree_search_frames_plan(int32_t n_searches, mg_primitive *const *prims, mg_cluster_tree *const *trees,
+                                       const mg_constraint_set *const *csets, const int32_t *trajectory_counts,
+                                       const mg_trajectory *const *trajectories, const double *min_u, const double *weights,
+                                       const mg_alignment_desc *const *alignments, const mg_tree_frame_lists *lists, int32_t n_candidates,
+                                       mg_tree_frames_plan_info *out);
+
 /* ---- k-means / KD cluster tree (reference space_partitioning/cluster_tree.py:117-149, cluster_tree_node.py:63-138,
  * kdtree.py:132-164,233-250) ----
  * The ClusterTree of a pickled model, flattened on the host.  Cluster nodes breadth first (node 0 the root): their
@@ -1481,6 +1532,11 @@ int mg_cluster_tree_search_trajectories_host(int32_t n_searches, mg_primitive *c
                                              const mg_constraint_set *const *csets, const int32_t *trajectory_counts,
                                              const mg_trajectory *const *trajectories, const double *min_u, const double *weights,
                                              const mg_alignment_desc *const *alignments, int32_t n_candidates, mg_tree_search_record *records);
+int mg_cluster_tree_search_frames_host(int32_t n_searches, mg_primitive *const *prims, mg_cluster_tree *const *trees,
+                                       const mg_constraint_set *const *csets, const int32_t *trajectory_counts,
+                                       const mg_trajectory *const *trajectories, const double *min_u, const double *weights,
+                                       const mg_alignment_desc *const *alignments, const mg_tree_frame_lists *lists, int32_t n_candidates,
+                                       void *scratch_dev, int64_t scratch_bytes, mg_tree_search_record *records);
 
 #ifdef __cplusplus
 }

@@ -108,6 +108,7 @@ EXPORTED_SYMBOLS = [
     "mg_score_constraint_residuals_chained", "mg_score_plan", "mg_option_step", "mg_options_step", "mg_options_step_device_counts", "mg_option_step_rows", "mg_options_step_rows", "mg_gmm_sample_rows", "mg_dist_broadcast",
     "mg_cluster_tree_create", "mg_cluster_tree_destroy", "mg_cluster_tree_search", "mg_cluster_tree_search_host",
     "mg_cluster_tree_search_trajectories", "mg_cluster_tree_search_trajectories_host", "mg_cluster_tree_search_plan",
+    "mg_cluster_tree_search_frames", "mg_cluster_tree_search_frames_host", "mg_cluster_tree_search_frames_plan",
     "mg_cluster_tree_create_kd", "mg_kmeans_segments", "mg_gmm_em_fit",
     "mg_spline_fit_batch", "mg_pca_fit", "mg_pca_project", "mg_pca_backproject",
     "mg_dtw_distance_grids", "mg_dtw_paths", "mg_warp_motions", "mg_dtw_pair_costs",
@@ -193,6 +194,18 @@ class TreeSearchPlanInfo(C.Structure):   # struct mg_tree_search_plan_info
                 ("trajectory_slots", C.c_int32), ("lds_opt_in", C.c_int32), ("refused", C.c_int32)]
 
 
+class TreeFrameLists(C.Structure):   # struct mg_tree_frame_lists
+    _fields_ = [("plans", C.c_void_p), ("grids", C.c_void_p), ("n_constraints", C.c_void_p), ("constraints", C.c_void_p), ("request_of", C.c_void_p),
+                ("rotation_grids", C.c_void_p)]
+
+
+class TreeFramesPlanInfo(C.Structure):   # struct mg_tree_frames_plan_info
+    _fields_ = [("lds_bytes", C.c_int64), ("w_rows", C.c_int32), ("root_rows", C.c_int32), ("poly_doubles", C.c_int32),
+                ("trajectory_slots", C.c_int32), ("lds_opt_in", C.c_int32), ("refused", C.c_int32), ("track_group", C.c_int32),
+                ("control_points", C.c_int32), ("tables_lds", C.c_int32), ("pad", C.c_int32), ("table_bytes", C.c_int64), ("scratch_bytes", C.c_int64)]
+
+
+MG_TREE_TRACK_GROUP = 4      # children whose control points a frames search keeps in LDS side by side (csrc/mg_tree_plan.h)
 MG_SCORE_KERNELS = ("valu", "tile", "wide")   # MG_SCORE_KERNEL_*
 MG_TRAJ_KERNELS = ("staged_lds", "staged_global", "stream", "coop8", "coop4", "stream_multi", "coop8_multi", "coop4_multi")   # MG_TRAJ_KERNEL_*
 
@@ -417,6 +430,9 @@ def load_library(path=None):
         "mg_cluster_tree_search_trajectories": [i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp],
         "mg_cluster_tree_search_trajectories_host": [i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp],
         "mg_cluster_tree_search_plan": [i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp],
+        "mg_cluster_tree_search_frames": [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, i64, vp],
+        "mg_cluster_tree_search_frames_host": [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, i64, vp],
+        "mg_cluster_tree_search_frames_plan": [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp],
         "mg_kmeans_segments": [vp, vp, i64, i32, i32, vp, vp, i32, i32, vp, vp, u64, i32, dbl, vp, vp, vp, vp],
         "mg_gmm_em_fit": [vp, vp, i64, i32, i32, vp, vp, dbl, dbl, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp],
         "mg_spline_fit_batch": [vp, vp, i64, i32, i32, vp, i32, vp],
@@ -1541,6 +1557,84 @@ def cluster_tree_search_plan(prims, trees, csets, n_candidates, trajectories=Non
         _check(lib.mg_cluster_tree_search_plan(m, hp, ht, hc, None, None, None, None, None, int(n_candidates), C.byref(info)))
     return dict(lds_bytes=int(info.lds_bytes), w_rows=int(info.w_rows), root_rows=int(info.root_rows), poly_doubles=int(info.poly_doubles),
                 trajectory_slots=int(info.trajectory_slots), lds_opt_in=bool(info.lds_opt_in), refused=bool(info.refused))
+
+
+def _tree_frame_lists(m, frame_lists):
+    """struct mg_tree_frame_lists for m searches: frame_lists[s] is None or an object with .plan (TrackPlan), .grids (one TimeGrid or
+    None per request), .descs (FrameConstraintDesc array), .req_of and .rotation_grids (one TimeGrid or None per constraint).  Returns
+    (the struct, what it points to -- keep both until the call has returned)."""
+    vp, R, K = C.c_void_p, MG_TRACK_MAX_REQUESTS, MG_FRAME_LIST_MAX
+    if len(frame_lists) != m:
+        raise ValueError("frame_lists must have one entry per search")
+    plans, grids, counts = (vp * max(m, 1))(), (vp * max(m * R, 1))(), (C.c_int32 * max(m, 1))()
+    cons, req, rot = (vp * max(m * K, 1))(), (C.c_int32 * max(m * K, 1))(), (vp * max(m * K, 1))()
+    for s, fl in enumerate(frame_lists):
+        if fl is None:
+            continue
+        n = len(fl.descs)
+        if n > K or len(fl.grids) > R:
+            raise ValueError("a search takes at most %d per-frame constraints over %d requests" % (K, R))
+        plans[s], counts[s] = fl.plan.handle.value, n
+        for q, g in enumerate(fl.grids):
+            grids[s * R + q] = g.handle.value if g is not None else None
+        for i in range(n):
+            cons[s * K + i] = C.addressof(fl.descs[i])
+            req[s * K + i] = int(fl.req_of[i])
+            g = fl.rotation_grids[i]
+            rot[s * K + i] = g.handle.value if g is not None else None
+    lists = TreeFrameLists()
+    keep = (plans, grids, counts, cons, req, rot)
+    lists.plans, lists.grids, lists.n_constraints, lists.constraints, lists.request_of, lists.rotation_grids = [C.addressof(a) for a in keep]
+    return lists, keep
+
+
+def _tree_frames_arguments(prims, trees, csets, trajectories, alignments, frame_lists):
+    m, hp, ht, hc = _tree_search_handles(prims, trees, csets)
+    counts, th, mu, wt, al, descs = _tree_search_trajectories(m, trajectories if trajectories is not None else [[]] * m, None)
+    # the alignment records: marshalled with the list's skeleton where the search has a list (its aligning joint may carry a name)
+    for s, a in enumerate(alignments or [None] * m):
+        if a is not None:
+            fl = frame_lists[s]
+            descs[s] = ConstraintSet._marshal_alignment(a, fl.skeleton if fl is not None else None)
+            al[s] = C.addressof(descs[s])
+    lists, keep = _tree_frame_lists(m, frame_lists)
+    return m, (hp, ht, hc, counts, th, mu, wt, al, C.byref(lists)), (descs, lists, keep)
+
+
+def cluster_tree_frames_plan(prims, trees, csets, n_candidates, trajectories, alignments, frame_lists):
+    """mg_cluster_tree_search_frames_plan: what search_cluster_trees_frames with these arguments would stage -- the fields of
+    cluster_tree_search_plan, then track_group, control_points, tables_lds, table_bytes and scratch_bytes.  Launches nothing."""
+    m, args, keep = _tree_frames_arguments(prims, trees, csets, trajectories, alignments, frame_lists)
+    lib = prims[0].lib if m else load_library()
+    info = TreeFramesPlanInfo()
+    _check(lib.mg_cluster_tree_search_frames_plan(m, *args, int(n_candidates), C.byref(info)))
+    return dict(lds_bytes=int(info.lds_bytes), w_rows=int(info.w_rows), root_rows=int(info.root_rows), poly_doubles=int(info.poly_doubles),
+                trajectory_slots=int(info.trajectory_slots), lds_opt_in=bool(info.lds_opt_in), refused=bool(info.refused),
+                track_group=int(info.track_group), control_points=int(info.control_points), tables_lds=bool(info.tables_lds),
+                table_bytes=int(info.table_bytes), scratch_bytes=int(info.scratch_bytes))
+
+
+def search_cluster_trees_frames(prims, trees, csets, n_candidates, trajectories, alignments, frame_lists, scratch_dev=None):
+    """mg_cluster_tree_search_frames_host: search_cluster_trees with per-frame constraint lists in the objective, ONE launch and one
+    read-back.  frame_lists: per search None or its list (frame_constraints.TreeFrameList).  scratch_dev: a DeviceBuffer of at least
+    cluster_tree_frames_plan(...)["scratch_bytes"]; None: sized by the plan query, allocated and freed here."""
+    m, args, keep = _tree_frames_arguments(prims, trees, csets, trajectories, alignments, frame_lists)
+    lib = prims[0].lib if m else load_library()
+    out = np.zeros(m, dtype=TREE_SEARCH_RECORD)
+    if m == 0:
+        return out
+    own = None
+    if scratch_dev is None:
+        info = TreeFramesPlanInfo()
+        _check(lib.mg_cluster_tree_search_frames_plan(m, *args, int(n_candidates), C.byref(info)))
+        own = scratch_dev = prims[0].ctx.malloc(max(int(info.scratch_bytes), 256))
+    try:
+        _check(lib.mg_cluster_tree_search_frames_host(m, *args, int(n_candidates), _dev_ptr(scratch_dev), int(scratch_dev.nbytes),
+                                                      out.ctypes.data_as(C.c_void_p)))
+    finally:
+        if own is not None:
+            own.free()
+    return out
 
 
 MG_KMEANS_MAX_DIM, MG_KMEANS_MAX_K, MG_KMEANS_MAX_N_INIT = 128, 64, 16   # mg_kmeans_segments (include/mg_hip.h)

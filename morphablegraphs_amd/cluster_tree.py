@@ -249,28 +249,54 @@ class HipFeatureClusterTree(_SearchTree):
 class TreeSearchSet(object):
     """What a one-launch search scores a row against: the device keyframe set, then the root trajectory constraints
     [(_capi.Trajectory, min_u, weight)] in list order, both under `alignment` (None: local coordinates).  The trajectories
-    are the cache's (candidate_scoring.cached_trajectory(..., pin=True)): release() hands them back, once."""
+    are the cache's (candidate_scoring.cached_trajectory(..., pin=True)): release() hands them back, once.
+    frame_constraints: None, or the per-frame constraint list scored behind them (frame_constraints.TreeFrameList: the track plan,
+    the descriptors in list order, their pinned trajectories and grids), released with the set."""
 
-    def __init__(self, cset, trajectories=(), alignment=None):
+    def __init__(self, cset, trajectories=(), alignment=None, frame_constraints=None):
         self.cset, self.trajectories, self.alignment = cset, list(trajectories), alignment
+        self.frame_constraints = frame_constraints
 
     def release(self):
         from .candidate_scoring import release_trajectory
         held, self.trajectories = self.trajectories, []
-        for t, _, _ in held:
-            release_trajectory(t)
+        frames, self.frame_constraints = self.frame_constraints, None
+        try:
+            if frames is not None:
+                frames.release()
+        finally:
+            for t, _, _ in held:
+                release_trajectory(t)
+
+
+def _frames_arguments(searches):
+    prims = [p for _, p, _ in searches]
+    trees = [t.device_tree(p) for t, p, _ in searches]
+    sets = [c if isinstance(c, TreeSearchSet) else TreeSearchSet(c) for _, _, c in searches]
+    return (prims, trees, [c.cset for c in sets]), ([c.trajectories for c in sets],
+                                                    [c.alignment if (c.trajectories or c.frame_constraints is not None) else None for c in sets],
+                                                    [c.frame_constraints for c in sets])
+
+
+def frames_search_plan(searches, n_candidates):
+    """What search_on_device would stage for searches that carry per-frame lists (_capi.cluster_tree_frames_plan); launches nothing."""
+    head, tail = _frames_arguments(searches)
+    return _capi.cluster_tree_frames_plan(*head, n_candidates, *tail)
 
 
 def search_on_device(searches, n_candidates):
     """searches: [(HipFeatureClusterTree | HipClusterTree, _capi.Primitive, _capi.ConstraintSet | TreeSearchSet)], all in one
-    context and of one tree kind.  ONE launch, one read-back, with or without trajectories (mg_cluster_tree_search[_trajectories]).
-    Returns the records (the caller interprets them with tree.result_of_record)."""
+    context and of one tree kind.  ONE launch, one read-back, with or without trajectories and per-frame lists
+    (mg_cluster_tree_search[_trajectories | _frames]).  Returns the records (the caller interprets them with tree.result_of_record)."""
     if not searches:
         return np.zeros(0, dtype=_capi.TREE_SEARCH_RECORD)
     prims = [p for _, p, _ in searches]
     trees = [t.device_tree(p) for t, p, _ in searches]
     sets = [c if isinstance(c, TreeSearchSet) else TreeSearchSet(c) for _, _, c in searches]
     csets = [c.cset for c in sets]
+    if any(c.frame_constraints is not None for c in sets):
+        head, tail = _frames_arguments(searches)
+        return _capi.search_cluster_trees_frames(*head, n_candidates, *tail)
     if not any(c.trajectories for c in sets):
         return _capi.search_cluster_trees(prims, trees, csets, n_candidates)
     return _capi.search_cluster_trees(prims, trees, csets, n_candidates, trajectories=[c.trajectories for c in sets],

@@ -19,7 +19,8 @@
 #include "mg_score_device.h"
 #include "mg_spline_device.h"
 #include "mg_traj_device.h"
-#include "mg_tree_plan.h"   // the chunk's size, the LDS plans and their ladder, the trajectory lists as a workgroup reads them
+#include "mg_frame_device.h"   // the per-frame chain scorers and the joint tracks' statements (mg_cluster_tree_search_frames)
+#include "mg_tree_plan.h"  // the chunk's size, the LDS plans and their ladder, the trajectory lists as a workgroup reads them
 
 struct mg_cluster_tree {
     mg_context *ctx = nullptr;
@@ -260,21 +261,122 @@ __device__ void mg_tree_score_chunk_trajectories(const mg_tree_traj_desc *__rest
     __syncthreads();
 }
 
-// The chunk scorer of both kernels: the set's value, then (a launch with trajectories, TRAJ) the search's trajectory terms.  Without
-// TRAJ this is mg_tree_score_chunk alone: the kernels a call without trajectories always launched.
-template <bool TRAJ>
+// ---- per-frame constraint lists behind the set and the trajectories (mg_cluster_tree_search_frames) ----
+// what a workgroup reads of its search's list (a second table of the launch, in device memory)
+struct mg_tree_frames_desc {
+    mg_track_args tk;                            // the tracks: out[q] = request q's part of the search's slab (no latents: the chunk's rows are in LDS)
+    int32_t n, pad;                              // constraints in the list (0: the search has none)
+    mg_fc_args c[MG_FRAME_LIST_MAX];             // the chain scorers' arguments, their tracks in the slab, B = the chunk
+    const int32_t *rot_i0[MG_FRAME_LIST_MAX];    // MG_FRAME_JOINT_ROTATION: the basis row of its frame index (a one-sample grid), else NULL
+    const double *rot_w[MG_FRAME_LIST_MAX];
+    double *rot_out[MG_FRAME_LIST_MAX];          // ... and its frame rows [64][D] in the slab (the quaternion's four channels are written)
+};
+// a launch's view of the lists: this workgroup's entry, the lists' LDS regions, the dynamic LDS
+struct mg_tree_frames_ctx {
+    const mg_tree_frames_desc *fd;
+    mg_tree_frames_lds fl;
+    unsigned char *smem;
+};
+
+// cval[j] += the search's per-frame constraints for row j, in list order: what mg_joint_tracks + mg_score_frame_constraints (or, for a
+// joint rotation, mg_back_project_frames_f64 + mg_align_frames + mg_score_frame_constraint) add behind mg_score_constraints and
+// mg_score_trajectory in candidate_scoring.errors_of_samples, with their statements (mg_frame_device.h).
+//   1. the chunk's tracks, fl.group children at a time: the control points of the kept channels as fma chains over the child's latents
+//      from the mean, its aligning transform from the first of them, then per (time, joint) four taps per channel and the chain --
+//      into the search's slab; a joint rotation's quaternion at its frame index likewise (sixteen chains per child).
+//   2. behind a barrier a lane per child runs the chain scorers over its tracks and adds the weighted errors to its value.
+// Every loop is bounded by what the entry point validated: cnt <= 64, the grids' T, the plan's joints and chain lengths, the list's n,
+// the tables' n_seg and granularity.  Called by every thread of the workgroup behind mg_tree_score_chunk[_trajectories], whose xs it reads.
+__device__ void mg_tree_score_chunk_frames(const mg_tree_frames_ctx &fx, const mg_tree_lds &s, int L, int cnt, int tid) {
+    const mg_tree_frames_desc *__restrict__ fd = fx.fd;
+    const mg_track_args &a = fd->tk;
+    const int xs_stride = L + 1, nc = a.n_chan, ncp = a.NB * nc, D = a.D, G = fx.fl.group, n = fd->n;
+    const size_t R = (size_t)a.R;
+    double *cp_all = (double *)(fx.smem + fx.fl.off_cp), *al_all = (double *)(fx.smem + fx.fl.off_al);
+    const double *tables = (const double *)(fx.smem + fx.fl.off_tab);
+    const int32_t *__restrict__ slot = a.slot;
+    auto slot_of = [&](int ch) { return slot[ch]; };
+    const bool aligned = a.align_mode != 0;
+    for (int g0 = 0; g0 < cnt; g0 += G) {
+        const int n_here = min(G, cnt - g0);
+        for (int e = tid; e < n_here * ncp; e += MG_TREE_THREADS) {
+            const int c = e / ncp, r = e - c * ncp, i = r / nc, q = r - i * nc;
+            const int row = i * D + a.chan[q];
+            const double *x = s.xs + (g0 + c) * xs_stride;
+            cp_all[e] = mg_control_point(a.mean[row], a.Et64 + row, R, L, [&](int k) { return x[k]; });
+        }
+        __syncthreads();
+        if (tid < n_here && aligned) mg_track_alignment(a, cp_all + (size_t)tid * ncp, slot_of, al_all + tid * 8);
+        __syncthreads();
+        for (int rq = 0; rq < a.n_requests; rq++) {
+            const int T = a.T[rq], j0 = a.req_joint0[rq], J = a.req_joint0[rq + 1] - j0;
+            const int32_t *i0 = a.i0[rq];
+            const double *w = a.w[rq];
+            for (int ce = tid; ce < n_here * T * J; ce += MG_TREE_THREADS) {
+                const int c = ce / (T * J), e = ce - c * (T * J), f = e / J, j = e - f * J;
+                double *out = a.out[rq] + (size_t)(g0 + c) * T * J * 3;
+                double p[3];
+                mg_track_point(cp_all + (size_t)c * ncp, nc, slot_of, i0[f], w + 4 * (size_t)f, a.records + (size_t)(j0 + j) * MG_TRACK_REC, aligned,
+                               al_all + c * 8, D, p);
+                out[(size_t)e * 3] = p[0]; out[(size_t)e * 3 + 1] = p[1]; out[(size_t)e * 3 + 2] = p[2];
+            }
+        }
+        for (int e = tid; e < n_here * n; e += MG_TREE_THREADS) {   // the joint rotations' quaternions, from the latents
+            const int c = e / n, i = e - c * n;
+            if (!fd->rot_i0[i]) continue;
+            const int qc = fd->c[i].quat_channel, i0 = fd->rot_i0[i][0];
+            const double *x = s.xs + (g0 + c) * xs_stride, *al = al_all + c * 8;
+            double q[4];
+            for (int k = 0; k < 4; k++) {
+                double v[4];
+                for (int t = 0; t < 4; t++) {
+                    const size_t row = (size_t)(i0 + t) * D + qc + k;
+                    v[t] = mg_control_point(a.mean[row], a.Et64 + row, R, L, [&](int kk) { return x[kk]; });
+                }
+                q[k] = mg_taps4(fd->rot_w[i], v, 1);
+            }
+            if (aligned && qc == 3 && D >= 7) mg_align_root_quat(al[5], al[6], q[0], q[1], q[2], q[3]);
+            double *row = fd->rot_out[i] + (size_t)(g0 + c) * D + qc;
+            row[0] = q[0]; row[1] = q[1]; row[2] = q[2]; row[3] = q[3];
+        }
+        __syncthreads();   // the group's control points are read: the next group overwrites them; the slab's rows are written
+    }
+    if (tid < cnt && s.cid[tid] >= 0) {
+        double err = s.cval[tid];
+        for (int i = 0; i < n; i++)
+            err = err + (fx.fl.tables_lds ? mg_fc_evaluate<true>(fd->c[i], tid, tables) : mg_fc_evaluate<false>(fd->c[i], tid, nullptr));
+        s.cval[tid] = err;
+    }
+    __syncthreads();
+}
+
+// the lists' trajectory tables into LDS where the plan has room for them (the caller's first __syncthreads publishes them)
+__device__ __forceinline__ void mg_tree_stage_frame_tables(const mg_tree_frames_ctx &fx, int tid) {
+    if (!fx.fl.tables_lds) return;
+    double *tables = (double *)(fx.smem + fx.fl.off_tab);
+    for (int i = 0; i < fx.fd->n; i++) mg_fc_stage_tables(fx.fd->c[i], tables, tid, MG_TREE_THREADS);
+}
+
+// The chunk scorer of both kernels: the set's value, then (a launch with trajectories, TRAJ) the search's trajectory terms, then (a
+// launch with per-frame lists, FRAMES) the search's list.  Without either this is mg_tree_score_chunk alone: the kernels a call
+// without trajectories always launched.
+template <bool TRAJ, bool FRAMES>
 __device__ __forceinline__ void mg_tree_score(const mg_tree_search_desc *__restrict__ d, const mg_score_args &a, const mg_tree_lds &s, const mg_tree_traj_lds &t,
-                                              const double *__restrict__ P, int dim, int cnt, int tid, int lane, int wave) {
+                                              const mg_tree_frames_ctx &fx, const double *__restrict__ P, int dim, int cnt, int tid, int lane, int wave) {
     mg_tree_score_chunk(a, s, P, dim, cnt, tid, lane, wave);
     if constexpr (TRAJ) {
         if (d->tr.n > 0) mg_tree_score_chunk_trajectories(&d->tr, s, t, a.L, cnt, tid, lane, wave);   // (uniform over the workgroup)
     }
+    if constexpr (FRAMES) {
+        if (fx.fd->n > 0) mg_tree_score_chunk_frames(fx, s, a.L, cnt, tid);                           // (uniform over the workgroup)
+    }
 }
 
 // ---- the FeatureClusterTree's search ----
-template <bool TRAJ>
-__global__ __launch_bounds__(MG_TREE_THREADS) void mg_tree_search_kernel(const mg_tree_search_desc *__restrict__ tab, mg_tree_lds_plan lp,
-                                                                         mg_tree_search_record *__restrict__ rec) {
+// (the body of the kernels below: mg_tree_search_kernel<TRAJ> is the launch there always was, mg_tree_search_frames_kernel adds the lists)
+template <bool TRAJ, bool FRAMES>
+__device__ __forceinline__ void mg_tree_search_body(const mg_tree_search_desc *__restrict__ tab, const mg_tree_lds_plan &lp, mg_tree_search_record *__restrict__ rec,
+                                                    const mg_tree_frames_desc *__restrict__ ftab, const mg_tree_frames_lds &fl) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     __shared__ int s_fr_len, s_total;
     __shared__ long long s_evals;
@@ -289,6 +391,8 @@ __global__ __launch_bounds__(MG_TREE_THREADS) void mg_tree_search_kernel(const m
     const mg_tree_lds s = mg_tree_lds_of(smem, lp.s, a, d->rows, tid);
     mg_tree_traj_lds tl = {};
     if constexpr (TRAJ) tl = mg_tree_traj_lds_of(smem, lp.s, &d->tr, tid);
+    mg_tree_frames_ctx fx = {};
+    if constexpr (FRAMES) { fx = mg_tree_frames_ctx{ftab + blockIdx.x, fl, smem}; mg_tree_stage_frame_tables(fx, tid); }
     // (cid from the plan, not s.cid: read back out of the struct it costs the KD kernel two VGPRs)
     int32_t *cid = (int32_t *)(smem + lp.s.off_cid), *clast = (int32_t *)(smem + lp.s.off_clast);
     int32_t *fr_n = (int32_t *)(smem + lp.s.off_frn), *fr_off = (int32_t *)(smem + lp.s.off_froff);
@@ -337,7 +441,7 @@ __global__ __launch_bounds__(MG_TREE_THREADS) void mg_tree_search_kernel(const m
                 cid[tid] = ch[cb[fr_n[f]] + (e - fr_off[f])];
             }
             __syncthreads();
-            mg_tree_score<TRAJ>(d, a, s, tl, means, dim, cnt, tid, lane, wave);
+            mg_tree_score<TRAJ, FRAMES>(d, a, s, tl, fx, means, dim, cnt, tid, lane, wave);
             if (tid == 0) {
                 for (int j = 0; j < cnt; j++) {
                     mg_heappush(lo, lo_len, lp.s.cap_local, mg_vn{s.cval[j], cid[j]}, lt, flags);   // _find_best_cluster_candidates
@@ -373,6 +477,18 @@ __global__ __launch_bounds__(MG_TREE_THREADS) void mg_tree_search_kernel(const m
     }
 }
 
+template <bool TRAJ>
+__global__ __launch_bounds__(MG_TREE_THREADS) void mg_tree_search_kernel(const mg_tree_search_desc *__restrict__ tab, mg_tree_lds_plan lp,
+                                                                         mg_tree_search_record *__restrict__ rec) {
+    mg_tree_search_body<TRAJ, false>(tab, lp, rec, nullptr, mg_tree_frames_lds{});
+}
+// ... with per-frame lists (and trajectories, where a search has them): ftab[search], the lists' regions behind the plan's
+__global__ __launch_bounds__(MG_TREE_THREADS) void mg_tree_search_frames_kernel(const mg_tree_search_desc *__restrict__ tab,
+                                                                                const mg_tree_frames_desc *__restrict__ ftab, mg_tree_lds_plan lp,
+                                                                                mg_tree_frames_lds fl, mg_tree_search_record *__restrict__ rec) {
+    mg_tree_search_body<true, true>(tab, lp, rec, ftab, fl);
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // The k-means / KD ClusterTree (reference space_partitioning/cluster_tree.py:117-149, cluster_tree_node.py:63-79,113-138,
 // kdtree.py:132-164,233-250): the same level loop, and after each level's k-means children every frontier leaf's
@@ -406,9 +522,9 @@ __device__ bool mg_kd_rows_lt(const double *__restrict__ P, int dim, int r, int 
     return false;
 }
 
-template <bool TRAJ>
-__global__ __launch_bounds__(MG_TREE_THREADS) void mg_kd_tree_search_kernel(const mg_tree_search_desc *__restrict__ tab, mg_kd_lds_plan lp,
-                                                                            mg_tree_search_record *__restrict__ rec) {
+template <bool TRAJ, bool FRAMES>
+__device__ __forceinline__ void mg_kd_tree_search_body(const mg_tree_search_desc *__restrict__ tab, const mg_kd_lds_plan &lp, mg_tree_search_record *__restrict__ rec,
+                                                       const mg_tree_frames_desc *__restrict__ ftab, const mg_tree_frames_lds &fl) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     __shared__ int s_fr_len, s_eff, s_total, s_ndesc, s_stop, s_kflags;
     __shared__ long long s_evals;
@@ -429,6 +545,8 @@ __global__ __launch_bounds__(MG_TREE_THREADS) void mg_kd_tree_search_kernel(cons
     const mg_tree_lds s = mg_tree_lds_of(smem, lp.s, a, d->rows, tid);
     mg_tree_traj_lds tl = {};
     if constexpr (TRAJ) tl = mg_tree_traj_lds_of(smem, lp.s, &d->tr, tid);
+    mg_tree_frames_ctx fx = {};
+    if constexpr (FRAMES) { fx = mg_tree_frames_ctx{ftab + blockIdx.x, fl, smem}; mg_tree_stage_frame_tables(fx, tid); }
     double *cval = s.cval;
     // (cid from the plan, not s.cid: read back out of the struct it costs the KD kernel two VGPRs)
     int32_t *cid = (int32_t *)(smem + lp.s.off_cid), *clast = (int32_t *)(smem + lp.s.off_clast);
@@ -506,7 +624,7 @@ __global__ __launch_bounds__(MG_TREE_THREADS) void mg_kd_tree_search_kernel(cons
                 cid[tid] = n_kd + ch[cb[fr_n[f]] + (e - fr_off[f])];
             }
             __syncthreads();
-            mg_tree_score<TRAJ>(d, a, s, tl, P, dim, cnt, tid, lane, wave);
+            mg_tree_score<TRAJ, FRAMES>(d, a, s, tl, fx, P, dim, cnt, tid, lane, wave);
             if (tid == 0) {
                 for (int j = 0; j < cnt; j++) {
                     mg_hent x;
@@ -544,7 +662,7 @@ __global__ __launch_bounds__(MG_TREE_THREADS) void mg_kd_tree_search_kernel(cons
                 dfr[tid] = f;
             }
             __syncthreads();
-            mg_tree_score<TRAJ>(d, a, s, tl, P, dim, gcnt, tid, lane, wave);
+            mg_tree_score<TRAJ, FRAMES>(d, a, s, tl, fx, P, dim, gcnt, tid, lane, wave);
             if (tid < gcnt) {   // the KD root's point (or the leaf's mean) at depth 0
                 mg_kent x;
                 x.v = cval[tid]; x.d = 0; x.pad = 0;
@@ -560,7 +678,7 @@ __global__ __launch_bounds__(MG_TREE_THREADS) void mg_kd_tree_search_kernel(cons
                     cid[2 * tid + 1] = active ? kl[cur] : -1;
                 }
                 if (!__syncthreads_or(active)) break;
-                mg_tree_score<TRAJ>(d, a, s, tl, P, dim, MG_TREE_CHUNK, tid, lane, wave);
+                mg_tree_score<TRAJ, FRAMES>(d, a, s, tl, fx, P, dim, MG_TREE_CHUNK, tid, lane, wave);
                 if (active) {   // _decide_direction_objective: left only if l < r
                     const int r = cid[2 * tid], l = cid[2 * tid + 1];
                     double cost = INFINITY;
@@ -639,6 +757,17 @@ __global__ __launch_bounds__(MG_TREE_THREADS) void mg_kd_tree_search_kernel(cons
         r.evaluations = s_evals;
         rec[blockIdx.x] = r;
     }
+}
+
+template <bool TRAJ>
+__global__ __launch_bounds__(MG_TREE_THREADS) void mg_kd_tree_search_kernel(const mg_tree_search_desc *__restrict__ tab, mg_kd_lds_plan lp,
+                                                                            mg_tree_search_record *__restrict__ rec) {
+    mg_kd_tree_search_body<TRAJ, false>(tab, lp, rec, nullptr, mg_tree_frames_lds{});
+}
+__global__ __launch_bounds__(MG_TREE_THREADS) void mg_kd_tree_search_frames_kernel(const mg_tree_search_desc *__restrict__ tab,
+                                                                                   const mg_tree_frames_desc *__restrict__ ftab, mg_kd_lds_plan lp,
+                                                                                   mg_tree_frames_lds fl, mg_tree_search_record *__restrict__ rec) {
+    mg_kd_tree_search_body<true, true>(tab, lp, rec, ftab, fl);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1023,5 +1152,197 @@ extern "C" int mg_cluster_tree_search_trajectories_host(int32_t n_searches, mg_p
     return mg_tree_search_to_host(n_searches, prims, records, [&](mg_tree_search_record *d_rec) {
         return mg_cluster_tree_search_trajectories(n_searches, prims, trees, csets, trajectory_counts, trajectories, min_u, weights, alignments, n_candidates,
                                                    d_rec);
+    });
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// mg_cluster_tree_search_frames: the same launch with per-frame constraint lists in the objective
+// ---------------------------------------------------------------------------------------------------------------
+// the lists of a validated call: the table its workgroups read, what its plan is sized by, the slabs
+struct mg_tree_frames_call {
+    std::vector<mg_tree_frames_desc> ftab;
+    mg_tree_frames_want want = {0, 0};
+    bool tables_fit = true;     // no search holds tables that the scorers' own bound keeps in memory
+    int64_t scratch_bytes = 0;  // the slabs of all searches, one behind the other
+    int with_lists = 0;
+};
+
+// The lists' arguments validated and gathered into f (the searches themselves: mg_tree_gather, before).  slab: where the slabs
+// begin (the plan query passes a place nothing is read from or written to).  Touches no device.
+static int mg_tree_gather_frames(const char *fn, int32_t n_searches, mg_primitive *const *prims, const mg_alignment_desc *const *alignments,
+                                 const mg_tree_frame_lists *lists, char *slab, mg_tree_frames_call &f) {
+    f.ftab.resize(n_searches);
+    for (int32_t s = 0; s < n_searches; s++) {
+        mg_tree_frames_desc &d = f.ftab[s];
+        memset(&d, 0, sizeof(d));
+        mg_track_plan *pl = lists && lists->plans ? lists->plans[s] : nullptr;
+        const int32_t n = lists && lists->n_constraints ? lists->n_constraints[s] : 0;
+        MG_TREE_REQUIRE(n >= 0 && n <= MG_FRAME_LIST_MAX, "%s: search %d: %d per-frame constraints outside [0, %d]", fn, s, n, MG_FRAME_LIST_MAX);
+        if (n == 0) continue;
+        mg_primitive *p = prims[s];
+        MG_TREE_REQUIRE(pl != nullptr && pl->prim == p, "%s: search %d has per-frame constraints but no track plan of its primitive", fn, s);
+        MG_TREE_REQUIRE(lists->grids && lists->constraints && lists->request_of, "%s: NULL grids, constraints or request_of", fn);
+        const mg_time_grid *const *grids = lists->grids + (size_t)s * MG_TRACK_MAX_REQUESTS;
+        // the slab: the requests' tracks, then the joint rotations' frame rows
+        int32_t T[MG_TRACK_MAX_REQUESTS], J[MG_TRACK_MAX_REQUESTS];
+        double *outs[MG_TRACK_MAX_REQUESTS] = {nullptr, nullptr, nullptr, nullptr};
+        char *at = slab + f.scratch_bytes;
+        for (int q = 0; q < pl->n_requests; q++) {
+            const mg_time_grid *g = grids[q] ? grids[q] : p->canonical;
+            MG_TREE_REQUIRE(g->prim == p && g->T >= 1, "%s: search %d: grid %d is empty or belongs to another primitive", fn, s, q);
+            T[q] = g->T; J[q] = pl->req_joint0[q + 1] - pl->req_joint0[q];
+            outs[q] = (double *)at;
+            at += (size_t)MG_TREE_CHUNK * T[q] * J[q] * 3 * 8;
+        }
+        size_t lds_unused = 0;
+        int rc = mg_track_fill_args(fn, pl, nullptr, MG_F64, 0, p->L, alignments ? alignments[s] : nullptr, grids, outs, &d.tk, &lds_unused);
+        if (rc != MG_OK) return rc;
+        int n_rot = 0;
+        for (int32_t i = 0; i < n; i++) {
+            const mg_frame_constraint_desc *c = lists->constraints[(size_t)s * MG_FRAME_LIST_MAX + i];
+            MG_TREE_REQUIRE(c != nullptr, "%s: search %d: constraint %d is NULL", fn, s, i);
+            if (c->type == MG_FRAME_JOINT_ROTATION) {
+                const mg_time_grid *g = lists->rotation_grids ? lists->rotation_grids[(size_t)s * MG_FRAME_LIST_MAX + i] : nullptr;
+                MG_TREE_REQUIRE(g != nullptr && g->prim == p && g->T == 1, "%s: search %d: joint rotation %d needs a one-sample grid of its primitive at its frame index", fn, s, i);
+                MG_TREE_REQUIRE(p->D >= 7, "%s: search %d: joint rotation %d on a primitive without quaternions", fn, s, i);
+                d.rot_i0[i] = g->d_i0; d.rot_w[i] = g->d_w; d.rot_out[i] = (double *)at;
+                rc = mg_fc_args_from_desc(fn, p, c, (const double *)at, MG_TREE_CHUNK, 1, (int32_t)p->D, nullptr, &d.c[i]);
+                at += (size_t)MG_TREE_CHUNK * p->D * 8;
+                n_rot++;
+            } else {
+                const int q = lists->request_of[(size_t)s * MG_FRAME_LIST_MAX + i];
+                MG_TREE_REQUIRE(q >= 0 && q < pl->n_requests, "%s: search %d: constraint %d reads request %d of %d", fn, s, i, q, pl->n_requests);
+                rc = mg_fc_args_from_desc(fn, p, c, outs[q], MG_TREE_CHUNK, T[q], J[q], nullptr, &d.c[i]);
+            }
+            if (rc != MG_OK) return rc;
+        }
+        d.n = n;
+        f.scratch_bytes += mg_tree_frames_scratch(pl->n_requests, T, J, n_rot, (int)p->D);
+        bool has_tables = false;
+        const size_t tb = mg_fc_place_list_tables(d.c, n, &has_tables);
+        if (has_tables && tb == 0) f.tables_fit = false;
+        f.want.table_bytes = std::max(f.want.table_bytes, tb);
+        f.want.ncp = std::max(f.want.ncp, (int)(p->NB * pl->n_chan));
+        f.with_lists++;
+    }
+    if (!f.tables_fit) f.want.table_bytes = 0;
+    if (f.scratch_bytes > MG_TREE_SCRATCH_MAX) {
+        mg_set_error("%s: the searches' track slabs take %lld bytes (at most %lld)", fn, (long long)f.scratch_bytes, (long long)MG_TREE_SCRATCH_MAX);
+        return MG_ERR_UNSUPPORTED;
+    }
+    return MG_OK;
+}
+
+// The plan of a gathered call with lists as its ladder settles it, and the kernel that goes with it: f(plan, lists' regions, kernel).
+template <class F>
+static int mg_tree_frames_planned(const mg_tree_call &c, const mg_tree_frames_call &fc, int n_candidates, F f) {
+    const mg_tree_maxima &m = c.m;
+    const mg_tree_staging want{m.rows_known ? m.wrows : 0, m.cp_rows, m.poly_doubles};
+    mg_tree_frames_lds fl;
+    if (c.kind == 1) {
+        const auto lp = mg_tree_frames_fit(want, m.traj, fc.want, [&](const mg_tree_staging &st) {
+            return mg_kd_plan(m.L, m.nc, n_candidates, m.children, m.depth, m.kd_children, m.kd_depth, m.traj, st);
+        }, &fl);
+        return f(lp, fl, mg_kd_tree_search_frames_kernel);
+    }
+    const auto lp = mg_tree_frames_fit(want, m.traj, fc.want, [&](const mg_tree_staging &st) { return mg_tree_plan(m.L, m.nc, n_candidates, m.children, m.depth, m.traj, st); }, &fl);
+    return f(lp, fl, mg_tree_search_frames_kernel);
+}
+
+// gather + validate a frames call: the searches, then their lists
+static int mg_tree_frames_gather_all(int32_t n_searches, mg_primitive *const *prims, mg_cluster_tree *const *trees, const mg_constraint_set *const *csets,
+                                     const int32_t *trajectory_counts, const mg_trajectory *const *trajectories, const double *min_u, const double *weights,
+                                     const mg_alignment_desc *const *alignments, const mg_tree_frame_lists *lists, int32_t n_candidates, char *slab,
+                                     mg_tree_call &c, mg_tree_frames_call &fc) {
+    MG_TREE_REQUIRE(prims && trees && csets, "mg_cluster_tree_search_frames: NULL argument");
+    // (a search whose only constraints are per-frame ones is aligned through its plan's joint, which the trajectories' record refuses:
+    // the trajectories see the records of the searches that have trajectories, as mg_cluster_tree_search_trajectories does)
+    const int rc{mg_tree_gather(n_searches, prims, trees, csets, trajectory_counts, trajectories, min_u, weights, alignments, n_candidates, c)};
+    if (rc != MG_OK) return rc;
+    return mg_tree_gather_frames("mg_cluster_tree_search_frames", n_searches, prims, alignments, lists, slab, fc);
+}
+
+extern "C" int mg_cluster_tree_search_frames_plan(int32_t n_searches, mg_primitive *const *prims, mg_cluster_tree *const *trees,
+                                                  const mg_constraint_set *const *csets, const int32_t *trajectory_counts,
+                                                  const mg_trajectory *const *trajectories, const double *min_u, const double *weights,
+                                                  const mg_alignment_desc *const *alignments, const mg_tree_frame_lists *lists, int32_t n_candidates,
+                                                  mg_tree_frames_plan_info *out) {
+    MG_TREE_REQUIRE(out != nullptr, "mg_cluster_tree_search_frames_plan: out is NULL");
+    memset(out, 0, sizeof(*out));
+    MG_TREE_REQUIRE(n_searches >= 0, "mg_cluster_tree_search_frames: n_searches = %d", n_searches);
+    if (n_searches == 0) return MG_OK;
+    mg_tree_call c;
+    mg_tree_frames_call fc;
+    static char nowhere[256];
+    const int rc = mg_tree_frames_gather_all(n_searches, prims, trees, csets, trajectory_counts, trajectories, min_u, weights, alignments, lists, n_candidates,
+                                             nowhere, c, fc);
+    if (rc != MG_OK) return rc;
+    return mg_tree_frames_planned(c, fc, n_candidates, [&](const auto &lp, const mg_tree_frames_lds &fl, auto) {
+        out->lds_bytes = (int64_t)fl.bytes;
+        out->w_rows = lp.s.wrows; out->root_rows = lp.s.cp_rows; out->poly_doubles = lp.s.poly_doubles; out->trajectory_slots = lp.s.traj;
+        out->lds_opt_in = fl.bytes > 64 * 1024;
+        out->refused = fl.bytes > MG_TREE_LDS_MAX;
+        out->track_group = fl.group; out->control_points = fl.ncp; out->tables_lds = fl.tables_lds; out->table_bytes = (int64_t)fl.table_bytes;
+        out->scratch_bytes = fc.scratch_bytes;
+        return MG_OK;
+    });
+}
+
+extern "C" int mg_cluster_tree_search_frames(int32_t n_searches, mg_primitive *const *prims, mg_cluster_tree *const *trees,
+                                             const mg_constraint_set *const *csets, const int32_t *trajectory_counts,
+                                             const mg_trajectory *const *trajectories, const double *min_u, const double *weights,
+                                             const mg_alignment_desc *const *alignments, const mg_tree_frame_lists *lists, int32_t n_candidates,
+                                             void *scratch_dev, int64_t scratch_bytes, mg_tree_search_record *records_dev) {
+    MG_TREE_REQUIRE(n_searches >= 0, "mg_cluster_tree_search_frames: n_searches = %d", n_searches);
+    if (n_searches == 0) return MG_OK;
+    MG_TREE_REQUIRE(records_dev != nullptr, "mg_cluster_tree_search_frames: NULL argument");
+    mg_tree_call c;
+    mg_tree_frames_call fc;
+    static char nowhere[256];
+    const int rc = mg_tree_frames_gather_all(n_searches, prims, trees, csets, trajectory_counts, trajectories, min_u, weights, alignments, lists, n_candidates,
+                                             scratch_dev ? (char *)scratch_dev : nowhere, c, fc);
+    if (rc != MG_OK) return rc;
+    if (fc.with_lists == 0)   // no lists anywhere: the launch without them, byte for byte
+        return mg_tree_search(n_searches, prims, trees, csets, trajectory_counts, trajectories, min_u, weights, alignments, n_candidates, records_dev);
+    MG_TREE_REQUIRE(scratch_dev != nullptr && scratch_bytes >= fc.scratch_bytes && ((size_t)scratch_dev & 15) == 0,
+                    "mg_cluster_tree_search_frames: the track slabs need %lld bytes at a 16-byte boundary (mg_cluster_tree_search_frames_plan), %lld given",
+                    (long long)fc.scratch_bytes, (long long)scratch_bytes);
+    return mg_tree_frames_planned(c, fc, n_candidates, [&](const auto &lp, const mg_tree_frames_lds &fl, auto kernel) {
+        if (fl.bytes > MG_TREE_LDS_MAX) {
+            mg_set_error("mg_cluster_tree_search_frames: %zu bytes of LDS (latents %d, constraints %d, candidates %d, children %d, trajectories %d, control points %d) "
+                         "beyond 160 KiB", fl.bytes, c.m.L, c.m.nc, n_candidates, c.m.children, c.m.traj, fl.ncp);
+            return (int)MG_ERR_UNSUPPORTED;
+        }
+        if (!fl.tables_lds)
+            for (auto &d : fc.ftab) mg_fc_unplace_tables(d.c, d.n);
+        mg_context *ctx = c.ctx;
+        MG_HIP_CHECK(hipSetDevice(ctx->device));
+        // one table: the searches, then their lists
+        const size_t sb = c.tab.size() * sizeof(mg_tree_search_desc), fb = fc.ftab.size() * sizeof(mg_tree_frames_desc);
+        static_assert(sizeof(mg_tree_search_desc) % 8 == 0 && sizeof(mg_tree_frames_desc) % 8 == 0, "the lists' table follows the searches'");
+        std::vector<unsigned char> both(sb + fb);
+        memcpy(both.data(), c.tab.data(), sb);
+        memcpy(both.data() + sb, fc.ftab.data(), fb);
+        mg_device_table &dt = ctx->tab[MG_TABLE_TREE];
+        const int rcu = dt.upload(ctx, "mg_cluster_tree_search_frames", both.data(), both.size());
+        if (rcu != MG_OK) return rcu;
+        if (fl.bytes > 64 * 1024) MG_HIP_CHECK(mg_lds_opt_in(MG_TREE_LDS_MAX, kernel));
+        mg_prof_begin(ctx, MG_PROF_CLUSTER_TREE_SEARCH);
+        hipLaunchKernelGGL(kernel, dim3((unsigned)c.tab.size()), dim3(MG_TREE_THREADS), fl.bytes, ctx->stream, (const mg_tree_search_desc *)dt.base(),
+                           (const mg_tree_frames_desc *)(dt.base() + sb), lp, fl, records_dev);
+        mg_prof_end(ctx, MG_PROF_CLUSTER_TREE_SEARCH);
+        MG_HIP_CHECK(hipGetLastError());
+        return (int)MG_OK;
+    });
+}
+
+extern "C" int mg_cluster_tree_search_frames_host(int32_t n_searches, mg_primitive *const *prims, mg_cluster_tree *const *trees,
+                                                  const mg_constraint_set *const *csets, const int32_t *trajectory_counts,
+                                                  const mg_trajectory *const *trajectories, const double *min_u, const double *weights,
+                                                  const mg_alignment_desc *const *alignments, const mg_tree_frame_lists *lists, int32_t n_candidates,
+                                                  void *scratch_dev, int64_t scratch_bytes, mg_tree_search_record *records) {
+    return mg_tree_search_to_host(n_searches, prims, records, [&](mg_tree_search_record *d_rec) {
+        return mg_cluster_tree_search_frames(n_searches, prims, trees, csets, trajectory_counts, trajectories, min_u, weights, alignments, lists, n_candidates,
+                                             scratch_dev, scratch_bytes, d_rec);
     });
 }

@@ -203,3 +203,64 @@ inline auto mg_tree_plan_fit(const mg_tree_staging &want, int traj, PlanFn plan)
     }
     return lp;
 }
+
+// ---- per-frame constraint lists inside the search (mg_cluster_tree_search_frames) ----
+// A search with a list forms, per chunk, its children's joint tracks: MG_TREE_TRACK_GROUP children at a time have the control points
+// of the channels the joints' chains read in LDS, [group][ncp] (ncp = NB x kept channels), with their aligning transforms [group][8];
+// the tracks go to the search's slab in device memory (mg_tree_frames_scratch).  The lists' trajectory tables (local trajectories,
+// trajectory sets, joint trajectories) stand in LDS behind them where they fit.  These regions lie BEHIND the kernel's own plan, so a
+// call without lists has the plan, to the byte, that it always had.
+#define MG_TREE_TRACK_GROUP 4
+#define MG_TREE_SCRATCH_MAX ((int64_t)256 << 20)   // the slabs of one call; beyond it the call is refused
+struct mg_tree_frames_want {
+    int ncp;              // the most control points one child keeps, over the searches with a list (0: no search has one)
+    size_t table_bytes;   // the most LDS one search's tables take (0: no tables, or tables the scorers' own bound keeps in memory)
+};
+struct mg_tree_frames_lds {
+    int group, ncp, tables_lds;     // group 0: no lists in this call
+    size_t table_bytes;
+    size_t off_cp, off_al, off_tab, bytes;   // bytes: the launch's dynamic LDS, the kernel's own plan included
+};
+
+inline mg_tree_frames_lds mg_tree_frames_carve(size_t plan_bytes, int ncp, int group, size_t table_bytes) {
+    mg_tree_frames_lds f;
+    f.ncp = ncp;
+    f.group = ncp > 0 ? group : 0;
+    f.table_bytes = ncp > 0 ? table_bytes : 0;
+    f.tables_lds = f.table_bytes > 0 ? 1 : 0;
+    size_t o = plan_bytes;          // (a multiple of 16)
+    f.off_cp = o;  o += (size_t)f.group * ncp * 8;
+    f.off_al = o;  o += (size_t)f.group * 8 * 8;
+    f.off_tab = o; o += f.table_bytes;
+    f.bytes = (o + 15) & ~(size_t)15;
+    return f;
+}
+
+// The ladder with lists: the steps there always were, in their order (W, the polynomials, the root rows), then the lists' tables read
+// from memory (every look-up of the arc-length walks then waits for L2), then the track group halved down to one child (more
+// barriers per chunk).  *fl: the lists' regions on the rung taken; returns the kernel's plan there.  fl->bytes > MG_TREE_LDS_MAX: refused.
+template <class PlanFn>
+inline auto mg_tree_frames_fit(const mg_tree_staging &want, int traj, const mg_tree_frames_want &fw, PlanFn plan, mg_tree_frames_lds *fl) -> decltype(plan(want)) {
+    mg_tree_staging st = want;
+    int group = MG_TREE_TRACK_GROUP;
+    size_t tables = fw.table_bytes;
+    auto lp = plan(st);
+    auto carve = [&]() { lp = plan(st); *fl = mg_tree_frames_carve(lp.bytes, fw.ncp, group, tables); return fl->bytes; };
+    if (carve() > MG_TREE_LDS_MAX && st.wrows > 0) { st.wrows = 0; carve(); }
+    if (traj > 0) {
+        if (fl->bytes > MG_TREE_LDS_MAX && st.poly_doubles > 0) { st.poly_doubles = 0; carve(); }
+        if (fl->bytes > MG_TREE_LDS_MAX && st.cp_rows > 0) { st.cp_rows = 0; carve(); }
+    }
+    if (fl->bytes > MG_TREE_LDS_MAX && tables > 0) { tables = 0; carve(); }
+    while (fl->bytes > MG_TREE_LDS_MAX && fw.ncp > 0 && group > 1) { group /= 2; carve(); }
+    return lp;
+}
+
+// A search's slab: its chunk's tracks, request after request [64][T][joints][3], then one frame row [64][D] per joint-rotation
+// constraint; doubles, rounded up to 256 bytes.
+inline int64_t mg_tree_frames_scratch(int n_requests, const int32_t *T, const int32_t *joints, int n_rotations, int D) {
+    int64_t doubles = 0;
+    for (int q = 0; q < n_requests; q++) doubles += (int64_t)MG_TREE_CHUNK * T[q] * joints[q] * 3;
+    doubles += (int64_t)MG_TREE_CHUNK * n_rotations * D;
+    return (doubles * 8 + 255) & ~(int64_t)255;
+}

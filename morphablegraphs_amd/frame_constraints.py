@@ -402,6 +402,64 @@ class TrackScorer(object):
         self.keep = []
 
 
+class TreeFrameList(object):
+    """A per-frame constraint list as the one-launch tree search takes it (mg_cluster_tree_search_frames): the track plan, the grids
+    and the descriptors in LIST order -- the track constraints' through a TrackScorer (its records, its pinned trajectories), a
+    joint rotation's with a one-sample grid at its frame index.  Raises NotImplementedError for what the launch does not cover: a list
+    longer than MG_FRAME_LIST_MAX, more than MG_TRACK_MAX_REQUESTS requests, joints without a skeleton.  release() hands everything
+    back, once."""
+
+    def __init__(self, prim, frame_list, skeleton, alignment):
+        if not frame_list or len(frame_list) > _capi.MG_FRAME_LIST_MAX:
+            raise NotImplementedError("the tree search takes 1..%d per-frame constraints per search" % _capi.MG_FRAME_LIST_MAX)
+        self.prim, self.skeleton, self.alignment = prim, _skeleton_or_root(skeleton), alignment
+        self.constraints = list(frame_list)
+        self._own_grids = []
+        tracks = [c for c in frame_list if c["type"] != "frame_joint_rotation"]
+        # (a list of joint rotations alone still aligns its candidates through a plan: the root's own track on the canonical grid)
+        self.scorer = TrackScorer(prim, tracks or [{"type": "frame_ca_position", "joint": 0, "target": [0.0, 0.0, 0.0], "n_frames": 1, "weight": 0.0}],
+                                  skeleton, alignment)
+        try:
+            self.plan, self.grids = self.scorer.plan, self.scorer.grids
+            m = len(frame_list)
+            self.descs = (_capi.FrameConstraintDesc * m)()
+            self.req_of, self.rotation_grids = [0] * m, [None] * m
+            k = 0
+            for i, c in enumerate(frame_list):
+                d = self.descs[i]
+                if c["type"] == "frame_joint_rotation":
+                    d.type, d.weight, d.n_joints = _capi.MG_FRAME_JOINT_ROTATION, float(c.get("weight", 1.0)), 1
+                    d.quat_channel = 3 + 4 * int(c["joint_index"])
+                    for e in range(4):
+                        d.quaternion[e] = float(c["quaternion"][e])
+                    g = prim.time_grid(np.asarray([float(c["frame_idx"])], dtype=np.float64))     # aligned_spline.evaluate(frame_idx)
+                    self._own_grids.append(g)
+                    self.rotation_grids[i] = g
+                else:
+                    C.memmove(C.addressof(d), C.addressof(self.scorer.descs[k]), C.sizeof(_capi.FrameConstraintDesc))
+                    self.req_of[i] = self.scorer.req_of[k]
+                    k += 1
+        except Exception:
+            self.release()
+            raise
+
+    def release(self):
+        scorer, self.scorer = self.scorer, None
+        grids, self._own_grids = self._own_grids, []
+        if scorer is not None:
+            scorer.close()          # (synchronizes: no launch reads the records or the grids any more)
+        for g in grids:
+            g.close()
+
+
+def tree_frame_list(prim, frame_list, skeleton, alignment):
+    """The list made ready for the one-launch tree search, or None where the launch does not cover it (TreeFrameList)."""
+    try:
+        return TreeFrameList(prim, frame_list, skeleton, alignment)
+    except NotImplementedError:
+        return None
+
+
 def _fused(prim, S, frame_list, skeleton, alignment, d_err, accumulate, residuals):
     """The fused route; None when the list is not covered (the caller takes the chain)."""
     if not FUSED:

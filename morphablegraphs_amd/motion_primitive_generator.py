@@ -219,6 +219,9 @@ class HipMotionPrimitiveGenerator(object):
         # "exhaustive" (default): every stored sample of the tree scored in one launch; "descend": the reference's own descent
         # (feature_cluster_tree.py:129-187) with n_cluster_search_candidates kept per level
         self.cluster_tree_search_method = algorithm_config.get("cluster_tree_search_method", "exhaustive")
+        # "descend" only: lists with per-frame constraints (collision avoidance, pick / carry) take the one launch as well
+        # (mg_cluster_tree_search_frames); off: they keep the host-driven descent
+        self.cluster_tree_search_per_frame = bool(algorithm_config.get("cluster_tree_search_per_frame", False))
         self.use_local_coordinates = algorithm_config.get("use_local_coordinates", True)
         # gpu_batch only: draw the candidates with the device sampler and keep them on the GPU (not sklearn's stream)
         # a distributed.MgCommunicator (or FileCommunicator) when the candidate loop is sharded over the GPUs of a node: this
@@ -317,12 +320,15 @@ class HipMotionPrimitiveGenerator(object):
         once per visited mean or sample.  At GPU batch sizes the whole tree is cheaper to score than to descend:
         every stored sample in one launch, first minimum -- the result of find_best_example_exhaustive.
         With algorithm_config["cluster_tree_search_method"] = "descend" the reference's descent instead (its sample and
-        min_error): one launch when the constraints make a device search set (keyframe constraints and the action's root
-        trajectory constraints), else the host-driven descent that scores each level's children in one batched call."""
+        min_error): one launch when the constraints make a device search set (keyframe constraints, the action's root
+        trajectory constraints and, with algorithm_config["cluster_tree_search_per_frame"], per-frame constraint lists), else the
+        host-driven descent that scores each level's children in one batched call."""
         if self.cluster_tree_search_method == "descend":
             n = self.n_cluster_search_candidates if n_candidates < 1 else n_candidates
             skeleton = getattr(constraints, "hip_skeleton", None)
-            search_set = graph_node._tree_search_set(constraints, prev_frames, skeleton)
+            per_frame = bool(getattr(self, "cluster_tree_search_per_frame", False))
+            search_set = graph_node._tree_search_set(constraints, prev_frames, skeleton, per_frame=True) if per_frame else \
+                graph_node._tree_search_set(constraints, prev_frames, skeleton)
             if search_set is not None:     # (released by the search)
                 distance, s = graph_node.search_best_sample_on_device(constraints, n, prev_frames, skeleton, search_set=search_set)
             else:

@@ -134,19 +134,24 @@ class HipMotionStateGraphNode(HipMotionPrimitiveModelWrapper):
             return self.cluster_tree.find_best_example_excluding_search_candidates(obj, data, n_candidates)
         return np.inf, None
 
-    def _tree_search_set(self, constraints, prev_frames=None, skeleton=None):
+    def _tree_search_set(self, constraints, prev_frames=None, skeleton=None, per_frame=False):
         """What a one-launch tree search scores against (cluster_tree.TreeSearchSet: the device keyframe set, the root
-        trajectory constraints as pinned device trajectories, the alignment), or None when the launch does not cover the
-        constraints: per-frame constraints, more than MG_TREE_MAX_TRAJECTORIES trajectories, trajectories aligned to another
-        joint than the root.  The caller release()s the set after its call."""
+        trajectory constraints as pinned device trajectories, the alignment and, with per_frame, the per-frame constraint list), or
+        None when the launch does not cover the constraints: more than MG_TREE_MAX_TRAJECTORIES trajectories, trajectories
+        aligned to another joint than the root, and per-frame constraints -- all of them by default (per_frame=False: the
+        routing there always was); with per_frame=True only a list longer than MG_FRAME_LIST_MAX (or over more than
+        MG_TRACK_MAX_REQUESTS requests) and a plan no rung of the kernel's LDS ladder takes.  The caller release()s the set after
+        its call."""
+        from . import cluster_tree as _ct, frame_constraints as _fc
         from .candidate_scoring import alignment_from_prev_frames, cached_constraint_set, cached_trajectory, split_trajectories
         from .frame_constraints import is_frame_constraint
         clist = constraints.constraints if hasattr(constraints, "constraints") else constraints
         skeleton = skeleton if skeleton is not None else getattr(constraints, "hip_skeleton", None)
         form = constraints_to_device_form(clist)
-        if any(is_frame_constraint(c) for c in form):
+        frames = [c for c in form if is_frame_constraint(c)]
+        if frames and (not per_frame or len(frames) > _capi.MG_FRAME_LIST_MAX):
             return None
-        keyframes, trajectories = split_trajectories(form)
+        keyframes, trajectories = split_trajectories([c for c in form if not is_frame_constraint(c)])
         if len(trajectories) > _capi.MG_TREE_MAX_TRAJECTORIES:
             return None
         alignment = alignment_from_prev_frames(prev_frames, constraints, skeleton)
@@ -158,6 +163,11 @@ class HipMotionStateGraphNode(HipMotionPrimitiveModelWrapper):
         try:
             for c in trajectories:
                 sset.trajectories.append((cached_trajectory(prim, c, pin=True), c.get("min_u", 0.0), c.get("weight", 1.0)))
+            if frames:
+                sset.frame_constraints = _fc.tree_frame_list(prim, frames, skeleton, alignment)
+                if sset.frame_constraints is None or _ct.frames_search_plan([(self._search_tree(), prim, sset)], 1)["refused"]:
+                    sset.release()
+                    return None
         except Exception:
             sset.release()
             raise
@@ -168,19 +178,20 @@ class HipMotionStateGraphNode(HipMotionPrimitiveModelWrapper):
             raise NotImplementedError("node %r has no cluster tree to descend (only stored samples)" % (self.name,))
         return self.cluster_tree
 
-    def search_best_sample_on_device(self, constraints, n_candidates, prev_frames=None, skeleton=None, search_set=None):
+    def search_best_sample_on_device(self, constraints, n_candidates, prev_frames=None, skeleton=None, search_set=None, per_frame=False):
         """search_best_sample with the reference's objective (the constraints' summed weighted errors, aligned to prev_frames
-        outside local mode) as ONE launch (mg_cluster_tree_search[_trajectories]): (error, sample).  Adds the objectives scored
-        to constraints.evaluations.  search_set: what _tree_search_set returned for these arguments, where the caller has asked
-        already; it is released here either way."""
+        outside local mode) as ONE launch (mg_cluster_tree_search[_trajectories | _frames]): (error, sample).  Adds the objectives
+        scored to constraints.evaluations.  search_set: what _tree_search_set returned for these arguments, where the caller has
+        asked already; it is released here either way.  per_frame: per-frame constraint lists take the launch as well
+        (_tree_search_set's flag)."""
         sset = search_set
         try:
             tree = self._search_tree()
             if sset is None:
-                sset = self._tree_search_set(constraints, prev_frames, skeleton)
+                sset = self._tree_search_set(constraints, prev_frames, skeleton, per_frame=per_frame)
             if sset is None:
-                raise NotImplementedError("the one-launch tree search scores keyframe constraints and up to %d root trajectories"
-                                          % _capi.MG_TREE_MAX_TRAJECTORIES)
+                raise NotImplementedError("the one-launch tree search scores keyframe constraints, up to %d root trajectories and, with "
+                                          "per_frame, up to %d per-frame constraints" % (_capi.MG_TREE_MAX_TRAJECTORIES, _capi.MG_FRAME_LIST_MAX))
             rec = search_on_device([(tree, self.motion_primitive._prim, sset)], n_candidates)[0]
         finally:
             if sset is not None:
@@ -366,18 +377,20 @@ class HipMotionStateGraph(object):
                         from_node_key, to_node_key, self._get_transition_type(from_node_key, to_node_key), None)
 
     def evaluate_options(self, options, constraints_per_option, n_samples, rng_seed=None, use_cluster_trees=False, prev_frames=None,
-                         skeleton=None):
+                         skeleton=None, per_frame=False):
         """GraphWalkPlanner._evaluate_options over this graph's nodes (reference graph_walk_planner.py:184-226): options are node
         keys.  With use_cluster_trees every option whose node has a cluster tree is searched with n_candidates = 1, as
         _evaluate_option does (:205-207), ALL of them in one launch; the other options draw n_samples candidates, score them and
-        keep the first minimum.  Returns (best_option, {option: (best_sample, min_error)})."""
+        keep the first minimum.  per_frame: options whose lists carry per-frame constraints take that launch too
+        (_tree_search_set's flag; off: they take the host-driven descent, as before).  Returns (best_option, {option: (best_sample, min_error)})."""
         results, searches, general = {}, [], []
         try:
             for key in options:
                 node = self.nodes[key]
                 cons = constraints_per_option[key]
                 if use_cluster_trees and isinstance(node.cluster_tree, _SEARCH_TREES):
-                    sset = node._tree_search_set(cons, prev_frames, skeleton)
+                    sset = node._tree_search_set(cons, prev_frames, skeleton, per_frame=per_frame) if per_frame else \
+                        node._tree_search_set(cons, prev_frames, skeleton)
                     if sset is not None:
                         searches.append((key, (node.cluster_tree, node.motion_primitive._prim, sset)))
                         continue

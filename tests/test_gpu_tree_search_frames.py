@@ -16,7 +16,6 @@ from morphablegraphs_amd.candidate_scoring import alignment_from_start_pose, err
 from morphablegraphs_amd.cluster_tree import TreeSearchSet, frames_search_plan, search_on_device
 from morphablegraphs_amd.motion_primitive_generator import HipMotionPrimitiveGenerator
 from morphablegraphs_amd.motion_state_graph import HipMotionStateGraphNode
-from test_gpu_kd_cluster_tree import _kd_tree
 
 pytestmark = pytest.mark.gpu
 
@@ -62,10 +61,7 @@ class Search(object):
         if not with_frames:
             self.cons = [c for c in self.cons if not frame_constraints.is_frame_constraint(c)]
         self.kf, self.trajs = candidate_scoring.split_trajectories([c for c in self.cons if not frame_constraints.is_frame_constraint(c)])
-        self.tree = fc.host_tree(r)
-        if r["kind"] == "kd":
-            counts = np.array(fc.tree_counts(r["tree"]))
-            self.tree = _kd_tree(counts, (counts == 0).astype(np.int32), fc.tree_means(r), n_spatial=prim.n_components)
+        self.tree = fc.kd_tree(r) if r["kind"] == "kd" else fc.host_tree(r)
         self.cset = _capi.ConstraintSet(prim, self.kf, self.sk, self.al)
         self.handles = [_capi.Trajectory(prim, t["control_points"], granularity=t.get("granularity", 1000)) for t in self.trajs]
         flist = frame_constraints.TreeFrameList(prim, frames, self.sk, self.al) if with_frames and frames else None

@@ -190,7 +190,7 @@ def test_frames_plan_header_alone():
 def test_restated_frames_plan_is_the_headers():
     """frames_fit of tests/tree_search_frames_cases.py against mg_tree_frames_fit on the rows' shapes and on shapes around every further rung"""
     shapes = []
-    for r in fc.ROWS:
+    for r in fc.ROWS + fc.SWEEP_ROWS:
         cons = fc.constraints_of(r)
         c = fc.call_of(r, len([k for k in cons if k["type"] == "position"]), [len(k["control_points"]) - 1 for k in cons if k["type"] == "trajectory"])
         shapes.append((r["kind"], c, fc.PRIMS[r["prim"]][1] * r["n_chan"], fc.table_bytes(r["tables"])))
@@ -242,3 +242,133 @@ def test_every_row_is_conditioned_for_the_oracle(name):
         need = 1000.0 * fc.tolerance(r, largest)
         print("%s level %d: kept-dropped %.3g, best-second %.3g, needed %.3g" % (name, level, kept_dropped, best_second, need))
         assert kept_dropped > need and best_second > need, (name, level, kept_dropped, best_second, need)
+
+
+# ---- the sweep (fc.SWEEP_ROWS): where its rows stand, the ledger, the conditioning --------------------------------------------------------
+def _family(name, kind=None):
+    return [r for r in fc.SWEEP_ROWS if r["family"] == name and kind in (None, r["kind"])]
+
+
+def test_the_sweeps_rows_stand_where_the_table_says():
+    plans = {r["name"]: fc.row_plan(r) for r in fc.SWEEP_ROWS}
+    assert len(set(plans)) == len(fc.SWEEP_ROWS) and not set(plans) & set(fc.ROW_IDS)
+    for kind in sc.KINDS:
+        one = lambda name: plans[_family(name, kind)[0]["name"]]
+        stay, leave = one("tables_stay"), one("tables_leave")
+        assert stay["tables_lds"] and stay["table_bytes"] == 144336 and stay["lds_opt_in"] and stay["track_group"] == 4
+        assert not leave["tables_lds"] and leave["table_bytes"] == 0 and not leave["lds_opt_in"] and leave["track_group"] == 4
+        assert fc.n_keyframes_of(_family("tables_leave", kind)[0]["build"]) == fc.n_keyframes_of(_family("tables_stay", kind)[0]["build"]) + 1
+        # a staging rung moved by the lists' regions alone: the search without its list keeps what the search with it loses
+        for name, key, keeps in (("lists_push_w", "w_rows", ("all_staged",)), ("lists_push_polynomials", "poly_doubles", ("all_staged", "w_memory")),
+                                 ("lists_push_root_rows", "root_rows", ("all_staged", "w_memory", "polynomials_memory"))):
+            r = _family(name, kind)[0]
+            bare = sc.plan_fit(kind, fc.call_of(r, fc.n_keyframes_of(r["build"]), fc.segments_of(r["build"])))
+            assert bare["state"] in keeps and bare[key] > 0 and one(name)[key] == 0 and one(name)["tables_lds"] and one(name)["track_group"] == 4, (name, kind, bare)
+            assert one(name.replace("push", "keep"))[key] > 0
+        assert one("lists_push_polynomials")["root_rows"] > 0 and len(fc.segments_of(_family("lists_push_root_rows", kind)[0]["build"])) == 2
+        # every rung of the ladder, in one search
+        r = _family("everything_left", kind)[0]
+        c, p = fc.call_of(r, fc.n_keyframes_of(r["build"]), fc.segments_of(r["build"])), one("everything_left")
+        assert c["wrows"] > 0 and c["poly_doubles"] > 0 and c["cp_rows"] > 0 and fc.table_bytes(r["tables"]) > 0
+        assert (p["w_rows"], p["poly_doubles"], p["root_rows"], p["tables_lds"]) == (0, 0, 0, False) and p["track_group"] in (1, 2) and not p["refused"]
+        assert set(fc.row_trace(r)) >= {"w", "poly", "cp", "tables", "group4"} and all(fc.row_trace(r)[k][1] for k in ("w", "poly", "cp", "tables", "group4"))
+        # the groups, for the Hips skeleton (49 control points) and the chain (77)
+        for fam, ncp in (("hips", 49), ("chain", 77)):
+            got = {r["family"]: plans[r["name"]] for r in fc.SWEEP_ROWS if r["kind"] == kind and ("-%s-" % fam) in r["name"]}
+            assert [got[n]["track_group"] for n in ("group4_last", "group2_first", "group1_first", "group1_last")] == [4, 2, 1, 1]
+            assert all(p["control_points"] == ncp and not p["refused"] for n, p in got.items() if n != "refused_by_group")
+        assert one("group2_65_children")["track_group"] == 2 and _family("group2_65_children", kind)[0]["tree"] == ("flat", 65)
+        assert one("refused_by_group")["refused"] and _family("refused_by_group", kind)[0]["refused"]
+        halved = [r for r in fc.SWEEP_ROWS if r["kind"] == kind and plans[r["name"]]["track_group"] in (1, 2)]
+        assert {r["align"] for r in halved} >= {1, 2}
+        assert any(r["tree"][1] % 2 for r in halved if plans[r["name"]]["track_group"] == 2)          # a count the group does not divide: a tail of one
+    # the KD descents: one group of descents and one more, one and two levels, each on group 4 and on a halved group
+    for fam, groups in (("kd_descents_group4", (4,)), ("kd_descents_halved", (1, 2))):
+        rows = _family(fam)
+        assert {r["kd"] for r in rows} == {(n, lv) for n in (1, 32, 33) for lv in (1, 2)} and all(plans[r["name"]]["track_group"] in groups for r in rows)
+        assert all(len(r["build"]) == 2 and r["kind"] == "kd" for r in rows)
+    assert max(r["kd"][0] for r in fc.SWEEP_ROWS) > sc.KD_GROUP
+    # the yardstick: scorer_refuses on both sides of the VALU kernel's 150 KiB (64 rows of L + 1 latents and of max(n, 1) residuals), for
+    # the wide primitives by the latent and for the tiny one by the keyframe; the GPU file asserts the refusal itself for every such row
+    assert not fc.scorer_refuses(298, 1) and fc.scorer_refuses(299, 1) and not fc.scorer_refuses(3, 296) and fc.scorer_refuses(3, 297)
+    assert not fc.scorer_refuses(296, 3) and fc.scorer_refuses(297, 3)
+    for r in fc.SWEEP_ROWS:
+        L, n = fc.PRIMS[r["prim"]][0], fc.n_keyframes_of(r["build"])
+        assert (r["yardstick"] == "oracle") == ((64 * (L + 1) + max(n, 1) * 64) * 8 > 150 * 1024), r["name"]
+    assert {r["yardstick"] for r in fc.SWEEP_ROWS} == {"oracle", "batched"}
+    # a halved row's winner is decided by a score that only a group of that size forms: its place among the level's children -- for a
+    # KD descent its start's place, or the pair of slots of the step that scored it -- lies in the second pair of a stride of four on
+    # group 2, behind the first of four on group 1.  The record shows the winner alone, so this is where a wrong stride must show.
+    halved = [r for r in fc.SWEEP_ROWS if not r["refused"] and plans[r["name"]]["track_group"] in (1, 2)]
+    assert len(halved) == 22 and sum(plans[r["name"]]["track_group"] == 2 for r in halved) == 14
+    for r in halved:
+        assert fc.in_later_group(fc.oracle_of(r)["slot"], plans[r["name"]]["track_group"]), (r["name"], fc.oracle_of(r)["slot"], r["seed"])
+    assert [fc.in_later_group(k, 2) for k in range(8)] == [False, False, True, True] * 2 and [fc.in_later_group(k, 1) for k in range(4)] == [False, True, True, True]
+
+
+def _ledger_problems(rows):
+    problems = []
+    for e in fc.LEDGER:
+        for side in ("below", "above"):
+            listed = [r for r in rows if r["family"] in e[side]]
+            for r in listed:
+                got = fc.row_trace(r).get(e["comparison"])
+                if got is None or got[1] != (side == "above"):
+                    problems.append("%s: %s is not %s (%s)" % (e["boundary"], r["name"], side, got))
+            for kind in sc.KINDS:
+                if not any(r["kind"] == kind for r in listed):
+                    problems.append("%s: nothing %s for %s" % (e["boundary"], side, kind))
+    return problems
+
+
+def test_the_ledger_lands_on_both_sides_of_every_comparison():
+    rows = fc.ROWS + fc.SWEEP_ROWS
+    assert _ledger_problems(rows) == []
+    assert {e["comparison"] for e in fc.LEDGER} == {"64k", "w", "poly", "cp", "tables", "group4", "group2", "refused"}      # every comparison ladder_trace makes
+    # ... and notices a side that goes missing
+    for e in fc.LEDGER:
+        for side in ("below", "above"):
+            rest = [r for r in rows if r["family"] not in e[side]]
+            assert any(p.startswith(e["boundary"]) and ("nothing %s" % side) in p for p in _ledger_problems(rest)), (e["boundary"], side)
+    # the distance from the boundary: one step of what the shapes move the plan by there
+    for e in fc.LEDGER:
+        if e["step"] is None:
+            continue
+        limit = sc.LDS_MAX
+        for kind in sc.KINDS:
+            for side in ("below", "above"):
+                bs = [fc.row_trace(r)[e["comparison"]][0] for r in rows if r["family"] in e[side] and r["kind"] == kind]
+                assert min(abs(b - limit) for b in bs) <= e["step"], (e["boundary"], kind, side, bs)
+
+
+def test_the_restated_kd_descent_is_the_trees_own():
+    """kd_replay against HipClusterTree.descend_rows on seeded values: the same value, row, leaf and evaluation count"""
+    for r in fc.SWEEP_ROWS:
+        if r["kind"] != "kd" or r["refused"]:
+            continue
+        tree = fc.kd_tree(r)
+        values = np.random.default_rng(len(r["name"])).uniform(1.0, 2.0, len(tree.points))
+        value, row, leaf, n_eval, groups = fc.kd_replay(tree, values, r["n_cand"])
+        assert (value, row, leaf, n_eval) == tuple(tree.descend_rows(lambda rows: values[rows], r["n_cand"])), r["name"]
+        assert tree.kd_depth == r["kd"][1] and sum(len(g) == 2 for g in groups) >= r["kd"][0] * r["kd"][1]
+
+
+@pytest.mark.parametrize("name", [r["name"] for r in fc.SWEEP_ROWS if not r["refused"]])
+def test_every_sweep_row_is_conditioned_for_the_oracle(name):
+    """Any two values the search compares among themselves -- a node's children, right against left at every KD step, a descent's heap,
+    the descents of a leaf, the leaves' results -- are more than 1000 tolerances apart by the oracle's objective: a device value within
+    the tolerance descends the same way.  (A refused row launches nothing: it has no descent to condition.)"""
+    r = fc.BY_NAME[name]
+    o = fc.oracle_of(r)
+    assert np.isfinite(o["value"]) and np.all(np.isfinite(o["values"]))
+    if o["groups"] is None:         # no KD descents: the levels' gaps, as test_every_row_is_conditioned_for_the_oracle takes them
+        assert len(o["gaps"]) == 1
+        for level, kept_dropped, best_second, largest in o["gaps"]:
+            need = 1000.0 * fc.tolerance(r, largest)
+            print("%s level %d: kept-dropped %.3g, best-second %.3g, needed %.3g" % (name, level, kept_dropped, best_second, need))
+            assert kept_dropped > need and best_second > need, (name, level, kept_dropped, best_second, need)
+        return
+    gap, largest = fc.smallest_gap(o["groups"])
+    need = 1000.0 * fc.tolerance(r, largest)
+    print("%s: smallest gap %.3g over %d comparisons' values, needed %.3g; value %.15g at row %d" % (name, gap, len(o["groups"]), need, o["value"], o["row"]))
+    assert gap > need, (name, gap, need)

@@ -155,7 +155,7 @@ extern "C" int mg_dtw_pair_costs(mg_context *ctx, const double *clouds_dev, cons
     if (ref_indices) MG_HIP_CHECK(hipMemcpyAsync(blk.extra, ref_indices, (size_t)n_refs * 8, hipMemcpyHostToDevice, ctx->stream));
     dtw_launch_nonfinite(ctx, clouds_dev, offsets[n_motions] * 3 * (int64_t)n_joints, blk.flag);
     int32_t pass_rows = PAIRS_PASS_ROWS;
-    while (pairs_lds_doubles(n_joints, pass_rows, (int32_t)longest_ref) * 8 > PAIRS_LDS_BYTES) pass_rows /= 2;   // 32 at J = 64, and from J = 59 on when a reference motion has 1024 frames
+    while (pairs_lds_doubles(n_joints, pass_rows, (int32_t)longest_ref) * 8 > PAIRS_LDS_BYTES) pass_rows /= 2;   // 32 at J = 64, and from J = 58 on when a reference motion has 1024 frames
     const size_t lds = pairs_lds_doubles(n_joints, pass_rows, (int32_t)longest_ref) * 8;
     if (lds > 64 * 1024)
         MG_HIP_CHECK(mg_lds_opt_in(PAIRS_LDS_BYTES, dtw_pair_costs_kernel));

@@ -555,6 +555,52 @@ int mg_score_trajectory_points(mg_primitive *prim, const mg_trajectory *trajecto
 int mg_trajectory_closest_points(mg_primitive *prim, const mg_trajectory *trajectory, const double *points_dev, int64_t n_samples, int32_t n_times,
                                  double min_u, double *params_dev, double *distances_dev, int32_t *evaluations_dev);
 
+/* ---- arc-length queries on a trajectory (csrc/mg_trajectory_arc.hip) --------------------------------------------------------------
+ * What a planner asks of ParameterizedSpline between the scoring launches (constraints/spatial_constraints/splines/
+ * parameterized_spline.py), for a batch, on the tables of any of the three spline types.  Every device result has the bits of
+ * its NumPy statement in morphablegraphs_amd/spline_types.py (point_by_arc_length_host, tangent_at_arc_length_host,
+ * angle_at_arc_length_2d_host, arc_length_of_point_host); the reference's own numbers are in tests/golden/trajectory_arc_queries.npz.
+ *
+ * The parameters the point look-up scans, as the reference forms them (u = 0; u += 1.0 / granularity while u <= 1.0: granularity or
+ * granularity + 1 sums, as they round): built once on the host when the trajectory is created, kept on the device beside its
+ * tables.  u_host (NULL, or room for granularity + 1 doubles) receives them, n_samples (NULL or a pointer) their number. */
+int mg_trajectory_sample_parameters(const mg_trajectory *trajectory, double *u_host, int32_t *n_samples);
+
+/* query_point_by_absolute_arc_length (:131-155), get_tangent_at_arc_length (:186-207) and the angle of get_angle_at_arc_length_2d
+ * (:217-240) for n arc lengths arc_dev (n) float64, one lane per query; any of the outputs may be NULL, not all of them:
+ *   points_dev (n, 3)    the point at the arc length; above the full arc length the last control point
+ *   tangents_dev (n, 3)  (p(arc + r) - p(arc - r)) / |.| with r = eval_range (the reference's default: 0.5), r += 0.1 while the two
+ *                        points coincide, as the reference widens it; the norm is sqrt(x x + y y + z z), summed in that order
+ *   angles_dev (n)       degrees between (tangent x, tangent z) and reference_dir (2 doubles on the host, required with angles_dev),
+ *                        both normalised: acos of their dot product by the fdlibm statement (the host statement is the same one, so
+ *                        the bits agree), times 180 / pi; NaN where rounding takes the dot product outside [-1, 1] (the reference
+ *                        raises there)
+ * The widening is bounded by MG_ARC_MAX_WIDENINGS rounds: a row that exhausts them (a query more than about a hundred units past the
+ * end of the path, or a path of coinciding points) makes the CALL return MG_ERR_UNSUPPORTED, its tangent and angle rows are NaN --
+ * never an approximate answer.  Only calls that ask for tangents or angles wait for the launch (they read that flag back).  A
+ * non-finite arc length gives NaN rows.  eval_range must be finite and >= 0.  n == 0 returns MG_OK and launches nothing. */
+#define MG_ARC_MAX_WIDENINGS 1024
+int mg_trajectory_points_by_arc_length(mg_primitive *prim, const mg_trajectory *trajectory, const double *arc_dev, int64_t n, double eval_range,
+                                       double *points_dev, double *tangents_dev, double *angles_dev, const double *reference_dir);
+
+/* get_absolute_arc_length_of_point (:242-273) for n points points_dev (n, 3) float64, one wave per point: over the parameters above,
+ * among those whose absolute arc length (arc_length_map.py:73-90, restated with its index rounding and its end case) is > the
+ * point's min_arc_dev entry (NULL: 0 for every point), the FIRST strict minimum of the distance sqrt(dx dx + dy dy + dz dz) -- products and
+ * sums rounded in that order, no contraction; lanes stride over the parameters and reduce on (distance, index), so the smallest
+ * index wins among equal distances whatever the order of reduction.  arc_out_dev (n): the arc length at that parameter, -1 where no
+ * parameter qualifies (min_arc at or above the full arc length, a point with a non-finite coordinate); min_point_dev (n, 3) or NULL:
+ * the curve's point there, the row left UNTOUCHED where the result is -1; min_index_dev (n) int32 or NULL: the parameter's index, -1.
+ * The three tables stand in LDS where they fit 64 KiB, else they are read from global memory: the same bits.  Asynchronous on the
+ * context's stream.  n == 0 returns MG_OK and launches nothing. */
+int mg_trajectory_arc_length_of_points(mg_primitive *prim, const mg_trajectory *trajectory, const double *points_dev, const double *min_arc_dev, int64_t n,
+                                       double *arc_out_dev, double *min_point_dev, int32_t *min_index_dev);
+
+/* The curve's points at n parameters u_dev (n), each taken no further than its u_max_dev entry where u_max_dev is not NULL:
+ * points_dev (n, 3) -- what stands between mg_trajectory_closest_points (parameters) and mg_trajectory_arc_length_of_points (points)
+ * when a walk's travelled arc length is advanced without a download.  One lane per parameter, asynchronous. */
+int mg_trajectory_points_at_parameters(mg_primitive *prim, const mg_trajectory *trajectory, const double *u_dev, const double *u_max_dev, int64_t n,
+                                       double *points_dev);
+
 /* Constraints that walk a joint through EVERY frame of a candidate (mg_frame_constraints.hip), on float64 frames and joint tracks
  * that are on the device already (mg_back_project_frames_f64, mg_joint_positions):
  *

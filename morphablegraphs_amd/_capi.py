@@ -95,6 +95,7 @@ EXPORTED_SYMBOLS = [
     "mg_primitive_create", "mg_primitive_destroy", "mg_primitive_info", "mg_primitive_info2", "mg_primitive_root_mode", "mg_primitive_get_precisions_cholesky",
     "mg_time_function_canonical", "mg_time_function_canonical_host", "mg_time_function_sample", "mg_time_function_sample_rows", "mg_back_project_frames_at",
     "mg_trajectory_create", "mg_trajectory_create_typed", "mg_trajectory_spline_type", "mg_trajectory_tables", "mg_trajectory_destroy", "mg_score_trajectory", "mg_score_trajectory_chained", "mg_score_trajectories", "mg_score_trajectory_points", "mg_trajectory_closest_points", "mg_trajectory_plan", "mg_joint_positions",
+    "mg_trajectory_sample_parameters", "mg_trajectory_points_by_arc_length", "mg_trajectory_arc_length_of_points", "mg_trajectory_points_at_parameters",
     "mg_time_grid_create", "mg_time_grid_destroy", "mg_primitive_canonical_grid", "mg_time_grid_size",
     "mg_time_grid_get_tables",
     "mg_back_project_frames", "mg_back_project_frames_f64", "mg_back_project_coeffs", "mg_spline_evaluate",
@@ -368,6 +369,10 @@ def load_library(path=None):
         "mg_score_trajectory_points": [vp, vp, vp, i64, i32, dbl, dbl, vp, i32, vp],
         "mg_trajectory_closest_points": [vp, vp, vp, i64, i32, dbl, vp, vp, vp],
         "mg_trajectory_plan": [vp, i32, i32, i32, i64, i64, i32, vp],
+        "mg_trajectory_sample_parameters": [vp, vp, C.POINTER(C.c_int32)],
+        "mg_trajectory_points_by_arc_length": [vp, vp, vp, i64, dbl, vp, vp, vp, vp],
+        "mg_trajectory_arc_length_of_points": [vp, vp, vp, vp, i64, vp, vp, vp],
+        "mg_trajectory_points_at_parameters": [vp, vp, vp, vp, i64, vp],
         "mg_align_frames": [vp, vp, i64, i32, vp, i32, C.POINTER(AlignmentDesc)],
         "mg_frame_constraint_width": [C.POINTER(FrameConstraintDesc), i32],
         "mg_score_frame_constraint": [vp, C.POINTER(FrameConstraintDesc), vp, i64, i32, i32, vp, i32, vp],
@@ -1016,6 +1021,72 @@ class Trajectory(object):
         poly, arc = np.empty(n_seg.value * 12 + 3), np.empty(G.value + 1)
         _check(self.prim.lib.mg_trajectory_tables(self.handle, poly.ctypes.data_as(C.c_void_p), arc.ctypes.data_as(C.c_void_p), None, None, None))
         return poly, arc, full.value
+
+    def sample_parameters(self):
+        """mg_trajectory_sample_parameters: the parameters arc_length_of_points scans (u += 1.0 / granularity while u <= 1.0)"""
+        n = C.c_int32()
+        _check(self.prim.lib.mg_trajectory_sample_parameters(self.handle, None, C.byref(n)))
+        us = np.empty(n.value)
+        _check(self.prim.lib.mg_trajectory_sample_parameters(self.handle, us.ctypes.data_as(C.c_void_p), None))
+        return us
+
+    # ---- the arc-length queries (mg_trajectory_arc.hip); the _dev forms take device pointers and leave the results on the device ----
+    def points_by_arc_length_dev(self, arcs_dev, n, points_dev=None, tangents_dev=None, angles_dev=None, reference_dir=None, eval_range=0.5):
+        """mg_trajectory_points_by_arc_length on device arrays: arcs_dev (n) -> points_dev (n, 3), tangents_dev (n, 3), angles_dev (n),
+        each optional.  Waits for the launch only when tangents or angles are asked for."""
+        ref = None if reference_dir is None else (C.c_double * 2)(float(reference_dir[0]), float(reference_dir[1]))
+        ptr = lambda b: _dev_ptr(b) if b is not None else None
+        _check(self.prim.lib.mg_trajectory_points_by_arc_length(self.prim.handle, self.handle, ptr(arcs_dev), int(n), float(eval_range), ptr(points_dev),
+                                                                ptr(tangents_dev), ptr(angles_dev), ref))
+
+    def points_by_arc_length(self, arcs, tangents=False, reference_dir=None, eval_range=0.5):
+        """ParameterizedSpline.query_point_by_absolute_arc_length for arcs (n): points (n, 3); tangents=True: (points, unit tangents
+        (n, 3)) as get_tangent_at_arc_length gives them; reference_dir (2,): (points, tangents, angles in degrees (n)) as
+        get_angle_at_arc_length_2d does."""
+        a = np.ascontiguousarray(arcs, dtype=np.float64).reshape(-1)
+        n, ctx = len(a), self.prim.ctx
+        want_t, want_a = bool(tangents) or reference_dir is not None, reference_dir is not None
+        if n == 0:
+            out = (np.empty((0, 3)),) + ((np.empty((0, 3)),) if want_t else ()) + ((np.empty(0),) if want_a else ())
+            return out if len(out) > 1 else out[0]
+        with ctx.buffers() as bufs:
+            d_a, d_p = bufs.upload(a), bufs.malloc(n * 24)
+            d_t = bufs.malloc(n * 24) if want_t else None
+            d_g = bufs.malloc(n * 8) if want_a else None
+            self.points_by_arc_length_dev(d_a, n, d_p, d_t, d_g, reference_dir, eval_range)
+            out = (ctx.download(d_p, (n, 3), np.float64),)
+            if want_t:
+                out += (ctx.download(d_t, (n, 3), np.float64),)
+            if want_a:
+                out += (ctx.download(d_g, (n,), np.float64),)
+        return out if len(out) > 1 else out[0]
+
+    def arc_length_of_points_dev(self, points_dev, n, arc_out_dev, min_arc_dev=None, min_point_dev=None, min_index_dev=None):
+        """mg_trajectory_arc_length_of_points on device arrays: points_dev (n, 3), min_arc_dev (n) or None -> arc_out_dev (n),
+        min_point_dev (n, 3) and min_index_dev (n) int32, both optional.  Asynchronous."""
+        ptr = lambda b: _dev_ptr(b) if b is not None else None
+        _check(self.prim.lib.mg_trajectory_arc_length_of_points(self.prim.handle, self.handle, ptr(points_dev), ptr(min_arc_dev), int(n), ptr(arc_out_dev),
+                                                                ptr(min_point_dev), ptr(min_index_dev)))
+
+    def arc_length_of_points(self, points, min_arc_length=None):
+        """ParameterizedSpline.get_absolute_arc_length_of_point for points (n, 3): (arc lengths (n), the curve's points there (n, 3),
+        the parameters' indices (n) int32); min_arc_length: None (0), a number or (n).  Where no parameter qualifies the arc length
+        and the index are -1 and the point's row is NaN."""
+        P = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+        n, ctx = len(P), self.prim.ctx
+        if n == 0:
+            return np.empty(0), np.empty((0, 3)), np.empty(0, dtype=np.int32)
+        with ctx.buffers() as bufs:
+            d_p, d_o, d_i = bufs.upload(P), bufs.malloc(n * 8), bufs.malloc(n * 4)
+            d_q = bufs.upload(np.full((n, 3), np.nan))
+            d_m = None if min_arc_length is None else bufs.upload(np.ascontiguousarray(np.broadcast_to(np.asarray(min_arc_length, dtype=np.float64), (n,))))
+            self.arc_length_of_points_dev(d_p, n, d_o, d_m, d_q, d_i)
+            return ctx.download(d_o, (n,), np.float64), ctx.download(d_q, (n, 3), np.float64), ctx.download(d_i, (n,), np.int32)
+
+    def points_at_parameters_dev(self, u_dev, n, points_dev, u_max_dev=None):
+        """mg_trajectory_points_at_parameters on device arrays: u_dev (n), each no further than u_max_dev (n) where given -> points_dev (n, 3)"""
+        _check(self.prim.lib.mg_trajectory_points_at_parameters(self.prim.handle, self.handle, _dev_ptr(u_dev), _dev_ptr(u_max_dev) if u_max_dev is not None else None,
+                                                                int(n), _dev_ptr(points_dev)))
 
     def close(self):
         if getattr(self, "handle", None) and self.prim.handle and self.prim.ctx.handle:

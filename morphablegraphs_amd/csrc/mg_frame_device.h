@@ -52,32 +52,10 @@ __device__ __forceinline__ void mg_fc_point(const mg_fc_traj &t, const double *p
     for (int d = 0; d < 3; d++) p[d] = ((A[d] * tt + A[3 + d]) * tt + A[6 + d]) * tt + A[9 + d];
 }
 
-// ParameterizedSpline.query_point_by_absolute_arc_length (splines/parameterized_spline.py:131-155): beyond the full arc length the last
-// control point; else the table entries bounding the relative arc length, their parameters interpolated linearly
-// (arc_length_map.py:97-160)
+// ParameterizedSpline.query_point_by_absolute_arc_length on a list's trajectory: the one statement of it, mg_traj_point_by_arc
+// (mg_traj_device.h), which the arc-length queries (mg_trajectory_arc.hip) run as well
 __device__ __forceinline__ void mg_fc_point_by_arc(const mg_fc_traj &t, const double *poly, const double *arcs, double arc, double *p) {
-    if (arc > t.full || !(t.full > 0.0)) {
-        const double *q = poly + (size_t)t.n_seg * 12;
-        p[0] = q[0]; p[1] = q[1]; p[2] = q[2];
-        return;
-    }
-    const double rel = arc / t.full;
-    double u;
-    if (rel <= arcs[0]) {
-        u = 0.0;
-    } else if (rel >= arcs[t.G]) {
-        u = 1.0;
-    } else {
-        int lo = 0, hi = t.G;                       // arc[lo] <= rel < arc[hi]
-        while (hi - lo > 1) {
-            const int mid = (lo + hi) >> 1;
-            if (arcs[mid] <= rel) lo = mid; else hi = mid;
-        }
-        const double l0 = arcs[lo], l1 = arcs[lo + 1];
-        const double u0 = lo / (double)t.G, u1 = (lo + 1) / (double)t.G;
-        u = l0 == rel ? u0 : u0 + (rel - l0) / (l1 - l0) * (u1 - u0);
-    }
-    mg_fc_point(t, poly, u, p);
+    mg_traj_point_by_arc(poly, arcs, t.n_seg, t.G, t.full, arc, p);
 }
 
 __device__ __forceinline__ void mg_fc_rotmat(const double *q, double *m) {

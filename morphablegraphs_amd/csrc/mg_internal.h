@@ -301,6 +301,8 @@ struct mg_trajectory {
     double *d_poly = nullptr;    // [n_seg][4][3]: point(t) = ((A0 t + A1) t + A2) t + A3 on a segment; then the last control point [3]
     double *d_arc = nullptr;     // [granularity + 1]: relative arc length at u = k / granularity (arc_length_map.py:45-71)
     double full_arc = 0.0;
-    double *d_E = nullptr;       // [rows][L]: root coefficient rows (i * 3 + d), then the first control point's root quaternion (4 rows)
+    double *d_uk = nullptr;      // [n_uk]: the parameters get_absolute_arc_length_of_point scans (parameterized_spline.py:251-268): u = 0, then
+    int32_t n_uk = 0;            // u += 1.0 / granularity while u <= 1.0 -- the sums as they round, granularity or granularity + 1 of them
+    double *d_E = nullptr;      // [rows][L]: root coefficient rows (i * 3 + d), then the first control point's root quaternion (4 rows)
     double *d_mean = nullptr;    // [rows]
 };

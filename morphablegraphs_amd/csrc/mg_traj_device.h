@@ -31,6 +31,36 @@ MG_HD __forceinline__ double mg_traj_d2(const double *poly, int n_seg, double u,
     return x * x + y * y + z * z;
 }
 
+// ParameterizedSpline.query_point_by_absolute_arc_length (splines/parameterized_spline.py:131-155) on a trajectory's two tables (poly,
+// and arcs: G + 1 relative arc lengths at k / G, `full` the length they are relative to): beyond the full arc length the last control
+// point; else the table entries bounding the relative arc length, their parameters interpolated linearly (arc_length_map.py:97-160).
+// The one statement of it: the per-frame constraints that look their targets up by walked arc length (mg_frame_device.h) and the
+// arc-length queries (mg_trajectory_arc.hip) both call this; spline_types.py point_by_arc_length_host states it in Python.
+MG_HD __forceinline__ void mg_traj_point_by_arc(const double *poly, const double *arcs, int n_seg, int G, double full, double arc, double *p) {
+    if (arc > full || !(full > 0.0)) {
+        const double *q = poly + (size_t)n_seg * 12;
+        p[0] = q[0]; p[1] = q[1]; p[2] = q[2];
+        return;
+    }
+    const double rel = arc / full;
+    double u;
+    if (rel <= arcs[0]) {
+        u = 0.0;
+    } else if (rel >= arcs[G]) {
+        u = 1.0;
+    } else {
+        int lo = 0, hi = G;                         // arc[lo] <= rel < arc[hi]
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (arcs[mid] <= rel) lo = mid; else hi = mid;
+        }
+        const double l0 = arcs[lo], l1 = arcs[lo + 1];
+        const double u0 = lo / (double)G, u1 = (lo + 1) / (double)G;
+        u = l0 == rel ? u0 : u0 + (rel - l0) / (l1 - l0) * (u1 - u0);
+    }
+    mg_traj_point(poly, n_seg, u, p);
+}
+
 // squared distance, and its first and second derivative in u (the segment's cubic differentiated; false past the last segment)
 __device__ __forceinline__ bool mg_traj_d2_derivs(const double *poly, int n_seg, double u, const double *q, double *f0, double *f1, double *f2) {
     const double scaled = n_seg * u;

@@ -394,6 +394,7 @@ extern "C" void mg_trajectory_destroy(mg_trajectory *t) {
     (void)hipFree(t->d_E);
     (void)hipFree(t->d_mean);
     (void)hipFree(t->d_arc);
+    (void)hipFree(t->d_uk);
     delete t;
 }
 
@@ -479,8 +480,18 @@ static int mg_traj_finish(mg_primitive *p, const std::vector<double> &poly, int3
         t->full_arc = acc;
         if (acc > 0.0) for (double &v : arc) v /= acc;
     }
+    // the parameters get_absolute_arc_length_of_point scans (parameterized_spline.py:251-268): repeated addition, not k / granularity --
+    // the sums drift, so how many there are and every one of them is decided by these roundings (the same in any IEEE double
+    // arithmetic, independent of the curve); mg_trajectory_arc.hip reads them, it never forms a parameter itself
+    std::vector<double> uk;
+    {
+        const double step_size = 1.0 / granularity;
+        for (double u = 0.0; u <= 1.0 && uk.size() <= (size_t)granularity + 1; u += step_size) uk.push_back(u);
+        t->n_uk = (int32_t)uk.size();
+    }
     int rc = mg_traj_upload(poly, &t->d_poly);
     if (rc == MG_OK) rc = mg_traj_upload(arc, &t->d_arc);
+    if (rc == MG_OK) rc = mg_traj_upload(uk, &t->d_uk);
     if (rc == MG_OK) rc = mg_traj_upload(E, &t->d_E);
     if (rc == MG_OK) rc = mg_traj_upload(mean, &t->d_mean);
     if (rc != MG_OK) { mg_trajectory_destroy(t); return rc; }

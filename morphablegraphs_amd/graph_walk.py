@@ -614,6 +614,19 @@ class HipGraphWalk(object):
             st.arc_length = float(travelled)
         return lengths
 
+    def advance_along_trajectory(self, trajectory, travelled, look_ahead):
+        """GraphWalkPlanner._update_path's rule (graph_walk_planner.py:269-273) for this walk: the arc length of `trajectory` (a
+        _capi.Trajectory) travelled once the walk's last frame is taken into account, from the arc length travelled before it.
+        The last frame's root position is read where the frames are -- on the device no frame is downloaded
+        (trajectory_queries.advance_along_trajectory)."""
+        from .trajectory_queries import advance_along_trajectory
+        if self._n_frames == 0:
+            return float(travelled)
+        store = self._store()
+        if self._is_host:
+            return float(advance_along_trajectory(trajectory, store.read(1, self._n_frames - 1)[:, :3], travelled, look_ahead)[0])
+        return float(advance_along_trajectory(trajectory, store.address(self._n_frames - 1), travelled, look_ahead, n=1)[0])
+
     def get_global_spatial_parameter_vector(self, start_step=0):
         out = []
         for step in self.steps[start_step:]:

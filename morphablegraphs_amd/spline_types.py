@@ -13,6 +13,7 @@ t = n_seg u - floor(n_seg u), point(t) = ((A0 t + A1) t + A2) t + A3; then the l
 Pure Python floats in the statement order of the C++ (which is compiled without contraction): the device table is expected to
 equal this one bit for bit.  Needs NumPy only -- no library, no GPU."""
 import math
+import struct
 
 import numpy as np
 
@@ -155,27 +156,161 @@ def arc_length_table_host(poly, granularity=1000):
     return np.array(arc, dtype=np.float64), acc
 
 
-def point_by_arc_length_host(poly, arcs, full, arc):
-    """mg_fc_point_by_arc (csrc/mg_frame_constraints.hip): ParameterizedSpline.query_point_by_absolute_arc_length
-    (parameterized_spline.py:131-155, arc_length_map.py:97-160) on the two tables"""
-    n_seg = (len(poly) - 3) // 12
+def parameter_by_arc_length_host(arcs, full, arc):
+    """The parameter mg_traj_point_by_arc (csrc/mg_traj_device.h) evaluates the curve at: the table entries bounding the relative
+    arc length, their parameters interpolated linearly (arc_length_map.py:97-160); None beyond the full arc length, where the
+    query returns the last control point."""
     G = len(arcs) - 1
+    arc, full = float(arc), float(full)
     if arc > full or not full > 0.0:
-        return np.array([float(poly[n_seg * 12 + d]) for d in range(3)])
+        return None
     rel = arc / full
     if rel <= arcs[0]:
-        u = 0.0
-    elif rel >= arcs[G]:
-        u = 1.0
-    else:
-        lo, hi = 0, G
-        while hi - lo > 1:
-            mid = (lo + hi) >> 1
-            if arcs[mid] <= rel:
-                lo = mid
-            else:
-                hi = mid
-        l0, l1 = float(arcs[lo]), float(arcs[lo + 1])
-        u0, u1 = lo / float(G), (lo + 1) / float(G)
-        u = u0 if l0 == rel else u0 + (rel - l0) / (l1 - l0) * (u1 - u0)
+        return 0.0
+    if rel >= arcs[G]:
+        return 1.0
+    lo, hi = 0, G
+    while hi - lo > 1:
+        mid = (lo + hi) >> 1
+        if arcs[mid] <= rel:
+            lo = mid
+        else:
+            hi = mid
+    l0, l1 = float(arcs[lo]), float(arcs[lo + 1])
+    u0, u1 = lo / float(G), (lo + 1) / float(G)
+    return u0 if l0 == rel else u0 + (rel - l0) / (l1 - l0) * (u1 - u0)
+
+
+def point_by_arc_length_host(poly, arcs, full, arc):
+    """mg_traj_point_by_arc (csrc/mg_traj_device.h): ParameterizedSpline.query_point_by_absolute_arc_length
+    (parameterized_spline.py:131-155, arc_length_map.py:97-160) on the two tables"""
+    n_seg = (len(poly) - 3) // 12
+    u = parameter_by_arc_length_host(arcs, full, arc)
+    if u is None:
+        return np.array([float(poly[n_seg * 12 + d]) for d in range(3)])
     return polynomial_point(poly, u)
+
+
+# ---- the arc-length queries (csrc/mg_trajectory_arc.hip), statement for statement ------------------------------------------------------
+MAX_WIDENINGS = 1024        # MG_ARC_MAX_WIDENINGS
+
+
+class TangentWideningExhausted(ValueError):
+    """The two points of a tangent still coincide after MAX_WIDENINGS widenings (the library: MG_ERR_UNSUPPORTED)."""
+
+
+def sample_parameters_host(granularity):
+    """The parameters get_absolute_arc_length_of_point scans (parameterized_spline.py:251-268): u = 0, u += 1.0 / granularity while
+    u <= 1.0 -- repeated addition, so the sums drift and there are granularity or granularity + 1 of them.  What
+    mg_trajectory_sample_parameters returns."""
+    step_size = 1.0 / int(granularity)
+    us, u = [], 0.0
+    while u <= 1.0:
+        us.append(u)
+        u += step_size
+    return np.array(us, dtype=np.float64)
+
+
+def absolute_arc_length_host(arcs, full, t):
+    """mg_arc_absolute: RelativeArcLengthMap.get_absolute_arc_length (arc_length_map.py:73-90) on the table of relative arc lengths"""
+    G = len(arcs) - 1
+    t, full = float(t), float(full)
+    step_size = 1.0 / G
+    table_index = min(max(int(t / step_size), 0), G)
+    if table_index < G:
+        t_i, t_i_1 = table_index / float(G), (table_index + 1) / float(G)
+        a_i, a_i_1 = float(arcs[table_index]), float(arcs[table_index + 1])
+        arc_length = a_i + ((t - t_i) / (t_i_1 - t_i)) * (a_i_1 - a_i)
+        return arc_length * full
+    return float(arcs[table_index]) * full
+
+
+def _norm3(x, y, z):
+    return math.sqrt(x * x + y * y + z * z)
+
+
+def arc_length_of_point_host(poly, arcs, full, point, min_arc_length=0.0, us=None):
+    """mg_trajectory_arc_length_of_points for one point: ParameterizedSpline.get_absolute_arc_length_of_point
+    (parameterized_spline.py:242-273) -> (arc length, the curve's point there, the parameter's index), or (-1.0, None, -1) where no
+    parameter's arc length is > min_arc_length.  The distance is sqrt(dx dx + dy dy + dz dz) in that order; the first strict minimum
+    wins.  us: sample_parameters_host(granularity), to share between calls."""
+    if us is None:
+        us = sample_parameters_host(len(arcs) - 1)
+    q = [float(v) for v in point]
+    min_arc_length = float(min_arc_length)
+    min_distance, min_k, min_point = math.inf, -1, None
+    for k, u in enumerate(us):
+        if absolute_arc_length_host(arcs, full, u) > min_arc_length:
+            p = polynomial_point(poly, u)
+            distance = _norm3(float(p[0]) - q[0], float(p[1]) - q[1], float(p[2]) - q[2])
+            if distance < min_distance:
+                min_distance, min_k, min_point = distance, k, p
+    if min_k < 0:
+        return -1.0, None, -1
+    return absolute_arc_length_host(arcs, full, us[min_k]), min_point, min_k
+
+
+def tangent_at_arc_length_host(poly, arcs, full, arc, eval_range=0.5):
+    """mg_trajectory_points_by_arc_length's tangent: ParameterizedSpline.get_tangent_at_arc_length (parameterized_spline.py:186-207)
+    -> (start point, unit direction); the chord over [arc - r, arc + r], r += 0.1 while its ends coincide, at most MAX_WIDENINGS
+    times (then TangentWideningExhausted)."""
+    arc, eval_range = float(arc), float(eval_range)
+    start = point_by_arc_length_host(poly, arcs, full, arc)
+    for _ in range(MAX_WIDENINGS + 1):
+        p1 = point_by_arc_length_host(poly, arcs, full, arc - eval_range)
+        p2 = point_by_arc_length_host(poly, arcs, full, arc + eval_range)
+        d = [float(p2[0]) - float(p1[0]), float(p2[1]) - float(p1[1]), float(p2[2]) - float(p1[2])]
+        magnitude = _norm3(d[0], d[1], d[2])
+        eval_range += 0.1
+        if magnitude != 0.0:
+            return start, np.array([d[0] / magnitude, d[1] / magnitude, d[2] / magnitude])
+    raise TangentWideningExhausted("the tangent's two points coincide at arc length %r" % (arc,))
+
+
+def _clear_low_word(x):
+    return struct.unpack("<d", struct.pack("<Q", struct.unpack("<Q", struct.pack("<d", x))[0] & 0xffffffff00000000))[0]
+
+
+def acos_host(x):
+    """mg_arc_acos: acos as fdlibm states it (e_acos.c), in plain IEEE operations and sqrt; NaN for |x| > 1"""
+    pio2_hi, pio2_lo, pi = 1.57079632679489655800e+00, 6.12323399573676603587e-17, 3.14159265358979311600e+00
+    pS = (1.66666666666666657415e-01, -3.25565818622400915405e-01, 2.01212532134862925881e-01, -4.00555345006794114027e-02,
+          7.91534994289814532176e-04, 3.47933107596021167570e-05)
+    qS = (-2.40339491173441421878e+00, 2.02094576023350569471e+00, -6.88283971605453293030e-01, 7.70381505559019352791e-02)
+    x = float(x)
+    ax = abs(x)
+    if not ax < 1.0:
+        if x == 1.0:
+            return 0.0
+        if x == -1.0:
+            return pi + 2.0 * pio2_lo
+        return math.nan
+    z = x * x if ax < 0.5 else ((1.0 + x) * 0.5 if x < 0.0 else (1.0 - x) * 0.5)
+    p = z * (pS[0] + z * (pS[1] + z * (pS[2] + z * (pS[3] + z * (pS[4] + z * pS[5])))))
+    q = 1.0 + z * (qS[0] + z * (qS[1] + z * (qS[2] + z * qS[3])))
+    r = p / q
+    if ax < 0.5:
+        return pio2_hi - (x - (pio2_lo - r * x))
+    s = math.sqrt(z)
+    if x < 0.0:
+        w = r * s - pio2_lo
+        return pi - 2.0 * (s + w)
+    df = _clear_low_word(s)
+    c = (z - df * df) / (s + df)
+    w = r * s + c
+    return 2.0 * (df + w)
+
+
+def angle_at_arc_length_2d_host(poly, arcs, full, arc, reference_vector, eval_range=0.5):
+    """mg_trajectory_points_by_arc_length's angle: ParameterizedSpline.get_angle_at_arc_length_2d (parameterized_spline.py:217-240)
+    -> (start point, unit tangent, degrees between (tangent x, tangent z) and the 2-D reference vector)"""
+    start, tangent = tangent_at_arc_length_host(poly, arcs, full, arc, eval_range)
+    r0, r1 = float(reference_vector[0]), float(reference_vector[1])
+    na = math.sqrt(r0 * r0 + r1 * r1)
+    a0, a1 = r0 / na, r1 / na
+    t0, t2 = float(tangent[0]), float(tangent[2])
+    nb = math.sqrt(t0 * t0 + t2 * t2)
+    if na == 0.0 or nb == 0.0:           # (a zero reference or a vertical tangent: the device's 0 / 0)
+        return start, tangent, math.nan
+    b0, b1 = t0 / nb, t2 / nb
+    return start, tangent, acos_host(a0 * b0 + a1 * b1) * (180.0 / math.pi)

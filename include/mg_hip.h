@@ -1107,6 +1107,22 @@ int mg_pca_project(mg_context *ctx, const double *x_dev, const double *vt_dev, i
 int mg_pca_backproject(mg_context *ctx, const double *low_dev, const double *vt_dev, const double *mean_dev, int64_t n, int64_t p,
                        int64_t l, double *high_dev);
 
+/* The LEADING principal components of the device matrix a_dev (n, p), for shapes beyond mg_pca_fit's short-side limit: as many as
+ * sklearn's PCA(n_components = fraction) keeps, searchsorted(cumsum(ratio), fraction, side = "right") + 1 with ratio = s^2 / |a - mean|_F^2.
+ * Blocked subspace iteration on (a - mean)^T (a - mean): Y = Xc Q^T and Z = Y^T Xc on the float64 MFMA GEMMs, the block re-orthonormalised
+ * and ordered by mg_pca_fit(Z, centre = 0), until every kept component's residual |Xc^T Xc v - s^2 v| is at most tol s_1^2 or
+ * max_iterations rounds have run (tol <= 0: 64 eps sqrt(max(n, p)); max_iterations <= 0: 100).  The block starts at 12 rows and doubles
+ * until it captures more than `fraction` with four rows to spare.  mean (host, p): the column means as mg_pca_fit adds them; centred_dev
+ * (device, n, p) = a - mean; *k: the components kept; singular_values, ratios (host, k_cap), vt (host, (k_cap, p)): their first *k
+ * entries / rows, descending, each row's entry of largest magnitude positive; iterations: rounds run; status: 1 converged, 2 stopped at
+ * the cap (the values are then the last round's).  Every sum runs in an order fixed by the shape: two calls give the same bits.
+ * Synchronises.  MG_ERR_INVALID_ARGUMENT: NULL, n < 2, fraction outside (0, 1), non-finite values, a matrix without variance, or
+ * *k > k_cap (*k then holds the count to ask again with).  MG_ERR_UNSUPPORTED only where an index would overflow -- n >= 2^24, p > 2^20,
+ * 2^31 or more 16 x 16 tiles -- or where more than 4096 components (mg_pca_fit's limit for the block) would have to be kept. */
+int mg_pca_fit_leading(mg_context *ctx, const double *a_dev, int64_t n, int64_t p, double fraction, double tol, int32_t max_iterations,
+                       double *centred_dev, double *mean, int32_t k_cap, int32_t *k, double *singular_values, double *vt, double *ratios,
+                       int32_t *iterations, int32_t *status);
+
 /* ---- temporal alignment: exact dynamic time warping of motions against one reference motion (reference construction/dtw.py),
  * float64, synchronising, bit-reproducible.  Motions are ragged: motion n has F_n = offsets[n + 1] - offsets[n] frames and its rows
  * start at row offsets[n] of a table; offsets is a HOST array of n_motions + 1 entries, offsets[0] = 0, rising.
@@ -1330,7 +1346,7 @@ int mg_walk_time_table_uploads(mg_context *ctx, int64_t *uploads);   /* mg_conte
  * of mg_options_step's one-launch path, mg_cluster_tree_search, mg_walk_frames, mg_score_walk_residuals, mg_score_walk_time and
  * mg_step_lengths, of mg_feature_points, of mg_feature_points_warped and of mg_mixture_scores.  mg_context_table_uploads: how often table `which` of the context went to the device so far. */
 enum { MG_TABLE_FUSED = 0, MG_TABLE_TREE = 1, MG_TABLE_WALK = 2, MG_TABLE_WALK_SCORE = 3, MG_TABLE_WALK_TIME = 4, MG_TABLE_STEP_LENGTH = 5,
-       MG_TABLE_FEATURE_POINTS = 6, MG_TABLE_FEATURE_POINTS_WARPED = 7, MG_TABLE_MIXTURE_SCORES = 8, MG_TABLE_COUNT = 9 };
+       MG_TABLE_FEATURE_POINTS = 6, MG_TABLE_FEATURE_POINTS_WARPED = 7, MG_TABLE_MIXTURE_SCORES = 8, MG_TABLE_POINT_CLOUDS = 9, MG_TABLE_COUNT = 10 };
 int mg_context_table_uploads(mg_context *ctx, int which, int64_t *uploads);
 
 /* Step lengths without frames in memory, ONE launch for every candidate of every item (csrc/mg_step_length.hip): what
@@ -1417,6 +1433,20 @@ typedef struct {
     double *heading_len_dev;            /* (n_samples) or NULL */
 } mg_feature_point_item;
 int mg_feature_points(int32_t n_items, const mg_feature_point_item *items, int latent_dtype);
+
+/* The point clouds a feature cluster tree's "euclidean_pca" features are made of (reference space_partitioning/features.py:133-153,
+ * map_motions_to_euclidean_space), WITHOUT frames in memory and in one launch: out_dev (n, F, n_joints, 3) float64, entry [i, f, j, :] the
+ * global position of joints[j] in frame step * (f / step) of latent row i -- a frame whose index is not a multiple of step
+ * repeats the cloud of the last one that is; each kept frame is evaluated once.  grid: the F frames' times (the cluster-tree builder
+ * evaluates the integer canonical frames 0 .. F - 1, `spline.evaluate(frame_idx)`); NULL: the primitive's canonical grid.  latents_dev: n rows of ld elements (float32 or
+ * float64), the primitive's n_components first.  Bit for bit what mg_back_project_frames_f64 on the same grid followed by
+ * mg_joint_positions gives.  Does not synchronise; allocates nothing but the context's cached table (MG_TABLE_POINT_CLOUDS).
+ * MG_ERR_INVALID_ARGUMENT: NULL pointers, n < 0, ld below n_components, step < 1, n_joints outside 1 .. MG_FEATURE_POINTS_MAX_JOINTS, an
+ * incomplete skeleton, a joint out of range.  MG_ERR_UNSUPPORTED, never an approximate answer: fewer than 7 channels, chains of more
+ * than MG_MAX_CHAIN links, a skeleton channel beyond the primitive's, control points that do not fit LDS even with the large-LDS
+ * opt-in (4 candidates x n_basis x the channels the chains read).  n == 0: MG_OK, no launch. */
+int mg_point_cloud_features(mg_primitive *prim, const mg_time_grid *grid, const mg_skeleton_desc *skeleton, const int32_t *joints, int32_t n_joints, int32_t step,
+                            const void *latents_dev, int latent_dtype, int64_t n, int64_t ld, double *out_dev);
 
 /* Feature points of the TIME-WARPED motion, no time function and no frame in memory, ONE launch for every candidate of every item
  * (csrc/mg_feature_points.hip): what the reference's FeaturePointModel takes from back_project(s, use_time_parameters=True) -- its

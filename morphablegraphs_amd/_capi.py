@@ -40,9 +40,9 @@ MG_CONSTRAINT_VALUE_POSITION, MG_CONSTRAINT_VALUE_HEADING = 7, 8   # values of t
 PROFILE_SLOTS = {"frames": 0, "gmm_log_prob": 1, "score_constraints": 2, "argmin": 3,
                  "gmm_sample": 4, "spline_evaluate": 5, "step": 6, "options_step": 7, "joint_tracks": 8, "frame_constraints": 9, "trajectory": 10,
                  "cluster_tree_search": 11, "walk_frames": 12, "walk_time": 13, "step_lengths": 14, "feature_points": 15,
-                 "feature_points_warped": 16, "mixture_scores": 17}
+                 "feature_points_warped": 16, "mixture_scores": 17, "point_clouds": 18}
 DEVICE_TABLES = {"fused": 0, "tree": 1, "walk": 2, "walk_score": 3, "walk_time": 4, "step_length": 5, "feature_points": 6,
-                 "feature_points_warped": 7, "mixture_scores": 8}    # MG_TABLE_* (include/mg_hip.h)
+                 "feature_points_warped": 7, "mixture_scores": 8, "point_clouds": 9}    # MG_TABLE_* (include/mg_hip.h)
 MG_TREE_MAX_DEPTH, MG_TREE_MAX_CHILDREN, MG_TREE_MAX_CANDIDATES = 64, 256, 64    # include/mg_hip.h
 MG_TREE_TIE, MG_TREE_NO_RESULT, MG_TREE_OVERFLOW, MG_TREE_NO_MEAN = 1, 2, 4, 8
 MG_TREE_MAX_TRAJECTORIES = 4    # root trajectory constraints of one search (mg_cluster_tree_search_trajectories)
@@ -122,6 +122,7 @@ EXPORTED_SYMBOLS = [
     "mg_feature_points", "mg_feature_points_host", "mg_feature_points_warped", "mg_feature_points_warped_host",
     "mg_feature_mixture_create", "mg_feature_mixture_destroy", "mg_feature_mixture_info", "mg_feature_mixture_get_image",
     "mg_mixture_scores", "mg_mixture_scores_host",
+    "mg_point_cloud_features", "mg_pca_fit_leading",
 ]
 
 
@@ -473,6 +474,8 @@ def load_library(path=None):
         "mg_feature_mixture_get_image": [vp, vp, vp, vp],
         "mg_mixture_scores": [vp, i32, vp],
         "mg_mixture_scores_host": [vp, i32, vp],
+        "mg_point_cloud_features": [vp, vp, vp, vp, i32, i32, vp, i32, i64, i64, vp],
+        "mg_pca_fit_leading": [vp, vp, i64, i64, dbl, dbl, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp],
     }
     for name, argtypes in sigs.items():
         fn = getattr(lib, name)
@@ -1800,6 +1803,39 @@ def pca_backproject(ctx, low_dev, vt_dev, mean_dev, n, p, l, high_dev):
     """mg_pca_backproject: high_dev (n, p) = low_dev (n, l) . vt_dev (l, p) + mean_dev (p) (None: no mean)."""
     _check(ctx.lib.mg_pca_backproject(ctx.handle, _dev_ptr(low_dev), _dev_ptr(vt_dev), None if mean_dev is None else _dev_ptr(mean_dev),
                                       int(n), int(p), int(l), _dev_ptr(high_dev)))
+
+
+def pca_fit_leading(ctx, a_dev, n, p, centred_dev, fraction, tol=0.0, max_iterations=0, k_cap=64):
+    """mg_pca_fit_leading of the device matrix a_dev (n, p) float64: the leading principal components that sklearn's PCA(n_components=fraction)
+    keeps, by blocked subspace iteration; centred_dev receives a - mean.  tol, max_iterations: 0 = the library's.  Returns {"mean" (p,), "k",
+    "singular_values" (k,), "vt" (k, p), "ratios" (k,), "iterations", "status"}.  k_cap: room for the components at the first try; a call
+    that keeps more is repeated with the count it reported."""
+    n, p = int(n), int(p)
+    for _ in range(2):
+        k_cap = max(int(k_cap), 1)
+        mean, sv, vt, ratios = np.zeros(max(p, 1)), np.zeros(k_cap), np.zeros((k_cap, max(p, 1))), np.zeros(k_cap)
+        k, iters, status = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        rc = ctx.lib.mg_pca_fit_leading(ctx.handle, _dev_ptr(a_dev), n, p, float(fraction), float(tol), int(max_iterations), _dev_ptr(centred_dev),
+                                        _host_ptr(mean), k_cap, C.byref(k), _host_ptr(sv), _host_ptr(vt), _host_ptr(ratios), C.byref(iters), C.byref(status))
+        if rc == MG_ERR_INVALID_ARGUMENT and k.value > k_cap:
+            k_cap = k.value
+            continue
+        _check(rc)
+        kk = int(k.value)
+        return {"mean": mean, "k": kk, "singular_values": sv[:kk].copy(), "vt": vt[:kk].copy(), "ratios": ratios[:kk].copy(),
+                "iterations": int(iters.value), "status": int(status.value)}
+    _check(rc)
+
+
+def point_cloud_features_dev(prim, grid, skeleton, joint_indices, step, latents_dev, latent_dtype, n, ld, out_dev):
+    """mg_point_cloud_features: out_dev (n, F, len(joint_indices), 3) float64 <- n latent rows (ld elements each, float32 or float64) of
+    `prim` (a Primitive) on the device, at the F times of `grid` (a TimeGrid; None: the canonical grid); joint_indices:
+    skeleton.indices(joints), or None for a NULL list.  Asynchronous on the context's stream."""
+    d = skeleton.desc() if skeleton is not None else None
+    code = MG_F64 if np.dtype(latent_dtype) == np.float64 else MG_F32
+    _check(prim.lib.mg_point_cloud_features(prim.handle, prim._grid_handle(grid), C.byref(d) if d is not None else None, None if joint_indices is None else _host_ptr(joint_indices),
+                                            0 if joint_indices is None else len(joint_indices), int(step), None if latents_dev is None else _dev_ptr(latents_dev),
+                                            code, int(n), int(ld), None if out_dev is None else _dev_ptr(out_dev)))
 
 
 MG_DTW_MAX_FRAMES, MG_DTW_MAX_JOINTS = 1024, 64   # mg_dtw.hip (include/mg_hip.h)

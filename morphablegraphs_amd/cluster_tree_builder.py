@@ -502,6 +502,7 @@ class HipClusterTreeBuilder(object):
         self.output_mode = settings["output_mode"]
         self.skeleton = None
         self.joint_names = None
+        self.device_features = False       # "euclidean_pca" features on the device (mg_point_cloud_features, mg_pca_fit_leading); opt-in
         self.ctx = ctx
         self.sampler = HipClusterTreeSampler(self.n_samples)
 
@@ -514,6 +515,7 @@ class HipClusterTreeBuilder(object):
         self.only_spatial_parameters = config["only_spatial_parameters"]
         self.store_indices = config["store_data_indices_in_nodes"]
         self.use_kd_tree = config["use_kd_tree"]
+        self.device_features = bool(config.get("device_features", self.device_features))
         self.sampler.n_samples = int(self.n_samples)
 
     def _seed(self):
@@ -550,6 +552,8 @@ class HipClusterTreeBuilder(object):
 
     def _extract_features(self, motion_primitive, data):
         if self.feature_type == FEATURE_TYPE_EUCLIDEAN_PCA:
+            if self.device_features:
+                return self.sampler._extract_features(motion_primitive, data, "euclidean_pca", self.skeleton, self.joint_names, step=1, device_features=True)
             return self.sampler._extract_features(motion_primitive, data, "euclidean_pca", self.skeleton, self.joint_names, step=1)
         return self.sampler._extract_features(motion_primitive, data, "latent")
 

@@ -25,6 +25,7 @@
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
+#include <cstring>
 #include <new>
 #include <numeric>
 #include <vector>
@@ -375,5 +376,216 @@ extern "C" int mg_pca_fit(mg_context *ctx, const double *a_dev, int64_t n, int64
     }
     *n_sweeps = sweeps;
     *status = st;
+    return MG_OK;
+}
+
+// ---- mg_pca_fit_leading: the leading principal components of a matrix beyond Jacobi's short-side limit -------------------------------
+// Blocked subspace iteration on the Gram form Xc^T Xc with a block Q (b, p) of orthonormal rows:
+//   Y = Xc Q^T (n, b)      fpca_gemm_kernel, as mg_pca_project runs it
+//   Z = Y^T Xc (b, p)      fpca_gemm_ta_kernel below: row i of Z is (Xc^T Xc) q_i
+//   the host reads Z: lambda_i = q_i . z_i (the Rayleigh quotient, s_i^2), residual_i = |z_i - lambda_i q_i|, the component count
+//   Q <- the right singular vectors of Z by mg_pca_fit(Z, centre = 0): Jacobi on a short side of b, ordered, with its sign rule
+// until every kept component's residual is at most tol lambda_1, or the cap.  The block starts at FP_LEAD_START rows and doubles
+// (the rows it has, plus new start rows, re-orthonormalised by mg_pca_fit) while it captures no more than `fraction` of the variance
+// or keeps fewer than FP_LEAD_SPARE rows beyond the kept ones.  The start rows are a counter-based hash of (row, column): the same
+// for every call.  Every sum -- the column sums of squares in row order, the host's sums in index order, the MFMA's k order -- is fixed
+// by the shape alone.
+#define FP_LEAD_START 12
+#define FP_LEAD_SPARE 4
+#define FP_LEAD_MAX_ITERATIONS 100
+
+// C (M, Nc) = A^T . B with A (K, M) and B (K, Nc) row-major: one wave per 16 x 16 tile like fpca_gemm_kernel, lane l supplies
+// A^T[row l & 15][k l >> 4] = A[k][row] and B[k][col l & 15]; the k-tail and the edge tiles by a select on a clamped address.
+struct fp_gemm_ta_args {
+    const double *A, *B;
+    double *C;
+    int64_t lda, ldb, ldc;
+    int32_t M, Nc, K, tiles_n, n_tiles;
+};
+
+__global__ __launch_bounds__(FP_BLOCK) void fpca_gemm_ta_kernel(fp_gemm_ta_args g) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int tile = blockIdx.x * (FP_BLOCK / 64) + wave;
+    if (tile >= g.n_tiles) return;   // whole wave
+    const int ti = tile / g.tiles_n, tj = tile % g.tiles_n;
+    const int cl = lane & 15, q = lane >> 4;
+    const int row = ti * 16 + cl, col = tj * 16 + cl;
+    const bool rok = row < g.M, cok = col < g.Nc;
+    const double *a = g.A + (rok ? row : g.M - 1);
+    const double *b = g.B + (cok ? col : g.Nc - 1);
+    fp_f64x4 acc = {0.0, 0.0, 0.0, 0.0};
+    for (int k0 = 0; k0 < g.K; k0 += 4) {
+        const int k = k0 + q;
+        const bool kok = k < g.K;
+        const int kc = kok ? k : g.K - 1;
+        const double av = a[(int64_t)kc * g.lda], bv = b[(int64_t)kc * g.ldb];
+        acc = __builtin_amdgcn_mfma_f64_16x16x4f64((rok && kok) ? av : 0.0, (cok && kok) ? bv : 0.0, acc, 0, 0, 0);
+    }
+    if (!cok) return;
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+        const int orow = ti * 16 + q + 4 * r;
+        if (orow < g.M) g.C[(int64_t)orow * g.ldc + col] = acc[r];
+    }
+}
+
+static int fp_gemm_ta(mg_context *ctx, const double *A, const double *B, double *C, int64_t M, int64_t Nc, int64_t K, int64_t lda, int64_t ldb, int64_t ldc) {
+    fp_gemm_ta_args g;
+    g.A = A, g.B = B, g.C = C, g.lda = lda, g.ldb = ldb, g.ldc = ldc;
+    g.M = (int32_t)M, g.Nc = (int32_t)Nc, g.K = (int32_t)K;
+    const int64_t tn = (Nc + 15) / 16, tiles = ((M + 15) / 16) * tn;
+    g.tiles_n = (int32_t)tn, g.n_tiles = (int32_t)tiles;
+    hipLaunchKernelGGL(fpca_gemm_ta_kernel, dim3((unsigned)((tiles + FP_BLOCK / 64 - 1) / (FP_BLOCK / 64))), dim3(FP_BLOCK), 0, ctx->stream, g);
+    MG_HIP_CHECK(hipGetLastError());
+    return MG_OK;
+}
+
+// ss[j] = the sum of squares of column j, the rows added in row order
+__global__ __launch_bounds__(FP_BLOCK) void fpca_column_squares_kernel(const double *__restrict__ A, int64_t n, int64_t p, double *__restrict__ ss) {
+    const int64_t j = (int64_t)blockIdx.x * FP_BLOCK + threadIdx.x;
+    if (j >= p) return;
+    double s = 0.0;
+    for (int64_t i = 0; i < n; i++) { const double v = A[i * p + j]; s = s + v * v; }
+    ss[j] = s;
+}
+
+// start row r of the block: uniform in [-1, 1) from a hash of (r, column) (splitmix64's finaliser)
+static void fp_lead_start_row(int64_t r, int64_t p, double *out) {
+    for (int64_t e = 0; e < p; e++) {
+        uint64_t z = ((uint64_t)r << 32) + (uint64_t)e + 0x9e3779b97f4a7c15ull;
+        z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+        z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+        z = z ^ (z >> 31);
+        out[e] = (double)(z >> 11) * (1.0 / 4503599627370496.0) - 1.0;   // 53 bits / 2^52 - 1
+    }
+}
+
+extern "C" int mg_pca_fit_leading(mg_context *ctx, const double *a_dev, int64_t n, int64_t p, double fraction, double tol, int32_t max_iterations,
+                                  double *centred_dev, double *mean, int32_t k_cap, int32_t *k_out, double *singular_values, double *vt, double *ratios,
+                                  int32_t *iterations, int32_t *status) {
+    const char *who = "mg_pca_fit_leading";
+    MG_REQUIRE_AS(ctx && a_dev && centred_dev && mean && k_out && singular_values && vt && ratios && iterations && status, MG_ERR_INVALID_ARGUMENT,
+                  "%s: NULL argument", who);
+    MG_REQUIRE_AS(n >= 2 && p >= 1 && k_cap >= 1, MG_ERR_INVALID_ARGUMENT, "%s: matrix %lld x %lld, room for %d components", who, (long long)n, (long long)p, k_cap);
+    MG_REQUIRE_AS(fraction > 0.0 && fraction < 1.0, MG_ERR_INVALID_ARGUMENT, "%s: fraction %g outside (0, 1)", who, fraction);
+    MG_REQUIRE_AS(n < ((int64_t)1 << 24) && p <= FP_MAX_LONG && ((n + 15) / 16) * ((p + 15) / 16) < ((int64_t)1 << 31), MG_ERR_UNSUPPORTED,
+                  "%s: table too large (n below 2^24, p at most 2^20, fewer than 2^31 tiles of 16 x 16)", who);
+    const int64_t m = std::min(n, p), b_max = std::min<int64_t>(m, FP_MAX_SHORT);
+    if (!(tol > 0.0)) tol = 64.0 * DBL_EPSILON * std::sqrt((double)std::max(n, p));
+    const int32_t cap = max_iterations > 0 ? max_iterations : FP_LEAD_MAX_ITERATIONS;
+    *k_out = 0, *iterations = 0, *status = 2;
+    MG_HIP_CHECK(hipSetDevice(ctx->device));
+
+    // centring and the total variance
+    std::vector<double> colss;
+    try { colss.resize((size_t)p); } catch (const std::bad_alloc &) { return MG_ERR_OUT_OF_MEMORY; }
+    {
+        mg_workspace ws(ctx, who);
+        const size_t o_mean = ws.carve((size_t)p * 8), o_ss = ws.carve((size_t)p * 8);
+        const int ra = ws.alloc();
+        if (ra != MG_OK) return ra;
+        double *d_mean = ws.at<double>(o_mean), *d_ss = ws.at<double>(o_ss);
+        const unsigned gp = (unsigned)((p + FP_BLOCK - 1) / FP_BLOCK);
+        hipLaunchKernelGGL(fpca_mean_kernel, dim3(gp), dim3(FP_BLOCK), 0, ctx->stream, a_dev, n, p, d_mean);
+        hipLaunchKernelGGL(fpca_centre_kernel, dim3((unsigned)((n * p + FP_BLOCK - 1) / FP_BLOCK)), dim3(FP_BLOCK), 0, ctx->stream, a_dev, (const double *)d_mean, n, p,
+                           centred_dev, centred_dev, 0);
+        hipLaunchKernelGGL(fpca_column_squares_kernel, dim3(gp), dim3(FP_BLOCK), 0, ctx->stream, (const double *)centred_dev, n, p, d_ss);
+        MG_HIP_CHECK(hipGetLastError());
+        MG_HIP_CHECK(hipMemcpyAsync(mean, d_mean, (size_t)p * 8, hipMemcpyDeviceToHost, ctx->stream));
+        MG_HIP_CHECK(hipMemcpyAsync(colss.data(), d_ss, (size_t)p * 8, hipMemcpyDeviceToHost, ctx->stream));
+        MG_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    }
+    double total = 0.0;      // |Xc|_F^2 = (n - 1) x the total variance, the columns added in blocks of 64
+    for (int64_t e0 = 0; e0 < p; e0 += 64) {
+        double s = 0.0;
+        for (int64_t e = e0; e < std::min<int64_t>(p, e0 + 64); e++) s = s + colss[(size_t)e];
+        total = total + s;
+    }
+    MG_REQUIRE_AS(std::isfinite(total), MG_ERR_INVALID_ARGUMENT, "%s: the matrix holds non-finite values (or its norms overflow)", who);
+    MG_REQUIRE_AS(total > 0.0, MG_ERR_INVALID_ARGUMENT, "%s: the matrix has no variance", who);
+
+    int64_t b = std::min<int64_t>(b_max, FP_LEAD_START);
+    std::vector<double> hQ, hZ, lam, resid, sv_tmp, mean_tmp;
+    int32_t iters = 0, in_block = 0, st = 2, k = 0;
+    bool q_ready = false;    // hQ holds orthonormal rows and the device has them
+    for (;;) {
+        try {
+            hQ.resize((size_t)b * p); hZ.resize((size_t)b * p); lam.resize((size_t)b); resid.resize((size_t)b); sv_tmp.resize((size_t)b); mean_tmp.resize((size_t)p);
+        } catch (const std::bad_alloc &) {
+            mg_set_error("%s: cannot allocate the host copies of a %lld x %lld block", who, (long long)b, (long long)p);
+            return MG_ERR_OUT_OF_MEMORY;
+        }
+        mg_workspace ws(ctx, who);
+        const size_t o_q = ws.carve((size_t)b * p * 8), o_z = ws.carve((size_t)b * p * 8), o_c = ws.carve((size_t)b * p * 8), o_y = ws.carve((size_t)n * b * 8);
+        const int ra = ws.alloc();
+        if (ra != MG_OK) return ra;
+        double *Q = ws.at<double>(o_q), *Z = ws.at<double>(o_z), *Cz = ws.at<double>(o_c), *Y = ws.at<double>(o_y);
+        int32_t sweeps = 0, jst = 0;
+        if (!q_ready) {
+            // rows the caller of this block left in hQ (the first `k` of them, 0 at the start), then start rows; orthonormalised by Jacobi
+            for (int64_t r = k; r < b; r++) fp_lead_start_row(r, p, hQ.data() + (size_t)r * p);
+            MG_HIP_CHECK(hipMemcpyAsync(Z, hQ.data(), (size_t)b * p * 8, hipMemcpyHostToDevice, ctx->stream));
+            const int rc = mg_pca_fit(ctx, Z, b, p, 0, Cz, mean_tmp.data(), sv_tmp.data(), hQ.data(), &sweeps, &jst);
+            if (rc != MG_OK) return rc;
+            MG_HIP_CHECK(hipMemcpyAsync(Q, hQ.data(), (size_t)b * p * 8, hipMemcpyHostToDevice, ctx->stream));
+            q_ready = true;
+            in_block = 0;
+        }
+        bool grow = false;
+        for (;;) {
+            int rc = fp_gemm(ctx, centred_dev, Q, nullptr, Y, 1, 0, 0, 0, n, b, p, p, 1, p, b);            // Y = Xc Q^T
+            if (rc == MG_OK) rc = fp_gemm_ta(ctx, Y, centred_dev, Z, b, p, n, b, p, p);                      // Z = Y^T Xc
+            if (rc != MG_OK) return rc;
+            MG_HIP_CHECK(hipMemcpyAsync(hZ.data(), Z, (size_t)b * p * 8, hipMemcpyDeviceToHost, ctx->stream));
+            MG_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+            iters++, in_block++;
+            double lam_max = 0.0;
+            for (int64_t i = 0; i < b; i++) {
+                const double *q = hQ.data() + (size_t)i * p, *z = hZ.data() + (size_t)i * p;
+                double dot = 0.0, r2 = 0.0;
+                for (int64_t e = 0; e < p; e++) dot = dot + q[e] * z[e];
+                for (int64_t e = 0; e < p; e++) { const double d = z[e] - dot * q[e]; r2 = r2 + d * d; }
+                lam[(size_t)i] = dot > 0.0 ? dot : 0.0;
+                resid[(size_t)i] = std::sqrt(r2);
+                lam_max = std::max(lam_max, lam[(size_t)i]);
+            }
+            // sklearn's count for a float n_components: searchsorted(cumsum(ratio), fraction, side = "right") + 1
+            double cum = 0.0;
+            int64_t below = 0;
+            for (int64_t i = 0; i < b; i++) { cum = cum + lam[(size_t)i] / total; if (cum <= fraction) below++; }
+            const bool captured = below < b;
+            k = (int32_t)std::min<int64_t>(below + 1, b);
+            const bool small_block = b < b_max && (!captured || k + FP_LEAD_SPARE > b);
+            bool converged = captured && !small_block;
+            for (int64_t i = 0; i < k && converged; i++) converged = resid[(size_t)i] <= tol * lam_max;
+            if (converged) { st = 1; break; }
+            if (iters >= cap) { st = 2; break; }
+            if (b == b_max && b < m && !captured && in_block >= 8) {
+                // (the quotients rise towards the eigenvalues: eight rounds in, a block of Jacobi's limit that still captures too little will not)
+                mg_set_error("%s: more than %lld components are needed for %g of the variance", who, (long long)b_max, fraction);
+                return MG_ERR_UNSUPPORTED;
+            }
+            if (small_block && in_block >= 2) { grow = true; break; }
+            rc = mg_pca_fit(ctx, Z, b, p, 0, Cz, mean_tmp.data(), sv_tmp.data(), hQ.data(), &sweeps, &jst);
+            if (rc != MG_OK) return rc;
+            MG_HIP_CHECK(hipMemcpyAsync(Q, hQ.data(), (size_t)b * p * 8, hipMemcpyHostToDevice, ctx->stream));
+        }
+        if (!grow) break;
+        // the block doubles: its rows stay (as (Xc^T Xc) q_i, one more step), new start rows join them
+        const int64_t b2 = std::min<int64_t>(b_max, 2 * b);
+        try { hZ.resize((size_t)b2 * p); } catch (const std::bad_alloc &) { return MG_ERR_OUT_OF_MEMORY; }
+        hQ.swap(hZ);
+        k = (int32_t)b;      // rows kept
+        b = b2;
+        q_ready = false;
+    }
+    *k_out = k;          // (what a caller with too little room asks again with)
+    MG_REQUIRE_AS(k <= k_cap, MG_ERR_INVALID_ARGUMENT, "%s: %d components kept, room for %d", who, k, k_cap);
+    for (int32_t i = 0; i < k; i++) {
+        singular_values[i] = std::sqrt(lam[(size_t)i]);
+        ratios[i] = lam[(size_t)i] / total;
+        memcpy(vt + (size_t)i * p, hQ.data() + (size_t)i * p, (size_t)p * 8);
+    }
+    *k_out = k, *iterations = iters, *status = st;
     return MG_OK;
 }

@@ -424,22 +424,8 @@ __device__ __forceinline__ void mg_joint_tracks_body(const mg_track_args &a, con
     }
     for (int d = tid; d < D; d += MG_TRACK_BLOCK) slot[d] = a.slot[d];
     __syncthreads();
-    // (mg_control_point's statement for MG_TRACK_CANDS candidates side by side: one read of an eigenvector element feeds all of them,
-    // which the helper's one-chain form cannot express)
-    for (int e = tid; e < ncp; e += MG_TRACK_BLOCK) {
-        const int i = e / nc, q = e - i * nc;
-        const int r = i * D + a.chan[q];
-        double acc[MG_TRACK_CANDS];
-#pragma unroll
-        for (int c = 0; c < MG_TRACK_CANDS; c++) acc[c] = a.mean[r];
-        for (int k = 0; k < L; k++) {
-            const double ev = a.Et64[(size_t)k * R + r];
-#pragma unroll
-            for (int c = 0; c < MG_TRACK_CANDS; c++) acc[c] = fma(ev, s_all[c * L + k], acc[c]);
-        }
-#pragma unroll
-        for (int c = 0; c < MG_TRACK_CANDS; c++) cp_all[(size_t)c * ncp + e] = acc[c];
-    }
+    // the group's control points of the kept channels (mg_track_control_points, mg_frame_device.h)
+    mg_track_control_points<MG_TRACK_CANDS, MG_TRACK_BLOCK>(a.Et64, a.mean, L, R, D, a.NB, nc, a.chan, s_all, cp_all);
     __syncthreads();
     // the candidate's aligning transform from its FIRST control point (mg_track_alignment, mg_frame_device.h)
     if (tid < MG_TRACK_CANDS && a.align_mode != 0) mg_track_alignment(a, cp_all + (size_t)tid * ncp, [&](int ch) { return slot[ch]; }, al_all + tid * 8);

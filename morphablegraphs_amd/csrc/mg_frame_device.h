@@ -255,6 +255,31 @@ struct mg_track_args {
 int mg_track_fill_args(const char *who, mg_track_plan *pl, const void *lat, int dt, int64_t B, int64_t ld, const mg_alignment_desc *al,
                        const mg_time_grid *const *grids, double *const *tracks_dev, mg_track_args *out, size_t *lds_out);
 
+// The control-point staging of a workgroup of BLOCK threads that owns CANDS candidates (mg_joint_tracks_body, mg_point_clouds_kernel):
+// from their latents s_all [CANDS][L] in LDS (staged by the caller, a barrier behind them) the control points of the kept channels
+// chan[0 .. nc) into cp_all [CANDS][NB][nc]; the caller's barrier follows.
+// (mg_control_point's statement for CANDS candidates side by side: one read of an eigenvector element feeds all of them, which the
+// helper's one-chain form cannot express)
+template <int CANDS, int BLOCK>
+__device__ __forceinline__ void mg_track_control_points(const double *Et64, const double *mean, int L, int R, int D, int NB, int nc, const int32_t *chan,
+                                                        const double *s_all, double *cp_all) {
+    const int tid = threadIdx.x, ncp = NB * nc;
+    for (int e = tid; e < ncp; e += BLOCK) {
+        const int i = e / nc, q = e - i * nc;
+        const int r = i * D + chan[q];
+        double acc[CANDS];
+#pragma unroll
+        for (int c = 0; c < CANDS; c++) acc[c] = mean[r];
+        for (int k = 0; k < L; k++) {
+            const double ev = Et64[(size_t)k * R + r];
+#pragma unroll
+            for (int c = 0; c < CANDS; c++) acc[c] = fma(ev, s_all[c * L + k], acc[c]);
+        }
+#pragma unroll
+        for (int c = 0; c < CANDS; c++) cp_all[(size_t)c * ncp + e] = acc[c];
+    }
+}
+
 // A candidate's aligning transform from its FIRST control point (a clamped spline's value at t = 0), into al[8]: c, s, tx, tz, ty, then
 // the half angle (aw, ay) its root quaternion turns by.  cp: its control points of the kept channels [NB][n_chan]; slot: channel -> slot.
 template <typename SlotFn>

@@ -18,7 +18,7 @@
 enum { MG_PROF_FRAMES = 0, MG_PROF_GMM_LOG_PROB, MG_PROF_SCORE_CONSTRAINTS, MG_PROF_ARGMIN, MG_PROF_GMM_SAMPLE, MG_PROF_SPLINE_EVALUATE, MG_PROF_STEP,
        MG_PROF_OPTIONS_STEP, MG_PROF_JOINT_TRACKS, MG_PROF_FRAME_CONSTRAINTS, MG_PROF_TRAJECTORY, MG_PROF_CLUSTER_TREE_SEARCH, MG_PROF_WALK_FRAMES,
        MG_PROF_WALK_TIME, MG_PROF_STEP_LENGTHS, MG_PROF_FEATURE_POINTS, MG_PROF_FEATURE_POINTS_WARPED, MG_PROF_MIXTURE_SCORES,
-       MG_PROFILE_SLOTS = MG_PROF_MIXTURE_SCORES + 1 };
+       MG_PROF_POINT_CLOUDS, MG_PROFILE_SLOTS = MG_PROF_POINT_CLOUDS + 1 };
 
 int mg_hip_fail(hipError_t e, const char *what);
 
@@ -50,7 +50,7 @@ struct mg_device_table {
 // bits of mg_context::attr_traj: kernels whose dynamic-LDS limit is already raised on this context's device
 enum { MG_LDS_TRAJECTORY = 1, MG_LDS_TIMEWARP = 2, MG_LDS_JOINT_TRACKS = 4, MG_LDS_FRAME_CONSTRAINTS = 8, MG_LDS_WALK_FRAMES = 16, MG_LDS_WALK_SCORE = 32,
        MG_LDS_WALK_TIME = 64, MG_LDS_STEP_LENGTH_F32 = 128, MG_LDS_STEP_LENGTH_F64 = 256, MG_LDS_FEATURE_POINTS_F32 = 512, MG_LDS_FEATURE_POINTS_F64 = 1024,
-       MG_LDS_FEATURE_POINTS_WARPED_F32 = 2048, MG_LDS_FEATURE_POINTS_WARPED_F64 = 4096, MG_LDS_MIXTURE_SCORES = 8192 };
+       MG_LDS_FEATURE_POINTS_WARPED_F32 = 2048, MG_LDS_FEATURE_POINTS_WARPED_F64 = 4096, MG_LDS_MIXTURE_SCORES = 8192, MG_LDS_POINT_CLOUDS = 16384 };
 
 struct mg_context {
     int device = 0;

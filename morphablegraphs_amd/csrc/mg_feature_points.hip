@@ -31,7 +31,7 @@
 
 #include "mg_feature_rows.h"
 #include "mg_items.h"
-#include "mg_pack.h"
+#include "mg_joint_plan.h"
 #include "mg_score_device.h"
 #include "mg_timewarp_device.h"
 
@@ -182,6 +182,7 @@ __global__ __launch_bounds__(256) void mg_feature_points_kernel(const mg_fp_args
 // chain records, the host-planned frames' tap rows, the LDS bytes of a workgroup; the time-warped item's plan starts with it
 struct mg_fp_plan {
     mg_feature_rows rows;
+    mg_joint_plan joints;                // the listed joints' chains, formed while the arguments are checked
     std::vector<double> rec;
     int32_t rec_stride = MG_FP_REC_HDR;
     double w[MG_FP_SLOTS * 4] = {0};
@@ -202,9 +203,9 @@ static int mg_fp_refuse(const char *who, int i, int D, const mg_skeleton_desc *s
     return MG_OK;
 }
 
-// the argument errors of one item's joint list (MG_ERR_INVALID_ARGUMENT)
+// the argument errors of one item's joint list (MG_ERR_INVALID_ARGUMENT); jp: the chains of its joints (mg_joint_plan.h)
 template <class Item>
-static int mg_fp_check_joints(const char *who, int i, const Item &q) {
+static int mg_fp_joint_list(const char *who, int i, const Item &q, mg_joint_plan &jp) {
     MG_ITEM_REQUIRE(q.n_joints >= 0 && q.n_joints <= MG_FEATURE_POINTS_MAX_JOINTS, "%s: item %d: %d joints (0 .. %d)", who, i, q.n_joints,
                     MG_FEATURE_POINTS_MAX_JOINTS);
     MG_ITEM_REQUIRE((q.n_joints > 0) == (q.points_dev != nullptr), "%s: item %d: %d joints and %s points output", who, i, q.n_joints,
@@ -212,44 +213,21 @@ static int mg_fp_check_joints(const char *who, int i, const Item &q) {
     if (q.n_joints == 0) return MG_OK;
     const mg_skeleton_desc *sk = q.skeleton;
     MG_ITEM_REQUIRE(sk && q.joints, "%s: item %d: joints without a skeleton or a joint list", who, i);
-    MG_ITEM_REQUIRE(sk->n_joints > 0 && sk->parents && sk->offsets && sk->quat_channel && sk->parents[0] < 0, "%s: item %d: incomplete skeleton", who, i);
-    for (int j = 0; j < q.n_joints; j++) {
-        std::vector<int> ch;
-        int bad;
-        const int st = mg_joint_chain(sk->parents, sk->n_joints, q.joints[j], ch, &bad);
-        MG_ITEM_REQUIRE(st == MG_CHAIN_OK, "%s: item %d: joint %d%s", who, i, bad, mg_chain_why(st));
-    }
+    MG_ITEM_REQUIRE(mg_skeleton_complete(sk), "%s: item %d: incomplete skeleton", who, i);
+    const mg_plan_failure f = jp.check(sk, q.joints, q.n_joints);
+    MG_ITEM_REQUIRE(!f, "%s: item %d: joint %d%s", who, i, f.joint, mg_chain_why(f.kind));
     return MG_OK;
 }
 
-// the chains of an item's listed joints (checked: mg_fp_check_joints); wanted(qc): every quaternion channel along them
-template <class Item, class Wanted>
-static int mg_fp_chains_of(const char *who, int i, const Item &q, std::vector<std::vector<int>> &chains, Wanted wanted) {
-    const mg_skeleton_desc *sk = q.skeleton;
-    chains.assign((size_t)q.n_joints, std::vector<int>());
-    for (int j = 0; j < q.n_joints; j++) {
-        mg_joint_chain(sk->parents, sk->n_joints, q.joints[j], chains[(size_t)j]);
-        const int m = (int)chains[(size_t)j].size() - 1;
-        MG_ITEM_REFUSE(m > MG_MAX_CHAIN, "%s: item %d: chain of %d joints exceeds %d", who, i, m, MG_MAX_CHAIN);
-        for (int k = 0; k < m; k++) {
-            const int qc = sk->quat_channel[chains[(size_t)j][(size_t)k]];
-            if (qc >= 0) wanted(qc);
-        }
-    }
+// what the kernels do not take of those chains (MG_ERR_UNSUPPORTED), then the channels they read (pl.joints.need; root_xyz: the root
+// position among them) and their records (mg_fk_position_table's layout), all as long as the longest chain's
+static int mg_fp_measure(const char *who, int i, int D, bool root_xyz, mg_fp_plan &pl) {
+    const mg_plan_failure f = pl.joints.measure(D, root_xyz);
+    MG_ITEM_REFUSE(f.kind == MG_PLAN_TOO_LONG, "%s: item %d: chain of %d joints exceeds %d", who, i, f.length, MG_MAX_CHAIN);
+    MG_ITEM_REFUSE(f.kind == MG_PLAN_CHANNEL_OUTSIDE, "%s: item %d: the skeleton's joint %d has channels %d .. %d, the primitive %d", who, i, f.joint, f.channel,
+                   f.channel + 3, D);      // (mg_fp_refuse has said so of any joint already)
+    pl.rec_stride = pl.joints.records(MG_FP_REC_HDR, 0, pl.rec);
     return MG_OK;
-}
-
-// ... and their records (mg_fk_position_table's layout), all as long as the longest chain's
-static void mg_fp_records_of(const mg_skeleton_desc *sk, const std::vector<std::vector<int>> &chains, int32_t &rec_stride, std::vector<double> &rec) {
-    size_t longest = 0;
-    for (const std::vector<int> &ch : chains) longest = std::max(longest, ch.size() - 1);
-    rec_stride = MG_FP_REC_HDR + 4 * (int32_t)longest;
-    rec.assign(chains.size() * rec_stride, 0.0);
-    for (size_t j = 0; j < chains.size(); j++) {
-        double *r = &rec[j * rec_stride];
-        r[4] = (double)(chains[j].size() - 1);
-        mg_chain_links(chains[j], sk->offsets, [&](int joint) { return sk->quat_channel[joint]; }, r + MG_FP_REC_HDR);
-    }
 }
 
 // the plan of one item whose arguments passed; what the kernels do not take is MG_ERR_UNSUPPORTED
@@ -274,10 +252,10 @@ static int mg_fp_plan_of(const char *who, int i, const mg_feature_point_item &q,
     }
     // the root position of frame 0; the root position and the quaternions along the listed joints' chains of frame_idx; the root pose of F - 1
     std::vector<mg_feature_range> wanted = {{0, 0, 3}, {1, 0, 3}, {2, 0, 7}};
-    std::vector<std::vector<int>> chains;
-    if ((rc = mg_fp_chains_of(who, i, q, chains, [&](int qc) { wanted.push_back({1, qc, 4}); })) != MG_OK) return rc;
+    if ((rc = mg_fp_measure(who, i, D, false, pl)) != MG_OK) return rc;
+    for (int d = 0; d < D; d++)
+        if (pl.joints.need[(size_t)d]) wanted.push_back({1, d, 1});
     pl.rows = mg_feature_rows_of(D, first, wanted);
-    mg_fp_records_of(q.skeleton, chains, pl.rec_stride, pl.rec);
     pl.lds = (int64_t)p->L * pl.rows.NRS > (1 << 20) ? INT_MAX : mg_fp_layout_of(p->L, pl.rows.NRS, pl.rows.NCP, D, q.n_joints, pl.rec_stride).total_bytes;
     MG_ITEM_REFUSE(pl.lds > MG_FP_LDS_MAX, "%s: item %d: the tables (%d x %d control-point values, %d joints) do not fit LDS", who, i, p->L, pl.rows.NRS, q.n_joints);
     MG_ITEM_REFUSE_GRID(who, i, q.n_samples, MG_FP_TILE);
@@ -286,15 +264,15 @@ static int mg_fp_plan_of(const char *who, int i, const mg_feature_point_item &q,
 
 // the checks both entry points make of an item table (nothing is launched or copied before they pass); plans: one per item
 static int mg_fp_check(const char *who, int32_t n_items, const mg_feature_point_item *items, int latent_dtype, std::vector<mg_fp_plan> &plans) {
+    plans.resize((size_t)std::max(n_items, 0));
     int rc = mg_items_check(
         who, n_items, items, latent_dtype, [](int, const mg_feature_point_item &) { return (int)MG_OK; },
         [&](int i, const mg_feature_point_item &q) -> int {
             MG_ITEM_REQUIRE(q.frame_idx >= 0 && q.frame_idx < q.prim->F, "%s: item %d: frame %d of %d", who, i, q.frame_idx, q.prim->F);
             MG_ITEM_REQUIRE(q.start_root_dev || q.points_dev || q.root_end_dev || q.heading_end_dev || q.heading_len_dev, "%s: item %d: all outputs are NULL", who, i);
-            return mg_fp_check_joints(who, i, q);
+            return mg_fp_joint_list(who, i, q, plans[(size_t)i].joints);
         });
     if (rc != MG_OK) return rc;
-    plans.resize((size_t)n_items);
     for (int i = 0; i < n_items; i++)
         if ((rc = mg_fp_plan_of(who, i, items[i], plans[(size_t)i])) != MG_OK) return rc;
     return MG_OK;
@@ -562,17 +540,12 @@ static int mg_fpw_plan_of(const char *who, int i, const mg_warped_feature_point_
     }
     pl.rows = mg_feature_rows_of(D, first, {{0, 0, 3}, {1, 0, 7}});
     // the mid frame's channels: the root position and the quaternions along the listed joints' chains
-    std::vector<char> mid((size_t)D, 0);
-    std::vector<std::vector<int>> chains;
-    if ((rc = mg_fp_chains_of(who, i, q, chains, [&](int qc) { for (int e = 0; e < 4; e++) mid[(size_t)(qc + e)] = 1; })) != MG_OK) return rc;
-    if (q.n_joints > 0) mid[0] = mid[1] = mid[2] = 1;
-    std::vector<int32_t> pos((size_t)D, -1);
-    for (int d = 0; d < D; d++)
-        if (mid[(size_t)d]) { pos[(size_t)d] = (int32_t)pl.chan.size(); pl.chan.push_back(d); }
+    if ((rc = mg_fp_measure(who, i, D, q.n_joints > 0, pl)) != MG_OK) return rc;
+    std::vector<int32_t> pos;
+    pl.joints.compact(pl.chan, pos);
     pl.NC = (int32_t)pl.chan.size();
     pl.chan.insert(pl.chan.end(), pos.begin(), pos.end());
     pl.need_mid = q.n_joints > 0 || q.time_mid_dev != nullptr;
-    mg_fp_records_of(q.skeleton, chains, pl.rec_stride, pl.rec);
     pl.lds = mg_fpw_layout_of(F, p->Lt, pl.need_mid, p->L, pl.rows.NRS, pl.rows.NCP, pl.NC, D, q.n_joints, pl.rec_stride).total_bytes;
     MG_ITEM_REFUSE(pl.lds > MG_FP_LDS_MAX, "%s: item %d: the tables (%d canonical frames x %d candidates, %d x %d control-point values, %d joints) do not fit LDS", who,
                    i, F, MG_FP_TILE, p->L, pl.rows.NRS, q.n_joints);
@@ -582,6 +555,7 @@ static int mg_fpw_plan_of(const char *who, int i, const mg_warped_feature_point_
 
 static int mg_fpw_check(const char *who, int32_t n_items, const mg_warped_feature_point_item *items, int latent_dtype, std::vector<mg_fpw_plan> &plans) {
     typedef mg_warped_feature_point_item item;
+    plans.resize((size_t)std::max(n_items, 0));
     int rc = mg_items_check(
         who, n_items, items, latent_dtype,
         [&](int i, const item &q) -> int {
@@ -598,10 +572,9 @@ static int mg_fpw_check(const char *who, int32_t n_items, const mg_warped_featur
             MG_ITEM_REQUIRE(q.frame_idx >= 0, "%s: item %d: frame %d", who, i, q.frame_idx);
             MG_ITEM_REQUIRE(q.start_root_dev || q.points_dev || q.root_end_dev || q.heading_end_dev || q.heading_len_dev || q.time_mid_dev || q.n_frames_dev,
                             "%s: item %d: all outputs are NULL", who, i);
-            return mg_fp_check_joints(who, i, q);
+            return mg_fp_joint_list(who, i, q, plans[(size_t)i].joints);
         });
     if (rc != MG_OK) return rc;
-    plans.resize((size_t)n_items);
     for (int i = 0; i < n_items; i++)
         if ((rc = mg_fpw_plan_of(who, i, items[i], plans[(size_t)i])) != MG_OK) return rc;
     return MG_OK;

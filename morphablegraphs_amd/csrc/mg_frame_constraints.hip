@@ -23,7 +23,7 @@
 #include <vector>
 
 #include "mg_internal.h"
-#include "mg_pack.h"
+#include "mg_joint_plan.h"
 #include "mg_score_device.h"
 #include "mg_spline_device.h"
 #include "mg_frame_device.h"   // the chain scorers, the tracks' statements and their argument blocks (shared with mg_cluster_tree.hip)
@@ -468,84 +468,51 @@ extern "C" void mg_track_plan_destroy(mg_track_plan *pl) {
     delete pl;
 }
 
-static int mg_track_chain_record(const char *who, const mg_skeleton_desc *sk, int joint, int n_dim, double *rec, std::vector<char> &need) {
-    std::vector<int> ch;
-    int bad;
-    const int st = mg_joint_chain(sk->parents, sk->n_joints, joint, ch, &bad);
-    if (st != MG_CHAIN_OK) { mg_set_error("%s: joint %d%s", who, bad, mg_chain_why(st)); return MG_ERR_INVALID_ARGUMENT; }
-    const int m = (int)ch.size() - 1;
-    if (m > MG_MAX_CHAIN) { mg_set_error("%s: chain of %d joints exceeds %d", who, m, MG_MAX_CHAIN); return MG_ERR_INVALID_ARGUMENT; }
-    for (int k = 0; k < m; k++) {
-        const int qc = sk->quat_channel[ch[(size_t)k]];
-        if (qc >= 0 && qc + 4 > n_dim) { mg_set_error("%s: quaternion channel %d outside n_dim = %d", who, qc, n_dim); return MG_ERR_INVALID_ARGUMENT; }
-        if (qc >= 0) for (int e = 0; e < 4; e++) need[(size_t)qc + e] = 1;
-    }
-    rec[0] = m;
-    mg_chain_links(ch, sk->offsets, [&](int j) { return sk->quat_channel[j]; }, rec + 1);
-    return MG_OK;
-}
-
 // joints: the requests' joints back to back, n_joints[q] of them for request q (each 1 .. MG_FRAME_MAX_JOINTS).  align_joint: the
 // node candidates are aligned through when an alignment is given at the call (0 = the root; -1: no alignment will ever be given).
 extern "C" int mg_track_plan_create(mg_primitive *p, const mg_skeleton_desc *sk, int32_t n_requests, const int32_t *n_joints, const int32_t *joints,
                                     int32_t align_joint, mg_track_plan **out) {
-    if (!p || !sk || !out || n_requests < 1 || n_requests > MG_TRACK_MAX_REQUESTS || !n_joints || !joints) {
-        mg_set_error("mg_track_plan_create: bad arguments (1 .. %d requests)", MG_TRACK_MAX_REQUESTS);
-        return MG_ERR_INVALID_ARGUMENT;
-    }
+    const char *who = "mg_track_plan_create";
+    MG_REQUIRE(p && sk && out && n_requests >= 1 && n_requests <= MG_TRACK_MAX_REQUESTS && n_joints && joints, "%s: bad arguments (1 .. %d requests)", who,
+               MG_TRACK_MAX_REQUESTS);
     *out = nullptr;
-    if (!(sk->n_joints > 0 && sk->parents && sk->offsets && sk->quat_channel && sk->parents[0] < 0) || p->D < 3) {
-        mg_set_error("mg_track_plan_create: incomplete skeleton, or a primitive without root channels");
-        return MG_ERR_INVALID_ARGUMENT;
-    }
+    MG_REQUIRE(mg_skeleton_complete(sk) && p->D >= 3, "%s: incomplete skeleton, or a primitive without root channels", who);
     MG_HIP_CHECK(hipSetDevice(p->ctx->device));
+    int32_t joint0[MG_TRACK_MAX_REQUESTS + 1] = {0};
+    for (int q = 0; q < n_requests; q++) {
+        MG_REQUIRE(n_joints[q] >= 1 && n_joints[q] <= MG_FRAME_MAX_JOINTS, "%s: request %d has %d joints (1 .. %d)", who, q, n_joints[q], MG_FRAME_MAX_JOINTS);
+        joint0[q + 1] = joint0[q] + n_joints[q];
+    }
+    // the host's tables (mg_joint_plan.h): every listed joint's record, the aligning node's quaternions, the channels both read
+    mg_joint_plan plan;
+    const mg_plan_failure f = plan.build(sk, joints, joint0[n_requests], p->D, true);
+    MG_REQUIRE(!f.of_skeleton(), "%s: joint %d%s", who, f.joint, mg_chain_why(f.kind));
+    MG_REQUIRE(f.kind != MG_PLAN_TOO_LONG, "%s: chain of %d joints exceeds %d", who, f.length, MG_MAX_CHAIN);
+    MG_REQUIRE(f.kind != MG_PLAN_CHANNEL_OUTSIDE, "%s: quaternion channel %d outside n_dim = %d", who, f.channel, p->D);
+    std::vector<double> records, arec(MG_TRACK_REC, 0.0);
+    plan.records(1, MG_TRACK_REC, records);
+    std::vector<int32_t> quats;
+    if (align_joint >= 0) {
+        // the aligning node's global orientation: the quaternions of the chain root .. node, the node's own included
+        const mg_plan_failure g = mg_aligning_quaternions(sk, align_joint, p->D, quats);
+        MG_REQUIRE(!g.of_skeleton(), "%s: %sjoint %d%s", who, g.kind == MG_PLAN_NO_JOINT ? "aligning " : "", g.joint, mg_chain_why(g.kind));
+        MG_REQUIRE(!g, "%s: aligning chain does not fit", who);
+        arec[0] = (double)quats.size();
+        for (size_t m = 0; m < quats.size(); m++) { arec[1 + 4 * m] = quats[m]; plan.want(quats[m]); }
+    }
+    std::vector<int32_t> chan, slot;
+    plan.compact(chan, slot);
     mg_track_plan *pl = new (std::nothrow) mg_track_plan();
     if (!pl) return MG_ERR_OUT_OF_MEMORY;
-    pl->prim = p; pl->n_requests = n_requests;
-    std::vector<char> need((size_t)p->D + 4, 0);
-    need[0] = need[1] = need[2] = 1;
-    int total = 0;
-    for (int q = 0; q < n_requests; q++) {
-        if (n_joints[q] < 1 || n_joints[q] > MG_FRAME_MAX_JOINTS) { mg_set_error("mg_track_plan_create: request %d has %d joints (1 .. %d)", q, n_joints[q], MG_FRAME_MAX_JOINTS); delete pl; return MG_ERR_INVALID_ARGUMENT; }
-        pl->req_joint0[q] = total;
-        total += n_joints[q];
-    }
-    pl->req_joint0[n_requests] = total;
-    std::vector<double> records((size_t)total * MG_TRACK_REC, 0.0), arec(MG_TRACK_REC, 0.0);
-    int rc = MG_OK;
-    for (int o = 0; o < total && rc == MG_OK; o++) rc = mg_track_chain_record("mg_track_plan_create", sk, joints[o], p->D, &records[(size_t)o * MG_TRACK_REC], need);
-    if (rc == MG_OK && align_joint >= 0) {
-        // the aligning node's global orientation: the quaternions of the chain root .. node, the node's own included
-        std::vector<int> ch;
-        int bad;
-        const int st = mg_joint_chain(sk->parents, sk->n_joints, align_joint, ch, &bad);
-        if (st != MG_CHAIN_OK) { mg_set_error("mg_track_plan_create: %sjoint %d%s", st == MG_CHAIN_NO_JOINT ? "aligning " : "", bad, mg_chain_why(st)); rc = MG_ERR_INVALID_ARGUMENT; }
-        else {
-            int m = 0;
-            for (int j : ch) {
-                const int qc = sk->quat_channel[j];
-                if (qc < 0) continue;
-                if (qc + 4 > p->D || m >= MG_MAX_CHAIN) { mg_set_error("mg_track_plan_create: aligning chain does not fit"); rc = MG_ERR_INVALID_ARGUMENT; break; }
-                arec[1 + 4 * m] = qc;
-                for (int e = 0; e < 4; e++) need[(size_t)qc + e] = 1;
-                m++;
-            }
-            arec[0] = m;
-            pl->align_m = m;
-            pl->align_joint = align_joint;
-        }
-    }
-    if (rc != MG_OK) { delete pl; return rc; }
-    std::vector<int32_t> chan, slot((size_t)p->D, -1);
-    for (int d = 0; d < p->D; d++)
-        if (need[(size_t)d]) { slot[(size_t)d] = (int32_t)chan.size(); chan.push_back(d); }
-    pl->n_chan = (int32_t)chan.size();
+    pl->prim = p; pl->n_requests = n_requests; pl->n_chan = (int32_t)chan.size();
+    std::copy(joint0, joint0 + n_requests + 1, pl->req_joint0);
+    if (align_joint >= 0) { pl->align_m = (int32_t)quats.size(); pl->align_joint = align_joint; }
     auto up = [&](const void *h, size_t bytes, void **d) -> int {
         MG_HIP_CHECK(hipMalloc(d, std::max<size_t>(bytes, 16)));
         MG_HIP_CHECK(hipMemcpy(*d, h, bytes, hipMemcpyHostToDevice));
         return MG_OK;
     };
-    rc = up(records.data(), records.size() * 8, (void **)&pl->d_records);
+    int rc = up(records.data(), records.size() * 8, (void **)&pl->d_records);
     if (rc == MG_OK) rc = up(arec.data(), arec.size() * 8, (void **)&pl->d_align_rec);
     if (rc == MG_OK) rc = up(chan.data(), chan.size() * 4, (void **)&pl->d_chan);
     if (rc == MG_OK) rc = up(slot.data(), slot.size() * 4, (void **)&pl->d_slot);

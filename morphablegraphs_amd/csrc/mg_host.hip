@@ -12,6 +12,7 @@
 
 #include "mg_internal.h"
 #include "mg_constraint_image.h"
+#include "mg_joint_plan.h"
 #include "mg_primitive_image.h"
 #include <dlfcn.h>
 
@@ -1213,23 +1214,14 @@ static int mg_step_plan_impl(const mg_primitive *p, int64_t B, const void *frame
 extern "C" int mg_joint_positions(mg_context *ctx, const mg_skeleton_desc *sk, const int32_t *joints, int32_t n_out,
                                   const double *frames_dev, int64_t n_frames, int32_t n_dim, double *out_dev) {
     MG_REQUIRE(ctx && sk && joints && n_out > 0 && n_frames >= 0 && n_dim >= 3, "mg_joint_positions: bad arguments");
-    MG_REQUIRE(sk->n_joints > 0 && sk->parents && sk->offsets && sk->quat_channel && sk->parents[0] < 0, "mg_joint_positions: incomplete skeleton");
-    std::vector<double> table((size_t)n_out * (1 + 4 * MG_MAX_CHAIN), 0.0);
-    for (int o = 0; o < n_out; o++) {
-        std::vector<int> ch;
-        int bad;
-        const int st = mg_joint_chain(sk->parents, sk->n_joints, joints[o], ch, &bad);
-        MG_REQUIRE(st == MG_CHAIN_OK, "mg_joint_positions: joint %d%s", bad, mg_chain_why(st));
-        const int m = (int)ch.size() - 1;
-        MG_REQUIRE(m <= MG_MAX_CHAIN, "mg_joint_positions: chain of %d joints exceeds %d", m, MG_MAX_CHAIN);
-        for (int k = 0; k < m; k++) {
-            const int qc = sk->quat_channel[ch[(size_t)k]];
-            MG_REQUIRE(qc < 0 || qc + 4 <= n_dim, "mg_joint_positions: quaternion channel %d outside n_dim = %d", qc, n_dim);
-        }
-        double *rec = &table[(size_t)o * (1 + 4 * MG_MAX_CHAIN)];
-        rec[0] = m;
-        mg_chain_links(ch, sk->offsets, [&](int j) { return sk->quat_channel[j]; }, rec + 1);
-    }
+    MG_REQUIRE(mg_skeleton_complete(sk), "mg_joint_positions: incomplete skeleton");
+    mg_joint_plan plan;
+    const mg_plan_failure f = plan.build(sk, joints, n_out, n_dim, true);
+    MG_REQUIRE(!f.of_skeleton(), "mg_joint_positions: joint %d%s", f.joint, mg_chain_why(f.kind));
+    MG_REQUIRE(f.kind != MG_PLAN_TOO_LONG, "mg_joint_positions: chain of %d joints exceeds %d", f.length, MG_MAX_CHAIN);
+    MG_REQUIRE(f.kind != MG_PLAN_CHANNEL_OUTSIDE, "mg_joint_positions: quaternion channel %d outside n_dim = %d", f.channel, n_dim);
+    std::vector<double> table;
+    plan.records(1, 1 + 4 * MG_MAX_CHAIN, table);
     if (n_frames == 0) return MG_OK;
     MG_REQUIRE(frames_dev && out_dev, "mg_joint_positions: NULL pointer");
     { int rc0 = mg_use_device(ctx); if (rc0 != MG_OK) return rc0; }

@@ -22,7 +22,7 @@
 #include <vector>
 
 #include "mg_frame_device.h"
-#include "mg_pack.h"
+#include "mg_joint_plan.h"
 
 #define MG_PC_BLOCK 256
 #define MG_PC_CANDS 4
@@ -88,14 +88,11 @@ extern "C" int mg_point_cloud_features(mg_primitive *p, const mg_time_grid *grid
     MG_REQUIRE(step >= 1, "%s: step %d", who, step);
     MG_REQUIRE(n_joints >= 1 && n_joints <= MG_FEATURE_POINTS_MAX_JOINTS, "%s: %d joints (1 .. %d)", who, n_joints, MG_FEATURE_POINTS_MAX_JOINTS);
     MG_REQUIRE(sk && joints, "%s: no skeleton or no joint list", who);
-    MG_REQUIRE(sk->n_joints > 0 && sk->parents && sk->offsets && sk->quat_channel && sk->parents[0] < 0, "%s: incomplete skeleton", who);
+    MG_REQUIRE(mg_skeleton_complete(sk), "%s: incomplete skeleton", who);
     MG_REQUIRE(out_dev && (n == 0 || latents_dev), "%s: NULL buffer", who);
-    std::vector<std::vector<int>> chains((size_t)n_joints);
-    for (int j = 0; j < n_joints; j++) {
-        int bad;
-        const int st = mg_joint_chain(sk->parents, sk->n_joints, joints[j], chains[(size_t)j], &bad);
-        MG_REQUIRE(st == MG_CHAIN_OK, "%s: joint %d%s", who, bad, mg_chain_why(st));
-    }
+    mg_joint_plan plan;
+    mg_plan_failure f = plan.check(sk, joints, n_joints);
+    MG_REQUIRE(!f, "%s: joint %d%s", who, f.joint, mg_chain_why(f.kind));
     // what the kernel does not take
     const mg_time_grid *g = grid ? grid : p->canonical;
     MG_REQUIRE(!grid || grid->prim == p, "%s: the grid belongs to another primitive", who);
@@ -106,30 +103,15 @@ extern "C" int mg_point_cloud_features(mg_primitive *p, const mg_time_grid *grid
     for (int f = 0; f < F; f++)
         MG_REQUIRE_AS(g->i0[(size_t)f] >= 0 && g->i0[(size_t)f] + 4 <= NB, MG_ERR_UNSUPPORTED, "%s: frame %d takes control points %d .. %d of %d", who, f,
                       g->i0[(size_t)f], g->i0[(size_t)f] + 3, NB);
-    std::vector<char> need((size_t)D, 0);
-    need[0] = need[1] = need[2] = 1;
-    size_t longest = 0;
-    for (const std::vector<int> &ch : chains) {
-        const size_t m = ch.size() - 1;
-        MG_REQUIRE_AS(m <= MG_MAX_CHAIN, MG_ERR_UNSUPPORTED, "%s: chain of %zu joints exceeds %d", who, m, MG_MAX_CHAIN);
-        longest = std::max(longest, m);
-        for (size_t k = 0; k < m; k++) {
-            const int qc = sk->quat_channel[ch[k]];
-            MG_REQUIRE_AS(qc < 0 || qc + 4 <= D, MG_ERR_UNSUPPORTED, "%s: the skeleton's joint %d has channels %d .. %d, the primitive %d", who, ch[k], qc, qc + 3, D);
-            if (qc >= 0) for (int e = 0; e < 4; e++) need[(size_t)qc + e] = 1;
-        }
-    }
+    f = plan.measure(D, true);
+    MG_REQUIRE_AS(f.kind != MG_PLAN_TOO_LONG, MG_ERR_UNSUPPORTED, "%s: chain of %d joints exceeds %d", who, f.length, MG_MAX_CHAIN);
+    MG_REQUIRE_AS(f.kind != MG_PLAN_CHANNEL_OUTSIDE, MG_ERR_UNSUPPORTED, "%s: the skeleton's joint %d has channels %d .. %d, the primitive %d", who, f.joint, f.channel,
+                  f.channel + 3, D);
     // the cached table: the records, then the kept channels and the channel -> slot map
-    const int32_t RS = 1 + 4 * (int32_t)longest;
-    std::vector<double> rec((size_t)n_joints * RS, 0.0);
-    for (int j = 0; j < n_joints; j++) {
-        double *r = &rec[(size_t)j * RS];
-        r[0] = (double)(chains[(size_t)j].size() - 1);
-        mg_chain_links(chains[(size_t)j], sk->offsets, [&](int joint) { return sk->quat_channel[joint]; }, r + 1);
-    }
-    std::vector<int32_t> chan, slot((size_t)D, -1);
-    for (int d = 0; d < D; d++)
-        if (need[(size_t)d]) { slot[(size_t)d] = (int32_t)chan.size(); chan.push_back(d); }
+    std::vector<double> rec;
+    const int32_t RS = plan.records(1, 0, rec);
+    std::vector<int32_t> chan, slot;
+    plan.compact(chan, slot);
     const int n_chan = (int)chan.size();
     const size_t lds = (int64_t)NB * n_chan > (1 << 20) ? (size_t)MG_PC_LDS_MAX + 1 : mg_pc_lds_bytes(NB, n_chan, p->L, n_joints, RS, D);
     MG_REQUIRE_AS(lds <= MG_PC_LDS_MAX, MG_ERR_UNSUPPORTED, "%s: %d basis functions x %d channels for %d candidates and %d joints' chains do not fit LDS", who, NB,

@@ -27,6 +27,7 @@
 #include <hip/hip_ext.h>
 
 #include "mg_construct.h"
+#include "mg_joint_plan.h"
 #include "mg_score_device.h"
 #include "mg_spline_device.h"
 
@@ -263,19 +264,14 @@ extern "C" int mg_walk_frames(int32_t n_steps, mg_primitive *const *prims, const
         a.n_link = 1; a.link[0] = 3;
     } else {
         MG_WALK_REQUIRE(sk != nullptr, "mg_walk_frames: aligning joint %d is not the root: a skeleton is needed", joint);
-        MG_WALK_REQUIRE(sk->n_joints > 0 && sk->parents && sk->quat_channel && sk->parents[0] < 0 && joint >= 0 && joint < sk->n_joints,
+        MG_WALK_REQUIRE(mg_skeleton_complete(sk, false) && joint >= 0 && joint < sk->n_joints,      // (no position is formed: the offsets are not read)
                         "mg_walk_frames: incomplete skeleton or aligning joint %d out of range", joint);
-        std::vector<int> chain;
-        for (int j = joint; j >= 0; j = sk->parents[j]) {
-            MG_WALK_REQUIRE(sk->parents[j] < j, "mg_walk_frames: joint %d: parents must precede their children", j);
-            chain.insert(chain.begin(), j);
-        }
-        for (int j : chain) {
-            const int qc = sk->quat_channel[j];
-            if (qc < 0) continue;
-            MG_WALK_REQUIRE(qc + 4 <= D && a.n_link < MG_MAX_CHAIN, "mg_walk_frames: the aligning chain does not fit (channel %d, n_dim %d)", qc, D);
-            a.link[a.n_link++] = qc;
-        }
+        std::vector<int32_t> quats;
+        const mg_plan_failure f = mg_aligning_quaternions(sk, joint, D, quats);
+        MG_WALK_REQUIRE(!f.of_skeleton(), "mg_walk_frames: joint %d%s", f.joint, mg_chain_why(f.kind));
+        MG_WALK_REQUIRE(!f, "mg_walk_frames: the aligning chain does not fit (channel %d, n_dim %d)", f.channel, D);
+        a.n_link = (int32_t)quats.size();
+        std::copy(quats.begin(), quats.end(), a.link);
     }
     // lengths and offsets: every step inside its walk's rows, no two steps on the same row
     const int64_t nws = n_walks * n_steps;

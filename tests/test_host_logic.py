@@ -456,6 +456,19 @@ def test_primitive_and_grid_images_decode():
     assert done.returncode == 0, done.stdout.decode(errors="replace")
 
 
+def test_joint_plans_hold_the_written_out_values():
+    """csrc/mg_joint_plan.h states once what the entry points that walk a joint list make of a skeleton, the list and a primitive's
+    channels: the chains, their records, the channels they read, the aligning node's quaternions, and the refusals as data;
+    tests/native/joint_plan_check.cpp compares every value with one written out, at the channel and chain-length boundaries, and
+    pins which of two failures comes first.  A program of its own, built and run as pack_check is: nothing is loaded into this
+    process."""
+    import subprocess
+    native = os.path.join(ROOT, "tests", "native")
+    subprocess.check_call(["make", "-s", "-C", native, "joint_plan_check"])
+    done = subprocess.run([os.path.join(native, "joint_plan_check")], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=60)
+    assert done.returncode == 0, done.stdout.decode(errors="replace")
+
+
 def test_keyframe_scorers_route_is_the_restated_one():
     """csrc/mg_score_route.h states once which kernel the keyframe scorers launch (VALU / tile / wide), its LDS, the opt-in and the
     grid; tests/native/score_route_check.cpp holds it to a restatement over a dense grid of k-step counts, row tiles, constraint

@@ -1,7 +1,7 @@
 """The graph-walk sweep without a device (tests/walk_shape_cases.py; the device half is tests/test_gpu_walk_shapes.py).
 
-1. walk_frames_plan, walk_score_plan and walk_time_plan are held to the C text of csrc/mg_walk.hip, mg_walk_score.hip and
-   mg_walk_time.hip line by line, k_steps to mg_primitive_create.
+1. walk_frames_plan, walk_score_plan and walk_time_plan are held to the C text of csrc/mg_walk.hip (its aligning list: csrc/mg_joint_plan.h
+   over mg_pack.h's chain), mg_walk_score.hip and mg_walk_time.hip line by line, k_steps to mg_primitive_create.
 2. FRAME_ROWS lands on both sides of every comparison of walk_frames_plan, and every row takes the routes it names.
 3. The boundaries of the other two plans, as numbers: the packed / staged width, the 64 KiB opt-in and the 150 KiB refusal of the
    score kernel; the chunk count, the register / memory split of the time latents, both arms of wave_doubles and the K = 240 / 241
@@ -59,14 +59,24 @@ def test_restatements_match_the_source():
                  "const bool aligned_any = n_steps > 1 || al != nullptr;", "MG_WALK_REQUIRE(D >= 3 && (!aligned_any || D >= 7),",
                  "if (al->joint == MG_ALIGN_START_POSE) {", "joint = al->joint;",
                  "if (!aligned_any) {", "a.n_link = 0;", "} else if (joint == 0 && !sk) {", "a.n_link = 1; a.link[0] = 3;",
-                 "MG_WALK_REQUIRE(sk != nullptr,", "for (int j = joint; j >= 0; j = sk->parents[j]) {", "chain.insert(chain.begin(), j);",
-                 "if (qc < 0) continue;", "MG_WALK_REQUIRE(qc + 4 <= D && a.n_link < MG_MAX_CHAIN,", "a.link[a.n_link++] = qc;",
+                 "MG_WALK_REQUIRE(sk != nullptr,", "const mg_plan_failure f = mg_aligning_quaternions(sk, joint, D, quats);",
+                 "MG_WALK_REQUIRE(!f, \"mg_walk_frames: the aligning chain does not fit (channel %d, n_dim %d)\", f.channel, D);",
+                 "a.n_link = (int32_t)quats.size();", "std::copy(quats.begin(), quats.end(), a.link);",
                  "const size_t lds_f = ((size_t)rmax + lmax + MG_WALK_TILE * 4) * 8 + MG_WALK_TILE * 4;",
                  "const size_t lds_c = ((size_t)lmax + 5 * (3 + 4 * a.n_link) + 4) * 8 + 16;",
                  "MG_REQUIRE_AS(lds_f <= MG_WALK_LDS_MAX, MG_ERR_UNSUPPORTED,",
                  "tiles += ((lengths ? (int64_t)t_cap : (int64_t)st.T) + MG_WALK_TILE - 1) / MG_WALK_TILE;",
                  "MG_HIP_CHECK(mg_lds_opt_in_once(ctx, MG_LDS_WALK_FRAMES, 160 * 1024,", "a.lmax = lmax; a.rmax = rmax;"):
         assert line in body, line
+    # ... whose aligning list is mg_aligning_quaternions' (mg_joint_plan.h) over mg_joint_chain's chain (mg_pack.h)
+    plan, pack = _csrc("mg_joint_plan.h"), _csrc("mg_pack.h")
+    aligning = plan[plan.index("inline mg_plan_failure mg_aligning_quaternions("):]
+    for line in ("f.kind = mg_joint_chain(sk->parents, sk->n_joints, node, ch, &f.joint);", "for (int j : ch) {", "if (qc < 0) continue;",
+                 "if (qc + 4 > D) { f.kind = MG_PLAN_CHANNEL_OUTSIDE; return f; }",
+                 "if ((int)quats.size() >= MG_MAX_CHAIN) { f.kind = MG_PLAN_TOO_LONG; f.length = MG_MAX_CHAIN + 1; return f; }", "quats.push_back(qc);"):
+        assert line in aligning, line
+    for line in ("for (int j = joint; j >= 0; j = parents ? parents[j] : -1) {", "out.push_back(j);", "std::reverse(out.begin(), out.end());"):
+        assert line in pack, line
     assert body.index("MG_REQUIRE_AS(lds_f <= MG_WALK_LDS_MAX") < body.index("dt.upload(") < body.index("hipLaunchKernelGGL(")      # refused before anything is written
     for line in ("const int nch = 3 + 4 * a.n_link;", "for (int e = tid; e < 5 * nch; e += MG_WALK_CHAIN_BLOCK) {",
                  "const int ch = q < 3 ? q : a.link[(q - 3) >> 2] + ((q - 3) & 3);", "if (!aligned || d >= 7) return v;",

@@ -1123,6 +1123,35 @@ int mg_pca_fit_leading(mg_context *ctx, const double *a_dev, int64_t n, int64_t 
                        double *centred_dev, double *mean, int32_t k_cap, int32_t *k, double *singular_values, double *vt, double *ratios,
                        int32_t *iterations, int32_t *status);
 
+/* ---- scaled functional PCA (reference construction/fpca/scaled_fpca.py, sfpca_objective_func): the joint-space error of the rank-npc
+ * PCA reconstruction of feature-weighted spline coefficients, for a batch of weight vectors; float64, synchronising, bit-reproducible.
+ * A weight vector has 3 + J entries, J = (n_dims - 3) / 4: one per root channel, one per joint (its four quaternion channels share it).
+ * The weights enter only through the projector U_k U_k^T on the sample axis, U the eigenvectors of sum_g w_g^2 G_g with G_g the (n, n)
+ * Gram matrix of group g's centred columns: mg_sfpca_create forms the G_g, the mean's and the centred samples' frames and
+ * the originals' joint positions once; a call combines the G_g, finds the leading eigenvectors by one-sided Jacobi (mg_pca_fit's schedule,
+ * stopping rule, cap of 30 sweeps and sign rule; the kept vectors' means taken out -- ones is the centring's null vector -- and one
+ * Newton-Schulz step on them), and reconstructs, walks the chains and reduces in one fused kernel.
+ *
+ * mg_sfpca_create: coeffs_dev (n, n_basis, n_dims) float64 on the device, as mg_spline_fit_batch leaves it (read during the call only);
+ * joints (n_joints_out) of `skeleton`: the joints whose global positions are compared; design (host, (n_sampled_frames, n_basis)): the
+ * B-spline design rows at the sampled canonical frames.  MG_ERR_UNSUPPORTED, before anything is launched, outside 2 <= n <= 1024,
+ * n_basis <= 64, J <= 64, n_sampled_frames <= 1024, n_joints_out <= 256, or for a chain of more than MG_MAX_CHAIN links;
+ * MG_ERR_INVALID_ARGUMENT for NULL, n_dims not 3 + 4 J, a joint outside the skeleton, non-finite coefficients or design values.
+ *
+ * mg_sfpca_errors: weights (host, (m, n_weights)), n_weights == 3 + J, every entry > 0 and finite; 1 <= npc <= n - 1.  errors (host, m):
+ * the mean over samples, sampled frames and listed joints of the squared distance between the joint's position in the reconstructed and in
+ * the original motion, both evaluated from their control points through `design` and through mg_joint_positions' statements.  statuses
+ * (host, m): 1 converged, 2 stopped at the sweep cap.  A weight vector gives the same bits alone or in any batch.
+ *
+ * mg_sfpca_projector: u_k (host, (n, npc)): the leading eigenvectors as columns, each column's entry of largest magnitude positive (the
+ * first one on ties); a column whose eigenvalue is at most eps n times the largest is zero (it carries none of the data).  status as above. */
+typedef struct mg_sfpca mg_sfpca;
+int mg_sfpca_create(mg_context *ctx, const double *coeffs_dev, int32_t n, int32_t n_basis, int32_t n_dims, const mg_skeleton_desc *skeleton,
+                    const int32_t *joints, int32_t n_joints_out, const double *design, int32_t n_sampled_frames, mg_sfpca **handle);
+int mg_sfpca_errors(mg_sfpca *handle, const double *weights, int32_t m, int32_t n_weights, int32_t npc, double *errors, int32_t *statuses);
+int mg_sfpca_projector(mg_sfpca *handle, const double *weights, int32_t n_weights, int32_t npc, double *u_k, int32_t *status);
+void mg_sfpca_destroy(mg_sfpca *handle);
+
 /* ---- temporal alignment: exact dynamic time warping of motions against one reference motion (reference construction/dtw.py),
  * float64, synchronising, bit-reproducible.  Motions are ragged: motion n has F_n = offsets[n + 1] - offsets[n] frames and its rows
  * start at row offsets[n] of a table; offsets is a HOST array of n_motions + 1 entries, offsets[0] = 0, rising.

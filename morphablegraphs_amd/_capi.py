@@ -123,6 +123,7 @@ EXPORTED_SYMBOLS = [
     "mg_feature_mixture_create", "mg_feature_mixture_destroy", "mg_feature_mixture_info", "mg_feature_mixture_get_image",
     "mg_mixture_scores", "mg_mixture_scores_host",
     "mg_point_cloud_features", "mg_pca_fit_leading",
+    "mg_sfpca_create", "mg_sfpca_errors", "mg_sfpca_projector", "mg_sfpca_destroy",
 ]
 
 
@@ -318,7 +319,7 @@ def load_library(path=None):
     lib.mg_primitive_canonical_grid.argtypes = [C.c_void_p]
     lib.mg_time_grid_size.argtypes = [C.c_void_p]
     for name in ("mg_context_destroy", "mg_primitive_destroy", "mg_time_grid_destroy", "mg_constraint_set_destroy", "mg_trajectory_destroy", "mg_track_plan_destroy",
-                 "mg_cluster_tree_destroy", "mg_feature_mixture_destroy"):
+                 "mg_cluster_tree_destroy", "mg_feature_mixture_destroy", "mg_sfpca_destroy"):
         getattr(lib, name).restype = None
         getattr(lib, name).argtypes = [C.c_void_p]
     vp, i32, i64, u64, dbl = C.c_void_p, C.c_int, C.c_int64, C.c_uint64, C.c_double
@@ -476,6 +477,9 @@ def load_library(path=None):
         "mg_mixture_scores_host": [vp, i32, vp],
         "mg_point_cloud_features": [vp, vp, vp, vp, i32, i32, vp, i32, i64, i64, vp],
         "mg_pca_fit_leading": [vp, vp, i64, i64, dbl, dbl, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp],
+        "mg_sfpca_create": [vp, vp, i32, i32, i32, vp, vp, i32, vp, i32, C.POINTER(vp)],
+        "mg_sfpca_errors": [vp, vp, i32, i32, i32, vp, vp],
+        "mg_sfpca_projector": [vp, vp, i32, i32, vp, vp],
     }
     for name, argtypes in sigs.items():
         fn = getattr(lib, name)
@@ -1803,6 +1807,54 @@ def pca_backproject(ctx, low_dev, vt_dev, mean_dev, n, p, l, high_dev):
     """mg_pca_backproject: high_dev (n, p) = low_dev (n, l) . vt_dev (l, p) + mean_dev (p) (None: no mean)."""
     _check(ctx.lib.mg_pca_backproject(ctx.handle, _dev_ptr(low_dev), _dev_ptr(vt_dev), None if mean_dev is None else _dev_ptr(mean_dev),
                                       int(n), int(p), int(l), _dev_ptr(high_dev)))
+
+
+MG_SFPCA_MAX_SAMPLES, MG_SFPCA_MAX_BASIS, MG_SFPCA_MAX_JOINTS = 1024, 64, 64   # mg_sfpca.hip (include/mg_hip.h)
+
+
+class ScaledFPCA(object):
+    """mg_sfpca_create on the device coefficients coeffs_dev (n, n_basis, n_dims) float64: the handle that scores weight vectors
+    (errors) and returns the leading eigenvectors of one (projector).  skeleton: a Skeleton; joints: the int32 indices of the
+    joints whose positions are compared; design: the (n_sampled_frames, n_basis) B-spline design rows at the sampled frames."""
+
+    def __init__(self, ctx, coeffs_dev, n, n_basis, n_dims, skeleton, joints, design):
+        self.ctx, self.n, self.n_weights = ctx, int(n), 3 + (int(n_dims) - 3) // 4
+        design = np.ascontiguousarray(design, dtype=np.float64)
+        if design.ndim != 2 or design.shape[1] != int(n_basis):
+            raise ValueError("design must be (n_sampled_frames, n_basis = %d), got %s" % (n_basis, design.shape))
+        joints = np.ascontiguousarray(joints, dtype=np.int32).reshape(-1)
+        d = skeleton.desc()
+        h = C.c_void_p()
+        self.handle = None
+        _check(ctx.lib.mg_sfpca_create(ctx.handle, _dev_ptr(coeffs_dev), int(n), int(n_basis), int(n_dims), C.byref(d), _host_ptr(joints), len(joints),
+                                       _host_ptr(design), len(design), C.byref(h)))
+        self.handle = h
+
+    def errors(self, weights, npc):
+        """mg_sfpca_errors: (errors (m,), statuses (m,)) of the weight vectors weights (m, 3 + J)."""
+        w = np.ascontiguousarray(np.atleast_2d(np.asarray(weights, dtype=np.float64)))
+        errors, statuses = np.zeros(len(w)), np.zeros(len(w), dtype=np.int32)
+        _check(self.ctx.lib.mg_sfpca_errors(self.handle, _host_ptr(w), len(w), w.shape[1], int(npc), _host_ptr(errors), _host_ptr(statuses)))
+        return errors, statuses
+
+    def projector(self, weights, npc):
+        """mg_sfpca_projector: (u_k (n, npc), status) of one weight vector."""
+        w = np.ascontiguousarray(np.asarray(weights, dtype=np.float64).reshape(-1))
+        u = np.zeros((self.n, max(int(npc), 1)))
+        status = C.c_int32(0)
+        _check(self.ctx.lib.mg_sfpca_projector(self.handle, _host_ptr(w), len(w), int(npc), _host_ptr(u), C.byref(status)))
+        return u, int(status.value)
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self.ctx.lib.mg_sfpca_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def pca_fit_leading(ctx, a_dev, n, p, centred_dev, fraction, tol=0.0, max_iterations=0, k_cap=64):

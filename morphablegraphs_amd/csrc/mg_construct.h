@@ -96,6 +96,11 @@ struct mg_workspace {
     }
 };
 
+// mg_fpca.hip's batched float64 MFMA product on the context's stream, no synchronise: C[b] (M, Nc; rows ldc apart) = A[b] (M, K; rows lda
+// apart) . B[b] (+ bias[col]), B's element (k, j) at k * sbk + j * sbj; batch b's matrices sAb, sBb, sCb doubles on
+int mg_fpca_gemm(mg_context *ctx, const double *A, const double *B, const double *bias, double *C, int64_t batch, int64_t sAb, int64_t sBb, int64_t sCb,
+                 int64_t M, int64_t Nc, int64_t K, int64_t lda, int64_t sbk, int64_t sbj, int64_t ldc);
+
 // An offsets table of n_motions + 1 entries starts at 0 and rises, no motion longer than max_frames (`limit`: that bound in the
 // caller's words, code_too_long: its status); *longest: the longest motion.
 static inline int mg_check_offsets(const char *who, const int64_t *offsets, int64_t n_motions, int64_t max_frames, const char *limit, int code_too_long,

@@ -94,6 +94,12 @@ static int fp_gemm(mg_context *ctx, const double *A, const double *B, const doub
     return MG_OK;
 }
 
+// the same launches for the other construction files (mg_construct.h)
+int mg_fpca_gemm(mg_context *ctx, const double *A, const double *B, const double *bias, double *C, int64_t batch, int64_t sAb, int64_t sBb, int64_t sCb,
+                 int64_t M, int64_t Nc, int64_t K, int64_t lda, int64_t sbk, int64_t sbj, int64_t ldc) {
+    return fp_gemm(ctx, A, B, bias, C, batch, sAb, sBb, sCb, M, Nc, K, lda, sbk, sbj, ldc);
+}
+
 extern "C" int mg_spline_fit_batch(mg_context *ctx, const double *motions_dev, int64_t n_motions, int32_t n_frames, int32_t n_dims,
                                    const double *operator_dev, int32_t n_basis, double *coeffs_dev) {
     MG_REQUIRE_AS(ctx && motions_dev && operator_dev && coeffs_dev, MG_ERR_INVALID_ARGUMENT, "mg_spline_fit_batch: NULL argument");

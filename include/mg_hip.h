@@ -1296,6 +1296,45 @@ int mg_walk_frames(int32_t n_steps, mg_primitive *const *prims, const int64_t *l
                    const mg_alignment_desc *alignment, const mg_skeleton_desc *skeleton, double *frames_dev, int64_t walk_stride,
                    double *transforms_dev);
 
+/* ---- a population of walks with their own node sequences (csrc/mg_walks_mixed.hip) ---------------------------------
+ * What MotionStateGraph.generate_random_walk produces (reference motion_model/motion_state_graph.py:52-71, motion_state_group.py:
+ * 107-129, 177-214): every walk has its own nodes, its own number of steps and its own frame count per step.  Shared tables:
+ *   prims[n_nodes]           the primitives of the nodes that occur, all of one context and one n_dim
+ *   node_of                  HOST int32 (n_walks, s_max): indices into prims; entries at or past n_steps[w] are not read
+ *   n_steps                  HOST int32 (n_walks), 1 <= n_steps[w] <= s_max
+ * Both calls check the tables before any launch (a node index outside [0, n_nodes), n_steps[w] outside [1, s_max], ld too small for a
+ * node that occurs, primitives of two contexts or widths: MG_ERR_INVALID_ARGUMENT, nothing launched) and carry them to the device in
+ * a cached table of their own (MG_TABLE_WALKS_SAMPLE, MG_TABLE_WALKS_MIXED), rewritten only when it differs from the last call's.
+ * Caps, MG_ERR_UNSUPPORTED: n_walks * s_max of 2^31 on; for the frames, 2^31 tiles of 32 frames on and a node whose control points
+ * do not fit LDS (mg_walk_frames' limit); for the sampler, a mixture of more than 299 dimensions.  s_max itself has no cap.
+ *
+ * mg_walks_sample_latents: ONE launch.  x_dev (n_walks, s_max, ld) of x_dtype; row (w, i), i < n_steps[w], is a draw from the mixture
+ * of node node_of[w][i] over its n_gmm_dims columns; the columns behind them and the rows of steps at or past n_steps[w] are 0.
+ * component_dev: NULL or int32 (n_walks, s_max), -1 for such steps.  With r = w * s_max + i the row's global index:
+ *   component   one Philox4x32-10 word: key (seed & 0xffffffff, seed >> 32), counter (r & 0xffffffff, r >> 32, 0, 1), the first of
+ *               the four outputs (the normals of row r use the counters (r & 0xffffffff, r >> 32, column group, 0)); u = (word +
+ *               0.5) * 2^-32 in float64; the first c with u < cum[c], cum[c] = cum[c - 1] + weights[c] in float64 from cum[0] =
+ *               weights[0] (the weights as given to mg_primitive_create, not normalised); the last component takes what is left;
+ *   values      the normals and x = mu_c + z L_c^T are mg_gmm_sample's statement for global row r under `seed`: the bits of
+ *               mg_gmm_sample_rows(prim, n_walks * s_max, counts = all rows in component c, seed, r, 1, ..).
+ * A row's values depend on (seed, r, its node) only.  Like mg_gmm_sample the draw is validated distributionally against the
+ * reference; it is deterministic on gfx950.
+ *
+ * mg_walks_frames: TWO launches, canonical grids only (time-warped steps: mg_walk_frames per sequence).  latents_dev (n_walks, s_max,
+ * ld): step (w, i) reads the first n_components columns of its own row, the layout the sampler leaves.  frame_offset: HOST int64
+ * (n_walks, s_max), the first output row of every step inside its walk, or NULL: back to back.  alignment, skeleton, frames_dev,
+ * walk_stride as in mg_walk_frames; the alignment is that of every walk's first step.  transforms_dev: NULL or (n_walks, s_max, 4);
+ * the entries of steps at or past n_steps[w] are not written, nor are rows of frames_dev no step owns.  Further
+ * MG_ERR_INVALID_ARGUMENT: steps that overlap or pass walk_stride, a non-root aligning joint without a skeleton.
+ * Contract: walk w's frames and transforms are, bit for bit, those of mg_walk_frames called for that walk alone (n_walks = 1, its
+ * node sequence, its latents packed into one row, the same alignment). */
+int mg_walks_sample_latents(int32_t n_nodes, mg_primitive *const *prims, const int32_t *node_of, const int32_t *n_steps, int64_t n_walks,
+                            int32_t s_max, uint64_t seed, void *x_dev, int x_dtype, int64_t ld, int32_t *component_dev);
+int mg_walks_frames(int32_t n_nodes, mg_primitive *const *prims, const int32_t *node_of, const int32_t *n_steps, const void *latents_dev,
+                    int latent_dtype, int64_t n_walks, int32_t s_max, int64_t ld, const int64_t *frame_offset,
+                    const mg_alignment_desc *alignment, const mg_skeleton_desc *skeleton, double *frames_dev, int64_t walk_stride,
+                    double *transforms_dev);
+
 /* The objective of a whole graph walk in ONE launch (csrc/mg_walk_score.hip): what n_steps calls of mg_score_constraint_residuals
  * [_chained] give when each step's four exit values (MG_CONSTRAINT_VALUE_HEADING x, z; MG_CONSTRAINT_VALUE_POSITION x, z at the step's
  * exit time) are the next step's per-candidate alignment (obj_global_error_sum and its residual-vector forms, reference
@@ -1373,9 +1412,11 @@ int mg_walk_time_table_uploads(mg_context *ctx, int64_t *uploads);   /* mg_conte
 
 /* The per-call descriptor tables a context keeps on the device, each rewritten only when a call's table differs from the last call's:
  * of mg_options_step's one-launch path, mg_cluster_tree_search, mg_walk_frames, mg_score_walk_residuals, mg_score_walk_time and
- * mg_step_lengths, of mg_feature_points, of mg_feature_points_warped and of mg_mixture_scores.  mg_context_table_uploads: how often table `which` of the context went to the device so far. */
+ * mg_step_lengths, of mg_feature_points, of mg_feature_points_warped, of mg_mixture_scores, of mg_point_cloud_features, of mg_walks_frames and
+ * of mg_walks_sample_latents.  mg_context_table_uploads: how often table `which` of the context went to the device so far. */
 enum { MG_TABLE_FUSED = 0, MG_TABLE_TREE = 1, MG_TABLE_WALK = 2, MG_TABLE_WALK_SCORE = 3, MG_TABLE_WALK_TIME = 4, MG_TABLE_STEP_LENGTH = 5,
-       MG_TABLE_FEATURE_POINTS = 6, MG_TABLE_FEATURE_POINTS_WARPED = 7, MG_TABLE_MIXTURE_SCORES = 8, MG_TABLE_POINT_CLOUDS = 9, MG_TABLE_COUNT = 10 };
+       MG_TABLE_FEATURE_POINTS = 6, MG_TABLE_FEATURE_POINTS_WARPED = 7, MG_TABLE_MIXTURE_SCORES = 8, MG_TABLE_POINT_CLOUDS = 9,
+       MG_TABLE_WALKS_MIXED = 10, MG_TABLE_WALKS_SAMPLE = 11, MG_TABLE_COUNT = 12 };
 int mg_context_table_uploads(mg_context *ctx, int which, int64_t *uploads);
 
 /* Step lengths without frames in memory, ONE launch for every candidate of every item (csrc/mg_step_length.hip): what
@@ -1611,6 +1652,16 @@ int mg_walk_frames_host(int32_t n_steps, mg_primitive *const *prims, const int64
                         int64_t n_walks, int64_t ld, const double *times, const int32_t *lengths, int32_t t_cap, const int64_t *frame_offset,
                         const mg_alignment_desc *alignment, const mg_skeleton_desc *skeleton, double *frames, int64_t walk_stride,
                         double *transforms);
+/* mg_walks_sample_latents with x and component in host memory: the device's draw copied back, as mg_gmm_sample_host is mg_gmm_sample's
+ * (the same bits as the device-pointer form) */
+int mg_walks_sample_latents_host(int32_t n_nodes, mg_primitive *const *prims, const int32_t *node_of, const int32_t *n_steps, int64_t n_walks,
+                                 int32_t s_max, uint64_t seed, void *x, int x_dtype, int64_t ld, int32_t *component);
+/* mg_walks_frames with latents, frames and transforms in host memory; `frames` and `transforms` are read first, so what no step owns
+ * keeps its values */
+int mg_walks_frames_host(int32_t n_nodes, mg_primitive *const *prims, const int32_t *node_of, const int32_t *n_steps, const void *latents,
+                         int latent_dtype, int64_t n_walks, int32_t s_max, int64_t ld, const int64_t *frame_offset,
+                         const mg_alignment_desc *alignment, const mg_skeleton_desc *skeleton, double *frames, int64_t walk_stride,
+                         double *transforms);
 int mg_back_project_frames_host(mg_primitive *prim, const mg_time_grid *grid, const void *latents,
                                 int latent_dtype, int64_t n_samples, int64_t ld, float *frames, int path);
 int mg_back_project_frames_f64_host(mg_primitive *prim, const mg_time_grid *grid, const void *latents,

@@ -9,10 +9,11 @@ from .motion_primitive import HipMotionPrimitive, get_context  # noqa: F401
 from .motion_primitive_wrapper import (HipMotionPrimitiveModelWrapper, HipStaticMotionPrimitive,  # noqa: F401
                                        mgrd_json_to_legacy)
 from .motion_spline import HipMotionSpline  # noqa: F401
+from .random_walks import RandomWalks, assemble_walks_mixed_host, choose_random_walks  # noqa: F401
 from .scaled_fpca import HipScaledFunctionalPCA, sfpca_objective_func  # noqa: F401
 from .segmentation import KeyframeDetector, Segmentation  # noqa: F401
 
 __all__ = ["HipFPCASpatialData", "HipFPCATimeSemantic", "HipFunctionalData", "HipGaussianMixture", "HipMotionPrimitive",
            "HipMotionPrimitiveModelWrapper", "HipMotionSpline", "HipPCAFunctionalData", "HipScaledFunctionalPCA", "HipStaticMotionPrimitive", "KeyframeDetector",
-           "Segmentation", "align_frames_temporally", "construct_motion_primitive_model", "get_context", "mgrd_json_to_legacy", "sample_like_sklearn",
+           "RandomWalks", "Segmentation", "align_frames_temporally", "assemble_walks_mixed_host", "choose_random_walks", "construct_motion_primitive_model", "get_context", "mgrd_json_to_legacy", "sample_like_sklearn",
            "sfpca_objective_func"]

@@ -557,22 +557,12 @@ __global__ __launch_bounds__(MG_SAMPLE_BLOCK) void mg_gmm_sample_kernel(mg_sampl
     const int tid = threadIdx.x;
     const int64_t b = a.row_lo + (int64_t)blockIdx.x * MG_SAMPLE_BLOCK + tid;
     if (b < a.row_hi) {
-        double *z = lds_z + (size_t)tid * zs;
-        for (int i = 0; i < L; i += 4) {
-            double zz[4];
-            mg_normal4(b, i >> 2, a.seed, zz);
-            for (int q = 0; q < 4 && i + q < L; q++) z[i + q] = zz[q];
-        }
         int c = 0;
         while (c + 1 < a.K && b >= a.cum[c + 1]) c++;
-        const double *Lc = a.chol + (size_t)c * L * L;
-        const double *mu = a.mean + (size_t)c * L;
-        for (int i = 0; i < L; i++) {
-            double acc = mu[i];
-            for (int j = 0; j <= i; j++) acc = fma(Lc[i * L + j], z[j], acc);
+        mg_gmm_sample_row(b, a.seed, L, lds_z + (size_t)tid * zs, a.chol + (size_t)c * L * L, a.mean + (size_t)c * L, [&](int i, double acc) {
             if (X_F64) ((double *)a.x)[(b - a.row_lo) * a.ld + i] = acc;
             else ((float *)a.x)[(b - a.row_lo) * a.ld + i] = (float)acc;
-        }
+        });
         if (a.comp) a.comp[b - a.row_lo] = c;
     }
 }

@@ -254,3 +254,20 @@ __device__ __forceinline__ void mg_normal4(int64_t b, int q, uint64_t seed, doub
     z[0] = (double)(m0 * __builtin_amdgcn_cosf(a0)); z[1] = (double)(m0 * __builtin_amdgcn_sinf(a0));
     z[2] = (double)(m1 * __builtin_amdgcn_cosf(a1)); z[3] = (double)(m1 * __builtin_amdgcn_sinf(a1));
 }
+
+// One row of the lane-per-row sampler: the standard normals of global row b of the draw under `seed` into z[0 .. L), then
+// x[i] = mu[i] + sum_{j <= i} Lc[i][j] z[j], an fma chain over j ascending from the mean; store(i, x[i]) for i ascending.  Lc: the
+// component's lower Cholesky factor (L, L), mu its mean.  mg_gmm_sample_kernel and mg_walks_sample_kernel draw through this function.
+template <class Store>
+__device__ __forceinline__ void mg_gmm_sample_row(int64_t b, uint64_t seed, int L, double *z, const double *Lc, const double *mu, Store store) {
+    for (int i = 0; i < L; i += 4) {
+        double zz[4];
+        mg_normal4(b, i >> 2, seed, zz);
+        for (int q = 0; q < 4 && i + q < L; q++) z[i + q] = zz[q];
+    }
+    for (int i = 0; i < L; i++) {
+        double acc = mu[i];
+        for (int j = 0; j <= i; j++) acc = fma(Lc[i * L + j], z[j], acc);
+        store(i, acc);
+    }
+}

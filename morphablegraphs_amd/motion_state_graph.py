@@ -5,6 +5,7 @@ n candidates, score them against the path-following constraints, keep the first 
 the option with the smallest error (np.argmin over options, graph_walk_planner.py:191-192).
 Graph loading / transitions / control flow stay in the reference; only the scoring is replaced."""
 import ctypes as C
+import random
 from collections import namedtuple
 
 import numpy as np
@@ -24,6 +25,16 @@ from .motion_primitive_wrapper import HipMotionPrimitiveModelWrapper
 NODE_TYPE_START = "start"
 NODE_TYPE_STANDARD = "standard"
 NODE_TYPE_END = "end"
+
+
+def random_edge(outgoing_edges, accept, rng=random):
+    """One of the edges of `outgoing_edges` (in its order) that `accept(edge_key)` keeps, drawn the way the reference draws it
+    (motion_state_graph_node.py:152-160, 170-181: rng.randrange(0, len(edges), 1)); None without such an edge, and then nothing
+    is drawn."""
+    edges = [edge_key for edge_key in outgoing_edges.keys() if accept(edge_key)]
+    if len(edges) > 0:
+        return edges[rng.randrange(0, len(edges), 1)]
+    return None
 
 
 def arc_length_xz(root_positions):
@@ -55,6 +66,7 @@ class HipMotionStateGraphNode(HipMotionPrimitiveModelWrapper):
     def __init__(self, motion_state_group=None, context=None, device=0):
         super(HipMotionStateGraphNode, self).__init__(context=context, device=device)
         self.motion_state_group = motion_state_group
+        self.motion_state_graph = None     # the graph that holds the node (HipMotionStateGraph._build_nodes)
         self.outgoing_edges = dict()
         self.node_type = NODE_TYPE_STANDARD
         self.n_standard_transitions = 0
@@ -116,6 +128,19 @@ class HipMotionStateGraphNode(HipMotionPrimitiveModelWrapper):
     # ---- transitions (motion_state_graph_node.py:232-272) -----------------------------------------
     def has_transition_model(self, to_node_key):
         return to_node_key in self.outgoing_edges and getattr(self.outgoing_edges[to_node_key], "transition_model", None) is not None
+
+    def generate_random_transition(self, transition_type=NODE_TYPE_STANDARD):
+        """The key of a random transition of that type, or None (motion_state_graph_node.py:144-160); draws from the global
+        `random`, as there."""
+        return random_edge(self.outgoing_edges, lambda key: self.outgoing_edges[key].transition_type == transition_type)
+
+    def generate_random_action_transition(self, elementary_action_name, cycle=False):
+        """The key of a random transition to a start state (with cycle: or a cycle state) of that action, or None
+        (motion_state_graph_node.py:162-181; the reference's `+=` also lengthens the action's own start_states, which is not
+        repeated here)."""
+        info = self.motion_state_graph.node_groups[elementary_action_name]["info"]
+        states = list(info.get("start_states", [])) + (list(info.get("cycle_states", [])) if cycle else [])
+        return random_edge(self.outgoing_edges, lambda key: key[0] == elementary_action_name and key[1] in states)
 
     def predict_parameters(self, to_node_key, current_parameters):
         gmm = self.outgoing_edges[to_node_key].transition_model.predict(current_parameters)
@@ -321,6 +346,7 @@ class HipMotionStateGraph(object):
                 if "spatial_coeffs" in desc["mm"]:
                     continue   # static primitives carry no statistical model (motion_primitive_wrapper.py:61-66)
                 node = HipMotionStateGraphNode(group, context=self.ctx)
+                node.motion_state_graph = self
                 node.init_from_dict(action_data["name"], desc)
                 if "space_partition_pickle" in desc:   # motion_state_graph_node.py:96-97
                     node.cluster_tree = desc["space_partition_pickle"]
@@ -419,6 +445,20 @@ class HipMotionStateGraph(object):
             results[key] = evaluate_samples_using_constraints(samples, node, constraints_per_option[key], prev_frames, skeleton)
         errors = [results[k][1] for k in options]
         return options[int(np.argmin(errors))], results
+
+    # ---- random walks (motion_state_graph.py:52-71; random_walks.py) -------------------------------------------------
+    def generate_random_walk(self, start_action, number_of_steps, use_transition_model=True):
+        """MotionStateGraph.generate_random_walk: a list of {"node_key", "parameters"}; the nodes by the reference's rule from the
+        global `random`, the parameters from the device sampler (one launch for the walk), keyed by a seed taken from NumPy's
+        global stream -- the stream the reference's sampling consumes."""
+        from . import random_walks
+        return random_walks.generate_random_walk(self, start_action, number_of_steps, use_transition_model)
+
+    def generate_random_walks(self, start_action, number_of_steps, n_walks, seed, rng=None, dtype=np.float64):
+        """A population of n_walks random walks (random_walks.RandomWalks): the node sequences from `rng` (a random.Random;
+        default: the global `random`), every step's parameters from ONE mg_walks_sample_latents launch under `seed`."""
+        from . import random_walks
+        return random_walks.generate_random_walks(self, start_action, number_of_steps, n_walks, seed, rng, dtype)
 
     def close(self):
         for node in self.nodes.values():

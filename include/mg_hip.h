@@ -1320,7 +1320,7 @@ int mg_walk_frames(int32_t n_steps, mg_primitive *const *prims, const int64_t *l
  * A row's values depend on (seed, r, its node) only.  Like mg_gmm_sample the draw is validated distributionally against the
  * reference; it is deterministic on gfx950.
  *
- * mg_walks_frames: TWO launches, canonical grids only (time-warped steps: mg_walk_frames per sequence).  latents_dev (n_walks, s_max,
+ * mg_walks_frames: TWO launches, canonical grids (time-warped steps: mg_walks_time_functions, then mg_walks_frames_at, below).  latents_dev (n_walks, s_max,
  * ld): step (w, i) reads the first n_components columns of its own row, the layout the sampler leaves.  frame_offset: HOST int64
  * (n_walks, s_max), the first output row of every step inside its walk, or NULL: back to back.  alignment, skeleton, frames_dev,
  * walk_stride as in mg_walk_frames; the alignment is that of every walk's first step.  transforms_dev: NULL or (n_walks, s_max, 4);
@@ -1334,6 +1334,39 @@ int mg_walks_frames(int32_t n_nodes, mg_primitive *const *prims, const int32_t *
                     int latent_dtype, int64_t n_walks, int32_t s_max, int64_t ld, const int64_t *frame_offset,
                     const mg_alignment_desc *alignment, const mg_skeleton_desc *skeleton, double *frames_dev, int64_t walk_stride,
                     double *transforms_dev);
+
+/* The time-warped motion of such a population: what GraphWalk.convert_graph_walk_to_quaternion_frames(use_time_parameters=True) hands
+ * back (reference motion_generator/graph_walk.py:154-176, back_project(s, True) per step).  The tables and their checks are those above;
+ * each call has a cached table of its own (MG_TABLE_WALKS_TIME, MG_TABLE_WALKS_WARPED).
+ *
+ * mg_walks_time_functions: ONE launch, one wave per (walk, step).  times_dev (n_walks, s_max, t_cap) float64, lengths_dev int32
+ * (n_walks, s_max).  Row (w, i) of a node WITH a time model: gamma = columns n_components .. n_components + n_time_components of the
+ * step's own latent row (the layout the sampler leaves); the row and its length are, bit for bit, mg_time_function_sample_rows' for
+ * that primitive, gamma, speed and t_cap.  Of a node WITHOUT one: numpy.linspace(0, F, int(F * (1 / speed))) -- q * (F / (count - 1)),
+ * the last entry F itself, the single value 0 for a count of 1.  Lengths as in mg_time_function_sample: T where T <= t_cap; -T, the row
+ * not written, where it does not fit; 0 for a time function that is not finite; 0, the row not written, for steps at or past
+ * n_steps[w].  Before any launch, MG_ERR_INVALID_ARGUMENT: speed <= 0 or not finite, a node without a time model whose count is below 1,
+ * ld below a node's n_components + n_time_components; MG_ERR_UNSUPPORTED: a node with a time model and more than 2048 canonical frames
+ * (or fewer than 4), a count above 2^24, n_walks * s_max of 2^31 on.  Does not synchronise.
+ *
+ * mg_walks_frames_at: TWO launches, mg_walks_frames with every step at its own time row.  times_dev (n_walks, s_max, t_cap); lengths and
+ * frame_offset: HOST tables (n_walks, s_max) as in mg_walk_frames, both required.  A step's exit pose -- what the next step is aligned
+ * to -- is taken at the LAST entry of its row; each frame's basis row comes from the FITPACK recurrence at its own time.  Further
+ * MG_ERR_INVALID_ARGUMENT: a length below 1 or above t_cap on a step the walk has; NULL times_dev, lengths or frame_offset; what
+ * mg_walks_frames refuses.  MG_ERR_UNSUPPORTED: the caps of mg_walks_frames.
+ * Contract: walk w's frames and transforms are, bit for bit, those of mg_walk_frames called for that walk alone (n_walks = 1, its node
+ * sequence, its latents packed into one row, its time rows as times_dev (1, n_steps, t_cap), the same lengths, offsets and alignment).
+ * Rows no step owns and transforms of steps the walk does not have are not written.
+ * Out of scope: smoothed time functions (smooth_time_parameters: the Savitzky-Golay pass needs the row on the host) and parameters
+ * predicted by transition models. */
+int mg_walks_time_functions(int32_t n_nodes, mg_primitive *const *prims, const int32_t *node_of, const int32_t *n_steps,
+                            const void *latents_dev, int latent_dtype, int64_t n_walks, int32_t s_max, int64_t ld, double speed,
+                            double *times_dev, int32_t *lengths_dev, int32_t t_cap);
+int mg_walks_frames_at(int32_t n_nodes, mg_primitive *const *prims, const int32_t *node_of, const int32_t *n_steps,
+                       const void *latents_dev, int latent_dtype, int64_t n_walks, int32_t s_max, int64_t ld,
+                       const double *times_dev, const int32_t *lengths, int32_t t_cap, const int64_t *frame_offset,
+                       const mg_alignment_desc *alignment, const mg_skeleton_desc *skeleton, double *frames_dev,
+                       int64_t walk_stride, double *transforms_dev);
 
 /* The objective of a whole graph walk in ONE launch (csrc/mg_walk_score.hip): what n_steps calls of mg_score_constraint_residuals
  * [_chained] give when each step's four exit values (MG_CONSTRAINT_VALUE_HEADING x, z; MG_CONSTRAINT_VALUE_POSITION x, z at the step's
@@ -1412,11 +1445,11 @@ int mg_walk_time_table_uploads(mg_context *ctx, int64_t *uploads);   /* mg_conte
 
 /* The per-call descriptor tables a context keeps on the device, each rewritten only when a call's table differs from the last call's:
  * of mg_options_step's one-launch path, mg_cluster_tree_search, mg_walk_frames, mg_score_walk_residuals, mg_score_walk_time and
- * mg_step_lengths, of mg_feature_points, of mg_feature_points_warped, of mg_mixture_scores, of mg_point_cloud_features, of mg_walks_frames and
- * of mg_walks_sample_latents.  mg_context_table_uploads: how often table `which` of the context went to the device so far. */
+ * mg_step_lengths, of mg_feature_points, of mg_feature_points_warped, of mg_mixture_scores, of mg_point_cloud_features, of mg_walks_frames,
+ * of mg_walks_sample_latents, of mg_walks_frames_at and of mg_walks_time_functions.  mg_context_table_uploads: how often table `which` of the context went to the device so far. */
 enum { MG_TABLE_FUSED = 0, MG_TABLE_TREE = 1, MG_TABLE_WALK = 2, MG_TABLE_WALK_SCORE = 3, MG_TABLE_WALK_TIME = 4, MG_TABLE_STEP_LENGTH = 5,
        MG_TABLE_FEATURE_POINTS = 6, MG_TABLE_FEATURE_POINTS_WARPED = 7, MG_TABLE_MIXTURE_SCORES = 8, MG_TABLE_POINT_CLOUDS = 9,
-       MG_TABLE_WALKS_MIXED = 10, MG_TABLE_WALKS_SAMPLE = 11, MG_TABLE_COUNT = 12 };
+       MG_TABLE_WALKS_MIXED = 10, MG_TABLE_WALKS_SAMPLE = 11, MG_TABLE_WALKS_WARPED = 12, MG_TABLE_WALKS_TIME = 13, MG_TABLE_COUNT = 14 };
 int mg_context_table_uploads(mg_context *ctx, int which, int64_t *uploads);
 
 /* Step lengths without frames in memory, ONE launch for every candidate of every item (csrc/mg_step_length.hip): what
@@ -1662,6 +1695,15 @@ int mg_walks_frames_host(int32_t n_nodes, mg_primitive *const *prims, const int3
                          int latent_dtype, int64_t n_walks, int32_t s_max, int64_t ld, const int64_t *frame_offset,
                          const mg_alignment_desc *alignment, const mg_skeleton_desc *skeleton, double *frames, int64_t walk_stride,
                          double *transforms);
+/* mg_walks_time_functions with latents, times and lengths in host memory; `times` is read first, so rows that are not written keep
+ * their values.  mg_walks_frames_at with latents, times, frames and transforms in host memory, as mg_walks_frames_host. */
+int mg_walks_time_functions_host(int32_t n_nodes, mg_primitive *const *prims, const int32_t *node_of, const int32_t *n_steps,
+                                 const void *latents, int latent_dtype, int64_t n_walks, int32_t s_max, int64_t ld, double speed,
+                                 double *times, int32_t *lengths, int32_t t_cap);
+int mg_walks_frames_at_host(int32_t n_nodes, mg_primitive *const *prims, const int32_t *node_of, const int32_t *n_steps, const void *latents,
+                            int latent_dtype, int64_t n_walks, int32_t s_max, int64_t ld, const double *times, const int32_t *lengths,
+                            int32_t t_cap, const int64_t *frame_offset, const mg_alignment_desc *alignment,
+                            const mg_skeleton_desc *skeleton, double *frames, int64_t walk_stride, double *transforms);
 int mg_back_project_frames_host(mg_primitive *prim, const mg_time_grid *grid, const void *latents,
                                 int latent_dtype, int64_t n_samples, int64_t ld, float *frames, int path);
 int mg_back_project_frames_f64_host(mg_primitive *prim, const mg_time_grid *grid, const void *latents,

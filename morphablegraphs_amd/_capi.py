@@ -42,7 +42,8 @@ PROFILE_SLOTS = {"frames": 0, "gmm_log_prob": 1, "score_constraints": 2, "argmin
                  "cluster_tree_search": 11, "walk_frames": 12, "walk_time": 13, "step_lengths": 14, "feature_points": 15,
                  "feature_points_warped": 16, "mixture_scores": 17, "point_clouds": 18}
 DEVICE_TABLES = {"fused": 0, "tree": 1, "walk": 2, "walk_score": 3, "walk_time": 4, "step_length": 5, "feature_points": 6,
-                 "feature_points_warped": 7, "mixture_scores": 8, "point_clouds": 9, "walks_mixed": 10, "walks_sample": 11}    # MG_TABLE_* (include/mg_hip.h)
+                 "feature_points_warped": 7, "mixture_scores": 8, "point_clouds": 9, "walks_mixed": 10, "walks_sample": 11,
+                 "walks_warped": 12, "walks_time": 13}    # MG_TABLE_* (include/mg_hip.h)
 MG_TREE_MAX_DEPTH, MG_TREE_MAX_CHILDREN, MG_TREE_MAX_CANDIDATES = 64, 256, 64    # include/mg_hip.h
 MG_TREE_TIE, MG_TREE_NO_RESULT, MG_TREE_OVERFLOW, MG_TREE_NO_MEAN = 1, 2, 4, 8
 MG_TREE_MAX_TRAJECTORIES = 4    # root trajectory constraints of one search (mg_cluster_tree_search_trajectories)
@@ -117,6 +118,7 @@ EXPORTED_SYMBOLS = [
     "mg_align_motions_spatially", "mg_prepare_aligned_frames",
     "mg_walk_frames", "mg_walk_frames_host",
     "mg_walks_sample_latents", "mg_walks_sample_latents_host", "mg_walks_frames", "mg_walks_frames_host",
+    "mg_walks_time_functions", "mg_walks_time_functions_host", "mg_walks_frames_at", "mg_walks_frames_at_host",
     "mg_score_walk_residuals", "mg_score_walk_residuals_host", "mg_score_walk_residuals_steps", "mg_score_walk_residuals_steps_host",
     "mg_score_walk_time", "mg_score_walk_time_host", "mg_walk_time_table_uploads", "mg_context_table_uploads",
     "mg_step_lengths", "mg_step_lengths_host",
@@ -461,6 +463,10 @@ def load_library(path=None):
         "mg_walks_sample_latents_host": [i32, vp, vp, vp, i64, i32, u64, vp, i32, i64, vp],
         "mg_walks_frames": [i32, vp, vp, vp, vp, i32, i64, i32, i64, vp, vp, vp, vp, i64, vp],
         "mg_walks_frames_host": [i32, vp, vp, vp, vp, i32, i64, i32, i64, vp, vp, vp, vp, i64, vp],
+        "mg_walks_time_functions": [i32, vp, vp, vp, vp, i32, i64, i32, i64, dbl, vp, vp, i32],
+        "mg_walks_time_functions_host": [i32, vp, vp, vp, vp, i32, i64, i32, i64, dbl, vp, vp, i32],
+        "mg_walks_frames_at": [i32, vp, vp, vp, vp, i32, i64, i32, i64, vp, vp, i32, vp, vp, vp, vp, i64, vp],
+        "mg_walks_frames_at_host": [i32, vp, vp, vp, vp, i32, i64, i32, i64, vp, vp, i32, vp, vp, vp, vp, i64, vp],
         "mg_score_walk_residuals": [i32, vp, vp, i32, i64, i64, vp, i64, vp, vp],
         "mg_score_walk_residuals_host": [i32, vp, vp, i32, i64, i64, vp, i64, vp, vp],
         "mg_score_walk_residuals_steps": [i32, vp, vp, i32, i64, i64, vp, i64, vp, vp, vp],

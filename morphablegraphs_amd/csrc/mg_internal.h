@@ -51,7 +51,7 @@ struct mg_device_table {
 enum { MG_LDS_TRAJECTORY = 1, MG_LDS_TIMEWARP = 2, MG_LDS_JOINT_TRACKS = 4, MG_LDS_FRAME_CONSTRAINTS = 8, MG_LDS_WALK_FRAMES = 16, MG_LDS_WALK_SCORE = 32,
        MG_LDS_WALK_TIME = 64, MG_LDS_STEP_LENGTH_F32 = 128, MG_LDS_STEP_LENGTH_F64 = 256, MG_LDS_FEATURE_POINTS_F32 = 512, MG_LDS_FEATURE_POINTS_F64 = 1024,
        MG_LDS_FEATURE_POINTS_WARPED_F32 = 2048, MG_LDS_FEATURE_POINTS_WARPED_F64 = 4096, MG_LDS_MIXTURE_SCORES = 8192, MG_LDS_POINT_CLOUDS = 16384,
-       MG_LDS_WALKS_FRAMES = 32768, MG_LDS_WALKS_SAMPLE = 65536 };
+       MG_LDS_WALKS_FRAMES = 32768, MG_LDS_WALKS_SAMPLE = 65536, MG_LDS_WALKS_WARPED = 131072, MG_LDS_WALKS_TIME = 262144 };
 
 struct mg_context {
     int device = 0;

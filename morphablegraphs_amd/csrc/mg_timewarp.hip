@@ -22,9 +22,6 @@
 #include "mg_spline_device.h"
 #include "mg_timewarp_device.h"
 
-#define MG_TW_BLOCK 64
-#define MG_TW_MAX_F 2048   // canonical frames the inversion holds in LDS (5 arrays of doubles)
-
 __global__ __launch_bounds__(MG_TW_BLOCK) void mg_timewarp_kernel(const double *__restrict__ tphi, const double *__restrict__ tmean,
                                                                   const void *__restrict__ gamma, int gamma_f64, int64_t ld, int F, int Lt,
                                                                   double inv_speed, double *__restrict__ times, int32_t *__restrict__ lens,

@@ -17,6 +17,9 @@
 #include <cstddef>
 #include <cstdint>
 
+#define MG_TW_BLOCK 64      // one wave per row of samples (mg_timewarp_kernel, mg_walks_time_kernel)
+#define MG_TW_MAX_F 2048   // canonical frames the inversion holds in LDS (4 arrays of doubles)
+
 struct mg_tw_strided {
     double *p;
     int stride;

@@ -1,8 +1,8 @@
 // A population of walks in which every walk has its OWN node sequence (gfx950 / MI355X), float64: the shape of random graph walks
 // (MotionStateGraph.generate_random_walk, reference motion_model/motion_state_graph.py:52-71, motion_state_group.py:177-214), where
 // mg_walk.hip serves the optimiser's batch -- many walks over one sequence.  The nodes that occur travel as a table of per-node
-// records (ctx->tab[MG_TABLE_WALKS_MIXED] / [MG_TABLE_WALKS_SAMPLE]); what mg_walk_step holds per step -- the latent column, the
-// first tile -- is per (walk, step) here.
+// records (ctx->tab[MG_TABLE_WALKS_MIXED] / [MG_TABLE_WALKS_SAMPLE] / [MG_TABLE_WALKS_WARPED] / [MG_TABLE_WALKS_TIME], one per entry
+// point); what mg_walk_step holds per step -- the latent column, the first tile -- is per (walk, step) here.
 //
 //   mg_walks_sample_kernel   one lane per (walk, step): the mixture component from one Philox word of the row's own stream, then the
 //                            lane-per-row sampler's statement (mg_gmm_sample_row, mg_gmm_device.h) for global row w * s_max + i.
@@ -10,9 +10,15 @@
 //   mg_walks_frames_kernel   grid over all tiles of all walks: the walk by bisection in the per-walk tile prefix (mg_item_at's
 //                            search), the step by bisection in the walk's per-step tile starts.
 //
-// The chain and frames kernels restate mg_walk_chain_kernel and mg_walk_frames_kernel (canonical grids) statement by statement over
-// the same device helpers; mg_walk.hip's text is held line by line by tests/test_walk_shapes_host.py and stays where it is.  The
-// contract -- a walk's frames and transforms are the bits of mg_walk_frames for that walk alone -- is tests/test_gpu_random_walks.py's.
+//   mg_walks_time_kernel     one wave per (walk, step): the step's time row -- mg_timewarp_kernel's statements on the time latents of
+//                            the step's own row for a node with a time model, numpy.linspace(0, F, count) for one without.
+//
+// The chain and frames kernels restate mg_walk_chain_kernel and mg_walk_frames_kernel statement by statement over the same device
+// helpers; mg_walk.hip's text is held line by line by tests/test_walk_shapes_host.py and stays where it is.  WARPED = false is the
+// canonical grids (mg_walks_frames), WARPED = true every step at its own time row (mg_walks_frames_at): the step's length from the
+// lengths table, each frame's basis row by the FITPACK recurrence at its own time, the exit pose at the row's last entry.  The
+// contract -- a walk's frames and transforms are the bits of mg_walk_frames for that walk alone -- is tests/test_gpu_random_walks.py's
+// and tests/test_gpu_random_walks_warped.py's.
 #include <cmath>
 #include <cstring>
 
@@ -25,19 +31,26 @@
 #include "mg_joint_plan.h"
 #include "mg_score_device.h"
 #include "mg_spline_device.h"
+#include "mg_timewarp_device.h"
 
-#define MG_WALKS_TILE 32          // frames per workgroup of the frames kernel: mg_walk.hip's MG_WALK_TILE
+#define MG_WALKS_TILE 32         // frames per workgroup of the frames kernel: mg_walk.hip's MG_WALK_TILE
 #define MG_WALKS_BLOCK 256
 #define MG_WALKS_CHAIN_BLOCK 64
 #define MG_WALKS_SAMPLE_BLOCK 64
 #define MG_WALKS_LDS_MAX (160 * 1024 - 64)
 #define MG_WALKS_SAMPLE_LDS_MAX (150 * 1024)
 
-struct mg_walks_node {            // one node's constants on the device (48 bytes): mg_walk_step without lat_off / tile0
-    const double *Et64, *mean;
+struct mg_walks_node {            // one node's constants on the device (56 bytes): mg_walk_step without lat_off / tile0
+    const double *Et64, *mean, *knots;
     const int32_t *i0;            // the canonical grid's tables
     const double *w;
-    int32_t L, R, T, pad;         // T: samples of the canonical grid
+    int32_t L, R, NB, T;          // T: samples of the canonical grid
+};
+
+struct mg_walks_time_node {       // what a node's time row is made of (32 bytes)
+    const double *tphi, *tmean;   // [F][Lt], [F]; NULL for a node without a time model
+    int32_t F, Lt, L;             // canonical frames; time latents, in columns L .. L + Lt of a step's row
+    int32_t count;                // Lt == 0: samples of numpy.linspace(0, F, count)
 };
 
 struct mg_walks_mixture {         // one node's mixture on the device (32 bytes)
@@ -53,12 +66,14 @@ struct mg_walks_args {
     const int32_t *walk_tile;     // (n_walks + 1): the first tile of every walk
     const int32_t *step_tile;     // (n_walks, s_max): the first tile of a step among its walk's tiles
     const int64_t *frame_offset;  // (n_walks, s_max)
+    const int32_t *lengths;       // WARPED: (n_walks, s_max), the samples of every step's time row
+    const double *times;          // WARPED: (n_walks, s_max, t_cap)
     const void *lat;              // (n_walks, s_max, ld)
     double *xf;                   // (n_walks, s_max, 8): c, s, tx, tz, ty, cos(phi / 2), sin(phi / 2), 1 if the step is aligned
     double *transforms;           // NULL or (n_walks, s_max, 4)
     double *frames;
     int64_t n_walks, ld, walk_stride;
-    int32_t s_max, D;
+    int32_t s_max, D, t_cap;
     int32_t lmax, rmax;           // the longest latent row and the most control-point rows of a node: LDS pitches
     int32_t align_mode;           // first step: 0 as it is, 1 previous frame, 2 start pose
     int32_t n_link;               // animated joints along the aligning node's chain
@@ -111,7 +126,76 @@ __global__ __launch_bounds__(MG_WALKS_SAMPLE_BLOCK) void mg_walks_sample_kernel(
     if (a.comp) a.comp[r] = c;
 }
 
+struct mg_walks_time_args {
+    const mg_walks_time_node *nodes;
+    const int32_t *node_of, *n_steps;
+    const void *lat;              // (n_walks, s_max, ld)
+    double *times;                // (n_walks, s_max, t_cap)
+    int32_t *lens;                // (n_walks, s_max)
+    int64_t ld;
+    double inv_speed;
+    int32_t s_max, t_cap;
+};
+
+// Row (w, i) of a node with a time model: mg_timewarp_kernel (mg_timewarp.hip) statement by statement, gamma read from the step's own
+// latent row.  Of a node without one: numpy.linspace(0, F, count) = arange(count) * (F / (count - 1)), the last one F itself.
 template <bool LAT_F64>
+__global__ __launch_bounds__(MG_TW_BLOCK) void mg_walks_time_kernel(const mg_walks_time_args a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int64_t ws = blockIdx.x, wk = ws / a.s_max;
+    const int tid = threadIdx.x;
+    if ((int)(ws - wk * a.s_max) >= a.n_steps[wk]) {   // a step the walk does not have: length 0, nothing else written
+        if (tid == 0) a.lens[ws] = 0;
+        return;
+    }
+    const mg_walks_time_node nd = a.nodes[a.node_of[ws]];
+    const int F = nd.F;
+    double *tb = a.times + ws * (int64_t)a.t_cap;
+    if (nd.Lt == 0) {
+        const int T = nd.count;
+        if (tid == 0) a.lens[ws] = T <= a.t_cap ? T : -T;
+        if (T > a.t_cap) return;
+        const double step = T > 1 ? (double)F / (double)(T - 1) : 0.0;
+        for (int j = tid; j < T; j += MG_TW_BLOCK) tb[j] = (j == T - 1 && T > 1) ? (double)F : (double)j * step;
+        return;
+    }
+    double *x = (double *)smem;      // [F] the canonical time function t(t'): the spline's abscissae; ordinates are 0 .. F-1
+    double *M = x + F;               // [F] second derivatives
+    double *cp = M + F;              // [F] Thomas: modified upper diagonal
+    double *dp = cp + F;             // [F] Thomas: modified right-hand side
+    const int64_t g0 = ws * a.ld + nd.L;
+    for (int i = tid; i < F; i += MG_TW_BLOCK)   // the increments (parked in M)
+        M[i] = mg_tw_increment(nd.tphi, nd.tmean, i, nd.Lt, [&](int l) { return mg_load_lat<LAT_F64>(a.lat, g0 + l); });
+    __syncthreads();
+    if (tid == 0) {
+        mg_tw_running_sum(M, x, F);
+        mg_tw_second_derivatives(x, M, cp, dp, F, 1);
+    }
+    __syncthreads();
+    // the samples: 0, the inverse spline at linspace(1, x[F-2], num), F - 1
+    const double stop = x[F - 2];
+    int num;
+    if (!mg_tw_sample_count(stop, a.inv_speed, num)) {   // no row: length 0, nothing written
+        if (tid == 0) a.lens[ws] = 0;
+        return;
+    }
+    const int T = num + 2;
+    if (tid == 0) a.lens[ws] = T <= a.t_cap ? T : -T;   // (negative: the caller's rows are too short; nothing else is written)
+    if (T > a.t_cap) return;
+    const double step = mg_tw_sample_step(stop, num);
+    for (int j = tid; j < T; j += MG_TW_BLOCK) {
+        double v;
+        if (j == 0) v = 0.0;
+        else if (j == T - 1) v = (double)(F - 1);
+        else {
+            const double t = mg_tw_sample_point(j - 1, num, stop, step);
+            v = mg_tw_inverse_at(x, M, mg_tw_interval(x, F, t), t);
+        }
+        tb[j] = v;
+    }
+}
+
+template <bool LAT_F64, bool WARPED>
 __global__ __launch_bounds__(MG_WALKS_CHAIN_BLOCK) void mg_walks_chain_kernel(const mg_walks_args a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int nch = 3 + 4 * a.n_link;
@@ -128,8 +212,12 @@ __global__ __launch_bounds__(MG_WALKS_CHAIN_BLOCK) void mg_walks_chain_kernel(co
         const mg_walks_node st = a.nodes[a.node_of[ws]];
         for (int k = tid; k < st.L; k += MG_WALKS_CHAIN_BLOCK) s[k] = mg_load_lat<LAT_F64>(a.lat, ws * a.ld + k);
         if (tid == 0) {
-            *i0l = st.i0[st.T - 1];
-            for (int j = 0; j < 4; j++) wl[j] = st.w[4 * (size_t)(st.T - 1) + j];
+            if (WARPED) {              // the exit pose follows the step's time row: its last entry
+                mg_basis_row_dev(st.knots, st.NB + 4, a.times[ws * a.t_cap + a.lengths[ws] - 1], i0l, wl);
+            } else {
+                *i0l = st.i0[st.T - 1];
+                for (int j = 0; j < 4; j++) wl[j] = st.w[4 * (size_t)(st.T - 1) + j];
+            }
         }
         __syncthreads();
         const int il = *i0l;
@@ -194,7 +282,7 @@ __device__ __forceinline__ int mg_walks_last_not_past(const int32_t *starts, int
     return lo;
 }
 
-template <bool LAT_F64>
+template <bool LAT_F64, bool WARPED>
 __global__ __launch_bounds__(MG_WALKS_BLOCK) void mg_walks_frames_kernel(const mg_walks_args a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     double *cp = (double *)smem;                    // [rows of the tile's window][D], at most rmax doubles
@@ -206,14 +294,18 @@ __global__ __launch_bounds__(MG_WALKS_BLOCK) void mg_walks_frames_kernel(const m
     const int i = mg_walks_last_not_past(a.step_tile + wk * a.s_max, a.n_steps[wk], kt);
     const int64_t ws = wk * a.s_max + i;
     const mg_walks_node st = a.nodes[a.node_of[ws]];
-    const int len = st.T;
+    const int len = WARPED ? a.lengths[ws] : st.T;
     const int f0 = (kt - a.step_tile[ws]) * MG_WALKS_TILE;
     if (f0 >= len) return;
     const int nf = len - f0 < MG_WALKS_TILE ? len - f0 : MG_WALKS_TILE;
     const int tid = threadIdx.x, D = a.D;
     if (tid < nf) {
-        i0t[tid] = st.i0[f0 + tid];
-        for (int j = 0; j < 4; j++) wt[4 * tid + j] = st.w[4 * (size_t)(f0 + tid) + j];
+        if (WARPED) {
+            mg_basis_row_dev(st.knots, st.NB + 4, a.times[ws * a.t_cap + f0 + tid], &i0t[tid], &wt[4 * tid]);
+        } else {
+            i0t[tid] = st.i0[f0 + tid];
+            for (int j = 0; j < 4; j++) wt[4 * tid + j] = st.w[4 * (size_t)(f0 + tid) + j];
+        }
     }
     for (int k = tid; k < st.L; k += MG_WALKS_BLOCK) s[k] = mg_load_lat<LAT_F64>(a.lat, ws * a.ld + k);
     __syncthreads();
@@ -343,14 +435,20 @@ extern "C" int mg_walks_sample_latents(int32_t n_nodes, mg_primitive *const *pri
     return MG_OK;
 }
 
-extern "C" int mg_walks_frames(int32_t n_nodes, mg_primitive *const *prims, const int32_t *node_of, const int32_t *n_steps, const void *latents_dev, int dtype,
-                               int64_t n_walks, int32_t s_max, int64_t ld, const int64_t *frame_offset, const mg_alignment_desc *al,
-                               const mg_skeleton_desc *sk, double *frames_dev, int64_t walk_stride, double *transforms_dev) {
-    const char *who = "mg_walks_frames";
+// mg_walks_frames (WARPED = false: times_dev, lengths NULL) and mg_walks_frames_at (WARPED = true), each with a table of its own
+template <bool WARPED>
+static int mg_walks_frames_launch(const char *who, int table, unsigned lds_bit, int32_t n_nodes, mg_primitive *const *prims, const int32_t *node_of,
+                                  const int32_t *n_steps, const void *latents_dev, int dtype, int64_t n_walks, int32_t s_max, int64_t ld, const double *times_dev,
+                                  const int32_t *lengths, int32_t t_cap, const int64_t *frame_offset, const mg_alignment_desc *al, const mg_skeleton_desc *sk,
+                                  double *frames_dev, int64_t walk_stride, double *transforms_dev) {
     std::vector<char> occurs;
     int rc = mg_walks_check_tables(who, n_nodes, prims, node_of, n_steps, n_walks, s_max, occurs);
     if (rc != MG_OK) return rc;
     MG_WALKS_REQUIRE((dtype == MG_F32 || dtype == MG_F64) && ld >= 1 && walk_stride >= 1, "%s: bad arguments", who);
+    if (WARPED) {
+        MG_WALKS_REQUIRE(t_cap >= 1, "%s: t_cap %d", who, t_cap);
+        MG_WALKS_REQUIRE(n_walks == 0 || (times_dev && lengths && frame_offset), "%s: times, lengths and frame offsets are required", who);
+    }
     mg_context *ctx = prims[0]->ctx;
     const int D = prims[0]->D;
     int lmax = 0, rmax = 0;
@@ -407,7 +505,9 @@ extern "C" int mg_walks_frames(int32_t n_nodes, mg_primitive *const *prims, cons
         int64_t next = 0, walk_tiles = 0;
         spans.clear();
         for (int i = 0; i < n_steps[w]; i++) {
-            const int64_t ws = w * s_max + i, len = prims[node_of[ws]]->canonical->T;
+            const int64_t ws = w * s_max + i, len = WARPED ? lengths[ws] : prims[node_of[ws]]->canonical->T;
+            MG_WALKS_REQUIRE(!WARPED || (len >= 1 && len <= t_cap), "%s: walk %lld, step %d has %lld samples (1 .. t_cap = %d)", who, (long long)w, i, (long long)len,
+                             t_cap);
             const int64_t off = frame_offset ? frame_offset[ws] : next;
             MG_WALKS_REQUIRE(off >= 0, "%s: walk %lld, step %d starts at row %lld", who, (long long)w, i, (long long)off);
             offs[(size_t)ws] = off;
@@ -437,15 +537,16 @@ extern "C" int mg_walks_frames(int32_t n_nodes, mg_primitive *const *prims, cons
     for (int k = 0; k < n_nodes; k++) {
         const mg_primitive *p = prims[k];
         mg_walks_node nd;
-        nd.Et64 = p->d_Et64; nd.mean = p->d_mean; nd.i0 = p->canonical->d_i0; nd.w = p->canonical->d_w;
-        nd.L = p->L; nd.R = p->R; nd.T = p->canonical->T; nd.pad = 0;
+        nd.Et64 = p->d_Et64; nd.mean = p->d_mean; nd.knots = p->d_knots; nd.i0 = p->canonical->d_i0; nd.w = p->canonical->d_w;
+        nd.L = p->L; nd.R = p->R; nd.NB = p->NB; nd.T = p->canonical->T;
         memcpy(tab.data() + (size_t)k * sizeof(nd), &nd, sizeof(nd));
     }
     const size_t off_offs = mg_table_append(tab, offs.data(), (size_t)nws * 8);
     const size_t off_node = mg_table_append(tab, node_of, (size_t)nws * 4), off_steps = mg_table_append(tab, n_steps, (size_t)n_walks * 4);
     const size_t off_wtile = mg_table_append(tab, walk_tile.data(), walk_tile.size() * 4), off_stile = mg_table_append(tab, step_tile.data(), (size_t)nws * 4);
+    const size_t off_lens = WARPED ? mg_table_append(tab, lengths, (size_t)nws * 4) : 0;
     MG_HIP_CHECK(hipSetDevice(ctx->device));
-    mg_device_table &dt = ctx->tab[MG_TABLE_WALKS_MIXED];
+    mg_device_table &dt = ctx->tab[table];
     rc = dt.upload(ctx, who, tab.data(), tab.size(), 0, (size_t)nws * 8 * 8);   // behind the table: the steps' transforms
     if (rc != MG_OK) return rc;
     char *base = dt.base();
@@ -453,19 +554,90 @@ extern "C" int mg_walks_frames(int32_t n_nodes, mg_primitive *const *prims, cons
     a.frame_offset = (const int64_t *)(base + off_offs);
     a.node_of = (const int32_t *)(base + off_node); a.n_steps = (const int32_t *)(base + off_steps);
     a.walk_tile = (const int32_t *)(base + off_wtile); a.step_tile = (const int32_t *)(base + off_stile);
+    a.lengths = WARPED ? (const int32_t *)(base + off_lens) : nullptr;
+    a.times = times_dev; a.t_cap = t_cap;
     a.lat = latents_dev;
     a.xf = (double *)dt.scratch();
     a.transforms = transforms_dev; a.frames = frames_dev;
     a.n_walks = n_walks; a.ld = ld; a.walk_stride = walk_stride;
     a.s_max = s_max; a.D = D; a.lmax = lmax; a.rmax = rmax;
-    MG_HIP_CHECK(mg_lds_opt_in_once(ctx, MG_LDS_WALKS_FRAMES, 160 * 1024, mg_walks_frames_kernel<true>, mg_walks_frames_kernel<false>));
+    MG_HIP_CHECK(mg_lds_opt_in_once(ctx, lds_bit, 160 * 1024, mg_walks_frames_kernel<true, WARPED>, mg_walks_frames_kernel<false, WARPED>));
     hipStream_t st = ctx->stream;
     const bool lf = dtype == MG_F64;
-    if (lf) hipLaunchKernelGGL(mg_walks_chain_kernel<true>, dim3((unsigned)n_walks), dim3(MG_WALKS_CHAIN_BLOCK), lds_c, st, a);
-    else hipLaunchKernelGGL(mg_walks_chain_kernel<false>, dim3((unsigned)n_walks), dim3(MG_WALKS_CHAIN_BLOCK), lds_c, st, a);
+    if (lf) hipLaunchKernelGGL((mg_walks_chain_kernel<true, WARPED>), dim3((unsigned)n_walks), dim3(MG_WALKS_CHAIN_BLOCK), lds_c, st, a);
+    else hipLaunchKernelGGL((mg_walks_chain_kernel<false, WARPED>), dim3((unsigned)n_walks), dim3(MG_WALKS_CHAIN_BLOCK), lds_c, st, a);
     MG_HIP_CHECK(hipGetLastError());
-    if (lf) hipLaunchKernelGGL(mg_walks_frames_kernel<true>, dim3((unsigned)tiles), dim3(MG_WALKS_BLOCK), lds_f, st, a);
-    else hipLaunchKernelGGL(mg_walks_frames_kernel<false>, dim3((unsigned)tiles), dim3(MG_WALKS_BLOCK), lds_f, st, a);
+    if (lf) hipLaunchKernelGGL((mg_walks_frames_kernel<true, WARPED>), dim3((unsigned)tiles), dim3(MG_WALKS_BLOCK), lds_f, st, a);
+    else hipLaunchKernelGGL((mg_walks_frames_kernel<false, WARPED>), dim3((unsigned)tiles), dim3(MG_WALKS_BLOCK), lds_f, st, a);
+    MG_HIP_CHECK(hipGetLastError());
+    return MG_OK;
+}
+
+extern "C" int mg_walks_frames(int32_t n_nodes, mg_primitive *const *prims, const int32_t *node_of, const int32_t *n_steps, const void *latents_dev, int dtype,
+                               int64_t n_walks, int32_t s_max, int64_t ld, const int64_t *frame_offset, const mg_alignment_desc *al,
+                               const mg_skeleton_desc *sk, double *frames_dev, int64_t walk_stride, double *transforms_dev) {
+    return mg_walks_frames_launch<false>("mg_walks_frames", MG_TABLE_WALKS_MIXED, MG_LDS_WALKS_FRAMES, n_nodes, prims, node_of, n_steps, latents_dev, dtype, n_walks,
+                                         s_max, ld, nullptr, nullptr, 0, frame_offset, al, sk, frames_dev, walk_stride, transforms_dev);
+}
+
+extern "C" int mg_walks_frames_at(int32_t n_nodes, mg_primitive *const *prims, const int32_t *node_of, const int32_t *n_steps, const void *latents_dev, int dtype,
+                                  int64_t n_walks, int32_t s_max, int64_t ld, const double *times_dev, const int32_t *lengths, int32_t t_cap,
+                                  const int64_t *frame_offset, const mg_alignment_desc *al, const mg_skeleton_desc *sk, double *frames_dev, int64_t walk_stride,
+                                  double *transforms_dev) {
+    return mg_walks_frames_launch<true>("mg_walks_frames_at", MG_TABLE_WALKS_WARPED, MG_LDS_WALKS_WARPED, n_nodes, prims, node_of, n_steps, latents_dev, dtype,
+                                        n_walks, s_max, ld, times_dev, lengths, t_cap, frame_offset, al, sk, frames_dev, walk_stride, transforms_dev);
+}
+
+// Every step's time row.  What a row is made of is a node's; which node, and where gamma lies, is the step's.
+extern "C" int mg_walks_time_functions(int32_t n_nodes, mg_primitive *const *prims, const int32_t *node_of, const int32_t *n_steps, const void *latents_dev,
+                                       int dtype, int64_t n_walks, int32_t s_max, int64_t ld, double speed, double *times_dev, int32_t *lengths_dev,
+                                       int32_t t_cap) {
+    const char *who = "mg_walks_time_functions";
+    std::vector<char> occurs;
+    int rc = mg_walks_check_tables(who, n_nodes, prims, node_of, n_steps, n_walks, s_max, occurs);
+    if (rc != MG_OK) return rc;
+    MG_WALKS_REQUIRE((dtype == MG_F32 || dtype == MG_F64) && ld >= 1 && t_cap >= 1, "%s: bad arguments", who);
+    MG_WALKS_REQUIRE(speed > 0.0 && std::isfinite(speed), "%s: speed must be positive and finite", who);
+    const double inv_speed = 1.0 / speed;
+    std::vector<mg_walks_time_node> nodes((size_t)n_nodes);
+    int fmax = 0;
+    for (int k = 0; k < n_nodes; k++) {
+        const mg_primitive *p = prims[k];
+        mg_walks_time_node &nd = nodes[(size_t)k];
+        nd.tphi = p->Lt > 0 ? p->d_tphi : nullptr; nd.tmean = p->Lt > 0 ? p->d_tmean : nullptr;
+        nd.F = p->F; nd.Lt = p->Lt; nd.L = p->L; nd.count = 0;
+        if (!occurs[(size_t)k]) continue;
+        MG_WALKS_REQUIRE(p->L + p->Lt <= ld, "%s: node %d reads %d latent columns, ld is %lld", who, k, p->L + p->Lt, (long long)ld);
+        if (p->Lt > 0) {
+            MG_REQUIRE_AS(p->F >= 4 && p->F <= MG_TW_MAX_F, MG_ERR_UNSUPPORTED, "%s: node %d has %d canonical frames (4 .. %d supported)", who, k, p->F, MG_TW_MAX_F);
+            fmax = std::max(fmax, (int)p->F);
+        } else {
+            const double countf = (double)p->F * inv_speed;   // int(F * (1 / speed)), numpy.linspace's num
+            MG_WALKS_REQUIRE(countf >= 1.0, "%s: node %d of %d canonical frames has no sample at speed %g", who, k, p->F, speed);
+            MG_REQUIRE_AS(countf <= 16777216.0, MG_ERR_UNSUPPORTED, "%s: node %d asks for %g samples at speed %g", who, k, countf, speed);
+            nd.count = (int32_t)countf;
+        }
+    }
+    if (n_walks == 0) return MG_OK;
+    MG_WALKS_REQUIRE(latents_dev && times_dev && lengths_dev, "%s: NULL pointer", who);
+    mg_context *ctx = prims[0]->ctx;
+    const int64_t rows = n_walks * s_max;
+    std::vector<unsigned char> tab((size_t)n_nodes * sizeof(mg_walks_time_node));
+    memcpy(tab.data(), nodes.data(), tab.size());
+    const size_t off_node = mg_table_append(tab, node_of, (size_t)rows * 4), off_steps = mg_table_append(tab, n_steps, (size_t)n_walks * 4);
+    MG_HIP_CHECK(hipSetDevice(ctx->device));
+    mg_device_table &dt = ctx->tab[MG_TABLE_WALKS_TIME];
+    rc = dt.upload(ctx, who, tab.data(), tab.size());
+    if (rc != MG_OK) return rc;
+    mg_walks_time_args a;
+    a.nodes = (const mg_walks_time_node *)dt.base();
+    a.node_of = (const int32_t *)(dt.base() + off_node); a.n_steps = (const int32_t *)(dt.base() + off_steps);
+    a.lat = latents_dev; a.times = times_dev; a.lens = lengths_dev;
+    a.ld = ld; a.inv_speed = inv_speed; a.s_max = s_max; a.t_cap = t_cap;
+    const size_t lds = (size_t)4 * fmax * 8;   // x, M, cp, dp of the longest timed node that occurs
+    MG_HIP_CHECK(mg_lds_opt_in_once(ctx, MG_LDS_WALKS_TIME, 160 * 1024, mg_walks_time_kernel<true>, mg_walks_time_kernel<false>));
+    if (dtype == MG_F64) hipLaunchKernelGGL(mg_walks_time_kernel<true>, dim3((unsigned)rows), dim3(MG_TW_BLOCK), lds, ctx->stream, a);
+    else hipLaunchKernelGGL(mg_walks_time_kernel<false>, dim3((unsigned)rows), dim3(MG_TW_BLOCK), lds, ctx->stream, a);
     MG_HIP_CHECK(hipGetLastError());
     return MG_OK;
 }
@@ -502,6 +674,46 @@ extern "C" int mg_walks_frames_host(int32_t n_nodes, mg_primitive *const *prims,
     if (rc != MG_OK) return rc;
     rc = mg_walks_frames(n_nodes, prims, node_of, n_steps, d_lat.dev<void>(), dtype, n_walks, s_max, ld, frame_offset, al, sk, d_frames.dev<double>(),
                          walk_stride, d_xf.dev<double>());
+    if (rc != MG_OK) return rc;
+    return ws.download();
+}
+
+extern "C" int mg_walks_time_functions_host(int32_t n_nodes, mg_primitive *const *prims, const int32_t *node_of, const int32_t *n_steps, const void *latents,
+                                            int dtype, int64_t n_walks, int32_t s_max, int64_t ld, double speed, double *times, int32_t *lengths, int32_t t_cap) {
+    MG_WALKS_REQUIRE(n_nodes >= 1 && prims && prims[0] && n_walks >= 0 && s_max >= 1 && ld >= 1 && t_cap >= 1 && (dtype == MG_F32 || dtype == MG_F64),
+                     "mg_walks_time_functions_host: bad arguments");
+    MG_WALKS_REQUIRE(n_walks == 0 || (latents && times && lengths), "mg_walks_time_functions_host: NULL pointer");
+    mg_workspace ws(prims[0]->ctx, "mg_walks_time_functions_host");
+    const mg_staged d_lat = ws.in(latents, (size_t)(n_walks * s_max * ld) * (dtype == MG_F64 ? 8 : 4));
+    const mg_staged d_times = ws.inout(times, (size_t)(n_walks * s_max * t_cap) * 8);   // rows that are not written stay the caller's
+    const mg_staged d_lens = ws.out(lengths, (size_t)(n_walks * s_max) * 4);
+    int rc = ws.upload();
+    if (rc != MG_OK) return rc;
+    rc = mg_walks_time_functions(n_nodes, prims, node_of, n_steps, d_lat.dev<void>(), dtype, n_walks, s_max, ld, speed, d_times.dev<double>(),
+                                 d_lens.dev<int32_t>(), t_cap);
+    if (rc != MG_OK) return rc;
+    return ws.download();
+}
+
+extern "C" int mg_walks_frames_at_host(int32_t n_nodes, mg_primitive *const *prims, const int32_t *node_of, const int32_t *n_steps, const void *latents, int dtype,
+                                       int64_t n_walks, int32_t s_max, int64_t ld, const double *times, const int32_t *lengths, int32_t t_cap,
+                                       const int64_t *frame_offset, const mg_alignment_desc *al, const mg_skeleton_desc *sk, double *frames, int64_t walk_stride,
+                                       double *transforms) {
+    MG_WALKS_REQUIRE(n_nodes >= 1 && prims && prims[0] && n_walks >= 0 && s_max >= 1 && ld >= 1 && walk_stride >= 1 && t_cap >= 1 &&
+                         (dtype == MG_F32 || dtype == MG_F64),
+                     "mg_walks_frames_at_host: bad arguments");
+    MG_WALKS_REQUIRE(n_walks == 0 || (latents && frames && times), "mg_walks_frames_at_host: NULL pointer");
+    mg_context *ctx = prims[0]->ctx;
+    const int64_t D = prims[0]->D;
+    mg_workspace ws(ctx, "mg_walks_frames_at_host");
+    const mg_staged d_lat = ws.in(latents, (size_t)(n_walks * s_max * ld) * (dtype == MG_F64 ? 8 : 4));
+    const mg_staged d_times = ws.in(times, (size_t)(n_walks * s_max * t_cap) * 8);
+    const mg_staged d_frames = ws.inout(frames, (size_t)(n_walks * walk_stride * D) * 8);   // rows no step owns stay the caller's
+    const mg_staged d_xf = ws.inout(transforms, (size_t)(n_walks * s_max * 4) * 8);          // ... and the entries of steps a walk does not have
+    int rc = ws.upload();
+    if (rc != MG_OK) return rc;
+    rc = mg_walks_frames_at(n_nodes, prims, node_of, n_steps, d_lat.dev<void>(), dtype, n_walks, s_max, ld, d_times.dev<double>(), lengths, t_cap, frame_offset, al,
+                            sk, d_frames.dev<double>(), walk_stride, d_xf.dev<double>());
     if (rc != MG_OK) return rc;
     return ws.download();
 }

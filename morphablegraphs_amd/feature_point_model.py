@@ -128,16 +128,16 @@ def canonical_time_function_host(time_model, F, gamma):
     return np.array(out[1:]) - 1.0
 
 
-def sample_time_function_host(canonical):
-    """The spline's time function at speed 1 (motion_primitive.py:304-319) as HipMotionPrimitive._invert_canonical_to_sample_
-    time_function states it: 0, scipy's interpolating cubic through (t(t'), t') at linspace(1, t(F - 2), int(round(t(F - 2)))),
-    F - 1.  None for a time function that is not finite or asks for more than 2^24 samples (the kernels' test)."""
+def sample_time_function_host(canonical, speed=1.0):
+    """The spline's time function (motion_primitive.py:304-319) as HipMotionPrimitive._invert_canonical_to_sample_
+    time_function states it: 0, scipy's interpolating cubic through (t(t'), t') at linspace(1, t(F - 2), int(round(t(F - 2)) *
+    (1 / speed))), F - 1.  None for a time function that is not finite or asks for more than 2^24 samples (the kernels' test)."""
     from scipy.interpolate import splev, splrep
     canonical = np.asarray(canonical, dtype=np.float64)
     F, last = len(canonical), canonical[-2]
-    if not np.isfinite(last) or not abs(last) <= 1.0e300 or np.round(last) > 16777216.0:
+    if not np.isfinite(last) or not abs(last) <= 1.0e300 or np.round(last) * (1.0 / float(speed)) > 16777216.0:
         return None
-    n_inner = int(np.round(last))
+    n_inner = int(np.round(last) * (1.0 / float(speed)))
     if n_inner <= 0:
         return np.array([0.0, F - 1.0])
     if not np.isfinite(canonical).all():

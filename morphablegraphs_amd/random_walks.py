@@ -8,10 +8,15 @@ an end transition, and every step's parameters are one draw from its node's mixt
   sample_walk_latents      every step's parameters of the whole population in ONE launch (mg_walks_sample_latents);
   RandomWalks.frames       every walk's motion in TWO launches (mg_walks_frames, csrc/mg_walks_mixed.hip), where
                            graph_walk.assemble_walks serves walks over one sequence and would take a call per distinct sequence;
-  assemble_walks_mixed_host  the NumPy statement of the frames: graph_walk.assemble_walk_host walk by walk.
+                           with use_time_parameters the time-warped motion the reference hands back from a finished walk
+                           (back_project(s, True) per step): every step's time row in ONE launch (mg_walks_time_functions, the
+                           time latents read where the sampler left them), one download of the lengths, the frames at those
+                           times in TWO launches (mg_walks_frames_at);
+  assemble_walks_mixed_host  the NumPy statement of the frames: graph_walk.assemble_walk_host walk by walk;
+  walk_time_rows_host      the NumPy statement of the time rows.
 
-Out of scope: parameters predicted by transition models (the predictor class is not in the reference tree) and time-warped
-mixed walks (the walks are assembled on their canonical grids).
+Out of scope: parameters predicted by transition models (the predictor class is not in the reference tree) and smoothed time
+functions (smooth_time_parameters: the Savitzky-Golay pass needs the row on the host; NotImplementedError).
 """
 import ctypes as C
 import random
@@ -19,7 +24,7 @@ import random
 import numpy as np
 
 from . import _capi
-from .graph_walk import HipGraphWalk, HipGraphWalkStep, _primitive_of, assemble_walk_host
+from .graph_walk import HipGraphWalk, HipGraphWalkStep, _primitive_of, _untimed_grid, assemble_walk_host
 from .motion_state_graph import NODE_TYPE_END, NODE_TYPE_STANDARD, random_edge
 
 
@@ -151,10 +156,95 @@ def walks_frames_host(prims, node_of, n_steps, latents, frames, frame_offset=Non
                                                    _capi._host_ptr(frames), frames.shape[1], _capi._host_ptr(transforms)))
 
 
+def walks_time_functions_dev(prims, node_of, n_steps, d_latents, dtype, ld, speed, d_times, d_lengths, t_cap):
+    """mg_walks_time_functions on device buffers: d_times (n_walks, s_max, t_cap) float64, d_lengths int32 (n_walks, s_max)."""
+    node_of, n_steps = np.ascontiguousarray(node_of, dtype=np.int32), np.ascontiguousarray(n_steps, dtype=np.int32)
+    code = _capi.MG_F64 if np.dtype(dtype) == np.float64 else _capi.MG_F32
+    _capi._check(prims[0].lib.mg_walks_time_functions(len(prims), _handles(prims), _capi._host_ptr(node_of), _capi._host_ptr(n_steps), _capi._dev_ptr(d_latents),
+                                                      code, node_of.shape[0], node_of.shape[1], int(ld), float(speed), _capi._dev_ptr(d_times),
+                                                      _capi._dev_ptr(d_lengths), int(t_cap)))
+
+
+def walks_time_functions_host(prims, node_of, n_steps, latents, speed, times, lengths):
+    """mg_walks_time_functions_host: latents (n_walks, s_max, ld) float32 / float64; times (n_walks, s_max, t_cap) float64 and
+    lengths (n_walks, s_max) int32 written in place (rows that are not written keep their values)."""
+    node_of, n_steps = np.ascontiguousarray(node_of, dtype=np.int32), np.ascontiguousarray(n_steps, dtype=np.int32)
+    latents = _capi._latents(latents.reshape(-1, latents.shape[-1])).reshape(latents.shape)
+    assert times.dtype == np.float64 and times.flags.c_contiguous and lengths.dtype == np.int32 and lengths.flags.c_contiguous
+    _capi._check(prims[0].lib.mg_walks_time_functions_host(len(prims), _handles(prims), _capi._host_ptr(node_of), _capi._host_ptr(n_steps), _capi._host_ptr(latents),
+                                                           _capi._dtype_code(latents), node_of.shape[0], node_of.shape[1], latents.shape[-1], float(speed),
+                                                           _capi._host_ptr(times), _capi._host_ptr(lengths), times.shape[2]))
+
+
+def walks_frames_at_dev(prims, node_of, n_steps, d_latents, dtype, ld, d_times, lengths, t_cap, frame_offset, d_frames, walk_stride, alignment=None,
+                        skeleton=None, d_transforms=None):
+    """mg_walks_frames_at on device buffers.  d_times (n_walks, s_max, t_cap); lengths int32 and frame_offset int64 (n_walks, s_max): host."""
+    node_of, n_steps, fo, al, sk = _frames_args(prims, node_of, n_steps, frame_offset, alignment, skeleton)
+    ln = None if lengths is None else np.ascontiguousarray(lengths, dtype=np.int32)
+    code = _capi.MG_F64 if np.dtype(dtype) == np.float64 else _capi.MG_F32
+    _capi._check(prims[0].lib.mg_walks_frames_at(len(prims), _handles(prims), _capi._host_ptr(node_of), _capi._host_ptr(n_steps), _capi._dev_ptr(d_latents), code,
+                                                 node_of.shape[0], node_of.shape[1], int(ld), _capi._dev_ptr(d_times) if d_times is not None else None,
+                                                 _capi._host_ptr(ln), int(t_cap), _capi._host_ptr(fo), C.byref(al) if al is not None else None,
+                                                 C.byref(sk) if sk is not None else None, _capi._dev_ptr(d_frames), int(walk_stride),
+                                                 _capi._dev_ptr(d_transforms) if d_transforms is not None else None))
+
+
+def walks_frames_at_host(prims, node_of, n_steps, latents, times, lengths, frame_offset, frames, alignment=None, skeleton=None, transforms=None):
+    """mg_walks_frames_at_host: times (n_walks, s_max, t_cap) float64; the rest as walks_frames_host."""
+    node_of, n_steps, fo, al, sk = _frames_args(prims, node_of, n_steps, frame_offset, alignment, skeleton)
+    latents = _capi._latents(latents.reshape(-1, latents.shape[-1])).reshape(latents.shape)
+    times, ln = np.ascontiguousarray(times, dtype=np.float64), np.ascontiguousarray(lengths, dtype=np.int32)
+    assert frames.dtype == np.float64 and frames.flags.c_contiguous and (transforms is None or (transforms.dtype == np.float64 and transforms.flags.c_contiguous))
+    _capi._check(prims[0].lib.mg_walks_frames_at_host(len(prims), _handles(prims), _capi._host_ptr(node_of), _capi._host_ptr(n_steps), _capi._host_ptr(latents),
+                                                      _capi._dtype_code(latents), node_of.shape[0], node_of.shape[1], latents.shape[-1], _capi._host_ptr(times),
+                                                      _capi._host_ptr(ln), times.shape[2], _capi._host_ptr(fo), C.byref(al) if al is not None else None,
+                                                      C.byref(sk) if sk is not None else None, _capi._host_ptr(frames), frames.shape[1],
+                                                      _capi._host_ptr(transforms)))
+
+
 # ---- the frames on the host ---------------------------------------------------------------------------------------------
-def assemble_walks_mixed_host(models, node_of, n_steps, parameters, alignment=None, skeleton=None):
+def _time_model_of(model):
+    """feature_point_model._time_model_host's (knots, mean vector, eigen vectors) of a node's model, None without a time model."""
+    from .feature_point_model import _time_model_host
+    if isinstance(model, dict):
+        return _time_model_host(model) if "eigen_vectors_time" in model and len(model["eigen_vectors_time"]) else None
+    mp = getattr(model, "motion_primitive", model)
+    return _time_model_host(mp) if mp.has_time_parameters and mp.get_n_time_components() > 0 else None
+
+
+def walk_time_rows_host(models, node_of, n_steps, parameters, speed=1.0):
+    """The NumPy statement of mg_walks_time_functions: times[w][i], the time row of step i of walk w.  models: one per node (JSON
+    dicts or primitives); parameters (n_walks, s_max, ld).  A node with a time model reads gamma from columns n_components ..
+    n_components + n_time_components of the step's row: feature_point_model's canonical_time_function_host and its inverse,
+    sample_time_function_host, at `speed` (ValueError where the time function is not finite).  A node without one:
+    graph_walk._untimed_grid, linspace(0, F, int(F * (1 / speed)))."""
+    from .feature_point_model import canonical_time_function_host, sample_time_function_host
+    from .graph_walk import _HostModel, _untimed_grid
+    hosts = [m if isinstance(m, _HostModel) else _HostModel(m) for m in models]
+    time_models = [_time_model_of(m) for m in models]
+    parameters = np.asarray(parameters, dtype=np.float64)
+    times = []
+    for w, ns in enumerate(np.asarray(n_steps)):
+        rows = []
+        for i, k in enumerate(np.asarray(node_of)[w, :ns]):
+            hm, tm = hosts[k], time_models[k]
+            if tm is None:
+                rows.append(_untimed_grid(hm.n_canonical_frames, speed))
+                continue
+            gamma = parameters[w, i, hm.n_components:hm.n_components + tm[2].shape[1]]
+            row = sample_time_function_host(canonical_time_function_host(tm, hm.n_canonical_frames, gamma), speed)
+            if row is None:
+                raise ValueError("a time function is not finite")
+            rows.append(row)
+        times.append(rows)
+    return times
+
+
+def assemble_walks_mixed_host(models, node_of, n_steps, parameters, alignment=None, skeleton=None, times=None, speed=1.0):
     """The NumPy statement of mg_walks_frames: graph_walk.assemble_walk_host for every walk on its own.  models: one per node
     (JSON dicts or primitives); parameters (n_walks, s_max, ld), step (w, i) reads the first n_components columns of its row.
+    times: None (canonical grids) or times[w][i], the step's time row (walk_time_rows_host; None for a step: its canonical grid
+    at `speed`) -- the statement of mg_walks_frames_at.
     Returns (frames: a list of (T_w, D) arrays, offsets: a list of (n_steps[w] + 1) arrays, transforms (n_walks, s_max, 4), NaN
     for the steps a walk does not have)."""
     from .graph_walk import _HostModel
@@ -164,7 +254,7 @@ def assemble_walks_mixed_host(models, node_of, n_steps, parameters, alignment=No
     for w, ns in enumerate(np.asarray(n_steps)):
         steps = [models[k] for k in np.asarray(node_of)[w, :ns]]
         S = np.concatenate([parameters[w, i, :m.n_components] for i, m in enumerate(steps)])[None, :]
-        fr, offs, tr = assemble_walk_host(steps, S, alignment=alignment, skeleton=skeleton)
+        fr, offs, tr = assemble_walk_host(steps, S, times=None if times is None else [times[w]], alignment=alignment, skeleton=skeleton, speed=speed)
         frames.append(fr[0])
         offsets.append(offs[0])
         transforms[w, :ns] = tr[0]
@@ -200,38 +290,75 @@ class RandomWalks(object):
         """(n_walks, s_max) int32: the mixture component every step was drawn from, -1 for the steps a walk does not have."""
         return self.ctx.download(self.components, self.node_of.shape, np.int32)
 
-    def frame_offsets(self):
-        """(n_walks, s_max + 1) int64: the first row of every step inside its walk, back to back; [w, n_steps[w]:] is the walk's length."""
-        T = np.array([mp.n_canonical_frames for mp in self._mps], dtype=np.int64)
-        lengths = np.where(self.node_of >= 0, T[np.maximum(self.node_of, 0)], 0)
+    def frame_offsets(self, lengths=None):
+        """(n_walks, s_max + 1) int64: the first row of every step inside its walk, back to back; [w, n_steps[w]:] is the walk's length.
+        lengths: None (the canonical grids) or (n_walks, s_max), the samples of every step's time row (time_functions)."""
+        if lengths is None:
+            T = np.array([mp.n_canonical_frames for mp in self._mps], dtype=np.int64)
+            lengths = T[np.maximum(self.node_of, 0)]
+        lengths = np.where(self.node_of >= 0, np.asarray(lengths, dtype=np.int64), 0)
         offsets = np.zeros((self.n_walks, self.node_of.shape[1] + 1), dtype=np.int64)
         offsets[:, 1:] = np.cumsum(lengths, axis=1)
         return offsets
 
-    def frames(self, alignment=None, skeleton=None, with_transforms=False):
+    def time_functions(self, speed=1.0):
+        """Every step's time row from ONE mg_walks_time_functions launch and one download of the lengths: (d_times, a device
+        buffer of (n_walks, s_max, t_cap) float64, the caller's to free, lengths int32 (n_walks, s_max), 0 for the steps a walk
+        does not have, t_cap).  t_cap starts by graph_walk._sample_times' rule; a row that needs more reports how
+        many and the table is laid out again.  ValueError for a time function that is not finite."""
+        has_time = [mp.has_time_parameters and mp.get_n_time_components() > 0 for mp in self._mps]
+        if any(ht and mp.smooth_time_parameters for mp, ht in zip(self._mps, has_time)):
+            raise NotImplementedError("smoothed time functions (smooth_time_parameters): the Savitzky-Golay pass needs the row on the host")
+        t_cap = max(int(4 * mp.n_canonical_frames / min(float(speed), 1.0)) + 8 if ht else len(_untimed_grid(mp.n_canonical_frames, speed))
+                    for mp, ht in zip(self._mps, has_time))
+        with self.ctx.buffers() as own:
+            d_l = own.malloc(4 * self.node_of.size)
+            while True:
+                d_t = own.malloc(8 * self.node_of.size * t_cap)
+                walks_time_functions_dev(self._prims, self.node_of, self.n_steps, self.parameters, self.dtype, self.ld, speed, d_t, d_l, t_cap)
+                lengths = self.ctx.download(d_l, self.node_of.shape, np.int32)
+                if ((lengths == 0) & (self.node_of >= 0)).any():
+                    raise ValueError("a time function is not finite")
+                if lengths.min() >= 0:
+                    return own.release(d_t), lengths, t_cap
+                t_cap = int(-lengths.min()) + 8              # (negative: the samples the row would need)
+
+    def frames(self, alignment=None, skeleton=None, with_transforms=False, use_time_parameters=False, speed=1.0):
         """Every walk's motion from ONE mg_walks_frames call: a list of (T_w, n_dim) float64 arrays (views of one download);
         alignment: of every walk's first step (None, a previous-frame record, a start-pose record), skeleton as in
         graph_walk.assemble_walks.  with_transforms: also (n_walks, s_max, 4) = (c, s, tx, tz), NaN for the steps a walk does
-        not have."""
-        offsets = self.frame_offsets()
+        not have.  use_time_parameters: the time-warped motion at `speed` -- one mg_walks_time_functions launch, the download of
+        the lengths, one mg_walks_frames_at call; every T_w is that walk's own."""
+        if not use_time_parameters and float(speed) != 1.0:
+            raise NotImplementedError("a speed other than 1 on the canonical grid")
         n, s_max, D = self.n_walks, self.node_of.shape[1], self._prims[0].n_dim
-        stride = int(offsets[:, -1].max())
         with self.ctx.buffers() as bufs:
+            if use_time_parameters:
+                d_t, lengths, t_cap = self.time_functions(speed)
+                bufs.bufs.append(d_t)                        # (freed with the call's other buffers)
+                offsets = self.frame_offsets(lengths)
+            else:
+                offsets = self.frame_offsets()
+            stride = int(offsets[:, -1].max())
             d_f = bufs.malloc(8 * n * stride * D)
             d_x = bufs.upload(np.full((n, s_max, 4), np.nan)) if with_transforms else None
-            walks_frames_dev(self._prims, self.node_of, self.n_steps, self.parameters, self.dtype, self.ld, d_f, stride, None, alignment, skeleton, d_x)
+            if use_time_parameters:
+                walks_frames_at_dev(self._prims, self.node_of, self.n_steps, self.parameters, self.dtype, self.ld, d_t, lengths, t_cap, offsets[:, :-1], d_f, stride,
+                                    alignment, skeleton, d_x)
+            else:
+                walks_frames_dev(self._prims, self.node_of, self.n_steps, self.parameters, self.dtype, self.ld, d_f, stride, None, alignment, skeleton, d_x)
             block = self.ctx.download(d_f, (n, stride, D), np.float64)
             transforms = self.ctx.download(d_x, (n, s_max, 4), np.float64) if with_transforms else None
         frames = [block[w, :int(offsets[w, -1])] for w in range(n)]
         return (frames, transforms) if with_transforms else frames
 
-    def to_graph_walks(self, skeleton=None):
+    def to_graph_walks(self, skeleton=None, use_time_parameters=False):
         """A HipGraphWalk per walk with its steps filled (node key, the step's n_gmm_dims parameters as float64), for the
         optimiser and the JSON export."""
         params = self.parameters_host()
         walks = []
         for w, keys in enumerate(self.node_keys):
-            walk = HipGraphWalk(self.graph, skeleton=skeleton, ctx=self.ctx)
+            walk = HipGraphWalk(self.graph, use_time_parameters=use_time_parameters, skeleton=skeleton, ctx=self.ctx)
             for i, key in enumerate(keys):
                 width = self._prims[self.node_of[w, i]].n_gmm_dims
                 walk.steps.append(HipGraphWalkStep.from_graph(self.graph, tuple(key), params[w, i, :width]))

@@ -341,7 +341,7 @@ int mg_memset(mg_context *ctx, void *dst_dev, int value, int64_t bytes);
  *       8 = mg_joint_tracks, 9 = mg_score_frame_constraints, 10 = mg_score_trajectory[_points],
  *       11 = mg_cluster_tree_search (both tree kinds: mg_tree_search_kernel or mg_kd_tree_search_kernel),
  *       12 = the frames kernel of mg_walk_frames, 13 = mg_score_walk_time, 14 = mg_step_lengths, 15 = mg_feature_points,
- *       16 = mg_feature_points_warped, 17 = mg_mixture_scores. */
+ *       16 = mg_feature_points_warped, 17 = mg_mixture_scores, 18 = mg_point_cloud_features, 19 = mg_feature_points_warped_smoothed. */
 int mg_profile_enable(mg_context *ctx, int enabled);
 int mg_profile_reset(mg_context *ctx);
 int mg_profile_get(mg_context *ctx, int slot, double *total_ms, int64_t *launches);
@@ -427,6 +427,18 @@ int mg_time_function_sample_rows(mg_primitive *prim, const void *gamma, int dtyp
                                  int32_t t_cap, int64_t row_pitch, double *canonical_out);
 int mg_back_project_frames_at(mg_primitive *prim, const void *latents, int dtype, int64_t n, int64_t ld, const double *times, const int32_t *lengths,
                               int32_t t_cap, void *out, int out_dtype);
+/* The SMOOTHED time function (smooth_time_parameters, reference motion_primitive.py:284-285, 320-331: scipy.signal.savgol_filter(t, 15,
+ * 3)) in the same one launch: row b is the Savitzky-Golay pass over mg_time_function_sample's row b, stated as a table -- sample q is a
+ * row of the 15 x 15 hat matrix H of the least-squares cubic on 15 points (csrc/mg_savgol_table.h) times 15 unsmoothed samples: row q on
+ * the first 15 for q < 7, row 15 - (T - q) on the last 15 for q >= T - 7, row 7 on samples q - 7 .. q + 7 otherwise; acc = H[0] u[0], then
+ * acc = acc + H[k] u[k] for k = 1 .. 14, every product and sum rounded on its own (time_smoothing.smooth_time_row_host's bits).  The
+ * unsmoothed row is never in memory; the first sample can be negative and the last one is no longer F - 1.  Lengths as above, and a row
+ * of 0 < T < 15 samples (scipy raises ValueError there) reports its T and is NOT written.  H travels in a cached table of its own
+ * (MG_TABLE_SAVGOL), uploaded once per context. */
+int mg_time_function_sample_smoothed(mg_primitive *prim, const void *gamma, int dtype, int64_t n, int64_t ld, double speed, double *times,
+                                     int32_t *lengths, int32_t t_cap, double *canonical_out);
+int mg_time_function_sample_smoothed_rows(mg_primitive *prim, const void *gamma, int dtype, int64_t n, int64_t ld, double speed, double *times,
+                                          int32_t *lengths, int32_t t_cap, int64_t row_pitch, double *canonical_out);
 
 /* ---- time grids ---------------------------------------------------------------------
  * A set of canonical times with its B-spline basis rows (FITPACK splev semantics,
@@ -1357,11 +1369,17 @@ int mg_walks_frames(int32_t n_nodes, mg_primitive *const *prims, const int32_t *
  * Contract: walk w's frames and transforms are, bit for bit, those of mg_walk_frames called for that walk alone (n_walks = 1, its node
  * sequence, its latents packed into one row, its time rows as times_dev (1, n_steps, t_cap), the same lengths, offsets and alignment).
  * Rows no step owns and transforms of steps the walk does not have are not written.
- * Out of scope: smoothed time functions (smooth_time_parameters: the Savitzky-Golay pass needs the row on the host) and parameters
- * predicted by transition models. */
+ * mg_walks_time_functions_smoothed: mg_walks_time_functions with smooth_of_node, one byte per node (HOST): the rows of a node with a time
+ * model and a byte other than 0 are mg_time_function_sample_smoothed_rows' for that primitive, bit for bit (a row of 0 < T < 15 samples
+ * reports T and is not written); every other row has the bits of mg_walks_time_functions.  A cached table of its own
+ * (MG_TABLE_WALKS_TIME_SMOOTHED).
+ * Out of scope: parameters predicted by transition models. */
 int mg_walks_time_functions(int32_t n_nodes, mg_primitive *const *prims, const int32_t *node_of, const int32_t *n_steps,
                             const void *latents_dev, int latent_dtype, int64_t n_walks, int32_t s_max, int64_t ld, double speed,
                             double *times_dev, int32_t *lengths_dev, int32_t t_cap);
+int mg_walks_time_functions_smoothed(int32_t n_nodes, mg_primitive *const *prims, const int32_t *node_of, const int32_t *n_steps,
+                                     const uint8_t *smooth_of_node, const void *latents_dev, int latent_dtype, int64_t n_walks, int32_t s_max,
+                                     int64_t ld, double speed, double *times_dev, int32_t *lengths_dev, int32_t t_cap);
 int mg_walks_frames_at(int32_t n_nodes, mg_primitive *const *prims, const int32_t *node_of, const int32_t *n_steps,
                        const void *latents_dev, int latent_dtype, int64_t n_walks, int32_t s_max, int64_t ld,
                        const double *times_dev, const int32_t *lengths, int32_t t_cap, const int64_t *frame_offset,
@@ -1449,7 +1467,8 @@ int mg_walk_time_table_uploads(mg_context *ctx, int64_t *uploads);   /* mg_conte
  * of mg_walks_sample_latents, of mg_walks_frames_at and of mg_walks_time_functions.  mg_context_table_uploads: how often table `which` of the context went to the device so far. */
 enum { MG_TABLE_FUSED = 0, MG_TABLE_TREE = 1, MG_TABLE_WALK = 2, MG_TABLE_WALK_SCORE = 3, MG_TABLE_WALK_TIME = 4, MG_TABLE_STEP_LENGTH = 5,
        MG_TABLE_FEATURE_POINTS = 6, MG_TABLE_FEATURE_POINTS_WARPED = 7, MG_TABLE_MIXTURE_SCORES = 8, MG_TABLE_POINT_CLOUDS = 9,
-       MG_TABLE_WALKS_MIXED = 10, MG_TABLE_WALKS_SAMPLE = 11, MG_TABLE_WALKS_WARPED = 12, MG_TABLE_WALKS_TIME = 13, MG_TABLE_COUNT = 14 };
+       MG_TABLE_WALKS_MIXED = 10, MG_TABLE_WALKS_SAMPLE = 11, MG_TABLE_WALKS_WARPED = 12, MG_TABLE_WALKS_TIME = 13, MG_TABLE_SAVGOL = 14,
+       MG_TABLE_WALKS_TIME_SMOOTHED = 15, MG_TABLE_FEATURE_POINTS_SMOOTHED = 16, MG_TABLE_COUNT = 17 };
 int mg_context_table_uploads(mg_context *ctx, int which, int64_t *uploads);
 
 /* Step lengths without frames in memory, ONE launch for every candidate of every item (csrc/mg_step_length.hip): what
@@ -1599,6 +1618,15 @@ typedef struct {
     int32_t *n_frames_dev;              /* (n_samples) or NULL */
 } mg_warped_feature_point_item;
 int mg_feature_points_warped(int32_t n_items, const mg_warped_feature_point_item *items, int latent_dtype);
+/* The same over a SMOOTHED time function (smooth_time_parameters; the statement: mg_time_function_sample_smoothed above).  smooth: one
+ * byte per item (HOST).  An item whose byte is 0 has the bits of mg_feature_points_warped.  For the others smoothing moves all three
+ * times of a candidate: the first becomes row 0 of the hat matrix on the first 15 samples of its time function (it can be negative), the
+ * last one row 14 on the last 15 (no longer F - 1), time_mid is smoothed sample frame_idx; the frames are the spline at those times, by
+ * the statements of the mid frame above (the bits of mg_back_project_frames_at at them; outside [0, F - 1] the end piece's polynomial).
+ * The lane evaluates the <= 45 unsmoothed samples itself; nothing new goes to device memory.  A candidate of fewer than 15 frames is NaN
+ * in every output but n_frames; frame_idx >= n_frames: NaN in points and time_mid only.  A device table (MG_TABLE_FEATURE_POINTS_SMOOTHED)
+ * and a profile slot (19) of its own. */
+int mg_feature_points_warped_smoothed(int32_t n_items, const mg_warped_feature_point_item *items, const uint8_t *smooth, int latent_dtype);
 
 /* Targets scored against the reachability mixtures of many nodes, ONE launch for every target of every item
  * (csrc/mg_mixture_scores.hip): what the reference's FeaturePointModel asks of its stored mixture in check_reachability,
@@ -1670,6 +1698,7 @@ int mg_step_lengths_host(int32_t n_items, const mg_step_length_item *items, int 
 int mg_feature_points_host(int32_t n_items, const mg_feature_point_item *items, int latent_dtype);
 /* mg_feature_points_warped in the same way */
 int mg_feature_points_warped_host(int32_t n_items, const mg_warped_feature_point_item *items, int latent_dtype);
+int mg_feature_points_warped_smoothed_host(int32_t n_items, const mg_warped_feature_point_item *items, const uint8_t *smooth, int latent_dtype);
 /* mg_score_walk_time with host arrays: latents, outputs and every step's spatial latents (`spatial_dev` is a host pointer here) */
 int mg_score_walk_time_host(int32_t n_steps, const mg_walk_time_step *steps, const void *latents, int latent_dtype, int64_t n_samples, int64_t ld,
                             int32_t n_constraints, const mg_walk_time_constraint *constraints, double start_keyframe, double frame_time,
@@ -1700,6 +1729,10 @@ int mg_walks_frames_host(int32_t n_nodes, mg_primitive *const *prims, const int3
 int mg_walks_time_functions_host(int32_t n_nodes, mg_primitive *const *prims, const int32_t *node_of, const int32_t *n_steps,
                                  const void *latents, int latent_dtype, int64_t n_walks, int32_t s_max, int64_t ld, double speed,
                                  double *times, int32_t *lengths, int32_t t_cap);
+/* mg_walks_time_functions_smoothed in the same way (smooth_of_node is a host table in both) */
+int mg_walks_time_functions_smoothed_host(int32_t n_nodes, mg_primitive *const *prims, const int32_t *node_of, const int32_t *n_steps,
+                                          const uint8_t *smooth_of_node, const void *latents, int latent_dtype, int64_t n_walks, int32_t s_max,
+                                          int64_t ld, double speed, double *times, int32_t *lengths, int32_t t_cap);
 int mg_walks_frames_at_host(int32_t n_nodes, mg_primitive *const *prims, const int32_t *node_of, const int32_t *n_steps, const void *latents,
                             int latent_dtype, int64_t n_walks, int32_t s_max, int64_t ld, const double *times, const int32_t *lengths,
                             int32_t t_cap, const int64_t *frame_offset, const mg_alignment_desc *alignment,

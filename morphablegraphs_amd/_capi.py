@@ -40,10 +40,11 @@ MG_CONSTRAINT_VALUE_POSITION, MG_CONSTRAINT_VALUE_HEADING = 7, 8   # values of t
 PROFILE_SLOTS = {"frames": 0, "gmm_log_prob": 1, "score_constraints": 2, "argmin": 3,
                  "gmm_sample": 4, "spline_evaluate": 5, "step": 6, "options_step": 7, "joint_tracks": 8, "frame_constraints": 9, "trajectory": 10,
                  "cluster_tree_search": 11, "walk_frames": 12, "walk_time": 13, "step_lengths": 14, "feature_points": 15,
-                 "feature_points_warped": 16, "mixture_scores": 17, "point_clouds": 18}
+                 "feature_points_warped": 16, "mixture_scores": 17, "point_clouds": 18, "feature_points_warped_smoothed": 19}
 DEVICE_TABLES = {"fused": 0, "tree": 1, "walk": 2, "walk_score": 3, "walk_time": 4, "step_length": 5, "feature_points": 6,
                  "feature_points_warped": 7, "mixture_scores": 8, "point_clouds": 9, "walks_mixed": 10, "walks_sample": 11,
-                 "walks_warped": 12, "walks_time": 13}    # MG_TABLE_* (include/mg_hip.h)
+                 "walks_warped": 12, "walks_time": 13, "savgol": 14, "walks_time_smoothed": 15,
+                 "feature_points_smoothed": 16}    # MG_TABLE_* (include/mg_hip.h)
 MG_TREE_MAX_DEPTH, MG_TREE_MAX_CHILDREN, MG_TREE_MAX_CANDIDATES = 64, 256, 64    # include/mg_hip.h
 MG_TREE_TIE, MG_TREE_NO_RESULT, MG_TREE_OVERFLOW, MG_TREE_NO_MEAN = 1, 2, 4, 8
 MG_TREE_MAX_TRAJECTORIES = 4    # root trajectory constraints of one search (mg_cluster_tree_search_trajectories)
@@ -94,7 +95,8 @@ EXPORTED_SYMBOLS = [
     "mg_context_device_info", "mg_device_malloc", "mg_device_malloc_chunked", "mg_device_malloc_placed", "mg_device_probe_placement", "mg_device_placement_info", "mg_device_free", "mg_context_trim_outputs", "mg_context_output_bytes", "mg_memcpy_h2d", "mg_memcpy_d2h", "mg_memcpy_d2d_rows",
     "mg_memset", "mg_profile_enable", "mg_profile_reset", "mg_profile_get", "mg_profile_get_samples",
     "mg_primitive_create", "mg_primitive_destroy", "mg_primitive_info", "mg_primitive_info2", "mg_primitive_root_mode", "mg_primitive_get_precisions_cholesky",
-    "mg_time_function_canonical", "mg_time_function_canonical_host", "mg_time_function_sample", "mg_time_function_sample_rows", "mg_back_project_frames_at",
+    "mg_time_function_canonical", "mg_time_function_canonical_host", "mg_time_function_sample", "mg_time_function_sample_rows",
+    "mg_time_function_sample_smoothed", "mg_time_function_sample_smoothed_rows", "mg_back_project_frames_at",
     "mg_trajectory_create", "mg_trajectory_create_typed", "mg_trajectory_spline_type", "mg_trajectory_tables", "mg_trajectory_destroy", "mg_score_trajectory", "mg_score_trajectory_chained", "mg_score_trajectories", "mg_score_trajectory_points", "mg_trajectory_closest_points", "mg_trajectory_plan", "mg_joint_positions",
     "mg_trajectory_sample_parameters", "mg_trajectory_points_by_arc_length", "mg_trajectory_arc_length_of_points", "mg_trajectory_points_at_parameters",
     "mg_time_grid_create", "mg_time_grid_destroy", "mg_primitive_canonical_grid", "mg_time_grid_size",
@@ -118,11 +120,12 @@ EXPORTED_SYMBOLS = [
     "mg_align_motions_spatially", "mg_prepare_aligned_frames",
     "mg_walk_frames", "mg_walk_frames_host",
     "mg_walks_sample_latents", "mg_walks_sample_latents_host", "mg_walks_frames", "mg_walks_frames_host",
-    "mg_walks_time_functions", "mg_walks_time_functions_host", "mg_walks_frames_at", "mg_walks_frames_at_host",
+    "mg_walks_time_functions", "mg_walks_time_functions_host", "mg_walks_time_functions_smoothed", "mg_walks_time_functions_smoothed_host", "mg_walks_frames_at", "mg_walks_frames_at_host",
     "mg_score_walk_residuals", "mg_score_walk_residuals_host", "mg_score_walk_residuals_steps", "mg_score_walk_residuals_steps_host",
     "mg_score_walk_time", "mg_score_walk_time_host", "mg_walk_time_table_uploads", "mg_context_table_uploads",
     "mg_step_lengths", "mg_step_lengths_host",
     "mg_feature_points", "mg_feature_points_host", "mg_feature_points_warped", "mg_feature_points_warped_host",
+    "mg_feature_points_warped_smoothed", "mg_feature_points_warped_smoothed_host",
     "mg_feature_mixture_create", "mg_feature_mixture_destroy", "mg_feature_mixture_info", "mg_feature_mixture_get_image",
     "mg_mixture_scores", "mg_mixture_scores_host",
     "mg_point_cloud_features", "mg_pca_fit_leading",
@@ -423,6 +426,8 @@ def load_library(path=None):
         "mg_objective_error_and_naturalness": [vp, vp, vp, i32, i64, i64, dbl, dbl, vp, vp, vp],
         "mg_time_function_sample": [vp, vp, i32, i64, i64, dbl, vp, vp, i32, vp],
         "mg_time_function_sample_rows": [vp, vp, i32, i64, i64, dbl, vp, vp, i32, i64, vp],
+        "mg_time_function_sample_smoothed": [vp, vp, i32, i64, i64, dbl, vp, vp, i32, vp],
+        "mg_time_function_sample_smoothed_rows": [vp, vp, i32, i64, i64, dbl, vp, vp, i32, i64, vp],
         "mg_back_project_frames_at": [vp, vp, i32, i64, i64, vp, vp, i32, vp, i32],
         "mg_track_plan_create": [vp, vp, i32, vp, vp, i32, C.POINTER(vp)],
         "mg_joint_tracks": [vp, vp, i32, i64, i64, vp, vp, vp],
@@ -465,6 +470,8 @@ def load_library(path=None):
         "mg_walks_frames_host": [i32, vp, vp, vp, vp, i32, i64, i32, i64, vp, vp, vp, vp, i64, vp],
         "mg_walks_time_functions": [i32, vp, vp, vp, vp, i32, i64, i32, i64, dbl, vp, vp, i32],
         "mg_walks_time_functions_host": [i32, vp, vp, vp, vp, i32, i64, i32, i64, dbl, vp, vp, i32],
+        "mg_walks_time_functions_smoothed": [i32, vp, vp, vp, vp, vp, i32, i64, i32, i64, dbl, vp, vp, i32],
+        "mg_walks_time_functions_smoothed_host": [i32, vp, vp, vp, vp, vp, i32, i64, i32, i64, dbl, vp, vp, i32],
         "mg_walks_frames_at": [i32, vp, vp, vp, vp, i32, i64, i32, i64, vp, vp, i32, vp, vp, vp, vp, i64, vp],
         "mg_walks_frames_at_host": [i32, vp, vp, vp, vp, i32, i64, i32, i64, vp, vp, i32, vp, vp, vp, vp, i64, vp],
         "mg_score_walk_residuals": [i32, vp, vp, i32, i64, i64, vp, i64, vp, vp],
@@ -481,6 +488,8 @@ def load_library(path=None):
         "mg_feature_points_host": [i32, vp, i32],
         "mg_feature_points_warped": [i32, vp, i32],
         "mg_feature_points_warped_host": [i32, vp, i32],
+        "mg_feature_points_warped_smoothed": [i32, vp, vp, i32],
+        "mg_feature_points_warped_smoothed_host": [i32, vp, vp, i32],
         "mg_feature_mixture_create": [vp, i32, i32, vp, vp, vp, dbl, C.POINTER(vp)],
         "mg_feature_mixture_info": [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(dbl)],
         "mg_feature_mixture_get_image": [vp, vp, vp, vp],
@@ -1379,19 +1388,34 @@ def feature_points_warped_table(lib, n_items, table, latent_dtype, host=True):
     _items_call(lib, "mg_feature_points_warped", n_items, table, latent_dtype, host)
 
 
-def feature_points_warped(items, outputs=WARPED_FEATURE_POINT_OUTPUTS):
+def feature_points_warped_smoothed_table(lib, n_items, table, smooth, latent_dtype, host=True):
+    """mg_feature_points_warped_smoothed_host or mg_feature_points_warped_smoothed on a (WarpedFeaturePointItem * n) table; smooth:
+    one flag per item (host)."""
+    flags = np.ascontiguousarray(np.asarray(smooth).astype(bool), dtype=np.uint8)
+    if len(flags) != int(n_items):
+        raise ValueError("%d smoothing flags for %d items" % (len(flags), n_items))
+    code = MG_F64 if np.dtype(latent_dtype) == np.float64 else MG_F32
+    fn = getattr(lib, "mg_feature_points_warped_smoothed" + ("_host" if host else ""))
+    _check(fn(int(n_items), C.cast(table, C.c_void_p) if table is not None else None, _host_ptr(flags), code))
+
+
+def feature_points_warped(items, outputs=WARPED_FEATURE_POINT_OUTPUTS, smooth=None):
     """The feature points of the TIME-WARPED motion of every candidate of every item in one mg_feature_points_warped call: items as
     for feature_points, on primitives with a time model; a row of S holds the spatial latents from latent_offset on and the time
     latents from time_offset on (default: right behind the spatial ones), frame_idx counts the warped motion's frames.  Returns per
     item what feature_points returns, and time_mid (n,) float64 -- the canonical time of frame frame_idx, NaN where the candidate's
-    motion is shorter -- and n_frames (n,) int32, the warped length (0: no time function)."""
+    motion is shorter -- and n_frames (n,) int32, the warped length (0: no time function).  smooth: None, or one flag per item --
+    ONE mg_feature_points_warped_smoothed call instead: a flagged item's three times are those of the smoothed time function, and a
+    candidate of fewer than 15 frames is NaN in every output but n_frames."""
     def fill(rec, it, S, n_joints):
         off = it.get("time_offset")
         rec.time_offset = int(off) if off is not None else int(it.get("latent_offset", 0)) + it["prim"].n_components
         return {"time_mid": ((S.shape[0],), np.float64), "n_frames": ((S.shape[0],), np.int32)}
 
     table, out, keep, dtype = _feature_point_table(items, outputs, WARPED_FEATURE_POINT_OUTPUTS, WarpedFeaturePointItem, fill)
-    if items:
+    if items and smooth is not None:
+        feature_points_warped_smoothed_table(items[0]["prim"].lib, len(items), table, smooth, dtype)
+    elif items:
         feature_points_warped_table(items[0]["prim"].lib, len(items), table, dtype)
     return out
 
@@ -2251,9 +2275,12 @@ class Primitive(object):
                                                         out.ctypes.data_as(C.c_void_p)))
         return out
 
-    def time_function_sample(self, gamma, speed=1.0, t_cap=None, with_canonical=False):
+    def time_function_sample(self, gamma, speed=1.0, t_cap=None, with_canonical=False, smoothed=False):
         """(B, n_time_components) time latents -> (times (B, t_cap) float64 padded with NaN, lengths (B)): the spline's time function
-        t'(t) of every row (mg_time_function_sample: back_project_time_function, motion_primitive.py:268-319, for the batch)."""
+        t'(t) of every row (mg_time_function_sample: back_project_time_function, motion_primitive.py:268-319, for the batch).
+        smoothed: mg_time_function_sample_smoothed, the rows after the Savitzky-Golay pass (a row of 0 < T < 15 samples reports T
+        and stays NaN)."""
+        sample = self.lib.mg_time_function_sample_smoothed if smoothed else self.lib.mg_time_function_sample
         G = _latents(gamma)
         B, F = G.shape[0], self.n_canonical_frames
         ctx = self.ctx
@@ -2263,8 +2290,7 @@ class Primitive(object):
             d_c = ctx.malloc(max(B, 1) * F * 8) if with_canonical else None
             try:
                 _check(self.lib.mg_memset(ctx.handle, d_t.ptr, 0xff, max(B, 1) * cap * 8))      # NaN padding
-                _check(self.lib.mg_time_function_sample(self.handle, d_g.ptr, _dtype_code(G), B, G.shape[1], float(speed), d_t.ptr, d_l.ptr, cap,
-                                                        d_c.ptr if d_c is not None else None))
+                _check(sample(self.handle, d_g.ptr, _dtype_code(G), B, G.shape[1], float(speed), d_t.ptr, d_l.ptr, cap, d_c.ptr if d_c is not None else None))
                 lens = ctx.download(d_l, (B,), np.int32)
                 if B and lens.min() < 0 and t_cap is None:      # a row needs more samples than assumed: once more with room for it
                     cap = int(-lens.min()) + 8
@@ -2276,6 +2302,39 @@ class Primitive(object):
                     if b is not None:
                         b.free()
             return (times, lens, canonical) if with_canonical else (times, lens)
+
+    def back_project_warped_smoothed(self, S, n_spatial, speed=1.0, dtype=np.float64):
+        """(B, n_spatial + n_time) latents -> (frames (B, t_max, D) padded with NaN, lengths (B), times (B, t_max) padded with NaN): the
+        SMOOTHED time function of every row (mg_time_function_sample_smoothed on the time columns) and the frames at it
+        (mg_back_project_frames_at on the spatial columns), the times never leaving the device in between: the lengths come back
+        (the sampling launch runs again only where a row needs more samples than 4 F + 8), a row of fewer than
+        15 samples raises ValueError as scipy would, then the frames launch reads the rows where the sampler left them."""
+        from .time_smoothing import require_smoothing_window
+        S = _latents(S)
+        B, F, ctx = S.shape[0], self.n_canonical_frames, self.ctx
+        item = np.dtype(dtype).itemsize
+        cap = int(4 * F / min(float(speed), 1.0)) + 8
+        off = n_spatial * S.dtype.itemsize
+        with ctx.buffers() as bufs:
+            d_s, d_l = bufs.upload(S), bufs.malloc(max(B, 1) * 4)
+            while True:
+                d_t = bufs.malloc(max(B, 1) * cap * 8)
+                _check(self.lib.mg_memset(ctx.handle, d_t.ptr, 0xff, max(B, 1) * cap * 8))      # NaN padding
+                _check(self.lib.mg_time_function_sample_smoothed(self.handle, C.c_void_p(d_s.address + off), _dtype_code(S), B, S.shape[1], float(speed),
+                                                                 d_t.ptr, d_l.ptr, cap, None))
+                lens = ctx.download(d_l, (B,), np.int32)
+                if not B or lens.min() >= 0:
+                    break
+                cap = int(-lens.min()) + 8                                                      # a row needs more samples than assumed: once more
+            require_smoothing_window(lens, "candidate %d")
+            d_o = bufs.malloc(max(B, 1) * cap * self.n_dim * item)
+            _check(self.lib.mg_memset(ctx.handle, d_o.ptr, 0xff, max(B, 1) * cap * self.n_dim * item))
+            _check(self.lib.mg_back_project_frames_at(self.handle, d_s.ptr, _dtype_code(S), B, S.shape[1], d_t.ptr, d_l.ptr, cap, d_o.ptr,
+                                                      MG_F64 if np.dtype(dtype) == np.float64 else MG_F32))
+            t_top = int(lens.max()) if B else 0
+            frames = ctx.download(d_o, (B, cap, self.n_dim), dtype)[:, :t_top]
+            times = ctx.download(d_t, (B, cap), np.float64)[:, :t_top]
+        return frames, lens, np.ascontiguousarray(times)
 
     def back_project_frames_at(self, S, times, lengths=None, dtype=np.float64):
         """(B, ld) latents, (B, t_cap) float64 times, (B) lengths -> (B, t_cap, D) frames of every candidate at ITS OWN times

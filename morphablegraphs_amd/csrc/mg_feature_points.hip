@@ -368,12 +368,33 @@ struct mg_fpw_args {
     int32_t n_items;
 };
 
+// mg_feature_points_warped_smoothed: an item whose `smooth` is not 0 takes its three times from the SMOOTHED time function
+// (mg_timewarp_device.h: mg_tw_smooth_window, mg_tw_smoothed over H, the hat matrix of mg_savgol_table.h) -- the first one row 0 of H
+// on the first 15 samples, the last one row 14 on the last 15, time_mid the case split at frame_idx -- so all three frames have tap
+// windows of the candidate's own: the end frames go the mid frame's way (control points straight from E', four taps) into
+// ends[cand][3 + 7], and the host-planned rows are not read.  The lane evaluates the <= 45 unsmoothed samples itself from the whole
+// set of second derivatives; a candidate of fewer than 15 frames is NaN in every output but n_frames.  smooth = 0: the statements above.
+struct mg_fpws_item : mg_fpw_item {
+    const double *H;
+    int32_t smooth, pad;
+};
+
+struct mg_fpws_args {
+    const char *base;
+    const mg_fpws_item *items;
+    int32_t n_items;
+};
+#define MG_FPW_ENDS 10                  // doubles per candidate: the root position at the first time, the root pose at the last one
+
 struct mg_fpw_layout {
-    int x, cpt, dpt, gam, tmid, wm, E, mean, w, lat, cp, mid, rec, ints, total_bytes;
+    int x, cpt, dpt, gam, tmid, wm, E, mean, w, lat, cp, mid, ends, rec, ints, total_bytes;
     int CS, MS;
 };
-__host__ __device__ static inline mg_fpw_layout mg_fpw_layout_of(int F, int Lt, int need_mid, int L, int NRS, int NCP, int NC, int D, int J, int rec_stride) {
+// smooth: three basis rows and three first taps per candidate (first, mid, last) instead of the mid frame's one, and ends[cand][10]
+__host__ __device__ static inline mg_fpw_layout mg_fpw_layout_of(int F, int Lt, int need_mid, int L, int NRS, int NCP, int NC, int D, int J, int rec_stride,
+                                                                 int smooth = 0) {
     mg_fpw_layout y;
+    const int slots = smooth ? 3 : 1;
     y.CS = NRS | 1;
     y.MS = NC | 1;
     y.x = 0;
@@ -382,30 +403,41 @@ __host__ __device__ static inline mg_fpw_layout mg_fpw_layout_of(int F, int Lt, 
     y.gam = y.dpt + (need_mid ? F * MG_FP_TILE : 0);
     y.tmid = y.gam + MG_FP_TILE * Lt;
     y.wm = y.tmid + MG_FP_TILE;
-    y.E = y.wm + MG_FP_TILE * 4;
+    y.E = y.wm + MG_FP_TILE * 4 * slots;
     y.mean = y.E + L * NRS;
     y.w = y.mean + NRS;
     y.lat = y.w + MG_FPW_SLOTS * 4;
     y.cp = y.lat + MG_FP_TILE * L;
     y.mid = y.cp + MG_FP_TILE * y.CS;
-    y.rec = y.mid + MG_FP_TILE * y.MS;
-    y.ints = y.rec + J * rec_stride;     // then int32: map[NCP * D], chan[NC], pos[D], tap[MG_FPW_SLOTS], bad[TILE], nf[TILE], i0[TILE]
-    y.total_bytes = y.ints * 8 + (NCP * D + NC + D + MG_FPW_SLOTS + 3 * MG_FP_TILE) * 4;
+    y.ends = y.mid + MG_FP_TILE * y.MS;
+    y.rec = y.ends + (smooth ? MG_FP_TILE * MG_FPW_ENDS : 0);
+    y.ints = y.rec + J * rec_stride;     // then int32: map[NCP * D], chan[NC], pos[D], tap[MG_FPW_SLOTS], bad[TILE], nf[TILE], i0[TILE][slots]
+    y.total_bytes = y.ints * 8 + (NCP * D + NC + D + MG_FPW_SLOTS + (2 + slots) * MG_FP_TILE) * 4;
     return y;
 }
 
-template <bool LAT_F64>
-__global__ __launch_bounds__(256) void mg_feature_points_warped_kernel(const mg_fpw_args a) {
+template <bool SMOOTH> struct mg_fpw_types { typedef mg_fpw_item item; typedef mg_fpw_args args; };
+template <> struct mg_fpw_types<true> { typedef mg_fpws_item item; typedef mg_fpws_args args; };
+__device__ __forceinline__ int mg_fpw_smooth_of(const mg_fpw_item *) { return 0; }
+__device__ __forceinline__ int mg_fpw_smooth_of(const mg_fpws_item *ip) { return ip->smooth; }
+__device__ __forceinline__ const double *mg_fpw_table_of(const mg_fpw_item *) { return nullptr; }
+__device__ __forceinline__ const double *mg_fpw_table_of(const mg_fpws_item *ip) { return ip->H; }
+
+template <bool LAT_F64, bool SMOOTH>
+__global__ __launch_bounds__(256) void mg_feature_points_warped_kernel(const typename mg_fpw_types<SMOOTH>::args a) {
 #pragma clang fp contract(off)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x;
-    const mg_fpw_item *ip = a.items + mg_item_of_workgroup(a.items, a.n_items);
+    const typename mg_fpw_types<SMOOTH>::item *ip = a.items + mg_item_of_workgroup(a.items, a.n_items);
+    const bool smooth = SMOOTH && mg_fpw_smooth_of(ip) != 0;
+    const double *H = mg_fpw_table_of(ip);
     const int L = ip->L, Lt = ip->Lt, D = ip->D, F = ip->F, J = ip->J, NRS = ip->NRS, NCP = ip->NCP, NC = ip->NC, RS = ip->rec_stride;
     const int frame_idx = ip->frame_idx, need_mid = ip->need_mid;
     const int64_t n = ip->n, ld = ip->ld;
     const size_t R = (size_t)ip->R;
-    const mg_fpw_layout y = mg_fpw_layout_of(F, Lt, need_mid, L, NRS, NCP, NC, D, J, RS);
+    const mg_fpw_layout y = mg_fpw_layout_of(F, Lt, need_mid, L, NRS, NCP, NC, D, J, RS, smooth ? 1 : 0);
     const int CS = y.CS, MS = y.MS;
+    double *sends = (double *)smem + y.ends;
     double *sm = (double *)smem;
     double *sx = sm + y.x, *scpt = sm + y.cpt, *sdpt = sm + y.dpt, *sgam = sm + y.gam, *stmid = sm + y.tmid, *swm = sm + y.wm;
     double *sE = sm + y.E, *smean = sm + y.mean, *sw = sm + y.w, *slat = sm + y.lat, *scp = sm + y.cp, *smid = sm + y.mid, *srec = sm + y.rec;
@@ -448,26 +480,59 @@ __global__ __launch_bounds__(256) void mg_feature_points_warped_kernel(const mg_
             const double stop = x[F - 2];
             int num = 0, T = 0, i0 = 0;
             double tmid = NAN;
-            if (mg_tw_sample_count(stop, 1.0, num)) {
-                T = num + 2;
-                if (frame_idx == 0) tmid = 0.0;
-                else if (frame_idx == T - 1) tmid = (double)(F - 1);
-                else if (frame_idx < T && need_mid) {
-                    const double t = mg_tw_sample_point(frame_idx - 1, num, stop, mg_tw_sample_step(stop, num));
-                    const int i = mg_tw_interval(x, F, t);
-                    const mg_tw_strided cpt = {scpt + c, MG_FP_TILE}, dpt = {sdpt + c, MG_FP_TILE};
-                    const int top = F - 3 > 1 ? F - 3 : 1;
-                    mg_tw_second_derivatives(x, dpt, cpt, dpt, F, i < 1 ? 1 : (i > top ? top : i));   // (M takes dp's place)
-                    tmid = mg_tw_inverse_at(x, dpt, i, t);
+            if (smooth) {
+                // all three times from the smoothed row: the whole set of second derivatives, then 15 unsmoothed samples per time
+                if (mg_tw_sample_count(stop, 1.0, num)) {
+                    T = num + 2;
+                    if (T >= MG_TW_SMOOTH_W) {
+                        const double step = mg_tw_sample_step(stop, num);
+                        const mg_tw_strided cpt = {scpt + c, MG_FP_TILE}, dpt = {sdpt + c, MG_FP_TILE};
+                        mg_tw_second_derivatives(x, dpt, cpt, dpt, F, 1);   // (M takes dp's place)
+                        auto smoothed_at = [&](int q) {
+                            int row, base;
+                            double u[MG_TW_SMOOTH_W];
+                            mg_tw_smooth_window(q, T, &row, &base);
+                            for (int k = 0; k < MG_TW_SMOOTH_W; k++) u[k] = mg_tw_row_sample(x, dpt, F, base + k, T, num, stop, step);
+                            return mg_tw_smoothed(H + MG_TW_SMOOTH_W * row, u);
+                        };
+                        const double tfirst = smoothed_at(0), tlast = smoothed_at(T - 1);
+                        mg_basis_row_dev(ip->knots, ip->NB + 4, tfirst, &si0[3 * c], swm + 12 * c);
+                        mg_basis_row_dev(ip->knots, ip->NB + 4, tlast, &si0[3 * c + 2], swm + 12 * c + 8);
+                        si0[3 * c + 1] = 0;
+                        if (frame_idx < T) {
+                            tmid = smoothed_at(frame_idx);
+                            if (NC > 0) mg_basis_row_dev(ip->knots, ip->NB + 4, tmid, &si0[3 * c + 1], swm + 12 * c + 4);
+                        }
+                    } else {
+                        sbad[c] = 1;                                        // no smoothed form: NaN in every output but n_frames
+                    }
                 }
+                snf[c] = T;
+                stmid[c] = tmid;
+                if (ip->n_frames) ip->n_frames[b0 + c] = T;
+                if (ip->time_mid) ip->time_mid[b0 + c] = tmid;
+            } else {
+                if (mg_tw_sample_count(stop, 1.0, num)) {
+                    T = num + 2;
+                    if (frame_idx == 0) tmid = 0.0;
+                    else if (frame_idx == T - 1) tmid = (double)(F - 1);
+                    else if (frame_idx < T && need_mid) {
+                        const double t = mg_tw_sample_point(frame_idx - 1, num, stop, mg_tw_sample_step(stop, num));
+                        const int i = mg_tw_interval(x, F, t);
+                        const mg_tw_strided cpt = {scpt + c, MG_FP_TILE}, dpt = {sdpt + c, MG_FP_TILE};
+                        const int top = F - 3 > 1 ? F - 3 : 1;
+                        mg_tw_second_derivatives(x, dpt, cpt, dpt, F, i < 1 ? 1 : (i > top ? top : i));   // (M takes dp's place)
+                        tmid = mg_tw_inverse_at(x, dpt, i, t);
+                    }
+                }
+                const bool mid_ok = T > 0 && frame_idx < T;
+                if (mid_ok && NC > 0) mg_basis_row_dev(ip->knots, ip->NB + 4, tmid, &i0, swm + 4 * c);
+                snf[c] = T;
+                si0[c] = i0;
+                stmid[c] = tmid;
+                if (ip->n_frames) ip->n_frames[b0 + c] = T;
+                if (ip->time_mid) ip->time_mid[b0 + c] = mid_ok ? tmid : NAN;
             }
-            const bool mid_ok = T > 0 && frame_idx < T;
-            if (mid_ok && NC > 0) mg_basis_row_dev(ip->knots, ip->NB + 4, tmid, &i0, swm + 4 * c);
-            snf[c] = T;
-            si0[c] = i0;
-            stmid[c] = tmid;
-            if (ip->n_frames) ip->n_frames[b0 + c] = T;
-            if (ip->time_mid) ip->time_mid[b0 + c] = mid_ok ? tmid : NAN;
         }
     } else {
         // phase 1 on the other three waves: the end frames' control points
@@ -475,8 +540,30 @@ __global__ __launch_bounds__(256) void mg_feature_points_warped_kernel(const mg_
     }
     __syncthreads();
 
+    // smoothed: the root position at the candidate's first time, the root pose at its last one, the mid frame's channels at time_mid
+    if (smooth) {
+        const int NE = NC + MG_FPW_ENDS;
+        for (int e = tid; e < ncand * NE; e += 256) {
+            const int c = e / NE, ch = e - c * NE;
+            if (sbad[c] || snf[c] <= 0) continue;
+            if (ch < NC && frame_idx >= snf[c]) continue;
+            const int slot = ch < NC ? 1 : (ch < NC + 3 ? 0 : 2);
+            const int chan = ch < NC ? schan[ch] : (ch < NC + 3 ? ch - NC : ch - NC - 3);
+            const double *s = slat + c * L;
+            const size_t r0 = (size_t)si0[3 * c + slot] * D + (size_t)chan;
+            double c4[4];
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const size_t r = r0 + (size_t)j * D;
+                c4[j] = mg_control_point(mean[r], Et + r, R, L, [&](int k) { return s[k]; });
+            }
+            const double v = mg_taps4(swm + 12 * c + 4 * slot, c4, 1);
+            if (ch < NC) smid[c * MS + ch] = v;
+            else sends[c * MG_FPW_ENDS + (ch - NC)] = v;
+        }
+    }
     // mid: channel schan[ch] of every candidate's frame at ITS time_mid
-    for (int e = tid; e < ncand * NC; e += 256) {
+    for (int e = tid; e < (smooth ? 0 : ncand * NC); e += 256) {
         const int c = e / NC, ch = e - c * NC;
         if (sbad[c] || snf[c] <= 0 || frame_idx >= snf[c]) continue;
         const double *s = slat + c * L;
@@ -495,9 +582,13 @@ __global__ __launch_bounds__(256) void mg_feature_points_warped_kernel(const mg_
     for (int e = tid; e < ncand * (J + 1); e += 256) {
         const int c = e / (J + 1), u = e - c * (J + 1);
         const double *cp = scp + c * CS;
-        auto channel = [&](int s, int d) { return mg_fp_channel(cp, sw, smap, stap, D, s, d); };
         const int T = snf[c];
         const bool bad = sbad[c] != 0 || T <= 0;
+        const double *ends = sends + c * MG_FPW_ENDS;
+        auto channel = [&](int s, int d) {
+            if (smooth) return bad ? 0.0 : ends[3 * s + d];                 // (slot 0: the first time's, slot 1: the last time's)
+            return mg_fp_channel(cp, sw, smap, stap, D, s, d);
+        };
         const int64_t b = b0 + c;
         const double s0[3] = {channel(0, 0), channel(0, 1), channel(0, 2)};
         if (u < J) {
@@ -519,7 +610,7 @@ struct mg_fpw_plan : mg_fp_plan {       // (w: the two end frames')
     int32_t NC = 0, need_mid = 0;
 };
 
-static int mg_fpw_plan_of(const char *who, int i, const mg_warped_feature_point_item &q, mg_fpw_plan &pl) {
+static int mg_fpw_plan_of(const char *who, int i, const mg_warped_feature_point_item &q, mg_fpw_plan &pl, bool smooth) {
     const mg_primitive *p = q.prim;
     const int D = p->D, F = p->F, NB = p->NB;
     int rc = mg_fp_refuse(who, i, D, q.skeleton, [&]() -> int {
@@ -545,15 +636,16 @@ static int mg_fpw_plan_of(const char *who, int i, const mg_warped_feature_point_
     pl.joints.compact(pl.chan, pos);
     pl.NC = (int32_t)pl.chan.size();
     pl.chan.insert(pl.chan.end(), pos.begin(), pos.end());
-    pl.need_mid = q.n_joints > 0 || q.time_mid_dev != nullptr;
-    pl.lds = mg_fpw_layout_of(F, p->Lt, pl.need_mid, p->L, pl.rows.NRS, pl.rows.NCP, pl.NC, D, q.n_joints, pl.rec_stride).total_bytes;
+    pl.need_mid = smooth || q.n_joints > 0 || q.time_mid_dev != nullptr;   // (a smoothed item always inverts: its end times are the candidate's own)
+    pl.lds = mg_fpw_layout_of(F, p->Lt, pl.need_mid, p->L, pl.rows.NRS, pl.rows.NCP, pl.NC, D, q.n_joints, pl.rec_stride, smooth ? 1 : 0).total_bytes;
     MG_ITEM_REFUSE(pl.lds > MG_FP_LDS_MAX, "%s: item %d: the tables (%d canonical frames x %d candidates, %d x %d control-point values, %d joints) do not fit LDS", who,
                    i, F, MG_FP_TILE, p->L, pl.rows.NRS, q.n_joints);
     MG_ITEM_REFUSE_GRID(who, i, q.n_samples, MG_FP_TILE);
     return MG_OK;
 }
 
-static int mg_fpw_check(const char *who, int32_t n_items, const mg_warped_feature_point_item *items, int latent_dtype, std::vector<mg_fpw_plan> &plans) {
+static int mg_fpw_check(const char *who, int32_t n_items, const mg_warped_feature_point_item *items, int latent_dtype, std::vector<mg_fpw_plan> &plans,
+                        const uint8_t *smooth = nullptr) {
     typedef mg_warped_feature_point_item item;
     plans.resize((size_t)std::max(n_items, 0));
     int rc = mg_items_check(
@@ -576,11 +668,20 @@ static int mg_fpw_check(const char *who, int32_t n_items, const mg_warped_featur
         });
     if (rc != MG_OK) return rc;
     for (int i = 0; i < n_items; i++)
-        if ((rc = mg_fpw_plan_of(who, i, items[i], plans[(size_t)i])) != MG_OK) return rc;
+        if ((rc = mg_fpw_plan_of(who, i, items[i], plans[(size_t)i], smooth && smooth[i])) != MG_OK) return rc;
     return MG_OK;
 }
 
-static int mg_fpw_run(const char *who, int32_t n_items, const mg_warped_feature_point_item *items, int latent_dtype, const std::vector<mg_fpw_plan> &plans) {
+// the members of the smoothed item beyond mg_fpw_item's (nothing for the plain one)
+static void mg_fpw_fill_smooth(mg_fpw_item &, int, const uint8_t *, const double *) {}
+static void mg_fpw_fill_smooth(mg_fpws_item &d, int i, const uint8_t *smooth, const double *H) { d.H = H; d.smooth = smooth[i] ? 1 : 0; }
+
+// SMOOTH: mg_feature_points_warped_smoothed -- `smooth` one byte per item, a device table, LDS bits and a profile slot of its own
+template <bool SMOOTH>
+static int mg_fpw_run(const char *who, int32_t n_items, const mg_warped_feature_point_item *items, int latent_dtype, const std::vector<mg_fpw_plan> &plans,
+                      const uint8_t *smooth = nullptr) {
+    typedef typename mg_fpw_types<SMOOTH>::item ditem;
+    typedef typename mg_fpw_types<SMOOTH>::args dargs;
     const size_t elem = latent_dtype == MG_F64 ? 8 : 4;
     auto samples_of = [&](int i) { return items[i].n_samples; };
     std::vector<int32_t> wg0;
@@ -588,8 +689,15 @@ static int mg_fpw_run(const char *who, int32_t n_items, const mg_warped_feature_
         mg_cut_items(n_items, samples_of, [&](int i) { return plans[(size_t)i].lds; }, MG_FP_TILE, MG_FEATURE_POINTS_MAX_ITEMS, wg0);
     if (launches.empty()) return MG_OK;
     mg_context *ctx = nullptr;
+    for (int i = 0; i < n_items; i++)
+        if (items[i].n_samples > 0) ctx = items[i].prim->ctx;
+    const double *H = nullptr;
+    if (SMOOTH) {
+        const int rc0 = mg_savgol_table_dev(ctx, &H);
+        if (rc0 != MG_OK) return rc0;
+    }
     std::vector<unsigned char> table;    // the items, then every item's row list, map, channel list and chain records
-    const int rc = mg_items_table<mg_fpw_item>(who, n_items, samples_of, table, [&](int i, mg_fpw_item &d, auto append) {
+    const int rc = mg_items_table<ditem>(who, n_items, samples_of, table, [&](int i, ditem &d, auto append) {
         const mg_warped_feature_point_item &q = items[i];
         const mg_primitive *p = q.prim;
         const mg_fpw_plan &pl = plans[(size_t)i];
@@ -601,27 +709,30 @@ static int mg_fpw_run(const char *who, int32_t n_items, const mg_warped_feature_
         d.Lt = p->Lt; d.F = p->F; d.NB = p->NB; d.NC = pl.NC;
         d.frame_idx = q.frame_idx; d.need_mid = pl.need_mid;
         d.off_chan = append(pl.chan); d.off_rec = append(pl.rec);
+        mg_fpw_fill_smooth(d, i, smooth, H);
     });
     if (rc != MG_OK) return rc;
     return mg_items_launch(
-        ctx, who, ctx->tab[MG_TABLE_FEATURE_POINTS_WARPED], table.data(), table.size(), std::max(table.size() * 2, (size_t)64 * 1024), launches, latent_dtype,
-        MG_LDS_FEATURE_POINTS_WARPED_F32, MG_LDS_FEATURE_POINTS_WARPED_F64, MG_PROF_FEATURE_POINTS_WARPED,
-        [](auto LAT_F64) { return mg_feature_points_warped_kernel<decltype(LAT_F64)::value>; },
-        [](const char *base, const mg_item_launch &l) { return mg_fpw_args{base, (const mg_fpw_item *)base + l.first, l.n_items}; });
+        ctx, who, ctx->tab[SMOOTH ? MG_TABLE_FEATURE_POINTS_SMOOTHED : MG_TABLE_FEATURE_POINTS_WARPED], table.data(), table.size(),
+        std::max(table.size() * 2, (size_t)64 * 1024), launches, latent_dtype, SMOOTH ? MG_LDS_FEATURE_POINTS_SMOOTHED_F32 : MG_LDS_FEATURE_POINTS_WARPED_F32,
+        SMOOTH ? MG_LDS_FEATURE_POINTS_SMOOTHED_F64 : MG_LDS_FEATURE_POINTS_WARPED_F64, SMOOTH ? MG_PROF_FEATURE_POINTS_SMOOTHED : MG_PROF_FEATURE_POINTS_WARPED,
+        [](auto LAT_F64) { return mg_feature_points_warped_kernel<decltype(LAT_F64)::value, SMOOTH>; },
+        [](const char *base, const mg_item_launch &l) { return dargs{base, (const ditem *)base + l.first, l.n_items}; });
 }
 
 extern "C" int mg_feature_points_warped(int32_t n_items, const mg_warped_feature_point_item *items, int latent_dtype) {
     std::vector<mg_fpw_plan> plans;
     const int rc = mg_fpw_check("mg_feature_points_warped", n_items, items, latent_dtype, plans);
     if (rc != MG_OK) return rc;
-    return mg_fpw_run("mg_feature_points_warped", n_items, items, latent_dtype, plans);
+    return mg_fpw_run<false>("mg_feature_points_warped", n_items, items, latent_dtype, plans);
 }
 
-extern "C" int mg_feature_points_warped_host(int32_t n_items, const mg_warped_feature_point_item *items, int latent_dtype) {
+// the _host twin of either form: host arrays in, host arrays out
+template <bool SMOOTH>
+static int mg_fpw_host(const char *who, int32_t n_items, const mg_warped_feature_point_item *items, const uint8_t *smooth, int latent_dtype) {
     typedef mg_warped_feature_point_item item;
-    const char *who = "mg_feature_points_warped_host";
     std::vector<mg_fpw_plan> plans;
-    const int rc = mg_fpw_check(who, n_items, items, latent_dtype, plans);
+    const int rc = mg_fpw_check(who, n_items, items, latent_dtype, plans, smooth);
     if (rc != MG_OK) return rc;
     const mg_item_output<item> outs[6] = {{&item::start_root_dev, 3, nullptr}, {&item::points_dev, 3, &item::n_joints}, {&item::root_end_dev, 2, nullptr},
                                           {&item::heading_end_dev, 2, nullptr}, {&item::heading_len_dev, 1, nullptr}, {&item::time_mid_dev, 1, nullptr}};
@@ -635,7 +746,25 @@ extern "C" int mg_feature_points_warped_host(int32_t n_items, const mg_warped_fe
         if (rc2 != MG_OK) return rc2;
         for (int i = 0; i < n_items; i++)
             if (items[i].n_samples > 0 && items[i].n_frames_dev) dev[i].n_frames_dev = at[(size_t)i].dev<int32_t>();
-        if ((rc2 = mg_fpw_run(who, n_items, dev, latent_dtype, plans)) != MG_OK) return rc2;
+        if ((rc2 = mg_fpw_run<SMOOTH>(who, n_items, dev, latent_dtype, plans, smooth)) != MG_OK) return rc2;
         return lens.download();
     });
+}
+
+extern "C" int mg_feature_points_warped_host(int32_t n_items, const mg_warped_feature_point_item *items, int latent_dtype) {
+    return mg_fpw_host<false>("mg_feature_points_warped_host", n_items, items, nullptr, latent_dtype);
+}
+
+extern "C" int mg_feature_points_warped_smoothed(int32_t n_items, const mg_warped_feature_point_item *items, const uint8_t *smooth, int latent_dtype) {
+    const char *who = "mg_feature_points_warped_smoothed";
+    MG_ITEM_REQUIRE(n_items <= 0 || smooth, "%s: smooth is NULL", who);
+    std::vector<mg_fpw_plan> plans;
+    const int rc = mg_fpw_check(who, n_items, items, latent_dtype, plans, smooth);
+    if (rc != MG_OK) return rc;
+    return mg_fpw_run<true>(who, n_items, items, latent_dtype, plans, smooth);
+}
+
+extern "C" int mg_feature_points_warped_smoothed_host(int32_t n_items, const mg_warped_feature_point_item *items, const uint8_t *smooth, int latent_dtype) {
+    MG_ITEM_REQUIRE(n_items <= 0 || smooth, "mg_feature_points_warped_smoothed_host: smooth is NULL");
+    return mg_fpw_host<true>("mg_feature_points_warped_smoothed_host", n_items, items, smooth, latent_dtype);
 }

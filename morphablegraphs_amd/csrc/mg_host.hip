@@ -14,6 +14,7 @@
 #include "mg_constraint_image.h"
 #include "mg_joint_plan.h"
 #include "mg_primitive_image.h"
+#include "mg_savgol_table.h"
 #include <dlfcn.h>
 
 // ---------------------------------------------------------------------------------------
@@ -200,6 +201,20 @@ int mg_device_table::upload(mg_context *ctx, const char *who, const void *data, 
 extern "C" int mg_context_table_uploads(mg_context *ctx, int which, int64_t *uploads) {
     MG_REQUIRE(ctx && uploads && which >= 0 && which < MG_TABLE_COUNT, "mg_context_table_uploads: bad arguments");
     *uploads = ctx->tab[which].uploads;
+    return MG_OK;
+}
+
+// The Savitzky-Golay hat matrix (225 doubles) for the kernels that smooth a time row: formed on the host, uploaded on first use
+int mg_savgol_table_dev(mg_context *ctx, const double **H) {
+    mg_device_table &dt = ctx->tab[MG_TABLE_SAVGOL];
+    if (dt.uploads == 0 || !dt.dev) {   // (the table never changes: once per context)
+        double table[MG_SAVGOL_WINDOW * MG_SAVGOL_WINDOW];
+        mg_savgol_hat_matrix(table);
+        MG_HIP_CHECK(hipSetDevice(ctx->device));
+        const int rc = dt.upload(ctx, "the Savitzky-Golay table", table, sizeof(table));
+        if (rc != MG_OK) return rc;
+    }
+    *H = (const double *)dt.base();
     return MG_OK;
 }
 
@@ -900,6 +915,26 @@ extern "C" int mg_time_function_sample_rows(mg_primitive *p, const void *gamma, 
     MG_REQUIRE(gamma && times && lengths, "mg_time_function_sample: NULL pointer");
     { int rc0 = mg_use_device(p->ctx); if (rc0 != MG_OK) return rc0; }
     return mg_launch_timewarp(p, gamma, gdt, B, ld, speed, times, lengths, t_cap, row_pitch, canonical_out);
+}
+
+// The same rows after the Savitzky-Golay pass (smooth_time_parameters): one launch, the unsmoothed row never in memory
+extern "C" int mg_time_function_sample_smoothed_rows(mg_primitive *p, const void *gamma, int gdt, int64_t B, int64_t ld, double speed, double *times, int32_t *lengths,
+                                                     int32_t t_cap, int64_t row_pitch, double *canonical_out) {
+    MG_REQUIRE(p != nullptr, "mg_time_function_sample_smoothed: primitive is NULL");
+    MG_REQUIRE(p->Lt > 0, "mg_time_function_sample_smoothed: the primitive has no time model");
+    MG_REQUIRE(B >= 0 && B < ((int64_t)1 << 31) && (gdt == MG_F32 || gdt == MG_F64) && ld >= p->Lt,
+               "mg_time_function_sample_smoothed: bad arguments (ld %lld, n_time_components %d)", (long long)ld, p->Lt);
+    MG_REQUIRE(speed > 0.0 && std::isfinite(speed) && t_cap >= 2, "mg_time_function_sample_smoothed: speed must be positive and finite, t_cap >= 2");
+    MG_REQUIRE(row_pitch >= t_cap, "mg_time_function_sample_smoothed: a row pitch of %lld doubles is shorter than t_cap %d", (long long)row_pitch, t_cap);
+    if (B == 0) return MG_OK;
+    MG_REQUIRE(gamma && times && lengths, "mg_time_function_sample_smoothed: NULL pointer");
+    { int rc0 = mg_use_device(p->ctx); if (rc0 != MG_OK) return rc0; }
+    return mg_launch_timewarp(p, gamma, gdt, B, ld, speed, times, lengths, t_cap, row_pitch, canonical_out, true);
+}
+
+extern "C" int mg_time_function_sample_smoothed(mg_primitive *p, const void *gamma, int gdt, int64_t B, int64_t ld, double speed, double *times, int32_t *lengths,
+                                                int32_t t_cap, double *canonical_out) {
+    return mg_time_function_sample_smoothed_rows(p, gamma, gdt, B, ld, speed, times, lengths, t_cap, t_cap, canonical_out);
 }
 
 extern "C" int mg_time_function_sample(mg_primitive *p, const void *gamma, int gdt, int64_t B, int64_t ld, double speed, double *times, int32_t *lengths,

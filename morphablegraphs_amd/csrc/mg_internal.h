@@ -18,7 +18,7 @@
 enum { MG_PROF_FRAMES = 0, MG_PROF_GMM_LOG_PROB, MG_PROF_SCORE_CONSTRAINTS, MG_PROF_ARGMIN, MG_PROF_GMM_SAMPLE, MG_PROF_SPLINE_EVALUATE, MG_PROF_STEP,
        MG_PROF_OPTIONS_STEP, MG_PROF_JOINT_TRACKS, MG_PROF_FRAME_CONSTRAINTS, MG_PROF_TRAJECTORY, MG_PROF_CLUSTER_TREE_SEARCH, MG_PROF_WALK_FRAMES,
        MG_PROF_WALK_TIME, MG_PROF_STEP_LENGTHS, MG_PROF_FEATURE_POINTS, MG_PROF_FEATURE_POINTS_WARPED, MG_PROF_MIXTURE_SCORES,
-       MG_PROF_POINT_CLOUDS, MG_PROFILE_SLOTS = MG_PROF_POINT_CLOUDS + 1 };
+       MG_PROF_POINT_CLOUDS, MG_PROF_FEATURE_POINTS_SMOOTHED, MG_PROFILE_SLOTS = MG_PROF_FEATURE_POINTS_SMOOTHED + 1 };
 
 int mg_hip_fail(hipError_t e, const char *what);
 
@@ -51,7 +51,8 @@ struct mg_device_table {
 enum { MG_LDS_TRAJECTORY = 1, MG_LDS_TIMEWARP = 2, MG_LDS_JOINT_TRACKS = 4, MG_LDS_FRAME_CONSTRAINTS = 8, MG_LDS_WALK_FRAMES = 16, MG_LDS_WALK_SCORE = 32,
        MG_LDS_WALK_TIME = 64, MG_LDS_STEP_LENGTH_F32 = 128, MG_LDS_STEP_LENGTH_F64 = 256, MG_LDS_FEATURE_POINTS_F32 = 512, MG_LDS_FEATURE_POINTS_F64 = 1024,
        MG_LDS_FEATURE_POINTS_WARPED_F32 = 2048, MG_LDS_FEATURE_POINTS_WARPED_F64 = 4096, MG_LDS_MIXTURE_SCORES = 8192, MG_LDS_POINT_CLOUDS = 16384,
-       MG_LDS_WALKS_FRAMES = 32768, MG_LDS_WALKS_SAMPLE = 65536, MG_LDS_WALKS_WARPED = 131072, MG_LDS_WALKS_TIME = 262144 };
+       MG_LDS_WALKS_FRAMES = 32768, MG_LDS_WALKS_SAMPLE = 65536, MG_LDS_WALKS_WARPED = 131072, MG_LDS_WALKS_TIME = 262144,
+       MG_LDS_WALKS_TIME_SMOOTHED = 524288, MG_LDS_FEATURE_POINTS_SMOOTHED_F32 = 1048576, MG_LDS_FEATURE_POINTS_SMOOTHED_F64 = 2097152 };
 
 struct mg_context {
     int device = 0;
@@ -274,7 +275,8 @@ int mg_launch_argmin_gather(mg_context *ctx, const void *v, int dt, int64_t n, v
 int mg_launch_gmm_jac(mg_primitive *p, const void *x, int xdt, int64_t B, int64_t ld, double *out);
 int mg_launch_time_function(mg_primitive *p, const void *gamma, int gdt, int64_t B, int64_t ld, double *out);
 int mg_launch_timewarp(mg_primitive *p, const void *gamma, int gdt, int64_t B, int64_t ld, double speed, double *times, int32_t *lens, int32_t t_cap,
-                       int64_t row_pitch, double *canonical_out);   // mg_timewarp.hip
+                       int64_t row_pitch, double *canonical_out, bool smooth = false);   // mg_timewarp.hip; smooth: the Savitzky-Golay pass on the way out
+int mg_savgol_table_dev(mg_context *ctx, const double **H);   // mg_host.hip: the hat matrix of mg_savgol_table.h on the device (MG_TABLE_SAVGOL), uploaded once
 int mg_launch_frames_at(mg_primitive *p, const void *lat, int ldt, int64_t B, int64_t ld, const double *times, const int32_t *lens, int32_t t_cap,
                         void *out, int odt);
 int mg_launch_argmin(mg_context *ctx, const void *v, int dt, int64_t n, void *out_dev);

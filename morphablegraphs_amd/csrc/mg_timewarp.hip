@@ -22,10 +22,14 @@
 #include "mg_spline_device.h"
 #include "mg_timewarp_device.h"
 
+// SMOOTH: the row goes through the Savitzky-Golay pass (H: the hat matrix, mg_savgol_table.h) on its way out -- mg_tw_smoothed_row, whose
+// window lies behind dp; a row of fewer than 15 samples reports its length and is not written.  false: H is not read.
+template <bool SMOOTH>
 __global__ __launch_bounds__(MG_TW_BLOCK) void mg_timewarp_kernel(const double *__restrict__ tphi, const double *__restrict__ tmean,
                                                                   const void *__restrict__ gamma, int gamma_f64, int64_t ld, int F, int Lt,
                                                                   double inv_speed, double *__restrict__ times, int32_t *__restrict__ lens,
-                                                                  int32_t t_cap, int64_t row_pitch, double *__restrict__ canonical_out) {
+                                                                  int32_t t_cap, int64_t row_pitch, double *__restrict__ canonical_out,
+                                                                  const double *__restrict__ H) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     double *x = (double *)smem;      // [F] the canonical time function t(t'): the spline's abscissae; ordinates are 0 .. F-1
     double *M = x + F;               // [F] second derivatives
@@ -56,6 +60,10 @@ __global__ __launch_bounds__(MG_TW_BLOCK) void mg_timewarp_kernel(const double *
     if (T > t_cap) return;
     double *tb = times + b * row_pitch;   // (a row holds t_cap samples; row_pitch >= t_cap doubles lie between two rows' starts)
     const double step = mg_tw_sample_step(stop, num);
+    if (SMOOTH) {
+        if (T >= MG_TW_SMOOTH_W) mg_tw_smoothed_row(x, M, F, T, num, stop, step, H, dp + F, tb, tid);
+        return;
+    }
     for (int j = tid; j < T; j += MG_TW_BLOCK) {
         double v;
         if (j == 0) v = 0.0;
@@ -104,17 +112,24 @@ __global__ __launch_bounds__(MG_FA_BLOCK) void mg_frames_at_kernel(const double 
 
 // (a property of kernel AND device: once per context)
 static hipError_t mg_tw_lds_opt_in(mg_context *ctx) {
-    return mg_lds_opt_in_once(ctx, MG_LDS_TIMEWARP, 160 * 1024, mg_timewarp_kernel, mg_frames_at_kernel<true, true>, mg_frames_at_kernel<true, false>,
+    return mg_lds_opt_in_once(ctx, MG_LDS_TIMEWARP, 160 * 1024, mg_timewarp_kernel<false>, mg_timewarp_kernel<true>, mg_frames_at_kernel<true, true>, mg_frames_at_kernel<true, false>,
                               mg_frames_at_kernel<false, true>, mg_frames_at_kernel<false, false>);
 }
 
 int mg_launch_timewarp(mg_primitive *p, const void *gamma, int gdt, int64_t B, int64_t ld, double speed, double *times, int32_t *lens, int32_t t_cap,
-                       int64_t row_pitch, double *canonical_out) {
-    const size_t lds = (size_t)4 * p->F * 8;
+                       int64_t row_pitch, double *canonical_out, bool smooth) {
+    const size_t lds = ((size_t)4 * p->F + (smooth ? MG_TW_SMOOTH_LDS : 0)) * 8;   // x, M, cp, dp; the smoothed row's window behind them
+    const double *H = nullptr;
+    if (smooth) {
+        const int rc = mg_savgol_table_dev(p->ctx, &H);
+        if (rc != MG_OK) return rc;
+    }
     if (p->F < 4 || p->F > MG_TW_MAX_F) { mg_set_error("mg_time_function_sample: %d canonical frames (4 .. %d supported)", p->F, MG_TW_MAX_F); return MG_ERR_UNSUPPORTED; }
     MG_HIP_CHECK(mg_tw_lds_opt_in(p->ctx));
-    hipLaunchKernelGGL(mg_timewarp_kernel, dim3((unsigned)B), dim3(MG_TW_BLOCK), lds, p->ctx->stream, (const double *)p->d_tphi, (const double *)p->d_tmean, gamma,
-                       gdt == MG_F64 ? 1 : 0, ld, (int)p->F, (int)p->Lt, 1.0 / speed, times, lens, t_cap, row_pitch, canonical_out);
+    mg_dispatch_flags(smooth, [&](auto SMOOTH) {
+        hipLaunchKernelGGL(mg_timewarp_kernel<SMOOTH>, dim3((unsigned)B), dim3(MG_TW_BLOCK), lds, p->ctx->stream, (const double *)p->d_tphi, (const double *)p->d_tmean,
+                           gamma, gdt == MG_F64 ? 1 : 0, ld, (int)p->F, (int)p->Lt, 1.0 / speed, times, lens, t_cap, row_pitch, canonical_out, H);
+    });
     MG_HIP_CHECK(hipGetLastError());
     return MG_OK;
 }

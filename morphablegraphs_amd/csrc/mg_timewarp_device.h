@@ -10,6 +10,11 @@
 //   mg_tw_sample_count         int(round(t(F - 2)) * (1 / speed)), or "no row" for a time function that is not finite or absurd
 //   mg_tw_sample_point         numpy.linspace(1, t(F - 2), num)[q]
 //   mg_tw_interval, mg_tw_inverse_at   the piece that holds a sample point, and the cubic on it
+//   mg_tw_row_sample           sample j of the row: 0, the inverse at sample point j - 1, F - 1
+// The smoothed row (smooth_time_parameters: scipy.signal.savgol_filter(row, 15, 3), stated as the table of mg_savgol_table.h):
+//   mg_tw_smooth_window        which row of the hat matrix H and which 15 unsmoothed samples make smoothed sample q
+//   mg_tw_smoothed             H's row times those samples, every product and sum rounded on its own, k ascending
+//   mg_tw_smoothed_row         a wave's whole row, 64 samples at a time through an LDS window of MG_TW_SMOOTH_LDS doubles
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -117,4 +122,68 @@ __device__ __forceinline__ double mg_tw_inverse_at(const X &x, const MA &M, int 
     const double hi_ = x[i + 1] - x[i], A = x[i + 1] - t, Bq = t - x[i];
     return M[i] * A * A * A / (6.0 * hi_) + M[i + 1] * Bq * Bq * Bq / (6.0 * hi_) + ((double)i / hi_ - M[i] * hi_ / 6.0) * A +
            ((double)(i + 1) / hi_ - M[i + 1] * hi_ / 6.0) * Bq;
+}
+
+// sample j of a row of T = num + 2 samples: 0 in front, F - 1 behind, between them the inverse at numpy.linspace(1, stop, num)[j - 1]
+template <class X, class MA>
+__device__ __forceinline__ double mg_tw_row_sample(const X &x, const MA &M, int F, int j, int T, int num, double stop, double step) {
+    if (j == 0) return 0.0;
+    if (j == T - 1) return (double)(F - 1);
+    const double t = mg_tw_sample_point(j - 1, num, stop, step);
+    return mg_tw_inverse_at(x, M, mg_tw_interval(x, F, t), t);
+}
+
+// ---- the smoothed row: savgol_filter(row, 15, 3), mode "interp" (mg_savgol_table.h) --------------------------------------------------
+#define MG_TW_SMOOTH_W 15                                            // the window; a row shorter than this has no smoothed form
+#define MG_TW_SMOOTH_HALF 7
+#define MG_TW_SMOOTH_MID (MG_TW_BLOCK + 2 * MG_TW_SMOOTH_HALF)       // unsmoothed samples the inner windows of 64 outputs span (78)
+#define MG_TW_SMOOTH_LDS (MG_TW_SMOOTH_MID + 2 * MG_TW_SMOOTH_W)     // ... then the row's first 15 and its last 15
+
+// smoothed sample q of a row of T >= 15: row `row` of H times unsmoothed samples base .. base + 14 (head and tail cannot overlap)
+__device__ __forceinline__ void mg_tw_smooth_window(int q, int T, int *row, int *base) {
+    if (q < MG_TW_SMOOTH_HALF) { *row = q; *base = 0; }
+    else if (q >= T - MG_TW_SMOOTH_HALF) { *row = MG_TW_SMOOTH_W - (T - q); *base = T - MG_TW_SMOOTH_W; }
+    else { *row = MG_TW_SMOOTH_HALF; *base = q - MG_TW_SMOOTH_HALF; }
+}
+
+// Hrow . u over the window, k ascending: every product and every sum rounded on its own (time_smoothing.smooth_time_row_host's bits)
+template <class U>
+__device__ __forceinline__ double mg_tw_smoothed(const double *Hrow, const U &u) {
+#pragma clang fp contract(off)
+    double acc = Hrow[0] * u[0];
+    for (int k = 1; k < MG_TW_SMOOTH_W; k++) {
+        const double prod = Hrow[k] * u[k];
+        acc = acc + prod;
+    }
+    return acc;
+}
+
+// The whole smoothed row of one wave (MG_TW_BLOCK lanes), T >= 15, into tb[0 .. T): per chunk of 64 outputs the unsmoothed samples the
+// chunk needs go to win[MG_TW_SMOOTH_LDS] -- win[e] = sample c0 - 7 + e for e < 78, where the row has one; the row's first 15 behind
+// them where the chunk holds an output below 7, its last 15 where it holds one from T - 7 on -- then every lane forms its output.
+// The row is never smoothed in place: nothing is read back from tb.
+template <class X, class MA>
+__device__ __forceinline__ void mg_tw_smoothed_row(const X &x, const MA &M, int F, int T, int num, double stop, double step, const double *H,
+                                                   double *win, double *tb, int tid) {
+    double *head = win + MG_TW_SMOOTH_MID, *tail = head + MG_TW_SMOOTH_W;
+    for (int c0 = 0; c0 < T; c0 += MG_TW_BLOCK) {
+        const int lo = c0 - MG_TW_SMOOTH_HALF;
+        const bool want_head = c0 < MG_TW_SMOOTH_HALF, want_tail = c0 + MG_TW_BLOCK > T - MG_TW_SMOOTH_HALF;
+        for (int e = tid; e < MG_TW_SMOOTH_LDS; e += MG_TW_BLOCK) {
+            int j = -1;
+            if (e < MG_TW_SMOOTH_MID) j = lo + e;
+            else if (e < MG_TW_SMOOTH_MID + MG_TW_SMOOTH_W) { if (want_head) j = e - MG_TW_SMOOTH_MID; }
+            else if (want_tail) j = T - MG_TW_SMOOTH_W + (e - MG_TW_SMOOTH_MID - MG_TW_SMOOTH_W);
+            if (j >= 0 && j < T) win[e] = mg_tw_row_sample(x, M, F, j, T, num, stop, step);
+        }
+        __syncthreads();
+        const int q = c0 + tid;
+        if (q < T) {
+            int row, base;
+            mg_tw_smooth_window(q, T, &row, &base);
+            const double *u = q < MG_TW_SMOOTH_HALF ? head : (q >= T - MG_TW_SMOOTH_HALF ? tail : win + (base - lo));
+            tb[q] = mg_tw_smoothed(H + MG_TW_SMOOTH_W * row, u);
+        }
+        __syncthreads();   // (the next chunk overwrites the window)
+    }
 }

@@ -135,11 +135,14 @@ struct mg_walks_time_args {
     int64_t ld;
     double inv_speed;
     int32_t s_max, t_cap;
+    const uint8_t *smooth;        // SMOOTH: one byte per node, other than 0: the node's rows go through the Savitzky-Golay pass
+    const double *H;              // SMOOTH: its hat matrix (mg_savgol_table.h)
 };
 
 // Row (w, i) of a node with a time model: mg_timewarp_kernel (mg_timewarp.hip) statement by statement, gamma read from the step's own
 // latent row.  Of a node without one: numpy.linspace(0, F, count) = arange(count) * (F / (count - 1)), the last one F itself.
-template <bool LAT_F64>
+// SMOOTH (mg_walks_time_functions_smoothed): as mg_timewarp_kernel<true> for the nodes a.smooth marks, the window behind dp.
+template <bool LAT_F64, bool SMOOTH>
 __global__ __launch_bounds__(MG_TW_BLOCK) void mg_walks_time_kernel(const mg_walks_time_args a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int64_t ws = blockIdx.x, wk = ws / a.s_max;
@@ -183,6 +186,10 @@ __global__ __launch_bounds__(MG_TW_BLOCK) void mg_walks_time_kernel(const mg_wal
     if (tid == 0) a.lens[ws] = T <= a.t_cap ? T : -T;   // (negative: the caller's rows are too short; nothing else is written)
     if (T > a.t_cap) return;
     const double step = mg_tw_sample_step(stop, num);
+    if (SMOOTH && a.smooth[a.node_of[ws]]) {
+        if (T >= MG_TW_SMOOTH_W) mg_tw_smoothed_row(x, M, F, T, num, stop, step, a.H, dp + F, tb, tid);
+        return;
+    }
     for (int j = tid; j < T; j += MG_TW_BLOCK) {
         double v;
         if (j == 0) v = 0.0;
@@ -589,15 +596,17 @@ extern "C" int mg_walks_frames_at(int32_t n_nodes, mg_primitive *const *prims, c
 }
 
 // Every step's time row.  What a row is made of is a node's; which node, and where gamma lies, is the step's.
-extern "C" int mg_walks_time_functions(int32_t n_nodes, mg_primitive *const *prims, const int32_t *node_of, const int32_t *n_steps, const void *latents_dev,
-                                       int dtype, int64_t n_walks, int32_t s_max, int64_t ld, double speed, double *times_dev, int32_t *lengths_dev,
-                                       int32_t t_cap) {
-    const char *who = "mg_walks_time_functions";
+// SMOOTH: smooth_of_node marks the nodes whose rows go through the Savitzky-Golay pass; a table of the entry point's own
+template <bool SMOOTH>
+static int mg_walks_time_launch(const char *who, int which_table, unsigned lds_bit, int32_t n_nodes, mg_primitive *const *prims, const int32_t *node_of,
+                                const int32_t *n_steps, const uint8_t *smooth_of_node, const void *latents_dev, int dtype, int64_t n_walks, int32_t s_max,
+                                int64_t ld, double speed, double *times_dev, int32_t *lengths_dev, int32_t t_cap) {
     std::vector<char> occurs;
     int rc = mg_walks_check_tables(who, n_nodes, prims, node_of, n_steps, n_walks, s_max, occurs);
     if (rc != MG_OK) return rc;
     MG_WALKS_REQUIRE((dtype == MG_F32 || dtype == MG_F64) && ld >= 1 && t_cap >= 1, "%s: bad arguments", who);
     MG_WALKS_REQUIRE(speed > 0.0 && std::isfinite(speed), "%s: speed must be positive and finite", who);
+    MG_WALKS_REQUIRE(!SMOOTH || smooth_of_node, "%s: smooth_of_node is NULL", who);
     const double inv_speed = 1.0 / speed;
     std::vector<mg_walks_time_node> nodes((size_t)n_nodes);
     int fmax = 0;
@@ -625,21 +634,41 @@ extern "C" int mg_walks_time_functions(int32_t n_nodes, mg_primitive *const *pri
     std::vector<unsigned char> tab((size_t)n_nodes * sizeof(mg_walks_time_node));
     memcpy(tab.data(), nodes.data(), tab.size());
     const size_t off_node = mg_table_append(tab, node_of, (size_t)rows * 4), off_steps = mg_table_append(tab, n_steps, (size_t)n_walks * 4);
+    const size_t off_smooth = SMOOTH ? mg_table_append(tab, smooth_of_node, (size_t)n_nodes) : 0;
     MG_HIP_CHECK(hipSetDevice(ctx->device));
-    mg_device_table &dt = ctx->tab[MG_TABLE_WALKS_TIME];
+    mg_device_table &dt = ctx->tab[which_table];
     rc = dt.upload(ctx, who, tab.data(), tab.size());
     if (rc != MG_OK) return rc;
     mg_walks_time_args a;
+    a.smooth = nullptr; a.H = nullptr;
+    if (SMOOTH) {
+        a.smooth = (const uint8_t *)(dt.base() + off_smooth);
+        if ((rc = mg_savgol_table_dev(ctx, &a.H)) != MG_OK) return rc;
+    }
     a.nodes = (const mg_walks_time_node *)dt.base();
     a.node_of = (const int32_t *)(dt.base() + off_node); a.n_steps = (const int32_t *)(dt.base() + off_steps);
     a.lat = latents_dev; a.times = times_dev; a.lens = lengths_dev;
     a.ld = ld; a.inv_speed = inv_speed; a.s_max = s_max; a.t_cap = t_cap;
-    const size_t lds = (size_t)4 * fmax * 8;   // x, M, cp, dp of the longest timed node that occurs
-    MG_HIP_CHECK(mg_lds_opt_in_once(ctx, MG_LDS_WALKS_TIME, 160 * 1024, mg_walks_time_kernel<true>, mg_walks_time_kernel<false>));
-    if (dtype == MG_F64) hipLaunchKernelGGL(mg_walks_time_kernel<true>, dim3((unsigned)rows), dim3(MG_TW_BLOCK), lds, ctx->stream, a);
-    else hipLaunchKernelGGL(mg_walks_time_kernel<false>, dim3((unsigned)rows), dim3(MG_TW_BLOCK), lds, ctx->stream, a);
+    const size_t lds = ((size_t)4 * fmax + (SMOOTH ? MG_TW_SMOOTH_LDS : 0)) * 8;   // x, M, cp, dp of the longest timed node that occurs; the smoothed row's window
+    MG_HIP_CHECK(mg_lds_opt_in_once(ctx, lds_bit, 160 * 1024, mg_walks_time_kernel<true, SMOOTH>, mg_walks_time_kernel<false, SMOOTH>));
+    if (dtype == MG_F64) hipLaunchKernelGGL((mg_walks_time_kernel<true, SMOOTH>), dim3((unsigned)rows), dim3(MG_TW_BLOCK), lds, ctx->stream, a);
+    else hipLaunchKernelGGL((mg_walks_time_kernel<false, SMOOTH>), dim3((unsigned)rows), dim3(MG_TW_BLOCK), lds, ctx->stream, a);
     MG_HIP_CHECK(hipGetLastError());
     return MG_OK;
+}
+
+extern "C" int mg_walks_time_functions(int32_t n_nodes, mg_primitive *const *prims, const int32_t *node_of, const int32_t *n_steps, const void *latents_dev,
+                                       int dtype, int64_t n_walks, int32_t s_max, int64_t ld, double speed, double *times_dev, int32_t *lengths_dev,
+                                       int32_t t_cap) {
+    return mg_walks_time_launch<false>("mg_walks_time_functions", MG_TABLE_WALKS_TIME, MG_LDS_WALKS_TIME, n_nodes, prims, node_of, n_steps, nullptr, latents_dev, dtype,
+                                       n_walks, s_max, ld, speed, times_dev, lengths_dev, t_cap);
+}
+
+extern "C" int mg_walks_time_functions_smoothed(int32_t n_nodes, mg_primitive *const *prims, const int32_t *node_of, const int32_t *n_steps,
+                                                const uint8_t *smooth_of_node, const void *latents_dev, int dtype, int64_t n_walks, int32_t s_max, int64_t ld,
+                                                double speed, double *times_dev, int32_t *lengths_dev, int32_t t_cap) {
+    return mg_walks_time_launch<true>("mg_walks_time_functions_smoothed", MG_TABLE_WALKS_TIME_SMOOTHED, MG_LDS_WALKS_TIME_SMOOTHED, n_nodes, prims, node_of, n_steps,
+                                      smooth_of_node, latents_dev, dtype, n_walks, s_max, ld, speed, times_dev, lengths_dev, t_cap);
 }
 
 // host arrays in, host arrays out: one device block for the call, synchronises
@@ -691,6 +720,24 @@ extern "C" int mg_walks_time_functions_host(int32_t n_nodes, mg_primitive *const
     if (rc != MG_OK) return rc;
     rc = mg_walks_time_functions(n_nodes, prims, node_of, n_steps, d_lat.dev<void>(), dtype, n_walks, s_max, ld, speed, d_times.dev<double>(),
                                  d_lens.dev<int32_t>(), t_cap);
+    if (rc != MG_OK) return rc;
+    return ws.download();
+}
+
+extern "C" int mg_walks_time_functions_smoothed_host(int32_t n_nodes, mg_primitive *const *prims, const int32_t *node_of, const int32_t *n_steps,
+                                                     const uint8_t *smooth_of_node, const void *latents, int dtype, int64_t n_walks, int32_t s_max, int64_t ld,
+                                                     double speed, double *times, int32_t *lengths, int32_t t_cap) {
+    MG_WALKS_REQUIRE(n_nodes >= 1 && prims && prims[0] && n_walks >= 0 && s_max >= 1 && ld >= 1 && t_cap >= 1 && (dtype == MG_F32 || dtype == MG_F64),
+                     "mg_walks_time_functions_smoothed_host: bad arguments");
+    MG_WALKS_REQUIRE(n_walks == 0 || (latents && times && lengths), "mg_walks_time_functions_smoothed_host: NULL pointer");
+    mg_workspace ws(prims[0]->ctx, "mg_walks_time_functions_smoothed_host");
+    const mg_staged d_lat = ws.in(latents, (size_t)(n_walks * s_max * ld) * (dtype == MG_F64 ? 8 : 4));
+    const mg_staged d_times = ws.inout(times, (size_t)(n_walks * s_max * t_cap) * 8);   // rows that are not written stay the caller's
+    const mg_staged d_lens = ws.out(lengths, (size_t)(n_walks * s_max) * 4);
+    int rc = ws.upload();
+    if (rc != MG_OK) return rc;
+    rc = mg_walks_time_functions_smoothed(n_nodes, prims, node_of, n_steps, smooth_of_node, d_lat.dev<void>(), dtype, n_walks, s_max, ld, speed,
+                                          d_times.dev<double>(), d_lens.dev<int32_t>(), t_cap);
     if (rc != MG_OK) return rc;
     return ws.download();
 }

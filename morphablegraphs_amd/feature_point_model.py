@@ -18,8 +18,8 @@ Scoring targets: score_targets, score_trajectory_targets and check_reachability_
 mg_mixture_scores (csrc/mg_mixture_scores.hip) against the model's mixture, uploaded once; HipReachabilityIndex scores a set of
 targets against the mixtures of ALL nodes of a graph in ONE launch.  mixture_scores_host is the NumPy statement of that kernel.
 
-Not restated: plot_orientation; smoothed time functions (smooth_time_parameters=True: the Savitzky-Golay pass needs the whole
-row) and speeds other than 1 in the time-warped features; the reference's mixture.GMM class (loading gives FeatureMixture, the
+Not restated: plot_orientation; smoothed time functions without the primitive's opt-in smooth_on_device (with it: one
+mg_feature_points_warped_smoothed call) and speeds other than 1 in the time-warped features; the reference's mixture.GMM class (loading gives FeatureMixture, the
 same JSON).
 """
 import json
@@ -30,6 +30,7 @@ import numpy as np
 from . import _capi
 from . import graph_walk as gw
 from .gaussian_mixture import sample_like_sklearn
+from .time_smoothing import require_smoothing_window
 from .gmm_trainer import ILL_DEFINED_MESSAGE, HipGMMTrainer, _compute_precision_cholesky, _estimate_weighted_log_prob
 
 REF_DIR = (0.0, 0.0, 1.0)          # pose_orientation_quat turns this axis
@@ -146,14 +147,17 @@ def sample_time_function_host(canonical, speed=1.0):
     return np.concatenate(([0.0], inner, [F - 1.0]))
 
 
-def feature_points_warped_host(model, S, skeleton=None, joints=(), frame_idx=0, time_mid=None):
+def feature_points_warped_host(model, S, skeleton=None, joints=(), frame_idx=0, time_mid=None, smooth=False):
     """The NumPy statement of mg_feature_points_warped for one item.  model: the reference's JSON dict or a primitive, with a
     time model; S (n, >= L + Lt): a candidate reads L spatial latents and, right behind them, Lt time latents; frame_idx counts
     the frames of the WARPED motion.  The frames are those of the times 0, time_mid and F - 1; with time_mid (n,) given, the mid
     frame is evaluated at those times instead of the statement's own (a NaN there: the candidate's motion is shorter).  Returns
     what feature_points_host returns and time_mid (n,), n_frames (n,) int32.  n_frames = 0 (no time function): NaN in every
     output of the row; a spatial latent that is not finite: NaN in the feature outputs; frame_idx >= n_frames: NaN in points
-    and time_mid only."""
+    and time_mid only.  smooth: the time function passes through time_smoothing.smooth_time_row_host first, which moves all three
+    times -- the first one becomes row 0 of the hat matrix on the first 15 samples (it can be negative), the last one row 14 on the
+    last 15 and is no longer F - 1; a candidate of fewer than 15 frames is NaN in every output but n_frames."""
+    from .time_smoothing import WINDOW, smooth_time_row_host
     hm = model if isinstance(model, gw._HostModel) else gw._HostModel(model)
     tm = _time_model_host(model)
     S = np.atleast_2d(np.asarray(S, dtype=np.float64))
@@ -170,6 +174,10 @@ def feature_points_warped_host(model, S, skeleton=None, joints=(), frame_idx=0, 
         if times is None:
             continue
         out["n_frames"][b] = len(times)
+        if smooth:
+            if len(times) < WINDOW:
+                continue
+            times = smooth_time_row_host(times)
         short = frame_idx >= len(times)
         if not short:
             out["time_mid"][b] = times[frame_idx]
@@ -177,7 +185,8 @@ def feature_points_warped_host(model, S, skeleton=None, joints=(), frame_idx=0, 
         short = short or (time_mid is not None and np.isnan(mid))
         if not np.isfinite(S[b, :L]).all():
             continue
-        _, fr = hm.frames(S[b, :L], np.array([0.0, 0.0 if short else mid, F - 1.0]))
+        first, last = (times[0], times[-1]) if smooth else (0.0, F - 1.0)
+        _, fr = hm.frames(S[b, :L], np.array([first, first if short else mid, last]))
         _state_row(out, b, fr, skeleton, () if short else joints)
     return out
 
@@ -364,7 +373,9 @@ class HipFeaturePointModel(object):
     whose warped motion has no frame frame_idx raises IndexError, as the reference's indexing does; so does a candidate without a
     time function (n_frames 0: exp overflowed, or a time latent is not finite) in the root features and in the builder, which name
     it instead of training on NaN rows.  smooth_time_parameters=True
-    on the primitive raises NotImplementedError (the Savitzky-Golay pass needs the whole time function and stays on the host).
+    on the primitive raises NotImplementedError unless the primitive also sets smooth_on_device: then one
+    mg_feature_points_warped_smoothed call takes all three of a candidate's times from the smoothed time function (the
+    Savitzky-Golay pass inside the kernel), and a candidate of fewer than 15 frames raises ValueError, as scipy would.
     Without a time model, or with use_time_parameters=False, the keyword changes nothing.
 
     Training: the reference writes GMMTrainer(training_samples) and reads .gmm and .averageScore, which does not match
@@ -406,8 +417,9 @@ class HipFeaturePointModel(object):
         if self._warps():
             if not self.time_warped:
                 raise NotImplementedError("time-warped feature points: pass time_warped=True, or use_time_parameters=False, for a primitive with a time model")
-            if getattr(mp, "smooth_time_parameters", False):
-                raise NotImplementedError("time-warped feature points of a smoothed time function: the Savitzky-Golay pass needs the whole row")
+            if getattr(mp, "smooth_time_parameters", False) and not getattr(mp, "smooth_on_device", False):
+                raise NotImplementedError("time-warped feature points of a smoothed time function: set smooth_on_device on the primitive for the "
+                                          "Savitzky-Golay pass inside the kernel")
         if self.latents is not None:
             S = _capi._latents(self.latents)
             if len(S) != n:
@@ -423,9 +435,25 @@ class HipFeaturePointModel(object):
     def _item(self, S, joints=(), frame_idx=0):
         return {"prim": self.motion_primitive_model._prim, "S": S, "skeleton": self.skeleton, "joints": list(joints), "frame_idx": frame_idx}
 
-    def _features(self, items, wanted):
-        """One call for `items` (all of this model's kind): mg_feature_points_warped where the motion is time-warped."""
-        return _capi.feature_points_warped(items, wanted) if self._warps() else _capi.feature_points(items, wanted)
+    def _features(self, items, wanted, smooth=None):
+        """One call for `items` (all of this model's kind): mg_feature_points_warped where the motion is time-warped,
+        mg_feature_points_warped_smoothed where a time function is smoothed (smooth_on_device).  smooth: one flag per item (None:
+        this model's for all of them)."""
+        if not self._warps():
+            return _capi.feature_points(items, wanted)
+        smooth = [self._smooths()] * len(items) if smooth is None else list(smooth)
+        if any(smooth):
+            return _capi.feature_points_warped(items, wanted, smooth=smooth)
+        return _capi.feature_points_warped(items, wanted)
+
+    def _smooths(self):
+        mp = self.motion_primitive_model
+        return bool(getattr(mp, "smooth_time_parameters", False) and getattr(mp, "smooth_on_device", False))
+
+    def _require_window(self, out, name=""):
+        """ValueError, as scipy's, for the first candidate whose time function is too short to smooth (out: with "n_frames")."""
+        if self._warps() and self._smooths() and "n_frames" in out:
+            require_smoothing_window(out["n_frames"], (name and name + ": ") + "candidate %d")
 
     @staticmethod
     def _require_frame(out, frame_idx, name=""):
@@ -456,6 +484,7 @@ class HipFeaturePointModel(object):
         S = self._draw(n)
         warps = self._warps()
         out = self._features([self._item(S, joint_name_list, frame_idx)], ("points", "heading_end", "heading_len") + (("n_frames",) if warps else ()))[0]
+        self._require_window(out)
         self._require_frame(out, int(frame_idx))
         self.low_dimension_vectors += np.asarray(S, dtype=np.float64).tolist()
         self.feature_points += list(out["points"])
@@ -465,6 +494,7 @@ class HipFeaturePointModel(object):
     def create_root_pos_ori(self, n):
         S = self._draw(n)
         out = self._features([self._item(S)], self._root_outputs())[0]
+        self._require_window(out)
         self._require_frame(out, 0)
         self._take_root(out, S)
 
@@ -663,8 +693,9 @@ class HipFeaturePointModelBuilder(object):
             which = [k for k, key in enumerate(keys) if models[key]._warps() == warped]
             if which:
                 first = models[keys[which[0]]]
-                got = first._features([models[keys[k]]._item(latents[k]) for k in which], first._root_outputs())
+                got = first._features([models[keys[k]]._item(latents[k]) for k in which], first._root_outputs(), [models[keys[k]]._smooths() for k in which])
                 for k, out in zip(which, got):
+                    models[keys[k]]._require_window(out, str(keys[k]))
                     first._require_frame(out, 0, str(keys[k]))
                     outs[k] = out
         result = {}

@@ -245,13 +245,17 @@ def _sample_times(ctx, bufs, mps, d_G, G, goffs, speed):
     One mg_time_function_sample_rows per step with a time model, its rows n_steps * t_cap doubles apart so that they land in place
     (a row that needs more than t_cap samples is not written and reports how many: the table is laid out again); the lengths of all
     steps come back in one download; steps without a time model get their canonical grid at `speed`.  With smooth_time_parameters
-    the rows pass through the host."""
+    the rows pass through the host -- or, for a primitive with smooth_on_device, come smoothed from
+    mg_time_function_sample_smoothed_rows and stay where they are (ValueError naming the (walk, step) whose row has fewer than
+    15 samples, as scipy would, once the lengths are known)."""
+    from .time_smoothing import require_smoothing_window
     n, m = G.shape[0], len(mps)
     has_time = [mp.has_time_parameters and mp.get_n_time_components() > 0 for mp in mps]
     timed = [i for i, ht in enumerate(has_time) if ht]
     grids = [None if ht else _untimed_grid(mp.n_canonical_frames, speed) for mp, ht in zip(mps, has_time)]
     t_cap = max([int(4 * mp.n_canonical_frames / min(float(speed), 1.0)) + 8 if ht else len(g) for mp, ht, g in zip(mps, has_time, grids)])
-    smooth = any(ht and mp.smooth_time_parameters for mp, ht in zip(mps, has_time))
+    on_device = [ht and mp.smooth_time_parameters and getattr(mp, "smooth_on_device", False) for mp, ht in zip(mps, has_time)]
+    smooth = any(ht and mp.smooth_time_parameters and not dev for mp, ht, dev in zip(mps, has_time, on_device))
     item = G.dtype.itemsize
     while True:
         lengths = np.zeros((n, m), dtype=np.int32)
@@ -266,9 +270,9 @@ def _sample_times(ctx, bufs, mps, d_G, G, goffs, speed):
         d_l = bufs.malloc(4 * n * max(len(timed), 1))
         for j, i in enumerate(timed):
             prim = mps[i]._prim
-            _capi._check(prim.lib.mg_time_function_sample_rows(prim.handle, C.c_void_p(d_G.address + int(goffs[i]) * item), _capi._dtype_code(G), n, G.shape[1],
-                                                               float(speed), C.c_void_p(d_t.address + 8 * i * t_cap), C.c_void_p(d_l.address + 4 * j * n), t_cap,
-                                                               m * t_cap, None))
+            sample_rows = prim.lib.mg_time_function_sample_smoothed_rows if on_device[i] else prim.lib.mg_time_function_sample_rows
+            _capi._check(sample_rows(prim.handle, C.c_void_p(d_G.address + int(goffs[i]) * item), _capi._dtype_code(G), n, G.shape[1], float(speed),
+                                     C.c_void_p(d_t.address + 8 * i * t_cap), C.c_void_p(d_l.address + 4 * j * n), t_cap, m * t_cap, None))
         if timed:
             ln = ctx.download(d_l, (len(timed), n), np.int32)
             if (ln == 0).any():
@@ -277,10 +281,12 @@ def _sample_times(ctx, bufs, mps, d_G, G, goffs, speed):
         if lengths.max() <= t_cap:
             break
         t_cap = int(lengths.max()) + 8
+    if any(on_device):
+        require_smoothing_window(np.where(np.array(on_device)[None, :], lengths, 0), "walk %d, step %d")
     if smooth:
         times = ctx.download(d_t, (n, m, t_cap), np.float64)
         for i, (mp, ht) in enumerate(zip(mps, has_time)):
-            if ht and mp.smooth_time_parameters:
+            if ht and mp.smooth_time_parameters and not on_device[i]:
                 for w in range(n):
                     times[w, i, :lengths[w, i]] = mp._smooth_time_function(times[w, i, :lengths[w, i]])
         d_t = bufs.upload(times)

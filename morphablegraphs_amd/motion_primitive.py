@@ -14,6 +14,7 @@ import numpy as np
 from . import _capi
 from .gaussian_mixture import HipGaussianMixture
 from .motion_spline import HipMotionSpline
+from .time_smoothing import require_smoothing_window
 
 _default_context = {}
 
@@ -37,6 +38,7 @@ class HipMotionPrimitive(object):
         self.n_canonical_frames = 0
         self.translation_maxima = np.array([1.0, 1.0, 1.0])
         self.smooth_time_parameters = False
+        self.smooth_on_device = False      # with smooth_time_parameters: the Savitzky-Golay pass inside the time-warp kernels (time_smoothing.py)
         self.has_time_parameters = True
         self.has_semantic_parameters = False
         self.animated_joints = []
@@ -173,10 +175,20 @@ class HipMotionPrimitive(object):
         from scipy.signal import savgol_filter        # motion_primitive.py:321-331
         return np.array(savgol_filter(time_function, 15, 3))
 
+    def _smooths_on_device(self):
+        """smooth_time_parameters with the opt-in smooth_on_device: the smoothed entry points, no row through the host."""
+        return bool(self.smooth_time_parameters and getattr(self, "smooth_on_device", False))
+
     def back_project_time_function(self, gamma, speed=1.0):
         """The time-warp t'(t) of a sample (motion_primitive.py:268-287), canonical time function and its inversion on the
         device (mg_time_function_sample; the host route with scipy, _invert_canonical_to_sample_time_function, stays for
-        callers that hold a canonical time function of their own)."""
+        callers that hold a canonical time function of their own).  With smooth_time_parameters the row passes through
+        scipy's savgol_filter on the host -- or, with smooth_on_device, comes smoothed from mg_time_function_sample_smoothed
+        (ValueError, as scipy's, for a row of fewer than 15 samples)."""
+        if self._smooths_on_device():
+            times, lens = self._prim.time_function_sample(np.asarray(gamma, dtype=np.float64).reshape(1, -1), speed, smoothed=True)
+            require_smoothing_window(lens, "candidate %d")
+            return times[0, :lens[0]].copy()
         times, lens = self._prim.time_function_sample(np.asarray(gamma, dtype=np.float64).reshape(1, -1), speed)
         sample_time_function = times[0, :lens[0]].copy()
         if self.smooth_time_parameters:
@@ -187,11 +199,15 @@ class HipMotionPrimitive(object):
         """back_project(s, use_time_parameters=True).get_motion_vector() for every row of `samples` (n, n_spatial + n_time
         latents) in two launches -- what GraphWalk.convert_graph_walk_to_quaternion_frames does step by step
         (graph_walk.py:154-176).  Returns (frames (n, t_max, D) padded with NaN, lengths (n), times (n, t_max) padded with NaN).
-        With smooth_time_parameters the time functions pass through the host (savgol_filter, as in the reference)."""
+        With smooth_time_parameters the time functions pass through the host (savgol_filter, as in the reference); with
+        smooth_on_device as well they come smoothed from the sampling launch and stay on the device for the frames launch:
+        only the lengths cross the bus in between (ValueError for a row of fewer than 15 samples, before the frames launch)."""
         S = np.ascontiguousarray(np.asarray(samples, dtype=np.float64))
         n_s = self.s_pca["n_components"]
         if not self.has_time_parameters:
             raise ValueError("the primitive has no time parameters")
+        if self._smooths_on_device():
+            return self._prim.back_project_warped_smoothed(S, n_s, speed, dtype=dtype)
         times, lens = self._prim.time_function_sample(S[:, n_s:], speed)
         t_max = int(lens.max()) if len(lens) else 0
         times = np.ascontiguousarray(times[:, :t_max])

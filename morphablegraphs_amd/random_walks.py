@@ -16,7 +16,8 @@ an end transition, and every step's parameters are one draw from its node's mixt
   walk_time_rows_host      the NumPy statement of the time rows.
 
 Out of scope: parameters predicted by transition models (the predictor class is not in the reference tree) and smoothed time
-functions (smooth_time_parameters: the Savitzky-Golay pass needs the row on the host; NotImplementedError).
+functions (smooth_time_parameters) of a primitive that does not opt in with smooth_on_device (NotImplementedError; with it the
+Savitzky-Golay pass runs inside mg_walks_time_functions_smoothed).
 """
 import ctypes as C
 import random
@@ -165,6 +166,30 @@ def walks_time_functions_dev(prims, node_of, n_steps, d_latents, dtype, ld, spee
                                                       _capi._dev_ptr(d_lengths), int(t_cap)))
 
 
+def walks_time_functions_smoothed_dev(prims, node_of, n_steps, smooth_of_node, d_latents, dtype, ld, speed, d_times, d_lengths, t_cap):
+    """mg_walks_time_functions_smoothed on device buffers: walks_time_functions_dev with smooth_of_node, one flag per node (host)."""
+    node_of, n_steps = np.ascontiguousarray(node_of, dtype=np.int32), np.ascontiguousarray(n_steps, dtype=np.int32)
+    smooth = np.ascontiguousarray(np.asarray(smooth_of_node).astype(bool), dtype=np.uint8)
+    assert len(smooth) == len(prims)
+    code = _capi.MG_F64 if np.dtype(dtype) == np.float64 else _capi.MG_F32
+    _capi._check(prims[0].lib.mg_walks_time_functions_smoothed(len(prims), _handles(prims), _capi._host_ptr(node_of), _capi._host_ptr(n_steps), _capi._host_ptr(smooth),
+                                                               _capi._dev_ptr(d_latents), code, node_of.shape[0], node_of.shape[1], int(ld), float(speed),
+                                                               _capi._dev_ptr(d_times), _capi._dev_ptr(d_lengths), int(t_cap)))
+
+
+def walks_time_functions_smoothed_host(prims, node_of, n_steps, smooth_of_node, latents, speed, times, lengths):
+    """mg_walks_time_functions_smoothed_host: walks_time_functions_host with smooth_of_node, one flag per node."""
+    node_of, n_steps = np.ascontiguousarray(node_of, dtype=np.int32), np.ascontiguousarray(n_steps, dtype=np.int32)
+    smooth = np.ascontiguousarray(np.asarray(smooth_of_node).astype(bool), dtype=np.uint8)
+    assert len(smooth) == len(prims)
+    latents = _capi._latents(latents.reshape(-1, latents.shape[-1])).reshape(latents.shape)
+    assert times.dtype == np.float64 and times.flags.c_contiguous and lengths.dtype == np.int32 and lengths.flags.c_contiguous
+    _capi._check(prims[0].lib.mg_walks_time_functions_smoothed_host(len(prims), _handles(prims), _capi._host_ptr(node_of), _capi._host_ptr(n_steps),
+                                                                    _capi._host_ptr(smooth), _capi._host_ptr(latents), _capi._dtype_code(latents), node_of.shape[0],
+                                                                    node_of.shape[1], latents.shape[-1], float(speed), _capi._host_ptr(times),
+                                                                    _capi._host_ptr(lengths), times.shape[2]))
+
+
 def walks_time_functions_host(prims, node_of, n_steps, latents, speed, times, lengths):
     """mg_walks_time_functions_host: latents (n_walks, s_max, ld) float32 / float64; times (n_walks, s_max, t_cap) float64 and
     lengths (n_walks, s_max) int32 written in place (rows that are not written keep their values)."""
@@ -212,13 +237,16 @@ def _time_model_of(model):
     return _time_model_host(mp) if mp.has_time_parameters and mp.get_n_time_components() > 0 else None
 
 
-def walk_time_rows_host(models, node_of, n_steps, parameters, speed=1.0):
+def walk_time_rows_host(models, node_of, n_steps, parameters, speed=1.0, smooth=None):
     """The NumPy statement of mg_walks_time_functions: times[w][i], the time row of step i of walk w.  models: one per node (JSON
     dicts or primitives); parameters (n_walks, s_max, ld).  A node with a time model reads gamma from columns n_components ..
     n_components + n_time_components of the step's row: feature_point_model's canonical_time_function_host and its inverse,
     sample_time_function_host, at `speed` (ValueError where the time function is not finite).  A node without one:
-    graph_walk._untimed_grid, linspace(0, F, int(F * (1 / speed)))."""
+    graph_walk._untimed_grid, linspace(0, F, int(F * (1 / speed))).  smooth: None, or one flag per node -- the rows of a flagged node
+    with a time model pass through time_smoothing.smooth_time_row_host, the statement of mg_walks_time_functions_smoothed
+    (ValueError for a row of fewer than 15 samples)."""
     from .feature_point_model import canonical_time_function_host, sample_time_function_host
+    from .time_smoothing import smooth_time_row_host
     from .graph_walk import _HostModel, _untimed_grid
     hosts = [m if isinstance(m, _HostModel) else _HostModel(m) for m in models]
     time_models = [_time_model_of(m) for m in models]
@@ -235,7 +263,7 @@ def walk_time_rows_host(models, node_of, n_steps, parameters, speed=1.0):
             row = sample_time_function_host(canonical_time_function_host(tm, hm.n_canonical_frames, gamma), speed)
             if row is None:
                 raise ValueError("a time function is not finite")
-            rows.append(row)
+            rows.append(smooth_time_row_host(row) if smooth is not None and smooth[k] else row)
         times.append(rows)
     return times
 
@@ -305,21 +333,32 @@ class RandomWalks(object):
         """Every step's time row from ONE mg_walks_time_functions launch and one download of the lengths: (d_times, a device
         buffer of (n_walks, s_max, t_cap) float64, the caller's to free, lengths int32 (n_walks, s_max), 0 for the steps a walk
         does not have, t_cap).  t_cap starts by graph_walk._sample_times' rule; a row that needs more reports how
-        many and the table is laid out again.  ValueError for a time function that is not finite."""
+        many and the table is laid out again.  ValueError for a time function that is not finite.  smooth_time_parameters on a
+        node's primitive is refused -- unless the primitive opts in with smooth_on_device: then ONE
+        mg_walks_time_functions_smoothed launch smooths those nodes' rows on their way out, and a row of fewer than 15 samples
+        raises ValueError naming its (walk, step), as scipy would, before any frames launch."""
+        from .time_smoothing import require_smoothing_window
         has_time = [mp.has_time_parameters and mp.get_n_time_components() > 0 for mp in self._mps]
-        if any(ht and mp.smooth_time_parameters for mp, ht in zip(self._mps, has_time)):
-            raise NotImplementedError("smoothed time functions (smooth_time_parameters): the Savitzky-Golay pass needs the row on the host")
+        smooths = [bool(ht and mp.smooth_time_parameters) for mp, ht in zip(self._mps, has_time)]
+        if any(sm and not getattr(mp, "smooth_on_device", False) for mp, sm in zip(self._mps, smooths)):
+            raise NotImplementedError("smoothed time functions (smooth_time_parameters): set smooth_on_device on the primitive for the Savitzky-Golay pass "
+                                      "inside the time kernel")
         t_cap = max(int(4 * mp.n_canonical_frames / min(float(speed), 1.0)) + 8 if ht else len(_untimed_grid(mp.n_canonical_frames, speed))
                     for mp, ht in zip(self._mps, has_time))
         with self.ctx.buffers() as own:
             d_l = own.malloc(4 * self.node_of.size)
             while True:
                 d_t = own.malloc(8 * self.node_of.size * t_cap)
-                walks_time_functions_dev(self._prims, self.node_of, self.n_steps, self.parameters, self.dtype, self.ld, speed, d_t, d_l, t_cap)
+                if any(smooths):
+                    walks_time_functions_smoothed_dev(self._prims, self.node_of, self.n_steps, smooths, self.parameters, self.dtype, self.ld, speed, d_t, d_l, t_cap)
+                else:
+                    walks_time_functions_dev(self._prims, self.node_of, self.n_steps, self.parameters, self.dtype, self.ld, speed, d_t, d_l, t_cap)
                 lengths = self.ctx.download(d_l, self.node_of.shape, np.int32)
                 if ((lengths == 0) & (self.node_of >= 0)).any():
                     raise ValueError("a time function is not finite")
                 if lengths.min() >= 0:
+                    if any(smooths):
+                        require_smoothing_window(np.where(np.array(smooths)[np.maximum(self.node_of, 0)] & (self.node_of >= 0), lengths, 0), "walk %d, step %d")
                     return own.release(d_t), lengths, t_cap
                 t_cap = int(-lengths.min()) + 8              # (negative: the samples the row would need)
 
